@@ -84,6 +84,38 @@ def cpu_baseline(a, b, levels, sched, mode):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+NPY_HEADER_BYTES = 128  # an .npy file's header (format 1.0) for arrays of up to 3 dimensions
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: array} as out_dir/<name>.npy within `budget` bytes in all (files included), in the given order: an array
+    is written in float64 if it fits the bytes left, else in float32, else as a fixed seeded sample of its flattened values
+    in float64, whose indices go along as <name>_sample_index.npy; once the budget is spent the rest is not written.
+    Returns {name: how it was written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    left, how = budget, {}
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        room = left - NPY_HEADER_BYTES
+        if arr.nbytes <= room:
+            data, how[name] = arr, "float64"
+        elif arr.nbytes // 2 <= room:
+            data, how[name] = arr.astype(np.float32), "float32"
+        else:
+            n = min(arr.size, (room - NPY_HEADER_BYTES) // 16)  # a float64 value and an int64 index per sampled element
+            if n <= 0:
+                how[name] = "not written (budget spent)"
+                continue
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, n, replace=False)).astype(np.int64)
+            data, how[name] = arr.ravel()[idx], "float64 sample of %d of %d values" % (n, arr.size)
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx)
+            left -= NPY_HEADER_BYTES + idx.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), data)
+        left -= NPY_HEADER_BYTES + data.nbytes
+    return how
+
+
 class stdout_to_stderr:
     """RCCL prints a version banner to STDOUT when a communicator is created; this program's stdout carries exactly one
     JSON line, so file descriptor 1 is pointed at stderr while communicators are being set up."""
@@ -250,8 +282,15 @@ def main():
     ap.add_argument("--simulate-step-ms", type=float, default=0.0,
                     help="CPU-only rehearsal of the N>1 protocol (tests): a step sleeps (rank+1) x this long instead "
                          "of running the GPU path; the printed value is meaningless")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (vx, vy, warpI2 of rank 0's "
+                         "first pair) as DIR/<name>.npy, at most 64 MiB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     simulate = args.simulate_step_ms > 0
+    if simulate and args.dump_outputs:
+        ap.error("--dump-outputs: a protocol rehearsal computes nothing")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -358,6 +397,13 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if use_cuda else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)  # the slowest rank defines the job's time
         elapsed = float(tt.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before anything else reuses the headline's device buffers
+        vx, vy, wi = np.zeros((h, w)), np.zeros((h, w)), np.zeros((h, w, c))
+        gpu.dev_download(vx, dvx)
+        gpu.dev_download(vy, dvy)
+        gpu.dev_download(wi, dwp)
+        dumped = dump_outputs(args.dump_outputs, {"vx": vx, "vy": vy, "warpI2": wi})
 
     tiles = None
     if use_cuda and not args.no_tiles and (world > 1 or args.force_tiles):
@@ -484,6 +530,8 @@ def main():
         }
         if tiles is not None:
             out["tiles"] = tiles
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if world == 1 and args.pairs == 1 and not simulate and args.concurrent:
             # secondary figure (not `value`): the same solve for 4 independent pairs in flight on one GPU -- what a
             # collection of frame pairs (the reference's TestSuite walks 101 per set) gets out of the device

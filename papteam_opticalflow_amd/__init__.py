@@ -126,7 +126,9 @@ def collection_in_flight(height, width):
     flat from 4 to 16, 1920x1080 peaks at 4).  What caps that at ~2 ms per 240x135 pair is NOT the host's launch path -- a call
     spends 1.0 of its 24 ms enqueueing, with 16 threads as with one -- but the device's dispatch of ~84 k small dependent kernels
     per second over 16 queues, each stretched to 50-65 us (tools/collection_trace.py, tools/trace_concurrency.py;
-    profiles/r04_collection_trace_240.txt, r04_collection_concurrency_240x16.txt): hence the batched path, collection_batch()."""
+    profiles/r04_collection_trace_240.txt, r04_collection_concurrency_240x16.txt): hence the batched path, collection_batch().
+    These figures were measured with the limit on hardware queues per process raised to 16, which the binding no longer
+    does; they have not been re-measured under the runtime's default limit."""
     mpix = height * width / 1e6
     return 16 if mpix <= 0.3 else (8 if mpix <= 1.0 else 4)
 

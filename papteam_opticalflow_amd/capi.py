@@ -63,10 +63,8 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise OSError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                       "or `make -C papteam_opticalflow_amd/csrc` (needs hipcc)" % LIB_PATH)
-    # Several calls in flight (flow_collection, one handle + two streams each) need more than the HIP runtime's default
-    # of 4 hardware queues, or streams share queues and serialise: 24 pairs of 1080p, 4 in flight, 153 -> 210 Mpix/s.
-    # Only effective if the runtime has not been initialised yet in this process; an explicit setting wins.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+    # The number of hardware queues is the host's setting (the HIP runtime's default or the caller's environment): several
+    # calls in flight (flow_collection, one handle + two streams each) share queues beyond it, and their kernels serialise.
     L = ctypes.CDLL(os.environ.get("PAPOF_LIB") or LIB_PATH)  # PAPOF_LIB: another build of the same ABI (A/B measurements)
     L.papof_strerror.restype = ctypes.c_char_p
     L.papof_strerror.argtypes = [c_int]

@@ -15,8 +15,16 @@ import numpy as np
 import pytest
 
 import cases
+from conftest import require_hw_queues
 
 pytestmark = pytest.mark.gpu
+# a handle that cuts levels into strips runs 5 streams (main, preparation, 3 strip streams) whose solver kernels wait for each
+# other; with the module's default handle (2 streams) and the runtime's null stream: 8
+STRIP_QUEUES = 8
+
+
+def _require_strip_queues():
+    require_hw_queues(STRIP_QUEUES, "the strips of one solve on several streams")
 
 
 @pytest.fixture(scope="module")
@@ -33,6 +41,7 @@ def _run(g, a, b, levels, sched):
 
 @pytest.mark.parametrize("strips", ["2", "3", "4"])
 def test_strips_give_the_bits_of_the_default_order(gpu, strips, monkeypatch):
+    _require_strip_queues()
     from papteam_opticalflow_amd import Papof
     monkeypatch.setenv("PAPOF_STRIPS", strips)
     g = Papof(0)
@@ -57,6 +66,7 @@ def test_strips_give_the_bits_of_the_default_order(gpu, strips, monkeypatch):
 
 def test_strips_sequence_and_graph_replay(monkeypatch):
     """strips inside a captured hipGraph (forked streams joined again) and in sequence mode"""
+    _require_strip_queues()
     from papteam_opticalflow_amd import Papof
     monkeypatch.setenv("PAPOF_STRIPS", "2")
     frames = [cases.load_frame_u8("960", i) for i in (1, 2, 1)]  # the 960 fixture holds two frames
@@ -87,12 +97,14 @@ def test_one_solve_in_two_launches_equals_the_whole_solve(gpu, h, w, n_sor, spli
     """the solver alone: bands < split on one stream, the others `delay` microseconds later on another -- every cell of
     the (du, dv) planes, intermediate sweeps included, as the one-launch solve leaves it (plain and two-sweeps-per-wave
     kernel, even and ODD sweep counts: the odd ones used to go wrong here, see sor.hip f_step)"""
+    _require_strip_queues()
     mm, nb = gpu.test_sor_strips(h, w, n_sor, split, reps=6, delay_us=delay)
     print("%dx%d sweeps %d: %d bands cut at %d, %d mismatching cells" % (w, h, n_sor, nb, split, mm))
     assert mm == 0
 
 
 def test_strips_raised_abort_word_reports_timeout(monkeypatch):
+    _require_strip_queues()
     from papteam_opticalflow_amd import Papof
     from papteam_opticalflow_amd.capi import PapofError
     monkeypatch.setenv("PAPOF_STRIPS", "2")

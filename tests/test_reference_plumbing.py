@@ -1,62 +1,55 @@
-"""BASELINE.json configs[0] (plumbing): the reference's own, UNMODIFIED OpticalFlowCalculation.py / InputCreation
-package driven against this repository's drop-in `pyflow` module.
+"""BASELINE.json configs[0] (plumbing): the reference's caller (Code/Serial/OpticalFlowCalculation.py) reaches this
+repository's drop-in `pyflow` module by module name alone, with frames it decodes itself.
 
-Only possible in the build container (the reference tree does not travel to the GPU box, and this container has no
-GPU), so the run is expected to reach our module through the reference's unchanged call
-`pyflow.coarse2fine_flow(im1, im2, pyramidLevels)` (OpticalFlowCalculation.py:73) and fail THERE with the loud
-no-device error -- which proves the binding: same module name, same positional signature, float64 HWC arrays from PIL.
-The positive half of the contract (4-tuple, str-valued timing dict, `u[..., None]` concatenation, tab-joined timing
-line) is exercised on the GPU by tests/test_gpu_parity.py::test_pyflow_dropin_entry_point.
-
-`cv2` is not installed here; the reference imports it at module level (OpticalFlowCalculation.py:13) but only uses
-it in a function the Serial tree disables (:137), so an empty stub module is put on PYTHONPATH.
+The caller's side is restated here on the committed frames (tests/golden/frames), in a fresh process whose PYTHONPATH
+holds only the drop-in's directory: PIL -> np.array -> astype(float) / 255., then the positional call
+`pyflow.coarse2fine_flow(im1, im2, pyramidLevels)` (OpticalFlowCalculation.py:65-73) and what the caller does with the
+result (`u[..., None]` concatenation, the 'Total C++ Execution' timer).  Without a device the call must fail THERE with
+the loud no-device error -- which proves the binding: same module name, same positional signature, float64 HWC arrays
+from PIL.  The full contract of the result is checked on the GPU by
+tests/test_gpu_parity.py::test_pyflow_dropin_entry_point.
 """
+import ctypes
 import os
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+FRAMES = os.path.join(ROOT, "tests", "golden", "frames", "240")
 
 DRIVER = r'''
 import os, sys
-from OpticalFlowCalculation import *          # the reference's caller, unmodified
-gen = TestImagePairGenerator()                # needs cwd under .../Code and images_New beside it
-pairs = gen.generateTestImagePairsFromCollectionName("HoChiMinhTraffic_10FPS_240")
-print("PAIRS", len(pairs), pairs[0].asStorageString(" -> ", long=False))
+import numpy as np
+from PIL import Image
+import pyflow
+frames = sys.argv[1]
+im1 = np.array(Image.open(os.path.join(frames, "frame_00001.jpg")))
+im2 = np.array(Image.open(os.path.join(frames, "frame_00002.jpg")))
+im1 = im1.astype(float) / 255.
+im2 = im2.astype(float) / 255.
+print("MODULE", os.path.basename(os.path.dirname(os.path.abspath(pyflow.__file__))))
 try:
-    CalculateOpticalFlow(pairs[0], 2, "_plumbing")
-    print("RESULT ok", os.path.exists("output/UniversalTiming.txt"))
+    timingDictionary, u, v, im2W = pyflow.coarse2fine_flow(im1, im2, 2)
+    flow = np.concatenate((u[..., None], v[..., None]), axis=2)
+    print("RESULT ok", flow.shape, im2W.shape, float(timingDictionary["Total C++ Execution"]) > 0)
 except RuntimeError as e:
     print("RESULT RuntimeError", e)
 '''
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "Code", "Serial")), reason="reference tree not present")
-def test_unmodified_reference_caller_reaches_our_pyflow(tmp_path):
+def test_reference_style_caller_reaches_our_pyflow(tmp_path):
     import __graft_entry__
-    if not os.path.exists(os.path.join(ROOT, "papteam_opticalflow_amd", "csrc", "libpapof.so")):
+    lib = os.path.join(ROOT, "papteam_opticalflow_amd", "csrc", "libpapof.so")
+    if not os.path.exists(lib):
         __graft_entry__.build()
-    serial = tmp_path / "proj" / "Code" / "Serial"
-    serial.mkdir(parents=True)
-    (serial / "output").mkdir()
-    os.symlink(os.path.join(REF, "Code", "Serial", "OpticalFlowCalculation.py"), serial / "OpticalFlowCalculation.py")
-    os.symlink(os.path.join(REF, "Code", "Serial", "InputCreation"), serial / "InputCreation")
-    os.symlink(os.path.join(REF, "images_New"), tmp_path / "proj" / "images_New")
-    stubs = tmp_path / "stubs"
-    stubs.mkdir()
-    (stubs / "cv2.py").write_text("# empty stand-in: only used by a code path the Serial tree disables\n")
-    env = dict(os.environ, MPLBACKEND="Agg", PYTHONDONTWRITEBYTECODE="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "papteam_opticalflow_amd", "dropin"), str(stubs)]))
-    out = subprocess.run([sys.executable, "-c", DRIVER], cwd=str(serial), env=env, capture_output=True, text=True,
-                         timeout=300)
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1",
+               PYTHONPATH=os.path.join(ROOT, "papteam_opticalflow_amd", "dropin"))
+    out = subprocess.run([sys.executable, "-c", DRIVER, FRAMES], cwd=str(tmp_path), env=env, capture_output=True,
+                         text=True, timeout=300)
     text = out.stdout + out.stderr
-    assert "PAIRS 101" in text, text[-3000:]
-    import ctypes
-    have_gpu = ctypes.CDLL(os.path.join(ROOT, "papteam_opticalflow_amd", "csrc", "libpapof.so")).papof_device_count() > 0
+    assert "MODULE dropin" in text, text[-3000:]
+    have_gpu = ctypes.CDLL(lib).papof_device_count() > 0
     if have_gpu:
-        assert "RESULT ok True" in text, text[-3000:]
+        assert "RESULT ok (135, 240, 2) (135, 240, 3) True" in text, text[-3000:]
     else:
         assert "RESULT RuntimeError" in text and "no usable gfx950 device" in text, text[-3000:]

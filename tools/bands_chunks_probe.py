@@ -3,12 +3,12 @@
 transport bound to the stand-in of tests/fake_rccl: ms per 1920x1080 config-4 pair and the solver kernels' share of rank 0 for
 1 / 2 / 3 / 5 / 10 ranges of sweeps per solve (PAPOF_BANDS_CHUNKS).  A rehearsal, not a multi-GPU measurement: the ranks share one
 chip (the latency-bound solver kernels leave most of it idle, the other stages do not), but it shows whether ranges of sweeps let
-the ranks overlap at all.  usage: bands_chunks_probe.py [nranks=8] [res=1920]"""
+the ranks overlap at all.  The ranks' kernels wait for each other on the device: every stream of every rank needs a hardware
+queue of its own (2 x nranks + 1), or the run ends in the stand-in's timeouts.  usage: bands_chunks_probe.py [nranks=8] [res=1920]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 os.environ["PAPOF_RCCL_LIB"] = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
 import numpy as np
 import cases
