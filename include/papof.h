@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 105 /* 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 106 /* 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -376,6 +376,35 @@ int papof_flow_batch(papof_handle* h, int n_pairs, int sequence, const double* c
 int papof_flow_batch_u8(papof_handle* h, int n_pairs, int sequence, const unsigned char* const* frames, int height,
                         int width, int c, int pyramid_levels, const papof_params* params, double* const* vx,
                         double* const* vy, double* const* warpI2, double timing_sec[PAPOF_N_TIMERS]);
+
+/* Strided 4-D device tensors (PyTorch's, or anyone's): element type and the distance, in ELEMENTS, between neighbours along
+ * the logical axes (frame or pair, row, column, channel or component).  NCHW and NHWC are different strides of the same
+ * description; a zero stride repeats an element (an expanded tensor). */
+enum { PAPOF_DTYPE_U8 = 0, PAPOF_DTYPE_F32 = 1, PAPOF_DTYPE_F64 = 2 };
+typedef struct papof_tensor {
+    void* data;          /* device memory on the handle's device */
+    int dtype;           /* PAPOF_DTYPE_* */
+    long long stride[4]; /* elements between neighbours along (frame|pair, row, column, channel|component) */
+} papof_tensor;
+
+/* papof_flow_batch on frames that are already in device memory, as strided tensors of uint8 (scaled by 1/255 as
+ * papof_flow_u8 does), float32 (widened exactly) or float64 samples, with results written into strided float32 (one
+ * round-to-nearest conversion) or float64 tensors.  sequence != 0: `frames` holds n_pairs + 1 frames, pair i = (i, i + 1),
+ * frames2 must be NULL; sequence == 0: pair i = (frames[i], frames2[i]), n_pairs frames each.  flow: (pair, row, column,
+ * {vx, vy}); warpI2: (pair, row, column, channel).  Every pair's results are bit-identical to papof_flow on the fp64 values
+ * of its frames.  The batched chain covers what papof_flow_batch's covers; anything else, a batch of one, and a pair whose
+ * Laplacian-noise guard cannot be proven open run pair by pair on the device (no frame crosses PCIe on any path).
+ * Stream contract: `stream` is the caller's hipStream_t (NULL: the null stream) on the handle's device.  The call records
+ * an event there on entry and the handle's streams wait for it, so inputs produced on that stream are read after they are
+ * written; the call returns once every output is written (the guard's proof needs the host).  It is stream-ordered on
+ * entry and complete on return, not asynchronous.  PAPOF_EINVAL, before anything is enqueued: a NULL descriptor or data
+ * pointer, an unknown dtype, a uint8 output, a negative stride, a zero stride on an output, frames2 given in sequence mode
+ * or missing in pair mode.  timing_sec as papof_flow_batch: Total = the caller's wall time, Phase5_SOR = the solver
+ * kernels' own time.  Any sequence kept by papof_seq_push* on the handle ends. */
+int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                            const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                            const papof_params* params, const papof_tensor* flow, const papof_tensor* warpI2, void* stream,
+                            double timing_sec[PAPOF_N_TIMERS]);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

@@ -27,6 +27,15 @@ class Params(ctypes.Structure):
                 ("sor_mode", c_int), ("phase_timing", c_int), ("interpolation", c_int), ("noise_model", c_int)]
 
 
+DTYPE_U8, DTYPE_F32, DTYPE_F64 = 0, 1, 2
+
+
+class PapofTensor(ctypes.Structure):
+    """struct papof_tensor (include/papof.h): device data, PAPOF_DTYPE_*, strides in elements along (frame | pair, row,
+    column, channel | component)."""
+    _fields_ = [("data", c_void_p), ("dtype", c_int), ("stride", ctypes.c_longlong * 4)]
+
+
 class PapofError(RuntimeError):
     def __init__(self, code, what, detail):
         super().__init__("%s failed: %s (%d)%s" % (what, detail[0], code, (": " + detail[1]) if detail[1] else ""))
@@ -51,7 +60,7 @@ SYMBOLS = [
     "papof_pyramid_levels_for_min_width", "papof_stage_smoothflow_ex", "papof_stage_est_gaussian_mixture",
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
-    "papof_flow_batch", "papof_flow_batch_u8",
+    "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor",
 ]
 
 
@@ -146,6 +155,9 @@ def load():
     for fn in (L.papof_flow_batch, L.papof_flow_batch_u8):
         fn.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _D]
         fn.restype = c_int
+    _T = ctypes.POINTER(PapofTensor)
+    L.papof_flow_batch_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, c_void_p, _D]
+    L.papof_flow_batch_tensor.restype = c_int
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
     L.papof_strip_plan.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),

@@ -631,11 +631,17 @@ void ensure_strip_streams(papof_handle* h) {  // without them levels are simply 
 
 // An interleaved HWC frame resident on the device: fp64 in [0,1] (the reference's buffers) or the decoded uint8
 // samples, which are scaled by 1/255 while they are planarised (OpticalFlowCalculation.py:69-70).
+// planar: already in the planar fp64 layout on the device (papof_flow_batch_tensor's frames, k_ingest_frames): copied as is.
 struct FrameIn {
     const void* d;
     bool u8;
+    bool planar = false;
 };
 int load_frame(papof_handle* h, const FrameIn& f, double* planar, int H, int W, int C) {
+    if (f.planar) {
+        PAPOF_HIP(hipMemcpyAsync(planar, f.d, (size_t)H * W * C * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return PAPOF_OK;
+    }
     if (f.u8) return hwc_u8_to_planar(h, static_cast<const unsigned char*>(f.d), planar, H, W, C);
     return hwc_to_planar(h, static_cast<const double*>(f.d), planar, H, W, C);
 }
@@ -695,7 +701,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         key.levels = levels;
         key.op = (int)op;
         key.slot1 = slot1;
-        key.u8 = fb.u8 ? 1 : 0;
+        key.u8 = fb.planar ? 2 : (fb.u8 ? 1 : 0);
         key.P = P;
         key.fa = op == kSeqNext ? nullptr : fa.d;
         key.fb = fb.d;
@@ -1282,6 +1288,14 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
     return PAPOF_OK;
 }
 
+// papof_flow_batch_tensor's pairs that run on their own (batch.hip): planar frames already on the device, the single call
+int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,
+                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
+    FrameIn a{f1, false}, b{f2, false};
+    a.planar = b.planar = true;
+    return flow_device(h, a, b, kPair, H, W, C, levels, P, d_vx, d_vy, d_warp, timing);
+}
+
 }  // namespace papof
 
 // =================================================================================================
@@ -1459,6 +1473,8 @@ void papof_destroy(papof_handle* h) {
     if (h->arena.base) hipFree(h->arena.base);
     if (h->sync_words) hipFree(h->sync_words);
     if (h->stage_dev) hipFree(h->stage_dev);
+    if (h->tensor_scratch) hipFree(h->tensor_scratch);
+    if (h->entry_event) hipEventDestroy(h->entry_event);
     if (h->pin) hipHostFree(h->pin);
     if (h->lap_flags_host) hipHostFree(h->lap_flags_host);  // the stamps live inside these two blocks
     if (h->lap_flags_dev) hipFree(h->lap_flags_dev);

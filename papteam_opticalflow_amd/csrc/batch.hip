@@ -21,6 +21,11 @@
 // of witness flags per pair and non-zero flags per frame (few-pixel levels: an exhaustive check behind every update); a pair that
 // ends without a proof for a consulted estimate (duplicate frames) is run again through the single call, which has the exact
 // pass.  Results: the reference's, either way.
+//
+// Device tensors (papof_flow_batch_tensor): the same chain with frames read where they are -- strided uint8 / float32 / float64
+// tensors, k_ingest_frames writes the level-0 array, no staging block -- and results written by k_emit_outputs into the
+// caller's strided tensors before anything else runs on the arena.  What the chain does not cover, a batch of one and a
+// re-run pair run one pair at a time on the device, their frames converted into a scratch block of the handle.
 #include <algorithm>
 #include <chrono>
 #include <cstring>
@@ -40,6 +45,15 @@ struct BatchOut {
     std::vector<int> unproven;     // pairs whose Laplacian-noise guard could not be proven open: run them through the single call
 };
 
+// The frames of a batch: host pointers (uploaded into the arena's staging block), or strided device tensors that
+// k_ingest_frames reads where they are (papof_flow_batch_tensor; no staging block, nothing crosses PCIe).
+struct BatchFrames {
+    const void* const* host = nullptr;  // nF frames, HWC, float64 or uint8 (u8)
+    bool u8 = false;
+    const papof_tensor* a = nullptr;    // device frames: a sequence, or the first frames of the pairs ...
+    const papof_tensor* b = nullptr;    // ... and their second frames (pairs only)
+};
+
 bool batch_applies(const papof_handle* h, int B, int H, int W, int C, int levels, const papof_params& P) {
     if (B < 2 || !h->use_dpp || h->use_graph || h->strips > 1) return false;
     if (P.sor_mode != PAPOF_SOR_EXACT || P.n_inner != 1 || P.interpolation != PAPOF_INTERP_BILINEAR ||
@@ -53,8 +67,18 @@ bool batch_applies(const papof_handle* h, int B, int H, int W, int C, int levels
     return slots <= kLapMaxSlots;
 }
 
+// One launch of the solver holds the tasks of ALL pairs, and all of them must be resident (sor.hip: resident_tasks): a
+// collection larger than that -- or than a few GB of arena -- goes through in sub-batches of the same shape.
+int batch_max(int H, int W, int C, int levels, const papof_params& P) {
+    const int nb0 = skew_dims(H, W, P.n_sor + (levels - 1) * P.n_sor_per_level, 1, 1).nb;
+    const size_t per_pair = arena_bytes_for(H, W, C, levels, P.n_sor + (levels - 1) * P.n_sor_per_level, P.ratio);
+    int max_b = (int)std::max<size_t>(2, std::min<size_t>((size_t)1024 / (size_t)nb0, ((size_t)24 << 30) / per_pair));
+    if (const char* e = std::getenv("PAPOF_BATCH_MAX")) max_b = std::max(2, std::min(max_b, std::atoi(e)));  // (and the tests')
+    return max_b;
+}
+
 // Everything on h->stream, one stream: B pairs fill the chip by themselves.
-int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* frames, bool u8, int H, int W, int C, int levels,
+int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& frames, int H, int W, int C, int levels,
                       const papof_params& P, double* timing, BatchOut& out) {
     PAPOF_TRY(check_params(P, levels));
     double ratio = P.ratio;
@@ -67,6 +91,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* f
     const size_t np0 = (size_t)H * W;
     const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
     const bool guard = h->lap_guard && h->lap_flags_dev != nullptr;
+    const bool u8 = frames.u8, staged = frames.host != nullptr;
     // ---- arena: one block, arrays over frames / pairs
     size_t pyr_px = 0;
     for (const Level& l : L) pyr_px += (size_t)l.w * l.h;
@@ -74,7 +99,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* f
     skew_capacity(H, W, n_sor_max, cells, cells_d);
     const size_t tiny_cells = std::min<size_t>(kTinyMaxCells, np0);
     size_t bytes = 0;
-    bytes += (size_t)nF * np0 * C * (u8 ? 1 : 8) + 4096;                            // the uploaded frames
+    if (staged) bytes += (size_t)nF * np0 * C * (u8 ? 1 : 8) + 4096;                // the uploaded frames
     bytes += (size_t)nF * pyr_px * (C + 2 * fc) * 8 + (size_t)levels * 3 * 4096;     // pyramids, features, smoothed features
     bytes += (size_t)nF * np0 * C * 8 * 5 + 5 * 4096;                               // two filter temporaries, three derivative planes
     bytes += (size_t)B * (4 * np0 * 8 + np0 * C * 8) + 3 * 4096;                    // two flow pairs, the warped image
@@ -92,7 +117,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* f
     h->sor_launches = 0;
     hipStream_t const st = h->stream;
 
-    unsigned char* stage = static_cast<unsigned char*>(A.alloc((size_t)nF * np0 * C * (u8 ? 1 : 8)));
+    unsigned char* stage = staged ? static_cast<unsigned char*>(A.alloc((size_t)nF * np0 * C * (u8 ? 1 : 8))) : nullptr;
     std::vector<double*> Lp(levels), F(levels), S(levels);
     for (int k = 0; k < levels; k++) {
         const size_t n = (size_t)L[k].w * L[k].h;
@@ -148,14 +173,17 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* f
 
     // ---- uploads, layout conversion, pyramids, features (frames are planes x frames for the plane-parallel kernels)
     const size_t frame_bytes = np0 * C * (u8 ? 1 : 8);
-    bool flat_in = true;  // frames stacked in one host block (the Python binding's): one copy
-    for (int f = 1; f < nF && flat_in; f++)
-        flat_in = (const unsigned char*)frames[f] == (const unsigned char*)frames[0] + (size_t)f * frame_bytes;
-    if (flat_in) {
-        PAPOF_HIP(hipMemcpyAsync(stage, frames[0], (size_t)nF * frame_bytes, hipMemcpyHostToDevice, st));
-    } else {
-        for (int f = 0; f < nF; f++)
-            PAPOF_HIP(hipMemcpyAsync(stage + (size_t)f * frame_bytes, frames[f], frame_bytes, hipMemcpyHostToDevice, st));
+    if (staged) {
+        const void* const* hf = frames.host;
+        bool flat_in = true;  // frames stacked in one host block (the Python binding's): one copy
+        for (int f = 1; f < nF && flat_in; f++)
+            flat_in = (const unsigned char*)hf[f] == (const unsigned char*)hf[0] + (size_t)f * frame_bytes;
+        if (flat_in) {
+            PAPOF_HIP(hipMemcpyAsync(stage, hf[0], (size_t)nF * frame_bytes, hipMemcpyHostToDevice, st));
+        } else {
+            for (int f = 0; f < nF; f++)
+                PAPOF_HIP(hipMemcpyAsync(stage + (size_t)f * frame_bytes, hf[f], frame_bytes, hipMemcpyHostToDevice, st));
+        }
     }
     if (prog_total && !sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
     if (++h->lap_epoch >= kLapNone) {  // (2^31 passes later: start over on cleared flags, as flow_device does -- the handle's own
@@ -168,7 +196,9 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const void* const* f
         PAPOF_HIP(hipMemsetAsync(wit, 0, (size_t)B * kLapFlagWords * sizeof(unsigned), st));
         PAPOF_HIP(hipMemsetAsync(nzf, 0, (size_t)nF * kLapNzWords * sizeof(unsigned), st));
     }
-    if (u8)
+    if (!staged)
+        PAPOF_TRY(ingest_frames(h, *frames.a, sequence ? nullptr : frames.b, Lp[0], H, W, C, nF));
+    else if (u8)
         PAPOF_TRY(hwc_u8_to_planar(h, stage, Lp[0], H, W, C, nF));
     else
         PAPOF_TRY(hwc_to_planar(h, reinterpret_cast<const double*>(stage), Lp[0], H, W, C, nF));
@@ -322,13 +352,9 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
         if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
         return PAPOF_OK;
     }
-    // One launch of the solver holds the tasks of ALL pairs, and all of them must be resident (sor.hip: resident_tasks): a
-    // collection larger than that -- or than a few GB of arena -- goes through in sub-batches of the same shape.
+    // sub-batches (batch_max)
     {
-        const int nb0 = skew_dims(H, W, P.n_sor + (levels - 1) * P.n_sor_per_level, 1, 1).nb;
-        const size_t per_pair = arena_bytes_for(H, W, C, levels, P.n_sor + (levels - 1) * P.n_sor_per_level, P.ratio);
-        int max_b = (int)std::max<size_t>(2, std::min<size_t>((size_t)1024 / (size_t)nb0, ((size_t)24 << 30) / per_pair));
-        if (const char* e = std::getenv("PAPOF_BATCH_MAX")) max_b = std::max(2, std::min(max_b, std::atoi(e)));  // (and the tests')
+        const int max_b = batch_max(H, W, C, levels, P);
         if (n_pairs > max_b) {
             const int step = sequence ? 1 : 2;
             for (int p0 = 0; p0 < n_pairs;) {
@@ -346,7 +372,10 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
     }
     BatchOut out;
     {
-        const int rc = flow_batch_device(h, n_pairs, sequence, frames, u8, H, W, C, levels, P, tm, out);
+        BatchFrames bf;
+        bf.host = frames;
+        bf.u8 = u8;
+        const int rc = flow_batch_device(h, n_pairs, sequence, bf, H, W, C, levels, P, tm, out);
         if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
             std::memset(tm, 0, sizeof tm);
             for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
@@ -383,6 +412,96 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
     return PAPOF_OK;
 }
 
+namespace {
+
+papof_tensor shifted(const papof_tensor& t, long long items) {  // the same tensor from item `items` of its first axis on
+    papof_tensor r = t;
+    const long long es = t.dtype == PAPOF_DTYPE_U8 ? 1 : (t.dtype == PAPOF_DTYPE_F32 ? 4 : 8);
+    r.data = static_cast<char*>(t.data) + items * t.stride[0] * es;
+    return r;
+}
+
+bool valid_tensor(const papof_tensor* t, bool output) {
+    if (!t || !t->data) return false;
+    if (t->dtype != PAPOF_DTYPE_F32 && t->dtype != PAPOF_DTYPE_F64 && (output || t->dtype != PAPOF_DTYPE_U8)) return false;
+    for (int i = 0; i < 4; i++)
+        if (t->stride[i] < 0 || (output && t->stride[i] == 0)) return false;  // (a zero input stride: an expanded tensor)
+    return true;
+}
+
+// papof_flow_batch_tensor behind its checks and its entry wait: flow_batch_host's orchestration on device tensors.  The frames
+// are read where they are (k_ingest_frames), the results leave the arena through k_emit_outputs before anything else runs on
+// it, and what the batched chain does not cover runs pair by pair on the device.  tm accumulates the phases.
+int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor& fa, const papof_tensor* fb, int H, int W,
+                      int C, int levels, const papof_params& P, const papof_tensor& flow, const papof_tensor& warp, double* tm) {
+    const size_t np0 = (size_t)H * W, frame = np0 * C;
+    // one pair on its own: its two frames into the handle's scratch (planar fp64; not in the arena, which the single call lays
+    // out anew), the device call (both passes of the guard), the results out
+    const auto single = [&](int p) -> int {
+        const size_t bytes = (2 * frame + 2 * np0 + frame) * sizeof(double);
+        if (h->tensor_scratch_bytes < bytes) {
+            if (h->tensor_scratch) {
+                PAPOF_HIP(hipStreamSynchronize(h->stream));
+                PAPOF_HIP(hipFree(h->tensor_scratch));
+            }
+            h->tensor_scratch = nullptr;
+            h->tensor_scratch_bytes = 0;
+            if (hipMalloc((void**)&h->tensor_scratch, bytes) != hipSuccess) {
+                h->tensor_scratch = nullptr;
+                return PAPOF_ENOMEM;
+            }
+            h->tensor_scratch_bytes = bytes;
+        }
+        double *f = h->tensor_scratch, *uv = f + 2 * frame, *wp = uv + 2 * np0;
+        const papof_tensor a = shifted(fa, p);
+        if (sequence) {
+            PAPOF_TRY(ingest_frames(h, a, nullptr, f, H, W, C, 2));
+        } else {
+            const papof_tensor b = shifted(*fb, p);
+            PAPOF_TRY(ingest_frames(h, a, &b, f, H, W, C, 2));
+        }
+        double t1[PAPOF_N_TIMERS];
+        PAPOF_TRY(flow_device_planar(h, f, f + frame, H, W, C, levels, P, uv, uv + np0, wp, t1));
+        PAPOF_TRY(emit_outputs(h, uv, shifted(flow, p), true, H, W, 2, 1));
+        PAPOF_TRY(emit_outputs(h, wp, shifted(warp, p), false, H, W, C, 1));
+        for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
+        return PAPOF_OK;
+    };
+    if (!batch_applies(h, n_pairs, H, W, C, levels, P)) {
+        for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
+        return PAPOF_OK;
+    }
+    const int max_b = batch_max(H, W, C, levels, P);
+    for (int p0 = 0; p0 < n_pairs;) {
+        int nb = std::min(max_b, n_pairs - p0);
+        if (n_pairs - (p0 + nb) == 1 && nb > 2) nb -= 1;  // leave two pairs for the last sub-batch rather than one
+        const papof_tensor a = shifted(fa, p0), b = sequence ? a : shifted(*fb, p0);
+        BatchFrames bf;
+        bf.a = &a;
+        bf.b = sequence ? nullptr : &b;
+        BatchOut out;
+        double t1[PAPOF_N_TIMERS];
+        const int rc = flow_batch_device(h, nb, sequence, bf, H, W, C, levels, P, t1, out);
+        if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
+            for (int p = p0; p < p0 + nb; p++) PAPOF_TRY(single(p));
+            p0 += nb;
+            continue;
+        }
+        PAPOF_TRY(rc);
+        for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
+        PAPOF_TRY(emit_outputs(h, out.uv, shifted(flow, p0), true, H, W, 2, nb));
+        PAPOF_TRY(emit_outputs(h, out.warp, shifted(warp, p0), false, H, W, C, nb));
+        for (int p : out.unproven) {
+            h->lap_reruns++;
+            PAPOF_TRY(single(p0 + p));
+        }
+        p0 += nb;
+    }
+    return PAPOF_OK;
+}
+
+}  // namespace
+
 }  // namespace papof
 
 using namespace papof;
@@ -401,6 +520,41 @@ int papof_flow_batch_u8(papof_handle* h, int n_pairs, int sequence, const unsign
                         double* const* warpI2, double timing_sec[PAPOF_N_TIMERS]) {
     return flow_batch_host(h, n_pairs, sequence, reinterpret_cast<const void* const*>(frames), true, height, width, c,
                            pyramid_levels, params, vx, vy, warpI2, timing_sec);
+}
+
+int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2,
+                            int height, int width, int c, int pyramid_levels, const papof_params* params, const papof_tensor* flow,
+                            const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
+    if (!valid_tensor(frames, false) || !valid_tensor(flow, true) || !valid_tensor(warpI2, true)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
+    papof_params P;
+    if (params)
+        P = *params;
+    else
+        papof_default_params(&P);
+    PAPOF_TRY(check_params(P, pyramid_levels));
+    PAPOF_HIP(hipSetDevice(h->device));
+    const double t0 = now_sec();
+    // stream order on entry: the handle's streams (non-blocking, hence also for the null stream) start behind what the caller
+    // has queued so far
+    if (!h->entry_event) PAPOF_HIP(hipEventCreateWithFlags(&h->entry_event, hipEventDisableTiming));
+    PAPOF_HIP(hipEventRecord(h->entry_event, static_cast<hipStream_t>(stream)));
+    PAPOF_HIP(hipStreamWaitEvent(h->stream, h->entry_event, 0));
+    if (h->prep_stream) PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->entry_event, 0));
+    double tm[PAPOF_N_TIMERS];
+    std::memset(tm, 0, sizeof tm);
+    const int rc = flow_batch_tensor(h, n_pairs, sequence, *frames, frames2, height, width, c, pyramid_levels, P, *flow, *warpI2,
+                                     tm);
+    const hipError_t se = hipStreamSynchronize(h->stream);  // complete on return: the emits are the last work of the call
+    PAPOF_TRY(rc);
+    if (se != hipSuccess) {
+        set_last_error("hipStreamSynchronize", se, __FILE__, __LINE__);
+        return PAPOF_EDEVICE;
+    }
+    tm[PAPOF_T_TOTAL] = now_sec() - t0;  // the caller's view
+    if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
+    return PAPOF_OK;
 }
 
 }  // extern "C"

@@ -256,6 +256,11 @@ struct papof_handle {
     size_t stage_dev_bytes = 0;
     char* pin = nullptr;
     size_t pin_bytes = 0;
+    // device-tensor path (papof_flow_batch_tensor): the planar frames and results of ONE pair that runs on its own (outside
+    // the arena, which the single call lays out anew), and the event that orders the handle's streams behind the caller's
+    double* tensor_scratch = nullptr;
+    size_t tensor_scratch_bytes = 0;
+    hipEvent_t entry_event = nullptr;
     int host_copy = 1;               // PAPOF_HOST_COPY: 1 = hipMemcpyAsync straight from / to the caller's memory (the runtime's
                                      // pageable path runs at 55 GB/s here; pinned result arrays are direct DMA), 0 = our pinned
                                      // bounce pipeline of round 1 (0.4-0.6 ms slower per 1080p call, same-box A/B)
@@ -364,6 +369,12 @@ int stamp_only(papof_handle* h);  // kernels.hip
 int hwc_to_planar(papof_handle* h, const double* hwc, double* planar, int H, int W, int C, int frames = 1);
 int hwc_u8_to_planar(papof_handle* h, const unsigned char* hwc, double* planar, int H, int W, int C, int frames = 1);
 int planar_to_hwc(papof_handle* h, const double* planar, double* hwc, int H, int W, int C);
+// strided device tensors (papof_flow_batch_tensor): `frames` frames of a (and b: pairs, interleaved a, b, a, b, ...) into the
+// planar fp64 frames [frame][channel][row][col]; results -- [pair][K][H * W] (comp_major: the flow) or [pair][H * W][K]
+// (warpI2) -- into a strided float32 / float64 tensor
+int ingest_frames(papof_handle* h, const papof_tensor& a, const papof_tensor* b, double* planar, int H, int W, int C,
+                  int frames);
+int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bool comp_major, int H, int W, int K, int pairs);
 int filter_h(papof_handle* h, const double* src, double* dst, int H, int W, int planes, const Taps& f,
              const Rect* rc = nullptr);
 int filter_v(papof_handle* h, const double* src, double* dst, int H, int W, int planes, const Taps& f,

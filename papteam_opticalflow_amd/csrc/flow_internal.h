@@ -130,9 +130,14 @@ int build_pyramid(papof_handle* h, const std::vector<Level>& L, const std::vecto
 int smooth_and_resize(papof_handle* h, const double* src, double* dst, double* tmp_a, double* tmp_b, const PyrPlan& p, int C,
                       int dh, int dw);  // one pyramid level from its source level; C may count the planes of SEVERAL contiguous frames
 int feature_channels(int C);
-// batch.hip: B frame pairs of one shape in one launch chain (host frames in, host results out); falls back to single calls
+// batch.hip: B frame pairs of one shape in one launch chain (host frames in, host results out; papof_flow_batch_tensor: device
+// tensors in and out); falls back to single calls
 int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* const* frames, bool u8, int H, int W, int C, int levels,
                     const papof_params* params, double* const* vx, double* const* vy, double* const* warpI2, double* timing_sec);
 void ensure_strip_streams(papof_handle* h);
+// the device call on two planar fp64 frames already on the device (api.hip: flow_device, both passes of the guard); returns
+// with the results written
+int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,
+                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing);
 
 }  // namespace papof

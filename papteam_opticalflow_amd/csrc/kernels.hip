@@ -77,6 +77,46 @@ __global__ void k_planar_to_hwc(const double* __restrict__ planar, double* __res
     for (int k = 0; k < C; k++) hwc[o * C + k] = planar[k * np + o];
 }
 
+// Strided device tensors (include/papof.h: papof_tensor; papof_flow_batch_tensor) in and out.  One lane per element of the
+// planar side, 64-bit indices throughout; strides are in elements along (frame | pair, row, column, channel | component).
+__device__ __forceinline__ double tensor_load(const void* p, int dtype, long long o) {
+    if (dtype == PAPOF_DTYPE_U8) return (double)static_cast<const unsigned char*>(p)[o] / 255.0;  // as k_hwc_u8_to_planar
+    if (dtype == PAPOF_DTYPE_F32) return (double)static_cast<const float*>(p)[o];                 // exact widening
+    return static_cast<const double*>(p)[o];
+}
+
+// frames -> the planar fp64 level-0 array [frame][channel][row][col] of the batch chain.  pairs != 0: frame 2p is a's frame p,
+// frame 2p + 1 is b's frame p (the interleaving of fstep = 2); else frame f is a's frame f.
+__global__ __launch_bounds__(256) void k_ingest_frames(const papof_tensor a, const papof_tensor b, int pairs,
+                                                       double* __restrict__ planar, long long H, long long W, long long C,
+                                                       long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long np = H * W, f = i / (np * C), r = i - f * np * C, c = r / np, px = r - c * np, row = px / W,
+                    col = px - row * W;
+    const bool second = pairs && (f & 1);
+    const long long fi = pairs ? f >> 1 : f;
+    const long long o = fi * (second ? b.stride[0] : a.stride[0]) + row * (second ? b.stride[1] : a.stride[1]) +
+                        col * (second ? b.stride[2] : a.stride[2]) + c * (second ? b.stride[3] : a.stride[3]);
+    planar[i] = tensor_load(second ? b.data : a.data, second ? b.dtype : a.dtype, o);
+}
+
+// the chain's results -> a strided float32 / float64 tensor.  comp_major: src is [pair][K][H * W] (the flow: K = 2, u then v);
+// else [pair][H * W][K] (warpI2, HWC).  The destination is (pair, row, column, K).
+__global__ __launch_bounds__(256) void k_emit_outputs(const double* __restrict__ src, const papof_tensor dst, int comp_major,
+                                                      long long H, long long W, long long K, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long np = H * W, p = i / (np * K), r = i - p * np * K;
+    const long long k = comp_major ? r / np : r % K, px = comp_major ? r - k * np : r / K, row = px / W, col = px - row * W;
+    const long long o = p * dst.stride[0] + row * dst.stride[1] + col * dst.stride[2] + k * dst.stride[3];
+    const double v = src[i];
+    if (dst.dtype == PAPOF_DTYPE_F32)
+        static_cast<float*>(dst.data)[o] = (float)v;
+    else
+        static_cast<double*>(dst.data)[o] = v;
+}
+
 // ------------------------------------------------------------------------------------------------
 // separable correlation with clamped borders: src/ImageProcessing.h:259-279 (h), :350-369 (v).
 // Accumulation into a zeroed destination, taps in order l = -fsize..fsize.
@@ -1721,6 +1761,27 @@ int hwc_to_planar(papof_handle* h, const double* hwc, double* planar, int H, int
 
 int hwc_u8_to_planar(papof_handle* h, const unsigned char* hwc, double* planar, int H, int W, int C, int frames) {
     hipLaunchKernelGGL(k_hwc_u8_to_planar, grid2d(W, H, frames), dim3(BX, BY), 0, h->stream, hwc, planar, H, W, C);
+    LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
+int ingest_frames(papof_handle* h, const papof_tensor& a, const papof_tensor* b, double* planar, int H, int W, int C,
+                  int frames) {
+    const long long total = (long long)frames * H * W * C, blocks = (total + 255) / 256;
+    if (total <= 0) return PAPOF_OK;
+    if (blocks > 0x7fffffffLL) return PAPOF_EINVAL;
+    hipLaunchKernelGGL(k_ingest_frames, dim3((unsigned)blocks), dim3(256), 0, h->stream, a, b ? *b : a, b ? 1 : 0, planar,
+                       (long long)H, (long long)W, (long long)C, total);
+    LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
+int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bool comp_major, int H, int W, int K, int pairs) {
+    const long long total = (long long)pairs * H * W * K, blocks = (total + 255) / 256;
+    if (total <= 0) return PAPOF_OK;
+    if (blocks > 0x7fffffffLL) return PAPOF_EINVAL;
+    hipLaunchKernelGGL(k_emit_outputs, dim3((unsigned)blocks), dim3(256), 0, h->stream, src, dst, comp_major ? 1 : 0,
+                       (long long)H, (long long)W, (long long)K, total);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
