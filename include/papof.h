@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 106 /* 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 107 /* 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -405,6 +405,38 @@ int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const pa
                             const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
                             const papof_params* params, const papof_tensor* flow, const papof_tensor* warpI2, void* stream,
                             double timing_sec[PAPOF_N_TIMERS]);
+
+/* papof_flow_batch_tensor in both directions, with the forward-backward consistency check (Sundaram, Brox, Keutzer 2010).
+ * Pair i runs forward (image 1 -> image 2: flow_fw, warp_fw) and backward (image 2 -> image 1: flow_bw, warp_bw) in ONE
+ * launch chain: every frame's pyramid, features and derivative planes are built once and serve both directions, only the
+ * per-pair work (systems, solves, updates, the final warp) doubles.  Each direction's results are bit-identical to
+ * papof_flow on its frames (backward: the frames exchanged).  Frames, flows and warps, fallbacks, sub-batches (a sub-batch of
+ * n frame pairs counts 2n against the batch bound), the stream contract and timing_sec are papof_flow_batch_tensor's.
+ * occlusion: NULL (both flows, no check), or a PAPOF_DTYPE_U8 tensor (pair, row, column, {fw, bw}) that receives 1 where the
+ * pixel is occluded and 0 elsewhere -- computed from the fp64 flows before they are written, so it does not depend on the
+ * outputs' dtype.  For pixel (r, x) of the forward direction, with f = flow_fw, b = flow_bw of the pair:
+ *     (u, v) = f(r, x);  (X, Y) = (x + u, r + v);  (bu, bv) = b sampled bilinearly at (X, Y) by the reference's rule
+ *     (src/ImageProcessing.h:138-157: truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image);
+ *     e = (u + bu)^2 + (v + bv)^2;  m = (u^2 + v^2) + (bu^2 + bv^2);
+ *     occluded = X < 0 || X > width - 1 || Y < 0 || Y > height - 1 || !(e <= alpha1 * m + alpha2)   (NaN: occluded)
+ * in fp64 without fused multiply-adds; the backward direction swaps f and b.  Sundaram et al.: alpha1 = 0.01, alpha2 = 0.5.
+ * PAPOF_EINVAL, before anything is enqueued: everything papof_flow_batch_tensor refuses (for all four outputs), an occlusion
+ * tensor that is not uint8 or has a zero or negative stride, a negative or non-finite alpha. */
+int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                               const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                               const papof_params* params, const papof_tensor* flow_fw, const papof_tensor* warp_fw,
+                               const papof_tensor* flow_bw, const papof_tensor* warp_bw, const papof_tensor* occlusion,
+                               double alpha1, double alpha2, void* stream, double timing_sec[PAPOF_N_TIMERS]);
+
+/* The forward-backward consistency check of papof_flow_batch_tensor_fb on any two flow tensors: flow_fw, flow_bw float32
+ * (widened exactly) or float64, (pair, row, column, {vx, vy}), any non-negative strides; occlusion as there.  For the same
+ * float64 flows it is the same mask.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null
+ * stream) and returns without waiting: ordered behind the work queued there so far, and ahead of what follows.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL descriptor or data pointer, a flow that is not float32 / float64, a
+ * negative flow stride, the occlusion tensor's refusals and the alphas' above. */
+int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,
+                          const papof_tensor* flow_bw, double alpha1, double alpha2, const papof_tensor* occlusion,
+                          void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

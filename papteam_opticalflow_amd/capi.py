@@ -60,7 +60,8 @@ SYMBOLS = [
     "papof_pyramid_levels_for_min_width", "papof_stage_smoothflow_ex", "papof_stage_est_gaussian_mixture",
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
-    "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor",
+    "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
+    "papof_fb_check_tensor",
 ]
 
 
@@ -158,6 +159,11 @@ def load():
     _T = ctypes.POINTER(PapofTensor)
     L.papof_flow_batch_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, c_void_p, _D]
     L.papof_flow_batch_tensor.restype = c_int
+    L.papof_flow_batch_tensor_fb.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, _T, _T, _T,
+                                             c_double, c_double, c_void_p, _D]
+    L.papof_flow_batch_tensor_fb.restype = c_int
+    L.papof_fb_check_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_double, c_double, _T, c_void_p]
+    L.papof_fb_check_tensor.restype = c_int
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
     L.papof_strip_plan.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),

@@ -26,8 +26,13 @@
 // tensors, k_ingest_frames writes the level-0 array, no staging block -- and results written by k_emit_outputs into the
 // caller's strided tensors before anything else runs on the arena.  What the chain does not cover, a batch of one and a
 // re-run pair run one pair at a time on the device, their frames converted into a scratch block of the handle.
+//
+// Both directions (papof_flow_batch_tensor_fb): B backward pairs join the B forward ones as solver pairs B .. 2B - 1 on the
+// same per-frame arrays -- the kernels that read frames swap a backward pair's two (common.h: BatchK::bw) -- and k_fb_check
+// turns the two fp64 flows into the occlusion mask before the arena is reused.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 
 #include "common.h"
@@ -40,7 +45,7 @@ namespace {
 double now_sec() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct BatchOut {
-    const double* uv = nullptr;    // [pair][2][H * W]: the final flow
+    const double* uv = nullptr;    // [pair][2][H * W]: the final flow (with_bw: the B forward pairs, then the B backward ones)
     const double* warp = nullptr;  // [pair][H * W * C]
     std::vector<int> unproven;     // pairs whose Laplacian-noise guard could not be proven open: run them through the single call
 };
@@ -77,8 +82,9 @@ int batch_max(int H, int W, int C, int levels, const papof_params& P) {
     return max_b;
 }
 
-// Everything on h->stream, one stream: B pairs fill the chip by themselves.
-int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& frames, int H, int W, int C, int levels,
+// Everything on h->stream, one stream: B pairs fill the chip by themselves.  with_bw: the B backward pairs as well (pair B + p = pair
+// p with its two frames exchanged; BatchK::bw), 2B solver pairs on the same per-frame arrays -- only the per-pair work doubles.
+int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const BatchFrames& frames, int H, int W, int C, int levels,
                       const papof_params& P, double* timing, BatchOut& out) {
     PAPOF_TRY(check_params(P, levels));
     double ratio = P.ratio;
@@ -87,6 +93,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
     std::vector<PyrPlan> plan;
     PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, L, plan));
     const int fstep = sequence ? 1 : 2, nF = sequence ? B + 1 : 2 * B;
+    const int NP = with_bw ? 2 * B : B;  // solver pairs: per-pair arrays, operands, witness blocks
     const int fc = feature_channels(C);
     const size_t np0 = (size_t)H * W;
     const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
@@ -102,10 +109,10 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
     if (staged) bytes += (size_t)nF * np0 * C * (u8 ? 1 : 8) + 4096;                // the uploaded frames
     bytes += (size_t)nF * pyr_px * (C + 2 * fc) * 8 + (size_t)levels * 3 * 4096;     // pyramids, features, smoothed features
     bytes += (size_t)nF * np0 * C * 8 * 5 + 5 * 4096;                               // two filter temporaries, three derivative planes
-    bytes += (size_t)B * (4 * np0 * 8 + np0 * C * 8) + 3 * 4096;                    // two flow pairs, the warped image
-    bytes += (size_t)B * ((3 * 2 * ((cells + kLanes + 63) / 64 * 64) + 2 * (cells_d + kLanes)) * 8 + 2 * 4096);  // solver operands
-    bytes += (size_t)B * (8 * (tiny_cells * 8 + 256));                              // row-major operands of k_sor_tiny's levels
-    bytes += (size_t)(B + nF) * kLapFlagWords * 4 + 8192;                           // guard flags
+    bytes += (size_t)NP * (4 * np0 * 8 + np0 * C * 8) + 3 * 4096;                   // two flow pairs, the warped image
+    bytes += (size_t)NP * ((3 * 2 * ((cells + kLanes + 63) / 64 * 64) + 2 * (cells_d + kLanes)) * 8 + 2 * 4096);  // solver operands
+    bytes += (size_t)NP * (8 * (tiny_cells * 8 + 256));                             // row-major operands of k_sor_tiny's levels
+    bytes += (size_t)(NP + nF) * kLapFlagWords * 4 + 8192;                          // guard flags
     bytes += (size_t)1 << 20;
     h->seq.valid = false;  // (the arena is laid out anew: a kept sequence pyramid does not survive a batch)
     PAPOF_TRY(ensure_arena(h, bytes));
@@ -130,20 +137,20 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
     double* gx = A.f64((size_t)nF * np0 * C);
     double* gy = A.f64((size_t)nF * np0 * C);
     double* gxy = A.f64((size_t)nF * np0 * C);
-    double* uvA = A.f64((size_t)B * 2 * np0);
-    double* uvB = A.f64((size_t)B * 2 * np0);
-    double* warp = A.f64((size_t)B * np0 * C);
-    unsigned* wit = reinterpret_cast<unsigned*>(A.alloc((size_t)B * kLapFlagWords * sizeof(unsigned)));
+    double* uvA = A.f64((size_t)NP * 2 * np0);
+    double* uvB = A.f64((size_t)NP * 2 * np0);
+    double* warp = A.f64((size_t)NP * np0 * C);
+    unsigned* wit = reinterpret_cast<unsigned*>(A.alloc((size_t)NP * kLapFlagWords * sizeof(unsigned)));
     unsigned* nzf = reinterpret_cast<unsigned*>(A.alloc((size_t)nF * kLapNzWords * sizeof(unsigned)));
     if (A.overflow) return PAPOF_ENOMEM;
     // the pairs' solver operands: identical allocation sequences, hence a constant stride from pair to pair
-    std::vector<SorPlanes> SP(B), ST(B);
-    for (int p = 0; p < B; p++) PAPOF_TRY(sor_alloc_planes(A, H, W, PAPOF_SOR_EXACT, n_sor_max, SP[p]));
-    for (int p = 0; p < B; p++) PAPOF_TRY(sor_alloc_tiny_planes(A, tiny_cells, ST[p]));
+    std::vector<SorPlanes> SP(NP), ST(NP);
+    for (int p = 0; p < NP; p++) PAPOF_TRY(sor_alloc_planes(A, H, W, PAPOF_SOR_EXACT, n_sor_max, SP[p]));
+    for (int p = 0; p < NP; p++) PAPOF_TRY(sor_alloc_tiny_planes(A, tiny_cells, ST[p]));
     if (A.overflow) return PAPOF_ENOMEM;
     const size_t sp_stride = (size_t)(SP[1].phi - SP[0].phi), spd_stride = (size_t)(SP[1].du - SP[0].du);
     const size_t st_stride = (size_t)(ST[1].phi - ST[0].phi);
-    for (int p = 1; p < B; p++)
+    for (int p = 1; p < NP; p++)
         if ((size_t)(SP[p].phi - SP[0].phi) != p * sp_stride || (size_t)(SP[p].du - SP[0].du) != p * spd_stride ||
             (size_t)(ST[p].phi - ST[0].phi) != p * st_stride || (size_t)(ST[p].du - ST[0].du) != p * st_stride)
             return PAPOF_EDEVICE;
@@ -160,7 +167,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
         LC[k].tiny = (size_t)L[k].w * L[k].h <= kTinyMaxCells && sor_tiny_fits(h, L[k].h, L[k].w, Kk);
         LC[k].per = LC[k].tiny ? 0 : (size_t)skew_dims(L[k].h, L[k].w, Kk, 1, 1).nb * Kk * 32;
         LC[k].off = prog_total;
-        prog_total += LC[k].per * (size_t)n_outer * B;
+        prog_total += LC[k].per * (size_t)n_outer * NP;
     }
     PAPOF_TRY(sor_counters_ensure(h, prog_total));
 
@@ -193,7 +200,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
     }
     const unsigned epoch = h->lap_epoch;  // a flag is set when it holds this call's number
     if (guard) {
-        PAPOF_HIP(hipMemsetAsync(wit, 0, (size_t)B * kLapFlagWords * sizeof(unsigned), st));
+        PAPOF_HIP(hipMemsetAsync(wit, 0, (size_t)NP * kLapFlagWords * sizeof(unsigned), st));
         PAPOF_HIP(hipMemsetAsync(nzf, 0, (size_t)nF * kLapNzWords * sizeof(unsigned), st));
     }
     if (!staged)
@@ -224,16 +231,16 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
             const size_t np = (size_t)lw * lh;
             const int K = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
             if (k == levels - 1) {
-                PAPOF_HIP(hipMemsetAsync(uv, 0, (size_t)B * 2 * np * sizeof(double), st));  // :801-806 (the warp is folded in)
+                PAPOF_HIP(hipMemsetAsync(uv, 0, (size_t)NP * 2 * np * sizeof(double), st));  // :801-806 (the warp is folded in)
             } else {  // :809-812: bilinear up-sampling times 1 / ratio, all pairs' u and v in one launch
-                PAPOF_TRY(resize(h, uv, uv2, ph, pw, 2 * B, lh, lw, (double)lw / pw, (double)lh / ph, true, 1 / ratio));
+                PAPOF_TRY(resize(h, uv, uv2, ph, pw, 2 * NP, lh, lw, (double)lw / pw, (double)lh / ph, true, 1 / ratio));
                 std::swap(uv, uv2);
             }
             const bool tiny = LC[k].tiny;
             SorPlanes sp = tiny ? ST[0] : SP[0];
             if (!tiny) {
                 PAPOF_TRY(sor_bind_plain(h, sp, lh, lw, K));
-                PAPOF_TRY(sor_reset_planes_batch(h, sp, B, sp_stride));
+                PAPOF_TRY(sor_reset_planes_batch(h, sp, NP, sp_stride));
             }
             BatchK bk{};
             bk.im = (size_t)fstep * np * fc;
@@ -241,7 +248,9 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
             bk.sp = tiny ? st_stride : sp_stride;
             bk.d = tiny ? st_stride : spd_stride;
             bk.wit = kLapFlagWords;
-            const SorBatch bt{B, sp_stride, spd_stride, LC[k].per, st_stride};
+            bk.bw = with_bw ? B : 0;
+            bk.fr = np * fc;
+            const SorBatch bt{NP, sp_stride, spd_stride, LC[k].per, st_stride};
             const double *f1 = F[k], *f2 = F[k] + np * fc, *s1 = S[k];
             // Few-pixel levels (the deep end of an 8- or 15-level pyramid): the flow leaves the image altogether in some iterations,
             // every warped value is then frame 1's and there is NO valid sample -- which only a look at every pixel can tell from
@@ -250,17 +259,17 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
             const bool exhaustive = guard && np <= 4096;
             for (int count = 0; count < n_outer; count++) {
                 unsigned* const w_prev = guard && !exhaustive && count > 0 ? wit + lap_wit_word(slot - 1) : nullptr;
-                PAPOF_TRY(flow_system(h, f1, f2, uv, uv + np, s1, lh, lw, fc, P.alpha, P.omega, sp, w_prev, 0, -1, B, &bk));
-                h->sor_prog_next = tiny ? nullptr : h->sync_words + 32 + LC[k].off + (size_t)count * LC[k].per * B;
+                PAPOF_TRY(flow_system(h, f1, f2, uv, uv + np, s1, lh, lw, fc, P.alpha, P.omega, sp, w_prev, 0, -1, NP, &bk));
+                h->sor_prog_next = tiny ? nullptr : h->sync_words + 32 + LC[k].off + (size_t)count * LC[k].per * NP;
                 const int rc = sor_solve(h, sp, lh, lw, P.alpha, P.omega, K, PAPOF_SOR_EXACT, &bt);
                 h->sor_prog_next = nullptr;
                 PAPOF_TRY(rc);
                 // the estimate behind the level's last update is witnessed by the update kernel itself (nobody evaluates that warp)
                 unsigned* const w_now = guard && !exhaustive && count + 1 == n_outer ? wit + lap_wit_word(slot) : nullptr;
                 PAPOF_TRY(update_warp_phi(h, sp, uv, uv + np, uv2, uv2 + np, f1, f2, nullptr, nullptr, lh, lw, fc, false, 0, -1,
-                                          w_now, B, &bk));
+                                          w_now, NP, &bk));
                 std::swap(uv, uv2);
-                if (exhaustive) PAPOF_TRY(lap_small_check(h, f1, f2, uv, uv + np, lh, lw, fc, wit + lap_wit_word(slot), B, &bk));
+                if (exhaustive) PAPOF_TRY(lap_small_check(h, f1, f2, uv, uv + np, lh, lw, fc, wit + lap_wit_word(slot), NP, &bk));
                 slot_level.push_back(k);
                 slot++;
             }
@@ -272,8 +281,10 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
         bk.im = (size_t)fstep * np0 * C;
         bk.uv = 2 * np0;
         bk.out = np0 * C;
+        bk.bw = with_bw ? B : 0;
+        bk.fr = np0 * C;
         PAPOF_TRY(bicubic_warp(h, Lp[0], Lp[0] + np0 * C, gx + np0 * C, gy + np0 * C, gxy + np0 * C, uv, uv + np0, warp, H, W, C,
-                               nullptr, false, true, B, &bk));
+                               nullptr, false, true, NP, &bk));
         return PAPOF_OK;
     };
     const int rc_levels = levels_loop();
@@ -288,13 +299,14 @@ int flow_batch_device(papof_handle* h, int B, int sequence, const BatchFrames& f
     PAPOF_HIP(hipStreamSynchronize(st));
     PAPOF_TRY(sor_check(h));
     if (guard) {
-        hw.resize((size_t)B * kLapFlagWords);
+        hw.resize((size_t)NP * kLapFlagWords);
         hn.resize((size_t)nF * kLapNzWords);
         PAPOF_HIP(hipMemcpy(hw.data(), wit, hw.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
         PAPOF_HIP(hipMemcpy(hn.data(), nzf, hn.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        for (int p = 0; p < B; p++) {
+        for (int p = 0; p < NP; p++) {
             bool open = true;
-            const int fa = p * fstep, fb = fa + 1;
+            const bool back = p >= B;  // a backward pair: the frames of pair p - B, exchanged
+            const int f1 = (back ? p - B : p) * fstep, fa = back ? f1 + 1 : f1, fb = back ? f1 : f1 + 1;
             for (int s = 0; s + 1 < slot && open; s++)  // the estimate behind the call's last update is never consulted
                 for (int c = 0; c < fc; c++) {
                     const unsigned w = hw[(size_t)p * kLapFlagWords + lap_wit_word(s) + c];
@@ -375,7 +387,7 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
         BatchFrames bf;
         bf.host = frames;
         bf.u8 = u8;
-        const int rc = flow_batch_device(h, n_pairs, sequence, bf, H, W, C, levels, P, tm, out);
+        const int rc = flow_batch_device(h, n_pairs, sequence, false, bf, H, W, C, levels, P, tm, out);
         if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
             std::memset(tm, 0, sizeof tm);
             for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
@@ -429,16 +441,43 @@ bool valid_tensor(const papof_tensor* t, bool output) {
     return true;
 }
 
-// papof_flow_batch_tensor behind its checks and its entry wait: flow_batch_host's orchestration on device tensors.  The frames
-// are read where they are (k_ingest_frames), the results leave the arena through k_emit_outputs before anything else runs on
-// it, and what the batched chain does not cover runs pair by pair on the device.  tm accumulates the phases.
+// The outputs of papof_flow_batch_tensor (flow, warp) and of papof_flow_batch_tensor_fb (also the backward pairs' flow_bw,
+// warp_bw and, when occ is given, the forward-backward check with a1, a2).
+struct TensorOut {
+    const papof_tensor* flow = nullptr;
+    const papof_tensor* warp = nullptr;
+    const papof_tensor* flow_bw = nullptr;  // NULL: forward pairs only
+    const papof_tensor* warp_bw = nullptr;
+    const papof_tensor* occ = nullptr;
+    double a1 = 0, a2 = 0;
+};
+
+papof_tensor planar_flow(const double* uv, int H, int W) {  // the chain's [pair][2][H * W] fp64 flows as a tensor
+    papof_tensor t;
+    t.data = const_cast<double*>(uv);
+    t.dtype = PAPOF_DTYPE_F64;
+    t.stride[0] = 2LL * H * W;
+    t.stride[1] = W;
+    t.stride[2] = 1;
+    t.stride[3] = (long long)H * W;
+    return t;
+}
+
+// papof_flow_batch_tensor(_fb) behind its checks and its entry wait: flow_batch_host's orchestration on device tensors.  The
+// frames are read where they are (k_ingest_frames), the results leave the arena through k_emit_outputs before anything else
+// runs on it, and what the batched chain does not cover runs pair by pair on the device.  With backward pairs, a sub-batch of
+// nb frame pairs is 2nb solver pairs (the batch bound counts solver pairs), and the forward-backward check runs on the fp64
+// flows before anything else is laid out in the arena (or the scratch) -- the mask does not depend on the output dtype.
+// tm accumulates the phases.
 int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor& fa, const papof_tensor* fb, int H, int W,
-                      int C, int levels, const papof_params& P, const papof_tensor& flow, const papof_tensor& warp, double* tm) {
+                      int C, int levels, const papof_params& P, const TensorOut& o, double* tm) {
     const size_t np0 = (size_t)H * W, frame = np0 * C;
+    const bool with_bw = o.flow_bw != nullptr;
     // one pair on its own: its two frames into the handle's scratch (planar fp64; not in the arena, which the single call lays
-    // out anew), the device call (both passes of the guard), the results out
+    // out anew), the device call (both passes of the guard), the results out; with backward pairs, the single call on the
+    // exchanged frames as well, and the check on the two fp64 flows
     const auto single = [&](int p) -> int {
-        const size_t bytes = (2 * frame + 2 * np0 + frame) * sizeof(double);
+        const size_t bytes = (with_bw ? 2 * frame + 4 * np0 + 2 * frame : 2 * frame + 2 * np0 + frame) * sizeof(double);
         if (h->tensor_scratch_bytes < bytes) {
             if (h->tensor_scratch) {
                 PAPOF_HIP(hipStreamSynchronize(h->stream));
@@ -452,7 +491,7 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
             }
             h->tensor_scratch_bytes = bytes;
         }
-        double *f = h->tensor_scratch, *uv = f + 2 * frame, *wp = uv + 2 * np0;
+        double *f = h->tensor_scratch, *uv = f + 2 * frame, *wp = uv + (with_bw ? 4 : 2) * np0;
         const papof_tensor a = shifted(fa, p);
         if (sequence) {
             PAPOF_TRY(ingest_frames(h, a, nullptr, f, H, W, C, 2));
@@ -462,16 +501,26 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         }
         double t1[PAPOF_N_TIMERS];
         PAPOF_TRY(flow_device_planar(h, f, f + frame, H, W, C, levels, P, uv, uv + np0, wp, t1));
-        PAPOF_TRY(emit_outputs(h, uv, shifted(flow, p), true, H, W, 2, 1));
-        PAPOF_TRY(emit_outputs(h, wp, shifted(warp, p), false, H, W, C, 1));
+        PAPOF_TRY(emit_outputs(h, uv, shifted(*o.flow, p), true, H, W, 2, 1));
+        PAPOF_TRY(emit_outputs(h, wp, shifted(*o.warp, p), false, H, W, C, 1));
         for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
+        if (with_bw) {
+            double *uvb = uv + 2 * np0, *wpb = wp + frame;
+            PAPOF_TRY(flow_device_planar(h, f + frame, f, H, W, C, levels, P, uvb, uvb + np0, wpb, t1));
+            PAPOF_TRY(emit_outputs(h, uvb, shifted(*o.flow_bw, p), true, H, W, 2, 1));
+            PAPOF_TRY(emit_outputs(h, wpb, shifted(*o.warp_bw, p), false, H, W, C, 1));
+            for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
+            if (o.occ)
+                PAPOF_TRY(fb_check(h, h->stream, planar_flow(uv, H, W), planar_flow(uvb, H, W), shifted(*o.occ, p), 1, H, W, o.a1,
+                                   o.a2));
+        }
         return PAPOF_OK;
     };
     if (!batch_applies(h, n_pairs, H, W, C, levels, P)) {
         for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
         return PAPOF_OK;
     }
-    const int max_b = batch_max(H, W, C, levels, P);
+    const int max_b = with_bw ? std::max(1, batch_max(H, W, C, levels, P) / 2) : batch_max(H, W, C, levels, P);
     for (int p0 = 0; p0 < n_pairs;) {
         int nb = std::min(max_b, n_pairs - p0);
         if (n_pairs - (p0 + nb) == 1 && nb > 2) nb -= 1;  // leave two pairs for the last sub-batch rather than one
@@ -481,7 +530,7 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         bf.b = sequence ? nullptr : &b;
         BatchOut out;
         double t1[PAPOF_N_TIMERS];
-        const int rc = flow_batch_device(h, nb, sequence, bf, H, W, C, levels, P, t1, out);
+        const int rc = flow_batch_device(h, nb, sequence, with_bw, bf, H, W, C, levels, P, t1, out);
         if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
             for (int p = p0; p < p0 + nb; p++) PAPOF_TRY(single(p));
             p0 += nb;
@@ -489,16 +538,76 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         }
         PAPOF_TRY(rc);
         for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
-        PAPOF_TRY(emit_outputs(h, out.uv, shifted(flow, p0), true, H, W, 2, nb));
-        PAPOF_TRY(emit_outputs(h, out.warp, shifted(warp, p0), false, H, W, C, nb));
+        PAPOF_TRY(emit_outputs(h, out.uv, shifted(*o.flow, p0), true, H, W, 2, nb));
+        PAPOF_TRY(emit_outputs(h, out.warp, shifted(*o.warp, p0), false, H, W, C, nb));
+        if (!with_bw) {
+            for (int p : out.unproven) {
+                h->lap_reruns++;
+                PAPOF_TRY(single(p0 + p));
+            }
+            p0 += nb;
+            continue;
+        }
+        const double* uvb = out.uv + (size_t)nb * 2 * np0;
+        PAPOF_TRY(emit_outputs(h, uvb, shifted(*o.flow_bw, p0), true, H, W, 2, nb));
+        PAPOF_TRY(emit_outputs(h, out.warp + (size_t)nb * frame, shifted(*o.warp_bw, p0), false, H, W, C, nb));
+        if (o.occ)
+            PAPOF_TRY(fb_check(h, h->stream, planar_flow(out.uv, H, W), planar_flow(uvb, H, W), shifted(*o.occ, p0), nb, H, W,
+                               o.a1, o.a2));
+        // an unproven solver pair -- forward pair q or backward pair nb + q -- runs again through the single call; both
+        // directions of frame pair q do, because its mask needs both fp64 flows and the arena does not outlive the single call
+        std::vector<char> redo(nb, 0);
         for (int p : out.unproven) {
             h->lap_reruns++;
-            PAPOF_TRY(single(p0 + p));
+            redo[p < nb ? p : p - nb] = 1;
         }
+        for (int q = 0; q < nb; q++)
+            if (redo[q]) PAPOF_TRY(single(p0 + q));
         p0 += nb;
     }
     return PAPOF_OK;
 }
+
+// the entry of papof_flow_batch_tensor(_fb) after the descriptors' checks: parameters, entry wait, the call, complete on return
+int tensor_entry(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2, int height,
+                 int width, int c, int pyramid_levels, const papof_params* params, const TensorOut& o, void* stream,
+                 double* timing_sec) {
+    papof_params P;
+    if (params)
+        P = *params;
+    else
+        papof_default_params(&P);
+    PAPOF_TRY(check_params(P, pyramid_levels));
+    PAPOF_HIP(hipSetDevice(h->device));
+    const double t0 = now_sec();
+    // stream order on entry: the handle's streams (non-blocking, hence also for the null stream) start behind what the caller
+    // has queued so far
+    if (!h->entry_event) PAPOF_HIP(hipEventCreateWithFlags(&h->entry_event, hipEventDisableTiming));
+    PAPOF_HIP(hipEventRecord(h->entry_event, static_cast<hipStream_t>(stream)));
+    PAPOF_HIP(hipStreamWaitEvent(h->stream, h->entry_event, 0));
+    if (h->prep_stream) PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->entry_event, 0));
+    double tm[PAPOF_N_TIMERS];
+    std::memset(tm, 0, sizeof tm);
+    const int rc = flow_batch_tensor(h, n_pairs, sequence, *frames, frames2, height, width, c, pyramid_levels, P, o, tm);
+    const hipError_t se = hipStreamSynchronize(h->stream);  // complete on return: the emits are the last work of the call
+    PAPOF_TRY(rc);
+    if (se != hipSuccess) {
+        set_last_error("hipStreamSynchronize", se, __FILE__, __LINE__);
+        return PAPOF_EDEVICE;
+    }
+    tm[PAPOF_T_TOTAL] = now_sec() - t0;  // the caller's view
+    if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
+    return PAPOF_OK;
+}
+
+bool valid_mask(const papof_tensor* t) {  // the uint8 occlusion output: every stride positive
+    if (!t || !t->data || t->dtype != PAPOF_DTYPE_U8) return false;
+    for (int i = 0; i < 4; i++)
+        if (t->stride[i] <= 0) return false;
+    return true;
+}
+
+bool valid_alphas(double a1, double a2) { return std::isfinite(a1) && std::isfinite(a2) && a1 >= 0 && a2 >= 0; }
 
 }  // namespace
 
@@ -528,33 +637,43 @@ int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const pa
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
     if (!valid_tensor(frames, false) || !valid_tensor(flow, true) || !valid_tensor(warpI2, true)) return PAPOF_EINVAL;
     if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
-    papof_params P;
-    if (params)
-        P = *params;
-    else
-        papof_default_params(&P);
-    PAPOF_TRY(check_params(P, pyramid_levels));
+    TensorOut o;
+    o.flow = flow;
+    o.warp = warpI2;
+    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec);
+}
+
+int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                               const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                               const papof_params* params, const papof_tensor* flow_fw, const papof_tensor* warp_fw,
+                               const papof_tensor* flow_bw, const papof_tensor* warp_bw, const papof_tensor* occlusion,
+                               double alpha1, double alpha2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
+    if (!valid_tensor(frames, false) || !valid_tensor(flow_fw, true) || !valid_tensor(warp_fw, true) ||
+        !valid_tensor(flow_bw, true) || !valid_tensor(warp_bw, true))
+        return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
+    if ((occlusion && !valid_mask(occlusion)) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
+    TensorOut o;
+    o.flow = flow_fw;
+    o.warp = warp_fw;
+    o.flow_bw = flow_bw;
+    o.warp_bw = warp_bw;
+    o.occ = occlusion;
+    o.a1 = alpha1;
+    o.a2 = alpha2;
+    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec);
+}
+
+int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,
+                          const papof_tensor* flow_bw, double alpha1, double alpha2, const papof_tensor* occlusion,
+                          void* stream) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1) return PAPOF_EINVAL;
+    for (const papof_tensor* t : {flow_fw, flow_bw})
+        if (!valid_tensor(t, false) || t->dtype == PAPOF_DTYPE_U8) return PAPOF_EINVAL;
+    if (!valid_mask(occlusion) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
-    const double t0 = now_sec();
-    // stream order on entry: the handle's streams (non-blocking, hence also for the null stream) start behind what the caller
-    // has queued so far
-    if (!h->entry_event) PAPOF_HIP(hipEventCreateWithFlags(&h->entry_event, hipEventDisableTiming));
-    PAPOF_HIP(hipEventRecord(h->entry_event, static_cast<hipStream_t>(stream)));
-    PAPOF_HIP(hipStreamWaitEvent(h->stream, h->entry_event, 0));
-    if (h->prep_stream) PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->entry_event, 0));
-    double tm[PAPOF_N_TIMERS];
-    std::memset(tm, 0, sizeof tm);
-    const int rc = flow_batch_tensor(h, n_pairs, sequence, *frames, frames2, height, width, c, pyramid_levels, P, *flow, *warpI2,
-                                     tm);
-    const hipError_t se = hipStreamSynchronize(h->stream);  // complete on return: the emits are the last work of the call
-    PAPOF_TRY(rc);
-    if (se != hipSuccess) {
-        set_last_error("hipStreamSynchronize", se, __FILE__, __LINE__);
-        return PAPOF_EDEVICE;
-    }
-    tm[PAPOF_T_TOTAL] = now_sec() - t0;  // the caller's view
-    if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
-    return PAPOF_OK;
+    return fb_check(h, static_cast<hipStream_t>(stream), *flow_fw, *flow_bw, *occlusion, n_pairs, height, width, alpha1, alpha2);
 }
 
 }  // extern "C"

@@ -52,7 +52,24 @@ struct BatchK {
     size_t d;     // ... and its (du, dv) planes
     size_t wit;   // witness words of the Laplacian-noise guard (unsigned)
     size_t out;   // the interleaved result image
+    // backward pairs (papof_flow_batch_tensor_fb): pairs bw .. 2 bw - 1 are pairs 0 .. bw - 1 with the roles of their frames
+    // swapped -- the per-frame pointers are those of pair p - bw, image 1 one frame (fr elements of the per-frame planes) on,
+    // image 2 one frame back.  bw = 0: forward pairs only.
+    size_t bw;
+    size_t fr;
 };
+
+// The per-frame pointers of the batch item p (blockIdx.y): im1 / im2 are pair 0's images 1 and 2, advanced to pair p's -- and,
+// for a backward pair, exchanged.  Returns the offset from pair 0's image-1 planes to pair p's image-1 planes.
+__device__ __forceinline__ size_t batch_frames(const BatchK& bk, size_t p, const double* __restrict__& im1,
+                                               const double* __restrict__& im2) {
+    const bool back = bk.bw != 0 && p >= bk.bw;
+    const size_t o = (back ? p - bk.bw : p) * bk.im;
+    const double *a = im1 + o, *b = im2 + o;
+    im1 = back ? b : a;
+    im2 = back ? a : b;
+    return back ? o + bk.fr : o;
+}
 
 struct Taps {                  // 1-D correlation taps, passed by value as a kernel argument
     double t[2 * kMaxFsize + 1];
@@ -375,6 +392,10 @@ int planar_to_hwc(papof_handle* h, const double* planar, double* hwc, int H, int
 int ingest_frames(papof_handle* h, const papof_tensor& a, const papof_tensor* b, double* planar, int H, int W, int C,
                   int frames);
 int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bool comp_major, int H, int W, int K, int pairs);
+// forward-backward consistency of `pairs` flow pairs (F32 / F64, (pair, row, column, component)) into the uint8 mask
+// (pair, row, column, {fw, bw}) on stream st: kernels.hip, k_fb_check
+int fb_check(papof_handle* h, hipStream_t st, const papof_tensor& fw, const papof_tensor& bw, const papof_tensor& mask,
+             int pairs, int H, int W, double a1, double a2);
 int filter_h(papof_handle* h, const double* src, double* dst, int H, int W, int planes, const Taps& f,
              const Rect* rc = nullptr);
 int filter_v(papof_handle* h, const double* src, double* dst, int H, int W, int planes, const Taps& f,

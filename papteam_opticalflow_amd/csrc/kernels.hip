@@ -117,6 +117,57 @@ __global__ __launch_bounds__(256) void k_emit_outputs(const double* __restrict__
         static_cast<double*>(dst.data)[o] = v;
 }
 
+// Forward-backward consistency (Sundaram, Brox, Keutzer 2010; papof_fb_check_tensor, papof_flow_batch_tensor_fb).
+// blockIdx.y = pair * 2 + direction; direction 0 follows the forward flow f = fw into the backward flow b = bw, direction
+// 1 the reverse, on the pixels of the pair's second frame.  For pixel (r, x): (u, v) = f, (X, Y) = (x + u, r + v), (bu, bv)
+// = b sampled bilinearly at (X, Y) by the reference's rule (bilinear_taps / bilinear_apply: truncation toward zero, fraction
+// clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0 in (m, n) order), and the pixel is occluded
+// where (X, Y) leaves [0, W - 1] x [0, H - 1] or !(|(u, v) + (bu, bv)|^2 <= a1 (|(u, v)|^2 + |(bu, bv)|^2) + a2) -- NaN
+// counts as occluded.  fp64 throughout, no contraction (the library's -ffp-contract=off).  mask: 1 byte per (pair, row,
+// column, direction).  A block is a 64 x 4 tile of one direction of one pair: the four taps of neighbouring pixels share lines.
+constexpr int kFbTX = 64, kFbTY = 4;
+__device__ __forceinline__ double flow_load(const papof_tensor& t, long long o) {
+    return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
+}
+__global__ __launch_bounds__(kFbTX * kFbTY) void k_fb_check(const papof_tensor fw, const papof_tensor bw, const papof_tensor mask,
+                                                         int H, int W, double a1, double a2) {
+    const int tx = (W + kFbTX - 1) / kFbTX;
+    const int x = (int)(blockIdx.x % tx) * kFbTX + threadIdx.x, r = (int)(blockIdx.x / tx) * kFbTY + threadIdx.y;
+    if (x >= W || r >= H) return;
+    const long long p = blockIdx.y >> 1;
+    const int dir = blockIdx.y & 1;
+    const papof_tensor& f = dir ? bw : fw;
+    const papof_tensor& b = dir ? fw : bw;
+    const long long of = p * f.stride[0] + r * f.stride[1] + x * f.stride[2];
+    const double u = flow_load(f, of), v = flow_load(f, of + f.stride[3]);
+    const double X = (double)x + u, Y = (double)r + v;
+    bool occluded = true;
+    if (X >= 0 && X <= (double)(W - 1) && Y >= 0 && Y <= (double)(H - 1)) {  // (false for a NaN: occluded)
+        const int xx = (int)X, yy = (int)Y;
+        double dx = X - xx, dy = Y - yy;
+        dx = dx > 1 ? 1.0 : dx;
+        dx = dx < 0 ? 0.0 : dx;
+        dy = dy > 1 ? 1.0 : dy;
+        dy = dy < 0 ? 0.0 : dy;
+        double bu = 0.0, bv = 0.0;
+#pragma unroll
+        for (int m = 0; m <= 1; m++)
+#pragma unroll
+            for (int n = 0; n <= 1; n++) {
+                const long long ob = p * b.stride[0] + clampi(yy + n, H) * b.stride[1] + clampi(xx + m, W) * b.stride[2];
+                const double s = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
+                bu += flow_load(b, ob) * s;
+                bv += flow_load(b, ob + b.stride[3]) * s;
+            }
+        const double du = u + bu, dv = v + bv;
+        const double e = du * du + dv * dv;
+        const double mag = (u * u + v * v) + (bu * bu + bv * bv);
+        occluded = !(e <= a1 * mag + a2);
+    }
+    static_cast<unsigned char*>(mask.data)[p * mask.stride[0] + r * mask.stride[1] + x * mask.stride[2] + dir * mask.stride[3]] =
+        occluded ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // separable correlation with clamped borders: src/ImageProcessing.h:259-279 (h), :350-369 (v).
 // Accumulation into a zeroed destination, taps in order l = -fsize..fsize.
@@ -1056,9 +1107,7 @@ __global__ __launch_bounds__(TX * 16, TX == 32 ? 4 : 1) void k_flow_system(const
                                                      unsigned mark, int row0, int row1, BatchK bk) {
     if (BATCH) {  // blockIdx.y: the pair of a batch (common.h: BatchK)
         const size_t p = blockIdx.y;
-        im1 += p * bk.im;
-        im2 += p * bk.im;
-        im1s += p * bk.im;
+        im1s += batch_frames(bk, p, im1, im2);  // (a backward pair: image 1's smoothed features are frame 2's)
         u += p * bk.uv;
         v += p * bk.uv;
         if (wit != nullptr) wit += p * bk.wit;
@@ -1433,8 +1482,7 @@ __global__ void k_update_warp_phi(const double* __restrict__ sdu, const double* 
         v += p * bk.uv;
         u_out += p * bk.uv;
         v_out += p * bk.uv;
-        im1 += p * bk.im;
-        im2 += p * bk.im;
+        batch_frames(bk, p, im1, im2);
         if (wit != nullptr) wit += p * bk.wit;
     }
     int tbx, tby;  // a contiguous run of blocks per XCD (xcd_tile): blocks above each other share the lines of the banded (du, dv)
@@ -1540,11 +1588,12 @@ __global__ void k_bicubic(const double* __restrict__ im1, const double* __restri
                           unsigned long long* stamp, int planar_out, int clamp, BatchK bk) {
     if (BATCH) {  // blockIdx.y: the pair of a batch (common.h: BatchK)
         const size_t p = blockIdx.y;
-        im1 += p * bk.im;
-        im2 += p * bk.im;
-        gx += p * bk.im;
-        gy += p * bk.im;
-        gxy += p * bk.im;
+        // gx, gy, gxy are image 2's planes: pair 0's frame 2, or -- a backward pair -- its frame 1, one frame back
+        const ptrdiff_t o1 = (ptrdiff_t)batch_frames(bk, p, im1, im2);
+        const ptrdiff_t o2 = bk.bw != 0 && p >= bk.bw ? o1 - 2 * (ptrdiff_t)bk.fr : o1;
+        gx += o2;
+        gy += o2;
+        gxy += o2;
         vx += p * bk.uv;
         vy += p * bk.uv;
         out += p * bk.out;
@@ -1783,6 +1832,26 @@ int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bo
     hipLaunchKernelGGL(k_emit_outputs, dim3((unsigned)blocks), dim3(256), 0, h->stream, src, dst, comp_major ? 1 : 0,
                        (long long)H, (long long)W, (long long)K, total);
     LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
+int fb_check(papof_handle* h, hipStream_t st, const papof_tensor& fw, const papof_tensor& bw, const papof_tensor& mask,
+             int pairs, int H, int W, double a1, double a2) {
+    const long long tiles = (long long)((W + kFbTX - 1) / kFbTX) * ((H + kFbTY - 1) / kFbTY);
+    if (pairs <= 0 || tiles <= 0) return PAPOF_OK;
+    if (tiles > 0x7fffffffLL) return PAPOF_EINVAL;
+    const auto at = [](const papof_tensor& t, long long items) {  // the same tensor from pair `items` on
+        papof_tensor r = t;
+        const long long es = t.dtype == PAPOF_DTYPE_U8 ? 1 : (t.dtype == PAPOF_DTYPE_F32 ? 4 : 8);
+        r.data = static_cast<char*>(t.data) + items * t.stride[0] * es;
+        return r;
+    };
+    for (int p0 = 0; p0 < pairs; p0 += 32767) {  // (gridDim.y: two directions of at most 32767 pairs per launch)
+        const int n = std::min(32767, pairs - p0);
+        hipLaunchKernelGGL(k_fb_check, dim3((unsigned)tiles, 2 * n), dim3(kFbTX, kFbTY), 0, st, at(fw, p0), at(bw, p0),
+                           at(mask, p0), H, W, a1, a2);
+        LAUNCH_CHECK();
+    }
     return PAPOF_OK;
 }
 
@@ -2239,8 +2308,7 @@ static __global__ __launch_bounds__(256) void k_lap_small(const double* __restri
     const int np = H * W;
     {   // blockIdx.y: the pair of a batch (common.h: BatchK)
         const size_t p = blockIdx.y;
-        im1 += p * bk.im;
-        im2 += p * bk.im;
+        batch_frames(bk, p, im1, im2);
         u += p * bk.uv;
         v += p * bk.uv;
         wit += p * bk.wit;

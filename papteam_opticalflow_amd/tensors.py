@@ -14,14 +14,25 @@ input's device, with no autograd graph.  Every pair is bit-identical to the sing
 Stream contract: the call is ordered behind the work queued so far on `torch.cuda.current_stream(device)` and returns once the
 outputs are written -- stream-ordered on entry, complete on return, not asynchronous.
 
+Forward and backward: `flow_video_fb` / `flow_pairs_fb` (include/papof.h: papof_flow_batch_tensor_fb) return both directions of
+every pair from one launch chain, and the occlusion mask of the forward-backward consistency check (Sundaram, Brox, Keutzer
+2010) computed from the float64 flows; `fb_consistency` is the same check on any two flow tensors.
+
+    fb = flow_video_fb(frames, 5, layout="NHWC")    # fb.flow_fw, fb.flow_bw, fb.warpI2_fw, fb.warpI2_bw, fb.occlusion, fb.timing
+
 torch is imported when a function is called, not when the package is imported.
 """
+import collections
 import ctypes
+import math
 import threading
 
 from . import capi
 
 LAYOUTS = ("NCHW", "NHWC")
+CONSISTENCY = (0.01, 0.5)  # (alpha1, alpha2) of Sundaram et al.
+
+FlowFB = collections.namedtuple("FlowFB", "flow_fw flow_bw warpI2_fw warpI2_bw occlusion timing")
 
 _lock = threading.Lock()
 _handles = {}  # device ordinal -> (Papof, lock of its calls)
@@ -116,21 +127,48 @@ def _handle(device):
         return _handles[device]
 
 
-def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver):
+def _alphas(consistency):
+    """(alpha1, alpha2) of a `consistency` argument: two finite numbers >= 0 (ValueError / TypeError otherwise)"""
+    try:
+        a1, a2 = consistency
+        a1, a2 = float(a1), float(a2)
+    except (TypeError, ValueError):
+        raise TypeError("consistency must be None or (alpha1, alpha2), got %r" % (consistency,)) from None
+    if not (math.isfinite(a1) and math.isfinite(a2) and a1 >= 0 and a2 >= 0):
+        raise ValueError("alpha1 and alpha2 must be finite and >= 0, got %r, %r" % (a1, a2))
+    return a1, a2
+
+
+def _index(dev):
+    return dev.index if dev.index is not None else _torch().cuda.current_device()
+
+
+def _outputs(n_pairs, H, W, C, layout, out_dtype, dev):
+    """a new flow tensor (B, 2, H, W) and warpI2 in `layout`, and their descriptors"""
     torch = _torch()
-    params = capi.default_params(**solver) if solver else None
-    (_, H, W, C), _, _ = descs[0]
-    dev = ts[0].device
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
     flow = torch.empty((n_pairs, 2, H, W), dtype=out_dtype, device=dev)
     if layout == "NCHW":
         warp = torch.empty((n_pairs, C, H, W), dtype=out_dtype, device=dev)
     else:
         warp = torch.empty((n_pairs, H, W, C), dtype=out_dtype, device=dev)
     out_code = capi.DTYPE_F32 if out_dtype == torch.float32 else capi.DTYPE_F64
+    return flow, warp, _struct(flow, (2 * H * W, W, 1, H * W), out_code), _struct(warp, descriptor(warp, layout)[1], out_code)
+
+
+def _mask(n_pairs, H, W, dev):
+    """a new uint8 mask (B, 2, H, W) -- channel 0 forward, 1 backward -- and its descriptor (pair, row, column, direction)"""
+    occ = _torch().empty((n_pairs, 2, H, W), dtype=_torch().uint8, device=dev)
+    return occ, _struct(occ, (2 * H * W, W, 1, H * W), capi.DTYPE_U8)
+
+
+def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver):
+    torch = _torch()
+    params = capi.default_params(**solver) if solver else None
+    (_, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    index = _index(dev)
+    flow, warp, d_flow, d_warp = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
-    d_flow = _struct(flow, (2 * H * W, W, 1, H * W), out_code)
-    d_warp = _struct(warp, descriptor(warp, layout)[1], out_code)
     t = (ctypes.c_double * capi.N_TIMERS)()
     gpu, lock = _handle(index)
     with lock, torch.cuda.device(index):
@@ -155,3 +193,84 @@ def flow_video(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, **solver
     Returns (flow (T - 1, 2, H, W), warpI2 (T - 1, ...) in `layout`, the reference's dict of ten timers)."""
     ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
     return _run(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, solver)
+
+
+def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, consistency, solver):
+    torch = _torch()
+    params = capi.default_params(**solver) if solver else None
+    (_, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    index = _index(dev)
+    flow_fw, warp_fw, d_flow_fw, d_warp_fw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
+    flow_bw, warp_bw, d_flow_bw, d_warp_bw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
+    occ, d_occ = _mask(n_pairs, H, W, dev) if consistency is not None else (None, None)
+    a1, a2 = consistency if consistency is not None else (0.0, 0.0)
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    t = (ctypes.c_double * capi.N_TIMERS)()
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_flow_batch_tensor_fb(gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+                                              None if sequence else ctypes.byref(d_in[1]), H, W, C, int(levels),
+                                              ctypes.byref(params) if params is not None else None, ctypes.byref(d_flow_fw),
+                                              ctypes.byref(d_warp_fw), ctypes.byref(d_flow_bw), ctypes.byref(d_warp_bw),
+                                              ctypes.byref(d_occ) if occ is not None else None, a1, a2,
+                                              ctypes.c_void_p(stream or None), t)
+    capi._chk(rc, "papof_flow_batch_tensor_fb")
+    return FlowFB(flow_fw, flow_bw, warp_fw, warp_bw, occ.view(torch.bool) if occ is not None else None,
+                  capi.format_timing(list(t)))
+
+
+def flow_pairs_fb(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """Both directions of the independent pairs (im1[i], im2[i]) in one launch chain, and their occlusion mask.
+    Returns FlowFB(flow_fw, flow_bw (B, 2, H, W), warpI2_fw, warpI2_bw (B, ...) in `layout`, occlusion, timing):
+    flow_fw / warpI2_fw are flow_pairs(im1, im2)'s, flow_bw / warpI2_bw flow_pairs(im2, im1)'s, bit for bit.  occlusion is a
+    torch.bool tensor (B, 2, H, W), channel 0 the forward pixels (of im1), 1 the backward ones (of im2), from the check with
+    consistency = (alpha1, alpha2) on the float64 flows (whatever out_dtype is) -- or None for consistency=None."""
+    alphas = _alphas(consistency) if consistency is not None else None
+    ts, descs, out_dtype = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels)
+    return _run_fb(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, solver)
+
+
+def flow_video_fb(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """Both directions of the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames in one launch chain -- each
+    frame's pyramid and features are built once for both -- and their occlusion mask: flow_pairs_fb on
+    (frames[:-1], frames[1:]), with T - 1 pairs."""
+    alphas = _alphas(consistency) if consistency is not None else None
+    ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
+    return _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, solver)
+
+
+def fb_consistency(flow_fw, flow_bw, alpha1=CONSISTENCY[0], alpha2=CONSISTENCY[1]):
+    """The forward-backward consistency check on two flow tensors (B, 2, H, W) of float32 or float64, any strides, on one
+    HIP device: a torch.bool tensor (B, 2, H, W), True where occluded -- channel 0 forward, 1 backward, as flow_video_fb's
+    occlusion, and the same mask for the same float64 flows (include/papof.h: papof_fb_check_tensor).  Enqueued on the
+    current stream; returns without waiting."""
+    torch = _torch()
+    a1, a2 = _alphas((alpha1, alpha2))
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    for n, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not isinstance(f, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (n, type(f).__name__))
+        if f.dim() != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+            raise ValueError("%s must be (B, 2, H, W) with B, H, W >= 1, got shape %s" % (n, tuple(f.shape)))
+        if f.dtype not in codes:
+            raise TypeError("%s must be float32 or float64, got %s" % (n, f.dtype))
+    if flow_fw.shape != flow_bw.shape:
+        raise ValueError("flow_fw %s and flow_bw %s differ in shape" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
+    if flow_fw.device != flow_bw.device:
+        raise ValueError("flow_fw is on %s, flow_bw on %s: both must be on one device" % (flow_fw.device, flow_bw.device))
+    if not _on_gpu(flow_fw):
+        raise ValueError("flows must be on a HIP device (cuda:N), got %s" % flow_fw.device)
+    B, _, H, W = (int(x) for x in flow_fw.shape)
+    dev = flow_fw.device
+    index = _index(dev)
+    d = [_struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), codes[f.dtype]) for f in (flow_fw, flow_bw)]
+    occ, d_occ = _mask(B, H, W, dev)
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_fb_check_tensor(gpu.h, B, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), a1, a2, ctypes.byref(d_occ),
+                                         ctypes.c_void_p(stream or None))
+    capi._chk(rc, "papof_fb_check_tensor")
+    return occ.view(torch.bool)
