@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 107 /* 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 108 /* 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -437,6 +437,42 @@ int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const
 int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,
                           const papof_tensor* flow_bw, double alpha1, double alpha2, const papof_tensor* occlusion,
                           void* stream);
+
+/* Point tracking through the flows of a video of n_frames = T frames (dense point trajectories, Sundaram, Brox, Keutzer
+ * 2010), one HIP kernel (track.hip: k_track) that follows every point through all T frames with its state in registers.
+ * flow_fw, flow_bw: the T - 1 pairs' flows as papof_fb_check_tensor takes them -- float32 (widened exactly) or float64,
+ * (pair, row, column, {vx, vy}), any non-negative strides; pair t runs from frame t to frame t + 1 (flow_fw[t]) and back
+ * (flow_bw[t]), as papof_flow_batch_tensor_fb returns them.
+ * queries: n_queries rows (t0, x, y) (CoTracker's convention), float32 or float64, stride[0] between points, stride[3]
+ * between t0, x and y; or NULL -- dense: every pixel of frame 0 in row-major order, N = height * width, point n =
+ * (0, n mod width, n div width).
+ * tracks: float64 (frame, point, -, {x, y}), stride[0] frames, stride[1] points, stride[3] x to y; visible: uint8 (frame,
+ * point, -, -), stride[0] frames, stride[1] points; other strides are ignored.  For each query:
+ *     frame t0: position (x, y) exactly, visible.
+ *     forward steps t -> t + 1 for t >= t0: f = flow_fw[t], b = flow_bw[t];
+ *     backward steps t -> t - 1 for t <= t0: f = flow_bw[t - 1], b = flow_fw[t - 1]  (a query mid-clip is tracked both ways).
+ * One step from a visible position (x, y), in fp64 without fused multiply-adds:
+ *     (u, v) = f sampled bilinearly at (x, y)  -- the rule of papof_fb_check_tensor (src/ImageProcessing.h:138-157):
+ *     (X, Y) = (x + u, y + v)                     truncation toward zero, fraction clamped to [0, 1], neighbours clamped
+ *                                                 into the image, taps accumulated from 0 in (m, n) order
+ *     lost if !(X >= 0 && X <= width - 1 && Y >= 0 && Y <= height - 1)                (NaN: lost)
+ *     use_check != 0 only:  (bu, bv) = b sampled bilinearly at (X, Y);
+ *                           e = (u + bu)^2 + (v + bv)^2;  m = (u^2 + v^2) + (bu^2 + bv^2);
+ *                           lost if !(e <= alpha1 * m + alpha2)                       (NaN: lost)
+ *     else the position at the next frame is (X, Y), visible.
+ * A point lost in one direction stays lost in that direction: its position is the quiet NaN 0x7ff8000000000000 in both
+ * coordinates and visible is 0.  A query is invalid -- that NaN and 0 at every frame -- where t0 is not an integer in
+ * [0, T - 1], x or y is not finite, or (x, y) lies outside [0, width - 1] x [0, height - 1]; the kernel decides it on the
+ * device.  At an integer position of finite flows the bilinear sample is the pixel's value, so in the dense mode visible[1]
+ * is papof_fb_check_tensor's forward mask of pair 0, negated, wherever the flows are finite.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting:
+ * ordered behind the work queued there so far, and ahead of what follows.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL descriptor (queries aside) or data pointer, flows or queries that are not
+ * float32 / float64, tracks that are not float64, visible that is not uint8, a negative stride or a zero stride of tracks
+ * or visible along an axis in use, n_frames < 2, height or width < 1, n_queries < 1 with queries given, a negative or non-finite alpha. */
+int papof_track_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* flow_fw,
+                       const papof_tensor* flow_bw, int n_queries, const papof_tensor* queries, int use_check, double alpha1,
+                       double alpha2, const papof_tensor* tracks, const papof_tensor* visible, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

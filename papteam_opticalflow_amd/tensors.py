@@ -20,6 +20,11 @@ every pair from one launch chain, and the occlusion mask of the forward-backward
 
     fb = flow_video_fb(frames, 5, layout="NHWC")    # fb.flow_fw, fb.flow_bw, fb.warpI2_fw, fb.warpI2_bw, fb.occlusion, fb.timing
 
+Point tracks: `track_points` (include/papof.h: papof_track_tensor) follows points through a video's forward and backward flows
+in one HIP kernel, dropping a point where the forward-backward check fails; `track_video` is flow_video_fb followed by it.
+
+    tv = track_video(frames, 5, queries, layout="NHWC")   # queries (N, 3) rows (t0, x, y); tv.tracks (T, N, 2), tv.visible (T, N)
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -33,6 +38,8 @@ LAYOUTS = ("NCHW", "NHWC")
 CONSISTENCY = (0.01, 0.5)  # (alpha1, alpha2) of Sundaram et al.
 
 FlowFB = collections.namedtuple("FlowFB", "flow_fw flow_bw warpI2_fw warpI2_bw occlusion timing")
+Tracks = collections.namedtuple("Tracks", "tracks visible")
+TrackVideo = collections.namedtuple("TrackVideo", "tracks visible flow_fw flow_bw timing")
 
 _lock = threading.Lock()
 _handles = {}  # device ordinal -> (Papof, lock of its calls)
@@ -274,3 +281,100 @@ def fb_consistency(flow_fw, flow_bw, alpha1=CONSISTENCY[0], alpha2=CONSISTENCY[1
                                          ctypes.c_void_p(stream or None))
     capi._chk(rc, "papof_fb_check_tensor")
     return occ.view(torch.bool)
+
+
+def _check_queries(queries, dev):
+    """queries: None (dense) or an (N, 3) float32 / float64 tensor with N >= 1 on `dev` -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    if queries is None:
+        return None
+    if not isinstance(queries, torch.Tensor):
+        raise TypeError("queries must be None or a torch.Tensor, got %s" % type(queries).__name__)
+    if queries.dim() != 2 or queries.shape[1] != 3 or queries.shape[0] < 1:
+        raise ValueError("queries must be (N, 3) rows (t0, x, y) with N >= 1, got shape %s" % (tuple(queries.shape),))
+    if queries.dtype not in (torch.float32, torch.float64):
+        raise TypeError("queries must be float32 or float64, got %s" % queries.dtype)
+    if queries.device != dev:
+        raise ValueError("queries are on %s, the flows on %s: both must be on one device" % (queries.device, dev))
+    return queries
+
+
+def _check_flows(flow_fw, flow_bw):
+    """every argument error of a (T - 1, 2, H, W) flow pair, before anything is launched: their dtype codes"""
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    for n, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not isinstance(f, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (n, type(f).__name__))
+        if f.dim() != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+            raise ValueError("%s must be (T - 1, 2, H, W) with T - 1, H, W >= 1, got shape %s" % (n, tuple(f.shape)))
+        if f.dtype not in codes:
+            raise TypeError("%s must be float32 or float64, got %s" % (n, f.dtype))
+    if flow_fw.shape != flow_bw.shape:
+        raise ValueError("flow_fw %s and flow_bw %s differ in shape" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
+    if flow_fw.device != flow_bw.device:
+        raise ValueError("flow_fw is on %s, flow_bw on %s: both must be on one device" % (flow_fw.device, flow_bw.device))
+    if not _on_gpu(flow_fw):
+        raise ValueError("flows must be on a HIP device (cuda:N), got %s" % flow_fw.device)
+    return codes[flow_fw.dtype], codes[flow_bw.dtype]
+
+
+def _track(flow_fw, flow_bw, codes, queries, alphas):
+    torch = _torch()
+    T, H, W = int(flow_fw.shape[0]) + 1, int(flow_fw.shape[2]), int(flow_fw.shape[3])
+    N = int(queries.shape[0]) if queries is not None else H * W
+    dev = flow_fw.device
+    index = _index(dev)
+    d = [_struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), c) for f, c in zip((flow_fw, flow_bw), codes)]
+    d_q = None
+    if queries is not None:
+        q_code = capi.DTYPE_F32 if queries.dtype == torch.float32 else capi.DTYPE_F64
+        d_q = _struct(queries, (queries.stride(0), 0, 0, queries.stride(1)), q_code)
+    tracks = torch.empty((T, N, 2), dtype=torch.float64, device=dev)
+    vis = torch.empty((T, N), dtype=torch.uint8, device=dev)
+    d_tr = _struct(tracks, (tracks.stride(0), tracks.stride(1), 0, tracks.stride(2)), capi.DTYPE_F64)
+    d_vis = _struct(vis, (vis.stride(0), vis.stride(1), 0, 0), capi.DTYPE_U8)
+    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_track_tensor(gpu.h, T, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), N if d_q is not None else 0,
+                                      ctypes.byref(d_q) if d_q is not None else None, 0 if alphas is None else 1, a1, a2,
+                                      ctypes.byref(d_tr), ctypes.byref(d_vis), ctypes.c_void_p(stream or None))
+    capi._chk(rc, "papof_track_tensor")
+    return Tracks(tracks, vis.view(torch.bool))
+
+
+def track_points(flow_fw, flow_bw, queries=None, *, consistency=CONSISTENCY):
+    """Follow points through the flows of a video of T frames: flow_fw, flow_bw (T - 1, 2, H, W) float32 or float64 on one
+    HIP device, any strides -- pair t from frame t to t + 1 and back, as flow_video_fb returns them.  queries: (N, 3) rows
+    (t0, x, y) of float32 / float64 on the flows' device, each tracked forward from frame t0 and backward to frame 0; None:
+    every pixel of frame 0, row-major (N = H * W, point n = (0, n % W, n // W)).  Returns Tracks(tracks (T, N, 2) float64
+    (x, y), visible (T, N) torch.bool).  A step moves a visible point by the forward flow sampled bilinearly where it is;
+    the point is lost where it leaves the image or -- consistency = (alpha1, alpha2); None: no check -- where the backward
+    flow sampled where it lands does not bring it back (the test of fb_consistency).  A lost point stays lost in that
+    direction: its position is NaN (0x7ff8000000000000) and visible False; an invalid query (t0 not an integer in [0, T - 1],
+    (x, y) not a finite point of the image) is lost at every frame.  include/papof.h (papof_track_tensor) states it exactly.
+    Enqueued on the current stream; returns without waiting.
+
+    A long video in chunks: let the chunks overlap by one frame, and pass the last frame's positions as t0 = 0 queries of
+    the next chunk -- torch.cat([torch.zeros(N, 1, dtype=torch.float64, device=dev), tracks[-1]], 1): a point lost so far is
+    NaN there, an invalid query, and stays lost."""
+    alphas = _alphas(consistency) if consistency is not None else None
+    codes = _check_flows(flow_fw, flow_bw)
+    queries = _check_queries(queries, flow_fw.device)
+    return _track(flow_fw, flow_bw, codes, queries, alphas)
+
+
+def track_video(frames, pyramidLevels, queries=None, *, layout="NCHW", consistency=CONSISTENCY, **solver):
+    """Flow and point tracks of a video of T >= 2 frames: flow_video_fb(frames, pyramidLevels, layout=layout,
+    consistency=None, **solver) -- both float64 flows of every pair in one launch chain -- followed by track_points on
+    them.  Returns TrackVideo(tracks (T, N, 2), visible (T, N), flow_fw, flow_bw (T - 1, 2, H, W), timing of the flow call).
+    Every argument error raises before anything is launched; the flows are complete on return, the tracks are enqueued on
+    the current stream behind them."""
+    alphas = _alphas(consistency) if consistency is not None else None
+    ts, descs, out_dtype = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    queries = _check_queries(queries, ts[0].device)
+    fb = _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, None, solver)
+    tr = _track(fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), queries, alphas)
+    return TrackVideo(tr.tracks, tr.visible, fb.flow_fw, fb.flow_bw, fb.timing)
