@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 108 /* 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 109 /* 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -332,8 +332,8 @@ int papof_bench_sor(papof_handle* h, int height, int width, int n_sor, int sor_m
 int papof_sor_plan(papof_handle* h, int height, int width, int n_sor, int sor_mode, int* launches, int* depth);
 
 /* Measurement aid for bench.py: what the LAST papof_flow* / papof_seq_push* call on this handle launched -- exact-order
- * solver kernels in all (a level solved as strips of bands issues one launch per strip and solve), and how many
- * seconds of the reported Phase5_SOR are launches on the strip streams, i.e. ran beside the main stream's time line. */
+ * solver kernels in all.  *strip_streams_sec is always 0: it was the share of Phase5_SOR that ran on the strip streams,
+ * and the strips schedule is gone (the argument stays for the ABI). */
 int papof_last_sor_stats(papof_handle* h, int* launches, double* strip_streams_sec);
 
 /* Measurement aid for bench.py (roofline.by_level / by_kernel): the solves of the LAST papof_flow* / papof_seq_push* call on
@@ -479,19 +479,11 @@ int papof_track_tensor(papof_handle* h, int n_frames, int height, int width, con
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */
 int papof_last_host_times(papof_handle* h, double out[3]);
 
-/* Test aid: the strip schedule (api.hip: smooth_flow_strips) a level of height x width with `n_sor` sweeps and
- * `n_outer` outer iterations gets on this handle.  *strips = S (1: the level is not cut).  out, if not NULL, receives
- * for n = 0 .. n_outer and s = 0 .. S five ints each -- first band, first row of the update / phi / smoothing / assembly
- * stage of strip s before solve n -- (n_outer + 1) * (S + 1) * 5 ints (cap = ints available); *band_rows, *koff: rows
- * per band and climb of the bands up to the last sweep of the bound solver layout. */
-int papof_strip_plan(papof_handle* h, int height, int width, int n_sor, int n_outer, int want_strips, int* strips,
-                     int* out, int cap, int* band_rows, int* koff, int* bands);
-
 /* Test aid: one exact-order solve of `n_sor` sweeps on synthetic height x width planes (the micro-benchmark's), once
- * whole and `reps` times as two strips of solver bands -- bands < split_band on a second stream, the rest `delay_us`
- * microseconds later on the handle's stream (sor.hip: sor_solve_bands).  *mismatches = 16-byte cells of the solver's
+ * whole and `reps` times as two band launches on two streams -- bands < split_band on a stream of the call's own, the
+ * rest `delay_us` microseconds later on the handle's stream (sor.hip: sor_solve_bands).  *mismatches = 16-byte cells of the solver's
  * (du, dv) planes, intermediate sweeps included, that differ from the whole solve's (0 expected); *bands = bands of the
- * layout.  PAPOF_EINVAL when this layout cannot be solved in strips (<= 8 bands, < 3 sweeps, split out of range). */
+ * layout.  PAPOF_EINVAL when this layout cannot be solved in band ranges (<= 8 bands, < 3 sweeps, split out of range). */
 int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int split_band, int reps, int delay_us,
                           long long* mismatches, int* bands);
 

@@ -427,207 +427,7 @@ int smooth_flow(papof_handle* h, const double* f1, const double* f2, double* war
     return PAPOF_OK;
 }
 
-// =================================================================================================
-// STRIPS: one level of the exact-order path as S horizontal strips, each on its own stream.
-//
-// The exact-order solve is a wave front: band b starts one band hop (63 steps + a hand-off) after band b-1 and finishes
-// as much later, so the top of the plane is final long before the bottom, and the bottom bands of the NEXT solve could
-// not start before the top ones anyway.  A level is therefore cut into strips of solver bands; per outer iteration a
-// strip's chain is [update + warp + phi] -> [smoothing + blend] -> [assembly] -> [its bands of the solve], enqueued on
-// the strip's own stream.  The non-solver kernels of the upper strips run while the lower strips still solve, the
-// non-solver kernels of the lowest strip while the upper strips' next solve climbs its ramp: the same kernels, the
-// same operations per pixel, only the row ranges and the order in time differ (results are bit-identical).
-//
-// Row ranges.  A stage whose stencil reaches h rows further down than its output can only be run on rows whose inputs
-// are final, so the boundary between strip s-1 and strip s moves UP from stage to stage: with F = the first row whose
-// final (du, dv) lies in the first band of strip s, the update kernel of strip s-1 ends at F - 1 (phi of row i reads
-// row i + 1), the smoothing at F - 3 (5 x 5), the assembly at F - 5 (5-point derivatives of the blend), and the next
-// solve's boundary is the last band boundary at or above that row: boundaries move up by one band per solve (two when the
-// sweep count exceeds 57).  The strip below starts each stage where the strip above ended; what it reads across the
-// boundary is ordered by ONE event per iteration (recorded behind the upper strip's assembly).  Inside a solve the
-// strips meet through the solver's progress counters (sor.hip: sor_solve_bands).  Dependencies between stages point
-// from upper to lower strips only -- except the solver's write-after-read guard, which keeps an upper strip within two
-// sweeps per band of the strip below.
-// =================================================================================================
-struct LevelInit {  // how the level's initial flow and warp come about (src/OpticalFlow.cpp:801-816)
-    bool coarsest;          // u = v = 0 and warp = frame 2's features: already enqueued by the caller
-    const double *pu, *pv;  // else: the coarser level's flow, up-sampled and scaled per strip, then warped
-    int ph, pw;
-    double xr, yr, inv;
-};
-
-struct StripSchedule {
-    int S = 1, n_solves = 0;
-    // per solve n = 0 .. n_solves (n_solves = the final update) and boundary s = 0 .. S: first band of strip s in solve n
-    // (beta), first row of strip s in the update / warp stage (rU), phi (rP), smoothing (rS), assembly (rA)
-    std::vector<int> beta, rU, rP, rS, rA;
-    int idx(int n, int s) const { return n * (S + 1) + s; }
-};
-
-bool plan_strips(const papof_handle* h, const SorPlanes& sp, int H, int n_sor, int n_solves, int want,
-                 StripSchedule& out) {
-    if (want < 2 || n_solves < 1 || !sor_strips_supported(h, sp, n_sor)) return false;
-    const int BR = sp.sd.band_rows, koff = sp.sd.koff, nb = sp.sd.nb;
-    const int d = (koff + 5 + BR - 1) / BR;  // bands a boundary moves up per solve
-    for (int S = std::min(want, 4); S >= 2; --S) {
-        StripSchedule q;
-        q.S = S;
-        q.n_solves = n_solves;
-        const size_t cells = (size_t)(n_solves + 1) * (S + 1);
-        q.beta.assign(cells, 0);
-        q.rU.assign(cells, 0);
-        q.rP.assign(cells, 0);
-        q.rS.assign(cells, 0);
-        q.rA.assign(cells, 0);
-        // boundaries of the first solve: even shares of the bands, moved down by half of what they will climb
-        std::vector<int> b0(S + 1, 0);
-        b0[S] = nb;
-        int top = std::min(nb - 1, (H - 6) / BR);  // the last boundary's first stage (row BR * beta + 4) lies inside the plane
-        for (int s = S - 1; s >= 1; --s) {
-            b0[s] = std::min(top, (s * nb + S / 2) / S + d * (n_solves - 1) / 2);
-            top = b0[s] - 1;
-        }
-        bool ok = true;
-        for (int n = 0; n <= n_solves && ok; n++) {
-            for (int s = 0; s <= S; s++) {
-                const int i = q.idx(n, s);
-                if (s == 0 || s == S) {
-                    q.beta[i] = s == 0 ? 0 : nb;
-                    q.rU[i] = q.rP[i] = q.rS[i] = q.rA[i] = s == 0 ? 0 : H;
-                    continue;
-                }
-                if (n == 0) {
-                    q.beta[i] = b0[s];
-                    q.rU[i] = BR * b0[s] + 4;
-                    q.rP[i] = q.rU[i] - 1;
-                } else {
-                    const int fin = BR * q.beta[q.idx(n - 1, s)] - koff;  // first row finalised by the strip's first band
-                    q.rU[i] = fin - 1;
-                    q.rP[i] = q.rU[i];
-                }
-                q.rS[i] = q.rU[i] - 2;
-                q.rA[i] = q.rU[i] - 4;
-                if (n > 0) q.beta[i] = q.rA[i] >= 0 ? q.rA[i] / BR : 0;
-                if (n == n_solves) q.beta[i] = q.beta[q.idx(n - 1, s)];  // no solve follows the final update
-            }
-            for (int s = 1; s <= S && ok; s++) {
-                const int i = q.idx(n, s), j = q.idx(n, s - 1);
-                ok = q.beta[i] > q.beta[j] && q.rU[i] > q.rU[j] && q.rA[i] > q.rA[j] && q.rS[i] > q.rS[j] &&
-                     q.rP[i] > q.rP[j] && q.rA[i] >= 0 && q.rU[i] <= H;
-            }
-        }
-        if (ok) {
-            out = q;
-            return true;
-        }
-    }
-    return false;
-}
-
-hipEvent_t strip_event(papof_handle* h) {
-    if (h->strip_events_used == h->strip_events.size()) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        h->strip_events.push_back(e);
-    }
-    return h->strip_events[h->strip_events_used++];
-}
-
-int smooth_flow_strips(papof_handle* h, const StripSchedule& q, const LevelInit& li, const double* f1, const double* f2,
-                       double* warp, double*& u, double*& v, double*& ua, double*& va, int H, int W, int fc, double alpha,
-                       int n_sor, double omega, SolveBuffers& B, PhaseClock& clk, PhaseClock& uclk, const double* im1s,
-                       unsigned* prog, size_t prog_per_solve, double* out_u, double* out_v) {
-    const int S = q.S, n_outer = q.n_solves;
-    if (S < 2 || (int)h->strip_streams.size() < S - 1 || !im1s || !prog) return PAPOF_EINVAL;
-    hipStream_t const main_stream = h->stream;
-    const auto stream_of = [&](int s) { return s == S - 1 ? main_stream : h->strip_streams[s]; };
-    struct StreamSwap {
-        papof_handle* h;
-        hipStream_t saved;
-        StreamSwap(papof_handle* hh, hipStream_t s) : h(hh), saved(hh->stream) { h->stream = s; }
-        ~StreamSwap() { h->stream = saved; }
-    };
-    clk.phase(PAPOF_T_ALLOCATION);
-    hipEvent_t const fork = strip_event(h);  // (the counters of every solve were cleared before the streams fork: `prog`)
-    if (!fork) return PAPOF_EDEVICE;
-    PAPOF_HIP(hipEventRecord(fork, main_stream));
-    PAPOF_HIP(hipStreamWaitEvent(stream_of(0), fork, 0));  // strip s > 0 waits for strip s - 1 in every iteration
-    std::vector<hipEvent_t> done(S, nullptr);
-    const auto sor_on_main = [](void* c, int on) {
-        static_cast<PhaseClock*>(c)->phase(on ? PAPOF_T_PHASE5_SOR : PAPOF_T_PHASE6_UPDATE);
-    };
-    const auto sor_on_strip = [](void* c, int on) { static_cast<PhaseClock*>(c)->phase(on ? PAPOF_T_PHASE5_SOR : -1); };
-    for (int n = 0; n <= n_outer; n++) {
-        const bool last = n == n_outer;
-        for (int s = 0; s < S; s++) {
-            StreamSwap on_strip(h, stream_of(s));
-            const bool crit = s == S - 1;  // the lowest strip's chain (main stream) carries the stamped phase timers
-            if (s > 0) PAPOF_HIP(hipStreamWaitEvent(h->stream, done[s - 1], 0));
-            const int i0 = q.idx(n, s), i1 = q.idx(n, s + 1);
-            const Rect ru{0, q.rU[i0], W, q.rU[i1]}, rp{0, q.rP[i0], W, q.rP[i1]}, ra{0, q.rA[i0], W, q.rA[i1]};
-            const double *un = u, *vn = v;  // the flow the assembly reads
-            if (n == 0) {
-                if (!li.coarsest) {  // src/OpticalFlow.cpp:809-814
-                    if (crit) clk.phase(PAPOF_T_ALLOCATION);
-                    PAPOF_TRY(resize(h, li.pu, u, li.ph, li.pw, 1, H, W, li.xr, li.yr, true, li.inv, &ru));
-                    PAPOF_TRY(resize(h, li.pv, v, li.ph, li.pw, 1, H, W, li.xr, li.yr, true, li.inv, &ru));
-                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, H, W, fc, &ru));
-                }
-                if (crit) clk.phase(PAPOF_T_PHASE2_DERIVATIVES);
-                PAPOF_TRY(compute_phi(h, u, v, nullptr, B.phi, H, W, &rp));
-            } else {  // Phase6 of iteration n - 1 with the phi of iteration n folded in (the main chain's Phase6 was
-                      // opened by its solver's end mark)
-                double* const wu = last && out_u && out_v ? out_u : ua;
-                double* const wv = last && out_u && out_v ? out_v : va;
-                PAPOF_TRY(update_warp_phi(h, B.sp, u, v, wu, wv, f1, f2, warp, last ? nullptr : B.phi, H, W, fc, !last,
-                                          ru.y0, ru.y1));
-                un = wu;
-                vn = wv;
-            }
-            if (!last) {
-                if (crit) clk.phase(PAPOF_T_PHASE1_GENERATE);
-                PAPOF_TRY(smooth_hv_blend(h, warp, im1s, B.blend, B.imdt, H, W, fc, q.rS[i0], q.rS[i1]));
-                if (crit) clk.phase(PAPOF_T_PHASE4_LINEARSYSTEM);
-                PAPOF_TRY(assemble_system(h, B.blend, B.imdt, B.phi, un, vn, H, W, fc, alpha, omega, B.sp, nullptr, nullptr,
-                                          nullptr, &ra, nullptr));
-            }
-            if (!crit) {
-                done[s] = strip_event(h);
-                if (!done[s]) return PAPOF_EDEVICE;
-                PAPOF_HIP(hipEventRecord(done[s], h->stream));
-            }
-            if (!last) {
-                h->sor_mark = crit ? +sor_on_main : +sor_on_strip;
-                h->sor_mark_ctx = crit ? &clk : &uclk;
-                const int rc = sor_solve_bands(h, B.sp, H, W, alpha, omega, n_sor, prog + (size_t)n * prog_per_solve,
-                                               q.beta[i0], q.beta[i1]);
-                h->sor_mark = nullptr;
-                h->sor_mark_ctx = nullptr;
-                PAPOF_TRY(rc);
-            }
-        }
-        if (n == n_outer && out_u && out_v) {
-            u = out_u;
-            v = out_v;
-        } else if (n > 0) {
-            std::swap(u, ua);
-            std::swap(v, va);
-        }
-    }
-    // join: the final update of strip S - 2 waited for strip S - 3's, and so on -- and the main stream for S - 2's
-    clk.phase(-1);
-    return PAPOF_OK;
-}
-
 int feature_channels(int C) { return C == 3 ? 5 : (C == 1 ? 3 : C); }
-
-void ensure_strip_streams(papof_handle* h) {  // without them levels are simply not cut
-    while (h->strip_streams.size() < 3) {
-        hipStream_t ss = nullptr;
-        if (hipStreamCreateWithFlags(&ss, hipStreamNonBlocking) != hipSuccess) break;
-        h->strip_streams.push_back(ss);
-    }
-}
 
 // An interleaved HWC frame resident on the device: fp64 in [0,1] (the reference's buffers) or the decoded uint8
 // samples, which are scaled by 1/255 while they are planarised (OpticalFlowCalculation.py:69-70).
@@ -775,12 +575,8 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     PhaseClock pclk{h, !in_capture};
     PhaseClock total{h, !in_capture};
     clk.only_sor = pclk.only_sor = (!h->phase_events && P.phase_timing == 0) || P.phase_timing == 2;
-    PhaseClock uclk{h, !in_capture};  // solver launches of the upper strips (smooth_flow_strips): events on their streams
-    uclk.only_sor = true;
-    h->strip_events_used = 0;
     h->sor_launches = 0;
     h->sor_log.clear();
-    h->sor_upper_sec = 0.0;
     clk.stamps = true;  // the main stream's phase boundaries are in-kernel stamps, not events (flow_internal.h)
     h->stamps_used = 0;
     h->next_stamp = nullptr;
@@ -807,21 +603,11 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         abandon_capture();
         return PAPOF_ENOMEM;
     }
-    const auto keep = [&](int slot) {
-        h->seq.valid = true;
-        h->seq.h = H;
-        h->seq.w = W;
-        h->seq.c = C;
-        h->seq.levels = levels;
-        h->seq.ratio = ratio;
-        h->seq.slot = slot;
-        h->seq.arena_base = A.base;
-    };
     if (op == kSeqPrime) {
         PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
         PAPOF_TRY(build_pyramid(h, L, plan, C, false, tmp_a, tmp_b));
         PAPOF_HIP(hipStreamSynchronize(h->stream));
-        keep(slot1);
+        keep_seq(slot1);
         if (timing) std::memset(timing, 0, tm_bytes);
         return PAPOF_OK;
     }
@@ -845,9 +631,6 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     double* warp = A.f64(np0 * fc);
     // the flow lives in two PAIRS of planes (the update of an outer iteration writes the other pair); within a pair v follows
     // u at the pitch of the level in work, so that the up-sampling of (u, v) is one launch and their first clear one fill
-    // [a handle that cuts levels into strips (PAPOF_STRIPS, an A/B switch) keeps the full-resolution pitch on every level: its
-    // strips read the previous level's pair while they write this level's, row range by row range]
-    const bool paired = h->strips <= 1;
     double* u = A.f64(2 * np0);
     double* v = u ? u + np0 : nullptr;
     double* u2 = A.f64(2 * np0);
@@ -908,6 +691,18 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         StreamSwap(papof_handle* hh, hipStream_t s) : h(hh), saved(hh->stream) { h->stream = s; }
         ~StreamSwap() { h->stream = saved; }
     };
+    // pyramid levels coarsest first when every level is derived from level 0 (<= 5 levels at ratio 0.75,
+    // src/GaussianPyramid.cpp:95-100); deeper pyramids chain through finer levels (:101-106): build those in order
+    bool from_level0 = true;
+    for (int i = 1; i < levels; i++) from_level0 = from_level0 && plan[i].src_level == 0;
+    const Taps g5 = smooth5_taps();
+    const auto build_level = [&](int i, int second) -> int {  // level i of frame 1 (second == 0) or frame 2
+        if (i == 0) return PAPOF_OK;
+        const PyrPlan& q = plan[i];
+        const double* src = second ? L[q.src_level].p2 : L[q.src_level].p1;
+        double* dst = second ? L[i].p2 : L[i].p1;
+        return smooth_and_resize(h, src, dst, tmp_a, tmp_b, q, C, L[i].h, L[i].w);
+    };
     const auto prepare = [&]() -> int {
         StreamSwap on_prep(h, prep);
         pclk.phase(PAPOF_T_ALLOCATION);  // the reference's buffers are zero-filled when they are allocated (src/Image.h:518-532)
@@ -915,27 +710,14 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         pclk.phase(PAPOF_T_CONSTRUCTION);  // src/OpticalFlow.cpp:757-758 (and the wrapper's copies, Coarse2FineFlowWrapper.cpp:23-28)
         if (op != kSeqNext) PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
         PAPOF_TRY(load_frame(h, fb, L[0].p2, H, W, C));
-        // pyramid levels coarsest first when every level is derived from level 0 (<= 5 levels at ratio 0.75,
-        // src/GaussianPyramid.cpp:95-100); deeper pyramids chain through finer levels (:101-106): build those in order
-        bool from_level0 = true;
-        for (int i = 1; i < levels; i++) from_level0 = from_level0 && plan[i].src_level == 0;
-        const Taps g5 = smooth5_taps();
-        const auto build_level = [&](int i) -> int {
-            if (i == 0) return PAPOF_OK;
-            const PyrPlan& q = plan[i];
-            for (int second = (op == kSeqNext ? 1 : 0); second < 2; second++) {
-                const double* src = second ? L[q.src_level].p2 : L[q.src_level].p1;
-                double* dst = second ? L[i].p2 : L[i].p1;
-                PAPOF_TRY(smooth_and_resize(h, src, dst, tmp_a, tmp_b, q, C, L[i].h, L[i].w));
-            }
-            return PAPOF_OK;
-        };
+        const int first = op == kSeqNext ? 1 : 0;  // a sequence push keeps frame 1's pyramid
         if (!from_level0)
-            for (int i = 1; i < levels; i++) PAPOF_TRY(build_level(i));
+            for (int i = 1; i < levels; i++)
+                for (int second = first; second < 2; second++) PAPOF_TRY(build_level(i, second));
         for (int k = levels - 1; k >= 0; k--) {
             if (from_level0) {
                 pclk.phase(PAPOF_T_CONSTRUCTION);
-                PAPOF_TRY(build_level(k));
+                for (int second = first; second < 2; second++) PAPOF_TRY(build_level(k, second));
             }
             pclk.phase(PAPOF_T_ALLOCATION);  // im2feature is inside the reference's Allocation timer (:797-798)
             PAPOF_TRY(im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C, lg ? lg->nz(k) : nullptr));
@@ -964,16 +746,6 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         hipStream_t const cs = h->copy_stream;
         pclk.phase(PAPOF_T_ALLOCATION);
         if (exact && !sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
-        bool from_level0 = true;
-        for (int i = 1; i < levels; i++) from_level0 = from_level0 && plan[i].src_level == 0;
-        const Taps g5 = smooth5_taps();
-        const auto build_level = [&](int i, int second) -> int {
-            if (i == 0) return PAPOF_OK;
-            const PyrPlan& q = plan[i];
-            const double* src = second ? L[q.src_level].p2 : L[q.src_level].p1;
-            double* dst = second ? L[i].p2 : L[i].p1;
-            return smooth_and_resize(h, src, dst, tmp_a, tmp_b, q, C, L[i].h, L[i].w);
-        };
         // ---- frame 1: upload (this call may hold the host until the bytes are staged), then its whole share
         if (io.im1) {
             PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(fa.d), io.im1, io.nb_in, hipMemcpyHostToDevice, cs));
@@ -1029,14 +801,10 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     {
         const int rc = hostio ? prepare_hostio() : prepare();
         if (rc != PAPOF_OK) {
-            if (in_capture) {
-                hipGraph_t graph = nullptr;
-                hipStreamEndCapture(main_stream, &graph);
-                if (graph) hipGraphDestroy(graph);
-                h->use_graph = false;
-            } else if (overlap) {
+            if (in_capture)
+                abandon_capture();
+            else if (overlap)
                 hipStreamSynchronize(prep);
-            }
             return rc;
         }
     }
@@ -1061,60 +829,32 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
             // the level's result goes straight to the caller's buffers on the finest level
             double* const out_u = k == 0 ? d_vx : nullptr;
             double* const out_v = k == 0 ? d_vy : nullptr;
-            // strips (smooth_flow_strips): big levels of the exact-order path, default branches, overlapping streams allowed
-            StripSchedule sch;
-            // OFF by default (PAPOF_STRIPS=2..4 enables): measured slower on every level it applies to
-            const int want = h->strips > 1 ? h->strips : 1;
-            const bool strips = overlap && (int)h->strip_streams.size() >= 3 && P.sor_mode == PAPOF_SOR_EXACT &&
-                                P.n_inner == 1 && !B.bgx && !B.gm && want >= 2 && !tiny_k &&
-                                plan_strips(h, B.sp, lh, n_sor_k, n_outer_k, want, sch);
-            LevelInit li{k == levels - 1, nullptr, nullptr, ph, pw, 0.0, 0.0, 1 / ratio};
-            const bool fold_warp = !strips && !B.bgx && !B.gm;  // the warped frame 2 lives only inside the smoothing kernel
+            const bool fold_warp = !B.bgx && !B.gm;  // the warped frame 2 lives only inside the smoothing kernel
             if (k == levels - 1) {  // src/OpticalFlow.cpp:801-806
-                if (paired) {
-                    v = u + np;
-                    v2 = u2 + np;
-                    PAPOF_HIP(hipMemsetAsync(u, 0, 2 * np * sizeof(double), h->stream));
-                } else {
-                    PAPOF_HIP(hipMemsetAsync(u, 0, np * sizeof(double), h->stream));
-                    PAPOF_HIP(hipMemsetAsync(v, 0, np * sizeof(double), h->stream));
-                }
+                v = u + np;
+                v2 = u2 + np;
+                PAPOF_HIP(hipMemsetAsync(u, 0, 2 * np * sizeof(double), h->stream));
                 if (!fold_warp)
                     PAPOF_HIP(hipMemcpyAsync(warp, f2, np * fc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
                 if (B.bgx) PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
             } else {  // :809-816
                 const double xr = (double)lw / pw, yr = (double)lh / ph, inv = 1 / ratio;
-                if (paired) v2 = u2 + np;  // the pair that receives this level's flow, at this level's pitch
-                if (strips) {  // up-sampling and warp happen per strip
-                    li.pu = u;
-                    li.pv = v;
-                    li.xr = xr;
-                    li.yr = yr;
-                } else if (paired) {
-                    PAPOF_TRY(resize(h, u, u2, ph, pw, 2, lh, lw, xr, yr, true, inv));  // u and v: two planes of one launch
-                } else {
-                    PAPOF_TRY(resize(h, u, u2, ph, pw, 1, lh, lw, xr, yr, true, inv));
-                    PAPOF_TRY(resize(h, v, v2, ph, pw, 1, lh, lw, xr, yr, true, inv));
-                }
+                // u and v: two planes of one launch, into the free pair at this level's pitch
+                PAPOF_TRY(resize(h, u, u2, ph, pw, 2, lh, lw, xr, yr, true, inv));
                 std::swap(u, u2);
-                std::swap(v, v2);
-                if (paired) v2 = u2 + np;  // the free pair, at this level's pitch too
-                if (strips || fold_warp) {
-                } else if (!B.bgx) {
-                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc));
-                } else {  // interpolation == Bicubic (:816): warpImageBicubicRef, no threshold here
+                v = u + np;
+                v2 = u2 + np;  // the free pair, at this level's pitch too
+                if (B.bgx) {  // interpolation == Bicubic (:816): warpImageBicubicRef, no threshold here
                     PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
                     PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, u, v, warp, lh, lw, fc, nullptr, true, false));
+                } else if (!fold_warp) {
+                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc));
                 }
             }
             if (!tiny_k) PAPOF_TRY(sor_reset_planes(h, B.sp));
-            if (strips)
-                PAPOF_TRY(smooth_flow_strips(h, sch, li, f1, f2, warp, u, v, u2, v2, lh, lw, fc, P.alpha, n_sor_k, P.omega, B,
-                                             clk, uclk, S1[k], prog_k, LP[k].prog_per, out_u, out_v));
-            else
-                PAPOF_TRY(smooth_flow(h, f1, f2, warp, u, v, u2, v2, lh, lw, fc, P.alpha, n_outer_k, P.n_inner, n_sor_k,
-                                      P.omega, P.sor_mode, B, clk, S1[k], false, prog_k, exact ? LP[k].prog_per : 0, out_u,
-                                      out_v, fold_warp, lg, k));
+            PAPOF_TRY(smooth_flow(h, f1, f2, warp, u, v, u2, v2, lh, lw, fc, P.alpha, n_outer_k, P.n_inner, n_sor_k, P.omega,
+                                  P.sor_mode, B, clk, S1[k], false, prog_k, exact ? LP[k].prog_per : 0, out_u, out_v,
+                                  fold_warp, lg, k));
             pw = lw;
             ph = lh;
         }
@@ -1163,7 +903,6 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         return rc_main != PAPOF_OK ? rc_main : PAPOF_EDEVICE;
     }
     if (rc_main != PAPOF_OK) {  // never leave work of this call running on any stream
-        for (hipStream_t ss : h->strip_streams) hipStreamSynchronize(ss);
         hipStreamSynchronize(main_stream);
         if (overlap) hipStreamSynchronize(prep);
         return rc_main;
@@ -1191,16 +930,8 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     clk.collect(tm);
     pclk.collect(tm);
     total.collect(tm);
-    if (clk.sor_span_sec.size() == h->sor_log.size())  // one span per solve (not when a level ran as strips)
+    if (clk.sor_span_sec.size() == h->sor_log.size())  // one span per solve
         for (size_t i = 0; i < h->sor_log.size(); i++) h->sor_log[i].sec = clk.sor_span_sec[i];
-    if (uclk.err != PAPOF_OK) return PAPOF_EDEVICE;
-    {   // Phase5_SOR = the solver kernels' own time, all strips (on the main chain's time line only the lowest strip's)
-        double tu[PAPOF_N_TIMERS + 1];
-        std::memset(tu, 0, sizeof tu);
-        uclk.collect(tu);
-        h->sor_upper_sec = tu[PAPOF_T_PHASE5_SOR];
-        tm[PAPOF_T_PHASE5_SOR] += tu[PAPOF_T_PHASE5_SOR];
-    }
     {   // the fused assembly kernel was recorded under Phase4: psi's share of it is Phase3_PsiData.  kPsiShare = the
         // kernel's arithmetic that belongs to :377-406 (per channel: t*t, + eps, sqrt, 2*, 1/) over all of it, counted in
         // the kernel's ISA (fp64 sqrt and division are ~25 instructions each); a fixed apportioning, not a measurement.
@@ -1227,7 +958,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         tm[PAPOF_T_PHASE4_LINEARSYSTEM] += f - 0.51 * f - 0.02 * f - 0.14 * f;
     }
     if (timing) std::memcpy(timing, tm, tm_bytes);
-    if (op == kSeqNext) keep(slot1 ^ 1);  // the frame just solved against becomes frame 1 of the next push
+    if (op == kSeqNext) keep_seq(slot1 ^ 1);  // the frame just solved against becomes frame 1 of the next push
     return PAPOF_OK;
 }
 
@@ -1237,9 +968,8 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
                 const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
     LapGuard lg;
     const int fc = feature_channels(C);
-    // [strips (PAPOF_STRIPS, off by default, an A/B switch) update the flow per strip and carry no witnesses]
     lg.on = h->lap_guard && op != kSeqPrime && P.noise_model == PAPOF_NOISE_LAPLACIAN && fc <= 8 && levels >= 1 &&
-            h->lap_flags_dev != nullptr && h->strips <= 1;
+            h->lap_flags_dev != nullptr;
     if (!lg.on) return flow_pass(h, fa, fb, op, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, nullptr);
     lg.flags = h->lap_flags_dev;
     lg.lap = h->lap_dev;
@@ -1398,10 +1128,6 @@ int papof_create(int device, papof_handle** out) {
         papof_destroy(h);
         return PAPOF_ENODEVICE;
     }
-    if (const char* cs = std::getenv("PAPOF_STRIPS")) h->strips = std::max(0, std::atoi(cs));
-    // strip streams (smooth_flow_strips; opt-in) are created only where they are used: a handle is two streams otherwise, and
-    // the runtime multiplexes streams onto a limited number of hardware queues (eight tile ranks on one device = 16 streams)
-    if (h->strips > 1) ensure_strip_streams(h);
     if (const char* cs = std::getenv("PAPOF_GRAPH")) h->use_graph = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_OVERLAP")) h->overlap_prep = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_PHASE_EVENTS")) h->phase_events = std::atoi(cs) != 0;
@@ -1455,13 +1181,8 @@ void papof_destroy(papof_handle* h) {
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
     if (h->prep_stream) hipStreamSynchronize(h->prep_stream);
-    for (hipStream_t ss : h->strip_streams) {
-        hipStreamSynchronize(ss);
-        hipStreamDestroy(ss);
-    }
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     for (hipEvent_t e : h->sync_events) hipEventDestroy(e);
-    for (hipEvent_t e : h->strip_events) hipEventDestroy(e);
     for (papof::GraphEntry& e : h->graphs)
         if (e.exec) hipGraphExecDestroy(e.exec);
     if (h->prep_stream) hipStreamDestroy(h->prep_stream);
@@ -2324,7 +2045,7 @@ int papof_sor_plan(papof_handle* h, int height, int width, int n_sor, int sor_mo
 int papof_last_sor_stats(papof_handle* h, int* launches, double* strip_streams_sec) {
     if (!h) return PAPOF_EINVAL;
     if (launches) *launches = h->sor_launches;
-    if (strip_streams_sec) *strip_streams_sec = h->sor_upper_sec;
+    if (strip_streams_sec) *strip_streams_sec = 0.0;
     return PAPOF_OK;
 }
 
@@ -2364,46 +2085,11 @@ int papof_last_sor_solves(papof_handle* h, int cap, int* n, int* info, double* s
     return PAPOF_OK;
 }
 
-int papof_strip_plan(papof_handle* h, int height, int width, int n_sor, int n_outer, int want_strips, int* strips,
-                     int* out, int cap, int* band_rows, int* koff, int* bands) {
-    if (!h || !strips || height < 1 || width < 1 || n_sor < 1 || n_outer < 1) return PAPOF_EINVAL;
-    SorPlanes sp{};
-    sp.skew = true;
-    sp.cap_cells = sp.cap_cells_d = ~size_t(0);
-    PAPOF_TRY(sor_bind(h, sp, height, width, n_sor));
-    if (band_rows) *band_rows = sp.sd.band_rows;
-    if (koff) *koff = sp.sd.koff;
-    if (bands) *bands = sp.sd.nb;
-    StripSchedule q;
-    const int want = want_strips > 0 ? want_strips : (h->strips > 1 ? h->strips : 1);
-    if (!plan_strips(h, sp, height, n_sor, n_outer, want, q)) {
-        *strips = 1;
-        return PAPOF_OK;
-    }
-    *strips = q.S;
-    if (out) {
-        const int need = (n_outer + 1) * (q.S + 1) * 5;
-        if (cap < need) return PAPOF_EINVAL;
-        for (int n = 0; n <= n_outer; n++)
-            for (int s = 0; s <= q.S; s++) {
-                int* o = out + (size_t)q.idx(n, s) * 5;
-                o[0] = q.beta[q.idx(n, s)];
-                o[1] = q.rU[q.idx(n, s)];
-                o[2] = q.rP[q.idx(n, s)];
-                o[3] = q.rS[q.idx(n, s)];
-                o[4] = q.rA[q.idx(n, s)];
-            }
-    }
-    return PAPOF_OK;
-}
-
-// Test aid (papof.h): one exact-order solve on synthetic planes, whole and as two strips of bands on two streams
+// Test aid (papof.h): one exact-order solve on synthetic planes, whole and as two band launches on two streams
 // (sor_solve_bands), `reps` times; *mismatches = 16-byte cells of the (du, dv) planes, both parities, that differ.
 int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int split_band, int reps, int delay_us,
                           long long* mismatches, int* bands) {
     if (!h || !mismatches) return PAPOF_EINVAL;
-    ensure_strip_streams(h);
-    if (h->strip_streams.empty()) return PAPOF_EINVAL;
     const size_t np = (size_t)height * width;
     Scope S(h, img_bytes(height, width, 1, 16) + sor_scratch_bytes(height, width, n_sor) +
                    12 * (size_t)height * width * sizeof(double));
@@ -2435,9 +2121,21 @@ int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int
     PAPOF_HIP(hipMemcpy(want.data(), sp.du, cells * 16, hipMemcpyDeviceToHost));
     *mismatches = 0;
     if (!sor_strips_supported(h, sp, n_sor) || split_band < 1 || split_band >= sp.sd.nb) return PAPOF_EINVAL;
-    hipStream_t const main_stream = h->stream, top = h->strip_streams[0];
-    hipEvent_t ev;
-    PAPOF_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    struct Owned {  // the upper bands' stream and the fork event, released on every return
+        hipStream_t top = nullptr;
+        hipEvent_t ev = nullptr;
+        ~Owned() {
+            if (top) {
+                hipStreamSynchronize(top);
+                hipStreamDestroy(top);
+            }
+            if (ev) hipEventDestroy(ev);
+        }
+    } own;
+    PAPOF_HIP(hipStreamCreateWithFlags(&own.top, hipStreamNonBlocking));
+    PAPOF_HIP(hipEventCreateWithFlags(&own.ev, hipEventDisableTiming));
+    hipStream_t const main_stream = h->stream, top = own.top;
+    hipEvent_t const ev = own.ev;
     for (int r = 0; r < reps; r++) {
         PAPOF_TRY(sor_strips_begin(h, sp, n_sor, 1));
         PAPOF_HIP(hipEventRecord(ev, main_stream));
@@ -2482,7 +2180,6 @@ int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int
         }
         *mismatches += mm;
     }
-    hipEventDestroy(ev);
     return PAPOF_OK;
 }
 

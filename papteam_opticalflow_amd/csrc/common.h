@@ -312,13 +312,6 @@ struct papof_handle {
         double sec;
     };
     std::vector<SorSolveLog> sor_log;
-    double sor_upper_sec = 0.0;      // ... of which: event time of the launches on the strip streams (added to Phase5_SOR)
-    // strips (api.hip: smooth_flow_strips): a level's plane as S horizontal strips of solver bands, each on its own
-    // stream, so that a strip's non-solver kernels run in the shadow of the other strips' solves
-    int strips = 0;                  // PAPOF_STRIPS: 0 / 1 = off (default), 2..4 = strips per level where the layout allows
-    std::vector<hipStream_t> strip_streams;  // S - 1 extra streams (the last strip runs on the main stream)
-    std::vector<hipEvent_t> strip_events;    // untimed events ordering the strips, reused from call to call
-    size_t strip_events_used = 0;
     // second stream for everything that does not depend on the flow (pyramids, features, smoothed frame 1 of every
     // level, derivative planes of the final bicubic warp): runs beside the coarse levels' latency-bound solves
     hipStream_t prep_stream = nullptr;
@@ -358,7 +351,7 @@ struct papof_handle {
     unsigned long long* stamps = nullptr;      // pinned host copy, fetched once per call
     int stamps_cap = 0, stamps_used = 0, stamps_fetched = 0;
     unsigned long long* next_stamp = nullptr;  // taken (and cleared) by the next kernel launch that supports stamps
-    hipStream_t stamp_stream = nullptr;        // ... on THIS stream only (the main chain): a launch on a strip / preparation
+    hipStream_t stamp_stream = nullptr;        // ... on THIS stream only (the main chain): a launch on the preparation
                                                // stream must not consume a stamp of the main stream's phase clock
     bool phase_events = true;        // PAPOF_PHASE_EVENTS=0: record only the total and the solver kernels' events (A/B of the events' cost)
     int sor_xcd_affine = 1;          // 0: off; 1: when there are at most 8 bands; 2: always (see sor.hip)      // all sweeps of a band on one XCD (block index -> task mapping, speed only)
@@ -477,8 +470,8 @@ int sor_blocked_launch(papof_handle* h, const SorPlanes& sp, int H, int W, doubl
                        int hs0, const Rect& out, const double* su, const double* sv, double* du, double* dv);
 int sor_plan(const papof_handle* h, int H, int W, int n_sor, int mode, int* launches, int* depth);
 int sor_check(papof_handle* h);  // after a stream sync: PAPOF_ETIMEOUT if a device-side wait expired
-// one solve as strips of bands on several streams (sor.hip): can this bound layout be solved in strips; clear the
-// counters of all `n_solves` solves of a level (before the streams fork); launch bands b0 .. b1-1 of solve `solve_idx`
+// one solve as band ranges on several streams (sor.hip): can this bound layout be solved in band ranges; clear the
+// counters of all `n_solves` solves (before the streams fork); launch bands b0 .. b1-1 of solve `solve_idx`
 bool sor_strips_supported(const papof_handle* h, const SorPlanes& sp, int n_sor);
 int sor_strips_begin(papof_handle* h, const SorPlanes& sp, int n_sor, int n_solves);
 // `split`: the ranges of bands of one solve live in different handles (tiles.hip: bands_flow; sor.hip: ExactArgs)

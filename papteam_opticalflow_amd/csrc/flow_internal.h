@@ -134,7 +134,6 @@ int feature_channels(int C);
 // tensors in and out); falls back to single calls
 int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* const* frames, bool u8, int H, int W, int C, int levels,
                     const papof_params* params, double* const* vx, double* const* vy, double* const* warpI2, double* timing_sec);
-void ensure_strip_streams(papof_handle* h);
 // the device call on two planar fp64 frames already on the device (api.hip: flow_device, both passes of the guard); returns
 // with the results written
 int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,

@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void k_smooth_hv_blend(const double* __restric
                                                          int W, Taps g, unsigned long long* stamp, int row0, int row1) {
     __shared__ double hs[kFuseRows + 4][BX];
     stamp_now(stamp);
-    // rows row0 .. row1-1 are written (a strip of the plane, api.hip: smooth_flow_strips; the whole plane otherwise)
+    // rows row0 .. row1-1 are written (a strip of the plane; the whole plane otherwise)
     const int j = blockIdx.x * BX + threadIdx.x, i0 = row0 + blockIdx.y * kFuseRows;
     const size_t np = (size_t)H * W;
     const double* src = warp + blockIdx.z * np;

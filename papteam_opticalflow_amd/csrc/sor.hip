@@ -108,8 +108,9 @@ struct ExactArgs {
     int xcd_affine;
     int k0;  // first sweep (k_sor_exact) / pair (k_sor_fused) of THIS launch: a solve whose tasks exceed what the chip
              // keeps resident is issued as consecutive launches over ranges of sweeps (sor_solve)
-    int b0, nbl;  // bands b0 .. b0 + nbl - 1 are THIS launch's (a strip of the plane, sor_solve_bands: the strips of a solve
-                  // are launched on different streams and meet through the progress counters); a whole solve: 0, nb
+    int b0, nbl;  // bands b0 .. b0 + nbl - 1 are THIS launch's (a band range, sor_solve_bands: the ranges of a solve are
+                  // launched on different streams or by different ranks and meet through the progress counters); a
+                  // whole solve: 0, nb
     double nalpha, om1;
     unsigned long long* dbg;  // diagnostics (PAPOF_SOR_DBG): per task 8 time stamps (s_memrealtime, 100 MHz), else null
     unsigned long long* stamp;  // phase stamp (flow_internal.h: PhaseClock): block 0 writes the 100 MHz clock on entry
@@ -1831,7 +1832,7 @@ int sor_redblack_halfsweep(papof_handle* h, const SorPlanes& sp, int H, int W, d
 // margin is for whatever else runs beside the solve); larger solves become consecutive launches over ranges of sweeps --
 // the ping-pong planes and the counters carry the state across the launch boundary.  PAPOF_SOR_RESIDENT (read when the
 // handle is created) overrides the bound: the tests use it to force many launches per solve.
-static int fill_pairs(papof_handle* h, void* base, size_t stride_bytes, size_t bytes, int batch);  // (defined with the strips' helpers below)
+static int fill_pairs(papof_handle* h, void* base, size_t stride_bytes, size_t bytes, int batch);  // (defined with the band ranges' helpers below)
 static int resident_tasks(const papof_handle* h) {
     if (h->sor_resident > 0) return h->sor_resident;
     return std::max(64, (h->cu_count > 0 ? h->cu_count : 256) * 8);
@@ -2382,14 +2383,15 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
     return PAPOF_EINVAL;
 }
 
-// ---- one solve as STRIPS of bands on several streams (api.hip: smooth_flow_strips) -------------------------
-// The bands b0 .. b1-1 of a solve are one launch; the launches of a solve run on different streams and meet through the
-// progress counters exactly as the tasks of one launch do (a task waits on (b, k-1), (b-1, k) and -- write-after-read --
-// (b+1, k-2): the first two point into the same or the upper strip, the third into the same or the LOWER one, so an upper
-// strip can run at most two sweeps per band ahead of the strip below it; every wait is bounded).  Because a strip starts
-// before the strips below it have even been launched, the counters of a solve must be zero before its FIRST strip
-// starts: every solve of a level has its own counter array, all cleared at once by sor_strips_begin() before the
-// streams fork.  The (du, dv) blocks of the strip's bands are cleared by the strip itself (cache warming, sor_solve).
+// ---- one solve as BAND RANGES on several streams or ranks (tiles.hip: bands_flow; api.hip: papof_test_sor_strips) --------
+// The bands b0 .. b1-1 of a solve are one launch; the launches of a solve run on different streams or by different ranks
+// and meet through the progress counters exactly as the tasks of one launch do (a task waits on (b, k-1), (b-1, k) and --
+// write-after-read -- (b+1, k-2): the first two point into the same or the upper range, the third into the same or the
+// LOWER one, so an upper range can run at most two sweeps per band ahead of the range below it; every wait is bounded).
+// Because a range starts before the ranges below it have even been launched, the counters of a solve must be zero before
+// its FIRST range starts: every solve has its own counter array, all cleared at once before the ranges are launched
+// (sor_strips_begin() for the test aid).  The (du, dv) blocks of a range's bands are cleared by the range itself (cache
+// warming, sor_solve).
 // Zero n16 16-byte cells of every pair of a batch (the pairs' blocks lie stride16 cells apart): blockIdx.y = pair.  The runtime's
 // 2-D fill reaches 0.75 TB/s on these shapes (43 MB in 58 us: profiles/r04_batch16_kernel_avgs_by_grid_xcd_affine.txt); this one
 // is a plain streaming store.
@@ -2418,7 +2420,7 @@ bool sor_strips_supported(const papof_handle* h, const SorPlanes& sp, int n_sor)
     if (!sp.skew || sp.sd.group > 1 || !h->use_dpp || n_sor < 3) return false;
     if (h->sor_xcd_affine && (sp.sd.nb <= 8 || h->sor_xcd_affine > 1)) return false;  // the XCD-affine task mapping
     const int per = sp.sd.nb, tasks = per * (sp.sd.fuse == 2 ? (n_sor + 1) / 2 : n_sor);
-    return tasks <= resident_tasks(h);  // one launch per strip: every task of the solve resident
+    return tasks <= resident_tasks(h);  // one launch per band range: every task of the solve resident
 }
 
 // Counters of one solve of a height x width plane (whichever layout sor_bind() picks), in unsigneds

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import cases
-from conftest import require_queues_for_ranks
+from conftest import require_hw_queues, require_queues_for_ranks
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -271,3 +271,16 @@ def test_band_split_random_shapes_ranks_and_schedules(gpu, tile_group, seed):
         (vx, vy, wi, _), _ = _run(nranks, a, b, levels, P, tile_group)
         want = gpu.coarse2fine_flow(a, b, levels, P)
         assert np.array_equal(vx, want[0]) and np.array_equal(vy, want[1]) and np.array_equal(wi, want[2]), (seed, case)
+
+
+@pytest.mark.parametrize("h,w,n_sor,split,delay", [(1080, 1920, 7, 9, 0), (1080, 1920, 9, 9, 100), (1080, 1920, 11, 5, 300),
+                                                   (1080, 1920, 3, 9, 0), (1080, 1920, 33, 12, 100), (1080, 1920, 30, 9, 50),
+                                                   (810, 1440, 9, 7, 0), (810, 1440, 30, 3, 200), (607, 1080, 12, 5, 0)])
+def test_one_solve_in_two_launches_equals_the_whole_solve(gpu, h, w, n_sor, split, delay):
+    """the solver alone: bands < split on one stream, the others `delay` microseconds later on another -- every cell of
+    the (du, dv) planes, intermediate sweeps included, as the one-launch solve leaves it (plain and two-sweeps-per-wave
+    kernel, even and ODD sweep counts: the odd ones used to go wrong here, see sor.hip f_step)"""
+    require_hw_queues(8, "the band launches of one solve on two streams")
+    mm, nb = gpu.test_sor_strips(h, w, n_sor, split, reps=6, delay_us=delay)
+    print("%dx%d sweeps %d: %d bands cut at %d, %d mismatching cells" % (w, h, n_sor, nb, split, mm))
+    assert mm == 0
