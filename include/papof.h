@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 109 /* 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 110 /* 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -213,13 +213,6 @@ int papof_tiles_stats(const papof_tiles* t, long* exchanges, size_t* bytes); /* 
 int papof_tiles_comm_info(const papof_tiles* t, int* nranks_seen, int* rank_seen, int* rows, int* cols, int* halo);
 void papof_tiles_destroy(papof_tiles* t);
 
-/* hipGraph replay of whole calls (also PAPOF_GRAPH=1 when the handle is created).  A call with given arguments runs
- * eagerly the first time, is captured (both streams, every kernel, memset and copy) the second time and is one
- * hipGraphLaunch from then on; only "Total C++ Execution" is timed in that mode.  For small frames, and for several
- * calls in flight, the host-side launch path is the limit: 240x135 pairs on the reference schedule are ~700 launches
- * each.  Results are the same bits. */
-int papof_set_graph_mode(papof_handle* h, int on);
-
 /* Whether a call spreads over several streams of its own (the preparation beside the coarse levels' solves, PCIe copies beside
  * kernels: the default, fastest for ONE call at a time) or stays on the handle's one stream (on = 0; also PAPOF_OVERLAP=0 when
  * the handle is created).  With several handles in flight -- a collection of pairs, flow_collection() -- the other handles'
@@ -350,8 +343,8 @@ int papof_last_sor_solves(papof_handle* h, int cap, int* n, int* info, double* s
  * the guard in the assembly, and the handle then stays in that exact pass until a call proves it unnecessary again.  Results
  * are the reference's either way.  out[0] = calls that were run twice, out[1] = calls run in the exact pass from the start,
  * out[2] = 1 when the next call will start in the exact pass, out[3] = 0 when PAPOF_LAP_GUARD=0 switched the guard off (an
- * A/B switch for its cost: results then differ from the reference's on tripping inputs).  hipGraph replay, the bicubic
- * branch and the papof_stage_smoothflow* entry points always take the exact pass; the Gaussian-mixture branch has no such
+ * A/B switch for its cost: results then differ from the reference's on tripping inputs).  The bicubic branch and the
+ * papof_stage_smoothflow* entry points always take the exact pass; the Gaussian-mixture branch has no such
  * guard (:381-397).  One pair over several ranks (papof_tiles_*): the exact-order band split has no exact pass, so it PROVES
  * per call that the guard cannot have tripped (every rank checks every pixel of its rows behind every update; the flags of
  * all ranks are gathered) or returns PAPOF_EINVAL on every rank with a message that names the one-GPU call; the red-black

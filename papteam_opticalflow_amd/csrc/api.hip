@@ -31,59 +31,6 @@ void set_last_error(const char* what, hipError_t e, const char* file, int line) 
 const char* last_error() { return g_last_error.c_str(); }
 void set_last_error_text(const std::string& text) { g_last_error = text; }
 
-CopyPool::CopyPool(int workers) {
-    for (int i = 0; i < workers; i++) threads_.emplace_back([this] { loop(); });
-}
-
-CopyPool::~CopyPool() {
-    {
-        std::lock_guard<std::mutex> lk(mu_);
-        stop_ = true;
-    }
-    wake_.notify_all();
-    for (auto& t : threads_) t.join();
-}
-
-void CopyPool::loop() {
-    for (;;) {
-        Job j;
-        {
-            std::unique_lock<std::mutex> lk(mu_);
-            wake_.wait(lk, [this] { return stop_ || !jobs_.empty(); });
-            if (jobs_.empty()) return;  // stop
-            j = jobs_.back();
-            jobs_.pop_back();
-        }
-        std::memcpy(j.dst, j.src, j.n);
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-}
-
-void CopyPool::copy(char* dst, const char* src, size_t n) {
-    const int parts = (int)threads_.size() + 1;
-    const size_t part = (n / parts + 4095) & ~size_t(4095);
-    int queued = 0;
-    {
-        std::lock_guard<std::mutex> lk(mu_);
-        for (int t = 1; t < parts; t++) {
-            const size_t off = (size_t)t * part;
-            if (off >= n) break;
-            jobs_.push_back(Job{dst + off, src + off, std::min(part, n - off)});
-            queued++;
-        }
-        pending_ += queued;
-    }
-    if (queued) wake_.notify_all();
-    std::memcpy(dst, src, std::min(part, n));
-    if (queued) {
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-    }
-}
-
 static double wall() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -279,7 +226,7 @@ int bicubic_planes(papof_handle* h, const double* f2, int H, int W, int fc, Solv
 struct LapGuard {
     bool on = false;        // Laplacian noise model, at most 8 feature channels, the handle has its flag block
     bool exact = false;     // the exact pass
-    bool collect = false;   // witnesses are collected (always, except inside a hipGraph: nobody could act on them)
+    bool collect = false;   // witnesses are collected (flow_device, except in the bicubic branch: it has no sampled warp)
     bool nz_known = false;  // the non-zero flags of the feature channels are collected too (im2feature ran for this call)
     unsigned* flags = nullptr;  // device: papof_handle::lap_flags_dev
     double* lap = nullptr;      // device: LapPara (exact pass)
@@ -488,43 +435,6 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     double tm[PAPOF_N_TIMERS + 1];  // + kTimerFused (flow_internal.h)
     std::memset(tm, 0, sizeof tm);
     const size_t tm_bytes = PAPOF_N_TIMERS * sizeof(double);  // what the caller gets
-
-    // ---- hipGraph mode: eager on the first call with these arguments, captured on the second, replayed afterwards
-    enum { kEager, kCapture, kReplay } gmode = kEager;
-    GraphEntry* ge = nullptr;
-    if (h->use_graph && op != kSeqPrime && P.phase_timing == 0 && P.noise_model == PAPOF_NOISE_LAPLACIAN) {
-        GraphKey key;
-        std::memset(&key, 0, sizeof key);
-        key.H = H;
-        key.W = W;
-        key.C = C;
-        key.levels = levels;
-        key.op = (int)op;
-        key.slot1 = slot1;
-        key.u8 = fb.planar ? 2 : (fb.u8 ? 1 : 0);
-        key.P = P;
-        key.fa = op == kSeqNext ? nullptr : fa.d;
-        key.fb = fb.d;
-        key.vx = d_vx;
-        key.vy = d_vy;
-        key.warp = d_warp;
-        key.arena_base = A.base;
-        key.sync_base = h->sync_words;
-        for (GraphEntry& e : h->graphs)
-            if (std::memcmp(&e.key, &key, sizeof key) == 0) ge = &e;
-        if (!ge) {
-            if (h->graphs.size() >= 8) {  // a handful of shapes per handle is the use case; start over beyond that
-                for (GraphEntry& e : h->graphs)
-                    if (e.exec) hipGraphExecDestroy(e.exec);
-                h->graphs.clear();
-            }
-            h->graphs.push_back(GraphEntry{});
-            ge = &h->graphs.back();
-            ge->key = key;
-        }
-        gmode = ge->exec ? kReplay : (ge->seen >= 1 ? kCapture : kEager);
-        ge->seen++;
-    }
     const auto keep_seq = [&](int slot) {
         h->seq.valid = true;
         h->seq.h = H;
@@ -535,45 +445,13 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         h->seq.slot = slot;
         h->seq.arena_base = A.base;
     };
-    const auto launch_graph = [&]() -> int {  // replay + the only two timers a graph call has: total, and nothing else
-        hipEvent_t e0, e1;
-        PAPOF_HIP(hipEventCreate(&e0));
-        PAPOF_HIP(hipEventCreate(&e1));
-        hipEventRecord(e0, h->stream);
-        hipError_t ge_rc = hipGraphLaunch(ge->exec, h->stream);
-        hipEventRecord(e1, h->stream);
-        hipError_t sy = hipStreamSynchronize(h->stream);
-        float ms = 0;
-        if (ge_rc == hipSuccess && sy == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        if (ge_rc != hipSuccess || sy != hipSuccess) {
-            set_last_error("hipGraphLaunch", ge_rc != hipSuccess ? ge_rc : sy, __FILE__, __LINE__);
-            return PAPOF_EDEVICE;
-        }
-        if (P.sor_mode == PAPOF_SOR_EXACT) PAPOF_TRY(sor_check(h));
-        tm[PAPOF_T_TOTAL] = ms * 1e-3;
-        if (timing) std::memcpy(timing, tm, tm_bytes);
-        if (op == kSeqNext) keep_seq(slot1 ^ 1);
-        return PAPOF_OK;
-    };
-    if (gmode == kReplay) return launch_graph();
-    const bool capturing = gmode == kCapture;
-    if (capturing) {
-        hipError_t ce = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
-        if (ce != hipSuccess) {  // no graphs on this runtime: stay eager
-            h->use_graph = false;
-            gmode = kEager;
-        }
-    }
-    const bool in_capture = gmode == kCapture;
     // All ten reference timers (src/OpticalFlow.cpp:850-860) are ALWAYS measured, with HIP events recorded on the streams
     // (no synchronisation): `clk` on the main stream, `pclk` on the preparation stream.  With phase_timing == 0 the two
     // streams overlap, so Construction / Allocation / PostProcessing (preparation stream) run beside the solver phases
     // and the ten values add up to more than the total; phase_timing == 1 runs everything on one stream.
-    PhaseClock clk{h, !in_capture};
-    PhaseClock pclk{h, !in_capture};
-    PhaseClock total{h, !in_capture};
+    PhaseClock clk{h, true};
+    PhaseClock pclk{h, true};
+    PhaseClock total{h, true};
     clk.only_sor = pclk.only_sor = (!h->phase_events && P.phase_timing == 0) || P.phase_timing == 2;
     h->sor_launches = 0;
     h->sor_log.clear();
@@ -592,17 +470,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     }
     double* tmp_a = A.f64(np0 * C);
     double* tmp_b = A.f64(np0 * C);
-    const auto abandon_capture = [&]() {  // an error return must not leave a stream capture open on this handle
-        if (!in_capture) return;
-        hipGraph_t graph = nullptr;
-        hipStreamEndCapture(h->stream, &graph);
-        if (graph) hipGraphDestroy(graph);
-        h->use_graph = false;
-    };
-    if (A.overflow) {
-        abandon_capture();
-        return PAPOF_ENOMEM;
-    }
+    if (A.overflow) return PAPOF_ENOMEM;
     if (op == kSeqPrime) {
         PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
         PAPOF_TRY(build_pyramid(h, L, plan, C, false, tmp_a, tmp_b));
@@ -638,19 +506,9 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     SolveBuffers B;
     {
         const int rc_alloc = alloc_solve_buffers(A, H, W, fc, P.sor_mode, n_sor_max, B);
-        if (rc_alloc != PAPOF_OK || A.overflow) {
-            abandon_capture();
-            return rc_alloc != PAPOF_OK ? rc_alloc : PAPOF_ENOMEM;
-        }
+        if (rc_alloc != PAPOF_OK || A.overflow) return rc_alloc != PAPOF_OK ? rc_alloc : PAPOF_ENOMEM;
     }
-
-    {
-        const int rc_br = alloc_branch_buffers(h, A, H, W, fc, P.interpolation, P.noise_model, B);
-        if (rc_br != PAPOF_OK) {
-            abandon_capture();
-            return rc_br;
-        }
-    }
+    PAPOF_TRY(alloc_branch_buffers(h, A, H, W, fc, P.interpolation, P.noise_model, B));
 
     // Exact-order path: the progress counters of EVERY solve of the call are cleared at once on the preparation stream (one
     // fill instead of one per solve in front of each solver launch on the main stream).  [Also tried: one set of coefficient
@@ -669,13 +527,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
             LP[k].prog_off = prog_total;
             prog_total += LP[k].prog_per * (size_t)((P.n_outer + k * P.n_outer_per_level) * P.n_inner);
         }
-        if (!in_capture) {
-            const int rc_c = sor_counters_ensure(h, prog_total);
-            if (rc_c != PAPOF_OK) return rc_c;
-        } else if (prog_total + 64 > h->sync_cap) {  // the eager call before the capture sized them
-            abandon_capture();
-            return PAPOF_EDEVICE;
-        }
+        PAPOF_TRY(sor_counters_ensure(h, prog_total));
     }
 
     const bool overlap = h->overlap_prep && P.phase_timing != 1 && h->prep_stream != nullptr;
@@ -740,7 +592,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     // inputs: same bits.  [The device-resident call keeps the level-interleaved order above: there the main stream starts
     // the coarsest level as early as possible.]
     papof_handle::HostIO& io = h->hostio;
-    const bool hostio = io.active && overlap && !in_capture && h->copy_stream && h->copy_events.size() >= 8;
+    const bool hostio = io.active && overlap && h->copy_stream && h->copy_events.size() >= 8;
     const auto prepare_hostio = [&]() -> int {
         StreamSwap on_prep(h, prep);
         hipStream_t const cs = h->copy_stream;
@@ -801,16 +653,12 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
     {
         const int rc = hostio ? prepare_hostio() : prepare();
         if (rc != PAPOF_OK) {
-            if (in_capture)
-                abandon_capture();
-            else if (overlap)
-                hipStreamSynchronize(prep);
+            if (overlap) hipStreamSynchronize(prep);
             return rc;
         }
     }
 
     int pw = 0, ph = 0;
-    int rc_main = PAPOF_OK;
     const auto solve_levels = [&]() -> int {
         if (lg && lg->guard())  // LapPara starts every call at 0.02 (src/OpticalFlow.cpp:773-775)
             PAPOF_HIP(hipMemcpyAsync(lg->lap, h->lap_init_dev, 8 * sizeof(double), hipMemcpyDeviceToDevice, main_stream));
@@ -887,21 +735,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         if (v != d_vy) PAPOF_HIP(hipMemcpyAsync(d_vy, v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         return PAPOF_OK;
     };
-    rc_main = solve_levels();
-    if (in_capture) {  // close the capture whatever happened; a failed capture falls back to eager calls for good
-        hipGraph_t graph = nullptr;
-        hipError_t ee = hipStreamEndCapture(main_stream, &graph);
-        if (rc_main == PAPOF_OK && ee == hipSuccess && graph &&
-            hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-            hipGraphDestroy(graph);
-            return launch_graph();
-        }
-        if (graph) hipGraphDestroy(graph);
-        ge->exec = nullptr;
-        h->use_graph = false;
-        g_last_error = "hipGraph capture failed; graph mode switched off for this handle";
-        return rc_main != PAPOF_OK ? rc_main : PAPOF_EDEVICE;
-    }
+    const int rc_main = solve_levels();
     if (rc_main != PAPOF_OK) {  // never leave work of this call running on any stream
         hipStreamSynchronize(main_stream);
         if (overlap) hipStreamSynchronize(prep);
@@ -977,8 +811,8 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
     // the non-zero flags of the feature channels are written by im2feature's 1- and 3-channel branches only (any other channel
     // count is passed through untouched, src/OpticalFlow.cpp:956-960): without them no channel may count as "all zero"
     lg.nz_known = (C == 1 || C == 3) && (size_t)levels * 8 <= (size_t)kLapNzWords;
-    // inside a hipGraph nobody could act on the flags, and the bicubic branch has no sampled warp: always the exact pass
-    const bool always_exact = h->use_graph || P.interpolation == PAPOF_INTERP_BICUBIC;
+    // the bicubic branch has no sampled warp: always the exact pass
+    const bool always_exact = P.interpolation == PAPOF_INTERP_BICUBIC;
     lg.collect = !always_exact;
     lg.exact = always_exact || h->lap_exact;
     const papof_handle::Seq seq0 = h->seq;
@@ -1111,28 +945,13 @@ int papof_create(int device, papof_handle** out) {
         delete h;
         return PAPOF_ENODEVICE;
     }
-    // The preparation stream may be confined to a share of the CUs (PAPOF_PREP_CUS = number of CUs; the mask's bits are
-    // dealt round-robin over the XCDs): its streaming kernels then take longer, still hidden behind the coarse levels'
-    // solves, but load the memory system less -- those latency-bound solves run 0.6 ms per 1080p pair slower beside an
-    // unconfined preparation stream than alone (same-box A/B).
-    int prep_cus = 0;
-    if (const char* cs = std::getenv("PAPOF_PREP_CUS")) prep_cus = std::atoi(cs);
-    if (prep_cus > 0 && prep_cus < h->cu_count) {
-        uint32_t mask[16] = {0};
-        for (int i = 0; i < prep_cus && i < 512; i++) mask[i / 32] |= 1u << (i % 32);
-        e = hipExtStreamCreateWithCUMask(&h->prep_stream, (uint32_t)((h->cu_count + 31) / 32), mask);
-        if (e != hipSuccess) h->prep_stream = nullptr;  // fall back to an ordinary stream
-    }
-    if (!h->prep_stream && (e = hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking)) != hipSuccess) {
+    if ((e = hipStreamCreateWithFlags(&h->prep_stream, hipStreamNonBlocking)) != hipSuccess) {
         set_last_error("hipStreamCreate", e, __FILE__, __LINE__);
         papof_destroy(h);
         return PAPOF_ENODEVICE;
     }
-    if (const char* cs = std::getenv("PAPOF_GRAPH")) h->use_graph = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_OVERLAP")) h->overlap_prep = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_PHASE_EVENTS")) h->phase_events = std::atoi(cs) != 0;
-    if (const char* cs = std::getenv("PAPOF_HOST_COPY")) h->host_copy = std::atoi(cs);
-    if (const char* cs = std::getenv("PAPOF_HOST_THREADS")) h->host_threads = std::max(1, std::atoi(cs));
     if (const char* cs = std::getenv("PAPOF_SOR_DEPTH")) h->sor_depth = std::max(4, std::atoi(cs));
     if (const char* cs = std::getenv("PAPOF_SOR_FUSE")) h->sor_fuse = std::max(1, std::atoi(cs));
     if (const char* cs = std::getenv("PAPOF_SOR_GROUP")) h->sor_group = std::max(1, std::atoi(cs));
@@ -1183,8 +1002,6 @@ void papof_destroy(papof_handle* h) {
     if (h->prep_stream) hipStreamSynchronize(h->prep_stream);
     for (hipEvent_t e : h->events) hipEventDestroy(e);
     for (hipEvent_t e : h->sync_events) hipEventDestroy(e);
-    for (papof::GraphEntry& e : h->graphs)
-        if (e.exec) hipGraphExecDestroy(e.exec);
     if (h->prep_stream) hipStreamDestroy(h->prep_stream);
     if (h->copy_stream) {
         hipStreamSynchronize(h->copy_stream);
@@ -1196,11 +1013,9 @@ void papof_destroy(papof_handle* h) {
     if (h->stage_dev) hipFree(h->stage_dev);
     if (h->tensor_scratch) hipFree(h->tensor_scratch);
     if (h->entry_event) hipEventDestroy(h->entry_event);
-    if (h->pin) hipHostFree(h->pin);
     if (h->lap_flags_host) hipHostFree(h->lap_flags_host);  // the stamps live inside these two blocks
     if (h->lap_flags_dev) hipFree(h->lap_flags_dev);
     if (h->lap_dev) hipFree(h->lap_dev);
-    delete h->pool;
     hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1306,12 +1121,6 @@ int papof_flow_device_u8(papof_handle* h, const unsigned char* d_im1, const unsi
                        d_vx, d_vy, d_warpI2, timing_sec);
 }
 
-int papof_set_graph_mode(papof_handle* h, int on) {
-    if (!h) return PAPOF_EINVAL;
-    h->use_graph = on != 0;
-    return PAPOF_OK;
-}
-
 int papof_set_stream_overlap(papof_handle* h, int on) {
     if (!h) return PAPOF_EINVAL;
     h->overlap_prep = on != 0;
@@ -1338,18 +1147,7 @@ int papof_seq_push_device(papof_handle* h, const void* d_frame, int is_u8, int h
 
 namespace {
 
-// Pageable user memory <-> pinned bounce buffer through the handle's persistent copy pool (one memcpy thread moves
-// ~10 GB/s; PCIe Gen5 wants ~50).
-void parallel_copy(papof_handle* h, char* dst, const char* src, size_t n) {
-    if (h->host_threads <= 1 || n < (size_t(1) << 20)) {
-        std::memcpy(dst, src, n);
-        return;
-    }
-    if (!h->pool) h->pool = new CopyPool(h->host_threads - 1);
-    h->pool->copy(dst, src, n);
-}
-
-int ensure_host_stage(papof_handle* h, size_t dev_bytes, size_t pin_bytes) {
+int ensure_host_stage(papof_handle* h, size_t dev_bytes) {
     if (dev_bytes > h->stage_dev_bytes) {
         PAPOF_HIP(hipStreamSynchronize(h->stream));
         if (h->stage_dev) PAPOF_HIP(hipFree(h->stage_dev));
@@ -1361,30 +1159,6 @@ int ensure_host_stage(papof_handle* h, size_t dev_bytes, size_t pin_bytes) {
             return PAPOF_ENOMEM;
         }
         h->stage_dev_bytes = dev_bytes;
-    }
-    if (pin_bytes > h->pin_bytes) {
-        PAPOF_HIP(hipStreamSynchronize(h->stream));
-        if (h->pin) PAPOF_HIP(hipHostFree(h->pin));
-        h->pin = nullptr;
-        h->pin_bytes = 0;
-        hipError_t e = hipHostMalloc((void**)&h->pin, pin_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            set_last_error("hipHostMalloc(pinned staging)", e, __FILE__, __LINE__);
-            return PAPOF_ENOMEM;
-        }
-        h->pin_bytes = pin_bytes;
-    }
-    return PAPOF_OK;
-}
-
-constexpr size_t kChunk = size_t(8) << 20;  // bounce granularity: the DMA of one chunk overlaps the memcpy of the next
-
-// user (pageable) -> pinned -> device, chunk by chunk on the handle's stream
-int upload_chunked(papof_handle* h, char* dev, const char* user, char* pin, size_t n) {
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = std::min(kChunk, n - off);
-        parallel_copy(h, pin + off, user + off, m);
-        PAPOF_HIP(hipMemcpyAsync(dev + off, pin + off, m, hipMemcpyHostToDevice, h->stream));
     }
     return PAPOF_OK;
 }
@@ -1401,10 +1175,8 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
     PAPOF_HIP(hipSetDevice(h->device));
     const size_t np = (size_t)height * width, nb_img = np * c * sizeof(double), nb_flow = np * sizeof(double);
     const size_t nb_in = np * c * (u8 ? 1 : sizeof(double));
-    // device staging for the interleaved frames and results (separate from the arena, which flow_device resets) and a
-    // pinned bounce buffer: inputs [im1 | im2], then reused for the outputs [warpI2 | vx | vy]
-    const size_t out_bytes = nb_img + 2 * nb_flow;
-    PAPOF_TRY(ensure_host_stage(h, 3 * nb_img + 2 * nb_flow, std::max(2 * nb_img, out_bytes)));
+    // device staging for the interleaved frames and results (separate from the arena, which flow_device resets)
+    PAPOF_TRY(ensure_host_stage(h, 3 * nb_img + 2 * nb_flow));
     double* d1 = h->stage_dev;
     double* d2 = d1 + np * c;
     double* dw = d2 + np * c;
@@ -1412,13 +1184,10 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
     double* dy = dx + np;
     double tm[PAPOF_N_TIMERS];
     std::memset(tm, 0, sizeof tm);
-    // host_copy = 1: the runtime's own pageable path (measured 55 GB/s both ways on this platform: hipMemcpyAsync from / to
-    // pageable memory); 0: our pinned bounce pipeline (pageable -> pinned by a thread pool, DMA per 8-MiB chunk)
-    const bool plain = h->host_copy == 1;
-    // PAPOF_HOSTIO=0: the copies around the call as in round 2 (A/B); default: the call issues them itself where they overlap
-    // device work (common.h: HostIO).  Not in graph mode (a captured call replays fixed pointers) and not for a priming push.
-    static const bool hostio_env = !(std::getenv("PAPOF_HOSTIO") && std::atoi(std::getenv("PAPOF_HOSTIO")) == 0);
-    bool use_io = plain && hostio_env && !h->use_graph && op != kSeqPrime && h->overlap_prep && h->prep_stream;
+    // The call issues the copies itself where they overlap device work (common.h: HostIO), except for a priming push and on
+    // one stream: there they are plain hipMemcpyAsync calls around it -- the runtime's own pageable path (measured 55 GB/s
+    // both ways on this platform)
+    bool use_io = op != kSeqPrime && h->overlap_prep && h->prep_stream;
     if (use_io && !h->copy_stream) {
         if (hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) != hipSuccess) h->copy_stream = nullptr;
         while (h->copy_stream && h->copy_events.size() < 8) {
@@ -1442,12 +1211,9 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
         h->hostio.im1 = op != kSeqNext ? im1 : nullptr;
         h->hostio.im2 = im2;
         h->hostio.nb_in = nb_in;
-    } else if (plain) {
+    } else {
         if (op != kSeqNext) PAPOF_HIP(hipMemcpyAsync(d1, im1, nb_in, hipMemcpyHostToDevice, h->stream));
         if (op != kSeqPrime) PAPOF_HIP(hipMemcpyAsync(d2, im2, nb_in, hipMemcpyHostToDevice, h->stream));
-    } else {
-        if (op != kSeqNext) PAPOF_TRY(upload_chunked(h, (char*)d1, (const char*)im1, h->pin, nb_in));
-        if (op != kSeqPrime) PAPOF_TRY(upload_chunked(h, (char*)d2, (const char*)im2, h->pin + nb_img, nb_in));
     }
     // The caller's result arrays are usually fresh allocations (pyflow.pyx: np.zeros per call): their first-touch page
     // faults (~20k pages at 1080p, ~4 ms) are taken by a helper thread WHILE the GPU computes, not while copying back.
@@ -1501,39 +1267,10 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
         if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
         return PAPOF_OK;
     }
-    if (plain) {
-        PAPOF_HIP(hipMemcpyAsync(warpI2, dw, nb_img, hipMemcpyDeviceToHost, h->stream));
-        PAPOF_HIP(hipMemcpyAsync(vx, dx, nb_flow, hipMemcpyDeviceToHost, h->stream));
-        PAPOF_HIP(hipMemcpyAsync(vy, dy, nb_flow, hipMemcpyDeviceToHost, h->stream));
-        PAPOF_HIP(hipStreamSynchronize(h->stream));
-    } else
-    // device -> pinned in chunks (dw, dx, dy are contiguous), each chunk handed to the user as soon as it has landed
-    {
-        const size_t n_chunks = (out_bytes + kChunk - 1) / kChunk;
-        std::vector<hipEvent_t> done(n_chunks);
-        for (size_t i = 0; i < n_chunks; i++) {
-            const size_t off = i * kChunk, m = std::min(kChunk, out_bytes - off);
-            PAPOF_HIP(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-            PAPOF_HIP(hipMemcpyAsync(h->pin + off, (const char*)dw + off, m, hipMemcpyDeviceToHost, h->stream));
-            PAPOF_HIP(hipEventRecord(done[i], h->stream));
-        }
-        auto scatter = [&](size_t off, size_t m) {  // [off, off+m) of [warpI2 | vx | vy] -> the three user buffers
-            const size_t bounds[4] = {0, nb_img, nb_img + nb_flow, nb_img + 2 * nb_flow};
-            char* dst[3] = {(char*)warpI2, (char*)vx, (char*)vy};
-            for (int k = 0; k < 3; k++) {
-                const size_t lo = std::max(off, bounds[k]), hi = std::min(off + m, bounds[k + 1]);
-                if (lo < hi) parallel_copy(h, dst[k] + (lo - bounds[k]), h->pin + lo, hi - lo);
-            }
-        };
-        int rc = PAPOF_OK;
-        for (size_t i = 0; i < n_chunks; i++) {
-            const size_t off = i * kChunk, m = std::min(kChunk, out_bytes - off);
-            if (rc == PAPOF_OK && hipEventSynchronize(done[i]) != hipSuccess) rc = PAPOF_EDEVICE;
-            if (rc == PAPOF_OK) scatter(off, m);
-            hipEventDestroy(done[i]);
-        }
-        PAPOF_TRY(rc);
-    }
+    PAPOF_HIP(hipMemcpyAsync(warpI2, dw, nb_img, hipMemcpyDeviceToHost, h->stream));
+    PAPOF_HIP(hipMemcpyAsync(vx, dx, nb_flow, hipMemcpyDeviceToHost, h->stream));
+    PAPOF_HIP(hipMemcpyAsync(vy, dy, nb_flow, hipMemcpyDeviceToHost, h->stream));
+    PAPOF_HIP(hipStreamSynchronize(h->stream));
     if (timing_sec) {
         tm[PAPOF_T_TOTAL] = wall() - t0;  // the caller-visible total includes both PCIe transfers
         std::memcpy(timing_sec, tm, sizeof tm);

@@ -60,7 +60,7 @@ struct BatchFrames {
 };
 
 bool batch_applies(const papof_handle* h, int B, int H, int W, int C, int levels, const papof_params& P) {
-    if (B < 2 || !h->use_dpp || h->use_graph) return false;
+    if (B < 2 || !h->use_dpp) return false;
     if (P.sor_mode != PAPOF_SOR_EXACT || P.n_inner != 1 || P.interpolation != PAPOF_INTERP_BILINEAR ||
         P.noise_model != PAPOF_NOISE_LAPLACIAN)
         return false;

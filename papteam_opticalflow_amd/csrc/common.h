@@ -15,13 +15,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include <condition_variable>
 #include <cstddef>
 #include <cstdint>
-#include <functional>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/papof.h"
@@ -212,53 +208,6 @@ struct SorPlanes {
 
 }  // namespace papof
 
-namespace papof {
-// A few persistent host threads per handle for the pageable <-> pinned copies of the host entry points (spawning
-// threads per 8-MiB chunk cost more than the copies; first-touch page faults of the caller's fresh result arrays are
-// spread over the workers).
-class CopyPool {
-public:
-    explicit CopyPool(int workers);
-    ~CopyPool();
-    void copy(char* dst, const char* src, size_t n);  // returns when all bytes are in place
-    int workers() const { return (int)threads_.size(); }
-
-private:
-    struct Job {
-        char* dst;
-        const char* src;
-        size_t n;
-    };
-    void loop();
-    std::vector<std::thread> threads_;
-    std::vector<Job> jobs_;
-    std::mutex mu_;
-    std::condition_variable wake_, done_;
-    int pending_ = 0;
-    bool stop_ = false;
-};
-}  // namespace papof
-
-namespace papof {
-// One captured call (hipGraph): everything flow_device enqueues for a given problem -- both streams, ~200 nodes at
-// 1080p, ~700 on the reference schedule -- replayed with a single launch.  Valid for exactly these arguments (the arena
-// layout is a pure function of them; pointers are part of the key).
-struct GraphKey {
-    int H, W, C, levels, op, slot1, u8;
-    papof_params P;
-    const void *fa, *fb;
-    void *vx, *vy, *warp;
-    const void* arena_base;
-    const void* sync_base;  // the progress counters / abort word (h->sync_words): captured memset nodes and kernel arguments hold
-                            // their addresses, and a later call that needs more counters reallocates them
-};
-struct GraphEntry {
-    GraphKey key;
-    int seen = 0;  // eager calls with this key so far (the first one sizes every lazily grown buffer)
-    hipGraphExec_t exec = nullptr;
-};
-}  // namespace papof
-
 struct papof_handle {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -268,26 +217,14 @@ struct papof_handle {
     std::vector<hipEvent_t> events;
     size_t events_used = 0;
     int cu_count = 0;
-    // host path (papof_flow): persistent device staging block and pinned bounce buffers
+    // host path (papof_flow): persistent device staging block
     double* stage_dev = nullptr;
     size_t stage_dev_bytes = 0;
-    char* pin = nullptr;
-    size_t pin_bytes = 0;
     // device-tensor path (papof_flow_batch_tensor): the planar frames and results of ONE pair that runs on its own (outside
     // the arena, which the single call lays out anew), and the event that orders the handle's streams behind the caller's
     double* tensor_scratch = nullptr;
     size_t tensor_scratch_bytes = 0;
     hipEvent_t entry_event = nullptr;
-    int host_copy = 1;               // PAPOF_HOST_COPY: 1 = hipMemcpyAsync straight from / to the caller's memory (the runtime's
-                                     // pageable path runs at 55 GB/s here; pinned result arrays are direct DMA), 0 = our pinned
-                                     // bounce pipeline of round 1 (0.4-0.6 ms slower per 1080p call, same-box A/B)
-    int host_threads = 6;            // threads used to move pageable user buffers to / from the pinned buffers
-    papof::CopyPool* pool = nullptr; // created by the first host-buffer call
-    // hipGraph replay of whole calls (PAPOF_GRAPH=1 / papof_set_graph_mode): for small frames a call is hundreds of
-    // launches of a few microseconds of work each, and with several calls in flight the host-side launch path is the
-    // limit; captured once (on the second call with the same arguments) a call becomes one hipGraphLaunch
-    bool use_graph = false;
-    std::vector<papof::GraphEntry> graphs;
     bool use_dpp = false;            // wave_shr/wave_shl DPP moves verified on this device (else ds_bpermute)
     int sor_depth = 0;               // software-pipeline depth R (steps) of the exact-order SOR kernel; 0 = by level size
     unsigned long long* sor_dbg = nullptr;  // device buffer for per-task wait statistics (PAPOF_SOR_DBG)
