@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 110 /* 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 111 /* 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -466,6 +466,50 @@ int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, c
 int papof_track_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* flow_fw,
                        const papof_tensor* flow_bw, int n_queries, const papof_tensor* queries, int use_check, double alpha1,
                        double alpha2, const papof_tensor* tracks, const papof_tensor* visible, void* stream);
+
+/* Motion-compensated frame interpolation (frame-rate up-conversion; Middlebury's interpolation error, Baker et al., IJCV
+ * 2011): the frames at times t in (0, 1) between the two frames of each pair, from its forward flow, its backward flow and,
+ * optionally, its occlusion mask -- one HIP kernel (interp.hip: k_interp), one lane per output pixel for every time.
+ * frames, frames2: as papof_flow_batch_tensor takes them -- uint8 (x / 255.0, as the flow's ingest), float32 (widened
+ * exactly) or float64, (frame, row, column, channel), any non-negative strides, the dtype decided per tensor; sequence != 0:
+ * pair i = (frames[i], frames[i + 1]), frames2 NULL; sequence == 0: pair i = (frames[i], frames2[i]).
+ * flow_fw (F01), flow_bw (F10): float32 / float64, (pair, row, column, {vx, vy}), any non-negative strides.
+ * occlusion: NULL (O0 = O1 = 0), or uint8 (pair, row, column, {fw, bw}) as papof_flow_batch_tensor_fb writes it, any
+ * non-negative strides: O0 is channel 0 (pixels of I0), O1 channel 1 (pixels of I1); a nonzero byte reads as 1.0.
+ * times: n_times values, each finite and strictly inside (0, 1).
+ * out: uint8, float32 or float64; element (pair i, time j, row r, column x, channel ch) at
+ *     out.data + i * stride[0] + j * time_stride + r * stride[1] + x * stride[2] + ch * stride[3]   (elements).
+ * For pixel p = (x, r) of pair i and each time t, in fp64 without fused multiply-adds, in this order:
+ *     s = 1 - t;  (u, v) = F01(r, x);  (bu, bv) = F10(r, x)        -- the flows at p itself (linear motion)
+ *     a0 = (t*t)*bu - (s*t)*u;  b0 = (t*t)*bv - (s*t)*v             -- F_t->0 = -s t F01 + t^2 F10
+ *     a1 = (s*s)*u - (s*t)*bu;  b1 = (s*s)*v - (s*t)*bv             -- F_t->1 =  s^2 F01 - s t F10
+ *     q0 = (x + a0, r + b0);  q1 = (x + a1, r + b1)
+ *     in0 = q0 in [0, width - 1] x [0, height - 1]  (false for NaN);  in1 likewise for q1
+ *     g0 = I0 sampled bilinearly at q0 (in0 only), g1 = I1 at q1 (in1 only), per channel -- the rule of
+ *         papof_fb_check_tensor (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1],
+ *         neighbours clamped into the image, taps accumulated from 0 in (m, n) order; the mask is sampled by the same rule
+ *     w0 = in0 ? s * (1 - (in1 ? O1 sampled at q1 : 0)) : 0
+ *     w1 = in1 ? t * (1 - (in0 ? O0 sampled at q0 : 0)) : 0
+ *     out = (w0*g0 + w1*g1) / (w0 + w1)           if w0 + w1 > 0
+ *         = (s*g0 + t*g1) / (s*[in0] + t*[in1])    else if in0 || in1
+ *         = s*I0(r, x) + t*I1(r, x)                else
+ *     where the term of an unavailable sample is omitted from the numerator (only in0: w0*g0, resp. s*g0).
+ * A point of I0 occluded in I1 (O0 = 1) makes g1 unreliable and the reverse for O1 and g0.  The result is stored as float64,
+ * float32 (one round-to-nearest) or uint8 = clamp(rint(255 * out), 0, 255) with rint rounding half to even (NaN: 0).
+ * Known answer: under constant integer motion F01 = 2d, F10 = -2d, the frame at t = 0.5 is I0 shifted by d (and I1 shifted
+ * back by d) wherever both samples stay in the image: q0 = p - d and q1 = p + d are integer points, so g0 = I0(p - d),
+ * g1 = I1(p + d), w0 = w1 = 0.5 without a mask, and out = g0 whenever I1(p + d) = I0(p - d).
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting:
+ * ordered behind the work queued there so far, and ahead of what follows.  The times travel as kernel arguments.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL descriptor (occlusion aside) or data pointer, frames that are not
+ * uint8 / float32 / float64, flows that are not float32 / float64, an occlusion mask that is not uint8, an output that is
+ * not uint8 / float32 / float64, a negative stride, a zero stride of out or a zero time_stride with n_times > 1, frames2
+ * given in sequence mode or missing in pair mode, n_times < 1, times NULL, a time that is not finite or not strictly inside
+ * (0, 1), height, width or c < 1, n_pairs < 1. */
+int papof_interp_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2,
+                        int height, int width, int c, const papof_tensor* flow_fw, const papof_tensor* flow_bw,
+                        const papof_tensor* occlusion, int n_times, const double* times, const papof_tensor* out,
+                        long long time_stride, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

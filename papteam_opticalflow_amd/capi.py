@@ -61,7 +61,7 @@ SYMBOLS = [
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
     "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
-    "papof_fb_check_tensor", "papof_track_tensor",
+    "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor",
 ]
 
 
@@ -166,6 +166,9 @@ def load():
     L.papof_track_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, _T, c_int, c_double, c_double, _T, _T,
                                      c_void_p]
     L.papof_track_tensor.restype = c_int
+    L.papof_interp_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _T,
+                                      ctypes.c_longlong, c_void_p]
+    L.papof_interp_tensor.restype = c_int
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
     _lib = L

@@ -1,0 +1,242 @@
+// papteam_opticalflow_amd/csrc/interp.hip -- motion-compensated frame interpolation (papof_interp_tensor).
+//
+// Why.  Frames between two frames (frame-rate up-conversion, slow motion; and Middlebury's interpolation error, Baker et al.,
+// IJCV 2011, the accepted way to judge a flow without ground truth) from the forward flow, the backward flow and the
+// occlusion mask that papof_flow_batch_tensor_fb returns.  Written with grid_sample it is about a dozen launches per
+// intermediate frame and several full-frame temporaries through HBM.  Here one lane makes one output pixel of every time:
+// the two flows at the pixel are read once, and each time costs two independent groups of bilinear taps (one per frame,
+// with the mask's taps at the same offsets) and the stores.
+//
+// Semantics: include/papof.h, papof_interp_tensor.  The bilinear rule is k_fb_check's and k_track's (the reference's,
+// src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image,
+// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).
+//
+// Mapping.  A block is a 64 x 4 tile of output pixels (as k_fb_check's): blockIdx.x the tile, blockIdx.y the pair.  A wave is
+// 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose stores are contiguous
+// along a row.  The times are kernel arguments (at most kMaxTimes per launch; more are launched in groups): they are the
+// same for every lane, so they sit in scalar registers with no load, and the call needs no device buffer and no copy to
+// fill one -- nothing the caller has to keep alive after the call returns.  Every offset is 64-bit.
+#include "common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
+
+namespace papof {
+
+namespace {
+
+constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+constexpr int kMaxTimes = 16;                  // times per launch (kernel arguments)
+constexpr long long kMaxPairs = 65535;         // gridDim.y
+constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
+
+struct InterpArgs {
+    papof_tensor f0, f1;  // frames of I0 and I1 (frame, row, column, channel); I1 of pair i is f1's frame i + seq
+    papof_tensor fw, bw;  // flows (pair, row, column, {vx, vy})
+    papof_tensor occ;     // uint8 mask (pair, row, column, {O0, O1}); data NULL: none
+    papof_tensor out;     // (pair, row, column, channel); time j at + j * tstride
+    long long tstride;
+    int H, W, C;
+    int seq;
+    int nt;               // times of this launch
+    double t[kMaxTimes];
+};
+
+// FD: the dtype of both frame tensors, fixed at compile time (the common case: one branch-free gather per tap), or -1: read
+// from each descriptor.  A uint8 sample is x / 255.0 as k_ingest_frames computes it, looked up in a table of the 256
+// quotients that the block fills once (lut): the same bits, without an fp64 division per tap.
+template <int FD>
+__device__ __forceinline__ double load_frame(const papof_tensor& t, long long o, const double* lut) {
+    const int d = FD >= 0 ? FD : t.dtype;
+    if (d == PAPOF_DTYPE_U8) return lut[static_cast<const unsigned char*>(t.data)[o]];
+    if (d == PAPOF_DTYPE_F32) return (double)static_cast<const float*>(t.data)[o];
+    return static_cast<const double*>(t.data)[o];
+}
+
+__device__ __forceinline__ double load_flow(const papof_tensor& t, long long o) {
+    return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
+}
+
+__device__ __forceinline__ int clamp_to(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
+    x = x < 0 ? 0 : x;
+    return x > n - 1 ? n - 1 : x;
+}
+
+// The four taps of the bilinear rule at (X, Y), a point of [0, W - 1] x [0, H - 1], in (m, n) order: their (row, column)
+// offsets in elements of a tensor whose row and column strides are s1, s2 -- for frames and mask alike, offsets are computed
+// per tensor -- and their weights.
+struct Taps {
+    int row[4], col[4];
+    double w[4];
+};
+
+__device__ __forceinline__ Taps taps_at(double X, double Y, int H, int W) {
+    Taps k;
+    const int xx = (int)X, yy = (int)Y;
+    double dx = X - xx, dy = Y - yy;
+    dx = dx > 1 ? 1.0 : dx;
+    dx = dx < 0 ? 0.0 : dx;
+    dy = dy > 1 ? 1.0 : dy;
+    dy = dy < 0 ? 0.0 : dy;
+#pragma unroll
+    for (int m = 0; m <= 1; m++)
+#pragma unroll
+        for (int n = 0; n <= 1; n++) {
+            k.row[2 * m + n] = clamp_to(yy + n, H);
+            k.col[2 * m + n] = clamp_to(xx + m, W);
+            k.w[2 * m + n] = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
+        }
+    return k;
+}
+
+template <int FD>
+__device__ __forceinline__ double sample_frame(const papof_tensor& t, long long base, const Taps& k, const double* lut) {
+    double g = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) g += load_frame<FD>(t, base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2], lut) * k.w[i];
+    return g;
+}
+
+__device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Taps& k) {  // bytes as 0 / 1
+    const unsigned char* m = static_cast<const unsigned char*>(t.data);
+    double o = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o += (m[base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2]] ? 1.0 : 0.0) * k.w[i];
+    return o;
+}
+
+__device__ __forceinline__ void store(const papof_tensor& t, long long o, double v) {
+    if (t.dtype == PAPOF_DTYPE_U8)  // clamp(rint(255 out), 0, 255), half to even; NaN -> 0 (fmax)
+        static_cast<unsigned char*>(t.data)[o] = (unsigned char)fmin(fmax(rint(255.0 * v), 0.0), 255.0);
+    else if (t.dtype == PAPOF_DTYPE_F32)
+        static_cast<float*>(t.data)[o] = (float)v;
+    else
+        static_cast<double*>(t.data)[o] = v;
+}
+
+// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: pair `pair0` + y.  Times
+// a.t[0 .. a.nt) are written at time slots j0 + j of out.
+template <int FD>
+__global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp(const InterpArgs a, long long tile0, long long pair0,
+                                                                 long long j0) {
+    __shared__ double lut[256];
+    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
+        const int k = threadIdx.y * kInterpTX + threadIdx.x;  // (256 lanes: one quotient each)
+        lut[k] = (double)k / 255.0;
+        __syncthreads();
+    }
+    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
+    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
+    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    if (x >= a.W || r >= a.H) return;
+    const int H = a.H, W = a.W;
+    const long long i = pair0 + blockIdx.y;
+    const long long of = i * a.fw.stride[0] + r * a.fw.stride[1] + x * a.fw.stride[2];
+    const long long ob = i * a.bw.stride[0] + r * a.bw.stride[1] + x * a.bw.stride[2];
+    const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
+    const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
+    const long long base0 = i * a.f0.stride[0], base1 = (i + a.seq) * a.f1.stride[0];
+    const long long baseo = i * a.occ.stride[0];
+    const long long pix0 = base0 + r * a.f0.stride[1] + x * a.f0.stride[2];
+    const long long pix1 = base1 + r * a.f1.stride[1] + x * a.f1.stride[2];
+    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    for (int j = 0; j < a.nt; j++) {
+        const double t = a.t[j], s = 1.0 - t;
+        const double tt = t * t, st = s * t, ss = s * s;
+        const double a0 = tt * bu - st * u, b0 = tt * bv - st * v;  // F_t->0 = -s t F01 + t^2 F10
+        const double a1 = ss * u - st * bu, b1 = ss * v - st * bv;  // F_t->1 =  s^2 F01 - s t F10
+        const double X0 = (double)x + a0, Y0 = (double)r + b0, X1 = (double)x + a1, Y1 = (double)r + b1;
+        // (false for a NaN)
+        const bool in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
+        const bool in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
+        const Taps k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
+        const Taps k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
+        double o0 = 0.0, o1 = 0.0;
+        if (a.occ.data && in0 && in1) {
+            o0 = sample_mask(a.occ, baseo, k0);
+            o1 = sample_mask(a.occ, baseo + a.occ.stride[3], k1);
+        }
+        const double w0 = in0 ? s * (1.0 - o1) : 0.0, w1 = in1 ? t * (1.0 - o0) : 0.0;
+        const bool weighted = w0 + w1 > 0;
+        const double c0 = weighted ? w0 : s, c1 = weighted ? w1 : t;
+        const double den = weighted ? w0 + w1 : (in0 ? s : 0.0) + (in1 ? t : 0.0);
+        const long long oj = outp + (j0 + j) * a.tstride;
+        for (int ch = 0; ch < a.C; ch++) {
+            double val;
+            if (in0 || in1) {
+                const double g0 = in0 ? sample_frame<FD>(a.f0, base0 + ch * a.f0.stride[3], k0, lut) : 0.0;
+                const double g1 = in1 ? sample_frame<FD>(a.f1, base1 + ch * a.f1.stride[3], k1, lut) : 0.0;
+                const double num = in0 && in1 ? c0 * g0 + c1 * g1 : (in0 ? c0 * g0 : c1 * g1);
+                val = num / den;
+            } else {
+                val = s * load_frame<FD>(a.f0, pix0 + ch * a.f0.stride[3], lut) + t * load_frame<FD>(a.f1, pix1 + ch * a.f1.stride[3], lut);
+            }
+            store(a.out, oj + ch * a.out.stride[3], val);
+        }
+    }
+}
+
+int launch_interp(hipStream_t st, InterpArgs a, int n_pairs, int n_times, const double* times) {
+    const int fd = a.f0.dtype == a.f1.dtype ? a.f0.dtype : -1;
+    const auto kernel = fd == PAPOF_DTYPE_U8    ? k_interp<PAPOF_DTYPE_U8>
+                        : fd == PAPOF_DTYPE_F32 ? k_interp<PAPOF_DTYPE_F32>
+                        : fd == PAPOF_DTYPE_F64 ? k_interp<PAPOF_DTYPE_F64>
+                                                : k_interp<-1>;
+    const long long tiles = ((a.W + kInterpTX - 1) / (long long)kInterpTX) * ((a.H + kInterpTY - 1) / (long long)kInterpTY);
+    for (int j0 = 0; j0 < n_times; j0 += kMaxTimes) {
+        a.nt = std::min(kMaxTimes, n_times - j0);
+        std::copy(times + j0, times + j0 + a.nt, a.t);
+        for (long long p0 = 0; p0 < n_pairs; p0 += kMaxPairs)
+            for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
+                const unsigned np = (unsigned)std::min(kMaxPairs, n_pairs - p0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
+                hipLaunchKernelGGL(kernel, dim3(nt, np), dim3(kInterpTX, kInterpTY), 0, st, a, t0, p0, (long long)j0);
+                PAPOF_HIP(hipGetLastError());
+            }
+    }
+    return PAPOF_OK;
+}
+
+// a descriptor with data, of one of `dtypes`, whose strides are >= 0 (positive: > 0)
+bool described(const papof_tensor* t, std::initializer_list<int> dtypes, bool positive) {
+    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
+    for (int i = 0; i < 4; i++)
+        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
+    return true;
+}
+
+}  // namespace
+
+}  // namespace papof
+
+using namespace papof;
+
+extern "C" int papof_interp_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                   const papof_tensor* frames2, int height, int width, int c, const papof_tensor* flow_fw,
+                                   const papof_tensor* flow_bw, const papof_tensor* occlusion, int n_times,
+                                   const double* times, const papof_tensor* out, long long time_stride, void* stream) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
+    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    if (!described(frames, I, false) || (sequence ? frames2 != nullptr : !described(frames2, I, false))) return PAPOF_EINVAL;
+    if (!described(flow_fw, F, false) || !described(flow_bw, F, false)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, false)) return PAPOF_EINVAL;
+    if (!described(out, I, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
+    if (n_times < 1 || !times) return PAPOF_EINVAL;
+    for (int j = 0; j < n_times; j++)
+        if (!std::isfinite(times[j]) || !(times[j] > 0.0 && times[j] < 1.0)) return PAPOF_EINVAL;
+    InterpArgs a{};
+    a.f0 = *frames;
+    a.f1 = sequence ? *frames : *frames2;
+    a.fw = *flow_fw;
+    a.bw = *flow_bw;
+    if (occlusion) a.occ = *occlusion;
+    a.out = *out;
+    a.tstride = time_stride;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    a.seq = sequence ? 1 : 0;
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_interp(static_cast<hipStream_t>(stream), a, n_pairs, n_times, times);
+}

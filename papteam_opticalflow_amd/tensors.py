@@ -25,6 +25,12 @@ in one HIP kernel, dropping a point where the forward-backward check fails; `tra
 
     tv = track_video(frames, 5, queries, layout="NHWC")   # queries (N, 3) rows (t0, x, y); tv.tracks (T, N, 2), tv.visible (T, N)
 
+Frame interpolation: `interpolate` (include/papof.h: papof_interp_tensor) makes the frames at times t in (0, 1) between the
+two frames of each pair from its forward and backward flows and, optionally, its occlusion mask, in one HIP kernel;
+`interpolate_pairs` and `interpolate_video` compute the flows first (flow_pairs_fb / flow_video_fb).
+
+    iv = interpolate_video(frames, 5, factor=3, layout="NHWC")   # iv.video: (3 (T - 1) + 1, H, W, C), frames at 3x the rate
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -40,6 +46,8 @@ CONSISTENCY = (0.01, 0.5)  # (alpha1, alpha2) of Sundaram et al.
 FlowFB = collections.namedtuple("FlowFB", "flow_fw flow_bw warpI2_fw warpI2_bw occlusion timing")
 Tracks = collections.namedtuple("Tracks", "tracks visible")
 TrackVideo = collections.namedtuple("TrackVideo", "tracks visible flow_fw flow_bw timing")
+InterpPairs = collections.namedtuple("InterpPairs", "frames flow_fw flow_bw occlusion timing")
+Interp = collections.namedtuple("Interp", "video flow_fw flow_bw occlusion timing")
 
 _lock = threading.Lock()
 _handles = {}  # device ordinal -> (Papof, lock of its calls)
@@ -378,3 +386,187 @@ def track_video(frames, pyramidLevels, queries=None, *, layout="NCHW", consisten
     fb = _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, None, solver)
     tr = _track(fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), queries, alphas)
     return TrackVideo(tr.tracks, tr.visible, fb.flow_fw, fb.flow_bw, fb.timing)
+
+
+def _times(times):
+    """the times as a list of floats, each finite and strictly inside (0, 1) -- TypeError / ValueError otherwise.  A tensor
+    is read on the host (a device tensor waits for its stream)."""
+    torch = _torch()
+    if isinstance(times, torch.Tensor):
+        if times.dim() > 1 or times.dtype == torch.bool or times.is_complex():
+            raise TypeError("times must be a float, a sequence or a 1-D real tensor, got %s of shape %s"
+                            % (times.dtype, tuple(times.shape)))
+        ts = [float(x) for x in times.reshape(-1).tolist()]
+    elif isinstance(times, (int, float)) and not isinstance(times, bool):
+        ts = [float(times)]
+    else:
+        try:
+            ts = [float(x) for x in times]
+        except (TypeError, ValueError):
+            raise TypeError("times must be a float, a sequence of floats or a 1-D tensor, got %r" % (times,)) from None
+    if not ts:
+        raise ValueError("times is empty")
+    for x in ts:
+        if not (math.isfinite(x) and 0.0 < x < 1.0):
+            raise ValueError("every time must lie strictly inside (0, 1), got %r" % x)
+    return ts
+
+
+def _out_code(out_dtype):
+    torch = _torch()
+    codes = {torch.uint8: capi.DTYPE_U8, torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if out_dtype not in codes:
+        raise TypeError("out_dtype must be torch.uint8, torch.float32 or torch.float64, got %s" % out_dtype)
+    return codes[out_dtype]
+
+
+def _check_interp_flows(flow_fw, flow_bw, occlusion, B, H, W, dev):
+    """the flows (B, 2, H, W) and the optional mask of interpolate on `dev`: (dtype codes of the flows, the mask as uint8)"""
+    torch = _torch()
+    codes = _check_flows(flow_fw, flow_bw)
+    if tuple(flow_fw.shape) != (B, 2, H, W):
+        raise ValueError("the flows must be (B, 2, H, W) = %s for these frames, got %s" % ((B, 2, H, W),
+                                                                                         tuple(flow_fw.shape)))
+    if flow_fw.device != dev:
+        raise ValueError("the flows are on %s, the frames on %s: all must be on one device" % (flow_fw.device, dev))
+    if occlusion is not None:
+        if not isinstance(occlusion, torch.Tensor):
+            raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
+        if occlusion.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
+        if tuple(occlusion.shape) != (B, 2, H, W):
+            raise ValueError("occlusion must be (B, 2, H, W) = %s, got %s" % ((B, 2, H, W), tuple(occlusion.shape)))
+        if occlusion.device != dev:
+            raise ValueError("occlusion is on %s, the frames on %s: all must be on one device" % (occlusion.device, dev))
+        occlusion = occlusion.view(torch.uint8)
+    return codes, occlusion
+
+
+def _flow_struct(f, code):
+    return _struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), code)
+
+
+def _interp(d_in, sequence, n_pairs, H, W, C, flows, codes, occlusion, times, out, d_out, time_stride, dev):
+    """papof_interp_tensor on the current stream of `dev`, writing through d_out"""
+    torch = _torch()
+    index = _index(dev)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
+    ts = (ctypes.c_double * len(times))(*times)
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_interp_tensor(gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+                                       None if sequence else ctypes.byref(d_in[1]), H, W, C, ctypes.byref(d_f[0]),
+                                       ctypes.byref(d_f[1]), ctypes.byref(d_occ) if d_occ is not None else None, len(times),
+                                       ts, ctypes.byref(d_out), time_stride, ctypes.c_void_p(stream or None))
+    capi._chk(rc, "papof_interp_tensor")
+    return out
+
+
+def _new_interp_out(B, K, H, W, C, layout, out_dtype, dev):
+    """a new (B, K, C, H, W) (NCHW) or (B, K, H, W, C) (NHWC) tensor, its descriptor and time stride"""
+    torch = _torch()
+    if layout == "NCHW":
+        out = torch.empty((B, K, C, H, W), dtype=out_dtype, device=dev)
+        strides = (out.stride(0), out.stride(3), out.stride(4), out.stride(2))
+    else:
+        out = torch.empty((B, K, H, W, C), dtype=out_dtype, device=dev)
+        strides = (out.stride(0), out.stride(2), out.stride(3), out.stride(4))
+    return out, _struct(out, strides, _out_code(out_dtype)), out.stride(1)
+
+
+def interpolate(im1, im2, flow_fw, flow_bw, times, *, occlusion=None, layout="NCHW", out_dtype=None):
+    """Motion-compensated interpolation between the frames of the pairs (im1[i], im2[i]): two tensors of one shape,
+    (B, C, H, W) or (B, H, W, C) by `layout`, of uint8 (read as x / 255), float32 or float64, any strides, on one HIP
+    device.  flow_fw, flow_bw: (B, 2, H, W) float32 / float64, im1 -> im2 and back, as flow_pairs_fb returns them.
+    occlusion: None, or the (B, 2, H, W) bool / uint8 mask of flow_pairs_fb (channel 0: pixels of im1 occluded in im2,
+    channel 1 the reverse).  times: a float, a sequence or a 1-D tensor of values strictly inside (0, 1), read on the host.
+    Returns the frames at those times, (B, K, C, H, W) for NCHW or (B, K, H, W, C) for NHWC, K = len(times), of out_dtype:
+    uint8 (clamp(rint(255 x), 0, 255)), float32 or float64 -- by default the frames' dtype (torch.promote_types of the two).
+    Each output pixel p samples im1 at p + F_t->0 and im2 at p + F_t->1, F_t->0 = -(1 - t) t F01 + t^2 F10,
+    F_t->1 = (1 - t)^2 F01 - (1 - t) t F10 with the flows at p, and blends the two with weights 1 - t and t, each lowered
+    where the mask says its sample is hidden in the other frame; include/papof.h (papof_interp_tensor) states it exactly.
+    Enqueued on the current stream; returns without waiting."""
+    torch = _torch()
+    ts, descs, _ = _check([("im1", im1), ("im2", im2)], layout, None, 1)
+    times = _times(times)
+    if out_dtype is None:
+        out_dtype = torch.promote_types(ts[0].dtype, ts[1].dtype)
+    _out_code(out_dtype)
+    (B, H, W, C), _, _ = descs[0]
+    codes, occ = _check_interp_flows(flow_fw, flow_bw, occlusion, B, H, W, ts[0].device)
+    out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    return _interp(d_in, False, B, H, W, C, (flow_fw, flow_bw), codes, occ, times, out, d_out, tstride, ts[0].device)
+
+
+def interpolate_pairs(im1, im2, pyramidLevels, times, *, layout="NCHW", consistency=CONSISTENCY, out_dtype=None, **solver):
+    """flow_pairs_fb(im1, im2, pyramidLevels, layout=layout, consistency=consistency, **solver) -- float64 flows whatever
+    out_dtype is -- followed by interpolate on its flows and mask (None for consistency=None: no mask).  Returns
+    InterpPairs(frames (B, K, ...) as interpolate's, flow_fw, flow_bw, occlusion, timing of the flow call).  Every argument
+    error raises before anything is launched; the flows are complete on return, the frames are enqueued on the current
+    stream behind them."""
+    torch = _torch()
+    alphas = _alphas(consistency) if consistency is not None else None
+    ts, descs, _ = _check([("im1", im1), ("im2", im2)], layout, None, pyramidLevels)
+    times = _times(times)
+    if out_dtype is None:
+        out_dtype = torch.promote_types(ts[0].dtype, ts[1].dtype)
+    _out_code(out_dtype)
+    (B, H, W, C), _, _ = descs[0]
+    fb = _run_fb(ts, descs, False, B, layout, torch.float64, pyramidLevels, alphas, solver)
+    occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
+    out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    _interp(d_in, False, B, H, W, C, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, times, out, d_out,
+            tstride, ts[0].device)
+    return InterpPairs(out, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
+
+
+def _converted(frames, out_dtype):
+    """frames in out_dtype by the kernel's conversions: the same dtype bit for bit; uint8 -> float as x / 255.0 in float64
+    (then one rounding to float32); float -> uint8 as clamp(rint(255 x), 0, 255) in float64, NaN -> 0"""
+    torch = _torch()
+    if frames.dtype == out_dtype:
+        return frames
+    x = frames.double()
+    if frames.dtype == torch.uint8:
+        x = x / 255.0
+    if out_dtype == torch.uint8:
+        x = torch.nan_to_num(torch.round(255.0 * x), nan=0.0).clamp(0.0, 255.0)
+    return x.to(out_dtype)
+
+
+def interpolate_video(frames, pyramidLevels, factor=2, *, layout="NCHW", consistency=CONSISTENCY, out_dtype=None,
+                      **solver):
+    """A video of T >= 2 frames at `factor` (an integer >= 2) times its frame rate: flow_video_fb(frames, pyramidLevels,
+    layout=layout, consistency=consistency, **solver) -- float64 flows whatever out_dtype is -- then interpolate between
+    every two consecutive frames at the times j / factor, j = 1 .. factor - 1.  Returns Interp(video, flow_fw, flow_bw,
+    occlusion, timing of the flow call): video has (T - 1) factor + 1 frames in `layout` and out_dtype (by default the
+    frames'); frame k factor is input frame k, copied bit for bit (converted as interpolate converts when out_dtype
+    differs), and the frames between are written by the kernel straight into the video.  Every argument error raises
+    before anything is launched; the flows are complete on return, the video is enqueued on the current stream."""
+    torch = _torch()
+    alphas = _alphas(consistency) if consistency is not None else None
+    ts, descs, _ = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    if isinstance(factor, bool) or not isinstance(factor, int) or factor < 2:
+        raise ValueError("factor must be an integer >= 2, got %r" % (factor,))
+    if out_dtype is None:
+        out_dtype = ts[0].dtype
+    code = _out_code(out_dtype)
+    (T, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, alphas, solver)
+    n = (T - 1) * factor + 1
+    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
+    video = torch.empty(shape, dtype=out_dtype, device=dev)
+    video[::factor].copy_(_converted(ts[0], out_dtype))
+    vs = descriptor(video, layout)[1]
+    d_out = _struct(video[1], (factor * vs[0],) + vs[1:], code)
+    occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
+    times = [j / factor for j in range(1, factor)]
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    _interp(d_in, True, T - 1, H, W, C, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, times, video, d_out,
+            vs[0], dev)
+    return Interp(video, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
