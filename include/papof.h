@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 111 /* 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 112 /* 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -420,6 +420,39 @@ int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const
                                const papof_params* params, const papof_tensor* flow_fw, const papof_tensor* warp_fw,
                                const papof_tensor* flow_bw, const papof_tensor* warp_bw, const papof_tensor* occlusion,
                                double alpha1, double alpha2, void* stream, double timing_sec[PAPOF_N_TIMERS]);
+
+/* papof_flow_batch_tensor (and _fb) started from the caller's initial flow instead of zero (refining a flow from elsewhere,
+ * large motion given a prior, a two-pass video flow).  init, init_fw, init_bw: NULL (zero flow: the calls above, bit for bit),
+ * or a float32 (widened exactly) or float64 tensor (pair, row, column, {vx, vy}) of the frames' height and width with any
+ * non-negative strides (a zero pair stride: one flow for every pair).  _fb_init: init_fw starts the forward pairs, init_bw
+ * the backward ones; either may be NULL (zero for that direction).  Everything else is papof_flow_batch_tensor's (_fb's).
+ *
+ * The rule.  L = pyramid_levels; ratio = params->ratio, or 0.75 where it lies outside [0.4, 0.98] (the pyramid's clamp; the
+ * up-sampling between levels multiplies by 1 / ratio).  The frames' Gaussian pyramid (papof_stage_pyramid: level i from level
+ * src(i) of the same plan, Gaussian smoothing then bilinear resize) is applied to the initial flow as a two-channel image,
+ * P_k(init) its level k; it is the pyramid papof_stage_pyramid returns for the (height, width, 2) array (vx, vy) bit for
+ * bit.  s = 1.0 multiplied by ratio L - 1 times in fp64.  Then the coarsest level L - 1 starts from
+ *     L == 1:  (u, v) = init;
+ *     L >= 2:  (u, v) = P_{L-1}(init) * s, one fp64 rounding per element,
+ * instead of (0, 0), and it is entered as every finer level is (src/OpticalFlow.cpp:813-816): frame 2's features are warped
+ * at (u, v) -- warpFL with bilinear interpolation, warpImageBicubicRef without threshold with bicubic -- instead of being
+ * copied.  Everything after that is unchanged: the levels' solves, the up-sampling, the Laplacian-noise guard with LapPara
+ * starting at 0.02 on the coarsest level's first iteration, the final bicubic warp.  On the default branches the warp at the
+ * flow is part of the solve already, so an all-zero init gives the bits of no init (the flow planes are +0.0 either way).
+ * PAPOF_EINVAL, before anything is enqueued: what the call without init refuses, a non-NULL init descriptor with NULL data,
+ * a dtype other than F32 / F64, a negative stride.  PAPOF_EINVAL after the entry wait, with nothing written to any output: a
+ * component that is NaN, +-Inf or larger than 1e6 in magnitude.  (The device step that reads init also writes 0 in place of
+ * any such value, so none reaches a sampler.) */
+int papof_flow_batch_tensor_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                 const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                                 const papof_params* params, const papof_tensor* init, const papof_tensor* flow,
+                                 const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]);
+int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                    const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                                    const papof_params* params, const papof_tensor* init_fw, const papof_tensor* init_bw,
+                                    const papof_tensor* flow_fw, const papof_tensor* warp_fw, const papof_tensor* flow_bw,
+                                    const papof_tensor* warp_bw, const papof_tensor* occlusion, double alpha1, double alpha2,
+                                    void* stream, double timing_sec[PAPOF_N_TIMERS]);
 
 /* The forward-backward consistency check of papof_flow_batch_tensor_fb on any two flow tensors: flow_fw, flow_bw float32
  * (widened exactly) or float64, (pair, row, column, {vx, vy}), any non-negative strides; occlusion as there.  For the same

@@ -61,7 +61,8 @@ SYMBOLS = [
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
     "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
-    "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor",
+    "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
+    "papof_flow_batch_tensor_fb_init",
 ]
 
 
@@ -161,6 +162,12 @@ def load():
     L.papof_flow_batch_tensor_fb.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, _T, _T, _T,
                                              c_double, c_double, c_void_p, _D]
     L.papof_flow_batch_tensor_fb.restype = c_int
+    L.papof_flow_batch_tensor_init.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, _T,
+                                               c_void_p, _D]
+    L.papof_flow_batch_tensor_init.restype = c_int
+    L.papof_flow_batch_tensor_fb_init.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, PP, _T, _T, _T,
+                                                  _T, _T, _T, _T, c_double, c_double, c_void_p, _D]
+    L.papof_flow_batch_tensor_fb_init.restype = c_int
     L.papof_fb_check_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_double, c_double, _T, c_void_p]
     L.papof_fb_check_tensor.restype = c_int
     L.papof_track_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, _T, c_int, c_double, c_double, _T, _T,

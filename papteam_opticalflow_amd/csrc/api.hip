@@ -143,6 +143,57 @@ int smooth_and_resize(papof_handle* h, const double* src, double* dst, double* t
     return resize(h, tmp_b, dst, p.sh, p.sw, C, dh, dw, p.rate, p.rate, false, 0.0);
 }
 
+// The caller's initial flow at the coarsest level (include/papof.h, papof_flow_batch_tensor_init: the rule).  Pairs 0 ..
+// pairs_a - 1 read `a`, the next pairs_b read `b` (NULL: zero flow) through k_ingest_frames -- a pair's (vx, vy) are a frame's
+// two channels, so X is [pair][2][H * W], the layout of the chain's flow -- and refused values become +0.0 (k_init_sanitize).
+// Then the frames' own pyramid steps (smooth_and_resize, on all pairs' planes at once) along the chain of the coarsest level's
+// ancestors in the plan, the last step scaled by s = ratio^(L - 1) in k_resize's post-scale: one rounding per element.
+// X and Y hold 2 (pairs_a + pairs_b) full-resolution planes each; T, of t_planes full-resolution planes, is the temporary of
+// the two-pass filter (half-widths beyond the fused kernel's), taken in chunks of planes when it is smaller.  `out` is X or Y,
+// the coarsest level's (u, v) at its pitch, v behind u.
+int reduce_init(papof_handle* h, const papof_tensor* a, const papof_tensor* b, int pairs_a, int pairs_b, int H, int W,
+                const std::vector<Level>& L, const std::vector<PyrPlan>& plan, double ratio, double* X, double* Y, double* T,
+                size_t t_planes, double*& out) {
+    const size_t np0 = (size_t)H * W;
+    const int planes = 2 * (pairs_a + pairs_b), levels = (int)L.size();
+    double* const parts[2] = {X, X + (size_t)pairs_a * 2 * np0};
+    const papof_tensor* const src[2] = {a, b};
+    const int n[2] = {pairs_a, pairs_b};
+    for (int i = 0; i < 2; i++) {
+        if (n[i] == 0) continue;
+        if (src[i])
+            PAPOF_TRY(ingest_frames(h, *src[i], nullptr, parts[i], H, W, 2, n[i]));
+        else
+            PAPOF_HIP(hipMemsetAsync(parts[i], 0, (size_t)n[i] * 2 * np0 * sizeof(double), h->stream));
+    }
+    PAPOF_TRY(init_sanitize(h, X, (size_t)planes * np0));
+    out = X;
+    if (levels == 1) return PAPOF_OK;
+    std::vector<int> chain;  // the coarsest level's ancestors, finest first (level 0 excluded)
+    for (int i = levels - 1; i > 0; i = plan[i].src_level) chain.insert(chain.begin(), i);
+    double s = 1.0;
+    for (int i = 1; i < levels; i++) s *= ratio;
+    double *cur = X, *other = Y;
+    for (const int i : chain) {
+        const PyrPlan& p = plan[i];
+        const bool last = i == levels - 1;
+        const Taps g = gaussian_taps(p.sigma, p.fsize);
+        if (g.fsize == 0 && g.t[0] == 1.0) {  // smooth_and_resize's identity smoothing: the resize reads the source
+            PAPOF_TRY(resize(h, cur, other, p.sh, p.sw, planes, L[i].h, L[i].w, p.rate, p.rate, last, last ? s : 0.0));
+            std::swap(cur, other);
+            continue;
+        }
+        const size_t ns = (size_t)p.sw * p.sh;
+        const int chunk = filter_hv_needs_tmp(g, g) ? (int)std::min<size_t>((size_t)planes, t_planes * np0 / ns) : planes;
+        if (chunk < 1) return PAPOF_EINVAL;
+        for (int c0 = 0; c0 < planes; c0 += chunk)
+            PAPOF_TRY(filter_hv(h, cur + c0 * ns, other + c0 * ns, T, p.sh, p.sw, std::min(chunk, planes - c0), g, g));
+        PAPOF_TRY(resize(h, other, cur, p.sh, p.sw, planes, L[i].h, L[i].w, p.rate, p.rate, last, last ? s : 0.0));
+    }
+    out = cur;
+    return PAPOF_OK;
+}
+
 int build_pyramid(papof_handle* h, const std::vector<Level>& L, const std::vector<PyrPlan>& plan, int C, bool second,
                   double* tmp_a, double* tmp_b) {
     for (size_t i = 1; i < L.size(); i++) {
@@ -408,8 +459,10 @@ bool seq_matches(const papof_handle* h, int H, int W, int C, int levels, double 
 }
 
 // The whole call on device-resident buffers: ONE pass (flow_device below runs it once, or twice: LapGuard).
+// init: the caller's initial flow of this pair (papof_flow_batch_tensor_init), or NULL: zero.
 int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, int H, int W, int C, int levels,
-              const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing, LapGuard* lg) {
+              const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing, LapGuard* lg,
+              const papof_tensor* init = nullptr) {
     const double t_entry = wall();
     PAPOF_TRY(check_params(P, levels));
     double ratio = P.ratio;
@@ -678,7 +731,20 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
             double* const out_u = k == 0 ? d_vx : nullptr;
             double* const out_v = k == 0 ? d_vy : nullptr;
             const bool fold_warp = !B.bgx && !B.gm;  // the warped frame 2 lives only inside the smoothing kernel
-            if (k == levels - 1) {  // src/OpticalFlow.cpp:801-806
+            if (k == levels - 1 && init) {  // the caller's initial flow (reduce_init; u, u2 and warp are free until here),
+                // and the coarsest level entered as every finer one is: frame 2's features warped at (u, v)
+                double* r = nullptr;
+                PAPOF_TRY(reduce_init(h, init, nullptr, 1, 0, H, W, L, plan, ratio, u, u2, warp, (size_t)fc, r));
+                if (r != u) std::swap(u, u2);
+                v = u + np;
+                v2 = u2 + np;
+                if (B.bgx) {
+                    PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
+                    PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, u, v, warp, lh, lw, fc, nullptr, true, false));
+                } else if (!fold_warp) {
+                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc));
+                }
+            } else if (k == levels - 1) {  // src/OpticalFlow.cpp:801-806
                 v = u + np;
                 v2 = u2 + np;
                 PAPOF_HIP(hipMemsetAsync(u, 0, 2 * np * sizeof(double), h->stream));
@@ -799,12 +865,13 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
 // The whole call on device-resident buffers, with the Laplacian-noise guard (LapGuard): the optimistic pass, and the exact
 // pass behind it when a consulted estimate is left without a proof.
 int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, int H, int W, int C, int levels,
-                const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
+                const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing,
+                const papof_tensor* init = nullptr) {
     LapGuard lg;
     const int fc = feature_channels(C);
     lg.on = h->lap_guard && op != kSeqPrime && P.noise_model == PAPOF_NOISE_LAPLACIAN && fc <= 8 && levels >= 1 &&
             h->lap_flags_dev != nullptr;
-    if (!lg.on) return flow_pass(h, fa, fb, op, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, nullptr);
+    if (!lg.on) return flow_pass(h, fa, fb, op, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, nullptr, init);
     lg.flags = h->lap_flags_dev;
     lg.lap = h->lap_dev;
     lg.scratch = h->lap_scratch_dev;
@@ -827,7 +894,7 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
         lg.slot = 0;
         lg.slot_level.clear();
         lg.slot_channels.clear();
-        PAPOF_TRY(flow_pass(h, fa, fb, op, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, &lg));
+        PAPOF_TRY(flow_pass(h, fa, fb, op, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, &lg, init));
         if (pass == 1 && timing) timing[PAPOF_T_TOTAL] += first_pass_total;  // the call cost both passes (phases: the exact pass's)
         if (!lg.collect) return PAPOF_OK;
         const int unknown = lg.unknown(h->lap_flags_host);
@@ -854,10 +921,11 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
 
 // papof_flow_batch_tensor's pairs that run on their own (batch.hip): planar frames already on the device, the single call
 int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,
-                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
+                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing,
+                       const papof_tensor* init) {
     FrameIn a{f1, false}, b{f2, false};
     a.planar = b.planar = true;
-    return flow_device(h, a, b, kPair, H, W, C, levels, P, d_vx, d_vy, d_warp, timing);
+    return flow_device(h, a, b, kPair, H, W, C, levels, P, d_vx, d_vy, d_warp, timing, init);
 }
 
 }  // namespace papof
@@ -1012,6 +1080,7 @@ void papof_destroy(papof_handle* h) {
     if (h->sync_words) hipFree(h->sync_words);
     if (h->stage_dev) hipFree(h->stage_dev);
     if (h->tensor_scratch) hipFree(h->tensor_scratch);
+    if (h->init_flag_dev) hipFree(h->init_flag_dev);
     if (h->entry_event) hipEventDestroy(h->entry_event);
     if (h->lap_flags_host) hipHostFree(h->lap_flags_host);  // the stamps live inside these two blocks
     if (h->lap_flags_dev) hipFree(h->lap_flags_dev);

@@ -57,6 +57,10 @@ struct BatchFrames {
     bool u8 = false;
     const papof_tensor* a = nullptr;    // device frames: a sequence, or the first frames of the pairs ...
     const papof_tensor* b = nullptr;    // ... and their second frames (pairs only)
+    // the caller's initial flows (papof_flow_batch_tensor_init), from the batch's first pair on: of the B forward pairs and of
+    // the B backward ones (with_bw); NULL: zero.  Both NULL: the chain starts from zero flow exactly as it always has.
+    const papof_tensor* init_fw = nullptr;
+    const papof_tensor* init_bw = nullptr;
 };
 
 bool batch_applies(const papof_handle* h, int B, int H, int W, int C, int levels, const papof_params& P) {
@@ -230,7 +234,13 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             const int lw = L[k].w, lh = L[k].h;
             const size_t np = (size_t)lw * lh;
             const int K = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
-            if (k == levels - 1) {
+            if (k == levels - 1 && (frames.init_fw || frames.init_bw)) {
+                // the caller's initial flows of all pairs (reduce_init): uvA, uvB and the warped image are free until here
+                double* r = nullptr;
+                PAPOF_TRY(reduce_init(h, frames.init_fw, frames.init_bw, B, with_bw ? B : 0, H, W, L, plan, ratio, uvB, uvA, warp,
+                                      (size_t)NP * C, r));
+                if (r != uv) std::swap(uv, uv2);
+            } else if (k == levels - 1) {
                 PAPOF_HIP(hipMemsetAsync(uv, 0, (size_t)NP * 2 * np * sizeof(double), st));  // :801-806 (the warp is folded in)
             } else {  // :809-812: bilinear up-sampling times 1 / ratio, all pairs' u and v in one launch
                 PAPOF_TRY(resize(h, uv, uv2, ph, pw, 2 * NP, lh, lw, (double)lw / pw, (double)lh / ph, true, 1 / ratio));
@@ -452,6 +462,12 @@ struct TensorOut {
     double a1 = 0, a2 = 0;
 };
 
+// the caller's initial flows (papof_flow_batch_tensor_init, _fb_init): of the forward pairs, of the backward pairs; NULL: zero
+struct TensorInit {
+    const papof_tensor* fw = nullptr;
+    const papof_tensor* bw = nullptr;
+};
+
 papof_tensor planar_flow(const double* uv, int H, int W) {  // the chain's [pair][2][H * W] fp64 flows as a tensor
     papof_tensor t;
     t.data = const_cast<double*>(uv);
@@ -470,9 +486,15 @@ papof_tensor planar_flow(const double* uv, int H, int W) {  // the chain's [pair
 // flows before anything else is laid out in the arena (or the scratch) -- the mask does not depend on the output dtype.
 // tm accumulates the phases.
 int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor& fa, const papof_tensor* fb, int H, int W,
-                      int C, int levels, const papof_params& P, const TensorOut& o, double* tm) {
+                      int C, int levels, const papof_params& P, const TensorOut& o, const TensorInit& ini, double* tm) {
     const size_t np0 = (size_t)H * W, frame = np0 * C;
     const bool with_bw = o.flow_bw != nullptr;
+    // an initial flow from pair p on, in `buf` (NULL where there is none)
+    const auto init_at = [](const papof_tensor* t, int p, papof_tensor& buf) -> const papof_tensor* {
+        if (!t) return nullptr;
+        buf = shifted(*t, p);
+        return &buf;
+    };
     // one pair on its own: its two frames into the handle's scratch (planar fp64; not in the arena, which the single call lays
     // out anew), the device call (both passes of the guard), the results out; with backward pairs, the single call on the
     // exchanged frames as well, and the check on the two fp64 flows
@@ -500,13 +522,14 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
             PAPOF_TRY(ingest_frames(h, a, &b, f, H, W, C, 2));
         }
         double t1[PAPOF_N_TIMERS];
-        PAPOF_TRY(flow_device_planar(h, f, f + frame, H, W, C, levels, P, uv, uv + np0, wp, t1));
+        papof_tensor ifw, ibw;
+        PAPOF_TRY(flow_device_planar(h, f, f + frame, H, W, C, levels, P, uv, uv + np0, wp, t1, init_at(ini.fw, p, ifw)));
         PAPOF_TRY(emit_outputs(h, uv, shifted(*o.flow, p), true, H, W, 2, 1));
         PAPOF_TRY(emit_outputs(h, wp, shifted(*o.warp, p), false, H, W, C, 1));
         for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
         if (with_bw) {
             double *uvb = uv + 2 * np0, *wpb = wp + frame;
-            PAPOF_TRY(flow_device_planar(h, f + frame, f, H, W, C, levels, P, uvb, uvb + np0, wpb, t1));
+            PAPOF_TRY(flow_device_planar(h, f + frame, f, H, W, C, levels, P, uvb, uvb + np0, wpb, t1, init_at(ini.bw, p, ibw)));
             PAPOF_TRY(emit_outputs(h, uvb, shifted(*o.flow_bw, p), true, H, W, 2, 1));
             PAPOF_TRY(emit_outputs(h, wpb, shifted(*o.warp_bw, p), false, H, W, C, 1));
             for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
@@ -528,6 +551,9 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         BatchFrames bf;
         bf.a = &a;
         bf.b = sequence ? nullptr : &b;
+        papof_tensor ifw, ibw;
+        bf.init_fw = init_at(ini.fw, p0, ifw);
+        bf.init_bw = with_bw ? init_at(ini.bw, p0, ibw) : nullptr;
         BatchOut out;
         double t1[PAPOF_N_TIMERS];
         const int rc = flow_batch_device(h, nb, sequence, with_bw, bf, H, W, C, levels, P, t1, out);
@@ -571,7 +597,7 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
 // the entry of papof_flow_batch_tensor(_fb) after the descriptors' checks: parameters, entry wait, the call, complete on return
 int tensor_entry(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2, int height,
                  int width, int c, int pyramid_levels, const papof_params* params, const TensorOut& o, void* stream,
-                 double* timing_sec) {
+                 double* timing_sec, const TensorInit& ini = TensorInit{}) {
     papof_params P;
     if (params)
         P = *params;
@@ -586,9 +612,19 @@ int tensor_entry(papof_handle* h, int n_pairs, int sequence, const papof_tensor*
     PAPOF_HIP(hipEventRecord(h->entry_event, static_cast<hipStream_t>(stream)));
     PAPOF_HIP(hipStreamWaitEvent(h->stream, h->entry_event, 0));
     if (h->prep_stream) PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->entry_event, 0));
+    if (ini.fw || ini.bw) {  // the initial flows' values, behind the entry wait and before anything is written: refused -> EINVAL
+        if (!h->init_flag_dev) PAPOF_HIP(hipMalloc((void**)&h->init_flag_dev, sizeof(unsigned)));
+        PAPOF_HIP(hipMemsetAsync(h->init_flag_dev, 0, sizeof(unsigned), h->stream));
+        for (const papof_tensor* t : {ini.fw, ini.bw})
+            if (t) PAPOF_TRY(init_check(h, *t, n_pairs, height, width, h->init_flag_dev));
+        unsigned refused = 0;
+        PAPOF_HIP(hipMemcpyAsync(&refused, h->init_flag_dev, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        PAPOF_HIP(hipStreamSynchronize(h->stream));
+        if (refused) return PAPOF_EINVAL;
+    }
     double tm[PAPOF_N_TIMERS];
     std::memset(tm, 0, sizeof tm);
-    const int rc = flow_batch_tensor(h, n_pairs, sequence, *frames, frames2, height, width, c, pyramid_levels, P, o, tm);
+    const int rc = flow_batch_tensor(h, n_pairs, sequence, *frames, frames2, height, width, c, pyramid_levels, P, o, ini, tm);
     const hipError_t se = hipStreamSynchronize(h->stream);  // complete on return: the emits are the last work of the call
     PAPOF_TRY(rc);
     if (se != hipSuccess) {
@@ -608,6 +644,10 @@ bool valid_mask(const papof_tensor* t) {  // the uint8 occlusion output: every s
 }
 
 bool valid_alphas(double a1, double a2) { return std::isfinite(a1) && std::isfinite(a2) && a1 >= 0 && a2 >= 0; }
+
+bool valid_init(const papof_tensor* t) {  // an initial flow: absent, or float32 / float64 data with non-negative strides
+    return !t || (valid_tensor(t, false) && t->dtype != PAPOF_DTYPE_U8);
+}
 
 }  // namespace
 
@@ -663,6 +703,51 @@ int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const
     o.a1 = alpha1;
     o.a2 = alpha2;
     return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec);
+}
+
+int papof_flow_batch_tensor_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                 const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                                 const papof_params* params, const papof_tensor* init, const papof_tensor* flow,
+                                 const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
+    if (!valid_tensor(frames, false) || !valid_tensor(flow, true) || !valid_tensor(warpI2, true)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
+    if (!valid_init(init)) return PAPOF_EINVAL;
+    TensorOut o;
+    o.flow = flow;
+    o.warp = warpI2;
+    TensorInit ini;
+    ini.fw = init;
+    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec,
+                        ini);
+}
+
+int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                    const papof_tensor* frames2, int height, int width, int c, int pyramid_levels,
+                                    const papof_params* params, const papof_tensor* init_fw, const papof_tensor* init_bw,
+                                    const papof_tensor* flow_fw, const papof_tensor* warp_fw, const papof_tensor* flow_bw,
+                                    const papof_tensor* warp_bw, const papof_tensor* occlusion, double alpha1, double alpha2,
+                                    void* stream, double timing_sec[PAPOF_N_TIMERS]) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
+    if (!valid_tensor(frames, false) || !valid_tensor(flow_fw, true) || !valid_tensor(warp_fw, true) ||
+        !valid_tensor(flow_bw, true) || !valid_tensor(warp_bw, true))
+        return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
+    if ((occlusion && !valid_mask(occlusion)) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
+    if (!valid_init(init_fw) || !valid_init(init_bw)) return PAPOF_EINVAL;
+    TensorOut o;
+    o.flow = flow_fw;
+    o.warp = warp_fw;
+    o.flow_bw = flow_bw;
+    o.warp_bw = warp_bw;
+    o.occ = occlusion;
+    o.a1 = alpha1;
+    o.a2 = alpha2;
+    TensorInit ini;
+    ini.fw = init_fw;
+    ini.bw = init_bw;
+    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec,
+                        ini);
 }
 
 int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,

@@ -225,6 +225,7 @@ struct papof_handle {
     double* tensor_scratch = nullptr;
     size_t tensor_scratch_bytes = 0;
     hipEvent_t entry_event = nullptr;
+    unsigned* init_flag_dev = nullptr;  // the refusal flag of a caller's initial flow (papof_flow_batch_tensor_init)
     bool use_dpp = false;            // wave_shr/wave_shl DPP moves verified on this device (else ds_bpermute)
     int sor_depth = 0;               // software-pipeline depth R (steps) of the exact-order SOR kernel; 0 = by level size
     unsigned long long* sor_dbg = nullptr;  // device buffer for per-task wait statistics (PAPOF_SOR_DBG)
@@ -322,6 +323,11 @@ int planar_to_hwc(papof_handle* h, const double* planar, double* hwc, int H, int
 int ingest_frames(papof_handle* h, const papof_tensor& a, const papof_tensor* b, double* planar, int H, int W, int C,
                   int frames);
 int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bool comp_major, int H, int W, int K, int pairs);
+// the caller's initial flow (papof_flow_batch_tensor_init): raise *flag when a component of `pairs` pairs of the strided
+// float32 / float64 tensor (pair, row, column, component) is NaN, +-Inf or beyond 1e6 in magnitude; write +0.0 over every such
+// value of n planar fp64 values
+int init_check(papof_handle* h, const papof_tensor& t, int pairs, int H, int W, unsigned* flag);
+int init_sanitize(papof_handle* h, double* planar, size_t n);
 // forward-backward consistency of `pairs` flow pairs (F32 / F64, (pair, row, column, component)) into the uint8 mask
 // (pair, row, column, {fw, bw}) on stream st: kernels.hip, k_fb_check
 int fb_check(papof_handle* h, hipStream_t st, const papof_tensor& fw, const papof_tensor& bw, const papof_tensor& mask,
@@ -332,6 +338,7 @@ int filter_v(papof_handle* h, const double* src, double* dst, int H, int W, int 
              const Rect* rc = nullptr);
 int filter_hv(papof_handle* h, const double* src, double* dst, double* tmp, int H, int W, int planes, const Taps& fh,
               const Taps& fv);  // both passes in one launch (same bits); `tmp` only for half-widths beyond the fused kernel's
+bool filter_hv_needs_tmp(const Taps& fh, const Taps& fv);  // ... which these are
 int resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int planes, int dh, int dw, double xr,
            double yr, bool use_post, double post, const Rect* rc = nullptr);
 int im2feature(papof_handle* h, const double* im, double* feat, int H, int W, int C, unsigned* nz = nullptr, int frames = 1,

@@ -136,7 +136,13 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
                     const papof_params* params, double* const* vx, double* const* vy, double* const* warpI2, double* timing_sec);
 // the device call on two planar fp64 frames already on the device (api.hip: flow_device, both passes of the guard); returns
 // with the results written
+// with the caller's initial flow of the pair (init: one pair of a strided float32 / float64 tensor; NULL: zero)
 int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,
-                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing);
+                       const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing,
+                       const papof_tensor* init = nullptr);
+// the initial flow's coarsest level for the pairs of a call (api.hip: the rule of include/papof.h)
+int reduce_init(papof_handle* h, const papof_tensor* a, const papof_tensor* b, int pairs_a, int pairs_b, int H, int W,
+                const std::vector<Level>& L, const std::vector<PyrPlan>& plan, double ratio, double* X, double* Y, double* T,
+                size_t t_planes, double*& out);
 
 }  // namespace papof

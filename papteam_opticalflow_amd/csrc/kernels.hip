@@ -101,6 +101,29 @@ __global__ __launch_bounds__(256) void k_ingest_frames(const papof_tensor a, con
     planar[i] = tensor_load(second ? b.data : a.data, second ? b.dtype : a.dtype, o);
 }
 
+// The caller's initial flow (include/papof.h: papof_flow_batch_tensor_init): a component is refused when it is not a number
+// of magnitude <= kInitMax (NaN and +-Inf fail the comparison).  k_init_check reads a strided float32 / float64 tensor
+// (pair, row, column, component) where it is and raises *flag; k_init_sanitize writes +0.0 over every refused value of the
+// ingested planar flow, so that no refused value reaches a sampler even if a refusal were missed.
+constexpr double kInitMax = 1e6;
+__device__ __forceinline__ bool init_refused(double x) { return !(fabs(x) <= kInitMax); }
+
+__global__ __launch_bounds__(256) void k_init_check(const papof_tensor t, long long H, long long W, long long total,
+                                                    unsigned* __restrict__ flag) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long long np = H * W, p = i / (np * 2), r = i - p * np * 2, c = r / np, px = r - c * np, row = px / W,
+                    col = px - row * W;
+    const long long o = p * t.stride[0] + row * t.stride[1] + col * t.stride[2] + c * t.stride[3];
+    if (init_refused(tensor_load(t.data, t.dtype, o))) atomicOr(flag, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_init_sanitize(double* __restrict__ planar, long long total) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    if (init_refused(planar[i])) planar[i] = 0.0;
+}
+
 // the chain's results -> a strided float32 / float64 tensor.  comp_major: src is [pair][K][H * W] (the flow: K = 2, u then v);
 // else [pair][H * W][K] (warpI2, HWC).  The destination is (pair, row, column, K).
 __global__ __launch_bounds__(256) void k_emit_outputs(const double* __restrict__ src, const papof_tensor dst, int comp_major,
@@ -1824,6 +1847,27 @@ int ingest_frames(papof_handle* h, const papof_tensor& a, const papof_tensor* b,
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
+
+int init_check(papof_handle* h, const papof_tensor& t, int pairs, int H, int W, unsigned* flag) {
+    const long long total = (long long)pairs * H * W * 2, blocks = (total + 255) / 256;
+    if (total <= 0) return PAPOF_OK;
+    if (blocks > 0x7fffffffLL) return PAPOF_EINVAL;
+    hipLaunchKernelGGL(k_init_check, dim3((unsigned)blocks), dim3(256), 0, h->stream, t, (long long)H, (long long)W, total,
+                       flag);
+    LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
+int init_sanitize(papof_handle* h, double* planar, size_t n) {
+    const long long total = (long long)n, blocks = (total + 255) / 256;
+    if (total <= 0) return PAPOF_OK;
+    if (blocks > 0x7fffffffLL) return PAPOF_EINVAL;
+    hipLaunchKernelGGL(k_init_sanitize, dim3((unsigned)blocks), dim3(256), 0, h->stream, planar, total);
+    LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
+bool filter_hv_needs_tmp(const Taps& fh, const Taps& fv) { return fh.fsize > kHvMaxF || fv.fsize > kHvMaxF; }
 
 int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bool comp_major, int H, int W, int K, int pairs) {
     const long long total = (long long)pairs * H * W * K, blocks = (total + 255) / 256;

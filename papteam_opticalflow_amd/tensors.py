@@ -176,11 +176,48 @@ def _mask(n_pairs, H, W, dev):
     return occ, _struct(occ, (2 * H * W, W, 1, H * W), capi.DTYPE_U8)
 
 
-def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver):
+INIT_MAX = 1e6  # the largest magnitude of an initial flow's component (include/papof.h: papof_flow_batch_tensor_init)
+
+
+def _check_init(name, init, n_pairs, H, W, dev):
+    """the descriptor of an initial flow -- (B, 2, H, W), or (2, H, W) for every pair, float32 / float64 on the frames'
+    device -- or None; every error (TypeError / ValueError) before anything of this library is launched.  The value bound is
+    checked with torch on the tensor's device."""
+    if init is None:
+        return None
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if not isinstance(init, torch.Tensor):
+        raise TypeError("%s must be None or a torch.Tensor, got %s" % (name, type(init).__name__))
+    if init.dtype not in codes:
+        raise TypeError("%s must be float32 or float64, got %s" % (name, init.dtype))
+    if init.dim() not in (3, 4) or init.shape[-3] != 2:
+        raise ValueError("%s must be (B, 2, H, W) or (2, H, W), got shape %s" % (name, tuple(init.shape)))
+    if tuple(init.shape[-2:]) != (H, W):
+        raise ValueError("%s is %d x %d, the frames %d x %d" % (name, init.shape[-2], init.shape[-1], H, W))
+    if init.dim() == 4 and init.shape[0] != n_pairs:
+        raise ValueError("%s has %d flows for %d pairs" % (name, init.shape[0], n_pairs))
+    if init.device != dev:
+        raise ValueError("%s is on %s, the frames on %s" % (name, init.device, dev))
+    if not bool((init.abs() <= INIT_MAX).all()):
+        raise ValueError("%s has a component that is NaN, infinite or beyond %g in magnitude" % (name, INIT_MAX))
+    if init.dim() == 3:
+        strides = (0, init.stride(1), init.stride(2), init.stride(0))
+    else:
+        strides = (init.stride(0), init.stride(2), init.stride(3), init.stride(1))
+    return _struct(init, strides, codes[init.dtype])
+
+
+def _ref(d):
+    return ctypes.byref(d) if d is not None else None
+
+
+def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver, init_flow=None):
     torch = _torch()
     params = capi.default_params(**solver) if solver else None
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
+    d_init = _check_init("init_flow", init_flow, n_pairs, H, W, dev)
     index = _index(dev)
     flow, warp, d_flow, d_warp = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
@@ -188,33 +225,44 @@ def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver):
     gpu, lock = _handle(index)
     with lock, torch.cuda.device(index):
         stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_flow_batch_tensor(gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
-                                           None if sequence else ctypes.byref(d_in[1]), H, W, C, int(levels),
-                                           ctypes.byref(params) if params is not None else None, ctypes.byref(d_flow),
-                                           ctypes.byref(d_warp), ctypes.c_void_p(stream or None), t)
-    capi._chk(rc, "papof_flow_batch_tensor")
+        head = (gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W,
+                C, int(levels), ctypes.byref(params) if params is not None else None)
+        tail = (ctypes.byref(d_flow), ctypes.byref(d_warp), ctypes.c_void_p(stream or None), t)
+        if d_init is None:
+            what = "papof_flow_batch_tensor"
+            rc = gpu.L.papof_flow_batch_tensor(*head, *tail)
+        else:
+            what = "papof_flow_batch_tensor_init"
+            rc = gpu.L.papof_flow_batch_tensor_init(*head, ctypes.byref(d_init), *tail)
+    capi._chk(rc, what)
     return flow, warp, capi.format_timing(list(t))
 
 
-def flow_pairs(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, **solver):
+def flow_pairs(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, init_flow=None, **solver):
     """Flow of the independent pairs (im1[i], im2[i]): two tensors of one shape, (B, C, H, W) or (B, H, W, C) by `layout`.
-    Returns (flow (B, 2, H, W), warpI2 (B, ...) in `layout`, the reference's dict of ten timers)."""
+    Returns (flow (B, 2, H, W), warpI2 (B, ...) in `layout`, the reference's dict of ten timers).
+    init_flow: None (start from zero flow), or the flow each pair starts from -- (B, 2, H, W), or (2, H, W) for every pair,
+    float32 or float64 on the frames' device, any strides, every component finite and at most 1e6 in magnitude; it enters
+    the coarsest pyramid level through the frames' own pyramid, scaled to that level (include/papof.h:
+    papof_flow_batch_tensor_init states the rule).  An all-zero init_flow gives the bits of none."""
     ts, descs, out_dtype = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels)
-    return _run(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, solver)
+    return _run(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, solver, init_flow)
 
 
-def flow_video(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, **solver):
+def flow_video(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, init_flow=None, **solver):
     """Flow of the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames (each frame's pyramid is built once).
-    Returns (flow (T - 1, 2, H, W), warpI2 (T - 1, ...) in `layout`, the reference's dict of ten timers)."""
+    Returns (flow (T - 1, 2, H, W), warpI2 (T - 1, ...) in `layout`, the reference's dict of ten timers).
+    init_flow: as flow_pairs's, with B = T - 1."""
     ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
-    return _run(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, solver)
+    return _run(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, solver, init_flow)
 
 
-def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, consistency, solver):
+def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, consistency, solver, init_flow=None, init_flow_bw=None):
     torch = _torch()
     params = capi.default_params(**solver) if solver else None
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
+    d_init = [_check_init(n, f, n_pairs, H, W, dev) for n, f in (("init_flow", init_flow), ("init_flow_bw", init_flow_bw))]
     index = _index(dev)
     flow_fw, warp_fw, d_flow_fw, d_warp_fw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
     flow_bw, warp_bw, d_flow_bw, d_warp_bw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
@@ -225,35 +273,45 @@ def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, consistency
     gpu, lock = _handle(index)
     with lock, torch.cuda.device(index):
         stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_flow_batch_tensor_fb(gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
-                                              None if sequence else ctypes.byref(d_in[1]), H, W, C, int(levels),
-                                              ctypes.byref(params) if params is not None else None, ctypes.byref(d_flow_fw),
-                                              ctypes.byref(d_warp_fw), ctypes.byref(d_flow_bw), ctypes.byref(d_warp_bw),
-                                              ctypes.byref(d_occ) if occ is not None else None, a1, a2,
-                                              ctypes.c_void_p(stream or None), t)
-    capi._chk(rc, "papof_flow_batch_tensor_fb")
+        head = (gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W,
+                C, int(levels), ctypes.byref(params) if params is not None else None)
+        tail = (ctypes.byref(d_flow_fw), ctypes.byref(d_warp_fw), ctypes.byref(d_flow_bw), ctypes.byref(d_warp_bw),
+                ctypes.byref(d_occ) if occ is not None else None, a1, a2, ctypes.c_void_p(stream or None), t)
+        if d_init == [None, None]:
+            what = "papof_flow_batch_tensor_fb"
+            rc = gpu.L.papof_flow_batch_tensor_fb(*head, *tail)
+        else:
+            what = "papof_flow_batch_tensor_fb_init"
+            rc = gpu.L.papof_flow_batch_tensor_fb_init(*head, _ref(d_init[0]), _ref(d_init[1]), *tail)
+    capi._chk(rc, what)
     return FlowFB(flow_fw, flow_bw, warp_fw, warp_bw, occ.view(torch.bool) if occ is not None else None,
                   capi.format_timing(list(t)))
 
 
-def flow_pairs_fb(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+def flow_pairs_fb(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, init_flow=None,
+                  init_flow_bw=None, **solver):
     """Both directions of the independent pairs (im1[i], im2[i]) in one launch chain, and their occlusion mask.
     Returns FlowFB(flow_fw, flow_bw (B, 2, H, W), warpI2_fw, warpI2_bw (B, ...) in `layout`, occlusion, timing):
     flow_fw / warpI2_fw are flow_pairs(im1, im2)'s, flow_bw / warpI2_bw flow_pairs(im2, im1)'s, bit for bit.  occlusion is a
     torch.bool tensor (B, 2, H, W), channel 0 the forward pixels (of im1), 1 the backward ones (of im2), from the check with
-    consistency = (alpha1, alpha2) on the float64 flows (whatever out_dtype is) -- or None for consistency=None."""
+    consistency = (alpha1, alpha2) on the float64 flows (whatever out_dtype is) -- or None for consistency=None.
+    init_flow / init_flow_bw: the initial flows of the forward / backward pairs, as flow_pairs's init_flow (None: zero); each
+    direction is flow_pairs(..., init_flow=) on its frames, bit for bit."""
     alphas = _alphas(consistency) if consistency is not None else None
     ts, descs, out_dtype = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels)
-    return _run_fb(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, solver)
+    return _run_fb(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, solver, init_flow,
+                   init_flow_bw)
 
 
-def flow_video_fb(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+def flow_video_fb(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, init_flow=None,
+                  init_flow_bw=None, **solver):
     """Both directions of the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames in one launch chain -- each
     frame's pyramid and features are built once for both -- and their occlusion mask: flow_pairs_fb on
-    (frames[:-1], frames[1:]), with T - 1 pairs."""
+    (frames[:-1], frames[1:]), with T - 1 pairs (and its init_flow / init_flow_bw)."""
     alphas = _alphas(consistency) if consistency is not None else None
     ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
-    return _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, solver)
+    return _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, solver, init_flow,
+                   init_flow_bw)
 
 
 def fb_consistency(flow_fw, flow_bw, alpha1=CONSISTENCY[0], alpha2=CONSISTENCY[1]):
