@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 112 /* 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 113 /* 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -543,6 +543,81 @@ int papof_interp_tensor(papof_handle* h, int n_pairs, int sequence, const papof_
                         int height, int width, int c, const papof_tensor* flow_fw, const papof_tensor* flow_bw,
                         const papof_tensor* occlusion, int n_times, const double* times, const papof_tensor* out,
                         long long time_stride, void* stream);
+
+/* Global motion of a flow field (video stabilization, camera-motion compensation): one parametric motion per pair fitted to
+ * its forward flow by iteratively reweighted least squares (IRLS) with Cauchy weights, in fp64 without fused multiply-adds --
+ * two HIP kernels per iteration for all pairs (motion.hip: k_motion_sums, k_motion_solve).
+ * flow: float32 (widened exactly) or float64, (pair, row, column, {vx, vy}), any non-negative strides, as
+ * papof_fb_check_tensor takes it.  occlusion: NULL, or uint8 (pair, row, column, {fw, bw}) as papof_flow_batch_tensor_fb
+ * writes it, any non-negative strides; only channel 0 is read.  model: PAPOF_MOTION_SIMILARITY (scale, rotation,
+ * translation: 4 parameters) or PAPOF_MOTION_AFFINE (6).  n_iter >= 1 iterations; scale: the Cauchy scale c in pixels.
+ * For pixel (r, x) of a pair, with (u, v) = flow(r, x), H = height, W = width:
+ *     valid = (x + u, r + v) in [0, W - 1] x [0, H - 1] (false where u or v is NaN or infinite) and, with a mask, mask == 0
+ *     cx = (W - 1) / 2;  cy = (H - 1) / 2;  s = max(W, H) / 2
+ *     x^ = (x - cx) / s;  y^ = (r - cy) / s;  X^ = ((x + u) - cx) / s;  Y^ = ((r + v) - cy) / s
+ *     iteration 0:       w = valid                                                   (e^2 = 0)
+ *     iteration k >= 1:  e_x = (x + u) - ((m00 * x + m01 * r) + m02);  e_y = (r + v) - ((m10 * x + m11 * r) + m12)
+ *                        e^2 = e_x * e_x + e_y * e_y;  w = valid ? 1 / (1 + e^2 / (c * c)) : 0
+ *                        with M = (m00 m01 m02; m10 m11 m12) the pair's matrix after iteration k - 1
+ * and the fourteen sums over the pair's valid pixels, in this order (S0 .. S13):
+ *     S0 = sum w (x^ x^)   S1 = sum w (x^ y^)   S2 = sum w (y^ y^)   S3 = sum w x^   S4 = sum w y^   S5 = sum w
+ *     S6 = sum w (x^ X^)   S7 = sum w (y^ X^)   S8 = sum w X^        S9 = sum w (x^ Y^)   S10 = sum w (y^ Y^)   S11 = sum w Y^
+ *     S12 = sum valid      S13 = sum w e^2
+ * The order of the additions is fixed (a lane's pixels, then a fixed tree over lanes, waves and blocks: motion.hip), the
+ * same on every run and device, so the results are bitwise reproducible; it is not a row-major running sum.
+ * Solve, in normalised coordinates, by Gaussian elimination in natural order without row exchanges:
+ *     affine:      (S0 S1 S3; S1 S2 S4; S3 S4 S5) (a00, a01, tx) = (S6, S7, S8),  the same matrix (a10, a11, ty) = (S9, S10, S11)
+ *                  X^ = a00 x^ + a01 y^ + tx,  Y^ = a10 x^ + a11 y^ + ty
+ *     similarity:  with q = S0 + S2,
+ *                  ( q   0    S3  S4 ) (a )   ( S6 + S10 )
+ *                  ( 0   q   -S4  S3 ) (b ) = ( S9 - S7  )        X^ = a x^ - b y^ + tx,  Y^ = b x^ + a y^ + ty
+ *                  ( S3 -S4   S5  0  ) (tx)   ( S8       )        (a00 = a11 = a, a01 = -b, a10 = b)
+ *                  ( S4  S3   0   S5 ) (ty)   ( S11      )
+ * and back to pixels: M's linear part is (a00 a01; a10 a11); m02 = (cx + s tx) - (a00 cx + a01 cy),
+ * m12 = (cy + s ty) - (a10 cx + a11 cy).  M sends a pixel (x, r) of frame i to its position in frame i + 1.
+ * An iteration fails where S5 <= 0, where a pivot of the elimination is not > 1e-12 * S5, or where an entry of M is not
+ * finite.  A failed iteration k >= 1 leaves the matrix of the last successful one; a failed iteration 0 gives the identity and
+ * ok = 0, and the pair runs no further iterations.
+ * motion: float64 (pair, row, column) = M, strides [0..2] > 0 (stride[3] ignored); ok: uint8 (pair), 1 where some iteration
+ * succeeded, stride[0] > 0; support: float64 (pair) = S5 of the pair's last iteration / (H * W), stride[0] > 0.
+ * workspace: device memory of at least papof_motion_workspace(n_pairs, height, width) bytes, 8-byte aligned, owned by the
+ * caller, used by nothing else until the work enqueued here has run (on one stream: PyTorch's allocator on that stream).
+ * The handle's arena is not used.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting:
+ * ordered behind the work queued there so far, and ahead of what follows.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (occlusion aside) or data pointer, a flow that is not
+ * float32 / float64, a mask that is not uint8, a motion or support that is not float64, an ok that is not uint8, a negative
+ * stride of flow or occlusion, a zero or negative stride of an output along an axis in use, a model that is not
+ * PAPOF_MOTION_*, n_iter < 1, a scale that is not finite or not > 0, n_pairs, height or width < 1, a NULL workspace or
+ * workspace_bytes below papof_motion_workspace's value. */
+enum { PAPOF_MOTION_SIMILARITY = 0, PAPOF_MOTION_AFFINE = 1 };
+int papof_motion_fit_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow,
+                            const papof_tensor* occlusion, int model, int n_iter, double scale, const papof_tensor* motion,
+                            const papof_tensor* ok, const papof_tensor* support, void* workspace, long long workspace_bytes,
+                            void* stream);
+
+/* Bytes of the workspace of papof_motion_fit_tensor: 8 * n_pairs * (8 + 16 * ceil(width / 64) * ceil(height / 32)) -- a
+ * state row per pair and one row of partial sums per 64 x 32 block of pixels; -1 for n_pairs, height or width < 1 or
+ * more than 2^31 - 1 blocks per pair. */
+long long papof_motion_workspace(int n_pairs, int height, int width);
+
+/* Frames warped by one affine matrix each (motion.hip: k_warp_affine): out(i, r, x, ch) = frames[i] sampled at (X, Y), with
+ * M = matrices[i] and, in fp64 without fused multiply-adds,
+ *     X = (m00 * x + m01 * r) + m02;  Y = (m10 * x + m11 * r) + m12
+ * inside [0, width - 1] x [0, height - 1]: the bilinear rule of papof_interp_tensor (src/ImageProcessing.h:138-157:
+ * truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0 in (m, n)
+ * order); outside it, or for a NaN position: 0.
+ * frames: uint8 (x / 255.0), float32 (widened exactly) or float64, (frame, row, column, channel), any non-negative strides.
+ * matrices: float32 (widened exactly) or float64 (frame, row, column), 2 x 3, any non-negative strides (stride[3] ignored).
+ * out: uint8, float32 or float64 (frame, row, column, channel), strides > 0, stored as papof_interp_tensor stores (uint8 =
+ * clamp(rint(255 v), 0, 255), half to even).  valid: NULL, or uint8 (frame, row, column), strides [0..2] > 0: 1 where
+ * (X, Y) lies in the image, else 0.  out and valid must not overlap the inputs.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (valid aside) or data pointer, frames or out that are
+ * not uint8 / float32 / float64, matrices that are not float32 / float64, a valid that is not uint8, a negative stride, a
+ * zero stride of out or valid along an axis in use, n_frames, height, width or c < 1. */
+int papof_warp_affine_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                             const papof_tensor* matrices, const papof_tensor* out, const papof_tensor* valid, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

@@ -28,6 +28,7 @@ class Params(ctypes.Structure):
 
 
 DTYPE_U8, DTYPE_F32, DTYPE_F64 = 0, 1, 2
+MOTION_SIMILARITY, MOTION_AFFINE = 0, 1
 
 
 class PapofTensor(ctypes.Structure):
@@ -62,7 +63,7 @@ SYMBOLS = [
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
     "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
     "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
-    "papof_flow_batch_tensor_fb_init",
+    "papof_flow_batch_tensor_fb_init", "papof_motion_fit_tensor", "papof_motion_workspace", "papof_warp_affine_tensor",
 ]
 
 
@@ -176,6 +177,13 @@ def load():
     L.papof_interp_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _T,
                                       ctypes.c_longlong, c_void_p]
     L.papof_interp_tensor.restype = c_int
+    L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
+                                          ctypes.c_longlong, c_void_p]
+    L.papof_motion_fit_tensor.restype = c_int
+    L.papof_motion_workspace.argtypes = [c_int, c_int, c_int]
+    L.papof_motion_workspace.restype = ctypes.c_longlong
+    L.papof_warp_affine_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, _T, c_void_p]
+    L.papof_warp_affine_tensor.restype = c_int
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
     _lib = L

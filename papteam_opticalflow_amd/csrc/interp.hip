@@ -9,14 +9,15 @@
 //
 // Semantics: include/papof.h, papof_interp_tensor.  The bilinear rule is k_fb_check's and k_track's (the reference's,
 // src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image,
-// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).
+// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler is sampler.h's, shared
+// with motion.hip's k_warp_affine.
 //
 // Mapping.  A block is a 64 x 4 tile of output pixels (as k_fb_check's): blockIdx.x the tile, blockIdx.y the pair.  A wave is
 // 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose stores are contiguous
 // along a row.  The times are kernel arguments (at most kMaxTimes per launch; more are launched in groups): they are the
 // same for every lane, so they sit in scalar registers with no load, and the call needs no device buffer and no copy to
 // fill one -- nothing the caller has to keep alive after the call returns.  Every offset is 64-bit.
-#include "common.h"
+#include "sampler.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,76 +44,12 @@ struct InterpArgs {
     double t[kMaxTimes];
 };
 
-// FD: the dtype of both frame tensors, fixed at compile time (the common case: one branch-free gather per tap), or -1: read
-// from each descriptor.  A uint8 sample is x / 255.0 as k_ingest_frames computes it, looked up in a table of the 256
-// quotients that the block fills once (lut): the same bits, without an fp64 division per tap.
-template <int FD>
-__device__ __forceinline__ double load_frame(const papof_tensor& t, long long o, const double* lut) {
-    const int d = FD >= 0 ? FD : t.dtype;
-    if (d == PAPOF_DTYPE_U8) return lut[static_cast<const unsigned char*>(t.data)[o]];
-    if (d == PAPOF_DTYPE_F32) return (double)static_cast<const float*>(t.data)[o];
-    return static_cast<const double*>(t.data)[o];
-}
-
-__device__ __forceinline__ double load_flow(const papof_tensor& t, long long o) {
-    return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
-}
-
-__device__ __forceinline__ int clamp_to(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
-    x = x < 0 ? 0 : x;
-    return x > n - 1 ? n - 1 : x;
-}
-
-// The four taps of the bilinear rule at (X, Y), a point of [0, W - 1] x [0, H - 1], in (m, n) order: their (row, column)
-// offsets in elements of a tensor whose row and column strides are s1, s2 -- for frames and mask alike, offsets are computed
-// per tensor -- and their weights.
-struct Taps {
-    int row[4], col[4];
-    double w[4];
-};
-
-__device__ __forceinline__ Taps taps_at(double X, double Y, int H, int W) {
-    Taps k;
-    const int xx = (int)X, yy = (int)Y;
-    double dx = X - xx, dy = Y - yy;
-    dx = dx > 1 ? 1.0 : dx;
-    dx = dx < 0 ? 0.0 : dx;
-    dy = dy > 1 ? 1.0 : dy;
-    dy = dy < 0 ? 0.0 : dy;
-#pragma unroll
-    for (int m = 0; m <= 1; m++)
-#pragma unroll
-        for (int n = 0; n <= 1; n++) {
-            k.row[2 * m + n] = clamp_to(yy + n, H);
-            k.col[2 * m + n] = clamp_to(xx + m, W);
-            k.w[2 * m + n] = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
-        }
-    return k;
-}
-
-template <int FD>
-__device__ __forceinline__ double sample_frame(const papof_tensor& t, long long base, const Taps& k, const double* lut) {
-    double g = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) g += load_frame<FD>(t, base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2], lut) * k.w[i];
-    return g;
-}
-
 __device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Taps& k) {  // bytes as 0 / 1
     const unsigned char* m = static_cast<const unsigned char*>(t.data);
     double o = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; i++) o += (m[base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2]] ? 1.0 : 0.0) * k.w[i];
     return o;
-}
-
-__device__ __forceinline__ void store(const papof_tensor& t, long long o, double v) {
-    if (t.dtype == PAPOF_DTYPE_U8)  // clamp(rint(255 out), 0, 255), half to even; NaN -> 0 (fmax)
-        static_cast<unsigned char*>(t.data)[o] = (unsigned char)fmin(fmax(rint(255.0 * v), 0.0), 255.0);
-    else if (t.dtype == PAPOF_DTYPE_F32)
-        static_cast<float*>(t.data)[o] = (float)v;
-    else
-        static_cast<double*>(t.data)[o] = v;
 }
 
 // blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: pair `pair0` + y.  Times
@@ -122,8 +59,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp(const InterpArg
                                                                  long long j0) {
     __shared__ double lut[256];
     if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        const int k = threadIdx.y * kInterpTX + threadIdx.x;  // (256 lanes: one quotient each)
-        lut[k] = (double)k / 255.0;
+        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);  // (256 lanes: one quotient each)
         __syncthreads();
     }
     const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;

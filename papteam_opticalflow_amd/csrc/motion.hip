@@ -1,0 +1,377 @@
+// papteam_opticalflow_amd/csrc/motion.hip -- global motion of a flow field (papof_motion_fit_tensor) and the affine warp of
+// frames (papof_warp_affine_tensor): the two device halves of video stabilization.
+//
+// Why.  Global camera motion (stabilization, camera-motion compensation, shot-boundary checks) is a robust parametric fit to
+// a pair's flow.  Written with torch.linalg.lstsq it is a copy of the flow into a (pixels x parameters) system and several
+// launches per IRLS iteration; here it is a reduction of fourteen fp64 sums over the flow, read once per iteration, and a
+// 4 x 4 or 3 x 3 solve.
+//
+// Semantics: include/papof.h, papof_motion_fit_tensor and papof_warp_affine_tensor.  fp64 without contraction
+// (-ffp-contract=off).
+//
+// Reduction.  Bitwise reproducible from run to run and on every device, so there are no atomics.  Launch 1 (k_motion_sums):
+// a block is a 64 x 32 tile of pixels of one pair (blockIdx.x the tile, blockIdx.y the pair), a lane one column and 8 rows
+// (threadIdx.y + 4 k) in increasing row order; the lanes of a wave are summed by a fixed shuffle tree (__shfl_down, 32 .. 1),
+// the four waves in wave order through LDS, and the block writes one row of fourteen doubles to the workspace.  The number
+// of blocks of a pair is a function of (H, W) alone.  Launch 2 (k_motion_solve): one wave per pair; lane l adds the rows
+// l, l + 64, l + 128, ... in increasing order, the lanes are summed by the same shuffle tree, and lane 0 solves and writes
+// the pair's matrix to its state row and to the outputs.  The next iteration's launch 1 reads that matrix as uniform loads.
+// Every offset is 64-bit; launch 1 is split at gridDim.y = 65535 pairs.
+//
+// Warp.  k_warp_affine: a block is a 64 x 4 tile of output pixels (blockIdx.x the tile, blockIdx.y the frame), as k_interp's;
+// the block reads its frame's matrix once (uniform loads) and samples with sampler.h's bilinear rule.
+#include "sampler.h"
+
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
+
+namespace papof {
+
+namespace {
+
+constexpr int kFitTX = 64, kFitTY = 4, kFitRows = 8;  // a lane: one column, kFitRows rows kFitTY apart
+constexpr int kFitTH = kFitTY * kFitRows;            // a block: 64 x 32 pixels
+constexpr int kSums = 14;                             // include/papof.h: the order of the sums
+constexpr int kRow = 16;                              // doubles per partial row (kSums used)
+constexpr int kState = 8;                             // doubles per pair: matrix (6), ok (1), finished (1)
+constexpr int kWarpTX = 64, kWarpTY = 4;              // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+constexpr long long kMaxPairs = 65535;                // gridDim.y
+constexpr long long kMaxTiles = 0x7fffffffLL;         // gridDim.x
+
+long long fit_blocks(int H, int W) {
+    return ((W + kFitTX - 1) / (long long)kFitTX) * ((H + kFitTH - 1) / (long long)kFitTH);
+}
+
+struct FitArgs {
+    papof_tensor flow;  // (pair, row, column, {vx, vy})
+    papof_tensor occ;   // uint8 (pair, row, column, {fw, bw}); data NULL: none
+    const double* state;
+    double* part;       // (pair, block, kRow)
+    long long blocks;   // per pair
+    int H, W;
+    int iter;
+    double cx, cy, s, c2;
+};
+
+struct SolveArgs {
+    double* state;        // (pair, kState)
+    const double* part;
+    papof_tensor motion;  // float64 (pair, row, column)
+    papof_tensor ok;      // uint8 (pair)
+    papof_tensor support; // float64 (pair)
+    long long blocks;
+    int model;
+    int iter;
+    double cx, cy, s, hw;
+};
+
+// the sum of acc over the 64 lanes of the wave, in lane 0: a fixed tree
+__device__ __forceinline__ void wave_sum(double (&acc)[kSums]) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < kSums; k++) acc[k] += __shfl_down(acc[k], off, 64);
+}
+
+__global__ __launch_bounds__(kFitTX* kFitTY) void k_motion_sums(const FitArgs a, long long pair0) {
+    __shared__ double red[kFitTY][kSums];
+    const long long i = pair0 + blockIdx.y;
+    const double* st = a.state + i * kState;
+    if (a.iter > 0 && st[7] != 0.0) return;  // the pair's iteration 0 failed: finished (uniform over the block)
+    double m[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (a.iter > 0)
+#pragma unroll
+        for (int k = 0; k < 6; k++) m[k] = st[k];
+    const long long tx = (a.W + kFitTX - 1) / kFitTX, tile = blockIdx.x;
+    const int x = (int)(tile % tx) * kFitTX + (int)threadIdx.x;
+    const long long r0 = (tile / tx) * kFitTH + threadIdx.y;
+    double acc[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; k++) acc[k] = 0.0;
+    if (x < a.W) {
+        const double xd = (double)x, xh = (xd - a.cx) / a.s;
+        const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+        for (int j = 0; j < kFitRows; j++) {
+            const long long r = r0 + (long long)j * kFitTY;
+            if (r >= a.H) break;
+            const long long o = i * a.flow.stride[0] + r * a.flow.stride[1] + x * a.flow.stride[2];
+            const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
+            const double rd = (double)r, X = xd + u, Y = rd + v;
+            bool valid = X >= 0 && X <= W1 && Y >= 0 && Y <= H1;  // false for a NaN or an infinity
+            if (valid && a.occ.data)
+                valid = static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + r * a.occ.stride[1] +
+                                                                      x * a.occ.stride[2]] == 0;
+            if (!valid) continue;
+            double w = 1.0;
+            if (a.iter > 0) {
+                const double ex = X - ((m[0] * xd + m[1] * rd) + m[2]), ey = Y - ((m[3] * xd + m[4] * rd) + m[5]);
+                const double e2 = ex * ex + ey * ey;
+                w = 1.0 / (1.0 + e2 / a.c2);
+                acc[13] += w * e2;
+            }
+            const double yh = (rd - a.cy) / a.s, Xh = (X - a.cx) / a.s, Yh = (Y - a.cy) / a.s;
+            acc[0] += w * (xh * xh);
+            acc[1] += w * (xh * yh);
+            acc[2] += w * (yh * yh);
+            acc[3] += w * xh;
+            acc[4] += w * yh;
+            acc[5] += w;
+            acc[6] += w * (xh * Xh);
+            acc[7] += w * (yh * Xh);
+            acc[8] += w * Xh;
+            acc[9] += w * (xh * Yh);
+            acc[10] += w * (yh * Yh);
+            acc[11] += w * Yh;
+            acc[12] += 1.0;
+        }
+    }
+    wave_sum(acc);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < kSums; k++) red[threadIdx.y][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.y == 0 && threadIdx.x < kSums) {
+        const int k = threadIdx.x;
+        a.part[(i * a.blocks + tile) * kRow + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    }
+}
+
+// Gaussian elimination in natural order without row exchanges on the N x N matrix of `g` with R right-hand sides (columns
+// N .. N + R - 1); false where a pivot is not > tol (NaN included).  x[r] solves the system of right-hand side r.
+template <int N, int R>
+__device__ bool eliminate(double (&g)[N][N + R], double tol, double (&x)[R][N]) {
+    for (int k = 0; k < N; k++) {
+        const double piv = g[k][k];
+        if (!(piv > tol)) return false;
+        for (int i = k + 1; i < N; i++) {
+            const double f = g[i][k] / piv;
+            for (int j = k; j < N + R; j++) g[i][j] = g[i][j] - f * g[k][j];
+        }
+    }
+    for (int r = 0; r < R; r++)
+        for (int i = N - 1; i >= 0; i--) {
+            double v = g[i][N + r];
+            for (int j = i + 1; j < N; j++) v = v - g[i][j] * x[r][j];
+            x[r][i] = v / g[i][i];
+        }
+    return true;
+}
+
+// the pixel-coordinate matrix m of the normalised sums S (include/papof.h); false where the iteration fails
+__device__ bool fit_solve(const double (&S)[kSums], int model, double cx, double cy, double s, double (&m)[6]) {
+    const double sw = S[5];
+    if (!(sw > 0)) return false;
+    const double tol = 1e-12 * sw;
+    double L0, L1, L2, L3, tx, ty;
+    if (model == PAPOF_MOTION_AFFINE) {
+        double g[3][5] = {{S[0], S[1], S[3], S[6], S[9]}, {S[1], S[2], S[4], S[7], S[10]}, {S[3], S[4], S[5], S[8], S[11]}};
+        double p[2][3];
+        if (!eliminate<3, 2>(g, tol, p)) return false;
+        L0 = p[0][0], L1 = p[0][1], tx = p[0][2], L2 = p[1][0], L3 = p[1][1], ty = p[1][2];
+    } else {
+        const double s2 = S[0] + S[2];
+        double g[4][5] = {{s2, 0.0, S[3], S[4], S[6] + S[10]},
+                          {0.0, s2, -S[4], S[3], S[9] - S[7]},
+                          {S[3], -S[4], sw, 0.0, S[8]},
+                          {S[4], S[3], 0.0, sw, S[11]}};
+        double p[1][4];
+        if (!eliminate<4, 1>(g, tol, p)) return false;
+        L0 = p[0][0], L1 = -p[0][1], L2 = p[0][1], L3 = p[0][0], tx = p[0][2], ty = p[0][3];
+    }
+    m[0] = L0;
+    m[1] = L1;
+    m[2] = (cx + s * tx) - (L0 * cx + L1 * cy);
+    m[3] = L2;
+    m[4] = L3;
+    m[5] = (cy + s * ty) - (L2 * cx + L3 * cy);
+    for (int k = 0; k < 6; k++)
+        if (!isfinite(m[k])) return false;
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_motion_solve(const SolveArgs a, long long pair0) {
+    const long long i = pair0 + blockIdx.x;
+    double* st = a.state + i * kState;
+    if (a.iter > 0 && st[7] != 0.0) return;
+    const double* p = a.part + i * a.blocks * kRow;
+    double acc[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; k++) acc[k] = 0.0;
+    for (long long b = threadIdx.x; b < a.blocks; b += 64)
+#pragma unroll
+        for (int k = 0; k < kSums; k++) acc[k] += p[b * kRow + k];
+    wave_sum(acc);
+    if (threadIdx.x != 0) return;
+    double m[6];
+    if (fit_solve(acc, a.model, a.cx, a.cy, a.s, m)) {
+        for (int k = 0; k < 6; k++) st[k] = m[k];
+        st[6] = 1.0;
+        st[7] = 0.0;
+    } else if (a.iter == 0) {  // the identity, ok = 0, no further iterations
+        const double id[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+        for (int k = 0; k < 6; k++) st[k] = id[k];
+        st[6] = 0.0;
+        st[7] = 1.0;
+    }  // else: the last successful iteration's matrix stays
+    double* mo = static_cast<double*>(a.motion.data) + i * a.motion.stride[0];
+    for (int r = 0; r < 2; r++)
+        for (int c = 0; c < 3; c++) mo[r * a.motion.stride[1] + c * a.motion.stride[2]] = st[3 * r + c];
+    static_cast<unsigned char*>(a.ok.data)[i * a.ok.stride[0]] = st[6] != 0.0 ? 1 : 0;
+    static_cast<double*>(a.support.data)[i * a.support.stride[0]] = acc[5] / a.hw;
+}
+
+int launch_fit(hipStream_t st, FitArgs f, SolveArgs s, int n_pairs, int n_iter) {
+    for (int it = 0; it < n_iter; it++) {
+        f.iter = s.iter = it;
+        for (long long p0 = 0; p0 < n_pairs; p0 += kMaxPairs) {
+            const unsigned np = (unsigned)std::min(kMaxPairs, n_pairs - p0);
+            hipLaunchKernelGGL(k_motion_sums, dim3((unsigned)f.blocks, np), dim3(kFitTX, kFitTY), 0, st, f, p0);
+            PAPOF_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_motion_solve, dim3((unsigned)n_pairs), dim3(64), 0, st, s, 0LL);
+        PAPOF_HIP(hipGetLastError());
+    }
+    return PAPOF_OK;
+}
+
+struct WarpArgs {
+    papof_tensor fr;     // (frame, row, column, channel)
+    papof_tensor mat;    // float32 / float64 (frame, row, column): 2 x 3
+    papof_tensor out;    // (frame, row, column, channel)
+    papof_tensor valid;  // uint8 (frame, row, column); data NULL: none
+    int H, W, C;
+};
+
+// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y
+template <int FD>
+__global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs a, long long tile0, long long frame0) {
+    __shared__ double lut[256];
+    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
+        fill_u8_lut(lut, threadIdx.y * kWarpTX + threadIdx.x);  // (256 lanes: one quotient each)
+        __syncthreads();
+    }
+    const long long i = frame0 + blockIdx.y;
+    const long long mb = i * a.mat.stride[0];
+    double m[6];
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[1] + c * a.mat.stride[2]);
+    const long long tx = (a.W + kWarpTX - 1) / kWarpTX, tile = tile0 + blockIdx.x;
+    const int x = (int)(tile % tx) * kWarpTX + (int)threadIdx.x;
+    const long long r = (tile / tx) * kWarpTY + threadIdx.y;
+    if (x >= a.W || r >= a.H) return;
+    const double xd = (double)x, rd = (double)r;
+    const double X = (m[0] * xd + m[1] * rd) + m[2], Y = (m[3] * xd + m[4] * rd) + m[5];
+    const bool in = X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
+    if (a.valid.data)
+        static_cast<unsigned char*>(a.valid.data)[i * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = in;
+    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    if (!in) {
+        for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
+        return;
+    }
+    const Taps k = taps_at(X, Y, a.H, a.W);
+    const long long base = i * a.fr.stride[0];
+    for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], k, lut));
+}
+
+int launch_warp(hipStream_t st, const WarpArgs& a, int n_frames) {
+    const int fd = a.fr.dtype;
+    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_warp_affine<PAPOF_DTYPE_U8>
+                        : fd == PAPOF_DTYPE_F32 ? k_warp_affine<PAPOF_DTYPE_F32>
+                                                : k_warp_affine<PAPOF_DTYPE_F64>;
+    const long long tiles = ((a.W + kWarpTX - 1) / (long long)kWarpTX) * ((a.H + kWarpTY - 1) / (long long)kWarpTY);
+    for (long long f0 = 0; f0 < n_frames; f0 += kMaxPairs)
+        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
+            const unsigned nf = (unsigned)std::min(kMaxPairs, n_frames - f0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
+            hipLaunchKernelGGL(kernel, dim3(nt, nf), dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
+            PAPOF_HIP(hipGetLastError());
+        }
+    return PAPOF_OK;
+}
+
+// a descriptor with data, of one of `dtypes`, whose first `axes` strides are >= 0 (positive: > 0)
+bool described(const papof_tensor* t, std::initializer_list<int> dtypes, int axes, bool positive) {
+    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
+    for (int i = 0; i < axes; i++)
+        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
+    return true;
+}
+
+}  // namespace
+
+}  // namespace papof
+
+using namespace papof;
+
+extern "C" long long papof_motion_workspace(int n_pairs, int height, int width) {
+    if (n_pairs < 1 || height < 1 || width < 1) return -1;
+    const long long blocks = fit_blocks(height, width);
+    if (blocks > kMaxTiles) return -1;
+    return 8LL * n_pairs * (kState + blocks * kRow);
+}
+
+extern "C" int papof_motion_fit_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow,
+                                       const papof_tensor* occlusion, int model, int n_iter, double scale,
+                                       const papof_tensor* motion, const papof_tensor* ok, const papof_tensor* support,
+                                       void* workspace, long long workspace_bytes, void* stream) {
+    if (!h || n_pairs < 1 || height < 1 || width < 1 || n_iter < 1) return PAPOF_EINVAL;
+    if (model != PAPOF_MOTION_SIMILARITY && model != PAPOF_MOTION_AFFINE) return PAPOF_EINVAL;
+    if (!std::isfinite(scale) || !(scale > 0)) return PAPOF_EINVAL;
+    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, 4, false)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, 3, false)) return PAPOF_EINVAL;
+    if (!described(motion, {PAPOF_DTYPE_F64}, 3, true) || !described(ok, {PAPOF_DTYPE_U8}, 1, true) ||
+        !described(support, {PAPOF_DTYPE_F64}, 1, true))
+        return PAPOF_EINVAL;
+    const long long need = papof_motion_workspace(n_pairs, height, width);
+    if (need < 0 || !workspace || workspace_bytes < need) return PAPOF_EINVAL;
+    const double cx = (width - 1) / 2.0, cy = (height - 1) / 2.0, s = std::max(width, height) / 2.0;
+    FitArgs f{};
+    f.flow = *flow;
+    if (occlusion) f.occ = *occlusion;
+    f.state = static_cast<const double*>(workspace);
+    f.part = static_cast<double*>(workspace) + (long long)n_pairs * kState;
+    f.blocks = fit_blocks(height, width);
+    f.H = height;
+    f.W = width;
+    f.cx = cx;
+    f.cy = cy;
+    f.s = s;
+    f.c2 = scale * scale;
+    SolveArgs sa{};
+    sa.state = static_cast<double*>(workspace);
+    sa.part = f.part;
+    sa.motion = *motion;
+    sa.ok = *ok;
+    sa.support = *support;
+    sa.blocks = f.blocks;
+    sa.model = model;
+    sa.cx = cx;
+    sa.cy = cy;
+    sa.s = s;
+    sa.hw = (double)height * (double)width;
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_fit(static_cast<hipStream_t>(stream), f, sa, n_pairs, n_iter);
+}
+
+extern "C" int papof_warp_affine_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                        const papof_tensor* frames, const papof_tensor* matrices, const papof_tensor* out,
+                                        const papof_tensor* valid, void* stream) {
+    if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
+    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    if (!described(frames, I, 4, false) || !described(out, I, 4, true)) return PAPOF_EINVAL;
+    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, 3, false)) return PAPOF_EINVAL;
+    if (valid && !described(valid, {PAPOF_DTYPE_U8}, 3, true)) return PAPOF_EINVAL;
+    WarpArgs a{};
+    a.fr = *frames;
+    a.mat = *matrices;
+    a.out = *out;
+    if (valid) a.valid = *valid;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_warp(static_cast<hipStream_t>(stream), a, n_frames);
+}

@@ -31,6 +31,12 @@ two frames of each pair from its forward and backward flows and, optionally, its
 
     iv = interpolate_video(frames, 5, factor=3, layout="NHWC")   # iv.video: (3 (T - 1) + 1, H, W, C), frames at 3x the rate
 
+Stabilization: `global_motion` (include/papof.h: papof_motion_fit_tensor) fits one similarity or affine motion per pair to
+its forward flow (robust IRLS in float64, two HIP kernels per iteration), `stabilizing_transforms` smooths the camera path
+on the host and `warp_affine` (papof_warp_affine_tensor) resamples the frames; `stabilize_video` chains flow_video and them.
+
+    sv = stabilize_video(frames, 5, layout="NHWC", crop=0.9)   # sv.video: the stabilized frames, sv.valid (T, H, W)
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -48,6 +54,9 @@ Tracks = collections.namedtuple("Tracks", "tracks visible")
 TrackVideo = collections.namedtuple("TrackVideo", "tracks visible flow_fw flow_bw timing")
 InterpPairs = collections.namedtuple("InterpPairs", "frames flow_fw flow_bw occlusion timing")
 Interp = collections.namedtuple("Interp", "video flow_fw flow_bw occlusion timing")
+Motion = collections.namedtuple("Motion", "motion ok support")
+Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
+MODELS = {"similarity": capi.MOTION_SIMILARITY, "affine": capi.MOTION_AFFINE}
 
 _lock = threading.Lock()
 _handles = {}  # device ordinal -> (Papof, lock of its calls)
@@ -628,3 +637,226 @@ def interpolate_video(frames, pyramidLevels, factor=2, *, layout="NCHW", consist
     _interp(d_in, True, T - 1, H, W, C, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, times, video, d_out,
             vs[0], dev)
     return Interp(video, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
+
+
+def _check_fit(model, iters, scale):
+    """(PAPOF_MOTION_* code, iterations, Cauchy scale) of global_motion's keywords -- TypeError / ValueError otherwise"""
+    if model not in MODELS:
+        raise ValueError("model must be one of %s, got %r" % (sorted(MODELS), model))
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError("iters must be an integer >= 1, got %r" % (iters,))
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError("scale must be a number, got %r" % (scale,))
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError("scale must be finite and > 0, got %r" % (scale,))
+    return MODELS[model], iters, float(scale)
+
+
+def _check_motion_flow(flow, occlusion):
+    """flow (B, 2, H, W) float32 / float64 on a HIP device and its optional (B, 2, H, W) bool / uint8 mask: (flow's dtype code,
+    the mask as uint8 or None)"""
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if not isinstance(flow, torch.Tensor):
+        raise TypeError("flow must be a torch.Tensor, got %s" % type(flow).__name__)
+    if flow.dim() != 4 or flow.shape[1] != 2 or min(flow.shape) < 1:
+        raise ValueError("flow must be (B, 2, H, W) with B, H, W >= 1, got shape %s" % (tuple(flow.shape),))
+    if flow.dtype not in codes:
+        raise TypeError("flow must be float32 or float64, got %s" % flow.dtype)
+    if occlusion is not None:
+        if not isinstance(occlusion, torch.Tensor):
+            raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
+        if occlusion.dtype not in (torch.bool, torch.uint8):
+            raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
+        if occlusion.shape != flow.shape:
+            raise ValueError("occlusion must be (B, 2, H, W) = %s, got %s" % (tuple(flow.shape), tuple(occlusion.shape)))
+        if occlusion.device != flow.device:
+            raise ValueError("occlusion is on %s, the flow on %s: both must be on one device" % (occlusion.device, flow.device))
+        occlusion = occlusion.view(torch.uint8)
+    if not _on_gpu(flow):
+        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
+    return codes[flow.dtype], occlusion
+
+
+def _motion_fit(flow, code, occlusion, model, iters, scale):
+    torch = _torch()
+    B, _, H, W = (int(x) for x in flow.shape)
+    dev = flow.device
+    index = _index(dev)
+    motion = torch.empty((B, 2, 3), dtype=torch.float64, device=dev)
+    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
+    support = torch.empty((B,), dtype=torch.float64, device=dev)
+    d_flow = _flow_struct(flow, code)
+    d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
+    d_m = _struct(motion, (motion.stride(0), motion.stride(1), motion.stride(2), 0), capi.DTYPE_F64)
+    d_ok = _struct(ok, (ok.stride(0), 0, 0, 0), capi.DTYPE_U8)
+    d_s = _struct(support, (support.stride(0), 0, 0, 0), capi.DTYPE_F64)
+    gpu, lock = _handle(index)
+    nbytes = gpu.L.papof_motion_workspace(B, H, W)
+    if nbytes < 0:
+        raise ValueError("a %d x %d flow is too large for global_motion" % (H, W))
+    with lock, torch.cuda.device(index):
+        # the workspace comes from PyTorch's allocator on the current stream: it is reused only behind the work queued here
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_motion_fit_tensor(gpu.h, B, H, W, ctypes.byref(d_flow), _ref(d_occ), model, iters, scale,
+                                           ctypes.byref(d_m), ctypes.byref(d_ok), ctypes.byref(d_s),
+                                           ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream or None))
+        del ws
+    capi._chk(rc, "papof_motion_fit_tensor")
+    return Motion(motion, ok.view(torch.bool), support)
+
+
+def global_motion(flow, *, occlusion=None, model="affine", iters=5, scale=1.0):
+    """The global motion of each pair's forward flow: flow (B, 2, H, W) float32 / float64 on a HIP device, any strides, as
+    flow_video returns it; occlusion None or the (B, 2, H, W) bool / uint8 mask of flow_video_fb (channel 0 is read: masked
+    pixels are left out).  model: "similarity" (scale, rotation, translation) or "affine"; fitted by `iters` iterations of
+    reweighted least squares in float64 with Cauchy weights 1 / (1 + e^2 / scale^2), e the pixel distance between where the
+    flow sends a pixel and where the previous iteration's motion sends it.  Pixels whose flow is not finite or leaves the
+    image are left out.  Returns Motion(motion (B, 2, 3) float64 -- the pixel-coordinate matrix sending (x, y, 1) of frame i
+    to frame i + 1 --, ok (B,) bool -- False where no fit was possible (motion is the identity) --, support (B,) float64 --
+    the last iteration's sum of weights over H * W).  include/papof.h (papof_motion_fit_tensor) states the rule exactly; the
+    results are bitwise reproducible.  Enqueued on the current stream; returns without waiting."""
+    model, iters, scale = _check_fit(model, iters, scale)
+    code, occ = _check_motion_flow(flow, occlusion)
+    return _motion_fit(flow, code, occ, model, iters, scale)
+
+
+def _check_matrices(matrices, n, dev):
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if not isinstance(matrices, torch.Tensor):
+        raise TypeError("matrices must be a torch.Tensor, got %s" % type(matrices).__name__)
+    if matrices.dtype not in codes:
+        raise TypeError("matrices must be float32 or float64, got %s" % matrices.dtype)
+    if tuple(matrices.shape) != (n, 2, 3):
+        raise ValueError("matrices must be (B, 2, 3) = %s, got %s" % ((n, 2, 3), tuple(matrices.shape)))
+    if matrices.device != dev:
+        raise ValueError("matrices are on %s, the frames on %s: both must be on one device" % (matrices.device, dev))
+    return codes[matrices.dtype]
+
+
+def _warp(ts, descs, matrices, m_code, layout, out_dtype):
+    torch = _torch()
+    (B, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    index = _index(dev)
+    shape = (B, C, H, W) if layout == "NCHW" else (B, H, W, C)
+    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], descs[0][1], descs[0][2])
+    d_mat = _struct(matrices, (matrices.stride(0), matrices.stride(1), matrices.stride(2), 0), m_code)
+    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
+    d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_warp_affine_tensor(gpu.h, B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_out),
+                                            ctypes.byref(d_valid), ctypes.c_void_p(stream or None))
+    capi._chk(rc, "papof_warp_affine_tensor")
+    return out, valid.view(torch.bool)
+
+
+def warp_affine(frames, matrices, *, layout="NCHW", out_dtype=None):
+    """Each frame resampled through its own affine matrix: frames (B, C, H, W) or (B, H, W, C) by `layout`, uint8 (read as
+    x / 255), float32 or float64, any strides, on a HIP device; matrices (B, 2, 3) float32 / float64 on the same device.
+    Output pixel (x, y) of frame i is frames[i] sampled bilinearly (the rule of interpolate) at M (x, y, 1), M = matrices[i],
+    or 0 where that point is NaN or outside the frame.  Returns (frames_out in `layout` and out_dtype -- uint8 as
+    clamp(rint(255 x), 0, 255), float32 or float64; by default the frames' dtype --, valid (B, H, W) bool: True where the
+    point lay inside).  include/papof.h (papof_warp_affine_tensor) states it exactly.  Enqueued on the current stream;
+    returns without waiting."""
+    ts, descs, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
+    _out_code(out_dtype)
+    m_code = _check_matrices(matrices, descs[0][0][0], ts[0].device)
+    return _warp(ts, descs, matrices, m_code, layout, out_dtype)
+
+
+def _check_path(radius, crop, size):
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius < 0:
+        raise ValueError("radius must be an integer >= 0, got %r" % (radius,))
+    if isinstance(crop, bool) or not isinstance(crop, (int, float)):
+        raise TypeError("crop must be a number, got %r" % (crop,))
+    if not (math.isfinite(crop) and 0 < crop <= 1):
+        raise ValueError("crop must lie in (0, 1], got %r" % (crop,))
+    if size is None:
+        if crop != 1:
+            raise ValueError("crop != 1 zooms about the image centre: give size=(H, W)")
+        return 0.0, 0.0
+    try:
+        H, W = (int(x) for x in size)
+    except (TypeError, ValueError):
+        raise TypeError("size must be (H, W), got %r" % (size,)) from None
+    if H < 1 or W < 1:
+        raise ValueError("size must be positive, got %r" % (size,))
+    return (W - 1) / 2.0, (H - 1) / 2.0
+
+
+def stabilizing_transforms(motion, radius=15, crop=1.0, *, size=None):
+    """The sampling matrices that stabilize a video of T frames whose consecutive pairs move by `motion` -- a (T - 1, 2, 3)
+    tensor (global_motion's, any device) or a Motion, whose pairs with ok False enter as the identity.  In float64 on the
+    host (one small copy from the device; this is where stabilize_video waits), with 3 x 3 homogeneous matrices:
+        P_0 = I,  P_{t+1} = A_t P_t                        (the camera path: frame 0's coordinates to frame t's)
+        S_t = sum_k g_k P_{t+k} / sum_k g_k,  g_k = exp(-k^2 / (2 (radius / 2)^2)),  k in [-radius, radius] within the video
+        M_t = P_t S_t^-1 Z,  Z q = c + crop (q - c)        (c = ((W - 1) / 2, (H - 1) / 2) of size = (H, W): a zoom that hides
+                                                            the borders; size is needed only for crop < 1)
+    and stabilized frame t is frame t sampled at M_t q (warp_affine(frames, M)).  radius = 0: no smoothing, S_t = P_t.
+    Returns M (T, 2, 3) float64 on the motion's device."""
+    import numpy as np
+    torch = _torch()
+    ok = None
+    if isinstance(motion, Motion):
+        motion, ok = motion.motion, motion.ok
+    if not isinstance(motion, torch.Tensor):
+        raise TypeError("motion must be a torch.Tensor or a Motion, got %s" % type(motion).__name__)
+    if motion.dim() != 3 or tuple(motion.shape[1:]) != (2, 3) or motion.shape[0] < 1:
+        raise ValueError("motion must be (T - 1, 2, 3) with T >= 2, got shape %s" % (tuple(motion.shape),))
+    cx, cy = _check_path(radius, crop, size)
+    A = motion.detach().to("cpu", torch.float64).numpy()
+    if ok is not None:
+        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(2, 3))
+    return torch.from_numpy(path_transforms(A, radius, crop, cx, cy)).to(motion.device)
+
+
+def path_transforms(A, radius, crop, cx, cy):
+    """stabilizing_transforms on a numpy (T - 1, 2, 3) float64 array, c = (cx, cy): (T, 2, 3) float64"""
+    import numpy as np
+    n = A.shape[0] + 1
+    P = np.empty((n, 3, 3))
+    P[0] = np.eye(3)
+    for t in range(n - 1):
+        At = np.eye(3)
+        At[:2] = A[t]
+        P[t + 1] = At @ P[t]
+    Z = np.array([[crop, 0.0, cx - crop * cx], [0.0, crop, cy - crop * cy], [0.0, 0.0, 1.0]])
+    M = np.empty((n, 2, 3))
+    for t in range(n):
+        ks = range(max(-radius, -t), min(radius, n - 1 - t) + 1)
+        g = [math.exp(-k * k / (2.0 * (radius / 2.0) ** 2)) if radius > 0 else 1.0 for k in ks]
+        S = sum(gk * P[t + k] for gk, k in zip(g, ks)) / sum(g)
+        M[t] = (P[t] @ np.linalg.inv(S) @ Z)[:2]
+    return M
+
+
+def stabilize_video(frames, pyramidLevels, *, layout="NCHW", model="similarity", radius=15, crop=1.0, iters=5, scale=1.0,
+                    out_dtype=None, **solver):
+    """A video of T >= 2 frames with its camera shake removed: flow_video(frames, pyramidLevels, layout=layout, **solver)
+    (forward float64 flows), global_motion on them (model, iters, scale), stabilizing_transforms (radius, crop; the only
+    wait) and warp_affine of the frames by those matrices.  Returns Stabilized(video (T, ...) in `layout` and out_dtype (by
+    default the frames'), valid (T, H, W) bool, transforms (T, 2, 3) float64, motion (T - 1, 2, 3) float64, ok (T - 1,) bool,
+    flow (T - 1, 2, H, W) float64, timing of the flow call).  Every argument error raises before anything is launched; the
+    video is enqueued on the current stream."""
+    ts, descs, _ = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    code, iters, scale = _check_fit(model, iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    _check_path(radius, crop, (H, W))
+    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
+    _out_code(out_dtype)
+    if solver:
+        capi.default_params(**solver)  # an unknown solver keyword raises here
+    torch = _torch()
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, solver)
+    m = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
+    M = stabilizing_transforms(m, radius, crop, size=(H, W))
+    video, valid = _warp(ts, descs, M, capi.DTYPE_F64, layout, out_dtype)
+    return Stabilized(video, valid, M, m.motion, m.ok, flow, timing)
