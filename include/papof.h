@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 113 /* 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 114 /* 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -618,6 +618,50 @@ long long papof_motion_workspace(int n_pairs, int height, int width);
  * zero stride of out or valid along an axis in use, n_frames, height, width or c < 1. */
 int papof_warp_affine_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
                              const papof_tensor* matrices, const papof_tensor* out, const papof_tensor* valid, void* stream);
+
+/* Motion-compensated temporal denoising (Liu and Freeman, ECCV 2010; the MCTF pre-filter of video encoders): each pixel of
+ * a video of n_frames = T frames is averaged with the points it maps to in frames t +- 1 .. t +- radius, following the
+ * video's forward and backward flows hop by hop and dropping a neighbour where the motion fails the forward-backward check
+ * -- one HIP kernel (denoise.hip: k_temporal_filter), one lane per output pixel.
+ * frames: uint8 (x / 255.0, as the flow's ingest), float32 (widened exactly) or float64, (frame, row, column, channel), any
+ * non-negative strides, c = C channels, 1 <= C <= 4.
+ * flow_fw, flow_bw: the T - 1 pairs' flows as papof_track_tensor takes them -- float32 (widened exactly) or float64, (pair,
+ * row, column, {vx, vy}), any non-negative strides; pair t runs from frame t to frame t + 1 (flow_fw[t]) and back (flow_bw[t]).
+ * out: uint8, float32 or float64, (frame, row, column, channel), strides > 0; out must not overlap frames.
+ * support: NULL, or uint8 (frame, row, column), strides [0..2] > 0 (stride[3] ignored): the number of neighbours that entered.
+ * radius R: 1 .. 16; sigma >= 0 and finite (0: no photometric weight); use_check != 0: the consistency test with alpha1,
+ * alpha2 (finite, >= 0).  For the centre pixel p = (x, r) of frame t, with H, W, C, radius R, s2 = sigma * sigma, in fp64
+ * without fused multiply-adds:
+ *
+ * c_k   = frame[t](r, x, k)                         (uint8 as x / 255.0, float32 widened, float64 as is)
+ * num_k = c_k;  den = 1.0;  support = 0
+ * forward:  (X, Y) = (x, r), alive;  for j = 1 .. min(R, T - 1 - t):
+ *               hop from frame t + j - 1 to t + j exactly as k_track's step: flow_fw[t + j - 1] sampled at (X, Y) -> (X + u, Y + v);
+ *               alive &= inside [0, W - 1] x [0, H - 1];  with the check: flow_bw[t + j - 1] sampled there,
+ *               alive &= (u + bu)^2 + (v + bv)^2 <= a1 * ((u*u + v*v) + (bu*bu + bv*bv)) + a2      (NaN -> not alive)
+ *               once not alive, the chain stays dead
+ *               if alive: g_k = frame[t + j] sampled at (X, Y) (sampler.h taps, k = 0 .. C-1)
+ *                         D = 0; for k: d = g_k - c_k; D += d * d;   D = D / C
+ *                         w = sigma > 0 ? 1.0 / (1.0 + D / s2) : 1.0
+ *                         if w > 0 (false for NaN): num_k += w * g_k; den += w; support += 1
+ * backward: the same from (x, r) for j = 1 .. min(R, t), hop t - j + 1 -> t - j through flow_bw[t - j], checked with flow_fw[t - j]
+ * out_k = num_k / den      stored by sampler.h's store() rule (uint8: clamp(rint(255 v), 0, 255), NaN -> 0)
+ *
+ * The samplers are papof_track_tensor's (flows) and papof_interp_tensor's (frames): the reference's bilinear rule
+ * (src/ImageProcessing.h:138-157), truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image,
+ * taps accumulated from 0 in (m, n) order.  All of the forward sums come first, then all of the backward ones, each in order
+ * of j: the result is bitwise reproducible.  Where nothing enters, den is 1 and the output is the input value.  float32 out is
+ * one round-to-nearest; uint8 rounds half to even.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting:
+ * ordered behind the work queued there so far, and ahead of what follows.  No device memory besides the tensors is used.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (support aside) or data pointer, frames or out that
+ * are not uint8 / float32 / float64, flows that are not float32 / float64, a support that is not uint8, a negative stride,
+ * a zero stride of out or support along an axis in use, n_frames < 2, height or width < 1, c outside 1 .. 4, radius
+ * outside 1 .. 16, a sigma that is not finite or negative, an alpha that is not finite or negative. */
+int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                 const papof_tensor* flow_fw, const papof_tensor* flow_bw, int radius, double sigma,
+                                 int use_check, double alpha1, double alpha2, const papof_tensor* out,
+                                 const papof_tensor* support, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

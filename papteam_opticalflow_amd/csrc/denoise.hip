@@ -1,0 +1,188 @@
+// papteam_opticalflow_amd/csrc/denoise.hip -- motion-compensated temporal denoising (papof_temporal_filter_tensor).
+//
+// Why.  The classic use of dense, consistency-checked flow (Liu and Freeman, "A high-quality video denoising algorithm based
+// on reliable motion estimation", ECCV 2010; MCTF, the pre-filter of video encoders): each pixel of frame t is averaged with
+// the points it maps to in frames t +- 1 .. t +- R, and a sample whose motion cannot be trusted is dropped or down-weighted.
+// Written with grid_sample it is a handful of launches per frame and neighbour and a full-frame temporary per neighbour
+// through HBM.  Here one lane makes one output pixel: it follows the pixel's chain through the flows with its position, the
+// C centre values and the C running sums in registers, and writes each output element once.
+//
+// Semantics: include/papof.h, papof_temporal_filter_tensor.  A hop is k_track's step (track.hip): the flow sampled where the
+// chain is, the new position tested against the image, the reverse flow sampled there and the consistency test; a chain that
+// dies stays dead.  The samplers are sampler.h's (sample_flow: k_track's rule; sample_frame: k_interp's), fp64 without
+// contraction (-ffp-contract=off).  All forward samples are summed first, then all backward ones, in order of distance: the
+// result is bitwise reproducible.
+//
+// Mapping.  A block is a 64 x 4 tile of output pixels (as k_interp's and k_fb_check's): blockIdx.x the tile, blockIdx.y the
+// frame.  A wave is 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose
+// stores are contiguous along a row.  No atomics, no workspace: every output element belongs to one lane.  Every offset is
+// 64-bit.
+#include "sampler.h"
+
+#include <algorithm>
+#include <cmath>
+#include <initializer_list>
+
+namespace papof {
+
+namespace {
+
+constexpr int kFilterTX = 64, kFilterTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+constexpr int kMaxC = 4;                       // channels (registers per lane: centre values, sums, samples)
+constexpr int kMaxRadius = 16;
+constexpr long long kMaxFrames = 65535;        // gridDim.y
+constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
+
+struct FilterArgs {
+    papof_tensor fr;      // frames (frame, row, column, channel)
+    papof_tensor fw, bw;  // flows (pair, row, column, {vx, vy}); pair t runs from frame t to t + 1
+    papof_tensor out;     // (frame, row, column, channel)
+    papof_tensor sup;     // uint8 support (frame, row, column); data NULL: none
+    int T, H, W, C, R;
+    int check;            // the consistency test is applied
+    double sigma, s2;     // sigma > 0: the photometric weight 1 / (1 + D / s2), s2 = sigma * sigma
+    double a1, a2;
+};
+
+// The samples of one direction of frame t's pixel (x, r), added to num / den / support.  dir = +1: hops t + j - 1 -> t + j
+// through f = flow_fw[t + j - 1], checked with b = flow_bw[t + j - 1]; dir = -1: t - j + 1 -> t - j through f = flow_bw[t - j],
+// checked with b = flow_fw[t - j].
+template <int FD>
+__device__ __forceinline__ void chain(const FilterArgs& a, const papof_tensor& f, const papof_tensor& b, long long t, int dir,
+                                      int steps, double X, double Y, const double* c, double* num, double& den, int& support,
+                                      const double* lut) {
+    const int H = a.H, W = a.W;
+    for (int j = 1; j <= steps; j++) {
+        const long long pair = dir > 0 ? t + j - 1 : t - j, frame = t + dir * j;
+        double u, v;
+        sample_flow(f, pair * f.stride[0], taps_at(X, Y, H, W), u, v);
+        const double nX = X + u, nY = Y + v;
+        bool alive = nX >= 0 && nX <= (double)(W - 1) && nY >= 0 && nY <= (double)(H - 1);  // (false for a NaN)
+        if (alive && a.check) {
+            double bu, bv;
+            sample_flow(b, pair * b.stride[0], taps_at(nX, nY, H, W), bu, bv);
+            const double du = u + bu, dv = v + bv;
+            const double e = du * du + dv * dv;
+            const double mag = (u * u + v * v) + (bu * bu + bv * bv);
+            alive = e <= a.a1 * mag + a.a2;  // (false for a NaN)
+        }
+        if (!alive) return;  // once dead, the chain stays dead
+        X = nX;
+        Y = nY;
+        const Taps k = taps_at(X, Y, H, W);
+        const long long base = frame * a.fr.stride[0];
+        double g[kMaxC], D = 0.0;
+#pragma unroll
+        for (int ch = 0; ch < kMaxC; ch++)
+            if (ch < a.C) {
+                g[ch] = sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], k, lut);
+                const double d = g[ch] - c[ch];
+                D += d * d;
+            }
+        D = D / (double)a.C;
+        const double w = a.sigma > 0 ? 1.0 / (1.0 + D / a.s2) : 1.0;
+        if (w > 0) {  // (false for a NaN)
+#pragma unroll
+            for (int ch = 0; ch < kMaxC; ch++)
+                if (ch < a.C) num[ch] += w * g[ch];
+            den += w;
+            support += 1;
+        }
+    }
+}
+
+// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+template <int FD>
+__global__ __launch_bounds__(kFilterTX* kFilterTY) void k_temporal_filter(const FilterArgs a, long long tile0,
+                                                                          long long frame0) {
+    __shared__ double lut[256];
+    if (FD == PAPOF_DTYPE_U8) {
+        fill_u8_lut(lut, threadIdx.y * kFilterTX + threadIdx.x);  // (256 lanes: one quotient each)
+        __syncthreads();
+    }
+    const long long tx = (a.W + kFilterTX - 1) / kFilterTX, tile = tile0 + blockIdx.x;
+    const int x = (int)(tile % tx) * kFilterTX + (int)threadIdx.x;
+    const long long r = (tile / tx) * kFilterTY + threadIdx.y;
+    if (x >= a.W || r >= a.H) return;
+    const long long t = frame0 + blockIdx.y;
+    const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
+    double c[kMaxC], num[kMaxC];
+#pragma unroll
+    for (int ch = 0; ch < kMaxC; ch++)
+        if (ch < a.C) num[ch] = c[ch] = load_frame<FD>(a.fr, pix + ch * a.fr.stride[3], lut);
+    double den = 1.0;
+    int support = 0;
+    const int fwd = a.T - 1 - t < a.R ? (int)(a.T - 1 - t) : a.R, bwd = t < a.R ? (int)t : a.R;
+    chain<FD>(a, a.fw, a.bw, t, +1, fwd, (double)x, (double)r, c, num, den, support, lut);
+    chain<FD>(a, a.bw, a.fw, t, -1, bwd, (double)x, (double)r, c, num, den, support, lut);
+    const long long o = t * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+#pragma unroll
+    for (int ch = 0; ch < kMaxC; ch++)
+        if (ch < a.C) store(a.out, o + ch * a.out.stride[3], num[ch] / den);
+    if (a.sup.data)
+        static_cast<unsigned char*>(a.sup.data)[t * a.sup.stride[0] + r * a.sup.stride[1] + x * a.sup.stride[2]] =
+            (unsigned char)support;
+}
+
+int launch_filter(hipStream_t st, const FilterArgs& a) {
+    const auto kernel = a.fr.dtype == PAPOF_DTYPE_U8    ? k_temporal_filter<PAPOF_DTYPE_U8>
+                        : a.fr.dtype == PAPOF_DTYPE_F32 ? k_temporal_filter<PAPOF_DTYPE_F32>
+                                                        : k_temporal_filter<PAPOF_DTYPE_F64>;
+    const long long tiles =
+        ((a.W + kFilterTX - 1) / (long long)kFilterTX) * ((a.H + kFilterTY - 1) / (long long)kFilterTY);
+    for (long long f0 = 0; f0 < a.T; f0 += kMaxFrames)
+        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
+            const unsigned nf = (unsigned)std::min(kMaxFrames, a.T - f0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
+            hipLaunchKernelGGL(kernel, dim3(nt, nf), dim3(kFilterTX, kFilterTY), 0, st, a, t0, f0);
+            PAPOF_HIP(hipGetLastError());
+        }
+    return PAPOF_OK;
+}
+
+// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0)
+bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
+    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
+    for (int i : axes)
+        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
+    return true;
+}
+
+}  // namespace
+
+}  // namespace papof
+
+using namespace papof;
+
+extern "C" int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                            const papof_tensor* frames, const papof_tensor* flow_fw,
+                                            const papof_tensor* flow_bw, int radius, double sigma, int use_check,
+                                            double alpha1, double alpha2, const papof_tensor* out,
+                                            const papof_tensor* support, void* stream) {
+    if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
+    if (radius < 1 || radius > kMaxRadius || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
+    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0 || alpha2 < 0) return PAPOF_EINVAL;
+    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    if (!described(frames, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (support && !described(support, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    FilterArgs a{};
+    a.fr = *frames;
+    a.fw = *flow_fw;
+    a.bw = *flow_bw;
+    a.out = *out;
+    if (support) a.sup = *support;
+    a.T = n_frames;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    a.R = radius;
+    a.check = use_check ? 1 : 0;
+    a.sigma = sigma;
+    a.s2 = sigma * sigma;
+    a.a1 = alpha1;
+    a.a2 = alpha2;
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_filter(static_cast<hipStream_t>(stream), a);
+}

@@ -1,5 +1,5 @@
 // papteam_opticalflow_amd/csrc/sampler.h -- the bilinear sampler of the device-tensor kernels that read frames at
-// non-integer points (interp.hip: k_interp, motion.hip: k_warp_affine), written once.
+// non-integer points (interp.hip: k_interp, motion.hip: k_warp_affine, denoise.hip: k_temporal_filter), written once.
 //
 // The rule is the reference's (src/ImageProcessing.h:138-157), as k_fb_check and k_track apply it: truncation toward zero,
 // fraction clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0 in (m, n) order; fp64 without
@@ -61,6 +61,19 @@ __device__ __forceinline__ Taps taps_at(double X, double Y, int H, int W) {
             k.w[2 * m + n] = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
         }
     return k;
+}
+
+// (u, v) = the flow t (pair, row, column, {vx, vy}) sampled at the taps from `base` (the pair's offset): k_track's sample()
+// (track.hip), both components accumulated from 0 in (m, n) order.
+__device__ __forceinline__ void sample_flow(const papof_tensor& t, long long base, const Taps& k, double& u, double& v) {
+    u = 0.0;
+    v = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const long long o = base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2];
+        u += load_flow(t, o) * k.w[i];
+        v += load_flow(t, o + t.stride[3]) * k.w[i];
+    }
 }
 
 template <int FD>

@@ -37,6 +37,13 @@ on the host and `warp_affine` (papof_warp_affine_tensor) resamples the frames; `
 
     sv = stabilize_video(frames, 5, layout="NHWC", crop=0.9)   # sv.video: the stabilized frames, sv.valid (T, H, W)
 
+Denoising: `temporal_filter` (include/papof.h: papof_temporal_filter_tensor) averages each pixel with the points it maps to
+in the frames t +- 1 .. t +- radius along the forward and backward flows, dropping neighbours whose motion fails the
+forward-backward check and down-weighting those that look different, in one HIP kernel; `denoise_video` computes the flows
+first (flow_video_fb).
+
+    dv = denoise_video(frames, 5, radius=2, layout="NHWC")   # dv.video: the denoised frames, dv.support (T, H, W) uint8
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -56,6 +63,8 @@ InterpPairs = collections.namedtuple("InterpPairs", "frames flow_fw flow_bw occl
 Interp = collections.namedtuple("Interp", "video flow_fw flow_bw occlusion timing")
 Motion = collections.namedtuple("Motion", "motion ok support")
 Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
+Filtered = collections.namedtuple("Filtered", "video support")
+Denoised = collections.namedtuple("Denoised", "video support flow_fw flow_bw timing")
 MODELS = {"similarity": capi.MOTION_SIMILARITY, "affine": capi.MOTION_AFFINE}
 
 _lock = threading.Lock()
@@ -860,3 +869,105 @@ def stabilize_video(frames, pyramidLevels, *, layout="NCHW", model="similarity",
     M = stabilizing_transforms(m, radius, crop, size=(H, W))
     video, valid = _warp(ts, descs, M, capi.DTYPE_F64, layout, out_dtype)
     return Stabilized(video, valid, M, m.motion, m.ok, flow, timing)
+
+
+MAX_RADIUS = 16  # include/papof.h: papof_temporal_filter_tensor
+MAX_CHANNELS = 4
+
+
+def _check_filter(radius, sigma):
+    """(radius, sigma as a float: 0.0 for None) of temporal_filter's keywords -- TypeError / ValueError otherwise"""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= MAX_RADIUS:
+        raise ValueError("radius must be an integer in 1 .. %d, got %r" % (MAX_RADIUS, radius))
+    if sigma is None:
+        return radius, 0.0
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise TypeError("sigma must be None or a number, got %r" % (sigma,))
+    if not (math.isfinite(sigma) and sigma >= 0):
+        raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
+    return radius, float(sigma)
+
+
+def _check_video(frames, layout, levels, out_dtype):
+    """the frames of temporal_filter / denoise_video: (ts, descs, out_dtype) -- every error before anything is launched"""
+    ts, descs, _ = _check([("frames", frames)], layout, None, levels, min_frames=2)
+    C = descs[0][0][3]
+    if C > MAX_CHANNELS:
+        raise ValueError("frames must have 1 .. %d channels, got %d (layout %s)" % (MAX_CHANNELS, C, layout))
+    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
+    _out_code(out_dtype)
+    return ts, descs, out_dtype
+
+
+def _filter(ts, descs, flows, codes, radius, sigma, alphas, layout, out_dtype):
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    index = _index(dev)
+    shape = (T, C, H, W) if layout == "NCHW" else (T, H, W, C)
+    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    support = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
+    d_sup = _struct(support, (support.stride(0), support.stride(1), support.stride(2), 1), capi.DTYPE_U8)
+    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
+    gpu, lock = _handle(index)
+    with lock, torch.cuda.device(index):
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = gpu.L.papof_temporal_filter_tensor(gpu.h, T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]),
+                                                ctypes.byref(d_f[1]), radius, sigma, 0 if alphas is None else 1, a1, a2,
+                                                ctypes.byref(d_out), ctypes.byref(d_sup), ctypes.c_void_p(stream or None))
+    capi._chk(rc, "papof_temporal_filter_tensor")
+    return Filtered(out, support)
+
+
+def temporal_filter(frames, flow_fw, flow_bw, *, radius=2, sigma=0.15, consistency=CONSISTENCY, layout="NCHW",
+                    out_dtype=None):
+    """Motion-compensated temporal denoising of a video of T >= 2 frames: frames (T, C, H, W) or (T, H, W, C) by `layout`,
+    C = 1 .. 4, uint8 (read as x / 255), float32 or float64, any strides, on a HIP device; flow_fw, flow_bw (T - 1, 2, H, W)
+    float32 / float64 on the same device, pair t from frame t to t + 1 and back, as flow_video_fb returns them.
+    Each pixel of frame t follows its chain through the flows to the frames t + 1 .. t + radius and t - 1 .. t - radius
+    (radius 1 .. 16), hop by hop as track_points moves a point: a chain ends where it leaves the image or -- consistency =
+    (alpha1, alpha2); None: no check -- where the reverse flow does not bring it back.  Every neighbour it reaches enters
+    the average with the weight 1 / (1 + D / sigma^2), D the mean squared difference over the channels of its bilinear
+    sample and the centre pixel (in [0, 1] units for uint8), so that a neighbour that looks different counts less;
+    sigma=None (or 0): every reached neighbour has weight 1.  The centre has weight 1.
+    sigma = 0.15, the default, was calibrated on the committed frames with Gaussian noise of standard deviation 10 / 255
+    (tests/test_denoise_cpu.py): with radius 1 it raises the middle frame's PSNR by 4.06 dB (240x135) and 4.04 dB (480x270),
+    the best of the values tried (0.03 .. 0.2), against 3.98 and 3.90 dB without the photometric weight and 4.77 dB for the
+    ideal average of three aligned samples.
+    Returns Filtered(video in `layout` and out_dtype -- uint8 as clamp(rint(255 x), 0, 255), float32 or float64; by default
+    the frames' dtype --, support (T, H, W) uint8: the number of neighbours that entered).  include/papof.h
+    (papof_temporal_filter_tensor) states the rule exactly.  Enqueued on the current stream; returns without waiting."""
+    alphas = _alphas(consistency) if consistency is not None else None
+    radius, sigma = _check_filter(radius, sigma)
+    ts, descs, out_dtype = _check_video(frames, layout, 1, out_dtype)
+    (T, H, W, C), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw)
+    if tuple(flow_fw.shape) != (T - 1, 2, H, W):
+        raise ValueError("the flows must be (T - 1, 2, H, W) = %s for these frames, got %s" % ((T - 1, 2, H, W),
+                                                                                              tuple(flow_fw.shape)))
+    if flow_fw.device != ts[0].device:
+        raise ValueError("the flows are on %s, the frames on %s: all must be on one device" % (flow_fw.device, ts[0].device))
+    return _filter(ts, descs, (flow_fw, flow_bw), codes, radius, sigma, alphas, layout, out_dtype)
+
+
+def denoise_video(frames, pyramidLevels, *, radius=2, sigma=0.15, consistency=CONSISTENCY, layout="NCHW", out_dtype=None,
+                  **solver):
+    """A video of T >= 2 frames denoised along its motion: flow_video_fb(frames, pyramidLevels, layout=layout,
+    consistency=None, out_dtype=torch.float64, **solver) -- both float64 flows of every pair in one launch chain -- followed
+    by temporal_filter on them (radius, sigma, consistency).  Returns Denoised(video, support (T, H, W) uint8, flow_fw,
+    flow_bw (T - 1, 2, H, W) float64, timing of the flow call).  Every argument error raises before anything is launched;
+    the flows are complete on return, the video is enqueued on the current stream behind them."""
+    torch = _torch()
+    alphas = _alphas(consistency) if consistency is not None else None
+    radius, sigma = _check_filter(radius, sigma)
+    ts, descs, out_dtype = _check_video(frames, layout, pyramidLevels, out_dtype)
+    if solver:
+        capi.default_params(**solver)  # an unknown solver keyword raises here
+    T = descs[0][0][0]
+    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, None, solver)
+    f = _filter(ts, descs, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), radius, sigma, alphas, layout,
+                out_dtype)
+    return Denoised(f.video, f.support, fb.flow_fw, fb.flow_bw, fb.timing)
