@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 114 /* 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 115 /* 0.1.15: papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -662,6 +662,82 @@ int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int height, int 
                                  const papof_tensor* flow_fw, const papof_tensor* flow_bw, int radius, double sigma,
                                  int use_check, double alpha1, double alpha2, const papof_tensor* out,
                                  const papof_tensor* support, void* stream);
+
+/* Flow-guided video completion, 1 of 2 (inpaint.hip: k_fill_*): a field filled inside a mask -- the flows under a removed
+ * object before chains can cross it (c = 2), the pixels of a video that no frame shows (papof_propagate_tensor's status 2).
+ * x: n_frames frames of height x width x c, 1 <= c <= 4, uint8 (x / 255.0), float32 (widened exactly) or float64, (frame, row,
+ * column, channel), any non-negative strides.  mask: uint8 (frame, row, column), any non-negative strides (stride[3]
+ * ignored); nonzero marks a hole.  out: uint8, float32 or float64 (frame, row, column, channel), strides > 0, stored by
+ * sampler.h's store() rule (uint8: clamp(rint(255 v), 0, 255), half to even; NaN -> 0); out must not overlap x or mask.
+ * relax: Jacobi sweeps per level, 0 .. 65536.  Per frame and channel, in fp64 without fused multiply-adds:
+ *
+ * level 0 (h x w = height x width): v = x, known where mask == 0; v = 0, unknown elsewhere
+ * pull, l = 0, 1, ..: level l + 1 is ceil(h / 2) x ceil(w / 2), down to 1 x 1 (levels 0 .. L);  pixel (i, j) of level l + 1:
+ *     S = 0; N = 0;  for a = 0, 1: for b = 0, 1: if (2i + a, 2j + b) (row, column) lies in level l and is known there:
+ *                                                     S += v_l(2i + a, 2j + b); N += 1
+ *     N > 0: v = S / N, known;  N = 0: v = 0, unknown
+ * push, l = L - 1 down to 0: a known pixel of level l keeps its value; an unknown pixel (x, y) (column, row) takes
+ *     X = clamp(0.5 * x - 0.25, 0, w' - 1),  Y = clamp(0.5 * y - 0.25, 0, h' - 1)    (h' x w': level l + 1, already filled)
+ *     v = sum over the four taps of level l + 1 at (X, Y), from 0 in (m, n) order, of v_{l+1}(tap) * weight
+ *     (the bilinear rule of papof_interp_tensor: truncation toward zero, fraction clamped to [0, 1], neighbours clamped into
+ *     the level)
+ *   then `relax` Jacobi sweeps over the unknown pixels of level l, each reading only the previous iterate:
+ *     v(x, y) <- ((v(x, y - 1) + v(x, y + 1)) + (v(x - 1, y) + v(x + 1, y))) * 0.25,  neighbours clamped into the level
+ *   (level L, 1 x 1, runs none: a sweep there gives its pixel back)
+ * out = level 0: a pixel outside the mask is stored from its own input value (out of x's dtype: x's bytes), a hole from v.
+ *
+ * A frame with no known pixel comes out as zeros.  The result does not depend on the schedule: it is bitwise reproducible.
+ * workspace: device memory of at least papof_fill_workspace(n_frames, height, width, c) bytes, 8-byte aligned, owned by the
+ * caller, used by nothing else until the work enqueued here has run (on one stream: PyTorch's allocator on that stream).
+ * The handle's arena is not used.  All frames go in every launch (blockIdx.y): 2 + L * (2 + relax) launches per call.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor or data pointer, x or out that are not uint8 / float32
+ * / float64, a mask that is not uint8, a negative stride, a zero stride of out, n_frames, height or width < 1, c outside
+ * 1 .. 4, relax outside 0 .. 65536, a NULL or misaligned workspace, or workspace_bytes below papof_fill_workspace's value. */
+int papof_fill_holes_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* x,
+                            const papof_tensor* mask, int relax, const papof_tensor* out, void* workspace,
+                            long long workspace_bytes, void* stream);
+
+/* Bytes of the workspace of papof_fill_holes_tensor: the sum over its levels l = 0 .. L (h_l x w_l, as stated there) of
+ * 16 * c * P + 8 * ceil(P / 8), P = n_frames * h_l * w_l -- two fp64 iterates and a known byte per pixel; -1 for n_frames,
+ * height or width < 1, c outside 1 .. 4, or height * width above 2^31 - 1 blocks of 256 pixels. */
+long long papof_fill_workspace(int n_frames, int height, int width, int c);
+
+/* Flow-guided video completion, 2 of 2 (inpaint.hip: k_propagate): the holes of T = n_frames frames filled from other frames
+ * along the flows, one lane per output pixel.
+ * frames: uint8 (x / 255.0), float32 (widened exactly) or float64, (frame, row, column, channel), any non-negative strides,
+ * c = C channels, 1 <= C <= 4.  masks: uint8 (frame, row, column), any non-negative strides; nonzero marks a hole.
+ * flow_fw, flow_bw: the T - 1 (completed) flows as papof_track_tensor takes them, float32 / float64 (pair, row, column,
+ * {vx, vy}), any non-negative strides; pair t runs from frame t to frame t + 1 (flow_fw[t]) and back (flow_bw[t]).
+ * out: uint8, float32 or float64 (frame, row, column, channel), strides > 0, sampler.h's store() rule; status: uint8 (frame,
+ * row, column), strides [0..2] > 0; neither may overlap the inputs.  radius R: 1 .. T - 1; use_check != 0: the consistency
+ * test with alpha1, alpha2 (finite, >= 0).  For pixel p = (x, r) of frame t, in fp64 without fused multiply-adds:
+ *
+ * masks[t](r, x) == 0:  out = frame[t](r, x) (its own input value), status = 0
+ * a hole:
+ *   forward:  (X, Y) = (x, r), alive;  for j = 1 .. min(R, T - 1 - t):
+ *                 hop from frame t + j - 1 to t + j exactly as papof_temporal_filter_tensor's: flow_fw[t + j - 1] sampled at
+ *                 (X, Y) -> (X + u, Y + v); alive &= inside [0, W - 1] x [0, H - 1]; with the check, flow_bw[t + j - 1]
+ *                 sampled there, alive &= (u + bu)^2 + (v + bv)^2 <= a1 * ((u*u + v*v) + (bu*bu + bv*bv)) + a2 (NaN -> not
+ *                 alive); a chain that dies stays dead and gives no candidate
+ *                 if alive and masks[t + j] is 0 at all four clamped taps of (X, Y) (sampler.h: taps_at; whatever their
+ *                 weights): g_f = frame[t + j] sampled at (X, Y) (per channel), d_f = j; the chain stops
+ *   backward: the same from (x, r) for j = 1 .. min(R, t), hop t - j + 1 -> t - j through flow_bw[t - j], checked with
+ *             flow_fw[t - j]: g_b, d_b
+ *   both:     w_f = 1.0 / d_f, w_b = 1.0 / d_b, out_k = (w_f * g_f,k + w_b * g_b,k) / (w_f + w_b), status = 1
+ *   one:      out = that candidate's g, status = 1
+ *   none:     out = frame[t](r, x) (its own input value), status = 2
+ *
+ * The samplers are papof_temporal_filter_tensor's.  Enqueued on `stream` (the caller's hipStream_t on the handle's device,
+ * NULL: the null stream) and returns without waiting.  No device memory besides the tensors is used; no atomics.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor or data pointer, frames or out that are not uint8 /
+ * float32 / float64, masks or status that are not uint8, flows that are not float32 / float64, a negative stride, a zero
+ * stride of out or status along an axis in use, n_frames < 2, height or width < 1, c outside 1 .. 4, radius outside
+ * 1 .. n_frames - 1, an alpha that is not finite or negative. */
+int papof_propagate_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                           const papof_tensor* masks, const papof_tensor* flow_fw, const papof_tensor* flow_bw, int radius,
+                           int use_check, double alpha1, double alpha2, const papof_tensor* out, const papof_tensor* status,
+                           void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
