@@ -739,6 +739,74 @@ int papof_propagate_tensor(papof_handle* h, int n_frames, int height, int width,
                            int use_check, double alpha1, double alpha2, const papof_tensor* out, const papof_tensor* status,
                            void* stream);
 
+/* Blind video temporal consistency (Bonneel et al., SIGGRAPH Asia 2015; consistency.hip): a video P that a per-frame process
+ * made from the video I, made consistent along I's flows -- each output frame keeps P_t's spatial gradients and follows the
+ * previous output frame, warped along the flow, where the flow can be trusted.  One screened-Poisson solve per frame, the
+ * frames a chain: frame t starts when frame t - 1 is stored.  Callers discover it by its symbol.
+ * frames I: uint8 (x / 255.0), float32 (widened exactly) or float64, (frame, row, column, channel), any non-negative strides,
+ * c_frames = C_I channels.  processed P: the same dtypes, (frame, row, column, channel), any non-negative strides, c_out = C_P
+ * channels; 1 <= C_I, C_P <= 4 (they may differ).  flow_fw, flow_bw: the T - 1 pairs' flows as papof_track_tensor takes them,
+ * float32 / float64 (pair, row, column, {vx, vy}), any non-negative strides; pair t - 1 runs from frame t - 1 to t:
+ * flow_bw[t - 1] lives on frame t's grid and points into frame t - 1.  first: NULL (frame 0 is P_0), or one frame of C_P
+ * channels, uint8 / float32 / float64 (ignored, row, column, channel), strides [1..3] >= 0.  out O: uint8, float32 or float64
+ * (frame, row, column, channel), strides > 0, C_P channels, stored by sampler.h's store() rule (uint8: clamp(rint(255 v), 0,
+ * 255), half to even; NaN -> 0); out must not overlap an input or the workspace.  lambda >= 0, sigma >= 0, both finite;
+ * iters 0 .. 65536; use_check != 0: the consistency test with alpha1, alpha2 (finite, >= 0).
+ * In fp64 without fused multiply-adds, with H, W, n(p) = the number of p's 4-neighbours inside the image:
+ *
+ * O_0 = store(first) if first != NULL, else store(P_0)
+ * frame t = 1 .. T - 1, pixel p = (x, r):
+ *   hop, exactly as papof_temporal_filter_tensor's backward hop: (u, v) = flow_bw[t - 1] sampled at (x, r) (sampler.h taps),
+ *     (X, Y) = (x + u, r + v); valid = inside [0, W - 1] x [0, H - 1]; with the check, (fu, fv) = flow_fw[t - 1] sampled at
+ *     (X, Y), valid &= (u + fu)^2 + (v + fv)^2 <= a1 * ((u*u + v*v) + (fu*fu + fv*fv)) + a2      (NaN -> not valid)
+ *   if valid: D = 0; for k < C_I: d = I_t,k(p) - I_{t-1},k sampled at (X, Y); D += d * d;   D = D / C_I
+ *             w = sigma > 0 ? lambda / (1.0 + D / (sigma * sigma)) : lambda
+ *   w = 0 where not valid or where w is not > 0 (lambda = 0, a NaN); then a = 0 and r_k = 0; else a = w / lambda and
+ *             r_k = (O_{t-1},k read back in out's dtype, sampled at (X, Y)) - P_t,k(p)                      (k < C_P)
+ *   start value delta0 (per channel), pull-push with confidences (papof_fill_holes_tensor's levels, child order and push
+ *   point): level 0 holds (a, r); level l + 1 is ceil(h / 2) x ceil(w / 2), down to 1 x 1 (levels 0 .. L)
+ *     pull, pixel (i, j) of level l + 1: over the children (2i + a', 2j + b') inside level l, a' then b', from 0:
+ *           A = sum of a_child;  S_k = sum of a_child * v_child,k;   v_k = A > 0 ? S_k / A : 0;   a = min(A, 1)
+ *     push, l = L - 1 down to 0 (level L keeps its pulled value): g_k = level l + 1 (already pushed) sampled by the taps at
+ *           (clamp(0.5 x - 0.25, 0, w' - 1), clamp(0.5 y - 0.25, 0, h' - 1)), accumulated from 0 in (m, n) order;
+ *           v_k <- a * v_k + (1.0 - a) * g_k
+ *     delta0 = level 0 after its push (a 1 x 1 frame, L = 0: r itself)
+ *   iters Jacobi sweeps of (L + diag w) delta = w r, L the 4-neighbour graph Laplacian with Neumann borders; each reads only
+ *   the previous iterate:
+ *     S = ((delta(x, r - 1) + delta(x, r + 1)) + (delta(x - 1, r) + delta(x + 1, r))), a neighbour outside the image
+ *         entering as +0.0 (as leaving it out, but for the sign of a zero sum)
+ *     den = n(p) + w;   delta(p) <- den != 0 ? (S + w * r_k) / den : 0      (den = 0: a 1 x 1 frame with w = 0)
+ *   O_t,k(p) = store(P_t,k(p) + delta_k(p))
+ *
+ * This is Jacobi on the minimiser of sum over edges of (grad O - grad P)^2 + sum over p of w (O - Ohat)^2, O = P_t + delta.
+ * lambda = 0: w = a = r = 0 everywhere and delta = +0.0, so O = store(P + 0.0): with out of P's dtype, P's bytes, but for a
+ * float -0.0 of P, which comes back as +0.0.  O_{t-1} is read back from out, so a video cut into chunks that overlap by one
+ * frame, each chunk given the previous chunk's last output frame as `first` (of out's dtype), gives the bytes of one call.
+ * The result does not depend on the schedule or on PAPOF_TC_DEPTH (sweeps per launch): it is bitwise reproducible.
+ * workspace: device memory of at least papof_consistency_workspace(height, width, c_out) bytes, 8-byte aligned, owned by
+ * the caller, used by nothing else until the work enqueued here has run (on one stream: PyTorch's allocator on that
+ * stream); it holds one frame's levels and is reused by every frame.  The handle's arena is not used.  Per frame t >= 1:
+ * 1 + 2 L + max(1, ceil(iters / depth)) launches, depth = PAPOF_TC_DEPTH (1 .. 15, default 8); one more for frame 0.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream), back to back with no host
+ * synchronisation, and returns without waiting.  No atomics.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (first aside) or data pointer, frames, processed,
+ * first or out that are not uint8 / float32 / float64, flows that are not float32 / float64, a negative stride, a zero
+ * stride of out, out overlapping an input or the workspace, the workspace overlapping an input, n_frames < 2, height or
+ * width < 1, c_frames or c_out outside 1 .. 4, a lambda or sigma that is not finite or negative, iters outside 0 .. 65536,
+ * an alpha that is not finite or negative, a NULL or misaligned workspace, or workspace_bytes below
+ * papof_consistency_workspace's value. */
+int papof_temporal_consistency_tensor(papof_handle* h, int n_frames, int height, int width, int c_frames, int c_out,
+                                      const papof_tensor* frames, const papof_tensor* processed, const papof_tensor* flow_fw,
+                                      const papof_tensor* flow_bw, const papof_tensor* first, double lambda, double sigma,
+                                      int iters, int use_check, double alpha1, double alpha2, const papof_tensor* out,
+                                      void* workspace, long long workspace_bytes, void* stream);
+
+/* Bytes of the workspace of papof_temporal_consistency_tensor: 8 * ((2 + 3 c_out) P_0 + sum over levels l = 1 .. L of
+ * (1 + c_out) P_l), P_l = h_l * w_l (the levels stated there) -- level 0's confidences, weights, residuals and two iterates,
+ * each coarser level's confidences and values, all fp64; -1 for height or width < 1, c_out outside 1 .. 4, or
+ * height * width above 2^31 - 1 blocks of 256 pixels. */
+long long papof_consistency_workspace(int height, int width, int c_out);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

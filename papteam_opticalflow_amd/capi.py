@@ -65,6 +65,7 @@ SYMBOLS = [
     "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
     "papof_flow_batch_tensor_fb_init", "papof_motion_fit_tensor", "papof_motion_workspace", "papof_warp_affine_tensor",
     "papof_temporal_filter_tensor", "papof_fill_holes_tensor", "papof_fill_workspace", "papof_propagate_tensor",
+    "papof_temporal_consistency_tensor", "papof_consistency_workspace",
 ]
 
 
@@ -196,6 +197,12 @@ def load():
     L.papof_propagate_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, _T, c_int, c_int, c_double, c_double,
                                          _T, _T, c_void_p]
     L.papof_propagate_tensor.restype = c_int
+    L.papof_temporal_consistency_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, _T,
+                                                    c_double, c_double, c_int, c_int, c_double, c_double, _T, c_void_p,
+                                                    ctypes.c_longlong, c_void_p]
+    L.papof_temporal_consistency_tensor.restype = c_int
+    L.papof_consistency_workspace.argtypes = [c_int, c_int, c_int]
+    L.papof_consistency_workspace.restype = ctypes.c_longlong
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
     _lib = L
