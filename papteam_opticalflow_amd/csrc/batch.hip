@@ -438,18 +438,17 @@ namespace {
 
 papof_tensor shifted(const papof_tensor& t, long long items) {  // the same tensor from item `items` of its first axis on
     papof_tensor r = t;
-    const long long es = t.dtype == PAPOF_DTYPE_U8 ? 1 : (t.dtype == PAPOF_DTYPE_F32 ? 4 : 8);
-    r.data = static_cast<char*>(t.data) + items * t.stride[0] * es;
+    r.data = static_cast<char*>(t.data) + items * t.stride[0] * dtype_bytes(t.dtype);
     return r;
 }
 
-bool valid_tensor(const papof_tensor* t, bool output) {
-    if (!t || !t->data) return false;
-    if (t->dtype != PAPOF_DTYPE_F32 && t->dtype != PAPOF_DTYPE_F64 && (output || t->dtype != PAPOF_DTYPE_U8)) return false;
-    for (int i = 0; i < 4; i++)
-        if (t->stride[i] < 0 || (output && t->stride[i] == 0)) return false;  // (a zero input stride: an expanded tensor)
-    return true;
+// the descriptors of the tensor calls: frames of any dtype (a zero stride: an expanded tensor), and the float32 / float64 flow
+// and warp outputs, every stride positive
+const std::initializer_list<int> kAxes = {0, 1, 2, 3}, kFloat = {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64};
+bool valid_frames(const papof_tensor* t) {
+    return described(t, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, kAxes, false);
 }
+bool valid_output(const papof_tensor* t) { return described(t, kFloat, kAxes, true); }
 
 // The outputs of papof_flow_batch_tensor (flow, warp) and of papof_flow_batch_tensor_fb (also the backward pairs' flow_bw,
 // warp_bw and, when occ is given, the forward-backward check with a1, a2).
@@ -636,19 +635,6 @@ int tensor_entry(papof_handle* h, int n_pairs, int sequence, const papof_tensor*
     return PAPOF_OK;
 }
 
-bool valid_mask(const papof_tensor* t) {  // the uint8 occlusion output: every stride positive
-    if (!t || !t->data || t->dtype != PAPOF_DTYPE_U8) return false;
-    for (int i = 0; i < 4; i++)
-        if (t->stride[i] <= 0) return false;
-    return true;
-}
-
-bool valid_alphas(double a1, double a2) { return std::isfinite(a1) && std::isfinite(a2) && a1 >= 0 && a2 >= 0; }
-
-bool valid_init(const papof_tensor* t) {  // an initial flow: absent, or float32 / float64 data with non-negative strides
-    return !t || (valid_tensor(t, false) && t->dtype != PAPOF_DTYPE_U8);
-}
-
 }  // namespace
 
 }  // namespace papof
@@ -675,8 +661,8 @@ int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const pa
                             int height, int width, int c, int pyramid_levels, const papof_params* params, const papof_tensor* flow,
                             const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_tensor(frames, false) || !valid_tensor(flow, true) || !valid_tensor(warpI2, true)) return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
+    if (!valid_frames(frames) || !valid_output(flow) || !valid_output(warpI2)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
     TensorOut o;
     o.flow = flow;
     o.warp = warpI2;
@@ -689,11 +675,12 @@ int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const
                                const papof_tensor* flow_bw, const papof_tensor* warp_bw, const papof_tensor* occlusion,
                                double alpha1, double alpha2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_tensor(frames, false) || !valid_tensor(flow_fw, true) || !valid_tensor(warp_fw, true) ||
-        !valid_tensor(flow_bw, true) || !valid_tensor(warp_bw, true))
+    if (!valid_frames(frames) || !valid_output(flow_fw) || !valid_output(warp_fw) || !valid_output(flow_bw) ||
+        !valid_output(warp_bw))
         return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
-    if ((occlusion && !valid_mask(occlusion)) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, kAxes, true)) return PAPOF_EINVAL;
+    if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     TensorOut o;
     o.flow = flow_fw;
     o.warp = warp_fw;
@@ -710,9 +697,9 @@ int papof_flow_batch_tensor_init(papof_handle* h, int n_pairs, int sequence, con
                                  const papof_params* params, const papof_tensor* init, const papof_tensor* flow,
                                  const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_tensor(frames, false) || !valid_tensor(flow, true) || !valid_tensor(warpI2, true)) return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
-    if (!valid_init(init)) return PAPOF_EINVAL;
+    if (!valid_frames(frames) || !valid_output(flow) || !valid_output(warpI2)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
+    if (init && !described(init, kFloat, kAxes, false)) return PAPOF_EINVAL;
     TensorOut o;
     o.flow = flow;
     o.warp = warpI2;
@@ -729,12 +716,14 @@ int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, 
                                     const papof_tensor* warp_bw, const papof_tensor* occlusion, double alpha1, double alpha2,
                                     void* stream, double timing_sec[PAPOF_N_TIMERS]) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_tensor(frames, false) || !valid_tensor(flow_fw, true) || !valid_tensor(warp_fw, true) ||
-        !valid_tensor(flow_bw, true) || !valid_tensor(warp_bw, true))
+    if (!valid_frames(frames) || !valid_output(flow_fw) || !valid_output(warp_fw) || !valid_output(flow_bw) ||
+        !valid_output(warp_bw))
         return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_tensor(frames2, false)) return PAPOF_EINVAL;
-    if ((occlusion && !valid_mask(occlusion)) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    if (!valid_init(init_fw) || !valid_init(init_bw)) return PAPOF_EINVAL;
+    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, kAxes, true)) return PAPOF_EINVAL;
+    if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
+    if ((init_fw && !described(init_fw, kFloat, kAxes, false)) || (init_bw && !described(init_bw, kFloat, kAxes, false)))
+        return PAPOF_EINVAL;
     TensorOut o;
     o.flow = flow_fw;
     o.warp = warp_fw;
@@ -754,9 +743,8 @@ int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, c
                           const papof_tensor* flow_bw, double alpha1, double alpha2, const papof_tensor* occlusion,
                           void* stream) {
     if (!h || n_pairs < 1 || height < 1 || width < 1) return PAPOF_EINVAL;
-    for (const papof_tensor* t : {flow_fw, flow_bw})
-        if (!valid_tensor(t, false) || t->dtype == PAPOF_DTYPE_U8) return PAPOF_EINVAL;
-    if (!valid_mask(occlusion) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
+    if (!described(flow_fw, kFloat, kAxes, false) || !described(flow_bw, kFloat, kAxes, false)) return PAPOF_EINVAL;
+    if (!described(occlusion, {PAPOF_DTYPE_U8}, kAxes, true) || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
     return fb_check(h, static_cast<hipStream_t>(stream), *flow_fw, *flow_bw, *occlusion, n_pairs, height, width, alpha1, alpha2);
 }

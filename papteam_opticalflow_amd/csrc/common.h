@@ -15,8 +15,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -312,6 +315,19 @@ inline unsigned long long* take_stamp(papof_handle* h) {
     return s;
 }
 int stamp_only(papof_handle* h);  // kernels.hip
+
+// ---- the argument checks of the device-tensor calls (batch.hip and the video calls) ----
+// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0; a zero input stride is an
+// expanded tensor)
+inline bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
+    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
+    for (int i : axes)
+        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
+    return true;
+}
+// the (alpha1, alpha2) of the forward-backward test: finite and >= 0
+inline bool valid_alphas(double a1, double a2) { return std::isfinite(a1) && std::isfinite(a2) && a1 >= 0 && a2 >= 0; }
+inline long long dtype_bytes(int dtype) { return dtype == PAPOF_DTYPE_U8 ? 1 : dtype == PAPOF_DTYPE_F32 ? 4 : 8; }
 
 // ---- kernels.hip: launch wrappers (all asynchronous on h->stream) ----
 int hwc_to_planar(papof_handle* h, const double* hwc, double* planar, int H, int W, int C, int frames = 1);

@@ -7,8 +7,8 @@
 // output frame, warped along the input video's flow, wherever the flow can be trusted -- one screened-Poisson solve per frame,
 // and frame t cannot start before frame t - 1 is stored.
 //
-// Semantics: include/papof.h, papof_temporal_consistency_tensor.  The hop is k_temporal_filter's backward hop (denoise.hip),
-// the samplers are sampler.h's, the pull-push is papof_fill_holes_tensor's (inpaint.hip) with confidences; fp64 without
+// Semantics: include/papof.h, papof_temporal_consistency_tensor.  The hop is k_temporal_filter's backward hop (sampler.h:
+// hop), the samplers are sampler.h's, the pull-push is papof_fill_holes_tensor's (inpaint.hip) with confidences; fp64 without
 // contraction (-ffp-contract=off).
 //
 // Mapping.  The frames are a chain on the caller's stream, enqueued back to back with no host synchronisation: per frame t
@@ -23,11 +23,8 @@
 // last read of it.  No atomics; every element is written by one lane.  Every offset is 64-bit.
 #include "sampler.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdint>
 #include <cstdlib>
-#include <initializer_list>
 #include <vector>
 
 namespace papof {
@@ -41,7 +38,6 @@ constexpr int kMaxDepth = 15;                  // sweeps per launch: the core ti
 constexpr int kDefaultDepth = 8;               // measured: DESIGN.md 18, profiles/consistency_probe.txt
 constexpr int kMaxC = 4;
 constexpr int kMaxIters = 1 << 16;
-constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
 
 // One pyramid level of the start value, planar: a (h w confidences), v (C planes of h w values).  Level 0's v is r.
 struct Lv {
@@ -49,12 +45,6 @@ struct Lv {
     double* a;
     double* v;
 };
-
-std::vector<std::pair<long long, long long>> level_sizes(long long H, long long W) {
-    std::vector<std::pair<long long, long long>> s{{H, W}};
-    while (s.back().first > 1 || s.back().second > 1) s.push_back({(s.back().first + 1) / 2, (s.back().second + 1) / 2});
-    return s;
-}
 
 // level 0: a, w, r[C], d0[C], d1[C]; every coarser level: a, v[C] -- all fp64
 long long level_doubles(int l, long long px, int C) { return l == 0 ? (2 + 3LL * C) * px : (1 + (long long)C) * px; }
@@ -96,23 +86,13 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_setup(const SetupArgs A, const 
     const long long HW = (long long)H * W;
     const int x = (int)(i % W);
     const long long r = i / W, pair = t - 1;
-    double u, v;
-    sample_flow(A.bw, pair * A.bw.stride[0], taps_at((double)x, (double)r, H, W), u, v);
-    const double X = (double)x + u, Y = (double)r + v;
-    bool valid = X >= 0 && X <= (double)(W - 1) && Y >= 0 && Y <= (double)(H - 1);  // (false for a NaN)
-    if (valid && A.check) {
-        double fu, fv;
-        sample_flow(A.fw, pair * A.fw.stride[0], taps_at(X, Y, H, W), fu, fv);
-        const double du = u + fu, dv = v + fv;
-        const double e = du * du + dv * dv;
-        const double mag = (u * u + v * v) + (fu * fu + fv * fv);
-        valid = e <= A.a1 * mag + A.a2;  // (false for a NaN)
-    }
+    double X, Y;
+    const bool valid = hop(A.bw, A.fw, pair, H, W, A.check, A.a1, A.a2, (double)x, (double)r, X, Y);
     double w = 0.0, a = 0.0, res[kMaxC];
 #pragma unroll
     for (int ch = 0; ch < kMaxC; ch++) res[ch] = 0.0;
     if (valid) {
-        const Taps k = taps_at(X, Y, H, W);
+        const Bilinear k = taps_at(X, Y, H, W);
         const long long pix = t * A.fr.stride[0] + r * A.fr.stride[1] + x * A.fr.stride[2];
         const long long prev = pair * A.fr.stride[0];
         double D = 0.0;
@@ -184,7 +164,7 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_push(const Lv F, const Lv G, do
     X = X > (double)(G.w - 1) ? (double)(G.w - 1) : X;
     Y = Y < 0 ? 0.0 : Y;
     Y = Y > (double)(G.h - 1) ? (double)(G.h - 1) : Y;
-    const Taps k = taps_at(X, Y, (int)G.h, (int)G.w);
+    const Bilinear k = taps_at(X, Y, (int)G.h, (int)G.w);
     const double a = F.a[i];
 #pragma unroll
     for (int ch = 0; ch < kMaxC; ch++)
@@ -352,21 +332,13 @@ int launch_consistency(hipStream_t st, const SetupArgs& A, const papof_tensor* f
     return PAPOF_OK;
 }
 
-// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i : axes)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
-}
-
 // the bytes [lo, hi) a descriptor of sizes n[4] (non-negative strides) can touch
 struct Span {
     std::uintptr_t lo, hi;
 };
 
 Span span(const papof_tensor& t, std::initializer_list<long long> n) {
-    const long long es = t.dtype == PAPOF_DTYPE_U8 ? 1 : t.dtype == PAPOF_DTYPE_F32 ? 4 : 8;
+    const long long es = dtype_bytes(t.dtype);
     unsigned long long last = 0;
     int i = 0;
     for (long long k : n) last += (unsigned long long)(k - 1) * (unsigned long long)t.stride[i++];
@@ -399,8 +371,7 @@ extern "C" int papof_temporal_consistency_tensor(papof_handle* h, int n_frames, 
                                                  void* workspace, long long workspace_bytes, void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1 || c_frames < 1 || c_frames > kMaxC) return PAPOF_EINVAL;
     if (!std::isfinite(lambda) || lambda < 0 || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
-    if (iters < 0 || iters > kMaxIters) return PAPOF_EINVAL;
-    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0 || alpha2 < 0) return PAPOF_EINVAL;
+    if (iters < 0 || iters > kMaxIters || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     const long long need = papof_consistency_workspace(height, width, c_out);
     if (need < 0 || !workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 7) || workspace_bytes < need)
         return PAPOF_EINVAL;

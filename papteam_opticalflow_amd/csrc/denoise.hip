@@ -7,10 +7,9 @@
 // through HBM.  Here one lane makes one output pixel: it follows the pixel's chain through the flows with its position, the
 // C centre values and the C running sums in registers, and writes each output element once.
 //
-// Semantics: include/papof.h, papof_temporal_filter_tensor.  A hop is k_track's step (track.hip): the flow sampled where the
+// Semantics: include/papof.h, papof_temporal_filter_tensor.  A hop is sampler.h's, k_track's step: the flow sampled where the
 // chain is, the new position tested against the image, the reverse flow sampled there and the consistency test; a chain that
-// dies stays dead.  The samplers are sampler.h's (sample_flow: k_track's rule; sample_frame: k_interp's), fp64 without
-// contraction (-ffp-contract=off).  All forward samples are summed first, then all backward ones, in order of distance: the
+// dies stays dead.  The samplers are sampler.h's (sample_flow, sample_frame), fp64 without contraction (-ffp-contract=off).  All forward samples are summed first, then all backward ones, in order of distance: the
 // result is bitwise reproducible.
 //
 // Mapping.  A block is a 64 x 4 tile of output pixels (as k_interp's and k_fb_check's): blockIdx.x the tile, blockIdx.y the
@@ -19,9 +18,7 @@
 // 64-bit.
 #include "sampler.h"
 
-#include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 namespace papof {
 
@@ -30,8 +27,6 @@ namespace {
 constexpr int kFilterTX = 64, kFilterTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
 constexpr int kMaxC = 4;                       // channels (registers per lane: centre values, sums, samples)
 constexpr int kMaxRadius = 16;
-constexpr long long kMaxFrames = 65535;        // gridDim.y
-constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
 
 struct FilterArgs {
     papof_tensor fr;      // frames (frame, row, column, channel)
@@ -54,22 +49,11 @@ __device__ __forceinline__ void chain(const FilterArgs& a, const papof_tensor& f
     const int H = a.H, W = a.W;
     for (int j = 1; j <= steps; j++) {
         const long long pair = dir > 0 ? t + j - 1 : t - j, frame = t + dir * j;
-        double u, v;
-        sample_flow(f, pair * f.stride[0], taps_at(X, Y, H, W), u, v);
-        const double nX = X + u, nY = Y + v;
-        bool alive = nX >= 0 && nX <= (double)(W - 1) && nY >= 0 && nY <= (double)(H - 1);  // (false for a NaN)
-        if (alive && a.check) {
-            double bu, bv;
-            sample_flow(b, pair * b.stride[0], taps_at(nX, nY, H, W), bu, bv);
-            const double du = u + bu, dv = v + bv;
-            const double e = du * du + dv * dv;
-            const double mag = (u * u + v * v) + (bu * bu + bv * bv);
-            alive = e <= a.a1 * mag + a.a2;  // (false for a NaN)
-        }
-        if (!alive) return;  // once dead, the chain stays dead
+        double nX, nY;
+        if (!hop(f, b, pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY)) return;  // once dead, the chain stays dead
         X = nX;
         Y = nY;
-        const Taps k = taps_at(X, Y, H, W);
+        const Bilinear k = taps_at(X, Y, H, W);
         const long long base = frame * a.fr.stride[0];
         double g[kMaxC], D = 0.0;
 #pragma unroll
@@ -130,21 +114,9 @@ int launch_filter(hipStream_t st, const FilterArgs& a) {
                                                         : k_temporal_filter<PAPOF_DTYPE_F64>;
     const long long tiles =
         ((a.W + kFilterTX - 1) / (long long)kFilterTX) * ((a.H + kFilterTY - 1) / (long long)kFilterTY);
-    for (long long f0 = 0; f0 < a.T; f0 += kMaxFrames)
-        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-            const unsigned nf = (unsigned)std::min(kMaxFrames, a.T - f0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
-            hipLaunchKernelGGL(kernel, dim3(nt, nf), dim3(kFilterTX, kFilterTY), 0, st, a, t0, f0);
-            PAPOF_HIP(hipGetLastError());
-        }
-    return PAPOF_OK;
-}
-
-// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i : axes)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
+    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kFilterTX, kFilterTY), 0, st, a, t0, f0);
+    });
 }
 
 }  // namespace
@@ -160,7 +132,7 @@ extern "C" int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int h
                                             const papof_tensor* support, void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
     if (radius < 1 || radius > kMaxRadius || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
-    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0 || alpha2 < 0) return PAPOF_EINVAL;
+    if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     if (!described(frames, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;

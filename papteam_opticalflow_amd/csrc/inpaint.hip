@@ -21,10 +21,7 @@
 // output element belongs to one lane.  Every offset is 64-bit.
 #include "sampler.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdint>
-#include <initializer_list>
 #include <vector>
 
 namespace papof {
@@ -35,8 +32,6 @@ constexpr int kFillBlock = 256;                // lanes per block of the fill ke
 constexpr int kPropTX = 64, kPropTY = 4;       // a 64 x 4 tile of output pixels per block of k_propagate
 constexpr int kMaxC = 4;
 constexpr int kMaxRelax = 1 << 16;
-constexpr long long kMaxFrames = 65535;        // gridDim.y
-constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
 
 // One pyramid level of the fill's workspace: all frames' (row, column, channel) values, row-major, channels innermost.
 struct Level {
@@ -45,13 +40,6 @@ struct Level {
     double* v1;          // the second iterate of the unknown ones
     unsigned char* k;    // 1: known
 };
-
-// The level sizes: level l + 1 is ceil(h / 2) x ceil(w / 2) of level l, down to 1 x 1.
-std::vector<std::pair<long long, long long>> level_sizes(long long H, long long W) {
-    std::vector<std::pair<long long, long long>> s{{H, W}};
-    while (s.back().first > 1 || s.back().second > 1) s.push_back({(s.back().first + 1) / 2, (s.back().second + 1) / 2});
-    return s;
-}
 
 // the bytes of one level of n frames with C channels: two fp64 iterates and the known bytes, rounded up to 8
 long long level_bytes(long long n, long long h, long long w, int C) {
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_push(const Level F, const L
     X = X > (double)(G.w - 1) ? (double)(G.w - 1) : X;
     Y = Y < 0 ? 0.0 : Y;
     Y = Y > (double)(G.h - 1) ? (double)(G.h - 1) : Y;
-    const Taps k = taps_at(X, Y, (int)G.h, (int)G.w);
+    const Bilinear k = taps_at(X, Y, (int)G.h, (int)G.w);
     const long long base = t * G.h * G.w;
 #pragma unroll
     for (int ch = 0; ch < kMaxC; ch++)
@@ -168,16 +156,13 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_store(const Level L, const 
         if (ch < C) store(out, o + ch * out.stride[3], value(L, it, p, C, ch));
 }
 
-// Enqueues one kernel over every pixel of an h x w level of n frames (gridDim.y: the frame, in chunks of kMaxFrames).
+// Enqueues one kernel over every pixel of an h x w level of n frames (gridDim.y: the frame).
 template <typename K, typename... A>
 int launch_level(hipStream_t st, K kernel, long long n, long long h, long long w, const A&... args) {
     const long long blocks = (h * w + kFillBlock - 1) / kFillBlock;  // <= kMaxTiles: papof_fill_workspace
-    for (long long f0 = 0; f0 < n; f0 += kMaxFrames) {
-        const unsigned nf = (unsigned)std::min(kMaxFrames, n - f0);
-        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, nf), dim3(kFillBlock), 0, st, args..., f0);
-        PAPOF_HIP(hipGetLastError());
-    }
-    return PAPOF_OK;
+    return launch_tiles(blocks, n, [&](dim3 grid, long long, long long f0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kFillBlock), 0, st, args..., f0);
+    });
 }
 
 int launch_fill(hipStream_t st, const papof_tensor& x, const papof_tensor& mask, const papof_tensor& out, long long n,
@@ -233,22 +218,11 @@ __device__ __forceinline__ int candidate(const PropArgs& a, const papof_tensor& 
     const unsigned char* mk = static_cast<const unsigned char*>(a.mk.data);
     for (int j = 1; j <= steps; j++) {
         const long long pair = dir > 0 ? t + j - 1 : t - j, frame = t + dir * j;
-        double u, v;
-        sample_flow(f, pair * f.stride[0], taps_at(X, Y, H, W), u, v);
-        const double nX = X + u, nY = Y + v;
-        bool alive = nX >= 0 && nX <= (double)(W - 1) && nY >= 0 && nY <= (double)(H - 1);  // (false for a NaN)
-        if (alive && a.check) {
-            double bu, bv;
-            sample_flow(b, pair * b.stride[0], taps_at(nX, nY, H, W), bu, bv);
-            const double du = u + bu, dv = v + bv;
-            const double e = du * du + dv * dv;
-            const double mag = (u * u + v * v) + (bu * bu + bv * bv);
-            alive = e <= a.a1 * mag + a.a2;  // (false for a NaN)
-        }
-        if (!alive) return 0;  // once dead, the chain stays dead
+        double nX, nY;
+        if (!hop(f, b, pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY)) return 0;  // once dead, the chain stays dead
         X = nX;
         Y = nY;
-        const Taps k = taps_at(X, Y, H, W);
+        const Bilinear k = taps_at(X, Y, H, W);
         const long long mb = frame * a.mk.stride[0];
         bool clear = true;
 #pragma unroll
@@ -312,21 +286,9 @@ int launch_propagate(hipStream_t st, const PropArgs& a) {
                         : a.fr.dtype == PAPOF_DTYPE_F32 ? k_propagate<PAPOF_DTYPE_F32>
                                                         : k_propagate<PAPOF_DTYPE_F64>;
     const long long tiles = ((a.W + kPropTX - 1) / (long long)kPropTX) * ((a.H + kPropTY - 1) / (long long)kPropTY);
-    for (long long f0 = 0; f0 < a.T; f0 += kMaxFrames)
-        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-            const unsigned nf = (unsigned)std::min(kMaxFrames, a.T - f0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
-            hipLaunchKernelGGL(kernel, dim3(nt, nf), dim3(kPropTX, kPropTY), 0, st, a, t0, f0);
-            PAPOF_HIP(hipGetLastError());
-        }
-    return PAPOF_OK;
-}
-
-// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i : axes)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
+    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kPropTX, kPropTY), 0, st, a, t0, f0);
+    });
 }
 
 }  // namespace
@@ -367,8 +329,7 @@ extern "C" int papof_propagate_tensor(papof_handle* h, int n_frames, int height,
                                       const papof_tensor* flow_bw, int radius, int use_check, double alpha1, double alpha2,
                                       const papof_tensor* out, const papof_tensor* status, void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
-    if (radius < 1 || radius > n_frames - 1) return PAPOF_EINVAL;
-    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0 || alpha2 < 0) return PAPOF_EINVAL;
+    if (radius < 1 || radius > n_frames - 1 || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     if (!described(frames, I, {0, 1, 2, 3}, false) || !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false))

@@ -9,8 +9,7 @@
 //
 // Semantics: include/papof.h, papof_interp_tensor.  The bilinear rule is k_fb_check's and k_track's (the reference's,
 // src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image,
-// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler is sampler.h's, shared
-// with motion.hip's k_warp_affine.
+// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler is sampler.h's.
 //
 // Mapping.  A block is a 64 x 4 tile of output pixels (as k_fb_check's): blockIdx.x the tile, blockIdx.y the pair.  A wave is
 // 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose stores are contiguous
@@ -21,7 +20,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 namespace papof {
 
@@ -29,8 +27,6 @@ namespace {
 
 constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
 constexpr int kMaxTimes = 16;                  // times per launch (kernel arguments)
-constexpr long long kMaxPairs = 65535;         // gridDim.y
-constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
 
 struct InterpArgs {
     papof_tensor f0, f1;  // frames of I0 and I1 (frame, row, column, channel); I1 of pair i is f1's frame i + seq
@@ -44,7 +40,7 @@ struct InterpArgs {
     double t[kMaxTimes];
 };
 
-__device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Taps& k) {  // bytes as 0 / 1
+__device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Bilinear& k) {  // bytes as 0 / 1
     const unsigned char* m = static_cast<const unsigned char*>(t.data);
     double o = 0.0;
 #pragma unroll
@@ -86,8 +82,8 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp(const InterpArg
         // (false for a NaN)
         const bool in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
         const bool in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
-        const Taps k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
-        const Taps k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
+        const Bilinear k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
+        const Bilinear k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
         double o0 = 0.0, o1 = 0.0;
         if (a.occ.data && in0 && in1) {
             o0 = sample_mask(a.occ, baseo, k0);
@@ -123,22 +119,11 @@ int launch_interp(hipStream_t st, InterpArgs a, int n_pairs, int n_times, const 
     for (int j0 = 0; j0 < n_times; j0 += kMaxTimes) {
         a.nt = std::min(kMaxTimes, n_times - j0);
         std::copy(times + j0, times + j0 + a.nt, a.t);
-        for (long long p0 = 0; p0 < n_pairs; p0 += kMaxPairs)
-            for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-                const unsigned np = (unsigned)std::min(kMaxPairs, n_pairs - p0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
-                hipLaunchKernelGGL(kernel, dim3(nt, np), dim3(kInterpTX, kInterpTY), 0, st, a, t0, p0, (long long)j0);
-                PAPOF_HIP(hipGetLastError());
-            }
+        PAPOF_TRY(launch_tiles(tiles, n_pairs, [&](dim3 grid, long long t0, long long p0) {
+            hipLaunchKernelGGL(kernel, grid, dim3(kInterpTX, kInterpTY), 0, st, a, t0, p0, (long long)j0);
+        }));
     }
     return PAPOF_OK;
-}
-
-// a descriptor with data, of one of `dtypes`, whose strides are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i = 0; i < 4; i++)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
 }
 
 }  // namespace
@@ -154,10 +139,12 @@ extern "C" int papof_interp_tensor(papof_handle* h, int n_pairs, int sequence, c
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
     const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, false) || (sequence ? frames2 != nullptr : !described(frames2, I, false))) return PAPOF_EINVAL;
-    if (!described(flow_fw, F, false) || !described(flow_bw, F, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, false)) return PAPOF_EINVAL;
-    if (!described(out, I, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
+    const auto all = {0, 1, 2, 3};
+    if (!described(frames, I, all, false) || (sequence ? frames2 != nullptr : !described(frames2, I, all, false)))
+        return PAPOF_EINVAL;
+    if (!described(flow_fw, F, all, false) || !described(flow_bw, F, all, false)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, all, false)) return PAPOF_EINVAL;
+    if (!described(out, I, all, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
     if (n_times < 1 || !times) return PAPOF_EINVAL;
     for (int j = 0; j < n_times; j++)
         if (!std::isfinite(times[j]) || !(times[j] > 0.0 && times[j] < 1.0)) return PAPOF_EINVAL;

@@ -7,6 +7,7 @@
 // /root/reference/Code/Serial/) because the parity bar is bit-compatibility, and the file is compiled
 // with -ffp-contract=off for the same reason.
 #include "common.h"
+#include "sampler.h"
 
 #include <cmath>
 
@@ -142,16 +143,13 @@ __global__ __launch_bounds__(256) void k_emit_outputs(const double* __restrict__
 
 // Forward-backward consistency (Sundaram, Brox, Keutzer 2010; papof_fb_check_tensor, papof_flow_batch_tensor_fb).
 // blockIdx.y = pair * 2 + direction; direction 0 follows the forward flow f = fw into the backward flow b = bw, direction
-// 1 the reverse, on the pixels of the pair's second frame.  For pixel (r, x): (u, v) = f, (X, Y) = (x + u, r + v), (bu, bv)
-// = b sampled bilinearly at (X, Y) by the reference's rule (bilinear_taps / bilinear_apply: truncation toward zero, fraction
-// clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0 in (m, n) order), and the pixel is occluded
-// where (X, Y) leaves [0, W - 1] x [0, H - 1] or !(|(u, v) + (bu, bv)|^2 <= a1 (|(u, v)|^2 + |(bu, bv)|^2) + a2) -- NaN
-// counts as occluded.  fp64 throughout, no contraction (the library's -ffp-contract=off).  mask: 1 byte per (pair, row,
-// column, direction).  A block is a 64 x 4 tile of one direction of one pair: the four taps of neighbouring pixels share lines.
+// 1 the reverse, on the pixels of the pair's second frame.  For pixel (r, x): (u, v) = f at the pixel, (X, Y) = (x + u, r + v),
+// (bu, bv) = b sampled bilinearly at (X, Y) by the reference's rule (sampler.h: sample_flow), and the pixel is occluded
+// where (X, Y) leaves [0, W - 1] x [0, H - 1] or fails sampler.h's fb_passes -- NaN counts as occluded.  f is loaded at the
+// pixel, not sampled: a bilinear sample there would differ where a neighbour is not finite.  fp64 throughout, no contraction
+// (the library's -ffp-contract=off).  mask: 1 byte per (pair, row, column, direction).  A block is a 64 x 4 tile of one
+// direction of one pair: the four taps of neighbouring pixels share lines.
 constexpr int kFbTX = 64, kFbTY = 4;
-__device__ __forceinline__ double flow_load(const papof_tensor& t, long long o) {
-    return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
-}
 __global__ __launch_bounds__(kFbTX * kFbTY) void k_fb_check(const papof_tensor fw, const papof_tensor bw, const papof_tensor mask,
                                                          int H, int W, double a1, double a2) {
     const int tx = (W + kFbTX - 1) / kFbTX;
@@ -162,30 +160,13 @@ __global__ __launch_bounds__(kFbTX * kFbTY) void k_fb_check(const papof_tensor f
     const papof_tensor& f = dir ? bw : fw;
     const papof_tensor& b = dir ? fw : bw;
     const long long of = p * f.stride[0] + r * f.stride[1] + x * f.stride[2];
-    const double u = flow_load(f, of), v = flow_load(f, of + f.stride[3]);
+    const double u = load_flow(f, of), v = load_flow(f, of + f.stride[3]);
     const double X = (double)x + u, Y = (double)r + v;
     bool occluded = true;
     if (X >= 0 && X <= (double)(W - 1) && Y >= 0 && Y <= (double)(H - 1)) {  // (false for a NaN: occluded)
-        const int xx = (int)X, yy = (int)Y;
-        double dx = X - xx, dy = Y - yy;
-        dx = dx > 1 ? 1.0 : dx;
-        dx = dx < 0 ? 0.0 : dx;
-        dy = dy > 1 ? 1.0 : dy;
-        dy = dy < 0 ? 0.0 : dy;
-        double bu = 0.0, bv = 0.0;
-#pragma unroll
-        for (int m = 0; m <= 1; m++)
-#pragma unroll
-            for (int n = 0; n <= 1; n++) {
-                const long long ob = p * b.stride[0] + clampi(yy + n, H) * b.stride[1] + clampi(xx + m, W) * b.stride[2];
-                const double s = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
-                bu += flow_load(b, ob) * s;
-                bv += flow_load(b, ob + b.stride[3]) * s;
-            }
-        const double du = u + bu, dv = v + bv;
-        const double e = du * du + dv * dv;
-        const double mag = (u * u + v * v) + (bu * bu + bv * bv);
-        occluded = !(e <= a1 * mag + a2);
+        double bu, bv;
+        sample_flow(b, p * b.stride[0], taps_at(X, Y, H, W), bu, bv);
+        occluded = !fb_passes(u, v, bu, bv, a1, a2);
     }
     static_cast<unsigned char*>(mask.data)[p * mask.stride[0] + r * mask.stride[1] + x * mask.stride[2] + dir * mask.stride[3]] =
         occluded ? 1 : 0;
@@ -1883,11 +1864,10 @@ int fb_check(papof_handle* h, hipStream_t st, const papof_tensor& fw, const papo
              int pairs, int H, int W, double a1, double a2) {
     const long long tiles = (long long)((W + kFbTX - 1) / kFbTX) * ((H + kFbTY - 1) / kFbTY);
     if (pairs <= 0 || tiles <= 0) return PAPOF_OK;
-    if (tiles > 0x7fffffffLL) return PAPOF_EINVAL;
+    if (tiles > kMaxTiles) return PAPOF_EINVAL;
     const auto at = [](const papof_tensor& t, long long items) {  // the same tensor from pair `items` on
         papof_tensor r = t;
-        const long long es = t.dtype == PAPOF_DTYPE_U8 ? 1 : (t.dtype == PAPOF_DTYPE_F32 ? 4 : 8);
-        r.data = static_cast<char*>(t.data) + items * t.stride[0] * es;
+        r.data = static_cast<char*>(t.data) + items * t.stride[0] * dtype_bytes(t.dtype);
         return r;
     };
     for (int p0 = 0; p0 < pairs; p0 += 32767) {  // (gridDim.y: two directions of at most 32767 pairs per launch)

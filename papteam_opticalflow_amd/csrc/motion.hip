@@ -24,7 +24,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 namespace papof {
 
@@ -36,8 +35,6 @@ constexpr int kSums = 14;                             // include/papof.h: the or
 constexpr int kRow = 16;                              // doubles per partial row (kSums used)
 constexpr int kState = 8;                             // doubles per pair: matrix (6), ok (1), finished (1)
 constexpr int kWarpTX = 64, kWarpTY = 4;              // a 64 x 4 tile of output pixels per block (256 lanes: lut)
-constexpr long long kMaxPairs = 65535;                // gridDim.y
-constexpr long long kMaxTiles = 0x7fffffffLL;         // gridDim.x
 
 long long fit_blocks(int H, int W) {
     return ((W + kFitTX - 1) / (long long)kFitTX) * ((H + kFitTH - 1) / (long long)kFitTH);
@@ -224,11 +221,9 @@ __global__ __launch_bounds__(64) void k_motion_solve(const SolveArgs a, long lon
 int launch_fit(hipStream_t st, FitArgs f, SolveArgs s, int n_pairs, int n_iter) {
     for (int it = 0; it < n_iter; it++) {
         f.iter = s.iter = it;
-        for (long long p0 = 0; p0 < n_pairs; p0 += kMaxPairs) {
-            const unsigned np = (unsigned)std::min(kMaxPairs, n_pairs - p0);
-            hipLaunchKernelGGL(k_motion_sums, dim3((unsigned)f.blocks, np), dim3(kFitTX, kFitTY), 0, st, f, p0);
-            PAPOF_HIP(hipGetLastError());
-        }
+        PAPOF_TRY(launch_tiles(f.blocks, n_pairs, [&](dim3 grid, long long, long long p0) {  // (blocks <= kMaxTiles)
+            hipLaunchKernelGGL(k_motion_sums, grid, dim3(kFitTX, kFitTY), 0, st, f, p0);
+        }));
         hipLaunchKernelGGL(k_motion_solve, dim3((unsigned)n_pairs), dim3(64), 0, st, s, 0LL);
         PAPOF_HIP(hipGetLastError());
     }
@@ -272,7 +267,7 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;
     }
-    const Taps k = taps_at(X, Y, a.H, a.W);
+    const Bilinear k = taps_at(X, Y, a.H, a.W);
     const long long base = i * a.fr.stride[0];
     for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], k, lut));
 }
@@ -283,21 +278,9 @@ int launch_warp(hipStream_t st, const WarpArgs& a, int n_frames) {
                         : fd == PAPOF_DTYPE_F32 ? k_warp_affine<PAPOF_DTYPE_F32>
                                                 : k_warp_affine<PAPOF_DTYPE_F64>;
     const long long tiles = ((a.W + kWarpTX - 1) / (long long)kWarpTX) * ((a.H + kWarpTY - 1) / (long long)kWarpTY);
-    for (long long f0 = 0; f0 < n_frames; f0 += kMaxPairs)
-        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-            const unsigned nf = (unsigned)std::min(kMaxPairs, n_frames - f0), nt = (unsigned)std::min(kMaxTiles, tiles - t0);
-            hipLaunchKernelGGL(kernel, dim3(nt, nf), dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
-            PAPOF_HIP(hipGetLastError());
-        }
-    return PAPOF_OK;
-}
-
-// a descriptor with data, of one of `dtypes`, whose first `axes` strides are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, int axes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i = 0; i < axes; i++)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
+    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
+    });
 }
 
 }  // namespace
@@ -320,10 +303,10 @@ extern "C" int papof_motion_fit_tensor(papof_handle* h, int n_pairs, int height,
     if (!h || n_pairs < 1 || height < 1 || width < 1 || n_iter < 1) return PAPOF_EINVAL;
     if (model != PAPOF_MOTION_SIMILARITY && model != PAPOF_MOTION_AFFINE) return PAPOF_EINVAL;
     if (!std::isfinite(scale) || !(scale > 0)) return PAPOF_EINVAL;
-    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, 4, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, 3, false)) return PAPOF_EINVAL;
-    if (!described(motion, {PAPOF_DTYPE_F64}, 3, true) || !described(ok, {PAPOF_DTYPE_U8}, 1, true) ||
-        !described(support, {PAPOF_DTYPE_F64}, 1, true))
+    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!described(motion, {PAPOF_DTYPE_F64}, {0, 1, 2}, true) || !described(ok, {PAPOF_DTYPE_U8}, {0}, true) ||
+        !described(support, {PAPOF_DTYPE_F64}, {0}, true))
         return PAPOF_EINVAL;
     const long long need = papof_motion_workspace(n_pairs, height, width);
     if (need < 0 || !workspace || workspace_bytes < need) return PAPOF_EINVAL;
@@ -361,9 +344,9 @@ extern "C" int papof_warp_affine_tensor(papof_handle* h, int n_frames, int heigh
                                         const papof_tensor* valid, void* stream) {
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
     const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, 4, false) || !described(out, I, 4, true)) return PAPOF_EINVAL;
-    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, 3, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, 3, true)) return PAPOF_EINVAL;
+    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
     WarpArgs a{};
     a.fr = *frames;
     a.mat = *matrices;

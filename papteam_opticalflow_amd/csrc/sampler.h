@@ -1,10 +1,13 @@
-// papteam_opticalflow_amd/csrc/sampler.h -- the bilinear sampler of the device-tensor kernels that read frames at
-// non-integer points (interp.hip: k_interp, motion.hip: k_warp_affine, denoise.hip: k_temporal_filter), written once.
+// papteam_opticalflow_amd/csrc/sampler.h -- what the device-tensor video kernels share, written once: the bilinear sampler of
+// frames and flows at non-integer points (k_interp, k_warp_affine, k_temporal_filter, k_propagate, the fill and consistency
+// kernels, k_track, k_fb_check), the forward-backward test and the hop of a point through a pair's flows (k_track,
+// k_temporal_filter, k_propagate, k_tc_setup; the test also k_fb_check), and on the host the splitting of a (tile, frame)
+// grid at the grid's bounds and the pyramid level sizes of the fill and consistency workspaces.
 //
-// The rule is the reference's (src/ImageProcessing.h:138-157), as k_fb_check and k_track apply it: truncation toward zero,
-// fraction clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0 in (m, n) order; fp64 without
-// contraction (-ffp-contract=off).  Frames are papof_tensor descriptors (frame, row, column, channel) of uint8 (x / 255.0, as
-// k_ingest_frames computes it), float32 (widened exactly) or float64.
+// The rule is the reference's (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours
+// clamped into the image, taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  Frames are
+// papof_tensor descriptors (frame, row, column, channel) of uint8 (x / 255.0, as k_ingest_frames computes it), float32
+// (widened exactly) or float64.
 #pragma once
 
 #include "common.h"
@@ -38,14 +41,14 @@ __device__ __forceinline__ int clamp_to(int x, int n) {  // EnforceRange, src/Im
 
 // The four taps of the bilinear rule at (X, Y), a point of [0, W - 1] x [0, H - 1], in (m, n) order: their (row, column)
 // offsets in elements of a tensor whose row and column strides are s1, s2 -- for frames and mask alike, offsets are computed
-// per tensor -- and their weights.
-struct Taps {
+// per tensor -- and their weights.  (common.h's Taps are the 1-D correlation taps of the flow's filters.)
+struct Bilinear {
     int row[4], col[4];
     double w[4];
 };
 
-__device__ __forceinline__ Taps taps_at(double X, double Y, int H, int W) {
-    Taps k;
+__device__ __forceinline__ Bilinear taps_at(double X, double Y, int H, int W) {
+    Bilinear k;
     const int xx = (int)X, yy = (int)Y;
     double dx = X - xx, dy = Y - yy;
     dx = dx > 1 ? 1.0 : dx;
@@ -63,9 +66,9 @@ __device__ __forceinline__ Taps taps_at(double X, double Y, int H, int W) {
     return k;
 }
 
-// (u, v) = the flow t (pair, row, column, {vx, vy}) sampled at the taps from `base` (the pair's offset): k_track's sample()
-// (track.hip), both components accumulated from 0 in (m, n) order.
-__device__ __forceinline__ void sample_flow(const papof_tensor& t, long long base, const Taps& k, double& u, double& v) {
+// (u, v) = the flow t (pair, row, column, {vx, vy}) sampled at the taps from `base` (the pair's offset), both components
+// accumulated from 0 in (m, n) order.
+__device__ __forceinline__ void sample_flow(const papof_tensor& t, long long base, const Bilinear& k, double& u, double& v) {
     u = 0.0;
     v = 0.0;
 #pragma unroll
@@ -77,11 +80,38 @@ __device__ __forceinline__ void sample_flow(const papof_tensor& t, long long bas
 }
 
 template <int FD>
-__device__ __forceinline__ double sample_frame(const papof_tensor& t, long long base, const Taps& k, const double* lut) {
+__device__ __forceinline__ double sample_frame(const papof_tensor& t, long long base, const Bilinear& k, const double* lut) {
     double g = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; i++) g += load_frame<FD>(t, base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2], lut) * k.w[i];
     return g;
+}
+
+// The forward-backward test (Sundaram, Brox, Keutzer 2010) of a flow (u, v) and the reverse flow (bu, bv) where it lands:
+// |(u, v) + (bu, bv)|^2 <= a1 (|(u, v)|^2 + |(bu, bv)|^2) + a2, false for a NaN.
+__device__ __forceinline__ bool fb_passes(double u, double v, double bu, double bv, double a1, double a2) {
+    const double du = u + bu, dv = v + bv;
+    const double e = du * du + dv * dv;
+    const double mag = (u * u + v * v) + (bu * bu + bv * bv);
+    return e <= a1 * mag + a2;
+}
+
+// One hop of the point (X, Y) through pair `pair` of the flow f (pair, row, column, {vx, vy}): (nX, nY) = (X, Y) + f sampled
+// at (X, Y).  True where (nX, nY) lies in [0, W - 1] x [0, H - 1] (false for a NaN) and, with `check`, the reverse flow b
+// sampled there passes fb_passes.
+__device__ __forceinline__ bool hop(const papof_tensor& f, const papof_tensor& b, long long pair, int H, int W, int check,
+                                    double a1, double a2, double X, double Y, double& nX, double& nY) {
+    double u, v;
+    sample_flow(f, pair * f.stride[0], taps_at(X, Y, H, W), u, v);
+    nX = X + u;
+    nY = Y + v;
+    bool alive = nX >= 0 && nX <= (double)(W - 1) && nY >= 0 && nY <= (double)(H - 1);
+    if (alive && check) {
+        double bu, bv;
+        sample_flow(b, pair * b.stride[0], taps_at(nX, nY, H, W), bu, bv);
+        alive = fb_passes(u, v, bu, bv, a1, a2);
+    }
+    return alive;
 }
 
 // stores as papof_interp_tensor states: float64 as is, float32 with one round-to-nearest, uint8 = clamp(rint(255 v), 0, 255)
@@ -93,6 +123,29 @@ __device__ __forceinline__ void store(const papof_tensor& t, long long o, double
         static_cast<float*>(t.data)[o] = (float)v;
     else
         static_cast<double*>(t.data)[o] = v;
+}
+
+constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
+constexpr long long kMaxFrames = 65535;        // gridDim.y
+
+// A (tile, frame) grid of `tiles` x `frames` blocks in launches that fit the grid's bounds, frames outermost: launch(grid,
+// tile0, frame0) enqueues one of them, whose blockIdx.x is tile tile0 + x and blockIdx.y frame frame0 + y.
+template <typename L>
+int launch_tiles(long long tiles, long long frames, L launch) {
+    for (long long f0 = 0; f0 < frames; f0 += kMaxFrames)
+        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
+            launch(dim3((unsigned)std::min(kMaxTiles, tiles - t0), (unsigned)std::min(kMaxFrames, frames - f0)), t0, f0);
+            PAPOF_HIP(hipGetLastError());
+        }
+    return PAPOF_OK;
+}
+
+// The pyramid of the fill's and the consistency solve's workspaces: level l + 1 is ceil(h / 2) x ceil(w / 2) of level l, from
+// H x W down to 1 x 1.
+std::vector<std::pair<long long, long long>> level_sizes(long long H, long long W) {
+    std::vector<std::pair<long long, long long>> s{{H, W}};
+    while (s.back().first > 1 || s.back().second > 1) s.push_back({(s.back().first + 1) / 2, (s.back().second + 1) / 2});
+    return s;
 }
 
 }  // namespace

@@ -7,21 +7,21 @@
 // follows one (query, direction) through all T frames with its state in registers: one launch, no host synchronisation, and
 // each (frame, point) entry of the outputs is written once.
 //
-// Semantics: include/papof.h, papof_track_tensor.  The bilinear rule is the reference's (src/ImageProcessing.h:138-157), the
-// one k_fb_check applies to the backward flow: truncation toward zero, fraction clamped to [0, 1], neighbours clamped into
-// the image, taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  At an integer position
-// of finite flows it returns the pixel's value, so a dense track's first step is k_fb_check's test on its pixel.
+// Semantics: include/papof.h, papof_track_tensor.  A step is sampler.h's hop: the flow sampled bilinearly by the reference's
+// rule (src/ImageProcessing.h:138-157), the one k_fb_check applies to the backward flow, the landing point tested against
+// the image and the reverse flow sampled there tested by fb_passes; fp64 without contraction (-ffp-contract=off).  At an
+// integer position of finite flows the sampler returns the pixel's value, so a dense track's first step is k_fb_check's test
+// on its pixel.
 //
 // Mapping.  Queries: blockIdx.y is the direction (0 forward from t0, 1 backward), the 256 lanes of a block are 256 consecutive
 // queries, so a wave's stores at one frame are contiguous in the point index whenever its queries share t0.  Dense: a block
 // is a 64 x 4 tile of frame 0's pixels (as k_fb_check's), forward only; a wave is 64 neighbouring pixels of one row, whose
 // taps share cache lines while the flow is smooth, and whose stores are contiguous.  Every offset is 64-bit: N * T passes
 // 2^31 for a dense 1080p clip of ~1000 frames.
-#include "common.h"
+#include "sampler.h"
 
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 namespace papof {
 
@@ -29,7 +29,6 @@ namespace {
 
 constexpr int kTrackTX = 64, kTrackTY = 4;      // dense: a 64 x 4 tile of start pixels per block
 constexpr int kTrackQ = 256;                    // queries: lanes (queries of one direction) per block
-constexpr long long kMaxTileRows = 65535;       // dense: gridDim.y
 constexpr long long kMaxQueryBlocks = 1LL << 22;  // queries: blocks per launch (2^30 lanes: the x extent stays below 2^32)
 
 struct TrackArgs {
@@ -42,38 +41,6 @@ struct TrackArgs {
     int check;            // the consistency test is applied
     double a1, a2;
 };
-
-__device__ __forceinline__ double load_f(const papof_tensor& t, long long o) {
-    return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
-}
-
-__device__ __forceinline__ int clamp_to(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
-    x = x < 0 ? 0 : x;
-    return x > n - 1 ? n - 1 : x;
-}
-
-// (u, v) = the flow of pair `pair` of t sampled bilinearly at (X, Y), a point of [0, W - 1] x [0, H - 1]
-__device__ __forceinline__ void sample(const papof_tensor& t, long long pair, int H, int W, double X, double Y, double& u,
-                                       double& v) {
-    const int xx = (int)X, yy = (int)Y;
-    double dx = X - xx, dy = Y - yy;
-    dx = dx > 1 ? 1.0 : dx;
-    dx = dx < 0 ? 0.0 : dx;
-    dy = dy > 1 ? 1.0 : dy;
-    dy = dy < 0 ? 0.0 : dy;
-    const long long base = pair * t.stride[0];
-    u = 0.0;
-    v = 0.0;
-#pragma unroll
-    for (int m = 0; m <= 1; m++)
-#pragma unroll
-        for (int n = 0; n <= 1; n++) {
-            const long long o = base + clamp_to(yy + n, H) * t.stride[1] + clamp_to(xx + m, W) * t.stride[2];
-            const double s = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
-            u += load_f(t, o) * s;
-            v += load_f(t, o + t.stride[3]) * s;
-        }
-}
 
 __device__ __forceinline__ void put(const TrackArgs& a, long long t, long long n, double x, double y, bool visible) {
     double* tr = static_cast<double*>(a.tr.data) + t * a.tr.stride[0] + n * a.tr.stride[1];
@@ -104,9 +71,9 @@ __global__ __launch_bounds__(256) void k_track(const TrackArgs a, long long firs
         if (n >= a.n) return;
         dir = (int)blockIdx.y;
         const long long o = n * a.q.stride[0];
-        const double t0 = load_f(a.q, o);
-        x = load_f(a.q, o + a.q.stride[3]);
-        y = load_f(a.q, o + 2 * a.q.stride[3]);
+        const double t0 = load_flow(a.q, o);
+        x = load_flow(a.q, o + a.q.stride[3]);
+        y = load_flow(a.q, o + 2 * a.q.stride[3]);
         // (a NaN or an infinity fails a range test)
         alive = t0 >= 0 && t0 <= (double)(a.T - 1) && t0 == trunc(t0) && x >= 0 && x <= (double)(a.W - 1) && y >= 0 &&
                 y <= (double)(a.H - 1);
@@ -121,18 +88,8 @@ __global__ __launch_bounds__(256) void k_track(const TrackArgs a, long long firs
     for (int k = 0; k < steps; k++) {
         const long long pair = dir ? t - 1 : t;  // backward: t -> t - 1 through flow_bw[t - 1], checked with flow_fw[t - 1]
         if (alive) {
-            double u, v;
-            sample(f, pair, a.H, a.W, x, y, u, v);
-            const double X = x + u, Y = y + v;
-            alive = X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
-            if (alive && a.check) {
-                double bu, bv;
-                sample(b, pair, a.H, a.W, X, Y, bu, bv);
-                const double du = u + bu, dv = v + bv;
-                const double e = du * du + dv * dv;
-                const double mag = (u * u + v * v) + (bu * bu + bv * bv);
-                alive = e <= a.a1 * mag + a.a2;  // (false for a NaN)
-            }
+            double X, Y;
+            alive = hop(f, b, pair, a.H, a.W, a.check, a.a1, a.a2, x, y, X, Y);
             x = alive ? X : qnan;
             y = alive ? Y : qnan;
         }
@@ -144,8 +101,8 @@ __global__ __launch_bounds__(256) void k_track(const TrackArgs a, long long firs
 int launch_track(hipStream_t st, const TrackArgs& a, bool dense) {
     if (dense) {
         const long long tx = (a.W + kTrackTX - 1) / kTrackTX, ty = (a.H + kTrackTY - 1) / kTrackTY;
-        for (long long y0 = 0; y0 < ty; y0 += kMaxTileRows) {
-            const unsigned rows = (unsigned)std::min(kMaxTileRows, ty - y0);
+        for (long long y0 = 0; y0 < ty; y0 += kMaxFrames) {  // (tile rows along gridDim.y: sampler.h's bound)
+            const unsigned rows = (unsigned)std::min(kMaxFrames, ty - y0);
             hipLaunchKernelGGL(k_track<true>, dim3((unsigned)tx, rows), dim3(kTrackTX, kTrackTY), 0, st, a, y0);
             PAPOF_HIP(hipGetLastError());
         }
@@ -158,14 +115,6 @@ int launch_track(hipStream_t st, const TrackArgs& a, bool dense) {
         }
     }
     return PAPOF_OK;
-}
-
-// a descriptor with data, of one of `dtypes`, whose strides along `axes` are >= 0 (positive: > 0)
-bool described(const papof_tensor* t, std::initializer_list<int> dtypes, std::initializer_list<int> axes, bool positive) {
-    if (!t || !t->data || std::find(dtypes.begin(), dtypes.end(), t->dtype) == dtypes.end()) return false;
-    for (int i : axes)
-        if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
-    return true;
 }
 
 }  // namespace
@@ -184,7 +133,7 @@ extern "C" int papof_track_tensor(papof_handle* h, int n_frames, int height, int
     if (queries && (n_queries < 1 || !described(queries, F, {0, 3}, false))) return PAPOF_EINVAL;
     if (!described(tracks, {PAPOF_DTYPE_F64}, {0, 1, 3}, true) || !described(visible, {PAPOF_DTYPE_U8}, {0, 1}, true))
         return PAPOF_EINVAL;
-    if (!std::isfinite(alpha1) || !std::isfinite(alpha2) || alpha1 < 0 || alpha2 < 0) return PAPOF_EINVAL;
+    if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     TrackArgs a{};
     a.fw = *flow_fw;
     a.bw = *flow_bw;

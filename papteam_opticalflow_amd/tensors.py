@@ -141,8 +141,9 @@ def _as4d(name, t):
     return t
 
 
-def _check(named, layout, out_dtype, levels, min_frames=1):
-    """every argument error, before anything is launched: (4-D tensors, their descriptors, the output dtype)"""
+def _check(named, layout, out_dtype, levels, min_frames=1, solver=None):
+    """every argument error, before anything is launched: (4-D tensors, their descriptors, the output dtype, the solver's
+    papof_params of the keywords `solver` -- None without any; an unknown keyword raises here)"""
     torch = _torch()
     if layout not in LAYOUTS:
         raise ValueError("layout must be one of %s, got %r" % (LAYOUTS, layout))
@@ -166,7 +167,7 @@ def _check(named, layout, out_dtype, levels, min_frames=1):
             raise ValueError("%s is on %s, %s on %s: all frames must be on one device" % (n, t.device, named[0][0], dev))
     if not _on_gpu(ts[0]):
         raise ValueError("frames must be on a HIP device (cuda:N), got %s" % dev)
-    return ts, descs, out_dtype
+    return ts, descs, out_dtype, capi.default_params(**solver) if solver else None
 
 
 def _handle(device):
@@ -179,7 +180,10 @@ def _handle(device):
 
 
 def _alphas(consistency):
-    """(alpha1, alpha2) of a `consistency` argument: two finite numbers >= 0 (ValueError / TypeError otherwise)"""
+    """(use_check, alpha1, alpha2) of a `consistency` argument: (0, 0.0, 0.0) for None, else two finite numbers >= 0
+    (ValueError / TypeError otherwise)"""
+    if consistency is None:
+        return 0, 0.0, 0.0
     try:
         a1, a2 = consistency
         a1, a2 = float(a1), float(a2)
@@ -187,23 +191,46 @@ def _alphas(consistency):
         raise TypeError("consistency must be None or (alpha1, alpha2), got %r" % (consistency,)) from None
     if not (math.isfinite(a1) and math.isfinite(a2) and a1 >= 0 and a2 >= 0):
         raise ValueError("alpha1 and alpha2 must be finite and >= 0, got %r, %r" % (a1, a2))
-    return a1, a2
+    return 1, a1, a2
 
 
 def _index(dev):
     return dev.index if dev.index is not None else _torch().cuda.current_device()
 
 
+def _launch(dev, name, *args, workspace=None, timers=None):
+    """gpu.L.<name>(handle, *args[, workspace, its bytes], stream[, timers]) under the lock of the handle of `dev`, in the
+    device, on its current stream; a failing return code raises.  workspace: (the papof_*_workspace function, its arguments,
+    the ValueError's text when it refuses them); the bytes come from PyTorch's allocator on the current stream, so they are
+    reused only behind the work queued here.  timers: the ctypes array that follows the stream."""
+    torch = _torch()
+    index = _index(dev)
+    gpu, lock = _handle(index)
+    if workspace is not None:
+        size, size_args, refusal = workspace
+        nbytes = getattr(gpu.L, size)(*size_args)
+        if nbytes < 0:
+            raise ValueError(refusal)
+    with lock, torch.cuda.device(index):
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if workspace is not None else None
+        extra = (ctypes.c_void_p(ws.data_ptr()), nbytes) if ws is not None else ()
+        stream = torch.cuda.current_stream(index).cuda_stream
+        rc = getattr(gpu.L, name)(gpu.h, *args, *extra, ctypes.c_void_p(stream or None), *(() if timers is None else (timers,)))
+        del ws  # back to the allocator behind the call, on this stream
+    capi._chk(rc, name)
+
+
+def _new_frames(n, H, W, C, layout, out_dtype, dev):
+    """a new (n, C, H, W) (NCHW) or (n, H, W, C) (NHWC) tensor of out_dtype and its descriptor"""
+    out = _torch().empty((n, C, H, W) if layout == "NCHW" else (n, H, W, C), dtype=out_dtype, device=dev)
+    return out, _struct(out, *descriptor(out, layout)[1:])
+
+
 def _outputs(n_pairs, H, W, C, layout, out_dtype, dev):
     """a new flow tensor (B, 2, H, W) and warpI2 in `layout`, and their descriptors"""
-    torch = _torch()
-    flow = torch.empty((n_pairs, 2, H, W), dtype=out_dtype, device=dev)
-    if layout == "NCHW":
-        warp = torch.empty((n_pairs, C, H, W), dtype=out_dtype, device=dev)
-    else:
-        warp = torch.empty((n_pairs, H, W, C), dtype=out_dtype, device=dev)
-    out_code = capi.DTYPE_F32 if out_dtype == torch.float32 else capi.DTYPE_F64
-    return flow, warp, _struct(flow, (2 * H * W, W, 1, H * W), out_code), _struct(warp, descriptor(warp, layout)[1], out_code)
+    flow = _torch().empty((n_pairs, 2, H, W), dtype=out_dtype, device=dev)
+    warp, d_warp = _new_frames(n_pairs, H, W, C, layout, out_dtype, dev)
+    return flow, warp, _flow_struct(flow, _out_code(out_dtype)), d_warp
 
 
 def _mask(n_pairs, H, W, dev):
@@ -248,29 +275,26 @@ def _ref(d):
     return ctypes.byref(d) if d is not None else None
 
 
-def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, solver, init_flow=None):
-    torch = _torch()
-    params = capi.default_params(**solver) if solver else None
+def _head(ts, descs, sequence, n_pairs, levels, params):
+    """the arguments of the flow calls from n_pairs to params"""
+    (_, H, W, C), _, _ = descs[0]
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    return (n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W, C,
+            int(levels), _ref(params))
+
+
+def _run(ts, descs, sequence, n_pairs, layout, out_dtype, levels, params, init_flow=None):
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
     d_init = _check_init("init_flow", init_flow, n_pairs, H, W, dev)
-    index = _index(dev)
     flow, warp, d_flow, d_warp = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
-    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    head = _head(ts, descs, sequence, n_pairs, levels, params)
     t = (ctypes.c_double * capi.N_TIMERS)()
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        head = (gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W,
-                C, int(levels), ctypes.byref(params) if params is not None else None)
-        tail = (ctypes.byref(d_flow), ctypes.byref(d_warp), ctypes.c_void_p(stream or None), t)
-        if d_init is None:
-            what = "papof_flow_batch_tensor"
-            rc = gpu.L.papof_flow_batch_tensor(*head, *tail)
-        else:
-            what = "papof_flow_batch_tensor_init"
-            rc = gpu.L.papof_flow_batch_tensor_init(*head, ctypes.byref(d_init), *tail)
-    capi._chk(rc, what)
+    if d_init is None:
+        _launch(dev, "papof_flow_batch_tensor", *head, ctypes.byref(d_flow), ctypes.byref(d_warp), timers=t)
+    else:
+        _launch(dev, "papof_flow_batch_tensor_init", *head, ctypes.byref(d_init), ctypes.byref(d_flow), ctypes.byref(d_warp),
+                timers=t)
     return flow, warp, capi.format_timing(list(t))
 
 
@@ -281,45 +305,34 @@ def flow_pairs(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, init_f
     float32 or float64 on the frames' device, any strides, every component finite and at most 1e6 in magnitude; it enters
     the coarsest pyramid level through the frames' own pyramid, scaled to that level (include/papof.h:
     papof_flow_batch_tensor_init states the rule).  An all-zero init_flow gives the bits of none."""
-    ts, descs, out_dtype = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels)
-    return _run(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, solver, init_flow)
+    ts, descs, out_dtype, params = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, solver=solver)
+    return _run(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, params, init_flow)
 
 
 def flow_video(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, init_flow=None, **solver):
     """Flow of the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames (each frame's pyramid is built once).
     Returns (flow (T - 1, 2, H, W), warpI2 (T - 1, ...) in `layout`, the reference's dict of ten timers).
     init_flow: as flow_pairs's, with B = T - 1."""
-    ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
-    return _run(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, solver, init_flow)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
+    return _run(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, params, init_flow)
 
 
-def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, consistency, solver, init_flow=None, init_flow_bw=None):
+def _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, init_flow=None, init_flow_bw=None):
     torch = _torch()
-    params = capi.default_params(**solver) if solver else None
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
     d_init = [_check_init(n, f, n_pairs, H, W, dev) for n, f in (("init_flow", init_flow), ("init_flow_bw", init_flow_bw))]
-    index = _index(dev)
     flow_fw, warp_fw, d_flow_fw, d_warp_fw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
     flow_bw, warp_bw, d_flow_bw, d_warp_bw = _outputs(n_pairs, H, W, C, layout, out_dtype, dev)
-    occ, d_occ = _mask(n_pairs, H, W, dev) if consistency is not None else (None, None)
-    a1, a2 = consistency if consistency is not None else (0.0, 0.0)
-    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    occ, d_occ = _mask(n_pairs, H, W, dev) if alphas[0] else (None, None)
+    head = _head(ts, descs, sequence, n_pairs, levels, params)
+    tail = (ctypes.byref(d_flow_fw), ctypes.byref(d_warp_fw), ctypes.byref(d_flow_bw), ctypes.byref(d_warp_bw), _ref(d_occ),
+            *alphas[1:])
     t = (ctypes.c_double * capi.N_TIMERS)()
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        head = (gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W,
-                C, int(levels), ctypes.byref(params) if params is not None else None)
-        tail = (ctypes.byref(d_flow_fw), ctypes.byref(d_warp_fw), ctypes.byref(d_flow_bw), ctypes.byref(d_warp_bw),
-                ctypes.byref(d_occ) if occ is not None else None, a1, a2, ctypes.c_void_p(stream or None), t)
-        if d_init == [None, None]:
-            what = "papof_flow_batch_tensor_fb"
-            rc = gpu.L.papof_flow_batch_tensor_fb(*head, *tail)
-        else:
-            what = "papof_flow_batch_tensor_fb_init"
-            rc = gpu.L.papof_flow_batch_tensor_fb_init(*head, _ref(d_init[0]), _ref(d_init[1]), *tail)
-    capi._chk(rc, what)
+    if d_init == [None, None]:
+        _launch(dev, "papof_flow_batch_tensor_fb", *head, *tail, timers=t)
+    else:
+        _launch(dev, "papof_flow_batch_tensor_fb_init", *head, _ref(d_init[0]), _ref(d_init[1]), *tail, timers=t)
     return FlowFB(flow_fw, flow_bw, warp_fw, warp_bw, occ.view(torch.bool) if occ is not None else None,
                   capi.format_timing(list(t)))
 
@@ -333,9 +346,9 @@ def flow_pairs_fb(im1, im2, pyramidLevels, *, layout="NCHW", out_dtype=None, con
     consistency = (alpha1, alpha2) on the float64 flows (whatever out_dtype is) -- or None for consistency=None.
     init_flow / init_flow_bw: the initial flows of the forward / backward pairs, as flow_pairs's init_flow (None: zero); each
     direction is flow_pairs(..., init_flow=) on its frames, bit for bit."""
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, out_dtype = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels)
-    return _run_fb(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, solver, init_flow,
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, params = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, solver=solver)
+    return _run_fb(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, params, init_flow,
                    init_flow_bw)
 
 
@@ -344,9 +357,9 @@ def flow_video_fb(frames, pyramidLevels, *, layout="NCHW", out_dtype=None, consi
     """Both directions of the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames in one launch chain -- each
     frame's pyramid and features are built once for both -- and their occlusion mask: flow_pairs_fb on
     (frames[:-1], frames[1:]), with T - 1 pairs (and its init_flow / init_flow_bw)."""
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, out_dtype = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2)
-    return _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, solver, init_flow,
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
+    return _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, init_flow,
                    init_flow_bw)
 
 
@@ -355,34 +368,14 @@ def fb_consistency(flow_fw, flow_bw, alpha1=CONSISTENCY[0], alpha2=CONSISTENCY[1
     HIP device: a torch.bool tensor (B, 2, H, W), True where occluded -- channel 0 forward, 1 backward, as flow_video_fb's
     occlusion, and the same mask for the same float64 flows (include/papof.h: papof_fb_check_tensor).  Enqueued on the
     current stream; returns without waiting."""
-    torch = _torch()
-    a1, a2 = _alphas((alpha1, alpha2))
-    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
-    for n, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
-        if not isinstance(f, torch.Tensor):
-            raise TypeError("%s must be a torch.Tensor, got %s" % (n, type(f).__name__))
-        if f.dim() != 4 or f.shape[1] != 2 or min(f.shape) < 1:
-            raise ValueError("%s must be (B, 2, H, W) with B, H, W >= 1, got shape %s" % (n, tuple(f.shape)))
-        if f.dtype not in codes:
-            raise TypeError("%s must be float32 or float64, got %s" % (n, f.dtype))
-    if flow_fw.shape != flow_bw.shape:
-        raise ValueError("flow_fw %s and flow_bw %s differ in shape" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
-    if flow_fw.device != flow_bw.device:
-        raise ValueError("flow_fw is on %s, flow_bw on %s: both must be on one device" % (flow_fw.device, flow_bw.device))
-    if not _on_gpu(flow_fw):
-        raise ValueError("flows must be on a HIP device (cuda:N), got %s" % flow_fw.device)
+    _, a1, a2 = _alphas((alpha1, alpha2))
+    codes = _check_flows(flow_fw, flow_bw)
     B, _, H, W = (int(x) for x in flow_fw.shape)
-    dev = flow_fw.device
-    index = _index(dev)
-    d = [_struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), codes[f.dtype]) for f in (flow_fw, flow_bw)]
-    occ, d_occ = _mask(B, H, W, dev)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_fb_check_tensor(gpu.h, B, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), a1, a2, ctypes.byref(d_occ),
-                                         ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_fb_check_tensor")
-    return occ.view(torch.bool)
+    d = [_flow_struct(f, c) for f, c in zip((flow_fw, flow_bw), codes)]
+    occ, d_occ = _mask(B, H, W, flow_fw.device)
+    _launch(flow_fw.device, "papof_fb_check_tensor", B, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), a1, a2,
+            ctypes.byref(d_occ))
+    return occ.view(_torch().bool)
 
 
 def _check_queries(queries, dev):
@@ -401,24 +394,50 @@ def _check_queries(queries, dev):
     return queries
 
 
-def _check_flows(flow_fw, flow_bw):
-    """every argument error of a (T - 1, 2, H, W) flow pair, before anything is launched: their dtype codes"""
+def _check_flow(name, f):
+    """a (B, 2, H, W) float32 / float64 flow tensor with B, H, W >= 1: its dtype code -- TypeError / ValueError otherwise"""
     torch = _torch()
     codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
-    for n, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
-        if not isinstance(f, torch.Tensor):
-            raise TypeError("%s must be a torch.Tensor, got %s" % (n, type(f).__name__))
-        if f.dim() != 4 or f.shape[1] != 2 or min(f.shape) < 1:
-            raise ValueError("%s must be (T - 1, 2, H, W) with T - 1, H, W >= 1, got shape %s" % (n, tuple(f.shape)))
-        if f.dtype not in codes:
-            raise TypeError("%s must be float32 or float64, got %s" % (n, f.dtype))
+    if not isinstance(f, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(f).__name__))
+    if f.dim() != 4 or f.shape[1] != 2 or min(f.shape) < 1:
+        raise ValueError("%s must be (B, 2, H, W) with B, H, W >= 1, got shape %s" % (name, tuple(f.shape)))
+    if f.dtype not in codes:
+        raise TypeError("%s must be float32 or float64, got %s" % (name, f.dtype))
+    return codes[f.dtype]
+
+
+def _check_flows(flow_fw, flow_bw, shape=None, dev=None):
+    """every argument error of a flow pair on one HIP device -- of `shape` on the frames' device `dev` when given -- before
+    anything is launched: their dtype codes"""
+    codes = tuple(_check_flow(n, f) for n, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)))
     if flow_fw.shape != flow_bw.shape:
         raise ValueError("flow_fw %s and flow_bw %s differ in shape" % (tuple(flow_fw.shape), tuple(flow_bw.shape)))
     if flow_fw.device != flow_bw.device:
         raise ValueError("flow_fw is on %s, flow_bw on %s: both must be on one device" % (flow_fw.device, flow_bw.device))
     if not _on_gpu(flow_fw):
         raise ValueError("flows must be on a HIP device (cuda:N), got %s" % flow_fw.device)
-    return codes[flow_fw.dtype], codes[flow_bw.dtype]
+    if shape is not None and tuple(flow_fw.shape) != shape:
+        raise ValueError("the flows must be %s for these frames, got %s" % (shape, tuple(flow_fw.shape)))
+    if dev is not None and flow_fw.device != dev:
+        raise ValueError("the flows are on %s, the frames on %s: all must be on one device" % (flow_fw.device, dev))
+    return codes
+
+
+def _check_occlusion(occlusion, shape, dev):
+    """None, or a bool / uint8 occlusion mask of `shape` on `dev`: the mask as uint8 -- TypeError / ValueError otherwise"""
+    if occlusion is None:
+        return None
+    torch = _torch()
+    if not isinstance(occlusion, torch.Tensor):
+        raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
+    if occlusion.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
+    if tuple(occlusion.shape) != shape:
+        raise ValueError("occlusion must be (B, 2, H, W) = %s, got %s" % (shape, tuple(occlusion.shape)))
+    if occlusion.device != dev:
+        raise ValueError("occlusion is on %s, the flows on %s: all must be on one device" % (occlusion.device, dev))
+    return occlusion.view(torch.uint8)
 
 
 def _track(flow_fw, flow_bw, codes, queries, alphas):
@@ -426,8 +445,7 @@ def _track(flow_fw, flow_bw, codes, queries, alphas):
     T, H, W = int(flow_fw.shape[0]) + 1, int(flow_fw.shape[2]), int(flow_fw.shape[3])
     N = int(queries.shape[0]) if queries is not None else H * W
     dev = flow_fw.device
-    index = _index(dev)
-    d = [_struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), c) for f, c in zip((flow_fw, flow_bw), codes)]
+    d = [_flow_struct(f, c) for f, c in zip((flow_fw, flow_bw), codes)]
     d_q = None
     if queries is not None:
         q_code = capi.DTYPE_F32 if queries.dtype == torch.float32 else capi.DTYPE_F64
@@ -436,14 +454,8 @@ def _track(flow_fw, flow_bw, codes, queries, alphas):
     vis = torch.empty((T, N), dtype=torch.uint8, device=dev)
     d_tr = _struct(tracks, (tracks.stride(0), tracks.stride(1), 0, tracks.stride(2)), capi.DTYPE_F64)
     d_vis = _struct(vis, (vis.stride(0), vis.stride(1), 0, 0), capi.DTYPE_U8)
-    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_track_tensor(gpu.h, T, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), N if d_q is not None else 0,
-                                      ctypes.byref(d_q) if d_q is not None else None, 0 if alphas is None else 1, a1, a2,
-                                      ctypes.byref(d_tr), ctypes.byref(d_vis), ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_track_tensor")
+    _launch(dev, "papof_track_tensor", T, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), N if d_q is not None else 0, _ref(d_q),
+            *alphas, ctypes.byref(d_tr), ctypes.byref(d_vis))
     return Tracks(tracks, vis.view(torch.bool))
 
 
@@ -462,7 +474,7 @@ def track_points(flow_fw, flow_bw, queries=None, *, consistency=CONSISTENCY):
     A long video in chunks: let the chunks overlap by one frame, and pass the last frame's positions as t0 = 0 queries of
     the next chunk -- torch.cat([torch.zeros(N, 1, dtype=torch.float64, device=dev), tracks[-1]], 1): a point lost so far is
     NaN there, an invalid query, and stays lost."""
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     codes = _check_flows(flow_fw, flow_bw)
     queries = _check_queries(queries, flow_fw.device)
     return _track(flow_fw, flow_bw, codes, queries, alphas)
@@ -474,10 +486,10 @@ def track_video(frames, pyramidLevels, queries=None, *, layout="NCHW", consisten
     them.  Returns TrackVideo(tracks (T, N, 2), visible (T, N), flow_fw, flow_bw (T - 1, 2, H, W), timing of the flow call).
     Every argument error raises before anything is launched; the flows are complete on return, the tracks are enqueued on
     the current stream behind them."""
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, out_dtype = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     queries = _check_queries(queries, ts[0].device)
-    fb = _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, None, solver)
+    fb = _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, _alphas(None), params)
     tr = _track(fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), queries, alphas)
     return TrackVideo(tr.tracks, tr.visible, fb.flow_fw, fb.flow_bw, fb.timing)
 
@@ -514,26 +526,11 @@ def _out_code(out_dtype):
     return codes[out_dtype]
 
 
-def _check_interp_flows(flow_fw, flow_bw, occlusion, B, H, W, dev):
-    """the flows (B, 2, H, W) and the optional mask of interpolate on `dev`: (dtype codes of the flows, the mask as uint8)"""
-    torch = _torch()
-    codes = _check_flows(flow_fw, flow_bw)
-    if tuple(flow_fw.shape) != (B, 2, H, W):
-        raise ValueError("the flows must be (B, 2, H, W) = %s for these frames, got %s" % ((B, 2, H, W),
-                                                                                         tuple(flow_fw.shape)))
-    if flow_fw.device != dev:
-        raise ValueError("the flows are on %s, the frames on %s: all must be on one device" % (flow_fw.device, dev))
-    if occlusion is not None:
-        if not isinstance(occlusion, torch.Tensor):
-            raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
-        if occlusion.dtype not in (torch.bool, torch.uint8):
-            raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
-        if tuple(occlusion.shape) != (B, 2, H, W):
-            raise ValueError("occlusion must be (B, 2, H, W) = %s, got %s" % ((B, 2, H, W), tuple(occlusion.shape)))
-        if occlusion.device != dev:
-            raise ValueError("occlusion is on %s, the frames on %s: all must be on one device" % (occlusion.device, dev))
-        occlusion = occlusion.view(torch.uint8)
-    return codes, occlusion
+def _out_dtype(out_dtype, default):
+    """out_dtype, `default` for None -- TypeError for a dtype the kernels do not store"""
+    out_dtype = default if out_dtype is None else out_dtype
+    _out_code(out_dtype)
+    return out_dtype
 
 
 def _flow_struct(f, code):
@@ -542,19 +539,12 @@ def _flow_struct(f, code):
 
 def _interp(d_in, sequence, n_pairs, H, W, C, flows, codes, occlusion, times, out, d_out, time_stride, dev):
     """papof_interp_tensor on the current stream of `dev`, writing through d_out"""
-    torch = _torch()
-    index = _index(dev)
     d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
     d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
     ts = (ctypes.c_double * len(times))(*times)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_interp_tensor(gpu.h, n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
-                                       None if sequence else ctypes.byref(d_in[1]), H, W, C, ctypes.byref(d_f[0]),
-                                       ctypes.byref(d_f[1]), ctypes.byref(d_occ) if d_occ is not None else None, len(times),
-                                       ts, ctypes.byref(d_out), time_stride, ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_interp_tensor")
+    _launch(dev, "papof_interp_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+            None if sequence else ctypes.byref(d_in[1]), H, W, C, ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), _ref(d_occ),
+            len(times), ts, ctypes.byref(d_out), time_stride)
     return out
 
 
@@ -582,14 +572,12 @@ def interpolate(im1, im2, flow_fw, flow_bw, times, *, occlusion=None, layout="NC
     F_t->1 = (1 - t)^2 F01 - (1 - t) t F10 with the flows at p, and blends the two with weights 1 - t and t, each lowered
     where the mask says its sample is hidden in the other frame; include/papof.h (papof_interp_tensor) states it exactly.
     Enqueued on the current stream; returns without waiting."""
-    torch = _torch()
-    ts, descs, _ = _check([("im1", im1), ("im2", im2)], layout, None, 1)
+    ts, descs, _, _ = _check([("im1", im1), ("im2", im2)], layout, None, 1)
     times = _times(times)
-    if out_dtype is None:
-        out_dtype = torch.promote_types(ts[0].dtype, ts[1].dtype)
-    _out_code(out_dtype)
+    out_dtype = _out_dtype(out_dtype, _torch().promote_types(ts[0].dtype, ts[1].dtype))
     (B, H, W, C), _, _ = descs[0]
-    codes, occ = _check_interp_flows(flow_fw, flow_bw, occlusion, B, H, W, ts[0].device)
+    codes = _check_flows(flow_fw, flow_bw, (B, 2, H, W), ts[0].device)
+    occ = _check_occlusion(occlusion, (B, 2, H, W), ts[0].device)
     out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
     return _interp(d_in, False, B, H, W, C, (flow_fw, flow_bw), codes, occ, times, out, d_out, tstride, ts[0].device)
@@ -602,14 +590,12 @@ def interpolate_pairs(im1, im2, pyramidLevels, times, *, layout="NCHW", consiste
     error raises before anything is launched; the flows are complete on return, the frames are enqueued on the current
     stream behind them."""
     torch = _torch()
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, _ = _check([("im1", im1), ("im2", im2)], layout, None, pyramidLevels)
+    alphas = _alphas(consistency)
+    ts, descs, _, params = _check([("im1", im1), ("im2", im2)], layout, None, pyramidLevels, solver=solver)
     times = _times(times)
-    if out_dtype is None:
-        out_dtype = torch.promote_types(ts[0].dtype, ts[1].dtype)
-    _out_code(out_dtype)
+    out_dtype = _out_dtype(out_dtype, torch.promote_types(ts[0].dtype, ts[1].dtype))
     (B, H, W, C), _, _ = descs[0]
-    fb = _run_fb(ts, descs, False, B, layout, torch.float64, pyramidLevels, alphas, solver)
+    fb = _run_fb(ts, descs, False, B, layout, torch.float64, pyramidLevels, alphas, params)
     occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
     out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
@@ -642,21 +628,17 @@ def interpolate_video(frames, pyramidLevels, factor=2, *, layout="NCHW", consist
     differs), and the frames between are written by the kernel straight into the video.  Every argument error raises
     before anything is launched; the flows are complete on return, the video is enqueued on the current stream."""
     torch = _torch()
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, _ = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    alphas = _alphas(consistency)
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     if isinstance(factor, bool) or not isinstance(factor, int) or factor < 2:
         raise ValueError("factor must be an integer >= 2, got %r" % (factor,))
-    if out_dtype is None:
-        out_dtype = ts[0].dtype
-    code = _out_code(out_dtype)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
     (T, H, W, C), _, _ = descs[0]
     dev = ts[0].device
-    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, alphas, solver)
-    n = (T - 1) * factor + 1
-    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
-    video = torch.empty(shape, dtype=out_dtype, device=dev)
+    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, alphas, params)
+    video, _ = _new_frames((T - 1) * factor + 1, H, W, C, layout, out_dtype, dev)
     video[::factor].copy_(_converted(ts[0], out_dtype))
-    vs = descriptor(video, layout)[1]
+    _, vs, code = descriptor(video, layout)
     d_out = _struct(video[1], (factor * vs[0],) + vs[1:], code)
     occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
     times = [j / factor for j in range(1, factor)]
@@ -679,37 +661,10 @@ def _check_fit(model, iters, scale):
     return MODELS[model], iters, float(scale)
 
 
-def _check_motion_flow(flow, occlusion):
-    """flow (B, 2, H, W) float32 / float64 on a HIP device and its optional (B, 2, H, W) bool / uint8 mask: (flow's dtype code,
-    the mask as uint8 or None)"""
-    torch = _torch()
-    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
-    if not isinstance(flow, torch.Tensor):
-        raise TypeError("flow must be a torch.Tensor, got %s" % type(flow).__name__)
-    if flow.dim() != 4 or flow.shape[1] != 2 or min(flow.shape) < 1:
-        raise ValueError("flow must be (B, 2, H, W) with B, H, W >= 1, got shape %s" % (tuple(flow.shape),))
-    if flow.dtype not in codes:
-        raise TypeError("flow must be float32 or float64, got %s" % flow.dtype)
-    if occlusion is not None:
-        if not isinstance(occlusion, torch.Tensor):
-            raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
-        if occlusion.dtype not in (torch.bool, torch.uint8):
-            raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
-        if occlusion.shape != flow.shape:
-            raise ValueError("occlusion must be (B, 2, H, W) = %s, got %s" % (tuple(flow.shape), tuple(occlusion.shape)))
-        if occlusion.device != flow.device:
-            raise ValueError("occlusion is on %s, the flow on %s: both must be on one device" % (occlusion.device, flow.device))
-        occlusion = occlusion.view(torch.uint8)
-    if not _on_gpu(flow):
-        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
-    return codes[flow.dtype], occlusion
-
-
 def _motion_fit(flow, code, occlusion, model, iters, scale):
     torch = _torch()
     B, _, H, W = (int(x) for x in flow.shape)
     dev = flow.device
-    index = _index(dev)
     motion = torch.empty((B, 2, 3), dtype=torch.float64, device=dev)
     ok = torch.empty((B,), dtype=torch.uint8, device=dev)
     support = torch.empty((B,), dtype=torch.float64, device=dev)
@@ -718,19 +673,9 @@ def _motion_fit(flow, code, occlusion, model, iters, scale):
     d_m = _struct(motion, (motion.stride(0), motion.stride(1), motion.stride(2), 0), capi.DTYPE_F64)
     d_ok = _struct(ok, (ok.stride(0), 0, 0, 0), capi.DTYPE_U8)
     d_s = _struct(support, (support.stride(0), 0, 0, 0), capi.DTYPE_F64)
-    gpu, lock = _handle(index)
-    nbytes = gpu.L.papof_motion_workspace(B, H, W)
-    if nbytes < 0:
-        raise ValueError("a %d x %d flow is too large for global_motion" % (H, W))
-    with lock, torch.cuda.device(index):
-        # the workspace comes from PyTorch's allocator on the current stream: it is reused only behind the work queued here
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_motion_fit_tensor(gpu.h, B, H, W, ctypes.byref(d_flow), _ref(d_occ), model, iters, scale,
-                                           ctypes.byref(d_m), ctypes.byref(d_ok), ctypes.byref(d_s),
-                                           ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream or None))
-        del ws
-    capi._chk(rc, "papof_motion_fit_tensor")
+    _launch(dev, "papof_motion_fit_tensor", B, H, W, ctypes.byref(d_flow), _ref(d_occ), model, iters, scale, ctypes.byref(d_m),
+            ctypes.byref(d_ok), ctypes.byref(d_s),
+            workspace=("papof_motion_workspace", (B, H, W), "a %d x %d flow is too large for global_motion" % (H, W)))
     return Motion(motion, ok.view(torch.bool), support)
 
 
@@ -745,7 +690,10 @@ def global_motion(flow, *, occlusion=None, model="affine", iters=5, scale=1.0):
     the last iteration's sum of weights over H * W).  include/papof.h (papof_motion_fit_tensor) states the rule exactly; the
     results are bitwise reproducible.  Enqueued on the current stream; returns without waiting."""
     model, iters, scale = _check_fit(model, iters, scale)
-    code, occ = _check_motion_flow(flow, occlusion)
+    code = _check_flow("flow", flow)
+    occ = _check_occlusion(occlusion, tuple(flow.shape), flow.device)
+    if not _on_gpu(flow):
+        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
     return _motion_fit(flow, code, occ, model, iters, scale)
 
 
@@ -767,20 +715,13 @@ def _warp(ts, descs, matrices, m_code, layout, out_dtype):
     torch = _torch()
     (B, H, W, C), _, _ = descs[0]
     dev = ts[0].device
-    index = _index(dev)
-    shape = (B, C, H, W) if layout == "NCHW" else (B, H, W, C)
-    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    out, d_out = _new_frames(B, H, W, C, layout, out_dtype, dev)
     valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     d_in = _struct(ts[0], descs[0][1], descs[0][2])
     d_mat = _struct(matrices, (matrices.stride(0), matrices.stride(1), matrices.stride(2), 0), m_code)
-    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
     d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_warp_affine_tensor(gpu.h, B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_out),
-                                            ctypes.byref(d_valid), ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_warp_affine_tensor")
+    _launch(dev, "papof_warp_affine_tensor", B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_out),
+            ctypes.byref(d_valid))
     return out, valid.view(torch.bool)
 
 
@@ -792,9 +733,8 @@ def warp_affine(frames, matrices, *, layout="NCHW", out_dtype=None):
     clamp(rint(255 x), 0, 255), float32 or float64; by default the frames' dtype --, valid (B, H, W) bool: True where the
     point lay inside).  include/papof.h (papof_warp_affine_tensor) states it exactly.  Enqueued on the current stream;
     returns without waiting."""
-    ts, descs, _ = _check([("frames", frames)], layout, None, 1)
-    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
-    _out_code(out_dtype)
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
     m_code = _check_matrices(matrices, descs[0][0][0], ts[0].device)
     return _warp(ts, descs, matrices, m_code, layout, out_dtype)
 
@@ -873,16 +813,12 @@ def stabilize_video(frames, pyramidLevels, *, layout="NCHW", model="similarity",
     default the frames'), valid (T, H, W) bool, transforms (T, 2, 3) float64, motion (T - 1, 2, 3) float64, ok (T - 1,) bool,
     flow (T - 1, 2, H, W) float64, timing of the flow call).  Every argument error raises before anything is launched; the
     video is enqueued on the current stream."""
-    ts, descs, _ = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2)
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     code, iters, scale = _check_fit(model, iters, scale)
     (T, H, W, C), _, _ = descs[0]
     _check_path(radius, crop, (H, W))
-    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
-    _out_code(out_dtype)
-    if solver:
-        capi.default_params(**solver)  # an unknown solver keyword raises here
-    torch = _torch()
-    flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, solver)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
     m = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
     M = stabilizing_transforms(m, radius, crop, size=(H, W))
     video, valid = _warp(ts, descs, M, capi.DTYPE_F64, layout, out_dtype)
@@ -906,37 +842,27 @@ def _check_filter(radius, sigma):
     return radius, float(sigma)
 
 
-def _check_video(frames, layout, levels, out_dtype):
-    """the frames of temporal_filter / denoise_video: (ts, descs, out_dtype) -- every error before anything is launched"""
-    ts, descs, _ = _check([("frames", frames)], layout, None, levels, min_frames=2)
+def _check_video(frames, layout, levels, out_dtype, name="frames", min_frames=2, solver=None):
+    """the frames of the video calls, 1 .. MAX_CHANNELS channels: (ts, descs, out_dtype -- by default the frames' --, the
+    solver's params) -- every error before anything is launched"""
+    ts, descs, _, params = _check([(name, frames)], layout, None, levels, min_frames=min_frames, solver=solver)
     C = descs[0][0][3]
     if C > MAX_CHANNELS:
-        raise ValueError("frames must have 1 .. %d channels, got %d (layout %s)" % (MAX_CHANNELS, C, layout))
-    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
-    _out_code(out_dtype)
-    return ts, descs, out_dtype
+        raise ValueError("%s must have 1 .. %d channels, got %d (layout %s)" % (name, MAX_CHANNELS, C, layout))
+    return ts, descs, _out_dtype(out_dtype, ts[0].dtype), params
 
 
 def _filter(ts, descs, flows, codes, radius, sigma, alphas, layout, out_dtype):
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
-    index = _index(dev)
-    shape = (T, C, H, W) if layout == "NCHW" else (T, H, W, C)
-    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    out, d_out = _new_frames(T, H, W, C, layout, out_dtype, dev)
     support = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
     d_in = _struct(ts[0], strides, code)
     d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
-    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
     d_sup = _struct(support, (support.stride(0), support.stride(1), support.stride(2), 1), capi.DTYPE_U8)
-    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_temporal_filter_tensor(gpu.h, T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]),
-                                                ctypes.byref(d_f[1]), radius, sigma, 0 if alphas is None else 1, a1, a2,
-                                                ctypes.byref(d_out), ctypes.byref(d_sup), ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_temporal_filter_tensor")
+    _launch(dev, "papof_temporal_filter_tensor", T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]), ctypes.byref(d_f[1]),
+            radius, sigma, *alphas, ctypes.byref(d_out), ctypes.byref(d_sup))
     return Filtered(out, support)
 
 
@@ -958,16 +884,11 @@ def temporal_filter(frames, flow_fw, flow_bw, *, radius=2, sigma=0.15, consisten
     Returns Filtered(video in `layout` and out_dtype -- uint8 as clamp(rint(255 x), 0, 255), float32 or float64; by default
     the frames' dtype --, support (T, H, W) uint8: the number of neighbours that entered).  include/papof.h
     (papof_temporal_filter_tensor) states the rule exactly.  Enqueued on the current stream; returns without waiting."""
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     radius, sigma = _check_filter(radius, sigma)
-    ts, descs, out_dtype = _check_video(frames, layout, 1, out_dtype)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype)
     (T, H, W, C), _, _ = descs[0]
-    codes = _check_flows(flow_fw, flow_bw)
-    if tuple(flow_fw.shape) != (T - 1, 2, H, W):
-        raise ValueError("the flows must be (T - 1, 2, H, W) = %s for these frames, got %s" % ((T - 1, 2, H, W),
-                                                                                              tuple(flow_fw.shape)))
-    if flow_fw.device != ts[0].device:
-        raise ValueError("the flows are on %s, the frames on %s: all must be on one device" % (flow_fw.device, ts[0].device))
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
     return _filter(ts, descs, (flow_fw, flow_bw), codes, radius, sigma, alphas, layout, out_dtype)
 
 
@@ -979,13 +900,11 @@ def denoise_video(frames, pyramidLevels, *, radius=2, sigma=0.15, consistency=CO
     flow_bw (T - 1, 2, H, W) float64, timing of the flow call).  Every argument error raises before anything is launched;
     the flows are complete on return, the video is enqueued on the current stream behind them."""
     torch = _torch()
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     radius, sigma = _check_filter(radius, sigma)
-    ts, descs, out_dtype = _check_video(frames, layout, pyramidLevels, out_dtype)
-    if solver:
-        capi.default_params(**solver)  # an unknown solver keyword raises here
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
     T = descs[0][0][0]
-    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, None, solver)
+    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, _alphas(None), params)
     f = _filter(ts, descs, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), radius, sigma, alphas, layout,
                 out_dtype)
     return Denoised(f.video, f.support, fb.flow_fw, fb.flow_bw, fb.timing)
@@ -1023,35 +942,14 @@ def _mask_struct(m):
 
 def _fill(t, desc, mask, relax, layout, out_dtype):
     """papof_fill_holes_tensor of the 4-D tensor t (its descriptor `desc` in `layout`) under the uint8 mask: a new tensor"""
-    torch = _torch()
     (n, H, W, C), strides, code = desc
-    dev = t.device
-    index = _index(dev)
-    shape = (n, C, H, W) if layout == "NCHW" else (n, H, W, C)
-    out = torch.empty(shape, dtype=out_dtype, device=dev)
+    out, d_out = _new_frames(n, H, W, C, layout, out_dtype, t.device)
     d_in = _struct(t, strides, code)
     d_mask = _mask_struct(mask)
-    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
-    gpu, lock = _handle(index)
-    nbytes = gpu.L.papof_fill_workspace(n, H, W, C)
-    if nbytes < 0:
-        raise ValueError("%d frames of %d x %d x %d are too large for fill_holes" % (n, H, W, C))
-    with lock, torch.cuda.device(index):
-        # the workspace comes from PyTorch's allocator on the current stream: it is reused only behind the work queued here
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_fill_holes_tensor(gpu.h, n, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mask), relax,
-                                           ctypes.byref(d_out), ctypes.c_void_p(ws.data_ptr()), nbytes,
-                                           ctypes.c_void_p(stream or None))
-        del ws
-    capi._chk(rc, "papof_fill_holes_tensor")
+    _launch(t.device, "papof_fill_holes_tensor", n, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mask), relax,
+            ctypes.byref(d_out), workspace=("papof_fill_workspace", (n, H, W, C),
+                                            "%d frames of %d x %d x %d are too large for fill_holes" % (n, H, W, C)))
     return out
-
-
-def _check_channels(descs, layout):
-    C = descs[0][0][3]
-    if C > MAX_CHANNELS:
-        raise ValueError("frames must have 1 .. %d channels, got %d (layout %s)" % (MAX_CHANNELS, C, layout))
 
 
 def fill_holes(x, mask, *, layout="NCHW", relax=RELAX, out_dtype=None):
@@ -1066,10 +964,7 @@ def fill_holes(x, mask, *, layout="NCHW", relax=RELAX, out_dtype=None):
     states the rule exactly.  The workspace comes from PyTorch's allocator; enqueued on the current stream, returns without
     waiting."""
     relax = _check_relax(relax)
-    ts, descs, _ = _check([("x", x)], layout, None, 1)
-    _check_channels(descs, layout)
-    out_dtype = ts[0].dtype if out_dtype is None else out_dtype
-    _out_code(out_dtype)
+    ts, descs, out_dtype, _ = _check_video(x, layout, 1, out_dtype, name="x", min_frames=1)
     n, H, W, _ = descs[0][0]
     m = _check_masks("mask", mask, n, H, W, ts[0].device)
     return _fill(ts[0], descs[0], m, relax, layout, out_dtype)
@@ -1078,15 +973,6 @@ def fill_holes(x, mask, *, layout="NCHW", relax=RELAX, out_dtype=None):
 def _check_video_masks(ts, descs, masks):
     (T, H, W, _), _, _ = descs[0]
     return _check_masks("masks", masks, T, H, W, ts[0].device)
-
-
-def _check_video_flows(flow_fw, flow_bw, T, H, W, dev):
-    codes = _check_flows(flow_fw, flow_bw)
-    if tuple(flow_fw.shape) != (T - 1, 2, H, W):
-        raise ValueError("the flows must be (T - 1, 2, H, W) = %s, got %s" % ((T - 1, 2, H, W), tuple(flow_fw.shape)))
-    if flow_fw.device != dev:
-        raise ValueError("the flows are on %s, the masks on %s: all must be on one device" % (flow_fw.device, dev))
-    return codes
 
 
 def _complete(flows, m, relax):
@@ -1117,26 +1003,16 @@ def _check_radius(radius, T):
 
 
 def _propagate(ts, descs, m, flows, codes, radius, alphas, layout, out_dtype):
-    torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
-    index = _index(dev)
-    shape = (T, C, H, W) if layout == "NCHW" else (T, H, W, C)
-    out = torch.empty(shape, dtype=out_dtype, device=dev)
-    status = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    out, d_out = _new_frames(T, H, W, C, layout, out_dtype, dev)
+    status = _torch().empty((T, H, W), dtype=_torch().uint8, device=dev)
     d_in = _struct(ts[0], strides, code)
     d_m = _mask_struct(m)
     d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
-    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
     d_st = _mask_struct(status)
-    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
-    gpu, lock = _handle(index)
-    with lock, torch.cuda.device(index):
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_propagate_tensor(gpu.h, T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_m), ctypes.byref(d_f[0]),
-                                          ctypes.byref(d_f[1]), radius, 0 if alphas is None else 1, a1, a2,
-                                          ctypes.byref(d_out), ctypes.byref(d_st), ctypes.c_void_p(stream or None))
-    capi._chk(rc, "papof_propagate_tensor")
+    _launch(dev, "papof_propagate_tensor", T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_m), ctypes.byref(d_f[0]),
+            ctypes.byref(d_f[1]), radius, *alphas, ctypes.byref(d_out), ctypes.byref(d_st))
     return Propagated(out, status)
 
 
@@ -1156,12 +1032,12 @@ def propagate(frames, masks, flow_fw, flow_bw, *, radius=None, consistency=None,
     (tests/test_inpaint_cpu.py): inside completed flows the check only shortens the chains -- 34 % of the hole pixels found
     a candidate with it, 99.9 % without -- and inpaint_video's PSNR over the holes was 21.4 dB with it, 29.0 dB without,
     against 17.9 dB for fill_holes alone; Jacobi sweeps lowered it (25.4 dB with 8 per level)."""
-    alphas = _alphas(consistency) if consistency is not None else None
-    ts, descs, out_dtype = _check_video(frames, layout, 1, out_dtype)
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype)
     (T, H, W, _), _, _ = descs[0]
     radius = _check_radius(radius, T)
     m = _check_video_masks(ts, descs, masks)
-    codes = _check_video_flows(flow_fw, flow_bw, T, H, W, ts[0].device)
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
     return _propagate(ts, descs, m, (flow_fw, flow_bw), codes, radius, alphas, layout, out_dtype)
 
 
@@ -1176,26 +1052,30 @@ def inpaint_video(frames, masks, pyramidLevels, *, flows=None, radius=None, rela
     the frames' dtype: their bytes), status (T, H, W) uint8: 0 kept, 1 filled along the flows, 2 filled spatially).  Every
     argument error raises before anything is launched; the video is enqueued on the current stream."""
     torch = _torch()
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     relax = _check_relax(relax)
-    ts, descs, out_dtype = _check_video(frames, layout, pyramidLevels, out_dtype)
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
     (T, H, W, _), _, _ = descs[0]
     radius = _check_radius(radius, T)
     m = _check_video_masks(ts, descs, masks)
-    if flows is not None:
-        if not isinstance(flows, (tuple, list)) or len(flows) != 2:
-            raise TypeError("flows must be None or a pair (flow_fw, flow_bw), got %s" % type(flows).__name__)
-        flow_fw, flow_bw = flows
-        codes = _check_video_flows(flow_fw, flow_bw, T, H, W, ts[0].device)
-    if solver:
-        capi.default_params(**solver)  # an unknown solver keyword raises here
-    if flows is None:
-        fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, None, solver)
-        flow_fw, flow_bw, codes = fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64)
+    flow_fw, flow_bw, codes, _ = _given_or_run_fb(flows, ts, descs, layout, pyramidLevels, params)
     cf = _complete((flow_fw, flow_bw), m, relax)
     p = _propagate(ts, descs, m, cf, codes, radius, alphas, layout, torch.float64)
     video = _fill(p.video, descriptor(p.video, layout), (p.status == 2).view(torch.uint8), relax, layout, out_dtype)
     return Inpainted(video, p.status)
+
+
+def _given_or_run_fb(flows, ts, descs, layout, levels, params):
+    """the flows of the video ts[0]: flows = (flow_fw, flow_bw) checked against it -- the last argument check of its caller --
+    or, for None, flow_video_fb's float64 flows without a mask.  Returns (flow_fw, flow_bw, their dtype codes, the timing of
+    the flow call or None)."""
+    (T, H, W, _), _, _ = descs[0]
+    if flows is not None:
+        if not isinstance(flows, (tuple, list)) or len(flows) != 2:
+            raise TypeError("flows must be None or a pair (flow_fw, flow_bw), got %s" % type(flows).__name__)
+        return (*flows, _check_flows(*flows, (T - 1, 2, H, W), ts[0].device), None)
+    fb = _run_fb(ts, descs, True, T - 1, layout, _torch().float64, levels, _alphas(None), params)
+    return fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), fb.timing
 
 
 MAX_ITERS = 65536  # include/papof.h: papof_temporal_consistency_tensor
@@ -1229,9 +1109,7 @@ def _check_processed(ts, descs, processed, layout, out_dtype):
         raise ValueError("processed must have 1 .. %d channels, got %d (layout %s)" % (MAX_CHANNELS, d[0][3], layout))
     if p.device != ts[0].device:
         raise ValueError("processed is on %s, the frames on %s: all must be on one device" % (p.device, ts[0].device))
-    out_dtype = p.dtype if out_dtype is None else out_dtype
-    _out_code(out_dtype)
-    return p, d, out_dtype
+    return p, d, _out_dtype(out_dtype, p.dtype)
 
 
 def _check_first(first, layout, H, W, C, dev):
@@ -1251,31 +1129,16 @@ def _check_first(first, layout, H, W, C, dev):
 
 
 def _consistency(ts, descs, p, d_p, flows, codes, d_first, lam, sigma, iters, alphas, layout, out_dtype):
-    torch = _torch()
     (T, H, W, CI), strides, code = descs[0]
     CP = d_p[0][3]
-    dev = ts[0].device
-    index = _index(dev)
-    out = torch.empty((T, CP, H, W) if layout == "NCHW" else (T, H, W, CP), dtype=out_dtype, device=dev)
+    out, d_out = _new_frames(T, H, W, CP, layout, out_dtype, ts[0].device)
     d_in = _struct(ts[0], strides, code)
     d_pr = _struct(p, d_p[1], d_p[2])
     d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
-    d_out = _struct(out, descriptor(out, layout)[1], _out_code(out_dtype))
-    a1, a2 = alphas if alphas is not None else (0.0, 0.0)
-    gpu, lock = _handle(index)
-    nbytes = gpu.L.papof_consistency_workspace(H, W, CP)
-    if nbytes < 0:
-        raise ValueError("frames of %d x %d x %d are too large for temporal_consistency" % (H, W, CP))
-    with lock, torch.cuda.device(index):
-        # the workspace comes from PyTorch's allocator on the current stream: it is reused only behind the work queued here
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(index).cuda_stream
-        rc = gpu.L.papof_temporal_consistency_tensor(gpu.h, T, H, W, CI, CP, ctypes.byref(d_in), ctypes.byref(d_pr),
-                                                     ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), _ref(d_first), lam, sigma,
-                                                     iters, 0 if alphas is None else 1, a1, a2, ctypes.byref(d_out),
-                                                     ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream or None))
-        del ws
-    capi._chk(rc, "papof_temporal_consistency_tensor")
+    _launch(ts[0].device, "papof_temporal_consistency_tensor", T, H, W, CI, CP, ctypes.byref(d_in), ctypes.byref(d_pr),
+            ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), _ref(d_first), lam, sigma, iters, *alphas, ctypes.byref(d_out),
+            workspace=("papof_consistency_workspace", (H, W, CP),
+                       "frames of %d x %d x %d are too large for temporal_consistency" % (H, W, CP)))
     return out
 
 
@@ -1310,12 +1173,12 @@ def temporal_consistency(frames, processed, flow_fw, flow_bw, *, lam=LAM, sigma=
     A long video in chunks: let the chunks overlap by one frame and pass the previous chunk's last output frame as `first`
     (with the same out_dtype): the previous output is read back from the stored output, so the chunks give the bytes of one
     call."""
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     lam, sigma, iters = _check_solve(lam, sigma, iters)
-    ts, descs, _ = _check_video(frames, layout, 1, None)
+    ts, descs, _, _ = _check_video(frames, layout, 1, None)
     (T, H, W, _), _, _ = descs[0]
     p, d_p, out_dtype = _check_processed(ts, descs, processed, layout, out_dtype)
-    codes = _check_video_flows(flow_fw, flow_bw, T, H, W, ts[0].device)
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
     d_first = _check_first(first, layout, H, W, d_p[0][3], ts[0].device)
     return _consistency(ts, descs, p, d_p, (flow_fw, flow_bw), codes, d_first, lam, sigma, iters, alphas, layout,
                         out_dtype)
@@ -1328,24 +1191,13 @@ def consistent_video(frames, processed, pyramidLevels, *, flows=None, lam=LAM, s
     followed by temporal_consistency (lam, sigma, iters, consistency, first, out_dtype).  Returns Consistent(video, flow_fw,
     flow_bw, timing of the flow call (None with given flows)).  Every argument error raises before anything is launched;
     the video is enqueued on the current stream behind the flows."""
-    torch = _torch()
-    alphas = _alphas(consistency) if consistency is not None else None
+    alphas = _alphas(consistency)
     lam, sigma, iters = _check_solve(lam, sigma, iters)
-    ts, descs, _ = _check_video(frames, layout, pyramidLevels, None)
+    ts, descs, _, params = _check_video(frames, layout, pyramidLevels, None, solver=solver)
     (T, H, W, _), _, _ = descs[0]
     p, d_p, out_dtype = _check_processed(ts, descs, processed, layout, out_dtype)
     d_first = _check_first(first, layout, H, W, d_p[0][3], ts[0].device)
-    timing = None
-    if flows is not None:
-        if not isinstance(flows, (tuple, list)) or len(flows) != 2:
-            raise TypeError("flows must be None or a pair (flow_fw, flow_bw), got %s" % type(flows).__name__)
-        flow_fw, flow_bw = flows
-        codes = _check_video_flows(flow_fw, flow_bw, T, H, W, ts[0].device)
-    if solver:
-        capi.default_params(**solver)  # an unknown solver keyword raises here
-    if flows is None:
-        fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, None, solver)
-        flow_fw, flow_bw, codes, timing = fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), fb.timing
+    flow_fw, flow_bw, codes, timing = _given_or_run_fb(flows, ts, descs, layout, pyramidLevels, params)
     video = _consistency(ts, descs, p, d_p, (flow_fw, flow_bw), codes, d_first, lam, sigma, iters, alphas, layout,
                          out_dtype)
     return Consistent(video, flow_fw, flow_bw, timing)
