@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 115 /* 0.1.15: papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 115 /* 0.1.15: papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -806,6 +806,70 @@ int papof_temporal_consistency_tensor(papof_handle* h, int n_frames, int height,
  * each coarser level's confidences and values, all fp64; -1 for height or width < 1, c_out outside 1 .. 4, or
  * height * width above 2^31 - 1 blocks of 256 pixels. */
 long long papof_consistency_workspace(int height, int width, int c_out);
+
+/* Forward warping (splatting): every source pixel of x is moved along its own flow and deposited, bilinearly, where it lands
+ * (softmax splatting, Niklaus and Liu, CVPR 2020, with the caller's weights) -- how a frame, a flow or a mask is carried to
+ * the frame it points to.  Three steps on `stream`: the accumulator is cleared (hipMemsetAsync), k_splat (splat.hip; one lane
+ * per SOURCE pixel) adds, k_splat_resolve (one lane per TARGET pixel) divides and stores.
+ * x: uint8 (x / 255.0, as the flow's ingest), float32 (widened exactly) or float64, (item, row, column, channel), any
+ * non-negative strides.  flow: float32 / float64, (item, row, column, {vx, vy}).  weight: NULL (1.0 everywhere) or float32 /
+ * float64, (item, row, column, -): stride[3] is not read.  times: n_times finite values (0: the identity deposit; outside
+ * [0, 1]: extrapolation).  bound = 2^k, k an integer in [-20, 20]: values are scaled by 1 / bound (exact) before they are
+ * quantised; 1.0 for frames, for a flow field a bound on |x|.  A value with |x / bound| > 1 is the caller's error: the kernel
+ * clamps x / bound to [-1, 1] (fmin(fmax(., -1), 1): a NaN reads as -1), so that no sum can overflow.
+ * For source pixel (i, j) of item b and time t, in fp64 without fused multiply-adds:
+ *     (u, v) = flow[b, j, i];  w = weight[b, j, i]
+ *     skip the pixel if u, v or w is not finite, or !(w > 0);   w = min(w, 1)
+ *     X = i + t * u;  Y = j + t * v;       skip unless -1 < X < width and -1 < Y < height
+ *     x0 = floor(X); y0 = floor(Y); fx = X - x0; fy = Y - y0
+ *     for (m, n) in (0,0), (0,1), (1,0), (1,1):    target (x0 + n, y0 + m); the tap is dropped if it is outside the image
+ *         b_mn = (m ? fy : 1 - fy) * (n ? fx : 1 - fx);   wb = w * b_mn;   the tap is dropped if wb == 0
+ *         den[target]    += (int64) rint(wb * 4294967296.0)
+ *         num[target, c] += (int64) rint((wb * clamp(x[c] * (1 / bound))) * 4294967296.0)         for each channel c
+ * with rint rounding half to even.  Then, per target pixel:
+ *     coverage = (double) den * 2^-32
+ *     out[c]   = den >= 256 (a coverage of 2^-24) ? ((double) num[c] / (double) den) * bound : fill
+ * A hole is coverage < 2^-24.  out: uint8, float32 or float64, stored as papof_interp_tensor stores; element (item b, time k,
+ * row, column, channel) at out.data + b * stride[0] + k * time_stride + row * stride[1] + column * stride[2] + c * stride[3].
+ * coverage: NULL, or float64 with the axes (item, time, row, column).
+ * The sums are made with 64-bit integer atomic adds: integer addition is associative, so the order of arrival cannot change
+ * a bit and the results are bitwise reproducible.  Every term is at most 2^32 in magnitude and a target receives at most
+ * one tap per source pixel, so with height * width < 2^30 no sum leaves int64.
+ * workspace: device memory, 8-byte aligned, owned by the caller for the duration of the enqueued work -- the accumulator,
+ * int64 planes [item][time][c + 1][row][column] with den's last.  One time of all items takes T1 = 8 n height width (c + 1) bytes;
+ * workspace_bytes must be at least T1, and the call makes the times in groups of min(n_times, 16, workspace_bytes / T1) per
+ * clear-add-resolve round, with the same results for every grouping.  papof_splat_workspace returns
+ * min(n_times, 16, max(1, 2^30 / T1)) * T1: every time at once up to 1 GiB, never less than one time.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL descriptor (weight and coverage aside) or data pointer, a dtype other
+ * than those above, a negative stride, a zero stride of out or coverage or a zero time_stride with n_times > 1, n, height,
+ * width, c or n_times < 1, height * width >= 2^30, c > 2^20, a workspace beyond 2^62 bytes, times NULL or not finite, a
+ * bound that is not such a power of two, a NULL or too small workspace. */
+int papof_splat_tensor(papof_handle* h, int n, int height, int width, int c, const papof_tensor* x, const papof_tensor* flow,
+                       const papof_tensor* weight, int n_times, const double* times, double bound, double fill,
+                       const papof_tensor* out, long long time_stride, const papof_tensor* coverage, void* workspace,
+                       long long workspace_bytes, void* stream);
+
+/* Bytes of the workspace papof_splat_tensor is best given (stated there); -1 where that call refuses the sizes. */
+long long papof_splat_workspace(int n, int n_times, int height, int width, int c);
+
+/* Frame interpolation by splatting: papof_interp_tensor's arguments (frames, flows, mask, times strictly inside (0, 1), out
+ * and time_stride, sequence mode) plus the weights of the two frames' pixels -- weight_fw for the pixels of I0, weight_bw
+ * for those of I1, each NULL (1.0) or float32 / float64 (pair, row, column, -) -- and a workspace.  For each time t, I0 is
+ * accumulated along t * F01 with weight_fw into (num0, den0) and I1 along (1 - t) * F10 with weight_bw into (num1, den1),
+ * both by papof_splat_tensor's rule with bound = 1; then, per target pixel (k_interp_splat), with s = 1 - t:
+ *     den = s * (double) den0 + t * (double) den1;      num[c] = s * (double) num0[c] + t * (double) num1[c]
+ *     out[c] = den >= 256.0 ? num[c] / den : the value papof_interp_tensor's rule gives at this pixel (with the mask, if given)
+ * The occlusion mask affects only that fallback: the pixels hidden in the OTHER frame are the ones that must be splatted.
+ * Unlike papof_interp_tensor, whose flows are read at the output pixel, every pixel moves along its own flow: the result
+ * stays right at motion boundaries.  workspace: as papof_splat_tensor's with 2 n_pairs items (the two accumulators of a
+ * group of times, one after the other): papof_splat_workspace(2 * n_pairs, n_times, height, width, c).
+ * PAPOF_EINVAL, before anything is enqueued: as papof_interp_tensor and papof_splat_tensor. */
+int papof_interp_splat_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                              const papof_tensor* frames2, int height, int width, int c, const papof_tensor* flow_fw,
+                              const papof_tensor* flow_bw, const papof_tensor* weight_fw, const papof_tensor* weight_bw,
+                              const papof_tensor* occlusion, int n_times, const double* times, const papof_tensor* out,
+                              long long time_stride, void* workspace, long long workspace_bytes, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

@@ -65,7 +65,8 @@ SYMBOLS = [
     "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
     "papof_flow_batch_tensor_fb_init", "papof_motion_fit_tensor", "papof_motion_workspace", "papof_warp_affine_tensor",
     "papof_temporal_filter_tensor", "papof_fill_holes_tensor", "papof_fill_workspace", "papof_propagate_tensor",
-    "papof_temporal_consistency_tensor", "papof_consistency_workspace",
+    "papof_temporal_consistency_tensor", "papof_consistency_workspace", "papof_splat_tensor", "papof_splat_workspace",
+    "papof_interp_splat_tensor",
 ]
 
 
@@ -179,6 +180,14 @@ def load():
     L.papof_interp_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _T,
                                       ctypes.c_longlong, c_void_p]
     L.papof_interp_tensor.restype = c_int
+    L.papof_splat_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, _D, c_double, c_double, _T,
+                                     ctypes.c_longlong, _T, c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_splat_tensor.restype = c_int
+    L.papof_splat_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    L.papof_splat_workspace.restype = ctypes.c_longlong
+    L.papof_interp_splat_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, _T, _T, _T, _T, _T, c_int, _D,
+                                            _T, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_interp_splat_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

@@ -9,7 +9,8 @@
 //
 // Semantics: include/papof.h, papof_interp_tensor.  The bilinear rule is k_fb_check's and k_track's (the reference's,
 // src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours clamped into the image,
-// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler is sampler.h's.
+// taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler and the pixel's rule
+// (interp_pixel, which k_interp_splat of splat.hip applies where no splat lands) are sampler.h's.
 //
 // Mapping.  A block is a 64 x 4 tile of output pixels (as k_fb_check's): blockIdx.x the tile, blockIdx.y the pair.  A wave is
 // 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose stores are contiguous
@@ -25,29 +26,6 @@ namespace papof {
 
 namespace {
 
-constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
-constexpr int kMaxTimes = 16;                  // times per launch (kernel arguments)
-
-struct InterpArgs {
-    papof_tensor f0, f1;  // frames of I0 and I1 (frame, row, column, channel); I1 of pair i is f1's frame i + seq
-    papof_tensor fw, bw;  // flows (pair, row, column, {vx, vy})
-    papof_tensor occ;     // uint8 mask (pair, row, column, {O0, O1}); data NULL: none
-    papof_tensor out;     // (pair, row, column, channel); time j at + j * tstride
-    long long tstride;
-    int H, W, C;
-    int seq;
-    int nt;               // times of this launch
-    double t[kMaxTimes];
-};
-
-__device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Bilinear& k) {  // bytes as 0 / 1
-    const unsigned char* m = static_cast<const unsigned char*>(t.data);
-    double o = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) o += (m[base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2]] ? 1.0 : 0.0) * k.w[i];
-    return o;
-}
-
 // blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: pair `pair0` + y.  Times
 // a.t[0 .. a.nt) are written at time slots j0 + j of out.
 template <int FD>
@@ -62,51 +40,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp(const InterpArg
     const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
     const long long r = (tile / tx) * kInterpTY + threadIdx.y;
     if (x >= a.W || r >= a.H) return;
-    const int H = a.H, W = a.W;
-    const long long i = pair0 + blockIdx.y;
-    const long long of = i * a.fw.stride[0] + r * a.fw.stride[1] + x * a.fw.stride[2];
-    const long long ob = i * a.bw.stride[0] + r * a.bw.stride[1] + x * a.bw.stride[2];
-    const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
-    const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
-    const long long base0 = i * a.f0.stride[0], base1 = (i + a.seq) * a.f1.stride[0];
-    const long long baseo = i * a.occ.stride[0];
-    const long long pix0 = base0 + r * a.f0.stride[1] + x * a.f0.stride[2];
-    const long long pix1 = base1 + r * a.f1.stride[1] + x * a.f1.stride[2];
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
-    for (int j = 0; j < a.nt; j++) {
-        const double t = a.t[j], s = 1.0 - t;
-        const double tt = t * t, st = s * t, ss = s * s;
-        const double a0 = tt * bu - st * u, b0 = tt * bv - st * v;  // F_t->0 = -s t F01 + t^2 F10
-        const double a1 = ss * u - st * bu, b1 = ss * v - st * bv;  // F_t->1 =  s^2 F01 - s t F10
-        const double X0 = (double)x + a0, Y0 = (double)r + b0, X1 = (double)x + a1, Y1 = (double)r + b1;
-        // (false for a NaN)
-        const bool in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
-        const bool in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
-        const Bilinear k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
-        const Bilinear k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
-        double o0 = 0.0, o1 = 0.0;
-        if (a.occ.data && in0 && in1) {
-            o0 = sample_mask(a.occ, baseo, k0);
-            o1 = sample_mask(a.occ, baseo + a.occ.stride[3], k1);
-        }
-        const double w0 = in0 ? s * (1.0 - o1) : 0.0, w1 = in1 ? t * (1.0 - o0) : 0.0;
-        const bool weighted = w0 + w1 > 0;
-        const double c0 = weighted ? w0 : s, c1 = weighted ? w1 : t;
-        const double den = weighted ? w0 + w1 : (in0 ? s : 0.0) + (in1 ? t : 0.0);
-        const long long oj = outp + (j0 + j) * a.tstride;
-        for (int ch = 0; ch < a.C; ch++) {
-            double val;
-            if (in0 || in1) {
-                const double g0 = in0 ? sample_frame<FD>(a.f0, base0 + ch * a.f0.stride[3], k0, lut) : 0.0;
-                const double g1 = in1 ? sample_frame<FD>(a.f1, base1 + ch * a.f1.stride[3], k1, lut) : 0.0;
-                const double num = in0 && in1 ? c0 * g0 + c1 * g1 : (in0 ? c0 * g0 : c1 * g1);
-                val = num / den;
-            } else {
-                val = s * load_frame<FD>(a.f0, pix0 + ch * a.f0.stride[3], lut) + t * load_frame<FD>(a.f1, pix1 + ch * a.f1.stride[3], lut);
-            }
-            store(a.out, oj + ch * a.out.stride[3], val);
-        }
-    }
+    interp_pixel<FD>(a, lut, pair0 + blockIdx.y, r, x, j0, [](int, long long) { return false; });
 }
 
 int launch_interp(hipStream_t st, InterpArgs a, int n_pairs, int n_times, const double* times) {

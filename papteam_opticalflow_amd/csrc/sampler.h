@@ -1,7 +1,8 @@
 // papteam_opticalflow_amd/csrc/sampler.h -- what the device-tensor video kernels share, written once: the bilinear sampler of
 // frames and flows at non-integer points (k_interp, k_warp_affine, k_temporal_filter, k_propagate, the fill and consistency
 // kernels, k_track, k_fb_check), the forward-backward test and the hop of a point through a pair's flows (k_track,
-// k_temporal_filter, k_propagate, k_tc_setup; the test also k_fb_check), and on the host the splitting of a (tile, frame)
+// k_temporal_filter, k_propagate, k_tc_setup; the test also k_fb_check), the interpolation rule at one output pixel (k_interp,
+// k_interp_splat), and on the host the splitting of a (tile, frame)
 // grid at the grid's bounds and the pyramid level sizes of the fill and consistency workspaces.
 //
 // The rule is the reference's (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours
@@ -123,6 +124,83 @@ __device__ __forceinline__ void store(const papof_tensor& t, long long o, double
         static_cast<float*>(t.data)[o] = (float)v;
     else
         static_cast<double*>(t.data)[o] = v;
+}
+
+// ---- the rule of papof_interp_tensor at one output pixel, shared by k_interp (interp.hip) and by k_interp_splat
+// (splat.hip: the pixels that no splat reaches) ----
+constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of pixels per block (256 lanes: lut)
+constexpr int kMaxTimes = 16;                  // times per launch (kernel arguments)
+
+struct InterpArgs {
+    papof_tensor f0, f1;  // frames of I0 and I1 (frame, row, column, channel); I1 of pair i is f1's frame i + seq
+    papof_tensor fw, bw;  // flows (pair, row, column, {vx, vy})
+    papof_tensor occ;     // uint8 mask (pair, row, column, {O0, O1}); data NULL: none
+    papof_tensor out;     // (pair, row, column, channel); time j at + j * tstride
+    long long tstride;
+    int H, W, C;
+    int seq;
+    int nt;               // times of this launch
+    double t[kMaxTimes];
+};
+
+__device__ __forceinline__ double sample_mask(const papof_tensor& t, long long base, const Bilinear& k) {  // bytes as 0 / 1
+    const unsigned char* m = static_cast<const unsigned char*>(t.data);
+    double o = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) o += (m[base + k.row[i] * t.stride[1] + k.col[i] * t.stride[2]] ? 1.0 : 0.0) * k.w[i];
+    return o;
+}
+
+// Pixel (x, r) of pair i at the times a.t[0 .. a.nt), written at time slots j0 + j of out -- except the times j for which
+// done(j, offset of the pixel at that time slot in out) is true: those the caller has written (k_interp: none).
+template <int FD, typename D>
+__device__ __forceinline__ void interp_pixel(const InterpArgs& a, const double* lut, long long i, long long r, int x,
+                                             long long j0, D done) {
+    const int H = a.H, W = a.W;
+    const long long of = i * a.fw.stride[0] + r * a.fw.stride[1] + x * a.fw.stride[2];
+    const long long ob = i * a.bw.stride[0] + r * a.bw.stride[1] + x * a.bw.stride[2];
+    const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
+    const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
+    const long long base0 = i * a.f0.stride[0], base1 = (i + a.seq) * a.f1.stride[0];
+    const long long baseo = i * a.occ.stride[0];
+    const long long pix0 = base0 + r * a.f0.stride[1] + x * a.f0.stride[2];
+    const long long pix1 = base1 + r * a.f1.stride[1] + x * a.f1.stride[2];
+    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    for (int j = 0; j < a.nt; j++) {
+        const long long oj = outp + (j0 + j) * a.tstride;
+        if (done(j, oj)) continue;
+        const double t = a.t[j], s = 1.0 - t;
+        const double tt = t * t, st = s * t, ss = s * s;
+        const double a0 = tt * bu - st * u, b0 = tt * bv - st * v;  // F_t->0 = -s t F01 + t^2 F10
+        const double a1 = ss * u - st * bu, b1 = ss * v - st * bv;  // F_t->1 =  s^2 F01 - s t F10
+        const double X0 = (double)x + a0, Y0 = (double)r + b0, X1 = (double)x + a1, Y1 = (double)r + b1;
+        // (false for a NaN)
+        const bool in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
+        const bool in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
+        const Bilinear k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
+        const Bilinear k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
+        double o0 = 0.0, o1 = 0.0;
+        if (a.occ.data && in0 && in1) {
+            o0 = sample_mask(a.occ, baseo, k0);
+            o1 = sample_mask(a.occ, baseo + a.occ.stride[3], k1);
+        }
+        const double w0 = in0 ? s * (1.0 - o1) : 0.0, w1 = in1 ? t * (1.0 - o0) : 0.0;
+        const bool weighted = w0 + w1 > 0;
+        const double c0 = weighted ? w0 : s, c1 = weighted ? w1 : t;
+        const double den = weighted ? w0 + w1 : (in0 ? s : 0.0) + (in1 ? t : 0.0);
+        for (int ch = 0; ch < a.C; ch++) {
+            double val;
+            if (in0 || in1) {
+                const double g0 = in0 ? sample_frame<FD>(a.f0, base0 + ch * a.f0.stride[3], k0, lut) : 0.0;
+                const double g1 = in1 ? sample_frame<FD>(a.f1, base1 + ch * a.f1.stride[3], k1, lut) : 0.0;
+                const double num = in0 && in1 ? c0 * g0 + c1 * g1 : (in0 ? c0 * g0 : c1 * g1);
+                val = num / den;
+            } else {
+                val = s * load_frame<FD>(a.f0, pix0 + ch * a.f0.stride[3], lut) + t * load_frame<FD>(a.f1, pix1 + ch * a.f1.stride[3], lut);
+            }
+            store(a.out, oj + ch * a.out.stride[3], val);
+        }
+    }
 }
 
 constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x

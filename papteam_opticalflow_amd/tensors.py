@@ -31,6 +31,13 @@ two frames of each pair from its forward and backward flows and, optionally, its
 
     iv = interpolate_video(frames, 5, factor=3, layout="NHWC")   # iv.video: (3 (T - 1) + 1, H, W, C), frames at 3x the rate
 
+Forward warping: `splat` (include/papof.h: papof_splat_tensor) moves every pixel of a tensor along its own flow and deposits
+it where it lands, with optional per-pixel weights (`splat_weights`: exp(-alpha * photometric error)); the sums are 64-bit
+fixed-point integers, so the result is bitwise reproducible.  `interpolate(..., method="splat")`
+(papof_interp_splat_tensor) splats both frames to the time in between, which stays right at motion boundaries.
+
+    out, coverage = splat(frames[:-1], fb.flow_fw, 0.5, layout="NHWC")   # out (B, 1, H, W, C), coverage (B, 1, H, W)
+
 Stabilization: `global_motion` (include/papof.h: papof_motion_fit_tensor) fits one similarity or affine motion per pair to
 its forward flow (robust IRLS in float64, two HIP kernels per iteration), `stabilizing_transforms` smooths the camera path
 on the host and `warp_affine` (papof_warp_affine_tensor) resamples the frames; `stabilize_video` chains flow_video and them.
@@ -75,6 +82,9 @@ Tracks = collections.namedtuple("Tracks", "tracks visible")
 TrackVideo = collections.namedtuple("TrackVideo", "tracks visible flow_fw flow_bw timing")
 InterpPairs = collections.namedtuple("InterpPairs", "frames flow_fw flow_bw occlusion timing")
 Interp = collections.namedtuple("Interp", "video flow_fw flow_bw occlusion timing")
+Splat = collections.namedtuple("Splat", "out coverage")
+METHODS = ("gather", "splat")
+ALPHA = 20.0  # splat_weights: the weight of a pixel is exp(-ALPHA * its photometric error)
 Motion = collections.namedtuple("Motion", "motion ok support")
 Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
 Filtered = collections.namedtuple("Filtered", "video support")
@@ -494,9 +504,9 @@ def track_video(frames, pyramidLevels, queries=None, *, layout="NCHW", consisten
     return TrackVideo(tr.tracks, tr.visible, fb.flow_fw, fb.flow_bw, fb.timing)
 
 
-def _times(times):
-    """the times as a list of floats, each finite and strictly inside (0, 1) -- TypeError / ValueError otherwise.  A tensor
-    is read on the host (a device tensor waits for its stream)."""
+def _times(times, inside=True):
+    """the times as a list of floats, each finite and (with `inside`) strictly inside (0, 1) -- TypeError / ValueError
+    otherwise.  A tensor is read on the host (a device tensor waits for its stream)."""
     torch = _torch()
     if isinstance(times, torch.Tensor):
         if times.dim() > 1 or times.dtype == torch.bool or times.is_complex():
@@ -513,7 +523,9 @@ def _times(times):
     if not ts:
         raise ValueError("times is empty")
     for x in ts:
-        if not (math.isfinite(x) and 0.0 < x < 1.0):
+        if not math.isfinite(x):
+            raise ValueError("every time must be finite, got %r" % x)
+        if inside and not 0.0 < x < 1.0:
             raise ValueError("every time must lie strictly inside (0, 1), got %r" % x)
     return ts
 
@@ -537,14 +549,74 @@ def _flow_struct(f, code):
     return _struct(f, (f.stride(0), f.stride(2), f.stride(3), f.stride(1)), code)
 
 
-def _interp(d_in, sequence, n_pairs, H, W, C, flows, codes, occlusion, times, out, d_out, time_stride, dev):
-    """papof_interp_tensor on the current stream of `dev`, writing through d_out"""
+def _weight_struct(w):
+    """the descriptor (item, row, column, -) of a checked weight tensor, None for None"""
+    if w is None:
+        return None
+    code = capi.DTYPE_F32 if w.dtype == _torch().float32 else capi.DTYPE_F64
+    return _struct(w, (w.stride(0), w.stride(1), w.stride(2), 0), code)
+
+
+def _check_weight(name, w, shape, dev):
+    """None, or a float32 / float64 weight tensor of `shape` = (B, H, W) on `dev`: w itself -- TypeError / ValueError
+    otherwise"""
+    if w is None:
+        return None
+    torch = _torch()
+    codes = (torch.float32, torch.float64)
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("%s must be None or a torch.Tensor, got %s" % (name, type(w).__name__))
+    if w.dtype not in codes:
+        raise TypeError("%s must be float32 or float64, got %s" % (name, w.dtype))
+    if tuple(w.shape) != shape:
+        raise ValueError("%s must be (B, H, W) = %s, got %s" % (name, shape, tuple(w.shape)))
+    if w.device != dev:
+        raise ValueError("%s is on %s, the frames on %s: all must be on one device" % (name, w.device, dev))
+    return w
+
+
+def _check_method(method, weights, shape, dev):
+    """None for "gather", the two weight tensors (each may be None) for "splat" -- ValueError / TypeError otherwise"""
+    if method not in METHODS:
+        raise ValueError("method must be one of %s, got %r" % (METHODS, method))
+    if method == "gather":
+        if weights is not None:
+            raise ValueError("weights are for method=\"splat\"")
+        return None
+    if weights is None:
+        return None, None
+    if not isinstance(weights, (tuple, list)) or len(weights) != 2:
+        raise TypeError("weights must be None or a pair (w_fw, w_bw), got %r" % (weights,))
+    w_fw, w_bw = weights
+    return _check_weight("w_fw", w_fw, shape, dev), _check_weight("w_bw", w_bw, shape, dev)
+
+
+def _check_alpha(alpha):
+    try:
+        alpha = float(alpha)
+    except (TypeError, ValueError):
+        raise TypeError("alpha must be a number, got %r" % (alpha,)) from None
+    if not (math.isfinite(alpha) and alpha >= 0):
+        raise ValueError("alpha must be finite and >= 0, got %r" % alpha)
+    return alpha
+
+
+def _interp(d_in, sequence, n_pairs, H, W, C, flows, codes, occlusion, times, out, d_out, time_stride, dev, splat=None):
+    """papof_interp_tensor -- or, with splat = (the forward weights or None, the backward ones or None),
+    papof_interp_splat_tensor -- on the current stream of `dev`, writing through d_out"""
     d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
     d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
     ts = (ctypes.c_double * len(times))(*times)
-    _launch(dev, "papof_interp_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
-            None if sequence else ctypes.byref(d_in[1]), H, W, C, ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), _ref(d_occ),
-            len(times), ts, ctypes.byref(d_out), time_stride)
+    head = (n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]), None if sequence else ctypes.byref(d_in[1]), H, W, C,
+            ctypes.byref(d_f[0]), ctypes.byref(d_f[1]))
+    tail = (_ref(d_occ), len(times), ts, ctypes.byref(d_out), time_stride)
+    if splat is None:
+        _launch(dev, "papof_interp_tensor", *head, *tail)
+    else:
+        d_w = [_weight_struct(w) for w in splat]
+        _launch(dev, "papof_interp_splat_tensor", *head, _ref(d_w[0]), _ref(d_w[1]), *tail,
+                workspace=("papof_splat_workspace", (2 * n_pairs, len(times), H, W, C),
+                           "%d pairs of %d x %d x %d are too large to splat" % (n_pairs, H, W, C)))
     return out
 
 
@@ -560,7 +632,8 @@ def _new_interp_out(B, K, H, W, C, layout, out_dtype, dev):
     return out, _struct(out, strides, _out_code(out_dtype)), out.stride(1)
 
 
-def interpolate(im1, im2, flow_fw, flow_bw, times, *, occlusion=None, layout="NCHW", out_dtype=None):
+def interpolate(im1, im2, flow_fw, flow_bw, times, *, occlusion=None, layout="NCHW", out_dtype=None, method="gather",
+                weights=None):
     """Motion-compensated interpolation between the frames of the pairs (im1[i], im2[i]): two tensors of one shape,
     (B, C, H, W) or (B, H, W, C) by `layout`, of uint8 (read as x / 255), float32 or float64, any strides, on one HIP
     device.  flow_fw, flow_bw: (B, 2, H, W) float32 / float64, im1 -> im2 and back, as flow_pairs_fb returns them.
@@ -571,26 +644,113 @@ def interpolate(im1, im2, flow_fw, flow_bw, times, *, occlusion=None, layout="NC
     Each output pixel p samples im1 at p + F_t->0 and im2 at p + F_t->1, F_t->0 = -(1 - t) t F01 + t^2 F10,
     F_t->1 = (1 - t)^2 F01 - (1 - t) t F10 with the flows at p, and blends the two with weights 1 - t and t, each lowered
     where the mask says its sample is hidden in the other frame; include/papof.h (papof_interp_tensor) states it exactly.
+    method="splat" (papof_interp_splat_tensor) instead moves every pixel of im1 along t F01 and every pixel of im2 along
+    (1 - t) F10, each along its OWN flow, and divides the two blended sums; `weights` is None (all ones) or a pair
+    (w_fw, w_bw) of (B, H, W) float32 / float64 tensors for the pixels of im1 and of im2 (either may be None), as
+    splat_weights makes them.  Only the pixels that nothing reaches are method="gather"'s, and only they use the mask.
     Enqueued on the current stream; returns without waiting."""
     ts, descs, _, _ = _check([("im1", im1), ("im2", im2)], layout, None, 1)
     times = _times(times)
+    splat = _check_method(method, weights, descs[0][0][:3], ts[0].device)
     out_dtype = _out_dtype(out_dtype, _torch().promote_types(ts[0].dtype, ts[1].dtype))
     (B, H, W, C), _, _ = descs[0]
     codes = _check_flows(flow_fw, flow_bw, (B, 2, H, W), ts[0].device)
     occ = _check_occlusion(occlusion, (B, 2, H, W), ts[0].device)
     out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
-    return _interp(d_in, False, B, H, W, C, (flow_fw, flow_bw), codes, occ, times, out, d_out, tstride, ts[0].device)
+    return _interp(d_in, False, B, H, W, C, (flow_fw, flow_bw), codes, occ, times, out, d_out, tstride, ts[0].device, splat)
 
 
-def interpolate_pairs(im1, im2, pyramidLevels, times, *, layout="NCHW", consistency=CONSISTENCY, out_dtype=None, **solver):
+def _photometric_weights(im, warped, alpha, layout):
+    torch = _torch()
+    a, b = (t.double() / 255.0 if t.dtype == torch.uint8 else t.double() for t in (im, warped))
+    err = (a - b).abs().mean(dim=1 if layout == "NCHW" else 3)
+    return torch.exp(torch.clamp(-alpha * err, min=-11.0))
+
+
+def splat_weights(im, warped, alpha=ALPHA, *, layout="NCHW"):
+    """The weights of the pixels of `im` for splat / interpolate(method="splat"): exp(clamp(-alpha * mean over channels of
+    |im - warped|, min=-11)), a (B, H, W) float64 tensor made with torch operations on the tensors' device (uint8 read as
+    x / 255).  `warped` is the other frame brought to this one -- the warpI2 that the flow calls return: a pixel whose flow
+    is wrong or which is hidden in the other frame looks different there and counts for little where it lands.  The floor
+    e^-11 (about 2^-15.9) keeps every weight far above the resolution 2^-32 of the splat's fixed point, so a pixel that
+    only badly matched pixels reach is still covered."""
+    alpha = _check_alpha(alpha)
+    ts, _, _, _ = _check([("im", im), ("warped", warped)], layout, None, 1)
+    return _photometric_weights(ts[0], ts[1], alpha, layout)
+
+
+MAX_BOUND_LOG2 = 20  # include/papof.h: papof_splat_tensor
+
+
+def _check_bound(bound):
+    """bound as a float: 2^k with k an integer in [-20, 20] -- TypeError / ValueError otherwise"""
+    try:
+        bound = float(bound)
+    except (TypeError, ValueError):
+        raise TypeError("bound must be a number, got %r" % (bound,)) from None
+    if not (math.isfinite(bound) and bound > 0 and math.frexp(bound)[0] == 0.5
+            and abs(math.frexp(bound)[1] - 1) <= MAX_BOUND_LOG2):
+        raise ValueError("bound must be a power of two from 2^-%d to 2^%d, got %r" % (MAX_BOUND_LOG2, MAX_BOUND_LOG2, bound))
+    return bound
+
+
+def splat(x, flow, times=1.0, *, weight=None, bound=1.0, fill=0.0, layout="NCHW", out_dtype=None):
+    """Forward warping: every pixel of x -- (B, C, H, W) or (B, H, W, C) by `layout` (3-D: one item), uint8 (read as
+    x / 255), float32 or float64, any strides, on a HIP device -- is moved along t times its own flow, flow (B, 2, H, W)
+    float32 / float64, and deposited bilinearly on the four pixels around where it lands, for every t of `times`: a float,
+    a sequence or a 1-D tensor of finite values read on the host (0 deposits in place, values outside [0, 1] extrapolate).
+    weight: None (1.0) or (B, H, W) float32 / float64 -- a pixel counts with min(weight, 1) and not at all where its weight
+    is <= 0 or not finite, its flow is not finite or it lands outside the image.  bound: a power of two, 2^-20 .. 2^20,
+    that no |value| of x exceeds (1.0 for frames; larger values are clamped to it): splat(flow, flow, bound=1024.0) carries
+    a flow field of at most 1024 pixels to the frame it points to.  Returns Splat(out, coverage): out (B, K, C, H, W) or
+    (B, K, H, W, C), K = len(times), of out_dtype (uint8 as clamp(rint(255 v), 0, 255), float32 or float64; by default x's
+    dtype), the weighted mean of what landed on each pixel, or `fill` where coverage < 2^-24 (a hole); coverage
+    (B, K, H, W) float64, the sum of the weights that landed.  The sums are 64-bit fixed-point integers added atomically,
+    so the result does not depend on the order of arrival: it is bitwise reproducible.  include/papof.h
+    (papof_splat_tensor) states the rule exactly.  The workspace comes from PyTorch's allocator; enqueued on the current
+    stream, returns without waiting."""
+    torch = _torch()
+    ts, descs, _, _ = _check([("x", x)], layout, None, 1)
+    times = _times(times, inside=False)
+    bound = _check_bound(bound)
+    try:
+        fill = float(fill)
+    except (TypeError, ValueError):
+        raise TypeError("fill must be a number, got %r" % (fill,)) from None
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    (B, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    f_code = _check_flow("flow", flow)
+    if tuple(flow.shape) != (B, 2, H, W):
+        raise ValueError("flow must be %s for this x, got %s" % ((B, 2, H, W), tuple(flow.shape)))
+    if flow.device != dev:
+        raise ValueError("flow is on %s, x on %s: all must be on one device" % (flow.device, dev))
+    d_w = _weight_struct(_check_weight("weight", weight, (B, H, W), dev))
+    K = len(times)
+    out, d_out, tstride = _new_interp_out(B, K, H, W, C, layout, out_dtype, dev)
+    coverage = torch.empty((B, K, H, W), dtype=torch.float64, device=dev)
+    d_cov = _struct(coverage, coverage.stride(), capi.DTYPE_F64)
+    d_x, d_flow = _struct(ts[0], strides, code), _flow_struct(flow, f_code)
+    _launch(dev, "papof_splat_tensor", B, H, W, C, ctypes.byref(d_x), ctypes.byref(d_flow), _ref(d_w), K,
+            (ctypes.c_double * K)(*times), bound, fill, ctypes.byref(d_out), tstride, ctypes.byref(d_cov),
+            workspace=("papof_splat_workspace", (B, K, H, W, C),
+                       "%d items of %d x %d x %d are too large to splat" % (B, H, W, C)))
+    return Splat(out, coverage)
+
+
+def interpolate_pairs(im1, im2, pyramidLevels, times, *, layout="NCHW", consistency=CONSISTENCY, out_dtype=None,
+                      method="gather", alpha=ALPHA, **solver):
     """flow_pairs_fb(im1, im2, pyramidLevels, layout=layout, consistency=consistency, **solver) -- float64 flows whatever
     out_dtype is -- followed by interpolate on its flows and mask (None for consistency=None: no mask).  Returns
     InterpPairs(frames (B, K, ...) as interpolate's, flow_fw, flow_bw, occlusion, timing of the flow call).  Every argument
     error raises before anything is launched; the flows are complete on return, the frames are enqueued on the current
-    stream behind them."""
+    stream behind them.  method="splat": interpolate's, with the weights splat_weights(im1, warpI2_fw, alpha) and
+    splat_weights(im2, warpI2_bw, alpha) of the flow call's own warped frames."""
     torch = _torch()
     alphas = _alphas(consistency)
+    _check_method(method, None, None, None)
+    alpha = _check_alpha(alpha)
     ts, descs, _, params = _check([("im1", im1), ("im2", im2)], layout, None, pyramidLevels, solver=solver)
     times = _times(times)
     out_dtype = _out_dtype(out_dtype, torch.promote_types(ts[0].dtype, ts[1].dtype))
@@ -600,8 +760,15 @@ def interpolate_pairs(im1, im2, pyramidLevels, times, *, layout="NCHW", consiste
     out, d_out, tstride = _new_interp_out(B, len(times), H, W, C, layout, out_dtype, ts[0].device)
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
     _interp(d_in, False, B, H, W, C, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, times, out, d_out,
-            tstride, ts[0].device)
+            tstride, ts[0].device, _own_weights(method, ts[0], ts[1], fb, alpha, layout))
     return InterpPairs(out, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
+
+
+def _own_weights(method, im1, im2, fb, alpha, layout):
+    """_interp's `splat` from the warped frames of the flow call fb (None for method="gather")"""
+    if method == "gather":
+        return None
+    return tuple(_photometric_weights(im, warped, alpha, layout) for im, warped in ((im1, fb.warpI2_fw), (im2, fb.warpI2_bw)))
 
 
 def _converted(frames, out_dtype):
@@ -619,16 +786,19 @@ def _converted(frames, out_dtype):
 
 
 def interpolate_video(frames, pyramidLevels, factor=2, *, layout="NCHW", consistency=CONSISTENCY, out_dtype=None,
-                      **solver):
+                      method="gather", alpha=ALPHA, **solver):
     """A video of T >= 2 frames at `factor` (an integer >= 2) times its frame rate: flow_video_fb(frames, pyramidLevels,
     layout=layout, consistency=consistency, **solver) -- float64 flows whatever out_dtype is -- then interpolate between
     every two consecutive frames at the times j / factor, j = 1 .. factor - 1.  Returns Interp(video, flow_fw, flow_bw,
     occlusion, timing of the flow call): video has (T - 1) factor + 1 frames in `layout` and out_dtype (by default the
     frames'); frame k factor is input frame k, copied bit for bit (converted as interpolate converts when out_dtype
     differs), and the frames between are written by the kernel straight into the video.  Every argument error raises
-    before anything is launched; the flows are complete on return, the video is enqueued on the current stream."""
+    before anything is launched; the flows are complete on return, the video is enqueued on the current stream.
+    method="splat": as interpolate_pairs's, the weights from the flow call's own warped frames."""
     torch = _torch()
     alphas = _alphas(consistency)
+    _check_method(method, None, None, None)
+    alpha = _check_alpha(alpha)
     ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     if isinstance(factor, bool) or not isinstance(factor, int) or factor < 2:
         raise ValueError("factor must be an integer >= 2, got %r" % (factor,))
@@ -644,7 +814,7 @@ def interpolate_video(frames, pyramidLevels, factor=2, *, layout="NCHW", consist
     times = [j / factor for j in range(1, factor)]
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
     _interp(d_in, True, T - 1, H, W, C, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, times, video, d_out,
-            vs[0], dev)
+            vs[0], dev, _own_weights(method, ts[0][:-1], ts[0][1:], fb, alpha, layout))
     return Interp(video, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
 
 
