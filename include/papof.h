@@ -871,6 +871,60 @@ int papof_interp_splat_tensor(papof_handle* h, int n_pairs, int sequence, const 
                               const papof_tensor* occlusion, int n_times, const double* times, const papof_tensor* out,
                               long long time_stride, void* workspace, long long workspace_bytes, void* stream);
 
+/* Edge-aware flow refinement: the image-guided weighted median filter of a flow field (the non-local term of Sun, Roth and
+ * Black, "Secrets of optical flow estimation and their principles", CVPR 2010, as a post-process).  One kernel per pass on
+ * `stream` (k_refine, refine.hip: one lane per output pixel, the tile and its halo staged in LDS, a weighted quickselect).
+ * flow: float32 (widened exactly) or float64, (item, row, column, {vx, vy}), any non-negative strides.  guide: uint8, float32
+ * (widened exactly) or float64, (item, row, column, channel), c channels, c in 1 .. 4; its RAW values enter the rule (a
+ * uint8 sample as the integer 0 .. 255): the guide's scale and the division by c live in q.  occlusion: NULL, or uint8
+ * (item, row, column, -), nonzero = this pixel's flow is not to be trusted.  where: NULL (every pixel), or uint8 (item, row,
+ * column, -), nonzero = filter this pixel; the others are copied.  stride[3] of the masks is not read.
+ * radius r in 1 .. 15; S: DEVICE pointer to the (2 r + 1)^2 spatial weights, row-major in (dy, dx); R: DEVICE pointer to the
+ * 4096 range weights; S[.] * R[.] must stay below 2^31 (papof_refine_tables' do); q finite and >= 0; iters in 1 .. 65536.
+ * For output pixel p of an item, and every neighbour p' = p + (dx, dy), |dx|, |dy| <= r, inside the image:
+ *     D = (g_0(p) - g_0(p'))^2 + (g_1(p) - g_1(p'))^2 + ...     fp64, channels added in order from 0, no fused multiply-add
+ *     p' is DEAD (w = 0) if D is not finite, if a component of flow[p'] is not finite, or if occlusion[p'] != 0;
+ *     otherwise  k = (int) min(D * q, 4095.0)   (one fp64 product)   and   w = S[(dy + r) * (2 r + 1) + dx + r] * R[k]
+ *     T = sum of w                                                        (unsigned 64-bit)
+ *     per component (vx, then vy) separately: out = the smallest value x among the neighbours with w > 0 for which
+ *         2 * sum{w : value <= x} >= T                                    (the lower weighted median)
+ * Values are ordered by the monotone integer key of their float64 bits (b ^ ((b >> 63) & 0x7fff...f), compared as signed
+ * 64-bit integers), so -0.0 sorts below +0.0 and the result is the bits of one particular neighbour.  There is no float
+ * sum, so nothing depends on an order of evaluation: the result is a pure function of the inputs, bitwise reproducible.
+ * If T = 0 (every neighbour dead) or where[p] = 0 the output is flow[p].  The centre is an ordinary neighbour: dead if
+ * occluded or not finite, which is how such a pixel takes its neighbours' motion.
+ * iters > 1 repeats the pass on its own output (guide, masks and tables unchanged); the intermediate fields are float64 in
+ * the workspace, so a float64 flow stored as float32 is rounded once, to nearest, at the end.  out: float32 / float64,
+ * (item, row, column, {vx, vy}), positive strides; it must not overlap flow (a block reads its neighbours' pixels).
+ * passes: NULL, or uint8 (item, row, column, -): a measurement aid, the passes over the window that the pixel's lane made in
+ * the last iteration (0: copied; 1: T = 0 or both components constant; saturating at 255).
+ * Tables as papof_refine_tables fills them, with q = 128 / (sigma_c^2 c) for a float guide in 0 .. 1 and
+ * 128 / (sigma_c^2 c 255^2) for a uint8 guide, give the weight exp(-(dx^2 + dy^2) / (2 sigma_s^2)) * exp(-d2 / (2 sigma_c^2)),
+ * d2 the mean over channels of the squared difference of the guide scaled to 0 .. 1, sampled in 4096 bins up to
+ * d2 = 32 sigma_c^2 and zero beyond.
+ * workspace: device memory, 8-byte aligned, owned by the caller for the duration of the enqueued work;
+ * papof_refine_workspace gives its bytes (0 for iters = 1: workspace may then be NULL).
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (occlusion, where and passes aside) or data pointer,
+ * a dtype other than those above, a negative stride or a zero stride of out, n, height or width < 1, height * width >= 2^30,
+ * a workspace beyond 2^62 bytes, c outside 1 .. 4, radius outside 1 .. 15, S or R NULL, q negative or not finite,
+ * iters outside 1 .. 65536, a NULL or too small workspace where one is needed. */
+int papof_refine_flow_tensor(papof_handle* h, int n, int height, int width, int c, const papof_tensor* flow,
+                             const papof_tensor* guide, const papof_tensor* occlusion, const papof_tensor* where, int radius,
+                             const unsigned* S, const unsigned* R, double q, int iters, const papof_tensor* out,
+                             const papof_tensor* passes, void* workspace, long long workspace_bytes, void* stream);
+
+/* Bytes of papof_refine_flow_tensor's workspace: 0 for iters = 1, one float64 field (16 n height width) for iters = 2, two
+ * for more; -1 where that call refuses the sizes (n, height or width < 1, iters outside 1 .. 65536, height * width >= 2^30,
+ * beyond 2^62). */
+long long papof_refine_workspace(int n, int height, int width, int iters);
+
+/* The tables of papof_refine_flow_tensor on the HOST, with libm's exp:
+ *     S[(dy + r) * (2 r + 1) + dx + r] = rint(32768 * exp(-(dx^2 + dy^2) / (2 sigma_s^2))),   |dx|, |dy| <= r = radius
+ *     R[k] = rint(65536 * exp(-(k + 0.5) / 256)),   k = 0 .. 4095        (R[0] = 65408, R[4095] = 0; no sigma enters)
+ * PAPOF_EINVAL: radius outside 1 .. 15, sigma_s not finite or <= 0, S or R NULL. */
+int papof_refine_tables(int radius, double sigma_s, unsigned* S, unsigned* R);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

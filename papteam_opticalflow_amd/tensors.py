@@ -65,6 +65,13 @@ device; `consistent_video` computes the flows first (flow_video_fb).
 
     cv = consistent_video(frames, stylized, 5, layout="NHWC")   # cv.video: the consistent processed video
 
+Flow refinement: `refine_flow` (include/papof.h: papof_refine_flow_tensor) is the image-guided weighted median filter of a
+flow field (the non-local term of Sun, Roth and Black 2010): it sharpens the motion boundaries that the solver rounds off,
+along the edges of a guide image, and gives occluded or NaN pixels their neighbours' motion; integer weights and sums, so the
+result is bitwise reproducible.  `refine_video_flows` filters both directions of a video's flows and recomputes the mask.
+
+    fw, bw, occ = refine_video_flows(frames, fb.flow_fw, fb.flow_bw, occlusion=fb.occlusion, layout="NHWC")
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -93,6 +100,7 @@ Flows = collections.namedtuple("Flows", "flow_fw flow_bw")
 Propagated = collections.namedtuple("Propagated", "video status")
 Inpainted = collections.namedtuple("Inpainted", "video status")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
+RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
 MODELS = {"similarity": capi.MOTION_SIMILARITY, "affine": capi.MOTION_AFFINE}
 
 _lock = threading.Lock()
@@ -1371,3 +1379,185 @@ def consistent_video(frames, processed, pyramidLevels, *, flows=None, lam=LAM, s
     video = _consistency(ts, descs, p, d_p, (flow_fw, flow_bw), codes, d_first, lam, sigma, iters, alphas, layout,
                          out_dtype)
     return Consistent(video, flow_fw, flow_bw, timing)
+
+
+MAX_REFINE_RADIUS = 15  # include/papof.h: papof_refine_flow_tensor
+REFINE_BINS = 4096
+RADIUS, SIGMA_S, SIGMA_C = 7, 7.0, 7.0 / 255.0  # Sun, Roth and Black: a 15 x 15 window, 7 pixels, 7 grey levels
+
+
+def _check_refine(radius, sigma_s, sigma_c, iters):
+    """(radius, sigma_s, sigma_c, iters) as int, float, float, int -- TypeError / ValueError otherwise"""
+    for name, v in (("radius", radius), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("%s must be an int, got %r" % (name, v))
+    if not 1 <= radius <= MAX_REFINE_RADIUS:
+        raise ValueError("radius must be in 1 .. %d, got %d" % (MAX_REFINE_RADIUS, radius))
+    if iters < 1 or iters > MAX_ITERS:
+        raise ValueError("iters must be in 1 .. %d, got %d" % (MAX_ITERS, iters))
+    sig = []
+    for name, v in (("sigma_s", sigma_s), ("sigma_c", sigma_c)):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise TypeError("%s must be a number, got %r" % (name, v)) from None
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError("%s must be finite and > 0, got %r" % (name, v))
+        sig.append(v)
+    return radius, sig[0], sig[1], iters
+
+
+def refine_tables(radius, sigma_s):
+    """The two integer tables of refine_flow as numpy uint32 arrays, made by the library on the host (include/papof.h:
+    papof_refine_tables): S ((2 radius + 1)^2,) = rint(32768 exp(-(dx^2 + dy^2) / (2 sigma_s^2))), row-major in (dy, dx), and
+    R (4096,) = rint(65536 exp(-(k + 0.5) / 256))."""
+    import numpy as np
+    radius, sigma_s, _, _ = _check_refine(radius, sigma_s, 1.0, 1)
+    S, R = np.zeros((2 * radius + 1) ** 2, np.uint32), np.zeros(REFINE_BINS, np.uint32)
+    U = ctypes.POINTER(ctypes.c_uint)
+    capi._chk(capi.load().papof_refine_tables(radius, sigma_s, S.ctypes.data_as(U), R.ctypes.data_as(U)), "papof_refine_tables")
+    return S, R
+
+
+def refine_q(sigma_c, channels, uint8):
+    """The factor q of papof_refine_flow_tensor, in fp64: 128 / (sigma_c^2 C), over 255^2 for a uint8 guide"""
+    q = 128.0 / (sigma_c * sigma_c * channels)
+    return q / 65025.0 if uint8 else q
+
+
+def _check_plane_mask(name, m, shape, dev):
+    """None, or a bool / uint8 mask of `shape` = (B, H, W) on `dev`: its descriptor (item, row, column, -) and the uint8 view
+    that owns the memory -- TypeError / ValueError otherwise"""
+    if m is None:
+        return None, None
+    torch = _torch()
+    if not isinstance(m, torch.Tensor):
+        raise TypeError("%s must be None or a torch.Tensor, got %s" % (name, type(m).__name__))
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("%s must be torch.bool or torch.uint8, got %s" % (name, m.dtype))
+    if tuple(m.shape) != shape:
+        raise ValueError("%s must be (B, H, W) = %s, got %s" % (name, shape, tuple(m.shape)))
+    if m.device != dev:
+        raise ValueError("%s is on %s, the flow on %s: all must be on one device" % (name, m.device, dev))
+    m = m.view(torch.uint8)
+    return _struct(m, (m.stride(0), m.stride(1), m.stride(2), 0), capi.DTYPE_U8), m
+
+
+def _check_refine_flow(flow, guide, occlusion, where, layout, out_dtype):
+    """every argument error of refine_flow's tensors: (the guide as 4-D, its descriptor, the flow's code, the masks'
+    descriptors and views, out_dtype)"""
+    torch = _torch()
+    ts, descs, _, _ = _check([("guide", guide)], layout, None, 1)
+    (B, H, W, C), _, _ = descs[0]
+    if not 1 <= C <= MAX_CHANNELS:
+        raise ValueError("the guide must have 1 .. %d channels, got %d" % (MAX_CHANNELS, C))
+    dev = ts[0].device
+    code = _check_flow("flow", flow)
+    if tuple(flow.shape) != (B, 2, H, W):
+        raise ValueError("flow must be %s for this guide, got %s" % ((B, 2, H, W), tuple(flow.shape)))
+    if flow.device != dev:
+        raise ValueError("flow is on %s, the guide on %s: all must be on one device" % (flow.device, dev))
+    out_dtype = flow.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.float32 or torch.float64, got %s" % out_dtype)
+    occ = _check_plane_mask("occlusion", occlusion, (B, H, W), dev)
+    wh = _check_plane_mask("where", where, (B, H, W), dev)
+    return ts[0], descs[0], code, occ, wh, out_dtype
+
+
+_tables = collections.OrderedDict()  # (device ordinal, radius, sigma_s) -> the two tables on the device, the last 16 used
+MAX_TABLES = 16
+
+
+def _device_tables(dev, radius, sigma_s):
+    """refine_tables(radius, sigma_s) on `dev` as int32 tensors (entries below 2^31: the same bits).  They are uploaded once
+    per (device, radius, sigma_s) and the upload is waited for, so later calls read finished, immutable tables from any
+    stream and enqueue no copy; only the first call with new parameters blocks the host."""
+    torch = _torch()
+    index = _index(dev)
+    stream = torch.cuda.current_stream(index)
+    with _lock:
+        got = _tables.pop((index, radius, sigma_s), None)
+        if got is None:
+            with torch.cuda.device(index):
+                got = tuple(torch.from_numpy(t.view("int32")).to(dev) for t in refine_tables(radius, sigma_s))
+            stream.synchronize()
+        _tables[(index, radius, sigma_s)] = got
+        while len(_tables) > MAX_TABLES:
+            _tables.popitem(last=False)
+    for t in got:
+        t.record_stream(stream)  # (an evicted table is reused only behind the kernels that read it)
+    return got
+
+
+def _refine(flow, code, guide, desc, occ, wh, radius, sigma_s, sigma_c, iters, out_dtype, passes=False):
+    """papof_refine_flow_tensor on the current stream of the flow's device"""
+    torch = _torch()
+    (B, H, W, C), strides, g_code = desc
+    dev = flow.device
+    q = refine_q(sigma_c, C, g_code == capi.DTYPE_U8)
+    d_S, d_R = _device_tables(dev, radius, sigma_s)
+    out = torch.empty((B, 2, H, W), dtype=out_dtype, device=dev)
+    count = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if passes else None
+    d_count = _struct(count, (H * W, W, 1, 0), capi.DTYPE_U8) if passes else None
+    d_flow, d_guide, d_out = _flow_struct(flow, code), _struct(guide, strides, g_code), _flow_struct(out, _out_code(out_dtype))
+    _launch(dev, "papof_refine_flow_tensor", B, H, W, C, ctypes.byref(d_flow), ctypes.byref(d_guide), _ref(occ[0]), _ref(wh[0]),
+            radius, ctypes.c_void_p(d_S.data_ptr()), ctypes.c_void_p(d_R.data_ptr()), q, iters, ctypes.byref(d_out),
+            _ref(d_count), workspace=("papof_refine_workspace", (B, H, W, iters),
+                                      "%d flows of %d x %d are too large to refine" % (B, H, W)))
+    return (out, count) if passes else out
+
+
+def refine_flow(flow, guide, *, occlusion=None, where=None, radius=RADIUS, sigma_s=SIGMA_S, sigma_c=SIGMA_C, iters=1,
+                layout="NCHW", out_dtype=None):
+    """Edge-aware refinement of flow fields: the weighted median filter of Sun, Roth and Black (2010) guided by an image.
+    flow: (B, 2, H, W) float32 / float64, any strides, on a HIP device.  guide: (B, C, H, W) or (B, H, W, C) by `layout`
+    (3-D: one item), C in 1 .. 4, uint8, float32 or float64 (a float guide is taken to be scaled to 0 .. 1, a uint8 guide
+    to 0 .. 255), any strides -- usually the frame the flow starts from.  occlusion: None or a (B, H, W) bool / uint8 mask,
+    nonzero = this pixel's flow is not to be trusted (it gets no vote and, filtered, takes its neighbours' motion); where:
+    None or a (B, H, W) bool / uint8 mask, nonzero = filter this pixel, the others are copied.  Each output pixel is, per
+    component, the lower weighted median of the flows in the (2 radius + 1)^2 window around it, radius in 1 .. 15, with the
+    weights exp(-distance^2 / (2 sigma_s^2)) * exp(-d2 / (2 sigma_c^2)), d2 the mean squared difference of the guide over
+    its channels (sigma_c in units of a guide scaled to 0 .. 1), zero for neighbours that are outside the image, occluded or
+    not finite; a pixel whose window holds no weight keeps its flow.  The weights are products of two integer tables
+    (refine_tables) and the sums 64-bit integers, so the result is the bits of one of the window's values and bitwise
+    reproducible; include/papof.h (papof_refine_flow_tensor) states the rule exactly.  iters > 1 repeats the pass on its own
+    output.  Returns the refined flow (B, 2, H, W) of out_dtype (float32 / float64; by default the flow's), a new tensor.
+    The defaults are the paper's (15 x 15, 7 pixels, 7 grey levels).  Enqueued on the current stream; returns without
+    waiting."""
+    radius, sigma_s, sigma_c, iters = _check_refine(radius, sigma_s, sigma_c, iters)
+    g, desc, code, occ, wh, out_dtype = _check_refine_flow(flow, guide, occlusion, where, layout, out_dtype)
+    return _refine(flow, code, g, desc, occ, wh, radius, sigma_s, sigma_c, iters, out_dtype)
+
+
+def refine_video_flows(frames, flow_fw, flow_bw, *, occlusion=None, consistency=CONSISTENCY, layout="NCHW", **refine):
+    """Both directions of a video's flows refined in one launch: frames (T, C, H, W) or (T, H, W, C) by `layout`, T >= 2,
+    flow_fw / flow_bw (T - 1, 2, H, W) and occlusion (None, or the (T - 1, 2, H, W) bool / uint8 mask) as flow_video_fb
+    returns them.  The forward flows are guided by frames[:-1] and distrust the pixels of occlusion's channel 0, the
+    backward flows by frames[1:] and channel 1; `refine`: refine_flow's radius, sigma_s, sigma_c, iters, out_dtype.
+    Returns RefinedFlows(flow_fw, flow_bw, occlusion): the refined flows (views of one tensor) and the mask recomputed from
+    them by fb_consistency(*consistency) -- None for consistency=None.  Every argument error raises before anything is
+    launched."""
+    torch = _torch()
+    unknown = set(refine) - {"radius", "sigma_s", "sigma_c", "iters", "out_dtype"}
+    if unknown:
+        raise TypeError("unknown refinement parameter %r" % sorted(unknown)[0])
+    _, a1, a2 = _alphas(consistency)
+    radius, sigma_s, sigma_c, iters = _check_refine(refine.get("radius", RADIUS), refine.get("sigma_s", SIGMA_S),
+                                                    refine.get("sigma_c", SIGMA_C), refine.get("iters", 1))
+    ts, descs, _, _ = _check_video(frames, layout, 1, None)
+    (T, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), dev)
+    occ = _check_occlusion(occlusion, (T - 1, 2, H, W), dev)
+    common = torch.promote_types(flow_fw.dtype, flow_bw.dtype)
+    out_dtype = common if refine.get("out_dtype") is None else refine["out_dtype"]
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.float32 or torch.float64, got %s" % out_dtype)
+    flows = torch.cat((flow_fw.to(common), flow_bw.to(common)))
+    guide = torch.cat((ts[0][:-1], ts[0][1:]))
+    mask = torch.cat((occ[:, 0], occ[:, 1])) if occ is not None else None
+    g, desc, code, d_occ, wh, out_dtype = _check_refine_flow(flows, guide, mask, None, layout, out_dtype)
+    out = _refine(flows, code, g, desc, d_occ, wh, radius, sigma_s, sigma_c, iters, out_dtype)
+    fw, bw = out[:T - 1], out[T - 1:]
+    return RefinedFlows(fw, bw, fb_consistency(fw, bw, a1, a2) if consistency is not None else None)
