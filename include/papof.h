@@ -925,6 +925,84 @@ long long papof_refine_workspace(int n, int height, int width, int iters);
  * PAPOF_EINVAL: radius outside 1 .. 15, sigma_s not finite or <= 0, S or R NULL. */
 int papof_refine_tables(int radius, double sigma_s, unsigned* S, unsigned* R);
 
+/* Multi-frame super-resolution along the flows (superres.hip): every pixel of every frame is carried along the chains of
+ * flows to the frames around it and deposited on a grid `scale` times finer (shift and add: Farsiu, Robinson, Elad, Milanfar
+ * 2004), the sums are resolved against a cubic upsampling of the target frame, and `iters` steps of back-projection
+ * (Irani and Peleg 1991) against the target frame alone follow.  The sensor model is the scale x scale box; there is no
+ * deconvolution of the optics' blur beyond it and no learned prior.  Per round on `stream`: the accumulator is cleared
+ * (hipMemsetAsync), k_sr_accumulate (one lane per SOURCE pixel) adds, k_sr_resolve (one lane per FINE pixel) divides,
+ * k_sr_backproject (one block per tile of low-resolution pixels) runs `iters` times.
+ * frames: n_frames = T >= 1 frames of height x width x c (H, W, C), 1 <= c <= 4, uint8 (x / 255.0), float32 (widened
+ * exactly) or float64, (frame, row, column, channel), any non-negative strides.  flow_fw, flow_bw: float32 / float64, (pair,
+ * row, column, {vx, vy}), T - 1 pairs, pair t from frame t to t + 1 and back; not read (may be NULL) when T = 1 or radius = 0.
+ * scale S: 2, 3 or 4.  out: uint8, float32 or float64, (frame, row, column, channel) of T frames of S H x S W, strides > 0.
+ * coverage: NULL, or float64 (frame, row, column) of S H x S W, strides [0..2] > 0 (stride[3] is not read).
+ * A low-resolution coordinate p and the fine-grid coordinate q of the same point: q = S * (p + 0.5) - 0.5 (pixel centres).
+ * In fp64 without fused multiply-adds, with R = radius, s2 = sigma * sigma:
+ *
+ * Accumulate.  For every source pixel (i, j) (column, row) of every frame k:
+ *     v_c = frame[k](j, i, c);   val_c = fmin(fmax(v_c, -1), 1)       (papof_splat_tensor's clamp with bound 1)
+ *     deposit(k, (i, j), 1.0)
+ *     forward:  (X, Y) = (i, j);  for n = 1 .. min(R, T - 1 - k): hop from frame k + n - 1 to k + n exactly as
+ *               papof_temporal_filter_tensor's (flow_fw[k + n - 1] sampled at (X, Y), the image test, with use_check the
+ *               test against flow_bw[k + n - 1] sampled where it lands); once dead, the chain stays dead.  If alive:
+ *                   g_c = frame[k + n] sampled at (X, Y) (sampler.h taps);  D = 0; for c: d = v_c - g_c; D += d * d;  D = D / C
+ *                   w = (use_sigma != 0 and sigma > 0) ? 1.0 / (1.0 + D / s2) : 1.0
+ *                   if w > 0 (false for NaN): deposit(k + n, (X, Y), w)
+ *     backward: the same for n = 1 .. min(R, k), hop k - n + 1 -> k - n through flow_bw[k - n], checked with flow_fw[k - n],
+ *               into the targets k - n.
+ *     deposit(t, (PX, PY), w):  QX = S * (PX + 0.5) - 0.5;  QY = S * (PY + 0.5) - 0.5;  then papof_splat_tensor's taps on
+ *         target t's fine grid:  x0 = floor(QX); y0 = floor(QY); fx = QX - x0; fy = QY - y0
+ *         for (m, n) in (0,0), (0,1), (1,0), (1,1):  fine pixel (x0 + n, y0 + m), dropped outside the S W x S H grid
+ *             b_mn = (m ? fy : 1 - fy) * (n ? fx : 1 - fx);   wb = w * b_mn;   dropped if wb == 0
+ *             den[t, pixel]    += (int64) rint(wb * 4294967296.0)
+ *             num[t, pixel, c] += (int64) rint((wb * val_c) * 4294967296.0)
+ * A fine pixel receives at most one tap of each source pixel of at most 2 R + 1 frames and every term is at most 2^32 in
+ * magnitude, so with (2 R + 1) H W < 2^30 no sum leaves int64; integer sums: the order of arrival cannot change a bit.
+ *
+ * Resolve.  For the fine pixel (x, y) of target t:  px = (x + 0.5) / S - 0.5;  py = (y + 0.5) / S - 0.5;
+ *     x0 = floor(px); tx = px - x0;  y0 = floor(py); ty = py - y0
+ *     the cubic convolution weights (Keys 1981, a = -0.5) of the taps at -1, 0, 1, 2, for f = tx (wx) and f = ty (wy):
+ *         w[0] = ((-0.5 * f + 1.0) * f - 0.5) * f;     w[1] = (1.5 * f - 2.5) * f * f + 1.0
+ *         w[2] = ((-1.5 * f + 2.0) * f + 0.5) * f;     w[3] = (0.5 * f - 0.5) * f * f
+ *     base_c = 0; for m = 0 .. 3: { row = 0; for n = 0 .. 3: row += wx[n] * frame[t](clamp(y0 - 1 + m), clamp(x0 - 1 + n), c);
+ *                                   base_c += wy[m] * row }           (indices clamped into the image)
+ *     coverage = (double) den * 2^-32
+ *     X_c = ((double) num_c * 2^-32 + prior * base_c) / (coverage + prior)
+ * prior > 0 makes every pixel defined and is the whole answer where nothing lands.
+ *
+ * Back-projection, `iters` Jacobi steps (all of X is read before any of it is replaced), per target t and channel:
+ *     per low-resolution pixel (i, j):  sum = 0; for m = 0 .. S-1: for n = 0 .. S-1: sum += X(S j + m, S i + n)
+ *                                       r(j, i) = frame[t](j, i, c) - sum / (S * S)
+ *     per fine pixel, with px, py, x0, y0, tx, ty as above and x1 = x0 + 1, y1 = y0 + 1, all four indices clamped:
+ *         top = (1 - tx) * r(y0, x0) + tx * r(y0, x1);   bot = (1 - tx) * r(y1, x0) + tx * r(y1, x1)
+ *         X' = X + ((1 - ty) * top + ty * bot)
+ * out = X stored by sampler.h's store() rule (uint8: clamp(rint(255 v), 0, 255), half to even, NaN -> 0; float32: one
+ * round-to-nearest).
+ *
+ * workspace: device memory, 8-byte aligned, owned by the caller for the duration of the enqueued work.  One target frame
+ * takes P = 8 S^2 H W ((c + 1) + (iters > 0 ? 2 c : 0)) bytes: the accumulator, int64 planes [target][c + 1][S H][S W] with
+ * den's last, and with iters > 0 the two float64 buffers [target][c][S H][S W] of X.  workspace_bytes must be at least P; the
+ * call makes the targets in rounds of G = min(T, workspace_bytes / P) -- the targets [t0, t0 + G) accumulate from the sources
+ * [t0 - R, t0 + G + R) -- with the same results for every grouping.  papof_sr_workspace returns min(T, max(1, 2^31 / P)) * P:
+ * as many target frames as fit 2 GiB, never less than one.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting;
+ * nothing of the handle's own memory is used.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (coverage aside; the flows where they are not read)
+ * or data pointer, a dtype other than those above, a negative stride, a zero stride of out or coverage, n_frames, height or
+ * width < 1, c outside 1 .. 4, scale outside 2 .. 4, radius < 0, (2 radius + 1) * height * width >= 2^30, a sigma or alpha
+ * that is not finite or negative, a prior that is not finite or below 2^-24, iters outside 0 .. 65536, a NULL or too small
+ * workspace. */
+int papof_super_resolve_tensor(papof_handle* h, int n_frames, int height, int width, int c, int scale,
+                               const papof_tensor* frames, const papof_tensor* flow_fw, const papof_tensor* flow_bw,
+                               int radius, int use_sigma, double sigma, int use_check, double alpha1, double alpha2,
+                               double prior, int iters, const papof_tensor* out, const papof_tensor* coverage,
+                               void* workspace, long long workspace_bytes, void* stream);
+
+/* Bytes of the workspace papof_super_resolve_tensor is best given (stated there); -1 where that call refuses the sizes
+ * (n_frames, height or width < 1, c outside 1 .. 4, scale outside 2 .. 4, iters outside 0 .. 65536, height * width >= 2^30). */
+long long papof_sr_workspace(int n_frames, int height, int width, int c, int scale, int iters);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

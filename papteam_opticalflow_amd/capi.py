@@ -67,6 +67,7 @@ SYMBOLS = [
     "papof_temporal_filter_tensor", "papof_fill_holes_tensor", "papof_fill_workspace", "papof_propagate_tensor",
     "papof_temporal_consistency_tensor", "papof_consistency_workspace", "papof_splat_tensor", "papof_splat_workspace",
     "papof_interp_splat_tensor", "papof_refine_flow_tensor", "papof_refine_workspace", "papof_refine_tables",
+    "papof_super_resolve_tensor", "papof_sr_workspace",
 ]
 
 
@@ -196,6 +197,11 @@ def load():
     L.papof_refine_workspace.restype = ctypes.c_longlong
     L.papof_refine_tables.argtypes = [c_int, c_double, _U, _U]
     L.papof_refine_tables.restype = c_int
+    L.papof_super_resolve_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, c_double, c_int,
+                                             c_double, c_double, c_double, c_int, _T, _T, c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_super_resolve_tensor.restype = c_int
+    L.papof_sr_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
+    L.papof_sr_workspace.restype = ctypes.c_longlong
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

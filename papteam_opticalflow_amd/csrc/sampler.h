@@ -126,6 +126,12 @@ __device__ __forceinline__ void store(const papof_tensor& t, long long o, double
         static_cast<double*>(t.data)[o] = v;
 }
 
+// One term of a scattered fixed-point sum (k_splat, k_sr_accumulate): a no-return 64-bit integer atomic add at agent scope
+// (one global_atomic_add_x2, executed at the memory side; a signed term is added as its two's-complement bits).
+__device__ __forceinline__ void add64(unsigned long long* p, long long v) {
+    (void)__hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ---- the rule of papof_interp_tensor at one output pixel, shared by k_interp (interp.hip) and by k_interp_splat
 // (splat.hip: the pixels that no splat reaches) ----
 constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of pixels per block (256 lanes: lut)

@@ -46,10 +46,6 @@ struct SplatArgs {
     double t[kMaxTimes];
 };
 
-__device__ __forceinline__ void add64(unsigned long long* p, long long v) {
-    (void)__hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles of source pixels in row-major order; blockIdx.y: item
 // `item0` + y.
 template <int FD>

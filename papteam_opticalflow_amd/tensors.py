@@ -72,6 +72,13 @@ result is bitwise reproducible.  `refine_video_flows` filters both directions of
 
     fw, bw, occ = refine_video_flows(frames, fb.flow_fw, fb.flow_bw, occlusion=fb.occlusion, layout="NHWC")
 
+Super-resolution: `super_resolve` (include/papof.h: papof_super_resolve_tensor) carries every pixel of every frame along the
+chains of flows to the frames around it and deposits it on a grid 2, 3 or 4 times finer (shift and add), resolves the sums
+against a cubic upsampling and back-projects against the frame; fixed-point integer sums, so the result is bitwise
+reproducible.  `super_resolve_video` computes the flows first (flow_video_fb).
+
+    sv = super_resolve_video(frames, 5, scale=2, layout="NHWC")   # sv.video: (T, 2 H, 2 W, C), sv.coverage (T, 2 H, 2 W)
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -1561,3 +1568,124 @@ def refine_video_flows(frames, flow_fw, flow_bw, *, occlusion=None, consistency=
     out = _refine(flows, code, g, desc, d_occ, wh, radius, sigma_s, sigma_c, iters, out_dtype)
     fw, bw = out[:T - 1], out[T - 1:]
     return RefinedFlows(fw, bw, fb_consistency(fw, bw, a1, a2) if consistency is not None else None)
+
+
+SuperResolved = collections.namedtuple("SuperResolved", "video coverage")
+SuperResolvedVideo = collections.namedtuple("SuperResolvedVideo", "video coverage flow_fw flow_bw timing")
+SCALES = (2, 3, 4)  # include/papof.h: papof_super_resolve_tensor
+MIN_PRIOR = 2.0 ** -24
+# the defaults of super_resolve: chosen in tests/test_superres_cpu.py (test_quality_estimated_flows) over a small grid
+SR_SIGMA = 0.15
+SR_PRIOR = 0.05
+SR_ITERS = 2
+
+
+def _check_sr(scale, radius, sigma, prior, iters):
+    """(scale, radius, use_sigma, sigma, prior, iters) of super_resolve's keywords -- TypeError / ValueError otherwise"""
+    for name, v in (("scale", scale), ("radius", radius), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("%s must be an int, got %r" % (name, v))
+    if scale not in SCALES:
+        raise ValueError("scale must be one of %s, got %r" % (SCALES, scale))
+    if radius < 0:
+        raise ValueError("radius must be >= 0, got %r" % radius)
+    if not 0 <= iters <= MAX_ITERS:
+        raise ValueError("iters must be in 0 .. %d, got %r" % (MAX_ITERS, iters))
+    if sigma is not None:
+        if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+            raise TypeError("sigma must be None or a number, got %r" % (sigma,))
+        if not (math.isfinite(sigma) and sigma >= 0):
+            raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
+    if isinstance(prior, bool) or not isinstance(prior, (int, float)):
+        raise TypeError("prior must be a number, got %r" % (prior,))
+    if not (math.isfinite(prior) and prior >= MIN_PRIOR):
+        raise ValueError("prior must be finite and at least 2^-24, got %r" % (prior,))
+    return scale, radius, 1 if sigma else 0, float(sigma or 0.0), float(prior), iters
+
+
+def _check_sr_flows(flow_fw, flow_bw, T, H, W, dev):
+    """the dtype codes of the flows of T frames -- for T = 1 two empty (0, 2, H, W) tensors, which are not read: None"""
+    if T > 1:
+        return _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), dev)
+    torch = _torch()
+    for name, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if not isinstance(f, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(f).__name__))
+        if f.dtype not in (torch.float32, torch.float64):
+            raise TypeError("%s must be float32 or float64, got %s" % (name, f.dtype))
+        if tuple(f.shape) != (0, 2, H, W):
+            raise ValueError("the flows must be %s for these frames, got %s" % ((0, 2, H, W), tuple(f.shape)))
+    return None
+
+
+def _check_sr_size(H, W, radius):
+    """the bound of the fixed-point sums (include/papof.h: papof_super_resolve_tensor)"""
+    if (2 * radius + 1) * H * W >= 2 ** 30:
+        raise ValueError("(2 radius + 1) H W must stay below 2^30, got radius %d and %d x %d frames" % (radius, H, W))
+
+
+def _super_resolve(ts, descs, flows, codes, scale, radius, use_sigma, sigma, alphas, prior, iters, layout, out_dtype):
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    out, d_out = _new_frames(T, scale * H, scale * W, C, layout, out_dtype, dev)
+    coverage = torch.empty((T, scale * H, scale * W), dtype=torch.float64, device=dev)
+    d_cov = _struct(coverage, (coverage.stride(0), coverage.stride(1), coverage.stride(2), 1), capi.DTYPE_F64)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)] if codes is not None else [None, None]
+    _launch(dev, "papof_super_resolve_tensor", T, H, W, C, scale, ctypes.byref(d_in), _ref(d_f[0]), _ref(d_f[1]), radius,
+            use_sigma, sigma, *alphas, prior, iters, ctypes.byref(d_out), ctypes.byref(d_cov),
+            workspace=("papof_sr_workspace", (T, H, W, C, scale, iters),
+                       "%d frames of %d x %d x %d are too large to super-resolve" % (T, H, W, C)))
+    return SuperResolved(out, coverage)
+
+
+def super_resolve(frames, flow_fw, flow_bw, scale=2, *, radius=2, sigma=SR_SIGMA, consistency=CONSISTENCY, prior=SR_PRIOR,
+                  iters=SR_ITERS, layout="NCHW", out_dtype=None):
+    """Multi-frame super-resolution of a video of T >= 1 frames along its flows (shift and add, Farsiu et al. 2004, and
+    back-projection, Irani and Peleg 1991): frames (T, C, H, W) or (T, H, W, C) by `layout`, C = 1 .. 4, uint8 (read as
+    x / 255), float32 or float64, any strides, on a HIP device; flow_fw, flow_bw (T - 1, 2, H, W) float32 / float64 on the
+    same device, pair t from frame t to t + 1 and back, as flow_video_fb returns them.  scale: 2, 3 or 4.
+    Every pixel of every frame follows its chain through the flows to the frames up to `radius` before and after it, hop
+    by hop as temporal_filter does (a chain ends where it leaves the image or -- consistency = (alpha1, alpha2); None: no
+    check -- where the reverse flow does not bring it back), and is DEPOSITED where it lands, on that frame's grid made
+    `scale` times finer (bilinearly, on the four fine pixels around the point), with the weight 1 / (1 + D / sigma^2), D the
+    mean squared difference over the channels of the pixel and the frame it lands in (sigma=None or 0: weight 1).  Each
+    frame deposits itself with weight 1.  The sums are 64-bit fixed-point integers added atomically: bitwise reproducible.
+    Each fine pixel is then (sum of the deposits + prior * the cubic upsampling of the frame) / (sum of the weights +
+    prior) -- prior >= 2^-24 keeps every pixel defined and is the whole answer where nothing lands -- and `iters` steps of
+    back-projection follow: the difference between the frame and the scale x scale block means of the result, upsampled
+    bilinearly, is added (iters=0: none).
+    What this is not: the sensor model is the scale x scale box alone, so there is no deconvolution of the optics' blur
+    beyond it, and there is no learned prior.  A video without sub-pixel motion has nothing to add: the result is then
+    close to bilinear (scale 2) or cubic (scale 3) upsampling of each frame (tests/test_superres_cpu.py).
+    Returns SuperResolved(video (T, C, scale H, scale W) or (T, scale H, scale W, C) of out_dtype -- uint8 as
+    clamp(rint(255 x), 0, 255), float32 or float64; by default the frames' dtype --, coverage (T, scale H, scale W) float64:
+    the sum of the weights that landed on each fine pixel).  include/papof.h (papof_super_resolve_tensor) states the rule
+    exactly.  The workspace comes from PyTorch's allocator; enqueued on the current stream, returns without waiting."""
+    alphas = _alphas(consistency)
+    scale, radius, use_sigma, sigma, prior, iters = _check_sr(scale, radius, sigma, prior, iters)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype, min_frames=1)
+    (T, H, W, C), _, _ = descs[0]
+    _check_sr_size(H, W, radius)
+    codes = _check_sr_flows(flow_fw, flow_bw, T, H, W, ts[0].device)
+    return _super_resolve(ts, descs, (flow_fw, flow_bw), codes, scale, radius, use_sigma, sigma, alphas, prior, iters, layout,
+                          out_dtype)
+
+
+def super_resolve_video(frames, pyramidLevels, scale=2, *, flows=None, radius=2, sigma=SR_SIGMA, consistency=CONSISTENCY,
+                        prior=SR_PRIOR, iters=SR_ITERS, layout="NCHW", out_dtype=None, **solver):
+    """A video of T >= 2 frames super-resolved along its motion: flow_video_fb(frames, pyramidLevels, layout=layout,
+    consistency=None, out_dtype=torch.float64, **solver) -- or flows = (flow_fw, flow_bw) as it returns them -- followed by
+    super_resolve on them (scale, radius, sigma, consistency, prior, iters, out_dtype).  Returns
+    SuperResolvedVideo(video, coverage, flow_fw, flow_bw, timing of the flow call (None with given flows)).  Every argument
+    error raises before anything is launched; the video is enqueued on the current stream behind the flows."""
+    alphas = _alphas(consistency)
+    scale, radius, use_sigma, sigma, prior, iters = _check_sr(scale, radius, sigma, prior, iters)
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
+    (T, H, W, C), _, _ = descs[0]
+    _check_sr_size(H, W, radius)
+    flow_fw, flow_bw, codes, timing = _given_or_run_fb(flows, ts, descs, layout, pyramidLevels, params)
+    sr = _super_resolve(ts, descs, (flow_fw, flow_bw), codes, scale, radius, use_sigma, sigma, alphas, prior, iters, layout,
+                        out_dtype)
+    return SuperResolvedVideo(sr.video, sr.coverage, flow_fw, flow_bw, timing)
