@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 115 /* 0.1.15: papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 115 /* 0.1.15: papof_match_tensor / papof_match_workspace / papof_match_densify_tensor (dense block matching of decimated uint8 frames, a start for the solver on large displacements) -- additions only, the number stays; papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -1002,6 +1002,67 @@ int papof_super_resolve_tensor(papof_handle* h, int n_frames, int height, int wi
 /* Bytes of the workspace papof_super_resolve_tensor is best given (stated there); -1 where that call refuses the sizes
  * (n_frames, height or width < 1, c outside 1 .. 4, scale outside 2 .. 4, iters outside 0 .. 65536, height * width >= 2^30). */
 long long papof_sr_workspace(int n_frames, int height, int width, int c, int scale, int iters);
+
+/* Dense block matching (match.hip): for every cell of a decimated frame A the integer displacement into frame B that
+ * minimises a sum of absolute differences over a patch -- a start (papof_flow_batch_tensor_fb_init's init) for the solver
+ * on motion that does not survive its pyramid.  It is brute force over one window: stride * search bounds the motion, the
+ * displacements are whole cells, and repetitive texture is only caught by the forward-backward test of
+ * papof_match_densify_tensor.  Everything is integer arithmetic, so the result is a pure function of the inputs.
+ * frames: uint8, float32 or float64, (frame, row, column, channel), height x width x c, c in 1 .. 4, any non-negative
+ * strides.  sequence != 0: n_pairs + 1 frames in `frames`, pair i = (frame i, frame i + 1), frames2 not read; else n_pairs
+ * frames in each of frames and frames2, pair i = (frames[i], frames2[i]).
+ * Quantise.  A uint8 sample is taken as it is; a float32 (widened exactly) or float64 sample x becomes
+ *     rint(255.0 * x) clamped to 0 .. 255 (half to even), NaN -> 0.            Channels c .. 3 are 0.
+ * Decimate.  stride S in {1, 2, 4, 8}; the grid is h = height / S, w = width / S (integer division: the trailing rows and
+ * columns are dropped); per channel the coarse pixel (y, x) = (sum of the S x S samples from (S y, S x) + S * S / 2) / (S * S)
+ * in integers.  Each frame is decimated once (k_match_prepare), one packed dword per coarse pixel in the workspace.
+ * Cost.  With P = patch, for the coarse pixel p = (x, y) of A and the displacement d = (dx, dy), |dx|, |dy| <= search:
+ *     cost(p, d) = sum over ox, oy in -P .. P and over the channels of
+ *                      | A(clamp(y + oy, h), clamp(x + ox, w)) - B(clamp(y + oy + dy, h), clamp(x + ox + dx, w)) |
+ *                  + penalty * (|dx| + |dy|)                                   clamp(v, n) = min(max(v, 0), n - 1)
+ * d is admissible iff 0 <= x + dx < w and 0 <= y + dy < h (d = 0 always is).
+ * Argmin.  The match is the admissible d with the smallest key (cost, dx * dx + dy * dy, dy, dx), compared
+ * lexicographically: among equal costs the shortest, then the smallest dy, then the smallest dx.
+ * patch in 1 .. 7, search in 1 .. 32, penalty in 0 .. 65535: a cost stays below 2^24, exact in float32.
+ * Items: n_pairs forward (A the pair's first frame), then with both != 0 n_pairs backward (A the second, B the first).
+ * disp: float32 / float64, (item, row, column, {dx, dy}) of h x w, holding S * d -- full-resolution pixels, exact integers;
+ * cost: float32 / float64, (item, row, column, -) of h x w, the match's cost; strides positive (cost's stride[3] is not read).
+ * workspace: device memory, 4-byte aligned, owned by the caller for the duration of the enqueued work;
+ * papof_match_workspace gives its bytes.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the
+ * null stream; k_match_prepare per frame tensor, then k_match: one block per 32 x 8 tile of cells and item) and returns
+ * without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (frames2 in sequence mode aside) or data pointer, a
+ * dtype other than those above, a negative stride or a zero stride of disp or cost, n_pairs < 1, stride not 1, 2, 4 or 8,
+ * height or width < stride, height * width >= 2^30, c outside 1 .. 4, patch outside 1 .. 7, search outside 1 .. 32, penalty
+ * outside 0 .. 65535, a NULL, misaligned or too small workspace. */
+int papof_match_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2,
+                       int height, int width, int c, int stride, int patch, int search, int penalty, int both,
+                       const papof_tensor* disp, const papof_tensor* cost, void* workspace, long long workspace_bytes,
+                       void* stream);
+
+/* Bytes of papof_match_tensor's workspace: 4 (height / stride) (width / stride) per frame, n_pairs + 1 frames in sequence
+ * mode and 2 n_pairs otherwise; -1 where that call refuses the sizes. */
+long long papof_match_workspace(int n_pairs, int sequence, int height, int width, int stride);
+
+/* A full-resolution initial flow and its hole mask from matched displacements (k_match_densify, one lane per pixel).
+ * disp, disp_rev: float32 / float64, (item, row, column, {dx, dy}) on the h x w grid of papof_match_tensor (h = height /
+ * stride, w = width / stride), in full-resolution pixels: the field to densify and the field of the opposite direction.
+ * cost: float32 / float64 (item, row, column, -), read only if max_cost >= 0 (else it may be NULL).
+ * In fp64, for the cell p = (x, y) of item i:  dx = disp_x(p) / stride, dy = disp_y(p) / stride;  p is RELIABLE iff
+ *     dx and dy are whole numbers, q = (x + dx, y + dy) lies on the grid (false for a NaN),
+ *     |dx + disp_rev_x(q) / stride| <= tol and |dy + disp_rev_y(q) / stride| <= tol   (false for a NaN),
+ *     and, if max_cost >= 0, cost(p) <= max_cost.
+ * The pixel (X, Y) of the height x width frame belongs to the cell (min(X / stride, w - 1), min(Y / stride, h - 1)) -- the
+ * dropped trailing rows and columns take their nearest cell.  flow: float64 (item, row, column, {vx, vy}), the cell's disp
+ * where reliable and 0.0 elsewhere; mask: uint8 (item, row, column, -), 0 where reliable and 1 elsewhere: the hole mask
+ * that papof_fill_holes_tensor takes.  Strides of flow and mask positive (the mask's stride[3] is not read).
+ * Enqueued on `stream` and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (cost with max_cost < 0 aside) or data pointer, a
+ * dtype other than those above, a negative stride or a zero stride of flow or mask, n < 1, stride not 1, 2, 4 or 8, height
+ * or width < stride, height * width >= 2^30, tol outside 0 .. 64, max_cost NaN. */
+int papof_match_densify_tensor(papof_handle* h, int n, int height, int width, int stride, const papof_tensor* disp,
+                               const papof_tensor* disp_rev, const papof_tensor* cost, int tol, double max_cost,
+                               const papof_tensor* flow, const papof_tensor* mask, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

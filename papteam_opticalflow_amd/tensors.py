@@ -79,6 +79,14 @@ reproducible.  `super_resolve_video` computes the flows first (flow_video_fb).
 
     sv = super_resolve_video(frames, 5, scale=2, layout="NHWC")   # sv.video: (T, 2 H, 2 W, C), sv.coverage (T, 2 H, 2 W)
 
+Large displacements: `match_pairs` / `match_video` (include/papof.h: papof_match_tensor) find, for every cell of a
+decimated frame, the integer displacement that minimises a sum of absolute differences over a patch (brute force over one
+window, integer arithmetic, bitwise reproducible); `match_init` (papof_match_densify_tensor) keeps the cells that pass a
+forward-backward test and fills the rest (fill_holes); `flow_pairs_ld` / `flow_video_ld` start flow_pairs_fb from the result,
+which brings motion larger than the objects that carry it within the solver's reach.
+
+    fb = flow_video_ld(frames, layout="NHWC")   # a FlowFB, as flow_video_fb's
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -1689,3 +1697,232 @@ def super_resolve_video(frames, pyramidLevels, scale=2, *, flows=None, radius=2,
     sr = _super_resolve(ts, descs, (flow_fw, flow_bw), codes, scale, radius, use_sigma, sigma, alphas, prior, iters, layout,
                         out_dtype)
     return SuperResolvedVideo(sr.video, sr.coverage, flow_fw, flow_bw, timing)
+
+
+STRIDES = (1, 2, 4, 8)  # include/papof.h: papof_match_tensor
+MAX_PATCH = 7
+MAX_SEARCH = 32
+MAX_PENALTY = 65535
+MAX_TOL = 2 * MAX_SEARCH
+MATCH_STRIDE = 2
+MATCH_PATCH = 3
+MATCH_SEARCH = 20
+
+Matches = collections.namedtuple("Matches", "disp_fw disp_bw cost_fw cost_bw")
+MatchInit = collections.namedtuple("MatchInit", "init_fw init_bw reliable")
+
+
+def _int_in(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise ValueError("%s must be an integer in %d .. %d, got %r" % (name, lo, hi, v))
+    return v
+
+
+def _check_match(stride, patch, search, penalty):
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride not in STRIDES:
+        raise ValueError("stride must be one of %s, got %r" % (STRIDES, stride))
+    return (stride, _int_in("patch", patch, 1, MAX_PATCH), _int_in("search", search, 1, MAX_SEARCH),
+            _int_in("penalty", penalty, 0, MAX_PENALTY))
+
+
+def _check_densify(tol, max_cost):
+    """(tol, max_cost as the C ABI's double: -1.0 for None)"""
+    tol = _int_in("tol", tol, 0, MAX_TOL)
+    if max_cost is None:
+        return tol, -1.0
+    if isinstance(max_cost, bool) or not isinstance(max_cost, (int, float)) or not max_cost >= 0:
+        raise ValueError("max_cost must be None or a number >= 0, got %r" % (max_cost,))
+    return tol, float(max_cost)
+
+
+def _check_match_frames(named, layout, out_dtype, levels, stride, min_frames=1, solver=None):
+    """the frames of the matching calls: _check's results for 1 .. MAX_CHANNELS channels and frames of at least one cell"""
+    ts, descs, out_dtype, params = _check(named, layout, out_dtype, levels, min_frames=min_frames, solver=solver)
+    _, H, W, C = descs[0][0]
+    if C > MAX_CHANNELS:
+        raise ValueError("%s must have 1 .. %d channels, got %d (layout %s)" % (named[0][0], MAX_CHANNELS, C, layout))
+    if H < stride or W < stride:
+        raise ValueError("frames of %d x %d are smaller than one cell of stride %d" % (H, W, stride))
+    return ts, descs, out_dtype, params
+
+
+def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, out_dtype):
+    """papof_match_tensor on the current stream of the frames' device"""
+    torch = _torch()
+    (_, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    h, w, n = H // stride, W // stride, n_pairs * (2 if both else 1)
+    disp = torch.empty((n, 2, h, w), dtype=out_dtype, device=dev)
+    cost = torch.empty((n, h, w), dtype=out_dtype, device=dev)
+    code = _out_code(out_dtype)
+    d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
+    d_disp = _flow_struct(disp, code)
+    d_cost = _struct(cost, (cost.stride(0), cost.stride(1), cost.stride(2), 0), code)
+    _launch(dev, "papof_match_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+            None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, patch, search, penalty, 1 if both else 0,
+            ctypes.byref(d_disp), ctypes.byref(d_cost),
+            workspace=("papof_match_workspace", (n_pairs, 1 if sequence else 0, H, W, stride),
+                       "%d pairs of %d x %d are too large to match" % (n_pairs, H, W)))
+    if both:
+        return Matches(disp[:n_pairs], disp[n_pairs:], cost[:n_pairs], cost[n_pairs:])
+    return Matches(disp, None, cost, None)
+
+
+def match_pairs(im1, im2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
+                out_dtype=None):
+    """Dense block matching of the independent pairs (im1[i], im2[i]): two tensors of one shape, (B, C, H, W) or
+    (B, H, W, C) by `layout`, C = 1 .. 4, uint8, float32 or float64 (quantised to uint8 as rint(255 x)), any strides, on a HIP
+    device.  Each frame is box-decimated by `stride` (1, 2, 4 or 8) to h x w = H // stride x W // stride cells; every cell of
+    im1 gets the displacement d, |dx|, |dy| <= `search` (1 .. 32) cells, into im2 that minimises the sum of absolute
+    differences over the (2 patch + 1)^2 window (patch 1 .. 7) and the channels, plus penalty * (|dx| + |dy|) (0 .. 65535);
+    ties go to the shortest d, then the smallest dy, then dx.  include/papof.h (papof_match_tensor) states the rule exactly;
+    it is integer arithmetic, so the result is bitwise reproducible.
+    Returns Matches(disp_fw, disp_bw (B, 2, h, w): stride * d in full-resolution pixels, cost_fw, cost_bw (B, h, w)) of
+    out_dtype (float64, or float32: both hold the integers exactly); the backward fields (im2 -> im1) are None for
+    both=False.  The forward and backward fields are views of one tensor.
+    This is a START for the solver (match_init, flow_pairs_ld), not a flow: whole cells only, no hierarchy -- motion beyond
+    stride * search is not found -- and on repetitive texture only match_init's forward-backward test tells a wrong match.
+    The workspace comes from PyTorch's allocator; enqueued on the current stream, returns without waiting."""
+    stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
+    ts, descs, out_dtype, _ = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, 1, stride)
+    return _match(ts, descs, False, descs[0][0][0], stride, patch, search, penalty, bool(both), out_dtype)
+
+
+def match_video(frames, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
+                out_dtype=None):
+    """match_pairs on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames, each frame decimated once: T - 1
+    pairs."""
+    stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
+    ts, descs, out_dtype, _ = _check_match_frames([("frames", frames)], layout, out_dtype, 1, stride, min_frames=2)
+    return _match(ts, descs, True, descs[0][0][0] - 1, stride, patch, search, penalty, bool(both), out_dtype)
+
+
+def _check_size(size, h, w):
+    """(H, W, stride) of match_init's `size` for fields of h x w cells -- ValueError / TypeError otherwise"""
+    try:
+        H, W = size
+    except (TypeError, ValueError):
+        raise TypeError("size must be (H, W), got %r" % (size,)) from None
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in (H, W)):
+        raise ValueError("size must be two integers >= 1, got %r" % (size,))
+    for s in STRIDES:
+        if (H // s, W // s) == (h, w):
+            return H, W, s
+    raise ValueError("fields of %d x %d cells belong to no stride of %s for frames of %d x %d" % (h, w, STRIDES, H, W))
+
+
+def _check_cost(name, cost, shape, dev):
+    torch = _torch()
+    if not isinstance(cost, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(cost).__name__))
+    if cost.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s must be float32 or float64, got %s" % (name, cost.dtype))
+    if tuple(cost.shape) != shape:
+        raise ValueError("%s must be (B, h, w) = %s, got %s" % (name, shape, tuple(cost.shape)))
+    if cost.device != dev:
+        raise ValueError("%s is on %s, the displacements on %s: all must be on one device" % (name, cost.device, dev))
+    return capi.DTYPE_F32 if cost.dtype == torch.float32 else capi.DTYPE_F64
+
+
+def _check_fields(disp_fw, disp_bw, cost_fw, cost_bw, size, need_cost):
+    """every argument error of match_init's tensors: (H, W, stride, the displacements' codes, the costs' codes or None)"""
+    codes = tuple(_check_flow(n, f) for n, f in (("disp_fw", disp_fw), ("disp_bw", disp_bw)))
+    if disp_fw.shape != disp_bw.shape:
+        raise ValueError("disp_fw %s and disp_bw %s differ in shape" % (tuple(disp_fw.shape), tuple(disp_bw.shape)))
+    if disp_fw.device != disp_bw.device:
+        raise ValueError("disp_fw is on %s, disp_bw on %s: both must be on one device" % (disp_fw.device, disp_bw.device))
+    if not _on_gpu(disp_fw):
+        raise ValueError("displacements must be on a HIP device (cuda:N), got %s" % disp_fw.device)
+    B, _, h, w = (int(x) for x in disp_fw.shape)
+    H, W, stride = _check_size(size, h, w)
+    c_codes = None
+    if need_cost or cost_fw is not None or cost_bw is not None:
+        c_codes = tuple(_check_cost(n, c, (B, h, w), disp_fw.device) for n, c in (("cost_fw", cost_fw), ("cost_bw", cost_bw)))
+    return H, W, stride, codes, c_codes
+
+
+def _densify(disps, codes, costs, c_codes, H, W, stride, tol, max_cost):
+    """papof_match_densify_tensor of both directions: (flow (2 B, 2, H, W) float64, hole mask (2 B, H, W) uint8), the B
+    forward items first"""
+    torch = _torch()
+    B, dev = int(disps[0].shape[0]), disps[0].device
+    flow = torch.empty((2 * B, 2, H, W), dtype=torch.float64, device=dev)
+    mask = torch.empty((2 * B, H, W), dtype=torch.uint8, device=dev)
+    d = [_flow_struct(f, c) for f, c in zip(disps, codes)]
+    for k in (0, 1):
+        d_cost = None
+        if max_cost >= 0:
+            c = costs[k]
+            d_cost = _struct(c, (c.stride(0), c.stride(1), c.stride(2), 0), c_codes[k])
+        part, part_mask = flow[k * B:(k + 1) * B], mask[k * B:(k + 1) * B]
+        d_flow, d_mask = _flow_struct(part, capi.DTYPE_F64), _mask_struct(part_mask)
+        _launch(dev, "papof_match_densify_tensor", B, H, W, stride, ctypes.byref(d[k]), ctypes.byref(d[1 - k]), _ref(d_cost), tol,
+                max_cost, ctypes.byref(d_flow), ctypes.byref(d_mask))
+    return flow, mask
+
+
+def _match_init(disps, codes, costs, c_codes, H, W, stride, tol, max_cost, relax):
+    """both directions densified, then ONE papof_fill_holes_tensor chain over the unreliable pixels of both"""
+    torch = _torch()
+    B = int(disps[0].shape[0])
+    flow, mask = _densify(disps, codes, costs, c_codes, H, W, stride, tol, max_cost)
+    init = _fill(flow, descriptor(flow, "NCHW"), mask, relax, "NCHW", torch.float64)
+    reliable = (mask == 0).view(2, B, H, W).permute(1, 0, 2, 3)
+    return MatchInit(init[:B], init[B:], reliable)
+
+
+def match_init(disp_fw, disp_bw, cost_fw, cost_bw, size, *, tol=1, max_cost=None, relax=RELAX):
+    """The initial flows of flow_pairs_fb from matched displacements: disp_fw, disp_bw (B, 2, h, w) and cost_fw, cost_bw
+    (B, h, w) as match_pairs / match_video return them (float32 / float64 on one HIP device; the costs may be None with
+    max_cost=None), size = (H, W) of the frames (the stride follows from it).  A cell p is reliable iff its displacement d
+    lands on the grid and the opposite field brings it back: |d(p) + d_rev(p + d(p))| <= tol cells in both components
+    (tol 0 .. 64) -- and, with max_cost, its cost is at most max_cost.  Every cell is replicated over its stride^2 pixels
+    (the trailing rows and columns that the decimation dropped take their nearest cell) and the unreliable pixels are
+    filled from the reliable ones by fill_holes (relax).  include/papof.h (papof_match_densify_tensor) states the rule.
+    Returns MatchInit(init_fw, init_bw (B, 2, H, W) float64, reliable (B, 2, H, W) torch.bool: channel 0 the forward
+    pixels, 1 the backward ones).  Enqueued on the current stream; returns without waiting."""
+    tol, max_cost = _check_densify(tol, max_cost)
+    relax = _check_relax(relax)
+    H, W, stride, codes, c_codes = _check_fields(disp_fw, disp_bw, cost_fw, cost_bw, size, max_cost >= 0)
+    return _match_init((disp_fw, disp_bw), codes, (cost_fw, cost_bw), c_codes, H, W, stride, tol, max_cost, relax)
+
+
+def _run_ld(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, match, densify):
+    torch = _torch()
+    (_, H, W, _), _, _ = descs[0]
+    m = _match(ts, descs, sequence, n_pairs, *match, True, torch.float32)
+    code = (capi.DTYPE_F32, capi.DTYPE_F32)
+    init = _match_init((m.disp_fw, m.disp_bw), code, (m.cost_fw, m.cost_bw), code, H, W, match[0], *densify)
+    return _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, init.init_fw, init.init_bw)
+
+
+def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
+                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """Large-displacement flow of the independent pairs (im1[i], im2[i]): match_pairs (stride, patch, search, penalty),
+    match_init (tol, max_cost, relax) and flow_pairs_fb(im1, im2, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw,
+    ...) -- bit for bit what that call returns given match_init's flows, as FlowFB, so every call built on the flows takes
+    the result as it is.  The matcher brings motion of up to stride * search pixels (40 by default) within the solver's
+    reach, objects smaller than their displacement included, which no number of pyramid levels does; the solver then needs
+    few levels (2 by default: the prior is accurate to a cell).  Frames of C = 1 .. 4 channels.  When NOT to use it: on
+    ordinary video (motion of a few pixels) the cold flow_pairs_fb with 5 levels is as good and the matching is wasted
+    work; the displacements are whole cells and only a start; there is no hierarchical search, so motion beyond
+    stride * search is missed as before; and a wrong match on repetitive texture is only caught where the forward-backward
+    test fails.  Every argument error raises before anything is launched."""
+    alphas = _alphas(consistency)
+    match = _check_match(stride, patch, search, penalty)
+    densify = (*_check_densify(tol, max_cost), _check_relax(relax))
+    ts, descs, out_dtype, params = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, match[0],
+                                                       solver=solver)
+    return _run_ld(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, params, match, densify)
+
+
+def flow_video_ld(frames, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
+                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """flow_pairs_ld on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames: match_video, match_init and
+    flow_video_fb(frames, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw, ...)."""
+    alphas = _alphas(consistency)
+    match = _check_match(stride, patch, search, penalty)
+    densify = (*_check_densify(tol, max_cost), _check_relax(relax))
+    ts, descs, out_dtype, params = _check_match_frames([("frames", frames)], layout, out_dtype, pyramidLevels, match[0],
+                                                       min_frames=2, solver=solver)
+    return _run_ld(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, match, densify)
