@@ -240,13 +240,13 @@ struct papof_handle {
     int sor_group = 0;               // consecutive sweeps of a band per workgroup: 1, 2 or 4; 0 = by problem size
     int rb_depth = 0;                // blocked red-black / Jacobi solver: half-sweeps per launch; 0 = by region shape
     int rb_shape = 0;                // ... region shape 1..4 (sor.hip: blocked_shape); 0 = by plane size
-    int rb_naive = 0;                // 1: one launch per half-sweep on the planes (cross-check)
     int sor_resident = 0;            // tasks per launch of the exact-order kernels; 0 = 8 per CU (sor.hip: resident_tasks)
     int sor_skip_dead = 1;           // k_sor_exact: lanes whose row lies outside the image neither load nor store (PAPOF_SOR_DEAD=0: A/B)
     unsigned* sor_prog_next = nullptr;  // cleared progress counters for the NEXT sor_solve() (else it clears its own)
     int sor_launches = 0;            // exact-order solver kernels launched by the current / last call (measurement: bench.py)
     // one entry per sor_solve() of the current / last call, in stream order (measurement: bench.py's roofline.by_level);
-    // kind: 0 k_sor_exact, 1 k_sor_fused, 2 k_sor_group, 3 k_sor_blocked red-black, 4 k_sor_blocked Jacobi, 5 naive kernels;
+    // kind: 0 k_sor_exact, 1 k_sor_fused, 2 k_sor_group, 3 k_sor_blocked red-black, 4 k_sor_blocked Jacobi, 6 k_sor_tiny
+    // (5 is retired and stays unused: bench.py reads these numbers);
     // sec: the solver kernels' own HIP-event time (filled when the call's timers are collected, else 0)
     struct SorSolveLog {
         int H, W, n_sor, kind, depth, launches;
@@ -423,8 +423,6 @@ struct SorBatch {
 };
 int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor, int mode,
               const SorBatch* bt = nullptr);
-int sor_redblack_halfsweep(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int colour,
-                           const Rect& r);
 int sor_blocked_depth(const papof_handle* h, int mode, int H, int W);  // half-sweeps per launch the blocked solver uses
 int sor_blocked_launch(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int mode, int g,
                        int hs0, const Rect& out, const double* su, const double* sv, double* du, double* dv);
@@ -441,7 +439,7 @@ struct SorSplit {
     bool top_cut, bot_cut;
 };
 int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor,
-                    unsigned* prog, int b0, int b1, const SorSplit* split = nullptr, int k0 = 0, int k1 = -1);  // sweeps k0 .. k1-1 (split only)
+                    unsigned* prog, int b0, int b1, const SorSplit* split = nullptr);
 int sor_bind_plain(papof_handle* h, SorPlanes& sp, int H, int W, int n_sor);
 bool sor_tiny_fits(const papof_handle* h, int H, int W, int n_sor);
 constexpr size_t kTinyMaxCells = 8192;  // upper bound of what sor_tiny_fits() accepts (registers of one workgroup)

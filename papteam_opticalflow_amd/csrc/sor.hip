@@ -54,8 +54,7 @@
 //
 // PAPOF_SOR_REDBLACK / PAPOF_SOR_JACOBI -- throughput and correctness-gate modes whose results differ from the
 //   reference's order.  One LDS-tiled, temporally blocked kernel (k_sor_blocked, documented where it is
-//   defined): a workgroup keeps a region of the row-major planes on chip for ~10 half-sweeps per launch.  The first
-//   implementation -- one launch per half-sweep / sweep straight on the planes -- is kept as a cross-check (PAPOF_RB_NAIVE).
+//   defined): a workgroup keeps a region of the row-major planes on chip for ~10 half-sweeps per launch.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -170,44 +169,6 @@ __global__ void k_xlane_probe(int* out) {  // out[0..63] = from_above, out[64..1
     const double v = (double)(lane + 1);
     out[lane] = (int)from_above<true>(v);
     out[64 + lane] = (int)from_below<true>(v);
-}
-
-// Diagnostic (PAPOF_PROBE=1 at handle creation): cost of the per-step arithmetic alone, one wave, no memory.
-// out[0] = s_memtime ticks, out[1] = s_memrealtime ticks (100 MHz) for `n` steps.
-__global__ __launch_bounds__(1024) void k_alu_probe(unsigned long long* out, double* sink, int n, double seed) {
-    double duL = seed, dvL = seed * 0.5, phiL = 0.7, duC = 0.1, dvC = 0.2;
-    const double phiC = 0.9, xy = 0.01, a1 = 0.3, a2 = 0.4, b1 = 0.001, b2 = 0.002, nalpha = -0.012, om1 = -0.8;
-    double duR = 0.05 * seed, dvR = 0.06 * seed;
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-    for (int i = 0; i < n; i++) {
-        const double duU = from_above<true>(duL), dvU = from_above<true>(dvL), phiU = from_above<true>(phiL);
-        const double duD = from_below<true>(duR), dvD = from_below<true>(dvR);
-        double s1 = phiL * duL, s2 = phiL * dvL;
-        s1 += phiC * duR;
-        s2 += phiC * dvR;
-        s1 += phiU * duU;
-        s2 += phiU * dvU;
-        s1 += phiC * duD;
-        s2 += phiC * dvD;
-        s1 *= nalpha;
-        s2 *= nalpha;
-        s1 += xy * dvC;
-        const double duN = om1 * duC + a1 * (b1 - s1);
-        s2 += xy * duN;
-        const double dvN = om1 * dvC + a2 * (b2 - s2);
-        duL = duN;
-        dvL = dvN;
-        duC = duR;
-        dvC = dvR;
-        duR = duR * 0.999;
-        dvR = dvR * 0.999;
-    }
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-    if (threadIdx.x == 0) {
-        out[0] = t1 - t0;
-        out[1] = r1 - r0;
-    }
-    sink[threadIdx.x] = duL + dvL;
 }
 
 // ---- 16-byte accesses through buffer descriptors (one SGPR quad per paired plane) -------------------------
@@ -1293,77 +1254,14 @@ __global__ __launch_bounds__(64 * M) void k_sor_group(GroupArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// row-major modes
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void cell_update(const double* __restrict__ phi, const double* __restrict__ xy,
-                                            const double* __restrict__ a1, const double* __restrict__ a2,
-                                            const double* __restrict__ b1, const double* __restrict__ b2,
-                                            const double* ru, const double* rv, double* wu, double* wv, int i, int j,
-                                            int H, int W, double nalpha, double om1) {
-    const size_t o = (size_t)i * W + j;
-    const double pc = phi[o];
-    double s1 = 0.0, s2 = 0.0;
-    if (j > 0) {
-        const double w = phi[o - 1];
-        s1 += w * ru[o - 1];
-        s2 += w * rv[o - 1];
-    }
-    if (j < W - 1) {
-        s1 += pc * ru[o + 1];
-        s2 += pc * rv[o + 1];
-    }
-    if (i > 0) {
-        const double w = phi[o - W];
-        s1 += w * ru[o - W];
-        s2 += w * rv[o - W];
-    }
-    if (i < H - 1) {
-        s1 += pc * ru[o + W];
-        s2 += pc * rv[o + W];
-    }
-    s1 *= nalpha;
-    s2 *= nalpha;
-    s1 += xy[o] * rv[o];
-    const double nu = om1 * ru[o] + a1[o] * (b1[o] - s1);
-    s2 += xy[o] * nu;
-    const double nv = om1 * rv[o] + a2[o] * (b2[o] - s2);
-    wu[o] = nu;
-    wv[o] = nv;
-}
-
-// one colour of a red-black sweep: thread t of a row handles column 2t + ((i + colour) & 1)
-__global__ void k_sor_redblack(const double* __restrict__ phi, const double* __restrict__ xy,
-                               const double* __restrict__ a1, const double* __restrict__ a2,
-                               const double* __restrict__ b1, const double* __restrict__ b2, double* du, double* dv,
-                               int H, int W, double nalpha, double om1, int colour, Rect rc) {
-    const int i = rc.y0 + blockIdx.y * 4 + threadIdx.y;
-    if (i >= rc.y1) return;
-    // cells with (i + j) % 2 == colour; the class of a cell does not depend on the region it is visited in
-    const int j = rc.x0 + 2 * (blockIdx.x * 64 + threadIdx.x) + ((i + rc.x0 + colour) & 1);
-    if (j >= rc.x1) return;
-    cell_update(phi, xy, a1, a2, b1, b2, du, dv, du, dv, i, j, H, W, nalpha, om1);
-}
-
-__global__ void k_sor_jacobi(const double* __restrict__ phi, const double* __restrict__ xy,
-                             const double* __restrict__ a1, const double* __restrict__ a2,
-                             const double* __restrict__ b1, const double* __restrict__ b2,
-                             const double* __restrict__ ru, const double* __restrict__ rv, double* __restrict__ wu,
-                             double* __restrict__ wv, int H, int W, double nalpha, double om1) {
-    const int i = blockIdx.y * 4 + threadIdx.y, j = blockIdx.x * 64 + threadIdx.x;
-    if (i >= H || j >= W) return;
-    cell_update(phi, xy, a1, a2, b1, b2, ru, rv, wu, wv, i, j, H, W, nalpha, om1);
-}
-
-
-// ------------------------------------------------------------------------------------------------
 // LDS-TILED, TEMPORALLY BLOCKED red-black / Jacobi solver (the kernel behind PAPOF_SOR_REDBLACK / _JACOBI and behind
-// the multi-GPU tiles).  Same per-cell arithmetic as cell_update() above (src/OpticalFlow.cpp:458-505), other sweep order.
+// the multi-GPU tiles), on row-major planes.  The reference's per-cell arithmetic (src/OpticalFlow.cpp:458-505), other sweep order.
 //
 // A workgroup owns a REGION of 128 x (NW * RPT) cells = its core tile grown by a ghost ring `g` deep, keeps it on chip
 // and runs g half-sweeps (Jacobi: g sweeps) on it in ONE launch: half-sweep m is exact on the region shrunk by m + 1
 // cells from every edge that is not an image border (a cell one ring further out misses a neighbour one step earlier --
 // the same ghost-zone algebra tiles.hip uses between GPUs), so after g half-sweeps the core tile is exact and is the
-// only part written back.  The six coefficient planes are read ONCE per g half-sweeps (the naive kernels read them once
+// only part written back.  The six coefficient planes are read ONCE per g half-sweeps (a launch per half-sweep reads them once
 // per half-sweep) with full-line coalesced row loads (16 bytes per lane where rows are 16-byte aligned), never with
 // stride 2; a 30-sweep solve is ceil(60 / g) launches instead of 60.
 //   * ownership: lane t of wave w owns columns 2t, 2t+1 of the RPT rows w*RPT .. w*RPT+RPT-1 of the region: one cell of
@@ -1812,19 +1710,6 @@ __global__ __launch_bounds__(NW * 64) void k_sor_tiny(TinyArgs A_in) {
 
 }  // namespace
 
-// One colour of a red-black sweep on a region of the (row-major) operand planes.  The whole plane on one GPU; a tile
-// grown by its remaining ghost depth when a frame is sharded (tiles.hip).
-int sor_redblack_halfsweep(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int colour,
-                           const Rect& r) {
-    if (sp.skew) return PAPOF_EINVAL;
-    if (r.empty()) return PAPOF_OK;
-    const dim3 grid(((r.w() + 1) / 2 + 63) / 64, (r.h() + 3) / 4), block(64, 4);
-    hipLaunchKernelGGL(k_sor_redblack, grid, block, 0, h->stream, sp.phi, sp.xy, sp.a1, sp.a2, sp.b1, sp.b2, sp.du,
-                       sp.dv, H, W, -alpha, 1 - omega, colour, r);
-    PAPOF_HIP(hipGetLastError());
-    return PAPOF_OK;
-}
-
 // Tasks (waves) of the exact-order kernels that one launch may hold.  A task spins on progress counters written by tasks
 // of lower block index, which is deadlock-free only while every task of the launch is resident or the hardware
 // dispatches blocks in index order -- observed behaviour, not a HIP guarantee.  So a launch never exceeds what the chip
@@ -1955,24 +1840,21 @@ struct TinyShape {
     int waves;  // waves this plane needs: ceil(rows x lanes per row / 64)
 };
 static bool tiny_shape(int H, int W, int K, TinyShape& best) {
-    // Narrow tiles on many waves win while the lanes fit (tools/tiny_sweep.py on MI355X, profiles/r03_tiny_sweep.txt: e.g.
+    // Narrow tiles on many waves win while the lanes fit (measured on MI355X, profiles/r03_tiny_sweep.txt: e.g.
     // 60x33 x 66 sweeps 91 / 97 / 104 / 113 / 124 / 177 us at C = 1 / 2 / 3 / 4 / 6 / 8): the narrowest shape that holds the
     // plane is taken.  Tiles of 14 cells (the only shape that holds ~6.5 k cells) run as long as the task pipeline does
     // (108x60 x 60 sweeps: 249 us either way) and are left to it.
     static const TinyShape cand[] = {{1, 16, 0}, {2, 16, 0}, {3, 12, 0}, {4, 8, 0}, {5, 8, 0}, {6, 8, 0}, {8, 4, 0}, {10, 4, 0}};
-    static const int force_c = std::getenv("PAPOF_TINY_C") ? std::atoi(std::getenv("PAPOF_TINY_C")) : 0;  // A/B: force C where it fits
     (void)K;
-    bool found = false;
     for (TinyShape t : cand) {
         const int Q = (W + t.c - 1) / t.c, QP = (Q + 1) / 2;
         if ((long long)H * QP > t.nw * 64) continue;
         if ((size_t)(H + 2) * 2 * t.c * (QP + 2) * 16 > (size_t)150 * 1024) continue;  // LDS: the framed plane of 16-byte cells
         t.waves = (H * QP + 63) / 64;
-        if (!found || force_c == t.c) best = t;
-        found = true;
-        if (force_c <= 0) break;
+        best = t;
+        return true;
     }
-    return found;
+    return false;
 }
 
 // May a height x width plane be solved in exact order by k_sor_tiny?  (PAPOF_SOR_TINY=0 switches the path off: A/B)
@@ -2093,14 +1975,9 @@ int sor_plan(const papof_handle* h, int H, int W, int n_sor, int mode, int* laun
         nl = (units + chunk - 1) / chunk;
         d = sd.fuse == 2 ? 2 : sd.group;
     } else if (mode == PAPOF_SOR_REDBLACK || mode == PAPOF_SOR_JACOBI) {
-        if (h->rb_naive) {
-            nl = mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor;
-            d = 1;
-        } else {
-            const BlockedPlan bp = blocked_plan(h, mode, H, W, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor);
-            nl = bp.n_launch;
-            d = bp.q * (bp.base + (bp.rem ? 1 : 0));
-        }
+        const BlockedPlan bp = blocked_plan(h, mode, H, W, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor);
+        nl = bp.n_launch;
+        d = bp.q * (bp.base + (bp.rem ? 1 : 0));
     } else {
         return PAPOF_EINVAL;
     }
@@ -2200,20 +2077,14 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
         // The (du, dv) planes.  The grouped kernel reads du = dv = 0 before the first sweep (src/OpticalFlow.cpp:452-453) and
         // its halo rows from memory.  k_sor_exact / k_sor_fused read those zeros as out-of-range offsets and write every
         // position 1 .. n_iter * R of a plane before anybody reads it, so all they NEED cleared are the tail positions
-        // that ghost lanes read up to 65 steps ahead and nobody writes (PAPOF_SOR_CLEAR=tail: one strided memset).  Yet
-        // clearing both planes entirely is what is done by default, because it is FASTER, its own cost included: the
+        // that ghost lanes read up to 65 steps ahead and nobody writes (one strided memset would do).  Yet
+        // clearing both planes entirely is what is done, because it is FASTER, its own cost included: the
         // memset leaves the planes resident in the Infinity Cache, and every level's solve then runs 4-5 % faster
         // (1920x1080: 0.941 -> 0.900 ms, 607x341: 0.354 -> 0.338 ms, a whole 1080p pair 11.98 -> 11.56 ms).
-        static const char* const clear_env = std::getenv("PAPOF_SOR_CLEAR");
-        static const bool clear_tail_only = clear_env && std::strcmp(clear_env, "tail") == 0;
         if (bt) {  // every pair's two planes in one fill node (the pairs' planes lie bt->d doubles apart)
             PAPOF_TRY(fill_pairs(h, sp.du, bt->d * sizeof(double), sd.nd * 16, batch));
-        } else if (sd.group > 1 || !clear_tail_only) {
-            PAPOF_HIP(hipMemsetAsync(sp.du, 0, (sd.nd + sd.nh) * 16, h->stream));  // both planes (+ the halo rows)
         } else {
-            const size_t block = (size_t)sd.nb * kLanes * 16, par = (size_t)sd.npos_d * block;
-            PAPOF_HIP(hipMemset2DAsync((char*)sp.du + (size_t)sd.ns * block, par, 0, (size_t)(sd.npos_d - sd.ns) * block, 2,
-                                       h->stream));
+            PAPOF_HIP(hipMemsetAsync(sp.du, 0, (sd.nd + sd.nh) * 16, h->stream));  // both planes (+ the halo rows)
         }
         mark(1);  // everything below is solver kernels
         if (sd.group > 1) {
@@ -2334,53 +2205,13 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
         return PAPOF_OK;
     }
     if (sp.skew) return PAPOF_EINVAL;
-    if (!h->rb_naive) {  // the LDS-tiled, temporally blocked kernel: no plane clears (the first launch reads no unknowns)
-        mark(1);
-        PAPOF_TRY(sor_blocked_solve(h, sp, H, W, alpha, omega, mode, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor));
-        mark(0);
-        {
-            const BlockedPlan bp = blocked_plan(h, mode, H, W, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor);
-            log_solve(mode == PAPOF_SOR_REDBLACK ? 3 : 4, bp.q * (bp.base + (bp.rem ? 1 : 0)), bp.n_launch);
-        }
-        return PAPOF_OK;
-    }
-    // PAPOF_RB_NAIVE=1: one launch per half-sweep straight on the planes (the first implementation; kept as a cross-check)
-    const size_t np = (size_t)H * W;
-    PAPOF_HIP(hipMemsetAsync(sp.du, 0, np * sizeof(double), h->stream));  // src/OpticalFlow.cpp:452-453
-    PAPOF_HIP(hipMemsetAsync(sp.dv, 0, np * sizeof(double), h->stream));
+    // the LDS-tiled, temporally blocked kernel: no plane clears (the first launch reads no unknowns)
     mark(1);
-    if (mode == PAPOF_SOR_REDBLACK) {
-        for (int k = 0; k < n_sor; k++)
-            for (int colour = 0; colour < 2; colour++)
-                PAPOF_TRY(sor_redblack_halfsweep(h, sp, H, W, alpha, omega, colour, Rect{0, 0, W, H}));
-        mark(0);
-        log_solve(5, 1, 2 * n_sor);
-        return PAPOF_OK;
-    }
-    if (mode == PAPOF_SOR_JACOBI) {
-        if (!sp.du2 || !sp.dv2) return PAPOF_EINVAL;
-        const dim3 grid((W + 63) / 64, (H + 3) / 4), block(64, 4);
-        double *ru = sp.du, *rv = sp.dv, *wu = sp.du2, *wv = sp.dv2;
-        for (int k = 0; k < n_sor; k++) {
-            hipLaunchKernelGGL(k_sor_jacobi, grid, block, 0, h->stream, sp.phi, sp.xy, sp.a1, sp.a2, sp.b1, sp.b2, ru,
-                               rv, wu, wv, H, W, nalpha, om1);
-            double* t = ru;
-            ru = wu;
-            wu = t;
-            t = rv;
-            rv = wv;
-            wv = t;
-        }
-        PAPOF_HIP(hipGetLastError());
-        if (ru != sp.du) {  // odd sweep count: latest values are in the ping-pong buffers
-            PAPOF_HIP(hipMemcpyAsync(sp.du, ru, np * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            PAPOF_HIP(hipMemcpyAsync(sp.dv, rv, np * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
-        mark(0);
-        log_solve(5, 1, n_sor);
-        return PAPOF_OK;
-    }
-    return PAPOF_EINVAL;
+    PAPOF_TRY(sor_blocked_solve(h, sp, H, W, alpha, omega, mode, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor));
+    mark(0);
+    const BlockedPlan bp = blocked_plan(h, mode, H, W, mode == PAPOF_SOR_REDBLACK ? 2 * n_sor : n_sor);
+    log_solve(mode == PAPOF_SOR_REDBLACK ? 3 : 4, bp.q * (bp.base + (bp.rem ? 1 : 0)), bp.n_launch);
+    return PAPOF_OK;
 }
 
 // ---- one solve as BAND RANGES on several streams or ranks (tiles.hip: bands_flow; api.hip: papof_test_sor_strips) --------
@@ -2462,11 +2293,8 @@ int sor_strips_begin(papof_handle* h, const SorPlanes& sp, int n_sor, int n_solv
 }
 
 int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor,
-                    unsigned* prog, int b0, int b1, const SorSplit* split, int k0, int k1) {
-    // k0 .. k1-1: the sweeps of THIS launch (split solves only: tiles.hip issues a rank's solve as launches over ranges of
-    // sweeps so that the ranks pipeline; the ping-pong planes and the counters carry the state from launch to launch)
-    if (k1 < 0) k1 = n_sor;
-    if (!sp.skew || n_sor <= 0 || k0 < 0 || k1 > n_sor || k1 <= k0 || ((k0 != 0 || k1 != n_sor) && !split)) return PAPOF_EINVAL;
+                    unsigned* prog, int b0, int b1, const SorSplit* split) {
+    if (!sp.skew || n_sor <= 0) return PAPOF_EINVAL;
     // split over handles (tiles.hip: bands_flow): the plain kernel only, one inbox cell per sweep (ExactArgs)
     if (split && (sp.sd.fuse != 1 || sp.sd.group != 1 || n_sor > 128 || !h->use_dpp)) return PAPOF_EINVAL;
     const SkewDims sd = skew_dims(H, W, n_sor, sp.sd.group, sp.sd.fuse);
@@ -2480,11 +2308,9 @@ int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double a
     const int nbl = b1 - b0;
     if (std::getenv("PAPOF_SOR_INJECT_ABORT"))  // fault injection for the tests, as in sor_solve
         PAPOF_HIP(hipMemsetAsync(h->sync_words, 1, sizeof(unsigned), h->stream));
-    if (k0 == 0) {  // (once per solve: later launches of the solve read what the earlier ones wrote)
-        const unsigned n16 = (unsigned)(2 * sd.npos_d) * (unsigned)nbl * kLanes;
-        hipLaunchKernelGGL(k_sor_clear_bands, dim3((n16 + 255) / 256), dim3(256), 0, h->stream, (uint4*)sp.du, sd.nb, b0,
-                           nbl, n16);
-    }
+    const unsigned n16 = (unsigned)(2 * sd.npos_d) * (unsigned)nbl * kLanes;
+    hipLaunchKernelGGL(k_sor_clear_bands, dim3((n16 + 255) / 256), dim3(256), 0, h->stream, (uint4*)sp.du, sd.nb, b0, nbl,
+                       n16);
     ExactArgs A;
     A.phi = sp.phi;
     A.xy = sp.xy;
@@ -2508,7 +2334,7 @@ int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double a
     A.n_sor = n_sor;
     A.nalpha = -alpha;
     A.om1 = 1 - omega;
-    A.k0 = k0;
+    A.k0 = 0;
     A.b0 = b0;
     A.nbl = nbl;
     A.xcd_affine = 0;
@@ -2524,7 +2350,7 @@ int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double a
     if (h->sor_mark) h->sor_mark(h->sor_mark_ctx, 1);
     if (split) {
         const int R = h->sor_depth > 0 ? h->sor_depth : (sd.nb >= 8 ? 8 : 6);
-        const dim3 grid(nbl * (k1 - k0));
+        const dim3 grid(nbl * n_sor);
         if (R <= 6)
             hipLaunchKernelGGL((k_sor_exact<6, true, true>), grid, dim3(kLanes), 0, h->stream, A);
         else
@@ -2695,25 +2521,6 @@ int sor_probe_dpp(papof_handle* h) {
     for (int l = 1; l < 64; l++) ok = ok && host[l] == l;             // lane l sees lane l-1 (value l-1+1)
     for (int l = 0; l < 63; l++) ok = ok && host[64 + l] == l + 2;    // lane l sees lane l+1 (value l+1+1)
     h->use_dpp = ok;
-    if (std::getenv("PAPOF_PROBE")) {
-        unsigned long long* dt = nullptr;
-        double* sink = nullptr;
-        if (hipMalloc((void**)&dt, 16) == hipSuccess && hipMalloc((void**)&sink, 1024 * 8) == hipSuccess) {
-            for (int rep = 0; rep < 5; rep++) {  // 1, 2, 4, 8, 16 waves of ONE workgroup = one CU: does its fp64 issue scale?
-                const int n = 200000;
-                const int lanes = 64 << rep;
-                std::fprintf(stderr, "[papof probe] waves on one CU %d: ", lanes / 64);
-                hipLaunchKernelGGL(k_alu_probe, dim3(1), dim3(lanes), 0, h->stream, dt, sink, n, 1.0 + rep);
-                unsigned long long t[2] = {0, 0};
-                hipMemcpyAsync(t, dt, 16, hipMemcpyDeviceToHost, h->stream);
-                hipStreamSynchronize(h->stream);
-                std::fprintf(stderr, "[papof probe] dpp=%d  %d steps: %.1f shader cycles/step, %.4f us/step, clock %.0f MHz\n",
-                             (int)ok, n, (double)t[0] / n, (double)t[1] * 0.01 / n, (double)t[0] / ((double)t[1] * 0.01));
-            }
-        }
-        hipFree(dt);
-        hipFree(sink);
-    }
     if (const char* s = std::getenv("PAPOF_SOR_XLANE")) {
         if (std::strcmp(s, "shfl") == 0) h->use_dpp = false;
     }

@@ -125,31 +125,27 @@ def test_staged_protocol_of_the_rccl_transport_gives_the_same_bits(gpu, monkeypa
     assert n_ex > 0
 
 
-@pytest.mark.parametrize("chunks,nranks,res,levels,kw", [
-    (3, 2, "960", 5, dict(n_outer=3, n_outer_per_level=0, n_sor=30, n_sor_per_level=0)),
-    (4, 8, "480", 5, {}),
-    (7, 3, "240", 4, dict(n_outer=2, n_outer_per_level=1, n_sor=9, n_sor_per_level=4)),
-    (64, 5, "240", 2, dict(n_outer=2, n_outer_per_level=0, n_sor=5, n_sor_per_level=3)),   # more chunks than sweeps: one sweep per launch
+@pytest.mark.parametrize("nranks,res,levels,kw", [
+    (2, "960", 5, dict(n_outer=3, n_outer_per_level=0, n_sor=30, n_sor_per_level=0)),
+    (8, "480", 5, {}),
+    (3, "240", 4, dict(n_outer=2, n_outer_per_level=1, n_sor=9, n_sor_per_level=4)),
+    (5, "240", 2, dict(n_outer=2, n_outer_per_level=0, n_sor=5, n_sor_per_level=3)),
 ])
-def test_staged_protocol_in_ranges_of_sweeps_gives_the_same_bits(gpu, monkeypatch, tile_group, chunks, nranks, res, levels, kw):
-    """the staged protocol issues every rank's solve as launches over ranges of sweeps
-    (PAPOF_BANDS_CHUNKS) and sends the cut cells of a range as soon as its launch has ended, so that rank g + 1 runs sweeps
-    [k0, k1) while rank g runs [k1, k2).  Same bits as the one-GPU exact call for any number of ranges, on the LOCAL transport
-    (forced staged) and on the RCCL transport bound to the stand-in, where nothing but stream order holds the ranges apart."""
+def test_staged_protocol_over_the_rccl_stand_in_gives_the_same_bits(gpu, monkeypatch, tile_group, nranks, res, levels, kw):
+    """The staged protocol on the RCCL transport bound to the stand-in, where nothing but stream order holds the receive, the
+    unpacking, the launch and the send of a rank apart: same bits as the one-GPU exact call."""
     monkeypatch.setenv("PAPOF_BANDS_STAGED", "1")
-    monkeypatch.setenv("PAPOF_BANDS_CHUNKS", str(chunks))
     a, b = cases.load_pair(res)
     P = _params(**kw)
     want = gpu.coarse2fine_flow(a, b, levels, P)[:3]
     (vx, vy, wi, _), (n_ex, _) = _run(nranks, a, b, levels, P, tile_group)
     for name, g, w in zip(("vx", "vy", "warpI2"), (vx, vy, wi), want):
-        assert np.array_equal(g, w), "%d ranges, %d ranks %s L%d %s: max-abs %.3e" % (chunks, nranks, res, levels, name, np.abs(g - w).max())
+        assert np.array_equal(g, w), "%d ranks %s L%d %s: max-abs %.3e" % (nranks, res, levels, name, np.abs(g - w).max())
 
 
 def test_chunked_staged_split_returns_the_reference_bits_at_1080p(monkeypatch, tile_group):
-    """... and at size: 8 ranks, 3 ranges of sweeps per solve, the reference's golden of the 1920x1080 config-4 pair (full-array SHA)."""
+    """... and at size: 8 ranks, the reference's golden of the 1920x1080 config-4 pair (full-array SHA)."""
     monkeypatch.setenv("PAPOF_BANDS_STAGED", "1")
-    monkeypatch.setenv("PAPOF_BANDS_CHUNKS", "3")
     a, b = cases.load_pair("1920")
     kw = dict(n_outer=3, n_outer_per_level=0, n_sor=30, n_sor_per_level=0)
     (vx, vy, wi, _), _ = _run(8, a, b, 5, _params(**kw), tile_group)
