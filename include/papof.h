@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 115 /* 0.1.15: papof_match_tensor / papof_match_workspace / papof_match_densify_tensor (dense block matching of decimated uint8 frames, a start for the solver on large displacements) -- additions only, the number stays; papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 115 /* 0.1.15: papof_motion_blur_tensor (synthetic motion blur: the shutter's samples of papof_interp_tensor's rule summed in one kernel) -- an addition only, the number stays; papof_match_tensor / papof_match_workspace / papof_match_densify_tensor (dense block matching of decimated uint8 frames, a start for the solver on large displacements) -- additions only, the number stays; papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -1063,6 +1063,43 @@ long long papof_match_workspace(int n_pairs, int sequence, int height, int width
 int papof_match_densify_tensor(papof_handle* h, int n, int height, int width, int stride, const papof_tensor* disp,
                                const papof_tensor* disp_rev, const papof_tensor* cost, int tol, double max_cost,
                                const papof_tensor* flow, const papof_tensor* mask, void* stream);
+
+/* Synthetic motion blur along the flows (a longer shutter for a video shot, rendered or retimed with a short one): every
+ * frame becomes the weighted mean of the scene at n_samples times inside a shutter interval around it, the scene at an
+ * in-between time being what papof_interp_tensor states -- one HIP kernel (blur.hip: k_motion_blur), one lane per output
+ * pixel, the sums in registers.
+ * frames: ONE video of n_frames >= 2 frames, uint8 (x / 255.0), float32 (widened exactly) or float64, (frame, row, column,
+ * channel), any non-negative strides.  flow_fw[i], flow_bw[i]: the flows of the pair (i, i + 1) there and back, as
+ * papof_flow_batch_tensor_fb returns them in sequence mode: float32 / float64, (pair, row, column, {vx, vy}), n_frames - 1
+ * pairs, any non-negative strides.  occlusion: NULL, or that call's uint8 mask (pair, row, column, {fw, bw}), as
+ * papof_interp_tensor takes it.  out: uint8, float32 or float64, (frame, row, column, channel), strides > 0.
+ * offsets[k] = tau_k, the time of sample k relative to the frame, in frames: exactly 0, or 2^-20 <= |tau_k| <= 1 - 2^-20.
+ * weights[k] = w_k: finite and >= 0, their sum > 0.  1 <= n_samples <= 64.  Both arrays are read before the call returns
+ * (they travel as kernel arguments).
+ * For frame f, pixel p and channel ch, in fp64 without fused multiply-adds, with acc = wsum = 0 and k ascending:
+ *     w_k == 0:    the sample is skipped
+ *     tau_k == 0:  S_k = I_f(p)                                  (uint8: x / 255.0)
+ *     tau_k > 0:   S_k = the value papof_interp_tensor gives at p for the pair (f, f + 1) at t = tau_k, with flow_fw[f],
+ *                  flow_bw[f] and occlusion[f]; skipped on the last frame
+ *     tau_k < 0:   S_k = that value for the pair (f - 1, f) at t = 1.0 + tau_k, with flow_fw[f - 1], flow_bw[f - 1] and
+ *                  occlusion[f - 1]; skipped on frame 0
+ *     each kept sample:  acc = acc + w_k * S_k;  wsum = wsum + w_k
+ *     out = acc / wsum, or I_f(p) if no sample was kept
+ * stored as papof_interp_tensor stores: float64 as is, float32 with one round-to-nearest, uint8 = clamp(rint(255 * out), 0,
+ * 255) with rint rounding half to even (NaN: 0).  The end frames therefore get a one-sided shutter.  It is the gather rule:
+ * the flows are read at the output pixel, so at a motion boundary a sample reads the wrong flow, as papof_interp_tensor does.
+ * Known answers: identical frames and zero flows return the frames (for uint8 the same bytes); with offsets that are all
+ * >= 0 the last frame, and with offsets that are all <= 0 frame 0, is returned as it is (converted as stated).
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (occlusion aside) or data pointer, frames or an output
+ * that are not uint8 / float32 / float64, flows that are not float32 / float64, a mask that is not uint8, a negative stride,
+ * a zero stride of out, n_frames < 2, height, width or c < 1, n_samples outside 1 .. 64, offsets or weights NULL, an offset
+ * that is not 0 and not of a magnitude in [2^-20, 1 - 2^-20] (a NaN included), a weight that is negative or not finite, a
+ * sum of weights that is not > 0. */
+int papof_motion_blur_tensor(papof_handle* h, int n_frames, const papof_tensor* frames, int height, int width, int c,
+                             const papof_tensor* flow_fw, const papof_tensor* flow_bw, const papof_tensor* occlusion,
+                             int n_samples, const double* offsets, const double* weights, const papof_tensor* out,
+                             void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

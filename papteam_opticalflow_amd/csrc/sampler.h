@@ -2,7 +2,7 @@
 // frames and flows at non-integer points (k_interp, k_warp_affine, k_temporal_filter, k_propagate, the fill and consistency
 // kernels, k_track, k_fb_check), the forward-backward test and the hop of a point through a pair's flows (k_track,
 // k_temporal_filter, k_propagate, k_tc_setup; the test also k_fb_check), the interpolation rule at one output pixel (k_interp,
-// k_interp_splat), and on the host the splitting of a (tile, frame)
+// k_interp_splat, k_motion_blur), and on the host the splitting of a (tile, frame)
 // grid at the grid's bounds and the pyramid level sizes of the fill and consistency workspaces.
 //
 // The rule is the reference's (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours
@@ -157,6 +157,54 @@ __device__ __forceinline__ double sample_mask(const papof_tensor& t, long long b
     return o;
 }
 
+// ---- the rule at one output pixel and one time t, in the three steps that k_interp / k_interp_splat (interp_pixel) and
+// k_motion_blur (blur.hip) share: where the two samples land, their weights, the blend ----
+struct InterpPoints {
+    double s, t;      // 1 - t, t
+    bool in0, in1;    // q0, q1 in [0, W - 1] x [0, H - 1] (false for a NaN)
+    Bilinear k0, k1;  // the taps at q0 and q1 ((0, 0)'s where the point is not in the image)
+};
+
+// (u, v) = F01, (bu, bv) = F10 at the pixel (x, r)
+__device__ __forceinline__ InterpPoints interp_points(int x, long long r, double u, double v, double bu, double bv, double t,
+                                                      int H, int W) {
+    InterpPoints p;
+    p.t = t;
+    p.s = 1.0 - t;
+    const double s = p.s;
+    const double tt = t * t, st = s * t, ss = s * s;
+    const double a0 = tt * bu - st * u, b0 = tt * bv - st * v;  // F_t->0 = -s t F01 + t^2 F10
+    const double a1 = ss * u - st * bu, b1 = ss * v - st * bv;  // F_t->1 =  s^2 F01 - s t F10
+    const double X0 = (double)x + a0, Y0 = (double)r + b0, X1 = (double)x + a1, Y1 = (double)r + b1;
+    // (false for a NaN)
+    p.in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
+    p.in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
+    p.k0 = taps_at(p.in0 ? X0 : 0.0, p.in0 ? Y0 : 0.0, H, W);
+    p.k1 = taps_at(p.in1 ? X1 : 0.0, p.in1 ? Y1 : 0.0, H, W);
+    return p;
+}
+
+struct InterpWeights {
+    double c0, c1, den;
+};
+
+// o0, o1: the mask sampled at q0 (channel 0) and q1 (channel 1) where both points are in the image and there is a mask, else 0
+__device__ __forceinline__ InterpWeights interp_weights(const InterpPoints& p, double o0, double o1) {
+    const double w0 = p.in0 ? p.s * (1.0 - o1) : 0.0, w1 = p.in1 ? p.t * (1.0 - o0) : 0.0;
+    const bool weighted = w0 + w1 > 0;
+    InterpWeights q;
+    q.c0 = weighted ? w0 : p.s;
+    q.c1 = weighted ? w1 : p.t;
+    q.den = weighted ? w0 + w1 : (p.in0 ? p.s : 0.0) + (p.in1 ? p.t : 0.0);
+    return q;
+}
+
+// one channel where in0 || in1: g0, g1 the frames sampled at q0 and q1 (each read only where its point is in the image)
+__device__ __forceinline__ double interp_blend(const InterpPoints& p, const InterpWeights& q, double g0, double g1) {
+    const double num = p.in0 && p.in1 ? q.c0 * g0 + q.c1 * g1 : (p.in0 ? q.c0 * g0 : q.c1 * g1);
+    return num / q.den;
+}
+
 // Pixel (x, r) of pair i at the times a.t[0 .. a.nt), written at time slots j0 + j of out -- except the times j for which
 // done(j, offset of the pixel at that time slot in out) is true: those the caller has written (k_interp: none).
 template <int FD, typename D>
@@ -175,34 +223,21 @@ __device__ __forceinline__ void interp_pixel(const InterpArgs& a, const double* 
     for (int j = 0; j < a.nt; j++) {
         const long long oj = outp + (j0 + j) * a.tstride;
         if (done(j, oj)) continue;
-        const double t = a.t[j], s = 1.0 - t;
-        const double tt = t * t, st = s * t, ss = s * s;
-        const double a0 = tt * bu - st * u, b0 = tt * bv - st * v;  // F_t->0 = -s t F01 + t^2 F10
-        const double a1 = ss * u - st * bu, b1 = ss * v - st * bv;  // F_t->1 =  s^2 F01 - s t F10
-        const double X0 = (double)x + a0, Y0 = (double)r + b0, X1 = (double)x + a1, Y1 = (double)r + b1;
-        // (false for a NaN)
-        const bool in0 = X0 >= 0 && X0 <= (double)(W - 1) && Y0 >= 0 && Y0 <= (double)(H - 1);
-        const bool in1 = X1 >= 0 && X1 <= (double)(W - 1) && Y1 >= 0 && Y1 <= (double)(H - 1);
-        const Bilinear k0 = taps_at(in0 ? X0 : 0.0, in0 ? Y0 : 0.0, H, W);
-        const Bilinear k1 = taps_at(in1 ? X1 : 0.0, in1 ? Y1 : 0.0, H, W);
+        const InterpPoints p = interp_points(x, r, u, v, bu, bv, a.t[j], H, W);
         double o0 = 0.0, o1 = 0.0;
-        if (a.occ.data && in0 && in1) {
-            o0 = sample_mask(a.occ, baseo, k0);
-            o1 = sample_mask(a.occ, baseo + a.occ.stride[3], k1);
+        if (a.occ.data && p.in0 && p.in1) {
+            o0 = sample_mask(a.occ, baseo, p.k0);
+            o1 = sample_mask(a.occ, baseo + a.occ.stride[3], p.k1);
         }
-        const double w0 = in0 ? s * (1.0 - o1) : 0.0, w1 = in1 ? t * (1.0 - o0) : 0.0;
-        const bool weighted = w0 + w1 > 0;
-        const double c0 = weighted ? w0 : s, c1 = weighted ? w1 : t;
-        const double den = weighted ? w0 + w1 : (in0 ? s : 0.0) + (in1 ? t : 0.0);
+        const InterpWeights q = interp_weights(p, o0, o1);
         for (int ch = 0; ch < a.C; ch++) {
             double val;
-            if (in0 || in1) {
-                const double g0 = in0 ? sample_frame<FD>(a.f0, base0 + ch * a.f0.stride[3], k0, lut) : 0.0;
-                const double g1 = in1 ? sample_frame<FD>(a.f1, base1 + ch * a.f1.stride[3], k1, lut) : 0.0;
-                const double num = in0 && in1 ? c0 * g0 + c1 * g1 : (in0 ? c0 * g0 : c1 * g1);
-                val = num / den;
+            if (p.in0 || p.in1) {
+                const double g0 = p.in0 ? sample_frame<FD>(a.f0, base0 + ch * a.f0.stride[3], p.k0, lut) : 0.0;
+                const double g1 = p.in1 ? sample_frame<FD>(a.f1, base1 + ch * a.f1.stride[3], p.k1, lut) : 0.0;
+                val = interp_blend(p, q, g0, g1);
             } else {
-                val = s * load_frame<FD>(a.f0, pix0 + ch * a.f0.stride[3], lut) + t * load_frame<FD>(a.f1, pix1 + ch * a.f1.stride[3], lut);
+                val = p.s * load_frame<FD>(a.f0, pix0 + ch * a.f0.stride[3], lut) + p.t * load_frame<FD>(a.f1, pix1 + ch * a.f1.stride[3], lut);
             }
             store(a.out, oj + ch * a.out.stride[3], val);
         }

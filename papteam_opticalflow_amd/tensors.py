@@ -87,6 +87,12 @@ which brings motion larger than the objects that carry it within the solver's re
 
     fb = flow_video_ld(frames, layout="NHWC")   # a FlowFB, as flow_video_fb's
 
+Motion blur: `motion_blur` (include/papof.h: papof_motion_blur_tensor) gives a video a longer shutter: every frame becomes
+the weighted mean of the scene at the times of `blur_schedule` around it, each of them what `interpolate` states, summed in
+one HIP kernel; `blur_video` computes the flows first (flow_video_fb).
+
+    bv = blur_video(frames, 5, shutter=0.5, samples=16, layout="NHWC")   # bv.video: the frames' shape
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -115,6 +121,7 @@ Flows = collections.namedtuple("Flows", "flow_fw flow_bw")
 Propagated = collections.namedtuple("Propagated", "video status")
 Inpainted = collections.namedtuple("Inpainted", "video status")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
+Blurred = collections.namedtuple("Blurred", "video flow_fw flow_bw occlusion timing")
 RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
 MODELS = {"similarity": capi.MOTION_SIMILARITY, "affine": capi.MOTION_AFFINE}
 
@@ -1101,6 +1108,99 @@ def denoise_video(frames, pyramidLevels, *, radius=2, sigma=0.15, consistency=CO
     f = _filter(ts, descs, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), radius, sigma, alphas, layout,
                 out_dtype)
     return Denoised(f.video, f.support, fb.flow_fw, fb.flow_bw, fb.timing)
+
+
+MAX_SAMPLES = 64  # include/papof.h: papof_motion_blur_tensor
+MIN_OFFSET = 2.0 ** -20
+SHAPES = ("box", "triangle")
+
+
+def blur_schedule(shutter=0.5, samples=16, phase=-0.5, shape="box"):
+    """The shutter of motion_blur as (offsets, weights), two lists of `samples` floats, computed on the host: sample k is
+    taken at tau_k = shutter * ((k + 0.5) / samples + phase) frames from the frame (in that order in float64) with the
+    weight 1 ("box") or 1 - |2 (k + 0.5) / samples - 1| ("triangle").  shutter: the exposure in frame intervals, in (0, 1];
+    phase: where it opens, in shutters, in [-1, 0] -- -0.5 is centred on the frame, 0 opens at the frame, -1 closes at it;
+    samples: an integer in 1 .. 64.  ValueError for anything else, and for a schedule with an offset that
+    papof_motion_blur_tensor refuses (neither 0 nor of a magnitude in [2^-20, 1 - 2^-20])."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= MAX_SAMPLES:
+        raise ValueError("samples must be an integer in 1 .. %d, got %r" % (MAX_SAMPLES, samples))
+    for name, v in (("shutter", shutter), ("phase", phase)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError("%s must be a finite number, got %r" % (name, v))
+    shutter, phase = float(shutter), float(phase)
+    if not 0.0 < shutter <= 1.0:
+        raise ValueError("shutter must lie in (0, 1], got %r" % shutter)
+    if not -1.0 <= phase <= 0.0:
+        raise ValueError("phase must lie in [-1, 0], got %r" % phase)
+    if shape not in SHAPES:
+        raise ValueError("shape must be one of %s, got %r" % (SHAPES, shape))
+    offsets = [shutter * ((k + 0.5) / samples + phase) for k in range(samples)]
+    if shape == "box":
+        weights = [1.0] * samples
+    else:
+        weights = [1.0 - abs(2.0 * (k + 0.5) / samples - 1.0) for k in range(samples)]
+    for tau in offsets:
+        if tau != 0.0 and not MIN_OFFSET <= abs(tau) <= 1.0 - MIN_OFFSET:
+            raise ValueError("the schedule has the offset %r: neither 0 nor of a magnitude in [2^-20, 1 - 2^-20]" % tau)
+    return offsets, weights
+
+
+def _blur(ts, descs, flows, codes, occlusion, schedule, layout, out_dtype):
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    offsets, weights = schedule
+    out, d_out = _new_frames(T, H, W, C, layout, out_dtype, dev)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
+    n = len(offsets)
+    _launch(dev, "papof_motion_blur_tensor", T, ctypes.byref(d_in), H, W, C, ctypes.byref(d_f[0]), ctypes.byref(d_f[1]),
+            _ref(d_occ), n, (ctypes.c_double * n)(*offsets), (ctypes.c_double * n)(*weights), ctypes.byref(d_out))
+    return out
+
+
+def motion_blur(frames, flow_fw, flow_bw, *, shutter=0.5, samples=16, phase=-0.5, shape="box", occlusion=None, layout="NCHW",
+                out_dtype=None):
+    """Synthetic motion blur of a video of T >= 2 frames along its flows -- a longer shutter for a video shot, rendered or
+    retimed with a short one: frames (T, C, H, W) or (T, H, W, C) by `layout`, uint8 (read as x / 255), float32 or float64,
+    any strides, on a HIP device; flow_fw, flow_bw (T - 1, 2, H, W) float32 / float64 on the same device, pair t from frame t
+    to t + 1 and back, and occlusion None or their (T - 1, 2, H, W) bool / uint8 mask, as flow_video_fb returns them.
+    Every output pixel is the weighted mean of the scene at the `samples` times of blur_schedule(shutter, samples, phase,
+    shape) around its frame; the scene at an in-between time is what interpolate makes of the pair that holds that time
+    (pair (t, t + 1) after the frame, (t - 1, t) before it), and at offset 0 the frame itself.  All of it happens in one HIP
+    kernel whose sums stay in registers.  The first frame has no pair before it and the last none after it: their samples on
+    that side are dropped, so the end frames get a one-sided shutter (a frame with no sample left is returned as it is).
+    It is the gather rule (the flows are read at the output pixel): at a motion boundary a sample reads the wrong flow, as
+    interpolate(method="gather") does.  It adds blur and removes none.
+    Returns a new tensor of the frames' shape in `layout` and out_dtype -- uint8 as clamp(rint(255 x), 0, 255), float32 or
+    float64; by default the frames' dtype.  include/papof.h (papof_motion_blur_tensor) states the rule exactly.  Enqueued on
+    the current stream; returns without waiting."""
+    schedule = blur_schedule(shutter, samples, phase, shape)
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1, min_frames=2)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    (T, H, W, C), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
+    occ = _check_occlusion(occlusion, (T - 1, 2, H, W), ts[0].device)
+    return _blur(ts, descs, (flow_fw, flow_bw), codes, occ, schedule, layout, out_dtype)
+
+
+def blur_video(frames, pyramidLevels, *, shutter=0.5, samples=16, phase=-0.5, shape="box", layout="NCHW", out_dtype=None,
+               consistency=CONSISTENCY, **solver):
+    """A video of T >= 2 frames with a longer shutter: flow_video_fb(frames, pyramidLevels, layout=layout,
+    consistency=consistency, **solver) -- float64 flows whatever out_dtype is -- followed by motion_blur on its flows and
+    mask (None for consistency=None: no mask).  Returns Blurred(video, flow_fw, flow_bw, occlusion, timing of the flow call).
+    Every argument error raises before anything is launched; the flows are complete on return, the video is enqueued on the
+    current stream behind them."""
+    torch = _torch()
+    alphas = _alphas(consistency)
+    schedule = blur_schedule(shutter, samples, phase, shape)
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    T = descs[0][0][0]
+    fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, alphas, params)
+    occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
+    video = _blur(ts, descs, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, schedule, layout, out_dtype)
+    return Blurred(video, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
 
 
 MAX_RELAX = 65536  # include/papof.h: papof_fill_holes_tensor
