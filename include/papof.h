@@ -925,6 +925,66 @@ long long papof_refine_workspace(int n, int height, int width, int iters);
  * PAPOF_EINVAL: radius outside 1 .. 15, sigma_s not finite or <= 0, S or R NULL. */
 int papof_refine_tables(int radius, double sigma_s, unsigned* S, unsigned* R);
 
+/* Flow at reduced resolution (upsample.hip): the box decimation of frames, and the edge-aware up-sampling of a flow that was
+ * estimated on the decimated frames, guided by the full-resolution frame: joint bilateral upsampling (Kopf, Cohen,
+ * Lischinski, Uyttendaele, SIGGRAPH 2007).  In both calls the low-resolution grid of an H x W frame at `factor` f in 2 .. 4
+ * is h x w = ceil(H / f) x ceil(W / f), and cell (y, x) covers the pixels (f y .. f y + f - 1, f x .. f x + f - 1) that exist.
+ *
+ * Box decimation, one kernel on `stream` (k_decimate: one lane per low-resolution pixel).  frames: uint8 (a sample k is
+ * k / 255.0, one fp64 division), float32 (widened exactly) or float64, (item, row, column, channel), c channels, c in
+ * 1 .. 4, any non-negative strides.  out: float32 / float64, (item, row, column, channel) at h x w, positive strides.
+ *     out[y, x, ch] = (sum of the samples of cell (y, x), added from 0.0 in row-major order, fp64) / (their number)
+ * One fp64 division; a float32 out is rounded once, to nearest.  Edge cells are clipped, so no row or column is dropped and a
+ * height or width of 1 is legal.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor or data pointer, a dtype other than those above, a
+ * negative stride or a zero stride of out, n, height or width < 1, c outside 1 .. 4, factor outside 2 .. 4. */
+int papof_decimate_tensor(papof_handle* h, int n, int height, int width, int c, int factor, const papof_tensor* frames,
+                          const papof_tensor* out, void* stream);
+
+/* Edge-aware up-sampling of a low-resolution flow, one kernel on `stream` (k_upsample_flow: one lane per output pixel on a
+ * 32 x 8 tile, the tile's low-resolution window staged in LDS).
+ * flow_lr: float32 (widened exactly) or float64, (item, row, column, {vx, vy}) at h x w, in low-resolution pixels.  guide:
+ * uint8 (k / 255.0), float32 or float64, (item, row, column, channel) at height x width, c channels in 1 .. 4.  guide_lr:
+ * float32 / float64 at h x w, the guide as the decimation above gives it (a float guide is taken as it is: guide and guide_lr
+ * must be in one scale).  occlusion: NULL, or uint8 (item, row, column, -) at h x w, nonzero = this cell's flow is not to be
+ * trusted; stride[3] is not read.  Any non-negative strides.  radius r in 0 .. 3; S: DEVICE pointer to the f^2 (2 r + 1)^2
+ * spatial weights, R: DEVICE pointer to the 1024 range weights, as the tables call below fills them (every entry of both
+ * >= 1 and S[.] * R[.] < 2^53); q finite and >= 0.
+ * For output pixel (Y, X) of an item, with centre cell (cy, cx) = (Y / f, X / f) and phase (py, px) = (Y % f, X % f), and
+ * every tap (dy, dx), |dy|, |dx| <= r, rows outer (dy, then dx, ascending), whose cell (cy + dy, cx + dx) is in the grid:
+ *     the cell is DEAD if a component of flow_lr there is not finite or occlusion there is nonzero: it is skipped;
+ *     D = (g_0(Y, X) - gl_0(cell))^2 + (g_1(Y, X) - gl_1(cell))^2 + ...   fp64, channels added in order from 0.0, no fused
+ *                                                                          multiply-add
+ *     k = (int)(D * q) if D * q < 1023.0, else 1023 (a NaN included)      (one fp64 product)
+ *     w = S[((py * f + px) * (2 r + 1) + dy + r) * (2 r + 1) + dx + r] * R[k]     (an integer, exact as a float64)
+ *     su = su + w * vx(cell),  sv = sv + w * vy(cell),  sw = sw + w        (fp64 products and sums from 0.0; sw exact)
+ *     out(Y, X) = (su / sw * f, sv / sw * f)                               (one division and one product per component)
+ * The flow is scaled by f because it is measured in pixels.  Every live tap has w >= 1, so sw = 0 only when every tap is
+ * dead: the output is then (f * vx, f * vy) of the centre cell as it is, occluded or not, NaN and infinities included.
+ * Nothing depends on an order of evaluation other than the stated one: the result is a pure function of the inputs.
+ * out: float32 / float64, (item, row, column, {vx, vy}) at height x width, positive strides, overlapping no input.
+ * Tables as filled below with q = 32 / (sigma_c^2 c) give the range weight exp(-d2 / (2 sigma_c^2)), d2 the mean over
+ * the channels of the squared difference of guides scaled to 0 .. 1, in 1024 bins up to d2 = 32 sigma_c^2.
+ * Enqueued on `stream` and returns without waiting, like the decimation.  PAPOF_EINVAL, before anything is enqueued: a NULL
+ * handle, descriptor (occlusion aside) or data pointer, a dtype other than those above, a negative stride or a zero stride
+ * of out, n, height or width < 1, c outside 1 .. 4, factor outside 2 .. 4, radius outside 0 .. 3, S or R NULL, q negative
+ * or not finite. */
+int papof_upsample_flow_tensor(papof_handle* h, int n, int height, int width, int c, int factor, const papof_tensor* flow_lr,
+                               const papof_tensor* guide, const papof_tensor* guide_lr, const papof_tensor* occlusion,
+                               int radius, const unsigned* S, const unsigned* R, double q, const papof_tensor* out,
+                               void* stream);
+
+/* The tables of the up-sampling on the HOST, with libm's exp.  With (ty, tx) = (dy - (py - (f - 1) / 2) / f,
+ * dx - (px - (f - 1) / 2) / f), the tap's cell centre seen from the pixel, in cells:
+ *     S[((py * f + px) * (2 r + 1) + dy + r) * (2 r + 1) + dx + r] =
+ *         max(1, rint(32768 * (15 / 16 * max(0, 1 - |tx|) * max(0, 1 - |ty|) + 1 / 16 * exp(-(tx^2 + ty^2) / (2 sigma_s^2)))))
+ *     R[k] = max(1, rint(65536 * exp(-(k + 0.5) / 64))),   k = 0 .. 1023      (R[0] = 65026; 1 from k = 684 on)
+ * The tent is the bilinear weight: where the guide is flat the result is bilinear up-sampling to within 1 / 16; the Gaussian
+ * is the reach beyond the four nearest cells that lets a pixel next to an edge find cells of its own side.
+ * PAPOF_EINVAL: factor outside 2 .. 4, radius outside 0 .. 3, sigma_s not finite or <= 0, S or R NULL. */
+int papof_upsample_tables(int factor, int radius, double sigma_s, unsigned* S, unsigned* R);
+
 /* Multi-frame super-resolution along the flows (superres.hip): every pixel of every frame is carried along the chains of
  * flows to the frames around it and deposited on a grid `scale` times finer (shift and add: Farsiu, Robinson, Elad, Milanfar
  * 2004), the sums are resolved against a cubic upsampling of the target frame, and `iters` steps of back-projection

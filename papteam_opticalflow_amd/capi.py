@@ -68,7 +68,8 @@ SYMBOLS = [
     "papof_temporal_consistency_tensor", "papof_consistency_workspace", "papof_splat_tensor", "papof_splat_workspace",
     "papof_interp_splat_tensor", "papof_refine_flow_tensor", "papof_refine_workspace", "papof_refine_tables",
     "papof_super_resolve_tensor", "papof_sr_workspace", "papof_match_tensor", "papof_match_workspace",
-    "papof_match_densify_tensor", "papof_motion_blur_tensor",
+    "papof_match_densify_tensor", "papof_motion_blur_tensor", "papof_decimate_tensor", "papof_upsample_flow_tensor",
+    "papof_upsample_tables",
 ]
 
 
@@ -212,6 +213,13 @@ def load():
     L.papof_match_densify_tensor.restype = c_int
     L.papof_motion_blur_tensor.argtypes = [c_void_p, c_int, _T, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _D, _T, c_void_p]
     L.papof_motion_blur_tensor.restype = c_int
+    L.papof_decimate_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, c_void_p]
+    L.papof_decimate_tensor.restype = c_int
+    L.papof_upsample_flow_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, c_int, c_void_p,
+                                             c_void_p, c_double, _T, c_void_p]
+    L.papof_upsample_flow_tensor.restype = c_int
+    L.papof_upsample_tables.argtypes = [c_int, c_int, c_double, _U, _U]
+    L.papof_upsample_tables.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

@@ -1,0 +1,276 @@
+// papteam_opticalflow_amd/csrc/upsample.hip -- flow at reduced resolution: the box decimation of frames
+// (papof_decimate_tensor) and the edge-aware up-sampling of a low-resolution flow guided by the full-resolution frame
+// (papof_upsample_flow_tensor): joint bilateral upsampling (Kopf, Cohen, Lischinski, Uyttendaele, "Joint bilateral
+// upsampling", SIGGRAPH 2007).
+//
+// Why.  The solver's cost is proportional to pixels; most callers need the right motion on the right side of every object
+// edge, not the last level's sub-pixel detail everywhere.  Bilinear up-sampling spreads every motion boundary over `factor`
+// more pixels; here each output pixel weighs the (2 r + 1)^2 low-resolution cells around it by distance AND by how much the
+// decimated guide there looks like the full-resolution guide at the pixel, so it takes its motion from its own side.
+//
+// Semantics: include/papof.h.  The weights are INTEGERS (two host-made tables multiplied), the products and sums fp64 in tap
+// order without contraction, so the result is a pure function of the inputs.
+//
+// Mapping.  k_decimate: one lane per low-resolution pixel on a 64 x 4 tile, a loop over the channels and the block.
+// k_upsample_flow: a block is a 32 x 8 tile of OUTPUT pixels (blockIdx.x the tile, blockIdx.y the item), one lane per pixel.
+// The low-resolution window of the tile -- at most 31 / f + 2 + 2 r by 7 / f + 2 + 2 r cells -- is staged once in LDS: both
+// flow components and the decimated guide as float64, a dead byte folding "outside / occluded / not finite", the two tables
+// and the 256 quotients of a uint8 sample.  A lane then reads its own guide pixel from global memory, loops over the taps
+// in LDS and writes its two components.  The range table has 1024 bins (4 KiB), not papof_refine_tables' 4096: a block
+// writes 4 KiB, and staging 16 KiB of table per block would be most of its traffic.  LDS per block: at most 253 cells x
+// (16 + 8 c + 1) bytes + the tables, 18.9 KiB at most (f = 2, r = 3, c = 4).  Every offset is 64-bit.
+#include "sampler.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace papof {
+
+namespace {
+
+constexpr int kTX = 32, kTY = 8;   // k_upsample_flow's tile of output pixels (256 lanes: lut)
+constexpr int kDX = 64, kDY = 4;   // k_decimate's tile of low-resolution pixels
+constexpr int kMaxRadius = 3;
+constexpr int kBins = 1024;        // the range table's bins
+constexpr double kHalo = 1.0 / 16; // the Gaussian's share of a spatial weight; the tent has the rest
+
+struct DecimateArgs {
+    papof_tensor in;   // (item, row, column, channel)
+    papof_tensor out;  // (item, row, column, channel), float32 / float64
+    int H, W, C, f, h, w;
+};
+
+// blockIdx.x: tile `tile0` + x of the low-resolution frame's 64 x 4 tiles in row-major order; blockIdx.y: item `item0` + y.
+__global__ __launch_bounds__(kDX* kDY) void k_decimate(const DecimateArgs a, long long tile0, long long item0) {
+    __shared__ double lut[256];
+    fill_u8_lut(lut, (int)(threadIdx.y * kDX + threadIdx.x));
+    __syncthreads();
+    const long long tx = (a.w + kDX - 1) / kDX, tile = tile0 + blockIdx.x;
+    const int x = (int)(tile % tx) * kDX + (int)threadIdx.x, y = (int)(tile / tx) * kDY + (int)threadIdx.y;
+    if (x >= a.w || y >= a.h) return;
+    const long long i = item0 + blockIdx.y;
+    const int f = a.f, Y0 = y * f, X0 = x * f;
+    const int ny = min(f, a.H - Y0), nx = min(f, a.W - X0);
+    const double count = (double)(ny * nx);
+    const long long oi = i * a.in.stride[0], oo = i * a.out.stride[0] + (long long)y * a.out.stride[1] + (long long)x * a.out.stride[2];
+    for (int ch = 0; ch < a.C; ch++) {
+        double s = 0.0;
+        for (int j = 0; j < ny; j++)
+            for (int k = 0; k < nx; k++)
+                s += load_frame<-1>(a.in, oi + (long long)(Y0 + j) * a.in.stride[1] + (long long)(X0 + k) * a.in.stride[2] +
+                                              ch * a.in.stride[3], lut);
+        store(a.out, oo + ch * a.out.stride[3], s / count);
+    }
+}
+
+struct UpsampleArgs {
+    papof_tensor flow;      // (item, row, column, {vx, vy}) at h x w
+    papof_tensor guide;     // (item, row, column, channel) at H x W
+    papof_tensor guide_lr;  // (item, row, column, channel) at h x w, float32 / float64
+    papof_tensor occ;       // uint8 (item, row, column, -) at h x w; data NULL: none
+    papof_tensor out;       // (item, row, column, {vx, vy}) at H x W, float32 / float64
+    const unsigned* S;      // [f * f * (2 r + 1)^2]
+    const unsigned* R;      // [kBins]
+    double q;
+    int H, W, C, f, r, h, w;
+};
+
+__host__ __device__ inline int max_window(int tile, int f, int r) { return (tile - 1) / f + 2 + 2 * r; }
+
+// bytes of k_upsample_flow's LDS: u, v, the decimated guide, the lut, the range table, the spatial table, the dead bytes
+long long lds_bytes(int C, int f, int r) {
+    const long long cells = (long long)max_window(kTX, f, r) * max_window(kTY, f, r), side = 2 * r + 1;
+    return cells * (16 + 8LL * C) + 256 * 8 + kBins * 4 + f * f * side * side * 4 + ((cells + 15) & ~15LL);
+}
+
+// GD: the guide's dtype.  blockIdx.x: tile `tile0` + x of the output's 32 x 8 tiles in row-major order; blockIdx.y: item
+// `item0` + y.
+template <int GD>
+__global__ __launch_bounds__(kTX* kTY) void k_upsample_flow(const UpsampleArgs a, long long tile0, long long item0) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int r = a.r, C = a.C, f = a.f, side = 2 * r + 1, taps = side * side;
+    const int tid = threadIdx.y * kTX + threadIdx.x;
+    const long long tx = (a.W + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
+    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const long long i = item0 + blockIdx.y;
+    // the window: the cells of the tile's pixels and r around them
+    const int ox = x0 / f - r, oy = y0 / f - r;
+    const int PW = (x0 + kTX - 1) / f - x0 / f + 1 + 2 * r, PH = (y0 + kTY - 1) / f - y0 / f + 1 + 2 * r, cells = PW * PH;
+    const int room = max_window(kTX, f, r) * max_window(kTY, f, r);  // (what the launch sized the arrays for: >= cells)
+    double* const U = reinterpret_cast<double*>(smem);
+    double* const V = U + room;
+    double* const G = V + room;
+    double* const lut = G + (long long)room * C;
+    unsigned* const Rt = reinterpret_cast<unsigned*>(lut + 256);
+    unsigned* const St = Rt + kBins;
+    unsigned char* const dead = reinterpret_cast<unsigned char*>(St + f * f * taps);
+
+    // ---- stage the window and the tables
+    fill_u8_lut(lut, tid);
+    for (int c = tid; c < cells; c += kTX * kTY) {
+        const int cy = c / PW, cx = c - cy * PW;
+        const int gy = oy + cy, gx = ox + cx;
+        const bool in = gx >= 0 && gx < a.w && gy >= 0 && gy < a.h;
+        double u = 0.0, v = 0.0;
+        bool d = !in;
+        if (in) {
+            const long long o = i * a.flow.stride[0] + (long long)gy * a.flow.stride[1] + (long long)gx * a.flow.stride[2];
+            u = load_flow(a.flow, o);
+            v = load_flow(a.flow, o + a.flow.stride[3]);
+            d = !(isfinite(u) && isfinite(v));
+            if (a.occ.data)
+                d = d || static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + (long long)gy * a.occ.stride[1] +
+                                                                       (long long)gx * a.occ.stride[2]] != 0;
+        }
+        U[c] = u;
+        V[c] = v;
+        dead[c] = d ? 1 : 0;
+        const long long og = i * a.guide_lr.stride[0] + (long long)gy * a.guide_lr.stride[1] + (long long)gx * a.guide_lr.stride[2];
+        for (int ch = 0; ch < C; ch++) G[c * C + ch] = in ? load_flow(a.guide_lr, og + ch * a.guide_lr.stride[3]) : 0.0;
+    }
+    for (int k = tid; k < kBins; k += kTX * kTY) Rt[k] = a.R[k];
+    for (int k = tid; k < f * f * taps; k += kTX * kTY) St[k] = a.S[k];
+    __syncthreads();
+
+    // ---- the lane's pixel
+    const int X = x0 + (int)threadIdx.x, Y = y0 + (int)threadIdx.y;
+    if (X >= a.W || Y >= a.H) return;
+    const int cyc = Y / f, cxc = X / f;
+    const int cc = (cyc - oy) * PW + cxc - ox;  // the centre cell: r cells from the window's borders at least
+    const unsigned* const Sp = St + ((Y - cyc * f) * f + (X - cxc * f)) * taps;
+    double gc[4] = {0.0, 0.0, 0.0, 0.0};
+    const long long og = i * a.guide.stride[0] + (long long)Y * a.guide.stride[1] + (long long)X * a.guide.stride[2];
+    for (int ch = 0; ch < 4; ch++)
+        if (ch < C) gc[ch] = load_frame<GD>(a.guide, og + ch * a.guide.stride[3], lut);
+    const double q = a.q;
+
+    double su = 0.0, sv = 0.0;
+    unsigned long long sw = 0;
+    for (int dy = -r, si = 0; dy <= r; dy++)
+        for (int dx = -r; dx <= r; dx++, si++) {
+            const int n = cc + dy * PW + dx;
+            if (dead[n]) continue;
+            double D = 0.0;
+#pragma unroll
+            for (int ch = 0; ch < 4; ch++)
+                if (ch < C) {
+                    const double d = gc[ch] - G[n * C + ch];
+                    D = D + d * d;
+                }
+            const double Dq = D * q;
+            const int k = Dq < (double)(kBins - 1) ? (int)Dq : kBins - 1;  // (a NaN: the last bin)
+            const unsigned long long w = (unsigned long long)Sp[si] * Rt[k];
+            const double wd = (double)w;
+            su += wd * U[n];
+            sv += wd * V[n];
+            sw += w;
+        }
+    const double fd = (double)f;
+    double ou, ov;
+    if (sw == 0) {  // every tap dead: the centre cell as it is
+        ou = fd * U[cc];
+        ov = fd * V[cc];
+    } else {
+        const double den = (double)sw;
+        ou = su / den * fd;
+        ov = sv / den * fd;
+    }
+    const long long oo = i * a.out.stride[0] + (long long)Y * a.out.stride[1] + (long long)X * a.out.stride[2];
+    store(a.out, oo, ou);
+    store(a.out, oo + a.out.stride[3], ov);
+}
+
+bool valid_sizes(int n, int H, int W, int c, int factor) {
+    return n >= 1 && H >= 1 && W >= 1 && c >= 1 && c <= 4 && factor >= 2 && factor <= 4;
+}
+
+}  // namespace
+
+}  // namespace papof
+
+using namespace papof;
+
+extern "C" int papof_decimate_tensor(papof_handle* h, int n, int height, int width, int c, int factor,
+                                     const papof_tensor* frames, const papof_tensor* out, void* stream) {
+    if (!h || !valid_sizes(n, height, width, c, factor)) return PAPOF_EINVAL;
+    const auto all = {0, 1, 2, 3};
+    if (!described(frames, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, false) ||
+        !described(out, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, true))
+        return PAPOF_EINVAL;
+    DecimateArgs a{};
+    a.in = *frames;
+    a.out = *out;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    a.f = factor;
+    a.h = (height + factor - 1) / factor;
+    a.w = (width + factor - 1) / factor;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long tiles = ((a.w + kDX - 1) / (long long)kDX) * ((a.h + kDY - 1) / (long long)kDY);
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
+        hipLaunchKernelGGL(k_decimate, grid, dim3(kDX, kDY), 0, st, a, t0, i0);
+    });
+}
+
+extern "C" int papof_upsample_tables(int factor, int radius, double sigma_s, unsigned* S, unsigned* R) {
+    if (factor < 2 || factor > 4 || radius < 0 || radius > kMaxRadius || !std::isfinite(sigma_s) || !(sigma_s > 0) || !S || !R)
+        return PAPOF_EINVAL;
+    const double two = 2.0 * sigma_s * sigma_s, half = (double)(factor - 1) / 2.0;
+    int k = 0;
+    for (int py = 0; py < factor; py++)
+        for (int px = 0; px < factor; px++)
+            for (int dy = -radius; dy <= radius; dy++)
+                for (int dx = -radius; dx <= radius; dx++, k++) {
+                    // the tap's cell centre from the pixel, in cells
+                    const double ty = (double)dy - ((double)py - half) / (double)factor;
+                    const double tx = (double)dx - ((double)px - half) / (double)factor;
+                    const double tent = std::max(0.0, 1.0 - std::fabs(tx)) * std::max(0.0, 1.0 - std::fabs(ty));
+                    const double gauss = std::exp(-(tx * tx + ty * ty) / two);
+                    S[k] = (unsigned)std::max(1.0, std::rint(32768.0 * ((1.0 - kHalo) * tent + kHalo * gauss)));
+                }
+    for (int b = 0; b < kBins; b++) R[b] = (unsigned)std::max(1.0, std::rint(65536.0 * std::exp(-((double)b + 0.5) / 64.0)));
+    return PAPOF_OK;
+}
+
+extern "C" int papof_upsample_flow_tensor(papof_handle* h, int n, int height, int width, int c, int factor,
+                                          const papof_tensor* flow_lr, const papof_tensor* guide, const papof_tensor* guide_lr,
+                                          const papof_tensor* occlusion, int radius, const unsigned* S, const unsigned* R,
+                                          double q, const papof_tensor* out, void* stream) {
+    if (!h || !valid_sizes(n, height, width, c, factor) || radius < 0 || radius > kMaxRadius) return PAPOF_EINVAL;
+    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    const auto all = {0, 1, 2, 3};
+    if (!described(flow_lr, F, all, false) || !described(guide, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, false) ||
+        !described(guide_lr, F, all, false) || !described(out, F, all, true))
+        return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!S || !R || !std::isfinite(q) || q < 0) return PAPOF_EINVAL;
+    UpsampleArgs a{};
+    a.flow = *flow_lr;
+    a.guide = *guide;
+    a.guide_lr = *guide_lr;
+    if (occlusion) a.occ = *occlusion;
+    a.out = *out;
+    a.S = S;
+    a.R = R;
+    a.q = q;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    a.f = factor;
+    a.r = radius;
+    a.h = (height + factor - 1) / factor;
+    a.w = (width + factor - 1) / factor;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int gd = guide->dtype;
+    const auto kernel = gd == PAPOF_DTYPE_U8    ? k_upsample_flow<PAPOF_DTYPE_U8>
+                        : gd == PAPOF_DTYPE_F32 ? k_upsample_flow<PAPOF_DTYPE_F32>
+                                                : k_upsample_flow<PAPOF_DTYPE_F64>;
+    const size_t lds = (size_t)lds_bytes(c, factor, radius);
+    const long long tiles = ((width + kTX - 1) / (long long)kTX) * ((height + kTY - 1) / (long long)kTY);
+    PAPOF_HIP(hipSetDevice(h->device));
+    return launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
+    });
+}

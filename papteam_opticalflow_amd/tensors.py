@@ -93,6 +93,15 @@ one HIP kernel; `blur_video` computes the flows first (flow_video_fb).
 
     bv = blur_video(frames, 5, shutter=0.5, samples=16, layout="NHWC")   # bv.video: the frames' shape
 
+Reduced resolution: `decimate` (include/papof.h: papof_decimate_tensor) is the box decimation of frames by 2, 3 or 4 and
+`upsample_flow` (papof_upsample_flow_tensor) brings a flow estimated on the decimated frames up again, guided by the
+full-resolution frame (joint bilateral upsampling, Kopf et al. 2007), so that motion boundaries land on the image's edges
+instead of being spread over `factor` pixels; integer weights, sums in a stated order, bitwise reproducible.
+`flow_pairs_lr` / `flow_video_lr` chain them around flow_pairs_fb / flow_video_fb: a quarter of the solver's pixels at
+factor 2.
+
+    fb = flow_video_lr(frames, 4, factor=2, layout="NHWC")   # a FlowFB, as flow_video_fb's (warpI2_* None unless refined)
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -1580,24 +1589,27 @@ def _check_refine_flow(flow, guide, occlusion, where, layout, out_dtype):
     return ts[0], descs[0], code, occ, wh, out_dtype
 
 
-_tables = collections.OrderedDict()  # (device ordinal, radius, sigma_s) -> the two tables on the device, the last 16 used
+_tables = collections.OrderedDict()  # (device ordinal, radius, sigma_s[, factor]) -> the two tables on the device, the last 16 used
 MAX_TABLES = 16
 
 
-def _device_tables(dev, radius, sigma_s):
-    """refine_tables(radius, sigma_s) on `dev` as int32 tensors (entries below 2^31: the same bits).  They are uploaded once
-    per (device, radius, sigma_s) and the upload is waited for, so later calls read finished, immutable tables from any
-    stream and enqueue no copy; only the first call with new parameters blocks the host."""
+def _device_tables(dev, radius, sigma_s, factor=None):
+    """refine_tables(radius, sigma_s) -- with a factor: upsample_tables(factor, radius, sigma_s) -- on `dev` as int32 tensors
+    (entries below 2^31: the same bits).  They are uploaded once per (device, radius, sigma_s, factor) and the upload is
+    waited for, so later calls read finished, immutable tables from any stream and enqueue no copy; only the first call with
+    new parameters blocks the host."""
     torch = _torch()
     index = _index(dev)
     stream = torch.cuda.current_stream(index)
+    key = (index, radius, sigma_s) if factor is None else (index, radius, sigma_s, factor)
     with _lock:
-        got = _tables.pop((index, radius, sigma_s), None)
+        got = _tables.pop(key, None)
         if got is None:
+            made = refine_tables(radius, sigma_s) if factor is None else upsample_tables(factor, radius, sigma_s)
             with torch.cuda.device(index):
-                got = tuple(torch.from_numpy(t.view("int32")).to(dev) for t in refine_tables(radius, sigma_s))
+                got = tuple(torch.from_numpy(t.view("int32")).to(dev) for t in made)
             stream.synchronize()
-        _tables[(index, radius, sigma_s)] = got
+        _tables[key] = got
         while len(_tables) > MAX_TABLES:
             _tables.popitem(last=False)
     for t in got:
@@ -2026,3 +2038,212 @@ def flow_video_ld(frames, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_P
     ts, descs, out_dtype, params = _check_match_frames([("frames", frames)], layout, out_dtype, pyramidLevels, match[0],
                                                        min_frames=2, solver=solver)
     return _run_ld(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, match, densify)
+
+
+FACTORS = (2, 3, 4)  # include/papof.h: papof_decimate_tensor, papof_upsample_flow_tensor
+MAX_UPSAMPLE_RADIUS = 3
+UPSAMPLE_BINS = 1024
+UP_RADIUS, UP_SIGMA_S, UP_SIGMA_C = 2, 1.0, 0.05  # a 5 x 5 window of cells, 1 cell, 5 % of the guide's range
+
+
+def _check_factor(factor):
+    if isinstance(factor, bool) or not isinstance(factor, int):
+        raise TypeError("factor must be an int, got %r" % (factor,))
+    if factor not in FACTORS:
+        raise ValueError("factor must be one of %s, got %d" % (FACTORS, factor))
+    return factor
+
+
+def _check_upsample(factor, radius, sigma_s, sigma_c):
+    """(factor, radius, sigma_s, sigma_c) as int, int, float, float -- TypeError / ValueError otherwise"""
+    factor = _check_factor(factor)
+    if isinstance(radius, bool) or not isinstance(radius, int):
+        raise TypeError("radius must be an int, got %r" % (radius,))
+    if not 0 <= radius <= MAX_UPSAMPLE_RADIUS:
+        raise ValueError("radius must be in 0 .. %d, got %d" % (MAX_UPSAMPLE_RADIUS, radius))
+    _, sigma_s, sigma_c, _ = _check_refine(1, sigma_s, sigma_c, 1)
+    return factor, radius, sigma_s, sigma_c
+
+
+def upsample_tables(factor, radius, sigma_s):
+    """The two integer tables of upsample_flow as numpy uint32 arrays, made by the library on the host (include/papof.h:
+    papof_upsample_tables): S (factor^2 (2 radius + 1)^2,), indexed by the pixel's phase within its cell (py, px) and the tap
+    (dy, dx), 15 / 16 of the bilinear tent plus 1 / 16 of a Gaussian of sigma_s cells, and R (1024,) =
+    max(1, rint(65536 exp(-(k + 0.5) / 64))); every entry of both is >= 1."""
+    import numpy as np
+    factor, radius, sigma_s, _ = _check_upsample(factor, radius, sigma_s, 1.0)
+    S, R = np.zeros(factor * factor * (2 * radius + 1) ** 2, np.uint32), np.zeros(UPSAMPLE_BINS, np.uint32)
+    U = ctypes.POINTER(ctypes.c_uint)
+    capi._chk(capi.load().papof_upsample_tables(factor, radius, sigma_s, S.ctypes.data_as(U), R.ctypes.data_as(U)),
+              "papof_upsample_tables")
+    return S, R
+
+
+def upsample_q(sigma_c, channels):
+    """The factor q of papof_upsample_flow_tensor, in fp64: 32 / (sigma_c^2 C) (both guides are in the scale 0 .. 1)"""
+    return 32.0 / (sigma_c * sigma_c * channels)
+
+
+def _lr_size(H, W, factor):
+    return -(-H // factor), -(-W // factor)
+
+
+def _check_channels(name, C, layout):
+    if not 1 <= C <= MAX_CHANNELS:
+        raise ValueError("%s must have 1 .. %d channels, got %d (layout %s)" % (name, MAX_CHANNELS, C, layout))
+
+
+def _decimate(t, desc, factor, layout, out_dtype):
+    """papof_decimate_tensor on the current stream of the frames' device: the new tensor in `layout`"""
+    (N, H, W, C), strides, code = desc
+    h, w = _lr_size(H, W, factor)
+    out, d_out = _new_frames(N, h, w, C, layout, out_dtype, t.device)
+    d_in = _struct(t, strides, code)
+    _launch(t.device, "papof_decimate_tensor", N, H, W, C, factor, ctypes.byref(d_in), ctypes.byref(d_out))
+    return out
+
+
+def decimate(frames, factor, *, layout="NCHW", out_dtype=None):
+    """Box decimation of frames by `factor` in {2, 3, 4}: frames (N, C, H, W) or (N, H, W, C) by `layout` (3-D: one frame),
+    C in 1 .. 4, uint8, float32 or float64, any strides, on a HIP device.  Returns a new tensor of out_dtype (float64 by
+    default, or float32) in the same layout at ceil(H / factor) x ceil(W / factor): each pixel is the mean of the pixels of
+    its factor x factor block that exist (edge blocks are clipped, so no row or column is dropped), a uint8 sample read as
+    x / 255.0, summed in row-major order in float64 (include/papof.h: papof_decimate_tensor).  Enqueued on the current
+    stream; returns without waiting."""
+    factor = _check_factor(factor)
+    ts, descs, out_dtype, _ = _check([("frames", frames)], layout, out_dtype, 1)
+    _check_channels("frames", descs[0][0][3], layout)
+    return _decimate(ts[0], descs[0], factor, layout, out_dtype)
+
+
+def _check_guide_lr(guide_lr, shape, layout, dev):
+    """a given low-resolution guide: the 4-D tensor and its descriptor -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    g = _as4d("guide_lr", guide_lr)
+    sizes, strides, code = descriptor(g, layout)
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError("guide_lr must be float32 or float64 (decimate's output), got %s" % g.dtype)
+    if sizes != shape:
+        raise ValueError("guide_lr must be %s (items, rows, columns, channels) for this guide and factor, got %s" % (shape, sizes))
+    if g.device != dev:
+        raise ValueError("guide_lr is on %s, the guide on %s: all must be on one device" % (g.device, dev))
+    return g, (sizes, strides, code)
+
+
+def _upsample(flow_lr, code, guide, desc, guide_lr, desc_lr, d_occ, factor, radius, sigma_s, sigma_c, out_dtype):
+    """papof_upsample_flow_tensor on the current stream of the flow's device"""
+    torch = _torch()
+    (B, H, W, C), strides, g_code = desc
+    dev = flow_lr.device
+    d_S, d_R = _device_tables(dev, radius, sigma_s, factor)
+    out = torch.empty((B, 2, H, W), dtype=out_dtype, device=dev)
+    d_flow, d_guide, d_out = _flow_struct(flow_lr, code), _struct(guide, strides, g_code), _flow_struct(out, _out_code(out_dtype))
+    d_lr = _struct(guide_lr, *desc_lr[1:])
+    _launch(dev, "papof_upsample_flow_tensor", B, H, W, C, factor, ctypes.byref(d_flow), ctypes.byref(d_guide),
+            ctypes.byref(d_lr), _ref(d_occ), radius, ctypes.c_void_p(d_S.data_ptr()), ctypes.c_void_p(d_R.data_ptr()),
+            upsample_q(sigma_c, C), ctypes.byref(d_out))
+    return out
+
+
+def upsample_flow(flow_lr, guide, factor, *, guide_lr=None, occlusion=None, radius=UP_RADIUS, sigma_s=UP_SIGMA_S,
+                  sigma_c=UP_SIGMA_C, layout="NCHW", out_dtype=None):
+    """Edge-aware up-sampling of a flow that was estimated on decimated frames: joint bilateral upsampling (Kopf, Cohen,
+    Lischinski, Uyttendaele 2007) guided by the full-resolution frame.
+    flow_lr: (B, 2, h, w) float32 / float64, any strides, on a HIP device, in low-resolution pixels.  guide: (B, C, H, W) or
+    (B, H, W, C) by `layout` (3-D: one item), C in 1 .. 4, uint8 (read as x / 255.0), float32 or float64 (taken to be scaled
+    to 0 .. 1), with ceil(H / factor) = h and ceil(W / factor) = w -- usually the frame the flow starts from.  guide_lr:
+    None -- decimate(guide, factor) is computed -- or that tensor, float32 / float64 in `layout`; a caller that has it passes
+    it.  occlusion: None or a (B, h, w) bool / uint8 mask, nonzero = this cell's flow is not to be trusted.
+    Each output pixel is `factor` times the weighted mean of the flows of the cells within `radius` (0 .. 3) of its own
+    cell, weighted by an integer spatial table (the bilinear tent plus a Gaussian reach of sigma_s cells) times an integer
+    range table of the colour difference between the guide at the pixel and the decimated guide at the cell,
+    exp(-d2 / (2 sigma_c^2)) with d2 the mean squared difference over the channels; cells outside the grid, occluded or
+    not finite have no weight, every other cell has some, and a pixel whose cells are all dead gets `factor` times its own
+    cell's flow as it is.  Products and sums are float64 in a stated order: bitwise reproducible; include/papof.h
+    (papof_upsample_flow_tensor) states the rule exactly.  Where the guide is flat the result is close to bilinear
+    up-sampling; it invents no motion that the low-resolution grid lost.  Returns the flow (B, 2, H, W) of out_dtype
+    (float32 / float64; by default flow_lr's), a new tensor.  Enqueued on the current stream; returns without waiting."""
+    torch = _torch()
+    factor, radius, sigma_s, sigma_c = _check_upsample(factor, radius, sigma_s, sigma_c)
+    ts, descs, _, _ = _check([("guide", guide)], layout, None, 1)
+    (B, H, W, C), _, _ = descs[0]
+    _check_channels("the guide", C, layout)
+    dev = ts[0].device
+    h, w = _lr_size(H, W, factor)
+    code = _check_flow("flow_lr", flow_lr)
+    if tuple(flow_lr.shape) != (B, 2, h, w):
+        raise ValueError("flow_lr must be %s for this guide and factor, got %s" % ((B, 2, h, w), tuple(flow_lr.shape)))
+    if flow_lr.device != dev:
+        raise ValueError("flow_lr is on %s, the guide on %s: all must be on one device" % (flow_lr.device, dev))
+    out_dtype = flow_lr.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.float32 or torch.float64, got %s" % out_dtype)
+    d_occ, _keep = _check_plane_mask("occlusion", occlusion, (B, h, w), dev)
+    if guide_lr is not None:
+        g_lr, desc_lr = _check_guide_lr(guide_lr, (B, h, w, C), layout, dev)
+    else:
+        g_lr = _decimate(ts[0], descs[0], factor, layout, torch.float64)
+        desc_lr = descriptor(g_lr, layout)
+    return _upsample(flow_lr, code, ts[0], descs[0], g_lr, desc_lr, d_occ, factor, radius, sigma_s, sigma_c, out_dtype)
+
+
+def _check_lr(factor, refine_levels, radius, sigma_s, sigma_c):
+    if isinstance(refine_levels, bool) or not isinstance(refine_levels, int):
+        raise TypeError("refine_levels must be an int, got %r" % (refine_levels,))
+    if refine_levels < 0:
+        raise ValueError("refine_levels must be >= 0, got %d" % refine_levels)
+    return (*_check_upsample(factor, radius, sigma_s, sigma_c), refine_levels)
+
+
+def _run_lr(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, lr):
+    torch = _torch()
+    factor, radius, sigma_s, sigma_c, refine_levels = lr
+    _check_channels("the frames", descs[0][0][3], layout)
+    lo = [_decimate(t, d, factor, layout, torch.float64) for t, d in zip(ts, descs)]
+    lo_descs = [descriptor(t, layout) for t in lo]
+    low = _run_fb(lo, lo_descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params)
+    # forward flows: guided by the first frames, channel 0 of the mask; backward flows: the second frames, channel 1
+    ends = ((ts[0][:-1], lo[0][:-1]), (ts[0][1:], lo[0][1:])) if sequence else ((ts[0], lo[0]), (ts[1], lo[1]))
+    flows = []
+    for k, (flow, (g, g_lr)) in enumerate(zip((low.flow_fw, low.flow_bw), ends)):
+        d_occ, _keep = _check_plane_mask("occlusion", low.occlusion[:, k] if low.occlusion is not None else None,
+                                         tuple(flow.shape[i] for i in (0, 2, 3)), flow.device)
+        flows.append(_upsample(flow, _out_code(out_dtype), g, descriptor(g, layout), g_lr, descriptor(g_lr, layout), d_occ,
+                               factor, radius, sigma_s, sigma_c, out_dtype))
+    if refine_levels == 0:
+        occ = fb_consistency(flows[0], flows[1], *alphas[1:]) if alphas[0] else None
+        return FlowFB(flows[0], flows[1], None, None, occ, low.timing)
+    return _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, refine_levels, alphas, params, flows[0], flows[1])
+
+
+def flow_pairs_lr(im1, im2, pyramidLevels, *, factor=2, refine_levels=0, radius=UP_RADIUS, sigma_s=UP_SIGMA_S,
+                  sigma_c=UP_SIGMA_C, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """Flow of the independent pairs (im1[i], im2[i]) estimated at reduced resolution: decimate both frames by `factor`
+    (2, 3 or 4), flow_pairs_fb(..., pyramidLevels, ...) on the decimated frames, upsample_flow (radius, sigma_s, sigma_c)
+    of the forward flows guided by im1 with channel 0 of the low-resolution occlusion mask and of the backward flows guided
+    by im2 with channel 1, and then
+      refine_levels = 0: fb_consistency(*consistency) on the up-sampled flows -- nothing warps a frame at full resolution,
+        so warpI2_fw and warpI2_bw are None (refine_levels=1 gives them) and timing is the low-resolution call's;
+      refine_levels >= 1: flow_pairs_fb(im1, im2, refine_levels, init_flow=, init_flow_bw=) from the up-sampled flows at
+        full resolution, bit for bit what that call returns.
+    Returns a FlowFB, so every call built on the flows takes the result as it is.  The solver runs on 1 / factor^2 of the
+    pixels and a pyramid level of the decimated frames is `factor` times coarser than the same level of the frames: use one
+    level fewer at factor 2.  When NOT to use it: an object thinner than `factor` pixels is gone before the up-sampler sees
+    it, sub-pixel detail inside regions is the low-resolution solver's, and small frames are bound by launches, not by
+    pixels, and gain little.  Frames of C = 1 .. 4 channels; `solver` as flow_pairs_fb's.  Every argument error of this
+    call's own arguments raises before anything is launched."""
+    alphas = _alphas(consistency)
+    lr = _check_lr(factor, refine_levels, radius, sigma_s, sigma_c)
+    ts, descs, out_dtype, params = _check([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, solver=solver)
+    return _run_lr(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, params, lr)
+
+
+def flow_video_lr(frames, pyramidLevels, *, factor=2, refine_levels=0, radius=UP_RADIUS, sigma_s=UP_SIGMA_S,
+                  sigma_c=UP_SIGMA_C, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """flow_pairs_lr on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames: every frame is decimated once,
+    flow_video_fb runs on the decimated frames, forward flows are up-sampled with frames[:-1] as guide and backward flows
+    with frames[1:], as refine_video_flows pairs them."""
+    alphas = _alphas(consistency)
+    lr = _check_lr(factor, refine_levels, radius, sigma_s, sigma_c)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
+    return _run_lr(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, lr)
