@@ -1161,6 +1161,50 @@ int papof_motion_blur_tensor(papof_handle* h, int n_frames, const papof_tensor* 
                              int n_samples, const double* offsets, const double* weights, const papof_tensor* out,
                              void* stream);
 
+/* Video mosaics (mosaic.hip: k_mosaic): many frames, each through its own affine matrix, gathered into one output pixel and
+ * combined there -- the panorama of a panning shot, its clean plate (the per-pixel temporal median: what moved is gone),
+ * and the borders of a stabilized frame filled from the frames around it.  One kernel, one lane per output pixel, the
+ * samples of a pixel held in registers or LDS: no full-canvas temporary per source, no atomics.
+ * frames: n_frames frames of height x width x c (H, W, C), uint8 (x / 255.0), float32 (widened exactly) or float64, (frame,
+ * row, column, channel), any non-negative strides.  masks: NULL, or uint8 (frame, row, column), any non-negative strides
+ * (stride[3] is not read): nonzero = this pixel of the frame is left out.
+ * There are n_out outputs of out_height x out_width (Hc, Wc), each with n_src = N source slots.  sources: DEVICE pointer
+ * to n_out * N int32, contiguous (out, k): the frame of slot k, or a negative number for an empty slot; an index
+ * >= n_frames is the caller's error (it is not checked here).  matrices: float32 (widened exactly) or float64, (out, k, row,
+ * column), 2 x 3 each, any non-negative strides.
+ * At output pixel (o, r, x), in fp64 without fused multiply-adds, everything papof_warp_affine_tensor states reused as it
+ * stands, the slots are visited in the order k = 0 .. N - 1:
+ *     s = sources[o, k];  s < 0: the slot is dead
+ *     M = matrices[o, k];  X = (m00 * x + m01 * r) + m02;  Y = (m10 * x + m11 * r) + m12
+ *     the slot is LIVE when (X, Y) lies in [0, W - 1] x [0, H - 1] (false for a NaN) and, with masks, the mask of frame s
+ *     is 0 at every tap of the bilinear rule at (X, Y) whose weight is > 0 (a tap of weight 0 is not looked at)
+ *     its sample, per channel, is frames[s] under the bilinear rule of papof_interp_tensor at (X, Y) (truncation toward
+ *     zero, fraction clamped to [0, 1], neighbours clamped into the image, taps accumulated from 0.0 in (m, n) order)
+ * n = the number of live slots; count (NULL, or uint8 (out, row, column), strides [0..2] > 0) receives n.  n = 0: every
+ * channel is 0.  Otherwise, by mode:
+ *     PAPOF_MOSAIC_FIRST   the sample of the live slot with the smallest k
+ *     PAPOF_MOSAIC_MEAN    the live samples added from 0.0 in k order, divided by (double)n
+ *     PAPOF_MOSAIC_MEDIAN  per channel, the live samples ordered by (value, k): a sorts before b when a < b, or when a is
+ *                          not NaN and b is; samples that compare equal (-0.0 and +0.0 included) and NaNs among themselves
+ *                          are ordered by k.  The result is the element at index (n - 1) / 2 (the lower median): the bits
+ *                          of one sample, the same on every run.
+ * out: uint8, float32 or float64, (out, row, column, channel), strides > 0, stored as papof_interp_tensor stores (uint8 =
+ * clamp(rint(255 v), 0, 255), half to even, NaN -> 0).  out and count must not overlap the inputs.
+ * A tile of output pixels drops a slot whose matrix sends the tile's corners to a box that misses the frame: every step of
+ * X and Y is monotone in x and r under rounding, so this changes no byte.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting;
+ * the handle's arena is not used.  PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (masks and count
+ * aside), data pointer or sources, frames or out that are not uint8 / float32 / float64, matrices that are not float32 /
+ * float64, masks or count that are not uint8, a negative stride, a zero stride of out or count along an axis in use,
+ * n_frames, height, width, c, n_out, out_height or out_width < 1, n_src outside 1 .. PAPOF_MOSAIC_MAX_SOURCES, a mode that
+ * is none of the three, PAPOF_MOSAIC_MEDIAN with n_src > PAPOF_MOSAIC_MAX_MEDIAN. */
+enum { PAPOF_MOSAIC_FIRST = 0, PAPOF_MOSAIC_MEAN = 1, PAPOF_MOSAIC_MEDIAN = 2 };
+enum { PAPOF_MOSAIC_MAX_SOURCES = 255, PAPOF_MOSAIC_MAX_MEDIAN = 64 };
+int papof_mosaic_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                        const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
+                        const papof_tensor* matrices, int mode, const papof_tensor* out, const papof_tensor* count,
+                        void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -102,6 +102,15 @@ factor 2.
 
     fb = flow_video_lr(frames, 4, factor=2, layout="NHWC")   # a FlowFB, as flow_video_fb's (warpI2_* None unless refined)
 
+Video mosaics: `mosaic` (include/papof.h: papof_mosaic_tensor) gathers many frames, each through its own affine matrix, into
+one output pixel and keeps the first that covers it, their mean or their median -- one HIP kernel, the samples held on
+chip; `mosaic_transforms` and `neighbour_transforms` make its matrices from global motions on the host; `panorama` chains
+flow_video, global_motion and them (mode "median": the clean plate, what moved is gone); `stabilize_video_full` is
+stabilize_video with the empty borders filled from the neighbouring frames.
+
+    pano = panorama(frames, 5, mode="median", layout="NHWC")       # pano.image (Hc, Wc, C), pano.count (Hc, Wc)
+    sv = stabilize_video_full(frames, 5, layout="NHWC")            # sv.video, sv.valid, sv.filled
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -968,6 +977,16 @@ def _check_path(radius, crop, size):
     return (W - 1) / 2.0, (H - 1) / 2.0
 
 
+def _checked_motion(motion):
+    """a Motion or a (T - 1, 2, 3) tensor as it is -- TypeError / ValueError otherwise"""
+    m = motion.motion if isinstance(motion, Motion) else motion
+    if not isinstance(m, _torch().Tensor):
+        raise TypeError("motion must be a torch.Tensor or a Motion, got %s" % type(m).__name__)
+    if m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or m.shape[0] < 1:
+        raise ValueError("motion must be (T - 1, 2, 3) with T >= 2, got shape %s" % (tuple(m.shape),))
+    return motion
+
+
 def stabilizing_transforms(motion, radius=15, crop=1.0, *, size=None):
     """The sampling matrices that stabilize a video of T frames whose consecutive pairs move by `motion` -- a (T - 1, 2, 3)
     tensor (global_motion's, any device) or a Motion, whose pairs with ok False enter as the identity.  In float64 on the
@@ -978,24 +997,15 @@ def stabilizing_transforms(motion, radius=15, crop=1.0, *, size=None):
                                                             the borders; size is needed only for crop < 1)
     and stabilized frame t is frame t sampled at M_t q (warp_affine(frames, M)).  radius = 0: no smoothing, S_t = P_t.
     Returns M (T, 2, 3) float64 on the motion's device."""
-    import numpy as np
-    torch = _torch()
-    ok = None
-    if isinstance(motion, Motion):
-        motion, ok = motion.motion, motion.ok
-    if not isinstance(motion, torch.Tensor):
-        raise TypeError("motion must be a torch.Tensor or a Motion, got %s" % type(motion).__name__)
-    if motion.dim() != 3 or tuple(motion.shape[1:]) != (2, 3) or motion.shape[0] < 1:
-        raise ValueError("motion must be (T - 1, 2, 3) with T >= 2, got shape %s" % (tuple(motion.shape),))
+    motion = _checked_motion(motion)
     cx, cy = _check_path(radius, crop, size)
-    A = motion.detach().to("cpu", torch.float64).numpy()
-    if ok is not None:
-        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(2, 3))
-    return torch.from_numpy(path_transforms(A, radius, crop, cx, cy)).to(motion.device)
+    A, dev = _pair_motions(motion)
+    return _torch().from_numpy(path_transforms(A, radius, crop, cx, cy)).to(dev)
 
 
-def path_transforms(A, radius, crop, cx, cy):
-    """stabilizing_transforms on a numpy (T - 1, 2, 3) float64 array, c = (cx, cy): (T, 2, 3) float64"""
+def camera_path(A):
+    """the camera path P (T, 3, 3) of pair motions A (T - 1, 2, 3), numpy float64: P_0 = I, P_{t+1} = A_t P_t -- frame 0's
+    coordinates to frame t's"""
     import numpy as np
     n = A.shape[0] + 1
     P = np.empty((n, 3, 3))
@@ -1004,6 +1014,14 @@ def path_transforms(A, radius, crop, cx, cy):
         At = np.eye(3)
         At[:2] = A[t]
         P[t + 1] = At @ P[t]
+    return P
+
+
+def path_transforms(A, radius, crop, cx, cy):
+    """stabilizing_transforms on a numpy (T - 1, 2, 3) float64 array, c = (cx, cy): (T, 2, 3) float64"""
+    import numpy as np
+    n = A.shape[0] + 1
+    P = camera_path(A)
     Z = np.array([[crop, 0.0, cx - crop * cx], [0.0, crop, cy - crop * cy], [0.0, 0.0, 1.0]])
     M = np.empty((n, 2, 3))
     for t in range(n):
@@ -2247,3 +2265,298 @@ def flow_video_lr(frames, pyramidLevels, *, factor=2, refine_levels=0, radius=UP
     lr = _check_lr(factor, refine_levels, radius, sigma_s, sigma_c)
     ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
     return _run_lr(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, lr)
+
+
+# ---- video mosaics (include/papof.h: papof_mosaic_tensor) -------------------------------------------------------------------
+Mosaic = collections.namedtuple("Mosaic", "out count")
+Panorama = collections.namedtuple("Panorama", "image count matrices origin motion ok flow timing")
+StabilizedFull = collections.namedtuple("StabilizedFull", "video valid filled transforms motion ok flow timing")
+MOSAIC_MODES = {"first": capi.MOSAIC_FIRST, "mean": capi.MOSAIC_MEAN, "median": capi.MOSAIC_MEDIAN}
+MAX_SOURCES = capi.MOSAIC_MAX_SOURCES  # source slots of one output
+MAX_MEDIAN = capi.MOSAIC_MAX_MEDIAN    # of them under mode="median"
+MAX_PIXELS = 2 ** 26                   # mosaic_transforms: the largest canvas it returns unasked
+
+
+def _check_mode(mode):
+    if mode not in MOSAIC_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(MOSAIC_MODES), mode))
+    return MOSAIC_MODES[mode]
+
+
+def _check_canvas(size):
+    try:
+        Hc, Wc = size
+    except (TypeError, ValueError):
+        raise TypeError("size must be (H, W), got %r" % (size,)) from None
+    if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in (Hc, Wc)):
+        raise ValueError("size must be two integers >= 1, got %r" % (size,))
+    return Hc, Wc
+
+
+def _check_slots(mode, n, what="matrices have"):
+    if not 1 <= n <= MAX_SOURCES:
+        raise ValueError("%s %d sources per output, the kernel takes 1 .. %d" % (what, n, MAX_SOURCES))
+    if mode == "median" and n > MAX_MEDIAN:
+        raise ValueError("%s %d sources per output, mode=\"median\" takes 1 .. %d" % (what, n, MAX_MEDIAN))
+
+
+def _check_mosaic_matrices(matrices, dev):
+    """(dtype code, n_out, N) of matrices (n_out, N, 2, 3) float32 / float64 on `dev` -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if not isinstance(matrices, torch.Tensor):
+        raise TypeError("matrices must be a torch.Tensor, got %s" % type(matrices).__name__)
+    if matrices.dtype not in codes:
+        raise TypeError("matrices must be float32 or float64, got %s" % matrices.dtype)
+    if matrices.dim() != 4 or tuple(matrices.shape[2:]) != (2, 3) or min(matrices.shape[:2]) < 1:
+        raise ValueError("matrices must be (n_out, N, 2, 3), got %s" % (tuple(matrices.shape),))
+    if matrices.device != dev:
+        raise ValueError("matrices are on %s, the frames on %s: both must be on one device" % (matrices.device, dev))
+    return codes[matrices.dtype], int(matrices.shape[0]), int(matrices.shape[1])
+
+
+def _check_sources(sources, n_out, N, T):
+    """the sources as a contiguous int32 host tensor (n_out, N), or None for None: "source k is frame k" (N = T); an integer
+    tensor (any device: read on the host) or array otherwise, every entry < T -- TypeError / ValueError otherwise"""
+    import numpy as np
+    torch = _torch()
+    if sources is None:
+        if N != T:
+            raise ValueError("sources=None is frame k for source k: matrices have %d sources for %d frames" % (N, T))
+        return None
+    if isinstance(sources, torch.Tensor):
+        if sources.dtype.is_floating_point or sources.dtype.is_complex or sources.dtype == torch.bool:
+            raise TypeError("sources must hold integers, got %s" % sources.dtype)
+        s = sources.detach().to("cpu", torch.int64)
+    else:
+        try:
+            a = np.asarray(sources)
+        except Exception:  # noqa: BLE001
+            raise TypeError("sources must be None, an integer tensor or an integer array, got %r" % (sources,)) from None
+        if a.dtype.kind not in "iu":
+            raise TypeError("sources must hold integers, got %s" % a.dtype)
+        s = torch.from_numpy(np.ascontiguousarray(a).astype(np.int64))
+    if tuple(s.shape) != (n_out, N):
+        raise ValueError("sources must be (n_out, N) = %s as the matrices, got %s" % ((n_out, N), tuple(s.shape)))
+    if int(s.max()) >= T:
+        raise ValueError("sources name frame %d of %d frames" % (int(s.max()), T))
+    return s.clamp(min=-1).to(torch.int32).contiguous()
+
+
+def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True):
+    """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
+    count False: no count (None is returned for it; mode "first" then stops at the first live source)"""
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    n_out, N = int(src.shape[0]), int(src.shape[1])
+    out, d_out = _new_frames(n_out, Hc, Wc, C, layout, out_dtype, dev)
+    cnt = torch.empty((n_out, Hc, Wc), dtype=torch.uint8, device=dev) if count else None
+    d_in = _struct(ts[0], strides, code)
+    d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
+    d_mask = _mask_struct(masks) if masks is not None else None
+    d_cnt = _mask_struct(cnt) if count else None
+    _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+    return out, cnt
+
+
+def mosaic(frames, sources, matrices, size, *, mode="median", masks=None, layout="NCHW", out_dtype=None):
+    """Many frames, each through its own affine matrix, gathered into one output pixel and combined there: frames (T, C, H,
+    W) or (T, H, W, C) by `layout`, uint8 (read as x / 255), float32 or float64, any strides, on a HIP device; size = (Hc,
+    Wc) of the n_out outputs; matrices (n_out, N, 2, 3) float32 / float64 on the same device, N <= 255 sources per output
+    (64 for the median); sources (n_out, N) integers, any device or a numpy array -- the frame of each source, negative: an
+    empty slot -- or None: source k is frame k; masks None or (T, H, W) bool / uint8: nonzero pixels of a frame are left
+    out.  At output pixel (x, y) source k is LIVE where matrices[o, k] (x, y, 1) lies inside its frame and, with masks, no
+    bilinear tap of positive weight there is masked; its sample is the frame read bilinearly (the rule of warp_affine).
+    mode "first": the live source with the smallest k; "mean": the live samples added in k order over their number;
+    "median": per channel the lower median of the live samples, ties broken by k, NaN last -- the bits of one sample.
+    Returns Mosaic(out (n_out, C, Hc, Wc) or (n_out, Hc, Wc, C) of out_dtype (by default the frames'), 0 where no source
+    is live; count (n_out, Hc, Wc) uint8: the live sources).  include/papof.h (papof_mosaic_tensor) states it exactly;
+    bitwise reproducible.  The sources are checked on the host (a device tensor of sources waits for its stream); the kernel
+    is enqueued on the current stream and the call returns without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    Hc, Wc = _check_canvas(size)
+    (T, H, W, _), _, _ = descs[0]
+    dev = ts[0].device
+    m_code, n_out, N = _check_mosaic_matrices(matrices, dev)
+    src = _check_sources(sources, n_out, N, T)
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    _check_slots(mode, N)
+    if src is None:  # made on the device, on the current stream
+        src = _torch().arange(T, dtype=_torch().int32, device=dev).repeat(n_out, 1)
+    elif dev.type == "cuda":  # from page-locked memory: the copy is queued, the host does not wait for the stream
+        src = src.pin_memory().to(dev, non_blocking=True)
+    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype))
+
+
+def _pair_motions(motion):
+    """the (T - 1, 2, 3) float64 numpy array (pairs of a Motion with ok False: the identity) and the device of a motion that
+    _checked_motion has accepted"""
+    import numpy as np
+    ok = None
+    if isinstance(motion, Motion):
+        motion, ok = motion.motion, motion.ok
+    A = motion.detach().to("cpu", _torch().float64).numpy()
+    if ok is not None:
+        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(2, 3))
+    return A, motion.device
+
+
+def _int_at_least(name, v, lo):
+    if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+        raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))
+    return v
+
+
+def _check_ref(ref, T):
+    if ref is None:
+        return (T - 1) // 2
+    if isinstance(ref, bool) or not isinstance(ref, int) or not 0 <= ref < T:
+        raise ValueError("ref must be None or a frame index in 0 .. %d, got %r" % (T - 1, ref))
+    return ref
+
+
+def mosaic_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PIXELS):
+    """The canvas of a video's panorama and the matrices that fill it: motion a (T - 1, 2, 3) tensor (global_motion's, any
+    device) or a Motion (pairs with ok False enter as the identity), size = (H, W) of the frames.  In float64 on the host,
+    with P_t the camera path of stabilizing_transforms and `ref` (default (T - 1) // 2) the frame whose coordinates the
+    canvas keeps: the corners of every frame are mapped into the reference frame by P_ref P_t^-1; (x0, y0) is the floor of
+    their minima less `margin`, and the canvas reaches the ceiling of their maxima plus `margin`; canvas pixel q samples
+    frame t at matrix_t q, matrix_t = P_t P_ref^-1 translate(x0, y0).  Returns (matrices (1, T, 2, 3) float64 on the
+    motion's device -- mosaic's, for sources=None --, (Hc, Wc), (x0, y0)).  ValueError when the bounds are not finite or
+    Hc * Wc > max_pixels: a chain that drifted, or a shot that is no pan."""
+    import numpy as np
+    torch = _torch()
+    A, dev = _pair_motions(_checked_motion(motion))
+    H, W = _check_canvas(size)
+    T = A.shape[0] + 1
+    ref = _check_ref(ref, T)
+    _int_at_least("margin", margin, 0)
+    _int_at_least("max_pixels", max_pixels, 1)
+    corners = np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
+    # P_ref P_t^-1 as the chain of pair motions between t and ref, so that the reference frame and frames that do not
+    # move against it (pairs with ok False) map to their own integer corners exactly: no floor or ceiling of 1e-16
+    to_ref = [np.eye(3)] * T
+    with np.errstate(all="ignore"):
+        try:
+            for t in range(ref - 1, -1, -1):
+                to_ref[t] = to_ref[t + 1] @ np.vstack([A[t], [0.0, 0.0, 1.0]])
+            for t in range(ref + 1, T):
+                to_ref[t] = to_ref[t - 1] @ np.linalg.inv(np.vstack([A[t - 1], [0.0, 0.0, 1.0]]))
+            pts = np.stack([(m @ corners)[:2] for m in to_ref])  # (T, 2, 4)
+            from_ref = [np.linalg.inv(m) for m in to_ref]
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular: no canvas") from None
+    if not (np.isfinite(pts).all() and np.isfinite(np.array(from_ref)).all()):
+        raise ValueError("the bounds of the canvas are not finite")
+    x0, y0 = math.floor(pts[:, 0].min()) - margin, math.floor(pts[:, 1].min()) - margin
+    Wc, Hc = math.ceil(pts[:, 0].max()) + margin - x0 + 1, math.ceil(pts[:, 1].max()) + margin - y0 + 1
+    if Hc * Wc > max_pixels:
+        raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+    shift = np.array([[1.0, 0.0, x0], [0.0, 1.0, y0], [0.0, 0.0, 1.0]])
+    M = np.stack([(m @ shift)[:2] for m in from_ref])[None]
+    return torch.from_numpy(M).to(dev), (Hc, Wc), (x0, y0)
+
+
+def neighbour_transforms(transforms, motion, radius):
+    """The sources and matrices that fill each stabilized frame from the frames around it: transforms (T, 2, 3) the
+    sampling matrices M_t of stabilizing_transforms, motion the pair motions they came from (a tensor or a Motion), radius
+    >= 0 frames to either side (2 radius + 1 <= 255).  In float64 on the host: slot 0 is frame t itself through M_t; slot
+    2 d - 1 is frame t - d and slot 2 d frame t + d, each through P_s P_t^-1 M_t -- the stabilized pixel to frame t, then
+    along the camera path to frame s; the source is -1 where s is outside the video.  Returns (sources (T, 2 radius + 1)
+    int32, matrices (T, 2 radius + 1, 2, 3) float64), both on the transforms' device: mosaic's, mode "first" prefers the
+    frame itself, then the nearest in time."""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(transforms, torch.Tensor):
+        raise TypeError("transforms must be a torch.Tensor, got %s" % type(transforms).__name__)
+    A, _ = _pair_motions(_checked_motion(motion))
+    T = A.shape[0] + 1
+    if tuple(transforms.shape) != (T, 2, 3):
+        raise ValueError("transforms must be (T, 2, 3) = %s as the motion, got %s" % ((T, 2, 3), tuple(transforms.shape)))
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= 2 * radius + 1 <= MAX_SOURCES:
+        raise ValueError("radius must be an integer in 0 .. %d, got %r" % ((MAX_SOURCES - 1) // 2, radius))
+    Mt = transforms.detach().to("cpu", torch.float64).numpy()
+    P = camera_path(A)
+    N = 2 * radius + 1
+    src = np.full((T, N), -1, np.int32)
+    mats = np.tile(np.eye(2, 3), (T, N, 1, 1))
+    for t in range(T):
+        M3 = np.vstack([Mt[t], [0.0, 0.0, 1.0]])
+        try:
+            back = np.linalg.inv(P[t]) @ M3
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular at frame %d: no way back from it" % t) from None
+        src[t, 0], mats[t, 0] = t, Mt[t]
+        for d in range(1, radius + 1):
+            for slot, s in ((2 * d - 1, t - d), (2 * d, t + d)):
+                if 0 <= s < T:
+                    src[t, slot], mats[t, slot] = s, (P[s] @ back)[:2]
+    return torch.from_numpy(src).to(transforms.device), torch.from_numpy(mats).to(transforms.device)
+
+
+def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0, masks=None, model="affine", iters=5,
+             scale=1.0, layout="NCHW", out_dtype=None, **solver):
+    """The panorama of a panning video of T >= 2 frames -- with mode "median" its clean plate: what moved in front of the
+    background is gone wherever the background shows in more than half of the frames that cover a pixel.
+    flow_video(frames, pyramidLevels, layout=layout, **solver), global_motion on the flows (model, iters, scale),
+    mosaic_transforms (ref, margin; the only wait) and ONE mosaic of the frames 0, step, 2 step, ... (masks: (T, H, W),
+    nonzero pixels are left out).  The motion is chained over all pairs whatever the step.  At most 255 frames are
+    deposited, 64 under "median": a larger video needs a larger `step`.  Returns Panorama(image (C, Hc, Wc) or (Hc, Wc, C)
+    of out_dtype (by default the frames'), count (Hc, Wc) uint8, matrices (T, 2, 3) float64 -- canvas to frame t, of every
+    frame --, origin (x0, y0): the canvas pixel (0, 0) in the reference frame's coordinates, motion (T - 1, 2, 3), ok
+    (T - 1,) bool, flow (T - 1, 2, H, W) float64, timing of the flow call).  The model is affine: there is no projective
+    warp, no bundle adjustment, no exposure compensation and no seam blending (README).  Every argument error raises
+    before anything is launched."""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    code, iters, scale = _check_fit(model, iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    ref = _check_ref(ref, T)
+    _int_at_least("step", step, 1)
+    _int_at_least("margin", margin, 0)
+    dev = ts[0].device
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    picked = list(range(0, T, step))
+    _check_slots(mode, len(picked), "step = %d deposits" % step)
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    mo = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
+    M, (Hc, Wc), origin = mosaic_transforms(mo, (H, W), ref=ref, margin=margin)
+    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
+    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype)
+    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing)
+
+
+def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW", model="similarity", radius=15, crop=1.0,
+                         iters=5, scale=1.0, out_dtype=None, **solver):
+    """stabilize_video whose frames have no empty border: where stabilized frame t does not cover a pixel, the frames
+    t - 1, t + 1, t - 2, ... t +- fill_radius that saw it supply it, registered by the same global motions -- the final
+    warp_affine replaced by ONE mosaic(..., mode="first") over neighbour_transforms.  Returns StabilizedFull(video, valid
+    (T, H, W) bool as stabilize_video gives it -- where it holds, the video is stabilize_video's byte for byte --, filled
+    (T, H, W) bool: not valid, and supplied by a neighbour; transforms, motion, ok, flow, timing as stabilize_video).
+    Pixels that are neither stay 0.  Registration is by the global motion alone: where the scene has parallax a filled
+    border mis-registers; there is no local motion inpainting (README).  Every argument error raises before anything is
+    launched; the video is enqueued on the current stream."""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    code, iters, scale = _check_fit(model, iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    _check_path(radius, crop, (H, W))
+    if isinstance(fill_radius, bool) or not isinstance(fill_radius, int) or not 0 <= 2 * fill_radius + 1 <= MAX_SOURCES:
+        raise ValueError("fill_radius must be an integer in 0 .. %d, got %r" % ((MAX_SOURCES - 1) // 2, fill_radius))
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    torch = _torch()
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, params)
+    m = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
+    M = stabilizing_transforms(m, radius, crop, size=(H, W))
+    src, mats = neighbour_transforms(M, m, fill_radius)
+    video, count = _mosaic(ts, descs, src, mats, capi.DTYPE_F64, None, H, W, "first", layout, out_dtype)
+    # valid: slot 0 alone, on one channel (a view), through the same kernel -- its count is the frame's own coverage
+    one = ts[0][:, :1] if layout == "NCHW" else ts[0][..., :1]
+    _, own = _mosaic([one], [descriptor(one, layout)], src[:, :1].contiguous(), mats[:, :1], capi.DTYPE_F64, None, H, W,
+                     "first", layout, torch.uint8)
+    valid = own > 0
+    return StabilizedFull(video, valid, (count > 0) & ~valid, M, m.motion, m.ok, flow, timing)
