@@ -1205,6 +1205,42 @@ int papof_mosaic_tensor(papof_handle* h, int n_frames, int height, int width, in
                         const papof_tensor* matrices, int mode, const papof_tensor* out, const papof_tensor* count,
                         void* stream);
 
+/* Seamless mosaics: papof_mosaic_tensor with a gain per slot and a feathered mode (k_mosaic, the same kernel), and the
+ * pairwise overlap statistics from which the gains are solved (k_mosaic_overlap; Brown and Lowe 2007, section 6).  Frames,
+ * masks, sources, matrices and LIVENESS are exactly those of the call above -- its (X, Y), inside test, tap-wise mask rule
+ * and sampler, its tile culling --; fp64 without fused multiply-adds, slots visited in the order k = 0 .. N - 1.
+ *
+ * The blend call.  gains: NULL (every gain is 1), or float32 (widened exactly) / float64 over (out, k), strides [0..1] >= 0
+ * (0 broadcasts; strides [2..3] are not read).  The VALUE of a live slot is v = g * sample per channel, g = gains[o, k].
+ * FIRST, MEAN and MEDIAN are the rules above applied to v -- the median orders the compensated values and returns the bits
+ * of one g * sample; with gains NULL the three give the bytes of the call above (1.0 * x is x).  Gains are not inspected: a
+ * NaN gain makes a NaN value, which the median orders last.
+ *     PAPOF_MOSAIC_FEATHER  w = min(min(X, W1 - X), min(Y, H1 - Y)) + 1.0 with W1 = (double)(W - 1), H1 = (double)(H - 1):
+ *                           >= 1 for a live slot, 1 on the frame's border.  num[ch] and den start at 0.0 and add w * v and
+ *                           w in k order; out = num[ch] / den, 0 when no slot is live.
+ * count as above.  PAPOF_EINVAL: the list above, with n_src <= PAPOF_MOSAIC_MAX_SOURCES for FEATHER too, a mode outside
+ * 0 .. 3, gains that are not float32 / float64 or have a negative stride or NULL data.
+ *
+ * The overlap call.  sums, counts: DEVICE pointers to n_out * N * N int64 each, contiguous (out, i, j); the call zeroes them
+ * on `stream` first.  It visits every output pixel with x % step == 0 and r % step == 0 and every live slot there:
+ *     y = the channels' samples added from 0.0 in channel order, divided by (double)c; a NaN y takes the slot out at this pixel
+ *     t = y / bound clamped to [0, 1];  q = (long long)rint(t * 16777216.0), half to even
+ * and for every ordered pair (i, j) of slots left at the pixel, i = j included: counts[o, i, j] += 1, sums[o, i, j] += q_i.
+ * So sums[o, i, j] / counts[o, i, j] / 2^24 * bound is the mean luminance of slot i where it overlaps slot j.  The sums are
+ * integers -- any order of the additions gives the same bits --, and with q <= 2^24 and fewer than 2^31 pixels they stay
+ * below 2^55.  PAPOF_EINVAL: the list above (out and count aside), n_src outside 1 .. PAPOF_MOSAIC_MAX_OVERLAP, step < 1, a
+ * bound that is not finite and > 0, sums or counts NULL. */
+enum { PAPOF_MOSAIC_FEATHER = 3 }; /* the blend call only */
+enum { PAPOF_MOSAIC_MAX_OVERLAP = 64 };
+int papof_mosaic_blend_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                              const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                              const int* sources, const papof_tensor* matrices, const papof_tensor* gains, int mode,
+                              const papof_tensor* out, const papof_tensor* count, void* stream);
+int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                const int* sources, const papof_tensor* matrices, int step, double bound, long long* sums,
+                                long long* counts, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -29,8 +29,8 @@ class Params(ctypes.Structure):
 
 DTYPE_U8, DTYPE_F32, DTYPE_F64 = 0, 1, 2
 MOTION_SIMILARITY, MOTION_AFFINE = 0, 1
-MOSAIC_FIRST, MOSAIC_MEAN, MOSAIC_MEDIAN = 0, 1, 2
-MOSAIC_MAX_SOURCES, MOSAIC_MAX_MEDIAN = 255, 64
+MOSAIC_FIRST, MOSAIC_MEAN, MOSAIC_MEDIAN, MOSAIC_FEATHER = 0, 1, 2, 3
+MOSAIC_MAX_SOURCES, MOSAIC_MAX_MEDIAN, MOSAIC_MAX_OVERLAP = 255, 64, 64
 
 
 class PapofTensor(ctypes.Structure):
@@ -71,7 +71,7 @@ SYMBOLS = [
     "papof_interp_splat_tensor", "papof_refine_flow_tensor", "papof_refine_workspace", "papof_refine_tables",
     "papof_super_resolve_tensor", "papof_sr_workspace", "papof_match_tensor", "papof_match_workspace",
     "papof_match_densify_tensor", "papof_motion_blur_tensor", "papof_decimate_tensor", "papof_upsample_flow_tensor",
-    "papof_upsample_tables", "papof_mosaic_tensor",
+    "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor",
 ]
 
 
@@ -225,6 +225,12 @@ def load():
     L.papof_mosaic_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, c_void_p, _T, c_int,
                                       _T, _T, c_void_p]
     L.papof_mosaic_tensor.restype = c_int
+    L.papof_mosaic_blend_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, c_void_p, _T, _T,
+                                            c_int, _T, _T, c_void_p]
+    L.papof_mosaic_blend_tensor.restype = c_int
+    L.papof_mosaic_overlap_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, c_void_p, _T,
+                                              c_int, c_double, c_void_p, c_void_p, c_void_p]
+    L.papof_mosaic_overlap_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

@@ -21,11 +21,24 @@
 //      the element of rank (n - 1) / 2 under (value, k) is found by counting, for each candidate, the samples before it.
 // The instance is chosen by n_src: MEDIAN holds 8, 16, 32 or 64 samples per lane, in tiles of 64 x 4, 64 x 4, 64 x 2 and
 // 64 x 1 (16, 32, 32 and 32 KiB of samples per block): DESIGN.md section 25 has the registers and the occupancy of each.
+//
+// papof_mosaic_blend_tensor is the same kernel over BlendArgs: every live sample is multiplied by the gain of its slot, and
+// PAPOF_MOSAIC_FEATHER weighs it by the distance of (X, Y) to the frame's border.  The instances over MosaicArgs (the gain
+// is the constant 1.0 there) are what papof_mosaic_tensor launches, as before, and this call too without gains.
+//
+// k_mosaic_overlap (papof_mosaic_overlap_tensor).  A block is a 64 x 2 tile of SAMPLED pixels (every step-th column and
+// row).  Phases 1 and 2 as above, each lane writing the fixed-point luminance q of its live slots to LDS [slot][pixel] and
+// the 64-bit set of them.  Then the roles turn: lane j is source j (64 / NS pixels side by side where NS < 64), wave w owns
+// the rows i = w (mod 2) of an LDS table [i][lane], and for every pixel and every live i a lane whose own bit j is set adds
+// q[i] and 1 into its column of row i -- no LDS atomics, no conflicts.  The rows that were touched go out as 64-bit integer
+// atomic adds, one row of contiguous addresses per instruction.  Integer sums: the same bits in any order.  DESIGN.md
+// section 26 has the instances and what was measured.
 #include "sampler.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace papof {
 
@@ -47,11 +60,101 @@ struct MosaicArgs {
     int cull;            // 0: every source >= 0 is walked by every tile (measurements)
 };
 
+struct BlendArgs : MosaicArgs {
+    papof_tensor gains;  // float32 / float64 (out, k); data NULL: every gain is 1
+};
+
+__device__ __forceinline__ double slot_gain(const MosaicArgs&, long long, int) { return 1.0; }
+__device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int k) {
+    return b.gains.data ? load_flow(b.gains, o * b.gains.stride[0] + k * b.gains.stride[1]) : 1.0;
+}
+
 // a sorts before b: a < b, or a is a number and b is NaN
 __device__ __forceinline__ bool sorts_before(double a, double b) { return a < b || (a == a && b != b); }
 
-template <int FD, int MODE, int CAP, int TY>
-__global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const MosaicArgs a, long long tile0, long long out0) {
+// k_mosaic_overlap's phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its
+// matrices) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order; returns
+// their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
+// (k_mosaic's phase 1 in a function.  k_mosaic keeps its own text: called from there, this function and slot_live gave its
+// instances another register allocation, and the instances papof_mosaic_tensor launches are to stay the code they were.)
+template <int TY>
+__device__ __forceinline__ int cull_slots(const MosaicArgs& a, const int* src, long long mo, double xa, double xb, double ra,
+                                          double rb, unsigned short* list, int* wcount) {
+    constexpr int NT = kMosTX * TY;
+    const int tid = threadIdx.y * kMosTX + threadIdx.x;
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    int total = 0;
+    for (int base = 0; base < a.n_src; base += NT) {
+        const int k = base + tid;
+        bool keep = k < a.n_src && src[k] >= 0;
+        if (keep && a.cull) {
+            double m[6];
+            const long long mb = mo + k * a.mat.stride[1];
+#pragma unroll
+            for (int r = 0; r < 2; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
+            bool finite = true;
+#pragma unroll
+            for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
+            const double X0 = (m[0] * xa + m[1] * ra) + m[2], X1 = (m[0] * xb + m[1] * ra) + m[2];
+            const double X2 = (m[0] * xa + m[1] * rb) + m[2], X3 = (m[0] * xb + m[1] * rb) + m[2];
+            const double Y0 = (m[3] * xa + m[4] * ra) + m[5], Y1 = (m[3] * xb + m[4] * ra) + m[5];
+            const double Y2 = (m[3] * xa + m[4] * rb) + m[5], Y3 = (m[3] * xb + m[4] * rb) + m[5];
+            // (a NaN corner -- an overflow meeting its opposite -- proves nothing: every comparison is false, the source stays)
+            const bool missx = (X0 < -1.0 && X1 < -1.0 && X2 < -1.0 && X3 < -1.0) ||
+                               (X0 > W1 + 1.0 && X1 > W1 + 1.0 && X2 > W1 + 1.0 && X3 > W1 + 1.0);
+            const bool missy = (Y0 < -1.0 && Y1 < -1.0 && Y2 < -1.0 && Y3 < -1.0) ||
+                               (Y0 > H1 + 1.0 && Y1 > H1 + 1.0 && Y2 > H1 + 1.0 && Y3 > H1 + 1.0);
+            keep = finite && !missx && !missy;
+        }
+        const unsigned long long vote = __ballot(keep);
+        if (threadIdx.x == 0) wcount[threadIdx.y] = __popcll(vote);
+        __syncthreads();
+        int before = total, all = total;
+#pragma unroll
+        for (int w = 0; w < TY; w++) {
+            before += w < (int)threadIdx.y ? wcount[w] : 0;
+            all += wcount[w];
+        }
+        if (keep) list[before + __popcll(vote & ((1ULL << threadIdx.x) - 1ULL))] = (unsigned short)k;
+        total = all;
+        __syncthreads();
+    }
+    return total;
+}
+
+// k_mosaic's liveness, for k_mosaic_overlap: true where the slot (frame s, matrix at mb) is live at the pixel (xd, rd); then
+// X, Y and the taps are set
+__device__ __forceinline__ bool slot_live(const MosaicArgs& a, long long s, long long mb, double xd, double rd, double& X,
+                                          double& Y, Bilinear& t) {
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    double m[6];
+#pragma unroll
+    for (int rr = 0; rr < 2; rr++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
+    X = (m[0] * xd + m[1] * rd) + m[2];
+    Y = (m[3] * xd + m[4] * rd) + m[5];
+    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
+    t = taps_at(X, Y, a.H, a.W);
+    if (a.mask.data) {
+        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
+        bool masked = false;
+        const long long b = s * a.mask.stride[0];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
+        if (masked) return false;
+    }
+    return true;
+}
+
+// A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER
+template <int FD, int MODE, int CAP, int TY, typename A>
+__global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile0, long long out0) {
+    constexpr bool BLEND = std::is_same<A, BlendArgs>::value;
+    static_assert(BLEND || MODE != PAPOF_MOSAIC_FEATHER, "k_mosaic: FEATHER is a blend mode");
     constexpr int NT = kMosTX * TY;
     constexpr int CH = MODE == PAPOF_MOSAIC_MEDIAN ? 1 : 4;  // channels per walk of the list
     __shared__ double lut[256];
@@ -125,6 +228,7 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const MosaicArgs a, long 
         double acc[CH];
 #pragma unroll
         for (int j = 0; j < CH; j++) acc[j] = 0.0;
+        double den = 0.0;  // FEATHER: the sum of the weights
         int n = 0;
         for (int i = 0; i < total; i++) {
             const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
@@ -147,13 +251,20 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const MosaicArgs a, long 
                 if (masked) continue;
             }
             const long long base = s * a.fr.stride[0] + c0 * a.fr.stride[3];
+            const double gain = slot_gain(a, o, k);  // (MosaicArgs: the constant 1.0, and 1.0 * x is x: no instruction)
             if (MODE == PAPOF_MOSAIC_MEDIAN) {
-                smp[n * NT + tid] = sample_frame<FD>(a.fr, base, t, lut);
+                smp[n * NT + tid] = gain * sample_frame<FD>(a.fr, base, t, lut);
+            } else if (MODE == PAPOF_MOSAIC_FEATHER) {
+                const double w = fmin(fmin(X, W1 - X), fmin(Y, H1 - Y)) + 1.0;  // 1 on the frame's border
+#pragma unroll
+                for (int j = 0; j < CH; j++)
+                    if (c0 + j < a.C) acc[j] = acc[j] + w * (gain * sample_frame<FD>(a.fr, base + j * a.fr.stride[3], t, lut));
+                den = den + w;
             } else if (MODE == PAPOF_MOSAIC_MEAN || n == 0) {
 #pragma unroll
                 for (int j = 0; j < CH; j++)
                     if (c0 + j < a.C) {
-                        const double g = sample_frame<FD>(a.fr, base + j * a.fr.stride[3], t, lut);
+                        const double g = gain * sample_frame<FD>(a.fr, base + j * a.fr.stride[3], t, lut);
                         acc[j] = MODE == PAPOF_MOSAIC_MEAN ? acc[j] + g : g;
                     }
             }
@@ -186,31 +297,208 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const MosaicArgs a, long 
                 if (c0 + j < a.C) {
                     double v = acc[j];
                     if (MODE == PAPOF_MOSAIC_MEAN) v = n > 0 ? v / (double)n : 0.0;
+                    if (MODE == PAPOF_MOSAIC_FEATHER) v = n > 0 ? v / den : 0.0;
                     store(a.out, outp + (c0 + j) * a.out.stride[3], v);
                 }
         }
     }
 }
 
-template <int MODE, int CAP, int TY>
-int launch_mosaic_as(hipStream_t st, const MosaicArgs& a, int n_out) {
+template <int MODE, int CAP, int TY, typename A>
+int launch_mosaic_as(hipStream_t st, const A& a, int n_out) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic<PAPOF_DTYPE_U8, MODE, CAP, TY>
-                        : fd == PAPOF_DTYPE_F32 ? k_mosaic<PAPOF_DTYPE_F32, MODE, CAP, TY>
-                                                : k_mosaic<PAPOF_DTYPE_F64, MODE, CAP, TY>;
+    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic<PAPOF_DTYPE_U8, MODE, CAP, TY, A>
+                        : fd == PAPOF_DTYPE_F32 ? k_mosaic<PAPOF_DTYPE_F32, MODE, CAP, TY, A>
+                                                : k_mosaic<PAPOF_DTYPE_F64, MODE, CAP, TY, A>;
     const long long tiles = ((a.Wc + kMosTX - 1) / (long long)kMosTX) * ((a.Hc + TY - 1) / (long long)TY);
     return launch_tiles(tiles, n_out, [&](dim3 grid, long long t0, long long o0) {
         hipLaunchKernelGGL(kernel, grid, dim3(kMosTX, TY), 0, st, a, t0, o0);
     });
 }
 
-int launch_mosaic(hipStream_t st, const MosaicArgs& a, int n_out, int mode) {
+template <typename A>
+int launch_mosaic(hipStream_t st, const A& a, int n_out, int mode) {
+    const int n_src = a.n_src;
+    if (mode == PAPOF_MOSAIC_FEATHER) {
+        if constexpr (std::is_same<A, BlendArgs>::value) return launch_mosaic_as<PAPOF_MOSAIC_FEATHER, 0, 4>(st, a, n_out);
+        return PAPOF_EINVAL;
+    }
     if (mode == PAPOF_MOSAIC_FIRST) return launch_mosaic_as<PAPOF_MOSAIC_FIRST, 0, 4>(st, a, n_out);
     if (mode == PAPOF_MOSAIC_MEAN) return launch_mosaic_as<PAPOF_MOSAIC_MEAN, 0, 4>(st, a, n_out);
-    if (a.n_src <= 8) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 8, 4>(st, a, n_out);
-    if (a.n_src <= 16) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 16, 4>(st, a, n_out);
-    if (a.n_src <= 32) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 32, 2>(st, a, n_out);
+    if (n_src <= 8) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 8, 4>(st, a, n_out);
+    if (n_src <= 16) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 16, 4>(st, a, n_out);
+    if (n_src <= 32) return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 32, 2>(st, a, n_out);
     return launch_mosaic_as<PAPOF_MOSAIC_MEDIAN, 64, 1>(st, a, n_out);
+}
+
+// ---- papof_mosaic_overlap_tensor
+constexpr int kOvTY = 2;                   // a 64 x 2 tile of sampled pixels: two waves, and a column's sum fits 32 bits
+constexpr int kOvNT = kMosTX * kOvTY;
+constexpr double kOvOne = 16777216.0;      // q = rint(t * 2^24)
+
+struct OverlapArgs {
+    MosaicArgs m;                // out and count are not used
+    unsigned long long* sums;    // (out, i, j), contiguous
+    unsigned long long* counts;
+    double bound;
+    int step;
+    int nsx, nsr;                // sampled columns and rows: ceil(Wc / step), ceil(Hc / step)
+};
+
+// NS: the slots the tables hold (n_src <= NS), a power of two <= 64
+template <int FD, int NS>
+__global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgs args, long long tile0, long long out0) {
+    constexpr int G = 64 / NS;  // pixels side by side in phase 3
+    const MosaicArgs& a = args.m;
+    __shared__ double lut[256];
+    __shared__ unsigned short list[64];
+    __shared__ int wcount[kOvTY];
+    __shared__ unsigned long long live[kOvNT];  // bit k: slot k is live at the pixel (and its luminance a number)
+    __shared__ unsigned qs[NS * kOvNT];         // [slot][pixel], written where the bit is set
+    __shared__ unsigned tsum[NS * 64];          // [i][lane]: a lane adds <= kOvNT / G values <= 2^24, < 2^32
+    __shared__ unsigned tcnt[NS * 64];
+    const int tid = threadIdx.y * kMosTX + threadIdx.x;
+    if (FD == PAPOF_DTYPE_U8)
+        for (int j = tid; j < 256; j += kOvNT) fill_u8_lut(lut, j);
+    for (int j = tid; j < NS * 64; j += kOvNT) {
+        tsum[j] = 0;
+        tcnt[j] = 0;
+    }
+    const long long o = out0 + blockIdx.y;
+    const long long tx = (args.nsx + kMosTX - 1) / kMosTX, tile = tile0 + blockIdx.x;
+    const int sx0 = (int)(tile % tx) * kMosTX;
+    const long long sr0 = (tile / tx) * kOvTY;
+    const int* src = a.src + o * a.n_src;
+    const long long mo = o * a.mat.stride[0];
+    const long long step = args.step;
+
+    // ---- 1. the sources that can reach the tile's pixels (all of them lie in the rectangle of its corners)
+    const int total = cull_slots<kOvTY>(a, src, mo, (double)(sx0 * step),
+                                        (double)(std::min(sx0 + kMosTX - 1, args.nsx - 1) * step), (double)(sr0 * step),
+                                        (double)(std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step), list, wcount);
+
+    // ---- 2. the walk: the luminance of every live slot, in fixed point
+    const int sx = sx0 + (int)threadIdx.x;
+    const long long sr = sr0 + threadIdx.y;
+    unsigned long long mine = 0;
+    if (sx < args.nsx && sr < args.nsr) {
+        const double xd = (double)(sx * step), rd = (double)(sr * step);
+        for (int i = 0; i < total; i++) {
+            const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
+            const long long s = src[k];
+            double X, Y;
+            Bilinear t;
+            if (!slot_live(a, s, mo + k * a.mat.stride[1], xd, rd, X, Y, t)) continue;
+            const long long base = s * a.fr.stride[0];
+            double y = 0.0;
+            for (int ch = 0; ch < a.C; ch++) y = y + sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], t, lut);
+            y = y / (double)a.C;
+            if (y != y) continue;
+            double q = y / args.bound;
+            q = q < 0.0 ? 0.0 : q;
+            q = q > 1.0 ? 1.0 : q;
+            qs[k * kOvNT + tid] = (unsigned)(long long)rint(q * kOvOne);
+            mine |= 1ULL << k;
+        }
+    }
+    live[tid] = mine;
+    __syncthreads();
+
+    // ---- 3. lane = (pixel of G, source j); wave w owns the rows i = w (mod kOvTY) of the tables
+    const int lane = threadIdx.x;
+    const int sub = lane / NS, j = lane % NS;
+    unsigned long long rows = 0;
+    for (int i = threadIdx.y; i < NS; i += kOvTY) rows |= 1ULL << i;
+    unsigned touched_lo = 0, touched_hi = 0;
+    for (int pb = 0; pb < kOvNT; pb += G) {
+        unsigned long long any = 0;
+        for (int g = 0; g < G; g++) any |= live[pb + g];  // (one address each: a broadcast)
+        any &= rows;
+        unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)any), hi = __builtin_amdgcn_readfirstlane((unsigned)(any >> 32));
+        if (!(lo | hi)) continue;
+        touched_lo |= lo;
+        touched_hi |= hi;
+        const int p = pb + sub;
+        const unsigned long long m = live[p];
+        const bool has = (m >> j) & 1;
+        for (int half = 0; half < 2; half++) {
+            unsigned bits = half ? hi : lo;
+            while (bits) {
+                const int i = 32 * half + __builtin_ctz(bits);
+                bits &= bits - 1;
+                if (has && ((m >> i) & 1)) {
+                    tsum[i * 64 + lane] += qs[i * kOvNT + p];
+                    tcnt[i * 64 + lane] += 1;
+                }
+            }
+        }
+    }
+
+    // ---- the rows this wave touched: one contiguous row of 64-bit integer adds per instruction
+    const long long N = a.n_src;
+    for (int half = 0; half < 2; half++) {
+        unsigned bits = half ? touched_hi : touched_lo;
+        while (bits) {
+            const int i = 32 * half + __builtin_ctz(bits);
+            bits &= bits - 1;
+            if (lane < NS) {
+                unsigned long long sum = 0, cnt = 0;
+                for (int g = 0; g < G; g++) {
+                    sum += tsum[i * 64 + g * NS + lane];
+                    cnt += tcnt[i * 64 + g * NS + lane];
+                }
+                if (cnt != 0) {  // (bit `lane` was set at some pixel: lane < n_src, as i is)
+                    const long long e = (o * N + i) * N + lane;
+                    add64(args.sums + e, (long long)sum);
+                    add64(args.counts + e, (long long)cnt);
+                }
+            }
+        }
+    }
+}
+
+template <int NS>
+int launch_overlap_as(hipStream_t st, const OverlapArgs& a, int n_out) {
+    const int fd = a.m.fr.dtype;
+    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic_overlap<PAPOF_DTYPE_U8, NS>
+                        : fd == PAPOF_DTYPE_F32 ? k_mosaic_overlap<PAPOF_DTYPE_F32, NS>
+                                                : k_mosaic_overlap<PAPOF_DTYPE_F64, NS>;
+    const long long tiles = ((a.nsx + kMosTX - 1) / (long long)kMosTX) * ((a.nsr + kOvTY - 1) / (long long)kOvTY);
+    return launch_tiles(tiles, n_out, [&](dim3 grid, long long t0, long long o0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kMosTX, kOvTY), 0, st, a, t0, o0);
+    });
+}
+
+// The arguments the three calls share, checked and gathered; out and count are the caller's to check and set
+bool mosaic_args_from(MosaicArgs& a, const papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                      const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
+                      const papof_tensor* matrices) {
+    if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1 || n_out < 1 || out_height < 1 || out_width < 1) return false;
+    if (n_src < 1 || n_src > PAPOF_MOSAIC_MAX_SOURCES || !sources) return false;
+    if (!described(frames, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return false;
+    if (masks && !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return false;
+    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return false;
+    a.fr = *frames;
+    if (masks) a.mask = *masks;
+    a.mat = *matrices;
+    a.src = sources;
+    a.H = height;
+    a.W = width;
+    a.C = c;
+    a.Hc = out_height;
+    a.Wc = out_width;
+    a.n_src = n_src;
+    const char* e = std::getenv("PAPOF_MOSAIC_CULL");  // "0": no tile-level culling (tools/mosaic_probe.py measures its worth)
+    a.cull = !(e && e[0] == '0');
+    return true;
+}
+
+bool mosaic_outputs(MosaicArgs& a, const papof_tensor* out, const papof_tensor* count) {
+    if (!described(out, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, true)) return false;
+    if (count && !described(count, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return false;
+    a.out = *out;
+    if (count) a.count = *count;
+    return true;
 }
 
 }  // namespace
@@ -223,35 +511,65 @@ extern "C" int papof_mosaic_tensor(papof_handle* h, int n_frames, int height, in
                                    const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
                                    const int* sources, const papof_tensor* matrices, int mode, const papof_tensor* out,
                                    const papof_tensor* count, void* stream) {
-    if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1 || n_out < 1 || out_height < 1 || out_width < 1) return PAPOF_EINVAL;
-    if (n_src < 1 || n_src > PAPOF_MOSAIC_MAX_SOURCES || !sources) return PAPOF_EINVAL;
+    MosaicArgs a{};
+    if (!mosaic_args_from(a, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources, matrices))
+        return PAPOF_EINVAL;
     if (mode != PAPOF_MOSAIC_FIRST && mode != PAPOF_MOSAIC_MEAN && mode != PAPOF_MOSAIC_MEDIAN) return PAPOF_EINVAL;
     if (mode == PAPOF_MOSAIC_MEDIAN && n_src > PAPOF_MOSAIC_MAX_MEDIAN) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (masks && !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (count && !described(count, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
-    MosaicArgs a{};
-    a.fr = *frames;
-    if (masks) a.mask = *masks;
-    a.mat = *matrices;
-    a.out = *out;
-    if (count) a.count = *count;
-    a.src = sources;
-    a.H = height;
-    a.W = width;
-    a.C = c;
-    a.Hc = out_height;
-    a.Wc = out_width;
-    a.n_src = n_src;
-    const char* e = std::getenv("PAPOF_MOSAIC_CULL");  // "0": no tile-level culling (tools/mosaic_probe.py measures its worth)
-    a.cull = !(e && e[0] == '0');
+    if (!mosaic_outputs(a, out, count)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
     return launch_mosaic(static_cast<hipStream_t>(stream), a, n_out, mode);
+}
+
+extern "C" int papof_mosaic_blend_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                         const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                         const int* sources, const papof_tensor* matrices, const papof_tensor* gains, int mode,
+                                         const papof_tensor* out, const papof_tensor* count, void* stream) {
+    BlendArgs b{};
+    if (!mosaic_args_from(b, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                          matrices))
+        return PAPOF_EINVAL;
+    if (mode < PAPOF_MOSAIC_FIRST || mode > PAPOF_MOSAIC_FEATHER) return PAPOF_EINVAL;
+    if (mode == PAPOF_MOSAIC_MEDIAN && n_src > PAPOF_MOSAIC_MAX_MEDIAN) return PAPOF_EINVAL;
+    if (gains && !described(gains, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1}, false)) return PAPOF_EINVAL;
+    if (!mosaic_outputs(b, out, count)) return PAPOF_EINVAL;
+    PAPOF_HIP(hipSetDevice(h->device));
+    if (!gains && mode != PAPOF_MOSAIC_FEATHER)  // every gain 1: the instances papof_mosaic_tensor launches
+        return launch_mosaic(static_cast<hipStream_t>(stream), static_cast<const MosaicArgs&>(b), n_out, mode);
+    if (gains) b.gains = *gains;
+    return launch_mosaic(static_cast<hipStream_t>(stream), b, n_out, mode);
+}
+
+extern "C" int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                           const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                           const int* sources, const papof_tensor* matrices, int step, double bound,
+                                           long long* sums, long long* counts, void* stream) {
+    OverlapArgs a{};
+    if (!mosaic_args_from(a.m, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                          matrices))
+        return PAPOF_EINVAL;
+    if (n_src > PAPOF_MOSAIC_MAX_OVERLAP || step < 1 || !std::isfinite(bound) || !(bound > 0) || !sums || !counts)
+        return PAPOF_EINVAL;
+    a.sums = reinterpret_cast<unsigned long long*>(sums);
+    a.counts = reinterpret_cast<unsigned long long*>(counts);
+    a.bound = bound;
+    a.step = step;
+    a.nsx = (out_width - 1) / step + 1;
+    a.nsr = (out_height - 1) / step + 1;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PAPOF_HIP(hipSetDevice(h->device));
+    const size_t bytes = sizeof(long long) * (size_t)n_out * n_src * n_src;
+    PAPOF_HIP(hipMemsetAsync(sums, 0, bytes, st));
+    PAPOF_HIP(hipMemsetAsync(counts, 0, bytes, st));
+    if (n_src <= 8) return launch_overlap_as<8>(st, a, n_out);
+    if (n_src <= 16) return launch_overlap_as<16>(st, a, n_out);
+    if (n_src <= 32) return launch_overlap_as<32>(st, a, n_out);
+    return launch_overlap_as<64>(st, a, n_out);
 }
 
 // Every instance launch_mosaic dispatches to has a lane per slot (n_src <= 64 * TY), so phase 1's loop over the slots runs once.
 static_assert(kMaxSrc <= kMosTX * 4 && 8 <= kMosTX * 4 && 16 <= kMosTX * 4 && 32 <= kMosTX * 2 &&
                   PAPOF_MOSAIC_MAX_MEDIAN <= kMosTX * 1 && PAPOF_MOSAIC_MAX_SOURCES < kMaxSrc,
               "k_mosaic: a lane per slot in one pass of phase 1");
+static_assert(PAPOF_MOSAIC_MAX_OVERLAP <= 64 && PAPOF_MOSAIC_MAX_OVERLAP <= kOvNT && (long long)kOvNT * 16777216LL < (1LL << 32),
+              "k_mosaic_overlap: a bit and a lane per slot, a column's sum in 32 bits");

@@ -106,10 +106,14 @@ Video mosaics: `mosaic` (include/papof.h: papof_mosaic_tensor) gathers many fram
 one output pixel and keeps the first that covers it, their mean or their median -- one HIP kernel, the samples held on
 chip; `mosaic_transforms` and `neighbour_transforms` make its matrices from global motions on the host; `panorama` chains
 flow_video, global_motion and them (mode "median": the clean plate, what moved is gone); `stabilize_video_full` is
-stabilize_video with the empty borders filled from the neighbouring frames.
+stabilize_video with the empty borders filled from the neighbouring frames.  Seamless mosaics: `mosaic_overlap`
+(papof_mosaic_overlap_tensor) gathers the pairwise luminance statistics of the overlaps, `exposure_gains` solves one gain
+per source from them on the host, and `mosaic(..., gains=, mode="feather")` (papof_mosaic_blend_tensor) applies the gains
+and fades every frame out towards its border; `panorama(..., exposure=True)` chains them.
 
     pano = panorama(frames, 5, mode="median", layout="NHWC")       # pano.image (Hc, Wc, C), pano.count (Hc, Wc)
     sv = stabilize_video_full(frames, 5, layout="NHWC")            # sv.video, sv.valid, sv.filled
+    pano = panorama(frames, 5, mode="feather", exposure=True, layout="NHWC")   # no steps at frame borders; pano.gains
 
 torch is imported when a function is called, not when the package is imported.
 """
@@ -2269,11 +2273,15 @@ def flow_video_lr(frames, pyramidLevels, *, factor=2, refine_levels=0, radius=UP
 
 # ---- video mosaics (include/papof.h: papof_mosaic_tensor) -------------------------------------------------------------------
 Mosaic = collections.namedtuple("Mosaic", "out count")
-Panorama = collections.namedtuple("Panorama", "image count matrices origin motion ok flow timing")
+Panorama = collections.namedtuple("Panorama", "image count matrices origin motion ok flow timing gains", defaults=(None,))
+Overlap = collections.namedtuple("Overlap", "sums counts bound")
 StabilizedFull = collections.namedtuple("StabilizedFull", "video valid filled transforms motion ok flow timing")
-MOSAIC_MODES = {"first": capi.MOSAIC_FIRST, "mean": capi.MOSAIC_MEAN, "median": capi.MOSAIC_MEDIAN}
+MOSAIC_MODES = {"first": capi.MOSAIC_FIRST, "mean": capi.MOSAIC_MEAN, "median": capi.MOSAIC_MEDIAN,
+                "feather": capi.MOSAIC_FEATHER}
 MAX_SOURCES = capi.MOSAIC_MAX_SOURCES  # source slots of one output
 MAX_MEDIAN = capi.MOSAIC_MAX_MEDIAN    # of them under mode="median"
+MAX_OVERLAP = capi.MOSAIC_MAX_OVERLAP  # of them in mosaic_overlap
+OVERLAP_ONE = 2 ** 24                  # mosaic_overlap's fixed point: a luminance of `bound`
 MAX_PIXELS = 2 ** 26                   # mosaic_transforms: the largest canvas it returns unasked
 
 
@@ -2343,9 +2351,26 @@ def _check_sources(sources, n_out, N, T):
     return s.clamp(min=-1).to(torch.int32).contiguous()
 
 
-def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True):
+def _check_gains(gains, n_out, N, dev):
+    """None, or the (n_out, N) float32 / float64 gains on `dev` -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    if gains is None:
+        return None
+    if not isinstance(gains, torch.Tensor):
+        raise TypeError("gains must be None or a torch.Tensor, got %s" % type(gains).__name__)
+    if gains.dtype not in (torch.float32, torch.float64):
+        raise TypeError("gains must be float32 or float64, got %s" % gains.dtype)
+    if tuple(gains.shape) != (n_out, N):
+        raise ValueError("gains must be (n_out, N) = %s as the matrices, got %s" % ((n_out, N), tuple(gains.shape)))
+    if gains.device != dev:
+        raise ValueError("gains are on %s, the frames on %s: both must be on one device" % (gains.device, dev))
+    return gains
+
+
+def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None):
     """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
-    count False: no count (None is returned for it; mode "first" then stops at the first live source)"""
+    count False: no count (None is returned for it; mode "first" then stops at the first live source).  With gains (checked)
+    or mode "feather": papof_mosaic_blend_tensor."""
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
@@ -2356,12 +2381,41 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
     d_mask = _mask_struct(masks) if masks is not None else None
     d_cnt = _mask_struct(cnt) if count else None
-    _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+    if gains is None and mode != "feather":
+        _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+        return out, cnt
+    d_gain = None
+    if gains is not None:
+        d_gain = _struct(gains, (gains.stride(0), gains.stride(1), 0, 0),
+                         capi.DTYPE_F32 if gains.dtype == torch.float32 else capi.DTYPE_F64)
+    _launch(dev, "papof_mosaic_blend_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), _ref(d_gain), MOSAIC_MODES[mode], ctypes.byref(d_out),
+            _ref(d_cnt))
     return out, cnt
 
 
-def mosaic(frames, sources, matrices, size, *, mode="median", masks=None, layout="NCHW", out_dtype=None):
+def _mosaic_inputs(ts, descs, sources, matrices, size, masks):
+    """what mosaic and mosaic_overlap check alike behind their frames, in mosaic's order: (Hc, Wc, m_code, n_out, N, the host
+    sources or None, masks)"""
+    Hc, Wc = _check_canvas(size)
+    (T, H, W, _), _, _ = descs[0]
+    dev = ts[0].device
+    m_code, n_out, N = _check_mosaic_matrices(matrices, dev)
+    src = _check_sources(sources, n_out, N, T)
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    return Hc, Wc, m_code, n_out, N, src, m
+
+
+def _device_sources(src, T, n_out, dev):
+    if src is None:  # made on the device, on the current stream
+        return _torch().arange(T, dtype=_torch().int32, device=dev).repeat(n_out, 1)
+    if dev.type == "cuda":  # from page-locked memory: the copy is queued, the host does not wait for the stream
+        return src.pin_memory().to(dev, non_blocking=True)
+    return src
+
+
+def mosaic(frames, sources, matrices, size, *, mode="median", masks=None, layout="NCHW", out_dtype=None, gains=None):
     """Many frames, each through its own affine matrix, gathered into one output pixel and combined there: frames (T, C, H,
     W) or (T, H, W, C) by `layout`, uint8 (read as x / 255), float32 or float64, any strides, on a HIP device; size = (Hc,
     Wc) of the n_out outputs; matrices (n_out, N, 2, 3) float32 / float64 on the same device, N <= 255 sources per output
@@ -2370,26 +2424,118 @@ def mosaic(frames, sources, matrices, size, *, mode="median", masks=None, layout
     out.  At output pixel (x, y) source k is LIVE where matrices[o, k] (x, y, 1) lies inside its frame and, with masks, no
     bilinear tap of positive weight there is masked; its sample is the frame read bilinearly (the rule of warp_affine).
     mode "first": the live source with the smallest k; "mean": the live samples added in k order over their number;
-    "median": per channel the lower median of the live samples, ties broken by k, NaN last -- the bits of one sample.
-    Returns Mosaic(out (n_out, C, Hc, Wc) or (n_out, Hc, Wc, C) of out_dtype (by default the frames'), 0 where no source
-    is live; count (n_out, Hc, Wc) uint8: the live sources).  include/papof.h (papof_mosaic_tensor) states it exactly;
+    "median": per channel the lower median of the live samples, ties broken by k, NaN last -- the bits of one sample;
+    "feather": the live samples weighted by w = 1 + the distance of the sampled point to its frame's nearest border, added
+    in k order over the sum of the weights: no step where a frame ends.  gains None or (n_out, N) float32 / float64 on the
+    frames' device (a stride of 0 broadcasts): every sample of source k is multiplied by gains[o, k] before the mode sees
+    it (exposure_gains makes them); they are not inspected.  With gains None the first three modes are
+    papof_mosaic_tensor as before; otherwise papof_mosaic_blend_tensor.  Returns Mosaic(out (n_out, C, Hc, Wc) or (n_out,
+    Hc, Wc, C) of out_dtype (by default the frames'), 0 where no source is live; count (n_out, Hc, Wc) uint8: the live
+    sources).  include/papof.h (papof_mosaic_tensor, papof_mosaic_blend_tensor) states it exactly;
     bitwise reproducible.  The sources are checked on the host (a device tensor of sources waits for its stream); the kernel
     is enqueued on the current stream and the call returns without waiting."""
     ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
     out_dtype = _out_dtype(out_dtype, ts[0].dtype)
     _check_mode(mode)
-    Hc, Wc = _check_canvas(size)
-    (T, H, W, _), _, _ = descs[0]
-    dev = ts[0].device
-    m_code, n_out, N = _check_mosaic_matrices(matrices, dev)
-    src = _check_sources(sources, n_out, N, T)
-    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks)
     _check_slots(mode, N)
-    if src is None:  # made on the device, on the current stream
-        src = _torch().arange(T, dtype=_torch().int32, device=dev).repeat(n_out, 1)
-    elif dev.type == "cuda":  # from page-locked memory: the copy is queued, the host does not wait for the stream
-        src = src.pin_memory().to(dev, non_blocking=True)
-    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype))
+    dev = ts[0].device
+    gains = _check_gains(gains, n_out, N, dev)
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains))
+
+
+def _check_overlap_slots(n, what="matrices have"):
+    if not 1 <= n <= MAX_OVERLAP:
+        raise ValueError("%s %d sources per output, the overlap statistics take 1 .. %d" % (what, n, MAX_OVERLAP))
+
+
+def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound):
+    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's)"""
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    n_out, N = int(src.shape[0]), int(src.shape[1])
+    sums = torch.empty((n_out, N, N), dtype=torch.int64, device=dev)
+    counts = torch.empty((n_out, N, N), dtype=torch.int64, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
+    d_mask = _mask_struct(masks) if masks is not None else None
+    _launch(dev, "papof_mosaic_overlap_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), step, ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()),
+            ctypes.c_void_p(counts.data_ptr()))
+    return Overlap(sums, counts, bound)
+
+
+def mosaic_overlap(frames, sources, matrices, size, *, masks=None, step=2, bound=1.0, layout="NCHW"):
+    """The pairwise overlap statistics of a mosaic, from which exposure_gains solves one gain per source (Brown and Lowe
+    2007, section 6): frames, sources, matrices, size, masks and layout as mosaic's, N <= 64 sources per output.  At every
+    `step`-th column and row of the canvas the luminance of each live source -- the mean of its channels' samples, divided
+    by `bound` (finite, > 0: the value that counts as white), clamped to [0, 1], in 24-bit fixed point; a NaN luminance is
+    left out -- is added into sums[o, i, j] for every source j live at that pixel, i itself included, and counts[o, i, j]
+    counts the pixel: sums[o, i, j] / counts[o, i, j] / 2**24 * bound is the mean luminance of source i where it overlaps
+    source j.  Returns Overlap(sums, counts (n_out, N, N) int64 on the frames' device, bound).  Integer sums: bitwise
+    reproducible.  include/papof.h (papof_mosaic_overlap_tensor) states it exactly.  Enqueued on the current stream; the
+    call returns without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks)
+    _check_overlap_slots(N)
+    _int_at_least("step", step, 1)
+    bound = _positive("bound", bound)
+    dev = ts[0].device
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound)
+
+
+def _positive(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError("%s must be a number, got %r" % (name, v))
+    if not (math.isfinite(v) and v > 0):
+        raise ValueError("%s must be finite and > 0, got %r" % (name, v))
+    return float(v)
+
+
+def exposure_gains(overlap, *, sigma_n=10.0 / 255.0, sigma_g=0.1, anchor=None):
+    """One gain per source from mosaic_overlap's statistics (Brown and Lowe 2007, section 6): per output, with N_ij =
+    counts[i, j] for i != j and I_ij = sums[i, j] / counts[i, j] / 2**24 * bound (0 where the count is 0), the gains that
+    minimise  sum over i != j of N_ij ((g_i I_ij - g_j I_ji)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2)  -- the sources agree
+    where they overlap, and the prior keeps the gains near 1 (the error alone is minimal at g = 0).  The linear system is
+    solved on the host in float64 (the call waits for the statistics); a source that overlaps no other gets 1.  anchor: None,
+    or a source index k: every output's gains are divided by its g_k, so that source keeps its look.  Gains fix ratios, not
+    the level.  Returns (n_out, N) float64 on the statistics' device: mosaic's `gains`."""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(overlap, Overlap):
+        raise TypeError("overlap must be an Overlap (mosaic_overlap's), got %s" % type(overlap).__name__)
+    sums, counts = overlap.sums, overlap.counts
+    for name, t in (("sums", sums), ("counts", counts)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+            raise TypeError("overlap.%s must be an int64 tensor" % name)
+        if t.dim() != 3 or t.shape[1] != t.shape[2] or min(t.shape) < 1 or t.shape != sums.shape:
+            raise ValueError("overlap.sums and .counts must be (n_out, N, N), got %s and %s" % (tuple(sums.shape),
+                                                                                              tuple(counts.shape)))
+    bound = _positive("overlap.bound", overlap.bound)
+    sigma_n, sigma_g = _positive("sigma_n", sigma_n), _positive("sigma_g", sigma_g)
+    n_out, N = int(sums.shape[0]), int(sums.shape[1])
+    if anchor is not None and (isinstance(anchor, bool) or not isinstance(anchor, int) or not 0 <= anchor < N):
+        raise ValueError("anchor must be None or a source index in 0 .. %d, got %r" % (N - 1, anchor))
+    S = sums.detach().cpu().numpy().astype(np.float64)
+    Nij = counts.detach().cpu().numpy().astype(np.float64)
+    I = np.where(Nij > 0, S / np.maximum(Nij, 1.0) / OVERLAP_ONE * bound, 0.0)
+    Nij = Nij * (1.0 - np.eye(N))
+    n = Nij.sum(2)
+    g = np.ones((n_out, N))
+    for o in range(n_out):
+        A = -2.0 * Nij[o] * I[o] * I[o].T / sigma_n ** 2
+        A[np.diag_indices(N)] = (2.0 * Nij[o] * I[o] ** 2).sum(1) / sigma_n ** 2 + n[o] / sigma_g ** 2
+        b = n[o] / sigma_g ** 2
+        alone = n[o] == 0
+        A[alone, alone] = 1.0
+        b = np.where(alone, 1.0, b)
+        g[o] = np.linalg.solve(A, b)
+        if anchor is not None:
+            g[o] = g[o] / g[o, anchor]
+    return torch.from_numpy(g).to(sums.device)
 
 
 def _pair_motions(motion):
@@ -2499,18 +2645,23 @@ def neighbour_transforms(transforms, motion, radius):
 
 
 def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0, masks=None, model="affine", iters=5,
-             scale=1.0, layout="NCHW", out_dtype=None, **solver):
+             scale=1.0, layout="NCHW", out_dtype=None, exposure=False, **solver):
     """The panorama of a panning video of T >= 2 frames -- with mode "median" its clean plate: what moved in front of the
     background is gone wherever the background shows in more than half of the frames that cover a pixel.
     flow_video(frames, pyramidLevels, layout=layout, **solver), global_motion on the flows (model, iters, scale),
     mosaic_transforms (ref, margin; the only wait) and ONE mosaic of the frames 0, step, 2 step, ... (masks: (T, H, W),
     nonzero pixels are left out).  The motion is chained over all pairs whatever the step.  At most 255 frames are
-    deposited, 64 under "median": a larger video needs a larger `step`.  Returns Panorama(image (C, Hc, Wc) or (Hc, Wc, C)
+    deposited, 64 under "median" or with exposure=True: a larger video needs a larger `step`.  mode "feather" blends the
+    frames by their distance to the border (mosaic).  exposure=True compensates the frames' exposure first: mosaic_overlap
+    (step 2, bound 1.0: white is 1, as in uint8 frames and floats in [0, 1] -- float frames of another range clamp there and
+    their gains degrade: compose the three calls with a bound of your own) and exposure_gains on the deposited frames,
+    anchored at the reference frame when it is among them -- a second wait --, and the mosaic takes the gains.  Returns Panorama(image (C, Hc, Wc) or (Hc, Wc, C)
     of out_dtype (by default the frames'), count (Hc, Wc) uint8, matrices (T, 2, 3) float64 -- canvas to frame t, of every
     frame --, origin (x0, y0): the canvas pixel (0, 0) in the reference frame's coordinates, motion (T - 1, 2, 3), ok
-    (T - 1,) bool, flow (T - 1, 2, H, W) float64, timing of the flow call).  The model is affine: there is no projective
-    warp, no bundle adjustment, no exposure compensation and no seam blending (README).  Every argument error raises
-    before anything is launched."""
+    (T - 1,) bool, flow (T - 1, 2, H, W) float64, timing of the flow call, gains: None, or with exposure=True the float64
+    gain of every deposited frame).  The model is affine: there is no projective warp and no bundle adjustment; the
+    exposure is one gain per frame, and feathering ghosts where the registration is off (README).  Every argument error
+    raises before anything is launched."""
     ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     code, iters, scale = _check_fit(model, iters, scale)
     (T, H, W, C), _, _ = descs[0]
@@ -2522,13 +2673,22 @@ def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0
     dev = ts[0].device
     m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
     picked = list(range(0, T, step))
+    if not isinstance(exposure, bool):
+        raise TypeError("exposure must be True or False, got %r" % (exposure,))
+    if exposure and len(picked) > MAX_OVERLAP:
+        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
+                         % (step, len(picked), MAX_OVERLAP))
     _check_slots(mode, len(picked), "step = %d deposits" % step)
     flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
     mo = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
     M, (Hc, Wc), origin = mosaic_transforms(mo, (H, W), ref=ref, margin=margin)
     src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
-    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype)
-    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing)
+    gains = None
+    if exposure:
+        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0)
+        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
+    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains)
+    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0])
 
 
 def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW", model="similarity", radius=15, crop=1.0,
