@@ -324,6 +324,12 @@ int papof_bench_sor(papof_handle* h, int height, int width, int n_sor, int sor_m
  * wave; red-black: HALF-sweeps per launch of the LDS-tiled, temporally blocked kernel; Jacobi: sweeps per launch). */
 int papof_sor_plan(papof_handle* h, int height, int width, int n_sor, int sor_mode, int* launches, int* depth);
 
+/* Which instance of the one-workgroup exact-order solver (k_sor_tiny) a height x width plane selects -- a host-only query: no
+ * handle, no device.  *cells_per_tile = cells of a tile (the instance's template parameter), *waves = wavefronts of the
+ * launch; both 0 when no instance holds the plane (more than 8192 cells, more lanes than a workgroup has, or more than 150 KiB
+ * of LDS): the hyperplane kernels solve it.  PAPOF_SOR_TINY=0 (read when a handle is created) sends every plane to them. */
+int papof_sor_tiny_shape(int height, int width, int* cells_per_tile, int* waves);
+
 /* Measurement aid for bench.py: what the LAST papof_flow* / papof_seq_push* call on this handle launched -- exact-order
  * solver kernels in all.  *strip_streams_sec is always 0: it was the share of Phase5_SOR that ran on the strip streams,
  * and the strips schedule is gone (the argument stays for the ABI). */

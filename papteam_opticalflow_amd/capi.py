@@ -71,7 +71,7 @@ SYMBOLS = [
     "papof_interp_splat_tensor", "papof_refine_flow_tensor", "papof_refine_workspace", "papof_refine_tables",
     "papof_super_resolve_tensor", "papof_sr_workspace", "papof_match_tensor", "papof_match_workspace",
     "papof_match_densify_tensor", "papof_motion_blur_tensor", "papof_decimate_tensor", "papof_upsample_flow_tensor",
-    "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor",
+    "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", "papof_sor_tiny_shape",
 ]
 
 
@@ -154,6 +154,7 @@ def load():
     L.papof_stage_est_gaussian_mixture.argtypes = [c_void_p, _D, _D, c_int, c_int, c_int, _D]
     L.papof_stage_bicubic_warp_ex.argtypes = [c_void_p, _D, _D, _D, _D, c_int, c_int, c_int, c_int, _D]
     L.papof_pyramid_levels_for_min_width.argtypes = [c_int, c_double, c_int, ctypes.POINTER(c_int)]
+    L.papof_sor_tiny_shape.argtypes = [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
     L.papof_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(c_void_p)]
     L.papof_host_free.argtypes = [c_void_p]
     L.papof_sor_plan.argtypes = [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
@@ -767,6 +768,14 @@ def bands_plan(height, width, n_sor, nranks, rank):
     out = (c_int * 6)()
     _chk(load().papof_bands_plan(height, width, n_sor, nranks, rank, out), "papof_bands_plan")
     return {"B0": out[0], "B1": out[1], "coef_rows": (out[2], out[3]), "final_rows": (out[4], out[5])}
+
+
+def sor_tiny_shape(height, width):
+    """(cells per tile, waves) of the k_sor_tiny instance that solves a height x width plane in exact order, (0, 0) when
+    none does (include/papof.h: papof_sor_tiny_shape; host only: no handle, no device)"""
+    c, nw = c_int(0), c_int(0)
+    _chk(load().papof_sor_tiny_shape(height, width, ctypes.byref(c), ctypes.byref(nw)), "papof_sor_tiny_shape")
+    return c.value, nw.value
 
 
 def tiles_unique_id():

@@ -324,7 +324,7 @@ int smooth_flow(papof_handle* h, const double* f1, const double* f2, double* war
     const Taps g = smooth5_taps();
     int solve_idx = 0;
     // exact order on a plane small enough to be solved inside one workgroup: row-major operands + k_sor_tiny (sor.hip)
-    const bool tiny = mode == PAPOF_SOR_EXACT && B.sp_tiny.phi && (size_t)H * W <= kTinyMaxCells && sor_tiny_fits(h, H, W, n_sor);
+    const bool tiny = mode == PAPOF_SOR_EXACT && B.sp_tiny.phi && sor_tiny_fits(h, H, W, n_sor);
     SorPlanes& SP = tiny ? B.sp_tiny : B.sp;
     const double* im1s = im1s_ready;  // smoothed frame 1: constant within the level (prepared ahead by flow_device)
     if (!im1s) {
@@ -725,7 +725,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
             const int n_sor_k = P.n_sor + k * P.n_sor_per_level, n_outer_k = P.n_outer + k * P.n_outer_per_level;
             unsigned* prog_k = nullptr;
             if (exact) prog_k = h->sync_words + 32 + LP[k].prog_off;  // this level's counters, cleared by the preparation stream
-            const bool tiny_k = exact && (size_t)lw * lh <= kTinyMaxCells && sor_tiny_fits(h, lh, lw, n_sor_k);  // k_sor_tiny level
+            const bool tiny_k = exact && sor_tiny_fits(h, lh, lw, n_sor_k);  // k_sor_tiny level
             if (!tiny_k) PAPOF_TRY(sor_bind(h, B.sp, lh, lw, n_sor_k));
             // the level's result goes straight to the caller's buffers on the finest level
             double* const out_u = k == 0 ? d_vx : nullptr;
@@ -1022,6 +1022,7 @@ int papof_create(int device, papof_handle** out) {
     if (const char* cs = std::getenv("PAPOF_PHASE_EVENTS")) h->phase_events = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_SOR_DEPTH")) h->sor_depth = std::max(4, std::atoi(cs));
     if (const char* cs = std::getenv("PAPOF_SOR_FUSE")) h->sor_fuse = std::max(1, std::atoi(cs));
+    if (const char* cs = std::getenv("PAPOF_SOR_TINY")) h->sor_tiny = std::atoi(cs) != 0;
     if (const char* cs = std::getenv("PAPOF_SOR_GROUP")) h->sor_group = std::max(1, std::atoi(cs));
     if (const char* cs = std::getenv("PAPOF_SOR_XCD")) h->sor_xcd_affine = std::atoi(cs);
     if (const char* cs = std::getenv("PAPOF_RB_DEPTH")) h->rb_depth = std::max(0, std::atoi(cs));
@@ -1647,7 +1648,7 @@ int papof_stage_laplacian(papof_handle* h, const double* in, const double* weigh
 
 namespace {
 int alloc_sor_planes(Scope& S, int H, int W, int mode, int n_sor, SorPlanes& sp) {
-    if (mode == PAPOF_SOR_EXACT && (size_t)H * W <= kTinyMaxCells && sor_tiny_fits(S.h, H, W, n_sor)) {  // k_sor_tiny
+    if (mode == PAPOF_SOR_EXACT && sor_tiny_fits(S.h, H, W, n_sor)) {  // k_sor_tiny
         const int rc_t = sor_alloc_tiny_planes(S.h->arena, (size_t)H * W, sp);
         if (rc_t != PAPOF_OK) S.rc = rc_t;
         return S.rc;
@@ -1763,6 +1764,12 @@ int papof_pyramid_levels_for_min_width(int width, double ratio, int min_width, i
     if (width < 1 || min_width < 1 || !levels) return PAPOF_EINVAL;
     if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;  // src/GaussianPyramid.cpp:50-51
     *levels = (int)(std::log((double)min_width / width) / std::log(ratio));  // :53
+    return PAPOF_OK;
+}
+
+int papof_sor_tiny_shape(int height, int width, int* cells_per_tile, int* waves) {
+    if (height < 1 || width < 1 || !cells_per_tile || !waves) return PAPOF_EINVAL;
+    sor_tiny_shape(height, width, cells_per_tile, waves);
     return PAPOF_OK;
 }
 

@@ -168,7 +168,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
     size_t prog_total = 0;
     for (int k = 0; k < levels; k++) {
         const int Kk = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
-        LC[k].tiny = (size_t)L[k].w * L[k].h <= kTinyMaxCells && sor_tiny_fits(h, L[k].h, L[k].w, Kk);
+        LC[k].tiny = sor_tiny_fits(h, L[k].h, L[k].w, Kk);
         LC[k].per = LC[k].tiny ? 0 : (size_t)skew_dims(L[k].h, L[k].w, Kk, 1, 1).nb * Kk * 32;
         LC[k].off = prog_total;
         prog_total += LC[k].per * (size_t)n_outer * NP;

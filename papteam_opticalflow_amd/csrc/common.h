@@ -240,6 +240,7 @@ struct papof_handle {
     int sor_group = 0;               // consecutive sweeps of a band per workgroup: 1, 2 or 4; 0 = by problem size
     int rb_depth = 0;                // blocked red-black / Jacobi solver: half-sweeps per launch; 0 = by region shape
     int rb_shape = 0;                // ... region shape 1..4 (sor.hip: blocked_shape); 0 = by plane size
+    int sor_tiny = 1;                // planes that fit one workgroup are solved by k_sor_tiny (PAPOF_SOR_TINY=0: off; sor.hip: sor_tiny_fits)
     int sor_resident = 0;            // tasks per launch of the exact-order kernels; 0 = 8 per CU (sor.hip: resident_tasks)
     int sor_skip_dead = 1;           // k_sor_exact: lanes whose row lies outside the image neither load nor store (PAPOF_SOR_DEAD=0: A/B)
     unsigned* sor_prog_next = nullptr;  // cleared progress counters for the NEXT sor_solve() (else it clears its own)
@@ -441,8 +442,9 @@ struct SorSplit {
 int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor,
                     unsigned* prog, int b0, int b1, const SorSplit* split = nullptr);
 int sor_bind_plain(papof_handle* h, SorPlanes& sp, int H, int W, int n_sor);
-bool sor_tiny_fits(const papof_handle* h, int H, int W, int n_sor);
 constexpr size_t kTinyMaxCells = 8192;  // upper bound of what sor_tiny_fits() accepts (registers of one workgroup)
+bool sor_tiny_fits(const papof_handle* h, int H, int W, int n_sor);  // is this plane solved by k_sor_tiny (null handle: switch on)
+bool sor_tiny_shape(int H, int W, int* cells_per_tile, int* waves);  // ... and by which instance (host only, no handle)
 int sor_alloc_tiny_planes(Arena& A, size_t cells, SorPlanes& sp);  // exact order inside one workgroup (k_sor_tiny; row-major operands)  // as sor_bind, one sweep per wave / workgroup
 // progress counters cleared ahead of the solves that use them (flow_device: all of a call's, on the preparation stream)
 size_t sor_counters_words(int H, int W, int n_sor);

@@ -1576,8 +1576,8 @@ __global__ __launch_bounds__(NW * 64) void k_sor_blocked(BlockedArgs A) {
 //   * R + Q + 2 K - 2 tile-times, each bound by the vector issue of the one CU (~40 instructions per cell and wave).  Measured
 //     (MI355X, inside a 15-level call): 34x19 x 72 sweeps 60 us instead of 287, 60x33 x 66 sweeps 98 instead of 263, 108x60 x
 //     60 sweeps 219 instead of 249; a 240x135 pair on 15 levels 51.5 -> 18.9 ms.
-// Capacity: registers (7 doubles per cell) -- ~5 k cells (tiles of at most 10 cells; wider ones are no faster than the task
-// pipeline).  Operands are the
+// Capacity: registers (7 doubles per cell) and the 150 KiB of LDS -- ~5 k cells in tiles of at most 6 cells: the narrowest
+// tile that holds the plane is taken, and no plane that fits the LDS needs a wider one (PAPOF_TINY_SHAPES).  Operands are the
 // ROW-MAJOR planes the red-black / Jacobi modes use (k_assemble writes them, k_update_warp_phi<false> reads the result).
 // ------------------------------------------------------------------------------------------------
 struct TinyArgs {
@@ -1839,13 +1839,19 @@ struct TinyShape {
     int c, nw;  // cells per tile; most waves the instantiation may be launched with
     int waves;  // waves this plane needs: ceil(rows x lanes per row / 64)
 };
-static bool tiny_shape(int H, int W, int K, TinyShape& best) {
+// The instances of k_sor_tiny, X(cells per tile, most waves): tiny_shape() chooses among exactly these and sor_tiny_solve()
+// launches exactly these.  Every one is selected by some plane (tests/test_sor_tiny_shapes.py enumerates them all): tiles
+// of 4, 8 and 10 cells were candidates once, but a plane too large for the 6-cell tile exceeds their lanes or the LDS too.
+#define PAPOF_TINY_SHAPES(X) X(1, 16) X(2, 16) X(3, 12) X(5, 8) X(6, 8)
+static bool tiny_shape(int H, int W, TinyShape& best) {
     // Narrow tiles on many waves win while the lanes fit (measured on MI355X, profiles/r03_tiny_sweep.txt: e.g.
     // 60x33 x 66 sweeps 91 / 97 / 104 / 113 / 124 / 177 us at C = 1 / 2 / 3 / 4 / 6 / 8): the narrowest shape that holds the
     // plane is taken.  Tiles of 14 cells (the only shape that holds ~6.5 k cells) run as long as the task pipeline does
     // (108x60 x 60 sweeps: 249 us either way) and are left to it.
-    static const TinyShape cand[] = {{1, 16, 0}, {2, 16, 0}, {3, 12, 0}, {4, 8, 0}, {5, 8, 0}, {6, 8, 0}, {8, 4, 0}, {10, 4, 0}};
-    (void)K;
+#define PAPOF_TINY_CAND(CC, NWW) {CC, NWW, 0},
+    static const TinyShape cand[] = {PAPOF_TINY_SHAPES(PAPOF_TINY_CAND)};
+#undef PAPOF_TINY_CAND
+    if (H < 1 || W < 1 || (size_t)H * W > kTinyMaxCells) return false;
     for (TinyShape t : cand) {
         const int Q = (W + t.c - 1) / t.c, QP = (Q + 1) / 2;
         if ((long long)H * QP > t.nw * 64) continue;
@@ -1857,18 +1863,27 @@ static bool tiny_shape(int H, int W, int K, TinyShape& best) {
     return false;
 }
 
-// May a height x width plane be solved in exact order by k_sor_tiny?  (PAPOF_SOR_TINY=0 switches the path off: A/B)
+// Which instance of k_sor_tiny solves a height x width plane (papof_sor_tiny_shape): false when none does
+bool sor_tiny_shape(int H, int W, int* cells_per_tile, int* waves) {
+    TinyShape t{0, 0, 0};
+    const bool ok = tiny_shape(H, W, t);
+    if (cells_per_tile) *cells_per_tile = ok ? t.c : 0;
+    if (waves) *waves = ok ? t.waves : 0;
+    return ok;
+}
+
+// Is a height x width plane solved in exact order by k_sor_tiny?  The one predicate of every caller.  PAPOF_SOR_TINY=0
+// (read when the handle is created: papof_handle::sor_tiny) switches the path off: A/B, and how the tests reach the
+// hyperplane kernels on small planes; a null handle means "on".
 bool sor_tiny_fits(const papof_handle* h, int H, int W, int n_sor) {
-    static const bool off = std::getenv("PAPOF_SOR_TINY") && std::atoi(std::getenv("PAPOF_SOR_TINY")) == 0;
-    (void)h;
     TinyShape t;
-    return !off && H >= 1 && W >= 1 && n_sor >= 1 && tiny_shape(H, W, n_sor, t);
+    return (!h || h->sor_tiny) && n_sor >= 1 && tiny_shape(H, W, t);
 }
 
 static int sor_tiny_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor,
                           int batch = 1, size_t bstride = 0) {
     TinyShape t;
-    if (sp.skew || !tiny_shape(H, W, n_sor, t)) return PAPOF_EINVAL;
+    if (sp.skew || n_sor < 1 || !tiny_shape(H, W, t)) return PAPOF_EINVAL;
     TinyArgs A;
     A.phi = sp.phi;
     A.xy = sp.xy;
@@ -1897,22 +1912,10 @@ static int sor_tiny_solve(papof_handle* h, const SorPlanes& sp, int H, int W, do
         }                                                                                                             \
         hipLaunchKernelGGL((k_sor_tiny<CC, NWW>), dim3(batch), dim3(t.waves * 64), lds, h->stream, A);                    \
     } while (0)
-    if (t.c == 1)
-        PAPOF_TINY(1, 16);
-    else if (t.c == 2)
-        PAPOF_TINY(2, 16);
-    else if (t.c == 3)
-        PAPOF_TINY(3, 12);
-    else if (t.c == 4)
-        PAPOF_TINY(4, 8);
-    else if (t.c == 5)
-        PAPOF_TINY(5, 8);
-    else if (t.c == 6)
-        PAPOF_TINY(6, 8);
-    else if (t.c == 8)
-        PAPOF_TINY(8, 4);
-    else
-        PAPOF_TINY(10, 4);
+#define PAPOF_TINY_CASE(CC, NWW) \
+    if (t.c == CC) PAPOF_TINY(CC, NWW);
+    PAPOF_TINY_SHAPES(PAPOF_TINY_CASE)
+#undef PAPOF_TINY_CASE
 #undef PAPOF_TINY
     PAPOF_HIP(hipGetLastError());
     return PAPOF_OK;
@@ -2417,6 +2420,8 @@ int sor_reset_planes_batch(papof_handle* h, const SorPlanes& sp, int batch, size
 int sor_group_size(const papof_handle* h, int H, int W, int n_sor) {
     if (!h || !h->use_dpp || n_sor < 2) return 1;
     int g = h->sor_group;
+    // a REQUESTED fused kernel (PAPOF_SOR_FUSE=2) is not overruled by the size heuristic below, only by a requested group
+    if (g == 0 && h->sor_fuse == 2) return 1;
     if (g == 0) {
         // measured: an isolated 240x135 solve gains 17 % (0.25 -> 0.21 ms), a 240x135 pair nothing.  Round 3, inside
         // 15-level calls (profiles/r03_mid_level_kernels.txt): four sweeps per workgroup through LDS win where a solve is

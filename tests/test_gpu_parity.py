@@ -509,14 +509,19 @@ def test_pyflow_dropin_entry_point(oracle):
                                         ("PAPOF_SOR_XCD", "2"), ("PAPOF_OVERLAP", "0"), ("PAPOF_SOR_XLANE", "shfl"),
                                         ("PAPOF_SOR_FUSE", "2"), ("PAPOF_SOR_FUSE", "1"), ("PAPOF_SOR_FUSE+DEPTH", "2+10"),
                                         ("PAPOF_SOR_RESIDENT", "24"), ("PAPOF_SOR_RESIDENT+FUSE", "24+2"),
-                                        ("PAPOF_SOR_RESIDENT+GROUP", "24+4")])
+                                        ("PAPOF_SOR_RESIDENT+GROUP", "24+4"), ("PAPOF_SOR_TINY", "0"),
+                                        ("PAPOF_SOR_TINY+FUSE", "0+2"), ("PAPOF_SOR_TINY+GROUP", "0+2"),
+                                        ("PAPOF_SOR_TINY+GROUP", "0+4")])
 def test_every_solver_variant_matches_oracle(oracle, knob, value, monkeypatch):
     """Every tuning knob selects code that must give the reference's bits too: the opt-in grouped solver
     (PAPOF_SOR_GROUP: M sweeps of a band per workgroup, LDS hand-off; sor.hip k_sor_group), the pipeline depths the
     size heuristic does not pick, the XCD mappings, the single-stream orchestration, the ds_bpermute lane shifts, and
     the fused kernel (PAPOF_SOR_FUSE=2: two sweeps per wave, k_sor_fused; even and odd sweep counts, one and many bands)
     forced on for every size / forced off; PAPOF_SOR_RESIDENT: a solve split into many consecutive launches over ranges
-    of sweeps (what sor_solve does when a solve has more tasks than the chip keeps resident), for all three kernels."""
+    of sweeps (what sor_solve does when a solve has more tasks than the chip keeps resident), for all three kernels.
+    The planes of one and two bands in the list go to the one-workgroup solver (k_sor_tiny) whatever those knobs say; with
+    PAPOF_SOR_TINY=0 they reach the hyperplane kernels, alone and under the fused and grouped kernels
+    (tests/test_gpu_sor_kernels.py asserts per case which kernel ran)."""
     from papteam_opticalflow_amd import Papof
     group = knob + "=" + value
     if "+" in knob:  # two knobs at once
