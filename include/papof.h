@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define PAPOF_VERSION 115 /* 0.1.15: papof_motion_blur_tensor (synthetic motion blur: the shutter's samples of papof_interp_tensor's rule summed in one kernel) -- an addition only, the number stays; papof_match_tensor / papof_match_workspace / papof_match_densify_tensor (dense block matching of decimated uint8 frames, a start for the solver on large displacements) -- additions only, the number stays; papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
+#define PAPOF_VERSION 115 /* 0.1.15: papof_homography_fit_tensor / papof_homography_workspace / papof_warp_projective_tensor / papof_mosaic_projective_tensor / papof_mosaic_overlap_projective_tensor (the homography model: the fit, the warp, the mosaic and the overlap statistics over 3 x 3 matrices) -- additions only, the number stays; papof_motion_blur_tensor (synthetic motion blur: the shutter's samples of papof_interp_tensor's rule summed in one kernel) -- an addition only, the number stays; papof_match_tensor / papof_match_workspace / papof_match_densify_tensor (dense block matching of decimated uint8 frames, a start for the solver on large displacements) -- additions only, the number stays; papof_splat_tensor / papof_splat_workspace (forward warping: deterministic splatting along a flow, 64-bit fixed-point sums), papof_interp_splat_tensor (frame interpolation by splatting both frames) -- additions only, the number stays; papof_fill_holes_tensor / papof_fill_workspace (a field filled inside a mask: pull-push and Jacobi relaxation), papof_propagate_tensor (holes filled from other frames along the flows): flow-guided video completion; 0.1.14: papof_temporal_filter_tensor (motion-compensated temporal denoising along a video's forward and backward flows); 0.1.13: papof_motion_fit_tensor / papof_motion_workspace (global motion of a flow field, IRLS in fp64), papof_warp_affine_tensor (frames warped by per-frame affine matrices): video stabilization; 0.1.12: papof_flow_batch_tensor_init / papof_flow_batch_tensor_fb_init (the device-tensor calls started from a caller's initial flow); 0.1.11: papof_interp_tensor (motion-compensated frame interpolation from forward and backward flows and an occlusion mask); 0.1.10: papof_set_graph_mode removed (hipGraph replay, PAPOF_GRAPH, is retired; so are PAPOF_HOST_COPY / PAPOF_HOST_THREADS, PAPOF_HOSTIO and PAPOF_PREP_CUS); 0.1.9: papof_strip_plan removed (the strips schedule, PAPOF_STRIPS, is retired); 0.1.8: papof_track_tensor (point tracks through a video's forward and backward flows); 0.1.7: papof_flow_batch_tensor_fb (forward and backward pairs in one launch chain, occlusion masks), papof_fb_check_tensor; 0.1.6: papof_flow_batch_tensor (strided device tensors in and out, ordered on the caller's stream), papof_tensor / PAPOF_DTYPE_*; 0.1.5: papof_flow_batch / papof_flow_batch_u8, papof_last_host_times, PAPOF_RCCL_LIB / PAPOF_TILES_TIMEOUT_S; 0.1.4: the Laplacian-noise guard (papof_lap_guard_stats); 0.1.3: papof_last_sor_solves, exact-order band split over ranks (papof_tiles_*, PAPOF_SOR_EXACT); 0.1.2: measurement / test aids (papof_last_sor_stats, papof_strip_plan, papof_test_sor_strips); 0.1.1: papof_params gained interpolation / noise_model */
 
 enum {
     PAPOF_OK = 0,
@@ -1246,6 +1246,86 @@ int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int height, int w
                                 const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
                                 const int* sources, const papof_tensor* matrices, int step, double bound, long long* sums,
                                 long long* counts, void* stream);
+
+/* The homography model: the calls above over 3 x 3 matrices, for a camera that rotates (a pan on a tripod or in a hand moves
+ * the image by a homography, not by an affine map).  A parallel family: the affine calls are unchanged.
+ *
+ * PROJECTIVE SAMPLING (the rule of the warp, the mosaic and the overlap call below).  m: a 3 x 3 matrix, float32 (widened
+ * exactly) or float64.  At output pixel (x, r), in fp64 without fused multiply-adds:
+ *     D = (m20 * x + m21 * r) + m22;  Nx = (m00 * x + m01 * r) + m02;  Ny = (m10 * x + m11 * r) + m12
+ *     X = Nx / D;  Y = Ny / D                      (two divisions, not a reciprocal and two products)
+ *     live / inside iff D > 0 and 0 <= X <= W - 1 and 0 <= Y <= H - 1 (every comparison false for a NaN)
+ * and from (X, Y) on everything is the affine call's rule: the taps, the tap-wise mask rule, the gains, the feather weight,
+ * the modes, the count and the sampler.  A matrix whose last row is exactly (0, 0, 1) has D = 1.0, X = Nx and Y = Ny: the
+ * projective calls on such matrices return the BYTES of the affine calls on their top two rows.
+ *
+ * papof_warp_projective_tensor (motion.hip: k_warp_projective): papof_warp_affine_tensor with matrices (frame, row, column),
+ * 3 x 3; out is 0 and valid 0 where the pixel is not inside.  Arguments and PAPOF_EINVAL as there.
+ *
+ * papof_mosaic_projective_tensor (mosaic.hip: k_mosaic over ProjArgs): papof_mosaic_blend_tensor -- all four modes, gains
+ * NULL or given -- with matrices (out, k, row, column), 3 x 3.  papof_mosaic_overlap_projective_tensor: the overlap call
+ * likewise.  Arguments, limits (PAPOF_MOSAIC_MAX_SOURCES, _MAX_MEDIAN, _MAX_OVERLAP), PAPOF_MOSAIC_CULL and PAPOF_EINVAL as
+ * there.  Tile culling, which changes no byte: with the min and max of D, Nx and Ny over the tile's four corners (each is
+ * monotone in x and r under rounding, so these bound every pixel's when no corner value is NaN), a slot is dropped when an entry of its first two rows
+ * is not finite, when no corner has D > 0, or when every corner has D > 0 and the interval
+ * [min(Nx_min / D_min, Nx_min / D_max), max(Nx_max / D_min, Nx_max / D_max)], widened by a pixel, misses [0, W - 1] (the
+ * same for Y and H); correctly rounded division is monotone in each operand, so the interval holds every pixel's computed
+ * X.  A NaN corner value or quotient and a D of mixed sign prove nothing: the slot stays.  mosaic.hip has the proof.
+ *
+ * papof_homography_fit_tensor (motion.hip: k_homography_sums, k_homography_solve): papof_motion_fit_tensor's arguments
+ * without `model`; motion: float64 (pair, row, column) = the 3 x 3 matrix M with m22 == 1.0 that sends (x, r, 1) of frame i to
+ * frame i + 1 (divide by the third coordinate).  Valid pixels, cx, cy, s, x^, y^, X^, Y^ are that call's.  The unknowns are
+ * h0 .. h7 of Hn = (h0 h1 h2; h3 h4 h5; h6 h7 1) in normalised coordinates; a valid pixel contributes the two rows
+ *     (x^, y^, 1, 0, 0, 0, -x^ X^, -y^ X^ | X^)   and   (0, 0, 0, x^, y^, 1, -x^ Y^, -y^ Y^ | Y^),   each weighted by w:
+ *     iteration 0:       w = c = 1
+ *     iteration k >= 1:  with M the pair's matrix after iteration k - 1,
+ *                        d = (m20 * x + m21 * r) + m22;  dn = d / ((m20 * cx + m21 * cy) + m22)
+ *                        !(dn > PAPOF_HOMOGRAPHY_MIN_DEN): the pixel is left out of this iteration (it still counts in S23)
+ *                        e_x = (x + u) - ((m00 * x + m01 * r) + m02) / d;  e_y = (r + v) - ((m10 * x + m11 * r) + m12) / d
+ *                        e^2 = e_x * e_x + e_y * e_y;  c = 1 / (1 + e^2 / (scale * scale));  w = c / (dn * dn)
+ * (1 / dn^2 turns the algebraic rows into the geometric error of the previous iterate).  With xx = x^ * x^, xy = x^ * y^,
+ * yy = y^ * y^ and q = X^ * X^ + Y^ * Y^, every product grouped as written, the twenty-five sums are
+ *     S0 = sum w xx          S1 = sum w xy          S2 = sum w yy          S3 = sum w x^           S4 = sum w y^          S5 = sum w
+ *     S6 = sum w (xx * X^)   S7 = sum w (xy * X^)   S8 = sum w (yy * X^)   S9 = sum w (x^ * X^)    S10 = sum w (y^ * X^)  S11 = sum w X^
+ *     S12 = sum w (xx * Y^)  S13 = sum w (xy * Y^)  S14 = sum w (yy * Y^)  S15 = sum w (x^ * Y^)   S16 = sum w (y^ * Y^)  S17 = sum w Y^
+ *     S18 = sum w (xx * q)   S19 = sum w (xy * q)   S20 = sum w (yy * q)   S21 = sum w (x^ * q)    S22 = sum w (y^ * q)
+ *     S23 = sum valid        S24 = sum c
+ * added in papof_motion_fit_tensor's fixed order (no atomics: bitwise reproducible).  The normal equations
+ *     (  S0   S1   S3    0    0    0   -S6   -S7 ) (h0)   (  S9  )
+ *     (  S1   S2   S4    0    0    0   -S7   -S8 ) (h1)   (  S10 )
+ *     (  S3   S4   S5    0    0    0   -S9  -S10 ) (h2)   (  S11 )
+ *     (   0    0    0   S0   S1   S3  -S12  -S13 ) (h3) = (  S15 )
+ *     (   0    0    0   S1   S2   S4  -S13  -S14 ) (h4)   (  S16 )
+ *     (   0    0    0   S3   S4   S5  -S15  -S16 ) (h5)   (  S17 )
+ *     ( -S6  -S7  -S9 -S12 -S13 -S15   S18   S19 ) (h6)   ( -S21 )
+ *     ( -S7  -S8 -S10 -S13 -S14 -S16   S19   S20 ) (h7)   ( -S22 )
+ * are solved by Gaussian elimination in natural order without row exchanges; a pivot not > 1e-12 * S5 fails the iteration.
+ * Back to pixels, M = T^-1 Hn T with T = (1/s 0 -cx/s; 0 1/s -cy/s; 0 0 1), computed up to the factor s as
+ *     A[i][0] = Hn[i][0];  A[i][1] = Hn[i][1];  A[i][2] = s * Hn[i][2] - (Hn[i][0] * cx + Hn[i][1] * cy)       (A = Hn (s T))
+ *     B[0][j] = s * A[0][j] + cx * A[2][j];  B[1][j] = s * A[1][j] + cy * A[2][j];  B[2][j] = A[2][j]          (B = T^-1 A)
+ *     M[i][j] = B[i][j] / B[2][2]
+ * The iteration fails where S5 <= 0, at a pivot, where B[2][2] is not > 0, where an entry of M is not finite, or where the
+ * denominator (m20 * x + m21 * r) + m22 is not > 0 at one of the four image corners.  Failure semantics, ok, the workspace
+ * rules and PAPOF_EINVAL are papof_motion_fit_tensor's (a failed iteration 0: the 3 x 3 identity, ok = 0, no further
+ * iterations).  support = S24 of the pair's last iteration / (H * W): comparable with the affine fit's.
+ * papof_homography_workspace: 8 * n_pairs * (12 + 32 * ceil(width / 64) * ceil(height / 32)) bytes, or -1 as
+ * papof_motion_workspace. */
+#define PAPOF_HOMOGRAPHY_MIN_DEN 0.0625
+long long papof_homography_workspace(int n_pairs, int height, int width);
+int papof_homography_fit_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow,
+                                const papof_tensor* occlusion, int n_iter, double scale, const papof_tensor* motion,
+                                const papof_tensor* ok, const papof_tensor* support, void* workspace, long long workspace_bytes,
+                                void* stream);
+int papof_warp_projective_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                 const papof_tensor* matrices, const papof_tensor* out, const papof_tensor* valid, void* stream);
+int papof_mosaic_projective_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                   const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                   const int* sources, const papof_tensor* matrices, const papof_tensor* gains, int mode,
+                                   const papof_tensor* out, const papof_tensor* count, void* stream);
+int papof_mosaic_overlap_projective_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                           const papof_tensor* frames, const papof_tensor* masks, int n_out, int n_src,
+                                           int out_height, int out_width, const int* sources, const papof_tensor* matrices,
+                                           int step, double bound, long long* sums, long long* counts, void* stream);
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a

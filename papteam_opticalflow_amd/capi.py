@@ -72,6 +72,8 @@ SYMBOLS = [
     "papof_super_resolve_tensor", "papof_sr_workspace", "papof_match_tensor", "papof_match_workspace",
     "papof_match_densify_tensor", "papof_motion_blur_tensor", "papof_decimate_tensor", "papof_upsample_flow_tensor",
     "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", "papof_sor_tiny_shape",
+    "papof_homography_workspace", "papof_homography_fit_tensor", "papof_warp_projective_tensor",
+    "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor",
 ]
 
 
@@ -232,6 +234,17 @@ def load():
     L.papof_mosaic_overlap_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, c_void_p, _T,
                                               c_int, c_double, c_void_p, c_void_p, c_void_p]
     L.papof_mosaic_overlap_tensor.restype = c_int
+    L.papof_homography_workspace.argtypes = [c_int, c_int, c_int]
+    L.papof_homography_workspace.restype = ctypes.c_longlong
+    L.papof_homography_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_double, _T, _T, _T, c_void_p,
+                                              ctypes.c_longlong, c_void_p]
+    L.papof_homography_fit_tensor.restype = c_int
+    L.papof_warp_projective_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, _T, c_void_p]
+    L.papof_warp_projective_tensor.restype = c_int
+    L.papof_mosaic_projective_tensor.argtypes = L.papof_mosaic_blend_tensor.argtypes
+    L.papof_mosaic_projective_tensor.restype = c_int
+    L.papof_mosaic_overlap_projective_tensor.argtypes = L.papof_mosaic_overlap_tensor.argtypes
+    L.papof_mosaic_overlap_projective_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

@@ -26,6 +26,35 @@
 // PAPOF_MOSAIC_FEATHER weighs it by the distance of (X, Y) to the frame's border.  The instances over MosaicArgs (the gain
 // is the constant 1.0 there) are what papof_mosaic_tensor launches, as before, and this call too without gains.
 //
+// papof_mosaic_projective_tensor and papof_mosaic_overlap_projective_tensor are the same two kernels over ProjArgs: the
+// matrices are 3 x 3 and a pixel's point is (X, Y) = (Nx / D, Ny / D), live only where D > 0 (include/papof.h: projective
+// sampling).  The mapping and the culling are chosen at compile time by the argument type; the instances over MosaicArgs and
+// BlendArgs, and the affine overlap instances, are instruction for instruction what they were (only the overlap kernels'
+// mangled names gained the argument type).
+//   Culling under the projective rule (projective_keep).  Canvas coordinates are >= 0.  D, Nx and Ny are each
+//   (a x + b r) + c: every step is monotone in x and in r under rounding, overflow to +-inf included.  A NaN at a pixel
+//   arises in one of two ways.  (i) inf - inf in a x + b r, or that sum meeting an infinite c of the other sign: |a x| and
+//   |b r| grow with x and r, so the same infinities meet at the tile's far corner (xb, rb), which is NaN too.  (ii) 0 * inf:
+//   an infinite entry a or b (the last row's; (1) below removes the others) times x = 0 or r = 0 -- that pixel lies on the
+//   tile's edge x = xa = 0 or r = ra = 0, and the product is the same NaN at the corner of that edge.  So a NaN at a pixel
+//   means a NaN at a corner: when no corner value is NaN, no pixel's is, and the min and max over the four corners bound
+//   every pixel's D, Nx and Ny.
+//     (1) An entry of the first two rows that is not finite makes Nx or Ny +-inf or NaN at every pixel, and a quotient of it
+//         +-inf or NaN: live nowhere, dropped.  (An infinite entry of the LAST row can leave X = Nx / inf = 0 inside the
+//         frame: such a matrix goes through the corner test like any other.)
+//     (2) A NaN corner value proves nothing: kept.
+//     (3) D_max <= 0: D > 0 at no pixel: dropped.
+//     (4) D_min <= 0 < D_max: the horizon may cross the tile: kept.
+//     (5) 0 < D_min: correctly rounded division is monotone in each operand -- N / D does not decrease with N, and for D > 0
+//         does not increase with D when N >= 0 and does not decrease with D when N < 0.  So for every pixel
+//         fl(Nx / D) <= fl(Nx_max / D) <= max(fl(Nx_max / D_min), fl(Nx_max / D_max)), and likewise
+//         fl(Nx / D) >= min(fl(Nx_min / D_min), fl(Nx_min / D_max)).  When both upper quotients are < -1, or both lower ones
+//         > W - 1 + 1 (the affine box's one-pixel margin), X is outside [0, W - 1] at every pixel: dropped; the same for Y and
+//         H.  A quotient inf / inf is NaN, every comparison with it false: kept.
+//   Dropping changes no byte, as in the affine case.  The interval is looser than the affine corner box -- it pairs the
+//   extreme numerator with the extreme denominator, which need not meet at one pixel: DESIGN.md section 27 has the share of
+//   slots it keeps.
+//
 // k_mosaic_overlap (papof_mosaic_overlap_tensor).  A block is a 64 x 2 tile of SAMPLED pixels (every step-th column and
 // row).  Phases 1 and 2 as above, each lane writing the fixed-point luminance q of its live slots to LDS [slot][pixel] and
 // the 64-bit set of them.  Then the roles turn: lane j is source j (64 / NS pixels side by side where NS < 64), wave w owns
@@ -64,6 +93,11 @@ struct BlendArgs : MosaicArgs {
     papof_tensor gains;  // float32 / float64 (out, k); data NULL: every gain is 1
 };
 
+struct ProjArgs : BlendArgs {};  // mat is (out, k, row, column): 3 x 3, the projective rule of include/papof.h
+
+template <typename A>
+constexpr bool kProjective = std::is_same<A, ProjArgs>::value;
+
 __device__ __forceinline__ double slot_gain(const MosaicArgs&, long long, int) { return 1.0; }
 __device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int k) {
     return b.gains.data ? load_flow(b.gains, o * b.gains.stride[0] + k * b.gains.stride[1]) : 1.0;
@@ -72,13 +106,68 @@ __device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int
 // a sorts before b: a < b, or a is a number and b is NaN
 __device__ __forceinline__ bool sorts_before(double a, double b) { return a < b || (a == a && b != b); }
 
+// Phase 1 over a 3 x 3 matrix (at offset mb): false where the slot is live at no pixel of [xa, xb] x [ra, rb] (the header
+// comment has the proof)
+__device__ __forceinline__ bool projective_keep(const MosaicArgs& a, long long mb, double xa, double xb, double ra, double rb) {
+    double m[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
+    bool finite = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
+    if (!finite) return false;  // Nx or Ny is +-inf or NaN at every pixel, and so is its quotient
+    double v[3][4];             // D, Nx, Ny at the four corners
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const double mx = m[3 * ((q + 2) % 3)], mr = m[3 * ((q + 2) % 3) + 1], mc = m[3 * ((q + 2) % 3) + 2];
+        v[q][0] = (mx * xa + mr * ra) + mc;
+        v[q][1] = (mx * xb + mr * ra) + mc;
+        v[q][2] = (mx * xa + mr * rb) + mc;
+        v[q][3] = (mx * xb + mr * rb) + mc;
+    }
+    bool nan = false;
+#pragma unroll
+    for (int q = 0; q < 3; q++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) nan = nan || v[q][j] != v[q][j];
+    if (nan) return true;  // proves nothing
+    double lo[3], hi[3];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        lo[q] = fmin(fmin(v[q][0], v[q][1]), fmin(v[q][2], v[q][3]));
+        hi[q] = fmax(fmax(v[q][0], v[q][1]), fmax(v[q][2], v[q][3]));
+    }
+    if (!(hi[0] > 0)) return false;  // D > 0 at no pixel
+    if (!(lo[0] > 0)) return true;   // the horizon may cross the tile
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    // (a quotient inf / inf is NaN: every comparison is false, the source stays)
+    const bool missx = (hi[1] / lo[0] < -1.0 && hi[1] / hi[0] < -1.0) || (lo[1] / lo[0] > W1 + 1.0 && lo[1] / hi[0] > W1 + 1.0);
+    const bool missy = (hi[2] / lo[0] < -1.0 && hi[2] / hi[0] < -1.0) || (lo[2] / lo[0] > H1 + 1.0 && lo[2] / hi[0] > H1 + 1.0);
+    return !missx && !missy;
+}
+
+// The projective point of pixel (xd, rd) under the 3 x 3 matrix at mb: false where D is not > 0 (a NaN included)
+__device__ __forceinline__ bool projective_point(const MosaicArgs& a, long long mb, double xd, double rd, double& X, double& Y) {
+    double m[9];
+#pragma unroll
+    for (int rr = 0; rr < 3; rr++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
+    const double D = (m[6] * xd + m[7] * rd) + m[8];
+    X = ((m[0] * xd + m[1] * rd) + m[2]) / D;
+    Y = ((m[3] * xd + m[4] * rd) + m[5]) / D;
+    return D > 0;
+}
+
 // k_mosaic_overlap's phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its
 // matrices) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order; returns
 // their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
 // (k_mosaic's phase 1 in a function.  k_mosaic keeps its own text: called from there, this function and slot_live gave its
 // instances another register allocation, and the instances papof_mosaic_tensor launches are to stay the code they were.)
-template <int TY>
-__device__ __forceinline__ int cull_slots(const MosaicArgs& a, const int* src, long long mo, double xa, double xb, double ra,
+template <int TY, typename A>
+__device__ __forceinline__ int cull_slots(const A& a, const int* src, long long mo, double xa, double xb, double ra,
                                           double rb, unsigned short* list, int* wcount) {
     constexpr int NT = kMosTX * TY;
     const int tid = threadIdx.y * kMosTX + threadIdx.x;
@@ -87,7 +176,9 @@ __device__ __forceinline__ int cull_slots(const MosaicArgs& a, const int* src, l
     for (int base = 0; base < a.n_src; base += NT) {
         const int k = base + tid;
         bool keep = k < a.n_src && src[k] >= 0;
-        if (keep && a.cull) {
+        if constexpr (kProjective<A>) {
+            if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
+        } else if (keep && a.cull) {
             double m[6];
             const long long mb = mo + k * a.mat.stride[1];
 #pragma unroll
@@ -150,10 +241,31 @@ __device__ __forceinline__ bool slot_live(const MosaicArgs& a, long long s, long
     return true;
 }
 
-// A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER
+// slot_live over a 3 x 3 matrix (k_mosaic_overlap over ProjArgs).  An overload with its own text: as a template over the
+// argument type, slot_live gave the affine overlap instances another register allocation.
+__device__ __forceinline__ bool slot_live(const ProjArgs& a, long long s, long long mb, double xd, double rd, double& X,
+                                          double& Y, Bilinear& t) {
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    if (!projective_point(a, mb, xd, rd, X, Y)) return false;
+    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
+    t = taps_at(X, Y, a.H, a.W);
+    if (a.mask.data) {
+        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
+        bool masked = false;
+        const long long b = s * a.mask.stride[0];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
+        if (masked) return false;
+    }
+    return true;
+}
+
+// A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER; or ProjArgs:
+// BlendArgs under the projective rule
 template <int FD, int MODE, int CAP, int TY, typename A>
 __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile0, long long out0) {
-    constexpr bool BLEND = std::is_same<A, BlendArgs>::value;
+    constexpr bool BLEND = std::is_same<A, BlendArgs>::value || kProjective<A>;
     static_assert(BLEND || MODE != PAPOF_MOSAIC_FEATHER, "k_mosaic: FEATHER is a blend mode");
     constexpr int NT = kMosTX * TY;
     constexpr int CH = MODE == PAPOF_MOSAIC_MEDIAN ? 1 : 4;  // channels per walk of the list
@@ -180,7 +292,9 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
         for (int base = 0; base < a.n_src; base += NT) {
             const int k = base + tid;
             bool keep = k < a.n_src && src[k] >= 0;
-            if (keep && a.cull) {
+            if constexpr (kProjective<A>) {
+                if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
+            } else if (keep && a.cull) {
                 double m[6];
                 const long long mb = mo + k * a.mat.stride[1];
 #pragma unroll
@@ -234,12 +348,18 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
             const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
             const long long s = src[k];
             const long long mb = mo + k * a.mat.stride[1];
-            double m[6];
+            double X, Y;
+            if constexpr (kProjective<A>) {
+                if (!projective_point(a, mb, xd, rd, X, Y)) continue;
+            } else {
+                double m[6];
 #pragma unroll
-            for (int rr = 0; rr < 2; rr++)
+                for (int rr = 0; rr < 2; rr++)
 #pragma unroll
-                for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
-            const double X = (m[0] * xd + m[1] * rd) + m[2], Y = (m[3] * xd + m[4] * rd) + m[5];
+                    for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
+                X = (m[0] * xd + m[1] * rd) + m[2];
+                Y = (m[3] * xd + m[4] * rd) + m[5];
+            }
             if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) continue;  // (false for a NaN)
             const Bilinear t = taps_at(X, Y, a.H, a.W);
             if (mk) {
@@ -320,7 +440,7 @@ template <typename A>
 int launch_mosaic(hipStream_t st, const A& a, int n_out, int mode) {
     const int n_src = a.n_src;
     if (mode == PAPOF_MOSAIC_FEATHER) {
-        if constexpr (std::is_same<A, BlendArgs>::value) return launch_mosaic_as<PAPOF_MOSAIC_FEATHER, 0, 4>(st, a, n_out);
+        if constexpr (!std::is_same<A, MosaicArgs>::value) return launch_mosaic_as<PAPOF_MOSAIC_FEATHER, 0, 4>(st, a, n_out);
         return PAPOF_EINVAL;
     }
     if (mode == PAPOF_MOSAIC_FIRST) return launch_mosaic_as<PAPOF_MOSAIC_FIRST, 0, 4>(st, a, n_out);
@@ -336,8 +456,9 @@ constexpr int kOvTY = 2;                   // a 64 x 2 tile of sampled pixels: t
 constexpr int kOvNT = kMosTX * kOvTY;
 constexpr double kOvOne = 16777216.0;      // q = rint(t * 2^24)
 
-struct OverlapArgs {
-    MosaicArgs m;                // out and count are not used
+template <typename A>
+struct OverlapArgsOf {
+    A m;                         // MosaicArgs or ProjArgs; out, count and gains are not used
     unsigned long long* sums;    // (out, i, j), contiguous
     unsigned long long* counts;
     double bound;
@@ -346,10 +467,10 @@ struct OverlapArgs {
 };
 
 // NS: the slots the tables hold (n_src <= NS), a power of two <= 64
-template <int FD, int NS>
-__global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgs args, long long tile0, long long out0) {
+template <int FD, int NS, typename A>
+__global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A> args, long long tile0, long long out0) {
     constexpr int G = 64 / NS;  // pixels side by side in phase 3
-    const MosaicArgs& a = args.m;
+    const A& a = args.m;
     __shared__ double lut[256];
     __shared__ unsigned short list[64];
     __shared__ int wcount[kOvTY];
@@ -457,12 +578,12 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgs args
     }
 }
 
-template <int NS>
-int launch_overlap_as(hipStream_t st, const OverlapArgs& a, int n_out) {
+template <int NS, typename A>
+int launch_overlap_as(hipStream_t st, const OverlapArgsOf<A>& a, int n_out) {
     const int fd = a.m.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic_overlap<PAPOF_DTYPE_U8, NS>
-                        : fd == PAPOF_DTYPE_F32 ? k_mosaic_overlap<PAPOF_DTYPE_F32, NS>
-                                                : k_mosaic_overlap<PAPOF_DTYPE_F64, NS>;
+    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic_overlap<PAPOF_DTYPE_U8, NS, A>
+                        : fd == PAPOF_DTYPE_F32 ? k_mosaic_overlap<PAPOF_DTYPE_F32, NS, A>
+                                                : k_mosaic_overlap<PAPOF_DTYPE_F64, NS, A>;
     const long long tiles = ((a.nsx + kMosTX - 1) / (long long)kMosTX) * ((a.nsr + kOvTY - 1) / (long long)kOvTY);
     return launch_tiles(tiles, n_out, [&](dim3 grid, long long t0, long long o0) {
         hipLaunchKernelGGL(kernel, grid, dim3(kMosTX, kOvTY), 0, st, a, t0, o0);
@@ -521,11 +642,13 @@ extern "C" int papof_mosaic_tensor(papof_handle* h, int n_frames, int height, in
     return launch_mosaic(static_cast<hipStream_t>(stream), a, n_out, mode);
 }
 
-extern "C" int papof_mosaic_blend_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
-                                         const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
-                                         const int* sources, const papof_tensor* matrices, const papof_tensor* gains, int mode,
-                                         const papof_tensor* out, const papof_tensor* count, void* stream) {
-    BlendArgs b{};
+// papof_mosaic_blend_tensor (A = BlendArgs) and papof_mosaic_projective_tensor (A = ProjArgs)
+template <typename A>
+static int mosaic_blend(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                        const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
+                        const papof_tensor* matrices, const papof_tensor* gains, int mode, const papof_tensor* out,
+                        const papof_tensor* count, void* stream) {
+    A b{};
     if (!mosaic_args_from(b, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                           matrices))
         return PAPOF_EINVAL;
@@ -534,17 +657,37 @@ extern "C" int papof_mosaic_blend_tensor(papof_handle* h, int n_frames, int heig
     if (gains && !described(gains, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1}, false)) return PAPOF_EINVAL;
     if (!mosaic_outputs(b, out, count)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
-    if (!gains && mode != PAPOF_MOSAIC_FEATHER)  // every gain 1: the instances papof_mosaic_tensor launches
-        return launch_mosaic(static_cast<hipStream_t>(stream), static_cast<const MosaicArgs&>(b), n_out, mode);
+    if constexpr (!kProjective<A>)
+        if (!gains && mode != PAPOF_MOSAIC_FEATHER)  // every gain 1: the instances papof_mosaic_tensor launches
+            return launch_mosaic(static_cast<hipStream_t>(stream), static_cast<const MosaicArgs&>(b), n_out, mode);
     if (gains) b.gains = *gains;
     return launch_mosaic(static_cast<hipStream_t>(stream), b, n_out, mode);
 }
 
-extern "C" int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
-                                           const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
-                                           const int* sources, const papof_tensor* matrices, int step, double bound,
-                                           long long* sums, long long* counts, void* stream) {
-    OverlapArgs a{};
+extern "C" int papof_mosaic_blend_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                         const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                         const int* sources, const papof_tensor* matrices, const papof_tensor* gains, int mode,
+                                         const papof_tensor* out, const papof_tensor* count, void* stream) {
+    return mosaic_blend<BlendArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                   matrices, gains, mode, out, count, stream);
+}
+
+extern "C" int papof_mosaic_projective_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                              const papof_tensor* frames, const papof_tensor* masks, int n_out, int n_src,
+                                              int out_height, int out_width, const int* sources, const papof_tensor* matrices,
+                                              const papof_tensor* gains, int mode, const papof_tensor* out,
+                                              const papof_tensor* count, void* stream) {
+    return mosaic_blend<ProjArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                  matrices, gains, mode, out, count, stream);
+}
+
+// papof_mosaic_overlap_tensor (A = MosaicArgs) and papof_mosaic_overlap_projective_tensor (A = ProjArgs)
+template <typename A>
+static int mosaic_overlap(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                          const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
+                          const papof_tensor* matrices, int step, double bound, long long* sums, long long* counts,
+                          void* stream) {
+    OverlapArgsOf<A> a{};
     if (!mosaic_args_from(a.m, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                           matrices))
         return PAPOF_EINVAL;
@@ -565,6 +708,23 @@ extern "C" int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int he
     if (n_src <= 16) return launch_overlap_as<16>(st, a, n_out);
     if (n_src <= 32) return launch_overlap_as<32>(st, a, n_out);
     return launch_overlap_as<64>(st, a, n_out);
+}
+
+extern "C" int papof_mosaic_overlap_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                           const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                           const int* sources, const papof_tensor* matrices, int step, double bound,
+                                           long long* sums, long long* counts, void* stream) {
+    return mosaic_overlap<MosaicArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                      matrices, step, bound, sums, counts, stream);
+}
+
+extern "C" int papof_mosaic_overlap_projective_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                                      const papof_tensor* frames, const papof_tensor* masks, int n_out, int n_src,
+                                                      int out_height, int out_width, const int* sources,
+                                                      const papof_tensor* matrices, int step, double bound, long long* sums,
+                                                      long long* counts, void* stream) {
+    return mosaic_overlap<ProjArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                    matrices, step, bound, sums, counts, stream);
 }
 
 // Every instance launch_mosaic dispatches to has a lane per slot (n_src <= 64 * TY), so phase 1's loop over the slots runs once.

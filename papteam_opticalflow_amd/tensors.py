@@ -115,6 +115,14 @@ and fades every frame out towards its border; `panorama(..., exposure=True)` cha
     sv = stabilize_video_full(frames, 5, layout="NHWC")            # sv.video, sv.valid, sv.filled
     pano = panorama(frames, 5, mode="feather", exposure=True, layout="NHWC")   # no steps at frame borders; pano.gains
 
+The homography model: a parallel family of calls over 3 x 3 matrices for a camera that rotates -- `global_homography`
+(include/papof.h: papof_homography_fit_tensor) fits one homography per pair, `warp_homography`, `mosaic_homography` and
+`mosaic_overlap_homography` are the warp, the mosaic (all four modes, gains) and the overlap statistics under the projective
+rule, `homography_transforms` makes the canvas and `panorama_homography` chains them.  On matrices whose last row is
+(0, 0, 1) they return the bytes of the affine calls.
+
+    pano = panorama_homography(frames, 5, mode="median", layout="NHWC")   # a Panorama with (T, 3, 3) matrices and motion
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -136,6 +144,7 @@ Splat = collections.namedtuple("Splat", "out coverage")
 METHODS = ("gather", "splat")
 ALPHA = 20.0  # splat_weights: the weight of a pixel is exp(-ALPHA * its photometric error)
 Motion = collections.namedtuple("Motion", "motion ok support")
+Homography = collections.namedtuple("Homography", "motion ok support")
 Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
 Filtered = collections.namedtuple("Filtered", "video support")
 Denoised = collections.namedtuple("Denoised", "video support flow_fw flow_bw timing")
@@ -874,13 +883,18 @@ def _check_fit(model, iters, scale):
     """(PAPOF_MOTION_* code, iterations, Cauchy scale) of global_motion's keywords -- TypeError / ValueError otherwise"""
     if model not in MODELS:
         raise ValueError("model must be one of %s, got %r" % (sorted(MODELS), model))
+    return (MODELS[model],) + _check_irls(iters, scale)
+
+
+def _check_irls(iters, scale):
+    """(iterations, Cauchy scale) of a robust fit's keywords -- TypeError / ValueError otherwise"""
     if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
         raise ValueError("iters must be an integer >= 1, got %r" % (iters,))
     if isinstance(scale, bool) or not isinstance(scale, (int, float)):
         raise TypeError("scale must be a number, got %r" % (scale,))
     if not (math.isfinite(scale) and scale > 0):
         raise ValueError("scale must be finite and > 0, got %r" % (scale,))
-    return MODELS[model], iters, float(scale)
+    return iters, float(scale)
 
 
 def _motion_fit(flow, code, occlusion, model, iters, scale):
@@ -919,21 +933,21 @@ def global_motion(flow, *, occlusion=None, model="affine", iters=5, scale=1.0):
     return _motion_fit(flow, code, occ, model, iters, scale)
 
 
-def _check_matrices(matrices, n, dev):
+def _check_matrices(matrices, n, dev, rows=2):
     torch = _torch()
     codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
     if not isinstance(matrices, torch.Tensor):
         raise TypeError("matrices must be a torch.Tensor, got %s" % type(matrices).__name__)
     if matrices.dtype not in codes:
         raise TypeError("matrices must be float32 or float64, got %s" % matrices.dtype)
-    if tuple(matrices.shape) != (n, 2, 3):
-        raise ValueError("matrices must be (B, 2, 3) = %s, got %s" % ((n, 2, 3), tuple(matrices.shape)))
+    if tuple(matrices.shape) != (n, rows, 3):
+        raise ValueError("matrices must be (B, %d, 3) = %s, got %s" % (rows, (n, rows, 3), tuple(matrices.shape)))
     if matrices.device != dev:
         raise ValueError("matrices are on %s, the frames on %s: both must be on one device" % (matrices.device, dev))
     return codes[matrices.dtype]
 
 
-def _warp(ts, descs, matrices, m_code, layout, out_dtype):
+def _warp(ts, descs, matrices, m_code, layout, out_dtype, call="papof_warp_affine_tensor"):
     torch = _torch()
     (B, H, W, C), _, _ = descs[0]
     dev = ts[0].device
@@ -942,7 +956,7 @@ def _warp(ts, descs, matrices, m_code, layout, out_dtype):
     d_in = _struct(ts[0], descs[0][1], descs[0][2])
     d_mat = _struct(matrices, (matrices.stride(0), matrices.stride(1), matrices.stride(2), 0), m_code)
     d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
-    _launch(dev, "papof_warp_affine_tensor", B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_out),
+    _launch(dev, call, B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_out),
             ctypes.byref(d_valid))
     return out, valid.view(torch.bool)
 
@@ -2308,16 +2322,16 @@ def _check_slots(mode, n, what="matrices have"):
         raise ValueError("%s %d sources per output, mode=\"median\" takes 1 .. %d" % (what, n, MAX_MEDIAN))
 
 
-def _check_mosaic_matrices(matrices, dev):
-    """(dtype code, n_out, N) of matrices (n_out, N, 2, 3) float32 / float64 on `dev` -- TypeError / ValueError otherwise"""
+def _check_mosaic_matrices(matrices, dev, rows=2):
+    """(dtype code, n_out, N) of matrices (n_out, N, rows, 3) float32 / float64 on `dev` -- TypeError / ValueError otherwise"""
     torch = _torch()
     codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
     if not isinstance(matrices, torch.Tensor):
         raise TypeError("matrices must be a torch.Tensor, got %s" % type(matrices).__name__)
     if matrices.dtype not in codes:
         raise TypeError("matrices must be float32 or float64, got %s" % matrices.dtype)
-    if matrices.dim() != 4 or tuple(matrices.shape[2:]) != (2, 3) or min(matrices.shape[:2]) < 1:
-        raise ValueError("matrices must be (n_out, N, 2, 3), got %s" % (tuple(matrices.shape),))
+    if matrices.dim() != 4 or tuple(matrices.shape[2:]) != (rows, 3) or min(matrices.shape[:2]) < 1:
+        raise ValueError("matrices must be (n_out, N, %d, 3), got %s" % (rows, tuple(matrices.shape)))
     if matrices.device != dev:
         raise ValueError("matrices are on %s, the frames on %s: both must be on one device" % (matrices.device, dev))
     return codes[matrices.dtype], int(matrices.shape[0]), int(matrices.shape[1])
@@ -2367,10 +2381,11 @@ def _check_gains(gains, n_out, N, dev):
     return gains
 
 
-def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None):
+def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None,
+            projective=False):
     """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
     count False: no count (None is returned for it; mode "first" then stops at the first live source).  With gains (checked)
-    or mode "feather": papof_mosaic_blend_tensor."""
+    or mode "feather": papof_mosaic_blend_tensor.  projective: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor."""
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
@@ -2381,7 +2396,7 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
     d_mask = _mask_struct(masks) if masks is not None else None
     d_cnt = _mask_struct(cnt) if count else None
-    if gains is None and mode != "feather":
+    if gains is None and mode != "feather" and not projective:
         _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
                 ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
         return out, cnt
@@ -2389,19 +2404,19 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     if gains is not None:
         d_gain = _struct(gains, (gains.stride(0), gains.stride(1), 0, 0),
                          capi.DTYPE_F32 if gains.dtype == torch.float32 else capi.DTYPE_F64)
-    _launch(dev, "papof_mosaic_blend_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), _ref(d_gain), MOSAIC_MODES[mode], ctypes.byref(d_out),
-            _ref(d_cnt))
+    _launch(dev, "papof_mosaic_projective_tensor" if projective else "papof_mosaic_blend_tensor", T, H, W, C,
+            ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat),
+            _ref(d_gain), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
     return out, cnt
 
 
-def _mosaic_inputs(ts, descs, sources, matrices, size, masks):
+def _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=2):
     """what mosaic and mosaic_overlap check alike behind their frames, in mosaic's order: (Hc, Wc, m_code, n_out, N, the host
     sources or None, masks)"""
     Hc, Wc = _check_canvas(size)
     (T, H, W, _), _, _ = descs[0]
     dev = ts[0].device
-    m_code, n_out, N = _check_mosaic_matrices(matrices, dev)
+    m_code, n_out, N = _check_mosaic_matrices(matrices, dev, rows)
     src = _check_sources(sources, n_out, N, T)
     m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
     return Hc, Wc, m_code, n_out, N, src, m
@@ -2450,8 +2465,8 @@ def _check_overlap_slots(n, what="matrices have"):
         raise ValueError("%s %d sources per output, the overlap statistics take 1 .. %d" % (what, n, MAX_OVERLAP))
 
 
-def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound):
-    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's)"""
+def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound, projective=False):
+    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's); projective: papof_mosaic_overlap_projective_tensor"""
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
@@ -2461,9 +2476,9 @@ def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound
     d_in = _struct(ts[0], strides, code)
     d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
     d_mask = _mask_struct(masks) if masks is not None else None
-    _launch(dev, "papof_mosaic_overlap_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-            ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), step, ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()),
-            ctypes.c_void_p(counts.data_ptr()))
+    _launch(dev, "papof_mosaic_overlap_projective_tensor" if projective else "papof_mosaic_overlap_tensor", T, H, W, C,
+            ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), step,
+            ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
     return Overlap(sums, counts, bound)
 
 
@@ -2659,9 +2674,9 @@ def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0
     of out_dtype (by default the frames'), count (Hc, Wc) uint8, matrices (T, 2, 3) float64 -- canvas to frame t, of every
     frame --, origin (x0, y0): the canvas pixel (0, 0) in the reference frame's coordinates, motion (T - 1, 2, 3), ok
     (T - 1,) bool, flow (T - 1, 2, H, W) float64, timing of the flow call, gains: None, or with exposure=True the float64
-    gain of every deposited frame).  The model is affine: there is no projective warp and no bundle adjustment; the
-    exposure is one gain per frame, and feathering ghosts where the registration is off (README).  Every argument error
-    raises before anything is launched."""
+    gain of every deposited frame).  The model is affine (panorama_homography is the projective chain, for a camera that
+    rotates) and there is no bundle adjustment; the exposure is one gain per frame, and feathering ghosts where the
+    registration is off (README).  Every argument error raises before anything is launched."""
     ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     code, iters, scale = _check_fit(model, iters, scale)
     (T, H, W, C), _, _ = descs[0]
@@ -2720,3 +2735,200 @@ def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW"
                      "first", layout, torch.uint8)
     valid = own > 0
     return StabilizedFull(video, valid, (count > 0) & ~valid, M, m.motion, m.ok, flow, timing)
+
+
+# ---- the homography model: the calls above over 3 x 3 matrices
+def _homography_fit(flow, code, occlusion, iters, scale):
+    torch = _torch()
+    B, _, H, W = (int(x) for x in flow.shape)
+    dev = flow.device
+    motion = torch.empty((B, 3, 3), dtype=torch.float64, device=dev)
+    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
+    support = torch.empty((B,), dtype=torch.float64, device=dev)
+    d_flow = _flow_struct(flow, code)
+    d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
+    d_m = _struct(motion, (motion.stride(0), motion.stride(1), motion.stride(2), 0), capi.DTYPE_F64)
+    d_ok = _struct(ok, (ok.stride(0), 0, 0, 0), capi.DTYPE_U8)
+    d_s = _struct(support, (support.stride(0), 0, 0, 0), capi.DTYPE_F64)
+    _launch(dev, "papof_homography_fit_tensor", B, H, W, ctypes.byref(d_flow), _ref(d_occ), iters, scale, ctypes.byref(d_m),
+            ctypes.byref(d_ok), ctypes.byref(d_s),
+            workspace=("papof_homography_workspace", (B, H, W), "a %d x %d flow is too large for global_homography" % (H, W)))
+    return Homography(motion, ok.view(torch.bool), support)
+
+
+def global_homography(flow, *, occlusion=None, iters=5, scale=1.0):
+    """global_motion with a homography as the model -- the motion of the image under a camera that rotates: flow, occlusion,
+    iters and scale as there.  Every valid pixel contributes its two rows of the direct linear transform in normalised
+    coordinates, weighted by the Cauchy weight of its pixel distance to the previous iteration's homography over the square
+    of that homography's denominator (so that the rows measure pixels); an 8 x 8 solve per iteration.  Returns
+    Homography(motion (B, 3, 3) float64 with motion[:, 2, 2] == 1 -- (x, y, 1) of frame i to frame i + 1, up to the third
+    coordinate --, ok (B,) bool -- False where no fit was possible (motion is the identity) --, support (B,) float64: the
+    last iteration's sum of Cauchy weights over H * W).  A fit whose horizon would cross the image fails.  include/papof.h
+    (papof_homography_fit_tensor) states the rule exactly; bitwise reproducible.  Enqueued on the current stream; returns
+    without waiting."""
+    iters, scale = _check_irls(iters, scale)
+    code = _check_flow("flow", flow)
+    occ = _check_occlusion(occlusion, tuple(flow.shape), flow.device)
+    if not _on_gpu(flow):
+        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
+    return _homography_fit(flow, code, occ, iters, scale)
+
+
+def warp_homography(frames, matrices, *, layout="NCHW", out_dtype=None):
+    """warp_affine through 3 x 3 matrices: matrices (B, 3, 3) float32 / float64 on the frames' device.  Output pixel (x, y) of
+    frame i is frames[i] sampled at (Nx / D, Ny / D), (Nx, Ny, D) = M (x, y, 1), or 0 where D is not > 0 (behind the
+    horizon) or the point is NaN or outside the frame.  Returns (frames_out, valid (B, H, W) bool) as warp_affine; on
+    matrices whose last row is (0, 0, 1), its bytes.  include/papof.h (papof_warp_projective_tensor) states it exactly.
+    Enqueued on the current stream; returns without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    m_code = _check_matrices(matrices, descs[0][0][0], ts[0].device, rows=3)
+    return _warp(ts, descs, matrices, m_code, layout, out_dtype, "papof_warp_projective_tensor")
+
+
+def mosaic_homography(frames, sources, matrices, size, *, mode="median", masks=None, layout="NCHW", out_dtype=None,
+                      gains=None):
+    """mosaic through 3 x 3 matrices: matrices (n_out, N, 3, 3) float32 / float64; every other argument, the four modes, the
+    limits (255 sources, 64 for the median) and the result are mosaic's.  Source k is live at output pixel (x, y) where,
+    with (Nx, Ny, D) = matrices[o, k] (x, y, 1), D > 0 and (Nx / D, Ny / D) lies inside its frame (and no tap is masked);
+    from that point on everything is mosaic's rule.  On matrices whose last row is (0, 0, 1), mosaic's bytes and count.
+    include/papof.h (papof_mosaic_projective_tensor) states it exactly; bitwise reproducible.  Enqueued on the current
+    stream; returns without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=3)
+    _check_slots(mode, N)
+    dev = ts[0].device
+    gains = _check_gains(gains, n_out, N, dev)
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains, projective=True))
+
+
+def mosaic_overlap_homography(frames, sources, matrices, size, *, masks=None, step=2, bound=1.0, layout="NCHW"):
+    """mosaic_overlap through 3 x 3 matrices (n_out, N, 3, 3), liveness as mosaic_homography's: the Overlap that
+    exposure_gains takes.  include/papof.h (papof_mosaic_overlap_projective_tensor).  Enqueued on the current stream; returns
+    without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=3)
+    _check_overlap_slots(N)
+    _int_at_least("step", step, 1)
+    bound = _positive("bound", bound)
+    dev = ts[0].device
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound, projective=True)
+
+
+def _pair_homographies(motion):
+    """the (T - 1, 3, 3) float64 numpy array (pairs of a Homography with ok False: the identity) and the device of `motion`, a
+    (T - 1, 3, 3) tensor or a Homography -- TypeError / ValueError otherwise"""
+    import numpy as np
+    ok = None
+    if isinstance(motion, Homography):
+        motion, ok = motion.motion, motion.ok
+    if not isinstance(motion, _torch().Tensor):
+        raise TypeError("motion must be a torch.Tensor or a Homography, got %s" % type(motion).__name__)
+    if motion.dim() != 3 or tuple(motion.shape[1:]) != (3, 3) or motion.shape[0] < 1:
+        raise ValueError("motion must be (T - 1, 3, 3) with T >= 2, got shape %s" % (tuple(motion.shape),))
+    A = motion.detach().to("cpu", _torch().float64).numpy()
+    if ok is not None:
+        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(3))
+    return A, motion.device
+
+
+def homography_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PIXELS):
+    """mosaic_transforms for pair homographies: motion a (T - 1, 3, 3) tensor (global_homography's, any device) or a
+    Homography (pairs with ok False enter as the identity), size = (H, W) of the frames.  In float64 on the host, the chain
+    built as there -- frame t to the reference frame as the product of the pair motions in between, each product divided by
+    its [2][2], so the reference frame keeps its integer corners; a pair motion or a product whose [2][2] is not > 0 is
+    refused, since dividing by it would turn a frame behind the horizon into one in front of it --; the corners of every frame are projected into the
+    reference frame, (x0, y0) is the floor of their minima less `margin` and the canvas reaches the ceiling of their maxima
+    plus `margin`; canvas pixel q samples frame t at matrix_t q (projectively), matrix_t = (frame t <- reference)
+    translate(x0, y0) over its [2][2].  Returns (matrices (1, T, 3, 3) float64 on the motion's device -- mosaic_homography's,
+    for sources=None --, (Hc, Wc), (x0, y0)).  ValueError when a corner of a frame has a denominator that is not > 0 in the
+    reference frame (the frame crosses the horizon: a pan too wide for one plane), when the bounds are not finite or when
+    Hc * Wc > max_pixels."""
+    import numpy as np
+    torch = _torch()
+    A, dev = _pair_homographies(motion)
+    H, W = _check_canvas(size)
+    T = A.shape[0] + 1
+    ref = _check_ref(ref, T)
+    _int_at_least("margin", margin, 0)
+    _int_at_least("max_pixels", max_pixels, 1)
+    corners = np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
+
+    def unit(m):
+        if not m[2, 2] > 0:  # (a NaN included) the sign of every denominator would flip
+            raise ValueError("a motion along the chain has a [2][2] that is not > 0: it sends the image centre's "
+                             "neighbourhood behind its horizon")
+        return m / m[2, 2]
+
+    to_ref = [np.eye(3)] * T
+    with np.errstate(all="ignore"):
+        try:
+            for t in range(ref - 1, -1, -1):
+                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
+            for t in range(ref + 1, T):
+                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
+            pts = np.stack([m @ corners for m in to_ref])  # (T, 3, 4)
+            from_ref = [np.linalg.inv(m) for m in to_ref]
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular: no canvas") from None
+        if not (np.isfinite(pts).all() and np.isfinite(np.array(from_ref)).all()):
+            raise ValueError("the bounds of the canvas are not finite")
+        behind = ~(pts[:, 2] > 0).all(1)
+        if behind.any():
+            raise ValueError("frame %d crosses the horizon of the reference frame: the pan is too wide for one plane"
+                             % int(np.argmax(behind)))
+        pts = pts[:, :2] / pts[:, 2:]
+        if not np.isfinite(pts).all():
+            raise ValueError("the bounds of the canvas are not finite")
+        x0, y0 = math.floor(pts[:, 0].min()) - margin, math.floor(pts[:, 1].min()) - margin
+        Wc, Hc = math.ceil(pts[:, 0].max()) + margin - x0 + 1, math.ceil(pts[:, 1].max()) + margin - y0 + 1
+        if Hc * Wc > max_pixels:
+            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+        shift = np.array([[1.0, 0.0, x0], [0.0, 1.0, y0], [0.0, 0.0, 1.0]])
+        M = np.stack([unit(m @ shift) for m in from_ref])[None]
+    if not np.isfinite(M).all():
+        raise ValueError("the bounds of the canvas are not finite")
+    return torch.from_numpy(M).to(dev), (Hc, Wc), (x0, y0)
+
+
+def panorama_homography(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0, masks=None, iters=5, scale=1.0,
+                        layout="NCHW", out_dtype=None, exposure=False, **solver):
+    """panorama with the homography model, for a camera that rotates: flow_video, global_homography on the flows (iters,
+    scale), homography_transforms (ref, margin; the only wait) and ONE mosaic_homography of the frames 0, step, 2 step, ...;
+    exposure=True: mosaic_overlap_homography (step 2, bound 1.0) and exposure_gains first, as panorama.  Every argument, the
+    limits and the errors are panorama's (there is no `model`).  Returns Panorama with matrices (T, 3, 3) float64 -- canvas to
+    frame t, projectively -- and motion (T - 1, 3, 3).  The canvas is one plane: a pan that nears 90 degrees from the
+    reference frame is refused by homography_transforms; there is no bundle adjustment, no lens distortion and no parallax
+    (README).  Every argument error raises before anything is launched."""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    iters, scale = _check_irls(iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    ref = _check_ref(ref, T)
+    _int_at_least("step", step, 1)
+    _int_at_least("margin", margin, 0)
+    dev = ts[0].device
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    picked = list(range(0, T, step))
+    if not isinstance(exposure, bool):
+        raise TypeError("exposure must be True or False, got %r" % (exposure,))
+    if exposure and len(picked) > MAX_OVERLAP:
+        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
+                         % (step, len(picked), MAX_OVERLAP))
+    _check_slots(mode, len(picked), "step = %d deposits" % step)
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
+    M, (Hc, Wc), origin = homography_transforms(mo, (H, W), ref=ref, margin=margin)
+    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
+    gains = None
+    if exposure:
+        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, projective=True)
+        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
+    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
+                           projective=True)
+    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0])
