@@ -1327,6 +1327,46 @@ int papof_mosaic_overlap_projective_tensor(papof_handle* h, int n_frames, int he
                                            int out_height, int out_width, const int* sources, const papof_tensor* matrices,
                                            int step, double bound, long long* sums, long long* counts, void* stream);
 
+/* Wide panoramas: the mosaic and the overlap call on a canvas whose pixels are DIRECTIONS, not points of one plane -- a
+ * cylinder or a sphere around a camera that rotates by more than a plane can hold.  A parallel family: the affine and the
+ * projective calls are unchanged.
+ *
+ * RAY SAMPLING (the rule of the two calls below).  The canvas is given by two tables, float32 (widened exactly) or float64:
+ * cols (column, {u, w}), out_width rows, and rows (row, {s, c}), out_height rows (strides: stride[0] between entries,
+ * stride[1] between the two numbers of one).  m: a 3 x 3 matrix as above.  At output pixel (x, r), in fp64 without fused
+ * multiply-adds:
+ *     dx = u_x * c_r;  dy = s_r;  dz = w_x * c_r                                  (the pixel's ray)
+ *     D = (m20 * dx + m21 * dy) + m22 * dz;  Nx = (m00 * dx + m01 * dy) + m02 * dz;  Ny = (m10 * dx + m11 * dy) + m12 * dz
+ *     X = Nx / D;  Y = Ny / D                      (two divisions, not a reciprocal and two products)
+ *     live / inside iff D > 0 and 0 <= X <= W - 1 and 0 <= Y <= H - 1 (every comparison false for a NaN)
+ * and from (X, Y) on everything is the affine call's rule: the taps, the tap-wise mask rule, the gains, the feather weight,
+ * the modes, the count and the sampler.  The device evaluates no sine: the tables are the caller's (a cylinder is cols =
+ * (sin t_x, cos t_x), rows = (h_r, 1); a sphere is rows = (sin p_r, cos p_r)).  The plane's tables cols = (x, 1), rows = (r, 1)
+ * give dx = x, dy = r, dz = 1.0 and m22 * 1.0 = m22: the ray calls on them return the BYTES of the projective calls.
+ *
+ * papof_mosaic_ray_tensor (mosaic.hip: k_mosaic over RayArgs): papof_mosaic_projective_tensor with the two tables after the
+ * matrices.  papof_mosaic_overlap_ray_tensor: the overlap call likewise (the tables are indexed by the canvas pixel, every
+ * step-th of them sampled).  Arguments, limits (PAPOF_MOSAIC_MAX_SOURCES, _MAX_MEDIAN, _MAX_OVERLAP), PAPOF_MOSAIC_CULL and
+ * PAPOF_EINVAL as there; a table that is NULL, has no data, another dtype or a negative stride is PAPOF_EINVAL before any
+ * launch.  Tile culling, which changes no byte: the block reduces u and w over the tile's columns and s and c over its rows to
+ * their minima and maxima (a NaN entry makes them NaN); [dx_min, dx_max] and [dz_min, dz_max] are the min and max of the four
+ * endpoint products, [dy_min, dy_max] = [s_min, s_max]; the bounds of D, Nx and Ny are their expressions evaluated with, per
+ * term, the smaller (larger) of the two endpoint products m * d_min, m * d_max.  Every step is a correctly rounded monotone
+ * operation, so these bound every pixel's value that is not NaN.  From there the projective rule: a slot is dropped when an
+ * entry of its first two rows is not finite, when D_max <= 0, or when D_min > 0 and the interval [min(Nx_min / D_min, Nx_min /
+ * D_max), max(Nx_max / D_min, Nx_max / D_max)], widened by a pixel, misses [0, W - 1] (the same for Y and H).  A NaN bound or
+ * quotient and a D of mixed sign prove nothing: the slot stays.  mosaic.hip has the proof. */
+int papof_mosaic_ray_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                            const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
+                            const papof_tensor* matrices, const papof_tensor* cols, const papof_tensor* rows,
+                            const papof_tensor* gains, int mode, const papof_tensor* out, const papof_tensor* count,
+                            void* stream);
+int papof_mosaic_overlap_ray_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                    const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                    const int* sources, const papof_tensor* matrices, const papof_tensor* cols,
+                                    const papof_tensor* rows, int step, double bound, long long* sums, long long* counts,
+                                    void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -74,6 +74,7 @@ SYMBOLS = [
     "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", "papof_sor_tiny_shape",
     "papof_homography_workspace", "papof_homography_fit_tensor", "papof_warp_projective_tensor",
     "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor",
+    "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor",
 ]
 
 
@@ -245,6 +246,12 @@ def load():
     L.papof_mosaic_projective_tensor.restype = c_int
     L.papof_mosaic_overlap_projective_tensor.argtypes = L.papof_mosaic_overlap_tensor.argtypes
     L.papof_mosaic_overlap_projective_tensor.restype = c_int
+    # the projective twins' arguments with the two tables after the matrices (index 12)
+    L.papof_mosaic_ray_tensor.argtypes = L.papof_mosaic_blend_tensor.argtypes[:13] + [_T, _T] + L.papof_mosaic_blend_tensor.argtypes[13:]
+    L.papof_mosaic_ray_tensor.restype = c_int
+    L.papof_mosaic_overlap_ray_tensor.argtypes = (L.papof_mosaic_overlap_tensor.argtypes[:13] + [_T, _T] +
+                                                  L.papof_mosaic_overlap_tensor.argtypes[13:])
+    L.papof_mosaic_overlap_ray_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

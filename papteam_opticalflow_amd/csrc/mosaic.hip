@@ -55,6 +55,33 @@
 //   extreme numerator with the extreme denominator, which need not meet at one pixel: DESIGN.md section 27 has the share of
 //   slots it keeps.
 //
+// papof_mosaic_ray_tensor and papof_mosaic_overlap_ray_tensor are the same two kernels over RayArgs: the canvas pixel is a
+// direction d = (u_x c_r, s_r, w_x c_r) read from two tables (include/papof.h: ray sampling), and the 3 x 3 matrix is applied
+// to it: (D, Nx, Ny) = rows 2, 0, 1 of m times d, each (a dx + b dy) + c dz.  Chosen at compile time as ProjArgs is; the ray
+// is computed once per pixel, outside the walk.  The instances over MosaicArgs, BlendArgs and ProjArgs are instruction for
+// instruction what they were.
+//   Culling under the ray rule (ray_box, ray_keep).  The corners of a tile bound nothing here (sin is not monotone over 64
+//   columns), so the block bounds the tile's rays by intervals, from the tables themselves: lane x of a wave reads (u, w) of
+//   its column and a butterfly of min and max reduces them over the tile's columns; (s, c) are reduced over its <= 4 rows.
+//   These min and max hand a NaN on (nan_min, nan_max; fmin and fmax would drop it).  Only pixels whose values are numbers
+//   matter: a live pixel has D > 0 and X, Y inside, so none of dx, dz, the nine products, D, Nx, Ny is NaN there (a NaN
+//   operand makes every later step NaN).  Call such a pixel clean.
+//     (a) dx = fl(u c) with u in [u_lo, u_hi], c in [c_lo, c_hi].  For fixed c, fl(u c) is monotone in u (rounding is
+//         monotone, overflow to +-inf included), and for fixed u monotone in c; so a clean pixel's dx lies between the min and
+//         the max of the four endpoint products -- unless one of those is NaN (0 * inf: an infinite table entry against a
+//         zero one), which makes the bound NaN.  The same for dz; dy = s needs no product.
+//     (b) A term fl(m d) with d in [d_lo, d_hi] is monotone in d, so a clean pixel's term lies between the smaller and the
+//         larger of fl(m d_lo), fl(m d_hi) -- or one of them is NaN (0 * inf again: an infinite entry of the last row against
+//         a bound that is 0, or a zero entry against an infinite bound) and so is the bound.
+//     (c) fl(fl(t0 + t1) + t2) is monotone in each term; the sum of the three lower (upper) term bounds is a lower (upper)
+//         bound of a clean pixel's D, Nx, Ny, or NaN (inf - inf: the lower bounds hold -inf and +inf at once).
+//   So when none of the six bounds is NaN they bound D, Nx and Ny at every clean pixel, and rules (1) to (5) above apply word
+//   for word with them in place of the corner extremes: (1) an entry of the first two rows that is not finite makes Nx or Ny
+//   +-inf or NaN at every pixel (m d is +-inf, or NaN where d = 0); (2) a NaN bound proves nothing: kept; (3), (4), (5) as
+//   there.  The caller is never trusted for the ranges: they are read from the very entries the pixels read.
+//   PAPOF_MOSAIC_CULL=0 skips the reduction and the test.  The intervals ignore that u and w (sin and cos of one angle)
+//   move together, so they are looser than the projective corner test: DESIGN.md section 28 has the share of slots kept.
+//
 // k_mosaic_overlap (papof_mosaic_overlap_tensor).  A block is a 64 x 2 tile of SAMPLED pixels (every step-th column and
 // row).  Phases 1 and 2 as above, each lane writing the fixed-point luminance q of its live slots to LDS [slot][pixel] and
 // the 64-bit set of them.  Then the roles turn: lane j is source j (64 / NS pixels side by side where NS < 64), wave w owns
@@ -97,6 +124,14 @@ struct ProjArgs : BlendArgs {};  // mat is (out, k, row, column): 3 x 3, the pro
 
 template <typename A>
 constexpr bool kProjective = std::is_same<A, ProjArgs>::value;
+
+struct RayArgs : BlendArgs {  // mat is 3 x 3 as ProjArgs', applied to the ray of the pixel: the ray rule of include/papof.h
+    papof_tensor cols;        // float32 / float64 (column, {u, w})
+    papof_tensor rows;        // float32 / float64 (row, {s, c})
+};
+
+template <typename A>
+constexpr bool kRay = std::is_same<A, RayArgs>::value;
 
 __device__ __forceinline__ double slot_gain(const MosaicArgs&, long long, int) { return 1.0; }
 __device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int k) {
@@ -161,6 +196,116 @@ __device__ __forceinline__ bool projective_point(const MosaicArgs& a, long long 
     return D > 0;
 }
 
+// ---- the ray rule
+// min and max that hand a NaN on (fmin and fmax drop it)
+__device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+
+// A value that every active lane of the wave holds alike, moved to scalar registers
+__device__ __forceinline__ double wave_uniform(double v) {
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// The ray of canvas pixel (x, r): d = (u_x * c_r, s_r, w_x * c_r).  A wave is one row of the tile (blocks are 64 x TY), so its
+// lanes share r: s_r and c_r are held once per wave, and d[1] costs the walk no vector registers.
+__device__ __forceinline__ void ray_of(const RayArgs& a, long long x, long long r, double d[3]) {
+    const long long oc = x * a.cols.stride[0], orow = r * a.rows.stride[0];
+    const double u = load_flow(a.cols, oc), w = load_flow(a.cols, oc + a.cols.stride[1]);
+    const double s = wave_uniform(load_flow(a.rows, orow)), c = wave_uniform(load_flow(a.rows, orow + a.rows.stride[1]));
+    d[0] = u * c;
+    d[1] = s;
+    d[2] = w * c;
+}
+
+// The bounds lo[j] <= d[j] <= hi[j] of the rays of a tile, read from the tables by the block itself: the lanes of a wave hold
+// the tile's columns (`x` this lane's, clamped into the canvas by the caller), the tile's rows are ra, ra + dr, ..., rb.  Every
+// wave of the block computes the same twelve numbers; all 64 lanes of the wave must be here.  A NaN table entry makes its
+// bounds NaN (the header comment has the proof of what these bound).
+__device__ __forceinline__ void ray_box(const RayArgs& a, long long x, long long ra, long long rb, long long dr, double lo[3],
+                                        double hi[3]) {
+    const long long oc = x * a.cols.stride[0];
+    double ulo = load_flow(a.cols, oc), wlo = load_flow(a.cols, oc + a.cols.stride[1]);
+    double uhi = ulo, whi = wlo;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        ulo = nan_min(ulo, __shfl_xor(ulo, d));
+        uhi = nan_max(uhi, __shfl_xor(uhi, d));
+        wlo = nan_min(wlo, __shfl_xor(wlo, d));
+        whi = nan_max(whi, __shfl_xor(whi, d));
+    }
+    double slo = load_flow(a.rows, ra * a.rows.stride[0]), clo = load_flow(a.rows, ra * a.rows.stride[0] + a.rows.stride[1]);
+    double shi = slo, chi = clo;
+    for (long long r = ra + dr; r <= rb; r += dr) {
+        const double s = load_flow(a.rows, r * a.rows.stride[0]), c = load_flow(a.rows, r * a.rows.stride[0] + a.rows.stride[1]);
+        slo = nan_min(slo, s);
+        shi = nan_max(shi, s);
+        clo = nan_min(clo, c);
+        chi = nan_max(chi, c);
+    }
+    const double x0 = ulo * clo, x1 = ulo * chi, x2 = uhi * clo, x3 = uhi * chi;
+    const double z0 = wlo * clo, z1 = wlo * chi, z2 = whi * clo, z3 = whi * chi;
+    // (the same in every lane after the butterfly: held in scalar registers, ray_keep's products take them from there)
+    lo[0] = wave_uniform(nan_min(nan_min(x0, x1), nan_min(x2, x3)));
+    hi[0] = wave_uniform(nan_max(nan_max(x0, x1), nan_max(x2, x3)));
+    lo[1] = wave_uniform(slo);
+    hi[1] = wave_uniform(shi);
+    lo[2] = wave_uniform(nan_min(nan_min(z0, z1), nan_min(z2, z3)));
+    hi[2] = wave_uniform(nan_max(nan_max(z0, z1), nan_max(z2, z3)));
+}
+
+// Phase 1 under the ray rule: false where the slot of the 3 x 3 matrix at mb is live at no pixel of the tile whose rays lie in
+// [lo, hi] (ray_box; the header comment has the proof)
+__device__ __forceinline__ bool ray_keep(const MosaicArgs& a, long long mb, const double lo[3], const double hi[3]) {
+    double m[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
+    bool finite = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
+    if (!finite) return false;  // Nx or Ny is +-inf or NaN at every pixel, and so is its quotient
+    double blo[3], bhi[3];      // the bounds of D, Nx, Ny
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        const int row = 3 * ((q + 2) % 3);
+        double l[3], h[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const double p0 = m[row + j] * lo[j], p1 = m[row + j] * hi[j];
+            l[j] = nan_min(p0, p1);
+            h[j] = nan_max(p0, p1);
+        }
+        blo[q] = (l[0] + l[1]) + l[2];
+        bhi[q] = (h[0] + h[1]) + h[2];
+    }
+    bool nan = false;
+#pragma unroll
+    for (int q = 0; q < 3; q++) nan = nan || blo[q] != blo[q] || bhi[q] != bhi[q];
+    if (nan) return true;               // proves nothing
+    if (!(bhi[0] > 0)) return false;    // D > 0 at no pixel
+    if (!(blo[0] > 0)) return true;     // the horizon may cross the tile
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    // (a quotient inf / inf is NaN: every comparison is false, the source stays)
+    const bool missx = (bhi[1] / blo[0] < -1.0 && bhi[1] / bhi[0] < -1.0) || (blo[1] / blo[0] > W1 + 1.0 && blo[1] / bhi[0] > W1 + 1.0);
+    const bool missy = (bhi[2] / blo[0] < -1.0 && bhi[2] / bhi[0] < -1.0) || (blo[2] / blo[0] > H1 + 1.0 && blo[2] / bhi[0] > H1 + 1.0);
+    return !missx && !missy;
+}
+
+// The point of the ray d under the 3 x 3 matrix at mb: false where D is not > 0 (a NaN included)
+__device__ __forceinline__ bool ray_point(const MosaicArgs& a, long long mb, const double d[3], double& X, double& Y) {
+    double m[9];
+#pragma unroll
+    for (int rr = 0; rr < 3; rr++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
+    const double D = (m[6] * d[0] + m[7] * d[1]) + m[8] * d[2];
+    X = ((m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]) / D;
+    Y = ((m[3] * d[0] + m[4] * d[1]) + m[5] * d[2]) / D;
+    return D > 0;
+}
+
 // k_mosaic_overlap's phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its
 // matrices) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order; returns
 // their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
@@ -168,7 +313,8 @@ __device__ __forceinline__ bool projective_point(const MosaicArgs& a, long long 
 // instances another register allocation, and the instances papof_mosaic_tensor launches are to stay the code they were.)
 template <int TY, typename A>
 __device__ __forceinline__ int cull_slots(const A& a, const int* src, long long mo, double xa, double xb, double ra,
-                                          double rb, unsigned short* list, int* wcount) {
+                                          double rb, unsigned short* list, int* wcount, const double* lo = nullptr,
+                                          const double* hi = nullptr) {  // (lo, hi: RayArgs' ray_box, instead of the rectangle)
     constexpr int NT = kMosTX * TY;
     const int tid = threadIdx.y * kMosTX + threadIdx.x;
     const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
@@ -178,6 +324,8 @@ __device__ __forceinline__ int cull_slots(const A& a, const int* src, long long 
         bool keep = k < a.n_src && src[k] >= 0;
         if constexpr (kProjective<A>) {
             if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
+        } else if constexpr (kRay<A>) {
+            if (keep && a.cull) keep = ray_keep(a, mo + k * a.mat.stride[1], lo, hi);
         } else if (keep && a.cull) {
             double m[6];
             const long long mb = mo + k * a.mat.stride[1];
@@ -261,11 +409,30 @@ __device__ __forceinline__ bool slot_live(const ProjArgs& a, long long s, long l
     return true;
 }
 
+// slot_live under the ray rule (k_mosaic_overlap over RayArgs): d the pixel's ray
+__device__ __forceinline__ bool slot_live(const RayArgs& a, long long s, long long mb, const double d[3], double& X, double& Y,
+                                          Bilinear& t) {
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    if (!ray_point(a, mb, d, X, Y)) return false;
+    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
+    t = taps_at(X, Y, a.H, a.W);
+    if (a.mask.data) {
+        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
+        bool masked = false;
+        const long long b = s * a.mask.stride[0];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
+        if (masked) return false;
+    }
+    return true;
+}
+
 // A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER; or ProjArgs:
-// BlendArgs under the projective rule
+// BlendArgs under the projective rule; or RayArgs: BlendArgs under the ray rule
 template <int FD, int MODE, int CAP, int TY, typename A>
 __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile0, long long out0) {
-    constexpr bool BLEND = std::is_same<A, BlendArgs>::value || kProjective<A>;
+    constexpr bool BLEND = std::is_same<A, BlendArgs>::value || kProjective<A> || kRay<A>;
     static_assert(BLEND || MODE != PAPOF_MOSAIC_FEATHER, "k_mosaic: FEATHER is a blend mode");
     constexpr int NT = kMosTX * TY;
     constexpr int CH = MODE == PAPOF_MOSAIC_MEDIAN ? 1 : 4;  // channels per walk of the list
@@ -289,11 +456,17 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
     {
         const double xa = (double)x0, xb = (double)std::min(x0 + kMosTX - 1, a.Wc - 1);
         const double ra = (double)r0, rb = (double)std::min(r0 + TY - 1, (long long)a.Hc - 1);
+        double lo[3], hi[3];  // RayArgs: the bounds of the tile's rays
+        if constexpr (kRay<A>)
+            if (a.cull)
+                ray_box(a, std::min(x0 + (int)threadIdx.x, a.Wc - 1), r0, std::min(r0 + TY - 1, (long long)a.Hc - 1), 1, lo, hi);
         for (int base = 0; base < a.n_src; base += NT) {
             const int k = base + tid;
             bool keep = k < a.n_src && src[k] >= 0;
             if constexpr (kProjective<A>) {
                 if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
+            } else if constexpr (kRay<A>) {
+                if (keep && a.cull) keep = ray_keep(a, mo + k * a.mat.stride[1], lo, hi);
             } else if (keep && a.cull) {
                 double m[6];
                 const long long mb = mo + k * a.mat.stride[1];
@@ -338,6 +511,8 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
     const long long outp = o * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
     const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
     const bool all_sources = a.count.data != nullptr || MODE != PAPOF_MOSAIC_FIRST;
+    double ray[3];  // RayArgs: the pixel's ray, once for every source and channel
+    if constexpr (kRay<A>) ray_of(a, x, r, ray);
     for (int c0 = 0; c0 < a.C; c0 += CH) {
         double acc[CH];
 #pragma unroll
@@ -351,6 +526,8 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
             double X, Y;
             if constexpr (kProjective<A>) {
                 if (!projective_point(a, mb, xd, rd, X, Y)) continue;
+            } else if constexpr (kRay<A>) {
+                if (!ray_point(a, mb, ray, X, Y)) continue;
             } else {
                 double m[6];
 #pragma unroll
@@ -494,9 +671,14 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
     const long long step = args.step;
 
     // ---- 1. the sources that can reach the tile's pixels (all of them lie in the rectangle of its corners)
+    double lo[3], hi[3];  // RayArgs: the bounds of the rays of the tile's sampled pixels
+    if constexpr (kRay<A>)
+        if (a.cull)
+            ray_box(a, std::min(sx0 + (int)threadIdx.x, args.nsx - 1) * step, sr0 * step,
+                    std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step, step, lo, hi);
     const int total = cull_slots<kOvTY>(a, src, mo, (double)(sx0 * step),
                                         (double)(std::min(sx0 + kMosTX - 1, args.nsx - 1) * step), (double)(sr0 * step),
-                                        (double)(std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step), list, wcount);
+                                        (double)(std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step), list, wcount, lo, hi);
 
     // ---- 2. the walk: the luminance of every live slot, in fixed point
     const int sx = sx0 + (int)threadIdx.x;
@@ -504,12 +686,17 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
     unsigned long long mine = 0;
     if (sx < args.nsx && sr < args.nsr) {
         const double xd = (double)(sx * step), rd = (double)(sr * step);
+        double ray[3];
+        if constexpr (kRay<A>) ray_of(a, sx * step, sr * step, ray);
         for (int i = 0; i < total; i++) {
             const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
             const long long s = src[k];
             double X, Y;
             Bilinear t;
-            if (!slot_live(a, s, mo + k * a.mat.stride[1], xd, rd, X, Y, t)) continue;
+            if constexpr (kRay<A>) {
+                if (!slot_live(a, s, mo + k * a.mat.stride[1], ray, X, Y, t)) continue;
+            } else if (!slot_live(a, s, mo + k * a.mat.stride[1], xd, rd, X, Y, t))
+                continue;
             const long long base = s * a.fr.stride[0];
             double y = 0.0;
             for (int ch = 0; ch < a.C; ch++) y = y + sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], t, lut);
@@ -642,13 +829,26 @@ extern "C" int papof_mosaic_tensor(papof_handle* h, int n_frames, int height, in
     return launch_mosaic(static_cast<hipStream_t>(stream), a, n_out, mode);
 }
 
-// papof_mosaic_blend_tensor (A = BlendArgs) and papof_mosaic_projective_tensor (A = ProjArgs)
+// The tables of the ray rule, checked and gathered
+static bool ray_tables(RayArgs& a, const papof_tensor* cols, const papof_tensor* rows) {
+    if (!described(cols, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1}, false)) return false;
+    if (!described(rows, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1}, false)) return false;
+    a.cols = *cols;
+    a.rows = *rows;
+    return true;
+}
+
+// papof_mosaic_blend_tensor (A = BlendArgs), papof_mosaic_projective_tensor (A = ProjArgs) and papof_mosaic_ray_tensor (A =
+// RayArgs, with its tables)
 template <typename A>
 static int mosaic_blend(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
                         const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
                         const papof_tensor* matrices, const papof_tensor* gains, int mode, const papof_tensor* out,
-                        const papof_tensor* count, void* stream) {
+                        const papof_tensor* count, void* stream, const papof_tensor* cols = nullptr,
+                        const papof_tensor* rows = nullptr) {
     A b{};
+    if constexpr (kRay<A>)
+        if (!ray_tables(b, cols, rows)) return PAPOF_EINVAL;
     if (!mosaic_args_from(b, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                           matrices))
         return PAPOF_EINVAL;
@@ -657,7 +857,7 @@ static int mosaic_blend(papof_handle* h, int n_frames, int height, int width, in
     if (gains && !described(gains, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1}, false)) return PAPOF_EINVAL;
     if (!mosaic_outputs(b, out, count)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
-    if constexpr (!kProjective<A>)
+    if constexpr (std::is_same<A, BlendArgs>::value)
         if (!gains && mode != PAPOF_MOSAIC_FEATHER)  // every gain 1: the instances papof_mosaic_tensor launches
             return launch_mosaic(static_cast<hipStream_t>(stream), static_cast<const MosaicArgs&>(b), n_out, mode);
     if (gains) b.gains = *gains;
@@ -681,13 +881,16 @@ extern "C" int papof_mosaic_projective_tensor(papof_handle* h, int n_frames, int
                                   matrices, gains, mode, out, count, stream);
 }
 
-// papof_mosaic_overlap_tensor (A = MosaicArgs) and papof_mosaic_overlap_projective_tensor (A = ProjArgs)
+// papof_mosaic_overlap_tensor (A = MosaicArgs), papof_mosaic_overlap_projective_tensor (A = ProjArgs) and
+// papof_mosaic_overlap_ray_tensor (A = RayArgs, with its tables)
 template <typename A>
 static int mosaic_overlap(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
                           const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
                           const papof_tensor* matrices, int step, double bound, long long* sums, long long* counts,
-                          void* stream) {
+                          void* stream, const papof_tensor* cols = nullptr, const papof_tensor* rows = nullptr) {
     OverlapArgsOf<A> a{};
+    if constexpr (kRay<A>)
+        if (!ray_tables(a.m, cols, rows)) return PAPOF_EINVAL;
     if (!mosaic_args_from(a.m, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                           matrices))
         return PAPOF_EINVAL;
@@ -725,6 +928,24 @@ extern "C" int papof_mosaic_overlap_projective_tensor(papof_handle* h, int n_fra
                                                       long long* counts, void* stream) {
     return mosaic_overlap<ProjArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                                     matrices, step, bound, sums, counts, stream);
+}
+
+extern "C" int papof_mosaic_ray_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                       const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                       const int* sources, const papof_tensor* matrices, const papof_tensor* cols,
+                                       const papof_tensor* rows, const papof_tensor* gains, int mode, const papof_tensor* out,
+                                       const papof_tensor* count, void* stream) {
+    return mosaic_blend<RayArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                 matrices, gains, mode, out, count, stream, cols, rows);
+}
+
+extern "C" int papof_mosaic_overlap_ray_tensor(papof_handle* h, int n_frames, int height, int width, int c,
+                                               const papof_tensor* frames, const papof_tensor* masks, int n_out, int n_src,
+                                               int out_height, int out_width, const int* sources, const papof_tensor* matrices,
+                                               const papof_tensor* cols, const papof_tensor* rows, int step, double bound,
+                                               long long* sums, long long* counts, void* stream) {
+    return mosaic_overlap<RayArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
+                                   matrices, step, bound, sums, counts, stream, cols, rows);
 }
 
 // Every instance launch_mosaic dispatches to has a lane per slot (n_src <= 64 * TY), so phase 1's loop over the slots runs once.

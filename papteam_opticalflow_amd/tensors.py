@@ -123,6 +123,15 @@ rule, `homography_transforms` makes the canvas and `panorama_homography` chains 
 
     pano = panorama_homography(frames, 5, mode="median", layout="NHWC")   # a Panorama with (T, 3, 3) matrices and motion
 
+Wide panoramas: the plane of the homography model ends 90 degrees from the reference frame.  `mosaic_rays` and
+`mosaic_overlap_rays` (include/papof.h: papof_mosaic_ray_tensor, papof_mosaic_overlap_ray_tensor) are the mosaic and the
+overlap statistics on a canvas of directions given by two small tables -- a cylinder or a sphere --, `estimate_focal` finds
+the focal length from the pair homographies, `wide_transforms` makes the canvas, its tables and the matrices (a chain
+normalised by its determinant, which keeps its sign past 90 degrees), and `panorama_wide` chains them.  On the plane's tables
+they return the bytes of the homography calls.
+
+    pano = panorama_wide(frames, 5, surface="cylinder", layout="NHWC")    # a WidePanorama: Panorama's fields, focal, cols, rows
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -2382,10 +2391,11 @@ def _check_gains(gains, n_out, N, dev):
 
 
 def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None,
-            projective=False):
+            projective=False, rays=None):
     """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
     count False: no count (None is returned for it; mode "first" then stops at the first live source).  With gains (checked)
-    or mode "feather": papof_mosaic_blend_tensor.  projective: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor."""
+    or mode "feather": papof_mosaic_blend_tensor.  projective: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor.
+    rays: the checked tables (cols, rows), matrices (n_out, N, 3, 3): papof_mosaic_ray_tensor."""
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
@@ -2396,7 +2406,7 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
     d_mask = _mask_struct(masks) if masks is not None else None
     d_cnt = _mask_struct(cnt) if count else None
-    if gains is None and mode != "feather" and not projective:
+    if gains is None and mode != "feather" and not projective and rays is None:
         _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
                 ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
         return out, cnt
@@ -2404,6 +2414,12 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     if gains is not None:
         d_gain = _struct(gains, (gains.stride(0), gains.stride(1), 0, 0),
                          capi.DTYPE_F32 if gains.dtype == torch.float32 else capi.DTYPE_F64)
+    if rays is not None:
+        d_cols, d_rows = _table_struct(rays[0]), _table_struct(rays[1])
+        _launch(dev, "papof_mosaic_ray_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), ctypes.byref(d_cols), ctypes.byref(d_rows), _ref(d_gain),
+                MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+        return out, cnt
     _launch(dev, "papof_mosaic_projective_tensor" if projective else "papof_mosaic_blend_tensor", T, H, W, C,
             ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat),
             _ref(d_gain), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
@@ -2465,8 +2481,9 @@ def _check_overlap_slots(n, what="matrices have"):
         raise ValueError("%s %d sources per output, the overlap statistics take 1 .. %d" % (what, n, MAX_OVERLAP))
 
 
-def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound, projective=False):
-    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's); projective: papof_mosaic_overlap_projective_tensor"""
+def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound, projective=False, rays=None):
+    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's); projective: papof_mosaic_overlap_projective_tensor;
+    rays: papof_mosaic_overlap_ray_tensor"""
     torch = _torch()
     (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
@@ -2476,6 +2493,12 @@ def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound
     d_in = _struct(ts[0], strides, code)
     d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
     d_mask = _mask_struct(masks) if masks is not None else None
+    if rays is not None:
+        d_cols, d_rows = _table_struct(rays[0]), _table_struct(rays[1])
+        _launch(dev, "papof_mosaic_overlap_ray_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
+                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), ctypes.byref(d_cols), ctypes.byref(d_rows), step,
+                ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
+        return Overlap(sums, counts, bound)
     _launch(dev, "papof_mosaic_overlap_projective_tensor" if projective else "papof_mosaic_overlap_tensor", T, H, W, C,
             ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), step,
             ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
@@ -2932,3 +2955,254 @@ def panorama_homography(frames, pyramidLevels, *, mode="median", ref=None, step=
     image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
                            projective=True)
     return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0])
+
+
+# ---- wide panoramas: the mosaic on a canvas of directions (include/papof.h: ray sampling)
+WidePanorama = collections.namedtuple("WidePanorama", Panorama._fields + ("focal", "cols", "rows"))
+SURFACES = ("cylinder", "sphere")
+
+
+def _table_struct(t):
+    return _struct(t, (t.stride(0), t.stride(1), 0, 0), capi.DTYPE_F32 if t.dtype == _torch().float32 else capi.DTYPE_F64)
+
+
+def _check_table(name, t, dev):
+    """the length n of the (n, 2) float32 / float64 table `t` on `dev` -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError("%s must be float32 or float64, got %s" % (name, t.dtype))
+    if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1:
+        raise ValueError("%s must be (n, 2) with n >= 1, got %s" % (name, tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("%s are on %s, the frames on %s: both must be on one device" % (name, t.device, dev))
+    return int(t.shape[0])
+
+
+def _ray_inputs(ts, descs, sources, matrices, cols, rows, masks):
+    """_mosaic_inputs with the canvas taken from the tables"""
+    dev = ts[0].device
+    Wc, Hc = _check_table("cols", cols, dev), _check_table("rows", rows, dev)
+    return _mosaic_inputs(ts, descs, sources, matrices, (Hc, Wc), masks, rows=3)
+
+
+def mosaic_rays(frames, sources, matrices, cols, rows, *, mode="median", masks=None, layout="NCHW", out_dtype=None, gains=None):
+    """mosaic_homography on a canvas of directions: cols (Wc, 2) with rows (u_x, w_x) and rows (Hc, 2) with rows (s_y, c_y),
+    float32 / float64 on the frames' device (any strides), give canvas pixel (x, y) the ray d = (u_x c_y, s_y, w_x c_y); the
+    canvas is (Hc, Wc) = the tables' lengths.  Source k is live where, with (Nx, Ny, D) = matrices[o, k] d, D > 0 and
+    (Nx / D, Ny / D) lies inside its frame (and no tap is masked); from that point on everything is mosaic's rule, and every
+    other argument, the four modes, the limits (255 sources, 64 for the median) and the result are mosaic_homography's.  The
+    tables are the caller's -- wide_transforms makes a cylinder's (sin, cos of the column's angle; the row's height, 1) and a
+    sphere's (sin, cos of the row's latitude) --, the device evaluates no sine.  On the plane's tables cols = (x, 1), rows =
+    (y, 1): mosaic_homography's bytes and count.  include/papof.h (papof_mosaic_ray_tensor) states it exactly; bitwise
+    reproducible.  Enqueued on the current stream; returns without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    Hc, Wc, m_code, n_out, N, src, m = _ray_inputs(ts, descs, sources, matrices, cols, rows, masks)
+    _check_slots(mode, N)
+    dev = ts[0].device
+    gains = _check_gains(gains, n_out, N, dev)
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains, rays=(cols, rows)))
+
+
+def mosaic_overlap_rays(frames, sources, matrices, cols, rows, *, masks=None, step=2, bound=1.0, layout="NCHW"):
+    """mosaic_overlap_homography on a canvas of directions (cols, rows: mosaic_rays'), liveness as mosaic_rays': the Overlap
+    that exposure_gains takes.  include/papof.h (papof_mosaic_overlap_ray_tensor).  Enqueued on the current stream; returns
+    without waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    Hc, Wc, m_code, n_out, N, src, m = _ray_inputs(ts, descs, sources, matrices, cols, rows, masks)
+    _check_overlap_slots(N)
+    _int_at_least("step", step, 1)
+    bound = _positive("bound", bound)
+    dev = ts[0].device
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound, rays=(cols, rows))
+
+
+def estimate_focal(motion, size):
+    """The focal length in pixels of a camera that rotates, from its pair homographies (Szeliski and Shum 1997): motion a
+    (T - 1, 3, 3) tensor or a Homography (pairs with ok False give nothing), size = (H, W) of the frames.  On the host in
+    float64.  Per pair, with M the homography conjugated by the principal point ((W - 1) / 2, (H - 1) / 2), K^-1 M K is a
+    scaled rotation for K = diag(f, f, 1): its first two rows (of frame i + 1's focal length) have equal norms and are
+    orthogonal, and so have its first two columns (frame i's).  Each of the four conditions gives f^2 in closed form; one
+    whose denominator is negligible (under 1e-6 of the magnitude of its own terms) or whose f^2 is not positive and finite is
+    skipped.  Returns the median of the estimates
+    as a float; ValueError naming focal= when no pair gives one -- a camera that does not rotate, or translates."""
+    import numpy as np
+    A, _ = _pair_homographies(motion)
+    H, W = _check_canvas(size)
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    C = np.array([[1.0, 0.0, cx], [0.0, 1.0, cy], [0.0, 0.0, 1.0]])
+    Ci = np.array([[1.0, 0.0, -cx], [0.0, 1.0, -cy], [0.0, 0.0, 1.0]])
+    tiny = 1e-6  # a denominator below this share of the magnitude of its own terms is negligible: all cancellation
+    est = []
+    with np.errstate(all="ignore"):
+        for a in A:
+            m = Ci @ a @ C
+            d = np.linalg.det(m)
+            if not (np.isfinite(m).all() and np.isfinite(d) and d > 0):
+                continue
+            (m0, m1, m2), (m3, m4, m5), (m6, m7, _) = (m / np.cbrt(d)).tolist()  # K^-1 m K is now a rotation
+            block = (m0 * m0 + m1 * m1) + (m3 * m3 + m4 * m4)
+            last = m6 * m6 + m7 * m7
+            for num, den, size_of_den in (
+                    # rows 0 and 1 of K^-1 m K, (m0, m1, m2 / f) and (m3, m4, m5 / f): equal norms, then orthogonal
+                    (m5 * m5 - m2 * m2, (m0 * m0 + m1 * m1) - (m3 * m3 + m4 * m4), block),
+                    (-(m2 * m5), m0 * m3 + m1 * m4, block),
+                    # columns 0 and 1, (m0, m3, f m6) and (m1, m4, f m7)
+                    ((m0 * m0 + m3 * m3) - (m1 * m1 + m4 * m4), m7 * m7 - m6 * m6, last),
+                    (-(m0 * m1 + m3 * m4), m6 * m7, last)):
+                if abs(den) > tiny * size_of_den:
+                    f2 = num / den
+                    if f2 > 0 and math.isfinite(f2):
+                        est.append(math.sqrt(f2))
+    if not est:
+        raise ValueError("no pair homography gives a focal length (the camera does not rotate between frames): pass focal=")
+    return float(np.median(est))
+
+
+def _check_focal(focal):
+    if isinstance(focal, bool) or not isinstance(focal, (int, float)):
+        raise TypeError("focal must be a number of pixels, got %r" % (focal,))
+    if not (math.isfinite(focal) and focal > 0):
+        raise ValueError("focal must be finite and > 0, got %r" % (focal,))
+    return float(focal)
+
+
+def _check_surface(surface):
+    if surface not in SURFACES:
+        raise ValueError("surface must be one of %s, got %r" % (SURFACES, surface))
+    return surface
+
+
+def wide_transforms(motion, size, focal, *, surface="cylinder", ref=None, margin=0, max_pixels=MAX_PIXELS):
+    """The canvas of a wide pan, as directions: motion a (T - 1, 3, 3) tensor (global_homography's, any device) or a
+    Homography (pairs with ok False enter as the identity), size = (H, W) of the frames, focal the focal length in pixels
+    (estimate_focal's), surface "cylinder" or "sphere" about the reference frame's vertical axis.  In float64 on the host, the
+    chain built as homography_transforms builds it, but every pair motion and every product is divided by the cube root of its
+    determinant, not by its [2][2] -- a scale that keeps its sign when a frame passes 90 degrees from the reference (the
+    [2][2] goes through 0 there); a determinant that is not finite and > 0 is refused, and there is no horizon test: frames
+    behind the reference are the purpose.  With K = (f 0 cx; 0 f cy; 0 0 1) and the principal point (cx, cy) = ((W - 1) / 2,
+    (H - 1) / 2), matrix_t = (frame t <- reference) K sends a ray of the reference camera to frame t.  Every border pixel of
+    every frame (edges bulge on a cylinder) is sent back to its ray (x, y, z) and to (theta, v) = (atan2(x, z), y / hypot(x,
+    z)) on the cylinder or (atan2(x, z), atan2(y, hypot(x, z))) on the sphere, theta unwrapped along the chain: each frame's
+    centre within pi of its neighbour's, each border point within pi of its centre.  One canvas pixel is 1 / f (radian, or
+    height): the reference frame's centre keeps its scale.  Column x is theta_0 + x / f with cols[x] = (sin, cos) of it; row y
+    is v_0 + y / f with rows[y] = (v, 1) on the cylinder, (sin v, cos v) on the sphere; (theta_0, v_0) is the floor of the
+    bounds' minima in pixels, less `margin`.  Returns (matrices (1, T, 3, 3) float64 -- mosaic_rays', for sources=None --,
+    cols (Wc, 2), rows (Hc, 2) float64, (Hc, Wc), origin = (theta_0, v_0)), the tensors on the motion's device.  ValueError
+    when theta spans 2 pi or more, when the bounds are not finite (a cylinder under a camera pitched to the pole) or when
+    Hc * Wc > max_pixels."""
+    import numpy as np
+    torch = _torch()
+    A, dev = _pair_homographies(motion)
+    H, W = _check_canvas(size)
+    f = _check_focal(focal)
+    _check_surface(surface)
+    T = A.shape[0] + 1
+    ref = _check_ref(ref, T)
+    _int_at_least("margin", margin, 0)
+    _int_at_least("max_pixels", max_pixels, 1)
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    K = np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
+    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    border = np.concatenate([np.stack([xs, np.zeros(W)]), np.stack([xs, np.full(W, H - 1.0)]),
+                             np.stack([np.zeros(H), ys]), np.stack([np.full(H, W - 1.0), ys])], axis=1)
+    pts = np.vstack([np.concatenate([[[cx], [cy]], border], axis=1), np.ones((1, 1 + border.shape[1]))])  # centre first
+
+    def unit(m):
+        d = np.linalg.det(m)
+        if not (np.isfinite(d) and d > 0):
+            raise ValueError("a motion along the chain has a determinant that is not finite and > 0: it mirrors the image or is "
+                             "singular")
+        return m / np.cbrt(d)
+
+    to_ref = [np.eye(3)] * T
+    with np.errstate(all="ignore"):
+        try:
+            for t in range(ref - 1, -1, -1):
+                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
+            for t in range(ref + 1, T):
+                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
+            from_ref = [np.linalg.inv(m) for m in to_ref]
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular: no canvas") from None
+        Ki = np.linalg.inv(K)
+        rays = np.stack([Ki @ (m @ pts) for m in to_ref])  # (T, 3, 1 + border)
+        theta = np.arctan2(rays[:, 0], rays[:, 2])
+        rho = np.hypot(rays[:, 0], rays[:, 2])
+        v = rays[:, 1] / rho if surface == "cylinder" else np.arctan2(rays[:, 1], rho)
+        if not (np.isfinite(theta).all() and np.isfinite(v).all() and np.isfinite(np.array(from_ref)).all()):
+            raise ValueError("the bounds of the canvas are not finite")
+        two_pi = 2.0 * math.pi
+        centre = theta[:, 0].copy()
+        for order in (range(ref + 1, T), range(ref - 1, -1, -1)):
+            for t in order:
+                near = centre[t - 1] if t > ref else centre[t + 1]
+                centre[t] = centre[t] - two_pi * np.round((centre[t] - near) / two_pi)
+        theta = theta - two_pi * np.round((theta - centre[:, None]) / two_pi)
+        if not theta.max() - theta.min() < two_pi:
+            raise ValueError("the pan spans %.1f degrees: a canvas holds less than 360" % math.degrees(theta.max() - theta.min()))
+        x0, y0 = math.floor(theta.min() * f) - margin, math.floor(v.min() * f) - margin
+        Wc, Hc = math.ceil(theta.max() * f) + margin - x0 + 1, math.ceil(v.max() * f) + margin - y0 + 1
+        if Hc * Wc > max_pixels:
+            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+        th = (x0 + np.arange(Wc, dtype=np.float64)) / f
+        vv = (y0 + np.arange(Hc, dtype=np.float64)) / f
+        cols = np.stack([np.sin(th), np.cos(th)], axis=1)
+        rows = np.stack([vv, np.ones(Hc)], axis=1) if surface == "cylinder" else np.stack([np.sin(vv), np.cos(vv)], axis=1)
+        M = np.stack([unit(m @ K) for m in from_ref])[None]
+    if not np.isfinite(M).all():
+        raise ValueError("the bounds of the canvas are not finite")
+    return (torch.from_numpy(M).to(dev), torch.from_numpy(cols).to(dev), torch.from_numpy(rows).to(dev), (Hc, Wc),
+            (x0 / f, y0 / f))
+
+
+def panorama_wide(frames, pyramidLevels, *, focal=None, surface="cylinder", mode="median", ref=None, step=1, margin=0,
+                  masks=None, iters=5, scale=1.0, layout="NCHW", out_dtype=None, exposure=False, **solver):
+    """panorama_homography on a cylinder or a sphere, for a pan wider than a plane holds (the plane stretches 4 x at 60 degrees
+    from the reference frame and ends at 90): flow_video, global_homography on the flows (iters, scale), estimate_focal on the
+    homographies unless `focal` (pixels) is given, wide_transforms (surface, ref, margin; the only wait) and ONE mosaic_rays of
+    the frames 0, step, 2 step, ...; exposure=True: mosaic_overlap_rays (step 2, bound 1.0) and exposure_gains first, as
+    panorama.  Every other argument, the limits and the errors are panorama_homography's.  Returns WidePanorama: Panorama's
+    fields -- matrices (T, 3, 3) float64, a ray of the reference camera to frame t; origin (theta_0, v_0), the direction of
+    canvas pixel (0, 0) -- and focal, cols (Wc, 2), rows (Hc, 2): the canvas' tables.  A pan of 360 degrees or more is refused
+    and a full circle does not close (no bundle adjustment); one focal length for all frames, no lens distortion, no parallax
+    (README).  Every argument error raises before anything is launched."""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    iters, scale = _check_irls(iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    _check_surface(surface)
+    if focal is not None:
+        focal = _check_focal(focal)
+    ref = _check_ref(ref, T)
+    _int_at_least("step", step, 1)
+    _int_at_least("margin", margin, 0)
+    dev = ts[0].device
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    picked = list(range(0, T, step))
+    if not isinstance(exposure, bool):
+        raise TypeError("exposure must be True or False, got %r" % (exposure,))
+    if exposure and len(picked) > MAX_OVERLAP:
+        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
+                         % (step, len(picked), MAX_OVERLAP))
+    _check_slots(mode, len(picked), "step = %d deposits" % step)
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
+    if focal is None:
+        focal = estimate_focal(mo, (H, W))
+    M, cols, rows, (Hc, Wc), origin = wide_transforms(mo, (H, W), focal, surface=surface, ref=ref, margin=margin)
+    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
+    gains = None
+    if exposure:
+        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, rays=(cols, rows))
+        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
+    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
+                           rays=(cols, rows))
+    return WidePanorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0],
+                        focal, cols, rows)
