@@ -1367,6 +1367,52 @@ int papof_mosaic_overlap_ray_tensor(papof_handle* h, int n_frames, int height, i
                                     const papof_tensor* rows, int step, double bound, long long* sums, long long* counts,
                                     void* stream);
 
+/* Bundle adjustment for a camera that rotates: the device half.  A parallel family: no call above changes.
+ *
+ * A LINK l is an ordered frame pair (i, j) with a flow field from frame i to frame j.  The unknowns of the adjustment are one
+ * rotation per frame and one focal length; the host (tensors.py: bundle_adjust) owns them, and per evaluation hands the device,
+ * per link, the row rot[l] = (R00 R01 R02 R10 R11 R12 R20 R21 R22 f) of ten float64 with R = R_j R_i^T.  The device never
+ * knows how many frames there are.
+ *
+ * papof_bundle_sums_tensor (bundle.hip: k_bundle_sums, k_bundle_reduce): flow float32 (widened exactly) / float64 (link, row,
+ * column, {vx, vy}), any strides >= 0; occlusion NULL or uint8 (link, row, column, .): a pixel whose byte is not 0 is left
+ * out; rotations float64 (link, k), k = 0 .. 9, strides >= 0; sums float64 (link, k), k = 0 .. 19, strides > 0.  The SAMPLED
+ * pixels are (x, r) = (step * a, step * b), a = 0 .. Ws - 1, b = 0 .. Hs - 1, Ws = (width - 1) / step + 1, Hs = (height - 1)
+ * / step + 1 (integer division).  With (cx, cy) = ((width - 1) / 2, (height - 1) / 2), in fp64 without fused multiply-adds
+ * and grouped as written, at a sampled pixel:
+ *     X = x + u;  Y = r + v                                                       (the observed point)
+ *     valid iff 0 <= X <= width - 1 and 0 <= Y <= height - 1 (false for a NaN or an infinity) and the occlusion byte is 0
+ *     px = (x - cx) / f;  py = (r - cy) / f
+ *     qx = (R00 * px + R01 * py) + R02;  qy = (R10 * px + R11 * py) + R12;  qz = (R20 * px + R21 * py) + R22
+ *     valid only if qz > PAPOF_HOMOGRAPHY_MIN_DEN (false for a NaN)
+ *     gx = qx / qz;  gy = qy / qz;  fgx = f * gx;  fgy = f * gy
+ *     e_x = X - (fgx + cx);  e_y = Y - (fgy + cy)                                 (observed - predicted)
+ *     e2 = e_x * e_x + e_y * e_y;  w = 1 / (1 + e2 / (scale * scale))             (the Cauchy weight)
+ * The Jacobian of the predicted point in four parameters -- a small rotation a applied to q as dq = a x q, and f (through
+ * p as well: d(fgx + cx)/df = gx + (R02 - gx R22) / qz) --:
+ *     Jx = ( -(fgx * gy),   f + fgx * gx,   -fgy,   gx + (R02 - gx * R22) / qz )
+ *     Jy = ( -(f + fgy * gy),   fgx * gy,    fgx,   gy + (R12 - gy * R22) / qz )
+ * The twenty sums over the link's valid sampled pixels, with (a, b) running over the upper triangle in the order (0,0) (0,1)
+ * (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3):
+ *     S0 .. S9    = sum w * (Jx[a] * Jx[b] + Jy[a] * Jy[b])                        (sum w J^T J)
+ *     S10 .. S13  = sum w * (Jx[a] * e_x + Jy[a] * e_y),  a = 0 .. 3               (sum w J^T e)
+ *     S14 = sum w * e2      S15 = sum w      S16 = sum 1 (the valid pixels)      S17 = sum e2      S18 = S19 = 0 (spare)
+ * Frame j's update omega_j enters a link as a = omega_j and frame i's as a = -R omega_i; the Gauss-Newton step solves
+ * (sum w J^T J) d = sum w J^T e.  Fixed order, no atomics, bitwise reproducible: papof_motion_fit_tensor's order over 64 x 32
+ * tiles of SAMPLED pixels (a lane: sampled column a, sampled rows threadIdx.y + 4 k in increasing order; the wave's shuffle
+ * tree 32 .. 1; the four waves in wave order; blockIdx.x the tile in row-major order, blockIdx.y the link, split at 65535);
+ * then one wave per link adds the tiles' rows l, l + 64, ... per lane in increasing order and the lanes by the same tree.
+ * A link's sums do not depend on the other links of the call.  Nothing waits; the sums are on `stream` when it is reached.
+ * PAPOF_EINVAL before any launch: a NULL handle, n_links / height / width / step < 1, a scale that is not finite and > 0, a
+ * descriptor that is NULL, has no data, another dtype or a negative stride (sums: a stride that is not > 0), a workspace that
+ * is NULL or smaller than
+ * papof_bundle_workspace: 8 * n_links * 32 * ceil(Ws / 64) * ceil(Hs / 32) bytes, or -1 where an argument is < 1 or a link
+ * has more than 2^31 - 1 tiles. */
+long long papof_bundle_workspace(int n_links, int height, int width, int step);
+int papof_bundle_sums_tensor(papof_handle* h, int n_links, int height, int width, int step, const papof_tensor* flow,
+                             const papof_tensor* occlusion, const papof_tensor* rotations, double scale,
+                             const papof_tensor* sums, void* workspace, long long workspace_bytes, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

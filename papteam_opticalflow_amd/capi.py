@@ -75,6 +75,7 @@ SYMBOLS = [
     "papof_homography_workspace", "papof_homography_fit_tensor", "papof_warp_projective_tensor",
     "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor",
     "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor",
+    "papof_bundle_workspace", "papof_bundle_sums_tensor",
 ]
 
 
@@ -252,6 +253,11 @@ def load():
     L.papof_mosaic_overlap_ray_tensor.argtypes = (L.papof_mosaic_overlap_tensor.argtypes[:13] + [_T, _T] +
                                                   L.papof_mosaic_overlap_tensor.argtypes[13:])
     L.papof_mosaic_overlap_ray_tensor.restype = c_int
+    L.papof_bundle_workspace.argtypes = [c_int, c_int, c_int, c_int]
+    L.papof_bundle_workspace.restype = ctypes.c_longlong
+    L.papof_bundle_sums_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, _T, c_void_p,
+                                           ctypes.c_longlong, c_void_p]
+    L.papof_bundle_sums_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

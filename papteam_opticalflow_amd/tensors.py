@@ -132,6 +132,14 @@ they return the bytes of the homography calls.
 
     pano = panorama_wide(frames, 5, surface="cylinder", layout="NHWC")    # a WidePanorama: Panorama's fields, focal, cols, rows
 
+Bundle adjustment: the chains above multiply pair motions, so the pairs' errors add up.  `bundle_adjust` fits one rotation per
+frame and one focal length to the flows of all overlapping frame pairs at once -- `bundle_sums` (include/papof.h:
+papof_bundle_sums_tensor) reduces every link's flow to the twenty fp64 sums of a robust Gauss-Newton evaluation on the device,
+the host expands, damps and solves --; `chain_rotations`, `bundle_links` and `link_flows` make its start, its links and their
+flows, `bundle_transforms` makes the canvas (the full circle where the pan closes), and `panorama_bundle` chains them.
+
+    pano = panorama_bundle(frames, 5, focal=1150.0, layout="NHWC")        # a BundlePanorama: WidePanorama's fields, rotations, links, cost
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -3206,3 +3214,535 @@ def panorama_wide(frames, pyramidLevels, *, focal=None, surface="cylinder", mode
                            rays=(cols, rows))
     return WidePanorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0],
                         focal, cols, rows)
+
+
+# ---- bundle adjustment for a camera that rotates (include/papof.h: papof_bundle_sums_tensor)
+Bundle = collections.namedtuple("Bundle", "rotations focal cost accepted support ok")
+BundlePanorama = collections.namedtuple("BundlePanorama", WidePanorama._fields + ("rotations", "links", "cost"))
+MIN_DEN = 0.0625       # include/papof.h: PAPOF_HOMOGRAPHY_MIN_DEN
+BUNDLE_SUMS = 20       # include/papof.h: the sums of a link
+BUNDLE_MIN_VALID = 16  # a link with fewer valid samples contributes nothing
+BUNDLE_DAMPING = 1e-4  # bundle_adjust's first damping
+LINK_GRID = 16         # bundle_links: a LINK_GRID x LINK_GRID grid of frame i's pixels
+LINK_CHUNK = 64        # link_flows: pairs per flow_pairs_fb call
+
+
+def _nearest_rotation(m):
+    """the rotation nearest to the 3 x 3 matrix m in the Frobenius norm: U V^T of its SVD, determinant + 1"""
+    import numpy as np
+    u, _, vt = np.linalg.svd(m)
+    if np.linalg.det(u @ vt) < 0:
+        u = u * np.array([1.0, 1.0, -1.0])
+    return u @ vt
+
+
+def _rodrigues(w):
+    """exp([w]x) of the rotation vector w (3,)"""
+    import numpy as np
+    t = float(np.sqrt(w @ w))
+    Kx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if t < 1e-8:  # sin t / t and (1 - cos t) / t^2 to the second order
+        return np.eye(3) + Kx + 0.5 * (Kx @ Kx)
+    return np.eye(3) + (math.sin(t) / t) * Kx + ((1.0 - math.cos(t)) / (t * t)) * (Kx @ Kx)
+
+
+def _check_rotations(name, rotations, n=None):
+    """the (T, 3, 3) float64 numpy array and the device of `rotations`, a tensor of finite entries -- TypeError / ValueError
+    otherwise"""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(rotations, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(rotations).__name__))
+    if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3) or rotations.shape[0] < 1:
+        raise ValueError("%s must be (T, 3, 3) with T >= 1, got shape %s" % (name, tuple(rotations.shape)))
+    if n is not None and rotations.shape[0] != n:
+        raise ValueError("%s has %d matrices, %d are needed" % (name, rotations.shape[0], n))
+    R = rotations.detach().to("cpu", torch.float64).numpy()
+    if not np.isfinite(R).all():
+        raise ValueError("%s has an entry that is not finite" % name)
+    return R, rotations.device
+
+
+def _check_links(links, T):
+    """the (L, 2) int64 numpy array of `links`, pairs (i, j) of two different frames of 0 .. T - 1 -- TypeError / ValueError
+    otherwise"""
+    import numpy as np
+    torch = _torch()
+    if isinstance(links, torch.Tensor):
+        links = links.detach().cpu().numpy()
+    try:
+        a = np.asarray(links)
+    except Exception:
+        raise TypeError("links must be an (L, 2) array of frame indices, got %s" % type(links).__name__) from None
+    if a.dtype.kind not in "iu":
+        raise TypeError("links must hold integers, got %s" % a.dtype)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1:
+        raise ValueError("links must be (L, 2) with L >= 1, got shape %s" % (a.shape,))
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= T or (a[:, 0] == a[:, 1]).any():
+        raise ValueError("links must join two different frames of 0 .. %d" % (T - 1))
+    return a
+
+
+def chain_rotations(motion, size, focal, *, ref=None):
+    """The absolute rotations of a chain of pair homographies: motion, size, focal and ref as wide_transforms', and its chain --
+    frame t to the reference frame as the product of the pair motions in between, every factor and product divided by the
+    cube root of its determinant (one that is not finite and > 0 is refused).  With K = (f 0 cx; 0 f cy; 0 0 1), K^-1 (frame
+    t <- reference) K is a rotation when the homographies are exact and near one otherwise: each is replaced by the nearest
+    rotation (U V^T of its SVD, determinant + 1).  Returns (T, 3, 3) float64 on the motion's device: frame t sees the ray d of
+    the reference camera at K R_t d; R_ref is the identity.  The start of bundle_adjust."""
+    import numpy as np
+    torch = _torch()
+    A, dev = _pair_homographies(motion)
+    H, W = _check_canvas(size)
+    f = _check_focal(focal)
+    T = A.shape[0] + 1
+    ref = _check_ref(ref, T)
+    K = np.array([[f, 0.0, (W - 1) / 2.0], [0.0, f, (H - 1) / 2.0], [0.0, 0.0, 1.0]])
+    Ki = np.linalg.inv(K)
+
+    def unit(m):
+        d = np.linalg.det(m)
+        if not (np.isfinite(d) and d > 0):
+            raise ValueError("a motion along the chain has a determinant that is not finite and > 0: it mirrors the image or is "
+                             "singular")
+        return m / np.cbrt(d)
+
+    to_ref = [np.eye(3)] * T
+    with np.errstate(all="ignore"):
+        try:
+            for t in range(ref - 1, -1, -1):
+                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
+            for t in range(ref + 1, T):
+                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
+            G = np.stack([Ki @ np.linalg.inv(m) @ K for m in to_ref])
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular: no rotations") from None
+    if not np.isfinite(G).all():
+        raise ValueError("the camera path is not finite")
+    return torch.from_numpy(np.stack([_nearest_rotation(g) for g in G])).to(dev)
+
+
+def _link_overlap(R, H, W, f):
+    """the share of the LINK_GRID x LINK_GRID grid of a frame's pixels that the rotations R (..., 3, 3) = R_j R_i^T send inside
+    frame j with qz > MIN_DEN"""
+    import numpy as np
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    gx, gy = np.meshgrid(np.linspace(0.0, W - 1.0, LINK_GRID), np.linspace(0.0, H - 1.0, LINK_GRID))
+    p = np.stack([(gx.reshape(-1) - cx) / f, (gy.reshape(-1) - cy) / f, np.ones(LINK_GRID * LINK_GRID)])
+    with np.errstate(all="ignore"):
+        q = R @ p
+        X, Y = f * q[..., 0, :] / q[..., 2, :] + cx, f * q[..., 1, :] / q[..., 2, :] + cy
+        inside = (q[..., 2, :] > MIN_DEN) & (X >= 0) & (X <= W - 1) & (Y >= 0) & (Y <= H - 1)
+    return inside.mean(-1)
+
+
+def bundle_links(rotations, size, focal, *, min_overlap=0.3, max_links=None):
+    """The frame pairs that a bundle adjustment joins: rotations (T, 3, 3) (chain_rotations', any device), size = (H, W) of the
+    frames, focal in pixels.  On the host in float64.  The pair (i, j), i < j, is a link when at least `min_overlap` (in (0,
+    1]) of a fixed 16 x 16 grid of frame i's pixels (the corners included) lands inside frame j in front of its horizon (qz >
+    0.0625) under R_j R_i^T; the consecutive pairs (t, t + 1) are links whatever their overlap.  Returns the links sorted, as
+    an (L, 2) int64 array (numpy).  On a full circle these include the pairs that close the loop, (0, T - 1) first.
+    ValueError when L exceeds `max_links` (None: no bound)."""
+    import numpy as np
+    R, _ = _check_rotations("rotations", rotations)
+    H, W = _check_canvas(size)
+    f = _check_focal(focal)
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)):
+        raise TypeError("min_overlap must be a number, got %r" % (min_overlap,))
+    if not 0 < min_overlap <= 1:
+        raise ValueError("min_overlap must be in (0, 1], got %r" % (min_overlap,))
+    if max_links is not None:
+        _int_at_least("max_links", max_links, 1)
+    T = R.shape[0]
+    if T < 2:
+        raise ValueError("rotations must hold at least 2 frames, got %d" % T)
+    out = []
+    for i in range(T - 1):
+        share = _link_overlap(R[i + 1:] @ R[i].T, H, W, f)
+        out += [(i, i + 1 + int(k)) for k in np.nonzero((share >= min_overlap) | (np.arange(T - 1 - i) == 0))[0]]
+    if max_links is not None and len(out) > max_links:
+        raise ValueError("%d links, more than max_links = %d: raise min_overlap" % (len(out), max_links))
+    return np.array(out, dtype=np.int64)
+
+
+def _rotation_flow(R, H, W, f, dev):
+    """the flow of K R K^-1 for the rotations R (L, 3, 3) float64 on `dev`, in torch operations: (L, 2, H, W) float64, zero
+    where the denominator is not > MIN_DEN or a component is not finite or beyond INIT_MAX"""
+    torch = _torch()
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    x = torch.arange(W, dtype=torch.float64, device=dev).view(1, 1, W)
+    y = torch.arange(H, dtype=torch.float64, device=dev).view(1, H, 1)
+    px, py = (x - cx) / f, (y - cy) / f
+    r = R.view(-1, 9, 1, 1)
+    qx = (r[:, 0] * px + r[:, 1] * py) + r[:, 2]
+    qy = (r[:, 3] * px + r[:, 4] * py) + r[:, 5]
+    qz = (r[:, 6] * px + r[:, 7] * py) + r[:, 8]
+    flow = torch.stack([f * qx / qz + cx - x, f * qy / qz + cy - y], 1)
+    good = (qz > MIN_DEN).unsqueeze(1) & (flow.abs() <= INIT_MAX)  # (a NaN compares False)
+    return torch.where(good.all(1, keepdim=True), flow, torch.zeros((), dtype=torch.float64, device=dev))
+
+
+def _link_flows(ts, descs, links, R, f, levels, layout, out_dtype, alphas, params, chunk):
+    torch = _torch()
+    (T, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    Rt = torch.from_numpy(R).to(dev)
+    out = []
+    for k in range(0, len(links), chunk):
+        li = torch.from_numpy(links[k:k + chunk, 0]).to(dev)
+        lj = torch.from_numpy(links[k:k + chunk, 1]).to(dev)
+        a, b = ts[0].index_select(0, li), ts[0].index_select(0, lj)
+        fw = _rotation_flow(Rt[lj] @ Rt[li].transpose(1, 2), H, W, f, dev)
+        bw = _rotation_flow(Rt[li] @ Rt[lj].transpose(1, 2), H, W, f, dev)
+        pair = [a, b]
+        d = [descriptor(t, layout) for t in pair]
+        out.append(_run_fb(pair, d, False, len(li), layout, out_dtype, levels, alphas, params, fw, bw))
+    if len(out) == 1:
+        return out[0]
+    cat = lambda i: torch.cat([o[i] for o in out]) if out[0][i] is not None else None  # noqa: E731
+    timing = {k: "%f" % sum(float(o.timing[k]) for o in out) for k in out[0].timing}
+    return FlowFB(cat(0), cat(1), cat(2), cat(3), cat(4), timing)
+
+
+def link_flows(frames, links, rotations, focal, pyramidLevels=2, *, layout="NCHW", out_dtype=None, consistency=CONSISTENCY,
+               chunk=LINK_CHUNK, **solver):
+    """The flows of a bundle adjustment's links: flow_pairs_fb on (frames[i], frames[j]) for every row (i, j) of `links`
+    ((L, 2) integers, bundle_links'), at most `chunk` pairs per call, each pair started from the flow that its rotations
+    predict -- init_flow = the flow of K (R_j R_i^T) K^-1 and init_flow_bw its inverse's, made with torch operations from
+    rotations (T, 3, 3) and focal; zero where the denominator is not > 0.0625 or the value is not finite or beyond 1e6.  So a
+    pair of frames far apart in time and 60 px apart in the image is within the solver's reach at two pyramid levels.
+    Returns a FlowFB over the L links in their order (timing: the calls' timers added).  Every argument error raises before
+    anything is launched."""
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
+    (T, H, W, C), _, _ = descs[0]
+    R, _ = _check_rotations("rotations", rotations, T)
+    f = _check_focal(focal)
+    links = _check_links(links, T)
+    _int_at_least("chunk", chunk, 1)
+    return _link_flows(ts, descs, links, R, f, pyramidLevels, layout, out_dtype, alphas, params, chunk)
+
+
+def _bundle_sums(flow, code, occlusion, rot, step, scale):
+    torch = _torch()
+    L, _, H, W = (int(x) for x in flow.shape)
+    dev = flow.device
+    sums = torch.empty((L, BUNDLE_SUMS), dtype=torch.float64, device=dev)
+    d_flow = _flow_struct(flow, code)
+    d_occ = _flow_struct(occlusion, capi.DTYPE_U8) if occlusion is not None else None
+    d_rot = _struct(rot, (rot.stride(0), rot.stride(1), 0, 0), capi.DTYPE_F64)
+    d_sums = _struct(sums, (sums.stride(0), sums.stride(1), 0, 0), capi.DTYPE_F64)
+    _launch(dev, "papof_bundle_sums_tensor", L, H, W, step, ctypes.byref(d_flow), _ref(d_occ), ctypes.byref(d_rot), scale,
+            ctypes.byref(d_sums),
+            workspace=("papof_bundle_workspace", (L, H, W, step), "a %d x %d flow is too large for bundle_sums" % (H, W)))
+    return sums
+
+
+def _check_bundle(flow, occlusion, step, scale):
+    """(the flow's dtype code, the mask as uint8, step, scale) of the arguments that bundle_sums and bundle_adjust share"""
+    _, scale = _check_irls(1, scale)
+    _int_at_least("step", step, 1)
+    code = _check_flow("flow", flow)
+    occ = _check_occlusion(occlusion, tuple(flow.shape), flow.device)
+    if not _on_gpu(flow):
+        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
+    return code, occ, step, scale
+
+
+def bundle_sums(flow, rotations_ij, focal, *, occlusion=None, step=1, scale=1.0):
+    """One evaluation of a bundle adjustment's links on the device: flow (L, 2, H, W) float32 / float64 on a HIP device, any
+    strides -- link l's flow from its frame i to its frame j --, rotations_ij (L, 3, 3) the links' R_j R_i^T (any device),
+    focal in pixels, occlusion None or the (L, 2, H, W) bool / uint8 mask of flow_pairs_fb (channel 0 is read).  Every
+    step-th pixel of every step-th row is sampled; a sample counts where the flow stays inside the frame, is not masked and
+    lies in front of the link's horizon.  Returns (L, 20) float64 on the flow's device: the upper triangle of sum w J^T J (10),
+    sum w J^T e (4), sum w e^2, sum w, the number of valid samples, sum e^2 and two zeros -- J the Jacobian of the predicted
+    point in a small rotation of the link and the focal length, e the observed less the predicted point, w = 1 / (1 + e^2 /
+    scale^2).  include/papof.h (papof_bundle_sums_tensor) states every term and the order of the sums; bitwise reproducible,
+    and a link's row does not depend on the other links.  Enqueued on the current stream; returns without waiting."""
+    import numpy as np
+    torch = _torch()
+    code, occ, step, scale = _check_bundle(flow, occlusion, step, scale)
+    R, _ = _check_rotations("rotations_ij", rotations_ij, int(flow.shape[0]))
+    f = _check_focal(focal)
+    rot = np.concatenate([R.reshape(-1, 9), np.full((R.shape[0], 1), f)], 1)
+    return _bundle_sums(flow, code, occ, torch.from_numpy(rot).to(flow.device), step, scale)
+
+
+def bundle_solve(evaluate, links, rotations, focal, *, iters=10, ref=0, fix_focal=False):
+    """bundle_adjust's host half, in float64 numpy: Levenberg-Marquardt on one rotation per frame and one focal length, over
+    `evaluate(R_ij (L, 3, 3), f) -> (L, 20)`, the links' sums at the parameters it is handed (bundle_sums' rule).  links (L,
+    2) int64, rotations (T, 3, 3), focal a float.  A link whose count of valid samples (sum 16) is under 16 contributes
+    nothing.  The cost is the contributing links' sum w e^2.  Per link the 4 x 4 block (sums 0 .. 9) and the right-hand side
+    (10 .. 13) are those of d = (a, df) with a = omega_j - R omega_i: with P = (-R I 0; 0 0 1) they enter the system of
+    (omega_0 .. omega_T-1, df) as P^T A P and P^T g; frame `ref`'s three rows and columns are dropped (the gauge) and df's with
+    fix_focal.  A step solves (N + damping * diag N) d = g, with the damping starting at 1e-4, and is tried as R_t <- exp([omega_t]x)
+    R_t (Rodrigues), f <- f + df: kept when the cost does not increase (the damping is divided by 10), else dropped (the
+    damping is multiplied by 10 and the step retried from the kept parameters); a step that makes f not > 0, cannot be
+    solved or after which a frame is reached by no contributing link is dropped likewise.  `iters` steps are tried: iters + 1
+    evaluations.  Returns (rotations (T, 3, 3), focal, cost -- (iters + 1,) float64, the first evaluation's then every
+    tried step's --, accepted (iters,) bool, the kept parameters' sums (L, 20)).  ValueError when at the start a frame is
+    reached by no contributing link."""
+    import numpy as np
+    R = np.array(rotations, dtype=np.float64)
+    f = float(focal)
+    T, L = R.shape[0], len(links)
+    li, lj = links[:, 0], links[:, 1]
+
+    def sums_at(R, f):
+        S = np.array(evaluate(R[lj] @ R[li].transpose(0, 2, 1), f), dtype=np.float64)
+        live = S[:, 16] >= BUNDLE_MIN_VALID
+        S = np.where(live[:, None], S, 0.0)
+        reached = np.zeros(T, bool)
+        reached[li[live]] = True
+        reached[lj[live]] = True
+        return S, reached
+
+    S, reached = sums_at(R, f)
+    if not reached.all():
+        raise ValueError("frame %d is reached by no link with %d valid samples or more" % (int(np.argmin(reached)), BUNDLE_MIN_VALID))
+    cost = [float(S[:, 14].sum())]
+    kept = cost[0]  # the cost of the kept parameters
+    accepted = []
+    keep = np.ones(3 * T + 1, bool)
+    keep[3 * ref:3 * ref + 3] = False
+    keep[3 * T] = not fix_focal
+    iu = np.triu_indices(4)
+    lam = BUNDLE_DAMPING
+    for _ in range(iters):
+        N = np.zeros((3 * T + 1, 3 * T + 1))
+        g = np.zeros(3 * T + 1)
+        for l in range(L):
+            if S[l, 16] == 0:
+                continue
+            A = np.zeros((4, 4))
+            A[iu] = S[l, :10]
+            A = A + np.triu(A, 1).T
+            i, j = int(li[l]), int(lj[l])
+            P = np.zeros((4, 7))
+            P[:3, :3] = -(R[j] @ R[i].T)
+            P[:3, 3:6] = np.eye(3)
+            P[3, 6] = 1.0
+            idx = np.r_[3 * i:3 * i + 3, 3 * j:3 * j + 3, 3 * T]
+            N[np.ix_(idx, idx)] += P.T @ A @ P
+            g[idx] += P.T @ S[l, 10:14]
+        Nk, gk = N[np.ix_(keep, keep)], g[keep]
+        trial = None
+        with np.errstate(all="ignore"):
+            try:
+                d = np.zeros(3 * T + 1)
+                d[keep] = np.linalg.solve(Nk + lam * np.diag(np.diag(Nk)), gk)
+                if np.isfinite(d).all() and f + d[3 * T] > 0:
+                    trial = (np.stack([_rodrigues(d[3 * t:3 * t + 3]) @ R[t] for t in range(T)]), f + float(d[3 * T]))
+            except np.linalg.LinAlgError:
+                pass
+        if trial is None:
+            cost.append(math.inf)
+            accepted.append(False)
+            lam *= 10.0
+            continue
+        S1, reached = sums_at(*trial)
+        c1 = float(S1[:, 14].sum()) if reached.all() else math.inf
+        cost.append(c1)
+        if c1 <= kept:
+            R, f = trial
+            S, kept = S1, c1
+            accepted.append(True)
+            lam /= 10.0
+        else:
+            accepted.append(False)
+            lam *= 10.0
+    return R, f, np.array(cost), np.array(accepted, dtype=bool), S
+
+
+def bundle_adjust(flow, links, rotations, focal, *, occlusion=None, iters=10, scale=1.0, step=1, ref=0, fix_focal=False):
+    """Bundle adjustment of a camera that rotates: one joint robust least-squares fit of one rotation per frame and one
+    shared focal length to the dense flows of every link -- flow (L, 2, H, W) on a HIP device and occlusion as bundle_sums',
+    links (L, 2) integers (bundle_links'; row l = (i, j): flow[l] runs from frame i to frame j), rotations (T, 3, 3) the
+    start (chain_rotations'), focal the start in pixels.  Levenberg-Marquardt (bundle_solve states it): each of the iters + 1
+    evaluations is one bundle_sums on every `step`-th pixel with Cauchy scale `scale` and one copy of (L, 20) doubles to the
+    host, which WAITS for it; the host expands the links' 4 x 4 blocks into the system of 3 (T - 1) + 1 unknowns (frame `ref`
+    is fixed as the gauge, the focal length too with fix_focal=True), damps, solves and updates.  Returns Bundle(rotations
+    (T, 3, 3) float64 on the flow's device, focal, cost (iters + 1,) float64 numpy -- the history, sum w e^2 over the links
+    --, accepted (iters,) bool numpy, support (L,) float64 numpy -- each link's sum of weights over its sampled pixels at the
+    returned parameters, 0 for a link that does not contribute --, ok: a step was accepted).  One focal length, no lens
+    distortion, no translation (README).  Every argument error raises before anything is launched; ValueError when a frame is
+    reached by no link with 16 valid samples."""
+    import numpy as np
+    torch = _torch()
+    code, occ, step, scale = _check_bundle(flow, occlusion, step, scale)
+    R, _ = _check_rotations("rotations", rotations)
+    T = R.shape[0]
+    links = _check_links(links, T)
+    if len(links) != flow.shape[0]:
+        raise ValueError("flow has %d fields for %d links" % (flow.shape[0], len(links)))
+    f = _check_focal(focal)
+    _int_at_least("iters", iters, 1)
+    ref = _check_ref(ref, T)
+    if not isinstance(fix_focal, bool):
+        raise TypeError("fix_focal must be True or False, got %r" % (fix_focal,))
+    seen = np.zeros(T, bool)
+    seen[links.reshape(-1)] = True
+    if not seen.all():
+        raise ValueError("frame %d is in no link" % int(np.argmin(seen)))
+    H, W = int(flow.shape[2]), int(flow.shape[3])
+    n = ((H - 1) // step + 1) * ((W - 1) // step + 1)
+
+    def evaluate(Rij, fk):
+        return bundle_sums(flow, torch.from_numpy(np.ascontiguousarray(Rij)), fk, occlusion=occ, step=step,
+                           scale=scale).cpu().numpy()
+
+    R, f, cost, accepted, S = bundle_solve(evaluate, links, R, f, iters=iters, ref=ref, fix_focal=fix_focal)
+    return Bundle(torch.from_numpy(R).to(flow.device), f, cost, accepted, S[:, 15] / n, bool(accepted.any()))
+
+
+def bundle_transforms(rotations, size, focal, *, surface="cylinder", ref=None, margin=0, max_pixels=MAX_PIXELS):
+    """wide_transforms from absolute rotations: rotations (T, 3, 3) (bundle_adjust's, any device; frame t sees the ray d at K
+    R_t d), size, focal, surface, margin and max_pixels as there; ref names the frame whose centre sets the canvas' middle
+    (None: the middle frame) -- the rays are those of the rotations' own reference, which bundle_adjust keeps fixed.  The
+    border pixels of every frame go back to their rays R_t^T K^-1 p and to (theta, v) as there, theta unwrapped along the
+    frames' order.  Where theta spans less than 2 pi, the canvas is wide_transforms': column x is theta_0 + x / f.  Where it
+    spans 2 pi or more the canvas is the FULL CIRCLE: Wc = round(2 pi f) columns at a pitch of 2 pi / Wc, column x at
+    theta_ref - pi + x * pitch with theta_ref the direction of frame ref's centre, so that column Wc - 1's neighbour is
+    column 0; mosaic_rays needs to know nothing, its liveness is "in front of the camera and inside the frame".  Rows as
+    there, at 1 / f.  Returns (matrices (1, T, 3, 3) float64 = K R_t over the cube root of f^2, cols (Wc, 2), rows (Hc, 2),
+    (Hc, Wc), origin = (theta_0, v_0)), the tensors on the rotations' device.  ValueError when the bounds are not finite or
+    Hc * Wc > max_pixels."""
+    import numpy as np
+    torch = _torch()
+    R, dev = _check_rotations("rotations", rotations)
+    H, W = _check_canvas(size)
+    f = _check_focal(focal)
+    _check_surface(surface)
+    T = R.shape[0]
+    ref = _check_ref(ref, T)
+    _int_at_least("margin", margin, 0)
+    _int_at_least("max_pixels", max_pixels, 1)
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    K = np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
+    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    border = np.concatenate([np.stack([xs, np.zeros(W)]), np.stack([xs, np.full(W, H - 1.0)]),
+                             np.stack([np.zeros(H), ys]), np.stack([np.full(H, W - 1.0), ys])], axis=1)
+    pts = np.vstack([np.concatenate([[[cx], [cy]], border], axis=1), np.ones((1, 1 + border.shape[1]))])  # centre first
+    with np.errstate(all="ignore"):
+        rays = R.transpose(0, 2, 1) @ (np.linalg.inv(K) @ pts)  # (T, 3, 1 + border)
+        theta = np.arctan2(rays[:, 0], rays[:, 2])
+        rho = np.hypot(rays[:, 0], rays[:, 2])
+        v = rays[:, 1] / rho if surface == "cylinder" else np.arctan2(rays[:, 1], rho)
+        if not (np.isfinite(theta).all() and np.isfinite(v).all()):
+            raise ValueError("the bounds of the canvas are not finite")
+        two_pi = 2.0 * math.pi
+        centre = theta[:, 0].copy()
+        for order in (range(ref + 1, T), range(ref - 1, -1, -1)):
+            for t in order:
+                near = centre[t - 1] if t > ref else centre[t + 1]
+                centre[t] = centre[t] - two_pi * np.round((centre[t] - near) / two_pi)
+        theta = theta - two_pi * np.round((theta - centre[:, None]) / two_pi)
+        y0 = math.floor(v.min() * f) - margin
+        Hc = math.ceil(v.max() * f) + margin - y0 + 1
+        if theta.max() - theta.min() < two_pi:
+            x0 = math.floor(theta.min() * f) - margin
+            Wc = math.ceil(theta.max() * f) + margin - x0 + 1
+            th0 = x0 / f
+            th = (x0 + np.arange(Wc, dtype=np.float64)) / f
+        else:
+            Wc = int(round(two_pi * f))
+            th0 = float(centre[ref]) - math.pi
+            th = th0 + np.arange(Wc, dtype=np.float64) * (two_pi / Wc)
+        if Hc * Wc > max_pixels:
+            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+        vv = (y0 + np.arange(Hc, dtype=np.float64)) / f
+        cols = np.stack([np.sin(th), np.cos(th)], axis=1)
+        rows = np.stack([vv, np.ones(Hc)], axis=1) if surface == "cylinder" else np.stack([np.sin(vv), np.cos(vv)], axis=1)
+        M = (K @ R / np.cbrt(f * f))[None]
+    if not np.isfinite(M).all():
+        raise ValueError("the bounds of the canvas are not finite")
+    return (torch.from_numpy(M).to(dev), torch.from_numpy(cols).to(dev), torch.from_numpy(rows).to(dev), (Hc, Wc),
+            (th0, y0 / f))
+
+
+def panorama_bundle(frames, pyramidLevels, *, focal=None, surface="cylinder", mode="median", ref=None, step=1, margin=0,
+                    masks=None, iters=5, scale=1.0, layout="NCHW", out_dtype=None, exposure=False, bundle_iters=10,
+                    min_overlap=0.3, link_levels=2, bundle_step=1, max_links=None, fix_focal=False, **solver):
+    """panorama_wide with a bundle adjustment between the homographies and the canvas, so that the pairs' errors no longer
+    add up and a full circle can close: flow_video, global_homography on the flows (iters, scale), estimate_focal unless
+    `focal` is given (now only the start), chain_rotations, a FIRST bundle_adjust of the consecutive links alone with the focal
+    length held (it turns the chain of nearest rotations into the rotations that fit the flows at that focal length, which is
+    what the next two steps start from), bundle_links (min_overlap, max_links), link_flows at `link_levels` pyramid levels for
+    the links that are not consecutive frames, the bundle_adjust of all links (the focal length free unless fix_focal=True),
+    bundle_transforms (surface, ref, margin) and ONE mosaic_rays of the frames 0, step, 2 step, ...; exposure=True:
+    mosaic_overlap_rays (step 2, bound 1.0) and exposure_gains first.  Both adjustments take bundle_iters steps with the Cauchy
+    scale `scale` on every bundle_step-th pixel and keep frame `ref` fixed.  The consecutive links reuse the video's forward
+    flows; flow_video computes no backward flow, so they carry no occlusion mask (their pixels that leave the frame are what
+    the Cauchy weight is for), while the other links carry link_flows' forward-backward mask.  Every other argument, the
+    limits and the errors are panorama_wide's.  Returns BundlePanorama: WidePanorama's fields -- matrices (T, 3, 3) = K R_t up
+    to scale, focal the adjusted focal length, motion / ok the pair homographies that started it -- and rotations (T, 3, 3),
+    links (L, 2) int64 (numpy) and cost, the last bundle_adjust's history.  A pan of 360 degrees or more gets the full-circle
+    canvas; whether the circle CLOSES depends on the start: a link's flow starts from what the rotations predict, so the pair
+    that closes the loop is found and followed only when the chain misses it by less than the solver's reach (README: give
+    focal= for a full circle).  The host waits once per evaluation; one focal length, no lens distortion, no translation or
+    parallax, a few hundred frames at most (README).  Every argument error raises before anything is launched."""
+    import numpy as np
+    torch = _torch()
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    iters, scale = _check_irls(iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    _check_surface(surface)
+    if focal is not None:
+        focal = _check_focal(focal)
+    ref = _check_ref(ref, T)
+    _int_at_least("step", step, 1)
+    _int_at_least("margin", margin, 0)
+    _int_at_least("bundle_iters", bundle_iters, 1)
+    _int_at_least("link_levels", link_levels, 1)
+    _int_at_least("bundle_step", bundle_step, 1)
+    if max_links is not None:
+        _int_at_least("max_links", max_links, 1)
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)):
+        raise TypeError("min_overlap must be a number, got %r" % (min_overlap,))
+    if not 0 < min_overlap <= 1:
+        raise ValueError("min_overlap must be in (0, 1], got %r" % (min_overlap,))
+    if not isinstance(fix_focal, bool):
+        raise TypeError("fix_focal must be True or False, got %r" % (fix_focal,))
+    dev = ts[0].device
+    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    picked = list(range(0, T, step))
+    if not isinstance(exposure, bool):
+        raise TypeError("exposure must be True or False, got %r" % (exposure,))
+    if exposure and len(picked) > MAX_OVERLAP:
+        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
+                         % (step, len(picked), MAX_OVERLAP))
+    _check_slots(mode, len(picked), "step = %d deposits" % step)
+    flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, params)
+    mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
+    if focal is None:
+        focal = estimate_focal(mo, (H, W))
+    chain = np.stack([np.arange(T - 1), np.arange(1, T)], 1)
+    R0 = bundle_adjust(flow, chain, chain_rotations(mo, (H, W), focal, ref=ref), focal, iters=bundle_iters, scale=scale,
+                       step=bundle_step, ref=ref, fix_focal=True).rotations
+    links = bundle_links(R0, (H, W), focal, min_overlap=min_overlap, max_links=max_links)
+    near = links[:, 1] == links[:, 0] + 1
+    flows, occ = flow[torch.from_numpy(links[near, 0]).to(dev)], None
+    if not near.all():
+        far = _link_flows(ts, descs, links[~near], R0.cpu().numpy(), focal, link_levels, layout, torch.float64,
+                          _alphas(CONSISTENCY), params, LINK_CHUNK)
+        at = torch.from_numpy(near).to(dev)
+        both = torch.empty((len(links), 2, H, W), dtype=torch.float64, device=dev)
+        both[at], both[~at] = flows, far.flow_fw
+        occ = torch.zeros((len(links), 2, H, W), dtype=torch.uint8, device=dev)
+        occ[~at] = far.occlusion.view(torch.uint8)
+        flows = both
+    b = bundle_adjust(flows, links, R0, focal, occlusion=occ, iters=bundle_iters, scale=scale, step=bundle_step, ref=ref,
+                      fix_focal=fix_focal)
+    M, cols, rows, (Hc, Wc), origin = bundle_transforms(b.rotations, (H, W), b.focal, surface=surface, ref=ref, margin=margin)
+    src = torch.tensor([picked], dtype=torch.int32, device=dev)
+    gains = None
+    if exposure:
+        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, rays=(cols, rows))
+        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
+    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
+                           rays=(cols, rows))
+    return BundlePanorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0],
+                          b.focal, cols, rows, b.rotations, links, b.cost)
