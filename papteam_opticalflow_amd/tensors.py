@@ -1012,13 +1012,15 @@ def _check_path(radius, crop, size):
     return (W - 1) / 2.0, (H - 1) / 2.0
 
 
-def _checked_motion(motion):
-    """a Motion or a (T - 1, 2, 3) tensor as it is -- TypeError / ValueError otherwise"""
-    m = motion.motion if isinstance(motion, Motion) else motion
+def _checked_motion(motion, kind=Motion):
+    """a Motion or a (T - 1, 2, 3) tensor as it is, or with kind=Homography a Homography or a (T - 1, 3, 3) tensor --
+    TypeError / ValueError otherwise"""
+    rows = 2 if kind is Motion else 3
+    m = motion.motion if isinstance(motion, kind) else motion
     if not isinstance(m, _torch().Tensor):
-        raise TypeError("motion must be a torch.Tensor or a Motion, got %s" % type(m).__name__)
-    if m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or m.shape[0] < 1:
-        raise ValueError("motion must be (T - 1, 2, 3) with T >= 2, got shape %s" % (tuple(m.shape),))
+        raise TypeError("motion must be a torch.Tensor or a %s, got %s" % (kind.__name__, type(m).__name__))
+    if m.dim() != 3 or tuple(m.shape[1:]) != (rows, 3) or m.shape[0] < 1:
+        raise ValueError("motion must be (T - 1, %d, 3) with T >= 2, got shape %s" % (rows, tuple(m.shape)))
     return motion
 
 
@@ -2398,52 +2400,87 @@ def _check_gains(gains, n_out, N, dev):
     return gains
 
 
-def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None,
-            projective=False, rays=None):
+# how a source reaches the canvas: the rows of its matrices (2: affine, 3: projective), the entry points of the mosaic and of
+# the overlap statistics, and whether the canvas is a pair of tables (cols, rows) of directions instead of a size
+_Rule = collections.namedtuple("_Rule", "rows blend overlap tables")
+_AFFINE = _Rule(2, "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", False)
+_PROJECTIVE = _Rule(3, "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor", False)
+_RAYS = _Rule(3, "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor", True)
+
+
+def _mosaic_head(ts, descs, src, matrices, m_code, masks, Hc, Wc, tables):
+    """the arguments that every entry point of the mosaics begins with, the ray rule's tables behind the matrices (a byref
+    keeps its descriptor alive)"""
+    (T, H, W, C), strides, code = descs[0]
+    d_mask = _mask_struct(masks) if masks is not None else None
+    return (T, H, W, C, ctypes.byref(_struct(ts[0], strides, code)), _ref(d_mask), int(src.shape[0]), int(src.shape[1]), Hc, Wc,
+            ctypes.c_void_p(src.data_ptr()), ctypes.byref(_struct(matrices, tuple(matrices.stride()), m_code)),
+            *(ctypes.byref(_table_struct(t)) for t in tables))
+
+
+def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None, rule=_AFFINE,
+            tables=()):
     """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
     count False: no count (None is returned for it; mode "first" then stops at the first live source).  With gains (checked)
-    or mode "feather": papof_mosaic_blend_tensor.  projective: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor.
-    rays: the checked tables (cols, rows), matrices (n_out, N, 3, 3): papof_mosaic_ray_tensor."""
+    or mode "feather": papof_mosaic_blend_tensor.  rule _PROJECTIVE: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor.
+    rule _RAYS: tables the checked (cols, rows), matrices (n_out, N, 3, 3): papof_mosaic_ray_tensor."""
     torch = _torch()
-    (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
-    n_out, N = int(src.shape[0]), int(src.shape[1])
-    out, d_out = _new_frames(n_out, Hc, Wc, C, layout, out_dtype, dev)
+    n_out = int(src.shape[0])
+    out, d_out = _new_frames(n_out, Hc, Wc, descs[0][0][3], layout, out_dtype, dev)
     cnt = torch.empty((n_out, Hc, Wc), dtype=torch.uint8, device=dev) if count else None
-    d_in = _struct(ts[0], strides, code)
-    d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
-    d_mask = _mask_struct(masks) if masks is not None else None
     d_cnt = _mask_struct(cnt) if count else None
-    if gains is None and mode != "feather" and not projective and rays is None:
-        _launch(dev, "papof_mosaic_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+    head = _mosaic_head(ts, descs, src, matrices, m_code, masks, Hc, Wc, tables)
+    tail = (MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+    if rule is _AFFINE and gains is None and mode != "feather":
+        _launch(dev, "papof_mosaic_tensor", *head, *tail)
         return out, cnt
     d_gain = None
     if gains is not None:
         d_gain = _struct(gains, (gains.stride(0), gains.stride(1), 0, 0),
                          capi.DTYPE_F32 if gains.dtype == torch.float32 else capi.DTYPE_F64)
-    if rays is not None:
-        d_cols, d_rows = _table_struct(rays[0]), _table_struct(rays[1])
-        _launch(dev, "papof_mosaic_ray_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), ctypes.byref(d_cols), ctypes.byref(d_rows), _ref(d_gain),
-                MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
-        return out, cnt
-    _launch(dev, "papof_mosaic_projective_tensor" if projective else "papof_mosaic_blend_tensor", T, H, W, C,
-            ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat),
-            _ref(d_gain), MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
+    _launch(dev, rule.blend, *head, _ref(d_gain), *tail)
     return out, cnt
 
 
-def _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=2):
-    """what mosaic and mosaic_overlap check alike behind their frames, in mosaic's order: (Hc, Wc, m_code, n_out, N, the host
-    sources or None, masks)"""
-    Hc, Wc = _check_canvas(size)
+def _mosaic_inputs(rule, ts, descs, sources, matrices, canvas, masks):
+    """what the mosaics and their overlaps check alike behind their frames, in mosaic's order: (Hc, Wc, m_code, n_out, N, the
+    host sources or None, masks, the tables); canvas: the size, or with rule.tables (cols, rows), whose lengths are the size"""
     (T, H, W, _), _, _ = descs[0]
     dev = ts[0].device
-    m_code, n_out, N = _check_mosaic_matrices(matrices, dev, rows)
+    if rule.tables:
+        Wc, Hc = _check_table("cols", canvas[0], dev), _check_table("rows", canvas[1], dev)
+    else:
+        Hc, Wc = _check_canvas(canvas)
+    m_code, n_out, N = _check_mosaic_matrices(matrices, dev, rule.rows)
     src = _check_sources(sources, n_out, N, T)
     m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
-    return Hc, Wc, m_code, n_out, N, src, m
+    return Hc, Wc, m_code, n_out, N, src, m, tuple(canvas) if rule.tables else ()
+
+
+def _mosaic_call(rule, frames, sources, matrices, canvas, mode, masks, layout, out_dtype, gains):
+    """mosaic, mosaic_homography and mosaic_rays behind their docstrings"""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    Hc, Wc, m_code, n_out, N, src, m, tables = _mosaic_inputs(rule, ts, descs, sources, matrices, canvas, masks)
+    _check_slots(mode, N)
+    dev = ts[0].device
+    gains = _check_gains(gains, n_out, N, dev)
+    src = _device_sources(src, descs[0][0][0], n_out, dev)
+    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains, rule=rule,
+                           tables=tables))
+
+
+def _mosaic_overlap_call(rule, frames, sources, matrices, canvas, masks, step, bound, layout):
+    """mosaic_overlap, mosaic_overlap_homography and mosaic_overlap_rays behind their docstrings"""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    Hc, Wc, m_code, n_out, N, src, m, tables = _mosaic_inputs(rule, ts, descs, sources, matrices, canvas, masks)
+    _check_overlap_slots(N)
+    _int_at_least("step", step, 1)
+    bound = _positive("bound", bound)
+    src = _device_sources(src, descs[0][0][0], n_out, ts[0].device)
+    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound, rule, tables)
 
 
 def _device_sources(src, T, n_out, dev):
@@ -2473,15 +2510,7 @@ def mosaic(frames, sources, matrices, size, *, mode="median", masks=None, layout
     sources).  include/papof.h (papof_mosaic_tensor, papof_mosaic_blend_tensor) states it exactly;
     bitwise reproducible.  The sources are checked on the host (a device tensor of sources waits for its stream); the kernel
     is enqueued on the current stream and the call returns without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
-    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks)
-    _check_slots(mode, N)
-    dev = ts[0].device
-    gains = _check_gains(gains, n_out, N, dev)
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains))
+    return _mosaic_call(_AFFINE, frames, sources, matrices, size, mode, masks, layout, out_dtype, gains)
 
 
 def _check_overlap_slots(n, what="matrices have"):
@@ -2489,26 +2518,15 @@ def _check_overlap_slots(n, what="matrices have"):
         raise ValueError("%s %d sources per output, the overlap statistics take 1 .. %d" % (what, n, MAX_OVERLAP))
 
 
-def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound, projective=False, rays=None):
-    """papof_mosaic_overlap_tensor on checked arguments (as _mosaic's); projective: papof_mosaic_overlap_projective_tensor;
-    rays: papof_mosaic_overlap_ray_tensor"""
+def _mosaic_overlap(ts, descs, src, matrices, m_code, masks, Hc, Wc, step, bound, rule=_AFFINE, tables=()):
+    """the overlap entry point of `rule` (papof_mosaic_overlap_tensor, _projective_tensor, _ray_tensor) on checked arguments,
+    as _mosaic's"""
     torch = _torch()
-    (T, H, W, C), strides, code = descs[0]
     dev = ts[0].device
     n_out, N = int(src.shape[0]), int(src.shape[1])
     sums = torch.empty((n_out, N, N), dtype=torch.int64, device=dev)
     counts = torch.empty((n_out, N, N), dtype=torch.int64, device=dev)
-    d_in = _struct(ts[0], strides, code)
-    d_mat = _struct(matrices, tuple(matrices.stride()), m_code)
-    d_mask = _mask_struct(masks) if masks is not None else None
-    if rays is not None:
-        d_cols, d_rows = _table_struct(rays[0]), _table_struct(rays[1])
-        _launch(dev, "papof_mosaic_overlap_ray_tensor", T, H, W, C, ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc,
-                ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), ctypes.byref(d_cols), ctypes.byref(d_rows), step,
-                ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
-        return Overlap(sums, counts, bound)
-    _launch(dev, "papof_mosaic_overlap_projective_tensor" if projective else "papof_mosaic_overlap_tensor", T, H, W, C,
-            ctypes.byref(d_in), _ref(d_mask), n_out, N, Hc, Wc, ctypes.c_void_p(src.data_ptr()), ctypes.byref(d_mat), step,
+    _launch(dev, rule.overlap, *_mosaic_head(ts, descs, src, matrices, m_code, masks, Hc, Wc, tables), step,
             ctypes.c_double(bound), ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(counts.data_ptr()))
     return Overlap(sums, counts, bound)
 
@@ -2523,14 +2541,7 @@ def mosaic_overlap(frames, sources, matrices, size, *, masks=None, step=2, bound
     source j.  Returns Overlap(sums, counts (n_out, N, N) int64 on the frames' device, bound).  Integer sums: bitwise
     reproducible.  include/papof.h (papof_mosaic_overlap_tensor) states it exactly.  Enqueued on the current stream; the
     call returns without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks)
-    _check_overlap_slots(N)
-    _int_at_least("step", step, 1)
-    bound = _positive("bound", bound)
-    dev = ts[0].device
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound)
+    return _mosaic_overlap_call(_AFFINE, frames, sources, matrices, size, masks, step, bound, layout)
 
 
 def _positive(name, v):
@@ -2585,15 +2596,15 @@ def exposure_gains(overlap, *, sigma_n=10.0 / 255.0, sigma_g=0.1, anchor=None):
 
 
 def _pair_motions(motion):
-    """the (T - 1, 2, 3) float64 numpy array (pairs of a Motion with ok False: the identity) and the device of a motion that
-    _checked_motion has accepted"""
+    """the (T - 1, 2 or 3, 3) float64 numpy array (pairs of a Motion or Homography with ok False: the identity) and the device
+    of a motion that _checked_motion has accepted"""
     import numpy as np
     ok = None
-    if isinstance(motion, Motion):
+    if isinstance(motion, (Motion, Homography)):
         motion, ok = motion.motion, motion.ok
     A = motion.detach().to("cpu", _torch().float64).numpy()
     if ok is not None:
-        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(2, 3))
+        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(A.shape[1], 3))
     return A, motion.device
 
 
@@ -2609,6 +2620,62 @@ def _check_ref(ref, T):
     if isinstance(ref, bool) or not isinstance(ref, int) or not 0 <= ref < T:
         raise ValueError("ref must be None or a frame index in 0 .. %d, got %r" % (T - 1, ref))
     return ref
+
+
+def _as_it_is(m):
+    return m
+
+
+def _over_last(m):
+    if not m[2, 2] > 0:  # (a NaN included) the sign of every denominator would flip
+        raise ValueError("a motion along the chain has a [2][2] that is not > 0: it sends the image centre's "
+                         "neighbourhood behind its horizon")
+    return m / m[2, 2]
+
+
+def _over_det(m):
+    import numpy as np
+    d = np.linalg.det(m)
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError("a motion along the chain has a determinant that is not finite and > 0: it mirrors the image or is "
+                         "singular")
+    return m / np.cbrt(d)
+
+
+def _chain(A, ref, unit, nothing):
+    """(frame t to the reference frame, the reference frame to frame t) for the 3 x 3 pair motions A (T - 1, 3, 3), as the
+    chain of the pair motions between t and ref, every factor and every product through the normaliser `unit` (_as_it_is,
+    _over_last, _over_det) -- so that the reference frame and frames that do not move against it (pairs with ok False) map to
+    their own integer corners exactly: no floor or ceiling of 1e-16.  ValueError, naming what there is `nothing` of, where a
+    motion cannot be inverted"""
+    import numpy as np
+    T = A.shape[0] + 1
+    to_ref = [np.eye(3)] * T
+    with np.errstate(all="ignore"):
+        try:
+            for t in range(ref - 1, -1, -1):
+                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
+            for t in range(ref + 1, T):
+                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
+            return to_ref, [np.linalg.inv(m) for m in to_ref]
+        except np.linalg.LinAlgError:
+            raise ValueError("the camera path is singular: %s" % nothing) from None
+
+
+def _corners(H, W):
+    import numpy as np
+    return np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
+
+
+def _planar_canvas(pts, margin, max_pixels):
+    """the canvas around the finite points pts (T, 2, n) of the reference frame's plane: ((x0, y0), (Hc, Wc), the translation
+    from canvas to plane) -- ValueError beyond max_pixels"""
+    import numpy as np
+    x0, y0 = math.floor(pts[:, 0].min()) - margin, math.floor(pts[:, 1].min()) - margin
+    Wc, Hc = math.ceil(pts[:, 0].max()) + margin - x0 + 1, math.ceil(pts[:, 1].max()) + margin - y0 + 1
+    if Hc * Wc > max_pixels:
+        raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+    return (x0, y0), (Hc, Wc), np.array([[1.0, 0.0, x0], [0.0, 1.0, y0], [0.0, 0.0, 1.0]])
 
 
 def mosaic_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PIXELS):
@@ -2628,29 +2695,16 @@ def mosaic_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PIXELS
     ref = _check_ref(ref, T)
     _int_at_least("margin", margin, 0)
     _int_at_least("max_pixels", max_pixels, 1)
-    corners = np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
-    # P_ref P_t^-1 as the chain of pair motions between t and ref, so that the reference frame and frames that do not
-    # move against it (pairs with ok False) map to their own integer corners exactly: no floor or ceiling of 1e-16
-    to_ref = [np.eye(3)] * T
+    last = np.tile([[[0.0, 0.0, 1.0]]], (T - 1, 1, 1))  # P_ref P_t^-1 as the chain of the pair motions, each with its last row
+    to_ref, from_ref = _chain(np.concatenate([A, last], axis=1), ref, _as_it_is, "no canvas")
+    corners = _corners(H, W)
     with np.errstate(all="ignore"):
-        try:
-            for t in range(ref - 1, -1, -1):
-                to_ref[t] = to_ref[t + 1] @ np.vstack([A[t], [0.0, 0.0, 1.0]])
-            for t in range(ref + 1, T):
-                to_ref[t] = to_ref[t - 1] @ np.linalg.inv(np.vstack([A[t - 1], [0.0, 0.0, 1.0]]))
-            pts = np.stack([(m @ corners)[:2] for m in to_ref])  # (T, 2, 4)
-            from_ref = [np.linalg.inv(m) for m in to_ref]
-        except np.linalg.LinAlgError:
-            raise ValueError("the camera path is singular: no canvas") from None
+        pts = np.stack([(m @ corners)[:2] for m in to_ref])  # (T, 2, 4)
     if not (np.isfinite(pts).all() and np.isfinite(np.array(from_ref)).all()):
         raise ValueError("the bounds of the canvas are not finite")
-    x0, y0 = math.floor(pts[:, 0].min()) - margin, math.floor(pts[:, 1].min()) - margin
-    Wc, Hc = math.ceil(pts[:, 0].max()) + margin - x0 + 1, math.ceil(pts[:, 1].max()) + margin - y0 + 1
-    if Hc * Wc > max_pixels:
-        raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
-    shift = np.array([[1.0, 0.0, x0], [0.0, 1.0, y0], [0.0, 0.0, 1.0]])
+    origin, size, shift = _planar_canvas(pts, margin, max_pixels)
     M = np.stack([(m @ shift)[:2] for m in from_ref])[None]
-    return torch.from_numpy(M).to(dev), (Hc, Wc), (x0, y0)
+    return torch.from_numpy(M).to(dev), size, origin
 
 
 def neighbour_transforms(transforms, motion, radius):
@@ -2690,6 +2744,47 @@ def neighbour_transforms(transforms, motion, radius):
     return torch.from_numpy(src).to(transforms.device), torch.from_numpy(mats).to(transforms.device)
 
 
+def _check_bool(name, v):
+    if not isinstance(v, bool):
+        raise TypeError("%s must be True or False, got %r" % (name, v))
+
+
+_PanoramaArgs = collections.namedtuple("_PanoramaArgs", "ts descs params out_dtype ref masks picked step mode layout exposure")
+
+
+def _panorama_head(frames, pyramidLevels, solver, mode, ref, step, margin, masks, layout, out_dtype, exposure):
+    """the argument checks that the four panoramas share, and what they need of them: the frames and their descriptors, the
+    solver's params, the output dtype, the reference frame, the masks as uint8 and the frames `picked` for the mosaic"""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    (T, H, W, _), _, _ = descs[0]
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    _check_mode(mode)
+    ref = _check_ref(ref, T)
+    _int_at_least("step", step, 1)
+    _int_at_least("margin", margin, 0)
+    m = _check_masks("masks", masks, T, H, W, ts[0].device) if masks is not None else None
+    picked = list(range(0, T, step))
+    _check_bool("exposure", exposure)
+    if exposure and len(picked) > MAX_OVERLAP:
+        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
+                         % (step, len(picked), MAX_OVERLAP))
+    _check_slots(mode, len(picked), "step = %d deposits" % step)
+    return _PanoramaArgs(ts, descs, params, out_dtype, ref, m, picked, step, mode, layout, exposure)
+
+
+def _panorama_tail(p, rule, M, size, tables=()):
+    """the picked frames through M (1, T, ., 3) onto the canvas: with exposure the overlap statistics and their gains,
+    anchored at the reference frame when it is among the picked, then ONE mosaic -- (image, count, gains or None)"""
+    src = _torch().tensor([p.picked], dtype=_torch().int32, device=p.ts[0].device)
+    gains = None
+    if p.exposure:
+        ov = _mosaic_overlap(p.ts, p.descs, src, M[:, ::p.step], capi.DTYPE_F64, p.masks, *size, 2, 1.0, rule, tables)
+        gains = exposure_gains(ov, anchor=p.picked.index(p.ref) if p.ref in p.picked else None)
+    image, count = _mosaic(p.ts, p.descs, src, M[:, ::p.step], capi.DTYPE_F64, p.masks, *size, p.mode, p.layout, p.out_dtype,
+                           gains=gains, rule=rule, tables=tables)
+    return image[0], count[0], None if gains is None else gains[0]
+
+
 def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0, masks=None, model="affine", iters=5,
              scale=1.0, layout="NCHW", out_dtype=None, exposure=False, **solver):
     """The panorama of a panning video of T >= 2 frames -- with mode "median" its clean plate: what moved in front of the
@@ -2708,33 +2803,14 @@ def panorama(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0
     gain of every deposited frame).  The model is affine (panorama_homography is the projective chain, for a camera that
     rotates) and there is no bundle adjustment; the exposure is one gain per frame, and feathering ghosts where the
     registration is off (README).  Every argument error raises before anything is launched."""
-    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    p = _panorama_head(frames, pyramidLevels, solver, mode, ref, step, margin, masks, layout, out_dtype, exposure)
     code, iters, scale = _check_fit(model, iters, scale)
-    (T, H, W, C), _, _ = descs[0]
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
-    ref = _check_ref(ref, T)
-    _int_at_least("step", step, 1)
-    _int_at_least("margin", margin, 0)
-    dev = ts[0].device
-    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
-    picked = list(range(0, T, step))
-    if not isinstance(exposure, bool):
-        raise TypeError("exposure must be True or False, got %r" % (exposure,))
-    if exposure and len(picked) > MAX_OVERLAP:
-        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
-                         % (step, len(picked), MAX_OVERLAP))
-    _check_slots(mode, len(picked), "step = %d deposits" % step)
-    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    (T, H, W, _), _, _ = p.descs[0]
+    flow, _, timing = _run(p.ts, p.descs, True, T - 1, layout, _torch().float64, pyramidLevels, p.params)
     mo = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
-    M, (Hc, Wc), origin = mosaic_transforms(mo, (H, W), ref=ref, margin=margin)
-    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
-    gains = None
-    if exposure:
-        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0)
-        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
-    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains)
-    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0])
+    M, size, origin = mosaic_transforms(mo, (H, W), ref=p.ref, margin=margin)
+    image, count, gains = _panorama_tail(p, _AFFINE, M, size)
+    return Panorama(image, count, M[0], origin, mo.motion, mo.ok, flow, timing, gains)
 
 
 def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW", model="similarity", radius=15, crop=1.0,
@@ -2825,46 +2901,14 @@ def mosaic_homography(frames, sources, matrices, size, *, mode="median", masks=N
     from that point on everything is mosaic's rule.  On matrices whose last row is (0, 0, 1), mosaic's bytes and count.
     include/papof.h (papof_mosaic_projective_tensor) states it exactly; bitwise reproducible.  Enqueued on the current
     stream; returns without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
-    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=3)
-    _check_slots(mode, N)
-    dev = ts[0].device
-    gains = _check_gains(gains, n_out, N, dev)
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains, projective=True))
+    return _mosaic_call(_PROJECTIVE, frames, sources, matrices, size, mode, masks, layout, out_dtype, gains)
 
 
 def mosaic_overlap_homography(frames, sources, matrices, size, *, masks=None, step=2, bound=1.0, layout="NCHW"):
     """mosaic_overlap through 3 x 3 matrices (n_out, N, 3, 3), liveness as mosaic_homography's: the Overlap that
     exposure_gains takes.  include/papof.h (papof_mosaic_overlap_projective_tensor).  Enqueued on the current stream; returns
     without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    Hc, Wc, m_code, n_out, N, src, m = _mosaic_inputs(ts, descs, sources, matrices, size, masks, rows=3)
-    _check_overlap_slots(N)
-    _int_at_least("step", step, 1)
-    bound = _positive("bound", bound)
-    dev = ts[0].device
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound, projective=True)
-
-
-def _pair_homographies(motion):
-    """the (T - 1, 3, 3) float64 numpy array (pairs of a Homography with ok False: the identity) and the device of `motion`, a
-    (T - 1, 3, 3) tensor or a Homography -- TypeError / ValueError otherwise"""
-    import numpy as np
-    ok = None
-    if isinstance(motion, Homography):
-        motion, ok = motion.motion, motion.ok
-    if not isinstance(motion, _torch().Tensor):
-        raise TypeError("motion must be a torch.Tensor or a Homography, got %s" % type(motion).__name__)
-    if motion.dim() != 3 or tuple(motion.shape[1:]) != (3, 3) or motion.shape[0] < 1:
-        raise ValueError("motion must be (T - 1, 3, 3) with T >= 2, got shape %s" % (tuple(motion.shape),))
-    A = motion.detach().to("cpu", _torch().float64).numpy()
-    if ok is not None:
-        A = np.where(ok.detach().cpu().numpy().reshape(-1, 1, 1), A, np.eye(3))
-    return A, motion.device
+    return _mosaic_overlap_call(_PROJECTIVE, frames, sources, matrices, size, masks, step, bound, layout)
 
 
 def homography_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PIXELS):
@@ -2881,31 +2925,16 @@ def homography_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PI
     Hc * Wc > max_pixels."""
     import numpy as np
     torch = _torch()
-    A, dev = _pair_homographies(motion)
+    A, dev = _pair_motions(_checked_motion(motion, Homography))
     H, W = _check_canvas(size)
     T = A.shape[0] + 1
     ref = _check_ref(ref, T)
     _int_at_least("margin", margin, 0)
     _int_at_least("max_pixels", max_pixels, 1)
-    corners = np.array([[0.0, W - 1.0, 0.0, W - 1.0], [0.0, 0.0, H - 1.0, H - 1.0], [1.0, 1.0, 1.0, 1.0]])
-
-    def unit(m):
-        if not m[2, 2] > 0:  # (a NaN included) the sign of every denominator would flip
-            raise ValueError("a motion along the chain has a [2][2] that is not > 0: it sends the image centre's "
-                             "neighbourhood behind its horizon")
-        return m / m[2, 2]
-
-    to_ref = [np.eye(3)] * T
+    to_ref, from_ref = _chain(A, ref, _over_last, "no canvas")
+    corners = _corners(H, W)
     with np.errstate(all="ignore"):
-        try:
-            for t in range(ref - 1, -1, -1):
-                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
-            for t in range(ref + 1, T):
-                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
-            pts = np.stack([m @ corners for m in to_ref])  # (T, 3, 4)
-            from_ref = [np.linalg.inv(m) for m in to_ref]
-        except np.linalg.LinAlgError:
-            raise ValueError("the camera path is singular: no canvas") from None
+        pts = np.stack([m @ corners for m in to_ref])  # (T, 3, 4)
         if not (np.isfinite(pts).all() and np.isfinite(np.array(from_ref)).all()):
             raise ValueError("the bounds of the canvas are not finite")
         behind = ~(pts[:, 2] > 0).all(1)
@@ -2915,15 +2944,11 @@ def homography_transforms(motion, size, *, ref=None, margin=0, max_pixels=MAX_PI
         pts = pts[:, :2] / pts[:, 2:]
         if not np.isfinite(pts).all():
             raise ValueError("the bounds of the canvas are not finite")
-        x0, y0 = math.floor(pts[:, 0].min()) - margin, math.floor(pts[:, 1].min()) - margin
-        Wc, Hc = math.ceil(pts[:, 0].max()) + margin - x0 + 1, math.ceil(pts[:, 1].max()) + margin - y0 + 1
-        if Hc * Wc > max_pixels:
-            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
-        shift = np.array([[1.0, 0.0, x0], [0.0, 1.0, y0], [0.0, 0.0, 1.0]])
-        M = np.stack([unit(m @ shift) for m in from_ref])[None]
+        origin, size, shift = _planar_canvas(pts, margin, max_pixels)
+        M = np.stack([_over_last(m @ shift) for m in from_ref])[None]
     if not np.isfinite(M).all():
         raise ValueError("the bounds of the canvas are not finite")
-    return torch.from_numpy(M).to(dev), (Hc, Wc), (x0, y0)
+    return torch.from_numpy(M).to(dev), size, origin
 
 
 def panorama_homography(frames, pyramidLevels, *, mode="median", ref=None, step=1, margin=0, masks=None, iters=5, scale=1.0,
@@ -2935,34 +2960,14 @@ def panorama_homography(frames, pyramidLevels, *, mode="median", ref=None, step=
     frame t, projectively -- and motion (T - 1, 3, 3).  The canvas is one plane: a pan that nears 90 degrees from the
     reference frame is refused by homography_transforms; there is no bundle adjustment, no lens distortion and no parallax
     (README).  Every argument error raises before anything is launched."""
-    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    p = _panorama_head(frames, pyramidLevels, solver, mode, ref, step, margin, masks, layout, out_dtype, exposure)
     iters, scale = _check_irls(iters, scale)
-    (T, H, W, C), _, _ = descs[0]
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
-    ref = _check_ref(ref, T)
-    _int_at_least("step", step, 1)
-    _int_at_least("margin", margin, 0)
-    dev = ts[0].device
-    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
-    picked = list(range(0, T, step))
-    if not isinstance(exposure, bool):
-        raise TypeError("exposure must be True or False, got %r" % (exposure,))
-    if exposure and len(picked) > MAX_OVERLAP:
-        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
-                         % (step, len(picked), MAX_OVERLAP))
-    _check_slots(mode, len(picked), "step = %d deposits" % step)
-    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    (T, H, W, _), _, _ = p.descs[0]
+    flow, _, timing = _run(p.ts, p.descs, True, T - 1, layout, _torch().float64, pyramidLevels, p.params)
     mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
-    M, (Hc, Wc), origin = homography_transforms(mo, (H, W), ref=ref, margin=margin)
-    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
-    gains = None
-    if exposure:
-        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, projective=True)
-        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
-    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
-                           projective=True)
-    return Panorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0])
+    M, size, origin = homography_transforms(mo, (H, W), ref=p.ref, margin=margin)
+    image, count, gains = _panorama_tail(p, _PROJECTIVE, M, size)
+    return Panorama(image, count, M[0], origin, mo.motion, mo.ok, flow, timing, gains)
 
 
 # ---- wide panoramas: the mosaic on a canvas of directions (include/papof.h: ray sampling)
@@ -2988,13 +2993,6 @@ def _check_table(name, t, dev):
     return int(t.shape[0])
 
 
-def _ray_inputs(ts, descs, sources, matrices, cols, rows, masks):
-    """_mosaic_inputs with the canvas taken from the tables"""
-    dev = ts[0].device
-    Wc, Hc = _check_table("cols", cols, dev), _check_table("rows", rows, dev)
-    return _mosaic_inputs(ts, descs, sources, matrices, (Hc, Wc), masks, rows=3)
-
-
 def mosaic_rays(frames, sources, matrices, cols, rows, *, mode="median", masks=None, layout="NCHW", out_dtype=None, gains=None):
     """mosaic_homography on a canvas of directions: cols (Wc, 2) with rows (u_x, w_x) and rows (Hc, 2) with rows (s_y, c_y),
     float32 / float64 on the frames' device (any strides), give canvas pixel (x, y) the ray d = (u_x c_y, s_y, w_x c_y); the
@@ -3005,29 +3003,14 @@ def mosaic_rays(frames, sources, matrices, cols, rows, *, mode="median", masks=N
     sphere's (sin, cos of the row's latitude) --, the device evaluates no sine.  On the plane's tables cols = (x, 1), rows =
     (y, 1): mosaic_homography's bytes and count.  include/papof.h (papof_mosaic_ray_tensor) states it exactly; bitwise
     reproducible.  Enqueued on the current stream; returns without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
-    Hc, Wc, m_code, n_out, N, src, m = _ray_inputs(ts, descs, sources, matrices, cols, rows, masks)
-    _check_slots(mode, N)
-    dev = ts[0].device
-    gains = _check_gains(gains, n_out, N, dev)
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return Mosaic(*_mosaic(ts, descs, src, matrices, m_code, m, Hc, Wc, mode, layout, out_dtype, gains=gains, rays=(cols, rows)))
+    return _mosaic_call(_RAYS, frames, sources, matrices, (cols, rows), mode, masks, layout, out_dtype, gains)
 
 
 def mosaic_overlap_rays(frames, sources, matrices, cols, rows, *, masks=None, step=2, bound=1.0, layout="NCHW"):
     """mosaic_overlap_homography on a canvas of directions (cols, rows: mosaic_rays'), liveness as mosaic_rays': the Overlap
     that exposure_gains takes.  include/papof.h (papof_mosaic_overlap_ray_tensor).  Enqueued on the current stream; returns
     without waiting."""
-    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
-    Hc, Wc, m_code, n_out, N, src, m = _ray_inputs(ts, descs, sources, matrices, cols, rows, masks)
-    _check_overlap_slots(N)
-    _int_at_least("step", step, 1)
-    bound = _positive("bound", bound)
-    dev = ts[0].device
-    src = _device_sources(src, descs[0][0][0], n_out, dev)
-    return _mosaic_overlap(ts, descs, src, matrices, m_code, m, Hc, Wc, step, bound, rays=(cols, rows))
+    return _mosaic_overlap_call(_RAYS, frames, sources, matrices, (cols, rows), masks, step, bound, layout)
 
 
 def estimate_focal(motion, size):
@@ -3040,7 +3023,7 @@ def estimate_focal(motion, size):
     skipped.  Returns the median of the estimates
     as a float; ValueError naming focal= when no pair gives one -- a camera that does not rotate, or translates."""
     import numpy as np
-    A, _ = _pair_homographies(motion)
+    A, _ = _pair_motions(_checked_motion(motion, Homography))
     H, W = _check_canvas(size)
     cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
     C = np.array([[1.0, 0.0, cx], [0.0, 1.0, cy], [0.0, 0.0, 1.0]])
@@ -3050,10 +3033,12 @@ def estimate_focal(motion, size):
     with np.errstate(all="ignore"):
         for a in A:
             m = Ci @ a @ C
-            d = np.linalg.det(m)
-            if not (np.isfinite(m).all() and np.isfinite(d) and d > 0):
+            if not np.isfinite(m).all():
                 continue
-            (m0, m1, m2), (m3, m4, m5), (m6, m7, _) = (m / np.cbrt(d)).tolist()  # K^-1 m K is now a rotation
+            try:
+                (m0, m1, m2), (m3, m4, m5), (m6, m7, _) = _over_det(m).tolist()  # K^-1 m K is now a rotation
+            except ValueError:  # a pair that mirrors or is singular gives nothing
+                continue
             block = (m0 * m0 + m1 * m1) + (m3 * m3 + m4 * m4)
             last = m6 * m6 + m7 * m7
             for num, den, size_of_den in (
@@ -3086,6 +3071,59 @@ def _check_surface(surface):
     return surface
 
 
+def _camera(f, H, W):
+    """K = (f 0 cx; 0 f cy; 0 0 1) with the principal point at the frame's middle"""
+    import numpy as np
+    return np.array([[f, 0.0, (W - 1) / 2.0], [0.0, f, (H - 1) / 2.0], [0.0, 0.0, 1.0]])
+
+
+def _centre_and_border(H, W):
+    """the principal point, then every border pixel of a frame (edges bulge on a cylinder), homogeneous: (3, 1 + 2 W + 2 H)"""
+    import numpy as np
+    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    border = np.concatenate([np.stack([xs, np.zeros(W)]), np.stack([xs, np.full(W, H - 1.0)]),
+                             np.stack([np.zeros(H), ys]), np.stack([np.full(H, W - 1.0), ys])], axis=1)
+    return np.vstack([np.concatenate([[[(W - 1) / 2.0], [(H - 1) / 2.0]], border], axis=1), np.ones((1, 1 + border.shape[1]))])
+
+
+def _directions(rays, surface, ref):
+    """(theta, v, the centres' theta) of the rays (T, 3, n), each frame's centre first: (atan2(x, z), y / hypot(x, z)) on the
+    cylinder, (atan2(x, z), atan2(y, hypot(x, z))) on the sphere, theta unwrapped along the chain from frame ref -- each
+    frame's centre within pi of its neighbour's, each point within pi of its centre.  ValueError where one is not finite.
+    Call it with numpy's warnings off."""
+    import numpy as np
+    theta = np.arctan2(rays[:, 0], rays[:, 2])
+    rho = np.hypot(rays[:, 0], rays[:, 2])
+    v = rays[:, 1] / rho if surface == "cylinder" else np.arctan2(rays[:, 1], rho)
+    if not (np.isfinite(theta).all() and np.isfinite(v).all()):
+        raise ValueError("the bounds of the canvas are not finite")
+    two_pi = 2.0 * math.pi
+    centre = theta[:, 0].copy()
+    for t in range(ref + 1, len(centre)):
+        centre[t] = centre[t] - two_pi * np.round((centre[t] - centre[t - 1]) / two_pi)
+    for t in range(ref - 1, -1, -1):
+        centre[t] = centre[t] - two_pi * np.round((centre[t] - centre[t + 1]) / two_pi)
+    return theta - two_pi * np.round((theta - centre[:, None]) / two_pi), v, centre
+
+
+def _pan_columns(theta, f, margin):
+    """(x0, Wc) of a pan of less than a full circle at 1 / f per column: column x is (x0 + x) / f"""
+    x0 = math.floor(theta.min() * f) - margin
+    return x0, math.ceil(theta.max() * f) + margin - x0 + 1
+
+
+def _canvas_rows(v, f, surface, margin, Wc, max_pixels):
+    """(y0, Hc, the table rows (Hc, 2)) of a canvas of directions of Wc columns at 1 / f per row: row y is (y0 + y) / f, (v, 1)
+    of it on the cylinder and (sin v, cos v) on the sphere -- ValueError beyond max_pixels"""
+    import numpy as np
+    y0 = math.floor(v.min() * f) - margin
+    Hc = math.ceil(v.max() * f) + margin - y0 + 1
+    if Hc * Wc > max_pixels:
+        raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+    vv = (y0 + np.arange(Hc, dtype=np.float64)) / f
+    return y0, Hc, np.stack([vv, np.ones(Hc)], axis=1) if surface == "cylinder" else np.stack([np.sin(vv), np.cos(vv)], axis=1)
+
+
 def wide_transforms(motion, size, focal, *, surface="cylinder", ref=None, margin=0, max_pixels=MAX_PIXELS):
     """The canvas of a wide pan, as directions: motion a (T - 1, 3, 3) tensor (global_homography's, any device) or a
     Homography (pairs with ok False enter as the identity), size = (H, W) of the frames, focal the focal length in pixels
@@ -3106,7 +3144,7 @@ def wide_transforms(motion, size, focal, *, surface="cylinder", ref=None, margin
     Hc * Wc > max_pixels."""
     import numpy as np
     torch = _torch()
-    A, dev = _pair_homographies(motion)
+    A, dev = _pair_motions(_checked_motion(motion, Homography))
     H, W = _check_canvas(size)
     f = _check_focal(focal)
     _check_surface(surface)
@@ -3114,55 +3152,20 @@ def wide_transforms(motion, size, focal, *, surface="cylinder", ref=None, margin
     ref = _check_ref(ref, T)
     _int_at_least("margin", margin, 0)
     _int_at_least("max_pixels", max_pixels, 1)
-    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
-    K = np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
-    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
-    border = np.concatenate([np.stack([xs, np.zeros(W)]), np.stack([xs, np.full(W, H - 1.0)]),
-                             np.stack([np.zeros(H), ys]), np.stack([np.full(H, W - 1.0), ys])], axis=1)
-    pts = np.vstack([np.concatenate([[[cx], [cy]], border], axis=1), np.ones((1, 1 + border.shape[1]))])  # centre first
-
-    def unit(m):
-        d = np.linalg.det(m)
-        if not (np.isfinite(d) and d > 0):
-            raise ValueError("a motion along the chain has a determinant that is not finite and > 0: it mirrors the image or is "
-                             "singular")
-        return m / np.cbrt(d)
-
-    to_ref = [np.eye(3)] * T
+    K, pts = _camera(f, H, W), _centre_and_border(H, W)
+    to_ref, from_ref = _chain(A, ref, _over_det, "no canvas")
     with np.errstate(all="ignore"):
-        try:
-            for t in range(ref - 1, -1, -1):
-                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
-            for t in range(ref + 1, T):
-                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
-            from_ref = [np.linalg.inv(m) for m in to_ref]
-        except np.linalg.LinAlgError:
-            raise ValueError("the camera path is singular: no canvas") from None
         Ki = np.linalg.inv(K)
-        rays = np.stack([Ki @ (m @ pts) for m in to_ref])  # (T, 3, 1 + border)
-        theta = np.arctan2(rays[:, 0], rays[:, 2])
-        rho = np.hypot(rays[:, 0], rays[:, 2])
-        v = rays[:, 1] / rho if surface == "cylinder" else np.arctan2(rays[:, 1], rho)
-        if not (np.isfinite(theta).all() and np.isfinite(v).all() and np.isfinite(np.array(from_ref)).all()):
+        theta, v, _ = _directions(np.stack([Ki @ (m @ pts) for m in to_ref]), surface, ref)
+        if not np.isfinite(np.array(from_ref)).all():
             raise ValueError("the bounds of the canvas are not finite")
-        two_pi = 2.0 * math.pi
-        centre = theta[:, 0].copy()
-        for order in (range(ref + 1, T), range(ref - 1, -1, -1)):
-            for t in order:
-                near = centre[t - 1] if t > ref else centre[t + 1]
-                centre[t] = centre[t] - two_pi * np.round((centre[t] - near) / two_pi)
-        theta = theta - two_pi * np.round((theta - centre[:, None]) / two_pi)
-        if not theta.max() - theta.min() < two_pi:
+        if not theta.max() - theta.min() < 2.0 * math.pi:
             raise ValueError("the pan spans %.1f degrees: a canvas holds less than 360" % math.degrees(theta.max() - theta.min()))
-        x0, y0 = math.floor(theta.min() * f) - margin, math.floor(v.min() * f) - margin
-        Wc, Hc = math.ceil(theta.max() * f) + margin - x0 + 1, math.ceil(v.max() * f) + margin - y0 + 1
-        if Hc * Wc > max_pixels:
-            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
+        x0, Wc = _pan_columns(theta, f, margin)
+        y0, Hc, rows = _canvas_rows(v, f, surface, margin, Wc, max_pixels)
         th = (x0 + np.arange(Wc, dtype=np.float64)) / f
-        vv = (y0 + np.arange(Hc, dtype=np.float64)) / f
         cols = np.stack([np.sin(th), np.cos(th)], axis=1)
-        rows = np.stack([vv, np.ones(Hc)], axis=1) if surface == "cylinder" else np.stack([np.sin(vv), np.cos(vv)], axis=1)
-        M = np.stack([unit(m @ K) for m in from_ref])[None]
+        M = np.stack([_over_det(m @ K) for m in from_ref])[None]
     if not np.isfinite(M).all():
         raise ValueError("the bounds of the canvas are not finite")
     return (torch.from_numpy(M).to(dev), torch.from_numpy(cols).to(dev), torch.from_numpy(rows).to(dev), (Hc, Wc),
@@ -3180,40 +3183,19 @@ def panorama_wide(frames, pyramidLevels, *, focal=None, surface="cylinder", mode
     canvas pixel (0, 0) -- and focal, cols (Wc, 2), rows (Hc, 2): the canvas' tables.  A pan of 360 degrees or more is refused
     and a full circle does not close (no bundle adjustment); one focal length for all frames, no lens distortion, no parallax
     (README).  Every argument error raises before anything is launched."""
-    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    p = _panorama_head(frames, pyramidLevels, solver, mode, ref, step, margin, masks, layout, out_dtype, exposure)
     iters, scale = _check_irls(iters, scale)
-    (T, H, W, C), _, _ = descs[0]
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
     _check_surface(surface)
     if focal is not None:
         focal = _check_focal(focal)
-    ref = _check_ref(ref, T)
-    _int_at_least("step", step, 1)
-    _int_at_least("margin", margin, 0)
-    dev = ts[0].device
-    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
-    picked = list(range(0, T, step))
-    if not isinstance(exposure, bool):
-        raise TypeError("exposure must be True or False, got %r" % (exposure,))
-    if exposure and len(picked) > MAX_OVERLAP:
-        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
-                         % (step, len(picked), MAX_OVERLAP))
-    _check_slots(mode, len(picked), "step = %d deposits" % step)
-    flow, _, timing = _run(ts, descs, True, T - 1, layout, _torch().float64, pyramidLevels, params)
+    (T, H, W, _), _, _ = p.descs[0]
+    flow, _, timing = _run(p.ts, p.descs, True, T - 1, layout, _torch().float64, pyramidLevels, p.params)
     mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
     if focal is None:
         focal = estimate_focal(mo, (H, W))
-    M, cols, rows, (Hc, Wc), origin = wide_transforms(mo, (H, W), focal, surface=surface, ref=ref, margin=margin)
-    src = _torch().tensor([picked], dtype=_torch().int32, device=dev)
-    gains = None
-    if exposure:
-        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, rays=(cols, rows))
-        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
-    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
-                           rays=(cols, rows))
-    return WidePanorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0],
-                        focal, cols, rows)
+    M, cols, rows, size, origin = wide_transforms(mo, (H, W), focal, surface=surface, ref=p.ref, margin=margin)
+    image, count, gains = _panorama_tail(p, _RAYS, M, size, (cols, rows))
+    return WidePanorama(image, count, M[0], origin, mo.motion, mo.ok, flow, timing, gains, focal, cols, rows)
 
 
 # ---- bundle adjustment for a camera that rotates (include/papof.h: papof_bundle_sums_tensor)
@@ -3293,31 +3275,16 @@ def chain_rotations(motion, size, focal, *, ref=None):
     the reference camera at K R_t d; R_ref is the identity.  The start of bundle_adjust."""
     import numpy as np
     torch = _torch()
-    A, dev = _pair_homographies(motion)
+    A, dev = _pair_motions(_checked_motion(motion, Homography))
     H, W = _check_canvas(size)
     f = _check_focal(focal)
     T = A.shape[0] + 1
     ref = _check_ref(ref, T)
-    K = np.array([[f, 0.0, (W - 1) / 2.0], [0.0, f, (H - 1) / 2.0], [0.0, 0.0, 1.0]])
+    K = _camera(f, H, W)
     Ki = np.linalg.inv(K)
-
-    def unit(m):
-        d = np.linalg.det(m)
-        if not (np.isfinite(d) and d > 0):
-            raise ValueError("a motion along the chain has a determinant that is not finite and > 0: it mirrors the image or is "
-                             "singular")
-        return m / np.cbrt(d)
-
-    to_ref = [np.eye(3)] * T
+    _, from_ref = _chain(A, ref, _over_det, "no rotations")
     with np.errstate(all="ignore"):
-        try:
-            for t in range(ref - 1, -1, -1):
-                to_ref[t] = unit(to_ref[t + 1] @ unit(A[t]))
-            for t in range(ref + 1, T):
-                to_ref[t] = unit(to_ref[t - 1] @ unit(np.linalg.inv(unit(A[t - 1]))))
-            G = np.stack([Ki @ np.linalg.inv(m) @ K for m in to_ref])
-        except np.linalg.LinAlgError:
-            raise ValueError("the camera path is singular: no rotations") from None
+        G = np.stack([Ki @ m @ K for m in from_ref])
     if not np.isfinite(G).all():
         raise ValueError("the camera path is not finite")
     return torch.from_numpy(np.stack([_nearest_rotation(g) for g in G])).to(dev)
@@ -3337,6 +3304,15 @@ def _link_overlap(R, H, W, f):
     return inside.mean(-1)
 
 
+def _check_link_bounds(min_overlap, max_links):
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)):
+        raise TypeError("min_overlap must be a number, got %r" % (min_overlap,))
+    if not 0 < min_overlap <= 1:
+        raise ValueError("min_overlap must be in (0, 1], got %r" % (min_overlap,))
+    if max_links is not None:
+        _int_at_least("max_links", max_links, 1)
+
+
 def bundle_links(rotations, size, focal, *, min_overlap=0.3, max_links=None):
     """The frame pairs that a bundle adjustment joins: rotations (T, 3, 3) (chain_rotations', any device), size = (H, W) of the
     frames, focal in pixels.  On the host in float64.  The pair (i, j), i < j, is a link when at least `min_overlap` (in (0,
@@ -3348,12 +3324,7 @@ def bundle_links(rotations, size, focal, *, min_overlap=0.3, max_links=None):
     R, _ = _check_rotations("rotations", rotations)
     H, W = _check_canvas(size)
     f = _check_focal(focal)
-    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)):
-        raise TypeError("min_overlap must be a number, got %r" % (min_overlap,))
-    if not 0 < min_overlap <= 1:
-        raise ValueError("min_overlap must be in (0, 1], got %r" % (min_overlap,))
-    if max_links is not None:
-        _int_at_least("max_links", max_links, 1)
+    _check_link_bounds(min_overlap, max_links)
     T = R.shape[0]
     if T < 2:
         raise ValueError("rotations must hold at least 2 frames, got %d" % T)
@@ -3579,8 +3550,7 @@ def bundle_adjust(flow, links, rotations, focal, *, occlusion=None, iters=10, sc
     f = _check_focal(focal)
     _int_at_least("iters", iters, 1)
     ref = _check_ref(ref, T)
-    if not isinstance(fix_focal, bool):
-        raise TypeError("fix_focal must be True or False, got %r" % (fix_focal,))
+    _check_bool("fix_focal", fix_focal)
     seen = np.zeros(T, bool)
     seen[links.reshape(-1)] = True
     if not seen.all():
@@ -3618,42 +3588,20 @@ def bundle_transforms(rotations, size, focal, *, surface="cylinder", ref=None, m
     ref = _check_ref(ref, T)
     _int_at_least("margin", margin, 0)
     _int_at_least("max_pixels", max_pixels, 1)
-    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
-    K = np.array([[f, 0.0, cx], [0.0, f, cy], [0.0, 0.0, 1.0]])
-    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
-    border = np.concatenate([np.stack([xs, np.zeros(W)]), np.stack([xs, np.full(W, H - 1.0)]),
-                             np.stack([np.zeros(H), ys]), np.stack([np.full(H, W - 1.0), ys])], axis=1)
-    pts = np.vstack([np.concatenate([[[cx], [cy]], border], axis=1), np.ones((1, 1 + border.shape[1]))])  # centre first
+    K = _camera(f, H, W)
+    two_pi = 2.0 * math.pi
     with np.errstate(all="ignore"):
-        rays = R.transpose(0, 2, 1) @ (np.linalg.inv(K) @ pts)  # (T, 3, 1 + border)
-        theta = np.arctan2(rays[:, 0], rays[:, 2])
-        rho = np.hypot(rays[:, 0], rays[:, 2])
-        v = rays[:, 1] / rho if surface == "cylinder" else np.arctan2(rays[:, 1], rho)
-        if not (np.isfinite(theta).all() and np.isfinite(v).all()):
-            raise ValueError("the bounds of the canvas are not finite")
-        two_pi = 2.0 * math.pi
-        centre = theta[:, 0].copy()
-        for order in (range(ref + 1, T), range(ref - 1, -1, -1)):
-            for t in order:
-                near = centre[t - 1] if t > ref else centre[t + 1]
-                centre[t] = centre[t] - two_pi * np.round((centre[t] - near) / two_pi)
-        theta = theta - two_pi * np.round((theta - centre[:, None]) / two_pi)
-        y0 = math.floor(v.min() * f) - margin
-        Hc = math.ceil(v.max() * f) + margin - y0 + 1
-        if theta.max() - theta.min() < two_pi:
-            x0 = math.floor(theta.min() * f) - margin
-            Wc = math.ceil(theta.max() * f) + margin - x0 + 1
-            th0 = x0 / f
-            th = (x0 + np.arange(Wc, dtype=np.float64)) / f
+        theta, v, centre = _directions(R.transpose(0, 2, 1) @ (np.linalg.inv(K) @ _centre_and_border(H, W)), surface, ref)
+        full = not theta.max() - theta.min() < two_pi
+        if full:
+            Wc, th0 = int(round(two_pi * f)), float(centre[ref]) - math.pi
         else:
-            Wc = int(round(two_pi * f))
-            th0 = float(centre[ref]) - math.pi
-            th = th0 + np.arange(Wc, dtype=np.float64) * (two_pi / Wc)
-        if Hc * Wc > max_pixels:
-            raise ValueError("the canvas is %d x %d, more than max_pixels = %d" % (Hc, Wc, max_pixels))
-        vv = (y0 + np.arange(Hc, dtype=np.float64)) / f
+            x0, Wc = _pan_columns(theta, f, margin)
+            th0 = x0 / f
+        y0, Hc, rows = _canvas_rows(v, f, surface, margin, Wc, max_pixels)
+        cells = np.arange(Wc, dtype=np.float64)
+        th = th0 + cells * (two_pi / Wc) if full else (x0 + cells) / f
         cols = np.stack([np.sin(th), np.cos(th)], axis=1)
-        rows = np.stack([vv, np.ones(Hc)], axis=1) if surface == "cylinder" else np.stack([np.sin(vv), np.cos(vv)], axis=1)
         M = (K @ R / np.cbrt(f * f))[None]
     if not np.isfinite(M).all():
         raise ValueError("the bounds of the canvas are not finite")
@@ -3684,37 +3632,19 @@ def panorama_bundle(frames, pyramidLevels, *, focal=None, surface="cylinder", mo
     parallax, a few hundred frames at most (README).  Every argument error raises before anything is launched."""
     import numpy as np
     torch = _torch()
-    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    p = _panorama_head(frames, pyramidLevels, solver, mode, ref, step, margin, masks, layout, out_dtype, exposure)
     iters, scale = _check_irls(iters, scale)
-    (T, H, W, C), _, _ = descs[0]
-    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
-    _check_mode(mode)
     _check_surface(surface)
     if focal is not None:
         focal = _check_focal(focal)
-    ref = _check_ref(ref, T)
-    _int_at_least("step", step, 1)
-    _int_at_least("margin", margin, 0)
     _int_at_least("bundle_iters", bundle_iters, 1)
     _int_at_least("link_levels", link_levels, 1)
     _int_at_least("bundle_step", bundle_step, 1)
-    if max_links is not None:
-        _int_at_least("max_links", max_links, 1)
-    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float)):
-        raise TypeError("min_overlap must be a number, got %r" % (min_overlap,))
-    if not 0 < min_overlap <= 1:
-        raise ValueError("min_overlap must be in (0, 1], got %r" % (min_overlap,))
-    if not isinstance(fix_focal, bool):
-        raise TypeError("fix_focal must be True or False, got %r" % (fix_focal,))
+    _check_link_bounds(min_overlap, max_links)
+    _check_bool("fix_focal", fix_focal)
+    ts, descs, params, ref = p.ts, p.descs, p.params, p.ref
+    (T, H, W, _), _, _ = descs[0]
     dev = ts[0].device
-    m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
-    picked = list(range(0, T, step))
-    if not isinstance(exposure, bool):
-        raise TypeError("exposure must be True or False, got %r" % (exposure,))
-    if exposure and len(picked) > MAX_OVERLAP:
-        raise ValueError("step = %d deposits %d sources per output, exposure=True takes 1 .. %d: the video needs a larger step"
-                         % (step, len(picked), MAX_OVERLAP))
-    _check_slots(mode, len(picked), "step = %d deposits" % step)
     flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, params)
     mo = _homography_fit(flow, capi.DTYPE_F64, None, iters, scale)
     if focal is None:
@@ -3736,13 +3666,7 @@ def panorama_bundle(frames, pyramidLevels, *, focal=None, surface="cylinder", mo
         flows = both
     b = bundle_adjust(flows, links, R0, focal, occlusion=occ, iters=bundle_iters, scale=scale, step=bundle_step, ref=ref,
                       fix_focal=fix_focal)
-    M, cols, rows, (Hc, Wc), origin = bundle_transforms(b.rotations, (H, W), b.focal, surface=surface, ref=ref, margin=margin)
-    src = torch.tensor([picked], dtype=torch.int32, device=dev)
-    gains = None
-    if exposure:
-        ov = _mosaic_overlap(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, 2, 1.0, rays=(cols, rows))
-        gains = exposure_gains(ov, anchor=picked.index(ref) if ref in picked else None)
-    image, count = _mosaic(ts, descs, src, M[:, ::step], capi.DTYPE_F64, m, Hc, Wc, mode, layout, out_dtype, gains=gains,
-                           rays=(cols, rows))
-    return BundlePanorama(image[0], count[0], M[0], origin, mo.motion, mo.ok, flow, timing, None if gains is None else gains[0],
-                          b.focal, cols, rows, b.rotations, links, b.cost)
+    M, cols, rows, size, origin = bundle_transforms(b.rotations, (H, W), b.focal, surface=surface, ref=ref, margin=margin)
+    image, count, gains = _panorama_tail(p, _RAYS, M, size, (cols, rows))
+    return BundlePanorama(image, count, M[0], origin, mo.motion, mo.ok, flow, timing, gains, b.focal, cols, rows, b.rotations,
+                          links, b.cost)

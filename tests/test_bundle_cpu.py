@@ -149,6 +149,31 @@ def test_argument_errors_before_any_launch(stub, monkeypatch, call, exc):
     assert stub == []
 
 
+@pytest.mark.parametrize("name", ["panorama", "panorama_homography", "panorama_wide", "panorama_bundle"])
+@pytest.mark.parametrize("kw,exc,says", [
+    (dict(mode="max"), ValueError, "mode must be one of"),
+    (dict(ref=3), ValueError, "ref must be None or a frame index in 0 .. 2"), (dict(ref=True), ValueError, "ref must be"),
+    (dict(step=0), ValueError, "step must be an integer >= 1"), (dict(step=2.0), ValueError, "step must be an integer >= 1"),
+    (dict(margin=-1), ValueError, "margin must be an integer >= 0"),
+    (dict(masks=_z(3, 8, 8)), TypeError, "masks must be torch.bool or torch.uint8"),
+    (dict(masks=_z(2, 8, 8, dtype=torch.bool)), ValueError, r"masks must be \(N, H, W\) = \(3, 8, 8\)"),
+    (dict(iters=0), ValueError, "iters must be an integer >= 1"), (dict(scale=0.0), ValueError, "scale must be finite and > 0"),
+    (dict(scale="1"), TypeError, "scale must be a number"),
+    (dict(out_dtype=torch.int32), TypeError, "out_dtype must be"), (dict(layout="CHW"), ValueError, "layout must be one of"),
+    (dict(bogus=1), TypeError, "bogus"), (dict(exposure=1), TypeError, "exposure must be True or False, got 1"),
+    (dict(frames=_z(1, 3, 8, 8)), ValueError, "frames needs at least 2 frames, got 1"),
+    (dict(frames=_z(65, 3, 8, 8)), ValueError, r'step = 1 deposits 65 sources per output, mode="median" takes 1 .. 64'),
+])
+def test_the_four_panoramas_share_their_argument_errors(stub, monkeypatch, name, kw, exc, says):
+    """every argument that the four panoramas have in common is refused by each of them, in the same words, before anything
+    is launched"""
+    monkeypatch.setattr(tensors, "_launch", lambda *a, **k: stub.append("launch"))
+    kw = dict(kw)
+    with pytest.raises(exc, match=says):
+        getattr(tensors, name)(kw.pop("frames", _z(3, 3, 8, 8)), 2, **kw)
+    assert stub == []
+
+
 def test_the_named_tuples():
     assert tensors.Bundle._fields == ("rotations", "focal", "cost", "accepted", "support", "ok")
     assert tensors.BundlePanorama._fields == tensors.WidePanorama._fields + ("rotations", "links", "cost")

@@ -256,7 +256,7 @@ def test_mosaic_is_the_restatements_bytes(N):
             ts, descs, _, _ = tensors._check([("frames", t)], "NHWC", None, 1)
             out, none = tensors._mosaic(ts, descs, torch.from_numpy(src).to(torch.int32).cuda(), tm, tensors.capi.DTYPE_F64,
                                         None if masks is None else tmk.view(torch.uint8), HC, WC, mode, "NHWC", torch.float32,
-                                        count=False, gains=kw["gains"], projective=True)
+                                        count=False, gains=kw["gains"], rule=tensors._PROJECTIVE)
             assert none is None
             _same_bytes(out, want, "NHWC", what + " no count")
     assert torch.equal(t, before[0]) and torch.equal(tm.view(torch.int64), before[1].view(torch.int64))

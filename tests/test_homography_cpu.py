@@ -397,7 +397,7 @@ def test_the_projective_calls_accept_the_bounds_of_their_slots(monkeypatch):
 
 
 def test_the_count_less_call_passes_a_null_count(monkeypatch):
-    """_mosaic(count=False, projective=True): the projective entry point with count NULL, and None returned for it"""
+    """_mosaic(count=False, rule=_PROJECTIVE): the projective entry point with count NULL, and None returned for it"""
     _on_gpu_stub(monkeypatch)
     reached = []
     monkeypatch.setattr(tensors, "_launch", lambda dev, name, *args, **kw: reached.append((name, args[-1])))
@@ -405,7 +405,7 @@ def test_the_count_less_call_passes_a_null_count(monkeypatch):
     ts, descs, _, _ = tensors._check([("frames", f)], "NHWC", None, 1)
     for mode in ("first", "mean", "median", "feather"):
         out, cnt = tensors._mosaic(ts, descs, torch.zeros(1, 3, dtype=torch.int32), _M(), capi.DTYPE_F64, None, 4, 5, mode, "NHWC",
-                                   torch.float32, count=False, projective=True)
+                                   torch.float32, count=False, rule=tensors._PROJECTIVE)
         assert cnt is None and tuple(out.shape) == (1, 4, 5, 3)
     assert reached == [("papof_mosaic_projective_tensor", None)] * 4
 

@@ -347,6 +347,45 @@ def test_the_ray_calls_reach_their_entry_points_with_the_tables_lengths(monkeypa
     assert (d.stride[0], d.stride[1], d.dtype) == (8, 1, capi.DTYPE_F64) and tensors._table_struct(cols).dtype == capi.DTYPE_F32
 
 
+def test_every_rule_reaches_its_entry_point_with_its_argument_list(monkeypatch):
+    """the three rules' mosaics and overlaps, with and without gains, under "first" and "feather": which C symbol is reached,
+    how many arguments it gets behind the handle, and the two tables behind the matrices (positions 12 and 13) for the ray rule
+    alone -- the descriptor of a (Wc, 2) and an (Hc, 2) table there, the gains or the step otherwise"""
+    _on_gpu_stub(monkeypatch)
+    reached = []
+    monkeypatch.setattr(tensors, "_launch", lambda dev, name, *args, **kw: reached.append((name, args)))
+    f, g = _z(3, 3, 8, 8), torch.ones(1, 3, dtype=torch.float64)
+    cols, rows = _z(7, 2, dtype=torch.float64) + 2.0, _z(5, 2, dtype=torch.float64) + 3.0
+    for blend, overlap, stem, mats, canvas in (
+            (tensors.mosaic, tensors.mosaic_overlap, "", _z(1, 3, 2, 3, dtype=torch.float64), ((5, 7),)),
+            (tensors.mosaic_homography, tensors.mosaic_overlap_homography, "_projective", _M(), ((5, 7),)),
+            (tensors.mosaic_rays, tensors.mosaic_overlap_rays, "_ray", _M(), (cols, rows))):
+        ray = stem == "_ray"
+        for gains, mode in ((None, "first"), (None, "feather"), (g, "first"), (g, "feather")):
+            del reached[:]
+            blend(f, None, mats, *canvas, mode=mode, gains=gains)
+            overlap(f, None, mats, *canvas)
+            (name, args), (oname, oargs) = reached
+            want = "papof_mosaic%s_tensor" % (stem or "_blend")
+            if not stem and gains is None and mode == "first":  # the one special case: the call without gains or weights
+                want = "papof_mosaic_tensor"
+            what = (blend.__name__, gains is not None, mode)
+            assert name == want and oname == "papof_mosaic_overlap%s_tensor" % stem, what
+            assert len(args) == (15 if name == "papof_mosaic_tensor" else 16) + 2 * ray and len(oargs) == 16 + 2 * ray, what
+            assert args[:4] == oargs[:4] == (3, 8, 8, 3) and args[6:10] == oargs[6:10] == (1, 3, 5, 7), what
+            for a in (args, oargs):
+                assert a[11]._obj.data == mats.data_ptr(), what
+                if ray:
+                    assert (a[12]._obj.data, a[13]._obj.data) == (cols.data_ptr(), rows.data_ptr()), what
+            behind = 12 + 2 * ray
+            assert oargs[behind] == 2 and oargs[behind + 1].value == 1.0, what                     # step, bound
+            if name == "papof_mosaic_tensor":
+                assert args[behind] == tensors.MOSAIC_MODES[mode], what
+            else:
+                assert (args[behind] is None) == (gains is None) and args[behind + 1] == tensors.MOSAIC_MODES[mode], what
+                assert gains is None or args[behind]._obj.data == g.data_ptr(), what
+
+
 @pytest.mark.parametrize("kw,exc", [
     (dict(motion=torch.zeros(4, 2, 3)), ValueError), (dict(motion=torch.zeros(0, 3, 3)), ValueError), (dict(motion=[1]), TypeError),
     (dict(size=(8,)), TypeError), (dict(size=(0, 8)), ValueError),
