@@ -1110,6 +1110,49 @@ int papof_match_tensor(papof_handle* h, int n_pairs, int sequence, const papof_t
  * mode and 2 n_pairs otherwise; -1 where that call refuses the sizes. */
 long long papof_match_workspace(int n_pairs, int sequence, int height, int width, int stride);
 
+/* Hierarchical block matching (match.hip): papof_match_tensor's search carried from a coarse level down, so that the reach
+ * is stride * 2^(levels - 1) * search pixels plus the refinements, at a fraction of the flat search's candidates.  Integer
+ * arithmetic throughout: the result is a pure function of the inputs (tests/_hmatch_ref.py restates it).  The frames,
+ * sequence, c, patch, search, penalty, both, disp, cost and stream are papof_match_tensor's; levels L in 1 .. 4, refine r
+ * in 1 .. 3.
+ * Levels.  Level l (0 = finest) has the stride S_l = stride * 2^l and the grid h_l x w_l = height / S_l x width / S_l.
+ * The frames of level l are the quantised frames decimated by S_l DIRECTLY, by papof_match_tensor's rule
+ * (sum of the S_l x S_l samples + S_l * S_l / 2) / (S_l * S_l) -- not a decimation of level l - 1.  S_(L-1) <= 32, and the
+ * frame holds at least one cell of the top level.
+ * Top level L - 1.  papof_match_tensor's rule unchanged on its grid, with `search` and `penalty`: d_(L-1) in that level's cells.
+ * Level l < L - 1, cell (x, y).  With the level above h' x w' and clamp(v, n) = min(max(v, 0), n - 1):
+ *     parent           px = min(x >> 1, w' - 1), py = min(y >> 1, h' - 1)
+ *     side neighbour   nx = clamp(px + (x odd ? +1 : -1), w'), ny = clamp(py + (y odd ? +1 : -1), h')
+ *     predictors       2 * d_(l+1) at (px, py), (nx, py), (px, ny), (nx, ny), and the zero vector
+ *     candidates       d = predictor + (ex, ey), |ex|, |ey| <= r
+ * d is admissible iff 0 <= x + dx < w_l and 0 <= y + dy < h_l (d = 0 always is).  cost(p, d) is papof_match_tensor's on grid
+ * l: the clamped-window sum of absolute differences over (2 patch + 1)^2 cells and the channels + penalty * (|dx| + |dy|).
+ * d_l is the admissible candidate with the smallest key (cost, dx * dx + dy * dy, dy, dx), compared lexicographically; a
+ * candidate that several predictors give counts once.
+ * Result.  disp = stride * d_0 and cost = cost_0 on the h_0 x w_0 grid: the shapes, dtypes and meaning of
+ * papof_match_tensor's outputs, so papof_match_densify_tensor takes them as they are.  With levels == 1 the call IS
+ * papof_match_tensor (refine is checked and not used) and returns its bytes.
+ * Bounds.  |d| <= 32 * 8 + 3 * 7 = 277 cells per component at every level and a cost stays below 15 * 15 * 4 * 255 +
+ * 65535 * 554 < 2^26, so the key is held exactly in 26 + 18 + 10 + 10 bits.
+ * When not to use it: a structure smaller than the top level's window (2 patch + 1 cells of stride S_(L-1)) is matched
+ * there with the background around it and the lower levels only refine that; small objects that move far keep levels 1.
+ * workspace: papof_match_hier_workspace's bytes, 4-byte aligned -- the packed frames of every level, then one packed
+ * displacement dword per cell and item of every level above 0.  Enqueued on `stream` (k_match_prepare per level and frame
+ * tensor, k_match on the top level, k_match_refine per lower level from the top down: one block per 32 x 8 tile of cells and
+ * item) and returns without waiting.  The environment variable PAPOF_MATCH_STAGED=0, read per call, makes every tile of
+ * k_match_refine read B through global addresses instead of its LDS window; the bytes are the same.
+ * PAPOF_EINVAL, before anything is enqueued: what papof_match_tensor refuses, levels outside 1 .. 4, refine outside 1 .. 3,
+ * stride * 2^(levels - 1) > 32, height or width < stride * 2^(levels - 1), a workspace below papof_match_hier_workspace. */
+int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2,
+                            int height, int width, int c, int stride, int levels, int patch, int search, int refine, int penalty,
+                            int both, const papof_tensor* disp, const papof_tensor* cost, void* workspace,
+                            long long workspace_bytes, void* stream);
+
+/* Bytes of papof_match_hier_tensor's workspace: with F = n_pairs + 1 frames in sequence mode and 2 n_pairs otherwise,
+ * 4 * (F * sum over l = 0 .. levels - 1 of h_l w_l + 2 n_pairs * sum over l = 1 .. levels - 1 of h_l w_l) -- with levels == 1
+ * papof_match_workspace's; -1 where that call refuses the sizes. */
+long long papof_match_hier_workspace(int n_pairs, int sequence, int height, int width, int stride, int levels);
+
 /* A full-resolution initial flow and its hole mask from matched displacements (k_match_densify, one lane per pixel).
  * disp, disp_rev: float32 / float64, (item, row, column, {dx, dy}) on the h x w grid of papof_match_tensor (h = height /
  * stride, w = width / stride), in full-resolution pixels: the field to densify and the field of the opposite direction.

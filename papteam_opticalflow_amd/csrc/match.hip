@@ -21,11 +21,27 @@
 // consecutive dwords of one LDS row: no bank conflict whatever the row pitch.  The running best is one 64-bit key per lane
 // (cost, dx^2 + dy^2, dy, dx packed from the top), so the order of the visit does not matter.
 // k_match_densify: one lane per full-resolution pixel; the forward-backward test of its cell, the flow and the hole mask.
+//
+// Hierarchical search (papof_match_hier_tensor; tests/_hmatch_ref.py restates it).  k_match_prepare decimates the frames
+// once per level (strides up to 32; from 8 up its sibling k_match_prepare_wide, 16 or 64 lanes per cell), k_match runs on the top level and leaves its displacements as packed dwords (dx in the
+// low half, dy in the high half, two's complement) in the workspace, and k_match_refine<P> takes every lower level from its
+// parents: a block is again a 32 x 8 tile and an item, one lane per cell.  A's tile (halo P) and B's window around the zero
+// predictor (halo P + r) are staged in LDS; the doubled vectors of the tile's parents -- the 16 x 4 parent cells and the
+// ring their side neighbours reach, 19 x 7 with both clamps -- go to LDS too and are reduced to a bounding box with LDS
+// atomics.  Where the box spreads over at most kSpread cells in x and in y the block stages ONE window of B that covers
+// every parent-predicted candidate of the tile and the lanes walk their candidates from LDS: the 2 r + 1 candidates
+// adjacent in dx of a predictor share their register rows as k_match's kG candidates do -- (2 P + 1) + (2 P + 1 + 2 r)
+// LDS reads for (2 r + 1) (2 P + 1) v_sad_u8.  Where it spreads further (a motion boundary crosses the tile) the block reads
+// B through clamped global addresses; the choice is block-uniform and both paths read the same values in the same order,
+// so they give the same bytes (PAPOF_MATCH_STAGED=0 sends every tile down the global path).  kSpread = 16: with P = 7 and
+// r = 3 the three tiles are 1012 + 1456 + 2992 dwords = 21.8 KB, so seven blocks share a CU's 160 KB of LDS.
 #include "sampler.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 
 namespace papof {
 
@@ -35,7 +51,16 @@ constexpr int kTX = 32, kTY = 8;  // the tile of coarse pixels (256 lanes)
 constexpr int kG = 4;             // candidates along dx that a lane evaluates together (1, 8, 16)
 constexpr int kMaxPatch = 7, kMaxSearch = 32, kMaxPenalty = 65535;
 
+constexpr int kMaxLevels = 4, kMaxRefine = 3, kMaxTopStride = 32;
+constexpr int kSpread = 16;           // k_match_refine: the largest spread of the doubled parent vectors that is staged
+constexpr int kRingW = 19, kRingH = 7;  // k_match_refine: the parents of a tile, from (x0 / 2 - 2, y0 / 2 - 2)
+
 inline bool valid_stride(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+
+// a displacement in cells as one dword: dx in the low half, dy in the high half (|d| <= 277 at every level)
+__device__ __forceinline__ unsigned pack_d(int dx, int dy) { return ((unsigned)dx & 0xffffu) | ((unsigned)dy << 16); }
+__device__ __forceinline__ int unpack_dx(unsigned v) { return (int)(short)(v & 0xffffu); }
+__device__ __forceinline__ int unpack_dy(unsigned v) { return (int)(short)(v >> 16); }
 
 // groups of kG candidates that cover dx = -search .. search
 __host__ __device__ inline int groups_of(int search) { return (2 * search + 1 + kG - 1) / kG; }
@@ -81,17 +106,51 @@ __global__ __launch_bounds__(256) void k_match_prepare(const PrepArgs a, long lo
     a.packed[f * cells + cell] = pk;
 }
 
+// The same for the strides of the hierarchical search's upper levels (8 .. 32), where one lane per cell would read up to
+// 1024 x C samples one after the other: G lanes share a cell (G a power of two <= 64, a divisor of stride^2: the lanes of
+// one wave), each sums every G-th sample of the cell in row-major order, and the partial sums meet through the wave's
+// shuffles.  A lane's sums stay below 1024 x 255 < 2^18.  blockIdx.x: 256 / G cells from `cell0` x 256 / G.
+template <int G>
+__global__ __launch_bounds__(256) void k_match_prepare_wide(const PrepArgs a, long long cell0, long long frame0) {
+    const long long cell = (cell0 + blockIdx.x) * (256 / G) + threadIdx.x / G, cells = (long long)a.h * a.w;
+    if (cell >= cells) return;  // (the G lanes of a cell leave together)
+    const int t = (int)threadIdx.x % G, s = a.stride;
+    const long long f = frame0 + blockIdx.y;
+    const int y = (int)(cell / a.w), x = (int)(cell - (long long)y * a.w);
+    const long long base = f * a.in.stride[0] + (long long)y * s * a.in.stride[1] + (long long)x * s * a.in.stride[2];
+    unsigned sum[4] = {0, 0, 0, 0};
+    for (int idx = t; idx < s * s; idx += G) {
+        const int j = idx / s, i = idx - j * s;
+        const long long o = base + j * a.in.stride[1] + i * a.in.stride[2];
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if (c < a.C) sum[c] += quantise(a.in, o + c * a.in.stride[3]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+#pragma unroll
+        for (int m = G / 2; m > 0; m >>= 1) sum[c] += __shfl_xor(sum[c], m);
+    if (t != 0) return;
+    const unsigned area = (unsigned)(s * s);
+    unsigned pk = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) pk |= ((sum[c] + area / 2) / area) << (8 * c);  // (a missing channel: (0 + area / 2) / area = 0)
+    a.packed[f * cells + cell] = pk;
+}
+
 struct MatchArgs {
     const unsigned* packed;  // [frame][h][w]
     papof_tensor disp;       // (item, row, column, {dx, dy})
     papof_tensor cost;       // (item, row, column, -)
     int h, w, stride, search, penalty;
     int n_pairs, seq;
+    unsigned* out;           // k_match<P, true>: [item][h][w] packed displacements in cells, instead of disp and cost
 };
 
 // P: the patch radius.  blockIdx.x: tile `tile0` + x of the grid's 32 x 8 tiles in row-major order; blockIdx.y: item
 // `item0` + y -- items below n_pairs run forward (A the pair's first frame), the others backward.
-template <int P>
+// PACKED: the top level of the hierarchical search -- the match goes to a.out as one packed dword.
+template <int P, bool PACKED = false>
 __global__ __launch_bounds__(kTX* kTY) void k_match(const MatchArgs a, long long tile0, long long item0) {
     extern __shared__ __align__(16) unsigned smem_match[];
     constexpr int WN = 2 * P + 1;
@@ -160,6 +219,10 @@ __global__ __launch_bounds__(kTX* kTY) void k_match(const MatchArgs a, long long
     }
     if (x >= w || y >= h) return;
     const int bdx = (int)(best & 127) - 64, bdy = (int)((best >> 7) & 127) - 64;
+    if constexpr (PACKED) {
+        a.out[item * cells + (long long)y * w + x] = pack_d(bdx, bdy);
+        return;
+    }
     const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
     store(a.disp, od, (double)(a.stride * bdx));
     store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
@@ -208,13 +271,244 @@ bool valid_frame_size(int height, int width, int stride) {
     return valid_stride(stride) && height >= stride && width >= stride && (long long)height * width < (1LL << 30);
 }
 
-template <int P>
+template <int P, bool PACKED = false>
 int launch_match(hipStream_t st, const MatchArgs& a, long long items) {
     const size_t lds = (size_t)lds_bytes(P, a.search);
     const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
     return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(k_match<P>, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
+        hipLaunchKernelGGL((k_match<P, PACKED>), grid, dim3(kTX, kTY), lds, st, a, t0, i0);
     });
+}
+
+// the top level of the hierarchical search
+int launch_match_packed(hipStream_t st, const MatchArgs& a, long long items, int patch) {
+    switch (patch) {
+        case 1: return launch_match<1, true>(st, a, items);
+        case 2: return launch_match<2, true>(st, a, items);
+        case 3: return launch_match<3, true>(st, a, items);
+        case 4: return launch_match<4, true>(st, a, items);
+        case 5: return launch_match<5, true>(st, a, items);
+        case 6: return launch_match<6, true>(st, a, items);
+        default: return launch_match<7, true>(st, a, items);
+    }
+}
+
+// ---- the hierarchical search
+struct RefineArgs {
+    const unsigned* packed;  // the level's frames [frame][h][w]
+    const unsigned* parent;  // [item][h1][w1]: the packed displacements of the level above
+    unsigned* out;           // levels above 0: [item][h][w] packed displacements
+    papof_tensor disp, cost;  // level 0: as MatchArgs
+    int h, w, h1, w1, stride, refine, penalty;
+    int n_pairs, seq, last, staged;
+};
+
+// the sizes of k_match_refine's staged tiles, in dwords: A as k_match's, B around the zero predictor, B under the parents
+__host__ __device__ inline int z_width(int P, int r) { return kTX + 2 * (P + r); }
+__host__ __device__ inline int z_height(int P, int r) { return kTY + 2 * (P + r); }
+
+long long refine_lds_bytes(int P, int r) {
+    return 4LL * (a_width(P) * a_height(P) + z_width(P, r) * z_height(P, r) +
+                  (z_width(P, r) + kSpread) * (z_height(P, r) + kSpread));
+}
+
+// The 2 R + 1 candidates (px - R .. px + R, dy) of every dy = py - R .. py + R around one predictor (px, py), for the
+// cell (x, y) = lane (lx, ly).  STAGED: B's rows come from the LDS window `bw` of pitch `pitch`, whose entry (0, 0) is
+// B(clamp(y0 - P + py - R), clamp(x0 - P + px - R)) for the block's (x0, y0) -- bw already points at the lane's column and
+// row 0; otherwise from B through clamped addresses.  Either way the same values meet the same v_sad_u8 in the same order.
+template <int P, int R, bool STAGED>
+__device__ __forceinline__ void refine_predictor(unsigned long long& best, const unsigned* As, int AW, const unsigned* bw,
+                                                 int pitch, const unsigned* B, int h, int w, int x, int y, int lx, int ly,
+                                                 int px, int py, int penalty) {
+    constexpr int WN = 2 * P + 1, NC = 2 * R + 1;
+#pragma unroll 1
+    for (int eyi = 0; eyi < NC; eyi++) {
+        const int dy = py + eyi - R;
+        unsigned acc[NC];
+#pragma unroll
+        for (int j = 0; j < NC; j++) acc[j] = 0;
+#pragma unroll 1
+        for (int oy = 0; oy < WN; oy++) {
+            const unsigned* const ar = As + (ly + oy) * AW + lx;
+            unsigned av[WN], bv[WN + NC - 1];
+#pragma unroll
+            for (int k = 0; k < WN; k++) av[k] = ar[k];
+            if constexpr (STAGED) {
+                const unsigned* const br = bw + (oy + eyi) * pitch;
+#pragma unroll
+                for (int k = 0; k < WN + NC - 1; k++) bv[k] = br[k];
+            } else {
+                const unsigned* const br = B + (long long)clamp_to(y - P + oy + dy, h) * w;
+#pragma unroll
+                for (int k = 0; k < WN + NC - 1; k++) bv[k] = br[clamp_to(x - P + k + px - R, w)];
+            }
+#pragma unroll
+            for (int k = 0; k < WN; k++)
+#pragma unroll
+                for (int j = 0; j < NC; j++) acc[j] = __builtin_amdgcn_sad_u8(av[k], bv[k + j], acc[j]);
+        }
+        const bool row_in = y + dy >= 0 && y + dy < h;
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            const int dx = px + j - R;
+            const bool ok = row_in && x + dx >= 0 && x + dx < w;
+            const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+            const unsigned long long c = acc[j] + (unsigned)(penalty * (ax + ay));
+            // (cost, dx^2 + dy^2, dy, dx) in 26 + 18 + 10 + 10 bits: |d| <= 277, a cost below 2^26
+            const unsigned long long key = (c << 38) | ((unsigned long long)(unsigned)(dx * dx + dy * dy) << 20) |
+                                           ((unsigned long long)(unsigned)(dy + 512) << 10) | (unsigned long long)(unsigned)(dx + 512);
+            best = ok && key < best ? key : best;
+        }
+    }
+}
+
+// P: the patch radius.  blockIdx as k_match's.  Level l's cells from the packed displacements of level l + 1.
+template <int P>
+__global__ __launch_bounds__(kTX* kTY) void k_match_refine(const RefineArgs a, long long tile0, long long item0) {
+    extern __shared__ __align__(16) unsigned smem_refine[];
+    __shared__ int ring_x[kRingW * kRingH], ring_y[kRingW * kRingH], box[4];
+    const int r = a.refine, h = a.h, w = a.w, h1 = a.h1, w1 = a.w1;
+    const int AW = a_width(P), AH = a_height(P), ZW = z_width(P, r), ZH = z_height(P, r);
+    unsigned* const As = smem_refine;
+    unsigned* const Zs = As + AW * AH;
+    unsigned* const Ws = Zs + ZW * ZH;
+
+    const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
+    const long long tx = (w + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
+    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const int x = x0 + lx, y = y0 + ly;
+    const long long item = item0 + blockIdx.y, cells = (long long)h * w, cells1 = (long long)h1 * w1;
+    const bool back = item >= a.n_pairs;
+    const long long pair = back ? item - a.n_pairs : item;
+    const long long first = pair, second = a.seq ? pair + 1 : a.n_pairs + pair;
+    const unsigned* const A = a.packed + (back ? second : first) * cells;
+    const unsigned* const B = a.packed + (back ? first : second) * cells;
+
+    // ---- the parents' doubled vectors and their bounding box
+    const int rx0 = x0 / 2 - 2, ry0 = y0 / 2 - 2;
+    if (tid == 0) {
+        box[0] = box[2] = 0x7fffffff;
+        box[1] = box[3] = -0x7fffffff;
+    }
+    __syncthreads();
+    if (tid < kRingW * kRingH) {
+        const int ry = tid / kRingW, rx = tid - ry * kRingW;
+        const unsigned v = a.parent[item * cells1 + (long long)clamp_to(ry0 + ry, h1) * w1 + clamp_to(rx0 + rx, w1)];
+        const int vx = 2 * unpack_dx(v), vy = 2 * unpack_dy(v);
+        ring_x[tid] = vx;
+        ring_y[tid] = vy;
+        atomicMin(&box[0], vx);
+        atomicMax(&box[1], vx);
+        atomicMin(&box[2], vy);
+        atomicMax(&box[3], vy);
+    }
+    // ---- stage A's tile and B's window around the zero predictor, every coordinate clamped into the grid
+    for (int c = tid; c < AW * AH; c += kTX * kTY) {
+        const int cy = c / AW, cx = c - cy * AW;
+        As[c] = A[(long long)clamp_to(y0 - P + cy, h) * w + clamp_to(x0 - P + cx, w)];
+    }
+    for (int c = tid; c < ZW * ZH; c += kTX * kTY) {
+        const int cy = c / ZW, cx = c - cy * ZW;
+        Zs[c] = B[(long long)clamp_to(y0 - P - r + cy, h) * w + clamp_to(x0 - P - r + cx, w)];
+    }
+    __syncthreads();
+    const int min_x = box[0], min_y = box[2];
+    const long long spread_x = (long long)box[1] - min_x, spread_y = (long long)box[3] - min_y;
+    const bool staged = a.staged && spread_x <= kSpread && spread_y <= kSpread;  // block-uniform
+    const int WP = ZW + (int)(staged ? spread_x : 0);
+    if (staged) {  // ---- ONE window of B under every parent-predicted candidate of the tile
+        const int WH = ZH + (int)spread_y;
+        for (int c = tid; c < WP * WH; c += kTX * kTY) {
+            const int cy = c / WP, cx = c - cy * WP;
+            Ws[c] = B[(long long)clamp_to(y0 - P - r + min_y + cy, h) * w + clamp_to(x0 - P - r + min_x + cx, w)];
+        }
+        __syncthreads();
+    }
+
+    // ---- the lane's predictors: its parent, the side neighbours in x, in y and in both, and zero
+    const int px = min(x >> 1, w1 - 1), py = min(y >> 1, h1 - 1);
+    const int nx = clamp_to(px + ((x & 1) ? 1 : -1), w1), ny = clamp_to(py + ((y & 1) ? 1 : -1), h1);
+    const int ipx = clamp_to(px - rx0, kRingW), inx = clamp_to(nx - rx0, kRingW);
+    const int ipy = clamp_to(py - ry0, kRingH), iny = clamp_to(ny - ry0, kRingH);
+    unsigned long long best = ~0ULL;
+#pragma unroll 1
+    for (int k = 0; k < 5; k++) {
+        const int ri = (k & 2 ? iny : ipy) * kRingW + (k & 1 ? inx : ipx);
+        const int vx = k == 4 ? 0 : ring_x[ri], vy = k == 4 ? 0 : ring_y[ri];
+        const bool lds = k == 4 || staged;
+        const unsigned* const bw = k == 4 ? Zs + ly * ZW + lx : staged ? Ws + (ly + vy - min_y) * WP + lx + (vx - min_x) : Zs;
+        const int pitch = k == 4 ? ZW : WP;
+#define PAPOF_REFINE(R)                                                                                                  \
+    if (lds)                                                                                                             \
+        refine_predictor<P, R, true>(best, As, AW, bw, pitch, B, h, w, x, y, lx, ly, vx, vy, a.penalty);                 \
+    else                                                                                                                 \
+        refine_predictor<P, R, false>(best, As, AW, bw, pitch, B, h, w, x, y, lx, ly, vx, vy, a.penalty)
+        if (r == 1) {
+            PAPOF_REFINE(1);
+        } else if (r == 2) {
+            PAPOF_REFINE(2);
+        } else {
+            PAPOF_REFINE(3);
+        }
+#undef PAPOF_REFINE
+    }
+    if (x >= w || y >= h) return;
+    const int bdx = (int)(best & 1023) - 512, bdy = (int)((best >> 10) & 1023) - 512;
+    if (!a.last) {
+        a.out[item * cells + (long long)y * w + x] = pack_d(bdx, bdy);
+        return;
+    }
+    const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    store(a.disp, od, (double)(a.stride * bdx));
+    store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
+    store(a.cost, item * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2],
+          (double)(best >> 38));
+}
+
+template <int P>
+int launch_refine(hipStream_t st, const RefineArgs& a, long long items) {
+    const size_t lds = (size_t)refine_lds_bytes(P, a.refine);
+    const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
+    return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
+        hipLaunchKernelGGL(k_match_refine<P>, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
+    });
+}
+
+// k_match_prepare of both frame tensors at one stride, into `packed` ([frame][h][w], the first tensor's frames first)
+// (the hierarchical call's: strides from 8 up go to k_match_prepare_wide; papof_match_tensor launches what it always did)
+int launch_prepare(hipStream_t st, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2, int height,
+                   int width, int c, int stride, unsigned* packed) {
+    PrepArgs p{};
+    p.h = height / stride;
+    p.w = width / stride;
+    p.C = c;
+    p.stride = stride;
+    const long long cells = (long long)p.h * p.w, blocks = (cells + 255) / 256;
+    const long long n_first = sequence ? (long long)n_pairs + 1 : n_pairs;
+    for (int k = 0; k < (sequence ? 1 : 2); k++) {
+        p.in = k == 0 ? *frames : *frames2;
+        p.packed = packed + (k == 0 ? 0 : n_first * cells);
+        const long long n = k == 0 ? n_first : n_pairs;
+        if (stride >= 16)
+            PAPOF_TRY(launch_tiles((cells + 3) / 4, n, [&](dim3 grid, long long c0, long long f0) {
+                hipLaunchKernelGGL(k_match_prepare_wide<64>, grid, dim3(256), 0, st, p, c0, f0);
+            }));
+        else if (stride == 8)
+            PAPOF_TRY(launch_tiles((cells + 15) / 16, n, [&](dim3 grid, long long c0, long long f0) {
+                hipLaunchKernelGGL(k_match_prepare_wide<16>, grid, dim3(256), 0, st, p, c0, f0);
+            }));
+        else
+            PAPOF_TRY(launch_tiles(blocks, n, [&](dim3 grid, long long c0, long long f0) {
+                hipLaunchKernelGGL(k_match_prepare, grid, dim3(256), 0, st, p, c0, f0);
+            }));
+    }
+    return PAPOF_OK;
+}
+
+bool valid_hier(int height, int width, int stride, int levels) {
+    if (levels < 1 || levels > kMaxLevels || !valid_frame_size(height, width, stride)) return false;
+    const int top = stride << (levels - 1);
+    return top <= kMaxTopStride && height >= top && width >= top;
 }
 
 }  // namespace
@@ -286,6 +580,104 @@ extern "C" int papof_match_tensor(papof_handle* h, int n_pairs, int sequence, co
         case 6: return launch_match<6>(st, a, items);
         default: return launch_match<7>(st, a, items);
     }
+}
+
+extern "C" long long papof_match_hier_workspace(int n_pairs, int sequence, int height, int width, int stride, int levels) {
+    if (n_pairs < 1 || height < 1 || width < 1 || !valid_hier(height, width, stride, levels)) return -1;
+    const long long frames = sequence ? (long long)n_pairs + 1 : 2LL * n_pairs;
+    long long dwords = 0;
+    for (int l = 0; l < levels; l++) {
+        const long long cells = (long long)(height / (stride << l)) * (width / (stride << l));
+        const long long per = frames + (l > 0 ? 2LL * n_pairs : 0);  // the frames; above level 0 a displacement per item too
+        if (per > ((1LL << 60) - dwords) / cells) return -1;
+        dwords += per * cells;
+    }
+    return 4 * dwords;
+}
+
+extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                       const papof_tensor* frames2, int height, int width, int c, int stride, int levels, int patch,
+                                       int search, int refine, int penalty, int both, const papof_tensor* disp,
+                                       const papof_tensor* cost, void* workspace, long long workspace_bytes, void* stream) {
+    if (!h || refine < 1 || refine > kMaxRefine) return PAPOF_EINVAL;
+    const long long need = papof_match_hier_workspace(n_pairs, sequence, height, width, stride, levels);
+    if (need < 0) return PAPOF_EINVAL;
+    if (levels == 1)
+        return papof_match_tensor(h, n_pairs, sequence, frames, frames2, height, width, c, stride, patch, search, penalty, both, disp,
+                                  cost, workspace, workspace_bytes, stream);
+    if (c < 1 || c > 4 || patch < 1 || patch > kMaxPatch || search < 1 || search > kMaxSearch || penalty < 0 || penalty > kMaxPenalty)
+        return PAPOF_EINVAL;
+    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    if (!described(frames, I, {0, 1, 2, 3}, false) || (!sequence && !described(frames2, I, {0, 1, 2, 3}, false)))
+        return PAPOF_EINVAL;
+    if (!described(disp, F, {0, 1, 2, 3}, true) || !described(cost, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 3) || workspace_bytes < need) return PAPOF_EINVAL;
+    const char* const env = std::getenv("PAPOF_MATCH_STAGED");
+    const int staged = !(env && std::strcmp(env, "0") == 0);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PAPOF_HIP(hipSetDevice(h->device));
+
+    // the workspace: the packed frames of levels 0 .. levels - 1, then the packed displacements of levels 1 .. levels - 1
+    const long long n_frames = sequence ? (long long)n_pairs + 1 : 2LL * n_pairs, items = both ? 2LL * n_pairs : n_pairs;
+    unsigned* packed[kMaxLevels];
+    unsigned* field[kMaxLevels] = {};
+    unsigned* at = static_cast<unsigned*>(workspace);
+    for (int l = 0; l < levels; l++) {
+        packed[l] = at;
+        at += n_frames * (height / (stride << l)) * (width / (stride << l));
+    }
+    for (int l = 1; l < levels; l++) {
+        field[l] = at;
+        at += 2LL * n_pairs * (height / (stride << l)) * (width / (stride << l));
+    }
+    for (int l = 0; l < levels; l++)
+        PAPOF_TRY(launch_prepare(st, n_pairs, sequence, frames, frames2, height, width, c, stride << l, packed[l]));
+
+    const int top = levels - 1;
+    MatchArgs m{};
+    m.packed = packed[top];
+    m.h = height / (stride << top);
+    m.w = width / (stride << top);
+    m.stride = stride << top;
+    m.search = search;
+    m.penalty = penalty;
+    m.n_pairs = n_pairs;
+    m.seq = sequence ? 1 : 0;
+    m.out = field[top];
+    PAPOF_TRY(launch_match_packed(st, m, items, patch));
+
+    for (int l = top - 1; l >= 0; l--) {
+        RefineArgs a{};
+        a.packed = packed[l];
+        a.parent = field[l + 1];
+        a.out = field[l];
+        a.disp = *disp;
+        a.cost = *cost;
+        a.h = height / (stride << l);
+        a.w = width / (stride << l);
+        a.h1 = height / (stride << (l + 1));
+        a.w1 = width / (stride << (l + 1));
+        a.stride = stride;
+        a.refine = refine;
+        a.penalty = penalty;
+        a.n_pairs = n_pairs;
+        a.seq = sequence ? 1 : 0;
+        a.last = l == 0;
+        a.staged = staged;
+        int rc;
+        switch (patch) {
+            case 1: rc = launch_refine<1>(st, a, items); break;
+            case 2: rc = launch_refine<2>(st, a, items); break;
+            case 3: rc = launch_refine<3>(st, a, items); break;
+            case 4: rc = launch_refine<4>(st, a, items); break;
+            case 5: rc = launch_refine<5>(st, a, items); break;
+            case 6: rc = launch_refine<6>(st, a, items); break;
+            default: rc = launch_refine<7>(st, a, items); break;
+        }
+        PAPOF_TRY(rc);
+    }
+    return PAPOF_OK;
 }
 
 extern "C" int papof_match_densify_tensor(papof_handle* h, int n, int height, int width, int stride, const papof_tensor* disp,

@@ -83,9 +83,14 @@ Large displacements: `match_pairs` / `match_video` (include/papof.h: papof_match
 decimated frame, the integer displacement that minimises a sum of absolute differences over a patch (brute force over one
 window, integer arithmetic, bitwise reproducible); `match_init` (papof_match_densify_tensor) keeps the cells that pass a
 forward-backward test and fills the rest (fill_holes); `flow_pairs_ld` / `flow_video_ld` start flow_pairs_fb from the result,
-which brings motion larger than the objects that carry it within the solver's reach.
+which brings motion larger than the objects that carry it within the solver's reach.  With `levels` = 2 .. 4
+(`match_levels` of the _ld calls; include/papof.h: papof_match_hier_tensor) the search is hierarchical: the flat search on
+the grid of stride * 2^(levels - 1), then per level twice the parents' vectors +- `refine` cells -- pans and large
+structures beyond stride * search pixels (160 px at the defaults with 3 levels), not objects smaller than the top
+level's window, which keep levels=1.
 
     fb = flow_video_ld(frames, layout="NHWC")   # a FlowFB, as flow_video_fb's
+    fb = flow_video_ld(frames, layout="NHWC", match_levels=3)   # a fast pan: up to 160 px per frame
 
 Motion blur: `motion_blur` (include/papof.h: papof_motion_blur_tensor) gives a video a longer shutter: every frame becomes
 the weighted mean of the scene at the times of `blur_schedule` around it, each of them what `interpolate` states, summed in
@@ -1874,6 +1879,9 @@ MAX_TOL = 2 * MAX_SEARCH
 MATCH_STRIDE = 2
 MATCH_PATCH = 3
 MATCH_SEARCH = 20
+MAX_MATCH_LEVELS = 4  # include/papof.h: papof_match_hier_tensor
+MAX_REFINE = 3
+MAX_TOP_STRIDE = 32
 
 Matches = collections.namedtuple("Matches", "disp_fw disp_bw cost_fw cost_bw")
 MatchInit = collections.namedtuple("MatchInit", "init_fw init_bw reliable")
@@ -1890,6 +1898,15 @@ def _check_match(stride, patch, search, penalty):
         raise ValueError("stride must be one of %s, got %r" % (STRIDES, stride))
     return (stride, _int_in("patch", patch, 1, MAX_PATCH), _int_in("search", search, 1, MAX_SEARCH),
             _int_in("penalty", penalty, 0, MAX_PENALTY))
+
+
+def _check_hier(stride, levels, refine):
+    """(levels, refine, the top level's stride) of the hierarchical search"""
+    levels, refine = _int_in("levels", levels, 1, MAX_MATCH_LEVELS), _int_in("refine", refine, 1, MAX_REFINE)
+    top = stride << (levels - 1)
+    if top > MAX_TOP_STRIDE:
+        raise ValueError("stride %d with %d levels gives a top level of stride %d: at most %d" % (stride, levels, top, MAX_TOP_STRIDE))
+    return levels, refine, top
 
 
 def _check_densify(tol, max_cost):
@@ -1913,8 +1930,8 @@ def _check_match_frames(named, layout, out_dtype, levels, stride, min_frames=1, 
     return ts, descs, out_dtype, params
 
 
-def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, out_dtype):
-    """papof_match_tensor on the current stream of the frames' device"""
+def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, out_dtype, levels=1, refine=1):
+    """papof_match_tensor, or with levels > 1 papof_match_hier_tensor, on the current stream of the frames' device"""
     torch = _torch()
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
@@ -1925,18 +1942,25 @@ def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, o
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
     d_disp = _flow_struct(disp, code)
     d_cost = _struct(cost, (cost.stride(0), cost.stride(1), cost.stride(2), 0), code)
-    _launch(dev, "papof_match_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
-            None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, patch, search, penalty, 1 if both else 0,
-            ctypes.byref(d_disp), ctypes.byref(d_cost),
-            workspace=("papof_match_workspace", (n_pairs, 1 if sequence else 0, H, W, stride),
-                       "%d pairs of %d x %d are too large to match" % (n_pairs, H, W)))
+    if levels == 1:
+        _launch(dev, "papof_match_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+                None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, patch, search, penalty, 1 if both else 0,
+                ctypes.byref(d_disp), ctypes.byref(d_cost),
+                workspace=("papof_match_workspace", (n_pairs, 1 if sequence else 0, H, W, stride),
+                           "%d pairs of %d x %d are too large to match" % (n_pairs, H, W)))
+    else:
+        _launch(dev, "papof_match_hier_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+                None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, levels, patch, search, refine, penalty,
+                1 if both else 0, ctypes.byref(d_disp), ctypes.byref(d_cost),
+                workspace=("papof_match_hier_workspace", (n_pairs, 1 if sequence else 0, H, W, stride, levels),
+                           "%d pairs of %d x %d are too large to match" % (n_pairs, H, W)))
     if both:
         return Matches(disp[:n_pairs], disp[n_pairs:], cost[:n_pairs], cost[n_pairs:])
     return Matches(disp, None, cost, None)
 
 
 def match_pairs(im1, im2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
-                out_dtype=None):
+                out_dtype=None, levels=1, refine=1):
     """Dense block matching of the independent pairs (im1[i], im2[i]): two tensors of one shape, (B, C, H, W) or
     (B, H, W, C) by `layout`, C = 1 .. 4, uint8, float32 or float64 (quantised to uint8 as rint(255 x)), any strides, on a HIP
     device.  Each frame is box-decimated by `stride` (1, 2, 4 or 8) to h x w = H // stride x W // stride cells; every cell of
@@ -1947,21 +1971,33 @@ def match_pairs(im1, im2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATC
     Returns Matches(disp_fw, disp_bw (B, 2, h, w): stride * d in full-resolution pixels, cost_fw, cost_bw (B, h, w)) of
     out_dtype (float64, or float32: both hold the integers exactly); the backward fields (im2 -> im1) are None for
     both=False.  The forward and backward fields are views of one tensor.
-    This is a START for the solver (match_init, flow_pairs_ld), not a flow: whole cells only, no hierarchy -- motion beyond
-    stride * search is not found -- and on repetitive texture only match_init's forward-backward test tells a wrong match.
+    This is a START for the solver (match_init, flow_pairs_ld), not a flow: whole cells only, and on repetitive texture
+    only match_init's forward-backward test tells a wrong match.  With levels=1 it is one flat search: motion beyond
+    stride * search pixels (40 at the defaults) is not found.
+    levels = 2 .. 4 searches hierarchically (papof_match_hier_tensor states the rule): the flat search runs on the grid of
+    stride * 2^(levels - 1) (at most 32) and every lower level tries, per cell, twice the vectors of its parent cell and
+    of three neighbours of the parent, and zero, each +- `refine` (1 .. 3) cells.  The reach is stride * 2^(levels - 1) *
+    search pixels plus the refinements -- 160 px at stride 2, levels 3, search 20 -- for about a tenth of the flat search's
+    candidates, and the outputs have the same shapes and meaning.  Use it for pans and large structures that move beyond
+    40 px.  Do NOT use it for an object smaller than the top level's window ((2 patch + 1) cells of the top stride: 56 px
+    at the defaults with levels 3): the top level sees the background around it and the lower levels only refine what it
+    found, so a small object that moves far is lost where the flat search finds it -- keep levels=1 there.
     The workspace comes from PyTorch's allocator; enqueued on the current stream, returns without waiting."""
     stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
-    ts, descs, out_dtype, _ = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, 1, stride)
-    return _match(ts, descs, False, descs[0][0][0], stride, patch, search, penalty, bool(both), out_dtype)
+    levels, refine, top = _check_hier(stride, levels, refine)
+    ts, descs, out_dtype, _ = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, 1, top)
+    return _match(ts, descs, False, descs[0][0][0], stride, patch, search, penalty, bool(both), out_dtype, levels, refine)
 
 
 def match_video(frames, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
-                out_dtype=None):
-    """match_pairs on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames, each frame decimated once: T - 1
-    pairs."""
+                out_dtype=None, levels=1, refine=1):
+    """match_pairs on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames, each frame decimated once per
+    level: T - 1 pairs.  levels, refine: the hierarchical search of match_pairs, for pans and large structures beyond
+    stride * search pixels; an object smaller than the top level's window keeps levels=1."""
     stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
-    ts, descs, out_dtype, _ = _check_match_frames([("frames", frames)], layout, out_dtype, 1, stride, min_frames=2)
-    return _match(ts, descs, True, descs[0][0][0] - 1, stride, patch, search, penalty, bool(both), out_dtype)
+    levels, refine, top = _check_hier(stride, levels, refine)
+    ts, descs, out_dtype, _ = _check_match_frames([("frames", frames)], layout, out_dtype, 1, top, min_frames=2)
+    return _match(ts, descs, True, descs[0][0][0] - 1, stride, patch, search, penalty, bool(both), out_dtype, levels, refine)
 
 
 def _check_size(size, h, w):
@@ -2054,17 +2090,18 @@ def match_init(disp_fw, disp_bw, cost_fw, cost_bw, size, *, tol=1, max_cost=None
     return _match_init((disp_fw, disp_bw), codes, (cost_fw, cost_bw), c_codes, H, W, stride, tol, max_cost, relax)
 
 
-def _run_ld(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, match, densify):
+def _run_ld(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, match, densify, hier):
     torch = _torch()
     (_, H, W, _), _, _ = descs[0]
-    m = _match(ts, descs, sequence, n_pairs, *match, True, torch.float32)
+    m = _match(ts, descs, sequence, n_pairs, *match, True, torch.float32, *hier)
     code = (capi.DTYPE_F32, capi.DTYPE_F32)
     init = _match_init((m.disp_fw, m.disp_bw), code, (m.cost_fw, m.cost_bw), code, H, W, match[0], *densify)
     return _run_fb(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, params, init.init_fw, init.init_bw)
 
 
 def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
-                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, match_levels=1, match_refine=1,
+                  **solver):
     """Large-displacement flow of the independent pairs (im1[i], im2[i]): match_pairs (stride, patch, search, penalty),
     match_init (tol, max_cost, relax) and flow_pairs_fb(im1, im2, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw,
     ...) -- bit for bit what that call returns given match_init's flows, as FlowFB, so every call built on the flows takes
@@ -2072,27 +2109,35 @@ def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH
     reach, objects smaller than their displacement included, which no number of pyramid levels does; the solver then needs
     few levels (2 by default: the prior is accurate to a cell).  Frames of C = 1 .. 4 channels.  When NOT to use it: on
     ordinary video (motion of a few pixels) the cold flow_pairs_fb with 5 levels is as good and the matching is wasted
-    work; the displacements are whole cells and only a start; there is no hierarchical search, so motion beyond
-    stride * search is missed as before; and a wrong match on repetitive texture is only caught where the forward-backward
-    test fails.  Every argument error raises before anything is launched."""
+    work; the displacements are whole cells and only a start; and a wrong match on repetitive texture is only caught
+    where the forward-backward test fails.  match_levels = 2 .. 4 and match_refine are match_pairs' levels and refine: the
+    hierarchical search reaches stride * 2^(match_levels - 1) * search pixels (160 at stride 2, 3 levels, search 20) -- use
+    it for pans and large structures that move beyond 40 px.  With match_levels=1 motion beyond stride * search is missed
+    as before; with more, an object smaller than the top level's window ((2 patch + 1) cells of the top stride) is lost
+    where the flat search finds it: keep match_levels=1 for small objects that move far.  Every argument error raises
+    before anything is launched."""
     alphas = _alphas(consistency)
     match = _check_match(stride, patch, search, penalty)
+    *hier, top = _check_hier(match[0], match_levels, match_refine)
     densify = (*_check_densify(tol, max_cost), _check_relax(relax))
-    ts, descs, out_dtype, params = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, match[0],
+    ts, descs, out_dtype, params = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, top,
                                                        solver=solver)
-    return _run_ld(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, params, match, densify)
+    return _run_ld(ts, descs, False, descs[0][0][0], layout, out_dtype, pyramidLevels, alphas, params, match, densify, hier)
 
 
 def flow_video_ld(frames, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
-                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+                  max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, match_levels=1, match_refine=1,
+                  **solver):
     """flow_pairs_ld on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames: match_video, match_init and
-    flow_video_fb(frames, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw, ...)."""
+    flow_video_fb(frames, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw, ...).  match_levels, match_refine as
+    there: the hierarchical search for pans and large structures beyond stride * search pixels, not for small objects."""
     alphas = _alphas(consistency)
     match = _check_match(stride, patch, search, penalty)
+    *hier, top = _check_hier(match[0], match_levels, match_refine)
     densify = (*_check_densify(tol, max_cost), _check_relax(relax))
-    ts, descs, out_dtype, params = _check_match_frames([("frames", frames)], layout, out_dtype, pyramidLevels, match[0],
+    ts, descs, out_dtype, params = _check_match_frames([("frames", frames)], layout, out_dtype, pyramidLevels, top,
                                                        min_frames=2, solver=solver)
-    return _run_ld(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, match, densify)
+    return _run_ld(ts, descs, True, descs[0][0][0] - 1, layout, out_dtype, pyramidLevels, alphas, params, match, densify, hier)
 
 
 FACTORS = (2, 3, 4)  # include/papof.h: papof_decimate_tensor, papof_upsample_flow_tensor
