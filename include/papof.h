@@ -1456,6 +1456,81 @@ int papof_bundle_sums_tensor(papof_handle* h, int n_links, int height, int width
                              const papof_tensor* occlusion, const papof_tensor* rotations, double scale,
                              const papof_tensor* sums, void* workspace, long long workspace_bytes, void* stream);
 
+/* Spatially varying stabilization (SteadyFlow, Liu, Yuan, Tan, Sun, CVPR 2014; MeshFlow, Liu, Tan, Yuan, Sun, Zeng, ECCV
+ * 2016): the robust motion of a flow field at the vertices of a coarse mesh, and the affine warp plus a displacement mesh.
+ * A parallel family: no call above changes.
+ *
+ * THE MESH.  grid_rows = GH and grid_cols = GW cells on frames of height = H rows and width = W columns, 1 <= GH <= min(H - 1,
+ * PAPOF_MESH_MAX_CELLS) and 1 <= GW <= min(W - 1, PAPOF_MESH_MAX_CELLS).  Vertex (i, j), i = 0 .. GH, j = 0 .. GW, sits at
+ *     px = (j * (W - 1)) / GW;  py = (i * (H - 1)) / GH          (fp64: the product of two exact integers, then one division)
+ *
+ * papof_mesh_motion_tensor (mesh.hip: k_mesh_median, k_mesh_spatial): the lower median, per component, of the flow's residual
+ * against the pair's global motion over a window around every vertex.
+ * flow: float32 (widened exactly) or float64 (pair, row, column, {vx, vy}), any non-negative strides.  occlusion: NULL, or
+ * uint8 (pair, row, column), any non-negative strides (stride[3] ignored): a pixel whose byte is not 0 is left out.  motion:
+ * NULL (every pair: the identity, exactly the matrix (1 0 0; 0 1 0)), or float64 (pair, row, column), 2 x 3, any non-negative
+ * strides: M = (m00 m01 m02; m10 m11 m12), papof_motion_fit_tensor's.
+ * WINDOW of vertex (i, j): the pixels (x, r) within one cell width and one cell height of the vertex, clipped to the image, in
+ * integers:
+ *     x_lo = max(0, ceil((j - 1) (W - 1) / GW));  x_hi = min(W - 1, floor((j + 1) (W - 1) / GW));  r_lo, r_hi likewise with i, H, GH
+ * LATTICE: with Lx = floor(2 (W - 1) / GW) and Ly = floor(2 (H - 1) / GH), step is the smallest integer s >= 1 with
+ * (floor(Lx / s) + 1) * (floor(Ly / s) + 1) <= 1024 -- no window, clipped or not, then holds more than 1024 lattice points.
+ * The SAMPLES of a window are its pixels with x % step == 0 and r % step == 0, in row-major order (r outer, x inner).
+ * At a sample, in fp64 without fused multiply-adds and grouped as written, with (u, v) the flow there:
+ *     valid iff 0 <= x + u <= W - 1 and 0 <= r + v <= H - 1 (false where u or v is NaN or infinite), the occlusion byte is 0,
+ *               and neither rx nor ry below is a NaN (one can be only through a matrix that is not finite)
+ *     rx = u - (((m00 * x + m01 * r) + m02) - x);  ry = v - (((m10 * x + m11 * r) + m12) - r)          (the residual)
+ * SELECTION, per component separately: n = the number of valid samples (the same for both components); the n residuals are
+ * ordered by their bit patterns as signed numbers -- numerically, with -0 before +0 -- and by sample order among equal bit
+ * patterns, and the one of rank (n - 1) / 2 (integer division, ranks from 0: the LOWER median) is taken: the result is the
+ * bits of one sample (of two different samples for x and y, in general).  n = 0: (0, 0).  support(i, j) = n; the vertex is
+ * VALID iff n >= min_support.
+ * SPATIAL PASS (MeshFlow's second filter), spatial != 0: the residual of vertex (i, j) is, per component, the lower median --
+ * the same order and rank -- of the window medians of the VALID vertices among (i + di, j + dj), di, dj = -1 .. 1 in row-major
+ * order, itself included, inside the mesh; (0, 0) where none is valid, so that the vertex follows the global motion.
+ * spatial == 0: the vertex's own window median where it is valid, else (0, 0).
+ * OUTPUT: residuals(i, j) = (Rx, Ry) as above; vertices(i, j) = (Rx + gx, Ry + gy) with the global motion at the vertex
+ *     gx = ((m00 * px + m01 * py) + m02) - px;  gy = ((m10 * px + m11 * py) + m12) - py
+ * Subtracting the global motion first keeps the median of a clipped border window unbiased under rotation and zoom; on an
+ * exactly affine flow every residual is zero to rounding.
+ * vertices, residuals: float64 (pair, vertex row, vertex column, {x, y}), strides > 0.  support: n_pairs * (GH + 1) * (GW + 1)
+ * int32, contiguous (pair, vertex row, vertex column), device memory.  workspace: device memory of at least
+ * papof_mesh_workspace(n_pairs, grid_rows, grid_cols) = 16 * n_pairs * (GH + 1) * (GW + 1) bytes (the window medians between
+ * the two kernels; -1 for an argument < 1 or a grid beyond PAPOF_MESH_MAX_CELLS), 8-byte aligned, the caller's, used by
+ * nothing else until the work enqueued here has run.  No atomics: the results are bitwise reproducible, and a pair's rows are
+ * the same alone and in a batch.  Enqueued on `stream` and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (occlusion and motion aside), data pointer or support,
+ * a flow that is not float32 / float64, a mask that is not uint8, a motion, vertices or residuals that is not float64, a
+ * negative stride, a zero stride of an output, a grid outside the bounds above, min_support < 1, n_pairs, height or width
+ * < 1, a NULL workspace or workspace_bytes below papof_mesh_workspace's value.
+ *
+ * papof_warp_mesh_tensor (mesh.hip: k_warp_mesh): papof_warp_affine_tensor with a displacement added to the sampling point,
+ * interpolated bilinearly from the frame's table mesh: float64 (frame, vertex row, vertex column, {dx, dy}), any non-negative
+ * strides.  At output pixel (x, r) of frame i, with M = matrices[i], D = mesh[i], in fp64 without fused multiply-adds and
+ * grouped as written:
+ *     X0 = (m00 * x + m01 * r) + m02;  Y0 = (m10 * x + m11 * r) + m12                 (papof_warp_affine_tensor's point)
+ *     gx = (X0 * GW) / (W - 1);  gx = gx < 0 ? 0 : (gx > GW ? GW : gx);  gy likewise with Y0, GH, H    (a NaN stays a NaN)
+ *     j = gx >= 0 ? min((int)gx, GW - 1) : 0;  fx = gx - j;  i likewise;  fy = gy - i   (truncation; a NaN takes cell 0)
+ *     dx = dy = 0;  for m = 0, 1: for n = 0, 1:  w = |(1 - m) - fx| * |(1 - n) - fy|;
+ *                                                dx += D(i + n, j + m).dx * w;  dy += D(i + n, j + m).dy * w
+ *     X = X0 + dx;  Y = Y0 + dy
+ * -- the weights and the (m, n) order of the sampler's taps.  Inside [0, W - 1] x [0, H - 1] (false for a NaN, which a NaN
+ * in one of the cell's four table entries gives) the frame is sampled at (X, Y) and stored as papof_warp_affine_tensor does,
+ * and valid = 1; outside, out = 0 and valid = 0.  A table whose entries are all +0.0 gives the BYTES of
+ * papof_warp_affine_tensor.  The displacement is looked up at the sampling point X0, not at the moved vertex: this is the
+ * backward approximation of MeshFlow's forward mesh render, and differs from it at second order in the displacement's
+ * gradient.  Arguments otherwise and PAPOF_EINVAL as papof_warp_affine_tensor's, and a mesh that is NULL, has no data, is not
+ * float64 or has a negative stride, or a grid outside the bounds above. */
+#define PAPOF_MESH_MAX_CELLS 64
+long long papof_mesh_workspace(int n_pairs, int grid_rows, int grid_cols);
+int papof_mesh_motion_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow,
+                             const papof_tensor* occlusion, const papof_tensor* motion, int grid_rows, int grid_cols,
+                             int min_support, int spatial, const papof_tensor* vertices, const papof_tensor* residuals,
+                             int* support, void* workspace, long long workspace_bytes, void* stream);
+int papof_warp_mesh_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                           const papof_tensor* matrices, const papof_tensor* mesh, int grid_rows, int grid_cols,
+                           const papof_tensor* out, const papof_tensor* valid, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -31,6 +31,7 @@ DTYPE_U8, DTYPE_F32, DTYPE_F64 = 0, 1, 2
 MOTION_SIMILARITY, MOTION_AFFINE = 0, 1
 MOSAIC_FIRST, MOSAIC_MEAN, MOSAIC_MEDIAN, MOSAIC_FEATHER = 0, 1, 2, 3
 MOSAIC_MAX_SOURCES, MOSAIC_MAX_MEDIAN, MOSAIC_MAX_OVERLAP = 255, 64, 64
+MESH_MAX_CELLS = 64  # PAPOF_MESH_MAX_CELLS
 
 
 class PapofTensor(ctypes.Structure):
@@ -77,6 +78,7 @@ SYMBOLS = [
     "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor",
     "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor",
     "papof_bundle_workspace", "papof_bundle_sums_tensor",
+    "papof_mesh_workspace", "papof_mesh_motion_tensor", "papof_warp_mesh_tensor",
 ]
 
 
@@ -264,6 +266,13 @@ def load():
     L.papof_bundle_sums_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, _T, c_void_p,
                                            ctypes.c_longlong, c_void_p]
     L.papof_bundle_sums_tensor.restype = c_int
+    L.papof_mesh_workspace.argtypes = [c_int, c_int, c_int]
+    L.papof_mesh_workspace.restype = ctypes.c_longlong
+    L.papof_mesh_motion_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, c_int, c_int, _T, _T, c_void_p,
+                                           c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_mesh_motion_tensor.restype = c_int
+    L.papof_warp_mesh_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, _T, _T, c_void_p]
+    L.papof_warp_mesh_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

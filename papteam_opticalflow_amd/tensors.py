@@ -145,6 +145,14 @@ flows, `bundle_transforms` makes the canvas (the full circle where the pan close
 
     pano = panorama_bundle(frames, 5, focal=1150.0, layout="NHWC")        # a BundlePanorama: WidePanorama's fields, rotations, links, cost
 
+Mesh stabilization: shake that varies across the image (parallax, rolling shutter) is not one matrix per frame.  `mesh_motion`
+(include/papof.h: papof_mesh_motion_tensor) reduces each pair's flow to the lower median of its residual against the global
+motion around every vertex of a coarse mesh (SteadyFlow / MeshFlow), `mesh_transforms` smooths the vertices' profiles in
+time on the host, `warp_mesh` (papof_warp_mesh_tensor) is warp_affine plus the bilinearly interpolated displacement table,
+and `stabilize_video_mesh` chains them behind flow_video_fb and global_motion.
+
+    sv = stabilize_video_mesh(frames, 5, layout="NHWC", grid=(16, 16))   # a MeshStabilized: Stabilized's fields, mesh, vertex_motion, support
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -168,6 +176,8 @@ ALPHA = 20.0  # splat_weights: the weight of a pixel is exp(-ALPHA * its photome
 Motion = collections.namedtuple("Motion", "motion ok support")
 Homography = collections.namedtuple("Homography", "motion ok support")
 Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
+MeshMotion = collections.namedtuple("MeshMotion", "vertices support residuals")
+MeshStabilized = collections.namedtuple("MeshStabilized", "video valid transforms motion ok flow timing mesh vertex_motion support")
 Filtered = collections.namedtuple("Filtered", "video support")
 Denoised = collections.namedtuple("Denoised", "video support flow_fw flow_bw timing")
 Flows = collections.namedtuple("Flows", "flow_fw flow_bw")
@@ -1092,6 +1102,249 @@ def stabilize_video(frames, pyramidLevels, *, layout="NCHW", model="similarity",
     M = stabilizing_transforms(m, radius, crop, size=(H, W))
     video, valid = _warp(ts, descs, M, capi.DTYPE_F64, layout, out_dtype)
     return Stabilized(video, valid, M, m.motion, m.ok, flow, timing)
+
+
+# ---- spatially varying stabilization: per-vertex motion profiles and a mesh warp (SteadyFlow / MeshFlow)
+MAX_CELLS = capi.MESH_MAX_CELLS  # include/papof.h: PAPOF_MESH_MAX_CELLS
+GRID = (16, 16)
+MIN_SUPPORT = 16
+
+
+def _check_grid(grid, H, W):
+    """(GH, GW) of a `grid` argument: integers with 1 <= GH <= min(MAX_CELLS, H - 1), 1 <= GW <= min(MAX_CELLS, W - 1)"""
+    try:
+        gh, gw = grid
+    except (TypeError, ValueError):
+        raise TypeError("grid must be (GH, GW), got %r" % (grid,)) from None
+    for v in (gh, gw):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError("grid must be two integers, got %r" % (grid,))
+    if not (1 <= gh <= min(MAX_CELLS, H - 1) and 1 <= gw <= min(MAX_CELLS, W - 1)):
+        raise ValueError("grid must lie in 1 .. min(%d, H - 1) x 1 .. min(%d, W - 1) for %d x %d frames, got %r"
+                         % (MAX_CELLS, MAX_CELLS, H, W, grid))
+    return gh, gw
+
+
+def _check_mesh_motion_args(min_support, spatial):
+    _int_at_least("min_support", min_support, 1)
+    _check_bool("spatial", spatial)
+
+
+def _check_plane_occlusion(occlusion, B, H, W, dev):
+    """None, or a bool / uint8 mask (B, H, W) or (B, 2, H, W) (channel 0 is read) on `dev`: a uint8 (B, H, W) view"""
+    if occlusion is None:
+        return None
+    torch = _torch()
+    if not isinstance(occlusion, torch.Tensor):
+        raise TypeError("occlusion must be None or a torch.Tensor, got %s" % type(occlusion).__name__)
+    if occlusion.dtype not in (torch.bool, torch.uint8):
+        raise TypeError("occlusion must be torch.bool or torch.uint8, got %s" % occlusion.dtype)
+    if tuple(occlusion.shape) not in ((B, H, W), (B, 2, H, W)):
+        raise ValueError("occlusion must be (B, H, W) = %s or (B, 2, H, W), got %s" % ((B, H, W), tuple(occlusion.shape)))
+    if occlusion.device != dev:
+        raise ValueError("occlusion is on %s, the flow on %s: both must be on one device" % (occlusion.device, dev))
+    occ = occlusion.view(torch.uint8)
+    return occ[:, 0] if occ.dim() == 4 else occ
+
+
+def _check_pair_matrices(motion, B, dev):
+    """None, or the pairs' (B, 2, 3) float64 matrices on `dev` of a tensor or a Motion (pairs with ok False: the identity,
+    replaced on the device without a wait)"""
+    if motion is None:
+        return None
+    torch = _torch()
+    ok = None
+    if isinstance(motion, Motion):
+        motion, ok = motion.motion, motion.ok
+    if not isinstance(motion, torch.Tensor):
+        raise TypeError("motion must be None, a torch.Tensor or a Motion, got %s" % type(motion).__name__)
+    if motion.dtype != torch.float64:
+        raise TypeError("motion must be float64, got %s" % motion.dtype)
+    if tuple(motion.shape) != (B, 2, 3):
+        raise ValueError("motion must be (B, 2, 3) = %s, got %s" % ((B, 2, 3), tuple(motion.shape)))
+    if motion.device != dev:
+        raise ValueError("motion is on %s, the flow on %s: both must be on one device" % (motion.device, dev))
+    if ok is not None:
+        if not isinstance(ok, torch.Tensor) or tuple(ok.shape) != (B,) or ok.device != dev:
+            raise ValueError("a Motion's ok must be (B,) = %s on the flow's device" % ((B,),))
+        eye = torch.eye(2, 3, dtype=torch.float64, device=dev)
+        motion = torch.where(ok.to(torch.bool).reshape(B, 1, 1), motion, eye)
+    return motion
+
+
+def _vertex_struct(t):
+    """the descriptor (item, vertex row, vertex column, component) of a (N, GH + 1, GW + 1, 2) float64 tensor"""
+    return _struct(t, tuple(t.stride(i) for i in range(4)), capi.DTYPE_F64)
+
+
+def _mesh_motion(flow, code, occ, mats, gh, gw, min_support, spatial):
+    torch = _torch()
+    B, _, H, W = (int(x) for x in flow.shape)
+    dev = flow.device
+    vertices = torch.empty((B, gh + 1, gw + 1, 2), dtype=torch.float64, device=dev)
+    residuals = torch.empty((B, gh + 1, gw + 1, 2), dtype=torch.float64, device=dev)
+    support = torch.empty((B, gh + 1, gw + 1), dtype=torch.int32, device=dev)
+    d_flow = _flow_struct(flow, code)
+    d_occ = _struct(occ, (occ.stride(0), occ.stride(1), occ.stride(2), 0), capi.DTYPE_U8) if occ is not None else None
+    d_m = _struct(mats, (mats.stride(0), mats.stride(1), mats.stride(2), 0), capi.DTYPE_F64) if mats is not None else None
+    d_v, d_r = _vertex_struct(vertices), _vertex_struct(residuals)
+    _launch(dev, "papof_mesh_motion_tensor", B, H, W, ctypes.byref(d_flow), _ref(d_occ), _ref(d_m), gh, gw, min_support,
+            1 if spatial else 0, ctypes.byref(d_v), ctypes.byref(d_r), ctypes.c_void_p(support.data_ptr()),
+            workspace=("papof_mesh_workspace", (B, gh, gw), "a %d x %d grid is too large for mesh_motion" % (gh, gw)))
+    return MeshMotion(vertices, support, residuals)
+
+
+def mesh_motion(flow, *, motion=None, occlusion=None, grid=GRID, min_support=MIN_SUPPORT, spatial=True):
+    """The robust motion of each pair's flow at the vertices of a coarse mesh (the motion profiles' increments of SteadyFlow /
+    MeshFlow): flow (B, 2, H, W) float32 / float64 on a HIP device, any strides; motion None or the pairs' global motions --
+    a (B, 2, 3) float64 tensor (global_motion's) or a Motion, whose pairs with ok False enter as the identity --; occlusion
+    None or a bool / uint8 mask (B, H, W), or the (B, 2, H, W) mask of flow_video_fb (channel 0 is read).  grid = (GH, GW)
+    cells, 1 <= GH <= min(64, H - 1), 1 <= GW <= min(64, W - 1); vertex (i, j) sits at (j (W - 1) / GW, i (H - 1) / GH).
+    Per vertex, the lower median per component of the residual flow - (A q - q) over the pixels within one cell of the vertex
+    -- sampled on a lattice so that a window holds at most 1024, leaving out pixels whose flow is not finite, leaves the image
+    or is occluded --; a vertex with fewer than min_support samples is invalid.  spatial=True replaces every vertex's
+    residual by the lower median of the valid ones in its 3 x 3 vertex neighbourhood (an invalid vertex with no valid
+    neighbour: 0, it follows the global motion); spatial=False gives invalid vertices 0 directly.  Returns
+    MeshMotion(vertices (B, GH + 1, GW + 1, 2) float64 -- residual plus A v - v at the vertex --, support (B, GH + 1, GW + 1)
+    int32 -- the samples of the vertex's window --, residuals (B, GH + 1, GW + 1, 2) float64).  include/papof.h
+    (papof_mesh_motion_tensor) states the rule exactly; no atomics, bitwise reproducible, a pair's rows the same alone and
+    in a batch.  Enqueued on the current stream; returns without waiting."""
+    code = _check_flow("flow", flow)
+    B, _, H, W = (int(x) for x in flow.shape)
+    gh, gw = _check_grid(grid, H, W)
+    _check_mesh_motion_args(min_support, spatial)
+    occ = _check_plane_occlusion(occlusion, B, H, W, flow.device)
+    if not _on_gpu(flow):
+        raise ValueError("flow must be on a HIP device (cuda:N), got %s" % flow.device)
+    mats = _check_pair_matrices(motion, B, flow.device)
+    return _mesh_motion(flow, code, occ, mats, gh, gw, min_support, spatial)
+
+
+def mesh_profiles(residuals, radius):
+    """mesh_transforms on a numpy (T - 1, GH + 1, GW + 1, 2) float64 array of per-pair vertex residuals: the displacement
+    tables (T, GH + 1, GW + 1, 2) float64.  C(0) = 0, C(t + 1) = C(t) + r(t) (the profile AT a vertex, not a trajectory);
+    S(t) = sum_k g_k C(t + k) / sum_k g_k with path_transforms's weights g_k = exp(-k^2 / (2 (radius / 2)^2)), k in
+    [-radius, radius] within the video; D(t) = C(t) - S(t).  radius = 0: D = 0 exactly."""
+    import numpy as np
+    r = np.asarray(residuals, np.float64)
+    n = r.shape[0] + 1
+    C = np.zeros((n,) + r.shape[1:])
+    for t in range(n - 1):
+        C[t + 1] = C[t] + r[t]
+    D = np.zeros_like(C)
+    if radius == 0:
+        return D
+    for t in range(n):
+        ks = range(max(-radius, -t), min(radius, n - 1 - t) + 1)
+        g = [math.exp(-k * k / (2.0 * (radius / 2.0) ** 2)) for k in ks]
+        S = sum(gk * C[t + k] for gk, k in zip(g, ks)) / sum(g)
+        D[t] = C[t] - S
+    return D
+
+
+def _check_residuals(mesh_motion):
+    r = mesh_motion.residuals if isinstance(mesh_motion, MeshMotion) else mesh_motion
+    if not isinstance(r, _torch().Tensor):
+        raise TypeError("mesh_motion must be a MeshMotion or a torch.Tensor of residuals, got %s" % type(r).__name__)
+    if r.dim() != 4 or r.shape[3] != 2 or r.shape[0] < 1 or r.shape[1] < 2 or r.shape[2] < 2:
+        raise ValueError("the residuals must be (T - 1, GH + 1, GW + 1, 2) with T >= 2, got shape %s" % (tuple(r.shape),))
+    return r
+
+
+def mesh_transforms(mesh_motion, radius=15):
+    """The displacement tables that stabilize a video of T frames whose consecutive pairs' vertices move by `mesh_motion` --
+    a MeshMotion, or its residuals (T - 1, GH + 1, GW + 1, 2) -- beyond the global motion: the residuals alone are used
+    (vertices minus A v - v; the global part is stabilizing_transforms's).  In float64 on the host (one small copy from the
+    device: a wait), mesh_profiles: the residuals accumulate to a profile per vertex, the profile is smoothed by the
+    Gaussian of stabilizing_transforms, and the table is profile minus smoothed profile.  Returns (T, GH + 1, GW + 1, 2)
+    float64 on the motion's device, for warp_mesh."""
+    r = _check_residuals(mesh_motion)
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius < 0:
+        raise ValueError("radius must be an integer >= 0, got %r" % (radius,))
+    D = mesh_profiles(r.detach().to("cpu", _torch().float64).numpy(), radius)
+    return _torch().from_numpy(D).to(r.device)
+
+
+def _check_mesh(mesh, n, dev, H, W):
+    """a (n, GH + 1, GW + 1, 2) float64 table on `dev` whose grid fits H x W frames: (GH, GW)"""
+    torch = _torch()
+    if not isinstance(mesh, torch.Tensor):
+        raise TypeError("mesh must be a torch.Tensor, got %s" % type(mesh).__name__)
+    if mesh.dtype != torch.float64:
+        raise TypeError("mesh must be float64, got %s" % mesh.dtype)
+    if mesh.dim() != 4 or mesh.shape[0] != n or mesh.shape[3] != 2:
+        raise ValueError("mesh must be (B, GH + 1, GW + 1, 2) with B = %d, got shape %s" % (n, tuple(mesh.shape)))
+    if mesh.device != dev:
+        raise ValueError("mesh is on %s, the frames on %s: both must be on one device" % (mesh.device, dev))
+    return _check_grid((int(mesh.shape[1]) - 1, int(mesh.shape[2]) - 1), H, W)
+
+
+def _warp_mesh(ts, descs, matrices, m_code, mesh, gh, gw, layout, out_dtype):
+    torch = _torch()
+    (B, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    out, d_out = _new_frames(B, H, W, C, layout, out_dtype, dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], descs[0][1], descs[0][2])
+    d_mat = _struct(matrices, (matrices.stride(0), matrices.stride(1), matrices.stride(2), 0), m_code)
+    d_mesh = _vertex_struct(mesh)
+    d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
+    _launch(dev, "papof_warp_mesh_tensor", B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_mat), ctypes.byref(d_mesh), gh, gw,
+            ctypes.byref(d_out), ctypes.byref(d_valid))
+    return out, valid.view(torch.bool)
+
+
+def warp_mesh(frames, matrices, mesh, *, layout="NCHW", out_dtype=None):
+    """warp_affine with a spatially varying displacement: output pixel q of frame i is frames[i] sampled at M q + d, d the
+    bilinear interpolation of the frame's table mesh[i] -- mesh (B, GH + 1, GW + 1, 2) float64 (dx, dy) on the frames'
+    device, any strides, the vertices of mesh_motion's mesh -- at the mesh coordinates of M q, clamped to the mesh.  frames,
+    matrices, layout, out_dtype and the result (frames_out, valid (B, H, W) bool) as warp_affine's; a table of +0.0 gives
+    warp_affine's bytes.  The displacement is looked up at the sampling point, not at the moved vertex: the backward
+    approximation of MeshFlow's forward mesh render, different at second order in the displacement's gradient.
+    include/papof.h (papof_warp_mesh_tensor) states the rule exactly.  Enqueued on the current stream; returns without
+    waiting."""
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    (B, H, W, _), _, _ = descs[0]
+    m_code = _check_matrices(matrices, B, ts[0].device)
+    gh, gw = _check_mesh(mesh, B, ts[0].device, H, W)
+    return _warp_mesh(ts, descs, matrices, m_code, mesh, gh, gw, layout, out_dtype)
+
+
+def stabilize_video_mesh(frames, pyramidLevels, *, grid=GRID, radius=15, crop=1.0, model="similarity", iters=5, scale=1.0,
+                         min_support=MIN_SUPPORT, spatial=True, consistency=CONSISTENCY, layout="NCHW", out_dtype=None,
+                         **solver):
+    """stabilize_video for shake that varies across the image (parallax, rolling shutter): flow_video_fb(frames,
+    pyramidLevels, consistency=consistency, layout=layout, **solver) (float64 flows and the occlusion mask; with
+    consistency=None, flow_video and no mask), global_motion on the forward flows (model, iters, scale), mesh_motion(flow_fw,
+    motion=, occlusion=, grid=, min_support=, spatial=), stabilizing_transforms (radius, crop) and mesh_transforms (radius) --
+    the waits, where stabilize_video waits -- and ONE warp_mesh.  Returns MeshStabilized(video, valid, transforms, motion, ok,
+    flow, timing as stabilize_video's, mesh (T, GH + 1, GW + 1, 2) float64: the displacement tables, vertex_motion
+    (T - 1, GH + 1, GW + 1, 2): mesh_motion's vertices, support (T - 1, GH + 1, GW + 1) int32).  With radius=0 the video and
+    valid are stabilize_video's.  The base matrix is affine, the borders are not filled, the smoothing is neither causal nor
+    adaptive (README).  Every argument error raises before anything is launched; the video is enqueued on the current
+    stream."""
+    ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
+    code, iters, scale = _check_fit(model, iters, scale)
+    (T, H, W, C), _, _ = descs[0]
+    _check_path(radius, crop, (H, W))
+    gh, gw = _check_grid(grid, H, W)
+    _check_mesh_motion_args(min_support, spatial)
+    alphas = _alphas(consistency)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    f64 = _torch().float64
+    if alphas[0]:
+        fb = _run_fb(ts, descs, True, T - 1, layout, f64, pyramidLevels, alphas, params)
+        flow, timing, occ = fb.flow_fw, fb.timing, fb.occlusion.view(_torch().uint8)[:, 0]
+    else:
+        flow, _, timing = _run(ts, descs, True, T - 1, layout, f64, pyramidLevels, params)
+        occ = None
+    m = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
+    mm = _mesh_motion(flow, capi.DTYPE_F64, occ, _check_pair_matrices(m, T - 1, flow.device), gh, gw, min_support, spatial)
+    M = stabilizing_transforms(m, radius, crop, size=(H, W))
+    D = mesh_transforms(mm, radius)
+    video, valid = _warp_mesh(ts, descs, M, capi.DTYPE_F64, D, gh, gw, layout, out_dtype)
+    return MeshStabilized(video, valid, M, m.motion, m.ok, flow, timing, D, mm.vertices, mm.support)
 
 
 MAX_RADIUS = 16  # include/papof.h: papof_temporal_filter_tensor
