@@ -1531,6 +1531,50 @@ int papof_warp_mesh_tensor(papof_handle* h, int n_frames, int height, int width,
                            const papof_tensor* matrices, const papof_tensor* mesh, int grid_rows, int grid_cols,
                            const papof_tensor* out, const papof_tensor* valid, void* stream);
 
+/* Full-frame mesh stabilization: the mosaic under the mesh rule (mosaic.hip: k_mosaic over MeshMosaicArgs, behind
+ * k_mesh_bounds) -- papof_mosaic_blend_tensor with a displacement table per SLOT, so that the frames around a mesh-stabilized
+ * frame fill its borders registered as the mesh registers them.  A parallel call: no call above changes.
+ * Arguments: the blend call's, and
+ *     mesh: float64 (slot, vertex row, vertex column, {dx, dy}), any non-negative strides, slot = o * n_src + k (a descriptor
+ *           has four strides: the (out, k) pair is one axis); n_out * n_src tables of (GH + 1) x (GW + 1) vertices
+ *     grid_rows = GH, grid_cols = GW: THE MESH's bounds above against the FRAMES' height = H and width = W -- the table is
+ *           looked up in the coordinates of the source frame
+ *     workspace: device memory of at least papof_mosaic_mesh_workspace(n_out, n_src) = 32 * n_out * n_src bytes (four doubles
+ *           per slot: the extremes of its table; -1 for n_out < 1 or n_src outside 1 .. PAPOF_MOSAIC_MAX_SOURCES), 8-byte
+ *           aligned, the caller's, used by nothing else until the work enqueued here has run
+ * At output pixel (x, r) of output o and slot k with s = sources[o, k] >= 0, M = matrices[o, k], D = mesh[o * n_src + k], in
+ * fp64 without fused multiply-adds and grouped as written:
+ *     X0 = (m00 * x + m01 * r) + m02;  Y0 = (m10 * x + m11 * r) + m12                          (papof_mosaic_tensor's point)
+ *     (dx, dy): word for word the rule of papof_warp_mesh_tensor above at (X0, Y0) with the table D -- gx, gy and their clamp,
+ *               the truncation to the cell (j, i), fx, fy, the four weights w = |(1 - m) - fx| * |(1 - n) - fy| and the sums
+ *               dx += D(i + n, j + m).dx * w, dy likewise, from 0 in (m, n) order
+ *     X = X0 + dx;  Y = Y0 + dy
+ * The slot is LIVE when (X, Y) lies in [0, W - 1] x [0, H - 1] (false for a NaN, which a NaN in one of the cell's four entries
+ * gives) and, with masks, the mask of frame s is 0 at every tap of the bilinear rule at (X, Y) whose weight is > 0.  Its
+ * sample is frames[s] under the bilinear rule at (X, Y); PAPOF_MOSAIC_FEATHER's weight is taken at (X, Y).  Everything behind
+ * the point is the blend call's: the gains, the four modes, count, the limits PAPOF_MOSAIC_MAX_SOURCES and _MAX_MEDIAN.
+ *     INVARIANT A.  With every table entry +0.0 (dx = dy = +0.0 then, and X0 + 0.0 orders and samples as X0 does) the call
+ *     returns the BYTES of papof_mosaic_blend_tensor: in all four modes, with and without gains, masks and count.
+ *     INVARIANT B.  With n_src = 1, sources[o] = o, a canvas of the frames' size and PAPOF_MOSAIC_FIRST, out is
+ *     papof_warp_mesh_tensor's out byte for byte (matrices[o, 0] and mesh[o] that call's), and count is its valid.
+ * Culling: the corner box of papof_mosaic_tensor alone would be wrong here -- a table can carry a source into a tile that its
+ * matrix misses.  k_mesh_bounds, ahead of k_mosaic on the stream, reduces every slot's table to the extremes of its dx and of
+ * its dy (a NaN entry makes them NaN), and a tile drops a slot only when its corner box WIDENED by the bound
+ * ((l + l) + l) + l <= d <= ((u + u) + u) + u, l = min(lo, 0), u = max(hi, 0) -- the four-term sum of the rule above at its
+ * extreme terms -- misses the frame (mosaic.hip has the proof that this changes no byte); a NaN bound keeps the slot, a matrix
+ * entry that is not finite drops it as before.  The same bound lets a pixel skip a slot before it reads the table.
+ * PAPOF_MOSAIC_CULL=0 skips the reduction, the bounds' use and both tests.  The overlap statistics have no mesh twin.
+ * Enqueued on `stream` and returns without waiting; bitwise reproducible, an output the same alone and in a batch.
+ * PAPOF_EINVAL, before anything is enqueued: papof_mosaic_blend_tensor's list, a mesh that is NULL, has no data, is not float64
+ * or has a negative stride, a grid outside the bounds above, a NULL workspace or workspace_bytes below
+ * papof_mosaic_mesh_workspace's value. */
+long long papof_mosaic_mesh_workspace(int n_out, int n_src);
+int papof_mosaic_mesh_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                             const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                             const int* sources, const papof_tensor* matrices, const papof_tensor* mesh, int grid_rows,
+                             int grid_cols, const papof_tensor* gains, int mode, const papof_tensor* out,
+                             const papof_tensor* count, void* workspace, long long workspace_bytes, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -79,6 +79,7 @@ SYMBOLS = [
     "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor",
     "papof_bundle_workspace", "papof_bundle_sums_tensor",
     "papof_mesh_workspace", "papof_mesh_motion_tensor", "papof_warp_mesh_tensor",
+    "papof_mosaic_mesh_workspace", "papof_mosaic_mesh_tensor",
 ]
 
 
@@ -273,6 +274,12 @@ def load():
     L.papof_mesh_motion_tensor.restype = c_int
     L.papof_warp_mesh_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, _T, _T, c_void_p]
     L.papof_warp_mesh_tensor.restype = c_int
+    L.papof_mosaic_mesh_workspace.argtypes = [c_int, c_int]
+    L.papof_mosaic_mesh_workspace.restype = ctypes.c_longlong
+    # the blend call's arguments with the tables and the grid after the matrices (index 12), the workspace before the stream
+    L.papof_mosaic_mesh_tensor.argtypes = (L.papof_mosaic_blend_tensor.argtypes[:13] + [_T, c_int, c_int] +
+                                           L.papof_mosaic_blend_tensor.argtypes[13:-1] + [c_void_p, ctypes.c_longlong, c_void_p])
+    L.papof_mosaic_mesh_tensor.restype = c_int
     L.papof_motion_fit_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_int, c_int, c_double, _T, _T, _T, c_void_p,
                                           ctypes.c_longlong, c_void_p]
     L.papof_motion_fit_tensor.restype = c_int

@@ -82,6 +82,38 @@
 //   PAPOF_MOSAIC_CULL=0 skips the reduction and the test.  The intervals ignore that u and w (sin and cos of one angle)
 //   move together, so they are looser than the projective corner test: DESIGN.md section 28 has the share of slots kept.
 //
+// papof_mosaic_mesh_tensor is k_mosaic over MeshMosaicArgs: BlendArgs whose affine point (X0, Y0) is moved by the displacement
+// (dx, dy) of the SLOT's own table, looked up at (X0, Y0) by papof_warp_mesh_tensor's rule (include/papof.h: the mosaic under
+// the mesh rule) -- the borders of a mesh-stabilized frame filled from its neighbours, each registered by its own table.  Chosen
+// at compile time as the other rules are; the instances over MosaicArgs, BlendArgs, ProjArgs and RayArgs are instruction for
+// instruction what they were.  The four entries per (pixel, slot) are read through global addresses: an output at fill radius
+// 15 has 31 tables (143 KB at 17 x 17), too many to stage, few enough to stay in the cache.
+//   Culling under the mesh rule (k_mesh_bounds, mesh_widening, mesh_keep, mesh_point).  The affine corner box alone is wrong
+//   here: a table can carry a source into a tile that its matrix misses.  k_mesh_bounds, ahead of k_mosaic on the stream, one
+//   wave per slot, reduces the slot's table to lo <= t.dx <= hi over its entries t, and the same for dy, with min and max that
+//   hand a NaN on (nan_min, nan_max).  Only pixels whose X and Y are numbers matter -- a NaN is live nowhere --: call such a
+//   pixel clean; none of its weights, terms, partial sums, X0 or Y0 is a NaN (a NaN operand makes every later step NaN).
+//     (a) A weight w = fl(|a - fx| * |b - fy|), a, b in {0, 1}: gx is clamped to [0, GW] and the cell index to [0, GW - 1],
+//         so fx = gx - j lies in [0, 1] (exactly: both are integers or gx < 2^53), |a - fx| in [0, 1], and the rounded product
+//         of two numbers of [0, 1] lies in [0, 1].
+//     (b) A term fl(t * w) with lo <= t <= hi and w in [0, 1]: t * w lies between 0 and t, hence in [l, u] with l = min(lo, 0),
+//         u = max(hi, 0); l and u are doubles and rounding is monotone, so fl(t * w) lies in [l, u] too (an infinite entry
+//         against w = 0 is a NaN term: not a clean pixel).
+//     (c) dx = fl(fl(fl(fl(0 + t0) + t1) + t2) + t3) over four such terms.  fl(p + q) is monotone in p and in q, so by
+//         induction over the partial sums dx >= ((l + l) + l) + l =: L and dx <= ((u + u) + u) + u =: U, both evaluated in
+//         fp64 in the order written (fl(0 + t0) = t0 >= l): the very chain of additions at its extreme terms, no epsilon.
+//     (d) X = fl(X0 + dx) is monotone in both operands, and over a tile X0 takes its extremes at the corners (phase 1's
+//         affine argument): at every clean pixel fl(X0_min + L) <= X <= fl(X0_max + U).
+//   Phase 1 drops a slot when fl(c + U) < -1 at all four corner values c of X0, or fl(c + L) > W - 1 + 1 at all four, or the
+//   same for Y with H (the affine box's one-pixel margin, kept): by (d) X or Y is then outside the frame at every clean pixel,
+//   the slot is live at no pixel of the tile, and dropping it changes no byte.  A NaN bound (a NaN entry, or +inf and -inf
+//   meeting in L + ... ) or a NaN corner makes every comparison false: kept.  A matrix entry that is not finite makes X0 or Y0
+//   +-inf or NaN at every pixel and X or Y with it (inf + dx is inf or NaN): dropped as before.
+//   The walk uses the same bound per pixel, before the table is read: fl(X0 + U) < 0 or fl(X0 + L) > W - 1 (or the same for
+//   Y) means, by (c) and the monotone sum, X < 0 or X > W - 1 or a pixel that is not clean: not live, skipped without a load.
+//   The slot's index is uniform, so its four bounds are scalar loads.  With `count` every slot is walked at every pixel, and
+//   most of a neighbour's pixels are far outside.  PAPOF_MOSAIC_CULL=0 skips k_mesh_bounds, the bounds' use and both tests.
+//
 // k_mosaic_overlap (papof_mosaic_overlap_tensor).  A block is a 64 x 2 tile of SAMPLED pixels (every step-th column and
 // row).  Phases 1 and 2 as above, each lane writing the fixed-point luminance q of its live slots to LDS [slot][pixel] and
 // the 64-bit set of them.  Then the roles turn: lane j is source j (64 / NS pixels side by side where NS < 64), wave w owns
@@ -132,6 +164,15 @@ struct RayArgs : BlendArgs {  // mat is 3 x 3 as ProjArgs', applied to the ray o
 
 template <typename A>
 constexpr bool kRay = std::is_same<A, RayArgs>::value;
+
+struct MeshMosaicArgs : BlendArgs {  // mat is 2 x 3 as BlendArgs'; the point is moved by the table of its slot
+    papof_tensor mesh;               // float64 (slot, vertex row, vertex column, {dx, dy}), slot = out * n_src + k
+    const double* bounds;            // (slot, {dx lo, dx hi, dy lo, dy hi}): k_mesh_bounds'; read only where cull
+    int GH, GW;                      // the cells of the mesh, on the FRAMES' H x W
+};
+
+template <typename A>
+constexpr bool kMesh = std::is_same<A, MeshMosaicArgs>::value;
 
 __device__ __forceinline__ double slot_gain(const MosaicArgs&, long long, int) { return 1.0; }
 __device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int k) {
@@ -306,6 +347,109 @@ __device__ __forceinline__ bool ray_point(const MosaicArgs& a, long long mb, con
     return D > 0;
 }
 
+// ---- the mesh rule
+// The extremes of every slot's table: blockIdx.x is slot `slot0` + x, the block one wave.  bounds[slot] = (dx lo, dx hi, dy lo,
+// dy hi) over the (GH + 1) x (GW + 1) entries (at least four); a NaN entry makes its two bounds NaN.
+__global__ __launch_bounds__(64) void k_mesh_bounds(const papof_tensor mesh, int VH, int VW, double* bounds, long long slot0,
+                                                    long long) {
+    const long long slot = slot0 + blockIdx.x;
+    const double* t = static_cast<const double*>(mesh.data) + slot * mesh.stride[0];
+    double xl = HUGE_VAL, xh = -HUGE_VAL, yl = HUGE_VAL, yh = -HUGE_VAL;
+    for (int v = threadIdx.x; v < VH * VW; v += 64) {
+        const long long e = (v / VW) * mesh.stride[1] + (v % VW) * mesh.stride[2];
+        const double dx = t[e], dy = t[e + mesh.stride[3]];
+        xl = nan_min(xl, dx);
+        xh = nan_max(xh, dx);
+        yl = nan_min(yl, dy);
+        yh = nan_max(yh, dy);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        xl = nan_min(xl, __shfl_xor(xl, d));
+        xh = nan_max(xh, __shfl_xor(xh, d));
+        yl = nan_min(yl, __shfl_xor(yl, d));
+        yh = nan_max(yh, __shfl_xor(yh, d));
+    }
+    if (threadIdx.x == 0) {
+        double* b = bounds + slot * 4;
+        b[0] = xl;
+        b[1] = xh;
+        b[2] = yl;
+        b[3] = yh;
+    }
+}
+
+// L <= dx <= U and the same for dy at every clean pixel of the slot whose bounds are b (the header comment, (a) to (c)): the
+// four-term sum at its extreme terms, in the order the rule adds them.  A NaN bound stays a NaN.
+__device__ __forceinline__ void mesh_widening(const double* b, double (&L)[2], double (&U)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const double l = nan_min(b[2 * q], 0.0), u = nan_max(b[2 * q + 1], 0.0);
+        L[q] = ((l + l) + l) + l;
+        U[q] = ((u + u) + u) + u;
+    }
+}
+
+// Phase 1 under the mesh rule: false where slot `slot` (its 2 x 3 matrix at mb) is live at no pixel of [xa, xb] x [ra, rb]
+// (the header comment has the proof)
+__device__ __forceinline__ bool mesh_keep(const MeshMosaicArgs& a, long long mb, long long slot, double xa, double xb, double ra,
+                                          double rb) {
+    double m[6];
+#pragma unroll
+    for (int r = 0; r < 2; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
+    bool finite = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
+    if (!finite) return false;  // X0 or Y0 is +-inf or NaN at every pixel, and X or Y with it
+    double L[2], U[2];
+    mesh_widening(a.bounds + slot * 4, L, U);
+    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
+    const double X0 = (m[0] * xa + m[1] * ra) + m[2], X1 = (m[0] * xb + m[1] * ra) + m[2];
+    const double X2 = (m[0] * xa + m[1] * rb) + m[2], X3 = (m[0] * xb + m[1] * rb) + m[2];
+    const double Y0 = (m[3] * xa + m[4] * ra) + m[5], Y1 = (m[3] * xb + m[4] * ra) + m[5];
+    const double Y2 = (m[3] * xa + m[4] * rb) + m[5], Y3 = (m[3] * xb + m[4] * rb) + m[5];
+    // (a NaN corner or bound proves nothing: every comparison is false, the source stays)
+    const bool missx = (X0 + U[0] < -1.0 && X1 + U[0] < -1.0 && X2 + U[0] < -1.0 && X3 + U[0] < -1.0) ||
+                       (X0 + L[0] > W1 + 1.0 && X1 + L[0] > W1 + 1.0 && X2 + L[0] > W1 + 1.0 && X3 + L[0] > W1 + 1.0);
+    const bool missy = (Y0 + U[1] < -1.0 && Y1 + U[1] < -1.0 && Y2 + U[1] < -1.0 && Y3 + U[1] < -1.0) ||
+                       (Y0 + L[1] > H1 + 1.0 && Y1 + L[1] > H1 + 1.0 && Y2 + L[1] > H1 + 1.0 && Y3 + L[1] > H1 + 1.0);
+    return !missx && !missy;
+}
+
+// The affine point (X, Y) = (X0, Y0) moved by the displacement of slot `slot`'s table there: papof_warp_mesh_tensor's rule
+// word for word (mesh.hip: k_warp_mesh, the table read from global memory).  False -- before the table is read -- where the
+// slot's bounds prove that the moved point is outside the frame (the header comment; `slot` is uniform: scalar loads).
+__device__ __forceinline__ bool mesh_point(const MeshMosaicArgs& a, long long slot, double& X, double& Y) {
+    const double X0 = X, Y0 = Y;
+    if (a.cull) {
+        double L[2], U[2];
+        mesh_widening(a.bounds + slot * 4, L, U);
+        if (X0 + U[0] < 0 || X0 + L[0] > (double)(a.W - 1) || Y0 + U[1] < 0 || Y0 + L[1] > (double)(a.H - 1)) return false;
+    }
+    const double* mesh = static_cast<const double*>(a.mesh.data) + slot * a.mesh.stride[0];
+    // mesh coordinates clamped to the mesh; a NaN stays one, takes cell 0 and makes (X, Y) a NaN
+    double gx = (X0 * (double)a.GW) / (double)(a.W - 1), gy = (Y0 * (double)a.GH) / (double)(a.H - 1);
+    gx = gx < 0 ? 0.0 : (gx > (double)a.GW ? (double)a.GW : gx);
+    gy = gy < 0 ? 0.0 : (gy > (double)a.GH ? (double)a.GH : gy);
+    const int cj = gx >= 0 ? std::min((int)gx, a.GW - 1) : 0, ci = gy >= 0 ? std::min((int)gy, a.GH - 1) : 0;
+    const double fx = gx - (double)cj, fy = gy - (double)ci;
+    double dx = 0.0, dy = 0.0;
+#pragma unroll
+    for (int mm = 0; mm <= 1; mm++)
+#pragma unroll
+        for (int nn = 0; nn <= 1; nn++) {
+            const double w = fabs((double)(1 - mm) - fx) * fabs((double)(1 - nn) - fy);
+            const long long e = (ci + nn) * a.mesh.stride[1] + (cj + mm) * a.mesh.stride[2];
+            dx += mesh[e] * w;
+            dy += mesh[e + a.mesh.stride[3]] * w;
+        }
+    X = X0 + dx;
+    Y = Y0 + dy;
+    return true;
+}
+
 // k_mosaic_overlap's phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its
 // matrices) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order; returns
 // their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
@@ -429,10 +573,10 @@ __device__ __forceinline__ bool slot_live(const RayArgs& a, long long s, long lo
 }
 
 // A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER; or ProjArgs:
-// BlendArgs under the projective rule; or RayArgs: BlendArgs under the ray rule
+// BlendArgs under the projective rule; or RayArgs: BlendArgs under the ray rule; or MeshMosaicArgs: BlendArgs under the mesh rule
 template <int FD, int MODE, int CAP, int TY, typename A>
 __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile0, long long out0) {
-    constexpr bool BLEND = std::is_same<A, BlendArgs>::value || kProjective<A> || kRay<A>;
+    constexpr bool BLEND = std::is_same<A, BlendArgs>::value || kProjective<A> || kRay<A> || kMesh<A>;
     static_assert(BLEND || MODE != PAPOF_MOSAIC_FEATHER, "k_mosaic: FEATHER is a blend mode");
     constexpr int NT = kMosTX * TY;
     constexpr int CH = MODE == PAPOF_MOSAIC_MEDIAN ? 1 : 4;  // channels per walk of the list
@@ -467,6 +611,8 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
                 if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
             } else if constexpr (kRay<A>) {
                 if (keep && a.cull) keep = ray_keep(a, mo + k * a.mat.stride[1], lo, hi);
+            } else if constexpr (kMesh<A>) {
+                if (keep && a.cull) keep = mesh_keep(a, mo + k * a.mat.stride[1], o * a.n_src + k, xa, xb, ra, rb);
             } else if (keep && a.cull) {
                 double m[6];
                 const long long mb = mo + k * a.mat.stride[1];
@@ -536,6 +682,8 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
                     for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
                 X = (m[0] * xd + m[1] * rd) + m[2];
                 Y = (m[3] * xd + m[4] * rd) + m[5];
+                if constexpr (kMesh<A>)
+                    if (!mesh_point(a, o * a.n_src + k, X, Y)) continue;
             }
             if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) continue;  // (false for a NaN)
             const Bilinear t = taps_at(X, Y, a.H, a.W);
@@ -838,17 +986,41 @@ static bool ray_tables(RayArgs& a, const papof_tensor* cols, const papof_tensor*
     return true;
 }
 
-// papof_mosaic_blend_tensor (A = BlendArgs), papof_mosaic_projective_tensor (A = ProjArgs) and papof_mosaic_ray_tensor (A =
-// RayArgs, with its tables)
+// What papof_mosaic_mesh_tensor takes beyond the blend call
+struct MeshTables {
+    const papof_tensor* mesh;
+    int grid_rows, grid_cols;
+    void* workspace;
+    long long workspace_bytes;
+};
+
+// The tables of the mesh rule, checked and gathered (the grid's bounds are papof_warp_mesh_tensor's, against the frames)
+static bool mesh_tables(MeshMosaicArgs& a, const MeshTables* t, int height, int width, int n_out, int n_src) {
+    if (!t || !described(t->mesh, {PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return false;
+    const int gh = t->grid_rows, gw = t->grid_cols;
+    if (gh < 1 || gw < 1 || gh > PAPOF_MESH_MAX_CELLS || gw > PAPOF_MESH_MAX_CELLS || gh > height - 1 || gw > width - 1) return false;
+    const long long need = papof_mosaic_mesh_workspace(n_out, n_src);
+    if (need < 0 || !t->workspace || t->workspace_bytes < need) return false;
+    a.mesh = *t->mesh;
+    a.bounds = static_cast<const double*>(t->workspace);
+    a.GH = gh;
+    a.GW = gw;
+    return true;
+}
+
+// papof_mosaic_blend_tensor (A = BlendArgs), papof_mosaic_projective_tensor (A = ProjArgs), papof_mosaic_ray_tensor (A =
+// RayArgs, with its tables) and papof_mosaic_mesh_tensor (A = MeshMosaicArgs, with its tables and workspace)
 template <typename A>
 static int mosaic_blend(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
                         const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width, const int* sources,
                         const papof_tensor* matrices, const papof_tensor* gains, int mode, const papof_tensor* out,
                         const papof_tensor* count, void* stream, const papof_tensor* cols = nullptr,
-                        const papof_tensor* rows = nullptr) {
+                        const papof_tensor* rows = nullptr, const MeshTables* tables = nullptr) {
     A b{};
     if constexpr (kRay<A>)
         if (!ray_tables(b, cols, rows)) return PAPOF_EINVAL;
+    if constexpr (kMesh<A>)
+        if (!mesh_tables(b, tables, height, width, n_out, n_src)) return PAPOF_EINVAL;
     if (!mosaic_args_from(b, h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                           matrices))
         return PAPOF_EINVAL;
@@ -861,6 +1033,12 @@ static int mosaic_blend(papof_handle* h, int n_frames, int height, int width, in
         if (!gains && mode != PAPOF_MOSAIC_FEATHER)  // every gain 1: the instances papof_mosaic_tensor launches
             return launch_mosaic(static_cast<hipStream_t>(stream), static_cast<const MosaicArgs&>(b), n_out, mode);
     if (gains) b.gains = *gains;
+    if constexpr (kMesh<A>)
+        if (b.cull)  // the extremes of every slot's table, ahead of k_mosaic on the stream
+            PAPOF_TRY(launch_tiles((long long)n_out * n_src, 1, [&](dim3 grid, long long s0, long long f0) {
+                hipLaunchKernelGGL(k_mesh_bounds, grid, dim3(64), 0, static_cast<hipStream_t>(stream), b.mesh, b.GH + 1,
+                                   b.GW + 1, static_cast<double*>(tables->workspace), s0, f0);
+            }));
     return launch_mosaic(static_cast<hipStream_t>(stream), b, n_out, mode);
 }
 
@@ -946,6 +1124,22 @@ extern "C" int papof_mosaic_overlap_ray_tensor(papof_handle* h, int n_frames, in
                                                long long* sums, long long* counts, void* stream) {
     return mosaic_overlap<RayArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width, sources,
                                    matrices, step, bound, sums, counts, stream, cols, rows);
+}
+
+extern "C" long long papof_mosaic_mesh_workspace(int n_out, int n_src) {
+    if (n_out < 1 || n_src < 1 || n_src > PAPOF_MOSAIC_MAX_SOURCES) return -1;
+    return 32LL * n_out * n_src;
+}
+
+extern "C" int papof_mosaic_mesh_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                                        const papof_tensor* masks, int n_out, int n_src, int out_height, int out_width,
+                                        const int* sources, const papof_tensor* matrices, const papof_tensor* mesh,
+                                        int grid_rows, int grid_cols, const papof_tensor* gains, int mode,
+                                        const papof_tensor* out, const papof_tensor* count, void* workspace,
+                                        long long workspace_bytes, void* stream) {
+    const MeshTables tables{mesh, grid_rows, grid_cols, workspace, workspace_bytes};
+    return mosaic_blend<MeshMosaicArgs>(h, n_frames, height, width, c, frames, masks, n_out, n_src, out_height, out_width,
+                                        sources, matrices, gains, mode, out, count, stream, nullptr, nullptr, &tables);
 }
 
 // Every instance launch_mosaic dispatches to has a lane per slot (n_src <= 64 * TY), so phase 1's loop over the slots runs once.

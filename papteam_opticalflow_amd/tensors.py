@@ -153,6 +153,12 @@ and `stabilize_video_mesh` chains them behind flow_video_fb and global_motion.
 
     sv = stabilize_video_mesh(frames, 5, layout="NHWC", grid=(16, 16))   # a MeshStabilized: Stabilized's fields, mesh, vertex_motion, support
 
+Full-frame mesh stabilization: `mosaic_mesh` (include/papof.h: papof_mosaic_mesh_tensor) is mosaic with a displacement table per
+(output, source) slot, `neighbour_mesh` makes the tables that register the frames around a mesh-stabilized frame as its own
+table registers it, and `stabilize_video_mesh_full` is stabilize_video_mesh whose borders those frames fill.
+
+    sv = stabilize_video_mesh_full(frames, 5, layout="NHWC", fill_radius=15)   # a MeshStabilizedFull: MeshStabilized's fields, filled
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -178,6 +184,7 @@ Homography = collections.namedtuple("Homography", "motion ok support")
 Stabilized = collections.namedtuple("Stabilized", "video valid transforms motion ok flow timing")
 MeshMotion = collections.namedtuple("MeshMotion", "vertices support residuals")
 MeshStabilized = collections.namedtuple("MeshStabilized", "video valid transforms motion ok flow timing mesh vertex_motion support")
+MeshStabilizedFull = collections.namedtuple("MeshStabilizedFull", MeshStabilized._fields + ("filled",))
 Filtered = collections.namedtuple("Filtered", "video support")
 Denoised = collections.namedtuple("Denoised", "video support flow_fw flow_bw timing")
 Flows = collections.namedtuple("Flows", "flow_fw flow_bw")
@@ -1225,12 +1232,24 @@ def mesh_profiles(residuals, radius):
     tables (T, GH + 1, GW + 1, 2) float64.  C(0) = 0, C(t + 1) = C(t) + r(t) (the profile AT a vertex, not a trajectory);
     S(t) = sum_k g_k C(t + k) / sum_k g_k with path_transforms's weights g_k = exp(-k^2 / (2 (radius / 2)^2)), k in
     [-radius, radius] within the video; D(t) = C(t) - S(t).  radius = 0: D = 0 exactly."""
+    return _profile_tables(_accumulated_profiles(residuals), radius)
+
+
+def _accumulated_profiles(residuals):
+    """C of mesh_profiles: (T, GH + 1, GW + 1, 2) float64, C(0) = 0, C(t + 1) = C(t) + r(t)"""
     import numpy as np
     r = np.asarray(residuals, np.float64)
     n = r.shape[0] + 1
     C = np.zeros((n,) + r.shape[1:])
     for t in range(n - 1):
         C[t + 1] = C[t] + r[t]
+    return C
+
+
+def _profile_tables(C, radius):
+    """D of mesh_profiles from the accumulated profiles C"""
+    import numpy as np
+    n = C.shape[0]
     D = np.zeros_like(C)
     if radius == 0:
         return D
@@ -1321,9 +1340,24 @@ def stabilize_video_mesh(frames, pyramidLevels, *, grid=GRID, radius=15, crop=1.
     the waits, where stabilize_video waits -- and ONE warp_mesh.  Returns MeshStabilized(video, valid, transforms, motion, ok,
     flow, timing as stabilize_video's, mesh (T, GH + 1, GW + 1, 2) float64: the displacement tables, vertex_motion
     (T - 1, GH + 1, GW + 1, 2): mesh_motion's vertices, support (T - 1, GH + 1, GW + 1) int32).  With radius=0 the video and
-    valid are stabilize_video's.  The base matrix is affine, the borders are not filled, the smoothing is neither causal nor
-    adaptive (README).  Every argument error raises before anything is launched; the video is enqueued on the current
+    valid are stabilize_video's.  The base matrix is affine, the borders are not filled (stabilize_video_mesh_full fills
+    them), the smoothing is neither causal nor adaptive (README).  Every argument error raises before anything is launched; the video is enqueued on the current
     stream."""
+    p = _mesh_stabilizer(frames, pyramidLevels, grid, radius, crop, model, iters, scale, min_support, spatial, consistency, layout,
+                         out_dtype, solver)
+    D = mesh_transforms(p.mm, radius)
+    video, valid = _warp_mesh(p.ts, p.descs, p.M, capi.DTYPE_F64, D, *p.grid, layout, p.out_dtype)
+    return MeshStabilized(video, valid, p.M, p.m.motion, p.m.ok, p.flow, p.timing, D, p.mm.vertices, p.mm.support)
+
+
+_MeshStabilizer = collections.namedtuple("_MeshStabilizer", "ts descs grid out_dtype flow timing m mm M")
+
+
+def _mesh_stabilizer(frames, pyramidLevels, grid, radius, crop, model, iters, scale, min_support, spatial, consistency, layout,
+                     out_dtype, solver, check=None):
+    """stabilize_video_mesh and stabilize_video_mesh_full up to their last call: the argument checks (`check`: one more, of
+    the frames' descriptors, before anything is launched), the flows, the global motion m, the mesh motion mm and the
+    sampling matrices M"""
     ts, descs, _, params = _check([("frames", frames)], layout, None, pyramidLevels, min_frames=2, solver=solver)
     code, iters, scale = _check_fit(model, iters, scale)
     (T, H, W, C), _, _ = descs[0]
@@ -1332,6 +1366,8 @@ def stabilize_video_mesh(frames, pyramidLevels, *, grid=GRID, radius=15, crop=1.
     _check_mesh_motion_args(min_support, spatial)
     alphas = _alphas(consistency)
     out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    if check is not None:
+        check()
     f64 = _torch().float64
     if alphas[0]:
         fb = _run_fb(ts, descs, True, T - 1, layout, f64, pyramidLevels, alphas, params)
@@ -1342,9 +1378,7 @@ def stabilize_video_mesh(frames, pyramidLevels, *, grid=GRID, radius=15, crop=1.
     m = _motion_fit(flow, capi.DTYPE_F64, None, code, iters, scale)
     mm = _mesh_motion(flow, capi.DTYPE_F64, occ, _check_pair_matrices(m, T - 1, flow.device), gh, gw, min_support, spatial)
     M = stabilizing_transforms(m, radius, crop, size=(H, W))
-    D = mesh_transforms(mm, radius)
-    video, valid = _warp_mesh(ts, descs, M, capi.DTYPE_F64, D, gh, gw, layout, out_dtype)
-    return MeshStabilized(video, valid, M, m.motion, m.ok, flow, timing, D, mm.vertices, mm.support)
+    return _MeshStabilizer(ts, descs, (gh, gw), out_dtype, flow, timing, m, mm, M)
 
 
 MAX_RADIUS = 16  # include/papof.h: papof_temporal_filter_tensor
@@ -2704,16 +2738,26 @@ _Rule = collections.namedtuple("_Rule", "rows blend overlap tables")
 _AFFINE = _Rule(2, "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", False)
 _PROJECTIVE = _Rule(3, "papof_mosaic_projective_tensor", "papof_mosaic_overlap_projective_tensor", False)
 _RAYS = _Rule(3, "papof_mosaic_ray_tensor", "papof_mosaic_overlap_ray_tensor", True)
+_MESH = _Rule(2, "papof_mosaic_mesh_tensor", None, True)  # the tables: (mesh (n_out, N, GH + 1, GW + 1, 2), GH, GW)
+
+
+def _table_args(tables):
+    """what follows the matrices in the entry points of a rule with tables: the ray rule's (cols, rows), or the mesh rule's
+    (mesh (n_out * N, GH + 1, GW + 1, 2), GH, GW)"""
+    if tables and tables[0].dim() == 4:
+        mesh, gh, gw = tables
+        return ctypes.byref(_vertex_struct(mesh)), gh, gw
+    return tuple(ctypes.byref(_table_struct(t)) for t in tables)
 
 
 def _mosaic_head(ts, descs, src, matrices, m_code, masks, Hc, Wc, tables):
-    """the arguments that every entry point of the mosaics begins with, the ray rule's tables behind the matrices (a byref
+    """the arguments that every entry point of the mosaics begins with, the rule's tables behind the matrices (a byref
     keeps its descriptor alive)"""
     (T, H, W, C), strides, code = descs[0]
     d_mask = _mask_struct(masks) if masks is not None else None
     return (T, H, W, C, ctypes.byref(_struct(ts[0], strides, code)), _ref(d_mask), int(src.shape[0]), int(src.shape[1]), Hc, Wc,
             ctypes.c_void_p(src.data_ptr()), ctypes.byref(_struct(matrices, tuple(matrices.stride()), m_code)),
-            *(ctypes.byref(_table_struct(t)) for t in tables))
+            *_table_args(tables))
 
 
 def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_dtype, count=True, gains=None, rule=_AFFINE,
@@ -2721,13 +2765,16 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     """papof_mosaic_tensor on checked arguments: src the int32 (n_out, N) sources on the frames' device, masks uint8 or None;
     count False: no count (None is returned for it; mode "first" then stops at the first live source).  With gains (checked)
     or mode "feather": papof_mosaic_blend_tensor.  rule _PROJECTIVE: matrices (n_out, N, 3, 3), papof_mosaic_projective_tensor.
-    rule _RAYS: tables the checked (cols, rows), matrices (n_out, N, 3, 3): papof_mosaic_ray_tensor."""
+    rule _RAYS: tables the checked (cols, rows), matrices (n_out, N, 3, 3): papof_mosaic_ray_tensor.  rule _MESH: tables the
+    checked (mesh, GH, GW): papof_mosaic_mesh_tensor, with its workspace."""
     torch = _torch()
     dev = ts[0].device
     n_out = int(src.shape[0])
     out, d_out = _new_frames(n_out, Hc, Wc, descs[0][0][3], layout, out_dtype, dev)
     cnt = torch.empty((n_out, Hc, Wc), dtype=torch.uint8, device=dev) if count else None
     d_cnt = _mask_struct(cnt) if count else None
+    if rule is _MESH:  # (n_out, N, ...) as (n_out * N, ...): a view where the strides allow, else a copy, held until the launch
+        tables = (tables[0].reshape((-1,) + tuple(tables[0].shape[2:])),) + tuple(tables[1:])
     head = _mosaic_head(ts, descs, src, matrices, m_code, masks, Hc, Wc, tables)
     tail = (MOSAIC_MODES[mode], ctypes.byref(d_out), _ref(d_cnt))
     if rule is _AFFINE and gains is None and mode != "feather":
@@ -2737,22 +2784,30 @@ def _mosaic(ts, descs, src, matrices, m_code, masks, Hc, Wc, mode, layout, out_d
     if gains is not None:
         d_gain = _struct(gains, (gains.stride(0), gains.stride(1), 0, 0),
                          capi.DTYPE_F32 if gains.dtype == torch.float32 else capi.DTYPE_F64)
-    _launch(dev, rule.blend, *head, _ref(d_gain), *tail)
+    ws = None
+    if rule is _MESH:
+        ws = ("papof_mosaic_mesh_workspace", (n_out, int(src.shape[1])), "%d sources per output are too many" % int(src.shape[1]))
+    _launch(dev, rule.blend, *head, _ref(d_gain), *tail, workspace=ws)
     return out, cnt
 
 
 def _mosaic_inputs(rule, ts, descs, sources, matrices, canvas, masks):
     """what the mosaics and their overlaps check alike behind their frames, in mosaic's order: (Hc, Wc, m_code, n_out, N, the
-    host sources or None, masks, the tables); canvas: the size, or with rule.tables (cols, rows), whose lengths are the size"""
+    host sources or None, masks, the tables); canvas: the size, or with _RAYS (cols, rows), whose lengths are the size, or
+    with _MESH (the size, the mesh)"""
     (T, H, W, _), _, _ = descs[0]
     dev = ts[0].device
-    if rule.tables:
+    if rule is _MESH:
+        Hc, Wc = _check_canvas(canvas[0])
+    elif rule.tables:
         Wc, Hc = _check_table("cols", canvas[0], dev), _check_table("rows", canvas[1], dev)
     else:
         Hc, Wc = _check_canvas(canvas)
     m_code, n_out, N = _check_mosaic_matrices(matrices, dev, rule.rows)
     src = _check_sources(sources, n_out, N, T)
     m = _check_masks("masks", masks, T, H, W, dev) if masks is not None else None
+    if rule is _MESH:
+        return Hc, Wc, m_code, n_out, N, src, m, (canvas[1],) + _check_slot_mesh(canvas[1], n_out, N, dev, H, W)
     return Hc, Wc, m_code, n_out, N, src, m, tuple(canvas) if rule.tables else ()
 
 
@@ -3125,8 +3180,7 @@ def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW"
     code, iters, scale = _check_fit(model, iters, scale)
     (T, H, W, C), _, _ = descs[0]
     _check_path(radius, crop, (H, W))
-    if isinstance(fill_radius, bool) or not isinstance(fill_radius, int) or not 0 <= 2 * fill_radius + 1 <= MAX_SOURCES:
-        raise ValueError("fill_radius must be an integer in 0 .. %d, got %r" % ((MAX_SOURCES - 1) // 2, fill_radius))
+    _check_fill_radius(fill_radius)
     out_dtype = _out_dtype(out_dtype, ts[0].dtype)
     torch = _torch()
     flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, params)
@@ -3140,6 +3194,102 @@ def stabilize_video_full(frames, pyramidLevels, *, fill_radius=15, layout="NCHW"
                      "first", layout, torch.uint8)
     valid = own > 0
     return StabilizedFull(video, valid, (count > 0) & ~valid, M, m.motion, m.ok, flow, timing)
+
+
+# ---- full-frame mesh stabilization: the mosaic with a displacement table per slot (include/papof.h: papof_mosaic_mesh_tensor)
+def _check_fill_radius(fill_radius):
+    if isinstance(fill_radius, bool) or not isinstance(fill_radius, int) or not 0 <= 2 * fill_radius + 1 <= MAX_SOURCES:
+        raise ValueError("fill_radius must be an integer in 0 .. %d, got %r" % ((MAX_SOURCES - 1) // 2, fill_radius))
+
+
+def _check_slot_mesh(mesh, n_out, N, dev, H, W):
+    """a (n_out, N, GH + 1, GW + 1, 2) float64 table on `dev` whose grid fits H x W frames: (GH, GW)"""
+    torch = _torch()
+    if not isinstance(mesh, torch.Tensor):
+        raise TypeError("mesh must be a torch.Tensor, got %s" % type(mesh).__name__)
+    if mesh.dtype != torch.float64:
+        raise TypeError("mesh must be float64, got %s" % mesh.dtype)
+    if mesh.dim() != 5 or tuple(mesh.shape[:2]) != (n_out, N) or mesh.shape[4] != 2:
+        raise ValueError("mesh must be (n_out, N, GH + 1, GW + 1, 2) with (n_out, N) = %s as the matrices, got shape %s"
+                         % ((n_out, N), tuple(mesh.shape)))
+    if mesh.device != dev:
+        raise ValueError("mesh is on %s, the frames on %s: both must be on one device" % (mesh.device, dev))
+    return _check_grid((int(mesh.shape[2]) - 1, int(mesh.shape[3]) - 1), H, W)
+
+
+def mosaic_mesh(frames, sources, matrices, mesh, size, *, mode="median", masks=None, layout="NCHW", out_dtype=None, gains=None):
+    """mosaic with a spatially varying displacement per source: at output pixel q, source k of output o is sampled at
+    M q + d, M = matrices[o, k] and d the bilinear interpolation of the slot's table mesh[o, k] at the mesh coordinates of
+    M q, clamped to the mesh -- warp_mesh's rule, with a table per (output, source) instead of one per frame.  mesh (n_out, N,
+    GH + 1, GW + 1, 2) float64 (dx, dy) on the frames' device, the vertices of mesh_motion's mesh on the FRAMES' H x W (the
+    table is looked up in the source frame's coordinates); it is passed as (n_out * N, GH + 1, GW + 1, 2): a view where its
+    strides allow (a contiguous tensor, a slice along one of its axes, an expanded one), a copy otherwise.  The source is live
+    where the moved point lies inside its frame (and no tap is masked), and "feather" weighs by the moved point; every other
+    argument, the four modes, the limits (255 sources, 64 for the median) and the result Mosaic(out, count) are mosaic's.  A
+    table of +0.0 gives mosaic's bytes; one source per output, source o = frame o, on a canvas of the frames' size under
+    mode "first" gives warp_mesh's out, and its valid as count.  A tile drops a source only by its matrix's corner box widened
+    by the extremes of the source's table, which a small kernel reduces first: no byte depends on it.
+    include/papof.h (papof_mosaic_mesh_tensor) states the rule exactly; bitwise reproducible.  Every argument error raises
+    before anything is launched; enqueued on the current stream, returns without waiting."""
+    return _mosaic_call(_MESH, frames, sources, matrices, (size, mesh), mode, masks, layout, out_dtype, gains)
+
+
+def neighbour_mesh(mesh_motion, radius, fill_radius):
+    """The displacement tables that go with neighbour_transforms(transforms, motion, fill_radius) when the video is stabilized
+    by stabilizing_transforms and mesh_transforms(mesh_motion, radius): mesh_motion a MeshMotion or its residuals (T - 1,
+    GH + 1, GW + 1, 2).  In float64 on the host (one small copy from the device: a wait), from mesh_profiles's accumulated
+    profile C and tables D = C - S: E[t, slot of s] = D[t] + (C[s] - C[t]) -- the stabilized pixel to frame t by t's own table,
+    then from t to s by what the vertex moved beyond the global motion in between -- in neighbour_transforms's slot order
+    (slot 0: t itself, E[t, 0] = D[t], mesh_transforms's table; slot 2 d - 1: t - d; slot 2 d: t + d), +0.0 where s is
+    outside the video.  Returns (T, 2 fill_radius + 1, GH + 1, GW + 1, 2) float64 on the motion's device, for mosaic_mesh.
+    The profile is the motion AT a vertex's position, not along a trajectory, and registers a neighbour only as well as the
+    profiles do (README)."""
+    import numpy as np
+    r = _check_residuals(mesh_motion)
+    if isinstance(radius, bool) or not isinstance(radius, int) or radius < 0:
+        raise ValueError("radius must be an integer >= 0, got %r" % (radius,))
+    _check_fill_radius(fill_radius)
+    C = _accumulated_profiles(r.detach().to("cpu", _torch().float64).numpy())
+    D = _profile_tables(C, radius)
+    T = C.shape[0]
+    E = np.zeros((T, 2 * fill_radius + 1) + C.shape[1:])
+    for t in range(T):
+        E[t, 0] = D[t]
+        for d in range(1, fill_radius + 1):
+            for slot, s in ((2 * d - 1, t - d), (2 * d, t + d)):
+                if 0 <= s < T:
+                    E[t, slot] = D[t] + (C[s] - C[t])
+    return _torch().from_numpy(E).to(r.device)
+
+
+def stabilize_video_mesh_full(frames, pyramidLevels, *, fill_radius=15, grid=GRID, radius=15, crop=1.0, model="similarity",
+                              iters=5, scale=1.0, min_support=MIN_SUPPORT, spatial=True, consistency=CONSISTENCY,
+                              layout="NCHW", out_dtype=None, **solver):
+    """stabilize_video_mesh whose frames have no empty border: where mesh-stabilized frame t does not cover a pixel, the
+    frames t - 1, t + 1, t - 2, ... t +- fill_radius that saw it supply it, each registered by the global motions AND by its
+    own displacement table -- stabilize_video_mesh's chain with the final warp_mesh replaced by ONE mosaic_mesh(...,
+    mode="first") over neighbour_transforms and neighbour_mesh.  Every argument of stabilize_video_mesh, and fill_radius as
+    stabilize_video_full's.  Returns MeshStabilizedFull: MeshStabilized's fields -- valid (T, H, W) bool as
+    stabilize_video_mesh gives it (slot 0 alone): where it holds, the video is stabilize_video_mesh's byte for byte; mesh
+    (T, GH + 1, GW + 1, 2): the frames' own tables -- and filled (T, H, W) bool: not valid, and supplied by a neighbour.
+    Pixels that are neither stay 0.  With fill_radius=0 the video is stabilize_video_mesh's.  A neighbour registers as well
+    as the vertex profiles do and no better; this is no local inpainting (README).  Every argument error raises before
+    anything is launched; the video is enqueued on the current stream."""
+    p = _mesh_stabilizer(frames, pyramidLevels, grid, radius, crop, model, iters, scale, min_support, spatial, consistency, layout,
+                         out_dtype, solver, check=lambda: _check_fill_radius(fill_radius))
+    torch = _torch()
+    (T, H, W, C), _, _ = p.descs[0]
+    src, mats = neighbour_transforms(p.M, p.m, fill_radius)
+    E = neighbour_mesh(p.mm, radius, fill_radius)
+    video, count = _mosaic(p.ts, p.descs, src, mats, capi.DTYPE_F64, None, H, W, "first", layout, p.out_dtype, rule=_MESH,
+                           tables=(E,) + p.grid)
+    # valid: slot 0 alone, on one channel (a view), through the same kernel -- its count is the frame's own coverage
+    one = p.ts[0][:, :1] if layout == "NCHW" else p.ts[0][..., :1]
+    _, own = _mosaic([one], [descriptor(one, layout)], src[:, :1].contiguous(), mats[:, :1], capi.DTYPE_F64, None, H, W,
+                     "first", layout, torch.uint8, rule=_MESH, tables=(E[:, :1],) + p.grid)
+    valid = own > 0
+    return MeshStabilizedFull(video, valid, p.M, p.m.motion, p.m.ok, p.flow, p.timing, E[:, 0], p.mm.vertices, p.mm.support,
+                              (count > 0) & ~valid)
 
 
 # ---- the homography model: the calls above over 3 x 3 matrices
