@@ -24,14 +24,16 @@
 //
 // papof_mosaic_blend_tensor is the same kernel over BlendArgs: every live sample is multiplied by the gain of its slot, and
 // PAPOF_MOSAIC_FEATHER weighs it by the distance of (X, Y) to the frame's border.  The instances over MosaicArgs (the gain
-// is the constant 1.0 there) are what papof_mosaic_tensor launches, as before, and this call too without gains.
+// is the constant 1.0 there) are what papof_mosaic_tensor launches, and this call too without gains.
+//
+// Every rule below is chosen at compile time by the argument type, and each is stated once: phase 1 is cull_slots with one
+// keep-test per rule (affine_keep, projective_keep, ray_keep, mesh_keep), a pixel's point is slot_point, and whether that
+// point is live (inside the frame, no masked tap) is live_taps.  Both kernels call these.
 //
 // papof_mosaic_projective_tensor and papof_mosaic_overlap_projective_tensor are the same two kernels over ProjArgs: the
 // matrices are 3 x 3 and a pixel's point is (X, Y) = (Nx / D, Ny / D), live only where D > 0 (include/papof.h: projective
-// sampling).  The mapping and the culling are chosen at compile time by the argument type; the instances over MosaicArgs and
-// BlendArgs, and the affine overlap instances, are instruction for instruction what they were (only the overlap kernels'
-// mangled names gained the argument type).
-//   Culling under the projective rule (projective_keep).  Canvas coordinates are >= 0.  D, Nx and Ny are each
+// sampling).
+//   Culling under the projective rule (projective_keep, quotients_keep).  Canvas coordinates are >= 0.  D, Nx and Ny are each
 //   (a x + b r) + c: every step is monotone in x and in r under rounding, overflow to +-inf included.  A NaN at a pixel
 //   arises in one of two ways.  (i) inf - inf in a x + b r, or that sum meeting an infinite c of the other sign: |a x| and
 //   |b r| grow with x and r, so the same infinities meet at the tile's far corner (xb, rb), which is NaN too.  (ii) 0 * inf:
@@ -57,12 +59,12 @@
 //
 // papof_mosaic_ray_tensor and papof_mosaic_overlap_ray_tensor are the same two kernels over RayArgs: the canvas pixel is a
 // direction d = (u_x c_r, s_r, w_x c_r) read from two tables (include/papof.h: ray sampling), and the 3 x 3 matrix is applied
-// to it: (D, Nx, Ny) = rows 2, 0, 1 of m times d, each (a dx + b dy) + c dz.  Chosen at compile time as ProjArgs is; the ray
-// is computed once per pixel, outside the walk.  The instances over MosaicArgs, BlendArgs and ProjArgs are instruction for
-// instruction what they were.
-//   Culling under the ray rule (ray_box, ray_keep).  The corners of a tile bound nothing here (sin is not monotone over 64
-//   columns), so the block bounds the tile's rays by intervals, from the tables themselves: lane x of a wave reads (u, w) of
-//   its column and a butterfly of min and max reduces them over the tile's columns; (s, c) are reduced over its <= 4 rows.
+// to it: (D, Nx, Ny) = rows 2, 0, 1 of m times d, each (a dx + b dy) + c dz.  The ray is computed once per pixel, outside the
+// walk.
+//   Culling under the ray rule (ray_box, ray_keep, quotients_keep).  The corners of a tile bound nothing here (sin is not
+//   monotone over 64 columns), so the block bounds the tile's rays by intervals, from the tables themselves: lane x of a wave
+//   reads (u, w) of its column and a butterfly of min and max reduces them over the tile's columns; (s, c) are reduced over its
+//   <= 4 rows.
 //   These min and max hand a NaN on (nan_min, nan_max; fmin and fmax would drop it).  Only pixels whose values are numbers
 //   matter: a live pixel has D > 0 and X, Y inside, so none of dx, dz, the nine products, D, Nx, Ny is NaN there (a NaN
 //   operand makes every later step NaN).  Call such a pixel clean.
@@ -84,10 +86,9 @@
 //
 // papof_mosaic_mesh_tensor is k_mosaic over MeshMosaicArgs: BlendArgs whose affine point (X0, Y0) is moved by the displacement
 // (dx, dy) of the SLOT's own table, looked up at (X0, Y0) by papof_warp_mesh_tensor's rule (include/papof.h: the mosaic under
-// the mesh rule) -- the borders of a mesh-stabilized frame filled from its neighbours, each registered by its own table.  Chosen
-// at compile time as the other rules are; the instances over MosaicArgs, BlendArgs, ProjArgs and RayArgs are instruction for
-// instruction what they were.  The four entries per (pixel, slot) are read through global addresses: an output at fill radius
-// 15 has 31 tables (143 KB at 17 x 17), too many to stage, few enough to stay in the cache.
+// the mesh rule) -- the borders of a mesh-stabilized frame filled from its neighbours, each registered by its own table.  The
+// four entries per (pixel, slot) are read through global addresses: an output at fill radius 15 has 31 tables (143 KB at
+// 17 x 17), too many to stage, few enough to stay in the cache.
 //   Culling under the mesh rule (k_mesh_bounds, mesh_widening, mesh_keep, mesh_point).  The affine corner box alone is wrong
 //   here: a table can carry a source into a tile that its matrix misses.  k_mesh_bounds, ahead of k_mosaic on the stream, one
 //   wave per slot, reduces the slot's table to lo <= t.dx <= hi over its entries t, and the same for dy, with min and max that
@@ -182,39 +183,75 @@ __device__ __forceinline__ double slot_gain(const BlendArgs& b, long long o, int
 // a sorts before b: a < b, or a is a number and b is NaN
 __device__ __forceinline__ bool sorts_before(double a, double b) { return a < b || (a == a && b != b); }
 
-// Phase 1 over a 3 x 3 matrix (at offset mb): false where the slot is live at no pixel of [xa, xb] x [ra, rb] (the header
-// comment has the proof)
-__device__ __forceinline__ bool projective_keep(const MosaicArgs& a, long long mb, double xa, double xb, double ra, double rb) {
-    double m[9];
+// min and max that hand a NaN on (fmin and fmax drop it)
+__device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+
+// The ROWS x 3 matrix at offset mb
+template <int ROWS>
+__device__ __forceinline__ void load_mat(const MosaicArgs& a, long long mb, double (&m)[3 * ROWS]) {
 #pragma unroll
-    for (int r = 0; r < 3; r++)
+    for (int r = 0; r < ROWS; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
+}
+
+// A matrix row applied to the pixel p = (x, r): (a x + b r) + c; under the ray rule to its ray p = d: (a dx + b dy) + c dz
+template <bool RAY = false>
+__device__ __forceinline__ double row_at(const double* row, const double* p) {
+    return (row[0] * p[0] + row[1] * p[1]) + (RAY ? row[2] * p[2] : row[2]);
+}
+
+// False where an entry of a matrix's first two rows is not finite: X and Y (Nx and Ny, and their quotients) are then +-inf or
+// NaN at every pixel, live nowhere (phase 1 of the header comment, and rule (1) there)
+__device__ __forceinline__ bool rows_finite(const double* m) {
     bool finite = true;
 #pragma unroll
     for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
-    if (!finite) return false;  // Nx or Ny is +-inf or NaN at every pixel, and so is its quotient
-    double v[3][4];             // D, Nx, Ny at the four corners
+    return finite;
+}
+
+// The affine corner box of one coordinate (the header comment, phase 1): true where its values v at the tile's four corners are
+// all < -1 or all > top + 1.  WIDEN: the values are fl(v + U) below and fl(v + L) above (the mesh rule, (d)).  A NaN: false.
+template <bool WIDEN>
+__device__ __forceinline__ bool box_misses(const double (&v)[4], double top, double L, double U) {
+    const auto low = [&](int j) { return WIDEN ? v[j] + L : v[j]; };
+    const auto upp = [&](int j) { return WIDEN ? v[j] + U : v[j]; };
+    return (upp(0) < -1.0 && upp(1) < -1.0 && upp(2) < -1.0 && upp(3) < -1.0) ||
+           (low(0) > top + 1.0 && low(1) > top + 1.0 && low(2) > top + 1.0 && low(3) > top + 1.0);
+}
+
+// Phase 1 over the 2 x 3 matrix m, its first two rows finite: false where the slot is live at no pixel of [xa, xb] x [ra, rb]
+// (the header comment, phase 1; WIDEN: under the mesh rule, its point moved by L[q] <= d <= U[q], the header's (d) there)
+template <bool WIDEN>
+__device__ __forceinline__ bool box_keep(const MosaicArgs& a, const double (&m)[6], double xa, double xb, double ra, double rb,
+                                         const double* L = nullptr, const double* U = nullptr) {
+    const double c[4][2] = {{xa, ra}, {xb, ra}, {xa, rb}, {xb, rb}};
+    double X[4], Y[4];
 #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        const double mx = m[3 * ((q + 2) % 3)], mr = m[3 * ((q + 2) % 3) + 1], mc = m[3 * ((q + 2) % 3) + 2];
-        v[q][0] = (mx * xa + mr * ra) + mc;
-        v[q][1] = (mx * xb + mr * ra) + mc;
-        v[q][2] = (mx * xa + mr * rb) + mc;
-        v[q][3] = (mx * xb + mr * rb) + mc;
+    for (int j = 0; j < 4; j++) {
+        X[j] = row_at(m, c[j]);
+        Y[j] = row_at(m + 3, c[j]);
     }
-    bool nan = false;
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) nan = nan || v[q][j] != v[q][j];
-    if (nan) return true;  // proves nothing
-    double lo[3], hi[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++) {
-        lo[q] = fmin(fmin(v[q][0], v[q][1]), fmin(v[q][2], v[q][3]));
-        hi[q] = fmax(fmax(v[q][0], v[q][1]), fmax(v[q][2], v[q][3]));
-    }
+    // (a NaN corner -- an overflow meeting its opposite -- or bound proves nothing: every comparison is false, the slot stays)
+    const bool missx = box_misses<WIDEN>(X, (double)(a.W - 1), WIDEN ? L[0] : 0.0, WIDEN ? U[0] : 0.0);
+    const bool missy = box_misses<WIDEN>(Y, (double)(a.H - 1), WIDEN ? L[1] : 0.0, WIDEN ? U[1] : 0.0);
+    return !missx && !missy;
+}
+
+// Phase 1 over a 2 x 3 matrix (at offset mb): the corner box of the header comment, phase 1
+__device__ __forceinline__ bool affine_keep(const MosaicArgs& a, long long mb, double xa, double xb, double ra, double rb) {
+    double m[6];
+    load_mat<2>(a, mb, m);
+    const bool box = box_keep<false>(a, m, xa, xb, ra, rb);
+    return rows_finite(m) & box;  // (no short circuit: with it mosaic_overlap measured 2 % slower)
+}
+
+// Rules (2) to (5) of the header comment on the bounds lo[q] <= (D, Nx, Ny)[q] <= hi[q] over a tile, for a matrix that passed
+// rule (1), rows_finite: false where the slot is live at no pixel of the tile.  nan: rule (2)'s test, true where a bound, or a
+// value the bounds were taken from, is a NaN.
+__device__ __forceinline__ bool quotients_keep(const MosaicArgs& a, bool nan, const double (&lo)[3], const double (&hi)[3]) {
+    if (nan) return true;            // proves nothing
     if (!(hi[0] > 0)) return false;  // D > 0 at no pixel
     if (!(lo[0] > 0)) return true;   // the horizon may cross the tile
     const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
@@ -224,24 +261,27 @@ __device__ __forceinline__ bool projective_keep(const MosaicArgs& a, long long m
     return !missx && !missy;
 }
 
-// The projective point of pixel (xd, rd) under the 3 x 3 matrix at mb: false where D is not > 0 (a NaN included)
-__device__ __forceinline__ bool projective_point(const MosaicArgs& a, long long mb, double xd, double rd, double& X, double& Y) {
+// Phase 1 over a 3 x 3 matrix (at offset mb): false where the slot is live at no pixel of [xa, xb] x [ra, rb]: the bounds of
+// D, Nx and Ny are their extremes over the four corners (the header comment has the proof)
+__device__ __forceinline__ bool projective_keep(const MosaicArgs& a, long long mb, double xa, double xb, double ra, double rb) {
     double m[9];
+    load_mat<3>(a, mb, m);
+    if (!rows_finite(m)) return false;  // (1)
+    const double c[4][2] = {{xa, ra}, {xb, ra}, {xa, rb}, {xb, rb}};
+    double lo[3], hi[3];
+    bool nan = false;
 #pragma unroll
-    for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
-    const double D = (m[6] * xd + m[7] * rd) + m[8];
-    X = ((m[0] * xd + m[1] * rd) + m[2]) / D;
-    Y = ((m[3] * xd + m[4] * rd) + m[5]) / D;
-    return D > 0;
+    for (int q = 0; q < 3; q++) {
+        const double* row = m + 3 * ((q + 2) % 3);
+        const double v0 = row_at(row, c[0]), v1 = row_at(row, c[1]), v2 = row_at(row, c[2]), v3 = row_at(row, c[3]);
+        nan = nan || v0 != v0 || v1 != v1 || v2 != v2 || v3 != v3;
+        lo[q] = fmin(fmin(v0, v1), fmin(v2, v3));
+        hi[q] = fmax(fmax(v0, v1), fmax(v2, v3));
+    }
+    return quotients_keep(a, nan, lo, hi);
 }
 
 // ---- the ray rule
-// min and max that hand a NaN on (fmin and fmax drop it)
-__device__ __forceinline__ double nan_min(double a, double b) { return (a != a || b != b) ? a + b : fmin(a, b); }
-__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
-
 // A value that every active lane of the wave holds alike, moved to scalar registers
 __device__ __forceinline__ double wave_uniform(double v) {
     const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
@@ -299,15 +339,9 @@ __device__ __forceinline__ void ray_box(const RayArgs& a, long long x, long long
 // [lo, hi] (ray_box; the header comment has the proof)
 __device__ __forceinline__ bool ray_keep(const MosaicArgs& a, long long mb, const double lo[3], const double hi[3]) {
     double m[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
-    bool finite = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
-    if (!finite) return false;  // Nx or Ny is +-inf or NaN at every pixel, and so is its quotient
-    double blo[3], bhi[3];      // the bounds of D, Nx, Ny
+    load_mat<3>(a, mb, m);
+    if (!rows_finite(m)) return false;  // (1)
+    double blo[3], bhi[3];              // the bounds of D, Nx, Ny
 #pragma unroll
     for (int q = 0; q < 3; q++) {
         const int row = 3 * ((q + 2) % 3);
@@ -324,27 +358,7 @@ __device__ __forceinline__ bool ray_keep(const MosaicArgs& a, long long mb, cons
     bool nan = false;
 #pragma unroll
     for (int q = 0; q < 3; q++) nan = nan || blo[q] != blo[q] || bhi[q] != bhi[q];
-    if (nan) return true;               // proves nothing
-    if (!(bhi[0] > 0)) return false;    // D > 0 at no pixel
-    if (!(blo[0] > 0)) return true;     // the horizon may cross the tile
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
-    // (a quotient inf / inf is NaN: every comparison is false, the source stays)
-    const bool missx = (bhi[1] / blo[0] < -1.0 && bhi[1] / bhi[0] < -1.0) || (blo[1] / blo[0] > W1 + 1.0 && blo[1] / bhi[0] > W1 + 1.0);
-    const bool missy = (bhi[2] / blo[0] < -1.0 && bhi[2] / bhi[0] < -1.0) || (blo[2] / blo[0] > H1 + 1.0 && blo[2] / bhi[0] > H1 + 1.0);
-    return !missx && !missy;
-}
-
-// The point of the ray d under the 3 x 3 matrix at mb: false where D is not > 0 (a NaN included)
-__device__ __forceinline__ bool ray_point(const MosaicArgs& a, long long mb, const double d[3], double& X, double& Y) {
-    double m[9];
-#pragma unroll
-    for (int rr = 0; rr < 3; rr++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
-    const double D = (m[6] * d[0] + m[7] * d[1]) + m[8] * d[2];
-    X = ((m[0] * d[0] + m[1] * d[1]) + m[2] * d[2]) / D;
-    Y = ((m[3] * d[0] + m[4] * d[1]) + m[5] * d[2]) / D;
-    return D > 0;
+    return quotients_keep(a, nan, blo, bhi);
 }
 
 // ---- the mesh rule
@@ -390,32 +404,16 @@ __device__ __forceinline__ void mesh_widening(const double* b, double (&L)[2], d
     }
 }
 
-// Phase 1 under the mesh rule: false where slot `slot` (its 2 x 3 matrix at mb) is live at no pixel of [xa, xb] x [ra, rb]
-// (the header comment has the proof)
+// Phase 1 under the mesh rule: false where slot `slot` (its 2 x 3 matrix at mb) is live at no pixel of [xa, xb] x [ra, rb]: the
+// affine corner box widened by the slot's bounds (the header comment has the proof)
 __device__ __forceinline__ bool mesh_keep(const MeshMosaicArgs& a, long long mb, long long slot, double xa, double xb, double ra,
                                           double rb) {
     double m[6];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
-    bool finite = true;
-#pragma unroll
-    for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
-    if (!finite) return false;  // X0 or Y0 is +-inf or NaN at every pixel, and X or Y with it
+    load_mat<2>(a, mb, m);
+    if (!rows_finite(m)) return false;  // X0 or Y0 is +-inf or NaN at every pixel, and X or Y with it
     double L[2], U[2];
     mesh_widening(a.bounds + slot * 4, L, U);
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
-    const double X0 = (m[0] * xa + m[1] * ra) + m[2], X1 = (m[0] * xb + m[1] * ra) + m[2];
-    const double X2 = (m[0] * xa + m[1] * rb) + m[2], X3 = (m[0] * xb + m[1] * rb) + m[2];
-    const double Y0 = (m[3] * xa + m[4] * ra) + m[5], Y1 = (m[3] * xb + m[4] * ra) + m[5];
-    const double Y2 = (m[3] * xa + m[4] * rb) + m[5], Y3 = (m[3] * xb + m[4] * rb) + m[5];
-    // (a NaN corner or bound proves nothing: every comparison is false, the source stays)
-    const bool missx = (X0 + U[0] < -1.0 && X1 + U[0] < -1.0 && X2 + U[0] < -1.0 && X3 + U[0] < -1.0) ||
-                       (X0 + L[0] > W1 + 1.0 && X1 + L[0] > W1 + 1.0 && X2 + L[0] > W1 + 1.0 && X3 + L[0] > W1 + 1.0);
-    const bool missy = (Y0 + U[1] < -1.0 && Y1 + U[1] < -1.0 && Y2 + U[1] < -1.0 && Y3 + U[1] < -1.0) ||
-                       (Y0 + L[1] > H1 + 1.0 && Y1 + L[1] > H1 + 1.0 && Y2 + L[1] > H1 + 1.0 && Y3 + L[1] > H1 + 1.0);
-    return !missx && !missy;
+    return box_keep<true>(a, m, xa, xb, ra, rb, L, U);
 }
 
 // The affine point (X, Y) = (X0, Y0) moved by the displacement of slot `slot`'s table there: papof_warp_mesh_tensor's rule
@@ -450,46 +448,29 @@ __device__ __forceinline__ bool mesh_point(const MeshMosaicArgs& a, long long sl
     return true;
 }
 
-// k_mosaic_overlap's phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its
-// matrices) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order; returns
-// their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
-// (k_mosaic's phase 1 in a function.  k_mosaic keeps its own text: called from there, this function and slot_live gave its
-// instances another register allocation, and the instances papof_mosaic_tensor launches are to stay the code they were.)
+// Phase 1, for a block of 64 x TY lanes: the slots of output o (src its sources, mo the offset of its matrices, slot0 the index
+// of its first slot) that can be live somewhere in the pixel rectangle [xa, xb] x [ra, rb], compacted into `list` in k order;
+// returns their number.  Ends with a barrier: list, and what the block wrote to LDS before the call, are visible after it.
 template <int TY, typename A>
-__device__ __forceinline__ int cull_slots(const A& a, const int* src, long long mo, double xa, double xb, double ra,
-                                          double rb, unsigned short* list, int* wcount, const double* lo = nullptr,
+__device__ __forceinline__ int cull_slots(const A& a, const int* src, long long mo, long long slot0, double xa, double xb,
+                                          double ra, double rb, unsigned short* list, int* wcount, const double* lo = nullptr,
                                           const double* hi = nullptr) {  // (lo, hi: RayArgs' ray_box, instead of the rectangle)
     constexpr int NT = kMosTX * TY;
     const int tid = threadIdx.y * kMosTX + threadIdx.x;
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
     int total = 0;
     for (int base = 0; base < a.n_src; base += NT) {
         const int k = base + tid;
         bool keep = k < a.n_src && src[k] >= 0;
-        if constexpr (kProjective<A>) {
-            if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
-        } else if constexpr (kRay<A>) {
-            if (keep && a.cull) keep = ray_keep(a, mo + k * a.mat.stride[1], lo, hi);
-        } else if (keep && a.cull) {
-            double m[6];
+        if (keep && a.cull) {
             const long long mb = mo + k * a.mat.stride[1];
-#pragma unroll
-            for (int r = 0; r < 2; r++)
-#pragma unroll
-                for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
-            bool finite = true;
-#pragma unroll
-            for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
-            const double X0 = (m[0] * xa + m[1] * ra) + m[2], X1 = (m[0] * xb + m[1] * ra) + m[2];
-            const double X2 = (m[0] * xa + m[1] * rb) + m[2], X3 = (m[0] * xb + m[1] * rb) + m[2];
-            const double Y0 = (m[3] * xa + m[4] * ra) + m[5], Y1 = (m[3] * xb + m[4] * ra) + m[5];
-            const double Y2 = (m[3] * xa + m[4] * rb) + m[5], Y3 = (m[3] * xb + m[4] * rb) + m[5];
-            // (a NaN corner -- an overflow meeting its opposite -- proves nothing: every comparison is false, the source stays)
-            const bool missx = (X0 < -1.0 && X1 < -1.0 && X2 < -1.0 && X3 < -1.0) ||
-                               (X0 > W1 + 1.0 && X1 > W1 + 1.0 && X2 > W1 + 1.0 && X3 > W1 + 1.0);
-            const bool missy = (Y0 < -1.0 && Y1 < -1.0 && Y2 < -1.0 && Y3 < -1.0) ||
-                               (Y0 > H1 + 1.0 && Y1 > H1 + 1.0 && Y2 > H1 + 1.0 && Y3 > H1 + 1.0);
-            keep = finite && !missx && !missy;
+            if constexpr (kProjective<A>)
+                keep = projective_keep(a, mb, xa, xb, ra, rb);
+            else if constexpr (kRay<A>)
+                keep = ray_keep(a, mb, lo, hi);
+            else if constexpr (kMesh<A>)
+                keep = mesh_keep(a, mb, slot0 + k, xa, xb, ra, rb);
+            else
+                keep = affine_keep(a, mb, xa, xb, ra, rb);
         }
         const unsigned long long vote = __ballot(keep);
         if (threadIdx.x == 0) wcount[threadIdx.y] = __popcll(vote);
@@ -507,69 +488,65 @@ __device__ __forceinline__ int cull_slots(const A& a, const int* src, long long 
     return total;
 }
 
-// k_mosaic's liveness, for k_mosaic_overlap: true where the slot (frame s, matrix at mb) is live at the pixel (xd, rd); then
-// X, Y and the taps are set
-__device__ __forceinline__ bool slot_live(const MosaicArgs& a, long long s, long long mb, double xd, double rd, double& X,
-                                          double& Y, Bilinear& t) {
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
-    double m[6];
-#pragma unroll
-    for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
-    X = (m[0] * xd + m[1] * rd) + m[2];
-    Y = (m[3] * xd + m[4] * rd) + m[5];
-    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
-    t = taps_at(X, Y, a.H, a.W);
-    if (a.mask.data) {
-        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
-        bool masked = false;
-        const long long b = s * a.mask.stride[0];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
-        if (masked) return false;
+// The point (X, Y) of a pixel in slot `slot`, whose matrix is at mb, under the rule of A (include/papof.h): p is the pixel
+// (x, r), under the ray rule its ray.  False where the point does not exist: D is not > 0 (a NaN included), or mesh_point's
+// early-out.
+template <typename A>
+__device__ __forceinline__ bool slot_point(const A& a, long long mb, const double* p, long long slot, double& X, double& Y) {
+    if constexpr (kProjective<A> || kRay<A>) {
+        double m[9];
+        load_mat<3>(a, mb, m);
+        const double D = row_at<kRay<A>>(m + 6, p);
+        X = row_at<kRay<A>>(m, p) / D;
+        Y = row_at<kRay<A>>(m + 3, p) / D;
+        return D > 0;
+    } else {
+        double m[6];
+        load_mat<2>(a, mb, m);
+        X = row_at(m, p);
+        Y = row_at(m + 3, p);
+        if constexpr (kMesh<A>) return mesh_point(a, slot, X, Y);
+        return true;
     }
-    return true;
 }
 
-// slot_live over a 3 x 3 matrix (k_mosaic_overlap over ProjArgs).  An overload with its own text: as a template over the
-// argument type, slot_live gave the affine overlap instances another register allocation.
-__device__ __forceinline__ bool slot_live(const ProjArgs& a, long long s, long long mb, double xd, double rd, double& X,
-                                          double& Y, Bilinear& t) {
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
-    if (!projective_point(a, mb, xd, rd, X, Y)) return false;
-    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
-    t = taps_at(X, Y, a.H, a.W);
-    if (a.mask.data) {
-        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
-        bool masked = false;
-        const long long b = s * a.mask.stride[0];
+// The mask rule: true where a tap of positive weight of frame s is masked
+__device__ __forceinline__ bool taps_masked(const MosaicArgs& a, long long s, const Bilinear& t) {
+    const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
+    bool masked = false;
+    const long long b = s * a.mask.stride[0];
 #pragma unroll
-        for (int j = 0; j < 4; j++)
-            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
-        if (masked) return false;
-    }
-    return true;
+    for (int j = 0; j < 4; j++)
+        masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
+    return masked;
 }
 
-// slot_live under the ray rule (k_mosaic_overlap over RayArgs): d the pixel's ray
-__device__ __forceinline__ bool slot_live(const RayArgs& a, long long s, long long mb, const double d[3], double& X, double& Y,
-                                          Bilinear& t) {
-    const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
-    if (!ray_point(a, mb, d, X, Y)) return false;
-    if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) return false;  // (false for a NaN)
-    t = taps_at(X, Y, a.H, a.W);
-    if (a.mask.data) {
-        const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
-        bool masked = false;
-        const long long b = s * a.mask.stride[0];
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
-        if (masked) return false;
+// Liveness: the taps of the point (X, Y) in frame s, live where the point is inside the frame and, under masks, none of its
+// taps of positive weight is masked (the taps are set only where the point is inside).  Returned by value: through a reference
+// the BlendArgs instances of k_mosaic took 73 VGPRs for 67, a wave per SIMD less.
+struct LiveTaps : Bilinear {
+    bool live;
+};
+// EARLY: leave at the first test that fails, instead of one exit.  The same tests either way; measured,
+// the early exits cost mosaic_overlap 2 % and mosaic_homography's MEDIAN 2.6 %, the single exit mosaic_rays' MEDIAN 3 %.
+template <typename A>
+constexpr bool kEarlyLive = kRay<A>;
+template <bool EARLY>
+__device__ __forceinline__ LiveTaps live_taps(const MosaicArgs& a, long long s, double X, double Y) {
+    LiveTaps t;
+    t.live = X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
+    if constexpr (EARLY) {
+        if (!t.live) return t;
+        static_cast<Bilinear&>(t) = taps_at(X, Y, a.H, a.W);
+        t.live = false;
+        if (a.mask.data)
+            if (taps_masked(a, s, t)) return t;
+        t.live = true;
+    } else if (t.live) {
+        static_cast<Bilinear&>(t) = taps_at(X, Y, a.H, a.W);
+        if (a.mask.data) t.live = !taps_masked(a, s, t);
     }
-    return true;
+    return t;
 }
 
 // A: MosaicArgs (papof_mosaic_tensor), or BlendArgs: the sample of a live slot times its gain, and MODE FEATHER; or ProjArgs:
@@ -596,69 +573,21 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
     const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
 
     // ---- 1. the sources that can reach this tile, in k order
-    int total = 0;
-    {
-        const double xa = (double)x0, xb = (double)std::min(x0 + kMosTX - 1, a.Wc - 1);
-        const double ra = (double)r0, rb = (double)std::min(r0 + TY - 1, (long long)a.Hc - 1);
-        double lo[3], hi[3];  // RayArgs: the bounds of the tile's rays
-        if constexpr (kRay<A>)
-            if (a.cull)
-                ray_box(a, std::min(x0 + (int)threadIdx.x, a.Wc - 1), r0, std::min(r0 + TY - 1, (long long)a.Hc - 1), 1, lo, hi);
-        for (int base = 0; base < a.n_src; base += NT) {
-            const int k = base + tid;
-            bool keep = k < a.n_src && src[k] >= 0;
-            if constexpr (kProjective<A>) {
-                if (keep && a.cull) keep = projective_keep(a, mo + k * a.mat.stride[1], xa, xb, ra, rb);
-            } else if constexpr (kRay<A>) {
-                if (keep && a.cull) keep = ray_keep(a, mo + k * a.mat.stride[1], lo, hi);
-            } else if constexpr (kMesh<A>) {
-                if (keep && a.cull) keep = mesh_keep(a, mo + k * a.mat.stride[1], o * a.n_src + k, xa, xb, ra, rb);
-            } else if (keep && a.cull) {
-                double m[6];
-                const long long mb = mo + k * a.mat.stride[1];
-#pragma unroll
-                for (int r = 0; r < 2; r++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[2] + c * a.mat.stride[3]);
-                bool finite = true;
-#pragma unroll
-                for (int j = 0; j < 6; j++) finite = finite && isfinite(m[j]);
-                const double X0 = (m[0] * xa + m[1] * ra) + m[2], X1 = (m[0] * xb + m[1] * ra) + m[2];
-                const double X2 = (m[0] * xa + m[1] * rb) + m[2], X3 = (m[0] * xb + m[1] * rb) + m[2];
-                const double Y0 = (m[3] * xa + m[4] * ra) + m[5], Y1 = (m[3] * xb + m[4] * ra) + m[5];
-                const double Y2 = (m[3] * xa + m[4] * rb) + m[5], Y3 = (m[3] * xb + m[4] * rb) + m[5];
-                // (a NaN corner -- an overflow meeting its opposite -- proves nothing: every comparison is false, the source stays)
-                const bool missx = (X0 < -1.0 && X1 < -1.0 && X2 < -1.0 && X3 < -1.0) ||
-                                   (X0 > W1 + 1.0 && X1 > W1 + 1.0 && X2 > W1 + 1.0 && X3 > W1 + 1.0);
-                const bool missy = (Y0 < -1.0 && Y1 < -1.0 && Y2 < -1.0 && Y3 < -1.0) ||
-                                   (Y0 > H1 + 1.0 && Y1 > H1 + 1.0 && Y2 > H1 + 1.0 && Y3 > H1 + 1.0);
-                keep = finite && !missx && !missy;
-            }
-            const unsigned long long vote = __ballot(keep);
-            if (threadIdx.x == 0) wcount[threadIdx.y] = __popcll(vote);
-            __syncthreads();
-            int before = total, all = total;
-#pragma unroll
-            for (int w = 0; w < TY; w++) {
-                before += w < (int)threadIdx.y ? wcount[w] : 0;
-                all += wcount[w];
-            }
-            if (keep) list[before + __popcll(vote & ((1ULL << threadIdx.x) - 1ULL))] = (unsigned short)k;
-            total = all;
-            __syncthreads();
-        }
-    }
+    const long long rb = std::min(r0 + TY - 1, (long long)a.Hc - 1);
+    double lo[3], hi[3];  // RayArgs: the bounds of the tile's rays
+    if constexpr (kRay<A>)
+        if (a.cull) ray_box(a, std::min(x0 + (int)threadIdx.x, a.Wc - 1), r0, rb, 1, lo, hi);
+    const int total = cull_slots<TY>(a, src, mo, o * a.n_src, (double)x0, (double)std::min(x0 + kMosTX - 1, a.Wc - 1),
+                                     (double)r0, (double)rb, list, wcount, lo, hi);
     const int x = x0 + (int)threadIdx.x;
     const long long r = r0 + threadIdx.y;
     if (x >= a.Wc || r >= a.Hc) return;  // (no barrier below)
 
     // ---- 2, 3. the walk
-    const double xd = (double)x, rd = (double)r;
     const long long outp = o * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
-    const unsigned char* mk = static_cast<const unsigned char*>(a.mask.data);
     const bool all_sources = a.count.data != nullptr || MODE != PAPOF_MOSAIC_FIRST;
-    double ray[3];  // RayArgs: the pixel's ray, once for every source and channel
-    if constexpr (kRay<A>) ray_of(a, x, r, ray);
+    double p[3] = {(double)x, (double)r};  // the pixel, or (RayArgs) its ray: once for every source and channel
+    if constexpr (kRay<A>) ray_of(a, x, r, p);
     for (int c0 = 0; c0 < a.C; c0 += CH) {
         double acc[CH];
 #pragma unroll
@@ -668,33 +597,10 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
         for (int i = 0; i < total; i++) {
             const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
             const long long s = src[k];
-            const long long mb = mo + k * a.mat.stride[1];
             double X, Y;
-            if constexpr (kProjective<A>) {
-                if (!projective_point(a, mb, xd, rd, X, Y)) continue;
-            } else if constexpr (kRay<A>) {
-                if (!ray_point(a, mb, ray, X, Y)) continue;
-            } else {
-                double m[6];
-#pragma unroll
-                for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) m[3 * rr + c] = load_flow(a.mat, mb + rr * a.mat.stride[2] + c * a.mat.stride[3]);
-                X = (m[0] * xd + m[1] * rd) + m[2];
-                Y = (m[3] * xd + m[4] * rd) + m[5];
-                if constexpr (kMesh<A>)
-                    if (!mesh_point(a, o * a.n_src + k, X, Y)) continue;
-            }
-            if (!(X >= 0 && X <= W1 && Y >= 0 && Y <= H1)) continue;  // (false for a NaN)
-            const Bilinear t = taps_at(X, Y, a.H, a.W);
-            if (mk) {
-                bool masked = false;
-                const long long b = s * a.mask.stride[0];
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    masked = masked || (t.w[j] > 0 && mk[b + t.row[j] * a.mask.stride[1] + t.col[j] * a.mask.stride[2]] != 0);
-                if (masked) continue;
-            }
+            if (!slot_point(a, mo + k * a.mat.stride[1], p, o * a.n_src + k, X, Y)) continue;
+            const LiveTaps t = live_taps<kEarlyLive<A>>(a, s, X, Y);
+            if (!t.live) continue;
             const long long base = s * a.fr.stride[0] + c0 * a.fr.stride[3];
             const double gain = slot_gain(a, o, k);  // (MosaicArgs: the constant 1.0, and 1.0 * x is x: no instruction)
             if (MODE == PAPOF_MOSAIC_MEDIAN) {
@@ -824,7 +730,7 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
         if (a.cull)
             ray_box(a, std::min(sx0 + (int)threadIdx.x, args.nsx - 1) * step, sr0 * step,
                     std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step, step, lo, hi);
-    const int total = cull_slots<kOvTY>(a, src, mo, (double)(sx0 * step),
+    const int total = cull_slots<kOvTY>(a, src, mo, o * a.n_src, (double)(sx0 * step),
                                         (double)(std::min(sx0 + kMosTX - 1, args.nsx - 1) * step), (double)(sr0 * step),
                                         (double)(std::min(sr0 + kOvTY - 1, (long long)args.nsr - 1) * step), list, wcount, lo, hi);
 
@@ -833,18 +739,15 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
     const long long sr = sr0 + threadIdx.y;
     unsigned long long mine = 0;
     if (sx < args.nsx && sr < args.nsr) {
-        const double xd = (double)(sx * step), rd = (double)(sr * step);
-        double ray[3];
-        if constexpr (kRay<A>) ray_of(a, sx * step, sr * step, ray);
+        double p[3] = {(double)(sx * step), (double)(sr * step)};  // the pixel, or (RayArgs) its ray
+        if constexpr (kRay<A>) ray_of(a, sx * step, sr * step, p);
         for (int i = 0; i < total; i++) {
             const int k = __builtin_amdgcn_readfirstlane((int)list[i]);
             const long long s = src[k];
             double X, Y;
-            Bilinear t;
-            if constexpr (kRay<A>) {
-                if (!slot_live(a, s, mo + k * a.mat.stride[1], ray, X, Y, t)) continue;
-            } else if (!slot_live(a, s, mo + k * a.mat.stride[1], xd, rd, X, Y, t))
-                continue;
+            if (!slot_point(a, mo + k * a.mat.stride[1], p, o * a.n_src + k, X, Y)) continue;
+            const LiveTaps t = live_taps<kEarlyLive<A>>(a, s, X, Y);
+            if (!t.live) continue;
             const long long base = s * a.fr.stride[0];
             double y = 0.0;
             for (int ch = 0; ch < a.C; ch++) y = y + sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], t, lut);

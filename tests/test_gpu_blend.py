@@ -306,7 +306,7 @@ def test_overlap_is_the_restatement_integer_for_integer(N):
 @pytest.mark.parametrize("frame,canvas", PAIRS)
 def test_overlap_on_every_frame_and_canvas_pair(frame, canvas):
     """frames of one row, one column and 5 x 4 (W - 1 or H - 1 = 0, taps that collapse) and a canvas of one pixel: the
-    kernel's own copy of the culling and of the liveness test against the restatement, at step 1 and 2, with and without
+    kernel's culling and liveness test against the restatement, at step 1 and 2, with and without
     masks, every frame dtype, 1 .. 4 channels, both layouts"""
     from papteam_opticalflow_amd.tensors import mosaic_overlap
     (H, W), (Hc, Wc) = frame, canvas
@@ -350,6 +350,37 @@ def test_overlap_in_nchw_from_views_and_default_arguments():
     _equal_ints(got.sums, ws, "views sums")
     _equal_ints(got.counts, wc, "views counts")
     assert got.bound == 1.0 and got.sums.is_cuda
+
+
+def test_culling_changes_no_byte(monkeypatch):
+    """PAPOF_MOSAIC_CULL=0 walks every source in every tile: the blend with gains in its four modes and the overlap
+    statistics are the same bytes as with the tile-level culling, at the shapes and matrices of test_gpu_mosaic's test of
+    that name (tiles with no source, with all of them and cut by a frame's edge, entries that are not finite)"""
+    from papteam_opticalflow_amd.tensors import mosaic_overlap
+    T, H, W, N, Hc, Wc = 5, 37, 53, 32, 150, 200
+    rng = np.random.default_rng(21)
+    t = torch.from_numpy(_guide(T, H, W, 3, torch.float32, 22)).cuda()
+    tm = torch.from_numpy(_mats(rng, 2, N, H, W, Hc, Wc)).cuda()
+    src = _sources(rng, 2, N, T)
+    mk = torch.from_numpy(_frame_masks(rng, T, H, W)).cuda()
+    tg = torch.from_numpy(_gains(rng, 2, N)).cuda()
+
+    def both(call):
+        monkeypatch.delenv("PAPOF_MOSAIC_CULL", raising=False)
+        on = call()
+        monkeypatch.setenv("PAPOF_MOSAIC_CULL", "0")
+        off = call()
+        monkeypatch.delenv("PAPOF_MOSAIC_CULL", raising=False)
+        return on, off
+
+    for mode in MODES:
+        (out, cnt), (out0, cnt0) = both(lambda: _blend_call(t, src, tm, (Hc, Wc), mode, tg, mk))
+        assert torch.equal(out.view(torch.int32), out0.view(torch.int32)) and torch.equal(cnt, cnt0), mode
+        assert int(cnt.min()) == 0 and int(cnt.max()) >= 2
+    for step in (1, 2):
+        on, off = both(lambda: mosaic_overlap(t, src, tm, (Hc, Wc), masks=mk, step=step, layout="NHWC"))
+        assert torch.equal(on.sums, off.sums) and torch.equal(on.counts, off.counts), step
+        assert int(on.counts.max()) > 0, step
 
 
 # ---- pipelines and hygiene
