@@ -1153,6 +1153,48 @@ int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequence, const pa
  * papof_match_workspace's; -1 where that call refuses the sizes. */
 long long papof_match_hier_workspace(int n_pairs, int sequence, int height, int width, int stride, int levels);
 
+/* Re-centred block search (match.hip): the hierarchical search says, tile by tile, where the flat search's window is
+ * centred, so that a small structure that moves against a large pan -- blind spot of both: the flat search ends at stride *
+ * search pixels, the hierarchy matches a structure smaller than its top window with the background around it -- is found.
+ * Integer arithmetic throughout: the result is a pure function of the inputs (tests/_recentre_ref.py restates it).  The
+ * arguments are papof_match_hier_tensor's, with levels L in 2 .. 4, and window in 1 .. 32.
+ * Hierarchy.  papof_match_hier_tensor's rule unchanged, down to level 0: d_h(p) for every cell p of the finest grid h_0 x w_0.
+ * Tile origin.  The finest grid is cut into tiles of 32 x 8 cells (32 along x) from (0, 0), the last ones clipped to the
+ * grid.  The origin o = (o_x, o_y) of a tile and item is, per component, the lower median of d_h over the tile's n in-grid
+ * cells: the value of rank (n - 1) / 2 (integer division, ranks from 0) in ascending order.  The tile size is part of the
+ * rule, not of a kernel's launch.
+ * Candidates of the cell p of a tile: o + (ex, ey), |ex|, |ey| <= window, and d_h(p) itself; a candidate that occurs twice
+ * counts once.  d is admissible iff 0 <= x + dx < w_0 and 0 <= y + dy < h_0, papof_match_tensor's test; d_h(p) always is, by
+ * the hierarchy's rule, so every cell has a match even where its whole window is inadmissible.
+ * Cost and argmin.  papof_match_tensor's on grid 0: the clamped-window sum of absolute differences over (2 patch + 1)^2 cells
+ * and the channels + penalty * (|dx| + |dy|); the match is the admissible candidate with the smallest key (cost, dx * dx +
+ * dy * dy, dy, dx), compared lexicographically.
+ * Result.  disp = stride * d and cost on the h_0 x w_0 grid, in papof_match_tensor's shapes and dtypes, so
+ * papof_match_densify_tensor takes them as they are.  Items, `both` and `sequence` as in the hierarchical call.
+ * Two properties follow.  (a) Every cell's key is <= the key of the hierarchical result at that cell: the candidates hold
+ * d_h(p).  (b) On a tile whose origin is (0, 0), with window == search, a cell whose d_h lies within the window gets
+ * papof_match_tensor's result at the finest stride.
+ * Bounds.  |d| <= 277 + 32 = 309 cells per component, so dx * dx + dy * dy <= 190962 < 2^18 and d + 512 lies in 0 .. 1023; a
+ * cost stays at or below 15 * 15 * 4 * 255 + 65535 * 618 = 40730130 < 2^26 (the hierarchical rule's bound with 618 for 554):
+ * the key is still held exactly in 26 + 18 + 10 + 10 bits.
+ * What it is not: the origin is one vector per tile, so a tile that a motion boundary halves serves one side (the other
+ * keeps d_h or what the window happens to hold); a structure whose motion relative to its tile's origin exceeds window cells
+ * is still lost; and the cost is the flat search's on grid 0, not comparable with a coarser level's.
+ * workspace: papof_match_recentre_workspace's bytes, 4-byte aligned -- the hierarchical call's workspace, then one packed
+ * displacement dword per level-0 cell and item (d_h), then one per tile and item (the origins).  Enqueued on `stream` (the
+ * hierarchical call's chain with level 0 writing d_h, k_match_origin: one block per tile and item, k_match_recentre: one
+ * block per tile and item) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: what papof_match_hier_tensor refuses, levels < 2, window outside 1 .. 32, a
+ * workspace below papof_match_recentre_workspace. */
+int papof_match_recentre_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                const papof_tensor* frames2, int height, int width, int c, int stride, int levels, int patch,
+                                int search, int refine, int window, int penalty, int both, const papof_tensor* disp,
+                                const papof_tensor* cost, void* workspace, long long workspace_bytes, void* stream);
+
+/* Bytes of papof_match_recentre_tensor's workspace: papof_match_hier_workspace's + 4 * 2 n_pairs * (h_0 w_0 + ceil(h_0 / 8)
+ * ceil(w_0 / 32)); -1 where the hierarchical call refuses the sizes or levels < 2. */
+long long papof_match_recentre_workspace(int n_pairs, int sequence, int height, int width, int stride, int levels);
+
 /* A full-resolution initial flow and its hole mask from matched displacements (k_match_densify, one lane per pixel).
  * disp, disp_rev: float32 / float64, (item, row, column, {dx, dy}) on the h x w grid of papof_match_tensor (h = height /
  * stride, w = width / stride), in full-resolution pixels: the field to densify and the field of the opposite direction.

@@ -71,7 +71,7 @@ SYMBOLS = [
     "papof_temporal_consistency_tensor", "papof_consistency_workspace", "papof_splat_tensor", "papof_splat_workspace",
     "papof_interp_splat_tensor", "papof_refine_flow_tensor", "papof_refine_workspace", "papof_refine_tables",
     "papof_super_resolve_tensor", "papof_sr_workspace", "papof_match_tensor", "papof_match_workspace",
-    "papof_match_hier_tensor", "papof_match_hier_workspace",
+    "papof_match_hier_tensor", "papof_match_hier_workspace", "papof_match_recentre_tensor", "papof_match_recentre_workspace",
     "papof_match_densify_tensor", "papof_motion_blur_tensor", "papof_decimate_tensor", "papof_upsample_flow_tensor",
     "papof_upsample_tables", "papof_mosaic_tensor", "papof_mosaic_blend_tensor", "papof_mosaic_overlap_tensor", "papof_sor_tiny_shape",
     "papof_homography_workspace", "papof_homography_fit_tensor", "papof_warp_projective_tensor",
@@ -225,6 +225,11 @@ def load():
     L.papof_match_hier_tensor.restype = c_int
     L.papof_match_hier_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
     L.papof_match_hier_workspace.restype = ctypes.c_longlong
+    L.papof_match_recentre_tensor.argtypes = [c_void_p, c_int, c_int, _T, _T, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_int, _T, _T, c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_match_recentre_tensor.restype = c_int
+    L.papof_match_recentre_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
+    L.papof_match_recentre_workspace.restype = ctypes.c_longlong
     L.papof_match_densify_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, c_double, _T, _T, c_void_p]
     L.papof_match_densify_tensor.restype = c_int
     L.papof_motion_blur_tensor.argtypes = [c_void_p, c_int, _T, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _D, _T, c_void_p]

@@ -35,6 +35,13 @@
 // B through clamped global addresses; the choice is block-uniform and both paths read the same values in the same order,
 // so they give the same bytes (PAPOF_MATCH_STAGED=0 sends every tile down the global path).  kSpread = 16: with P = 7 and
 // r = 3 the three tiles are 1012 + 1456 + 2992 dwords = 21.8 KB, so seven blocks share a CU's 160 KB of LDS.
+//
+// Re-centred search (papof_match_recentre_tensor; tests/_recentre_ref.py restates it).  The hierarchical chain runs down to
+// level 0 and leaves d_h there as packed dwords; k_match_origin, one block per 32 x 8 tile and item, selects per component
+// the lower median of the tile's vectors by rank counting in LDS (one writer, no atomics) and writes one packed origin per
+// tile; k_match_recentre<P>, k_match's sibling, stages B's window displaced by that origin and runs k_match's loop on it with
+// k_match_refine's 26 + 18 + 10 + 10 bit key, then takes the lane's own d_h where the window did not hold it.  LDS is
+// k_match's with `window` for `search`: 43264 bytes at window 32, patch 7, three blocks per CU.  All on the caller's stream.
 #include "sampler.h"
 
 #include <algorithm>
@@ -505,6 +512,174 @@ int launch_prepare(hipStream_t st, int n_pairs, int sequence, const papof_tensor
     return PAPOF_OK;
 }
 
+// ---- the re-centred search (papof_match_recentre_tensor; tests/_recentre_ref.py restates it)
+constexpr int kMaxWindow = 32;
+
+struct OriginArgs {
+    const unsigned* dh;  // [item][h][w]: the hierarchy's packed displacements of level 0
+    unsigned* origin;    // [item][tile]: the packed origin of every 32 x 8 tile
+    int h, w;
+};
+
+// blockIdx.x: tile `tile0` + x; blockIdx.y: item `item0` + y; one lane per cell of the tile.  The tile's packed vectors go
+// to LDS; every in-grid lane counts, per component, the cells before its own in the order (value, lane): the lane whose
+// count is the rank (n - 1) / 2 holds the lower median.  Every rank is held by exactly one lane: one writer, no atomics.
+__global__ __launch_bounds__(kTX* kTY) void k_match_origin(const OriginArgs a, long long tile0, long long item0) {
+    __shared__ unsigned vec[kTX * kTY];
+    __shared__ int med[2];
+    const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
+    const long long tx = (a.w + kTX - 1) / kTX, ty = (a.h + kTY - 1) / kTY, tile = tile0 + blockIdx.x;
+    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const int tw = min(kTX, a.w - x0), th = min(kTY, a.h - y0), n = tw * th;  // the tile clipped to the grid
+    const long long item = item0 + blockIdx.y;
+    const bool in = lx < tw && ly < th;
+    const unsigned mine = in ? a.dh[item * a.h * a.w + (long long)(y0 + ly) * a.w + x0 + lx] : 0u;
+    vec[tid] = mine;
+    __syncthreads();
+    if (in) {
+        const int mx = unpack_dx(mine), my = unpack_dy(mine);
+        int before_x = 0, before_y = 0;
+        for (int j = 0; j < th; j++)
+            for (int i = 0; i < tw; i++) {
+                const int k = j * kTX + i;
+                const unsigned v = vec[k];
+                const int vx = unpack_dx(v), vy = unpack_dy(v);
+                before_x += vx < mx || (vx == mx && k < tid);
+                before_y += vy < my || (vy == my && k < tid);
+            }
+        if (before_x == (n - 1) / 2) med[0] = mx;
+        if (before_y == (n - 1) / 2) med[1] = my;
+    }
+    __syncthreads();
+    if (tid == 0) a.origin[item * (tx * ty) + tile] = pack_d(med[0], med[1]);
+}
+
+struct RecentreArgs {
+    const unsigned* packed;  // level 0's frames [frame][h][w]
+    const unsigned* dh;      // [item][h][w]: the hierarchy's packed displacements
+    const unsigned* origin;  // [item][tile]
+    papof_tensor disp;       // (item, row, column, {dx, dy})
+    papof_tensor cost;       // (item, row, column, -)
+    int h, w, stride, window, penalty;
+    int n_pairs, seq;
+};
+
+// (cost, dx^2 + dy^2, dy, dx) in 26 + 18 + 10 + 10 bits, k_match_refine's key: |d| <= 277 + 32 = 309 < 512 per component,
+// dx^2 + dy^2 <= 2 * 309^2 = 190962 < 2^18, a cost of at most 15 * 15 * 4 * 255 + 65535 * 618 = 40730130 < 2^26
+__device__ __forceinline__ unsigned long long wide_key(unsigned sad, int dx, int dy, int penalty) {
+    const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
+    const unsigned long long c = sad + (unsigned)(penalty * (ax + ay));
+    return (c << 38) | ((unsigned long long)(unsigned)(dx * dx + dy * dy) << 20) | ((unsigned long long)(unsigned)(dy + 512) << 10) |
+           (unsigned long long)(unsigned)(dx + 512);
+}
+
+// k_match's sibling: the same tile, lanes, LDS tiles (sizes at `window` for `search`), register rows of kG candidates and
+// running 64-bit key, with B's window displaced by the tile's origin (ox, oy) -- the candidates are d = o + e, |ex|, |ey| <=
+// window -- and with k_match_refine's wider key.  The rows and groups that no cell of the tile may take are skipped with the
+// origin added.  Then the lane's own d_h(p): where it lies inside the window it HAS been evaluated from LDS (it is
+// admissible, so neither its row nor its group was skipped) and counts once; where it lies outside, the lane reads B's
+// (2 P + 1)^2 cells through clamped global addresses -- the values the staged window would hold, were it wider.
+template <int P>
+__global__ __launch_bounds__(kTX* kTY) void k_match_recentre(const RecentreArgs a, long long tile0, long long item0) {
+    extern __shared__ __align__(16) unsigned smem_recentre[];
+    constexpr int WN = 2 * P + 1;
+    const int s = a.window, h = a.h, w = a.w, ng = groups_of(s);
+    const int AW = a_width(P), AH = a_height(P), BW = b_width(P, s), BH = b_height(P, s);
+    unsigned* const As = smem_recentre;
+    unsigned* const Bs = As + AW * AH;
+
+    const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
+    const long long tx = (w + kTX - 1) / kTX, ty = (h + kTY - 1) / kTY, tile = tile0 + blockIdx.x;
+    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const int x = x0 + lx, y = y0 + ly;
+    const long long item = item0 + blockIdx.y, cells = (long long)h * w;
+    const bool back = item >= a.n_pairs;
+    const long long pair = back ? item - a.n_pairs : item;
+    const long long first = pair, second = a.seq ? pair + 1 : a.n_pairs + pair;
+    const unsigned* const A = a.packed + (back ? second : first) * cells;
+    const unsigned* const B = a.packed + (back ? first : second) * cells;
+    const unsigned org = a.origin[item * (tx * ty) + tile];  // block-uniform
+    const int ox = unpack_dx(org), oy = unpack_dy(org);
+
+    // ---- stage both tiles, every coordinate clamped into the grid; B's around the origin
+    for (int c = tid; c < AW * AH; c += kTX * kTY) {
+        const int cy = c / AW, cx = c - cy * AW;
+        As[c] = A[(long long)clamp_to(y0 - P + cy, h) * w + clamp_to(x0 - P + cx, w)];
+    }
+    for (int c = tid; c < BW * BH; c += kTX * kTY) {
+        const int cy = c / BW, cx = c - cy * BW;
+        Bs[c] = B[(long long)clamp_to(y0 - P - s + oy + cy, h) * w + clamp_to(x0 - P - s + ox + cx, w)];
+    }
+    __syncthreads();
+
+    // ---- the lane's candidates around the origin: rows of dy, groups of kG along dx
+    unsigned long long best = ~0ULL;
+    for (int eyi = 0; eyi <= 2 * s; eyi++) {
+        const int dy = oy + eyi - s;
+        if (y0 + kTY - 1 + dy < 0 || y0 + dy >= h) continue;  // inadmissible for every cell of the tile
+        const bool row_in = y + dy >= 0 && y + dy < h;
+        for (int g = 0; g < ng; g++) {
+            const int gx = ox + kG * g - s;  // the group's first dx
+            if (x0 + kTX - 1 + gx + kG - 1 < 0 || x0 + gx >= w) continue;  // likewise
+            unsigned acc[kG];
+#pragma unroll
+            for (int j = 0; j < kG; j++) acc[j] = 0;
+            for (int wy = 0; wy < WN; wy++) {
+                const unsigned* const ar = As + (ly + wy) * AW + lx;
+                const unsigned* const br = Bs + (ly + wy + eyi) * BW + lx + kG * g;
+                unsigned av[WN], bv[WN + kG - 1];
+#pragma unroll
+                for (int k = 0; k < WN; k++) av[k] = ar[k];
+#pragma unroll
+                for (int k = 0; k < WN + kG - 1; k++) bv[k] = br[k];
+#pragma unroll
+                for (int k = 0; k < WN; k++)
+#pragma unroll
+                    for (int j = 0; j < kG; j++) acc[j] = __builtin_amdgcn_sad_u8(av[k], bv[k + j], acc[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < kG; j++) {
+                const int dx = gx + j;
+                const bool ok = kG * g + j <= 2 * s && row_in && x + dx >= 0 && x + dx < w;
+                const unsigned long long key = wide_key(acc[j], dx, dy, a.penalty);
+                best = ok && key < best ? key : best;
+            }
+        }
+    }
+    if (x >= w || y >= h) return;
+
+    // ---- the hierarchy's own vector, where the window has not held it
+    const unsigned own = a.dh[item * cells + (long long)y * w + x];
+    const int hx = unpack_dx(own), hy = unpack_dy(own);
+    if (hx - ox < -s || hx - ox > s || hy - oy < -s || hy - oy > s) {
+        unsigned sad = 0;
+#pragma unroll 1
+        for (int wy = 0; wy < WN; wy++) {  // (rolled: the rare path must not set the kernel's register count)
+            const unsigned* const ar = As + (ly + wy) * AW + lx;
+            const unsigned* const br = B + (long long)clamp_to(y - P + wy + hy, h) * w;
+#pragma unroll
+            for (int k = 0; k < WN; k++) sad = __builtin_amdgcn_sad_u8(ar[k], br[clamp_to(x - P + k + hx, w)], sad);
+        }
+        const unsigned long long key = wide_key(sad, hx, hy, a.penalty);
+        best = key < best ? key : best;
+    }
+    const int bdx = (int)(best & 1023) - 512, bdy = (int)((best >> 10) & 1023) - 512;
+    const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    store(a.disp, od, (double)(a.stride * bdx));
+    store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
+    store(a.cost, item * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2],
+          (double)(best >> 38));
+}
+
+template <int P>
+int launch_recentre(hipStream_t st, const RecentreArgs& a, long long items) {
+    const size_t lds = (size_t)lds_bytes(P, a.window);
+    const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
+    return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
+        hipLaunchKernelGGL(k_match_recentre<P>, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
+    });
+}
+
 bool valid_hier(int height, int width, int stride, int levels) {
     if (levels < 1 || levels > kMaxLevels || !valid_frame_size(height, width, stride)) return false;
     const int top = stride << (levels - 1);
@@ -595,10 +770,12 @@ extern "C" long long papof_match_hier_workspace(int n_pairs, int sequence, int h
     return 4 * dwords;
 }
 
-extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
-                                       const papof_tensor* frames2, int height, int width, int c, int stride, int levels, int patch,
-                                       int search, int refine, int penalty, int both, const papof_tensor* disp,
-                                       const papof_tensor* cost, void* workspace, long long workspace_bytes, void* stream) {
+// papof_match_hier_tensor; with `field0` its level 0 leaves packed displacements there ([item][h_0][w_0]) instead of disp and
+// cost (levels >= 2: the re-centred search's d_h)
+static int match_hier(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2, int height,
+                      int width, int c, int stride, int levels, int patch, int search, int refine, int penalty, int both,
+                      const papof_tensor* disp, const papof_tensor* cost, void* workspace, long long workspace_bytes, void* stream,
+                      unsigned* field0) {
     if (!h || refine < 1 || refine > kMaxRefine) return PAPOF_EINVAL;
     const long long need = papof_match_hier_workspace(n_pairs, sequence, height, width, stride, levels);
     if (need < 0) return PAPOF_EINVAL;
@@ -651,7 +828,7 @@ extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequenc
         RefineArgs a{};
         a.packed = packed[l];
         a.parent = field[l + 1];
-        a.out = field[l];
+        a.out = l == 0 ? field0 : field[l];
         a.disp = *disp;
         a.cost = *cost;
         a.h = height / (stride << l);
@@ -663,7 +840,7 @@ extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequenc
         a.penalty = penalty;
         a.n_pairs = n_pairs;
         a.seq = sequence ? 1 : 0;
-        a.last = l == 0;
+        a.last = l == 0 && !field0;
         a.staged = staged;
         int rc;
         switch (patch) {
@@ -678,6 +855,74 @@ extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequenc
         PAPOF_TRY(rc);
     }
     return PAPOF_OK;
+}
+
+extern "C" int papof_match_hier_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                       const papof_tensor* frames2, int height, int width, int c, int stride, int levels, int patch,
+                                       int search, int refine, int penalty, int both, const papof_tensor* disp,
+                                       const papof_tensor* cost, void* workspace, long long workspace_bytes, void* stream) {
+    return match_hier(h, n_pairs, sequence, frames, frames2, height, width, c, stride, levels, patch, search, refine, penalty, both,
+                      disp, cost, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" long long papof_match_recentre_workspace(int n_pairs, int sequence, int height, int width, int stride, int levels) {
+    const long long hier = papof_match_hier_workspace(n_pairs, sequence, height, width, stride, levels);
+    if (hier < 0 || levels < 2) return -1;
+    const long long ch = height / stride, cw = width / stride;
+    const long long per = ch * cw + ((ch + kTY - 1) / kTY) * ((cw + kTX - 1) / kTX);  // d_h and the origins of one item
+    if (2LL * n_pairs > ((1LL << 60) - hier / 4) / per) return -1;
+    return hier + 4 * 2LL * n_pairs * per;
+}
+
+extern "C" int papof_match_recentre_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
+                                           const papof_tensor* frames2, int height, int width, int c, int stride, int levels,
+                                           int patch, int search, int refine, int window, int penalty, int both,
+                                           const papof_tensor* disp, const papof_tensor* cost, void* workspace,
+                                           long long workspace_bytes, void* stream) {
+    if (!h || levels < 2 || window < 1 || window > kMaxWindow) return PAPOF_EINVAL;
+    const long long need = papof_match_recentre_workspace(n_pairs, sequence, height, width, stride, levels);
+    if (need < 0 || workspace_bytes < need) return PAPOF_EINVAL;
+    // the workspace: the hierarchical call's, then d_h [item][h_0][w_0], then the origins [item][tile], 2 n_pairs items each
+    const long long hier = papof_match_hier_workspace(n_pairs, sequence, height, width, stride, levels);
+    const int ch = height / stride, cw = width / stride;
+    unsigned* const dh = static_cast<unsigned*>(workspace) + hier / 4;
+    unsigned* const origin = dh + 2LL * n_pairs * ch * cw;
+    // (every remaining refusal is the hierarchical call's, made before it enqueues anything)
+    PAPOF_TRY(match_hier(h, n_pairs, sequence, frames, frames2, height, width, c, stride, levels, patch, search, refine, penalty, both,
+                         disp, cost, workspace, workspace_bytes, stream, dh));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long items = both ? 2LL * n_pairs : n_pairs;
+    const long long tiles = ((cw + kTX - 1) / (long long)kTX) * ((ch + kTY - 1) / (long long)kTY);
+    OriginArgs o{};
+    o.dh = dh;
+    o.origin = origin;
+    o.h = ch;
+    o.w = cw;
+    PAPOF_TRY(launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
+        hipLaunchKernelGGL(k_match_origin, grid, dim3(kTX, kTY), 0, st, o, t0, i0);
+    }));
+    RecentreArgs a{};
+    a.packed = static_cast<const unsigned*>(workspace);  // level 0's frames come first
+    a.dh = dh;
+    a.origin = origin;
+    a.disp = *disp;
+    a.cost = *cost;
+    a.h = ch;
+    a.w = cw;
+    a.stride = stride;
+    a.window = window;
+    a.penalty = penalty;
+    a.n_pairs = n_pairs;
+    a.seq = sequence ? 1 : 0;
+    switch (patch) {
+        case 1: return launch_recentre<1>(st, a, items);
+        case 2: return launch_recentre<2>(st, a, items);
+        case 3: return launch_recentre<3>(st, a, items);
+        case 4: return launch_recentre<4>(st, a, items);
+        case 5: return launch_recentre<5>(st, a, items);
+        case 6: return launch_recentre<6>(st, a, items);
+        default: return launch_recentre<7>(st, a, items);
+    }
 }
 
 extern "C" int papof_match_densify_tensor(papof_handle* h, int n, int height, int width, int stride, const papof_tensor* disp,

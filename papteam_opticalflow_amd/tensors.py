@@ -87,10 +87,13 @@ which brings motion larger than the objects that carry it within the solver's re
 (`match_levels` of the _ld calls; include/papof.h: papof_match_hier_tensor) the search is hierarchical: the flat search on
 the grid of stride * 2^(levels - 1), then per level twice the parents' vectors +- `refine` cells -- pans and large
 structures beyond stride * search pixels (160 px at the defaults with 3 levels), not objects smaller than the top
-level's window, which keep levels=1.
+level's window, which keep levels=1.  With `recentre` = 1 .. 32 besides (`match_recentre`; papof_match_recentre_tensor) the
+flat search runs once more on the finest grid, its window centred tile by tile on the hierarchy's dominant vector: a small
+object that moves fast against a large pan.
 
     fb = flow_video_ld(frames, layout="NHWC")   # a FlowFB, as flow_video_fb's
     fb = flow_video_ld(frames, layout="NHWC", match_levels=3)   # a fast pan: up to 160 px per frame
+    fb = flow_video_ld(frames, layout="NHWC", match_levels=3, match_recentre=20)   # and a ball that crosses it
 
 Motion blur: `motion_blur` (include/papof.h: papof_motion_blur_tensor) gives a video a longer shutter: every frame becomes
 the weighted mean of the scene at the times of `blur_schedule` around it, each of them what `interpolate` states, summed in
@@ -2169,6 +2172,7 @@ MATCH_SEARCH = 20
 MAX_MATCH_LEVELS = 4  # include/papof.h: papof_match_hier_tensor
 MAX_REFINE = 3
 MAX_TOP_STRIDE = 32
+MAX_WINDOW = 32  # include/papof.h: papof_match_recentre_tensor
 
 Matches = collections.namedtuple("Matches", "disp_fw disp_bw cost_fw cost_bw")
 MatchInit = collections.namedtuple("MatchInit", "init_fw init_bw reliable")
@@ -2196,6 +2200,16 @@ def _check_hier(stride, levels, refine):
     return levels, refine, top
 
 
+def _check_recentre(recentre, levels):
+    """the window of the re-centred search, or None"""
+    if recentre is None:
+        return None
+    recentre = _int_in("recentre", recentre, 1, MAX_WINDOW)
+    if levels < 2:
+        raise ValueError("recentre needs the hierarchical search for its tile origins: levels >= 2, got %d" % levels)
+    return recentre
+
+
 def _check_densify(tol, max_cost):
     """(tol, max_cost as the C ABI's double: -1.0 for None)"""
     tol = _int_in("tol", tol, 0, MAX_TOL)
@@ -2217,8 +2231,9 @@ def _check_match_frames(named, layout, out_dtype, levels, stride, min_frames=1, 
     return ts, descs, out_dtype, params
 
 
-def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, out_dtype, levels=1, refine=1):
-    """papof_match_tensor, or with levels > 1 papof_match_hier_tensor, on the current stream of the frames' device"""
+def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, out_dtype, levels=1, refine=1, recentre=None):
+    """papof_match_tensor, with levels > 1 papof_match_hier_tensor, or with a window papof_match_recentre_tensor, on the
+    current stream of the frames' device"""
     torch = _torch()
     (_, H, W, C), _, _ = descs[0]
     dev = ts[0].device
@@ -2229,7 +2244,13 @@ def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, o
     d_in = [_struct(t, s, c) for t, (_, s, c) in zip(ts, descs)]
     d_disp = _flow_struct(disp, code)
     d_cost = _struct(cost, (cost.stride(0), cost.stride(1), cost.stride(2), 0), code)
-    if levels == 1:
+    if recentre is not None:
+        _launch(dev, "papof_match_recentre_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
+                None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, levels, patch, search, refine, recentre, penalty,
+                1 if both else 0, ctypes.byref(d_disp), ctypes.byref(d_cost),
+                workspace=("papof_match_recentre_workspace", (n_pairs, 1 if sequence else 0, H, W, stride, levels),
+                           "%d pairs of %d x %d are too large to match" % (n_pairs, H, W)))
+    elif levels == 1:
         _launch(dev, "papof_match_tensor", n_pairs, 1 if sequence else 0, ctypes.byref(d_in[0]),
                 None if sequence else ctypes.byref(d_in[1]), H, W, C, stride, patch, search, penalty, 1 if both else 0,
                 ctypes.byref(d_disp), ctypes.byref(d_cost),
@@ -2247,7 +2268,7 @@ def _match(ts, descs, sequence, n_pairs, stride, patch, search, penalty, both, o
 
 
 def match_pairs(im1, im2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
-                out_dtype=None, levels=1, refine=1):
+                out_dtype=None, levels=1, refine=1, recentre=None):
     """Dense block matching of the independent pairs (im1[i], im2[i]): two tensors of one shape, (B, C, H, W) or
     (B, H, W, C) by `layout`, C = 1 .. 4, uint8, float32 or float64 (quantised to uint8 as rint(255 x)), any strides, on a HIP
     device.  Each frame is box-decimated by `stride` (1, 2, 4 or 8) to h x w = H // stride x W // stride cells; every cell of
@@ -2268,23 +2289,36 @@ def match_pairs(im1, im2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATC
     candidates, and the outputs have the same shapes and meaning.  Use it for pans and large structures that move beyond
     40 px.  Do NOT use it for an object smaller than the top level's window ((2 patch + 1) cells of the top stride: 56 px
     at the defaults with levels 3): the top level sees the background around it and the lower levels only refine what it
-    found, so a small object that moves far is lost where the flat search finds it -- keep levels=1 there.
+    found, so a small object that moves far is lost where the flat search finds it -- keep levels=1 there, or give
+    recentre.
+    recentre = None, or a window of 1 .. 32 cells with levels >= 2 (papof_match_recentre_tensor states the rule): the
+    hierarchy's field only says where the flat search looks.  The finest grid is cut into tiles of 32 x 8 cells; a tile's
+    origin is the lower median, per component, of the hierarchy's vectors over its cells; every cell of the tile takes the
+    best of origin + e, |ex|, |ey| <= recentre, and of the hierarchy's own vector, by the flat search's cost and key.  A
+    small object that moves up to stride * recentre pixels against a pan of up to the hierarchy's reach is found.  It is
+    NOT a merge of two fields: the origin is one vector per tile, so a tile that a motion boundary halves serves one side;
+    an object whose motion relative to its tile's dominant motion exceeds stride * recentre is still lost; and the cost
+    returned is the flat search's on the finest grid, not the hierarchy's.
     The workspace comes from PyTorch's allocator; enqueued on the current stream, returns without waiting."""
     stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
     levels, refine, top = _check_hier(stride, levels, refine)
+    recentre = _check_recentre(recentre, levels)
     ts, descs, out_dtype, _ = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, 1, top)
-    return _match(ts, descs, False, descs[0][0][0], stride, patch, search, penalty, bool(both), out_dtype, levels, refine)
+    return _match(ts, descs, False, descs[0][0][0], stride, patch, search, penalty, bool(both), out_dtype, levels, refine, recentre)
 
 
 def match_video(frames, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, both=True, layout="NCHW",
-                out_dtype=None, levels=1, refine=1):
+                out_dtype=None, levels=1, refine=1, recentre=None):
     """match_pairs on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames, each frame decimated once per
     level: T - 1 pairs.  levels, refine: the hierarchical search of match_pairs, for pans and large structures beyond
-    stride * search pixels; an object smaller than the top level's window keeps levels=1."""
+    stride * search pixels; an object smaller than the top level's window keeps levels=1, or takes recentre (match_pairs'
+    re-centred search: a window of 1 .. 32 cells around each tile's dominant vector, with levels >= 2)."""
     stride, patch, search, penalty = _check_match(stride, patch, search, penalty)
     levels, refine, top = _check_hier(stride, levels, refine)
+    recentre = _check_recentre(recentre, levels)
     ts, descs, out_dtype, _ = _check_match_frames([("frames", frames)], layout, out_dtype, 1, top, min_frames=2)
-    return _match(ts, descs, True, descs[0][0][0] - 1, stride, patch, search, penalty, bool(both), out_dtype, levels, refine)
+    return _match(ts, descs, True, descs[0][0][0] - 1, stride, patch, search, penalty, bool(both), out_dtype, levels, refine,
+                  recentre)
 
 
 def _check_size(size, h, w):
@@ -2388,7 +2422,7 @@ def _run_ld(ts, descs, sequence, n_pairs, layout, out_dtype, levels, alphas, par
 
 def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
                   max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, match_levels=1, match_refine=1,
-                  **solver):
+                  match_recentre=None, **solver):
     """Large-displacement flow of the independent pairs (im1[i], im2[i]): match_pairs (stride, patch, search, penalty),
     match_init (tol, max_cost, relax) and flow_pairs_fb(im1, im2, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw,
     ...) -- bit for bit what that call returns given match_init's flows, as FlowFB, so every call built on the flows takes
@@ -2401,11 +2435,14 @@ def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH
     hierarchical search reaches stride * 2^(match_levels - 1) * search pixels (160 at stride 2, 3 levels, search 20) -- use
     it for pans and large structures that move beyond 40 px.  With match_levels=1 motion beyond stride * search is missed
     as before; with more, an object smaller than the top level's window ((2 patch + 1) cells of the top stride) is lost
-    where the flat search finds it: keep match_levels=1 for small objects that move far.  Every argument error raises
-    before anything is launched."""
+    where the flat search finds it: keep match_levels=1 for small objects that move far, or give
+    match_recentre (match_pairs' recentre: None, or a window of 1 .. 32 cells with match_levels >= 2) for a small object
+    that moves against a pan -- within stride * match_recentre pixels of its tile's dominant motion.  Every argument error
+    raises before anything is launched."""
     alphas = _alphas(consistency)
     match = _check_match(stride, patch, search, penalty)
     *hier, top = _check_hier(match[0], match_levels, match_refine)
+    hier.append(_check_recentre(match_recentre, hier[0]))
     densify = (*_check_densify(tol, max_cost), _check_relax(relax))
     ts, descs, out_dtype, params = _check_match_frames([("im1", im1), ("im2", im2)], layout, out_dtype, pyramidLevels, top,
                                                        solver=solver)
@@ -2414,13 +2451,15 @@ def flow_pairs_ld(im1, im2, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH
 
 def flow_video_ld(frames, pyramidLevels=2, *, stride=MATCH_STRIDE, patch=MATCH_PATCH, search=MATCH_SEARCH, penalty=0, tol=1,
                   max_cost=None, relax=RELAX, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, match_levels=1, match_refine=1,
-                  **solver):
+                  match_recentre=None, **solver):
     """flow_pairs_ld on the consecutive pairs (frames[i], frames[i + 1]) of T >= 2 frames: match_video, match_init and
     flow_video_fb(frames, pyramidLevels, init_flow=init_fw, init_flow_bw=init_bw, ...).  match_levels, match_refine as
-    there: the hierarchical search for pans and large structures beyond stride * search pixels, not for small objects."""
+    there: the hierarchical search for pans and large structures beyond stride * search pixels, not for small objects;
+    match_recentre as there: the re-centred search for small objects that move against such a pan."""
     alphas = _alphas(consistency)
     match = _check_match(stride, patch, search, penalty)
     *hier, top = _check_hier(match[0], match_levels, match_refine)
+    hier.append(_check_recentre(match_recentre, hier[0]))
     densify = (*_check_densify(tol, max_cost), _check_relax(relax))
     ts, descs, out_dtype, params = _check_match_frames([("frames", frames)], layout, out_dtype, pyramidLevels, top,
                                                        min_frames=2, solver=solver)
