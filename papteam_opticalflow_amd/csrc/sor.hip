@@ -35,7 +35,10 @@
 //       above from D[k&1][s+64][b-1][62].  Re-using the parity buffer two sweeps later is a write-after-read on the
 //       block's cell 62 w.r.t. the band below, hence a third, practically never binding dependency (below);
 //     * left-new is the lane's own previous result, up-new the previous result of lane l-1, down-old the pending
-//       centre of lane l+1 (DPP wave shifts); right-old is loaded and becomes the next centre;
+//       centre of lane l+1 (DPP wave shifts); right-old is loaded and becomes the next centre.  The up term wU*duU of
+//       lane l is, factor for factor, the left term wL*duL lane l-1 forms in the same step (lane l-1 is one column
+//       ahead: its left cell is lane l's upper cell), so the two PRODUCTS cross the wave, not their three factors: per
+//       step 26 fp64 operations and 8 DPP dword moves (4 for the two products, 4 for down-old) instead of 28 and 10;
 //     * every load is issued R = 8 steps before its use (register software pipeline; 5 memory operations per step
 //       keep R <= 12 within gfx9's 6-bit vmcnt);
 //     * all nb * n_sor tasks are launched at once (one 64-thread workgroup each; a few hundred waves, all
@@ -197,7 +200,8 @@ constexpr unsigned kOob = 0x80000000u;  // byte offset beyond every plane (sor_s
 // i*R + t and immediately refilled with the operands of step (i+1)*R + t, i.e. every global load is issued
 // R steps before its use, so the latency of the write-through du/dv traffic and of the coefficient streams is
 // hidden behind R steps of arithmetic.  A step costs 4 loads + 2 stores; R <= 9 keeps the operations in
-// flight within the 6-bit vmcnt range (63) of gfx9.
+// flight within the 6-bit vmcnt range (63) of gfx9.  (Per step of k_sor_exact<8>'s loop the wave issues ~39 vector
+// instructions -- 26 fp64, 8 DPP moves, 3 moved() -- and 81 in k_sor_fused<8>'s: profiles/step_products_isa.txt.)
 template <int R>
 struct Slots {
     u32x4 pa[R], pb[R], pc[R];  // (phi, xy) (a1, a2) (b1, b2) of this lane's cell at skew position s
@@ -277,20 +281,23 @@ __device__ __forceinline__ void step(const ExactArgs& A, const Task& T, const La
     const double nalpha = A.nalpha;
     const D2 pa = as_d2(c.pa[t]), pb = as_d2(c.pb[t]), pc = as_d2(c.pc[t]), pd = as_d2(c.pd[t]);
     const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duU = from_above<DPP>(S.duL);
-    const double dvU = from_above<DPP>(S.dvL);
-    const double phiU = from_above<DPP>(S.phiL);
     const double duD = from_below<DPP>(duR);
     const double dvD = from_below<DPP>(dvR);
     // Every operand that does not exist (image border, padding) is an exact 0.0 here, so the reference's
     // conditional terms (src/OpticalFlow.cpp:468-495) reduce to adding +-0 in the same order.  Ghost lanes
     // (om1 == 1, a1 == a2 == 0) pass their centre value through: 1*c + 0*(..) == c.
+    // The up term phi(up) * du(up) is the left product of the lane above, formed there in this very step from the same two
+    // registers: it is fetched as a product (before anything is added to it) and added where the reference adds it.  A ghost
+    // lane's product is made of the real phi of its row and its passed-through centre, a dead lane's is 0 * 0; the wave-edge
+    // lane receives 0 (DPP bound_ctrl) or its own product (__shfl_up) -- what its two factors used to give.
     double s1 = S.phiL * S.duL;
     double s2 = S.phiL * S.dvL;
+    const double upU = from_above<DPP>(s1);
+    const double upV = from_above<DPP>(s2);
     s1 += phiC * duR;
     s2 += phiC * dvR;
-    s1 += phiU * duU;
-    s2 += phiU * dvU;
+    s1 += upU;
+    s2 += upV;
     s1 += phiC * duD;
     s2 += phiC * dvD;
     s1 *= nalpha;
@@ -614,9 +621,10 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
 // everything the second sweep needs from the first -- centre (r, j), right (r, j+1), down (r+1, j) at sweep k -- was
 // produced one / two steps earlier by this lane or by lane l + 1, so it is taken from registers; the coefficient cells
 // of step s - 2 are simply kept two steps longer (their slot is refilled after the second sweep has used it).  The two
-// updates of a step are independent chains, so the wave issues them interleaved: a step costs little more than one
-// sweep's, but moves the memory operations of ONE sweep (4 loads + 1 store) for TWO sweeps of work, and the number of
-// sweep-to-sweep hand-offs through memory halves.
+// updates of a step are independent chains, so the wave issues them interleaved: a step costs less than two sweeps'
+// (81 vector instructions against 2 x 39 + the ghost masks, but 0.197 us against 2 x 0.139 for a lone task), and moves
+// the memory operations of ONE sweep (4 loads + 1 store) for TWO sweeps of work, and the number of sweep-to-sweep
+// hand-offs through memory halves.
 //   lanes, first sweep:   0 carrier (below)   1 ghost: row above, sweep k      2..62 real (61 rows)   63 ghost: row below
 //   lanes, second sweep:  0 ghost: row above, sweep k+1      1..61 real (the same 61 rows + 1 = bands climb two rows
 //                         per pair)            62 its first-sweep value IS the row below at sweep k    63 unused
@@ -661,17 +669,16 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
         const u32x4 qbm = ID2 ? (c.pb[t2] & u32x4{0u, 0u, 0u, 0u}) : c.pb[t2];
         const D2 qb = as_d2(qbm);
         const double phiC = qa.x, xy = qa.y;
-        const double duU = from_above<DPP>(S2.duL);
-        const double dvU = from_above<DPP>(S2.dvL);
-        const double phiU = from_above<DPP>(S2.phiL);
         const double duD = from_below<DPP>(duR2);
         const double dvD = from_below<DPP>(dvR2);
         double s1 = S2.phiL * S2.duL;
         double s2 = S2.phiL * S2.dvL;
+        const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
+        const double upV = from_above<DPP>(s2);
         s1 += phiC * duR2;
         s2 += phiC * dvR2;
-        s1 += phiU * duU;
-        s2 += phiU * dvU;
+        s1 += upU;
+        s2 += upV;
         s1 += phiC * duD;
         s2 += phiC * dvD;
         s1 *= nalpha;
@@ -687,17 +694,16 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
     const u32x4 pbm = c.pb[t] & u32x4{F.m1, F.m1, F.m1, F.m1};
     const D2 pb = as_d2(pbm);
     const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duU = from_above<DPP>(S1.duL);
-    const double dvU = from_above<DPP>(S1.dvL);
-    const double phiU = from_above<DPP>(S1.phiL);
     const double duD = from_below<DPP>(duR);
     const double dvD = from_below<DPP>(dvR);
     double s1 = S1.phiL * S1.duL;
     double s2 = S1.phiL * S1.dvL;
+    const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
+    const double upV = from_above<DPP>(s2);
     s1 += phiC * duR;
     s2 += phiC * dvR;
-    s1 += phiU * duU;
-    s2 += phiU * dvU;
+    s1 += upU;
+    s2 += upV;
     s1 += phiC * duD;
     s2 += phiC * dvD;
     s1 *= nalpha;
@@ -949,17 +955,16 @@ __device__ __forceinline__ void g_step(const GroupArgs& A, const Task& T, const 
     }
     const D2 pd = as_d2(raw);
     const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duU = from_above<DPP>(S.duL);
-    const double dvU = from_above<DPP>(S.dvL);
-    const double phiU = from_above<DPP>(S.phiL);
     const double duD = from_below<DPP>(duR);
     const double dvD = from_below<DPP>(dvR);
     double s1 = S.phiL * S.duL;
     double s2 = S.phiL * S.dvL;
+    const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
+    const double upV = from_above<DPP>(s2);
     s1 += phiC * duR;
     s2 += phiC * dvR;
-    s1 += phiU * duU;
-    s2 += phiU * dvU;
+    s1 += upU;
+    s2 += upV;
     s1 += phiC * duD;
     s2 += phiC * dvD;
     s1 *= nalpha;
