@@ -1617,6 +1617,70 @@ int papof_mosaic_mesh_tensor(papof_handle* h, int n_frames, int height, int widt
                              int grid_cols, const papof_tensor* gains, int mode, const papof_tensor* out,
                              const papof_tensor* count, void* workspace, long long workspace_bytes, void* stream);
 
+/* Dirt and dropout removal, 1 of 2 (restore.hip: k_defect_detect): the detector of defects that live in ONE frame of a video
+ * of n_frames = T >= 3 frames -- film dirt and sparkle, dropouts, transmission errors, a bird that crosses one frame --,
+ * Kokaram's spike detection index in its range form, one lane per pixel: a pixel is flagged when, in some channel, it lies
+ * outside the range of the two points it maps to in two other frames by more than `threshold`.  The masks feed
+ * papof_mask_dilate_tensor, papof_fill_holes_tensor (the flows under them) and papof_propagate_tensor.  A parallel call: no
+ * call above changes.
+ * frames, flow_fw, flow_bw: as papof_temporal_filter_tensor takes them -- frames uint8 (x / 255.0), float32 (widened exactly)
+ * or float64, (frame, row, column, channel), any non-negative strides, c = C channels, 1 <= C <= 4; the T - 1 pairs' flows
+ * float32 (widened exactly) or float64, (pair, row, column, {vx, vy}), any non-negative strides, pair t from frame t to
+ * frame t + 1 (flow_fw[t]) and back (flow_bw[t]).
+ * mask: uint8 (frame, row, column), strides [0..2] > 0 (stride[3] ignored): 1 a defect, 0 not.  score: NULL, or float32 (one
+ * round-to-nearest) / float64, (frame, row, column), strides [0..2] > 0.  support: NULL, or uint8 (frame, row, column),
+ * strides [0..2] > 0.  None of them may overlap an input.
+ * threshold: finite, >= 0, in the frames' [0, 1] units; use_check != 0: the consistency test with alpha1, alpha2 (finite,
+ * >= 0).  For the pixel p = (x, r) of frame t, in fp64 without fused multiply-adds:
+ *
+ * references: the frames t + o1 and t + o2, (o1, o2) = (-1, +1) for 0 < t < T - 1, (+1, +2) for t = 0, (-1, -2) for t = T - 1
+ * hops:       each reference is reached from (X, Y) = (x, r) hop by hop exactly as papof_temporal_filter_tensor reaches it: a
+ *             forward hop from frame f to f + 1 through flow_fw[f] checked with flow_bw[f], a backward hop from f to f - 1
+ *             through flow_bw[f - 1] checked with flow_fw[f - 1]; alive &= inside [0, W - 1] x [0, H - 1], and with the check
+ *             alive &= (u + bu)^2 + (v + bv)^2 <= a1 * ((u*u + v*v) + (bu*bu + bv*bv)) + a2  (NaN -> not alive).  Inside the
+ *             video the two references are two chains of one hop; at an end frame they are the first and the second hop of
+ *             ONE chain, which stays dead once it died: reference 2 is then never alive without reference 1.
+ * support   = the number of references alive (0 .. 2)
+ * support < 2:  score = 0.0, mask = 0 -- the pixel is not judged
+ * otherwise:    c_k = frame[t](r, x, k);  g1_k, g2_k = frame[t + o1], frame[t + o2] sampled at their landing points (sampler.h
+ *               taps);  s = 0.0;  for k = 0 .. C - 1:
+ *                   lo = g2_k < g1_k ? g2_k : g1_k;   hi = g2_k > g1_k ? g2_k : g1_k
+ *                   a = c_k - hi;   b = lo - c_k;   d = b > a ? b : a;   s = d > s ? d : s
+ *               (every comparison is false for a NaN: a NaN never raises s -- a NaN c_k or g1_k silences channel k; a NaN g2_k
+ *               leaves lo = hi = g1_k, a range of one point)
+ *               score = s;  mask = s > threshold
+ *
+ * A centre between its two references scores 0.  The samplers are papof_temporal_filter_tensor's.  What the detector is
+ * not: a defect that persists over frames (a line scratch, a sensor pixel under a static camera) agrees with its references
+ * and is not found; a small object that outruns the flow (a ball, rain) is found; a defect of less than the threshold stays;
+ * the end frames, whose references lie on one side, are weaker.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * No device memory besides the tensors is used; no atomics; bitwise reproducible.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (score and support aside) or data pointer, frames that
+ * are not uint8 / float32 / float64, flows or a score that are not float32 / float64, a mask or support that is not uint8, a
+ * negative stride, a zero stride of mask, score or support along an axis in use, n_frames < 3, height or width < 1, c
+ * outside 1 .. 4, a threshold that is not finite or negative, an alpha that is not finite or negative. */
+int papof_defect_detect_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                               const papof_tensor* flow_fw, const papof_tensor* flow_bw, double threshold, int use_check,
+                               double alpha1, double alpha2, const papof_tensor* mask, const papof_tensor* score,
+                               const papof_tensor* support, void* stream);
+
+/* Dirt and dropout removal, 2 of 2 (restore.hip: k_mask_dilate): binary dilation of n_frames masks of height x width by a
+ * square of side 2 * radius + 1 -- the margin that the completion calls ask for around a mask, because a defect's damage to
+ * the flows reaches beyond it.
+ * mask: uint8 (frame, row, column), any non-negative strides (stride[3] ignored); nonzero is set.  out: uint8 (frame, row,
+ * column), strides [0..2] > 0; out must not overlap mask.  radius: 0 .. 32.
+ *
+ * out(t, r, x) = 1 where mask(t, r', x') != 0 for some max(r - radius, 0) <= r' <= min(r + radius, height - 1) and
+ *                max(x - radius, 0) <= x' <= min(x + radius, width - 1); 0 otherwise
+ *
+ * (radius 0: the mask as 0 / 1.)  Enqueued on `stream` and returns without waiting; no device memory besides the tensors.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor or data pointer, a mask or out that is not uint8, a
+ * negative stride, a zero stride of out along an axis in use, n_frames, height or width < 1, radius outside 0 .. 32, or an
+ * out that starts where mask does. */
+int papof_mask_dilate_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* mask, int radius,
+                             const papof_tensor* out, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

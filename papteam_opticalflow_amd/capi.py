@@ -80,6 +80,7 @@ SYMBOLS = [
     "papof_bundle_workspace", "papof_bundle_sums_tensor",
     "papof_mesh_workspace", "papof_mesh_motion_tensor", "papof_warp_mesh_tensor",
     "papof_mosaic_mesh_workspace", "papof_mosaic_mesh_tensor",
+    "papof_defect_detect_tensor", "papof_mask_dilate_tensor",
 ]
 
 
@@ -303,6 +304,11 @@ def load():
     L.papof_propagate_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, _T, c_int, c_int, c_double, c_double,
                                          _T, _T, c_void_p]
     L.papof_propagate_tensor.restype = c_int
+    L.papof_defect_detect_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, c_int, c_double, c_double,
+                                             _T, _T, _T, c_void_p]
+    L.papof_defect_detect_tensor.restype = c_int
+    L.papof_mask_dilate_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, c_int, _T, c_void_p]
+    L.papof_mask_dilate_tensor.restype = c_int
     L.papof_temporal_consistency_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, _T,
                                                     c_double, c_double, c_int, c_int, c_double, c_double, _T, c_void_p,
                                                     ctypes.c_longlong, c_void_p]

@@ -162,6 +162,15 @@ table registers it, and `stabilize_video_mesh_full` is stabilize_video_mesh whos
 
     sv = stabilize_video_mesh_full(frames, 5, layout="NHWC", fill_radius=15)   # a MeshStabilizedFull: MeshStabilized's fields, filled
 
+Dirt and dropout removal: `detect_defects` (include/papof.h: papof_defect_detect_tensor) flags the pixels of a frame that lie
+outside the range of the two points they map to in the neighbouring frames -- defects that live in one frame: dirt,
+sparkle, dropouts, a bird --, `dilate_masks` (papof_mask_dilate_tensor) grows masks on the device, `repair_defects` is one
+pass on given flows (detect, dilate, complete_flows, detect again, then inpaint_video's steps under the masks) and
+`restore_video` runs the passes, estimating the flows again on each pass's video.  Persistent defects (line scratches) are
+not found; a small object that outruns the flow is removed like a defect.
+
+    rv = restore_video(frames, 4, layout="NHWC")   # rv.video, rv.masks, rv.detected (T, H, W) bool, rv.status
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -193,6 +202,9 @@ Denoised = collections.namedtuple("Denoised", "video support flow_fw flow_bw tim
 Flows = collections.namedtuple("Flows", "flow_fw flow_bw")
 Propagated = collections.namedtuple("Propagated", "video status")
 Inpainted = collections.namedtuple("Inpainted", "video status")
+Defects = collections.namedtuple("Defects", "mask score support")
+Restored = collections.namedtuple("Restored", "video masks detected status")
+RestoredVideo = collections.namedtuple("RestoredVideo", Restored._fields + ("flow_fw", "flow_bw", "timing"))
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
 Blurred = collections.namedtuple("Blurred", "video flow_fw flow_bw occlusion timing")
 RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
@@ -1728,6 +1740,164 @@ def _given_or_run_fb(flows, ts, descs, layout, levels, params):
         return (*flows, _check_flows(*flows, (T - 1, 2, H, W), ts[0].device), None)
     fb = _run_fb(ts, descs, True, T - 1, layout, _torch().float64, levels, _alphas(None), params)
     return fb.flow_fw, fb.flow_bw, (capi.DTYPE_F64, capi.DTYPE_F64), fb.timing
+
+
+MAX_DILATE = 32  # include/papof.h: papof_mask_dilate_tensor
+# the defaults of the defect calls: calibrated in tests/test_restore_cpu.py (test_quality_calibration)
+DEFECT_THRESHOLD = 0.08
+DEFECT_DILATE = 2
+DEFECT_PASSES = 2
+MAX_PASSES = 8
+
+
+def _check_threshold(threshold):
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)):
+        raise TypeError("threshold must be a number, got %r" % (threshold,))
+    if not (math.isfinite(threshold) and threshold >= 0):
+        raise ValueError("threshold must be finite and >= 0, got %r" % (threshold,))
+    return float(threshold)
+
+
+def _check_dilate(name, radius):
+    return _int_in(name, radius, 0, MAX_DILATE)
+
+
+def _detect(ts, descs, flows, codes, threshold, alphas):
+    """papof_defect_detect_tensor of the checked video ts[0] on the flows: Defects(mask bool, score float64, support uint8)"""
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    mask = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    score = torch.empty((T, H, W), dtype=torch.float64, device=dev)
+    support = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_m, d_sup = _mask_struct(mask), _mask_struct(support)
+    d_sc = _struct(score, (score.stride(0), score.stride(1), score.stride(2), 0), capi.DTYPE_F64)
+    _launch(dev, "papof_defect_detect_tensor", T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]), ctypes.byref(d_f[1]),
+            threshold, *alphas, ctypes.byref(d_m), ctypes.byref(d_sc), ctypes.byref(d_sup))
+    return Defects(mask.view(torch.bool), score, support)
+
+
+def _dilate(m, radius):
+    """papof_mask_dilate_tensor of the uint8 masks m (T, H, W): a new uint8 tensor of 0 / 1"""
+    T, H, W = (int(s) for s in m.shape)
+    out = _torch().empty((T, H, W), dtype=_torch().uint8, device=m.device)
+    d_m, d_out = _mask_struct(m), _mask_struct(out)
+    _launch(m.device, "papof_mask_dilate_tensor", T, H, W, ctypes.byref(d_m), radius, ctypes.byref(d_out))
+    return out
+
+
+def detect_defects(frames, flow_fw, flow_bw, *, threshold=DEFECT_THRESHOLD, consistency=None, layout="NCHW"):
+    """The defects that live in ONE frame of a video of T >= 3 frames -- film dirt and sparkle, analogue dropouts,
+    transmission errors, a bird that crosses one frame -- found along the flows (Kokaram's spike detection index in its
+    range form): frames (T, C, H, W) or (T, H, W, C) by `layout`, C = 1 .. 4, uint8 (read as x / 255), float32 or float64,
+    any strides, on a HIP device; flow_fw, flow_bw (T - 1, 2, H, W) float32 / float64 on the same device, pair t from frame
+    t to t + 1 and back, as flow_video_fb returns them.  Each pixel of frame t is carried to the frames t - 1 and t + 1
+    (frame 0: 1 and 2; frame T - 1: T - 2 and T - 3), hop by hop as temporal_filter moves it (consistency = (alpha1,
+    alpha2); None, the default: no check); where both are reached its score is the largest amount, over the channels, by
+    which it lies outside the range of the two samples there, and it is flagged where score > threshold (in [0, 1] units).
+    Returns Defects(mask (T, H, W) bool, score (T, H, W) float64, support (T, H, W) uint8: the references reached, 0 .. 2 --
+    with fewer than 2 the pixel is not judged: score 0, not flagged).  include/papof.h (papof_defect_detect_tensor) states
+    the rule exactly.  Not found: a defect that persists over frames (a line scratch, a sensor pixel under a static
+    camera), a defect below the threshold; found though no defect: a small object that outruns the flow (a ball, rain --
+    flow_video_ld's flows help); the end frames, with both references on one side, are weaker.  Enqueued on the current
+    stream; returns without waiting."""
+    alphas = _alphas(consistency)
+    threshold = _check_threshold(threshold)
+    ts, descs, _, _ = _check_video(frames, layout, 1, None, min_frames=3)
+    (T, H, W, _), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
+    return _detect(ts, descs, (flow_fw, flow_bw), codes, threshold, alphas)
+
+
+def dilate_masks(masks, radius):
+    """Masks grown by `radius` pixels (0 .. 32) in every direction -- binary dilation by a square of side 2 radius + 1,
+    clipped to the image: masks (T, H, W) (2-D: one frame) bool / uint8 on a HIP device, nonzero set.  Returns a new
+    (T, H, W) bool tensor (radius 0: masks != 0).  One HIP kernel on the masks' bytes (include/papof.h:
+    papof_mask_dilate_tensor); enqueued on the current stream, returns without waiting."""
+    torch = _torch()
+    radius = _check_dilate("radius", radius)
+    if not isinstance(masks, torch.Tensor):
+        raise TypeError("masks must be a torch.Tensor, got %s" % type(masks).__name__)
+    if masks.dim() == 2:
+        masks = masks.unsqueeze(0)
+    if masks.dim() != 3 or min(masks.shape) < 1:
+        raise ValueError("masks must be (T, H, W) with T, H, W >= 1 (or 2-D: one frame), got shape %s" % (tuple(masks.shape),))
+    if not _on_gpu(masks):
+        raise ValueError("masks must be on a HIP device (cuda:N), got %s" % masks.device)
+    m = _check_masks("masks", masks, *(int(s) for s in masks.shape), masks.device)
+    return _dilate(m, radius).view(torch.bool)
+
+
+def _repair(ts, descs, flows, codes, given, threshold, dilate, radius, relax, alphas, layout, out_dtype):
+    """repair_defects behind its argument checks: `given` the caller's uint8 masks or None"""
+    torch = _torch()
+    grown = lambda d: _dilate((d if given is None else d | (given != 0)).view(torch.uint8), dilate)  # noqa: E731
+    first = _detect(ts, descs, flows, codes, threshold, alphas).mask
+    second = _detect(ts, descs, _complete(flows, grown(first), relax), codes, threshold, alphas).mask
+    detected = first | second
+    m = grown(detected)
+    p = _propagate(ts, descs, m, _complete(flows, m, relax), codes, radius, alphas, layout, torch.float64)
+    video = _fill(p.video, descriptor(p.video, layout), (p.status == 2).view(torch.uint8), relax, layout, out_dtype)
+    return Restored(video, m.view(torch.bool), detected, p.status)
+
+
+def repair_defects(frames, flow_fw, flow_bw, *, masks=None, threshold=DEFECT_THRESHOLD, dilate=DEFECT_DILATE, radius=None,
+                   relax=RELAX, consistency=None, layout="NCHW", out_dtype=None):
+    """One pass of dirt and dropout removal on the caller's flows: frames and flows as detect_defects takes them (T >= 3);
+    masks: None, or (T, H, W) bool / uint8 on the frames' device, pixels to repair whatever the detector says.
+        1. detect_defects on the flows (threshold, consistency);  2. OR with `masks`;  3. dilate_masks by `dilate` (0 .. 32);
+        4. complete_flows under that set (relax);  5. detect_defects on the completed flows -- a large defect drags the flow
+        under it along, and what it hid shows once the flow there is its surroundings';  6. OR with 1. and `masks`;
+        7. dilate_masks by `dilate`;  8. inpaint_video's steps on the flows as they were given under that set: complete_flows,
+        propagate (radius, consistency) into float64, fill_holes (relax) of what is still a hole.
+    Returns Restored(video in `layout` and out_dtype (by default the frames'; pixels outside `masks` are their input values,
+    of the frames' dtype: their bytes), masks (T, H, W) bool: the repaired set of step 7, detected (T, H, W) bool: what the
+    two detections flagged, undilated, status (T, H, W) uint8: 0 kept, 1 filled along the flows, 2 filled spatially).  The
+    defaults were calibrated in tests/test_restore_cpu.py.  Every argument error raises before anything is launched; the
+    video is enqueued on the current stream."""
+    alphas = _alphas(consistency)
+    threshold = _check_threshold(threshold)
+    dilate = _check_dilate("dilate", dilate)
+    relax = _check_relax(relax)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype, min_frames=3)
+    (T, H, W, _), _, _ = descs[0]
+    radius = _check_radius(radius, T)
+    given = None if masks is None else _check_video_masks(ts, descs, masks)
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
+    return _repair(ts, descs, (flow_fw, flow_bw), codes, given, threshold, dilate, radius, relax, alphas, layout, out_dtype)
+
+
+def restore_video(frames, pyramidLevels, *, passes=DEFECT_PASSES, masks=None, threshold=DEFECT_THRESHOLD, dilate=DEFECT_DILATE,
+                  radius=None, relax=RELAX, consistency=None, layout="NCHW", out_dtype=None, **solver):
+    """A video of T >= 3 frames with its one-frame defects removed, `passes` (1 .. 8) passes: pass 0 is flow_video_fb(frames,
+    pyramidLevels, layout=layout, consistency=None, out_dtype=torch.float64, **solver) followed by repair_defects on those
+    flows; every later pass estimates the flows again on the previous pass's video -- the defects no longer drag them
+    along -- and runs repair_defects on the ORIGINAL frames with those flows and masks = `masks` OR everything detected so
+    far.  Returns RestoredVideo(video, masks, detected -- of all passes --, status of the last pass, flow_fw, flow_bw
+    (T - 1, 2, H, W) float64 and timing of the last flow call).  Every argument error raises before anything is launched;
+    the flows are complete on return, the video is enqueued on the current stream behind them."""
+    torch = _torch()
+    alphas = _alphas(consistency)
+    passes = _int_in("passes", passes, 1, MAX_PASSES)
+    threshold = _check_threshold(threshold)
+    dilate = _check_dilate("dilate", dilate)
+    relax = _check_relax(relax)
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, min_frames=3, solver=solver)
+    (T, _, _, _), _, _ = descs[0]
+    radius = _check_radius(radius, T)
+    given = None if masks is None else _check_video_masks(ts, descs, masks)
+    codes = (capi.DTYPE_F64, capi.DTYPE_F64)
+    r, detected = None, None
+    for k in range(passes):
+        src = ts if r is None else [r.video]
+        fb = _run_fb(src, [descriptor(src[0], layout)], True, T - 1, layout, torch.float64, pyramidLevels, _alphas(None), params)
+        known = given if detected is None else (detected if given is None else detected | (given != 0)).view(torch.uint8)
+        r = _repair(ts, descs, (fb.flow_fw, fb.flow_bw), codes, known, threshold, dilate, radius, relax, alphas, layout,
+                    out_dtype if k == passes - 1 else ts[0].dtype)
+        detected = r.detected if detected is None else detected | r.detected
+    return RestoredVideo(r.video, r.masks, detected, r.status, fb.flow_fw, fb.flow_bw, fb.timing)
 
 
 MAX_ITERS = 65536  # include/papof.h: papof_temporal_consistency_tensor
