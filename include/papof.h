@@ -1681,6 +1681,66 @@ int papof_defect_detect_tensor(papof_handle* h, int n_frames, int height, int wi
 int papof_mask_dilate_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* mask, int radius,
                              const papof_tensor* out, void* stream);
 
+/* Motion-compensated deinterlacing (deinterlace.hip: k_deinterlace): n_fields = T >= 4 fields of field_height = Hf rows become T
+ * full frames of 2 Hf rows, one per field (double rate).  Frame t keeps its own field's lines; the lines it lacks have the
+ * parity of fields t - 1 and t + 1, whose flows -- two fields of one parity share a sampling lattice -- are the solver's on the
+ * fields themselves, and are the frame in between those two at time 0.5: papof_interp_tensor's gather rule on the field
+ * lattice, protected per pixel by the phase of the landing rows and by the agreement of the two samples, over a four-tap cubic
+ * of the own field.  A parallel call: no call above changes.
+ * fields: uint8 (x / 255.0), float32 (widened exactly) or float64, (field, row, column, channel), any non-negative strides,
+ * c = C channels, 1 <= C <= 4.  Field k holds the rows of parity p_k = (k + first) & 1 of frame k; first is 0 or 1.
+ * flow_fw, flow_bw: the T - 2 pairs' flows, float32 (widened exactly) or float64, (pair, row, column, {vx, vy}), any
+ * non-negative strides, in FIELD coordinates (rows of Hf): pair k runs from field k to field k + 2 (flow_fw[k]) and back from
+ * field k + 2 to field k (flow_bw[k]).  mode 0 reads no flows: both may be NULL.
+ * video: uint8 / float32 / float64, (frame, row, column, channel) with 2 Hf rows, strides [0..3] > 0; it must not overlap
+ * fields.  confidence: NULL, or float32 (one round-to-nearest) / float64, (frame, row, column) with Hf rows, strides [0..2] >
+ * 0: q of each made pixel.  sigma: finite, > 0, in the fields' [0, 1] units.
+ * For the column x and the field row j of frame t, p = p_t, pm = 1 - p, in fp64 in the stated order without fused multiply-adds;
+ * load is the field's value as fp64, store papof_interp_tensor's (float64 as is, float32 with one round-to-nearest, uint8 =
+ * clamp(rint(255 v), 0, 255), half to even, NaN -> 0), sample the bilinear sampler of papof_interp_tensor on an Hf x W field:
+ *
+ * kept line:  video[t](2 j + p, x, k) = store(load(field[t](j, x, k)))  -- uint8 to uint8: the input's bytes
+ * made line:  video[t](2 j + pm, x, k) = store(out_k), confidence[t](j, x) = q, with
+ *   spatial:  the own field's rows at frame distance -1, +1, -3, +3 of the made line, indices clamped into [0, Hf - 1]:
+ *             a1, b1, a3, b3 = field[t] rows j, j + 1, j - 1, j + 2 for pm = 1 and rows j - 1, j, j - 2, j + 1 for pm = 0
+ *             s_k = (9.0 * (a1_k + b1_k) - (a3_k + b3_k)) * 0.0625           (no clamp)
+ *   mode 0:   out_k = s_k, q = 0 (the bob)
+ *   temporal, 1 <= t <= T - 2:  (u, v) = flow_fw[t - 1](j, x), (bu, bv) = flow_bw[t - 1](j, x); the landing points of
+ *             papof_interp_tensor at time 0.5 on the field lattice,
+ *                 (X0, Y0) = (x + (0.25 * bu - 0.25 * u), j + (0.25 * bv - 0.25 * v)) in field t - 1
+ *                 (X1, Y1) = (x + (0.25 * u - 0.25 * bu), j + (0.25 * v - 0.25 * bv)) in field t + 1
+ *             in_i = 0 <= X_i <= W - 1 and 0 <= Y_i <= Hf - 1 (false for a NaN)
+ *   temporal, t = 0:      one point, (X1, Y1) = (x + 0.5 * u, j + 0.5 * v) in field 1 with (u, v) = flow_fw[1](j, x); in0 = false
+ *   temporal, t = T - 1:  one point, (X0, Y0) = (x + 0.5 * bu, j + 0.5 * bv) in field T - 2 with (bu, bv) = flow_bw[T - 4](j, x);
+ *             in1 = false
+ *   phase:    c_i = in_i ? 1.0 - 2.0 * |Y_i - rint(Y_i)| : 0.0  (rint: half to even) -- a sample on a field line counts fully, one
+ *             halfway between two lines, which carries no detail, does not count
+ *   samples:  g0_k, g1_k = field[t - 1], field[t + 1] sampled at (X0, Y0), (X1, Y1), each only where c_i > 0
+ *   c0 > 0 and c1 > 0:   m_k = (c0 * g0_k + c1 * g1_k) / (c0 + c1)
+ *                        D = 0.0; for k = 0 .. C - 1: d = g0_k - g1_k; D = D + d * d
+ *                        q = (c1 > c0 ? c1 : c0) / (1.0 + (D / C) / (sigma * sigma))
+ *   only c_i > 0:        m_k = gi_k, q = 0.5 * c_i
+ *   neither:             q = 0.0
+ *   blend:    out_k = s_k where q == 0 -- every NaN or infinite flow and every point out of the image: a NaN never reaches the
+ *             output through a zero weight --, else out_k = (1.0 - q) * s_k + q * m_k
+ *
+ * A static scene with zero flows has c0 = c1 = 1, D = 0, q = 1 and out_k = 0 * s_k + g0_k: the interior frames are the
+ * progressive video exactly.  What it is not: at the critical velocity (an odd number of frame rows per field) the
+ * neighbouring fields hold the current field's lines, c = 0 and the output is mode 0's; the end frames, with one neighbour
+ * and q <= 0.5, are weaker; the flows assume motion linear over two field periods; no cadence or telecine detection; no model
+ * of chroma subsampling.
+ * One lane writes both rows 2 j and 2 j + 1 of its column: every output element is written once.  Enqueued on `stream` (the
+ * caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.  No device memory besides
+ * the tensors is used; no atomics; bitwise reproducible.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (confidence aside, and the flows in mode 0) or data
+ * pointer, fields or a video that are not uint8 / float32 / float64, flows or a confidence that are not float32 / float64, a
+ * negative stride, a zero stride of video or confidence along an axis in use, n_fields < 4, field_height < 1 or > 2^30 - 1,
+ * width < 1, c outside 1 .. 4, first or mode outside {0, 1}, a sigma that is not finite or not > 0, or a video that starts
+ * where fields does. */
+int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field_height, int width, int c, const papof_tensor* fields,
+                             int first, int mode, const papof_tensor* flow_fw, const papof_tensor* flow_bw, double sigma,
+                             const papof_tensor* video, const papof_tensor* confidence, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -1,0 +1,206 @@
+// papteam_opticalflow_amd/csrc/deinterlace.hip -- motion-compensated deinterlacing of a sequence of fields along the flows
+// between fields of the same parity (papof_deinterlace_tensor): one full frame per field, double rate.
+//
+// Why.  Interlaced material -- broadcast archives, tape transfers -- combs as woven frames wherever something moves, and as
+// fields it has half the lines, which jitter by a line from field to field: neither survives the flow solver, and every
+// call of the package assumes progressive frames.  Two fields of the same parity share one sampling lattice, so the flow
+// between fields t - 1 and t + 1 is the solver's on the fields themselves, and the lines that frame t lacks, which have the
+// parity of those two fields, are the frame in between them at time 0.5: papof_interp_tensor's gather rule (sampler.h:
+// interp_points) on the field lattice.  What a deinterlacer adds is the protection of each made pixel -- a sample that
+// lands halfway between two field lines carries no detail --, the spatial fallback (the four-tap cubic of the frame's own
+// field) and the weave of kept and made lines into full frames.
+//
+// What it is not.  At the critical velocity -- an odd number of frame rows per field -- the neighbouring fields hold the
+// lines of the current one and nothing is gained: the rule falls back to the cubic.  The end frames have one neighbour and
+// are weaker.  The flows assume motion that is linear over two field periods.  No cadence or telecine detection, no model
+// of chroma subsampling.
+//
+// Semantics: include/papof.h, papof_deinterlace_tensor.  The landing points and taps are sampler.h's (interp_points,
+// taps_at), the samplers too (sample_frame, load_frame, store), fp64 without contraction (-ffp-contract=off): the result is
+// bitwise reproducible.
+//
+// Mapping, k_deinterlace.  k_defect_detect's, on the field lattice: a block is a 64 x 4 tile of made pixels, blockIdx.x the
+// tile, blockIdx.y the frame; one lane reads the two flows at its pixel once, holds the cubic, the kept value and the two
+// temporal samples of up to four channels in registers, and writes BOTH output rows 2 j and 2 j + 1 of its column -- the
+// kept line and the made one --, so that every output byte is written once and rows stay coalesced.  No atomics, no
+// workspace, every offset 64-bit.
+#include "sampler.h"
+
+#include <cmath>
+
+namespace papof {
+
+namespace {
+
+constexpr int kDeintTX = 64, kDeintTY = 4;  // a 64 x 4 tile of made pixels per block (256 lanes: lut)
+constexpr int kMaxC = 4;                    // channels (registers per lane)
+
+struct DeintArgs {
+    papof_tensor fl;      // fields (field, row, column, channel)
+    papof_tensor fw, bw;  // flows (pair, row, column, {vx, vy}) in field coordinates; pair k runs from field k to k + 2
+    papof_tensor out;     // (frame, row, column, channel), 2 Hf rows
+    papof_tensor conf;    // float32 / float64 (frame, row, column) on the field lattice; data NULL: none
+    int T, Hf, W, C;
+    int first;            // field k holds the rows of parity (k + first) & 1
+    double s2;            // sigma^2
+};
+
+// the phase confidence of a landing row Y of the image: 1 on a field line, 0 halfway between two
+__device__ __forceinline__ double phase_confidence(double Y) { return 1.0 - 2.0 * fabs(Y - rint(Y)); }
+
+// blockIdx.x: tile `tile0` + x of the field's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+template <int FD, int MODE>
+__global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintArgs a, long long tile0, long long frame0) {
+    __shared__ double lut[256];
+    if (FD == PAPOF_DTYPE_U8) {
+        fill_u8_lut(lut, threadIdx.y * kDeintTX + threadIdx.x);  // (256 lanes: one quotient each)
+        __syncthreads();
+    }
+    const long long tx = (a.W + kDeintTX - 1) / kDeintTX, tile = tile0 + blockIdx.x;
+    const int x = (int)(tile % tx) * kDeintTX + (int)threadIdx.x;
+    const long long j = (tile / tx) * kDeintTY + threadIdx.y;
+    if (x >= a.W || j >= a.Hf) return;
+    const long long t = frame0 + blockIdx.y;
+    const int Hf = a.Hf, W = a.W;
+    const int pm = 1 - (int)((t + a.first) & 1);  // the parity of the made lines
+    // the own field's rows around the made line, at frame distance -1, +1, -3, +3; the kept line j is a1 (pm 1) or b1 (pm 0)
+    const int ja1 = clamp_to((int)j - 1 + pm, Hf), jb1 = clamp_to((int)j + pm, Hf);
+    const int ja3 = clamp_to((int)j - 2 + pm, Hf), jb3 = clamp_to((int)j + 1 + pm, Hf);
+    const long long own = t * a.fl.stride[0] + x * a.fl.stride[2];
+
+    // the temporal samples: side 0 in field t - 1, side 1 in field t + 1; c_i > 0 where side i counts
+    double c0 = 0.0, c1 = 0.0;
+    Bilinear k0, k1;
+    if (MODE) {
+        if (t >= 1 && t <= a.T - 2) {
+            const long long of = (t - 1) * a.fw.stride[0] + j * a.fw.stride[1] + x * a.fw.stride[2];
+            const long long ob = (t - 1) * a.bw.stride[0] + j * a.bw.stride[1] + x * a.bw.stride[2];
+            const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
+            const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
+            const InterpPoints p = interp_points(x, j, u, v, bu, bv, 0.5, Hf, W);
+            // the landing rows, as interp_points makes them at t = 0.5 (s = t = 0.5: t t = s t = s s = 0.25)
+            const double Y0 = (double)j + (0.25 * bv - 0.25 * v), Y1 = (double)j + (0.25 * v - 0.25 * bv);
+            c0 = p.in0 ? phase_confidence(Y0) : 0.0;
+            c1 = p.in1 ? phase_confidence(Y1) : 0.0;
+            k0 = p.k0;
+            k1 = p.k1;
+        } else {
+            // frame 0: field 1 along half of flow_fw[1]; frame T - 1: field T - 2 along half of flow_bw[T - 4]
+            const papof_tensor& f = t == 0 ? a.fw : a.bw;
+            const long long o = (t == 0 ? 1 : a.T - 4) * f.stride[0] + j * f.stride[1] + x * f.stride[2];
+            const double X = (double)x + 0.5 * load_flow(f, o), Y = (double)j + 0.5 * load_flow(f, o + f.stride[3]);
+            const bool in = X >= 0 && X <= (double)(W - 1) && Y >= 0 && Y <= (double)(Hf - 1);  // (false for a NaN)
+            const Bilinear k = taps_at(in ? X : 0.0, in ? Y : 0.0, Hf, W);
+            const double c = in ? phase_confidence(Y) : 0.0;
+            if (t == 0) {
+                c1 = c;
+                k1 = k;
+            } else {
+                c0 = c;
+                k0 = k;
+            }
+        }
+    }
+    const bool use0 = c0 > 0, use1 = c1 > 0;  // (both false in mode 0)
+    const long long base0 = (t - 1) * a.fl.stride[0], base1 = (t + 1) * a.fl.stride[0];  // (read only where use_i)
+
+    double s[kMaxC], kept[kMaxC], g0[kMaxC], g1[kMaxC];
+    double D = 0.0;
+#pragma unroll
+    for (int ch = 0; ch < kMaxC; ch++)
+        if (ch < a.C) {
+            const long long oc = own + ch * a.fl.stride[3];
+            const double a1 = load_frame<FD>(a.fl, oc + ja1 * a.fl.stride[1], lut);
+            const double b1 = load_frame<FD>(a.fl, oc + jb1 * a.fl.stride[1], lut);
+            const double a3 = load_frame<FD>(a.fl, oc + ja3 * a.fl.stride[1], lut);
+            const double b3 = load_frame<FD>(a.fl, oc + jb3 * a.fl.stride[1], lut);
+            s[ch] = (9.0 * (a1 + b1) - (a3 + b3)) * 0.0625;
+            kept[ch] = pm ? a1 : b1;  // (row j is not clamped: 0 <= j < Hf)
+            g0[ch] = use0 ? sample_frame<FD>(a.fl, base0 + ch * a.fl.stride[3], k0, lut) : 0.0;
+            g1[ch] = use1 ? sample_frame<FD>(a.fl, base1 + ch * a.fl.stride[3], k1, lut) : 0.0;
+            if (use0 && use1) {
+                const double d = g0[ch] - g1[ch];
+                D += d * d;
+            }
+        }
+    double q = 0.0;
+    if (use0 && use1)
+        q = (c1 > c0 ? c1 : c0) / (1.0 + (D / (double)a.C) / a.s2);
+    else if (use0)
+        q = 0.5 * c0;
+    else if (use1)
+        q = 0.5 * c1;
+
+    const long long ok = t * a.out.stride[0] + (2 * j + 1 - pm) * a.out.stride[1] + x * a.out.stride[2];
+    const long long om = t * a.out.stride[0] + (2 * j + pm) * a.out.stride[1] + x * a.out.stride[2];
+#pragma unroll
+    for (int ch = 0; ch < kMaxC; ch++)
+        if (ch < a.C) {
+            double made = s[ch];
+            if (q != 0) {  // (q == 0: the cubic alone -- a NaN never reaches the output through a zero weight)
+                const double m = use0 && use1 ? (c0 * g0[ch] + c1 * g1[ch]) / (c0 + c1) : (use0 ? g0[ch] : g1[ch]);
+                made = (1.0 - q) * s[ch] + q * m;
+            }
+            store(a.out, ok + ch * a.out.stride[3], kept[ch]);
+            store(a.out, om + ch * a.out.stride[3], made);
+        }
+    if (a.conf.data) {
+        const long long oq = t * a.conf.stride[0] + j * a.conf.stride[1] + x * a.conf.stride[2];
+        if (a.conf.dtype == PAPOF_DTYPE_F32)
+            static_cast<float*>(a.conf.data)[oq] = (float)q;
+        else
+            static_cast<double*>(a.conf.data)[oq] = q;
+    }
+}
+
+template <int MODE>
+int launch_deinterlace(hipStream_t st, const DeintArgs& a) {
+    const auto kernel = a.fl.dtype == PAPOF_DTYPE_U8    ? k_deinterlace<PAPOF_DTYPE_U8, MODE>
+                        : a.fl.dtype == PAPOF_DTYPE_F32 ? k_deinterlace<PAPOF_DTYPE_F32, MODE>
+                                                        : k_deinterlace<PAPOF_DTYPE_F64, MODE>;
+    const long long tiles = ((a.W + kDeintTX - 1) / (long long)kDeintTX) * ((a.Hf + kDeintTY - 1) / (long long)kDeintTY);
+    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kDeintTX, kDeintTY), 0, st, a, t0, f0);
+    });
+}
+
+}  // namespace
+
+}  // namespace papof
+
+using namespace papof;
+
+extern "C" int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field_height, int width, int c,
+                                        const papof_tensor* fields, int first, int mode, const papof_tensor* flow_fw,
+                                        const papof_tensor* flow_bw, double sigma, const papof_tensor* video,
+                                        const papof_tensor* confidence, void* stream) {
+    if (!h || n_fields < 4 || field_height < 1 || field_height > 0x3fffffff || width < 1 || c < 1 || c > kMaxC)
+        return PAPOF_EINVAL;
+    if ((first != 0 && first != 1) || (mode != 0 && mode != 1)) return PAPOF_EINVAL;
+    if (!std::isfinite(sigma) || !(sigma > 0)) return PAPOF_EINVAL;
+    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
+    if (!described(fields, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (mode && (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)))
+        return PAPOF_EINVAL;
+    if (!described(video, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (confidence && !described(confidence, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (video->data == fields->data) return PAPOF_EINVAL;
+    DeintArgs a{};
+    a.fl = *fields;
+    if (mode) {
+        a.fw = *flow_fw;
+        a.bw = *flow_bw;
+    }
+    a.out = *video;
+    if (confidence) a.conf = *confidence;
+    a.T = n_fields;
+    a.Hf = field_height;
+    a.W = width;
+    a.C = c;
+    a.first = first;
+    a.s2 = sigma * sigma;
+    PAPOF_HIP(hipSetDevice(h->device));
+    return mode ? launch_deinterlace<1>(static_cast<hipStream_t>(stream), a)
+                : launch_deinterlace<0>(static_cast<hipStream_t>(stream), a);
+}

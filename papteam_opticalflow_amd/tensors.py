@@ -171,6 +171,15 @@ not found; a small object that outruns the flow is removed like a defect.
 
     rv = restore_video(frames, 4, layout="NHWC")   # rv.video, rv.masks, rv.detected (T, H, W) bool, rv.status
 
+Deinterlacing: `deinterlace_fields` (include/papof.h: papof_deinterlace_tensor) turns a sequence of fields into full frames,
+one per field: each frame keeps its field's lines and makes the others from the two neighbouring fields of that parity
+along the flows between them (`field_flows`: the solver on the fields themselves), weighted by the phase of the landing
+rows and the agreement of the two samples, over a four-tap cubic of the own field (`bob_fields`, the fallback);
+`split_fields` makes the fields from woven frames and `deinterlace_video` chains field_flows and deinterlace_fields.  No gain
+at the critical velocity; weaker end frames; no cadence detection.
+
+    dv = deinterlace_video(split_fields(frames, layout="NHWC"), 4, layout="NHWC")   # dv.video (2 N, H, W, C), dv.confidence
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -205,6 +214,8 @@ Inpainted = collections.namedtuple("Inpainted", "video status")
 Defects = collections.namedtuple("Defects", "mask score support")
 Restored = collections.namedtuple("Restored", "video masks detected status")
 RestoredVideo = collections.namedtuple("RestoredVideo", Restored._fields + ("flow_fw", "flow_bw", "timing"))
+Deinterlaced = collections.namedtuple("Deinterlaced", "video confidence")
+DeinterlacedVideo = collections.namedtuple("DeinterlacedVideo", Deinterlaced._fields + ("flow_fw", "flow_bw", "timing"))
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
 Blurred = collections.namedtuple("Blurred", "video flow_fw flow_bw occlusion timing")
 RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
@@ -1898,6 +1909,140 @@ def restore_video(frames, pyramidLevels, *, passes=DEFECT_PASSES, masks=None, th
                     out_dtype if k == passes - 1 else ts[0].dtype)
         detected = r.detected if detected is None else detected | r.detected
     return RestoredVideo(r.video, r.masks, detected, r.status, fb.flow_fw, fb.flow_bw, fb.timing)
+
+
+# sigma of the deinterlacer's agreement weight: calibrated in tests/test_deinterlace_cpu.py (test_quality_calibration)
+DEINT_SIGMA = 0.05
+MAX_FIELD_HEIGHT = 2 ** 30 - 1  # include/papof.h: papof_deinterlace_tensor
+
+
+def _check_parity(first):
+    if isinstance(first, bool) or not isinstance(first, int) or first not in (0, 1):
+        raise ValueError("first must be 0 or 1 (the parity of field 0's rows), got %r" % (first,))
+    return first
+
+
+def _check_deint_sigma(sigma):
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)):
+        raise TypeError("sigma must be a number, got %r" % (sigma,))
+    if not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError("sigma must be finite and > 0, got %r" % (sigma,))
+    return float(sigma)
+
+
+def _check_field_video(fields, layout, levels, out_dtype, solver=None):
+    """the fields of the deinterlacing calls: _check_video's returns for T >= 4 fields"""
+    ts, descs, out_dtype, params = _check_video(fields, layout, levels, out_dtype, name="fields", min_frames=4, solver=solver)
+    if descs[0][0][1] > MAX_FIELD_HEIGHT:
+        raise ValueError("fields must have at most %d rows, got %d" % (MAX_FIELD_HEIGHT, descs[0][0][1]))
+    return ts, descs, out_dtype, params
+
+
+def _deinterlace(ts, descs, first, mode, flows, codes, sigma, layout, out_dtype):
+    """papof_deinterlace_tensor of the checked fields ts[0]: Deinterlaced(video, confidence float64 -- None in mode 0)"""
+    torch = _torch()
+    (T, Hf, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    out, d_out = _new_frames(T, 2 * Hf, W, C, layout, out_dtype, dev)
+    d_in = _struct(ts[0], strides, code)
+    if mode:
+        conf = torch.empty((T, Hf, W), dtype=torch.float64, device=dev)
+        d_conf = _struct(conf, (conf.stride(0), conf.stride(1), conf.stride(2), 0), capi.DTYPE_F64)
+        d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    else:
+        conf, d_conf, d_f = None, None, (None, None)
+    _launch(dev, "papof_deinterlace_tensor", T, Hf, W, C, ctypes.byref(d_in), first, mode, _ref(d_f[0]), _ref(d_f[1]), sigma,
+            ctypes.byref(d_out), _ref(d_conf))
+    return Deinterlaced(out, conf)
+
+
+def split_fields(frames, top_first=True, *, layout="NCHW"):
+    """Woven interlaced frames as the sequence of their fields, with torch operations on any device: frames (N, C, H, W) or
+    (N, H, W, C) by `layout` (3-D: one frame), H even -> a new tensor (2 N, C, H / 2, W) or (2 N, H / 2, W, C): frame n
+    gives fields 2 n and 2 n + 1, the top field (rows 0, 2, ...) before the bottom one when top_first, else after it.
+    The deinterlacing calls take these fields with first = 0 for top_first, first = 1 otherwise."""
+    frames = _as4d("frames", frames)
+    if layout not in LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (LAYOUTS, layout))
+    if not isinstance(top_first, (bool, int)) or top_first not in (0, 1):
+        raise ValueError("top_first must be True or False, got %r" % (top_first,))
+    axis = 2 if layout == "NCHW" else 1
+    if min(frames.shape) < 1:
+        raise ValueError("empty frames: shape %s" % (tuple(frames.shape),))
+    if frames.shape[axis] % 2:
+        raise ValueError("interlaced frames have an even number of rows, got %d (layout %s)" % (frames.shape[axis], layout))
+    rows = lambda p: frames[:, :, p::2] if axis == 2 else frames[:, p::2]  # noqa: E731
+    p0 = 0 if top_first else 1
+    return _torch().stack((rows(p0), rows(1 - p0)), 1).flatten(0, 1)
+
+
+def bob_fields(fields, first=0, *, layout="NCHW", out_dtype=None):
+    """The spatial deinterlacer alone (papof_deinterlace_tensor, mode 0): T >= 4 fields (T, C, Hf, W) or (T, Hf, W, C) by
+    `layout`, C = 1 .. 4, uint8 (read as x / 255), float32 or float64, any strides, on a HIP device; field k holds the rows
+    of parity (k + first) & 1 of frame k.  Returns the video (T, ..., 2 Hf, W ...) in `layout` and out_dtype (by default the
+    fields'): every frame keeps its field's lines and makes the others with the four-tap cubic (9 (a1 + b1) - (a3 + b3)) /
+    16 of the lines above and below, rows clamped at the borders.  No flows are read.  Enqueued on the current stream;
+    returns without waiting."""
+    first = _check_parity(first)
+    ts, descs, out_dtype, _ = _check_field_video(fields, layout, 1, out_dtype)
+    return _deinterlace(ts, descs, first, 0, None, None, DEINT_SIGMA, layout, out_dtype).video
+
+
+def field_flows(fields, pyramidLevels, *, layout="NCHW", **solver):
+    """The flows that deinterlace_fields takes: flow_pairs_fb(fields[:-2], fields[2:], pyramidLevels, layout=layout,
+    consistency=None, out_dtype=torch.float64, **solver) -- pair k from field k to field k + 2, two fields of one parity,
+    which share a sampling lattice, so that the solver needs no special treatment; (T - 2, 2, Hf, W) float64 in field
+    coordinates.  The pairs are independent: every field that is both a pair's second and another pair's first has its
+    pyramid built twice (DESIGN.md section 35 has the measured cost against two flow_video_fb calls on the even and the
+    odd fields).  Returns a FlowFB (occlusion None).  T >= 4."""
+    ts, descs, _, params = _check_field_video(fields, layout, pyramidLevels, None, solver=solver)
+    return _field_flows(ts, descs, layout, pyramidLevels, params)
+
+
+def _field_flows(ts, descs, layout, levels, params):
+    (T, Hf, W, C), strides, code = descs[0]
+    pair = [ts[0][:-2], ts[0][2:]]
+    d = [((T - 2, Hf, W, C), strides, code)] * 2
+    return _run_fb(pair, d, False, T - 2, layout, _torch().float64, levels, _alphas(None), params)
+
+
+def deinterlace_fields(fields, flow_fw, flow_bw, first=0, *, sigma=DEINT_SIGMA, layout="NCHW", out_dtype=None):
+    """Motion-compensated deinterlacing of T >= 4 fields into T full frames, one per field (double rate): fields
+    (T, C, Hf, W) or (T, Hf, W, C) by `layout`, C = 1 .. 4, uint8 (read as x / 255), float32 or float64, any strides, on a
+    HIP device; field k holds the rows of parity (k + first) & 1 of frame k (split_fields: first = 0 for top_first);
+    flow_fw, flow_bw (T - 2, 2, Hf, W) float32 / float64 on the same device in FIELD coordinates, pair k from field k to
+    field k + 2 and back, as field_flows returns them.
+    Frame t keeps its field's lines.  Each line it lacks is the blend (1 - q) s + q m of the bob's cubic s and of m, the
+    fields t - 1 and t + 1 sampled where interpolate's gather rule at time 0.5 lands in them -- each sample weighted by
+    c = 1 - 2 |Y - rint(Y)|, which is 1 on a field line and 0 halfway between two, where a sample carries no detail --,
+    with q = max(c0, c1) / (1 + D / sigma^2), D the mean squared difference of the two samples over the channels; one
+    sample only (the other out of the image, or an end frame): q = c / 2; none, or a NaN or infinite flow: the cubic.
+    sigma = 0.05 was calibrated in tests/test_deinterlace_cpu.py.
+    Returns Deinterlaced(video (T, ..., 2 Hf, W ...) in `layout` and out_dtype -- by default the fields'; uint8 to uint8
+    keeps the kept lines' bytes --, confidence (T, Hf, W) float64: q of every made pixel).  include/papof.h
+    (papof_deinterlace_tensor) states the rule exactly.  Not gained: anything at the critical velocity (an odd number of
+    frame rows per field: the neighbouring fields hold the same lines, the output is bob_fields'); the end frames are
+    weaker; the flows assume motion linear over two field periods; no cadence or telecine detection, no
+    chroma-subsampling model.  Enqueued on the current stream; returns without waiting."""
+    first = _check_parity(first)
+    sigma = _check_deint_sigma(sigma)
+    ts, descs, out_dtype, _ = _check_field_video(fields, layout, 1, out_dtype)
+    (T, Hf, W, _), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw, (T - 2, 2, Hf, W), ts[0].device)
+    return _deinterlace(ts, descs, first, 1, (flow_fw, flow_bw), codes, sigma, layout, out_dtype)
+
+
+def deinterlace_video(fields, pyramidLevels, first=0, *, sigma=DEINT_SIGMA, layout="NCHW", out_dtype=None, **solver):
+    """T >= 4 fields deinterlaced along their motion: field_flows(fields, pyramidLevels, layout=layout, **solver) followed
+    by deinterlace_fields on those flows (first, sigma).  Returns DeinterlacedVideo(video, confidence, flow_fw, flow_bw
+    (T - 2, 2, Hf, W) float64 in field coordinates, timing of the flow call).  Every argument error raises before anything
+    is launched; the flows are complete on return, the video is enqueued on the current stream behind them."""
+    first = _check_parity(first)
+    sigma = _check_deint_sigma(sigma)
+    ts, descs, out_dtype, params = _check_field_video(fields, layout, pyramidLevels, out_dtype, solver=solver)
+    fb = _field_flows(ts, descs, layout, pyramidLevels, params)
+    d = _deinterlace(ts, descs, first, 1, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), sigma, layout, out_dtype)
+    return DeinterlacedVideo(d.video, d.confidence, fb.flow_fw, fb.flow_bw, fb.timing)
 
 
 MAX_ITERS = 65536  # include/papof.h: papof_temporal_consistency_tensor
