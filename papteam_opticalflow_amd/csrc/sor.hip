@@ -195,6 +195,50 @@ __device__ __forceinline__ u32x4 as_u4(double x, double y) {
 constexpr int kAuxPlain = 0, kAuxSc1 = 16;
 constexpr unsigned kOob = 0x80000000u;  // byte offset beyond every plane (sor_solve enforces planes < 1 GiB) that
                                         // cannot wrap while it advances by 1 KiB per step
+constexpr unsigned kBlock = kLanes * 16u;  // one task's (du, dv) cells of one position
+
+// Compile-time range loop: f(std::integral_constant<int, t>{}) for t = T0 .. T1 - 1, in order (static_for<N>: 0 .. N - 1).
+// Every unrolled loop over pipeline slots, steps or rows goes through it; the bodies are always_inline lambdas.
+template <int T0, int T1, class F, class... Args>
+__device__ __forceinline__ void static_for(F&& f, Args... args) {
+    if constexpr (T0 < T1) {
+        static_for<T0, T1 - 1>(f, args...);
+        f(std::integral_constant<int, T1 - 1>{}, args...);
+    }
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for<0, N>(f);
+}
+
+// THE cell update, stated once for every solver kernel of this file: the reference's order of operations
+// (src/OpticalFlow.cpp:468-505) -- left, right, up and down terms, * -alpha, + imdxy * dv, relax du, + imdxy * du(new),
+// relax dv.  wl / wu / wc = phi of the left cell, the upper cell and this cell (which weighs the right and the down
+// neighbour).  The wave kernels, which hand the left and the up term across lanes as PRODUCTS (wave_cell() below), pass
+// them with the weight 1.0: x * 1.0 is x, exactly, and is folded away at compile time.  (Taking the products themselves
+// as arguments moves the up multiplications of k_sor_blocked / k_sor_tiny ahead of the right term in the instruction
+// stream: same results, but k_sor_tiny's 3- and 5-cell instances ran 1.0 % and 1.4 % slower -- profiles/sor_once_ab.txt.)
+// Every operand that does not exist (image border, padding) is an exact 0.0 here, so the reference's conditional terms
+// (src/OpticalFlow.cpp:468-495) reduce to adding +-0 in the same order.  Ghost lanes of the wave kernels
+// (om1 == 1, a1 == a2 == 0) pass their centre value through: 1*c + 0*(..) == c.
+__device__ __forceinline__ D2 sor_cell(double wl, double duL, double dvL, double wu, double duU, double dvU, double wc,
+                                       double duR, double dvR, double duD, double dvD, double nalpha, double xy,
+                                       double duC, double dvC, double om1, double a1, double a2, double b1, double b2) {
+    double s1 = wl * duL, s2 = wl * dvL;
+    s1 += wc * duR;
+    s2 += wc * dvR;
+    s1 += wu * duU;
+    s2 += wu * dvU;
+    s1 += wc * duD;
+    s2 += wc * dvD;
+    s1 *= nalpha;
+    s2 *= nalpha;
+    s1 += xy * dvC;
+    const double duN = om1 * duC + a1 * (b1 - s1);
+    s2 += xy * duN;
+    const double dvN = om1 * dvC + a2 * (b2 - s2);
+    return D2{duN, dvN};
+}
 
 // Operands of R consecutive steps held in registers: slot t of the running iteration is consumed by step
 // i*R + t and immediately refilled with the operands of step (i+1)*R + t, i.e. every global load is issued
@@ -224,6 +268,9 @@ __device__ __forceinline__ void publish(const Task& T, unsigned lane_off, unsign
 // Per-lane ABSOLUTE byte offsets (constant VGPRs); the step index enters only through uniform soffsets
 // (s * pos_c for the coefficient planes, s * pos_d for the unknowns).  kOob switches an access off (reads 0.0)
 // without touching EXEC.
+struct BufAt {  // where one buffer access goes: per-lane byte offset (voffset) + wave-uniform byte offset (soffset)
+    unsigned lane, uniform;
+};
 struct LaneOffs {
     unsigned pa;     // (phi, xy) of this lane's cell at step s (64 consecutive rows of one skew position)
     unsigned pbc;    // (a1, a2) and (b1, b2)                     [ghosts: off -> 0 -> pass-through]
@@ -232,28 +279,59 @@ struct LaneOffs {
     unsigned pos_c;  // bytes per coefficient skew position = hp * 16
     unsigned pos_d;  // bytes per (du, dv) position = nb * 1 KiB
     unsigned hs;     // SPLIT: store of step s into the inbox of the rank below (lane 62 of the band above a cut; else off)
+    __device__ __forceinline__ BufAt unknowns_at(int s) const { return BufAt{pd, (unsigned)s * pos_d}; }
 };
 
-template <int R, int t>
-__device__ __forceinline__ void load_coef(const Task& T, const LaneOffs& L, int s, Slots<R>& c) {
+// Loads of step s into slot t; Lane = LaneOffs, or the grouped kernel's GLane (other addressing of the unknowns)
+template <int R, int t, class Lane>
+__device__ __forceinline__ void load_coef(const Task& T, const Lane& L, int s, Slots<R>& c) {
     const unsigned off = (unsigned)s * L.pos_c;  // wave-uniform byte offsets -> soffset
     c.pa[t] = __builtin_amdgcn_raw_buffer_load_b128(T.ra, L.pa, off, kAuxPlain);
     c.pb[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rb, L.pbc, off, kAuxPlain);
     c.pc[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rc, L.pbc, off, kAuxPlain);
 }
-template <int R, int t>
-__device__ __forceinline__ void load_unknowns(const Task& T, const LaneOffs& L, int s, Slots<R>& c) {
-    c.pd[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rd, L.pd, (unsigned)s * L.pos_d, kAuxSc1);
+template <int R, int t, class Lane>
+__device__ __forceinline__ void load_unknowns(const Task& T, const Lane& L, int s, Slots<R>& c) {
+    const BufAt at = L.unknowns_at(s);
+    c.pd[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rd, at.lane, at.uniform, kAuxSc1);
 }
-template <int R, int t>
-__device__ __forceinline__ void load_slot(const Task& T, const LaneOffs& L, int s, Slots<R>& c) {
+template <int R, int t, class Lane>
+__device__ __forceinline__ void load_slot(const Task& T, const Lane& L, int s, Slots<R>& c) {
     load_coef<R, t>(T, L, s, c);
     load_unknowns<R, t>(T, L, s, c);
+}
+// The start-up loads of a task: steps 0 .. R-1 into their slots
+template <int R, class Lane>
+__device__ __forceinline__ void fill_coef(const Task& T, const Lane& L, Slots<R>& c) {
+    static_for<R>([&](auto t) __attribute__((always_inline)) { load_coef<R, t()>(T, L, t(), c); });
+}
+template <int R, class Lane>
+__device__ __forceinline__ void fill_unknowns(const Task& T, const Lane& L, Slots<R>& c) {
+    static_for<R>([&](auto t) __attribute__((always_inline)) { load_unknowns<R, t()>(T, L, t(), c); });
 }
 
 struct State {
     double duL, dvL, phiL, duC, dvC;
 };
+
+// The cell update of a wave kernel's lane: the two cross-lane moves around sor_cell().  pa / pb / pc = (phi, xy) (a1, a2)
+// (b1, b2) of the cell, (duR, dvR) its right-old neighbour; down-old is the pending centre of the lane below.
+// The up term phi(up) * du(up) is the left product of the lane above, formed there in this very step from the same two
+// registers: it is fetched as a product (before anything is added to it) and added where the reference adds it.  A ghost
+// lane's product is made of the real phi of its row and its passed-through centre, a dead lane's is 0 * 0; the wave-edge
+// lane receives 0 (DPP bound_ctrl) or its own product (__shfl_up) -- what its two factors used to give.
+template <bool DPP>
+__device__ __forceinline__ D2 wave_cell(const State& S, double om1, double nalpha, const D2& pa, const D2& pb,
+                                        const D2& pc, double duR, double dvR) {
+    const double duD = from_below<DPP>(duR);
+    const double dvD = from_below<DPP>(dvR);
+    const double leftU = S.phiL * S.duL;
+    const double leftV = S.phiL * S.dvL;
+    const double upU = from_above<DPP>(leftU);
+    const double upV = from_above<DPP>(leftV);
+    return sor_cell(1.0, leftU, leftV, 1.0, upU, upV, pa.x, duR, dvR, duD, dvD, nalpha, pa.y, S.duC, S.dvC, om1, pb.x, pb.y,
+                    pc.x, pc.y);  // (weights 1.0: the products are formed already)
+}
 
 // A value that outlives the operand slot it came from is MOVED out of the slot's registers (an opaque v_mov the
 // compiler cannot fold away).  Otherwise the slot's registers stay live across the refill, the refill lands in other
@@ -278,85 +356,21 @@ __device__ __forceinline__ double moved(double x) {
 template <int R, int t, bool DPP, bool SPLIT = false>
 __device__ __forceinline__ void step(const ExactArgs& A, const Task& T, const LaneOffs& L, double om1, int s,
                                      Slots<R>& c, State& S) {
-    const double nalpha = A.nalpha;
     const D2 pa = as_d2(c.pa[t]), pb = as_d2(c.pb[t]), pc = as_d2(c.pc[t]), pd = as_d2(c.pd[t]);
-    const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duD = from_below<DPP>(duR);
-    const double dvD = from_below<DPP>(dvR);
-    // Every operand that does not exist (image border, padding) is an exact 0.0 here, so the reference's
-    // conditional terms (src/OpticalFlow.cpp:468-495) reduce to adding +-0 in the same order.  Ghost lanes
-    // (om1 == 1, a1 == a2 == 0) pass their centre value through: 1*c + 0*(..) == c.
-    // The up term phi(up) * du(up) is the left product of the lane above, formed there in this very step from the same two
-    // registers: it is fetched as a product (before anything is added to it) and added where the reference adds it.  A ghost
-    // lane's product is made of the real phi of its row and its passed-through centre, a dead lane's is 0 * 0; the wave-edge
-    // lane receives 0 (DPP bound_ctrl) or its own product (__shfl_up) -- what its two factors used to give.
-    double s1 = S.phiL * S.duL;
-    double s2 = S.phiL * S.dvL;
-    const double upU = from_above<DPP>(s1);
-    const double upV = from_above<DPP>(s2);
-    s1 += phiC * duR;
-    s2 += phiC * dvR;
-    s1 += upU;
-    s2 += upV;
-    s1 += phiC * duD;
-    s2 += phiC * dvD;
-    s1 *= nalpha;
-    s2 *= nalpha;
-    s1 += xy * S.dvC;
-    const double duN = om1 * S.duC + pb.x * (pc.x - s1);
-    s2 += xy * duN;
-    const double dvN = om1 * S.dvC + pb.y * (pc.y - s2);
-    __builtin_amdgcn_raw_buffer_store_b128(as_u4(duN, dvN), T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
+    const double phiC = pa.x, duR = pd.x, dvR = pd.y;
+    const D2 n = wave_cell<DPP>(S, om1, A.nalpha, pa, pb, pc, duR, dvR);
+    __builtin_amdgcn_raw_buffer_store_b128(as_u4(n.x, n.y), T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     if (SPLIT)  // lane 62 of the band above a cut: the same cell into the inbox of the rank below (every other lane: off)
-        __builtin_amdgcn_raw_buffer_store_b128(as_u4(duN, dvN), T.rd2, L.hs, (unsigned)s * L.pos_d, kAuxSc1);
+        __builtin_amdgcn_raw_buffer_store_b128(as_u4(n.x, n.y), T.rd2, L.hs, (unsigned)s * L.pos_d, kAuxSc1);
     store_data_guard();
-    S.duL = duN;
-    S.dvL = dvN;
+    S.duL = n.x;
+    S.dvL = n.y;
     S.phiL = moved(phiC);
     S.duC = moved(duR);
     S.dvC = moved(dvR);
     asm volatile("" ::: "memory");  // keep this step's store ahead of its refill loads in the instruction stream
     load_slot<R, t>(T, L, s + R, c);  // refill this slot for the step R ahead
 }
-
-template <int R, int t, bool DPP>
-struct Unroll {
-    static __device__ __forceinline__ void run(const ExactArgs& A, const Task& T, const LaneOffs& L, double om1,
-                                               int s0, Slots<R>& c, State& S) {
-        Unroll<R, t - 1, DPP>::run(A, T, L, om1, s0, c, S);
-        step<R, t, DPP, false>(A, T, L, om1, s0 + t, c, S);
-    }
-    static __device__ __forceinline__ void fill_coef(const Task& T, const LaneOffs& L, Slots<R>& c) {
-        Unroll<R, t - 1, DPP>::fill_coef(T, L, c);
-        load_coef<R, t>(T, L, t, c);
-    }
-    static __device__ __forceinline__ void fill_unknowns(const Task& T, const LaneOffs& L, Slots<R>& c) {
-        Unroll<R, t - 1, DPP>::fill_unknowns(T, L, c);
-        load_unknowns<R, t>(T, L, t, c);
-    }
-};
-template <int R, bool DPP>
-struct Unroll<R, -1, DPP> {
-    static __device__ __forceinline__ void run(const ExactArgs&, const Task&, const LaneOffs&, double, int, Slots<R>&,
-                                               State&) {}
-    static __device__ __forceinline__ void fill_coef(const Task&, const LaneOffs&, Slots<R>&) {}
-    static __device__ __forceinline__ void fill_unknowns(const Task&, const LaneOffs&, Slots<R>&) {}
-};
-
-// steps t0 .. t1-1 of the unrolled iteration
-template <int R, int t0, int t1, bool DPP, bool SPLIT = false>
-struct Seg {
-    static __device__ __forceinline__ void run(const ExactArgs& A, const Task& T, const LaneOffs& L, double om1,
-                                               int s0, Slots<R>& c, State& S) {
-        step<R, t0, DPP, SPLIT>(A, T, L, om1, s0 + t0, c, S);
-        Seg<R, t0 + 1, t1, DPP, SPLIT>::run(A, T, L, om1, s0, c, S);
-    }
-};
-template <int R, int t1, bool DPP, bool SPLIT>
-struct Seg<R, t1, t1, DPP, SPLIT> {
-    static __device__ __forceinline__ void run(const ExactArgs&, const Task&, const LaneOffs&, double, int, Slots<R>&,
-                                               State&) {}
-};
 
 // Progress of the two producers of a task, polled together (a missing producer reads as "finished").
 struct Polls {
@@ -427,6 +441,104 @@ __device__ __forceinline__ bool wait_covered(const ExactArgs& A, const Polls& pl
     return true;
 }
 
+// Block -> task of k_sor_exact / k_sor_fused: u = the sweep (k_sor_fused: the pair) and b = the band of this block;
+// false: the block has no task.
+// Workgroups are dealt round-robin over the 8 XCDs (blocks x and x + 8 share one; observed, speed only), so with
+// xcd_affine the sweeps of one band all run on one XCD: sweep k+1 re-reads the coefficient cells sweep k read a
+// few dozen steps earlier out of that XCD's L2 instead of the Infinity Cache.  Dependencies still point to lower
+// block indices only.
+__device__ __forceinline__ bool task_of_block(const ExactArgs& A, int& u, int& b) {
+    if (A.xcd_affine) {
+        // rows of S blocks per sweep, S a multiple of 8: the first 8 * (nb / 8) bands sit at their own index (band b on
+        // XCD b % 8 in every sweep); the nb % 8 remaining bands occupy consecutive places of one more group of 8 whose
+        // start moves with the sweep, so that they load every XCD equally instead of always the same ones
+        const int nf = A.nb >> 3, rem = A.nb & 7, S = 8 * nf + (rem ? 8 : 0);
+        const int ul = blockIdx.x / S;
+        u = A.k0 + ul;
+        const int r = blockIdx.x - ul * S;
+        if (r < 8 * nf) {
+            b = r;
+        } else {
+            const int j = r - 8 * nf - (nf ? u % (9 - rem) : 0);
+            b = 8 * nf + j;
+            if (j < 0 || j >= rem) return false;
+        }
+    } else {
+        const int ul = blockIdx.x / A.nbl;
+        u = A.k0 + ul;
+        b = A.b0 + (blockIdx.x - ul * A.nbl);
+    }
+    return true;
+}
+
+// Descriptors of the three paired coefficient planes and of the (du, dv) planes; returns the bytes of one parity of the latter
+__device__ __forceinline__ unsigned plane_descriptors(const ExactArgs& A, Task& T) {
+    const unsigned plane_bytes = (unsigned)(((size_t)A.npos * A.hp + kLanes) * 16u);
+    const unsigned par_bytes = (unsigned)A.npos_d * (unsigned)A.nb * kBlock;
+    T.ra = __builtin_amdgcn_make_buffer_rsrc((void*)A.phi, 0, plane_bytes, 0x00020000);
+    T.rb = __builtin_amdgcn_make_buffer_rsrc((void*)A.a1, 0, plane_bytes, 0x00020000);
+    T.rc = __builtin_amdgcn_make_buffer_rsrc((void*)A.b1, 0, plane_bytes, 0x00020000);
+    T.rd = __builtin_amdgcn_make_buffer_rsrc((void*)A.du, 0, 2u * par_bytes, 0x00020000);
+    return par_bytes;
+}
+
+// ---- one iteration = R steps of a task's software pipeline (k_sor_exact, k_sor_fused) ------------------------------
+// Every load must be covered by the producers' published progress before it is issued.  Iteration i issues the
+// loads of steps < (i + 2) R; its coverage check uses a poll that was itself issued one iteration earlier
+// (consuming a poll forces an in-order vmcnt wait on every older load, so finer-grained polling stalls).
+// MARKER loads: a 4-byte load issued right after the store of some step retires (vmcnt is in order) only after
+// that store has completed, so consuming it a few steps later proves the step complete and lets the task
+// publish it without draining the pipeline.  Two markers per iteration (after steps H-1 and R-1), each consumed
+// DM steps later, in the NEXT iteration (after its steps CA-1 / CB-1): published progress lags the real one by
+// DM .. DM + R/2 steps.  The marker reads the abort word, so a raised abort also ends every running task within two
+// iterations.
+// The first iteration (`first`: no markers to consume) is peeled off the callers' loops so that the loop header joins two
+// states with the same pipeline contents (after an iteration / after an iteration).
+struct Pipe {  // what an iteration hands to the next one
+    Polls pl;          // the poll its coverage check consumes
+    unsigned ma, mb;   // the markers it consumes
+};
+// run(t, s0): step s0 + t of the task, t a std::integral_constant, s0 = i R; publish(n): advertise n completed steps; S: the
+// state whose left-new values the last step produced.  OWN / UP / SELECTIVE: see covered() / wait_covered().
+// (Code generation is sensitive to HOW this is instantiated -- profiles/sor_once_isa.txt: k_sor_exact calls it from one plain
+// lambda with a run-time `first`, inlined at its two call sites after it has been optimised on its own, as its hand-written
+// iteration was; k_sor_fused from a generic lambda, one instance per value of `first`.)
+template <int R, int DM, bool MIDPOLL, int OWN, int UP, bool SELECTIVE, class Run, class Publish>
+__device__ __forceinline__ void pipeline_iteration(const ExactArgs& A, const Deps& D, const State& S, Pipe& P, int i,
+                                                   bool first, Run&& run, Publish&& publish) {
+    constexpr int H = R / 2;
+    constexpr int CA = H + DM - R, CB = DM;  // steps of the NEXT iteration after which markers A / B are consumed
+    static_assert(CA >= 0 && CA < H && CB >= H && CB < R, "marker consumption points");
+    if (!wait_covered<OWN, UP, SELECTIVE>(A, P.pl, D, (i + 2) * R)) end_task();
+    // The poll for the next iteration's check is consumed at the start of the next iteration, where it waits (in
+    // order) for every load issued before it.  Issued in the middle of this iteration (MIDPOLL) it is half an iteration
+    // fresher (a shorter hand-off) but then waits for the refills of the first half: at R >= 8 those are >= 4 steps old and long
+    // there (1080x607: 0.519 -> 0.505 ms, 810x455: 0.380 -> 0.370), at R = 6 only 3 steps (607x341: 0.336 -> 0.378).
+    Polls pn{0u, 0u, 0u};
+    if (!MIDPOLL) pn = poll(D);
+    // Markers are consumed DM steps after they were issued -- i.e. in the NEXT iteration: consuming a marker
+    // waits (in-order vmcnt) for every load issued before it, and with DM = 3 that exposed ~0.35 us of latency twice
+    // per iteration (the refills issued in those 3 steps).  R - 3 steps later all of them have long arrived.
+    static_for<0, CA>(run, i * R);
+    if (!first) {  // marker A of the previous iteration: its steps < (i-1)R + H are complete
+        asm volatile("" ::"v"(P.ma), "v"(S.duL), "v"(S.dvL) : "memory");
+        if (uni(P.ma) != 0u) end_task();
+        publish((unsigned)min(A.ns, (i - 1) * R + H));
+    }
+    static_for<CA, H>(run, i * R);
+    P.ma = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker A: after step H - 1
+    if (MIDPOLL) pn = poll(D);
+    static_for<H, CB>(run, i * R);
+    if (!first) {  // marker B of the previous iteration: steps < i R are complete
+        asm volatile("" ::"v"(P.mb), "v"(S.duL), "v"(S.dvL) : "memory");
+        if (uni(P.mb) != 0u) end_task();
+        publish((unsigned)min(A.ns, i * R));
+    }
+    static_for<CB, R>(run, i * R);
+    P.mb = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker B: after step R - 1
+    P.pl = pn;
+}
+
 template <int R, bool DPP, bool SPLIT = false>
 __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
     static_assert(R >= 4 && R % 2 == 0, "two markers per iteration");
@@ -441,43 +553,14 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
     }
     stamp_now(A.stamp);
     const unsigned lane = threadIdx.x;
-    // Workgroups are dealt round-robin over the 8 XCDs (blocks x and x + 8 share one; observed, speed only), so with
-    // xcd_affine the sweeps of one band all run on one XCD: sweep k+1 re-reads the coefficient cells sweep k read a
-    // few dozen steps earlier out of that XCD's L2 instead of the Infinity Cache.  Dependencies still point to lower
-    // block indices only.
     int k, b;
-    if (A.xcd_affine) {
-        // rows of S blocks per sweep, S a multiple of 8: the first 8 * (nb / 8) bands sit at their own index (band b on
-        // XCD b % 8 in every sweep); the nb % 8 remaining bands occupy consecutive places of one more group of 8 whose
-        // start moves with the sweep, so that they load every XCD equally instead of always the same ones
-        const int nf = A.nb >> 3, rem = A.nb & 7, S = 8 * nf + (rem ? 8 : 0);
-        const int kl = blockIdx.x / S;
-        k = A.k0 + kl;
-        const int r = blockIdx.x - kl * S;
-        if (r < 8 * nf) {
-            b = r;
-        } else {
-            const int j = r - 8 * nf - (nf ? k % (9 - rem) : 0);
-            if (j < 0 || j >= rem) return;
-            b = 8 * nf + j;
-        }
-    } else {
-        const int kl = blockIdx.x / A.nbl;
-        k = A.k0 + kl;
-        b = A.b0 + (blockIdx.x - kl * A.nbl);
-    }
+    if (!task_of_block(A, k, b)) return;
     const int ns = A.ns;
     const bool ghost = lane == 0 || lane == kLanes - 1;
     unsigned long long* const dbg = A.dbg ? A.dbg + (size_t)(k * A.nb + b) * 8 : nullptr;  // every lane stores the same
     if (dbg) dbg[0] = __builtin_amdgcn_s_memrealtime();
     Task T;
-    const unsigned plane_bytes = (unsigned)(((size_t)A.npos * A.hp + kLanes) * 16u);
-    constexpr unsigned kBlock = kLanes * 16u;                                  // one task's cells of one position
-    const unsigned par_bytes = (unsigned)A.npos_d * (unsigned)A.nb * kBlock;  // one parity of the (du, dv) planes
-    T.ra = __builtin_amdgcn_make_buffer_rsrc((void*)A.phi, 0, plane_bytes, 0x00020000);
-    T.rb = __builtin_amdgcn_make_buffer_rsrc((void*)A.a1, 0, plane_bytes, 0x00020000);
-    T.rc = __builtin_amdgcn_make_buffer_rsrc((void*)A.b1, 0, plane_bytes, 0x00020000);
-    T.rd = __builtin_amdgcn_make_buffer_rsrc((void*)A.du, 0, 2u * par_bytes, 0x00020000);
+    const unsigned par_bytes = plane_descriptors(A, T);  // one parity of the (du, dv) planes
     // lane 0 of task (b, k) stands for image row r0 = 62b - k - 1; at step 0 the task sits at position r0 + qt
     const int r0 = kBandRows * b - k - 1;
     LaneOffs L;
@@ -538,16 +621,13 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
     S.duL = S.dvL = S.phiL = 0.0;
     Slots<R> c;
 
-    // Every load must be covered by the producers' published progress before it is issued.  Iteration i issues the
-    // loads of steps < (i + 2) R; its coverage check uses a poll that was itself issued one iteration earlier
-    // (consuming a poll forces an in-order vmcnt wait on every older load, so finer-grained polling stalls).
     // The coefficient operands depend on nobody: their first R steps are requested before the task waits.
     // Start-up in two stages: the first R steps' unknowns are requested as soon as the producers cover THEM; the check
     // for the next R steps (the refills of iteration 0) is made with a fresh poll at the start of iteration 0, while those
     // first loads are in flight -- a hand-off then costs R steps and one load latency less than waiting for 2R up front.
-    Unroll<R, R - 1, DPP>::fill_coef(T, L, c);
-    Polls pl = poll(D);
-    if (!wait_covered<0, 63, true>(A, pl, D, R)) end_task();
+    fill_coef(T, L, c);
+    Pipe P{poll(D), 0u, 0u};
+    if (!wait_covered<0, 63, true>(A, P.pl, D, R)) end_task();
     {  // centre of the first cells = the right-old of "step -1" (lanes >= 1: left of column 0, zero; lane 0: position 63
        // of the block above)
         const unsigned first = (lane != 0 || L.pd == kOob) ? kOob : L.pd - L.pos_d;
@@ -556,50 +636,16 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
         S.dvC = c0.y;
     }
     if (dbg) dbg[1] = __builtin_amdgcn_s_memrealtime();
-    Unroll<R, R - 1, DPP>::fill_unknowns(T, L, c);
-    pl = poll(D);
+    fill_unknowns(T, L, c);
+    P.pl = poll(D);
 
-    // MARKER loads: a 4-byte load issued right after the store of some step retires (vmcnt is in order) only after
-    // that store has completed, so consuming it a few steps later proves the step complete and lets the task
-    // publish it without draining the pipeline.  Two markers per iteration (after steps H-1 and R-1), each consumed
-    // DM steps later (4 / 5 / R - 3 at depth 6 / 8 / >= 10, see PAPOF_V_DM*), in the next iteration: published progress lags
-    // the real one by DM .. DM + R/2 steps.  The marker reads the abort word, so a raised abort also ends every running task within two iterations.
-    constexpr int H = R / 2, DM = R >= 10 ? R - 3 : (R == 8 ? PAPOF_V_DM8 : (R == 6 ? PAPOF_V_DM6 : H));
-    constexpr int CA = H + DM - R, CB = DM;  // steps of the NEXT iteration after which markers A / B are consumed
-    static_assert(CA >= 0 && CA < H && CB >= H && CB < R, "marker consumption points");
-    unsigned ma = 0u, mb = 0u;
-    // one iteration = R steps; `i` is only used for step numbers.  The first iteration is peeled off the loop so that the
-    // loop header joins two states with the same pipeline contents (after an iteration / after an iteration).
+    // markers are consumed 4 / 5 / R - 3 steps after issue at depth 6 / 8 / >= 10 (see PAPOF_V_DM*)
+    constexpr int DM = R >= 10 ? R - 3 : (R == 8 ? PAPOF_V_DM8 : (R == 6 ? PAPOF_V_DM6 : R / 2));
     const auto iteration = [&](int i, bool first) {
-        if (!wait_covered<0, 63, true>(A, pl, D, (i + 2) * R)) end_task();
-        // The poll for the next iteration's check is consumed at the start of the next iteration, where it waits (in
-        // order) for every load issued before it.  Issued in the middle of this iteration it is half an iteration fresher
-        // (a shorter hand-off) but then waits for the refills of the first half: at R >= 8 those are >= 4 steps old and long
-        // there (1080x607: 0.519 -> 0.505 ms, 810x455: 0.380 -> 0.370), at R = 6 only 3 steps (607x341: 0.336 -> 0.378).
-        constexpr bool kMidPoll = R >= PAPOF_V_MIDPOLL;
-        Polls pn{0u, 0u, 0u};
-        if (!kMidPoll) pn = poll(D);
-        // Markers are consumed DM = R - 3 steps after they were issued -- i.e. in the NEXT iteration: consuming a marker
-        // waits (in-order vmcnt) for every load issued before it, and with DM = 3 that exposed ~0.35 us of latency twice
-        // per iteration (the refills issued in those 3 steps).  R - 3 steps later all of them have long arrived.
-        Seg<R, 0, CA, DPP, SPLIT>::run(A, T, L, om1, i * R, c, S);
-        if (!first) {  // marker A of the previous iteration: its steps < (i-1)R + H are complete
-            asm volatile("" ::"v"(ma), "v"(S.duL), "v"(S.dvL) : "memory");
-            if (uni(ma) != 0u) end_task();
-            publish_all((unsigned)min(ns, (i - 1) * R + H));
-        }
-        Seg<R, CA, H, DPP, SPLIT>::run(A, T, L, om1, i * R, c, S);
-        ma = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker A: after step H - 1
-        if (kMidPoll) pn = poll(D);
-        Seg<R, H, CB, DPP, SPLIT>::run(A, T, L, om1, i * R, c, S);
-        if (!first) {  // marker B of the previous iteration: steps < i R are complete
-            asm volatile("" ::"v"(mb), "v"(S.duL), "v"(S.dvL) : "memory");
-            if (uni(mb) != 0u) end_task();
-            publish_all((unsigned)min(ns, i * R));
-        }
-        Seg<R, CB, R, DPP, SPLIT>::run(A, T, L, om1, i * R, c, S);
-        mb = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker B: after step R - 1
-        pl = pn;
+        pipeline_iteration<R, DM, R >= PAPOF_V_MIDPOLL, 0, 63, true>(
+            A, D, S, P, i, first,
+            [&](auto t, int s0) __attribute__((always_inline)) { step<R, t(), DPP, SPLIT>(A, T, L, om1, s0 + t(), c, S); },
+            publish_all);
     };
     iteration(0, true);
     if (dbg) dbg[2] = __builtin_amdgcn_s_memrealtime();
@@ -668,50 +714,18 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
         const D2 qa = as_d2(c.pa[t2]), qc = as_d2(c.pc[t2]);
         const u32x4 qbm = ID2 ? (c.pb[t2] & u32x4{0u, 0u, 0u, 0u}) : c.pb[t2];
         const D2 qb = as_d2(qbm);
-        const double phiC = qa.x, xy = qa.y;
-        const double duD = from_below<DPP>(duR2);
-        const double dvD = from_below<DPP>(dvR2);
-        double s1 = S2.phiL * S2.duL;
-        double s2 = S2.phiL * S2.dvL;
-        const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
-        const double upV = from_above<DPP>(s2);
-        s1 += phiC * duR2;
-        s2 += phiC * dvR2;
-        s1 += upU;
-        s2 += upV;
-        s1 += phiC * duD;
-        s2 += phiC * dvD;
-        s1 *= nalpha;
-        s2 *= nalpha;
-        s1 += xy * S2.dvC;
-        duN2 = F.om1b * S2.duC + qb.x * (qc.x - s1);
-        s2 += xy * duN2;
-        dvN2 = F.om1b * S2.dvC + qb.y * (qc.y - s2);
-        S2.phiL = moved(phiC);
+        const D2 n2 = wave_cell<DPP>(S2, F.om1b, nalpha, qa, qb, qc, duR2, dvR2);
+        duN2 = n2.x;
+        dvN2 = n2.y;
+        S2.phiL = moved(qa.x);
     }
     // ---- first sweep, column s - l (as k_sor_exact::step, with the per-lane ghost mask on (a1, a2))
     const D2 pa = as_d2(c.pa[t]), pc = as_d2(c.pc[t]), pd = as_d2(c.pd[t]);
     const u32x4 pbm = c.pb[t] & u32x4{F.m1, F.m1, F.m1, F.m1};
     const D2 pb = as_d2(pbm);
-    const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duD = from_below<DPP>(duR);
-    const double dvD = from_below<DPP>(dvR);
-    double s1 = S1.phiL * S1.duL;
-    double s2 = S1.phiL * S1.dvL;
-    const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
-    const double upV = from_above<DPP>(s2);
-    s1 += phiC * duR;
-    s2 += phiC * dvR;
-    s1 += upU;
-    s2 += upV;
-    s1 += phiC * duD;
-    s2 += phiC * dvD;
-    s1 *= nalpha;
-    s2 *= nalpha;
-    s1 += xy * S1.dvC;
-    const double duN = F.om1a * S1.duC + pb.x * (pc.x - s1);
-    s2 += xy * duN;
-    const double dvN = F.om1a * S1.dvC + pb.y * (pc.y - s2);
+    const double phiC = pa.x, duR = pd.x, dvR = pd.y;
+    const D2 n1 = wave_cell<DPP>(S1, F.om1a, nalpha, pa, pb, pc, duR, dvR);
+    const double duN = n1.x, dvN = n1.y;
     const double o1 = F.first_out ? duN : duN2, o2 = F.first_out ? dvN : dvN2;
     __builtin_amdgcn_raw_buffer_store_b128(as_u4(o1, o2), T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     store_data_guard();
@@ -729,20 +743,6 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
     if (!SKIP2) load_coef<R, t2>(T, L, s - 2 + R, c);  // the slot of step s - 2 is free now
 }
 
-template <int R, int t0, int t1, bool DPP, bool FIRST, bool ID2>
-struct FSeg {
-    static __device__ __forceinline__ void run(const ExactArgs& A, const Task& T, const LaneOffs& L, const FLane& F,
-                                               int s0, Slots<R>& c, State& S1, State& S2) {
-        f_step<R, t0, DPP, FIRST && t0 < 2, ID2>(A, T, L, F, s0 + t0, c, S1, S2);
-        FSeg<R, t0 + 1, t1, DPP, FIRST, ID2>::run(A, T, L, F, s0, c, S1, S2);
-    }
-};
-template <int R, int t1, bool DPP, bool FIRST, bool ID2>
-struct FSeg<R, t1, t1, DPP, FIRST, ID2> {
-    static __device__ __forceinline__ void run(const ExactArgs&, const Task&, const LaneOffs&, const FLane&, int,
-                                               Slots<R>&, State&, State&) {}
-};
-
 template <int R, bool DPP, bool ID2>
 __device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, const LaneOffs& L, const FLane& F,
                                       const Deps& D, unsigned my_prog) {
@@ -752,46 +752,25 @@ __device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, const L
     S1.duL = S1.dvL = S1.phiL = 0.0;
     S2.duL = S2.dvL = S2.phiL = S2.duC = S2.dvC = 0.0;
     Slots<R> c;
-    Unroll<R, R - 1, DPP>::fill_coef(T, L, c);
-    Polls pl = poll(D);
-    if (!wait_covered<1, 64, PAPOF_V_FSELECTIVE>(A, pl, D, R)) end_task();  // staged start-up, see k_sor_exact
+    fill_coef(T, L, c);
+    Pipe P{poll(D), 0u, 0u};
+    if (!wait_covered<1, 64, PAPOF_V_FSELECTIVE>(A, P.pl, D, R)) end_task();  // staged start-up, see k_sor_exact
     {  // centre of the first cells = the right operand of "step -1" (lanes >= 2: left of column 0, zero)
         const unsigned first = (F.own_block || L.pd == kOob) ? kOob : L.pd - L.pos_d;
         const D2 c0 = as_d2(__builtin_amdgcn_raw_buffer_load_b128(T.rd, first, 0, kAuxSc1));
         S1.duC = c0.x;
         S1.dvC = c0.y;
     }
-    Unroll<R, R - 1, DPP>::fill_unknowns(T, L, c);
-    pl = poll(D);
-    // markers, polls and the peeled first iteration: exactly as in k_sor_exact (see there)
-    constexpr int H = R / 2, DM = R == 6 ? PAPOF_V_FDM6 : (R == 8 ? PAPOF_V_FDM8 : (R >= 6 ? R - 3 : H));
-    constexpr int CA = H + DM - R, CB = DM;
-    static_assert(CA >= 0 && CA < H && CB >= H && CB < R, "marker consumption points");
-    unsigned ma = 0u, mb = 0u;
-    const auto iteration = [&](int i, auto first_c) {
-        constexpr bool first = decltype(first_c)::value;
-        if (!wait_covered<1, 64, PAPOF_V_FSELECTIVE>(A, pl, D, (i + 2) * R)) end_task();
-        constexpr bool kMidPoll = R >= PAPOF_V_FMIDPOLL;
-        Polls pn{0u, 0u, 0u};
-        if (!kMidPoll) pn = poll(D);
-        FSeg<R, 0, CA, DPP, first, ID2>::run(A, T, L, F, i * R, c, S1, S2);
-        if (!first) {
-            asm volatile("" ::"v"(ma), "v"(S1.duL), "v"(S1.dvL) : "memory");
-            if (uni(ma) != 0u) end_task();
-            publish(T, my_prog, (unsigned)min(ns, (i - 1) * R + H));
-        }
-        FSeg<R, CA, H, DPP, first, ID2>::run(A, T, L, F, i * R, c, S1, S2);
-        ma = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker A: after step H - 1
-        if (kMidPoll) pn = poll(D);
-        FSeg<R, H, CB, DPP, first, ID2>::run(A, T, L, F, i * R, c, S1, S2);
-        if (!first) {
-            asm volatile("" ::"v"(mb), "v"(S1.duL), "v"(S1.dvL) : "memory");
-            if (uni(mb) != 0u) end_task();
-            publish(T, my_prog, (unsigned)min(ns, i * R));
-        }
-        FSeg<R, CB, R, DPP, first, ID2>::run(A, T, L, F, i * R, c, S1, S2);
-        mb = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker B: after step R - 1
-        pl = pn;
+    fill_unknowns(T, L, c);
+    P.pl = poll(D);
+    constexpr int DM = R == 6 ? PAPOF_V_FDM6 : (R == 8 ? PAPOF_V_FDM8 : R - 3);  // see PAPOF_V_FDM*
+    const auto iteration = [&](int i, auto first) {
+        pipeline_iteration<R, DM, R >= PAPOF_V_FMIDPOLL, 1, 64, PAPOF_V_FSELECTIVE>(
+            A, D, S1, P, i, first(),
+            [&](auto t, int s0) __attribute__((always_inline)) {  // in steps 0 and 1 of the task there is no second sweep yet
+                f_step<R, t(), DPP, first() && t() < 2, ID2>(A, T, L, F, s0 + t(), c, S1, S2);
+            },
+            [&](unsigned steps) __attribute__((always_inline)) { publish(T, my_prog, steps); });
     };
     iteration(0, std::true_type{});
     for (int i = 1; i < n_iter; ++i) iteration(i, std::false_type{});
@@ -806,31 +785,9 @@ __global__ __launch_bounds__(64) void k_sor_fused(ExactArgs A) {
     const unsigned lane = threadIdx.x;
     const int pairs = (A.n_sor + 1) >> 1;
     int q, b;
-    if (A.xcd_affine) {  // as k_sor_exact: all pairs of a band on one XCD (<= 8 bands)
-        const int nf = A.nb >> 3, rem = A.nb & 7, S = 8 * nf + (rem ? 8 : 0);
-        const int ql = blockIdx.x / S;
-        q = A.k0 + ql;
-        const int r = blockIdx.x - ql * S;
-        if (r < 8 * nf) {
-            b = r;
-        } else {
-            const int j = r - 8 * nf - (nf ? q % (9 - rem) : 0);
-            if (j < 0 || j >= rem) return;
-            b = 8 * nf + j;
-        }
-    } else {
-        const int ql = blockIdx.x / A.nbl;
-        q = A.k0 + ql;
-        b = A.b0 + (blockIdx.x - ql * A.nbl);
-    }
+    if (!task_of_block(A, q, b)) return;  // with xcd_affine all pairs of a band on one XCD
     Task T;
-    const unsigned plane_bytes = (unsigned)(((size_t)A.npos * A.hp + kLanes) * 16u);
-    constexpr unsigned kBlock = kLanes * 16u;
-    const unsigned par_bytes = (unsigned)A.npos_d * (unsigned)A.nb * kBlock;
-    T.ra = __builtin_amdgcn_make_buffer_rsrc((void*)A.phi, 0, plane_bytes, 0x00020000);
-    T.rb = __builtin_amdgcn_make_buffer_rsrc((void*)A.a1, 0, plane_bytes, 0x00020000);
-    T.rc = __builtin_amdgcn_make_buffer_rsrc((void*)A.b1, 0, plane_bytes, 0x00020000);
-    T.rd = __builtin_amdgcn_make_buffer_rsrc((void*)A.du, 0, 2u * par_bytes, 0x00020000);
+    const unsigned par_bytes = plane_descriptors(A, T);
     const int r0 = kFusedRows * b - 2 * q - 2;  // image row of lane 0
     LaneOffs L;
     L.pos_c = (unsigned)A.hp * 16u;
@@ -916,24 +873,8 @@ struct GLane {  // per-lane constant byte offsets (VGPRs)
     unsigned st;           // store of step s at st + s * pos_d                   [kOob unless last wave of the group]
     unsigned hs;           // halo store of step s at hs + s * 16                 [lane 62 only]
     unsigned pos_c, pos_d;
+    __device__ __forceinline__ BufAt unknowns_at(int s) const { return BufAt{pd + (unsigned)s * pd_step, 0u}; }
 };
-
-template <int R>
-struct GSlots {
-    u32x4 pa[R], pb[R], pc[R], pd[R];
-};
-
-template <int R, int t>
-__device__ __forceinline__ void g_load_coef(const Task& T, const GLane& L, int s, GSlots<R>& c) {
-    const unsigned off = (unsigned)s * L.pos_c;
-    c.pa[t] = __builtin_amdgcn_raw_buffer_load_b128(T.ra, L.pa, off, kAuxPlain);
-    c.pb[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rb, L.pbc, off, kAuxPlain);
-    c.pc[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rc, L.pbc, off, kAuxPlain);
-}
-template <int R, int t>
-__device__ __forceinline__ void g_load_unknowns(const Task& T, const GLane& L, int s, GSlots<R>& c) {
-    c.pd[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rd, L.pd + (unsigned)s * L.pd_step, 0, kAuxSc1);
-}
 
 // Role of a wave inside its group (compile-time: four straight-line variants of the sweep loop, chosen once per
 // wave by a scalar branch, so that the memory-counter bookkeeping of the software pipeline stays exact).
@@ -944,9 +885,8 @@ typedef __attribute__((address_space(3))) volatile unsigned lds_word;
 
 template <int R, int t, bool DPP, bool FROM_LDS, bool TO_LDS>
 __device__ __forceinline__ void g_step(const GroupArgs& A, const Task& T, const GLane& L, lds_u32x4* ring_out,
-                                       unsigned lane, double om1, int s, GSlots<R>& c, const u32x4 (&lpd)[R / 2],
+                                       unsigned lane, double om1, int s, Slots<R>& c, const u32x4 (&lpd)[R / 2],
                                        State& S) {
-    const double nalpha = A.nalpha;
     const D2 pa = as_d2(c.pa[t]), pb = as_d2(c.pb[t]), pc = as_d2(c.pc[t]);
     u32x4 raw = c.pd[t];
     if (FROM_LDS) {
@@ -954,72 +894,34 @@ __device__ __forceinline__ void g_step(const GroupArgs& A, const Task& T, const 
         raw = lane != 0 ? l : raw;
     }
     const D2 pd = as_d2(raw);
-    const double phiC = pa.x, xy = pa.y, duR = pd.x, dvR = pd.y;
-    const double duD = from_below<DPP>(duR);
-    const double dvD = from_below<DPP>(dvR);
-    double s1 = S.phiL * S.duL;
-    double s2 = S.phiL * S.dvL;
-    const double upU = from_above<DPP>(s1);  // the up term = the left product of the lane above (see step())
-    const double upV = from_above<DPP>(s2);
-    s1 += phiC * duR;
-    s2 += phiC * dvR;
-    s1 += upU;
-    s2 += upV;
-    s1 += phiC * duD;
-    s2 += phiC * dvD;
-    s1 *= nalpha;
-    s2 *= nalpha;
-    s1 += xy * S.dvC;
-    const double duN = om1 * S.duC + pb.x * (pc.x - s1);
-    s2 += xy * duN;
-    const double dvN = om1 * S.dvC + pb.y * (pc.y - s2);
-    const u32x4 out = as_u4(duN, dvN);
+    const double phiC = pa.x, duR = pd.x, dvR = pd.y;
+    const D2 n = wave_cell<DPP>(S, om1, A.nalpha, pa, pb, pc, duR, dvR);
+    const u32x4 out = as_u4(n.x, n.y);
     if (TO_LDS)
         ring_out[(s & (kRing - 1)) * kLanes + lane] = out;
     else
         __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.hs + (unsigned)s * 16u, 0, kAuxSc1);  // lane 62 -> halo row
     store_data_guard();
-    S.duL = duN;
-    S.dvL = dvN;
+    S.duL = n.x;
+    S.dvL = n.y;
     S.phiL = moved(phiC);  // see moved(): no slot register may stay live across its refill
     S.duC = moved(duR);
     S.dvC = moved(dvR);
     asm volatile("" ::: "memory");
-    g_load_coef<R, t>(T, L, s + R, c);
-    g_load_unknowns<R, t>(T, L, s + R, c);
+    load_slot<R, t>(T, L, s + R, c);
 }
 
-template <int R, int t0, int t1, bool DPP, bool FROM_LDS, bool TO_LDS>
-struct GSeg {
-    static __device__ __forceinline__ void run(const GroupArgs& A, const Task& T, const GLane& L, lds_u32x4* ring_out,
-                                               unsigned lane, double om1, int s0, GSlots<R>& c,
-                                               const u32x4 (&lpd)[R / 2], State& S) {
-        g_step<R, t0, DPP, FROM_LDS, TO_LDS>(A, T, L, ring_out, lane, om1, s0 + t0, c, lpd, S);
-        GSeg<R, t0 + 1, t1, DPP, FROM_LDS, TO_LDS>::run(A, T, L, ring_out, lane, om1, s0, c, lpd, S);
-    }
-};
-template <int R, int t1, bool DPP, bool FROM_LDS, bool TO_LDS>
-struct GSeg<R, t1, t1, DPP, FROM_LDS, TO_LDS> {
-    static __device__ __forceinline__ void run(const GroupArgs&, const Task&, const GLane&, lds_u32x4*, unsigned,
-                                               double, int, GSlots<R>&, const u32x4 (&)[R / 2], State&) {}
-};
-template <int R, int t>
-struct GFill {
-    static __device__ __forceinline__ void coef(const Task& T, const GLane& L, GSlots<R>& c) {
-        GFill<R, t - 1>::coef(T, L, c);
-        g_load_coef<R, t>(T, L, t, c);
-    }
-    static __device__ __forceinline__ void unknowns(const Task& T, const GLane& L, GSlots<R>& c) {
-        GFill<R, t - 1>::unknowns(T, L, c);
-        g_load_unknowns<R, t>(T, L, t, c);
-    }
-};
-template <int R>
-struct GFill<R, -1> {
-    static __device__ __forceinline__ void coef(const Task&, const GLane&, GSlots<R>&) {}
-    static __device__ __forceinline__ void unknowns(const Task&, const GLane&, GSlots<R>&) {}
-};
+// steps T0 .. T1-1 of the unrolled iteration that starts with step s0 (a function of its own: the same static_for written
+// inside g_run_wave's `iteration` lambda, which is inlined by cost, changes the code of every instance)
+template <int R, int T0, int T1, bool DPP, bool FROM_LDS, bool TO_LDS>
+__device__ __forceinline__ void g_steps(const GroupArgs& A, const Task& T, const GLane& L, lds_u32x4* ring_out,
+                                        unsigned lane, double om1, int s0, Slots<R>& c, const u32x4 (&lpd)[R / 2],
+                                        State& S) {
+    static_for<T0, T1>([&](auto t) __attribute__((always_inline)) {
+        g_step<R, t(), DPP, FROM_LDS, TO_LDS>(A, T, L, ring_out, lane, om1, s0 + t(), c, lpd, S);
+    });
+}
 
 // LDS progress words: the LDS unit executes a wave's operations in order, so cells written before a word are visible to
 // whoever has seen the word; an explicit lgkmcnt wait keeps the issue order.  Bounded like every other wait.
@@ -1069,7 +971,7 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
     };
     State S;
     S.duL = S.dvL = S.phiL = 0.0;
-    GSlots<R> c;
+    Slots<R> c;
     u32x4 lpd[H];
 #pragma unroll
     for (int q = 0; q < H; q++) lpd[q] = u32x4{0u, 0u, 0u, 0u};
@@ -1077,7 +979,7 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
 
     unsigned long long t_cov = 0, t_in = 0, t_out = 0, t_start = 0;
     const bool dbg = A.dbg != nullptr;
-    GFill<R, R - 1>::coef(T, L, c);
+    fill_coef(T, L, c);
     Polls pl = poll(W.D);
     if (!wait_covered<1, 63>(X, pl, W.D, 2 * R)) return give_up();
     if (dbg) t_start = __builtin_amdgcn_s_memtime();
@@ -1087,7 +989,7 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
         S.duC = c0.x;
         S.dvC = c0.y;
     }
-    GFill<R, R - 1>::unknowns(T, L, c);
+    fill_unknowns(T, L, c);
 
     // one half-iteration = H steps: LDS operands in, steps, progress words out
     const auto half_begin = [&](int sa) -> bool {
@@ -1115,8 +1017,10 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
         }
     };
 
-    // markers consumed R - 3 steps after issue, in the next iteration, and the first iteration peeled -- as in
-    // k_sor_exact (see there)
+    // The iteration of pipeline_iteration() (markers consumed R - 3 steps after issue, in the next iteration, and the first
+    // iteration peeled), on a form of its own: folding it in would cost that skeleton two more hooks (half_begin / half_end),
+    // a third way to give up (a wave of a group RETURNS, to tell its siblings, where a lone task ends) and switches for the
+    // check iteration 0 skips and the time stamps -- more parameters than the lines it would save.
     constexpr int DL = R - 3, CA = H + DL - R, CB = DL;
     static_assert(CA >= 0 && CA < H && CB >= H && CB < R, "marker consumption points");
     unsigned ma = 0u, mb = 0u;
@@ -1127,23 +1031,23 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
         const Polls pn = poll(W.D);
         const int s0 = i * R;
         if (!half_begin(s0)) return false;
-        GSeg<R, 0, CA, DPP, FROM_LDS, TO_LDS>::run(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
+        g_steps<R, 0, CA, DPP, FROM_LDS, TO_LDS>(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
         if (!first) {  // marker A of the previous iteration
             asm volatile("" ::"v"(ma), "v"(S.duL), "v"(S.dvL) : "memory");
             if (uni(ma) != 0u) return false;
             publish(T, W.my_prog, (unsigned)min(ns, s0 - R + H));
         }
-        GSeg<R, CA, H, DPP, FROM_LDS, TO_LDS>::run(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
+        g_steps<R, CA, H, DPP, FROM_LDS, TO_LDS>(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
         ma = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker A: after step H - 1
         half_end(s0);
         if (!half_begin(s0 + H)) return false;
-        GSeg<R, H, CB, DPP, FROM_LDS, TO_LDS>::run(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
+        g_steps<R, H, CB, DPP, FROM_LDS, TO_LDS>(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
         if (!first) {  // marker B of the previous iteration
             asm volatile("" ::"v"(mb), "v"(S.duL), "v"(S.dvL) : "memory");
             if (uni(mb) != 0u) return false;
             publish(T, W.my_prog, (unsigned)min(ns, s0));
         }
-        GSeg<R, CB, R, DPP, FROM_LDS, TO_LDS>::run(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
+        g_steps<R, CB, R, DPP, FROM_LDS, TO_LDS>(A, T, L, W.ring_out, lane, om1, s0, c, lpd, S);
         mb = __hip_atomic_load(A.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // marker B: after step R - 1
         half_end(s0 + H);
         pl = pn;
@@ -1208,7 +1112,6 @@ __global__ __launch_bounds__(64 * M) void k_sor_group(GroupArgs A) {
 
     Task T;
     const unsigned plane_bytes = (unsigned)(((size_t)A.npos * A.hp + kLanes) * 16u);
-    constexpr unsigned kBlock = kLanes * 16u;
     const unsigned par_bytes = (unsigned)A.npos_d * (unsigned)A.nb * kBlock;
     const unsigned all_bytes = A.halo_off + (unsigned)A.n_sor * (unsigned)A.nb * (unsigned)A.npos_d * 16u;
     T.ra = __builtin_amdgcn_make_buffer_rsrc((void*)A.phi, 0, plane_bytes, 0x00020000);
@@ -1300,14 +1203,6 @@ struct BlockedArgs {
     unsigned long long* stamp;  // as ExactArgs::stamp
     double nalpha, om1;
 };
-
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (N > 0) {
-        static_for<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
 
 template <bool VEC>
 __device__ __forceinline__ f64x2 load_pair(const double* __restrict__ plane, size_t o, bool ok0, bool ok1) {
@@ -1438,20 +1333,9 @@ __global__ __launch_bounds__(NW * 64) void k_sor_blocked(BlockedArgs A) {
             wu = ph[rr - 1][1 + p];
         else
             wu = up[p];
-        double s1 = wl * L.x, s2 = wl * L.y;
-        s1 += pc * R.x;
-        s2 += pc * R.y;
-        s1 += wu * U.x;
-        s2 += wu * U.y;
-        s1 += pc * D.x;
-        s2 += pc * D.y;
-        s1 *= nalpha;
-        s2 *= nalpha;
-        s1 += cxy[rr][p] * own.y;
-        const double nu = om1 * own.x + ca1[rr][p] * (cb1[rr][p] - s1);
-        s2 += cxy[rr][p] * nu;
-        const double nv = om1 * own.y + ca2[rr][p] * (cb2[rr][p] - s2);
-        return f64x2{nu, nv};
+        const D2 n = sor_cell(wl, L.x, L.y, wu, U.x, U.y, pc, R.x, R.y, D.x, D.y, nalpha, cxy[rr][p], own.x,
+                              own.y, om1, ca1[rr][p], ca2[rr][p], cb1[rr][p], cb2[rr][p]);
+        return f64x2{n.x, n.y};
     };
     if (MODE == PAPOF_SOR_REDBLACK) {
         // PAR = parity of (q0 + colour): the member of the lane's pair that has the half-sweep's colour in row rr is
@@ -1672,21 +1556,10 @@ __global__ __launch_bounds__(NW * 64) void k_sor_tiny(TinyArgs A_in) {
                     ndown = own0[(c + 1) * LS + RS];
                 }
                 const double pc = cphi[t][c];
-                // the terms in the reference's order: left, right, up, down (src/OpticalFlow.cpp:468-495)
-                double s1 = wl * left.x, s2 = wl * left.y;
-                s1 += pc * right.x;
-                s2 += pc * right.y;
-                s1 += cup[t][c] * up.x;
-                s2 += cup[t][c] * up.y;
-                s1 += pc * down.x;
-                s2 += pc * down.y;
-                s1 *= nalpha;
-                s2 *= nalpha;
-                s1 += cxy[t][c] * own.y;
-                const double nu = om1 * own.x + ca1[t][c] * (cb1[t][c] - s1);
-                s2 += cxy[t][c] * nu;
-                const double nv = om1 * own.y + ca2[t][c] * (cb2[t][c] - s2);
-                left = f64x2{nu, nv};
+                const D2 n = sor_cell(wl, left.x, left.y, cup[t][c], up.x, up.y, pc, right.x, right.y,
+                                      down.x, down.y, nalpha, cxy[t][c], own.x, own.y, om1, ca1[t][c], ca2[t][c],
+                                      cb1[t][c], cb2[t][c]);
+                left = f64x2{n.x, n.y};
                 wl = pc;
                 own = right;
                 // written at once: nobody reads this cell in this tile-time (tiles that share a T are not neighbours, and the
@@ -1726,6 +1599,112 @@ static int fill_pairs(papof_handle* h, void* base, size_t stride_bytes, size_t b
 static int resident_tasks(const papof_handle* h) {
     if (h->sor_resident > 0) return h->sor_resident;
     return std::max(64, (h->cu_count > 0 ? h->cu_count : 256) * 8);
+}
+
+// ---- the exact-order kernels' host side: arguments and instance selection (sor_solve, sor_solve_bands) ---------------
+// The arguments of a WHOLE, unbatched, unsplit solve in the bound layout `sd`, every band, first sweep, no diagnostics; the
+// callers set what differs (k0 per launch, b0 / nbl, xcd_affine, the batch strides, the split fields, dbg).
+static ExactArgs exact_args(const papof_handle* h, const SorPlanes& sp, const SkewDims& sd, int H, int W, double alpha,
+                            double omega, int n_sor, unsigned* prog) {
+    ExactArgs A;
+    A.phi = sp.phi;
+    A.xy = sp.xy;  // paired planes: only phi / a1 / b1 / du are used as the four plane bases
+    A.a1 = sp.a1;
+    A.a2 = sp.a2;
+    A.b1 = sp.b1;
+    A.b2 = sp.b2;
+    A.du = sp.du;
+    A.dv = sp.dv;
+    A.prog = prog;
+    A.abort = h->sync_words;
+    A.H = H;
+    A.W = W;
+    A.nb = sd.nb;
+    A.ns = sd.ns;
+    A.hp = sd.hp;
+    A.npos = sd.npos;
+    A.qt = sd.qt;
+    A.rt = sd.rt;
+    A.npos_d = sd.npos_d;
+    A.n_sor = n_sor;
+    A.xcd_affine = 0;
+    A.k0 = 0;
+    A.b0 = 0;
+    A.nbl = sd.nb;
+    A.nalpha = -alpha;
+    A.om1 = 1 - omega;
+    A.dbg = nullptr;
+    A.stamp = nullptr;  // no stamp at the head of the critical task (flow_internal.h: PhaseClock)
+    A.peer_du = nullptr;
+    A.peer_prog = nullptr;
+    A.top_cut = A.bot_cut = 0;
+    A.bs_coef = A.bs_d = A.bs_prog = 0;
+    A.skip_dead = h->sor_skip_dead;
+    return A;
+}
+
+// Pipeline depth of k_sor_exact: every load is issued R steps ahead and a task looks 2R steps ahead of its producers, so R
+// is also what a hand-off costs.  Measured (profiles/r01_s2_sor_depth_sweep.txt): the big levels want the deeper
+// pipeline (throughput; with the mid-iteration poll 1440x810: 0.85 -> 0.81 ms, 1080x607: 0.68 -> 0.65 ms), the
+// small, hand-off-bound levels the shorter one (607x341: 0.53 -> 0.47 ms).  (In-pair A/B of round 2: 6 / 10 on the big
+// levels, 4 / 8 on the small ones: all worse.)
+static int exact_depth(const papof_handle* h, const SkewDims& sd) {
+    return h->sor_depth > 0 ? h->sor_depth : (sd.nb >= 8 ? 8 : 6);
+}
+// ... of k_sor_fused (effective depth R - 2): isolated solves are equal at 6 / 8 / 10 (profiles/r01_s3_sor_sweeps.txt), but
+// INSIDE a pair -- other cache contents, the preparation stream beside it -- 8 is 0.18 ms per 1080p pair faster than 6 and
+// 0.07 faster than 10 (same-box A/B, profiles/r02_ab_variants.txt)
+static int fused_depth(const papof_handle* h) { return h->sor_depth > 0 ? h->sor_depth : 8; }
+
+// The instance of k_sor_exact for depth R.  dpp = false: the __shfl variant (depth 8 only); split: the SPLIT variants
+// (depths 6 and 8 only, DPP only: sor_solve_bands checks)
+static void launch_exact(const papof_handle* h, int R, bool dpp, bool split, dim3 grid, const ExactArgs& A) {
+    const dim3 block(kLanes);
+    if (split) {
+        if (R <= 6)
+            hipLaunchKernelGGL((k_sor_exact<6, true, true>), grid, block, 0, h->stream, A);
+        else
+            hipLaunchKernelGGL((k_sor_exact<8, true, true>), grid, block, 0, h->stream, A);
+    } else if (!dpp)
+        hipLaunchKernelGGL((k_sor_exact<8, false>), grid, block, 0, h->stream, A);
+    else if (R <= 4)
+        hipLaunchKernelGGL((k_sor_exact<4, true>), grid, block, 0, h->stream, A);
+    else if (R <= 6)
+        hipLaunchKernelGGL((k_sor_exact<6, true>), grid, block, 0, h->stream, A);
+    else if (R <= 8)
+        hipLaunchKernelGGL((k_sor_exact<8, true>), grid, block, 0, h->stream, A);
+    else if (R <= 10)
+        hipLaunchKernelGGL((k_sor_exact<10, true>), grid, block, 0, h->stream, A);
+    else
+        hipLaunchKernelGGL((k_sor_exact<12, true>), grid, block, 0, h->stream, A);
+}
+// ... of k_sor_fused
+static void launch_fused(const papof_handle* h, int R, dim3 grid, const ExactArgs& A) {
+    const dim3 block(kLanes);
+    if (R <= 6)
+        hipLaunchKernelGGL((k_sor_fused<6, true>), grid, block, 0, h->stream, A);
+    else if (R <= 8)
+        hipLaunchKernelGGL((k_sor_fused<8, true>), grid, block, 0, h->stream, A);
+    else if (R <= 10)
+        hipLaunchKernelGGL((k_sor_fused<10, true>), grid, block, 0, h->stream, A);
+    else
+        hipLaunchKernelGGL((k_sor_fused<12, true>), grid, block, 0, h->stream, A);
+}
+// ... of k_sor_group for `group` sweeps per workgroup; false: there is none
+static bool launch_group(const papof_handle* h, int group, int R, dim3 grid, const GroupArgs& A) {
+    if (group == 4 && R >= 12)
+        hipLaunchKernelGGL((k_sor_group<12, 4, true>), grid, dim3(kLanes * 4), 0, h->stream, A);
+    else if (group == 4 && R >= 10)
+        hipLaunchKernelGGL((k_sor_group<10, 4, true>), grid, dim3(kLanes * 4), 0, h->stream, A);
+    else if (group == 4 && R >= 8)
+        hipLaunchKernelGGL((k_sor_group<8, 4, true>), grid, dim3(kLanes * 4), 0, h->stream, A);
+    else if (group == 4)
+        hipLaunchKernelGGL((k_sor_group<6, 4, true>), grid, dim3(kLanes * 4), 0, h->stream, A);
+    else if (group == 2)
+        hipLaunchKernelGGL((k_sor_group<8, 2, true>), grid, dim3(kLanes * 2), 0, h->stream, A);
+    else
+        return false;
+    return true;
 }
 
 // ---- the blocked solver's host side -------------------------------------------------------------------
@@ -2044,40 +2023,14 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
             const size_t nbytes = (size_t)sd.nb * n_sor * kProgStride * sizeof(unsigned);
             PAPOF_HIP(hipMemsetAsync(prog, 0, nbytes, h->stream));
         }
-        ExactArgs A;
-        A.phi = sp.phi;
-        A.xy = sp.xy;  // paired planes: only phi / a1 / b1 / du are used as the four plane bases
-        A.a1 = sp.a1;
-        A.a2 = sp.a2;
-        A.b1 = sp.b1;
-        A.b2 = sp.b2;
-        A.du = sp.du;
-        A.dv = sp.dv;
-        A.prog = prog;
-        A.abort = h->sync_words;
-        A.H = H;
-        A.W = W;
-        A.nb = sd.nb;
-        A.ns = sd.ns;
-        A.hp = sd.hp;
-        A.npos = sd.npos;
-        A.qt = sd.qt;
-        A.rt = sd.rt;
-        A.npos_d = sd.npos_d;
-        A.n_sor = n_sor;
-        A.nalpha = nalpha;
-        A.om1 = om1;
-        A.k0 = 0;
-        A.b0 = 0;
-        A.nbl = sd.nb;
-        A.peer_du = nullptr;
-        A.peer_prog = nullptr;
-        A.top_cut = A.bot_cut = 0;
-        A.skip_dead = h->sor_skip_dead;
-        A.bs_coef = bt ? bt->coef : 0;
-        A.bs_d = bt ? bt->d : 0;
-        A.bs_prog = bt ? bt->prog : 0;
-        A.dbg = bt ? nullptr : h->sor_dbg;
+        ExactArgs A = exact_args(h, sp, sd, H, W, alpha, omega, n_sor, prog);
+        if (bt) {
+            A.bs_coef = bt->coef;
+            A.bs_d = bt->d;
+            A.bs_prog = bt->prog;
+        } else {
+            A.dbg = h->sor_dbg;
+        }
         // Fault injection for the tests (tests/test_gpu_parity.py): raise the abort word before the launch, as a task whose
         // bounded wait expired would -- every task must then END (s_endpgm on the fast path, the polling loops' abort
         // check elsewhere) and the call must report PAPOF_ETIMEOUT instead of hanging or returning numbers.
@@ -2125,19 +2078,7 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
                 Ga.g0 = g0;
                 h->sor_launches++;
                 Ga.stamp = nullptr;  // no stamp at the head of the critical task (flow_internal.h: PhaseClock)
-                const dim3 ggrid(per_g * std::min(chunk, groups - g0));
-                if (sd.group == 4 && Rg >= 12)
-                    hipLaunchKernelGGL((k_sor_group<12, 4, true>), ggrid, dim3(kLanes * 4), 0, h->stream, Ga);
-                else if (sd.group == 4 && Rg >= 10)
-                    hipLaunchKernelGGL((k_sor_group<10, 4, true>), ggrid, dim3(kLanes * 4), 0, h->stream, Ga);
-                else if (sd.group == 4 && Rg >= 8)
-                    hipLaunchKernelGGL((k_sor_group<8, 4, true>), ggrid, dim3(kLanes * 4), 0, h->stream, Ga);
-                else if (sd.group == 4)
-                    hipLaunchKernelGGL((k_sor_group<6, 4, true>), ggrid, dim3(kLanes * 4), 0, h->stream, Ga);
-                else if (sd.group == 2)
-                    hipLaunchKernelGGL((k_sor_group<8, 2, true>), ggrid, dim3(kLanes * 2), 0, h->stream, Ga);
-                else
-                    return PAPOF_EINVAL;
+                if (!launch_group(h, sd.group, Rg, dim3(per_g * std::min(chunk, groups - g0)), Ga)) return PAPOF_EINVAL;
             }
             PAPOF_HIP(hipGetLastError());
             mark(0);
@@ -2148,24 +2089,12 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
             const int pairs = (n_sor + 1) / 2;
             A.xcd_affine = (h->sor_xcd_affine && (sd.nb <= 8 || h->sor_xcd_affine > 1)) ? 1 : 0;
             const int per_q = A.xcd_affine ? 8 * ((sd.nb + 7) / 8) : sd.nb;  // workgroups per pair of sweeps
-            // depth 8: isolated solves are equal at 6 / 8 / 10 (profiles/r01_s3_sor_sweeps.txt), but INSIDE a pair -- other
-            // cache contents, the preparation stream beside it -- 8 is 0.18 ms per 1080p pair faster than 6 and 0.07 faster
-            // than 10 (same-box A/B, profiles/r02_ab_variants.txt)
-            const int Rf = h->sor_depth > 0 ? h->sor_depth : 8;
+            const int Rf = fused_depth(h);
             const int chunk = std::max(1, resident_tasks(h) / per_q);
             for (int q0 = 0; q0 < pairs; q0 += chunk) {
                 A.k0 = q0;
                 h->sor_launches++;
-                A.stamp = nullptr;
-                const dim3 fgrid(per_q * std::min(chunk, pairs - q0));
-                if (Rf <= 6)
-                    hipLaunchKernelGGL((k_sor_fused<6, true>), fgrid, dim3(kLanes), 0, h->stream, A);
-                else if (Rf <= 8)
-                    hipLaunchKernelGGL((k_sor_fused<8, true>), fgrid, dim3(kLanes), 0, h->stream, A);
-                else if (Rf <= 10)
-                    hipLaunchKernelGGL((k_sor_fused<10, true>), fgrid, dim3(kLanes), 0, h->stream, A);
-                else
-                    hipLaunchKernelGGL((k_sor_fused<12, true>), fgrid, dim3(kLanes), 0, h->stream, A);
+                launch_fused(h, Rf, dim3(per_q * std::min(chunk, pairs - q0)), A);
             }
             PAPOF_HIP(hipGetLastError());
             mark(0);
@@ -2181,31 +2110,12 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
         // that the XCDs are loaded equally: 0.82).
         if (bt) A.xcd_affine = 0;
         const int per_k = A.xcd_affine ? 8 * ((sd.nb + 7) / 8) : sd.nb;  // workgroups per sweep
-        const dim3 block(kLanes);
-        // pipeline depth: every load is issued R steps ahead and a task looks 2R steps ahead of its producers, so R is
-        // also what a hand-off costs.  Measured (profiles/r01_s2_sor_depth_sweep.txt): the big levels want the deeper
-        // pipeline (throughput; with the mid-iteration poll 1440x810: 0.85 -> 0.81 ms, 1080x607: 0.68 -> 0.65 ms), the
-        // small, hand-off-bound levels the shorter one (607x341: 0.53 -> 0.47 ms).
-        const int R = h->sor_depth > 0 ? h->sor_depth : (sd.nb >= 8 ? 8 : 6);  // (in-pair A/B of round 2: 6 / 10 on the big
-                                                                                // levels, 4 / 8 on the small ones: all worse)
+        const int R = exact_depth(h, sd);
         const int chunk = std::max(1, resident_tasks(h) / (per_k * batch));  // (every task of a launch resident: all pairs' count)
         for (int k0 = 0; k0 < n_sor; k0 += chunk) {
             A.k0 = k0;
             h->sor_launches++;
-            A.stamp = nullptr;
-            const dim3 grid(per_k * std::min(chunk, n_sor - k0), batch);
-            if (!h->use_dpp)
-                hipLaunchKernelGGL((k_sor_exact<8, false>), grid, block, 0, h->stream, A);
-            else if (R <= 4)
-                hipLaunchKernelGGL((k_sor_exact<4, true>), grid, block, 0, h->stream, A);
-            else if (R <= 6)
-                hipLaunchKernelGGL((k_sor_exact<6, true>), grid, block, 0, h->stream, A);
-            else if (R <= 8)
-                hipLaunchKernelGGL((k_sor_exact<8, true>), grid, block, 0, h->stream, A);
-            else if (R <= 10)
-                hipLaunchKernelGGL((k_sor_exact<10, true>), grid, block, 0, h->stream, A);
-            else
-                hipLaunchKernelGGL((k_sor_exact<12, true>), grid, block, 0, h->stream, A);
+            launch_exact(h, R, h->use_dpp, false, dim3(per_k * std::min(chunk, n_sor - k0), batch), A);
         }
         PAPOF_HIP(hipGetLastError());
         mark(0);
@@ -2319,75 +2229,23 @@ int sor_solve_bands(papof_handle* h, const SorPlanes& sp, int H, int W, double a
     const unsigned n16 = (unsigned)(2 * sd.npos_d) * (unsigned)nbl * kLanes;
     hipLaunchKernelGGL(k_sor_clear_bands, dim3((n16 + 255) / 256), dim3(256), 0, h->stream, (uint4*)sp.du, sd.nb, b0, nbl,
                        n16);
-    ExactArgs A;
-    A.phi = sp.phi;
-    A.xy = sp.xy;
-    A.a1 = sp.a1;
-    A.a2 = sp.a2;
-    A.b1 = sp.b1;
-    A.b2 = sp.b2;
-    A.du = sp.du;
-    A.dv = sp.dv;
-    A.prog = prog;
-    A.abort = h->sync_words;
-    A.H = H;
-    A.W = W;
-    A.nb = sd.nb;
-    A.ns = sd.ns;
-    A.hp = sd.hp;
-    A.npos = sd.npos;
-    A.qt = sd.qt;
-    A.rt = sd.rt;
-    A.npos_d = sd.npos_d;
-    A.n_sor = n_sor;
-    A.nalpha = -alpha;
-    A.om1 = 1 - omega;
-    A.k0 = 0;
+    ExactArgs A = exact_args(h, sp, sd, H, W, alpha, omega, n_sor, prog);
     A.b0 = b0;
     A.nbl = nbl;
-    A.xcd_affine = 0;
-    A.dbg = nullptr;
-    A.stamp = nullptr;
-    A.bs_coef = A.bs_d = A.bs_prog = 0;
-    A.skip_dead = h->sor_skip_dead;
-    A.peer_du = split ? split->peer_du : nullptr;
-    A.peer_prog = split ? split->peer_prog : nullptr;
-    A.top_cut = split && split->top_cut ? 1 : 0;
-    A.bot_cut = split && split->bot_cut && split->peer_du && split->peer_prog ? 1 : 0;
-    if (split && split->bot_cut && !A.bot_cut) return PAPOF_EINVAL;
-    if (h->sor_mark) h->sor_mark(h->sor_mark_ctx, 1);
     if (split) {
-        const int R = h->sor_depth > 0 ? h->sor_depth : (sd.nb >= 8 ? 8 : 6);
-        const dim3 grid(nbl * n_sor);
-        if (R <= 6)
-            hipLaunchKernelGGL((k_sor_exact<6, true, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else
-            hipLaunchKernelGGL((k_sor_exact<8, true, true>), grid, dim3(kLanes), 0, h->stream, A);
-    } else if (sd.fuse == 2) {
-        const int pairs = (n_sor + 1) / 2, Rf = h->sor_depth > 0 ? h->sor_depth : 8;
-        const dim3 grid(nbl * pairs);
-        if (Rf <= 6)
-            hipLaunchKernelGGL((k_sor_fused<6, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else if (Rf <= 8)
-            hipLaunchKernelGGL((k_sor_fused<8, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else if (Rf <= 10)
-            hipLaunchKernelGGL((k_sor_fused<10, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else
-            hipLaunchKernelGGL((k_sor_fused<12, true>), grid, dim3(kLanes), 0, h->stream, A);
-    } else {
-        const int R = h->sor_depth > 0 ? h->sor_depth : (sd.nb >= 8 ? 8 : 6);
-        const dim3 grid(nbl * n_sor);
-        if (R <= 4)
-            hipLaunchKernelGGL((k_sor_exact<4, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else if (R <= 6)
-            hipLaunchKernelGGL((k_sor_exact<6, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else if (R <= 8)
-            hipLaunchKernelGGL((k_sor_exact<8, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else if (R <= 10)
-            hipLaunchKernelGGL((k_sor_exact<10, true>), grid, dim3(kLanes), 0, h->stream, A);
-        else
-            hipLaunchKernelGGL((k_sor_exact<12, true>), grid, dim3(kLanes), 0, h->stream, A);
+        A.peer_du = split->peer_du;
+        A.peer_prog = split->peer_prog;
+        A.top_cut = split->top_cut ? 1 : 0;
+        A.bot_cut = split->bot_cut && split->peer_du && split->peer_prog ? 1 : 0;
+        if (split->bot_cut && !A.bot_cut) return PAPOF_EINVAL;
     }
+    if (h->sor_mark) h->sor_mark(h->sor_mark_ctx, 1);
+    // (always the DPP instances: split solves require them above, sor_strips_supported() for the strips; sor_solve falls
+    // back to the __shfl instance instead)
+    if (sd.fuse == 2)  // (never split, see above)
+        launch_fused(h, fused_depth(h), dim3(nbl * ((n_sor + 1) / 2)), A);
+    else
+        launch_exact(h, exact_depth(h, sd), true, split != nullptr, dim3(nbl * n_sor), A);
     PAPOF_HIP(hipGetLastError());
     h->sor_launches++;
     if (h->sor_mark) h->sor_mark(h->sor_mark_ctx, 0);
