@@ -10,6 +10,7 @@
 #include "sampler.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace papof {
 
@@ -1092,13 +1093,21 @@ __global__ __launch_bounds__(256) void k_assemble_skew(const double* __restrict_
 // order are those of the two kernels it replaces: same bits.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFT = 16, kFH = 4, kFW = kFT + 2 * kFH;  // tile rows and columns, halo, tile rows with halo
-// [163 registers: three workgroups per CU; forcing four or five waves per SIMD spills: 11.2 / 12.8 ms per 1080p pair against 10.35]
+// [162 - 164 registers (at most 168: three workgroups per CU, tests/test_codegen_flow_system.py); forcing four or five waves per
+// SIMD spills: 11.2 / 12.8 ms per 1080p pair against 10.35]
 // SKEW: the operands go to the exact-order solver's paired, skewed planes (pa, pb, pc); otherwise to six row-major planes
 // (q[0..5] = phi, xy, a1, a2, b1, b2: the one-workgroup solver of the small levels, k_sor_tiny).
 struct SixPlanes {
     double* q[6];
 };
-template <int PLANES, bool SKEW, bool BATCH = false>
+typedef double tap_pair __attribute__((ext_vector_type(2), aligned(8)));  // two neighbouring elements of a plane: ONE 16-byte load
+__device__ __forceinline__ double plane_ld(const double* plane, unsigned byte_off) {  // uniform base + 32-bit lane offset
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(plane) + byte_off);
+}
+__device__ __forceinline__ tap_pair plane_ld2(const double* plane, unsigned byte_off) {
+    return *reinterpret_cast<const tap_pair*>(reinterpret_cast<const char*>(plane) + byte_off);
+}
+template <int PLANES, bool SKEW, bool BATCH = false, bool W1 = false>
 __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict__ im1, const double* __restrict__ im2,
                                                      const double* __restrict__ u, const double* __restrict__ v,
                                                      const double* __restrict__ im1s, int H, int W, double alpha,
@@ -1135,32 +1144,73 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     const int vy0 = max(0, row0 - kFH), vy1 = min(H, row1 + kFH);  // rows on which the operands are valid
     const bool interior = ib >= vy0 + kFH && ib + kFT <= row1 && ib + kFT + kFH <= vy1 && j0 >= kFH && j0 + kFT + kFH <= W;  // block-uniform
     // ---- bilinear taps of the tile's pixels, once for all channels: (x0, y0), (dx, dy), or "outside" (frame 1's value)
+    // The 576 pixels are three slots per thread: pixel tid, pixel tid + 256 (10 rows and 16 columns further on in the 24-wide
+    // tile) and pixel 512 + lane.  The third slot is ONE wave's worth of pixels: every wave holds its taps and the four waves
+    // take turns at it, channel by channel (wave k & 3 on channel k; a scalar test), so that no wave gathers and blends for
+    // pixels that do not exist and none is always the last at the barrier.
+    // All addressing is per-lane 32-bit BYTE offsets into a channel plane, computed here once (flow_system() refuses planes
+    // beyond 2^29 elements); the channel's plane is a wave-uniform base.
     constexpr int kPer = (kFW * HWc + NT - 1) / NT;  // 3 (576 pixels, NT = 16 x 16)
-    int t_o[kPer], t_x0[kPer], t_y0[kPer];
+    static_assert(kFW * HWc == 2 * NT + 64 && NT + 16 < kFW * HWc, "the three slots of the warp");
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr bool w1 = W1;  // W == 1, one column: no pair of taps to load (an instantiation of its own, flow_system())
+    unsigned t_o[kPer], t_b0[kPer], t_b1[kPer];  // byte offsets of the own pixel and of the taps' two footprint rows
+    int t_ra[kPer];  // the pixel's place in raw
     double t_dx[kPer], t_dy[kPer];
-    bool t_in[kPer], t_out[kPer];
+    bool t_in[kPer], t_out[kPer], t_hi[kPer];
+    {
+        int r = tid / HWc, cc = tid - r * HWc;
 #pragma unroll
-    for (int q = 0; q < kPer; q++) {
-        const int c = tid + q * NT, r = c / HWc, cc = c - r * HWc;
-        const int i = ib - kFH + r, j = j0 - kFH + cc;
-        t_in[q] = c < kFW * HWc && i >= vy0 && i < vy1 && j >= 0 && j < W;
-        t_o[q] = t_in[q] ? i * W + j : 0;
-        double x = 0.0, y = 0.0;  // (a cell outside the image: any valid position, its value is not used)
-        t_out[q] = false;
-        if (t_in[q]) {
-            y = i + v[t_o[q]];
-            x = j + u[t_o[q]];
-            t_out[q] = x < 0 || x > W - 1 || y < 0 || y > H - 1;  // warp_value()
-            if (t_out[q]) {
-                x = j;
-                y = i;
+        for (int q = 0; q < kPer; q++) {
+            if (q == 1) {  // + 256 pixels
+                cc += NT - 10 * HWc;
+                r += 10;
+                if (cc >= HWc) {
+                    cc -= HWc;
+                    r++;
+                }
+            } else if (q == 2) {  // pixel 512 + lane
+                cc = lane + (2 * NT - (2 * NT / HWc) * HWc);
+                r = 2 * NT / HWc;
+                if (cc >= HWc) {
+                    cc -= HWc;
+                    r++;
+                }
+                if (cc >= HWc) {
+                    cc -= HWc;
+                    r++;
+                }
             }
+            const int i = ib - kFH + r, j = j0 - kFH + cc;
+            t_ra[q] = r * (HWc + 1) + cc;
+            t_in[q] = i >= vy0 && i < vy1 && j >= 0 && j < W;
+            const int o = t_in[q] ? i * W + j : 0;
+            t_o[q] = (unsigned)o * 8u;
+            double x = 0.0, y = 0.0;  // (a cell outside the image: any valid position, its value is not used)
+            t_out[q] = false;
+            if (t_in[q]) {
+                y = i + v[o];
+                x = j + u[o];
+                t_out[q] = x < 0 || x > W - 1 || y < 0 || y > H - 1;  // warp_value()
+                if (t_out[q]) {
+                    x = j;
+                    y = i;
+                }
+            }
+            // the taps (y0, x0), (y0, x1 = min(x0 + 1, W - 1)) of a footprint row lie side by side: ONE 16-byte load at
+            // xb = min(x0, W - 2) holds both -- (lo, hi), or (hi, hi) where x0 is the last column (the same operands)
+            const int x0 = (int)x, y0 = (int)y, y1 = min(y0 + 1, H - 1);
+            const int xb = w1 ? 0 : min(x0, W - 2);
+            t_hi[q] = x0 == W - 1;
+            t_b0[q] = (unsigned)(y0 * W + xb) * 8u;
+            t_b1[q] = (unsigned)(y1 * W + xb) * 8u;
+            t_dx[q] = x - x0;
+            t_dy[q] = y - y0;
         }
-        t_x0[q] = (int)x;
-        t_y0[q] = (int)y;
-        t_dx[q] = x - t_x0[q];
-        t_dy[q] = y - t_y0[q];
     }
+    // a pixel that leaves the image takes frame 1's value: loaded (beside the gathers, which such a pixel does around itself in
+    // frame 2, unused) only in a wave that has such a pixel -- a scalar test
+    const bool wout = __ballot(t_out[0] || t_out[1] || t_out[2]) != 0ull;
     // ---- phi of the tile and its upper / left neighbours (k_phi without an increment), and the flow of the own cell
     for (int c = tid; c < (kFT + 1) * (kFT + 1); c += NT) {
         const int r = c / (kFT + 1), cc = c - r * (kFT + 1);
@@ -1192,31 +1242,57 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     const bool sampler = wit != nullptr && tid < 64 &&
                          (ntiles <= 256 || ((tbx + 5 * tby) & 15) == 0);
     // The global operands of a channel are PREFETCHED while the previous channel is worked on (a workgroup barrier does not
-    // wait for loads in flight): the gathers (or frame 1's value for a pixel that leaves the image) right behind P1, the smoothed
+    // wait for loads in flight): the gathers (and frame 1's value for a pixel that leaves the image) right behind P1, the smoothed
     // frame 1 of the blend's pixels right behind P3 -- the phases between are LDS only.
     constexpr int kP3 = ((kFT + 4) * (kFT + 4) + NT - 1) / NT;  // 2
-    double gv[kPer][4], s1v[kP3], wv = 0.0;
+    // the blend's pixels of a thread, (row, column) of the tile + 2, and their (clamped) place in the smoothed frame 1
+    int s_r[kP3], s_c[kP3];
+    unsigned s_o[kP3];
+    // P2: two neighbouring columns per thread (240 threads), P3: two neighbouring rows (200 threads) -- six LDS reads feed the
+    // two sums where ten did, and each phase is one pass; every sum keeps its own order
+    static_assert(kP3 == 2 && kFW * (kFT + 4) / 2 <= NT && (kFT + 4) * (kFT + 4) / 2 <= NT, "two outputs per thread");
+    const int h_r = tid / ((kFT + 4) / 2), h_c = 2 * (tid - h_r * ((kFT + 4) / 2));  // P2: row of raw, first of the two columns of hs
+    {
+        const int t = min(tid, (kFT + 4) * (kFT + 4) / 2 - 1), rp = t / (kFT + 4);
+        s_r[0] = 2 * rp;
+        s_r[1] = 2 * rp + 1;
+        s_c[0] = s_c[1] = t - rp * (kFT + 4);
+    }
+#pragma unroll
+    for (int q = 0; q < kP3; q++)  // (branch-free: a position outside the image reads its clamped pixel and is not used)
+        s_o[q] = (unsigned)(clampi(ib - 2 + s_r[q], H) * W + clampi(j0 - 2 + s_c[q], W)) * 8u;
+    double* const rawf = &raw[0][0];
+    tap_pair ga[kPer], gb[kPer];  // the taps of the footprint's upper and lower row
+    double f1v[kPer] = {0.0, 0.0, 0.0}, s1v[kP3], wv = 0.0;
     const auto load_gathers = [&](int k) {
         const double *p1 = im1 + k * np, *p2 = im2 + k * np;
+        const bool third = (k & 3) == wave;
 #pragma unroll
-        for (int q = 0; q < kPer; q++) {  // branch-free: a pixel that leaves the image gathers around ITSELF in frame 1 (its taps were
-            // set to its own position: tap 0 is frame 1's value), a cell outside the image reads pixel 0 and is not used
-            const double* src = t_out[q] ? p1 : p2;
-            const int x0 = t_x0[q], y0 = t_y0[q], x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-            gv[q][0] = src[y0 * W + x0];
-            gv[q][1] = src[y1 * W + x0];
-            gv[q][2] = src[y0 * W + x1];
-            gv[q][3] = src[y1 * W + x1];
+        for (int q = 0; q < kPer; q++) {  // branch-free per lane: a cell outside the image reads pixel 0 and is not used
+            if (q == 2 && !third) continue;
+            if (w1) {
+                ga[q].x = plane_ld(p2, t_b0[q]);  // (both taps of the row are this element)
+                gb[q].x = plane_ld(p2, t_b1[q]);
+            } else {
+                ga[q] = plane_ld2(p2, t_b0[q]);
+                gb[q] = plane_ld2(p2, t_b1[q]);
+            }
+            if (wout) f1v[q] = plane_ld(p1, t_o[q]);
         }
-        if (sampler) wv = p1[t_o[0]];
+        if (sampler) wv = plane_ld(p1, t_o[0]);
     };
     const auto load_s1 = [&](int k) {
         const double* ps = im1s + k * np;
 #pragma unroll
-        for (int q = 0; q < kP3; q++) {  // (branch-free: a position outside the image reads its clamped pixel and is not used)
-            const int c = min(tid + q * NT, (kFT + 4) * (kFT + 4) - 1), r = c / (kFT + 4), cc = c - r * (kFT + 4);
-            s1v[q] = ps[(size_t)clampi(ib - 2 + r, H) * W + clampi(j0 - 2 + cc, W)];
-        }
+        for (int q = 0; q < kP3; q++) s1v[q] = plane_ld(ps, s_o[q]);
+    };
+    const auto two_sums = [&](const double(&x)[6], double& a0, double& a1) {
+        a0 = 0.0;
+        a1 = 0.0;
+#pragma unroll
+        for (int l = 0; l < 5; l++) a0 += x[l] * g.t[l];
+#pragma unroll
+        for (int l = 0; l < 5; l++) a1 += x[l + 1] * g.t[l];
     };
     load_gathers(0);
     load_s1(0);
@@ -1224,17 +1300,20 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     for (int k = 0; k < PLANES; k++) {
         // -- P1: the warp
         bool hit = false;
+        const bool third = (k & 3) == wave;
 #pragma unroll
         for (int q = 0; q < kPer; q++) {
-            const int c = tid + q * NT, r = c / HWc, cc = c - r * HWc;
+            if (q == 2 && !third) continue;
             const double dx = t_dx[q], dy = t_dy[q], ex = 1.0 - dx, ey = 1.0 - dy;
+            const double g0 = !w1 && t_hi[q] ? ga[q].y : ga[q].x, g1 = !w1 && t_hi[q] ? gb[q].y : gb[q].x;
+            const double g2 = w1 ? ga[q].x : ga[q].y, g3 = w1 ? gb[q].x : gb[q].y;
             double res = 0.0;
-            res += gv[q][0] * (ex * ey);
-            res += gv[q][1] * (ex * dy);
-            res += gv[q][2] * (dx * ey);
-            res += gv[q][3] * (dx * dy);
-            res = t_out[q] ? gv[q][0] : res;  // warp_value(): a pixel that leaves the image takes frame 1's value
-            if (t_in[q]) raw[r][cc] = res;
+            res += g0 * (ex * ey);
+            res += g1 * (ex * dy);
+            res += g2 * (dx * ey);
+            res += g3 * (dx * dy);
+            res = t_out[q] ? f1v[q] : res;  // warp_value(): a pixel that leaves the image takes frame 1's value
+            if (t_in[q]) rawf[t_ra[q]] = res;
             if (sampler && q == 0) {
                 const double dd = fabs(wv - res);
                 hit = t_in[q] && dd >= wit_thr && dd < 1000000;
@@ -1247,46 +1326,54 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
         if (k + 1 < PLANES) load_gathers(k + 1);
         __syncthreads();
         // -- P2: horizontal pass on every row of the tile, columns j0 - 2 .. j0 + 17
-        if (interior) {  // (block-uniform: every pixel of the tile + 4 is inside the image -- no clamps, no tests)
-            for (int c = tid; c < kFW * (kFT + 4); c += NT) {
-                const int r = c / (kFT + 4), cc = c - r * (kFT + 4);
-                double acc = 0.0;
+        if (tid < kFW * (kFT + 4) / 2) {
+            const double* const row = raw[h_r];
+            double x[6], a0, a1;
+            if (interior) {  // (block-uniform: every pixel of the tile + 4 is inside the image -- no clamps, no tests)
 #pragma unroll
-                for (int l = -2; l <= 2; l++) acc += raw[r][cc + 2 + l] * g.t[l + 2];
-                hs[r][cc] = acc;
-            }
-        } else {
-            for (int c = tid; c < kFW * (kFT + 4); c += NT) {
-                const int r = c / (kFT + 4), cc = c - r * (kFT + 4);
-                const int i = ib - kFH + r, j = j0 - 2 + cc;
-                if (i < 0 || i >= H || j < 0 || j >= W) continue;
-                double acc = 0.0;
+                for (int m = 0; m < 6; m++) x[m] = row[h_c + m];
+                two_sums(x, a0, a1);
+                hs[h_r][h_c] = a0;
+                hs[h_r][h_c + 1] = a1;
+            } else {
+                const int i = ib - kFH + h_r, j = j0 - 2 + h_c;
+                const bool ok0 = j >= 0 && j < W, ok1 = j + 1 >= 0 && j + 1 < W;
+                if (i >= 0 && i < H && (ok0 || ok1)) {
 #pragma unroll
-                for (int l = -2; l <= 2; l++) acc += raw[r][clampi(j + l, W) - (j0 - kFH)] * g.t[l + 2];
-                hs[r][cc] = acc;
+                    for (int m = 0; m < 6; m++) x[m] = row[clampi(j - 2 + m, W) - (j0 - kFH)];
+                    two_sums(x, a0, a1);
+                    if (ok0) hs[h_r][h_c] = a0;
+                    if (ok1) hs[h_r][h_c + 1] = a1;
+                }
             }
         }
         __syncthreads();
         // -- P3: vertical pass, blend and imdt on (ib - 2 .. ib + 17) x (j0 - 2 .. j0 + 17)
+        if (tid < (kFT + 4) * (kFT + 4) / 2) {
+            const int r0 = s_r[0], cc = s_c[0], i = ib - 2 + r0, j = j0 - 2 + cc;
+            const bool okj = j >= 0 && j < W, ok0 = okj && i >= 0 && i < H, ok1 = okj && i + 1 >= 0 && i + 1 < H;
+            if (ok0 || ok1) {
+                double x[6], a[2];
+                if (interior) {
 #pragma unroll
-        for (int q = 0; q < kP3; q++) {
-            const int c = tid + q * NT, r = c / (kFT + 4), cc = c - r * (kFT + 4);
-            const int i = ib - 2 + r, j = j0 - 2 + cc;
-            if (c >= (kFT + 4) * (kFT + 4) || i < 0 || i >= H || j < 0 || j >= W) continue;
-            double s2 = 0.0;
-            if (interior) {
+                    for (int m = 0; m < 6; m++) x[m] = hs[r0 + m][cc];
+                } else {
 #pragma unroll
-                for (int l = -2; l <= 2; l++) s2 += hs[r + 2 + l][cc] * g.t[l + 2];
-            } else {
+                    for (int m = 0; m < 6; m++) x[m] = hs[clampi(i - 2 + m, H) - (ib - kFH)][cc];
+                }
+                two_sums(x, a[0], a[1]);
 #pragma unroll
-                for (int l = -2; l <= 2; l++) s2 += hs[clampi(i + l, H) - (ib - kFH)][cc] * g.t[l + 2];
+                for (int e = 0; e < 2; e++) {
+                    if (!(e ? ok1 : ok0)) continue;
+                    const int r = r0 + e;
+                    const double s2 = a[e], s1 = s1v[e];
+                    double t = s1;
+                    t *= 0.4;
+                    t += s2 * 0.6;
+                    bl[r][cc] = t;
+                    if (r >= 2 && r < kFT + 2 && cc >= 2 && cc < kFT + 2) it[r - 2][cc - 2] = s2 - s1;
+                }
             }
-            const double s1 = s1v[q];
-            double t = s1;
-            t *= 0.4;
-            t += s2 * 0.6;
-            bl[r][cc] = t;
-            if (r >= 2 && r < kFT + 2 && cc >= 2 && cc < kFT + 2) it[r - 2][cc - 2] = s2 - s1;
         }
         if (k + 1 < PLANES) load_s1(k + 1);
         __syncthreads();
@@ -2064,6 +2151,7 @@ int flow_system(papof_handle* h, const double* im1, const double* im2, const dou
                 int H, int W, int planes, double alpha, double omega, const SorPlanes& out, unsigned* wit, int row0, int row1,
                 int batch, const BatchK* bk) {
     if (planes != 5 && planes != 3) return PAPOF_EINVAL;
+    if ((unsigned long long)H * (unsigned long long)W > (1ull << 29)) return PAPOF_EINVAL;  // 32-bit byte offsets into a plane
     if (row1 < 0) row1 = H;
     if (row0 < 0 || row1 > H) return PAPOF_EINVAL;
     if (row1 <= row0) return PAPOF_OK;
@@ -2071,10 +2159,14 @@ int flow_system(papof_handle* h, const double* im1, const double* im2, const dou
     const dim3 grid(8 * ((ntiles + 7) / 8), batch);  // (the kernel maps block -> tile: a contiguous run of tiles per XCD)
     const SixPlanes six{{out.phi, out.xy, out.a1, out.a2, out.b1, out.b2}};
     const BatchK bk0{0, 0, 0, 0, 0, 0};
-    const auto kern = batch > 1 ? (out.skew ? (planes == 5 ? k_flow_system<5, true, true> : k_flow_system<3, true, true>)
-                                            : (planes == 5 ? k_flow_system<5, false, true> : k_flow_system<3, false, true>))
-                                : (out.skew ? (planes == 5 ? k_flow_system<5, true> : k_flow_system<3, true>)
-                                            : (planes == 5 ? k_flow_system<5, false> : k_flow_system<3, false>));
+    const auto pick = [&](auto one_column) {
+        constexpr bool W1 = decltype(one_column)::value;
+        return batch > 1 ? (out.skew ? (planes == 5 ? k_flow_system<5, true, true, W1> : k_flow_system<3, true, true, W1>)
+                                     : (planes == 5 ? k_flow_system<5, false, true, W1> : k_flow_system<3, false, true, W1>))
+                         : (out.skew ? (planes == 5 ? k_flow_system<5, true, false, W1> : k_flow_system<3, true, false, W1>)
+                                     : (planes == 5 ? k_flow_system<5, false, false, W1> : k_flow_system<3, false, false, W1>));
+    };
+    const auto kern = W == 1 ? pick(std::true_type{}) : pick(std::false_type{});
     hipLaunchKernelGGL(kern, grid, dim3(kFT * kFT), 0, h->stream, im1, im2, u, v, im1s, H, W, alpha, omega,
                        out.skew ? skew_idx(out) : SkewIdx{0, 0, 0, 0, 0, 0, 0, 0, 0}, six, smooth5_taps(), deriv5_taps(),
                        take_stamp(h), wit, 2e-20 * (double)H * (double)W, h->lap_epoch, row0, row1, bk ? *bk : bk0);
