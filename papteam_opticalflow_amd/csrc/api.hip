@@ -295,11 +295,10 @@ struct LapGuard {
         int n = 0;
         for (int s = 0; s + 1 < slot; s++)  // the estimate behind the last iteration of a call is never consulted
             for (int c = 0; c < slot_channels[s]; c++) {
-                const unsigned w = host_flags[lap_wit_word(s) + c];
-                const bool witness = w == epoch || w == (epoch ^ kLapNone);  // a sample, or an exhaustive "no valid sample at all"
-                const bool all_zero = nz_known && host_flags[lap_nz_word(slot_level[s]) + c] != epoch;
-                n += !(witness || all_zero);
-                if (!(witness || all_zero) && std::getenv("PAPOF_LAP_TRACE"))
+                const unsigned nz = host_flags[lap_nz_word(slot_level[s]) + c];  // (both frames of the level set this word)
+                const bool proven = lap_proven(host_flags[lap_wit_word(s) + c], epoch, nz_known, nz, nz);
+                n += !proven;
+                if (!proven && std::getenv("PAPOF_LAP_TRACE"))
                     std::fprintf(stderr, "[lap guard] no proof: slot %d of %d, level %d, channel %d\n", s, slot, slot_level[s], c);
             }
         return n;

@@ -319,12 +319,10 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             const int f1 = (back ? p - B : p) * fstep, fa = back ? f1 + 1 : f1, fb = back ? f1 : f1 + 1;
             for (int s = 0; s + 1 < slot && open; s++)  // the estimate behind the call's last update is never consulted
                 for (int c = 0; c < fc; c++) {
-                    const unsigned w = hw[(size_t)p * kLapFlagWords + lap_wit_word(s) + c];
-                    const bool witness = w == epoch || w == (epoch ^ kLapNone);  // a sample, or an exhaustive "no valid sample at all"
                     const size_t nzw = (size_t)slot_level[s] * 8 + c;
-                    const bool all_zero = nz_known && hn[(size_t)fa * kLapNzWords + nzw] != epoch &&
-                                          hn[(size_t)fb * kLapNzWords + nzw] != epoch;
-                    if (!(witness || all_zero)) open = false;
+                    if (!lap_proven(hw[(size_t)p * kLapFlagWords + lap_wit_word(s) + c], epoch, nz_known,
+                                    hn[(size_t)fa * kLapNzWords + nzw], hn[(size_t)fb * kLapNzWords + nzw]))
+                        open = false;
                 }
             if (!open) out.unproven.push_back(p);
         }

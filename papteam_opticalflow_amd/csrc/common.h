@@ -393,8 +393,6 @@ int gm_scratch_doubles();
 int est_gaussian_mixture(papof_handle* h, const double* im1, const double* im2, int H, int W, int C, double* gm,
                          double* scratch);
 int laplacian(papof_handle* h, const double* in, const double* weight, double* out, int H, int W);
-int update_and_warp(papof_handle* h, const SorPlanes& sp, double* u, double* v, const double* im1,
-                    const double* im2, double* warp, int H, int W, int planes, bool do_warp = true);
 int bicubic_warp(papof_handle* h, const double* im1, const double* im2, const double* gx, const double* gy,
                  const double* gxy, const double* vx, const double* vy, double* out_hwc, int H, int W, int C,
                  const Rect* rc = nullptr, bool planar_out = false, bool clamp = true, int batch = 1, const BatchK* bk = nullptr);

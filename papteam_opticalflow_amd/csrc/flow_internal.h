@@ -107,6 +107,16 @@ struct PhaseClock {
     }
 };
 
+// The Laplacian-noise guard's verdict on ONE consulted estimate (api.hip: LapGuard; a flag is set when it holds the number
+// of the pass, `epoch`): it is proven by a witness -- a sample, or kLapNone: an exhaustive "no valid sample at all" -- or by a
+// channel that is all zero in both frames of the level (nz_known: im2feature collected the non-zero flags; nz_a, nz_b: the
+// channel's flag words of the two frames, one and the same word where the frames share their flags)
+inline bool lap_proven(unsigned wit, unsigned epoch, bool nz_known, unsigned nz_a, unsigned nz_b) {
+    const bool witness = wit == epoch || wit == (epoch ^ kLapNone);
+    const bool all_zero = nz_known && nz_a != epoch && nz_b != epoch;
+    return witness || all_zero;
+}
+
 struct Level {
     int w, h;
     double *p1, *p2;  // planar pyramid levels of frame 1 / frame 2

@@ -18,7 +18,8 @@ namespace {
 
 constexpr int BX = 64, BY = 4;
 
-inline dim3 grid2d(int W, int H, int planes = 1) { return dim3((W + BX - 1) / BX, (H + BY - 1) / BY, planes); }
+constexpr int tiles_of(int n, int t) { return (n + t - 1) / t; }  // tiles of t cells that cover n cells
+inline dim3 grid2d(int W, int H, int planes = 1) { return dim3(tiles_of(W, BX), tiles_of(H, BY), planes); }
 inline Rect region(const Rect* rc, int W, int H) { return rc ? *rc : Rect{0, 0, W, H}; }
 inline dim3 grid2d(const Rect& r, int planes = 1) { return grid2d(r.x1 - r.x0, r.y1 - r.y0, planes); }
 
@@ -47,6 +48,95 @@ __device__ __forceinline__ bool xcd_tile(int ntx, int nty, int& tx, int& ty) {
     return true;
 }
 static inline unsigned xcd_grid(int ntx, int nty) { return 8u * (unsigned)(((size_t)ntx * nty + 7) / 8); }
+
+// ------------------------------------------------------------------------------------------------
+// The expressions of the kernels between two solves, each stated ONCE.  The fused kernels and the forms they
+// grew out of all evaluate these, so bit parity with the reference holds by construction, not by identical edits.
+// ------------------------------------------------------------------------------------------------
+// correlation with 2 * half + 1 taps: accumulated from 0 in the order l = -half .. half (src/ImageProcessing.h:259-279);
+// at(l) is the operand at offset l -- the caller's clamp, LDS row or register lives there.  HALF: the half-width as a
+// compile-time constant (the 5-tap passes: tap_sum<2>), or -1: half_rt at run time
+template <int HALF = -1, class At>
+__device__ __forceinline__ double tap_sum(const Taps& f, At at, int half_rt = HALF) {
+    const int half = HALF >= 0 ? HALF : half_rt;
+    double acc = 0.0;
+#pragma unroll
+    for (int l = -half; l <= half; l++) acc += at(l) * f.t[l + half];
+    return acc;
+}
+
+// Im = Im1s * 0.4 + Im2s * 0.6 (Multiplywith, Add(..., 0.6): src/OpticalFlow.cpp:92-93) and imdt = Im2s - Im1s (:97)
+__device__ __forceinline__ void blend_imdt(double s1, double s2, double& blend, double& imdt) {
+    double t = s1;
+    t *= 0.4;
+    t += s2 * 0.6;
+    blend = t;
+    imdt = s2 - s1;
+}
+
+// phi, src/OpticalFlow.cpp:295-331, from the flow at the cell, its right and its lower neighbour: forward differences, zero
+// in the last column (!right) / row (!down) (src/Image.h:979-986, :1022-1029), phi = 0.5 / sqrt(ux^2 + uy^2 + vx^2 + vy^2 + eps)
+__device__ __forceinline__ double phi_value(double uc, double vc, double ur, double vr, double ud, double vd, bool right,
+                                            bool down) {
+    const double ux = right ? ur - uc : 0.0;
+    const double uy = down ? ud - uc : 0.0;
+    const double vx = right ? vr - vc : 0.0;
+    const double vy = down ? vd - vc : 0.0;
+    const double t = ux * ux + uy * uy + vx * vx + vy * vy;
+    return 0.5 / sqrt(t + 0.001 * 0.001);
+}
+// ... of the flow as it stands in memory (no increment): only neighbours that exist are loaded
+__device__ __forceinline__ double phi_at(const double* __restrict__ u, const double* __restrict__ v, int i, int j, int H,
+                                         int W) {
+    const size_t o = (size_t)i * W + j;
+    const double uc = u[o], vc = v[o];
+    double ur = 0.0, vr = 0.0, ud = 0.0, vd = 0.0;
+    if (j < W - 1) {
+        ur = u[o + 1];
+        vr = v[o + 1];
+    }
+    if (i < H - 1) {
+        ud = u[o + W];
+        vd = v[o + W];
+    }
+    return phi_value(uc, vc, ur, vr, ud, vd, j < W - 1, i < H - 1);
+}
+
+// ImageProcessing::warpImage, src/ImageProcessing.h:483-503: a pixel whose position leaves the image takes frame 1's value
+__device__ __forceinline__ bool leaves_image(double x, double y, int W, int H) {
+    return x < 0 || x > W - 1 || y < 0 || y > H - 1;
+}
+// BilinearInterpolate (:138-157) at a position INSIDE the image: 0 <= (int)x <= W - 1 needs no clamp from below, dx = x - (int)x
+// is in [0, 1) as it is, |1 - dx| = 1 - dx and |0 - dx| = dx -- the values of bilinear_taps() below with a third of the
+// instructions.  Taps in bilinear_apply()'s visiting order: g0 = (x0, y0), g1 = (x0, y1), g2 = (x1, y0), g3 = (x1, y1).
+__device__ __forceinline__ double bilinear_inside(double g0, double g1, double g2, double g3, double dx, double dy) {
+    const double ex = 1.0 - dx, ey = 1.0 - dy;
+    double res = 0.0;
+    res += g0 * (ex * ey);
+    res += g1 * (ex * dy);
+    res += g2 * (dx * ey);
+    res += g3 * (dx * dy);
+    return res;
+}
+// ... with the four taps gathered from a plane
+__device__ __forceinline__ double bilinear_inside_at(const double* __restrict__ p, int W, int H, double x, double y) {
+    const int x0 = (int)x, y0 = (int)y;
+    const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+    return bilinear_inside(p[y0 * W + x0], p[y1 * W + x0], p[y0 * W + x1], p[y1 * W + x1], x - x0, y - y0);
+}
+
+// Samples of the Laplacian-noise guard (api.hip: LapGuard): estLaplacianNoise (src/OpticalFlow.cpp:594-639) averages
+// d = |Im1 - warpIm2| over its VALID samples, those in (0, 1e6); one sample of at least thr = lap_wit_threshold() is a WITNESS
+// that this mean is not below 1e-20.  `sampled`: a condition of the caller's in front of the comparison (k_flow_system).
+__device__ __forceinline__ bool lap_valid(double d) { return d > 0 && d < 1000000; }
+__device__ __forceinline__ bool lap_witness(double d, double thr, bool sampled = true) {
+    return sampled && d >= thr && d < 1000000;
+}
+// thousands of stores to one word are not free: on a grid of more than 256 blocks one block in sixteen samples
+__device__ __forceinline__ bool lap_one_in_sixteen(int tbx, int tby) { return ((tbx + 5 * tby) & 15) == 0; }
+__device__ __forceinline__ bool lap_samples_here(int nblocks, int tbx, int tby) {
+    return nblocks <= 256 || lap_one_in_sixteen(tbx, tby);
+}
 
 // ------------------------------------------------------------------------------------------------
 // layout conversion (entry / exit of the call): HWC interleaved <-> planar
@@ -182,9 +272,7 @@ __global__ void k_filter_h(const double* __restrict__ src, double* __restrict__ 
     if (j >= rc.x1 || i >= rc.y1) return;
     const size_t np = (size_t)H * W;
     const double* row = src + blockIdx.z * np + (size_t)i * W;
-    double acc = 0.0;
-    for (int l = -f.fsize; l <= f.fsize; l++) acc += row[clampi(j + l, W)] * f.t[l + f.fsize];
-    dst[blockIdx.z * np + (size_t)i * W + j] = acc;
+    dst[blockIdx.z * np + (size_t)i * W + j] = tap_sum(f, [&](int l) { return row[clampi(j + l, W)]; }, f.fsize);
 }
 
 __global__ void k_filter_v(const double* __restrict__ src, double* __restrict__ dst, int H, int W, Taps f, Rect rc) {
@@ -192,9 +280,7 @@ __global__ void k_filter_v(const double* __restrict__ src, double* __restrict__ 
     if (j >= rc.x1 || i >= rc.y1) return;
     const size_t np = (size_t)H * W;
     const double* p = src + blockIdx.z * np + j;
-    double acc = 0.0;
-    for (int l = -f.fsize; l <= f.fsize; l++) acc += p[(size_t)clampi(i + l, H) * W] * f.t[l + f.fsize];
-    dst[blockIdx.z * np + (size_t)i * W + j] = acc;
+    dst[blockIdx.z * np + (size_t)i * W + j] = tap_sum(f, [&](int l) { return p[(size_t)clampi(i + l, H) * W]; }, f.fsize);
 }
 
 // Both passes of a separable filter in ONE kernel (h pass into LDS, v pass out of it): the operations and their order
@@ -216,10 +302,7 @@ __global__ __launch_bounds__(256) void k_filter_hv(const double* __restrict__ sr
     if (j < W) {
         for (int r = threadIdx.y; r < kHvRows + 2 * f; r += BY) {
             const double* row = plane + (size_t)clampi(i0 + r - f, H) * W;
-            double acc = 0.0;
-#pragma unroll
-            for (int l = -fx; l <= fx; l++) acc += row[clampi(j + l, W)] * fh.t[l + fx];
-            hs[r][threadIdx.x] = acc;
+            hs[r][threadIdx.x] = tap_sum<F>(fh, [&](int l) { return row[clampi(j + l, W)]; }, fx);
         }
     }
     __syncthreads();
@@ -227,10 +310,7 @@ __global__ __launch_bounds__(256) void k_filter_hv(const double* __restrict__ sr
     for (int r = threadIdx.y; r < kHvRows; r += BY) {
         const int i = i0 + r;
         if (i >= H) break;
-        double acc = 0.0;
-#pragma unroll
-        for (int l = -f; l <= f; l++) acc += hs[r + l + f][threadIdx.x] * fv.t[l + f];
-        dst[blockIdx.z * np + (size_t)i * W + j] = acc;
+        dst[blockIdx.z * np + (size_t)i * W + j] = tap_sum<F>(fv, [&](int l) { return hs[r + l + f][threadIdx.x]; }, f);
     }
 }
 
@@ -261,10 +341,7 @@ __global__ __launch_bounds__(256) void k_filter_hv_staged(const double* __restri
     }
     __syncthreads();
     for (int r = threadIdx.y; r < kHvsRows + 2 * F; r += BY) {
-        double acc = 0.0;
-#pragma unroll
-        for (int l = -F; l <= F; l++) acc += raw[r][threadIdx.x + F + l] * fh.t[l + F];
-        hs[r][threadIdx.x] = acc;
+        hs[r][threadIdx.x] = tap_sum<F>(fh, [&](int l) { return raw[r][threadIdx.x + F + l]; });
     }
     __syncthreads();
     const int j = j0 + threadIdx.x;
@@ -272,10 +349,7 @@ __global__ __launch_bounds__(256) void k_filter_hv_staged(const double* __restri
     for (int r = threadIdx.y; r < kHvsRows; r += BY) {
         const int i = i0 + r;
         if (i >= H) break;
-        double acc = 0.0;
-#pragma unroll
-        for (int l = -F; l <= F; l++) acc += hs[r + l + F][threadIdx.x] * fv.t[l + F];
-        dst[blockIdx.z * np + (size_t)i * W + j] = acc;
+        dst[blockIdx.z * np + (size_t)i * W + j] = tap_sum<F>(fv, [&](int l) { return hs[r + l + F][threadIdx.x]; });
     }
 }
 
@@ -468,12 +542,11 @@ __device__ __forceinline__ void warp_pixel(const double* __restrict__ im1, const
     const size_t np = (size_t)H * W, o = (size_t)i * W + j;
     const double y = i + fy;
     const double x = j + fx;
-    if (x < 0 || x > W - 1 || y < 0 || y > H - 1) {
+    if (leaves_image(x, y, W, H)) {
         for (int k = 0; k < planes; k++) out[k * np + o] = im1[k * np + o];
         return;
     }
-    const BilinearTaps b = bilinear_taps(W, H, x, y);
-    for (int k = 0; k < planes; k++) out[k * np + o] = bilinear_apply(im2 + k * np, b);
+    for (int k = 0; k < planes; k++) out[k * np + o] = bilinear_inside_at(im2 + k * np, W, H, x, y);
 }
 
 __global__ void k_warp(const double* __restrict__ im1, const double* __restrict__ im2, const double* __restrict__ vx,
@@ -497,15 +570,8 @@ __global__ void k_smooth_v_blend(const double* __restrict__ tmp, const double* _
     if (j >= rc.x1 || i >= rc.y1) return;
     const size_t np = (size_t)H * W, o = blockIdx.z * np + (size_t)i * W + j;
     const double* p = tmp + blockIdx.z * np + j;
-    double s2 = 0.0;
-#pragma unroll
-    for (int l = -2; l <= 2; l++) s2 += p[(size_t)clampi(i + l, H) * W] * g.t[l + 2];
-    const double s1 = im1s[o];
-    double t = s1;
-    t *= 0.4;
-    t += s2 * 0.6;
-    blend[o] = t;
-    imdt[o] = s2 - s1;
+    const double s2 = tap_sum<2>(g, [&](int l) { return p[(size_t)clampi(i + l, H) * W]; });
+    blend_imdt(im1s[o], s2, blend[o], imdt[o]);
 }
 
 // Both passes of the 5-tap smoothing of the warped frame + blend + imdt in ONE kernel (one-GPU path): a block owns
@@ -526,10 +592,7 @@ __global__ __launch_bounds__(256) void k_smooth_hv_blend(const double* __restric
     if (j < W) {
         for (int r = threadIdx.y; r < kFuseRows + 4; r += BY) {
             const double* row = src + (size_t)clampi(i0 + r - 2, H) * W;
-            double acc = 0.0;
-#pragma unroll
-            for (int l = -2; l <= 2; l++) acc += row[clampi(j + l, W)] * g.t[l + 2];
-            hs[r][threadIdx.x] = acc;
+            hs[r][threadIdx.x] = tap_sum<2>(g, [&](int l) { return row[clampi(j + l, W)]; });
         }
     }
     __syncthreads();
@@ -538,15 +601,8 @@ __global__ __launch_bounds__(256) void k_smooth_hv_blend(const double* __restric
         const int i = i0 + r;
         if (i >= row1) break;
         const size_t o = blockIdx.z * np + (size_t)i * W + j;
-        double s2 = 0.0;
-#pragma unroll
-        for (int l = -2; l <= 2; l++) s2 += hs[r + l + 2][threadIdx.x] * g.t[l + 2];
-        const double s1 = im1s[o];
-        double t = s1;
-        t *= 0.4;
-        t += s2 * 0.6;
-        blend[o] = t;
-        imdt[o] = s2 - s1;
+        const double s2 = tap_sum<2>(g, [&](int l) { return hs[r + l + 2][threadIdx.x]; });
+        blend_imdt(im1s[o], s2, blend[o], imdt[o]);
     }
 }
 
@@ -559,8 +615,8 @@ __device__ __forceinline__ double warp_value(const double* __restrict__ im1, con
                                              double fy, int i, int j, int H, int W) {  // one plane of warp_pixel()
     const double y = i + fy;
     const double x = j + fx;
-    if (x < 0 || x > W - 1 || y < 0 || y > H - 1) return im1[(size_t)i * W + j];
-    return bilinear_apply(im2, bilinear_taps(W, H, x, y));
+    if (leaves_image(x, y, W, H)) return im1[(size_t)i * W + j];
+    return bilinear_inside_at(im2, W, H, x, y);
 }
 #ifndef PAPOF_V_WSROWS
 #define PAPOF_V_WSROWS 16
@@ -597,15 +653,15 @@ __global__ __launch_bounds__(256) void k_warp_smooth_blend(const double* __restr
     const bool exhaustive = wit != nullptr && gridDim.x == 1u && gridDim.y == 1u;
     bool ex_hit = false, ex_valid = false;
     const bool sampler = wit != nullptr && !exhaustive && threadIdx.y == 0u &&
-                         (gridDim.x * gridDim.y <= 256u || ((blockIdx.x + 5u * blockIdx.y) & 15u) == 0u);
+                         lap_samples_here((int)(gridDim.x * gridDim.y), (int)blockIdx.x, (int)blockIdx.y);
     constexpr int kWitStride = (kWsRows + 4) * (BX + 4) / 64;
     const int wr = (int)(threadIdx.x * kWitStride) / (BX + 4), wc = (int)(threadIdx.x * kWitStride) - wr * (BX + 4);
     double own1 = 0.0;
     if (sampler) own1 = p1[(size_t)clampi(i0 + wr - 2, H) * W + clampi(j0 + wc - 2, W)];
     // The tile's cells (halo of 2 included) are warped in BATCHES of kWsBatch cells per thread: first the flow of every cell of
     // the batch, then all their taps and the 4 x kWsBatch gathers, then the blends -- two dependent memory round trips per
-    // batch instead of two per cell (the kernel was bound by those: 130 us at level 0 against ~45 us of HBM traffic).  Same
-    // expressions as warp_value(): same bits.
+    // batch instead of two per cell (the kernel was bound by those: 130 us at level 0 against ~45 us of HBM traffic).  The
+    // expressions are warp_value()'s own: leaves_image() and bilinear_inside().
     constexpr int kCells = (kWsRows + 4) * (BX + 4), kPer = (kCells + BX * BY - 1) / (BX * BY);
     const int tid = threadIdx.y * BX + threadIdx.x;
 #pragma unroll
@@ -628,13 +684,12 @@ __global__ __launch_bounds__(256) void k_warp_smooth_blend(const double* __restr
             const int r = c / (BX + 4), cc = c - r * (BX + 4);
             const int i = clampi(i0 + r - 2, H), j = clampi(j0 + cc - 2, W);
             double y = i + fy[q], x = j + fx[q];
-            outside[q] = x < 0 || x > W - 1 || y < 0 || y > H - 1;  // warp_value(): such a pixel takes frame 1's value
+            outside[q] = leaves_image(x, y, W, H);  // such a pixel takes frame 1's value
             if (outside[q]) {  // (any valid position: its gathers are issued and not used)
                 x = j;
                 y = i;
             }
-            // bilinear_taps() for a position INSIDE the image: 0 <= (int)x <= W-1 needs no clamp from below, dx = x - (int)x is in
-            // [0, 1) as it is, |1 - dx| = 1 - dx and |0 - dx| = dx -- the same values with a third of the instructions
+            // the gathers of bilinear_inside_at(), issued for the whole batch before the first blend
             const int x0 = (int)x, y0 = (int)y;
             const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
             val[q][0] = p2[y0 * W + x0];  // visiting order of bilinear_apply(): (m, n) = (0,0) (0,1) (1,0) (1,1), tap = (x_m, y_n)
@@ -649,22 +704,13 @@ __global__ __launch_bounds__(256) void k_warp_smooth_blend(const double* __restr
             const int c = tid + (q0 + q) * BX * BY;
             if (c >= kCells) continue;
             const int r = c / (BX + 4), cc = c - r * (BX + 4);
-            double res;
-            if (outside[q]) {
-                res = p1[off[q]];
-            } else {
-                const double dx = fx[q], dy = fy[q], ex = 1.0 - dx, ey = 1.0 - dy;
-                res = 0.0;
-                res += val[q][0] * (ex * ey);
-                res += val[q][1] * (ex * dy);
-                res += val[q][2] * (dx * ey);
-                res += val[q][3] * (dx * dy);
-            }
+            const double res =
+                outside[q] ? p1[off[q]] : bilinear_inside(val[q][0], val[q][1], val[q][2], val[q][3], fx[q], fy[q]);
             raw[r][cc] = res;
             if (exhaustive) {
                 const double d = fabs(p1[off[q]] - res);
-                ex_valid = ex_valid || (d > 0 && d < 1000000);
-                ex_hit = ex_hit || (d >= wit_thr && d < 1000000);
+                ex_valid = ex_valid || lap_valid(d);
+                ex_hit = ex_hit || lap_witness(d, wit_thr);
             }
         }
     }
@@ -675,14 +721,11 @@ __global__ __launch_bounds__(256) void k_warp_smooth_blend(const double* __restr
     }
     if (sampler) {
         const double d = fabs(own1 - raw[wr][wc]);
-        const unsigned long long hits = __ballot(d >= wit_thr && d < 1000000);
+        const unsigned long long hits = __ballot(lap_witness(d, wit_thr));
         if (hits != 0ull && threadIdx.x == 0u) wit[blockIdx.z] = mark;
     }
     for (int r = threadIdx.y; r < kWsRows + 4; r += BY) {
-        double acc = 0.0;
-#pragma unroll
-        for (int l = -2; l <= 2; l++) acc += raw[r][threadIdx.x + 2 + l] * g.t[l + 2];
-        hs[r][threadIdx.x] = acc;
+        hs[r][threadIdx.x] = tap_sum<2>(g, [&](int l) { return raw[r][threadIdx.x + 2 + l]; });
     }
     __syncthreads();
     const int j = j0 + threadIdx.x;
@@ -691,36 +734,11 @@ __global__ __launch_bounds__(256) void k_warp_smooth_blend(const double* __restr
         const int i = i0 + r;
         if (i >= H) break;
         const size_t o = blockIdx.z * np + (size_t)i * W + j;
-        double s2 = 0.0;
-#pragma unroll
-        for (int l = -2; l <= 2; l++) s2 += hs[r + l + 2][threadIdx.x] * g.t[l + 2];
-        const double s1 = im1s[o];
-        double t = s1;
-        t *= 0.4;
-        t += s2 * 0.6;
-        blend[o] = t;
-        imdt[o] = s2 - s1;
-        // phi of the flow this outer iteration starts from: k_phi's expressions without an increment, by the blocks of channel
-        // 0 -- no launch of its own, and the update kernel is spared the scattered reads of its neighbours' increments
-        if (phi_out != nullptr && blockIdx.z == 0) {
-            const size_t q = (size_t)i * W + j;
-            const double uc = u[q], vc = v[q];
-            double ur = 0.0, vr = 0.0, ud = 0.0, vd = 0.0;
-            if (j < W - 1) {
-                ur = u[q + 1];
-                vr = v[q + 1];
-            }
-            if (i < H - 1) {
-                ud = u[q + W];
-                vd = v[q + W];
-            }
-            const double ux = j < W - 1 ? ur - uc : 0.0;
-            const double uy = i < H - 1 ? ud - uc : 0.0;
-            const double vx = j < W - 1 ? vr - vc : 0.0;
-            const double vy = i < H - 1 ? vd - vc : 0.0;
-            const double tt = ux * ux + uy * uy + vx * vx + vy * vy;
-            phi_out[q] = 0.5 / sqrt(tt + 0.001 * 0.001);
-        }
+        const double s2 = tap_sum<2>(g, [&](int l) { return hs[r + l + 2][threadIdx.x]; });
+        blend_imdt(im1s[o], s2, blend[o], imdt[o]);
+        // phi of the flow this outer iteration starts from (no increment), by the blocks of channel 0 -- no launch of its own,
+        // and the update kernel is spared the scattered reads of its neighbours' increments
+        if (phi_out != nullptr && blockIdx.z == 0) phi_out[(size_t)i * W + j] = phi_at(u, v, i, j, H, W);
     }
 }
 
@@ -740,6 +758,45 @@ __device__ __forceinline__ size_t sor_index(int i, int j, int W, const SkewIdx& 
     if (SKEW) return 2 * skew_cell(i, j, k);
     return (size_t)i * W + j;
 }
+// A tile of assembled cells on its way to the exact-order solver's planes: cells are COMPUTED in row-major order (coalesced
+// plane reads), staged in LDS, and WRITTEN in skew order -- for one skew position (anti-diagonal) the COLS threads of a group
+// store COLS neighbouring rows, contiguous in each paired plane (pa = (phi, xy), pb = (a1, a2), pc = (b1, b2)) -- instead of
+// scattered 16-byte cells.  256 threads; the tile starts at (ib, j0), rows below row1 and columns below W exist.
+struct SystemCell {  // the operands of one cell of the linear system (and imdx2, imdy2 for the stage entry points)
+    double phi, xy, a1, a2, b1, b2, x2, y2;
+};
+struct double2s {
+    double x, y;
+};
+template <int ROWS, int PITCH>  // (PITCH = the tile's columns + 1)
+__device__ __forceinline__ void stage_cell(double (&stage)[6][ROWS][PITCH], int r, int jj, const SystemCell& s) {
+    stage[0][r][jj] = s.phi;
+    stage[1][r][jj] = s.xy;
+    stage[2][r][jj] = s.a1;
+    stage[3][r][jj] = s.a2;
+    stage[4][r][jj] = s.b1;
+    stage[5][r][jj] = s.b2;
+}
+template <int ROWS, int PITCH>
+__device__ __forceinline__ void store_skew_tile(const double (&stage)[6][ROWS][PITCH], int tid, int ib, int j0, int row1,
+                                                int W, const SkewIdx& sk, double2s* __restrict__ pa,
+                                                double2s* __restrict__ pb, double2s* __restrict__ pc) {
+    constexpr int COLS = PITCH - 1;
+    const int g = tid / COLS, jj = tid - g * COLS;  // 256 / COLS groups of COLS threads; a group walks anti-diagonals
+    const int j = j0 + jj;
+    if (j >= W) return;
+    for (int pp = g; pp <= ROWS + COLS - 2; pp += 256 / COLS) {  // pp = jj + (row in tile)
+        const int r = pp - jj;
+        if (r < 0 || r >= ROWS) continue;
+        const int i = ib + r;
+        if (i >= row1) continue;
+        const size_t q = skew_cell(i, j, sk);
+        pa[q] = double2s{stage[0][r][jj], stage[1][r][jj]};
+        pb[q] = double2s{stage[2][r][jj], stage[3][r][jj]};
+        pc[q] = double2s{stage[4][r][jj], stage[5][r][jj]};
+    }
+}
+
 // cell of (du, dv)(i, j) after the last sweep in the banded ping-pong planes (common.h)
 __device__ __forceinline__ size_t dudv_cell(int i, int j, const SkewIdx& k) {
     const int t = i + k.koff, b = t / k.band_rows, c = 1 + (t - b * k.band_rows);
@@ -810,28 +867,45 @@ __global__ void k_phi(const double* __restrict__ u, const double* __restrict__ v
             vd = vd + b;
         }
     }
-    const double ux = j < W - 1 ? ur - uc : 0.0;
-    const double uy = i < H - 1 ? ud - uc : 0.0;
-    const double vx = j < W - 1 ? vr - vc : 0.0;
-    const double vy = i < H - 1 ? vd - vc : 0.0;
-    const double t = ux * ux + uy * uy + vx * vx + vy * vy;
-    phi[o] = 0.5 / sqrt(t + 0.001 * 0.001);
+    phi[o] = phi_value(uc, vc, ur, vr, ud, vd, j < W - 1, i < H - 1);
+}
+
+// A cell's neighbourhood for the Laplacian and the diagonals: which neighbours exist, the plane's values at the cell and
+// around it, and phi at the cell, to its left and above (the weights of the four differences).  EDGE = false: the cell is
+// not on an image border, every neighbour exists -- no test, constant address offsets.  On a border the loads are branch-free:
+// a neighbour that does not exist reads the cell itself and is not used.
+struct Nbrs {
+    bool left, right, up, down;
+};
+__device__ __forceinline__ Nbrs nbrs_at(int i, int j, int H, int W) { return Nbrs{j > 0, j < W - 1, i > 0, i < H - 1}; }
+struct Cross {
+    double c, l, r, u, d;
+};
+template <bool EDGE>
+__device__ __forceinline__ Cross cross_at(const double* __restrict__ in, size_t o, int W, const Nbrs& n) {
+    return Cross{in[o], in[!EDGE || n.left ? o - 1 : o], in[!EDGE || n.right ? o + 1 : o], in[!EDGE || n.up ? o - W : o],
+                 in[!EDGE || n.down ? o + W : o]};
+}
+struct PhiAround {
+    double c, l, u;
+};
+template <bool EDGE>
+__device__ __forceinline__ PhiAround phi_around(const double* __restrict__ phi, size_t o, int W, const Nbrs& n) {
+    return PhiAround{phi[o], phi[!EDGE || n.left ? o - 1 : o], phi[!EDGE || n.up ? o - W : o]};
 }
 
 // OpticalFlow::Laplacian at one cell, src/OpticalFlow.cpp:641-690: column W-1 receives no horizontal
 // term and row H-1 no vertical term (the loops stop at W-2 / H-2).
-__device__ __forceinline__ double laplacian_at(const double* __restrict__ in, const double* __restrict__ wt, int i,
-                                               int j, int H, int W) {
-    const size_t o = (size_t)i * W + j;
-    const double c = in[o];
+template <bool EDGE>
+__device__ __forceinline__ double laplacian_value(const Cross& x, const PhiAround& p, const Nbrs& n) {
     double out = 0.0;
-    if (j < W - 1) {
-        out -= (in[o + 1] - c) * wt[o];
-        if (j > 0) out += (c - in[o - 1]) * wt[o - 1];
+    if (!EDGE || n.right) {
+        out -= (x.r - x.c) * p.c;
+        if (!EDGE || n.left) out += (x.c - x.l) * p.l;
     }
-    if (i < H - 1) {
-        out -= (in[o + W] - c) * wt[o];
-        if (i > 0) out += (c - in[o - W]) * wt[o - W];
+    if (!EDGE || n.down) {
+        out -= (x.d - x.c) * p.c;
+        if (!EDGE || n.up) out += (x.c - x.u) * p.u;
     }
     return out;
 }
@@ -840,22 +914,23 @@ __global__ void k_laplacian(const double* __restrict__ in, const double* __restr
                             int H, int W) {
     const int j = blockIdx.x * BX + threadIdx.x, i = blockIdx.y * BY + threadIdx.y;
     if (j >= W || i >= H) return;
-    out[(size_t)i * W + j] = laplacian_at(in, wt, i, j, H, W);
+    const size_t o = (size_t)i * W + j;
+    const Nbrs n = nbrs_at(i, j, H, W);
+    out[o] = laplacian_value<true>(cross_at<true>(in, o, W, n), phi_around<true>(wt, o, W, n), n);
 }
 
 // diagonal terms of the SOR update, src/OpticalFlow.cpp:468-501: coeff accumulated left, right, up, down,
 // scaled by alpha; a = omega / (imd?2 + alpha*0.05 + coeff).  They do not change during the sweeps, so
 // the two divisions per cell-update of the reference are hoisted out of the sweep loop (same bits:
 // the reference evaluates (omega/denominator) * (rhs - sigma) left to right).
-__device__ __forceinline__ void sor_diagonals(const double* __restrict__ phi, int i, int j, int H, int W,
-                                              double imdx2, double imdy2, double alpha, double omega, double& a1,
-                                              double& a2) {
-    const size_t o = (size_t)i * W + j;
+template <bool EDGE>
+__device__ __forceinline__ void sor_diagonals(const PhiAround& p, const Nbrs& n, double imdx2, double imdy2, double alpha,
+                                              double omega, double& a1, double& a2) {
     double coeff = 0.0;
-    if (j > 0) coeff += phi[o - 1];
-    if (j < W - 1) coeff += phi[o];
-    if (i > 0) coeff += phi[o - W];
-    if (i < H - 1) coeff += phi[o];
+    if (!EDGE || n.left) coeff += p.l;
+    if (!EDGE || n.right) coeff += p.c;
+    if (!EDGE || n.up) coeff += p.u;
+    if (!EDGE || n.down) coeff += p.c;
     coeff *= alpha;
     a1 = omega / (imdx2 + alpha * 0.05 + coeff);
     a2 = omega / (imdy2 + alpha * 0.05 + coeff);
@@ -870,9 +945,54 @@ __device__ __forceinline__ void sor_diagonals(const double* __restrict__ phi, in
 //   a1, a2     = hoisted SOR diagonals (above)
 // Reads 2*planes + 3 streams, writes 6 SOR operand planes in the layout the solver wants.
 // ------------------------------------------------------------------------------------------------
-struct SystemCell {
-    double phi, xy, a1, a2, b1, b2, x2, y2;
+// psi of the Laplacian noise model, src/OpticalFlow.cpp:401-404, from t = (imdt + imdx * du + imdy * dv)^2
+__device__ __forceinline__ double psi_value(double t) { return 1 / (2 * sqrt(t + 0.001 * 0.001)); }
+
+// the channel sums of (psi * a) * b, :414-427 with src/Image.h:1747-1763 (a single channel is assigned, not accumulated),
+// and their means over the channels, src/Image.h:1537-1545
+struct PsiTerms {
+    double xy = 0.0, x2 = 0.0, y2 = 0.0, tx = 0.0, ty = 0.0;
+    __device__ __forceinline__ void add(double psi, double gx, double gy, double gt, bool single) {
+        const double pgx = psi * gx, pgy = psi * gy;
+        if (single) {
+            xy = pgx * gy;
+            x2 = pgx * gx;
+            y2 = pgy * gy;
+            tx = pgx * gt;
+            ty = pgy * gt;
+        } else {
+            xy += pgx * gy;
+            x2 += pgx * gx;
+            y2 += pgy * gy;
+            tx += pgx * gt;
+            ty += pgy * gt;
+        }
+    }
+    __device__ __forceinline__ void mean(int planes) {
+        if (planes > 1) {
+            xy = xy / planes;
+            x2 = x2 / planes;
+            y2 = y2 / planes;
+            tx = tx / planes;
+            ty = ty / planes;
+        }
+    }
 };
+
+// rhs = -imdtd? - alpha * Laplacian(flow, phi) (:437-448) and the hoisted diagonals, from the channel means
+template <bool EDGE>
+__device__ __forceinline__ SystemCell system_cell(const PsiTerms& s, const PhiAround& p, const Cross& cu, const Cross& cv,
+                                                  const Nbrs& n, double alpha, double omega) {
+    SystemCell c;
+    c.b1 = -s.tx - alpha * laplacian_value<EDGE>(cu, p, n);
+    c.b2 = -s.ty - alpha * laplacian_value<EDGE>(cv, p, n);
+    sor_diagonals<EDGE>(p, n, s.x2, s.y2, alpha, omega, c.a1, c.a2);
+    c.phi = p.c;
+    c.xy = s.xy;
+    c.x2 = s.x2;
+    c.y2 = s.y2;
+    return c;
+}
 
 // EDGE = false: the cell is at least 2 pixels away from every image border, so no index needs clamping and every
 // neighbour exists -- the same operations in the same order with constant address offsets (the kernel is bound by
@@ -891,23 +1011,19 @@ __device__ __forceinline__ SystemCell assemble_cell(const double* __restrict__ b
                                                     const Increment& I) {
     const int planes = PLANES > 0 ? PLANES : planes_rt;
     const size_t np = (size_t)H * W, o = (size_t)i * W + j;
-    double sxy = 0.0, sx2 = 0.0, sy2 = 0.0, stx = 0.0, sty = 0.0;
+    PsiTerms s;
     double du = 0.0, dv = 0.0;
     if (!FAST) increment_at(I, i, j, W, du, dv);
     const auto channel = [&](int k) {
         const double* im = blend + k * np;
-        double gx = 0.0, gy = 0.0;
+        double gx, gy;
         if (EDGE) {
-#pragma unroll
-            for (int l = -2; l <= 2; l++) gx += im[(size_t)i * W + clampi(j + l, W)] * d.t[l + 2];
-#pragma unroll
-            for (int l = -2; l <= 2; l++) gy += im[(size_t)clampi(i + l, H) * W + j] * d.t[l + 2];
+            gx = tap_sum<2>(d, [&](int l) { return im[(size_t)i * W + clampi(j + l, W)]; });
+            gy = tap_sum<2>(d, [&](int l) { return im[(size_t)clampi(i + l, H) * W + j]; });
         } else {
             const double* p = im + o;
-#pragma unroll
-            for (int l = -2; l <= 2; l++) gx += p[l] * d.t[l + 2];
-#pragma unroll
-            for (int l = -2; l <= 2; l++) gy += p[(ptrdiff_t)l * W] * d.t[l + 2];
+            gx = tap_sum<2>(d, [&](int l) { return p[l]; });
+            gy = tap_sum<2>(d, [&](int l) { return p[(ptrdiff_t)l * W]; });
         }
         const double gt = imdt[k * np + o];
         double t = gt;  // imdt + imdx*du + imdy*dv (src/OpticalFlow.cpp:384); du = dv = 0 in the first inner iteration
@@ -915,7 +1031,7 @@ __device__ __forceinline__ SystemCell assemble_cell(const double* __restrict__ b
         t *= t;
         double psi;
         if (FAST) {
-            psi = 1 / (2 * sqrt(t + 0.001 * 0.001));
+            psi = psi_value(t);
         } else if (I.gm != nullptr) {  // :392-396 with GaussianMixture::Gaussian (src/NoiseModel.h:120-126).  The reference's PI there is
                                 // 3.1415927: Stochastic.h:19 defines it before NoiseModel.h's #ifndef (oracle/papof_oracle.c).
                                 // exp() is the device library's (<= 1 ulp, not glibc's bits): tolerance-checked branch.
@@ -930,22 +1046,9 @@ __device__ __forceinline__ SystemCell assemble_cell(const double* __restrict__ b
         } else if (I.lap != nullptr && I.lap[k] < 1E-20) {
             psi = 0.0;  // :399-400 `continue` on the freshly reset Psi_1st (:333)
         } else {
-            psi = 1 / (2 * sqrt(t + 0.001 * 0.001));
+            psi = psi_value(t);
         }
-        const double pgx = psi * gx, pgy = psi * gy;
-        if (planes == 1) {
-            sxy = pgx * gy;
-            sx2 = pgx * gx;
-            sy2 = pgy * gy;
-            stx = pgx * gt;
-            sty = pgy * gt;
-        } else {
-            sxy += pgx * gy;
-            sx2 += pgx * gx;
-            sy2 += pgy * gy;
-            stx += pgx * gt;
-            sty += pgy * gt;
-        }
+        s.add(psi, gx, gy, gt, planes == 1);
     };
     if (PLANES > 0) {
 #pragma unroll
@@ -954,46 +1057,10 @@ __device__ __forceinline__ SystemCell assemble_cell(const double* __restrict__ b
 #pragma unroll 1
         for (int k = 0; k < planes; k++) channel(k);
     }
-    if (planes > 1) {
-        sxy = sxy / planes;
-        sx2 = sx2 / planes;
-        sy2 = sy2 / planes;
-        stx = stx / planes;
-        sty = sty / planes;
-    }
-    SystemCell c;
-    if (EDGE) {
-        c.b1 = -stx - alpha * laplacian_at(u, phi, i, j, H, W);
-        c.b2 = -sty - alpha * laplacian_at(v, phi, i, j, H, W);
-        sor_diagonals(phi, i, j, H, W, sx2, sy2, alpha, omega, c.a1, c.a2);
-    } else {  // laplacian_at / sor_diagonals with every neighbour present
-        const double pc = phi[o], pl = phi[o - 1], pu = phi[o - W];
-        const double uc = u[o], vc = v[o];
-        double lu = 0.0, lv = 0.0;
-        lu -= (u[o + 1] - uc) * pc;
-        lu += (uc - u[o - 1]) * pl;
-        lu -= (u[o + W] - uc) * pc;
-        lu += (uc - u[o - W]) * pu;
-        lv -= (v[o + 1] - vc) * pc;
-        lv += (vc - v[o - 1]) * pl;
-        lv -= (v[o + W] - vc) * pc;
-        lv += (vc - v[o - W]) * pu;
-        c.b1 = -stx - alpha * lu;
-        c.b2 = -sty - alpha * lv;
-        double coeff = 0.0;
-        coeff += pl;
-        coeff += pc;
-        coeff += pu;
-        coeff += pc;
-        coeff *= alpha;
-        c.a1 = omega / (sx2 + alpha * 0.05 + coeff);
-        c.a2 = omega / (sy2 + alpha * 0.05 + coeff);
-    }
-    c.phi = phi[o];
-    c.xy = sxy;
-    c.x2 = sx2;
-    c.y2 = sy2;
-    return c;
+    s.mean(planes);
+    const Nbrs n = nbrs_at(i, j, H, W);
+    return system_cell<EDGE>(s, phi_around<EDGE>(phi, o, W, n), cross_at<EDGE>(u, o, W, n), cross_at<EDGE>(v, o, W, n), n,
+                             alpha, omega);
 }
 
 // row-major operands (red-black / Jacobi modes): one thread per cell
@@ -1019,10 +1086,8 @@ __global__ void k_assemble(const double* __restrict__ blend, const double* __res
     if (o_y2) o_y2[o] = c.y2;
 }
 
-// Skewed, paired operands of the exact-order solver.  A block owns a tile of 62 rows x kTileJ columns: cells are
-// COMPUTED in row-major order (coalesced plane reads), staged in LDS, and WRITTEN in skew order -- for one skew
-// position (anti-diagonal) the 16 threads of a group store 16 neighbouring rows = 256 contiguous bytes per paired
-// plane -- instead of scattered 16-byte cells.
+// Skewed, paired operands of the exact-order solver.  A block owns a tile of kAsmRows rows x kTileJ columns
+// (stage_cell / store_skew_tile above: 256 contiguous bytes per paired plane and skew position).
 #ifndef PAPOF_V_ASMCOLS
 #define PAPOF_V_ASMCOLS 16
 #endif
@@ -1031,9 +1096,6 @@ constexpr int kTileJ = PAPOF_V_ASMCOLS;  // columns of the assembly kernel's til
 #define PAPOF_V_ASMROWS 16  // same-box A/B (round 3, ms per 1080p pair): 62 rows 10.93-10.96, 31: 10.80, 24: 10.91, 16: 10.73-10.83, 12: 10.76-10.78, 8: 10.85-10.87
 #endif
 constexpr int kAsmRows = PAPOF_V_ASMROWS;  // rows of the assembly kernel's tile (its LDS stage bounds the workgroups per CU)
-struct double2s {
-    double x, y;
-};
 template <int PLANES, bool FAST>
 __global__ __launch_bounds__(256) void k_assemble_skew(const double* __restrict__ blend,
                                                        const double* __restrict__ imdt,
@@ -1057,30 +1119,13 @@ __global__ __launch_bounds__(256) void k_assemble_skew(const double* __restrict_
             const SystemCell s =
                 interior ? assemble_cell<false, PLANES, FAST>(blend, imdt, phi, u, v, i, j, H, W, planes, alpha, omega, d, I)
                          : assemble_cell<true, PLANES, FAST>(blend, imdt, phi, u, v, i, j, H, W, planes, alpha, omega, d, I);
-            stage[0][r][jj] = s.phi;
-            stage[1][r][jj] = s.xy;
-            stage[2][r][jj] = s.a1;
-            stage[3][r][jj] = s.a2;
-            stage[4][r][jj] = s.b1;
-            stage[5][r][jj] = s.b2;
+            stage_cell(stage, r, jj, s);
             if (o_x2) o_x2[(size_t)i * W + j] = s.x2;
             if (o_y2) o_y2[(size_t)i * W + j] = s.y2;
         }
     }
     __syncthreads();
-    const int g = tid / kTileJ, jj = tid - g * kTileJ;  // 16 groups of 16 threads; a group walks anti-diagonals
-    const int j = j0 + jj;
-    if (j >= W) return;
-    for (int pp = g; pp <= kAsmRows + kTileJ - 2; pp += 256 / kTileJ) {  // pp = jj + (row in tile)
-        const int r = pp - jj;
-        if (r < 0 || r >= kAsmRows) continue;
-        const int i = ib + r;
-        if (i >= row1) continue;
-        const size_t q = skew_cell(i, j, sk);
-        pa[q] = double2s{stage[0][r][jj], stage[1][r][jj]};
-        pb[q] = double2s{stage[2][r][jj], stage[3][r][jj]};
-        pc[q] = double2s{stage[4][r][jj], stage[5][r][jj]};
-    }
+    store_skew_tile(stage, tid, ib, j0, row1, W, sk, pa, pb, pc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1191,7 +1236,7 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
             if (t_in[q]) {
                 y = i + v[o];
                 x = j + u[o];
-                t_out[q] = x < 0 || x > W - 1 || y < 0 || y > H - 1;  // warp_value()
+                t_out[q] = leaves_image(x, y, W, H);
                 if (t_out[q]) {
                     x = j;
                     y = i;
@@ -1211,13 +1256,13 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     // a pixel that leaves the image takes frame 1's value: loaded (beside the gathers, which such a pixel does around itself in
     // frame 2, unused) only in a wave that has such a pixel -- a scalar test
     const bool wout = __ballot(t_out[0] || t_out[1] || t_out[2]) != 0ull;
-    // ---- phi of the tile and its upper / left neighbours (k_phi without an increment), and the flow of the own cell
+    // ---- phi of the tile and its upper / left neighbours (no increment)
     for (int c = tid; c < (kFT + 1) * (kFT + 1); c += NT) {
         const int r = c / (kFT + 1), cc = c - r * (kFT + 1);
         const int i = ib - 1 + r, j = j0 - 1 + cc;
         if (i < 0 || i >= min(H, row1) || j < 0 || j >= W) continue;
-        const size_t o = (size_t)i * W + j;
-        const double uc = u[o], vc = v[o];
+        const size_t o = (size_t)i * W + j;  // (phi_at()'s loads in place: through the function the register allocation of
+        const double uc = u[o], vc = v[o];    // every instance changes; with them here the code is the parent's)
         double ur = 0.0, vr = 0.0, ud = 0.0, vd = 0.0;
         if (j < W - 1) {
             ur = u[o + 1];
@@ -1227,20 +1272,15 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
             ud = u[o + W];
             vd = v[o + W];
         }
-        const double ux = j < W - 1 ? ur - uc : 0.0;
-        const double uy = i < H - 1 ? ud - uc : 0.0;
-        const double vx = j < W - 1 ? vr - vc : 0.0;
-        const double vy = i < H - 1 ? vd - vc : 0.0;
-        const double tt = ux * ux + uy * uy + vx * vx + vy * vy;
-        ph[r][cc] = 0.5 / sqrt(tt + 0.001 * 0.001);
+        ph[r][cc] = phi_value(uc, vc, ur, vr, ud, vd, j < W - 1, i < H - 1);
     }
     const int orow = tid / kFT, ocol = tid - orow * kFT;  // this thread's cell of the tile
     const int oi = ib + orow, oj = j0 + ocol;
     const bool own = oi < row1 && oj < W;
-    double sxy = 0.0, sx2 = 0.0, sy2 = 0.0, stx = 0.0, sty = 0.0;
+    PsiTerms s;
     // witnesses of the Laplacian-noise guard (k_warp_smooth_blend): one block in sixteen on large grids, its first wave
     const bool sampler = wit != nullptr && tid < 64 &&
-                         (ntiles <= 256 || ((tbx + 5 * tby) & 15) == 0);
+                         lap_samples_here(ntiles, tbx, tby);
     // The global operands of a channel are PREFETCHED while the previous channel is worked on (a workgroup barrier does not
     // wait for loads in flight): the gathers (and frame 1's value for a pixel that leaves the image) right behind P1, the smoothed
     // frame 1 of the blend's pixels right behind P3 -- the phases between are LDS only.
@@ -1287,12 +1327,8 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
         for (int q = 0; q < kP3; q++) s1v[q] = plane_ld(ps, s_o[q]);
     };
     const auto two_sums = [&](const double(&x)[6], double& a0, double& a1) {
-        a0 = 0.0;
-        a1 = 0.0;
-#pragma unroll
-        for (int l = 0; l < 5; l++) a0 += x[l] * g.t[l];
-#pragma unroll
-        for (int l = 0; l < 5; l++) a1 += x[l + 1] * g.t[l];
+        a0 = tap_sum<2>(g, [&](int l) { return x[l + 2]; });
+        a1 = tap_sum<2>(g, [&](int l) { return x[l + 3]; });
     };
     load_gathers(0);
     load_s1(0);
@@ -1304,6 +1340,9 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
 #pragma unroll
         for (int q = 0; q < kPer; q++) {
             if (q == 2 && !third) continue;
+            // bilinear_inside(g0, g1, g2, g3, dx, dy), KEPT IN PLACE: through the function (any form of it: values, references, a
+            // weights struct, a lambda) the exec-mask handling of every instance changes -- 25886 -> 25617 instructions over the
+            // 16 instances, SGPR spills to VGPR lanes 116 -> 146, one instance gains a private segment (profiles/level_once_isa.txt)
             const double dx = t_dx[q], dy = t_dy[q], ex = 1.0 - dx, ey = 1.0 - dy;
             const double g0 = !w1 && t_hi[q] ? ga[q].y : ga[q].x, g1 = !w1 && t_hi[q] ? gb[q].y : gb[q].x;
             const double g2 = w1 ? ga[q].x : ga[q].y, g3 = w1 ? gb[q].x : gb[q].y;
@@ -1312,11 +1351,11 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
             res += g1 * (ex * dy);
             res += g2 * (dx * ey);
             res += g3 * (dx * dy);
-            res = t_out[q] ? f1v[q] : res;  // warp_value(): a pixel that leaves the image takes frame 1's value
+            res = t_out[q] ? f1v[q] : res;  // a pixel that leaves the image takes frame 1's value
             if (t_in[q]) rawf[t_ra[q]] = res;
             if (sampler && q == 0) {
                 const double dd = fabs(wv - res);
-                hit = t_in[q] && dd >= wit_thr && dd < 1000000;
+                hit = lap_witness(dd, wit_thr, t_in[q]);
             }
         }
         if (sampler) {
@@ -1366,12 +1405,9 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
                 for (int e = 0; e < 2; e++) {
                     if (!(e ? ok1 : ok0)) continue;
                     const int r = r0 + e;
-                    const double s2 = a[e], s1 = s1v[e];
-                    double t = s1;
-                    t *= 0.4;
-                    t += s2 * 0.6;
-                    bl[r][cc] = t;
-                    if (r >= 2 && r < kFT + 2 && cc >= 2 && cc < kFT + 2) it[r - 2][cc - 2] = s2 - s1;
+                    double dt;
+                    blend_imdt(s1v[e], a[e], bl[r][cc], dt);
+                    if (r >= 2 && r < kFT + 2 && cc >= 2 && cc < kFT + 2) it[r - 2][cc - 2] = dt;
                 }
             }
         }
@@ -1379,6 +1415,8 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
         __syncthreads();
         // -- P4: derivatives, psi and the channel's terms of the own cell (assemble_cell, FAST)
         if (own) {
+            // tap_sum<2>(d, ...) four times, KEPT IN PLACE: through the function the kernel is at its SGPR limit elsewhere -- eight
+            // instances gain a private segment, SGPR spills to VGPR lanes 116 -> 171 (profiles/level_once_isa.txt)
             double gx = 0.0, gy = 0.0;
             if (interior) {
 #pragma unroll
@@ -1394,97 +1432,31 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
             const double gt = it[orow][ocol];
             double t = gt;
             t *= t;
-            const double psi = 1 / (2 * sqrt(t + 0.001 * 0.001));
-            const double pgx = psi * gx, pgy = psi * gy;
-            if (PLANES == 1) {
-                sxy = pgx * gy;
-                sx2 = pgx * gx;
-                sy2 = pgy * gy;
-                stx = pgx * gt;
-                sty = pgy * gt;
-            } else {
-                sxy += pgx * gy;
-                sx2 += pgx * gx;
-                sy2 += pgy * gy;
-                stx += pgx * gt;
-                sty += pgy * gt;
-            }
+            s.add(psi_value(t), gx, gy, gt, PLANES == 1);
         }
         // (the next channel's P1 writes raw, last read in P2; its P3 writes bl / it, read above: two barriers lie between)
     }
     if (own) {
-        if (PLANES > 1) {
-            sxy = sxy / PLANES;
-            sx2 = sx2 / PLANES;
-            sy2 = sy2 / PLANES;
-            stx = stx / PLANES;
-            sty = sty / PLANES;
-        }
-        const int i = oi, j = oj;
-        const size_t o = (size_t)i * W + j;
-        const double pc_ = ph[orow + 1][ocol + 1];
-        const double pl = j > 0 ? ph[orow + 1][ocol] : 0.0, pu = i > 0 ? ph[orow][ocol + 1] : 0.0;
-        // laplacian_at(u, phi) / laplacian_at(v, phi) and sor_diagonals(phi) with phi from LDS
-        const double uc = u[o], vc = v[o];
-        double lu = 0.0, lv = 0.0;
-        if (j < W - 1) {
-            lu -= (u[o + 1] - uc) * pc_;
-            if (j > 0) lu += (uc - u[o - 1]) * pl;
-        }
-        if (i < H - 1) {
-            lu -= (u[o + W] - uc) * pc_;
-            if (i > 0) lu += (uc - u[o - W]) * pu;
-        }
-        if (j < W - 1) {
-            lv -= (v[o + 1] - vc) * pc_;
-            if (j > 0) lv += (vc - v[o - 1]) * pl;
-        }
-        if (i < H - 1) {
-            lv -= (v[o + W] - vc) * pc_;
-            if (i > 0) lv += (vc - v[o - W]) * pu;
-        }
-        double coeff = 0.0;
-        if (j > 0) coeff += pl;
-        if (j < W - 1) coeff += pc_;
-        if (i > 0) coeff += pu;
-        if (i < H - 1) coeff += pc_;
-        coeff *= alpha;
-        const double a1 = omega / (sx2 + alpha * 0.05 + coeff), a2 = omega / (sy2 + alpha * 0.05 + coeff);
-        const double b1 = -stx - alpha * lu, b2 = -sty - alpha * lv;
+        s.mean(PLANES);
+        const size_t o = (size_t)oi * W + oj;
+        const Nbrs n = nbrs_at(oi, oj, H, W);
+        const PhiAround p{ph[orow + 1][ocol + 1], n.left ? ph[orow + 1][ocol] : 0.0, n.up ? ph[orow][ocol + 1] : 0.0};  // phi from LDS
+        const SystemCell c = system_cell<true>(s, p, cross_at<true>(u, o, W, n), cross_at<true>(v, o, W, n), n, alpha, omega);
         if (SKEW) {
-            stage[0][orow][ocol] = pc_;
-            stage[1][orow][ocol] = sxy;
-            stage[2][orow][ocol] = a1;
-            stage[3][orow][ocol] = a2;
-            stage[4][orow][ocol] = b1;
-            stage[5][orow][ocol] = b2;
+            stage_cell(stage, orow, ocol, c);
         } else {
-            out.q[0][o] = pc_;
-            out.q[1][o] = sxy;
-            out.q[2][o] = a1;
-            out.q[3][o] = a2;
-            out.q[4][o] = b1;
-            out.q[5][o] = b2;
+            out.q[0][o] = c.phi;
+            out.q[1][o] = c.xy;
+            out.q[2][o] = c.a1;
+            out.q[3][o] = c.a2;
+            out.q[4][o] = c.b1;
+            out.q[5][o] = c.b2;
         }
     }
     if (!SKEW) return;
-    double2s* const pa = reinterpret_cast<double2s*>(out.q[0]);
-    double2s* const pb = reinterpret_cast<double2s*>(out.q[2]);
-    double2s* const pc = reinterpret_cast<double2s*>(out.q[4]);
     __syncthreads();
-    // ---- written in skew order, as k_assemble_skew does: a group of 16 threads stores 16 neighbouring rows of one position
-    const int grp = tid / kFT, jj = tid - grp * kFT, j = j0 + jj;
-    if (j >= W) return;
-    for (int pp = grp; pp <= 2 * kFT - 2; pp += kFT) {
-        const int r = pp - jj;
-        if (r < 0 || r >= kFT) continue;
-        const int i = ib + r;
-        if (i >= row1) continue;
-        const size_t q = skew_cell(i, j, sk);
-        pa[q] = double2s{stage[0][r][jj], stage[1][r][jj]};
-        pb[q] = double2s{stage[2][r][jj], stage[3][r][jj]};
-        pc[q] = double2s{stage[4][r][jj], stage[5][r][jj]};
-    }
+    store_skew_tile(stage, tid, ib, j0, row1, W, sk, reinterpret_cast<double2s*>(out.q[0]),
+                    reinterpret_cast<double2s*>(out.q[2]), reinterpret_cast<double2s*>(out.q[4]));
 }
 
 // stage helper: SOR operands from already assembled row-major planes (tests / micro-benchmark)
@@ -1499,7 +1471,8 @@ __global__ void k_sor_prep(const double* __restrict__ phi, const double* __restr
     if (j >= W || i >= H) return;
     const size_t o = (size_t)i * W + j;
     double a1, a2;
-    sor_diagonals(phi, i, j, H, W, imdx2[o], imdy2[o], alpha, omega, a1, a2);
+    const Nbrs n = nbrs_at(i, j, H, W);
+    sor_diagonals<true>(phi_around<true>(phi, o, W, n), n, imdx2[o], imdy2[o], alpha, omega, a1, a2);
     const size_t q = sor_index<SKEW>(i, j, W, sk);
     o_phi[q] = phi[o];
     o_xy[q] = imdxy[o];
@@ -1603,13 +1576,13 @@ __global__ void k_update_warp_phi(const double* __restrict__ sdu, const double* 
             for (int k = bw * bh >= planes ? lin % planes : lin; k < planes; k += bw * bh) {
                 const double w = warp_value(im1 + k * np, im2 + k * np, fu, fv, i, j, H, W);
                 const double d = fabs(im1[k * np + o] - w);
-                if (d >= wit_thr && d < 1000000) wit[k] = mark;
+                if (lap_witness(d, wit_thr)) wit[k] = mark;
             }
-        } else if (((tbx + 5 * tby) & 15) == 0)  // a large grid: one block in sixteen samples
+        } else if (lap_one_in_sixteen(tbx, tby))  // a large grid
         for (int k = lin; k < planes; k += bw * bh) {  // (one trip of one thread per channel, unless the block has fewer pixels)
             const double w = warp_value(im1 + k * np, im2 + k * np, fu, fv, i, j, H, W);
             const double d = fabs(im1[k * np + o] - w);
-            if (d >= wit_thr && d < 1000000) wit[k] = mark;
+            if (lap_witness(d, wit_thr)) wit[k] = mark;
         }
     }
     if (phi_out != nullptr) {
@@ -1628,32 +1601,8 @@ __global__ void k_update_warp_phi(const double* __restrict__ sdu, const double* 
             ud += a;
             vd += b;
         }
-        const double ux = j < W - 1 ? ur - fu : 0.0;
-        const double uy = i < H - 1 ? ud - fu : 0.0;
-        const double vx = j < W - 1 ? vr - fv : 0.0;
-        const double vy = i < H - 1 ? vd - fv : 0.0;
-        const double t = ux * ux + uy * uy + vx * vx + vy * vy;
-        phi_out[o] = 0.5 / sqrt(t + 0.001 * 0.001);
+        phi_out[o] = phi_value(fu, fv, ur, vr, ud, vd, j < W - 1, i < H - 1);
     }
-    if (do_warp) warp_pixel(im1, im2, warp, fu, fv, i, j, H, W, planes);
-}
-
-// Exact-order solver layout: (du, dv) read straight from the paired skewed plane (16 bytes per thread; an LDS-staged
-// transposition of the tile was measured slower: the kernel is bound by the 4-tap x C-plane gather of the warp).
-__global__ void k_update_warp_skew(const double2s* __restrict__ pd, double* __restrict__ u, double* __restrict__ v,
-                                   const double* __restrict__ im1, const double* __restrict__ im2,
-                                   double* __restrict__ warp, int H, int W, int planes, SkewIdx sk,
-                                   unsigned long long* stamp, int do_warp) {
-    stamp_now(stamp);
-    const int j = blockIdx.x * BX + threadIdx.x, i = blockIdx.y * BY + threadIdx.y;
-    if (j >= W || i >= H) return;
-    const size_t o = (size_t)i * W + j;
-    const double2s c = pd[dudv_cell(i, j, sk)];
-    double fu = u[o], fv = v[o];
-    fu += c.x;
-    fv += c.y;
-    u[o] = fu;
-    v[o] = fv;
     if (do_warp) warp_pixel(im1, im2, warp, fu, fv, i, j, H, W, planes);
 }
 
@@ -1887,6 +1836,32 @@ Taps central3_taps() {  // src/Image.h:2589
 
 #define LAUNCH_CHECK() PAPOF_HIP(hipGetLastError())
 
+const SkewIdx kNoSkew{};  // operands that are not in the exact-order solver's skewed layout
+const BatchK kNoBatch{};  // a single call (common.h: BatchK)
+
+// The rows row0 .. row1-1 of a plane that a wrapper works on (row1 < 0: down to the last row).  false: nothing to launch,
+// rc says why -- PAPOF_EINVAL for a range outside the plane, PAPOF_OK for an empty one.
+static bool rows_of(int row0, int& row1, int H, int& rc) {
+    if (row1 < 0) row1 = H;
+    rc = row0 < 0 || row1 > H ? PAPOF_EINVAL : PAPOF_OK;
+    return rc == PAPOF_OK && row1 > row0;
+}
+
+// the witness threshold of the Laplacian-noise guard: a sample of 2e-20 x pixels keeps the mean over at most that many
+// samples at or above 1e-20 (lap_witness())
+static double lap_wit_threshold(int H, int W) { return 2e-20 * (double)H * (double)W; }
+
+// run-time flags -> template arguments: f(std::bool_constant<flag>...), every call of f returning the same type (a kernel)
+template <class F>
+static auto with_flags(F f) {
+    return f();
+}
+template <class F, class... Rest>
+static auto with_flags(F f, bool flag, Rest... rest) {
+    return flag ? with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...)
+                : with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+
 int hwc_to_planar(papof_handle* h, const double* hwc, double* planar, int H, int W, int C, int frames) {
     hipLaunchKernelGGL(k_hwc_to_planar, grid2d(W, H, frames), dim3(BX, BY), 0, h->stream, hwc, planar, H, W, C);
     LAUNCH_CHECK();
@@ -1943,7 +1918,7 @@ int emit_outputs(papof_handle* h, const double* src, const papof_tensor& dst, bo
 
 int fb_check(papof_handle* h, hipStream_t st, const papof_tensor& fw, const papof_tensor& bw, const papof_tensor& mask,
              int pairs, int H, int W, double a1, double a2) {
-    const long long tiles = (long long)((W + kFbTX - 1) / kFbTX) * ((H + kFbTY - 1) / kFbTY);
+    const long long tiles = (long long)tiles_of(W, kFbTX) * tiles_of(H, kFbTY);
     if (pairs <= 0 || tiles <= 0) return PAPOF_OK;
     if (tiles > kMaxTiles) return PAPOF_EINVAL;
     const auto at = [](const papof_tensor& t, long long items) {  // the same tensor from pair `items` on
@@ -1983,7 +1958,7 @@ int filter_v(papof_handle* h, const double* src, double* dst, int H, int W, int 
 }
 
 int central3_planes(papof_handle* h, const double* src, double* gx, double* gy, double* gxy, int H, int W, int planes) {
-    hipLaunchKernelGGL(k_central3_all, dim3(xcd_grid((W + BX - 1) / BX, (H + BY - 1) / BY), 1, planes), dim3(BX, BY), 0, h->stream, src, gx, gy, gxy, H, W,
+    hipLaunchKernelGGL(k_central3_all, dim3(xcd_grid(tiles_of(W, BX), tiles_of(H, BY)), 1, planes), dim3(BX, BY), 0, h->stream, src, gx, gy, gxy, H, W,
                        central3_taps());
     LAUNCH_CHECK();
     return PAPOF_OK;
@@ -1997,10 +1972,10 @@ int filter_hv(papof_handle* h, const double* src, double* dst, double* tmp, int 
         PAPOF_TRY(filter_h(h, src, tmp, H, W, planes, fh));
         return filter_v(h, tmp, dst, H, W, planes, fv);
     }
-    const dim3 grid((W + BX - 1) / BX, (H + kHvRows - 1) / kHvRows, planes), block(BX, BY);
+    const dim3 grid(tiles_of(W, BX), tiles_of(H, kHvRows), planes), block(BX, BY);
     const int f = fh.fsize == fv.fsize ? fh.fsize : -1;
     if (PAPOF_V_HVSTAGED && f >= 1 && f <= 3) {
-        const dim3 sgrid(xcd_grid((W + BX - 1) / BX, (H + kHvsRows - 1) / kHvsRows), 1, planes);
+        const dim3 sgrid(xcd_grid(tiles_of(W, BX), tiles_of(H, kHvsRows)), 1, planes);
         if (f == 1)
             hipLaunchKernelGGL(k_filter_hv_staged<1>, sgrid, block, 0, h->stream, src, dst, H, W, fh, fv);
         else if (f == 2)
@@ -2026,7 +2001,7 @@ int resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int 
            double yr, bool use_post, double post, const Rect* rc) {
     const Rect r = region(rc, dw, dh);
     if (r.empty()) return PAPOF_OK;
-    hipLaunchKernelGGL(k_resize, dim3(xcd_grid((r.x1 - r.x0 + BX - 1) / BX, (r.y1 - r.y0 + BY - 1) / BY), 1, planes), dim3(BX, BY), 0, h->stream, src, dst, sh, sw, dh, dw, xr, yr,
+    hipLaunchKernelGGL(k_resize, dim3(xcd_grid(tiles_of(r.x1 - r.x0, BX), tiles_of(r.y1 - r.y0, BY)), 1, planes), dim3(BX, BY), 0, h->stream, src, dst, sh, sw, dh, dw, xr, yr,
                        use_post ? 1 : 0, post, r, take_stamp(h));
     LAUNCH_CHECK();
     return PAPOF_OK;
@@ -2036,10 +2011,10 @@ int im2feature(papof_handle* h, const double* im, double* feat, int H, int W, in
     // frames > 1 (a batch): frame f reads im + f * (C planes), writes feat + f * (5 or 3 planes), flags nz + f * nz_stride
     const size_t np = (size_t)H * W;
     if (C == 3) {
-        hipLaunchKernelGGL((frames > 1 ? k_im2feature_tiled<3, true> : k_im2feature_tiled<3, false>), dim3(xcd_grid((W + BX - 1) / BX, (H + kFeatRows - 1) / kFeatRows), frames), dim3(BX, BY), 0,
+        hipLaunchKernelGGL((frames > 1 ? k_im2feature_tiled<3, true> : k_im2feature_tiled<3, false>), dim3(xcd_grid(tiles_of(W, BX), tiles_of(H, kFeatRows)), frames), dim3(BX, BY), 0,
                            h->stream, im, feat, H, W, deriv5_taps(), nz, h->lap_epoch, 3 * np, 5 * np, nz_stride);
     } else if (C == 1) {
-        hipLaunchKernelGGL((frames > 1 ? k_im2feature_tiled<1, true> : k_im2feature_tiled<1, false>), dim3(xcd_grid((W + BX - 1) / BX, (H + kFeatRows - 1) / kFeatRows), frames), dim3(BX, BY), 0,
+        hipLaunchKernelGGL((frames > 1 ? k_im2feature_tiled<1, true> : k_im2feature_tiled<1, false>), dim3(xcd_grid(tiles_of(W, BX), tiles_of(H, kFeatRows)), frames), dim3(BX, BY), 0,
                            h->stream, im, feat, H, W, deriv5_taps(), nz, h->lap_epoch, np, 3 * np, nz_stride);
     } else {  // src/OpticalFlow.cpp:956-957: any other channel count is passed through
         if (frames != 1) return PAPOF_EINVAL;
@@ -2076,17 +2051,16 @@ static SkewIdx skew_idx(const SorPlanes& sp) {
 
 // `prev` = operands of the previous inner iteration's solve (nullptr in the first one: du = dv = 0)
 static Increment increment_of(const SorPlanes* prev, const double* gm = nullptr, const double* lap = nullptr) {
-    if (!prev) return Increment{nullptr, nullptr, 0, SkewIdx{0, 0, 0, 0, 0, 0, 0}, gm, lap};
-    return Increment{prev->du, prev->dv, prev->skew ? 1 : 0, prev->skew ? skew_idx(*prev) : SkewIdx{0, 0, 0, 0, 0, 0, 0},
+    if (!prev) return Increment{nullptr, nullptr, 0, kNoSkew, gm, lap};
+    return Increment{prev->du, prev->dv, prev->skew ? 1 : 0, prev->skew ? skew_idx(*prev) : kNoSkew,
                      gm, lap};
 }
 
 int smooth_hv_blend(papof_handle* h, const double* warp, const double* im1s, double* blend, double* imdt, int H,
                     int W, int planes, int row0, int row1) {
-    if (row1 < 0) row1 = H;
-    if (row0 < 0 || row1 > H) return PAPOF_EINVAL;
-    if (row1 <= row0) return PAPOF_OK;
-    hipLaunchKernelGGL(k_smooth_hv_blend, dim3((W + BX - 1) / BX, (row1 - row0 + kFuseRows - 1) / kFuseRows, planes),
+    int rc;
+    if (!rows_of(row0, row1, H, rc)) return rc;
+    hipLaunchKernelGGL(k_smooth_hv_blend, dim3(tiles_of(W, BX), tiles_of(row1 - row0, kFuseRows), planes),
                        dim3(BX, BY), 0, h->stream, warp, im1s, blend, imdt, H, W, smooth5_taps(), take_stamp(h), row0,
                        row1);
     LAUNCH_CHECK();
@@ -2096,9 +2070,9 @@ int smooth_hv_blend(papof_handle* h, const double* warp, const double* im1s, dou
 int warp_smooth_blend(papof_handle* h, const double* im1, const double* im2, const double* u, const double* v,
                       const double* im1s, double* blend, double* imdt, int H, int W, int planes, unsigned* wit,
                       double* phi_out) {
-    hipLaunchKernelGGL(k_warp_smooth_blend, dim3((W + BX - 1) / BX, (H + kWsRows - 1) / kWsRows, planes), dim3(BX, BY), 0,
+    hipLaunchKernelGGL(k_warp_smooth_blend, dim3(tiles_of(W, BX), tiles_of(H, kWsRows), planes), dim3(BX, BY), 0,
                        h->stream, im1, im2, u, v, im1s, blend, imdt, H, W, smooth5_taps(), take_stamp(h), wit,
-                       2e-20 * (double)H * (double)W, h->lap_epoch, phi_out);
+                       lap_wit_threshold(H, W), h->lap_epoch, phi_out);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2132,7 +2106,7 @@ int assemble_system(papof_handle* h, const double* blend, const double* imdt, co
         const auto kern = planes == 5   ? (fast ? k_assemble_skew<5, true> : k_assemble_skew<5, false>)
                           : planes == 3 ? (fast ? k_assemble_skew<3, true> : k_assemble_skew<3, false>)
                                         : k_assemble_skew<0, false>;
-        hipLaunchKernelGGL(kern, dim3((W + kTileJ - 1) / kTileJ, (r.y1 - r.y0 + kAsmRows - 1) / kAsmRows),
+        hipLaunchKernelGGL(kern, dim3(tiles_of(W, kTileJ), tiles_of(r.y1 - r.y0, kAsmRows)),
                            dim3(256), 0, h->stream, blend, imdt, phi, u, v, H, W, planes, alpha, omega, skew_idx(out),
                            (double2s*)out.phi, (double2s*)out.a1, (double2s*)out.b1, opt_imdx2, opt_imdy2,
                            deriv5_taps(), I, take_stamp(h), r.y0, r.y1);
@@ -2152,24 +2126,16 @@ int flow_system(papof_handle* h, const double* im1, const double* im2, const dou
                 int batch, const BatchK* bk) {
     if (planes != 5 && planes != 3) return PAPOF_EINVAL;
     if ((unsigned long long)H * (unsigned long long)W > (1ull << 29)) return PAPOF_EINVAL;  // 32-bit byte offsets into a plane
-    if (row1 < 0) row1 = H;
-    if (row0 < 0 || row1 > H) return PAPOF_EINVAL;
-    if (row1 <= row0) return PAPOF_OK;
-    const int ntiles = ((W + kFT - 1) / kFT) * ((row1 - row0 + kFT - 1) / kFT);
-    const dim3 grid(8 * ((ntiles + 7) / 8), batch);  // (the kernel maps block -> tile: a contiguous run of tiles per XCD)
+    int rc;
+    if (!rows_of(row0, row1, H, rc)) return rc;
+    const dim3 grid(xcd_grid(tiles_of(W, kFT), tiles_of(row1 - row0, kFT)), batch);  // (the kernel maps block -> tile, as xcd_tile does)
     const SixPlanes six{{out.phi, out.xy, out.a1, out.a2, out.b1, out.b2}};
-    const BatchK bk0{0, 0, 0, 0, 0, 0};
-    const auto pick = [&](auto one_column) {
-        constexpr bool W1 = decltype(one_column)::value;
-        return batch > 1 ? (out.skew ? (planes == 5 ? k_flow_system<5, true, true, W1> : k_flow_system<3, true, true, W1>)
-                                     : (planes == 5 ? k_flow_system<5, false, true, W1> : k_flow_system<3, false, true, W1>))
-                         : (out.skew ? (planes == 5 ? k_flow_system<5, true, false, W1> : k_flow_system<3, true, false, W1>)
-                                     : (planes == 5 ? k_flow_system<5, false, false, W1> : k_flow_system<3, false, false, W1>));
-    };
-    const auto kern = W == 1 ? pick(std::true_type{}) : pick(std::false_type{});
+    const auto kern = with_flags([](auto five, auto skew, auto batched, auto one_column) {
+        return &k_flow_system<five.value ? 5 : 3, skew.value, batched.value, one_column.value>;
+    }, planes == 5, out.skew, batch > 1, W == 1);
     hipLaunchKernelGGL(kern, grid, dim3(kFT * kFT), 0, h->stream, im1, im2, u, v, im1s, H, W, alpha, omega,
-                       out.skew ? skew_idx(out) : SkewIdx{0, 0, 0, 0, 0, 0, 0, 0, 0}, six, smooth5_taps(), deriv5_taps(),
-                       take_stamp(h), wit, 2e-20 * (double)H * (double)W, h->lap_epoch, row0, row1, bk ? *bk : bk0);
+                       out.skew ? skew_idx(out) : kNoSkew, six, smooth5_taps(), deriv5_taps(),
+                       take_stamp(h), wit, lap_wit_threshold(H, W), h->lap_epoch, row0, row1, bk ? *bk : kNoBatch);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2180,39 +2146,19 @@ int laplacian(papof_handle* h, const double* in, const double* weight, double* o
     return PAPOF_OK;
 }
 
-int update_and_warp(papof_handle* h, const SorPlanes& sp, double* u, double* v, const double* im1,
-                    const double* im2, double* warp, int H, int W, int planes, bool do_warp) {
-    if (sp.skew) {
-        hipLaunchKernelGGL(k_update_warp_skew, grid2d(W, H), dim3(BX, BY), 0, h->stream, (const double2s*)sp.du, u, v,
-                           im1, im2, warp, H, W, planes, skew_idx(sp), take_stamp(h), do_warp ? 1 : 0);
-    } else {
-        hipLaunchKernelGGL(k_update_warp, grid2d(W, H), dim3(BX, BY), 0, h->stream, sp.du, sp.dv, u, v, im1, im2, warp,
-                           H, W, planes, Rect{0, 0, W, H}, do_warp ? 1 : 0, take_stamp(h));
-    }
-    LAUNCH_CHECK();
-    return PAPOF_OK;
-}
-
 int update_warp_phi(papof_handle* h, const SorPlanes& sp, const double* u, const double* v, double* u_out, double* v_out,
                     const double* im1, const double* im2, double* warp, double* phi_out, int H, int W, int planes,
                     bool do_warp, int row0, int row1, unsigned* wit, int batch, const BatchK* bk) {
-    const double wit_thr = 2e-20 * (double)H * (double)W;
-    const BatchK bk0{0, 0, 0, 0, 0, 0};
     if (batch > 1 && (warp || phi_out || do_warp)) return PAPOF_EINVAL;
     if (u == u_out || v == v_out) return PAPOF_EINVAL;
-    if (row1 < 0) row1 = H;
-    if (row0 < 0 || row1 > H) return PAPOF_EINVAL;
-    if (row1 <= row0) return PAPOF_OK;
-    const dim3 grid(xcd_grid((W + BX - 1) / BX, (row1 - row0 + BY - 1) / BY), batch);
-    if (sp.skew)
-        hipLaunchKernelGGL((batch > 1 ? k_update_warp_phi<true, true> : k_update_warp_phi<true, false>), grid, dim3(BX, BY), 0,
-                           h->stream, sp.du, sp.dv, skew_idx(sp),
-                           u, v, u_out, v_out, im1, im2, warp, phi_out, H, W, planes, do_warp ? 1 : 0, take_stamp(h),
-                           row0, row1, wit, wit_thr, h->lap_epoch, bk ? *bk : bk0);
-    else
-        hipLaunchKernelGGL((batch > 1 ? k_update_warp_phi<false, true> : k_update_warp_phi<false, false>), grid, dim3(BX, BY), 0, h->stream, sp.du, sp.dv,
-                           SkewIdx{0, 0, 0, 0, 0, 0, 0, 0, 0}, u, v, u_out, v_out, im1, im2, warp, phi_out, H, W, planes,
-                           do_warp ? 1 : 0, take_stamp(h), row0, row1, wit, wit_thr, h->lap_epoch, bk ? *bk : bk0);
+    int rc;
+    if (!rows_of(row0, row1, H, rc)) return rc;
+    const dim3 grid(xcd_grid(tiles_of(W, BX), tiles_of(row1 - row0, BY)), batch);
+    const auto kern = with_flags([](auto skew, auto batched) { return &k_update_warp_phi<skew.value, batched.value>; },
+                                 sp.skew, batch > 1);
+    hipLaunchKernelGGL(kern, grid, dim3(BX, BY), 0, h->stream, sp.du, sp.dv, sp.skew ? skew_idx(sp) : kNoSkew, u, v, u_out,
+                       v_out, im1, im2, warp, phi_out, H, W, planes, do_warp ? 1 : 0, take_stamp(h), row0, row1, wit,
+                       lap_wit_threshold(H, W), h->lap_epoch, bk ? *bk : kNoBatch);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2257,9 +2203,8 @@ int bicubic_warp(papof_handle* h, const double* im1, const double* im2, const do
                  const Rect* rc, bool planar_out, bool clamp, int batch, const BatchK* bk) {
     const Rect r = region(rc, W, H);
     if (r.empty()) return PAPOF_OK;
-    const BatchK bk0{0, 0, 0, 0, 0, 0};
-    hipLaunchKernelGGL(batch > 1 ? k_bicubic<true> : k_bicubic<false>, dim3(xcd_grid((r.x1 - r.x0 + BX - 1) / BX, (r.y1 - r.y0 + BY - 1) / BY), batch), dim3(BX, BY), 0, h->stream, im1, im2, gx, gy, gxy, vx, vy, out_hwc, H, W,
-                       C, r, take_stamp(h), planar_out ? 1 : 0, clamp ? 1 : 0, bk ? *bk : bk0);
+    hipLaunchKernelGGL(batch > 1 ? k_bicubic<true> : k_bicubic<false>, dim3(xcd_grid(tiles_of(r.x1 - r.x0, BX), tiles_of(r.y1 - r.y0, BY)), batch), dim3(BX, BY), 0, h->stream, im1, im2, gx, gy, gxy, vx, vy, out_hwc, H, W,
+                       C, r, take_stamp(h), planar_out ? 1 : 0, clamp ? 1 : 0, bk ? *bk : kNoBatch);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2372,7 +2317,7 @@ static __global__ __launch_bounds__(kLapThreads) void k_lap_partial(const double
             if (k >= C) break;
             const double w = u ? warp_value(im1 + k * np, im2 + k * np, fu, fv, i, j, H, W) : im2[k * np + o];
             const double d = fabs(im1[k * np + o] - w);
-            if (d > 0 && d < 1000000) {
+            if (lap_valid(d)) {
                 acc[k][0] += d;
                 acc[k][1] += 1.0;
             }
@@ -2419,8 +2364,8 @@ static __global__ __launch_bounds__(256) void k_lap_small(const double* __restri
     for (int o = threadIdx.x; o < np; o += 256) {
         const int i = o / W, j = o - i * W;
         const double d = fabs(p1[o] - warp_value(p1, p2, u[o], v[o], i, j, H, W));
-        valid = valid || (d > 0 && d < 1000000);
-        hit = hit || (d >= wit_thr && d < 1000000);
+        valid = valid || lap_valid(d);
+        hit = hit || lap_witness(d, wit_thr);
     }
     const int any_hit = __syncthreads_or(hit ? 1 : 0), any_valid = __syncthreads_or(valid ? 1 : 0);
     if (threadIdx.x == 0 && (any_hit || !any_valid)) wit[blockIdx.x] = any_hit ? mark : (mark ^ kLapNone);
@@ -2440,8 +2385,8 @@ static __global__ __launch_bounds__(256) void k_lap_rows(const double* __restric
         const int i = r0 + c / W, j = c - (c / W) * W;
         const size_t o = (size_t)i * W + j;
         const double d = fabs(p1[o] - warp_value(p1, p2, u[o], v[o], i, j, H, W));
-        valid = valid || (d > 0 && d < 1000000);
-        hit = hit || (d >= wit_thr && d < 1000000);
+        valid = valid || lap_valid(d);
+        hit = hit || lap_witness(d, wit_thr);
     }
     const int any_hit = __syncthreads_or(hit ? 1 : 0), any_valid = __syncthreads_or(valid ? 1 : 0);
     if (threadIdx.x == 0) {
@@ -2454,16 +2399,15 @@ int lap_rows_check(papof_handle* h, const double* im1, const double* im2, const 
     if (r1 <= r0) return PAPOF_OK;
     const int blocks = std::min(256, ((r1 - r0) * W + 255) / 256);
     hipLaunchKernelGGL(k_lap_rows, dim3(blocks, C), dim3(256), 0, h->stream, im1, im2, u, v, H, W, r0, r1, wit, val,
-                       2e-20 * (double)H * (double)W, mark);
+                       lap_wit_threshold(H, W), mark);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
 bool lap_one_block_level(int H, int W) { return H <= kWsRows && W <= BX; }
 int lap_small_check(papof_handle* h, const double* im1, const double* im2, const double* u, const double* v, int H, int W,
                     int C, unsigned* wit, int batch, const BatchK* bk) {
-    const BatchK bk0{0, 0, 0, 0, 0, 0};
     hipLaunchKernelGGL(k_lap_small, dim3(C, batch), dim3(256), 0, h->stream, im1, im2, u, v, H, W, wit,
-                       2e-20 * (double)H * (double)W, h->lap_epoch, bk ? *bk : bk0);
+                       lap_wit_threshold(H, W), h->lap_epoch, bk ? *bk : kNoBatch);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2494,7 +2438,7 @@ int sor_prep(papof_handle* h, const double* phi, const double* imdxy, const doub
                            out.b2);
     else
         hipLaunchKernelGGL(k_sor_prep<false>, grid2d(W, H), dim3(BX, BY), 0, h->stream, phi, imdxy, imdx2, imdy2,
-                           rhs1, rhs2, H, W, alpha, omega, SkewIdx{0, 0, 0, 0, 0, 0, 0}, out.phi, out.xy, out.a1, out.a2, out.b1,
+                           rhs1, rhs2, H, W, alpha, omega, kNoSkew, out.phi, out.xy, out.a1, out.a2, out.b1,
                            out.b2);
     LAUNCH_CHECK();
     return PAPOF_OK;
@@ -2506,7 +2450,7 @@ int sor_unpack(papof_handle* h, const SorPlanes& sp, double* du, double* dv, int
                            skew_idx(sp));
     else
         hipLaunchKernelGGL(k_sor_unpack<false>, grid2d(W, H), dim3(BX, BY), 0, h->stream, sp.du, sp.dv, du, dv, H,
-                           W, SkewIdx{0, 0, 0, 0, 0, 0, 0});
+                           W, kNoSkew);
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
