@@ -99,7 +99,7 @@ int check_params(const papof_params& P, int levels) {
 }
 
 int pyramid_plan(int H, int W, double ratio, int nlev, std::vector<Level>& L, std::vector<PyrPlan>& plan) {
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;  // :82-83
+    ratio = effective_ratio(ratio);                 // :82-83
     const double base_sigma = 1 / ratio - 1;        // :89
     const int n = (int)(std::log(0.25) / std::log(ratio));  // :90
     const double n_sigma = base_sigma * n;          // :91
@@ -127,6 +127,57 @@ int pyramid_plan(int H, int W, double ratio, int nlev, std::vector<Level>& L, st
         L[i].h = (int)((double)p.sh * p.rate);
         if (L[i].w < 1 || L[i].h < 1) return PAPOF_EINVAL;
         plan[i] = p;
+    }
+    return PAPOF_OK;
+}
+
+papof_params params_or_default(const papof_params* params) {
+    papof_params P;
+    if (params)
+        P = *params;
+    else
+        papof_default_params(&P);
+    return P;
+}
+
+int call_plan(int H, int W, int C, int levels, const papof_params& P, CallPlan& cp) {
+    PAPOF_TRY(check_params(P, levels));
+    cp.ratio = effective_ratio(P.ratio);
+    cp.levels = levels;
+    cp.fc = feature_channels(C);
+    PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, cp.L, cp.plan));
+    cp.n_sor.resize(levels);
+    cp.n_outer.resize(levels);
+    for (int k = 0; k < levels; k++) {
+        cp.n_sor[k] = CallPlan::n_sor_at(P, k);
+        cp.n_outer[k] = CallPlan::n_outer_at(P, k);
+    }
+    cp.n_sor_max = cp.n_sor[levels - 1];
+    cp.slots = CallPlan::slots_for(P, levels);
+    // pyramid levels are all derived from level 0 up to 5 levels at ratio 0.75 (src/GaussianPyramid.cpp:95-100); deeper
+    // pyramids chain through finer levels (:101-106)
+    cp.from_level0 = true;
+    for (int i = 1; i < levels; i++) cp.from_level0 = cp.from_level0 && cp.plan[i].src_level == 0;
+    return PAPOF_OK;
+}
+
+int lap_next_epoch(papof_handle* h, hipStream_t stream) {
+    if (++h->lap_epoch >= kLapNone) {
+        if (h->lap_flags_dev) PAPOF_HIP(hipMemsetAsync(h->lap_flags_dev, 0, kLapFlagWords * sizeof(unsigned), stream));
+        h->lap_epoch = 1u;
+    }
+    return PAPOF_OK;
+}
+
+int fork_prep(papof_handle* h, int levels, bool overlap) {
+    while (h->sync_events.size() < (size_t)levels + 2) {
+        hipEvent_t e;
+        PAPOF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->sync_events.push_back(e);
+    }
+    if (overlap) {
+        PAPOF_HIP(hipEventRecord(h->sync_events[levels + 1], h->stream));
+        PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->sync_events[levels + 1], 0));
     }
     return PAPOF_OK;
 }
@@ -210,7 +261,7 @@ struct SolveBuffers {
     SorPlanes sp;
     SorPlanes sp_tiny{};  // exact order: row-major operands of the levels small enough for k_sor_tiny (sor.hip), else unused
     // the reference's non-default branches (unreachable from its Python entry point; papof_params::interpolation /
-    // noise_model): derivative planes of the frame-2 features for in-loop bicubic warping (src/OpticalFlow.cpp:517-521),
+    // noise_model): derivative planes {-.5, 0, .5} of the frame-2 features for in-loop bicubic warping (src/Image.h:2587-2595),
     // and the Gaussian-mixture parameters + reduction scratch (:359-367, :539-591)
     double *bgx = nullptr, *bgy = nullptr, *bgxy = nullptr;
     double *gm = nullptr, *gm_scratch = nullptr;
@@ -257,12 +308,6 @@ int alloc_branch_buffers(papof_handle* h, Arena& A, int H, int W, int fc, int in
     return A.overflow ? PAPOF_ENOMEM : PAPOF_OK;
 }
 
-// derivative planes {-.5, 0, .5} of the frame-2 features of a level (Image::warpImageBicubicRef, src/Image.h:2587-2595)
-int bicubic_planes(papof_handle* h, const double* f2, int H, int W, int fc, SolveBuffers& B) {
-    PAPOF_TRY(central3_planes(h, f2, B.bgx, B.bgy, B.bgxy, H, W, fc));
-    return PAPOF_OK;
-}
-
 // The Laplacian-noise guard.  After every outer iteration the reference estimates, per channel, the mean of |Im1 - warpIm2|
 // over its samples in (0, 1e6) (estLaplacianNoise, src/OpticalFlow.cpp:594-639; 0.001 when there is none) and, in the next
 // linear system, leaves psi of a channel at 0 while that mean is below 1E-20 (:399-400 on the Psi_1st reset at :333).  No
@@ -305,120 +350,140 @@ struct LapGuard {
     }
 };
 
+// What smooth_flow() below solves: one level, with its frames, sizes and schedule
+struct LevelSolve {
+    SolveBuffers& B;
+    const double *f1 = nullptr, *f2 = nullptr;  // the level's features of the two frames
+    double* warp = nullptr;                     // frame 2's, warped at the flow
+    int H = 0, W = 0, fc = 0;
+    double alpha = 0, omega = 0;
+    int n_outer = 0, n_inner = 0, n_sor = 0, mode = PAPOF_SOR_EXACT;
+    const double* im1s_ready = nullptr;  // the smoothed frame 1, prepared ahead by flow_pass (else it is smoothed here)
+    bool final_warp = true;              // false: skip the re-warp behind the level's LAST update (nobody reads it)
+    // cleared progress counters of the call's solves (solve i of this level: counters->solve(h, level, i)), or null
+    const SolveCounters* counters = nullptr;
+    // where the LAST update writes the flow instead of the other pair of planes (the caller's result buffers)
+    double *out_u = nullptr, *out_v = nullptr;
+    // nobody but getDxs' smoothing reads the warped frame 2 (default branches, caller = flow_pass): it is evaluated inside the
+    // smoothing kernel from (u, v) and never written -- `warp` is then neither read nor written here
+    bool fold_warp = false;
+    LapGuard* lg = nullptr;
+    int level = 0;
+};
+
+// Phase5_SOR is the solver kernels' own duration (the roofline of the dominant kernel is priced on it): the events are
+// recorded by sor_solve() right around its kernel(s), BEHIND the memset nodes that prepare a solve, which therefore still
+// count as Phase4.  `prog`: the solve's cleared counters, or null (it clears its own).
+static int marked_solve(papof_handle* h, PhaseClock& clk, unsigned* prog, SorPlanes& SP, const LevelSolve& s) {
+    h->sor_mark = [](void* c, int on) {
+        static_cast<PhaseClock*>(c)->phase(on ? PAPOF_T_PHASE5_SOR : PAPOF_T_PHASE6_UPDATE);
+    };
+    h->sor_mark_ctx = &clk;
+    h->sor_prog_next = prog;
+    const int rc = sor_solve(h, SP, s.H, s.W, s.alpha, s.omega, s.n_sor, s.mode);
+    h->sor_prog_next = nullptr;
+    h->sor_mark = nullptr;
+    h->sor_mark_ctx = nullptr;
+    return rc;
+}
+
 // OpticalFlow::SmoothFlowSOR (src/OpticalFlow.cpp:238-536) for one level, everything on the device.
 // genInImageMask (:278) does not influence the results (the mask is never read) and is not executed;
 // estLaplacianNoise (:530) only feeds a `< 1e-20` guard: see LapGuard above.
 // (u, v) and (ua, va) are two pairs of planes: every outer iteration writes the updated flow into the other pair (its
 // update kernel also reads the neighbours' old values, for phi) and the references are swapped -- on return `u`, `v` name
 // the planes that hold the result.
-int smooth_flow(papof_handle* h, const double* f1, const double* f2, double* warp, double*& u, double*& v, double*& ua,
-                double*& va, int H, int W, int fc, double alpha, int n_outer, int n_inner, int n_sor, double omega,
-                int mode, SolveBuffers& B, PhaseClock& clk, const double* im1s_ready = nullptr,
-                bool final_warp = true, unsigned* prog = nullptr, size_t prog_per_solve = 0, double* out_u = nullptr,
-                double* out_v = nullptr, bool fold_warp = false, LapGuard* lg = nullptr, int level = 0) {
-    // fold_warp: nobody but getDxs' smoothing reads the warped frame 2 (default branches, caller = flow_device): it is
-    // evaluated inside the smoothing kernel from (u, v) and never written -- `warp` is then neither read nor written here
-    // prog: cleared progress counters of this level's solves (solve i: prog + i * prog_per_solve), or null;
-    // out_u / out_v: where the LAST update writes the flow instead of the other pair of planes (the caller's result buffers)
+int smooth_flow(papof_handle* h, const LevelSolve& s, PhaseClock& clk, double*& u, double*& v, double*& ua, double*& va) {
+    SolveBuffers& B = s.B;
     const Taps g = smooth5_taps();
     int solve_idx = 0;
     // exact order on a plane small enough to be solved inside one workgroup: row-major operands + k_sor_tiny (sor.hip)
-    const bool tiny = mode == PAPOF_SOR_EXACT && B.sp_tiny.phi && sor_tiny_fits(h, H, W, n_sor);
+    const bool tiny = s.mode == PAPOF_SOR_EXACT && B.sp_tiny.phi && sor_tiny_fits(h, s.H, s.W, s.n_sor);
     SorPlanes& SP = tiny ? B.sp_tiny : B.sp;
-    const double* im1s = im1s_ready;  // smoothed frame 1: constant within the level (prepared ahead by flow_device)
+    const double* im1s = s.im1s_ready;  // smoothed frame 1: constant within the level
     if (!im1s) {
         clk.phase(PAPOF_T_PHASE1_GENERATE);
-        PAPOF_TRY(filter_hv(h, f1, B.im1s, B.tmp, H, W, fc, g, g));
+        PAPOF_TRY(filter_hv(h, s.f1, B.im1s, B.tmp, s.H, s.W, s.fc, g, g));
         im1s = B.im1s;
     }
     // ONE kernel from the flow to the linear system (k_flow_system) where it applies: default branches, exact-order layout
     const char* const fused_sw = std::getenv("PAPOF_FUSED_SYSTEM");  // A/B switch, and how the tests reach the pair of kernels
     const bool fused_env = !(fused_sw && fused_sw[0] == '0');
     // (a one-block level keeps the pair of kernels while the guard collects proofs: their exhaustive check needs ONE block)
-    const bool fused_system = fused_env && fold_warp && n_inner == 1 && !B.gm && (fc == 5 || fc == 3) &&
-                              !(lg && lg->guard()) && !(lg && lg->on && lap_one_block_level(H, W));
-    for (int count = 0; count < n_outer; count++) {
+    const bool fused_system = fused_env && s.fold_warp && s.n_inner == 1 && !B.gm && (s.fc == 5 || s.fc == 3) &&
+                              !(s.lg && s.lg->guard()) && !(s.lg && s.lg->on && lap_one_block_level(s.H, s.W));
+    for (int count = 0; count < s.n_outer; count++) {
         clk.phase(fused_system ? kTimerFused : (int)PAPOF_T_PHASE1_GENERATE);
         if (fused_system)
-            PAPOF_TRY(flow_system(h, f1, f2, u, v, im1s, H, W, fc, alpha, omega, SP,
-                                  lg && count > 0 ? lg->wit(lg->slot - 1) : nullptr));
-        else if (fold_warp)
+            PAPOF_TRY(flow_system(h, s.f1, s.f2, u, v, im1s, s.H, s.W, s.fc, s.alpha, s.omega, SP,
+                                  s.lg && count > 0 ? s.lg->wit(s.lg->slot - 1) : nullptr));
+        else if (s.fold_warp)
             // warp + both passes + blend + imdt; the warp at the flow the previous iteration left is what that iteration's
             // noise estimate is about: its witnesses are taken here (LapGuard)
-            PAPOF_TRY(warp_smooth_blend(h, f1, f2, u, v, im1s, B.blend, B.imdt, H, W, fc,
-                                        lg && count > 0 && !B.gm ? lg->wit(lg->slot - 1) : nullptr,
+            PAPOF_TRY(warp_smooth_blend(h, s.f1, s.f2, u, v, im1s, B.blend, B.imdt, s.H, s.W, s.fc,
+                                        s.lg && count > 0 && !B.gm ? s.lg->wit(s.lg->slot - 1) : nullptr,
                                         B.phi));  // ... and phi of the flow as it stands (Phase2, :295-331), by the way
         else
-            PAPOF_TRY(smooth_hv_blend(h, warp, im1s, B.blend, B.imdt, H, W, fc));  // both passes + blend + imdt, fused
+            PAPOF_TRY(smooth_hv_blend(h, s.warp, im1s, B.blend, B.imdt, s.H, s.W, s.fc));  // both passes + blend + imdt, fused
         // inner fixed-point iterations (src/OpticalFlow.cpp:290-506): after the first one, phi is taken at u + du and
         // psi at imdt + imdx*du + imdy*dv with the increment of the previous solve; the solve itself restarts at 0
-        for (int hh = 0; hh < n_inner; hh++) {
+        for (int hh = 0; hh < s.n_inner; hh++) {
             const SorPlanes* prev = hh == 0 ? nullptr : &SP;
             // phi (Phase2): of the level's initial flow, and inside further inner iterations (at u + du), by its own kernel;
             // for every later outer iteration the previous iteration's update kernel has written it already
-            if ((count == 0 && !fold_warp) || hh > 0) {  // (fold_warp: warp_smooth_blend has written phi of (u, v))
+            if ((count == 0 && !s.fold_warp) || hh > 0) {  // (fold_warp: warp_smooth_blend has written phi of (u, v))
                 clk.phase(PAPOF_T_PHASE2_DERIVATIVES);
-                PAPOF_TRY(compute_phi(h, u, v, prev, B.phi, H, W));
+                PAPOF_TRY(compute_phi(h, u, v, prev, B.phi, s.H, s.W));
             }
             // psi (Phase3, src/OpticalFlow.cpp:377-406) and the linear system (Phase4, :414-448) are ONE kernel here: its
             // time is recorded under Phase4 and apportioned between the two timers when they are collected (kPsiShare)
             if (!fused_system) clk.phase(PAPOF_T_PHASE4_LINEARSYSTEM);
             if (!fused_system)
-                PAPOF_TRY(assemble_system(h, B.blend, B.imdt, B.phi, u, v, H, W, fc, alpha, omega, SP, nullptr, nullptr,
-                                          prev, nullptr, B.gm, lg ? lg->guard() : nullptr));
-            // Phase5_SOR is the solver kernels' own duration (the roofline of the dominant kernel is priced on it): the
-            // events are recorded by sor_solve() right around its kernel(s), BEHIND the memset nodes that prepare a solve,
-            // which therefore still count as Phase4
-            h->sor_mark = [](void* c, int on) {
-                static_cast<PhaseClock*>(c)->phase(on ? PAPOF_T_PHASE5_SOR : PAPOF_T_PHASE6_UPDATE);
-            };
-            h->sor_mark_ctx = &clk;
-            h->sor_prog_next = prog ? prog + (size_t)solve_idx * prog_per_solve : nullptr;
+                PAPOF_TRY(assemble_system(h, B.blend, B.imdt, B.phi, u, v, s.H, s.W, s.fc, s.alpha, s.omega, SP, nullptr, nullptr,
+                                          prev, nullptr, B.gm, s.lg ? s.lg->guard() : nullptr));
+            PAPOF_TRY(marked_solve(h, clk, s.counters ? s.counters->solve(h, s.level, (size_t)solve_idx) : nullptr, SP, s));
             solve_idx++;
-            const int rc_solve = sor_solve(h, SP, H, W, alpha, omega, n_sor, mode);
-            h->sor_prog_next = nullptr;
-            h->sor_mark = nullptr;
-            h->sor_mark_ctx = nullptr;
-            PAPOF_TRY(rc_solve);
         }
         // Phase6 (opened by the solver's end mark): u += du, v += dv and the re-warp of frame 2 (:513-521)
         // the next outer iteration's phi, fused in -- unless its warp_smooth_blend writes it (fold_warp: there it costs six
         // row-contiguous loads per pixel in a fifth of the blocks; here, three scattered reads of the increment instead of one)
-        double* const phi_next = count + 1 < n_outer && !fold_warp ? B.phi : nullptr;
+        double* const phi_next = count + 1 < s.n_outer && !s.fold_warp ? B.phi : nullptr;
         // the re-warp after the LAST outer iteration of a level (:516) is read by nobody when the caller is flow_device (the
         // next level warps anew, the result is the bicubic warp of the originals): final_warp = false skips it
-        const bool rewarp = !fold_warp && !B.bgx && (final_warp || count + 1 < n_outer || B.gm);
+        const bool rewarp = !s.fold_warp && !B.bgx && (s.final_warp || count + 1 < s.n_outer || B.gm);
         // witnesses of the Laplacian-noise guard (LapGuard); the bicubic branch has no sampled warp: it runs the exact pass
         // -- and taken by the next iteration's warp_smooth_blend where there is one on this level
-        const bool wit_later = fold_warp && count + 1 < n_outer;
+        const bool wit_later = s.fold_warp && count + 1 < s.n_outer;
         // (a one-block level gets the exhaustive check of lap_small_check() behind its last update instead of samples)
-        const bool wit_small = fold_warp && !wit_later && lap_one_block_level(H, W);
-        unsigned* const wit = lg && !B.gm && !B.bgx && !wit_later && !wit_small ? lg->wit(lg->slot) : nullptr;
-        if (out_u && out_v && count + 1 == n_outer) {  // the level's result goes straight to the caller's buffers
-            PAPOF_TRY(update_warp_phi(h, SP, u, v, out_u, out_v, f1, f2, warp, phi_next, H, W, fc, rewarp, 0, -1, wit));
-            u = out_u;
-            v = out_v;
+        const bool wit_small = s.fold_warp && !wit_later && lap_one_block_level(s.H, s.W);
+        unsigned* const wit = s.lg && !B.gm && !B.bgx && !wit_later && !wit_small ? s.lg->wit(s.lg->slot) : nullptr;
+        // the level's last update writes straight to the caller's buffers where there are any, every other one to the other pair
+        const bool to_caller = s.out_u && s.out_v && count + 1 == s.n_outer;
+        PAPOF_TRY(update_warp_phi(h, SP, u, v, to_caller ? s.out_u : ua, to_caller ? s.out_v : va, s.f1, s.f2, s.warp, phi_next,
+                                  s.H, s.W, s.fc, rewarp, 0, -1, wit));
+        if (to_caller) {
+            u = s.out_u;
+            v = s.out_v;
         } else {
-            PAPOF_TRY(update_warp_phi(h, SP, u, v, ua, va, f1, f2, warp, phi_next, H, W, fc, rewarp, 0, -1, wit));
             std::swap(u, ua);
             std::swap(v, va);
         }
         if (B.bgx)  // interpolation == Bicubic: warpImageBicubicRef + threshold() on the feature planes
-            PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, u, v, warp, H, W, fc, nullptr, true, true));
-        if (lg && lg->on && !B.gm && wit_small && lg->wit(lg->slot))
-            PAPOF_TRY(lap_small_check(h, f1, f2, u, v, H, W, fc, lg->wit(lg->slot)));
-        if (lg && lg->on && !B.gm) {
-            lg->slot_level.push_back(level);
-            lg->slot_channels.push_back(fc);
-            lg->slot++;
-            if (lg->exact) {  // :530, on the flow just updated
+            PAPOF_TRY(bicubic_warp(h, s.f1, s.f2, B.bgx, B.bgy, B.bgxy, u, v, s.warp, s.H, s.W, s.fc, nullptr, true, true));
+        if (s.lg && s.lg->on && !B.gm && wit_small && s.lg->wit(s.lg->slot))
+            PAPOF_TRY(lap_small_check(h, s.f1, s.f2, u, v, s.H, s.W, s.fc, s.lg->wit(s.lg->slot)));
+        if (s.lg && s.lg->on && !B.gm) {
+            s.lg->slot_level.push_back(s.level);
+            s.lg->slot_channels.push_back(s.fc);
+            s.lg->slot++;
+            if (s.lg->exact) {  // :530, on the flow just updated
                 if (B.bgx)
-                    PAPOF_TRY(est_laplacian_noise(h, f1, warp, nullptr, nullptr, H, W, fc, lg->lap, lg->scratch));
+                    PAPOF_TRY(est_laplacian_noise(h, s.f1, s.warp, nullptr, nullptr, s.H, s.W, s.fc, s.lg->lap, s.lg->scratch));
                 else
-                    PAPOF_TRY(est_laplacian_noise(h, f1, f2, u, v, H, W, fc, lg->lap, lg->scratch));
+                    PAPOF_TRY(est_laplacian_noise(h, s.f1, s.f2, u, v, s.H, s.W, s.fc, s.lg->lap, s.lg->scratch));
             }
         }
-        if (B.gm) PAPOF_TRY(est_gaussian_mixture(h, f1, warp, H, W, fc, B.gm, B.gm_scratch));  // :524-528
+        if (B.gm) PAPOF_TRY(est_gaussian_mixture(h, s.f1, s.warp, s.H, s.W, s.fc, B.gm, B.gm_scratch));  // :524-528
     }
     clk.phase(-1);
     return PAPOF_OK;
@@ -457,380 +522,335 @@ bool seq_matches(const papof_handle* h, int H, int W, int C, int levels, double 
            q.arena_base == h->arena.base && need <= h->arena.cap;
 }
 
-// The whole call on device-resident buffers: ONE pass (flow_device below runs it once, or twice: LapGuard).
-// init: the caller's initial flow of this pair (papof_flow_batch_tensor_init), or NULL: zero.
-int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, int H, int W, int C, int levels,
-              const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing, LapGuard* lg,
-              const papof_tensor* init = nullptr) {
-    const double t_entry = wall();
-    PAPOF_TRY(check_params(P, levels));
-    double ratio = P.ratio;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;
-    std::vector<Level> L;
-    std::vector<PyrPlan> plan;
-    PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, L, plan));
-    const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
-    const size_t need = arena_bytes_for(H, W, C, levels, n_sor_max, P.ratio);
-    if (op == kSeqNext && !seq_matches(h, H, W, C, levels, ratio, need)) {
-        g_last_error = "sequence push does not continue the primed sequence (shape, levels, ratio or arena changed)";
-        return PAPOF_EINVAL;
-    }
-    const int slot1 = op == kSeqNext ? h->seq.slot : 0;  // pyramid slot of frame 1
-    h->seq.valid = false;  // re-established below once the kept pyramid is complete
-    PAPOF_TRY(ensure_arena(h, need));
-    Arena& A = h->arena;
-    A.off = 0;
-    A.overflow = false;
-    h->events_used = 0;
-    const size_t np0 = (size_t)H * W;
-    const int fc = feature_channels(C);
-    double tm[PAPOF_N_TIMERS + 1];  // + kTimerFused (flow_internal.h)
-    std::memset(tm, 0, sizeof tm);
-    const size_t tm_bytes = PAPOF_N_TIMERS * sizeof(double);  // what the caller gets
-    const auto keep_seq = [&](int slot) {
-        h->seq.valid = true;
-        h->seq.h = H;
-        h->seq.w = W;
-        h->seq.c = C;
-        h->seq.levels = levels;
-        h->seq.ratio = ratio;
-        h->seq.slot = slot;
-        h->seq.arena_base = A.base;
-    };
-    // All ten reference timers (src/OpticalFlow.cpp:850-860) are ALWAYS measured, with HIP events recorded on the streams
-    // (no synchronisation): `clk` on the main stream, `pclk` on the preparation stream.  With phase_timing == 0 the two
-    // streams overlap, so Construction / Allocation / PostProcessing (preparation stream) run beside the solver phases
-    // and the ten values add up to more than the total; phase_timing == 1 runs everything on one stream.
-    PhaseClock clk{h, true};
-    PhaseClock pclk{h, true};
-    PhaseClock total{h, true};
-    clk.only_sor = pclk.only_sor = (!h->phase_events && P.phase_timing == 0) || P.phase_timing == 2;
+// ---- ONE pass of the whole call on device-resident buffers (flow_device below runs it once, or twice: LapGuard), as a list
+// of steps over one state: the arguments, the plan, the buffers carved from the arena, the two streams and the clocks.
+struct FlowPass {
+    papof_handle* h;
+    const FrameIn &fa, &fb;
+    SeqOp op;
+    int H, W, C;
+    const papof_params& P;
+    double *d_vx, *d_vy, *d_warp;
+    LapGuard* lg;
+    const papof_tensor* init;  // the caller's initial flow of this pair (papof_flow_batch_tensor_init), or NULL: zero
+    CallPlan cp;
+    int slot1 = 0;  // pyramid slot of frame 1
+    // -- the arena, in allocation order
+    double *tmp_a = nullptr, *tmp_b = nullptr;  // the pyramid's filter temporaries
+    std::vector<double*> F1, F2, S1;            // per level: the features of both frames, the smoothed features of frame 1
+    double *gx = nullptr, *gy = nullptr, *gxy = nullptr;  // frame 2's central differences for the final warp (src/Image.h:2590-2594)
+    double *prep_tmp = nullptr, *warp = nullptr;  // (prep_tmp is allocated ahead of gx)
+    // the flow lives in two PAIRS of planes (the update of an outer iteration writes the other pair); within a pair v follows
+    // u at the pitch of the level in work, so that the up-sampling of (u, v) is one launch and their first clear one fill
+    double *u = nullptr, *v = nullptr, *u2 = nullptr, *v2 = nullptr;
+    SolveBuffers B;
+    bool exact = false;      // exact-order solves: they have progress counters
+    SolveCounters counters;  // ... of every solve of the call
+    // -- streams
+    bool overlap = false;  // the preparation runs on a stream of its own
+    bool hostio = false;   // ... and the frames come from host buffers over the copy stream (papof_handle::HostIO)
+    hipStream_t main_stream = nullptr, prep = nullptr;
+    // -- clocks.  All ten reference timers (src/OpticalFlow.cpp:850-860) are ALWAYS measured (no synchronisation): `clk` on
+    // the main stream, `pclk` on the preparation stream.  With phase_timing == 0 the two streams overlap, so Construction /
+    // Allocation / PostProcessing (preparation stream) run beside the solver phases and the ten values add up to more than
+    // the total; phase_timing == 1 runs everything on one stream.
+    PhaseClock clk, pclk, total;
+};
+
+static void keep_seq(const FlowPass& S, int slot) {
+    S.h->seq = {.valid = true, .h = S.H, .w = S.W, .c = S.C, .levels = S.cp.levels, .slot = slot, .ratio = S.cp.ratio,
+                .arena_base = S.h->arena.base};
+}
+
+static void start_clocks(FlowPass& S) {
+    papof_handle* h = S.h;
+    S.clk = S.pclk = S.total = PhaseClock{h, true};
+    S.clk.only_sor = S.pclk.only_sor = (!h->phase_events && S.P.phase_timing == 0) || S.P.phase_timing == 2;
     h->sor_launches = 0;
     h->sor_log.clear();
-    clk.stamps = true;  // the main stream's phase boundaries are in-kernel stamps, not events (flow_internal.h)
+    S.clk.stamps = true;  // the main stream's phase boundaries are in-kernel stamps, not events (flow_internal.h)
     h->stamps_used = 0;
     h->next_stamp = nullptr;
     h->stamp_stream = h->stream;  // only launches on the main stream take phase stamps (take_stamp)
+    S.total.phase(PAPOF_T_TOTAL);
+}
 
-    total.phase(PAPOF_T_TOTAL);
-    for (int i = 0; i < levels; i++) {  // the two pyramid slots: always the first allocations, at fixed offsets
+// the two pyramid slots: always the first allocations, at fixed offsets (a sequence keeps one of them from call to call)
+static int carve_pyramids(FlowPass& S) {
+    Arena& A = S.h->arena;
+    for (Level& l : S.cp.L) {
         double* slot[2];
-        slot[0] = A.f64((size_t)L[i].w * L[i].h * C);
-        slot[1] = A.f64((size_t)L[i].w * L[i].h * C);
-        L[i].p1 = slot[slot1];
-        L[i].p2 = slot[slot1 ^ 1];
+        slot[0] = A.f64((size_t)l.w * l.h * S.C);
+        slot[1] = A.f64((size_t)l.w * l.h * S.C);
+        l.p1 = slot[S.slot1];
+        l.p2 = slot[S.slot1 ^ 1];
     }
-    double* tmp_a = A.f64(np0 * C);
-    double* tmp_b = A.f64(np0 * C);
-    if (A.overflow) return PAPOF_ENOMEM;
-    if (op == kSeqPrime) {
-        PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
-        PAPOF_TRY(build_pyramid(h, L, plan, C, false, tmp_a, tmp_b));
-        PAPOF_HIP(hipStreamSynchronize(h->stream));
-        keep_seq(slot1);
-        if (timing) std::memset(timing, 0, tm_bytes);
-        return PAPOF_OK;
-    }
+    const size_t np0 = (size_t)S.H * S.W;
+    S.tmp_a = A.f64(np0 * S.C);
+    S.tmp_b = A.f64(np0 * S.C);
+    return A.overflow ? PAPOF_ENOMEM : PAPOF_OK;
+}
 
-    // Everything that does not depend on the flow -- the pyramids, and per level the features of both frames
-    // (src/OpticalFlow.cpp:797-798) and the smoothed features of frame 1 (getDxs, :84-90) -- is PREPARED on a second
-    // stream, coarsest level first, while the main stream already solves the coarse levels: their SOR solves are
-    // dependency-latency bound and leave most of the chip idle.  One event per level orders the two streams.  With all
-    // ten reference timers requested the call runs on one stream so that the phases do not overlap.
-    std::vector<double*> F1(levels), F2(levels), S1(levels);
+static int carve_buffers(FlowPass& S) {
+    papof_handle* h = S.h;
+    Arena& A = h->arena;
+    const CallPlan& cp = S.cp;
+    const int levels = cp.levels, fc = cp.fc;
+    const size_t np0 = (size_t)S.H * S.W;
+    S.F1.resize(levels);
+    S.F2.resize(levels);
+    S.S1.resize(levels);
     for (int k = 0; k < levels; k++) {
-        const size_t n = (size_t)L[k].w * L[k].h * fc;
-        F1[k] = A.f64(n);
-        F2[k] = A.f64(n);
-        S1[k] = A.f64(n);
+        const size_t n = (size_t)cp.L[k].w * cp.L[k].h * fc;
+        S.F1[k] = A.f64(n);
+        S.F2[k] = A.f64(n);
+        S.S1[k] = A.f64(n);
     }
-    double* prep_tmp = A.f64(np0 * fc);
-    double* gx = A.f64(np0 * C);  // central differences of frame 2 for the final bicubic warp (src/Image.h:2590-2594)
-    double* gy = A.f64(np0 * C);
-    double* gxy = A.f64(np0 * C);
-    double* warp = A.f64(np0 * fc);
-    // the flow lives in two PAIRS of planes (the update of an outer iteration writes the other pair); within a pair v follows
-    // u at the pitch of the level in work, so that the up-sampling of (u, v) is one launch and their first clear one fill
-    double* u = A.f64(2 * np0);
-    double* v = u ? u + np0 : nullptr;
-    double* u2 = A.f64(2 * np0);
-    double* v2 = u2 ? u2 + np0 : nullptr;
-    SolveBuffers B;
-    {
-        const int rc_alloc = alloc_solve_buffers(A, H, W, fc, P.sor_mode, n_sor_max, B);
-        if (rc_alloc != PAPOF_OK || A.overflow) return rc_alloc != PAPOF_OK ? rc_alloc : PAPOF_ENOMEM;
-    }
-    PAPOF_TRY(alloc_branch_buffers(h, A, H, W, fc, P.interpolation, P.noise_model, B));
-
+    S.prep_tmp = A.f64(np0 * fc);
+    S.gx = A.f64(np0 * S.C);
+    S.gy = A.f64(np0 * S.C);
+    S.gxy = A.f64(np0 * S.C);
+    S.warp = A.f64(np0 * fc);
+    S.u = A.f64(2 * np0);
+    S.v = S.u ? S.u + np0 : nullptr;
+    S.u2 = A.f64(2 * np0);
+    S.v2 = S.u2 ? S.u2 + np0 : nullptr;
+    PAPOF_TRY(alloc_solve_buffers(A, S.H, S.W, fc, S.P.sor_mode, cp.n_sor_max, S.B));  // (ENOMEM when the arena overflowed)
+    PAPOF_TRY(alloc_branch_buffers(h, A, S.H, S.W, fc, S.P.interpolation, S.P.noise_model, S.B));
     // Exact-order path: the progress counters of EVERY solve of the call are cleared at once on the preparation stream (one
     // fill instead of one per solve in front of each solver launch on the main stream).  [Also tried: one set of coefficient
     // planes per level, zeroed ahead on the preparation stream instead of sor_reset_planes() on the main stream at the start
     // of each level -- 0.2 ms SLOWER per 1080p pair (same-box A/B 11.83 vs 11.62 ms, all of it in the solver kernels): the
     // fills in front of a level leave the planes in the Infinity Cache, exactly as the (du, dv) clear in front of a solve.]
-    struct LevelCounters {
-        size_t prog_off = 0, prog_per = 0;  // offset (unsigneds) of the level's first solve, stride per solve
-    };
-    std::vector<LevelCounters> LP(levels);
-    size_t prog_total = 0;
-    const bool exact = P.sor_mode == PAPOF_SOR_EXACT;
-    if (exact) {
-        for (int k = 0; k < levels; k++) {
-            LP[k].prog_per = sor_counters_words(L[k].h, L[k].w, P.n_sor + k * P.n_sor_per_level);
-            LP[k].prog_off = prog_total;
-            prog_total += LP[k].prog_per * (size_t)((P.n_outer + k * P.n_outer_per_level) * P.n_inner);
-        }
-        PAPOF_TRY(sor_counters_ensure(h, prog_total));
+    S.exact = S.P.sor_mode == PAPOF_SOR_EXACT;
+    if (S.exact) {
+        S.counters = SolveCounters(cp, [&](int k) { return sor_counters_words(cp.L[k].h, cp.L[k].w, cp.n_sor[k]); },
+                                   (size_t)S.P.n_inner);
+        PAPOF_TRY(sor_counters_ensure(h, S.counters.total));
     }
+    return PAPOF_OK;
+}
 
-    const bool overlap = h->overlap_prep && P.phase_timing != 1 && h->prep_stream != nullptr;
-    hipStream_t const main_stream = h->stream, prep = overlap ? h->prep_stream : h->stream;
-    while (h->sync_events.size() < (size_t)levels + 2) {
-        hipEvent_t e;
-        PAPOF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->sync_events.push_back(e);
-    }
-    struct StreamSwap {  // the launch wrappers enqueue on h->stream
-        papof_handle* h;
-        hipStream_t saved;
-        StreamSwap(papof_handle* hh, hipStream_t s) : h(hh), saved(hh->stream) { h->stream = s; }
-        ~StreamSwap() { h->stream = saved; }
-    };
-    // pyramid levels coarsest first when every level is derived from level 0 (<= 5 levels at ratio 0.75,
-    // src/GaussianPyramid.cpp:95-100); deeper pyramids chain through finer levels (:101-106): build those in order
-    bool from_level0 = true;
-    for (int i = 1; i < levels; i++) from_level0 = from_level0 && plan[i].src_level == 0;
+// ---- The preparation.  Everything that does not depend on the flow -- the pyramids, and per level the features of both
+// frames (src/OpticalFlow.cpp:797-798) and the smoothed features of frame 1 (getDxs, :84-90) -- is PREPARED on a second
+// stream, coarsest level first, while the main stream already solves the coarse levels: their SOR solves are
+// dependency-latency bound and leave most of the chip idle.  One event per level orders the two streams.  With all ten
+// reference timers requested the call runs on one stream so that the phases do not overlap.
+// The pieces (each enqueues on h->stream, which prepare() below points at the preparation stream):
+static bool prep_kept(const FlowPass& S, int second) { return second == 0 && S.op == kSeqNext; }  // a push keeps frame 1's pyramid
+static int prep_build_level(FlowPass& S, int i, int second) {  // level i of frame 1 (second == 0) or frame 2
+    if (i == 0 || prep_kept(S, second)) return PAPOF_OK;
+    const std::vector<Level>& L = S.cp.L;
+    const PyrPlan& q = S.cp.plan[i];
+    const double* src = second ? L[q.src_level].p2 : L[q.src_level].p1;
+    return smooth_and_resize(S.h, src, second ? L[i].p2 : L[i].p1, S.tmp_a, S.tmp_b, q, S.C, L[i].h, L[i].w);
+}
+static int prep_level_ready(FlowPass& S, int k) {  // the main stream may enter level k (k == levels: the final warp)
+    S.pclk.phase(-1);
+    if (S.overlap) PAPOF_HIP(hipEventRecord(S.h->sync_events[k], S.prep));
+    return PAPOF_OK;
+}
+// The share of the frames [first, last) of the pair (0: frame 1, 1: frame 2): planarise, the pyramid, and level by level,
+// coarsest first, the features (`smooth`: and the smoothing of frame 1's; `ready`: and the level's event).  The pyramid
+// levels are built inside that loop, coarsest first, when every level is derived from level 0; `chained`: all of them ahead,
+// in order (a pyramid that chains through finer levels, and frame 1's in the host order).
+static int prep_frames(FlowPass& S, int first, int last, bool chained, bool smooth, bool ready) {
+    const std::vector<Level>& L = S.cp.L;
+    const int levels = S.cp.levels;
     const Taps g5 = smooth5_taps();
-    const auto build_level = [&](int i, int second) -> int {  // level i of frame 1 (second == 0) or frame 2
-        if (i == 0) return PAPOF_OK;
-        const PyrPlan& q = plan[i];
-        const double* src = second ? L[q.src_level].p2 : L[q.src_level].p1;
-        double* dst = second ? L[i].p2 : L[i].p1;
-        return smooth_and_resize(h, src, dst, tmp_a, tmp_b, q, C, L[i].h, L[i].w);
-    };
-    const auto prepare = [&]() -> int {
-        StreamSwap on_prep(h, prep);
-        pclk.phase(PAPOF_T_ALLOCATION);  // the reference's buffers are zero-filled when they are allocated (src/Image.h:518-532)
-        if (exact && !sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
-        pclk.phase(PAPOF_T_CONSTRUCTION);  // src/OpticalFlow.cpp:757-758 (and the wrapper's copies, Coarse2FineFlowWrapper.cpp:23-28)
-        if (op != kSeqNext) PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
-        PAPOF_TRY(load_frame(h, fb, L[0].p2, H, W, C));
-        const int first = op == kSeqNext ? 1 : 0;  // a sequence push keeps frame 1's pyramid
-        if (!from_level0)
-            for (int i = 1; i < levels; i++)
-                for (int second = first; second < 2; second++) PAPOF_TRY(build_level(i, second));
-        for (int k = levels - 1; k >= 0; k--) {
-            if (from_level0) {
-                pclk.phase(PAPOF_T_CONSTRUCTION);
-                for (int second = first; second < 2; second++) PAPOF_TRY(build_level(k, second));
-            }
-            pclk.phase(PAPOF_T_ALLOCATION);  // im2feature is inside the reference's Allocation timer (:797-798)
-            PAPOF_TRY(im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C, lg ? lg->nz(k) : nullptr));
-            PAPOF_TRY(im2feature(h, L[k].p2, F2[k], L[k].h, L[k].w, C, lg ? lg->nz(k) : nullptr));
-            pclk.phase(PAPOF_T_PHASE1_GENERATE);  // smoothing of frame 1: first half of getDxs (:84-90)
-            PAPOF_TRY(filter_hv(h, F1[k], S1[k], prep_tmp, L[k].h, L[k].w, fc, g5, g5));
-            pclk.phase(-1);
-            if (overlap) PAPOF_HIP(hipEventRecord(h->sync_events[k], prep));
+    S.pclk.phase(PAPOF_T_CONSTRUCTION);  // src/OpticalFlow.cpp:757-758 (and the wrapper's copies, Coarse2FineFlowWrapper.cpp:23-28)
+    for (int second = first; second < last; second++)
+        if (!prep_kept(S, second)) PAPOF_TRY(load_frame(S.h, second ? S.fb : S.fa, second ? L[0].p2 : L[0].p1, S.H, S.W, S.C));
+    for (int i = 1; chained && i < levels; i++)
+        for (int second = first; second < last; second++) PAPOF_TRY(prep_build_level(S, i, second));
+    for (int k = levels - 1; k >= 0; k--) {
+        if (!chained) {
+            S.pclk.phase(PAPOF_T_CONSTRUCTION);
+            for (int second = first; second < last; second++) PAPOF_TRY(prep_build_level(S, k, second));
         }
-        pclk.phase(PAPOF_T_POSTPROCESSING);  // derivative planes of the final bicubic warp (src/Image.h:2590-2594)
-        PAPOF_TRY(central3_planes(h, L[0].p2, gx, gy, gxy, H, W, C));
-        pclk.phase(-1);
-        if (overlap) PAPOF_HIP(hipEventRecord(h->sync_events[levels], prep));
-        return PAPOF_OK;
-    };
-    // Host buffers (flow_host): the uploads are queued from HERE, on the copy stream, in an order that lets frame 1's whole
-    // share of the preparation -- planarise, its pyramid, its features and their smoothing on every level -- run while frame
-    // 2 is still crossing PCIe (0.9 ms per 1080p float64 frame); only frame 2's share (coarsest level first, one event per
-    // level) is left when the upload ends, and less streaming work runs beside the coarse levels' solves.  Same kernels, same
-    // inputs: same bits.  [The device-resident call keeps the level-interleaved order above: there the main stream starts
-    // the coarsest level as early as possible.]
-    papof_handle::HostIO& io = h->hostio;
-    const bool hostio = io.active && overlap && h->copy_stream && h->copy_events.size() >= 8;
-    const auto prepare_hostio = [&]() -> int {
-        StreamSwap on_prep(h, prep);
-        hipStream_t const cs = h->copy_stream;
-        pclk.phase(PAPOF_T_ALLOCATION);
-        if (exact && !sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
-        // ---- frame 1: upload (this call may hold the host until the bytes are staged), then its whole share
-        if (io.im1) {
-            PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(fa.d), io.im1, io.nb_in, hipMemcpyHostToDevice, cs));
-            PAPOF_HIP(hipEventRecord(h->copy_events[0], cs));
-            PAPOF_HIP(hipStreamWaitEvent(prep, h->copy_events[0], 0));
+        S.pclk.phase(PAPOF_T_ALLOCATION);  // im2feature is inside the reference's Allocation timer (:797-798)
+        for (int second = first; second < last; second++)
+            PAPOF_TRY(im2feature(S.h, second ? L[k].p2 : L[k].p1, second ? S.F2[k] : S.F1[k], L[k].h, L[k].w, S.C,
+                                 S.lg ? S.lg->nz(k) : nullptr));
+        if (smooth) {
+            S.pclk.phase(PAPOF_T_PHASE1_GENERATE);  // smoothing of frame 1: first half of getDxs (:84-90)
+            PAPOF_TRY(filter_hv(S.h, S.F1[k], S.S1[k], S.prep_tmp, L[k].h, L[k].w, S.cp.fc, g5, g5));
         }
-        pclk.phase(PAPOF_T_CONSTRUCTION);
-        if (op != kSeqNext) {
-            PAPOF_TRY(load_frame(h, fa, L[0].p1, H, W, C));
-            for (int i = 1; i < levels; i++) PAPOF_TRY(build_level(i, 0));
-        }
-        for (int k = levels - 1; k >= 0; k--) {
-            pclk.phase(PAPOF_T_ALLOCATION);
-            PAPOF_TRY(im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C, lg ? lg->nz(k) : nullptr));
-            pclk.phase(PAPOF_T_PHASE1_GENERATE);
-            PAPOF_TRY(filter_hv(h, F1[k], S1[k], prep_tmp, L[k].h, L[k].w, fc, g5, g5));
-        }
-        pclk.phase(-1);
-        // ---- frame 2: upload beside the kernels just queued, then its share, coarsest level first
-        if (io.im2) {
-            PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(fb.d), io.im2, io.nb_in, hipMemcpyHostToDevice, cs));
-            PAPOF_HIP(hipEventRecord(h->copy_events[1], cs));
-            PAPOF_HIP(hipStreamWaitEvent(prep, h->copy_events[1], 0));
-        }
-        pclk.phase(PAPOF_T_CONSTRUCTION);
-        PAPOF_TRY(load_frame(h, fb, L[0].p2, H, W, C));
-        if (!from_level0)
-            for (int i = 1; i < levels; i++) PAPOF_TRY(build_level(i, 1));
-        for (int k = levels - 1; k >= 0; k--) {
-            if (from_level0) {
-                pclk.phase(PAPOF_T_CONSTRUCTION);
-                PAPOF_TRY(build_level(k, 1));
-            }
-            pclk.phase(PAPOF_T_ALLOCATION);
-            PAPOF_TRY(im2feature(h, L[k].p2, F2[k], L[k].h, L[k].w, C, lg ? lg->nz(k) : nullptr));
-            pclk.phase(-1);
-            PAPOF_HIP(hipEventRecord(h->sync_events[k], prep));
-        }
-        pclk.phase(PAPOF_T_POSTPROCESSING);
-        PAPOF_TRY(central3_planes(h, L[0].p2, gx, gy, gxy, H, W, C));
-        pclk.phase(-1);
-        PAPOF_HIP(hipEventRecord(h->sync_events[levels], prep));
-        return PAPOF_OK;
-    };
-    if (io.active && !hostio) {  // the caller left the uploads to this call, which cannot overlap them: plain copies, in order
-        if (io.im1) PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(fa.d), io.im1, io.nb_in, hipMemcpyHostToDevice, main_stream));
-        if (io.im2) PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(fb.d), io.im2, io.nb_in, hipMemcpyHostToDevice, main_stream));
+        if (ready) PAPOF_TRY(prep_level_ready(S, k));
     }
-    if (overlap) {  // the preparation starts after whatever the caller queued on the main stream (the frame uploads)
-        PAPOF_HIP(hipEventRecord(h->sync_events[levels + 1], main_stream));
-        PAPOF_HIP(hipStreamWaitEvent(prep, h->sync_events[levels + 1], 0));
-    }
-    {
-        const int rc = hostio ? prepare_hostio() : prepare();
-        if (rc != PAPOF_OK) {
-            if (overlap) hipStreamSynchronize(prep);
-            return rc;
-        }
-    }
+    return PAPOF_OK;
+}
+static int prep_final_planes(FlowPass& S) {  // derivative planes of the final bicubic warp (src/Image.h:2590-2594)
+    S.pclk.phase(PAPOF_T_POSTPROCESSING);
+    PAPOF_TRY(central3_planes(S.h, S.cp.L[0].p2, S.gx, S.gy, S.gxy, S.H, S.W, S.C));
+    return prep_level_ready(S, S.cp.levels);
+}
+// a frame's upload on the copy stream, the preparation stream behind it (this call may hold the host until the bytes are staged)
+static int prep_upload(FlowPass& S, const void* host, const FrameIn& f, int event) {
+    papof_handle* h = S.h;
+    if (!host) return PAPOF_OK;
+    PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(f.d), host, h->hostio.nb_in, hipMemcpyHostToDevice, h->copy_stream));
+    PAPOF_HIP(hipEventRecord(h->copy_events[event], h->copy_stream));
+    PAPOF_HIP(hipStreamWaitEvent(S.prep, h->copy_events[event], 0));
+    return PAPOF_OK;
+}
 
+// The two orders.  Frames on the device: level-interleaved, both frames per level -- the main stream starts the coarsest level
+// as early as possible.  Host buffers (flow_host): the uploads are queued from HERE, on the copy stream, in an order that lets
+// frame 1's whole share of the preparation -- planarise, its pyramid, its features and their smoothing on every level -- run
+// while frame 2 is still crossing PCIe (0.9 ms per 1080p float64 frame); only frame 2's share (coarsest level first, one event
+// per level) is left when the upload ends, and less streaming work runs beside the coarse levels' solves.  Same kernels, same
+// inputs: same bits.
+static int prepare(FlowPass& S) {
+    StreamSwap on_prep(S.h, S.prep);
+    const bool chained = !S.cp.from_level0;
+    S.pclk.phase(PAPOF_T_ALLOCATION);  // the reference's buffers are zero-filled when they are allocated (src/Image.h:518-532)
+    if (S.exact && !sor_counters_clear(S.h, 0, S.counters.total)) return PAPOF_EDEVICE;
+    if (!S.hostio) {
+        PAPOF_TRY(prep_frames(S, 0, 2, chained, true, true));
+    } else {
+        PAPOF_TRY(prep_upload(S, S.h->hostio.im1, S.fa, 0));
+        PAPOF_TRY(prep_frames(S, 0, 1, true, true, false));
+        S.pclk.phase(-1);
+        PAPOF_TRY(prep_upload(S, S.h->hostio.im2, S.fb, 1));  // beside the kernels just queued
+        PAPOF_TRY(prep_frames(S, 1, 2, chained, false, true));
+    }
+    return prep_final_planes(S);
+}
+
+static int fork_and_prepare(FlowPass& S) {
+    papof_handle* h = S.h;
+    const papof_handle::HostIO& io = h->hostio;
+    S.overlap = h->overlap_prep && S.P.phase_timing != 1 && h->prep_stream != nullptr;
+    S.main_stream = h->stream;
+    S.prep = S.overlap ? h->prep_stream : h->stream;
+    S.hostio = io.active && S.overlap && h->copy_stream && h->copy_events.size() >= 8;
+    if (io.active && !S.hostio) {  // the caller left the uploads to this call, which cannot overlap them: plain copies, in order
+        if (io.im1) PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(S.fa.d), io.im1, io.nb_in, hipMemcpyHostToDevice, S.main_stream));
+        if (io.im2) PAPOF_HIP(hipMemcpyAsync(const_cast<void*>(S.fb.d), io.im2, io.nb_in, hipMemcpyHostToDevice, S.main_stream));
+    }
+    PAPOF_TRY(fork_prep(h, S.cp.levels, S.overlap));
+    const int rc = prepare(S);
+    if (rc != PAPOF_OK && S.overlap) hipStreamSynchronize(S.prep);
+    return rc;
+}
+
+// The flow the level starts from, and frame 2's features warped at it (src/OpticalFlow.cpp:801-816; `pw`, `ph`: the
+// coarser level's size).  On return (u, v) and the free pair (u2, v2) are at this level's pitch.
+static int enter_level(FlowPass& S, int k, int pw, int ph, bool fold_warp) {
+    papof_handle* h = S.h;
+    const int lw = S.cp.L[k].w, lh = S.cp.L[k].h, fc = S.cp.fc;
+    const size_t np = (size_t)lw * lh;
+    const double *f1 = S.F1[k], *f2 = S.F2[k];
+    SolveBuffers& B = S.B;
+    const bool coarsest = k == S.cp.levels - 1;
+    if (coarsest && S.init) {  // the caller's initial flow (reduce_init; u, u2 and warp are free until here),
+        // and the coarsest level entered as every finer one is: frame 2's features warped at (u, v)
+        double* r = nullptr;
+        PAPOF_TRY(reduce_init(h, S.init, nullptr, 1, 0, S.H, S.W, S.cp.L, S.cp.plan, S.cp.ratio, S.u, S.u2, S.warp, (size_t)fc, r));
+        if (r != S.u) std::swap(S.u, S.u2);
+    } else if (coarsest) {  // :801-806: zero flow, so the warped frame 2 is frame 2
+        PAPOF_HIP(hipMemsetAsync(S.u, 0, 2 * np * sizeof(double), h->stream));
+        if (!fold_warp) PAPOF_HIP(hipMemcpyAsync(S.warp, f2, np * fc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    } else {  // :809-816: u and v, two planes of one launch, into the free pair at this level's pitch
+        PAPOF_TRY(resize(h, S.u, S.u2, ph, pw, 2, lh, lw, (double)lw / pw, (double)lh / ph, true, 1 / S.cp.ratio));
+        std::swap(S.u, S.u2);
+    }
+    S.v = S.u + np;
+    S.v2 = S.u2 + np;
+    if (B.bgx) PAPOF_TRY(central3_planes(h, f2, B.bgx, B.bgy, B.bgxy, lh, lw, fc));
+    if (coarsest && !S.init) return PAPOF_OK;
+    if (B.bgx)  // interpolation == Bicubic (:816): warpImageBicubicRef, no threshold here
+        PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, S.u, S.v, S.warp, lh, lw, fc, nullptr, true, false));
+    else if (!fold_warp)
+        PAPOF_TRY(warp_bilinear(h, f1, f2, S.u, S.v, S.warp, lh, lw, fc));
+    return PAPOF_OK;
+}
+
+static int solve_levels(FlowPass& S) {
+    papof_handle* h = S.h;
+    const CallPlan& cp = S.cp;
+    LapGuard* const lg = S.lg;
+    if (lg && lg->guard())  // LapPara starts every call at 0.02 (src/OpticalFlow.cpp:773-775)
+        PAPOF_HIP(hipMemcpyAsync(lg->lap, h->lap_init_dev, 8 * sizeof(double), hipMemcpyDeviceToDevice, S.main_stream));
     int pw = 0, ph = 0;
-    const auto solve_levels = [&]() -> int {
-        if (lg && lg->guard())  // LapPara starts every call at 0.02 (src/OpticalFlow.cpp:773-775)
-            PAPOF_HIP(hipMemcpyAsync(lg->lap, h->lap_init_dev, 8 * sizeof(double), hipMemcpyDeviceToDevice, main_stream));
-        for (int k = levels - 1; k >= 0; k--) {
-            const int lw = L[k].w, lh = L[k].h;
-            const size_t np = (size_t)lw * lh;
-            clk.phase(-1);  // waiting for the preparation stream is nobody's phase
-            if (overlap) PAPOF_HIP(hipStreamWaitEvent(main_stream, h->sync_events[k], 0));
-            clk.phase(PAPOF_T_ALLOCATION);  // flow up-sampling and first warp of the level (:801-814)
-            const double *f1 = F1[k], *f2 = F2[k];
-            const int n_sor_k = P.n_sor + k * P.n_sor_per_level, n_outer_k = P.n_outer + k * P.n_outer_per_level;
-            unsigned* prog_k = nullptr;
-            if (exact) prog_k = h->sync_words + 32 + LP[k].prog_off;  // this level's counters, cleared by the preparation stream
-            const bool tiny_k = exact && sor_tiny_fits(h, lh, lw, n_sor_k);  // k_sor_tiny level
-            if (!tiny_k) PAPOF_TRY(sor_bind(h, B.sp, lh, lw, n_sor_k));
-            // the level's result goes straight to the caller's buffers on the finest level
-            double* const out_u = k == 0 ? d_vx : nullptr;
-            double* const out_v = k == 0 ? d_vy : nullptr;
-            const bool fold_warp = !B.bgx && !B.gm;  // the warped frame 2 lives only inside the smoothing kernel
-            if (k == levels - 1 && init) {  // the caller's initial flow (reduce_init; u, u2 and warp are free until here),
-                // and the coarsest level entered as every finer one is: frame 2's features warped at (u, v)
-                double* r = nullptr;
-                PAPOF_TRY(reduce_init(h, init, nullptr, 1, 0, H, W, L, plan, ratio, u, u2, warp, (size_t)fc, r));
-                if (r != u) std::swap(u, u2);
-                v = u + np;
-                v2 = u2 + np;
-                if (B.bgx) {
-                    PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
-                    PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, u, v, warp, lh, lw, fc, nullptr, true, false));
-                } else if (!fold_warp) {
-                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc));
-                }
-            } else if (k == levels - 1) {  // src/OpticalFlow.cpp:801-806
-                v = u + np;
-                v2 = u2 + np;
-                PAPOF_HIP(hipMemsetAsync(u, 0, 2 * np * sizeof(double), h->stream));
-                if (!fold_warp)
-                    PAPOF_HIP(hipMemcpyAsync(warp, f2, np * fc * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-                if (B.bgx) PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
-            } else {  // :809-816
-                const double xr = (double)lw / pw, yr = (double)lh / ph, inv = 1 / ratio;
-                // u and v: two planes of one launch, into the free pair at this level's pitch
-                PAPOF_TRY(resize(h, u, u2, ph, pw, 2, lh, lw, xr, yr, true, inv));
-                std::swap(u, u2);
-                v = u + np;
-                v2 = u2 + np;  // the free pair, at this level's pitch too
-                if (B.bgx) {  // interpolation == Bicubic (:816): warpImageBicubicRef, no threshold here
-                    PAPOF_TRY(bicubic_planes(h, f2, lh, lw, fc, B));
-                    PAPOF_TRY(bicubic_warp(h, f1, f2, B.bgx, B.bgy, B.bgxy, u, v, warp, lh, lw, fc, nullptr, true, false));
-                } else if (!fold_warp) {
-                    PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc));
-                }
-            }
-            if (!tiny_k) PAPOF_TRY(sor_reset_planes(h, B.sp));
-            PAPOF_TRY(smooth_flow(h, f1, f2, warp, u, v, u2, v2, lh, lw, fc, P.alpha, n_outer_k, P.n_inner, n_sor_k, P.omega,
-                                  P.sor_mode, B, clk, S1[k], false, prog_k, exact ? LP[k].prog_per : 0, out_u, out_v,
-                                  fold_warp, lg, k));
-            pw = lw;
-            ph = lh;
+    for (int k = cp.levels - 1; k >= 0; k--) {
+        const int lw = cp.L[k].w, lh = cp.L[k].h;
+        S.clk.phase(-1);  // waiting for the preparation stream is nobody's phase
+        if (S.overlap) PAPOF_HIP(hipStreamWaitEvent(S.main_stream, h->sync_events[k], 0));
+        S.clk.phase(PAPOF_T_ALLOCATION);  // flow up-sampling and first warp of the level (:801-814)
+        const bool tiny_k = S.exact && sor_tiny_fits(h, lh, lw, cp.n_sor[k]);  // k_sor_tiny level
+        if (!tiny_k) PAPOF_TRY(sor_bind(h, S.B.sp, lh, lw, cp.n_sor[k]));
+        // (no final warp: the next level warps anew, and the result is the bicubic warp of the originals)
+        const LevelSolve s{.B = S.B, .f1 = S.F1[k], .f2 = S.F2[k], .warp = S.warp, .H = lh, .W = lw, .fc = cp.fc,
+                           .alpha = S.P.alpha, .omega = S.P.omega, .n_outer = cp.n_outer[k], .n_inner = S.P.n_inner,
+                           .n_sor = cp.n_sor[k], .mode = S.P.sor_mode, .im1s_ready = S.S1[k], .final_warp = false,
+                           .counters = S.exact ? &S.counters : nullptr, .out_u = k == 0 ? S.d_vx : nullptr,
+                           .out_v = k == 0 ? S.d_vy : nullptr, .fold_warp = !S.B.bgx && !S.B.gm, .lg = lg, .level = k};
+        PAPOF_TRY(enter_level(S, k, pw, ph, s.fold_warp));
+        if (!tiny_k) PAPOF_TRY(sor_reset_planes(h, S.B.sp));
+        PAPOF_TRY(smooth_flow(h, s, S.clk, S.u, S.v, S.u2, S.v2));
+        pw = lw;
+        ph = lh;
+    }
+    return PAPOF_OK;
+}
+
+// src/OpticalFlow.cpp:841-842: the bicubic warp of the ORIGINAL frame 2 at the final flow, and the results where the caller
+// wants them
+static int final_warp(FlowPass& S) {
+    papof_handle* h = S.h;
+    papof_handle::HostIO& io = h->hostio;
+    const int H = S.H, W = S.W, C = S.C, levels = S.cp.levels;
+    const size_t np0 = (size_t)H * W;
+    const Level& l0 = S.cp.L[0];
+    S.clk.phase(-1);
+    if (S.overlap) PAPOF_HIP(hipStreamWaitEvent(S.main_stream, h->sync_events[levels], 0));
+    S.clk.phase(PAPOF_T_POSTPROCESSING);
+    if (S.hostio && io.early_out && S.u == S.d_vx && S.v == S.d_vy) {
+        // page-locked result arrays: (vx, vy) are final -- their copies run beside the bicubic warp -- and warpI2 follows
+        // its kernel in row chunks (the kernel takes a Rect; rows of the interleaved image are contiguous)
+        hipStream_t const cs = h->copy_stream;
+        PAPOF_HIP(hipEventRecord(h->copy_events[2], S.main_stream));
+        PAPOF_HIP(hipStreamWaitEvent(cs, h->copy_events[2], 0));
+        PAPOF_HIP(hipMemcpyAsync(io.vx, S.d_vx, io.nb_flow, hipMemcpyDeviceToHost, cs));
+        PAPOF_HIP(hipMemcpyAsync(io.vy, S.d_vy, io.nb_flow, hipMemcpyDeviceToHost, cs));
+        constexpr int kChunks = 4;
+        for (int q = 0; q < kChunks; q++) {
+            const Rect rc{0, (int)((long long)H * q / kChunks), W, (int)((long long)H * (q + 1) / kChunks)};
+            if (rc.empty()) continue;
+            PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, S.gx, S.gy, S.gxy, S.u, S.v, S.d_warp, H, W, C, &rc));
+            PAPOF_HIP(hipEventRecord(h->copy_events[3 + q], S.main_stream));
+            PAPOF_HIP(hipStreamWaitEvent(cs, h->copy_events[3 + q], 0));
+            const size_t off = (size_t)rc.y0 * W * C, cnt = (size_t)rc.h() * W * C;
+            PAPOF_HIP(hipMemcpyAsync(io.warp + off, S.d_warp + off, cnt * sizeof(double), hipMemcpyDeviceToHost, cs));
         }
-        clk.phase(-1);
-        if (overlap) PAPOF_HIP(hipStreamWaitEvent(main_stream, h->sync_events[levels], 0));
-        clk.phase(PAPOF_T_POSTPROCESSING);  // src/OpticalFlow.cpp:841-842
-        if (hostio && io.early_out && u == d_vx && v == d_vy) {
-            // page-locked result arrays: (vx, vy) are final -- their copies run beside the bicubic warp -- and warpI2 follows
-            // its kernel in row chunks (the kernel takes a Rect; rows of the interleaved image are contiguous)
-            hipStream_t const cs = h->copy_stream;
-            PAPOF_HIP(hipEventRecord(h->copy_events[2], main_stream));
-            PAPOF_HIP(hipStreamWaitEvent(cs, h->copy_events[2], 0));
-            PAPOF_HIP(hipMemcpyAsync(io.vx, d_vx, io.nb_flow, hipMemcpyDeviceToHost, cs));
-            PAPOF_HIP(hipMemcpyAsync(io.vy, d_vy, io.nb_flow, hipMemcpyDeviceToHost, cs));
-            constexpr int kChunks = 4;
-            for (int q = 0; q < kChunks; q++) {
-                const Rect rc{0, (int)((long long)H * q / kChunks), W, (int)((long long)H * (q + 1) / kChunks)};
-                if (rc.empty()) continue;
-                PAPOF_TRY(bicubic_warp(h, L[0].p1, L[0].p2, gx, gy, gxy, u, v, d_warp, H, W, C, &rc));
-                PAPOF_HIP(hipEventRecord(h->copy_events[3 + q], main_stream));
-                PAPOF_HIP(hipStreamWaitEvent(cs, h->copy_events[3 + q], 0));
-                const size_t off = (size_t)rc.y0 * W * C, cnt = (size_t)rc.h() * W * C;
-                PAPOF_HIP(hipMemcpyAsync(io.warp + off, d_warp + off, cnt * sizeof(double), hipMemcpyDeviceToHost, cs));
-            }
-            io.out_issued = true;
-            return PAPOF_OK;
-        }
-        PAPOF_TRY(bicubic_warp(h, L[0].p1, L[0].p2, gx, gy, gxy, u, v, d_warp, H, W, C));
-        if (u != d_vx) PAPOF_HIP(hipMemcpyAsync(d_vx, u, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        if (v != d_vy) PAPOF_HIP(hipMemcpyAsync(d_vy, v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        io.out_issued = true;
         return PAPOF_OK;
-    };
-    const int rc_main = solve_levels();
-    if (rc_main != PAPOF_OK) {  // never leave work of this call running on any stream
-        hipStreamSynchronize(main_stream);
-        if (overlap) hipStreamSynchronize(prep);
-        return rc_main;
     }
-    clk.phase(-1);
-    PAPOF_TRY(stamp_only(h));  // the closing stamp of the last phase
-    total.phase(-1);
+    PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, S.gx, S.gy, S.gxy, S.u, S.v, S.d_warp, H, W, C));
+    if (S.u != S.d_vx) PAPOF_HIP(hipMemcpyAsync(S.d_vx, S.u, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (S.v != S.d_vy) PAPOF_HIP(hipMemcpyAsync(S.d_vy, S.v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    return PAPOF_OK;
+}
+
+// Behind the total's end event, not part of any timer: the stamps and, in front of them in the same block, the guard's
+// flags of this call (the used witness slots end where the non-zero flags begin, those where the stamps begin)
+static int fetch_flags_and_stamps(FlowPass& S) {
+    papof_handle* h = S.h;
+    const LapGuard* lg = S.lg;
     h->stamps_fetched = 0;
-    {   // behind the total's end event, not part of any timer: the stamps and, in front of them in the same block, the guard's
-        // flags of this call (the used witness slots end where the non-zero flags begin, those where the stamps begin)
-        const bool flags = lg && lg->on && lg->collect;
-        const size_t first = flags ? lap_wit_word(std::min(lg->slot, kLapMaxSlots) - 1) : kLapFlagWords;
-        const size_t bytes = (kLapFlagWords - first) * sizeof(unsigned) + (size_t)h->stamps_used * sizeof(unsigned long long);
-        if (bytes > 0)
-            PAPOF_HIP(hipMemcpyAsync(h->lap_flags_host + first, h->lap_flags_dev + first, bytes, hipMemcpyDeviceToHost, h->stream));
-        h->stamps_fetched = h->stamps_used;
-    }
-    const double t_enqueued = wall();
-    PAPOF_HIP(hipStreamSynchronize(h->stream));
-    h->host_enqueue_sec = t_enqueued - t_entry;
-    h->host_wait_sec = wall() - t_enqueued;
-    h->next_stamp = nullptr;
-    if (P.sor_mode == PAPOF_SOR_EXACT) PAPOF_TRY(sor_check(h));
-    if (clk.err != PAPOF_OK || pclk.err != PAPOF_OK || total.err != PAPOF_OK) return PAPOF_EDEVICE;
-    clk.collect(tm);
-    pclk.collect(tm);
-    total.collect(tm);
-    if (clk.sor_span_sec.size() == h->sor_log.size())  // one span per solve
-        for (size_t i = 0; i < h->sor_log.size(); i++) h->sor_log[i].sec = clk.sor_span_sec[i];
+    const bool flags = lg && lg->on && lg->collect;
+    const size_t first = flags ? lap_wit_word(std::min(lg->slot, kLapMaxSlots) - 1) : kLapFlagWords;
+    const size_t bytes = (kLapFlagWords - first) * sizeof(unsigned) + (size_t)h->stamps_used * sizeof(unsigned long long);
+    if (bytes > 0)
+        PAPOF_HIP(hipMemcpyAsync(h->lap_flags_host + first, h->lap_flags_dev + first, bytes, hipMemcpyDeviceToHost, h->stream));
+    h->stamps_fetched = h->stamps_used;
+    return PAPOF_OK;
+}
+
+// The three fixed apportionings of kernels that do the work of several reference timers; tm holds PAPOF_N_TIMERS + 1 values.
+static void report_timers(double* tm) {
     {   // the fused assembly kernel was recorded under Phase4: psi's share of it is Phase3_PsiData.  kPsiShare = the
         // kernel's arithmetic that belongs to :377-406 (per channel: t*t, + eps, sqrt, 2*, 1/) over all of it, counted in
         // the kernel's ISA (fp64 sqrt and division are ~25 instructions each); a fixed apportioning, not a measurement.
@@ -856,8 +876,73 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
         tm[PAPOF_T_PHASE3_PSIDATA] += 0.14 * f;
         tm[PAPOF_T_PHASE4_LINEARSYSTEM] += f - 0.51 * f - 0.02 * f - 0.14 * f;
     }
-    if (timing) std::memcpy(timing, tm, tm_bytes);
-    if (op == kSeqNext) keep_seq(slot1 ^ 1);  // the frame just solved against becomes frame 1 of the next push
+}
+
+int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, int H, int W, int C, int levels,
+              const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing, LapGuard* lg,
+              const papof_tensor* init = nullptr) {
+    const double t_entry = wall();
+    FlowPass S{h, fa, fb, op, H, W, C, P, d_vx, d_vy, d_warp, lg, init};
+    // 1. the plan
+    PAPOF_TRY(call_plan(H, W, C, levels, P, S.cp));
+    const size_t need = arena_bytes_for(H, W, C, levels, S.cp.n_sor_max, P.ratio);
+    if (op == kSeqNext && !seq_matches(h, H, W, C, levels, S.cp.ratio, need)) {
+        g_last_error = "sequence push does not continue the primed sequence (shape, levels, ratio or arena changed)";
+        return PAPOF_EINVAL;
+    }
+    S.slot1 = op == kSeqNext ? h->seq.slot : 0;
+    h->seq.valid = false;  // re-established below once the kept pyramid is complete
+    // 2. the arena
+    PAPOF_TRY(ensure_arena(h, need));
+    h->arena.off = 0;
+    h->arena.overflow = false;
+    h->events_used = 0;
+    double tm[PAPOF_N_TIMERS + 1];  // + kTimerFused (flow_internal.h)
+    std::memset(tm, 0, sizeof tm);
+    start_clocks(S);
+    PAPOF_TRY(carve_pyramids(S));
+    // 3. a priming push ends here: the frame's pyramid, kept; no flow
+    if (op == kSeqPrime) {
+        PAPOF_TRY(load_frame(h, fa, S.cp.L[0].p1, H, W, C));
+        PAPOF_TRY(build_pyramid(h, S.cp.L, S.cp.plan, C, false, S.tmp_a, S.tmp_b));
+        PAPOF_HIP(hipStreamSynchronize(h->stream));
+        keep_seq(S, S.slot1);
+        if (timing) std::memset(timing, 0, PAPOF_N_TIMERS * sizeof(double));
+        return PAPOF_OK;
+    }
+    PAPOF_TRY(carve_buffers(S));
+    // 4. the preparation, on its own stream where the call overlaps
+    PAPOF_TRY(fork_and_prepare(S));
+    // 5., 6. the levels, coarsest first, and the final warp
+    int rc_main = solve_levels(S);
+    if (rc_main == PAPOF_OK) rc_main = final_warp(S);
+    if (rc_main != PAPOF_OK) {  // never leave work of this call running on any stream
+        hipStreamSynchronize(S.main_stream);
+        if (S.overlap) hipStreamSynchronize(S.prep);
+        return rc_main;
+    }
+    S.clk.phase(-1);
+    PAPOF_TRY(stamp_only(h));  // the closing stamp of the last phase
+    S.total.phase(-1);
+    // 7. the guard's flags and the stamps
+    PAPOF_TRY(fetch_flags_and_stamps(S));
+    // 8. drain and check
+    const double t_enqueued = wall();
+    PAPOF_HIP(hipStreamSynchronize(h->stream));
+    h->host_enqueue_sec = t_enqueued - t_entry;
+    h->host_wait_sec = wall() - t_enqueued;
+    h->next_stamp = nullptr;
+    if (S.exact) PAPOF_TRY(sor_check(h));
+    if (S.clk.err != PAPOF_OK || S.pclk.err != PAPOF_OK || S.total.err != PAPOF_OK) return PAPOF_EDEVICE;
+    // 9. the timers
+    S.clk.collect(tm);
+    S.pclk.collect(tm);
+    S.total.collect(tm);
+    if (S.clk.sor_span_sec.size() == h->sor_log.size())  // one span per solve
+        for (size_t i = 0; i < h->sor_log.size(); i++) h->sor_log[i].sec = S.clk.sor_span_sec[i];
+    report_timers(tm);
+    if (timing) std::memcpy(timing, tm, PAPOF_N_TIMERS * sizeof(double));  // what the caller gets
+    if (op == kSeqNext) keep_seq(S, S.slot1 ^ 1);  // the frame just solved against becomes frame 1 of the next push
     return PAPOF_OK;
 }
 
@@ -884,11 +969,7 @@ int flow_device(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
     const papof_handle::Seq seq0 = h->seq;
     double first_pass_total = 0.0;
     for (int pass = 0; pass < 2; pass++) {
-        // a flag is set when it holds the number of the pass that wrote it: no clearing, nothing stale can be taken for a proof
-        if (++h->lap_epoch >= kLapNone) {  // (2^31 passes later: start over on cleared flags)
-            PAPOF_HIP(hipMemsetAsync(h->lap_flags_dev, 0, kLapFlagWords * sizeof(unsigned), h->stream));
-            h->lap_epoch = 1u;
-        }
+        PAPOF_TRY(lap_next_epoch(h, h->stream));
         lg.epoch = h->lap_epoch;
         lg.slot = 0;
         lg.slot_level.clear();
@@ -1150,27 +1231,17 @@ int device_call(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op,
     if (!h || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
     if (op != kSeqNext && !fa.d) return PAPOF_EINVAL;
     if (op != kSeqPrime && (!fb.d || !d_vx || !d_vy || !d_warpI2)) return PAPOF_EINVAL;
-    papof_params P;
-    if (params)
-        P = *params;
-    else
-        papof_default_params(&P);
+    const papof_params P = params_or_default(params);
     PAPOF_HIP(hipSetDevice(h->device));
     return flow_device(h, fa, fb, op, height, width, c, pyramid_levels, P, d_vx, d_vy, d_warpI2, timing_sec);
 }
 
 // prime or continue?  (a push whose shape / plan differs from the kept frame starts a new sequence)
 SeqOp seq_op_for(papof_handle* h, int H, int W, int C, int levels, const papof_params* params) {
-    papof_params P;
-    if (params)
-        P = *params;
-    else
-        papof_default_params(&P);
-    double ratio = P.ratio;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;
+    const papof_params P = params_or_default(params);
     if (levels < 1) return kSeqPrime;
-    const size_t need = arena_bytes_for(H, W, C, levels, P.n_sor + (levels - 1) * P.n_sor_per_level, P.ratio);
-    return seq_matches(h, H, W, C, levels, ratio, need) ? kSeqNext : kSeqPrime;
+    const size_t need = arena_bytes_for(H, W, C, levels, CallPlan::n_sor_at(P, levels - 1), P.ratio);
+    return seq_matches(h, H, W, C, levels, effective_ratio(P.ratio), need) ? kSeqNext : kSeqPrime;
 }
 
 }  // namespace
@@ -1265,14 +1336,7 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
         }
     }
     use_io = use_io && h->copy_stream && h->copy_events.size() >= 8;
-    if (use_io) {
-        papof_params Pq;
-        if (params)
-            Pq = *params;
-        else
-            papof_default_params(&Pq);
-        use_io = Pq.phase_timing != 1;  // one-stream timing mode: nothing overlaps by definition
-    }
+    use_io = use_io && params_or_default(params).phase_timing != 1;  // one-stream timing mode: nothing overlaps by definition
     if (use_io) {
         h->hostio = papof_handle::HostIO{};
         h->hostio.active = true;
@@ -1324,25 +1388,14 @@ int flow_host(papof_handle* h, const void* im1, const void* im2, bool u8, SeqOp 
     }
     if (prefault.joinable()) prefault.join();
     PAPOF_TRY(rc_dev);
-    if (out_issued) {  // the result copies were queued by the call itself and have landed
-        if (timing_sec) {
-            tm[PAPOF_T_TOTAL] = wall() - t0;
-            std::memcpy(timing_sec, tm, sizeof tm);
-        }
-        return PAPOF_OK;
+    if (op != kSeqPrime && !out_issued) {  // (else the result copies were queued by the call itself and have landed)
+        PAPOF_HIP(hipMemcpyAsync(warpI2, dw, nb_img, hipMemcpyDeviceToHost, h->stream));
+        PAPOF_HIP(hipMemcpyAsync(vx, dx, nb_flow, hipMemcpyDeviceToHost, h->stream));
+        PAPOF_HIP(hipMemcpyAsync(vy, dy, nb_flow, hipMemcpyDeviceToHost, h->stream));
+        PAPOF_HIP(hipStreamSynchronize(h->stream));
     }
-    if (op == kSeqPrime) {
-        if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
-        return PAPOF_OK;
-    }
-    PAPOF_HIP(hipMemcpyAsync(warpI2, dw, nb_img, hipMemcpyDeviceToHost, h->stream));
-    PAPOF_HIP(hipMemcpyAsync(vx, dx, nb_flow, hipMemcpyDeviceToHost, h->stream));
-    PAPOF_HIP(hipMemcpyAsync(vy, dy, nb_flow, hipMemcpyDeviceToHost, h->stream));
-    PAPOF_HIP(hipStreamSynchronize(h->stream));
-    if (timing_sec) {
-        tm[PAPOF_T_TOTAL] = wall() - t0;  // the caller-visible total includes both PCIe transfers
-        std::memcpy(timing_sec, tm, sizeof tm);
-    }
+    if (op != kSeqPrime) tm[PAPOF_T_TOTAL] = wall() - t0;  // the caller-visible total includes both PCIe transfers
+    if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
     return PAPOF_OK;
 }
 
@@ -1719,7 +1772,7 @@ int papof_stage_smoothflow_ex(papof_handle* h, const double* im1, const double* 
     PAPOF_TRY(alloc_solve_buffers(h->arena, height, width, c, sor_mode, n_sor, B));
     PAPOF_TRY(alloc_branch_buffers(h, h->arena, height, width, c, interpolation, noise_model, B));
     if (B.gm && gm) PAPOF_HIP(hipMemcpyAsync(B.gm, gm, sizeof(double) * 5 * c, hipMemcpyHostToDevice, h->stream));
-    if (B.bgx) PAPOF_TRY(bicubic_planes(h, f2, height, width, c, B));
+    if (B.bgx) PAPOF_TRY(central3_planes(h, f2, B.bgx, B.bgy, B.bgxy, height, width, c));
     PAPOF_TRY(sor_bind(h, B.sp, height, width, n_sor));
     PAPOF_TRY(sor_reset_planes(h, B.sp));
     PhaseClock clk{h, false};
@@ -1729,8 +1782,10 @@ int papof_stage_smoothflow_ex(papof_handle* h, const double* im1, const double* 
     lg.lap = h->lap_dev;
     lg.scratch = h->lap_scratch_dev;
     if (lg.on) PAPOF_HIP(hipMemcpyAsync(lg.lap, h->lap_init_dev, 8 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    PAPOF_TRY(smooth_flow(h, f1, f2, w, du, dv, du_alt, dv_alt, height, width, c, alpha, n_outer, n_inner, n_sor, omega,
-                          sor_mode, B, clk, nullptr, true, nullptr, 0, nullptr, nullptr, false, &lg, 0));
+    // one level on its own: it smooths frame 1 itself, re-warps behind every update, clears its own counters
+    const LevelSolve s{.B = B, .f1 = f1, .f2 = f2, .warp = w, .H = height, .W = width, .fc = c, .alpha = alpha, .omega = omega,
+                       .n_outer = n_outer, .n_inner = n_inner, .n_sor = n_sor, .mode = sor_mode, .lg = &lg};
+    PAPOF_TRY(smooth_flow(h, s, clk, du, dv, du_alt, dv_alt));
     PAPOF_TRY(S.down_planar(w, warp, height, width, c));
     PAPOF_TRY(S.down_planar(du, u, height, width, 1));
     PAPOF_TRY(S.down_planar(dv, v, height, width, 1));
@@ -1761,7 +1816,7 @@ int papof_stage_est_gaussian_mixture(papof_handle* h, const double* im1, const d
 
 int papof_pyramid_levels_for_min_width(int width, double ratio, int min_width, int* levels) {
     if (width < 1 || min_width < 1 || !levels) return PAPOF_EINVAL;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;  // src/GaussianPyramid.cpp:50-51
+    ratio = effective_ratio(ratio);  // src/GaussianPyramid.cpp:50-51
     *levels = (int)(std::log((double)min_width / width) / std::log(ratio));  // :53
     return PAPOF_OK;
 }
@@ -1951,16 +2006,16 @@ int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int
         PAPOF_TRY(sor_strips_begin(h, sp, n_sor, 1));
         PAPOF_HIP(hipEventRecord(ev, main_stream));
         PAPOF_HIP(hipStreamWaitEvent(top, ev, 0));
-        h->stream = top;
-        int rc = sor_solve_bands(h, sp, height, width, 0.012, 1.8, n_sor, h->sync_words + 32, 0, split_band);
-        h->stream = main_stream;
-        PAPOF_TRY(rc);
+        {
+            StreamSwap on_top(h, top);
+            PAPOF_TRY(sor_solve_bands(h, sp, height, width, 0.012, 1.8, n_sor, counters_base(h), 0, split_band));
+        }
         if (delay_us > 0) {  // the lower strip starts later, as behind its own assembly kernels
             hipStreamSynchronize(main_stream);
             const double t0 = wall();
             while ((wall() - t0) * 1e6 < delay_us) {}
         }
-        PAPOF_TRY(sor_solve_bands(h, sp, height, width, 0.012, 1.8, n_sor, h->sync_words + 32, split_band, sp.sd.nb));
+        PAPOF_TRY(sor_solve_bands(h, sp, height, width, 0.012, 1.8, n_sor, counters_base(h), split_band, sp.sd.nb));
         PAPOF_HIP(hipStreamSynchronize(top));
         PAPOF_HIP(hipStreamSynchronize(main_stream));
         PAPOF_TRY(sor_check(h));

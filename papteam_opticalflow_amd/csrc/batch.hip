@@ -69,18 +69,17 @@ bool batch_applies(const papof_handle* h, int B, int H, int W, int C, int levels
         P.noise_model != PAPOF_NOISE_LAPLACIAN)
         return false;
     if (C != 1 && C != 3) return false;
-    const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
+    const int n_sor_max = CallPlan::n_sor_at(P, levels - 1);
     if (skew_dims(H, W, n_sor_max, 1, 1).nb >= 16) return false;  // big frames: the two-sweeps-per-wave kernel; they fill the chip alone
-    long slots = 0;
-    for (int k = 0; k < levels; k++) slots += P.n_outer + (long)k * P.n_outer_per_level;
-    return slots <= kLapMaxSlots;
+    return CallPlan::slots_for(P, levels) <= kLapMaxSlots;
 }
 
 // One launch of the solver holds the tasks of ALL pairs, and all of them must be resident (sor.hip: resident_tasks): a
 // collection larger than that -- or than a few GB of arena -- goes through in sub-batches of the same shape.
 int batch_max(int H, int W, int C, int levels, const papof_params& P) {
-    const int nb0 = skew_dims(H, W, P.n_sor + (levels - 1) * P.n_sor_per_level, 1, 1).nb;
-    const size_t per_pair = arena_bytes_for(H, W, C, levels, P.n_sor + (levels - 1) * P.n_sor_per_level, P.ratio);
+    const int n_sor_max = CallPlan::n_sor_at(P, levels - 1);
+    const int nb0 = skew_dims(H, W, n_sor_max, 1, 1).nb;
+    const size_t per_pair = arena_bytes_for(H, W, C, levels, n_sor_max, P.ratio);
     int max_b = (int)std::max<size_t>(2, std::min<size_t>((size_t)1024 / (size_t)nb0, ((size_t)24 << 30) / per_pair));
     if (const char* e = std::getenv("PAPOF_BATCH_MAX")) max_b = std::max(2, std::min(max_b, std::atoi(e)));  // (and the tests')
     return max_b;
@@ -90,17 +89,15 @@ int batch_max(int H, int W, int C, int levels, const papof_params& P) {
 // p with its two frames exchanged; BatchK::bw), 2B solver pairs on the same per-frame arrays -- only the per-pair work doubles.
 int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const BatchFrames& frames, int H, int W, int C, int levels,
                       const papof_params& P, double* timing, BatchOut& out) {
-    PAPOF_TRY(check_params(P, levels));
-    double ratio = P.ratio;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;
-    std::vector<Level> L;
-    std::vector<PyrPlan> plan;
-    PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, L, plan));
+    CallPlan cp;
+    PAPOF_TRY(call_plan(H, W, C, levels, P, cp));
+    const std::vector<Level>& L = cp.L;
+    const std::vector<PyrPlan>& plan = cp.plan;
+    const double ratio = cp.ratio;
     const int fstep = sequence ? 1 : 2, nF = sequence ? B + 1 : 2 * B;
     const int NP = with_bw ? 2 * B : B;  // solver pairs: per-pair arrays, operands, witness blocks
-    const int fc = feature_channels(C);
+    const int fc = cp.fc, n_sor_max = cp.n_sor_max;
     const size_t np0 = (size_t)H * W;
-    const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
     const bool guard = h->lap_guard && h->lap_flags_dev != nullptr;
     const bool u8 = frames.u8, staged = frames.host != nullptr;
     // ---- arena: one block, arrays over frames / pairs
@@ -159,27 +156,17 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             (size_t)(ST[p].phi - ST[0].phi) != p * st_stride || (size_t)(ST[p].du - ST[0].du) != p * st_stride)
             return PAPOF_EDEVICE;
 
-    // ---- counters of every solve of every pair, cleared once
-    struct LevelCounters {
-        size_t off, per;
-        bool tiny;
-    };
-    std::vector<LevelCounters> LC(levels);
-    size_t prog_total = 0;
-    for (int k = 0; k < levels; k++) {
-        const int Kk = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
-        LC[k].tiny = sor_tiny_fits(h, L[k].h, L[k].w, Kk);
-        LC[k].per = LC[k].tiny ? 0 : (size_t)skew_dims(L[k].h, L[k].w, Kk, 1, 1).nb * Kk * 32;
-        LC[k].off = prog_total;
-        prog_total += LC[k].per * (size_t)n_outer * NP;
-    }
+    // ---- counters of every solve of every pair (plain layout; a k_sor_tiny level has none), cleared once
+    const auto tiny_level = [&](int k) { return sor_tiny_fits(h, L[k].h, L[k].w, cp.n_sor[k]); };
+    const SolveCounters LC(
+        cp, [&](int k) { return tiny_level(k) ? 0 : (size_t)skew_dims(L[k].h, L[k].w, cp.n_sor[k], 1, 1).nb * cp.n_sor[k] * 32; },
+        (size_t)NP);
+    const size_t prog_total = LC.total;
     PAPOF_TRY(sor_counters_ensure(h, prog_total));
 
     // ---- timers: the total, and the solver kernels' own time (events around their launches)
     PhaseClock total{h, true}, sorclk{h, true};
     sorclk.only_sor = true;
-    double tm[PAPOF_N_TIMERS + 1];
-    std::memset(tm, 0, sizeof tm);
     total.phase(PAPOF_T_TOTAL);
 
     // ---- uploads, layout conversion, pyramids, features (frames are planes x frames for the plane-parallel kernels)
@@ -197,11 +184,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
         }
     }
     if (prog_total && !sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
-    if (++h->lap_epoch >= kLapNone) {  // (2^31 passes later: start over on cleared flags, as flow_device does -- the handle's own
-        // flag block holds pass numbers that are never cleared otherwise, and `epoch ^ kLapNone` must not be 0)
-        if (h->lap_flags_dev) PAPOF_HIP(hipMemsetAsync(h->lap_flags_dev, 0, kLapFlagWords * sizeof(unsigned), st));
-        h->lap_epoch = 1u;
-    }
+    PAPOF_TRY(lap_next_epoch(h, st));
     const unsigned epoch = h->lap_epoch;  // a flag is set when it holds this call's number
     if (guard) {
         PAPOF_HIP(hipMemsetAsync(wit, 0, (size_t)NP * kLapFlagWords * sizeof(unsigned), st));
@@ -233,7 +216,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
         for (int k = levels - 1; k >= 0; k--) {
             const int lw = L[k].w, lh = L[k].h;
             const size_t np = (size_t)lw * lh;
-            const int K = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
+            const int K = cp.n_sor[k], n_outer = cp.n_outer[k];
             if (k == levels - 1 && (frames.init_fw || frames.init_bw)) {
                 // the caller's initial flows of all pairs (reduce_init): uvA, uvB and the warped image are free until here
                 double* r = nullptr;
@@ -246,7 +229,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
                 PAPOF_TRY(resize(h, uv, uv2, ph, pw, 2 * NP, lh, lw, (double)lw / pw, (double)lh / ph, true, 1 / ratio));
                 std::swap(uv, uv2);
             }
-            const bool tiny = LC[k].tiny;
+            const bool tiny = tiny_level(k);
             SorPlanes sp = tiny ? ST[0] : SP[0];
             if (!tiny) {
                 PAPOF_TRY(sor_bind_plain(h, sp, lh, lw, K));
@@ -260,7 +243,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             bk.wit = kLapFlagWords;
             bk.bw = with_bw ? B : 0;
             bk.fr = np * fc;
-            const SorBatch bt{NP, sp_stride, spd_stride, LC[k].per, st_stride};
+            const SorBatch bt{NP, sp_stride, spd_stride, LC.lv[k].per, st_stride};
             const double *f1 = F[k], *f2 = F[k] + np * fc, *s1 = S[k];
             // Few-pixel levels (the deep end of an 8- or 15-level pyramid): the flow leaves the image altogether in some iterations,
             // every warped value is then frame 1's and there is NO valid sample -- which only a look at every pixel can tell from
@@ -270,7 +253,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             for (int count = 0; count < n_outer; count++) {
                 unsigned* const w_prev = guard && !exhaustive && count > 0 ? wit + lap_wit_word(slot - 1) : nullptr;
                 PAPOF_TRY(flow_system(h, f1, f2, uv, uv + np, s1, lh, lw, fc, P.alpha, P.omega, sp, w_prev, 0, -1, NP, &bk));
-                h->sor_prog_next = tiny ? nullptr : h->sync_words + 32 + LC[k].off + (size_t)count * LC[k].per * NP;
+                h->sor_prog_next = tiny ? nullptr : LC.solve(h, k, (size_t)count * NP);  // the NP pairs' counters of this solve
                 const int rc = sor_solve(h, sp, lh, lw, P.alpha, P.omega, K, PAPOF_SOR_EXACT, &bt);
                 h->sor_prog_next = nullptr;
                 PAPOF_TRY(rc);
@@ -327,10 +310,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             if (!open) out.unproven.push_back(p);
         }
     }
-    if (total.err != PAPOF_OK || sorclk.err != PAPOF_OK) return PAPOF_EDEVICE;
-    sorclk.collect(tm);
-    total.collect(tm);
-    if (timing) std::memcpy(timing, tm, PAPOF_N_TIMERS * sizeof(double));
+    PAPOF_TRY(collect_total_and_sor(total, sorclk, timing));
     out.uv = uv;
     out.warp = warp;
     return PAPOF_OK;
@@ -346,11 +326,7 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
         if (!frames[f]) return PAPOF_EINVAL;
     for (int p = 0; p < n_pairs; p++)
         if (!vx[p] || !vy[p] || !warpI2[p]) return PAPOF_EINVAL;
-    papof_params P;
-    if (params)
-        P = *params;
-    else
-        papof_default_params(&P);
+    const papof_params P = params_or_default(params);
     PAPOF_TRY(check_params(P, levels));
     PAPOF_HIP(hipSetDevice(h->device));
     const double t0 = now_sec();
@@ -367,11 +343,12 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
             for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
         return rc;
     };
-    if (!batch_applies(h, n_pairs, H, W, C, levels, P)) {
+    const auto all_single = [&]() -> int {  // the pairs one after the other
         for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
         if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
         return PAPOF_OK;
-    }
+    };
+    if (!batch_applies(h, n_pairs, H, W, C, levels, P)) return all_single();
     // sub-batches (batch_max)
     {
         const int max_b = batch_max(H, W, C, levels, P);
@@ -396,11 +373,9 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
         bf.host = frames;
         bf.u8 = u8;
         const int rc = flow_batch_device(h, n_pairs, sequence, false, bf, H, W, C, levels, P, tm, out);
-        if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
+        if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device
             std::memset(tm, 0, sizeof tm);
-            for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
-            if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
-            return PAPOF_OK;
+            return all_single();
         }
         PAPOF_TRY(rc);
     }
@@ -594,12 +569,8 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
 // the entry of papof_flow_batch_tensor(_fb) after the descriptors' checks: parameters, entry wait, the call, complete on return
 int tensor_entry(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2, int height,
                  int width, int c, int pyramid_levels, const papof_params* params, const TensorOut& o, void* stream,
-                 double* timing_sec, const TensorInit& ini = TensorInit{}) {
-    papof_params P;
-    if (params)
-        P = *params;
-    else
-        papof_default_params(&P);
+                 double* timing_sec, const TensorInit& ini) {
+    const papof_params P = params_or_default(params);
     PAPOF_TRY(check_params(P, pyramid_levels));
     PAPOF_HIP(hipSetDevice(h->device));
     const double t0 = now_sec();
@@ -658,13 +629,8 @@ int papof_flow_batch_u8(papof_handle* h, int n_pairs, int sequence, const unsign
 int papof_flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames, const papof_tensor* frames2,
                             int height, int width, int c, int pyramid_levels, const papof_params* params, const papof_tensor* flow,
                             const papof_tensor* warpI2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
-    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_frames(frames) || !valid_output(flow) || !valid_output(warpI2)) return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
-    TensorOut o;
-    o.flow = flow;
-    o.warp = warpI2;
-    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec);
+    return papof_flow_batch_tensor_init(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, nullptr, flow,
+                                        warpI2, stream, timing_sec);
 }
 
 int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
@@ -672,22 +638,9 @@ int papof_flow_batch_tensor_fb(papof_handle* h, int n_pairs, int sequence, const
                                const papof_params* params, const papof_tensor* flow_fw, const papof_tensor* warp_fw,
                                const papof_tensor* flow_bw, const papof_tensor* warp_bw, const papof_tensor* occlusion,
                                double alpha1, double alpha2, void* stream, double timing_sec[PAPOF_N_TIMERS]) {
-    if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1 || pyramid_levels < 1) return PAPOF_EINVAL;
-    if (!valid_frames(frames) || !valid_output(flow_fw) || !valid_output(warp_fw) || !valid_output(flow_bw) ||
-        !valid_output(warp_bw))
-        return PAPOF_EINVAL;
-    if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, kAxes, true)) return PAPOF_EINVAL;
-    if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    TensorOut o;
-    o.flow = flow_fw;
-    o.warp = warp_fw;
-    o.flow_bw = flow_bw;
-    o.warp_bw = warp_bw;
-    o.occ = occlusion;
-    o.a1 = alpha1;
-    o.a2 = alpha2;
-    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec);
+    return papof_flow_batch_tensor_fb_init(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, nullptr,
+                                           nullptr, flow_fw, warp_fw, flow_bw, warp_bw, occlusion, alpha1, alpha2, stream,
+                                           timing_sec);
 }
 
 int papof_flow_batch_tensor_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
@@ -698,13 +651,8 @@ int papof_flow_batch_tensor_init(papof_handle* h, int n_pairs, int sequence, con
     if (!valid_frames(frames) || !valid_output(flow) || !valid_output(warpI2)) return PAPOF_EINVAL;
     if (sequence ? frames2 != nullptr : !valid_frames(frames2)) return PAPOF_EINVAL;
     if (init && !described(init, kFloat, kAxes, false)) return PAPOF_EINVAL;
-    TensorOut o;
-    o.flow = flow;
-    o.warp = warpI2;
-    TensorInit ini;
-    ini.fw = init;
-    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec,
-                        ini);
+    return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params,
+                        TensorOut{.flow = flow, .warp = warpI2}, stream, timing_sec, TensorInit{.fw = init});
 }
 
 int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, const papof_tensor* frames,
@@ -722,19 +670,10 @@ int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, 
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     if ((init_fw && !described(init_fw, kFloat, kAxes, false)) || (init_bw && !described(init_bw, kFloat, kAxes, false)))
         return PAPOF_EINVAL;
-    TensorOut o;
-    o.flow = flow_fw;
-    o.warp = warp_fw;
-    o.flow_bw = flow_bw;
-    o.warp_bw = warp_bw;
-    o.occ = occlusion;
-    o.a1 = alpha1;
-    o.a2 = alpha2;
-    TensorInit ini;
-    ini.fw = init_fw;
-    ini.bw = init_bw;
+    const TensorOut o{.flow = flow_fw, .warp = warp_fw, .flow_bw = flow_bw, .warp_bw = warp_bw, .occ = occlusion, .a1 = alpha1,
+                      .a2 = alpha2};
     return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec,
-                        ini);
+                        TensorInit{.fw = init_fw, .bw = init_bw});
 }
 
 int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,

@@ -1,5 +1,5 @@
-// papteam_opticalflow_amd/csrc/flow_internal.h -- pieces of the orchestrator (api.hip) shared with the tiled
-// multi-GPU orchestrator (tiles.hip).  Internal; nothing here is part of the C ABI.
+// papteam_opticalflow_amd/csrc/flow_internal.h -- pieces of the orchestrator (api.hip) shared with the batched
+// (batch.hip) and the multi-GPU (tiles.hip) orchestrators.  Internal; nothing here is part of the C ABI.
 #pragma once
 
 #include <string>
@@ -121,15 +121,83 @@ struct Level {
     int w, h;
     double *p1, *p2;  // planar pyramid levels of frame 1 / frame 2
 };
-
-
-// GaussianPyramid::ConstructPyramidLevels (src/GaussianPyramid.cpp:79-108) for one frame, planar.
-// levels[i].p (selected by `which`) must be pre-allocated with the dims computed by pyramid_dims().
+// how GaussianPyramid::ConstructPyramidLevels (src/GaussianPyramid.cpp:79-108) derives a level: source level, filter, rate
 struct PyrPlan {
     int sw, sh, src_level, fsize;
     double sigma, rate;
 };
 
+// ---- the call plan: what every orchestrator (flow_pass, flow_batch_device, tiles_flow, bands_flow) derives from
+// (H, W, C, levels, P) before it touches the device ----
+inline double effective_ratio(double ratio) { return ratio > 0.98 || ratio < 0.4 ? 0.75 : ratio; }  // src/GaussianPyramid.cpp:82-83
+papof_params params_or_default(const papof_params* params);  // the caller's parameter block, or papof_default_params()
+struct CallPlan {
+    double ratio = 0.75;  // the effective one
+    int levels = 0, fc = 0;
+    std::vector<Level> L;
+    std::vector<PyrPlan> plan;
+    std::vector<int> n_sor, n_outer;  // the schedule of level k (src/OpticalFlow.cpp:784-823 as the Python entry point drives it)
+    int n_sor_max = 0;                // ... and its largest sweep count, the coarsest level's
+    long slots = 0;                   // outer iterations of the whole call: the Laplacian-noise guard's witness slots
+    bool from_level0 = true;          // every pyramid level is derived from level 0 (else deeper ones chain through finer levels)
+    static int n_sor_at(const papof_params& P, int k) { return P.n_sor + k * P.n_sor_per_level; }
+    static int n_outer_at(const papof_params& P, int k) { return P.n_outer + k * P.n_outer_per_level; }
+    static long slots_for(const papof_params& P, int levels) {
+        long s = 0;
+        for (int k = 0; k < levels; k++) s += n_outer_at(P, k);
+        return s;
+    }
+};
+int call_plan(int H, int W, int C, int levels, const papof_params& P, CallPlan& cp);  // check_params + pyramid_plan + the schedule
+
+// ---- the progress counters of every exact-order solve of a call: one block behind the handle's 32 control words, laid out
+// level by level and cleared at once.  `words(k)`: unsigneds per solve of level k (the path's own layout; 0: the level has
+// none); `solves_per_outer`: solves per outer iteration (n_inner of the single call, the solver pairs of a batch).
+inline unsigned* counters_base(const papof_handle* h) { return h->sync_words + 32; }  // the block: also the counters of a lone solve
+struct SolveCounters {
+    struct PerLevel {
+        size_t off = 0, per = 0;  // offset (unsigneds) of the level's first solve, stride per solve
+    };
+    std::vector<PerLevel> lv;
+    size_t total = 0;
+    SolveCounters() = default;
+    template <class Words>
+    SolveCounters(const CallPlan& cp, Words words, size_t solves_per_outer) : lv(cp.levels) {
+        for (int k = 0; k < cp.levels; k++) {
+            lv[k].per = words(k);
+            lv[k].off = total;
+            total += lv[k].per * (size_t)cp.n_outer[k] * solves_per_outer;
+        }
+    }
+    // the counters of solve i of level k (in the level's stream order)
+    unsigned* solve(const papof_handle* h, int k, size_t i) const { return counters_base(h) + lv[k].off + i * lv[k].per; }
+};
+
+// the number of the Laplacian-noise guard's next pass (papof_handle::lap_epoch): a flag is set when it holds the number of the
+// pass that wrote it -- no clearing, nothing stale can be taken for a proof; 2^31 passes later it starts over on cleared flags
+// (the handle's flag block holds pass numbers that are never cleared otherwise, and `epoch ^ kLapNone` must not be 0)
+int lap_next_epoch(papof_handle* h, hipStream_t stream);
+
+// the report of the orchestrators that measure the total and the solver kernels' own time only (after the stream has drained)
+inline int collect_total_and_sor(PhaseClock& total, PhaseClock& sorclk, double* timing) {
+    if (total.err != PAPOF_OK || sorclk.err != PAPOF_OK) return PAPOF_EDEVICE;
+    double tm[PAPOF_N_TIMERS + 1] = {};  // + kTimerFused
+    sorclk.collect(tm);
+    total.collect(tm);
+    for (int i = 0; timing && i < PAPOF_N_TIMERS; i++) timing[i] = tm[i];
+    return PAPOF_OK;
+}
+
+// ---- the preparation stream ----
+struct StreamSwap {  // the launch wrappers enqueue on h->stream
+    papof_handle* h;
+    hipStream_t saved;
+    StreamSwap(papof_handle* hh, hipStream_t s) : h(hh), saved(hh->stream) { h->stream = s; }
+    ~StreamSwap() { h->stream = saved; }
+};
+// one untimed event per level, one for the final warp's planes and one for this fork: with `overlap` the preparation stream
+// starts after whatever has been queued on the main stream (the frame uploads)
+int fork_prep(papof_handle* h, int levels, bool overlap);
 
 size_t arena_bytes_for(int H, int W, int C, int levels, int n_sor_max, double ratio);
 int ensure_arena(papof_handle* h, size_t bytes);
@@ -144,9 +212,8 @@ int feature_channels(int C);
 // tensors in and out); falls back to single calls
 int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* const* frames, bool u8, int H, int W, int C, int levels,
                     const papof_params* params, double* const* vx, double* const* vy, double* const* warpI2, double* timing_sec);
-// the device call on two planar fp64 frames already on the device (api.hip: flow_device, both passes of the guard); returns
-// with the results written
-// with the caller's initial flow of the pair (init: one pair of a strided float32 / float64 tensor; NULL: zero)
+// the device call on two planar fp64 frames already on the device (api.hip: flow_device, both passes of the guard), from the
+// caller's initial flow of the pair (init: one pair of a strided float32 / float64 tensor; NULL: zero); returns with the results written
 int flow_device_planar(papof_handle* h, const double* f1, const double* f2, int H, int W, int C, int levels,
                        const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing,
                        const papof_tensor* init = nullptr);

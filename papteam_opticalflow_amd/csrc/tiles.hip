@@ -494,25 +494,15 @@ int exchange_planes(papof_tiles& t, double* const* planes, int nplanes, int W, c
     return PAPOF_OK;
 }
 
-// The call, from one rank's point of view.  Collective: every rank of the group calls it with the same arguments
-// (each with its own device-resident copy of the two frames); rank 0 receives the assembled results.
-int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, int W, int C, int levels,
-               const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
+// The start of a call on a rank: the arena (the single call's bytes, the assembled image, `extra`, the exchange stage) laid out
+// anew -- first the stage, then both pyramids (replicated, read-only: GaussianPyramid::ConstructPyramidLevels,
+// src/GaussianPyramid.cpp:79-108) and their filter temporaries
+static int begin_rank_call(papof_tiles& t, CallPlan& cp, int H, int W, int C, const papof_params& P, size_t extra, double*& tmp_a,
+                           double*& tmp_b) {
     papof_handle* h = t.h;
-    PAPOF_TRY(check_params(P, levels));
-    if (P.sor_mode != PAPOF_SOR_REDBLACK || P.n_inner != 1) {
-        set_last_error_text("tiled solves use the red-black sweep order (sor_mode = PAPOF_SOR_REDBLACK) with n_inner = 1");
-        return PAPOF_EINVAL;
-    }
-    double ratio = P.ratio;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;
-    std::vector<Level> L;
-    std::vector<PyrPlan> plan;
-    PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, L, plan));
-    const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
     h->seq.valid = false;
-    PAPOF_TRY(ensure_arena(h, arena_bytes_for(H, W, C, levels, n_sor_max, P.ratio) + (size_t)H * W * C * sizeof(double) +
-                              2 * (stage_doubles(H, W, C) + 64) * sizeof(double)));
+    PAPOF_TRY(ensure_arena(h, arena_bytes_for(H, W, C, cp.levels, cp.n_sor_max, P.ratio) + (size_t)H * W * C * sizeof(double) +
+                              extra + 2 * (stage_doubles(H, W, C) + 64) * sizeof(double)));
     Arena& A = h->arena;
     A.off = 0;
     A.overflow = false;
@@ -520,22 +510,91 @@ int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
     h->events_used = 0;
     t.exchanges = 0;
     t.exchanged_bytes = 0;
+    for (Level& l : cp.L) {
+        l.p1 = A.f64((size_t)l.w * l.h * C);
+        l.p2 = A.f64((size_t)l.w * l.h * C);
+    }
+    tmp_a = A.f64((size_t)H * W * C);
+    tmp_b = A.f64((size_t)H * W * C);
+    return A.overflow ? PAPOF_ENOMEM : PAPOF_OK;
+}
+
+// The end of a call: every rank's own rectangle of (u, v) and of the interleaved warped image travels to rank 0, which
+// copies the assembled results into the caller's buffers.
+static int gather_to_rank0(papof_tiles& t, const RectOf& own, double* u, double* v, double* warp_hwc, int H, int W, int C,
+                           double* d_vx, double* d_vy, double* d_warp) {
     const size_t np0 = (size_t)H * W;
-    const int fc = feature_channels(C);
+    const RectOf need = [&](int r) { return r == 0 ? Rect{0, 0, W, H} : Rect{0, 0, 0, 0}; };
+    double* uv[2] = {u, v};
+    PAPOF_TRY(exchange_planes(t, uv, 2, W, own, need));
+    const RectOf own_c = [&](int r) {
+        const Rect q = own(r);
+        return Rect{q.x0 * C, q.y0, q.x1 * C, q.y1};
+    };
+    const RectOf need_c = [&](int r) { return r == 0 ? Rect{0, 0, W * C, H} : Rect{0, 0, 0, 0}; };
+    double* wp[1] = {warp_hwc};
+    PAPOF_TRY(exchange_planes(t, wp, 1, W * C, own_c, need_c));
+    if (t.tp->rank != 0) return PAPOF_OK;
+    if (!d_vx || !d_vy || !d_warp) return PAPOF_EINVAL;
+    PAPOF_HIP(hipMemcpyAsync(d_vx, u, np0 * sizeof(double), hipMemcpyDeviceToDevice, t.h->stream));
+    PAPOF_HIP(hipMemcpyAsync(d_vy, v, np0 * sizeof(double), hipMemcpyDeviceToDevice, t.h->stream));
+    PAPOF_HIP(hipMemcpyAsync(d_warp, warp_hwc, np0 * C * sizeof(double), hipMemcpyDeviceToDevice, t.h->stream));
+    return PAPOF_OK;
+}
+
+// A rank's replicated, flow-independent work -- both pyramids (GaussianPyramid::ConstructPyramidLevels,
+// src/GaussianPyramid.cpp:79-108) and the features of every level (src/OpticalFlow.cpp:797-798), coarsest level first, one
+// event per level; with (gx, gy, gxy) also the derivative planes of the final bicubic warp and their event -- forked onto
+// the preparation stream where the call overlaps.  A failure leaves nothing of it running.
+static int prepare_replicated(papof_handle* h, const CallPlan& cp, const double* d_im1, const double* d_im2, int H, int W, int C,
+                              double* tmp_a, double* tmp_b, const std::vector<double*>& F1, const std::vector<double*>& F2,
+                              bool overlap, double* gx, double* gy, double* gxy) {
+    PAPOF_TRY(fork_prep(h, cp.levels, overlap));
+    const auto enqueue = [&]() -> int {
+        StreamSwap on_prep(h, overlap ? h->prep_stream : h->stream);
+        const std::vector<Level>& L = cp.L;
+        PAPOF_TRY(hwc_to_planar(h, d_im1, L[0].p1, H, W, C));
+        PAPOF_TRY(hwc_to_planar(h, d_im2, L[0].p2, H, W, C));
+        PAPOF_TRY(build_pyramid(h, L, cp.plan, C, false, tmp_a, tmp_b));
+        PAPOF_TRY(build_pyramid(h, L, cp.plan, C, true, tmp_a, tmp_b));
+        for (int k = cp.levels - 1; k >= 0; k--) {
+            PAPOF_TRY(im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C));
+            PAPOF_TRY(im2feature(h, L[k].p2, F2[k], L[k].h, L[k].w, C));
+            if (overlap) PAPOF_HIP(hipEventRecord(h->sync_events[k], h->stream));
+        }
+        if (!gx) return PAPOF_OK;
+        PAPOF_TRY(central3_planes(h, L[0].p2, gx, gy, gxy, H, W, C));
+        if (overlap) PAPOF_HIP(hipEventRecord(h->sync_events[cp.levels], h->stream));
+        return PAPOF_OK;
+    };
+    const int rc = enqueue();
+    if (rc != PAPOF_OK && overlap) hipStreamSynchronize(h->prep_stream);
+    return rc;
+}
+
+// The call, from one rank's point of view.  Collective: every rank of the group calls it with the same arguments
+// (each with its own device-resident copy of the two frames); rank 0 receives the assembled results.
+int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, int W, int C, int levels,
+               const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
+    papof_handle* h = t.h;
+    PAPOF_TRY(check_params(P, levels));  // (ahead of the plan, which runs it again: the mode is refused before the pyramid)
+    if (P.sor_mode != PAPOF_SOR_REDBLACK || P.n_inner != 1) {
+        set_last_error_text("tiled solves use the red-black sweep order (sor_mode = PAPOF_SOR_REDBLACK) with n_inner = 1");
+        return PAPOF_EINVAL;
+    }
+    CallPlan cp;
+    PAPOF_TRY(call_plan(H, W, C, levels, P, cp));
+    std::vector<Level>& L = cp.L;
+    const double ratio = cp.ratio;
+    const int n_sor_max = cp.n_sor_max;
+    double *tmp_a = nullptr, *tmp_b = nullptr;
+    PAPOF_TRY(begin_rank_call(t, cp, H, W, C, P, 0, tmp_a, tmp_b));
+    Arena& A = h->arena;
+    const size_t np0 = (size_t)H * W;
+    const int fc = cp.fc;
     const int me = t.tp->rank, S = t.halo, HU = S + 3;
-    double tm[PAPOF_N_TIMERS + 1];  // + kTimerFused (flow_internal.h: PhaseClock::collect)
-    std::memset(tm, 0, sizeof tm);
     PhaseClock total{h, true}, sorclk{h, true};
     total.phase(PAPOF_T_TOTAL);
-
-    // replicated, read-only: both pyramids (GaussianPyramid::ConstructPyramidLevels, src/GaussianPyramid.cpp:79-108)
-    for (int i = 0; i < levels; i++) {
-        L[i].p1 = A.f64((size_t)L[i].w * L[i].h * C);
-        L[i].p2 = A.f64((size_t)L[i].w * L[i].h * C);
-    }
-    double* tmp_a = A.f64(np0 * C);
-    double* tmp_b = A.f64(np0 * C);
-    if (A.overflow) return PAPOF_ENOMEM;
     // Replicated, flow-independent work -- both pyramids and the features of every level (src/OpticalFlow.cpp:757-758,
     // :797-798) -- goes to the handle's PREPARATION stream, coarsest level first, beside the coarse levels' solves on the
     // main stream (as flow_device does): on N GPUs the per-rank solver work shrinks with N, this part does not (rocprof,
@@ -548,33 +607,7 @@ int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
     }
     if (A.overflow) return PAPOF_ENOMEM;
     const bool overlap = h->overlap_prep && h->prep_stream != nullptr;
-    while (h->sync_events.size() < (size_t)levels + 2) {
-        hipEvent_t e;
-        PAPOF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->sync_events.push_back(e);
-    }
-    {
-        hipStream_t const main_stream = h->stream;
-        if (overlap) {  // after whatever the caller queued on the main stream (the frame uploads)
-            PAPOF_HIP(hipEventRecord(h->sync_events[levels + 1], main_stream));
-            PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->sync_events[levels + 1], 0));
-            h->stream = h->prep_stream;  // the launch wrappers enqueue on h->stream
-        }
-        int rc = hwc_to_planar(h, d_im1, L[0].p1, H, W, C);
-        if (rc == PAPOF_OK) rc = hwc_to_planar(h, d_im2, L[0].p2, H, W, C);
-        if (rc == PAPOF_OK) rc = build_pyramid(h, L, plan, C, false, tmp_a, tmp_b);
-        if (rc == PAPOF_OK) rc = build_pyramid(h, L, plan, C, true, tmp_a, tmp_b);
-        for (int k = levels - 1; k >= 0 && rc == PAPOF_OK; k--) {
-            rc = im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C);
-            if (rc == PAPOF_OK) rc = im2feature(h, L[k].p2, F2[k], L[k].h, L[k].w, C);
-            if (rc == PAPOF_OK && overlap && hipEventRecord(h->sync_events[k], h->stream) != hipSuccess) rc = PAPOF_EDEVICE;
-        }
-        h->stream = main_stream;
-        if (rc != PAPOF_OK) {
-            if (overlap) hipStreamSynchronize(h->prep_stream);
-            return rc;
-        }
-    }
+    PAPOF_TRY(prepare_replicated(h, cp, d_im1, d_im2, H, W, C, tmp_a, tmp_b, F1, F2, overlap, nullptr, nullptr, nullptr));
 
     double* warp = A.f64(np0 * fc);
     double* u = A.f64(np0);
@@ -625,7 +658,7 @@ int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
             PAPOF_TRY(warp_bilinear(h, f1, f2, u, v, warp, lh, lw, fc, &Tu));
         }
         // OpticalFlow::SmoothFlowSOR (src/OpticalFlow.cpp:238-536) on the tile
-        const int n_outer = P.n_outer + k * P.n_outer_per_level, n_sor = P.n_sor + k * P.n_sor_per_level;
+        const int n_outer = cp.n_outer[k], n_sor = cp.n_sor[k];
         const Rect Rim = grow(T, S + 1, lw, lh);                    // smoothed / blended features
         const Rect Rh{Rim.x0, Tu.y0, Rim.x1, Tu.y1};                // horizontal pass: two more rows for the vertical one
         const Rect Rphi = grow(T, S, lw, lh), Rsys = grow(T, S - 1, lw, lh);
@@ -693,31 +726,12 @@ int tiles_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
         const Rect T = tile_rect(t.grid, me, W, H);
         PAPOF_TRY(bicubic_warp(h, L[0].p1, L[0].p2, gx, gy, gxy, u, v, warp_hwc, H, W, C, &T));
         const RectOf own = [&](int r) { return tile_rect(t.grid, r, W, H); };
-        const RectOf need = [&](int r) { return r == 0 ? Rect{0, 0, W, H} : Rect{0, 0, 0, 0}; };
-        double* uv[2] = {u, v};
-        PAPOF_TRY(exchange_planes(t, uv, 2, W, own, need));
-        const RectOf own_c = [&](int r) {
-            const Rect q = tile_rect(t.grid, r, W, H);
-            return Rect{q.x0 * C, q.y0, q.x1 * C, q.y1};
-        };
-        const RectOf need_c = [&](int r) { return r == 0 ? Rect{0, 0, W * C, H} : Rect{0, 0, 0, 0}; };
-        double* wp[1] = {warp_hwc};
-        PAPOF_TRY(exchange_planes(t, wp, 1, W * C, own_c, need_c));
-        if (me == 0) {
-            if (!d_vx || !d_vy || !d_warp) return PAPOF_EINVAL;
-            PAPOF_HIP(hipMemcpyAsync(d_vx, u, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            PAPOF_HIP(hipMemcpyAsync(d_vy, v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            PAPOF_HIP(hipMemcpyAsync(d_warp, warp_hwc, np0 * C * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
+        PAPOF_TRY(gather_to_rank0(t, own, u, v, warp_hwc, H, W, C, d_vx, d_vy, d_warp));
     }
     total.phase(-1);
     PAPOF_TRY(t.tp->drain(h));
     if (overlap) PAPOF_HIP(hipStreamSynchronize(h->prep_stream));
-    if (total.err != PAPOF_OK || sorclk.err != PAPOF_OK) return PAPOF_EDEVICE;
-    sorclk.collect(tm);
-    total.collect(tm);
-    if (timing) std::memcpy(timing, tm, PAPOF_N_TIMERS * sizeof(double));
-    return PAPOF_OK;
+    return collect_total_and_sor(total, sorclk, timing);
 }
 
 
@@ -774,54 +788,37 @@ struct BandSplit {
 int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, int W, int C, int levels,
                const papof_params& P, double* d_vx, double* d_vy, double* d_warp, double* timing) {
     papof_handle* h = t.h;
-    PAPOF_TRY(check_params(P, levels));
-    const int n_sor_max = P.n_sor + (levels - 1) * P.n_sor_per_level;
+    PAPOF_TRY(check_params(P, levels));  // (ahead of the plan, which runs it again: the mode is refused before the pyramid)
+    const int n_sor_max = CallPlan::n_sor_at(P, levels - 1);
     if (P.sor_mode != PAPOF_SOR_EXACT || P.n_inner != 1 || P.interpolation != PAPOF_INTERP_BILINEAR ||
         P.noise_model != PAPOF_NOISE_LAPLACIAN || n_sor_max > 128 || !h->use_dpp) {
         set_last_error_text("the exact-order band split takes the default branches with n_inner = 1 and at most 128 sweeps");
         return PAPOF_EINVAL;
     }
-    double ratio = P.ratio;
-    if (ratio > 0.98 || ratio < 0.4) ratio = 0.75;
-    std::vector<Level> L;
-    std::vector<PyrPlan> plan;
-    PAPOF_TRY(pyramid_plan(H, W, P.ratio, levels, L, plan));
-    h->seq.valid = false;
-    PAPOF_TRY(ensure_arena(h, arena_bytes_for(H, W, C, levels, n_sor_max, P.ratio) + (size_t)H * W * C * sizeof(double) +
-                              (size_t)(t.tp->nranks + 2) * kLapMaxSlots * 8 * sizeof(unsigned) +  // + the guard's flags of all ranks
-                              2 * (stage_doubles(H, W, C) + 64) * sizeof(double)));
+    CallPlan cp;
+    PAPOF_TRY(call_plan(H, W, C, levels, P, cp));
+    std::vector<Level>& L = cp.L;
+    const double ratio = cp.ratio;
+    // ---- identical allocation sequence on every rank: a buffer sits at the same arena offset everywhere, so a peer's
+    // pointer is its arena base + my offset
+    double *tmp_a = nullptr, *tmp_b = nullptr;
+    const size_t lap_bytes = (size_t)(t.tp->nranks + 2) * kLapMaxSlots * 8 * sizeof(unsigned);  // the guard's flags of all ranks
+    PAPOF_TRY(begin_rank_call(t, cp, H, W, C, P, lap_bytes, tmp_a, tmp_b));
     Arena& A = h->arena;
-    A.off = 0;
-    A.overflow = false;
-    PAPOF_TRY(stage_carve(t, A, H, W, C));
-    h->events_used = 0;
-    h->sor_log.clear();
-    t.exchanges = 0;
-    t.exchanged_bytes = 0;
+    h->sor_log.clear();  // (host-only, like the clocks below: their place relative to the carve above moves no enqueue)
     const size_t np0 = (size_t)H * W;
-    const int fc = feature_channels(C);
+    const int fc = cp.fc;
     const int me = t.tp->rank, n = t.tp->nranks;
-    double tm[PAPOF_N_TIMERS + 1];  // + kTimerFused (flow_internal.h: PhaseClock::collect)
-    std::memset(tm, 0, sizeof tm);
     PhaseClock total{h, true}, sorclk{h, true};
     total.phase(PAPOF_T_TOTAL);
 
-    // ---- identical allocation sequence on every rank: a buffer sits at the same arena offset everywhere, so a peer's
-    // pointer is its arena base + my offset
-    for (int i = 0; i < levels; i++) {
-        L[i].p1 = A.f64((size_t)L[i].w * L[i].h * C);
-        L[i].p2 = A.f64((size_t)L[i].w * L[i].h * C);
-    }
-    double* tmp_a = A.f64(np0 * C);
-    double* tmp_b = A.f64(np0 * C);
     // ---- the Laplacian-noise guard (api.hip: LapGuard; src/OpticalFlow.cpp:399-400).  This path runs the OPTIMISTIC pass only,
     // so it must PROVE that the guard cannot have tripped, or refuse: behind every update each rank checks every pixel of the
     // rows it owns -- a witness (|Im1 - warpIm2| >= 2e-20 x pixels), and whether there is a valid sample at all -- and at the end
     // of the call the flags of all ranks are gathered: an estimate is proven when SOME rank has a witness or NO rank has a valid
     // sample (the constant 0.001).  A consulted estimate without a proof ends the call with PAPOF_EINVAL on every rank: such a
     // pair (values scaled to ~1e-21) belongs on the one-GPU call, which has the exact pass.
-    long lap_slots = 0;
-    for (int k = 0; k < levels; k++) lap_slots += P.n_outer + (long)k * P.n_outer_per_level;
+    const long lap_slots = cp.slots;
     const bool lap_on = h->lap_guard;
     if (lap_on && (fc > 8 || lap_slots > kLapMaxSlots / 2)) {  // it proves or refuses: never a call without the check
         set_last_error_text("the band split cannot prove the reference's Laplacian-noise guard (src/OpticalFlow.cpp:399-400) for "
@@ -862,23 +859,15 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
     if (A.overflow) return PAPOF_ENOMEM;
 
     // ---- progress counters of every solve of the call (plain layout), cleared once; then the peers' bases
-    struct LevelCounters {
-        size_t off, per;
-    };
-    std::vector<LevelCounters> LP(levels);
-    size_t prog_total = 0;
-    for (int k = 0; k < levels; k++) {
-        const int Kk = P.n_sor + k * P.n_sor_per_level;
-        LP[k].per = (size_t)skew_dims(L[k].h, L[k].w, Kk, 1, 1).nb * Kk * 32;
-        LP[k].off = prog_total;
-        prog_total += LP[k].per * (size_t)(P.n_outer + k * P.n_outer_per_level);
-        if ((long long)skew_dims(L[k].h, L[k].w, Kk, 1, 1).nb * Kk > 2048) {  // all ranks' tasks of a solve are in flight together
+    const auto tasks = [&](int k) { return (size_t)skew_dims(L[k].h, L[k].w, cp.n_sor[k], 1, 1).nb * cp.n_sor[k]; };
+    for (int k = 0; k < levels; k++)
+        if (tasks(k) > 2048) {  // all ranks' tasks of a solve are in flight together
             set_last_error_text("solve too large for the co-resident band split");
             return PAPOF_EINVAL;
         }
-    }
-    PAPOF_TRY(sor_counters_ensure(h, prog_total));
-    if (!sor_counters_clear(h, 0, prog_total)) return PAPOF_EDEVICE;
+    const SolveCounters LP(cp, [&](int k) { return tasks(k) * 32; }, 1);
+    PAPOF_TRY(sor_counters_ensure(h, LP.total));
+    if (!sor_counters_clear(h, 0, LP.total)) return PAPOF_EDEVICE;
     // DIRECT: the producer's kernel stores the cut cells and its progress into the consumer's memory while both run (needs
     // peer addressing: the LOCAL transport).  STAGED (any transport, RCCL included): the same SPLIT kernels, but a rank's
     // kernel writes the cut cells into an OUTBOX of its own, and after it has finished they travel as one message per solve
@@ -900,7 +889,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
         const int npos_max = skew_dims(H, W, n_sor_max, 1, 1).npos_d;
         cutmsg = A.f64((size_t)2 * n_sor_max * npos_max);
         size_t per_max = 0;
-        for (int k = 0; k < levels; k++) per_max = std::max(per_max, LP[k].per);
+        for (int k = 0; k < levels; k++) per_max = std::max(per_max, LP.lv[k].per);
         outprog = reinterpret_cast<unsigned*>(A.f64(per_max / 2 + 64));
         if (A.overflow) return PAPOF_ENOMEM;
     }
@@ -911,35 +900,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
 
     // ---- replicated, flow-independent work on the preparation stream (as tiles_flow)
     const bool overlap = h->overlap_prep && h->prep_stream != nullptr;
-    while (h->sync_events.size() < (size_t)levels + 2) {
-        hipEvent_t e;
-        PAPOF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->sync_events.push_back(e);
-    }
-    {
-        hipStream_t const main_stream = h->stream;
-        if (overlap) {
-            PAPOF_HIP(hipEventRecord(h->sync_events[levels + 1], main_stream));
-            PAPOF_HIP(hipStreamWaitEvent(h->prep_stream, h->sync_events[levels + 1], 0));
-            h->stream = h->prep_stream;
-        }
-        int rc = hwc_to_planar(h, d_im1, L[0].p1, H, W, C);
-        if (rc == PAPOF_OK) rc = hwc_to_planar(h, d_im2, L[0].p2, H, W, C);
-        if (rc == PAPOF_OK) rc = build_pyramid(h, L, plan, C, false, tmp_a, tmp_b);
-        if (rc == PAPOF_OK) rc = build_pyramid(h, L, plan, C, true, tmp_a, tmp_b);
-        for (int k = levels - 1; k >= 0 && rc == PAPOF_OK; k--) {
-            rc = im2feature(h, L[k].p1, F1[k], L[k].h, L[k].w, C);
-            if (rc == PAPOF_OK) rc = im2feature(h, L[k].p2, F2[k], L[k].h, L[k].w, C);
-            if (rc == PAPOF_OK && overlap && hipEventRecord(h->sync_events[k], h->stream) != hipSuccess) rc = PAPOF_EDEVICE;
-        }
-        if (rc == PAPOF_OK) rc = central3_planes(h, L[0].p2, gx, gy, gxy, H, W, C);
-        if (rc == PAPOF_OK && overlap && hipEventRecord(h->sync_events[levels], h->stream) != hipSuccess) rc = PAPOF_EDEVICE;
-        h->stream = main_stream;
-        if (rc != PAPOF_OK) {
-            if (overlap) hipStreamSynchronize(h->prep_stream);
-            return rc;
-        }
-    }
+    PAPOF_TRY(prepare_replicated(h, cp, d_im1, d_im2, H, W, C, tmp_a, tmp_b, F1, F2, overlap, gx, gy, gxy));
 
     const Taps g5 = smooth5_taps();
     const char* const silent_env = std::getenv("PAPOF_BANDS_SILENT_RANK");  // fault injection (tests): this rank
@@ -950,7 +911,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
     for (int k = levels - 1; k >= 0; k--) {
         const int lw = L[k].w, lh = L[k].h;
         const size_t np = (size_t)lw * lh;
-        const int K = P.n_sor + k * P.n_sor_per_level, n_outer = P.n_outer + k * P.n_outer_per_level;
+        const int K = cp.n_sor[k], n_outer = cp.n_outer[k];
         PAPOF_TRY(sor_bind_plain(h, sp, lh, lw, K));
         const BandSplit bs{n, sp.sd.nb, K, lh};
         const int B0 = bs.B(me), B1 = bs.B(me + 1);
@@ -1015,7 +976,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
                     PAPOF_TRY(assemble_system(h, blend, imdt, phi, u, v, lh, lw, fc, P.alpha, P.omega, sp, nullptr, nullptr,
                                               nullptr, &Rsys));
                 }
-                unsigned* const prog = h->sync_words + 32 + LP[k].off + (size_t)count * LP[k].per;
+                unsigned* const prog = LP.solve(h, k, (size_t)count);
                 SorSplit cut{nullptr, nullptr, B0 > 0, below >= 0};
                 if (below >= 0 && direct) {
                     cut.peer_du = (double*)peer_ptr(below, sp.du, A.base, arenas[below]);
@@ -1038,7 +999,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
                 // the own last band's cut cells to g + 1.
                 const int m_ranks = std::min(n, sp.sd.nb);  // ranks with bands: 0 .. m_ranks - 1
                 const int npos = sp.sd.npos_d;
-                unsigned* const prog = h->sync_words + 32 + LP[k].off + (size_t)count * LP[k].per;
+                unsigned* const prog = LP.solve(h, k, (size_t)count);
                 SorSplit cut{below >= 0 ? outbox : nullptr, below >= 0 ? outprog : nullptr, B0 > 0, below >= 0};
                 const size_t msg_doubles = (size_t)2 * K * npos;
                 const dim3 cgrid((npos + 255) / 256, K), cblock(256);
@@ -1101,31 +1062,15 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
     // src/OpticalFlow.cpp:841-842: bicubic warp of the ORIGINAL frame 2 on the rows this rank owns, then everything to rank 0
     {
         if (overlap) PAPOF_HIP(hipStreamWaitEvent(h->stream, h->sync_events[levels], 0));
-        const int lw = W, lh = H;
         const BandSplit pb = prev;
         const RectOf own = [&](int r) {
             int y0, y1;
             pb.final_rows(r, y0, y1);
-            return y1 > y0 ? Rect{0, y0, lw, y1} : Rect{0, 0, 0, 0};
+            return y1 > y0 ? Rect{0, y0, W, y1} : Rect{0, 0, 0, 0};
         };
         const Rect T = own(me);
         PAPOF_TRY(bicubic_warp(h, L[0].p1, L[0].p2, gx, gy, gxy, u, v, warp_hwc, H, W, C, &T));
-        const RectOf need = [&](int r) { return r == 0 ? Rect{0, 0, lw, lh} : Rect{0, 0, 0, 0}; };
-        double* uv[2] = {u, v};
-        PAPOF_TRY(exchange_planes(t, uv, 2, W, own, need));
-        const RectOf own_c = [&](int r) {
-            const Rect q = own(r);
-            return Rect{q.x0 * C, q.y0, q.x1 * C, q.y1};
-        };
-        const RectOf need_c = [&](int r) { return r == 0 ? Rect{0, 0, W * C, H} : Rect{0, 0, 0, 0}; };
-        double* wp[1] = {warp_hwc};
-        PAPOF_TRY(exchange_planes(t, wp, 1, W * C, own_c, need_c));
-        if (me == 0) {
-            if (!d_vx || !d_vy || !d_warp) return PAPOF_EINVAL;
-            PAPOF_HIP(hipMemcpyAsync(d_vx, u, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            PAPOF_HIP(hipMemcpyAsync(d_vy, v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            PAPOF_HIP(hipMemcpyAsync(d_warp, warp_hwc, np0 * C * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
+        PAPOF_TRY(gather_to_rank0(t, own, u, v, warp_hwc, H, W, C, d_vx, d_vy, d_warp));
     }
     std::vector<unsigned> lap_host;
     if (lap_on) {  // every rank's flags to every rank: all of them reach the same verdict
@@ -1167,11 +1112,7 @@ int bands_flow(papof_tiles& t, const double* d_im1, const double* d_im2, int H, 
                 }
             }
     }
-    if (total.err != PAPOF_OK || sorclk.err != PAPOF_OK) return PAPOF_EDEVICE;
-    sorclk.collect(tm);
-    total.collect(tm);
-    if (timing) std::memcpy(timing, tm, PAPOF_N_TIMERS * sizeof(double));
-    return PAPOF_OK;
+    return collect_total_and_sor(total, sorclk, timing);
 }
 
 }  // namespace
@@ -1193,14 +1134,18 @@ int papof_tiles_grid(int nranks, int* rows, int* cols) {
     return PAPOF_OK;
 }
 
-int papof_tiles_rect(int width, int height, int rows, int cols, int rank, int rect[4]) {
-    if (width < 1 || height < 1 || rows < 1 || cols < 1 || rank < 0 || rank >= rows * cols || !rect) return PAPOF_EINVAL;
-    const Rect r = tile_rect(TileGrid{rows, cols}, rank, width, height);
+static int put_rect(const Rect& r, int rect[4]) {
     rect[0] = r.x0;
     rect[1] = r.y0;
     rect[2] = r.x1;
     rect[3] = r.y1;
     return PAPOF_OK;
+}
+
+int papof_tiles_rect(int width, int height, int rows, int cols, int rank, int rect[4]) {
+    if (width < 1 || height < 1 || rows < 1 || cols < 1 || rank < 0 || rank >= rows * cols || !rect) return PAPOF_EINVAL;
+    const Rect r = tile_rect(TileGrid{rows, cols}, rank, width, height);
+    return put_rect(r, rect);
 }
 
 int papof_tiles_halo_message(int width, int height, int rows, int cols, int halo, int src, int dst, int rect[4]) {
@@ -1210,11 +1155,7 @@ int papof_tiles_halo_message(int width, int height, int rows, int cols, int halo
     const TileGrid g{rows, cols};
     Rect r{0, 0, 0, 0};
     if (src != dst) r = intersect(tile_rect(g, src, width, height), grow(tile_rect(g, dst, width, height), halo, width, height));
-    rect[0] = r.x0;
-    rect[1] = r.y0;
-    rect[2] = r.x1;
-    rect[3] = r.y1;
-    return PAPOF_OK;
+    return put_rect(r, rect);
 }
 
 int papof_bands_plan(int height, int width, int n_sor, int nranks, int rank, int out[6]) {
@@ -1306,13 +1247,8 @@ int papof_tiles_flow_device(papof_tiles* t, const double* d_im1, const double* d
                             int pyramid_levels, const papof_params* params, double* d_vx, double* d_vy,
                             double* d_warpI2, double timing_sec[PAPOF_N_TIMERS]) {
     if (!t || !t->h || !t->tp || !d_im1 || !d_im2 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    papof_params P;
-    if (params)
-        P = *params;
-    else {
-        papof_default_params(&P);
-        P.sor_mode = PAPOF_SOR_REDBLACK;
-    }
+    papof_params P = params_or_default(params);
+    if (!params) P.sor_mode = PAPOF_SOR_REDBLACK;
     PAPOF_HIP(hipSetDevice(t->h->device));
     // PAPOF_SOR_EXACT: the exact-order split into horizontal ranges of solver bands over ALL ranks (the rows x cols grid is
     // the red-black tiles'); anything else: the 2-D tiles
