@@ -1741,6 +1741,67 @@ int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field_height, in
                              int first, int mode, const papof_tensor* flow_fw, const papof_tensor* flow_bw, double sigma,
                              const papof_tensor* video, const papof_tensor* confidence, void* stream);
 
+/* Rolling-shutter rectification along the flows (rolling.hip: k_rs_rectify, k_rs_flow).  A rolling shutter reads the rows of
+ * a frame one after another: row y of frame t of H rows is exposed at the time t + readout * (y - a) / H, in frame intervals,
+ * with a = anchor * (H - 1) the row that is exposed at the frame's own time.  The video's dense flows give every pixel's
+ * position one frame earlier and one frame later, each at its landing row's own time: three points of its trajectory.  The
+ * parabola through them, evaluated at the frame's time, is where a global shutter would have seen the pixel.
+ * n_frames = T >= 2 frames of height x width = H x W.  flow_fw, flow_bw: the T - 1 pairs' flows as
+ * papof_temporal_filter_tensor takes them: flow_fw[t] from frame t to t + 1, flow_bw[t - 1] from frame t to t - 1.
+ * readout: finite, |readout| <= 1 (negative: a sensor read from the bottom up); anchor in [0, 1]; iters 1 .. 8.
+ * In fp64 in the stated order without fused multiply-adds, with r = readout / (double)H and a = anchor * (double)(H - 1):
+ *
+ * The displacement L_t(P) of a point P = (X, Y) of [0, W - 1] x [0, H - 1] of frame t, and whether it is alive:
+ *   s = (a - Y) * r                          (the time from the row's exposure to the frame's time)
+ *   s == 0:  L = (+0, +0), alive, no flow is read (readout = 0; the anchor row)
+ *   else     (Fu, Fv) = flow_fw[t] (t < T - 1) and (Bu, Bv) = flow_bw[t - 1] (t > 0) sampled at P (sampler.h: taps_at,
+ *            sample_flow: papof_track_tensor's sampler)
+ *            tf = 1.0 + r * Fv;  tb = r * Bv - 1.0          (the times at which the point is at P + F and at P + B)
+ *   0 < t < T - 1:  alive = tf >= 0.5 && tb <= -0.5 (false for a NaN)
+ *            cF = (s * (s - tb)) / (tf * (tf - tb));  cB = (s * (s - tf)) / (tb * (tb - tf))
+ *            L = (cF * Fu + cB * Bu, cF * Fv + cB * Bv)
+ *   t = 0:          alive = tf >= 0.5;   cF = s / tf;  L = (cF * Fu, cF * Fv)        (a line: there is no backward flow)
+ *   t = T - 1:      alive = tb <= -0.5;  cB = s / tb;  L = (cB * Bu, cB * Bv)
+ * The solve for an output point Q, the P with P + L_t(P) = Q:
+ *   P_0 = Q;  P_(k+1) = (Qx - Lx_t(P_k), Qy - Ly_t(P_k)) for k = 0 .. iters - 1
+ *   alive only if Q, every P_k and P_iters lie in [0, W - 1] x [0, H - 1] (false for a NaN) and every evaluation was alive; the
+ *   first failure ends the solve.
+ *
+ * papof_rs_rectify_tensor: out(t, y, x, ch) = frames[t] sampled bilinearly at P_iters of Q, and valid(t, y, x) = 1; where the
+ * solve is dead, out = 0 and valid = 0 (papof_warp_affine_tensor's convention).  Q = (x, y) for matrices = NULL; else, with
+ * M = matrices[t], Q = (X, Y) of papof_warp_affine_tensor: X = (m00 * x + m01 * y) + m02;  Y = (m10 * x + m11 * y) + m12 -- the
+ * stabilizing warp and the rectification in one resampling.  frames, matrices, out, valid: layouts, strides, dtypes and
+ * stores as papof_warp_affine_tensor's, c = 1 .. 4 channels.  readout = 0 without matrices gives store(load(frames)), with
+ * matrices papof_warp_affine_tensor's out and valid.
+ *
+ * papof_rs_flow_tensor: the flows of the rectified video from the flows of the recorded one, both directions of every pair in
+ * one launch.  out_fw[i](q), q = (x, y) a pixel of rectified frame i, i < T - 1:
+ *   P = P_iters of the solve for Q = q in frame i;  (Fu, Fv) = flow_fw[i] sampled at P;  P' = (Px + Fu, Py + Fv) must lie in
+ *   the image;  L' = L_(i+1)(P') must be alive (one evaluation, no iteration)
+ *   out = (((Px - x) + Fu) + L'x, ((Py - y) + Fv) + L'y)
+ * out_bw[i](q), q a pixel of rectified frame i + 1: the same with the solve in frame i + 1, flow_bw[i] and L_i.
+ * Where anything is dead, and where a component comes out as a NaN, the component is the NaN 0x7ff8000000000000.  out_fw,
+ * out_bw: float32 (one round-to-nearest) or float64, (pair, row, column, {vx, vy}), strides > 0; they must not overlap the
+ * inputs.  readout = 0 gives finite input flows back wherever their landing point lies in the image (a NaN or infinite
+ * neighbour enters a sample through its zero weight, as everywhere in sampler.h).
+ *
+ * What it is not: readout is the caller's, it is not estimated; motion that changes faster than three samples one frame apart
+ * can follow (shake near half the frame rate) is not recovered; the end frames use a line; dead pixels are not filled.
+ * One lane makes one output pixel, its iterate in registers; no device memory besides the tensors, no atomics; bitwise
+ * reproducible.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns
+ * without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (matrices and valid aside) or data pointer, frames or
+ * out that are not uint8 / float32 / float64, flows, matrices or output flows that are not float32 / float64, a valid that is
+ * not uint8, a negative stride, a zero stride of an output along an axis in use, n_frames < 2, height or width < 1, c outside
+ * 1 .. 4, a readout that is not finite or beyond 1 in magnitude, an anchor outside [0, 1] (a NaN included), iters outside
+ * 1 .. 8. */
+int papof_rs_rectify_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                            const papof_tensor* flow_fw, const papof_tensor* flow_bw, double readout, double anchor, int iters,
+                            const papof_tensor* matrices, const papof_tensor* out, const papof_tensor* valid, void* stream);
+int papof_rs_flow_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* flow_fw,
+                         const papof_tensor* flow_bw, double readout, double anchor, int iters, const papof_tensor* out_fw,
+                         const papof_tensor* out_bw, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

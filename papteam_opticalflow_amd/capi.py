@@ -82,6 +82,7 @@ SYMBOLS = [
     "papof_mosaic_mesh_workspace", "papof_mosaic_mesh_tensor",
     "papof_defect_detect_tensor", "papof_mask_dilate_tensor",
     "papof_deinterlace_tensor",
+    "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
 ]
 
 
@@ -313,6 +314,11 @@ def load():
     L.papof_deinterlace_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, c_int, c_int, _T, _T, c_double, _T, _T,
                                            c_void_p]
     L.papof_deinterlace_tensor.restype = c_int
+    L.papof_rs_rectify_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, c_double, c_int, _T, _T, _T,
+                                          c_void_p]
+    L.papof_rs_rectify_tensor.restype = c_int
+    L.papof_rs_flow_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_double, c_double, c_int, _T, _T, c_void_p]
+    L.papof_rs_flow_tensor.restype = c_int
     L.papof_temporal_consistency_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, _T,
                                                     c_double, c_double, c_int, c_int, c_double, c_double, _T, c_void_p,
                                                     ctypes.c_longlong, c_void_p]

@@ -180,6 +180,17 @@ at the critical velocity; weaker end frames; no cadence detection.
 
     dv = deinterlace_video(split_fields(frames, layout="NHWC"), 4, layout="NHWC")   # dv.video (2 N, H, W, C), dv.confidence
 
+Rolling shutter: `rectify_frames` (include/papof.h: papof_rs_rectify_tensor) resamples a video whose rows were read out one
+after another -- row y of frame t at t + readout (y - a) / H -- to what a global shutter would have recorded at the frame's
+time: every pixel's position one frame earlier and later is in the flows, the parabola through the three points is its
+trajectory, and a few fixed-point iterations invert it per output pixel; with `matrices` the stabilizing warp is part of
+the same resampling.  `rectify_flows` (papof_rs_flow_tensor) gives the rectified video's flows without a second estimation,
+`rectify_video` chains flow_video_fb and both, and `stabilize_video_rs` is stabilize_video whose motion fit sees the
+rectified flows and whose one warp also rectifies.  readout is the caller's (phones: 0.5 .. 0.9), it is not estimated; shake
+near half the frame rate is not recovered; the end frames use a line; dead pixels are not filled.
+
+    rv = rectify_video(frames, 5, 0.8, layout="NHWC")   # rv.video, rv.valid, rv.flow_fw, rv.flow_bw, rv.occlusion
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -216,6 +227,8 @@ Restored = collections.namedtuple("Restored", "video masks detected status")
 RestoredVideo = collections.namedtuple("RestoredVideo", Restored._fields + ("flow_fw", "flow_bw", "timing"))
 Deinterlaced = collections.namedtuple("Deinterlaced", "video confidence")
 DeinterlacedVideo = collections.namedtuple("DeinterlacedVideo", Deinterlaced._fields + ("flow_fw", "flow_bw", "timing"))
+Rectified = collections.namedtuple("Rectified", "video valid flow_fw flow_bw occlusion timing")
+StabilizedRS = collections.namedtuple("StabilizedRS", "video valid transforms motion ok flow_fw flow_bw occlusion timing")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
 Blurred = collections.namedtuple("Blurred", "video flow_fw flow_bw occlusion timing")
 RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
@@ -2043,6 +2056,156 @@ def deinterlace_video(fields, pyramidLevels, first=0, *, sigma=DEINT_SIGMA, layo
     fb = _field_flows(ts, descs, layout, pyramidLevels, params)
     d = _deinterlace(ts, descs, first, 1, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), sigma, layout, out_dtype)
     return DeinterlacedVideo(d.video, d.confidence, fb.flow_fw, fb.flow_bw, fb.timing)
+
+
+MAX_RS_ITERS = 8  # include/papof.h: papof_rs_rectify_tensor
+_F64_FLOWS = (capi.DTYPE_F64, capi.DTYPE_F64)  # the dtype codes of flow_video_fb's float64 flows
+
+
+def _check_shutter(readout, anchor, iters, name="iters"):
+    """(readout, anchor, iterations of the solve) of the rolling-shutter calls as (float, float, int) -- TypeError /
+    ValueError otherwise"""
+    for n, v in (("readout", readout), ("anchor", anchor)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s must be a number, got %r" % (n, v))
+    if not (math.isfinite(readout) and abs(readout) <= 1):
+        raise ValueError("readout must be finite and at most 1 in magnitude (in frame intervals), got %r" % (readout,))
+    if not 0 <= anchor <= 1:
+        raise ValueError("anchor must lie in [0, 1], got %r" % (anchor,))
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= MAX_RS_ITERS:
+        raise ValueError("%s must be an integer in 1 .. %d, got %r" % (name, MAX_RS_ITERS, iters))
+    return float(readout), float(anchor), iters
+
+
+def _flow_dtype(out_dtype, default):
+    """the dtype of an output flow, `default` for None -- TypeError unless float32 or float64"""
+    torch = _torch()
+    out_dtype = default if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.float32 or torch.float64, got %s" % out_dtype)
+    return out_dtype
+
+
+def _rectify(ts, descs, flows, codes, shutter, matrices, m_code, layout, out_dtype):
+    """papof_rs_rectify_tensor of the checked frames ts[0]: (video, valid (T, H, W) bool)"""
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    out, d_out = _new_frames(T, H, W, C, layout, out_dtype, dev)
+    valid = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_mat = None
+    if matrices is not None:
+        d_mat = _struct(matrices, (matrices.stride(0), matrices.stride(1), matrices.stride(2), 0), m_code)
+    d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
+    _launch(dev, "papof_rs_rectify_tensor", T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), *shutter,
+            _ref(d_mat), ctypes.byref(d_out), ctypes.byref(d_valid))
+    return out, valid.view(torch.bool)
+
+
+def _rectify_flows(flows, codes, shutter, out_dtype):
+    """papof_rs_flow_tensor of the checked flows: Flows(flow_fw, flow_bw) of out_dtype"""
+    torch = _torch()
+    B, _, H, W = (int(x) for x in flows[0].shape)
+    dev = flows[0].device
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    outs = [torch.empty((B, 2, H, W), dtype=out_dtype, device=dev) for _ in range(2)]
+    d_o = [_flow_struct(o, _out_code(out_dtype)) for o in outs]
+    _launch(dev, "papof_rs_flow_tensor", B + 1, H, W, ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), *shutter, ctypes.byref(d_o[0]),
+            ctypes.byref(d_o[1]))
+    return Flows(*outs)
+
+
+def rectify_frames(frames, flow_fw, flow_bw, readout, *, anchor=0.5, iters=3, matrices=None, layout="NCHW", out_dtype=None):
+    """A rolling-shutter video of T >= 2 frames resampled to a global shutter's: frames (T, C, H, W) or (T, H, W, C) by
+    `layout`, C = 1 .. 4, uint8 (read as x / 255), float32 or float64, any strides, on a HIP device; flow_fw, flow_bw
+    (T - 1, 2, H, W) float32 / float64 on the same device, as flow_video_fb returns them for these frames.
+    readout: the time the sensor takes from the first row to the last, in frame intervals, |readout| <= 1 (negative: read
+    from the bottom up; phones are around 0.5 .. 0.9); anchor in [0, 1]: the row, as a fraction of H - 1, whose exposure
+    is the frame's time (0.5: the middle row stays where it is).  Row y was exposed readout (y - a) / H after the
+    frame's time.  The flows give where the pixel was one frame earlier and later, each landing at its own row's time; the
+    parabola through the three points, evaluated that much earlier, is its global-shutter position P + L(P) (a line on
+    the two end frames).  Output pixel Q is the frame sampled bilinearly at the P with P + L(P) = Q, found by `iters` (1 .. 8)
+    fixed-point iterations P <- Q - L(P) from P = Q (the error falls by about |readout| |v| / H per iteration, v the
+    vertical velocity in pixels per frame).  matrices: None, or (T, 2, 3) float32 / float64 on the same device: Q is
+    warp_affine's M (x, y, 1) -- stabilizing_transforms' matrices -- so that the video is resampled once.
+    Returns (video in `layout` and out_dtype -- by default the frames' --, valid (T, H, W) bool); a pixel whose Q or
+    iterate leaves the image, or whose flows are NaN or say that it crossed more than half of the sensor's readout in one
+    frame, is 0 and not valid.  readout = 0 gives the frames (with matrices: warp_affine's result).  include/papof.h
+    (papof_rs_rectify_tensor) states the rule exactly.  What it is not: readout is not estimated; shake near half the
+    frame rate is not recoverable from one flow per frame; dead pixels are not filled (stabilize_video_full fills
+    borders); the mesh, homography and mosaic calls take rectified videos and flows but have no readout of their own.
+    Enqueued on the current stream; returns without waiting."""
+    shutter = _check_shutter(readout, anchor, iters)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype)
+    (T, H, W, _), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
+    m_code = _check_matrices(matrices, T, ts[0].device) if matrices is not None else None
+    return _rectify(ts, descs, (flow_fw, flow_bw), codes, shutter, matrices, m_code, layout, out_dtype)
+
+
+def rectify_flows(flow_fw, flow_bw, readout, *, anchor=0.5, iters=3, out_dtype=None):
+    """The flows of the video that rectify_frames makes, from the flows of the recorded one -- no second estimation:
+    flow_fw, flow_bw (T - 1, 2, H, W) float32 / float64 on one HIP device, any strides; readout, anchor, iters as
+    rectify_frames'.  For pixel q of rectified frame i: P is rectify_frames' sampling point, the recorded flow at P takes
+    it to P' in the next frame, and the rectified flow is P' + L(P') - q.  Returns Flows(flow_fw, flow_bw) of out_dtype
+    (float32 / float64; by default flow_fw's), NaN where the solve is dead, P' leaves the image or L(P') is dead:
+    fb_consistency marks those occluded and global_motion leaves them out.  readout = 0 gives finite input flows back
+    wherever they land in the image.  include/papof.h (papof_rs_flow_tensor) states the rule exactly.  Enqueued on the
+    current stream; returns without waiting."""
+    shutter = _check_shutter(readout, anchor, iters)
+    codes = _check_flows(flow_fw, flow_bw)
+    out_dtype = _flow_dtype(out_dtype, flow_fw.dtype)
+    return _rectify_flows((flow_fw, flow_bw), codes, shutter, out_dtype)
+
+
+def rectify_video(frames, pyramidLevels, readout, *, anchor=0.5, iters=3, layout="NCHW", out_dtype=None,
+                  consistency=CONSISTENCY, **solver):
+    """A rolling-shutter video of T >= 2 frames and its flows rectified: flow_video_fb(frames, pyramidLevels, layout=layout,
+    consistency=None, out_dtype=torch.float64, **solver), rectify_frames and rectify_flows on those flows, and
+    fb_consistency(*consistency) on the rectified flows (None: no mask), where every dead pixel is occluded.  Returns
+    Rectified(video, valid (T, H, W) bool, flow_fw, flow_bw (T - 1, 2, H, W) float64 -- the rectified video's --, occlusion
+    (T - 1, 2, H, W) bool or None, timing of the flow call).  Every argument error raises before anything is launched."""
+    alphas = _alphas(consistency)
+    shutter = _check_shutter(readout, anchor, iters)
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
+    fb, flows, occ = _rectified_flows(ts, descs, layout, pyramidLevels, params, shutter, alphas)
+    video, valid = _rectify(ts, descs, (fb.flow_fw, fb.flow_bw), _F64_FLOWS, shutter, None, None, layout, out_dtype)
+    return Rectified(video, valid, flows.flow_fw, flows.flow_bw, occ, fb.timing)
+
+
+def _rectified_flows(ts, descs, layout, levels, params, shutter, alphas):
+    """the flow half of rectify_video on checked arguments: (the FlowFB of the recorded video, the rectified Flows, their
+    occlusion or None)"""
+    torch = _torch()
+    fb = _run_fb(ts, descs, True, descs[0][0][0] - 1, layout, torch.float64, levels, _alphas(None), params)
+    flows = _rectify_flows((fb.flow_fw, fb.flow_bw), _F64_FLOWS, shutter, torch.float64)
+    occ = fb_consistency(flows.flow_fw, flows.flow_bw, *alphas[1:]) if alphas[0] else None
+    return fb, flows, occ
+
+
+def stabilize_video_rs(frames, pyramidLevels, readout, *, anchor=0.5, rs_iters=3, layout="NCHW", model="similarity",
+                       radius=15, crop=1.0, iters=5, scale=1.0, consistency=CONSISTENCY, out_dtype=None, **solver):
+    """stabilize_video for a rolling-shutter camera: flow_video_fb (float64 flows), rectify_flows (readout, anchor, rs_iters
+    iterations of the solve), fb_consistency on the rectified flows (consistency; None: no mask), global_motion on the
+    rectified forward flows with that mask (model, iters, scale) -- the fit no longer sees the shear --,
+    stabilizing_transforms (radius, crop; the only wait) and ONE rectify_frames(matrices=transforms): the video is
+    resampled once.  Returns StabilizedRS(video, valid (T, H, W) bool, transforms (T, 2, 3) float64, motion (T - 1, 2, 3)
+    float64, ok (T - 1,) bool, flow_fw, flow_bw (T - 1, 2, H, W) float64 -- the rectified flows --, occlusion or None,
+    timing of the flow call).  Every argument error raises before anything is launched; the video is enqueued on the
+    current stream."""
+    alphas = _alphas(consistency)
+    shutter = _check_shutter(readout, anchor, rs_iters, "rs_iters")
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
+    code, iters, scale = _check_fit(model, iters, scale)
+    (_, H, W, _), _, _ = descs[0]
+    _check_path(radius, crop, (H, W))
+    fb, flows, occ = _rectified_flows(ts, descs, layout, pyramidLevels, params, shutter, alphas)
+    m = _motion_fit(flows.flow_fw, capi.DTYPE_F64, None if occ is None else occ.view(_torch().uint8), code, iters, scale)
+    M = stabilizing_transforms(m, radius, crop, size=(H, W))
+    video, valid = _rectify(ts, descs, (fb.flow_fw, fb.flow_bw), _F64_FLOWS, shutter, M, capi.DTYPE_F64, layout, out_dtype)
+    return StabilizedRS(video, valid, M, m.motion, m.ok, flows.flow_fw, flows.flow_bw, occ, fb.timing)
 
 
 MAX_ITERS = 65536  # include/papof.h: papof_temporal_consistency_tensor
