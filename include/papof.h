@@ -1802,6 +1802,75 @@ int papof_rs_flow_tensor(papof_handle* h, int n_frames, int height, int width, c
                          const papof_tensor* flow_bw, double readout, double anchor, int iters, const papof_tensor* out_fw,
                          const papof_tensor* out_bw, void* stream);
 
+/* Video deblurring: multi-frame Richardson-Lucy deconvolution along the flows (deblur.hip: k_deblur_ratio, k_deblur_update).
+ * A frame exposed over a shutter is the scene averaged along each pixel's path, shutter * velocity pixels long; the flows give
+ * the velocity, and the frames around a target, carried to it along the chains of flows, are blurred in other directions and
+ * fill the spectral zeros of its own blur.  papof_motion_blur_tensor is the forward model; this is its inverse.
+ * frames: ONE video of n_frames = T >= 2 frames of height x width x c (H, W, C), C = 1 .. 4, uint8 (x / 255.0), float32
+ * (widened exactly) or float64, (frame, row, column, channel), any non-negative strides.  flow_fw, flow_bw: the T - 1 pairs'
+ * flows as papof_temporal_filter_tensor takes them: float32 / float64, (pair, row, column, {vx, vy}), flow_fw[t] from frame t
+ * to t + 1, flow_bw[t] from frame t + 1 to t, any non-negative strides.  out: uint8, float32 or float64, (frame, row, column,
+ * channel), strides > 0; it must not overlap frames.  support: NULL, or uint8 (frame, row, column), strides > 0 (stride[3] is
+ * not read).  offsets[k] = tau_k and weights[k] = w_k: the shutter's sample table, as papof_motion_blur_tensor takes it: tau_k
+ * exactly 0 or 2^-20 <= |tau_k| <= 1 - 2^-20, w_k finite and >= 0 with a sum > 0, 1 <= n_samples <= 64; read before the call
+ * returns.  radius = R in 0 .. 4, iters in 1 .. 256; use_check, alpha1, alpha2: the forward-backward test of every hop, as
+ * papof_temporal_filter_tensor's.
+ *
+ * Everything is fp64 in the stated order without fused multiply-adds.  "Sampled at (X, Y)" is sampler.h's bilinear rule
+ * (taps_at: truncation toward zero, neighbours clamped into the image, the four taps accumulated from 0 in (m, n) order).
+ * clamp(v, 0, n) = fmin(fmax(v, 0.0), n).  wsum = the w_k > 0 summed from 0, k ascending; a sample with w_k == 0 is skipped
+ * everywhere.  EPS = 2^-10.
+ *   Data:      b_s(q, ch) = fmax(frames[s](q, ch), 0.0) (a NaN becomes 0).  L_t = b_t to start.
+ *   Velocity   of frame s at a pixel, per component: 0 < s < T - 1: v = 0.5 * (flow_fw[s] - flow_bw[s - 1]); s = 0: v =
+ *              flow_fw[0]; s = T - 1: v = 0.0 - flow_bw[T - 2].  At a point (X, Y) (pass B, every slot): both flows are sampled
+ *              at (X, Y) (sample_flow) and combined the same way.  Non-finite: a component that is a NaN or infinite.
+ *   Slots      of target t, in this order: s = t, t + 1, t - 1, t + 2, t - 2, ..., t + R, t - R; a slot outside 0 .. T - 1 is
+ *              absent.
+ *   Chains:    the chain of a point from frame a to frame b is the hop of papof_temporal_filter_tensor repeated: a < b through
+ *              flow_fw[a], flow_fw[a + 1], ..., each tested against flow_bw of the same pair; a > b through flow_bw[a - 1],
+ *              flow_bw[a - 2], ..., each tested against flow_fw.  A hop fails where it leaves [0, W - 1] x [0, H - 1] (or is a
+ *              NaN) or, with use_check, fails the test; the chain is then dead for good.  a == b: the point itself, alive.
+ *   Pass A (ratios), per target t, slot s, pixel q = (x, y) of frame s and channel ch:
+ *              (X, Y), alive = the chain of q from s to t;  (vx, vy) = the velocity of s at the pixel q
+ *              dead, or a non-finite velocity:  ratio_{t,s}(q, ch) = 1.0
+ *              else  est = 0;  k ascending:  est = est + w_k * (L_t(., ch) sampled at (clamp(X + tau_k * vx, 0, W - 1),
+ *                    clamp(Y + tau_k * vy, 0, H - 1)));   est = est / wsum;   ratio_{t,s}(q, ch) = b_s(q, ch) / fmax(est, EPS)
+ *   Pass B (update), per target t and pixel p, with corr_ch = 0 and n = 0, for the slots in order:
+ *              (X, Y), alive = the chain of p from t to s; dead: the slot is skipped
+ *              (vx, vy) = the velocity of s at the point (X, Y); non-finite: the slot is skipped
+ *              cs = 0;  k ascending:  cs = cs + w_k * (ratio_{t,s}(., ch) sampled at (clamp(X - tau_k * vx, 0, W - 1),
+ *                    clamp(Y - tau_k * vy, 0, H - 1)));   corr_ch = corr_ch + cs / wsum;   n = n + 1
+ *              n > 0:  L_t(p, ch) = L_t(p, ch) * (corr_ch / (double)n);  else L_t(p, ch) stays
+ * All of pass A of an iteration comes before its pass B.  After `iters` iterations out = L, stored as papof_interp_tensor
+ * stores (float64 as is, float32 with one round-to-nearest, uint8 = clamp(rint(255 * L), 0, 255), half to even, NaN: 0), and
+ * support = the n of the last iteration.  Pass B is the gather form of the adjoint: exact where the velocity is locally
+ * constant, wrong at motion boundaries.  A target reads only the recorded frames and its own L: any grouping of the targets
+ * gives the same bytes.
+ * Known answers: n_samples = 1 with offset 0, weight 1 and R = 0 returns finite frames whose values are 0 or >= EPS as they
+ * are (every ratio is then b / b = 1.0 or 0.0 / EPS), whatever the flows; zero flows, R = 0 and uint8 frames return the same
+ * bytes for any table; flows that are all NaN return store(fmax(frames, 0)) with support 0.
+ *
+ * Workspace (the caller's, device memory, as papof_super_resolve_tensor's): one target takes P = 8 * C * H * W * (2 R + 2)
+ * bytes -- its L and its 2 R + 1 ratio images in float64, pixel-major with the channels contiguous; the chains are recomputed
+ * in every pass, nothing else is kept.  The call runs the targets in rounds of G = min(T, workspace_bytes / P).
+ * papof_deblur_workspace returns min(T, max(1, 2 GiB / P)) * P, or -1 for sizes the call refuses.
+ * What it is not: the shutter (the table) is the caller's, it is not estimated; one straight line per pixel and frame -- a
+ * path that curves inside the exposure is modelled only through the neighbours; no prior or regulariser: ringing and noise
+ * grow with the iterations; a steady pan, where every frame has the same blur, gains little.
+ * Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor (support aside) or data pointer, frames or out that
+ * are not uint8 / float32 / float64, flows that are not float32 / float64, a support that is not uint8, a negative stride, a
+ * zero stride of out or support, n_frames < 2, height or width < 1, c outside 1 .. 4, height * width >= 2^30, radius outside
+ * 0 .. 4, iters outside 1 .. 256, alphas that are negative or not finite, n_samples outside 1 .. 64, offsets or weights NULL,
+ * an offset that is not 0 and not of a magnitude in [2^-20, 1 - 2^-20] (a NaN included), a weight that is negative or not
+ * finite, a sum of weights that is not > 0 or not finite, a workspace that is NULL or smaller than P. */
+int papof_deblur_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                        const papof_tensor* flow_fw, const papof_tensor* flow_bw, int n_samples, const double* offsets,
+                        const double* weights, int radius, int iters, int use_check, double alpha1, double alpha2,
+                        const papof_tensor* out, const papof_tensor* support, void* workspace, long long workspace_bytes,
+                        void* stream);
+long long papof_deblur_workspace(int n_frames, int height, int width, int c, int radius);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -83,6 +83,7 @@ SYMBOLS = [
     "papof_defect_detect_tensor", "papof_mask_dilate_tensor",
     "papof_deinterlace_tensor",
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
+    "papof_deblur_tensor", "papof_deblur_workspace",
 ]
 
 
@@ -319,6 +320,11 @@ def load():
     L.papof_rs_rectify_tensor.restype = c_int
     L.papof_rs_flow_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, c_double, c_double, c_int, _T, _T, c_void_p]
     L.papof_rs_flow_tensor.restype = c_int
+    L.papof_deblur_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_int, _D, _D, c_int, c_int, c_int, c_double,
+                                      c_double, _T, _T, c_void_p, ctypes.c_longlong, c_void_p]
+    L.papof_deblur_tensor.restype = c_int
+    L.papof_deblur_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    L.papof_deblur_workspace.restype = ctypes.c_longlong
     L.papof_temporal_consistency_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, _T,
                                                     c_double, c_double, c_int, c_int, c_double, c_double, _T, c_void_p,
                                                     ctypes.c_longlong, c_void_p]

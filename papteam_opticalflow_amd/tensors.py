@@ -191,6 +191,15 @@ near half the frame rate is not recovered; the end frames use a line; dead pixel
 
     rv = rectify_video(frames, 5, 0.8, layout="NHWC")   # rv.video, rv.valid, rv.flow_fw, rv.flow_bw, rv.occlusion
 
+Deblurring: `deblur` (include/papof.h: papof_deblur_tensor) is the inverse of motion_blur for footage whose shutter was open
+while the camera shook -- multi-frame Richardson-Lucy deconvolution with a line kernel per pixel from the flows: each
+iteration blurs a frame's estimate as the frames around it would have recorded it, divides the recorded frames by that and
+multiplies the estimate by the mean of the ratios blurred backwards, two HIP kernels per iteration; `deblur_video` computes
+the flows first (flow_video_fb), optionally again on its own result.  The shutter is the caller's; much under shake, little
+under a steady pan; few iterations, no prior.
+
+    dv = deblur_video(frames, 4, shutter=0.5, layout="NHWC")   # dv.video: the frames' shape, dv.support (T, H, W) uint8
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -231,6 +240,8 @@ Rectified = collections.namedtuple("Rectified", "video valid flow_fw flow_bw occ
 StabilizedRS = collections.namedtuple("StabilizedRS", "video valid transforms motion ok flow_fw flow_bw occlusion timing")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
 Blurred = collections.namedtuple("Blurred", "video flow_fw flow_bw occlusion timing")
+Deblurred = collections.namedtuple("Deblurred", "video support")
+DeblurredVideo = collections.namedtuple("DeblurredVideo", Deblurred._fields + ("flow_fw", "flow_bw", "occlusion", "timing"))
 RefinedFlows = collections.namedtuple("RefinedFlows", "flow_fw flow_bw occlusion")
 MODELS = {"similarity": capi.MOTION_SIMILARITY, "affine": capi.MOTION_AFFINE}
 
@@ -1596,6 +1607,96 @@ def blur_video(frames, pyramidLevels, *, shutter=0.5, samples=16, phase=-0.5, sh
     occ = fb.occlusion.view(torch.uint8) if fb.occlusion is not None else None
     video = _blur(ts, descs, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), occ, schedule, layout, out_dtype)
     return Blurred(video, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
+
+
+MAX_DEBLUR_RADIUS = 4  # include/papof.h: papof_deblur_tensor
+MAX_DEBLUR_ITERS = 256
+MAX_DEBLUR_PASSES = 8
+DEBLUR_ITERS = 6  # tests/test_deblur_cpu.py: with exact flows the gain peaks at 5 .. 6 iterations and falls behind them
+
+
+def _check_deblur(radius, iters):
+    return _int_in("radius", radius, 0, MAX_DEBLUR_RADIUS), _int_in("iters", iters, 1, MAX_DEBLUR_ITERS)
+
+
+def _deblur(ts, descs, flows, codes, schedule, radius, iters, alphas, layout, out_dtype):
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    offsets, weights = schedule
+    out, d_out = _new_frames(T, H, W, C, layout, out_dtype, dev)
+    support = torch.empty((T, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_f = [_flow_struct(f, c) for f, c in zip(flows, codes)]
+    d_sup = _struct(support, (support.stride(0), support.stride(1), support.stride(2), 1), capi.DTYPE_U8)
+    n = len(offsets)
+    _launch(dev, "papof_deblur_tensor", T, H, W, C, ctypes.byref(d_in), ctypes.byref(d_f[0]), ctypes.byref(d_f[1]), n,
+            (ctypes.c_double * n)(*offsets), (ctypes.c_double * n)(*weights), radius, iters, *alphas, ctypes.byref(d_out),
+            ctypes.byref(d_sup),
+            workspace=("papof_deblur_workspace", (T, H, W, C, radius),
+                       "%d frames of %d x %d x %d are too large to deblur" % (T, H, W, C)))
+    return Deblurred(out, support)
+
+
+def deblur(frames, flow_fw, flow_bw, *, shutter=0.5, samples=16, phase=-0.5, shape="box", radius=1, iters=DEBLUR_ITERS,
+           consistency=CONSISTENCY, layout="NCHW", out_dtype=None):
+    """Deblurring of a video of T >= 2 frames along its flows -- the inverse of motion_blur, for footage whose shutter was
+    open while the camera shook: frames (T, C, H, W) or (T, H, W, C) by `layout`, C = 1 .. 4, uint8 (read as x / 255),
+    float32 or float64, any strides, on a HIP device; flow_fw, flow_bw (T - 1, 2, H, W) float32 / float64 on the same device,
+    pair t from frame t to t + 1 and back, as flow_video_fb returns them.
+    It is multi-frame Richardson-Lucy deconvolution (Richardson 1972, Lucy 1974; along motion paths Tai, Tan and Brown 2011;
+    for video Kim and Lee 2015).  Every frame is taken to be the scene averaged over the times of blur_schedule(shutter,
+    samples, phase, shape) along a straight line per pixel, its velocity -- half the difference of the forward and the
+    backward flow -- times the sample's time.  Each of the `iters` (1 .. 256) iterations blurs the current estimate of a
+    frame as each of the frames t, t +- 1 .. t +- radius (radius 0 .. 4) would have recorded it -- carried there along the
+    chain of flows, hop by hop as temporal_filter does, a chain ending where it leaves the image or fails consistency =
+    (alpha1, alpha2) (None: no check) --, divides the recorded frames by that, and multiplies the estimate by the mean over
+    the frames of the ratios blurred backwards.  Two HIP kernels per iteration, fp64, bitwise reproducible.
+    Measured on a shaking camera (tests/test_deblur_cpu.py: 7 frames, shutter 0.5, speeds of 2 .. 7 pixels per frame, uint8)
+    with exact flows: 25.6 dB blurred, 36.4 dB after 6 iterations with radius 1, 40.0 dB with radius 2 and 26.8 dB with
+    radius 0; with flows estimated on the blurred frames 30.7 dB.  The iterations are few on purpose: there is no prior, and
+    beyond the default the result gets worse again (34.3 dB at 12).
+    What it is not: the shutter is given, not estimated; one straight line per pixel and frame, so a path that curves inside
+    the exposure is modelled only through the neighbours; the backward blur reads the velocity where it lands (the gather
+    adjoint), which is wrong at motion boundaries; a steady pan, where every frame carries the same blur, gains little
+    (2.6 dB at 8 iterations); ringing and noise grow with the iterations and there is no regulariser; the flows come from
+    blurred frames.
+    Returns Deblurred(video in `layout` and out_dtype -- uint8 as clamp(rint(255 x), 0, 255), float32 or float64; by default
+    the frames' dtype --, support (T, H, W) uint8: the number of frames that entered a pixel's last update).
+    include/papof.h (papof_deblur_tensor) states the rule exactly.  The workspace comes from PyTorch's allocator; enqueued
+    on the current stream, returns without waiting."""
+    alphas = _alphas(consistency)
+    schedule = blur_schedule(shutter, samples, phase, shape)
+    radius, iters = _check_deblur(radius, iters)
+    ts, descs, out_dtype, _ = _check_video(frames, layout, 1, out_dtype)
+    (T, H, W, C), _, _ = descs[0]
+    codes = _check_flows(flow_fw, flow_bw, (T - 1, 2, H, W), ts[0].device)
+    return _deblur(ts, descs, (flow_fw, flow_bw), codes, schedule, radius, iters, alphas, layout, out_dtype)
+
+
+def deblur_video(frames, pyramidLevels, *, passes=1, shutter=0.5, samples=16, phase=-0.5, shape="box", radius=1,
+                 iters=DEBLUR_ITERS, consistency=CONSISTENCY, layout="NCHW", out_dtype=None, **solver):
+    """A video of T >= 2 frames deblurred along its motion, `passes` (1 .. 8) passes: pass 0 is flow_video_fb(frames,
+    pyramidLevels, layout=layout, consistency=consistency, out_dtype=torch.float64, **solver) followed by deblur on those
+    flows; every later pass estimates the flows again on the previous pass's video -- sharper frames, better flows -- and
+    runs deblur on the ORIGINAL frames with them (restore_video's pattern).  Returns DeblurredVideo(video, support, flow_fw,
+    flow_bw (T - 1, 2, H, W) float64, occlusion and timing of the last flow call).  Every argument error raises before
+    anything is launched; the flows are complete on return, the video is enqueued on the current stream behind them."""
+    torch = _torch()
+    alphas = _alphas(consistency)
+    passes = _int_in("passes", passes, 1, MAX_DEBLUR_PASSES)
+    schedule = blur_schedule(shutter, samples, phase, shape)
+    radius, iters = _check_deblur(radius, iters)
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
+    T = descs[0][0][0]
+    codes = (capi.DTYPE_F64, capi.DTYPE_F64)
+    d = None
+    for k in range(passes):
+        src = ts if d is None else [d.video]
+        fb = _run_fb(src, [descriptor(src[0], layout)], True, T - 1, layout, torch.float64, pyramidLevels, alphas, params)
+        d = _deblur(ts, descs, (fb.flow_fw, fb.flow_bw), codes, schedule, radius, iters, alphas, layout,
+                    out_dtype if k == passes - 1 else ts[0].dtype)
+    return DeblurredVideo(d.video, d.support, fb.flow_fw, fb.flow_bw, fb.occlusion, fb.timing)
 
 
 MAX_RELAX = 65536  # include/papof.h: papof_fill_holes_tensor
