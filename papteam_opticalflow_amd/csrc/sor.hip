@@ -39,16 +39,18 @@
 //       lane l is, factor for factor, the left term wL*duL lane l-1 forms in the same step (lane l-1 is one column
 //       ahead: its left cell is lane l's upper cell), so the two PRODUCTS cross the wave, not their three factors: per
 //       step 26 fp64 operations and 8 DPP dword moves (4 for the two products, 4 for down-old) instead of 28 and 10;
-//     * every load is issued R = 8 steps before its use (register software pipeline; 5 memory operations per step
-//       keep R <= 12 within gfx9's 6-bit vmcnt);
+//     * every load is issued R = 8 steps before its use -- (phi, xy) and the unknowns R - 1 steps: their slot hands the
+//       left weight and the next centre to the following step and is refilled after that, its last, use (register
+//       software pipeline; 5 memory operations per step keep R <= 12 within gfx9's 6-bit vmcnt);
 //     * all nb * n_sor tasks are launched at once (one 64-thread workgroup each; a few hundred waves, all
 //       co-resident) and pipeline through per-task progress counters (one 128-byte line each).  Before issuing the
-//       loads of steps < e a task waits for
+//       unknowns' loads of steps < e (unknowns_end() below) a task waits for
 //           prog[k-1][b]   >= min(NS, e)          own band, previous sweep (its step s wrote what our step s reads)
 //           prog[k][b-1]   >= min(NS, e + 63)     band above, this sweep (ghost lane 0)
 //           prog[k-2][b+1] >= min(NS, e - 62)     band below, two sweeps ago (write-after-read of our block)
 //       A waiter only ever waits on lower block indices.  tests/sim_sor_wave.py executes this exact dataflow under
-//       a random scheduler and is checked bit-for-bit against the oracle on the CPU;
+//       a random scheduler and is checked bit-for-bit against the oracle on the CPU (tests/sim_sor_carry.py: the order
+//       in which the steps issue their loads today, on planes whose stores show only once they are published);
 //     * cross-workgroup visibility follows MI355X guide G16/R1: du/dv are stored write-through (`sc1`) and read with
 //       `sc1` loads; a counter only ever advertises steps whose stores are PROVEN complete -- by marker loads that
 //       retire (vmcnt is in order) after them, twice per R steps without draining the pipeline, and by a final
@@ -240,12 +242,16 @@ __device__ __forceinline__ D2 sor_cell(double wl, double duL, double dvL, double
     return D2{duN, dvN};
 }
 
-// Operands of R consecutive steps held in registers: slot t of the running iteration is consumed by step
-// i*R + t and immediately refilled with the operands of step (i+1)*R + t, i.e. every global load is issued
-// R steps before its use, so the latency of the write-through du/dv traffic and of the coefficient streams is
-// hidden behind R steps of arithmetic.  A step costs 4 loads + 2 stores; R <= 9 keeps the operations in
-// flight within the 6-bit vmcnt range (63) of gfx9.  (Per step of k_sor_exact<8>'s loop the wave issues ~39 vector
-// instructions -- 26 fp64, 8 DPP moves, 3 moved() -- and 81 in k_sor_fused<8>'s: profiles/step_products_isa.txt.)
+// Operands of R consecutive steps held in registers: slot t of the running iteration is consumed by step i*R + t.
+// Its (a1, a2) and (b1, b2) are dead then and refilled at once with those of step (i+1)*R + t, R steps before their
+// use.  Its phi and (du, dv) serve ONE MORE step -- the centre weight is the next step's left weight, right-old the next
+// centre -- so (phi, xy) and (du, dv) are refilled at the end of step i*R + t + 1, after their last use, with the operands
+// of step (i+1)*R + t: R - 1 steps before their use.  No value outlives its slot, so none is copied out of one (the
+// three v_mov_b64 per step that did so are gone: profiles/slot_carry_isa.txt).  Slot R - 1 is carried into step 0 of the
+// next iteration and refilled there.  The latency of the write-through du/dv traffic and of the coefficient streams is
+// hidden behind R - 1 .. R steps of arithmetic.  A step costs 4 loads + 2 stores; R <= 9 keeps the operations in
+// flight within the 6-bit vmcnt range (63) of gfx9.  (Per step of k_sor_exact<8>'s loop the wave issues 36 vector
+// instructions -- 26 fp64, 8 DPP moves: profiles/slot_carry_isa.txt.)
 template <int R>
 struct Slots {
     u32x4 pa[R], pb[R], pc[R];  // (phi, xy) (a1, a2) (b1, b2) of this lane's cell at skew position s
@@ -274,19 +280,33 @@ struct BufAt {  // where one buffer access goes: per-lane byte offset (voffset) 
 struct LaneOffs {
     unsigned pa;     // (phi, xy) of this lane's cell at step s (64 consecutive rows of one skew position)
     unsigned pbc;    // (a1, a2) and (b1, b2)                     [ghosts: off -> 0 -> pass-through]
-    unsigned pd;     // (du, dv) right-old of step s: own block, previous parity, cell lane-1 [lane 0: block above]
+    unsigned pd;     // (du, dv) right-old of step s: own block, previous parity, cell lane-1 [lane 0: block above],
+                     // advanced by pd_lead positions (below)
     unsigned st;     // (du, dv) store of step s: own block, this parity, cell lane (ghosts store their pass-through)
     unsigned pos_c;  // bytes per coefficient skew position = hp * 16
     unsigned pos_d;  // bytes per (du, dv) position = nb * 1 KiB
     unsigned hs;     // SPLIT: store of step s into the inbox of the rank below (lane 62 of the band above a cut; else off)
-    __device__ __forceinline__ BufAt unknowns_at(int s) const { return BufAt{pd, (unsigned)s * pos_d}; }
+    // A step loads the unknowns of the step R - 1 ahead and stores its own result: both advance by pos_d per step and
+    // differ by a wave-uniform constant.  After the start-up loads lead_unknowns(R - 1) folds that constant into the
+    // per-lane offset, so that the load of step s + R - 1 and the store of step s share ONE running soffset, s * pos_d
+    // (one scalar add per step instead of two).  A lane that is switched off stays at kOob exactly: out of range with
+    // every soffset of the task.  A live lane's offset stays below 2 GiB (both parities together are, sor_solve).
+    int pd_lead = 0;
+    __device__ __forceinline__ void lead_unknowns(int steps) {
+        pd = pd == kOob ? kOob : pd + (unsigned)steps * pos_d;
+        pd_lead = steps;
+    }
+    __device__ __forceinline__ BufAt unknowns_at(int s) const { return BufAt{pd, (unsigned)(s - pd_lead) * pos_d}; }
 };
 
 // Loads of step s into slot t; Lane = LaneOffs, or the grouped kernel's GLane (other addressing of the unknowns)
 template <int R, int t, class Lane>
-__device__ __forceinline__ void load_coef(const Task& T, const Lane& L, int s, Slots<R>& c) {
-    const unsigned off = (unsigned)s * L.pos_c;  // wave-uniform byte offsets -> soffset
-    c.pa[t] = __builtin_amdgcn_raw_buffer_load_b128(T.ra, L.pa, off, kAuxPlain);
+__device__ __forceinline__ void load_phi(const Task& T, const Lane& L, int s, Slots<R>& c) {
+    c.pa[t] = __builtin_amdgcn_raw_buffer_load_b128(T.ra, L.pa, (unsigned)s * L.pos_c, kAuxPlain);  // wave-uniform -> soffset
+}
+template <int R, int t, class Lane>
+__device__ __forceinline__ void load_ab(const Task& T, const Lane& L, int s, Slots<R>& c) {
+    const unsigned off = (unsigned)s * L.pos_c;
     c.pb[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rb, L.pbc, off, kAuxPlain);
     c.pc[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rc, L.pbc, off, kAuxPlain);
 }
@@ -295,19 +315,36 @@ __device__ __forceinline__ void load_unknowns(const Task& T, const Lane& L, int 
     const BufAt at = L.unknowns_at(s);
     c.pd[t] = __builtin_amdgcn_raw_buffer_load_b128(T.rd, at.lane, at.uniform, kAuxSc1);
 }
+// The refills at the end of step s, whose slot is t (k_sor_exact, k_sor_group): (a1, a2) (b1, b2) of step s + R into
+// slot t, (phi, xy) and (du, dv) of step s + R - 1 into the slot of the PREVIOUS step, whose phi and (du, dv) this step
+// has just used for the last time (as left weight and centre).
 template <int R, int t, class Lane>
-__device__ __forceinline__ void load_slot(const Task& T, const Lane& L, int s, Slots<R>& c) {
-    load_coef<R, t>(T, L, s, c);
-    load_unknowns<R, t>(T, L, s, c);
+__device__ __forceinline__ void refill(const Task& T, const Lane& L, int s, Slots<R>& c) {
+    constexpr int tp = (t + R - 1) % R;
+    load_phi<R, tp>(T, L, s + R - 1, c);
+    load_ab<R, t>(T, L, s + R, c);
+    load_unknowns<R, tp>(T, L, s + R - 1, c);
 }
-// The start-up loads of a task: steps 0 .. R-1 into their slots
-template <int R, class Lane>
+// THE coverage bound of the unknowns' loads, stated once: step s issues the unknowns of step s + R - 1, so iteration i
+// (steps i R .. i R + R - 1) issues those of steps < (i + 2) R - 1, and the start-up (i = -1) those of steps < R - 1, after
+// the first centre (the right-old of "step -1").  wait_covered() turns the bound into the producers' progress; it is
+// exact -- one step fewer reads a cell before it is written (tests/sim_sor_carry.py runs this order on poisoned planes).
+template <int R>
+__device__ __forceinline__ constexpr int unknowns_end(int i) {
+    return (i + 2) * R - 1;
+}
+// The start-up loads of a task: the coefficients of steps 0 .. R-1 ((phi, xy): of the first NPHI steps) into their slots,
+// and the unknowns of steps 0 .. R-2: slot R - 1 receives its first operands at the end of step 0
+template <int R, int NPHI, class Lane>
 __device__ __forceinline__ void fill_coef(const Task& T, const Lane& L, Slots<R>& c) {
-    static_for<R>([&](auto t) __attribute__((always_inline)) { load_coef<R, t()>(T, L, t(), c); });
+    static_for<R>([&](auto t) __attribute__((always_inline)) {
+        if constexpr (t() < NPHI) load_phi<R, t()>(T, L, t(), c);
+        load_ab<R, t()>(T, L, t(), c);
+    });
 }
 template <int R, class Lane>
 __device__ __forceinline__ void fill_unknowns(const Task& T, const Lane& L, Slots<R>& c) {
-    static_for<R>([&](auto t) __attribute__((always_inline)) { load_unknowns<R, t()>(T, L, t(), c); });
+    static_for<R - 1>([&](auto t) __attribute__((always_inline)) { load_unknowns<R, t()>(T, L, t(), c); });
 }
 
 struct State {
@@ -333,24 +370,32 @@ __device__ __forceinline__ D2 wave_cell(const State& S, double om1, double nalph
                     pc.x, pc.y);  // (weights 1.0: the products are formed already)
 }
 
-// A value that outlives the operand slot it came from is MOVED out of the slot's registers (an opaque v_mov the
-// compiler cannot fold away).  Otherwise the slot's registers stay live across the refill, the refill lands in other
-// registers, and the loop-carried slots need register copies at the top of every iteration -- which the compiler
-// guards with `s_waitcnt vmcnt(0)`: a full drain of the software pipeline once per iteration.
+// No value may outlive the operand slot it came from: the slot's registers would stay live across the refill, the refill
+// would land in other registers, and the loop-carried slots would need register copies at the top of every iteration --
+// which the compiler guards with `s_waitcnt vmcnt(0)`: a full drain of the software pipeline once per iteration.  The
+// steps therefore refill a slot only after the last use of everything in it (Slots above); until that order was found
+// they copied the left weight and the next centre out of the slot with an opaque `v_mov_b64` each (moved(), gone).
 // A 16-byte store reads its data registers over more than one cycle: a VALU write of those registers needs two wait
 // states behind the store (gfx940+).  Nothing provides them here: the compiler's hazard recognizer does not look inside
-// inline-asm statements (the moves of moved() below, which it may schedule and register-allocate straight behind a
-// store), and it skips this hazard ALTOGETHER for buffer stores whose soffset is a register -- the form of every solver
-// store -- so compiler-generated VALU writes are unguarded at these stores as well.  Found in round 2: with a second wave on
+// inline-asm statements, and it skips this hazard ALTOGETHER for buffer stores whose soffset is a register -- the form
+// of every solver store -- so compiler-generated VALU writes are unguarded at these stores.  Found in round 2: with a second wave on
 // the SIMD the store can slip a cycle, and the write then overwrites data not yet read (wrong quads of lanes, only under
 // concurrency -- DESIGN.md 5.1).  Every store of the solver steps is therefore followed by store_data_guard(): two wait
 // states, whatever comes next; tools/scan_store_hazard.py checks the generated code of every build (csrc/Makefile).
 __device__ __forceinline__ void store_data_guard() { asm volatile("s_nop 1" ::: "memory"); }
-
-__device__ __forceinline__ double moved(double x) {
-    double y;
-    asm volatile("v_mov_b64 %0, %1" : "=v"(y) : "v"(x));
-    return y;
+// The wave kernels' steps pass the stored data THROUGH the guard and take their left-new results from what comes out.
+// The statement above orders memory operations only: the next step's first product is formed in place, in the data
+// registers, and without the moves that used to follow the guard the scheduler lifted that multiplication in front of
+// it, right behind the store (and then the arithmetic of half an iteration in front of its stores and refills).  As an
+// operand of the guard the data stays live, in its registers, until the wait states have passed, and the next step's
+// chain, which starts from the left-new results, starts behind this step's store.
+__device__ __forceinline__ D2 store_data_guard(u32x4 data) {
+    asm volatile("s_nop 1" : "+v"(data) : : "memory");
+    return as_d2(data);
+}
+// ... where the stored data is a selection (k_sor_fused): the first sweep's left-new results (x, y) pass through beside it
+__device__ __forceinline__ void store_data_guard(const u32x4& data, double& x, double& y) {
+    asm volatile("s_nop 1" : "+v"(x), "+v"(y) : "v"(data) : "memory");
 }
 
 template <int R, int t, bool DPP, bool SPLIT = false>
@@ -359,17 +404,18 @@ __device__ __forceinline__ void step(const ExactArgs& A, const Task& T, const La
     const D2 pa = as_d2(c.pa[t]), pb = as_d2(c.pb[t]), pc = as_d2(c.pc[t]), pd = as_d2(c.pd[t]);
     const double phiC = pa.x, duR = pd.x, dvR = pd.y;
     const D2 n = wave_cell<DPP>(S, om1, A.nalpha, pa, pb, pc, duR, dvR);
-    __builtin_amdgcn_raw_buffer_store_b128(as_u4(n.x, n.y), T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
+    const u32x4 out = as_u4(n.x, n.y);
+    __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     if (SPLIT)  // lane 62 of the band above a cut: the same cell into the inbox of the rank below (every other lane: off)
-        __builtin_amdgcn_raw_buffer_store_b128(as_u4(n.x, n.y), T.rd2, L.hs, (unsigned)s * L.pos_d, kAuxSc1);
-    store_data_guard();
-    S.duL = n.x;
-    S.dvL = n.y;
-    S.phiL = moved(phiC);
-    S.duC = moved(duR);
-    S.dvC = moved(dvR);
+        __builtin_amdgcn_raw_buffer_store_b128(out, T.rd2, L.hs, (unsigned)s * L.pos_d, kAuxSc1);
+    const D2 left = store_data_guard(out);
+    S.duL = left.x;
+    S.dvL = left.y;
+    S.phiL = phiC;  // these three stay in slot t, which the NEXT step refills after it has used them
+    S.duC = duR;
+    S.dvC = dvR;
     asm volatile("" ::: "memory");  // keep this step's store ahead of its refill loads in the instruction stream
-    load_slot<R, t>(T, L, s + R, c);  // refill this slot for the step R ahead
+    refill<R, t>(T, L, s, c);
 }
 
 // Progress of the two producers of a task, polled together (a missing producer reads as "finished").
@@ -484,7 +530,7 @@ __device__ __forceinline__ unsigned plane_descriptors(const ExactArgs& A, Task& 
 
 // ---- one iteration = R steps of a task's software pipeline (k_sor_exact, k_sor_fused) ------------------------------
 // Every load must be covered by the producers' published progress before it is issued.  Iteration i issues the
-// loads of steps < (i + 2) R; its coverage check uses a poll that was itself issued one iteration earlier
+// unknowns' loads of steps < unknowns_end<R>(i); its coverage check uses a poll that was itself issued one iteration earlier
 // (consuming a poll forces an in-order vmcnt wait on every older load, so finer-grained polling stalls).
 // MARKER loads: a 4-byte load issued right after the store of some step retires (vmcnt is in order) only after
 // that store has completed, so consuming it a few steps later proves the step complete and lets the task
@@ -509,7 +555,7 @@ __device__ __forceinline__ void pipeline_iteration(const ExactArgs& A, const Dep
     constexpr int H = R / 2;
     constexpr int CA = H + DM - R, CB = DM;  // steps of the NEXT iteration after which markers A / B are consumed
     static_assert(CA >= 0 && CA < H && CB >= H && CB < R, "marker consumption points");
-    if (!wait_covered<OWN, UP, SELECTIVE>(A, P.pl, D, (i + 2) * R)) end_task();
+    if (!wait_covered<OWN, UP, SELECTIVE>(A, P.pl, D, unknowns_end<R>(i))) end_task();
     // The poll for the next iteration's check is consumed at the start of the next iteration, where it waits (in
     // order) for every load issued before it.  Issued in the middle of this iteration (MIDPOLL) it is half an iteration
     // fresher (a shorter hand-off) but then waits for the refills of the first half: at R >= 8 those are >= 4 steps old and long
@@ -622,12 +668,12 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
     Slots<R> c;
 
     // The coefficient operands depend on nobody: their first R steps are requested before the task waits.
-    // Start-up in two stages: the first R steps' unknowns are requested as soon as the producers cover THEM; the check
+    // Start-up in two stages: the first R - 1 steps' unknowns are requested as soon as the producers cover THEM; the check
     // for the next R steps (the refills of iteration 0) is made with a fresh poll at the start of iteration 0, while those
     // first loads are in flight -- a hand-off then costs R steps and one load latency less than waiting for 2R up front.
-    fill_coef(T, L, c);
+    fill_coef<R, R - 1>(T, L, c);
     Pipe P{poll(D), 0u, 0u};
-    if (!wait_covered<0, 63, true>(A, P.pl, D, R)) end_task();
+    if (!wait_covered<0, 63, true>(A, P.pl, D, unknowns_end<R>(-1))) end_task();
     {  // centre of the first cells = the right-old of "step -1" (lanes >= 1: left of column 0, zero; lane 0: position 63
        // of the block above)
         const unsigned first = (lane != 0 || L.pd == kOob) ? kOob : L.pd - L.pos_d;
@@ -637,6 +683,7 @@ __global__ __launch_bounds__(64) void k_sor_exact(ExactArgs A_in) {
     }
     if (dbg) dbg[1] = __builtin_amdgcn_s_memrealtime();
     fill_unknowns(T, L, c);
+    L.lead_unknowns(R - 1);
     P.pl = poll(D);
 
     // markers are consumed 4 / 5 / R - 3 steps after issue at depth 6 / 8 / >= 10 (see PAPOF_V_DM*)
@@ -693,11 +740,16 @@ struct FLane {       // per-lane constants of the fused kernel (VGPRs)
     bool own_block;  // lanes >= 2: the first sweep's operands come from the own block (lanes 0 / 1: from the band above)
 };
 
-template <int R, int t, bool DPP, bool SKIP2, bool ID2>
+// EARLY: the step's index in the task while that is < 3, else 3.  Steps 0 and 1 have no second sweep yet (every lane is
+// still left of column 0) and step 2 has no coefficient cells of "step -1" to replace.
+template <int R, int t, bool DPP, int EARLY, bool ID2>
 __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const LaneOffs& L, const FLane& F, int s,
                                        Slots<R>& c, State& S1, State& S2) {
     const double nalpha = A.nalpha;
+    constexpr bool SKIP2 = EARLY < 2;
     constexpr int t2 = (t + R - 2) % R;  // slot holding the coefficient cells of step s - 2
+    constexpr int t3 = (t + R - 3) % R;  // ... of step s - 3: its phi was this step's second-sweep left weight
+    constexpr int tp = (t + R - 1) % R;  // ... the unknowns of step s - 1: this step's first-sweep centre
     // ---- second sweep, column s - l - 2: operands are the first sweep's results of steps s - 2 (centre) and s - 1
     const double duR2 = S1.duL, dvR2 = S1.dvL;
     double duN2, dvN2;
@@ -708,16 +760,16 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
         // ID2 -- the identity second sweep of the LAST pair of an odd sweep count -- is the same arithmetic with (a1, a2)
         // masked to zero and 1 - omega -> 1 (F.om1b, set by the kernel): the exact pass-through the ghost lanes use.  (A
         // shortcut that simply forwarded the first sweep's results two steps later returned wrong quads of lanes whenever
-        // OTHER kernels ran on the chip at the same time: in its loop the compiler had placed the inline-asm moves of
-        // moved() straight behind the 16-byte stores, into the stores' data registers -- the hazard store_data_guard() now
-        // closes for every variant.  The shortcut saved nothing that matters and stays out.)
+        // OTHER kernels ran on the chip at the same time: in its loop the compiler had placed the inline-asm moves the
+        // steps then had straight behind the 16-byte stores, into the stores' data registers -- the hazard
+        // store_data_guard() now closes for every variant.  The shortcut saved nothing that matters and stays out.)
         const D2 qa = as_d2(c.pa[t2]), qc = as_d2(c.pc[t2]);
         const u32x4 qbm = ID2 ? (c.pb[t2] & u32x4{0u, 0u, 0u, 0u}) : c.pb[t2];
         const D2 qb = as_d2(qbm);
         const D2 n2 = wave_cell<DPP>(S2, F.om1b, nalpha, qa, qb, qc, duR2, dvR2);
         duN2 = n2.x;
         dvN2 = n2.y;
-        S2.phiL = moved(qa.x);
+        S2.phiL = qa.x;  // stays in slot t2's (phi, xy), refilled a step later than its (a, b) cells
     }
     // ---- first sweep, column s - l (as k_sor_exact::step, with the per-lane ghost mask on (a1, a2))
     const D2 pa = as_d2(c.pa[t]), pc = as_d2(c.pc[t]), pd = as_d2(c.pd[t]);
@@ -727,24 +779,26 @@ __device__ __forceinline__ void f_step(const ExactArgs& A, const Task& T, const 
     const D2 n1 = wave_cell<DPP>(S1, F.om1a, nalpha, pa, pb, pc, duR, dvR);
     const double duN = n1.x, dvN = n1.y;
     const double o1 = F.first_out ? duN : duN2, o2 = F.first_out ? dvN : dvN2;
-    __builtin_amdgcn_raw_buffer_store_b128(as_u4(o1, o2), T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
-    store_data_guard();
+    const u32x4 out = as_u4(o1, o2);
+    __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     S2.duL = duN2;
     S2.dvL = dvN2;
     S2.duC = duR2;
     S2.dvC = dvR2;
     S1.duL = duN;
     S1.dvL = dvN;
-    S1.phiL = phiC;  // its slot lives two more steps
-    S1.duC = moved(duR);
-    S1.dvC = moved(dvR);
+    store_data_guard(out, S1.duL, S1.dvL);
+    S1.phiL = phiC;  // its slot lives three more steps
+    S1.duC = duR;    // stay in slot t's (du, dv), which the next step refills after it has used them
+    S1.dvC = dvR;
     asm volatile("" ::: "memory");  // keep this step's store ahead of its refill loads in the instruction stream
-    load_unknowns<R, t>(T, L, s + R, c);
-    if (!SKIP2) load_coef<R, t2>(T, L, s - 2 + R, c);  // the slot of step s - 2 is free now
+    load_unknowns<R, tp>(T, L, s + R - 1, c);
+    if (EARLY >= 3) load_phi<R, t3>(T, L, s - 3 + R, c);  // the second sweep has used the phi of step s - 3 for the last time
+    if (!SKIP2) load_ab<R, t2>(T, L, s - 2 + R, c);       // ... and the (a, b) cells of step s - 2
 }
 
 template <int R, bool DPP, bool ID2>
-__device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, const LaneOffs& L, const FLane& F,
+__device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, LaneOffs L, const FLane& F,
                                       const Deps& D, unsigned my_prog) {
     const int ns = A.ns;
     const int n_iter = (ns + R - 1) / R;
@@ -752,9 +806,9 @@ __device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, const L
     S1.duL = S1.dvL = S1.phiL = 0.0;
     S2.duL = S2.dvL = S2.phiL = S2.duC = S2.dvC = 0.0;
     Slots<R> c;
-    fill_coef(T, L, c);
+    fill_coef<R, R>(T, L, c);
     Pipe P{poll(D), 0u, 0u};
-    if (!wait_covered<1, 64, PAPOF_V_FSELECTIVE>(A, P.pl, D, R)) end_task();  // staged start-up, see k_sor_exact
+    if (!wait_covered<1, 64, PAPOF_V_FSELECTIVE>(A, P.pl, D, unknowns_end<R>(-1))) end_task();  // staged start-up, see k_sor_exact
     {  // centre of the first cells = the right operand of "step -1" (lanes >= 2: left of column 0, zero)
         const unsigned first = (F.own_block || L.pd == kOob) ? kOob : L.pd - L.pos_d;
         const D2 c0 = as_d2(__builtin_amdgcn_raw_buffer_load_b128(T.rd, first, 0, kAuxSc1));
@@ -762,13 +816,14 @@ __device__ __forceinline__ void f_run(const ExactArgs& A, const Task& T, const L
         S1.dvC = c0.y;
     }
     fill_unknowns(T, L, c);
+    L.lead_unknowns(R - 1);
     P.pl = poll(D);
     constexpr int DM = R == 6 ? PAPOF_V_FDM6 : (R == 8 ? PAPOF_V_FDM8 : R - 3);  // see PAPOF_V_FDM*
     const auto iteration = [&](int i, auto first) {
         pipeline_iteration<R, DM, R >= PAPOF_V_FMIDPOLL, 1, 64, PAPOF_V_FSELECTIVE>(
             A, D, S1, P, i, first(),
-            [&](auto t, int s0) __attribute__((always_inline)) {  // in steps 0 and 1 of the task there is no second sweep yet
-                f_step<R, t(), DPP, first() && t() < 2, ID2>(A, T, L, F, s0 + t(), c, S1, S2);
+            [&](auto t, int s0) __attribute__((always_inline)) {  // the task's first three steps: see f_step (EARLY)
+                f_step<R, t(), DPP, (first() && t() < 3) ? t() : 3, ID2>(A, T, L, F, s0 + t(), c, S1, S2);
             },
             [&](unsigned steps) __attribute__((always_inline)) { publish(T, my_prog, steps); });
     };
@@ -902,14 +957,14 @@ __device__ __forceinline__ void g_step(const GroupArgs& A, const Task& T, const 
     else
         __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.st, (unsigned)s * L.pos_d, kAuxSc1);
     __builtin_amdgcn_raw_buffer_store_b128(out, T.rd, L.hs + (unsigned)s * 16u, 0, kAuxSc1);  // lane 62 -> halo row
-    store_data_guard();
-    S.duL = n.x;
-    S.dvL = n.y;
-    S.phiL = moved(phiC);  // see moved(): no slot register may stay live across its refill
-    S.duC = moved(duR);
-    S.dvC = moved(dvR);
+    const D2 left = store_data_guard(out);
+    S.duL = left.x;
+    S.dvL = left.y;
+    S.phiL = phiC;  // as in step(): they stay in slot t (LDS-fed lanes: the centre is the value selected above), which
+    S.duC = duR;    // the next step refills after it has used them
+    S.dvC = dvR;
     asm volatile("" ::: "memory");
-    load_slot<R, t>(T, L, s + R, c);
+    refill<R, t>(T, L, s, c);
 }
 
 // steps T0 .. T1-1 of the unrolled iteration that starts with step s0 (a function of its own: the same static_for written
@@ -979,9 +1034,9 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
 
     unsigned long long t_cov = 0, t_in = 0, t_out = 0, t_start = 0;
     const bool dbg = A.dbg != nullptr;
-    fill_coef(T, L, c);
+    fill_coef<R, R - 1>(T, L, c);
     Polls pl = poll(W.D);
-    if (!wait_covered<1, 63>(X, pl, W.D, 2 * R)) return give_up();
+    if (!wait_covered<1, 63>(X, pl, W.D, unknowns_end<R>(0))) return give_up();  // start-up and iteration 0 at once
     if (dbg) t_start = __builtin_amdgcn_s_memtime();
     {  // centre of the first cells: position 0 (zero; LDS-fed lanes: the same zero), lane 0: halo position 63
         const unsigned first = L.pd == kOob ? kOob : L.pd - L.pd_step;
@@ -1026,7 +1081,7 @@ __device__ __forceinline__ void g_run_wave(const GroupArgs& A, const Task& T, co
     unsigned ma = 0u, mb = 0u;
     const auto iteration = [&](int i, bool first) -> bool {
         const unsigned long long tc = dbg ? __builtin_amdgcn_s_memtime() : 0;
-        if (!first && !wait_covered<1, 63>(X, pl, W.D, (i + 2) * R)) return false;
+        if (!first && !wait_covered<1, 63>(X, pl, W.D, unknowns_end<R>(i))) return false;
         if (dbg) t_cov += __builtin_amdgcn_s_memtime() - tc;
         const Polls pn = poll(W.D);
         const int s0 = i * R;

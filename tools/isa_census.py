@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Static census of kernels in a saved gfx950 device assembly (.s of -save-temps): instructions by kind, registers, scratch.
 usage: isa_census.py kernels-hip-amdgcn-amd-amdhsa-gfx950.s [name-substring ...]   (default substring: k_flow_system)
+       isa_census.py --loops sor-hip-amdgcn-amd-amdhsa-gfx950.s [name-substring ...]    (default substring: k_sor_)
+           the sweep loops of the solver kernels (label .. backward branch, at least 4 vector-memory stores): instructions by
+           class, scalar ones included, and the s_waitcnt vmcnt(N) values in program order (profiles/slot_carry_isa.txt)
 The counts are static (every instruction of the kernel's text once), not what a thread executes."""
 import re
 import subprocess
@@ -82,7 +85,54 @@ def census(body):
     return c
 
 
+def loops(text, min_stores=4):
+    """The loops of a kernel's text (label .. backward branch to it) that hold at least min_stores vector-memory stores -- the
+    sweep loops of the solver kernels -- as lists of instructions, in program order of their closing branch."""
+    labels, body, out = {}, [], []
+    for ln in text:
+        s = ln.split(";")[0].strip()
+        if not s or s.startswith((".", "//")) and not s.endswith(":"):
+            continue
+        if s.endswith(":"):
+            labels[s[:-1]] = len(body)
+            continue
+        body.append(s)
+        m = re.match(r"s_c?branch\w*\s+(\S+)", s)
+        if m and m.group(1) in labels:
+            rng = body[labels[m.group(1)]:]
+            if sum(1 for i in rng if re.match(r"(buffer|global|flat)_store", i)) >= min_stores:
+                out.append(rng)
+    return out
+
+
+def loop_census(rng):
+    op = [i.split()[0] for i in rng]
+    return dict(stores=sum(o.startswith(("buffer_store", "global_store")) for o in op),
+                loads=sum(o.startswith(("buffer_load", "global_load")) for o in op),
+                valu=sum(o.startswith("v_") for o in op),
+                f64=sum(bool(re.search(r"_f64($|_)", o)) for o in op),
+                dpp=sum("dpp" in i or " wave_sh" in i for i in rng),
+                mov64=sum(o == "v_mov_b64" for o in op),
+                salu=sum(o.startswith("s_") and o not in ("s_waitcnt", "s_nop") for o in op),
+                s_add=sum(o.startswith(("s_add_", "s_addk_")) for o in op),
+                s_nop=sum(o == "s_nop" for o in op),
+                vmcnt=[int(m.group(1)) for i in rng for m in [re.search(r"vmcnt\((\d+)\)", i)] if m])
+
+
 def main():
+    if sys.argv[1] == "--loops":  # isa_census.py --loops file.s [name-substring ...]: the sweep loops, by instruction class
+        ks = kernels(sys.argv[2])
+        names = [n for n in ks if any(p in n for p in (sys.argv[3:] or ["k_sor_"]))]
+        dm = demangle(names)
+        for n in sorted(names, key=lambda n: dm[n]):
+            print(dm[n].replace("papof::(anonymous namespace)::", "").replace("void ", "").split("(")[0],
+                  "  VGPRs %s  scratch %s B" % (ks[n].get("vgpr", "?"), ks[n].get("scratch", "?")))
+            for j, rng in enumerate(loops(ks[n]["text"])):
+                c = loop_census(rng)
+                print("   loop %d: stores %2d loads %3d VALU %4d (f64 %4d, dpp %3d, v_mov_b64 %2d) scalar %3d (s_add %2d) s_nop %2d"
+                      "  vmcnt seq %s" % (j, c["stores"], c["loads"], c["valu"], c["f64"], c["dpp"], c["mov64"], c["salu"],
+                                          c["s_add"], c["s_nop"], c["vmcnt"]))
+        return
     path, pats = sys.argv[1], sys.argv[2:] or ["k_flow_system"]
     ks = kernels(path)
     names = [n for n in ks if any(p in n for p in pats)]

@@ -6,7 +6,8 @@ build of every translation unit, and by tests/test_codegen_hazards.py.
 Why a scanner: gfx940+ needs software wait states between certain pairs of instructions.  The compiler's hazard
 recognizer inserts them for pairs of ITS OWN instructions, with two holes that matter here:
   * an inline-asm statement is opaque to it: it neither sees what the statement writes nor what it reads -- sor.hip's
-    software pipeline uses inline-asm `v_mov_b64` (moved()) and EXEC-narrowed LDS writes;
+    software pipeline uses inline-asm store guards and EXEC-narrowed LDS writes (and, until its slots carried the left
+    weight and the next centre, an inline-asm `v_mov_b64` for every value that outlived its slot);
   * it skips the store-data hazard for buffer stores that carry their step offset in an SGPR soffset -- exactly the form
     of every solver store (sor.hip) -- so there even compiler-generated VALU writes are unguarded.  Round 2 found that
     hazard to be real on MI355X (wrong quads of lanes whenever a second wave shared the SIMD): every
