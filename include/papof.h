@@ -1871,6 +1871,44 @@ int papof_deblur_tensor(papof_handle* h, int n_frames, int height, int width, in
                         void* stream);
 long long papof_deblur_workspace(int n_frames, int height, int width, int c, int radius);
 
+/* The projective warp with one matrix per SOURCE row (rows.hip: k_warp_rows): rotation-path stabilization of a camera with a
+ * rolling shutter.  A camera that rotates by R(tau) and reads source row y of frame t at the time t + readout * (y - a) / H
+ * sends the stabilized camera's pixel q to K R(t + tau(y)) S^T K^-1 q, y the row that point lands in (Forssen and Ringaby
+ * 2010; Karpenko et al. 2011): a homography per source row, sampled by the caller at n_knots rows, and a fixed-point solve for
+ * the landing row.  The call is papof_warp_projective_tensor with these differences: matrices is a TABLE, float32 (widened
+ * exactly) or float64, indexed (frame, knot, row, column) -- n_knots = Kn >= 1 matrices of 3 x 3 per frame, any non-negative
+ * strides, stride[1] between a frame's knots --; for Kn >= 2 knot k belongs to source row k * (H - 1) / (Kn - 1); and `iters`
+ * in 1 .. 8 is the number of fixed-point iterations.  In fp64 in the stated order without fused multiply-adds, output pixel
+ * (x, r) of frame i:
+ *   Kn == 1:  M = knot 0; D, Nx, Ny, X = Nx / D, Y = Ny / D of PROJECTIVE SAMPLING above.  No iteration is run and iters is not
+ *             read: the call returns the bytes of papof_warp_projective_tensor on (frame, row, column) = the table without
+ *             its knot axis.
+ *   Kn >= 2:  Y_0 = (double)r;  g = (double)(Kn - 1) / (double)(H - 1)  (one division).  For j = 0 .. iters - 1:
+ *     clamp    Yc = Y_j if 0 <= Y_j <= H - 1;  Yc = +0.0 if !(Y_j >= 0) (a NaN goes here);  Yc = (double)(H - 1) if Y_j > H - 1
+ *     index    s = Yc * g;  k = (int)s, and k = Kn - 2 if k > Kn - 2;  f = s - (double)k
+ *     lerp     m_ab = A_ab + f * (B_ab - A_ab) for the nine entries, A = knot k, B = knot k + 1
+ *     project  D = (m20 * x + m21 * r) + m22;  Nx = (m00 * x + m01 * r) + m02;  Ny = (m10 * x + m11 * r) + m12
+ *     update   X = Nx / D;  Y_(j+1) = Ny / D     (two divisions, as in the projective rule)
+ *   The last iteration's X, Y = Y_iters and D decide: inside iff D > 0 and 0 <= X <= W - 1 and 0 <= Y <= H - 1 (every comparison
+ *   false for a NaN).  An earlier iterate may leave the frame, be a NaN or have D <= 0: only the clamp sees it.
+ * From (X, Y) on, the taps, the sampler, the stores, valid, and the 0 where the pixel is not inside are
+ * papof_warp_projective_tensor's.  A table whose knots are all equal gives the bytes of Kn == 1 unless an entry is -0.0
+ * (A + f * 0.0 is A for every other finite A).  The (int) conversion sees only a clamped s that is not a NaN, and k is clamped
+ * before an address is formed: no table, however hostile, is read out of bounds.
+ * One lane makes one output pixel on papof_warp_affine_tensor's 64 x 4 tiling, its iterate in registers; no device memory
+ * besides the tensors, no atomics; bitwise reproducible.  Enqueued on `stream` (the caller's hipStream_t on the handle's
+ * device, NULL: the null stream) and returns without waiting.
+ * What it is not: the table is the caller's (tensors.rotation_rows makes it from rotations); between knots the matrix is
+ * interpolated entry by entry, not on the rotation group; pixels that are not inside are not filled.
+ * PAPOF_EINVAL, before anything is enqueued: papof_warp_projective_tensor's list (a NULL handle, descriptor -- valid aside --
+ * or data pointer, frames or out that are not uint8 / float32 / float64, a valid that is not uint8, a zero stride of an
+ * output, n_frames, height, width or c < 1), n_knots < 1 or > PAPOF_ROWS_MAX_KNOTS, n_knots > 1 with height < 2, iters outside
+ * 1 .. 8 when n_knots > 1, a table that is not float32 / float64, a negative stride. */
+enum { PAPOF_ROWS_MAX_KNOTS = 4096 };
+int papof_warp_rows_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                           const papof_tensor* matrices, int n_knots, int iters, const papof_tensor* out,
+                           const papof_tensor* valid, void* stream);
+
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
  * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */

@@ -32,6 +32,7 @@ MOTION_SIMILARITY, MOTION_AFFINE = 0, 1
 MOSAIC_FIRST, MOSAIC_MEAN, MOSAIC_MEDIAN, MOSAIC_FEATHER = 0, 1, 2, 3
 MOSAIC_MAX_SOURCES, MOSAIC_MAX_MEDIAN, MOSAIC_MAX_OVERLAP = 255, 64, 64
 MESH_MAX_CELLS = 64  # PAPOF_MESH_MAX_CELLS
+ROWS_MAX_KNOTS = 4096  # PAPOF_ROWS_MAX_KNOTS
 
 
 class PapofTensor(ctypes.Structure):
@@ -84,6 +85,7 @@ SYMBOLS = [
     "papof_deinterlace_tensor",
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
     "papof_deblur_tensor", "papof_deblur_workspace",
+    "papof_warp_rows_tensor",
 ]
 
 
@@ -325,6 +327,8 @@ def load():
     L.papof_deblur_tensor.restype = c_int
     L.papof_deblur_workspace.argtypes = [c_int, c_int, c_int, c_int, c_int]
     L.papof_deblur_workspace.restype = ctypes.c_longlong
+    L.papof_warp_rows_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, c_int, c_int, _T, _T, c_void_p]
+    L.papof_warp_rows_tensor.restype = c_int
     L.papof_temporal_consistency_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, _T, _T, _T, _T, _T,
                                                     c_double, c_double, c_int, c_int, c_double, c_double, _T, c_void_p,
                                                     ctypes.c_longlong, c_void_p]

@@ -4736,3 +4736,271 @@ def panorama_bundle(frames, pyramidLevels, *, focal=None, surface="cylinder", mo
     image, count, gains = _panorama_tail(p, _RAYS, M, size, (cols, rows))
     return BundlePanorama(image, count, M[0], origin, mo.motion, mo.ok, flow, timing, gains, b.focal, cols, rows, b.rotations,
                           links, b.cost)
+
+
+# ---- rotation-path stabilization: one homography per source row (include/papof.h: papof_warp_rows_tensor)
+RotationStabilized = collections.namedtuple("RotationStabilized",
+                                            "video valid tables rotations smoothed focal motion ok flow timing")
+CameraRotations = collections.namedtuple("CameraRotations", "rotations focal motion ok")
+MAX_KNOTS = capi.ROWS_MAX_KNOTS  # include/papof.h: PAPOF_ROWS_MAX_KNOTS
+MAX_ROWS_ITERS = 8               # include/papof.h: papof_warp_rows_tensor
+
+
+def _rotation_log(R):
+    """the rotation vector w (3,) with exp([w]x) = R, |w| <= pi: with v = the vector of (R - R^T) / 2 = sin t a and
+    c = (tr R - 1) / 2 = cos t, t = atan2(|v|, c) and w = v t / sin t.  |v| < 1e-8 with c > 0 is the small-angle branch:
+    t / sin t = 1 + t^2 / 6 to the second order (w = v to rounding); |v| < 1e-8 with c <= 0 is a half turn, where v says
+    nothing: the axis is the largest column of the symmetric part, (R + R^T) / 2 = c I + (1 - c) a a^T"""
+    import numpy as np
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = float(np.sqrt(v @ v)), 0.5 * (float(np.trace(R)) - 1.0)
+    t = math.atan2(s, c)
+    if s >= 1e-8:
+        return v * (t / s)
+    if c > 0:
+        return v * (1.0 + t * t / 6.0)
+    B = (0.5 * (R + R.T) - c * np.eye(3)) / (1.0 - c)
+    i = int(np.argmax(np.diag(B)))
+    a = B[i] / math.sqrt(B[i, i])
+    return t * (-a if a @ v < 0 else a)
+
+
+def _check_rows_iters(iters):
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= MAX_ROWS_ITERS:
+        raise ValueError("iters must be an integer in 1 .. %d, got %r" % (MAX_ROWS_ITERS, iters))
+    return iters
+
+
+def _check_knots(knots, H, rolling):
+    if isinstance(knots, bool) or not isinstance(knots, int) or not 2 <= knots <= MAX_KNOTS:
+        raise ValueError("knots must be an integer in 2 .. %d, got %r" % (MAX_KNOTS, knots))
+    if rolling and knots > H:
+        raise ValueError("knots must be at most the %d rows of the frames, got %d" % (H, knots))
+    return knots
+
+
+def smooth_rotations(rotations, radius=15):
+    """A camera's rotations smoothed on the rotation group: rotations (T, 3, 3), any device (chain_rotations',
+    bundle_adjust's: frame t sees the ray d at K R_t d).  In float64 on the host, one pass in the tangent space at each R_t:
+        S_t = exp([sum_k g_k log(R_{t+k} R_t^T) / sum_k g_k]x) R_t,  g_k = exp(-k^2 / (2 (radius / 2)^2)),
+    k in [-radius, radius] within the video -- stabilizing_transforms' Gaussian and window, on rotation vectors instead of
+    matrix entries, so that every S_t is a rotation and there is no path of homographies to smooth.  A rotation at a
+    constant rate about one axis comes back unchanged away from the ends of the video.  radius = 0 returns the rotations as
+    they are.  Returns (T, 3, 3) float64 on the rotations' device."""
+    import numpy as np
+    R, dev = _check_rotations("rotations", rotations)
+    _check_path(radius, 1.0, None)
+    n = R.shape[0]
+    S = R.copy()
+    for t in range(n if radius > 0 else 0):
+        ks = range(max(-radius, -t), min(radius, n - 1 - t) + 1)
+        g = [math.exp(-k * k / (2.0 * (radius / 2.0) ** 2)) for k in ks]
+        w = sum(gk * _rotation_log(R[t + k] @ R[t].T) for gk, k in zip(g, ks)) / sum(g)
+        S[t] = _rodrigues(w) @ R[t]
+    return _torch().from_numpy(S).to(dev)
+
+
+def rotation_rows(rotations, smoothed, focal, size, readout, *, anchor=0.5, knots=17, crop=1.0):
+    """The tables that warp_rows takes, for a camera that rotates and reads its rows one after another: rotations (T, 3, 3) the
+    camera's, smoothed (T, 3, 3) the stabilized camera's (smooth_rotations'), any device; focal in pixels; size = (H, W);
+    readout, anchor as rectify_frames' (source row y of frame t is read at t + tau(y), tau(y) = readout (y - a) / H,
+    a = anchor (H - 1)); knots = Kn in 2 .. 4096 and <= H rows at which the family is sampled, knot k at row
+    y_k = k (H - 1) / (Kn - 1); crop as stabilizing_transforms'.  In float64 on the host:
+        M[t, k] = K R_t(tau(y_k)) S_t^T K^-1 Z,   K = (f 0 cx; 0 f cy; 0 0 1),   Z q = c + crop (q - c)
+    and between the frames' own times the camera is the parabola through three rotation vectors at R_t,
+        R_t(tau) = exp([w+ tau (tau + 1) / 2 + w- tau (tau - 1) / 2]x) R_t,   w+ = log(R_{t+1} R_t^T),  w- = log(R_{t-1} R_t^T),
+    the rotational twin of rectify_frames' parabola; on the two end frames the line through the one neighbour (w+ tau, or
+    -w- tau); a single frame does not move.  readout = 0 gives Kn = 1 whatever `knots` says: M[t, 0] = K R_t S_t^T K^-1 Z, and
+    warp_rows of it is warp_homography's.  Returns (T, Kn, 3, 3) float64 on the rotations' device."""
+    import numpy as np
+    R, dev = _check_rotations("rotations", rotations)
+    S, _ = _check_rotations("smoothed", smoothed, R.shape[0])
+    f = _check_focal(focal)
+    H, W = _check_canvas(size)
+    readout, anchor, _ = _check_shutter(readout, anchor, 1)
+    cx, cy = _check_path(0, crop, (H, W))
+    Kn = _check_knots(knots, H, readout != 0)
+    if readout == 0:
+        Kn = 1
+    T = R.shape[0]
+    K = _camera(f, H, W)
+    Ki = np.linalg.inv(K)
+    Z = np.array([[crop, 0.0, cx - crop * cx], [0.0, crop, cy - crop * cy], [0.0, 0.0, 1.0]])
+    a = anchor * (H - 1)
+    tau = [readout * (k * (H - 1) / (Kn - 1) - a) / H for k in range(Kn)] if Kn > 1 else [0.0]
+    M = np.empty((T, Kn, 3, 3))
+    for t in range(T):
+        wp = _rotation_log(R[t + 1] @ R[t].T) if t + 1 < T else None
+        wm = _rotation_log(R[t - 1] @ R[t].T) if t > 0 else None
+        right = S[t].T @ Ki @ Z
+        for k, s in enumerate(tau):
+            if wp is not None and wm is not None:
+                w = wp * (s * (s + 1.0) / 2.0) + wm * (s * (s - 1.0) / 2.0)
+            elif wp is not None:
+                w = wp * s
+            elif wm is not None:
+                w = wm * -s
+            else:
+                w = np.zeros(3)
+            M[t, k] = K @ (_rodrigues(w) @ R[t]) @ right
+    return _torch().from_numpy(M).to(dev)
+
+
+def _check_tables(tables, n, H, dev):
+    """the dtype code and Kn of warp_rows' tables -- TypeError / ValueError otherwise"""
+    torch = _torch()
+    codes = {torch.float32: capi.DTYPE_F32, torch.float64: capi.DTYPE_F64}
+    if not isinstance(tables, torch.Tensor):
+        raise TypeError("tables must be a torch.Tensor, got %s" % type(tables).__name__)
+    if tables.dtype not in codes:
+        raise TypeError("tables must be float32 or float64, got %s" % tables.dtype)
+    if tables.dim() != 4 or tables.shape[0] != n or tuple(tables.shape[2:]) != (3, 3):
+        raise ValueError("tables must be (B, Kn, 3, 3) with B = %d, got %s" % (n, tuple(tables.shape)))
+    Kn = int(tables.shape[1])
+    if not 1 <= Kn <= MAX_KNOTS:
+        raise ValueError("tables have %d knots per frame, the kernel takes 1 .. %d" % (Kn, MAX_KNOTS))
+    if Kn > 1 and H < 2:
+        raise ValueError("tables of %d knots need frames of at least two rows, got %d" % (Kn, H))
+    if tables.device != dev:
+        raise ValueError("tables are on %s, the frames on %s: both must be on one device" % (tables.device, dev))
+    return codes[tables.dtype], Kn
+
+
+def _warp_rows(ts, descs, tables, m_code, Kn, iters, layout, out_dtype):
+    """papof_warp_rows_tensor of the checked frames ts[0]: (video, valid (B, H, W) bool)"""
+    torch = _torch()
+    (B, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    out, d_out = _new_frames(B, H, W, C, layout, out_dtype, dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    d_tab = _struct(tables, tuple(tables.stride()), m_code)
+    d_valid = _struct(valid, (valid.stride(0), valid.stride(1), valid.stride(2), 1), capi.DTYPE_U8)
+    _launch(dev, "papof_warp_rows_tensor", B, H, W, C, ctypes.byref(d_in), ctypes.byref(d_tab), Kn, iters, ctypes.byref(d_out),
+            ctypes.byref(d_valid))
+    return out, valid.view(torch.bool)
+
+
+def warp_rows(frames, tables, *, iters=3, layout="NCHW", out_dtype=None):
+    """warp_homography with one matrix per SOURCE row: frames as warp_affine's; tables (B, Kn, 3, 3) float32 / float64 on the
+    frames' device, any strides (rotation_rows'), Kn >= 1 matrices per frame, knot k at source row k (H - 1) / (Kn - 1).
+    Output pixel (x, y) of frame i is frames[i] sampled at (Nx / D, Ny / D), (Nx, Ny, D) = M (x, y, 1), with M the table
+    interpolated linearly, entry by entry, at the row Y the point lands in -- which depends on M: `iters` (1 .. 8) fixed-point
+    iterations from Y = y, each clamping its row into the frame before it reads the table (the error falls by about
+    |dY / dy_source| per iteration: the rows' rotation rate times the focal length, a few per cent for a hand-held camera).
+    The last iterate decides: 0 and not valid where D is not > 0 or the point is NaN or outside the frame.  Kn = 1: no
+    iteration, warp_homography's bytes.  Returns (frames_out, valid (B, H, W) bool) as warp_affine.  include/papof.h
+    (papof_warp_rows_tensor) states it exactly; bitwise reproducible.  Enqueued on the current stream; returns without
+    waiting."""
+    _check_rows_iters(iters)
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    out_dtype = _out_dtype(out_dtype, ts[0].dtype)
+    (B, H, _, _), _, _ = descs[0]
+    m_code, Kn = _check_tables(tables, B, H, ts[0].device)
+    return _warp_rows(ts, descs, tables, m_code, Kn, iters, layout, out_dtype)
+
+
+def _check_camera(size, readout, anchor, rs_iters, focal, iters, scale, bundle_iters, bundle_step):
+    """the keywords that camera_rotations and stabilize_video_rotation share: ((H, W), shutter, focal or None, iters, scale)"""
+    size = _check_canvas(size)
+    shutter = _check_shutter(readout, anchor, rs_iters, "rs_iters")
+    if focal is not None:
+        focal = _check_focal(focal)
+    iters, scale = _check_irls(iters, scale)
+    _int_at_least("bundle_iters", bundle_iters, 1)
+    _int_at_least("bundle_step", bundle_step, 1)
+    return size, shutter, focal, iters, scale
+
+
+def _camera_rotations(flow, occ, size, focal, iters, scale, bundle_iters, bundle_step, ref):
+    """camera_rotations from its step 2 on, on checked arguments: flow the (rectified) float64 forward flows, occ their
+    uint8 mask or None"""
+    import numpy as np
+    mo = _homography_fit(flow, capi.DTYPE_F64, occ, iters, scale)
+    if focal is None:
+        focal = estimate_focal(mo, size)
+    T = int(flow.shape[0]) + 1
+    chain = np.stack([np.arange(T - 1), np.arange(1, T)], 1)
+    b = bundle_adjust(flow, chain, chain_rotations(mo, size, focal, ref=ref), focal, occlusion=occ, iters=bundle_iters,
+                      scale=scale, step=bundle_step, ref=ref, fix_focal=True)
+    return CameraRotations(b.rotations, focal, mo.motion, mo.ok)
+
+
+def camera_rotations(flow_fw, size, *, flow_bw=None, readout=0.0, anchor=0.5, rs_iters=3, focal=None, iters=5, scale=1.0,
+                     bundle_iters=10, bundle_step=1, ref=0):
+    """One rotation per frame and a focal length from a video's flows -- the estimation chain of a camera that rotates, stated
+    once: flow_fw (T - 1, 2, H, W) float32 / float64 on a HIP device (flow_video's), size = (H, W) of the frames.
+    1. readout != 0 (a rolling shutter; readout, anchor as rectify_frames'): rectify_flows(flow_fw, flow_bw, readout,
+       anchor=anchor, iters=rs_iters), for which flow_bw (flow_video_fb's) is required.  Whenever flow_bw is given,
+       fb_consistency on the (rectified) flows masks the fits below; rectify_flows' NaNs are all masked, as in
+       stabilize_video_rs.
+    2. global_homography of the forward flows (iters, scale).
+    3. estimate_focal, unless `focal` is given.
+    4. chain_rotations (ref: the frame whose rotation is the identity).
+    5. bundle_adjust of the consecutive links with the focal length held (bundle_iters, scale, bundle_step, ref): the chain
+       of nearest rotations becomes the rotations that fit the flows.
+    Returns CameraRotations(rotations (T, 3, 3) float64 on the flows' device -- frame t sees the ray d at K R_t d --, focal,
+    motion (T - 1, 3, 3) float64 the pair homographies, ok (T - 1,) bool).  The host waits in steps 3 to 5.  Every argument
+    error raises before anything is launched; ValueError as estimate_focal's and bundle_adjust's."""
+    size, shutter, focal, iters, scale = _check_camera(size, readout, anchor, rs_iters, focal, iters, scale, bundle_iters,
+                                                       bundle_step)
+    torch = _torch()
+    if flow_bw is None:
+        if shutter[0] != 0:
+            raise ValueError("readout != 0 rectifies the flows first: give flow_bw (flow_video_fb's)")
+        _check_flow("flow_fw", flow_fw)
+        if not _on_gpu(flow_fw):
+            raise ValueError("flows must be on a HIP device (cuda:N), got %s" % flow_fw.device)
+    else:
+        codes = _check_flows(flow_fw, flow_bw)
+    if tuple(flow_fw.shape[2:]) != size:
+        raise ValueError("size %s is not the flows' %s" % (size, tuple(flow_fw.shape[2:])))
+    ref = _check_ref(ref, int(flow_fw.shape[0]) + 1)
+    occ = None
+    if flow_bw is not None:
+        fw, bw = flow_fw, flow_bw
+        if shutter[0] != 0:
+            fw, bw = _rectify_flows((flow_fw, flow_bw), codes, shutter, torch.float64)
+        occ = fb_consistency(fw, bw).view(torch.uint8)
+        flow_fw = fw
+    return _camera_rotations(flow_fw.to(torch.float64), occ, size, focal, iters, scale, bundle_iters, bundle_step, ref)
+
+
+def stabilize_video_rotation(frames, pyramidLevels, *, readout=0.0, anchor=0.5, rs_iters=3, focal=None, radius=15, crop=1.0,
+                             knots=17, iters=3, layout="NCHW", out_dtype=None, fit_iters=5, scale=1.0, bundle_iters=10,
+                             **solver):
+    """stabilize_video for a hand-held camera that ROTATES, with or without a rolling shutter (Forssen and Ringaby 2010;
+    Karpenko et al. 2011): flow_video_fb(consistency=None) when readout != 0, else flow_video (float64 flows);
+    camera_rotations on them (readout, anchor, rs_iters, focal, fit_iters as its iters, scale, bundle_iters; ref = 0);
+    smooth_rotations (radius); rotation_rows (readout, anchor, knots, crop) and ONE warp_rows (iters) of the recorded frames
+    -- the stabilizing homography and the rectification of the rolling shutter in one resampling, where stabilize_video_rs
+    removes an affine path and leaves the perspective wobble of a rotation.  Returns RotationStabilized(video (T, ...) in
+    `layout` and out_dtype (by default the frames'), valid (T, H, W) bool, tables (T, Kn, 3, 3) float64 (Kn = 1 for
+    readout = 0), rotations, smoothed (T, 3, 3) float64, focal, motion (T - 1, 3, 3) float64 and ok (T - 1,) bool the pair
+    homographies, flow (T - 1, 2, H, W) float64 the recorded forward flows, timing of the flow call).  What it is not: pure
+    rotation -- no translation, no parallax; one focal length; readout is given, not estimated; the end frames use a line;
+    the borders are not filled (crop hides them); not causal: the whole video is read first.  The host waits in
+    camera_rotations.  Every argument error raises before anything is launched; the video is enqueued on the current
+    stream."""
+    ts, descs, out_dtype, params = _check_video(frames, layout, pyramidLevels, out_dtype, solver=solver)
+    (T, H, W, _), _, _ = descs[0]
+    size, shutter, focal, fit_iters, scale = _check_camera((H, W), readout, anchor, rs_iters, focal, fit_iters, scale,
+                                                           bundle_iters, 1)
+    _check_path(radius, crop, size)
+    _check_knots(knots, H, shutter[0] != 0)
+    _check_rows_iters(iters)
+    torch = _torch()
+    occ = None
+    if shutter[0] != 0:
+        fb = _run_fb(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, _alphas(None), params)
+        flow, timing = fb.flow_fw, fb.timing
+        fw, bw = _rectify_flows((fb.flow_fw, fb.flow_bw), _F64_FLOWS, shutter, torch.float64)
+        occ = fb_consistency(fw, bw).view(torch.uint8)
+    else:
+        flow, _, timing = _run(ts, descs, True, T - 1, layout, torch.float64, pyramidLevels, params)
+        fw = flow
+    cam = _camera_rotations(fw, occ, size, focal, fit_iters, scale, bundle_iters, 1, 0)
+    S = smooth_rotations(cam.rotations, radius)
+    tables = rotation_rows(cam.rotations, S, cam.focal, size, shutter[0], anchor=shutter[1], knots=knots, crop=crop)
+    video, valid = _warp_rows(ts, descs, tables, capi.DTYPE_F64, int(tables.shape[1]), iters, layout, out_dtype)
+    return RotationStabilized(video, valid, tables, cam.rotations, S, cam.focal, cam.motion, cam.ok, flow, timing)
