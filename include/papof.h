@@ -1922,6 +1922,24 @@ int papof_last_host_times(papof_handle* h, double out[3]);
 int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int split_band, int reps, int delay_us,
                           long long* mismatches, int* bands);
 
+/* Test aid: write the repeating 8-byte `pattern` (say a NaN) over every byte of every device block of the handle whose
+ * contents no later call may rely on, so that a test can show that call N + 1 does not depend on what call N -- or a
+ * corrupt frame -- left behind.  Waits for the handle's own streams (main, preparation, copy), fills on the main stream,
+ * waits again.  Filled: the arena over its whole capacity (not only what the last call carved out of it), the host path's
+ * staging block, the device-tensor path's one-pair scratch, the exact Laplacian-noise pass's reduction scratch and its
+ * LapPara (8 doubles: every pass that reads them copies the constant 0.02 over them first, solve_levels and the smooth-flow
+ * stage, so no call may rely on them either).  *bytes (may be NULL) = bytes filled; 0 on a handle that has run nothing
+ * but for that small Laplacian-noise block.  The kept sequence is reset as by papof_seq_reset: its pyramid lived in the arena.
+ * Left alone, because a pattern there would test nothing about data dependences:
+ *   - the solver's progress counters and abort word: kernels spin on them, garbage could only hang the device;
+ *   - the Laplacian-noise guard's flags: a flag is set when it EQUALS the pass number, a pattern could forge a proof;
+ *   - LapPara's initial value 0.02: a constant written once when the handle is made;
+ *   - the phase stamps (device slots and pinned host copy): they carry clock readings for the timers, never a result's data;
+ *   - the refusal flag of a caller's initial flow: cleared by the call that uses it, its value decides a return code.
+ * A caller that ran the device-tensor calls on a stream of its own waits for that stream first.
+ * PAPOF_EINVAL: a NULL handle. */
+int papof_test_poison(papof_handle* h, unsigned long long pattern, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,7 @@ SYMBOLS = [
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
     "papof_deblur_tensor", "papof_deblur_workspace",
     "papof_warp_rows_tensor",
+    "papof_test_poison",
 ]
 
 
@@ -337,6 +338,8 @@ def load():
     L.papof_consistency_workspace.restype = ctypes.c_longlong
     L.papof_test_sor_strips.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]
+    L.papof_test_poison.argtypes = [c_void_p, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_size_t)]
+    L.papof_test_poison.restype = c_int
     _lib = L
     return L
 
@@ -813,6 +816,13 @@ class Papof:
         _chk(self.L.papof_test_sor_strips(self.h, h, w, n_sor, split_band, reps, delay_us, ctypes.byref(mm),
                                           ctypes.byref(nb)), "papof_test_sor_strips")
         return mm.value, nb.value
+
+    def test_poison(self, pattern=0x7FF8DEAD7FF8DEAD):
+        """Fill every device block of the handle that no later call may rely on with the repeating 8-byte pattern (default:
+        NaN as fp64 and as two fp32) and forget the kept sequence; returns the bytes filled (include/papof.h: papof_test_poison)"""
+        n = ctypes.c_size_t(0)
+        _chk(self.L.papof_test_poison(self.h, pattern, ctypes.byref(n)), "papof_test_poison")
+        return n.value
 
     def bench_sor(self, h, w, n_sor, mode=SOR_EXACT, reps=5, seed=2):
         ms = c_double(0)

@@ -2049,6 +2049,56 @@ int papof_test_sor_strips(papof_handle* h, int height, int width, int n_sor, int
     return PAPOF_OK;
 }
 
+namespace {
+
+// `words` 8-byte words of `pattern` from d on, then `tail` (< 8) bytes of it
+__global__ __launch_bounds__(256) void k_poison(unsigned long long* __restrict__ d, size_t words, unsigned tail,
+                                                unsigned long long pattern) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) d[i] = pattern;
+    if (blockIdx.x == 0 && threadIdx.x < tail)
+        reinterpret_cast<unsigned char*>(d + words)[threadIdx.x] = (unsigned char)(pattern >> (8 * threadIdx.x));
+}
+
+int poison_block(papof_handle* h, void* p, size_t bytes, unsigned long long pattern, size_t* total) {
+    if (!p || !bytes) return PAPOF_OK;
+    const size_t words = bytes / 8;
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>(1, (words + 255) / 256), 4096);
+    hipLaunchKernelGGL(k_poison, dim3(blocks), dim3(256), 0, h->stream, static_cast<unsigned long long*>(p), words,
+                       (unsigned)(bytes % 8), pattern);
+    PAPOF_HIP(hipGetLastError());
+    *total += bytes;
+    return PAPOF_OK;
+}
+
+int sync_own_streams(papof_handle* h) {
+    PAPOF_HIP(hipStreamSynchronize(h->stream));
+    if (h->prep_stream) PAPOF_HIP(hipStreamSynchronize(h->prep_stream));
+    if (h->copy_stream) PAPOF_HIP(hipStreamSynchronize(h->copy_stream));
+    return PAPOF_OK;
+}
+
+}  // namespace
+
+// Test aid (papof.h): `pattern` over every device block of the handle whose contents no later call may rely on
+int papof_test_poison(papof_handle* h, unsigned long long pattern, size_t* bytes) {
+    if (!h) return PAPOF_EINVAL;
+    PAPOF_HIP(hipSetDevice(h->device));
+    PAPOF_TRY(sync_own_streams(h));
+    size_t total = 0;
+    PAPOF_TRY(poison_block(h, h->arena.base, h->arena.cap, pattern, &total));
+    PAPOF_TRY(poison_block(h, h->stage_dev, h->stage_dev_bytes, pattern, &total));
+    PAPOF_TRY(poison_block(h, h->tensor_scratch, h->tensor_scratch_bytes, pattern, &total));
+    if (h->lap_dev) {  // one allocation: LapPara (8 doubles), its constant initial value (8, kept), the reduction's scratch
+        PAPOF_TRY(poison_block(h, h->lap_dev, 8 * sizeof(double), pattern, &total));
+        PAPOF_TRY(poison_block(h, h->lap_scratch_dev, (size_t)lap_scratch_doubles() * sizeof(double), pattern, &total));
+    }
+    PAPOF_TRY(sync_own_streams(h));
+    h->seq.valid = false;  // papof_seq_reset: the kept pyramid lived in the arena
+    if (bytes) *bytes = total;
+    return PAPOF_OK;
+}
+
 int papof_bench_sor(papof_handle* h, int height, int width, int n_sor, int sor_mode, int reps, unsigned seed,
                     double* ms_per_solve) {
     if (!h || !ms_per_solve || height < 1 || width < 1 || n_sor < 1 || reps < 1 || sor_mode < PAPOF_SOR_EXACT ||
