@@ -1727,8 +1727,9 @@ int papof_mask_dilate_tensor(papof_handle* h, int n_frames, int height, int widt
  * A static scene with zero flows has c0 = c1 = 1, D = 0, q = 1 and out_k = 0 * s_k + g0_k: the interior frames are the
  * progressive video exactly.  What it is not: at the critical velocity (an odd number of frame rows per field) the
  * neighbouring fields hold the current field's lines, c = 0 and the output is mode 0's; the end frames, with one neighbour
- * and q <= 0.5, are weaker; the flows assume motion linear over two field periods; no cadence or telecine detection; no model
- * of chroma subsampling.
+ * and q <= 0.5, are weaker; the flows assume motion linear over two field periods; telecined film is not its case
+ * (papof_field_metrics_tensor and papof_weave_fields_tensor below find and weave the fields of one film frame); no model of
+ * chroma subsampling.
  * One lane writes both rows 2 j and 2 j + 1 of its column: every output element is written once.  Enqueued on `stream` (the
  * caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.  No device memory besides
  * the tensors is used; no atomics; bitwise reproducible.
@@ -1740,6 +1741,56 @@ int papof_mask_dilate_tensor(papof_handle* h, int n_frames, int height, int widt
 int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field_height, int width, int c, const papof_tensor* fields,
                              int first, int mode, const papof_tensor* flow_fw, const papof_tensor* flow_bw, double sigma,
                              const papof_tensor* video, const papof_tensor* confidence, void* stream);
+
+/* Inverse telecine, part 1 (telecine.hip: k_field_metrics): for every field of a sequence, how much worse it weaves with its
+ * next field than with its previous one, and the reverse, as integer counts per cell.  Film on interlaced video (3:2 pulldown,
+ * 2:2) repeats each film frame over two or three consecutive fields; those fields show one instant, and weaving them gives
+ * the film frame exactly, where papof_deinterlace_tensor would make up lines that the neighbouring field holds.  Absolute comb
+ * counts do not separate film from video -- vertical detail looks like combing --; the counts below compare the two candidate
+ * weaves pixel by pixel, at the same rows of two fields of one parity, so that the texture cancels.  A parallel call: no call
+ * above changes.
+ * fields: n_fields = T >= 3 fields of field_height = Hf rows, width = W; uint8, float32 or float64, (field, row, column,
+ * channel), any non-negative strides, c = C channels, 1 <= C <= 4.  Field k holds the rows of parity (k + first) & 1 of frame
+ * k; first is 0 or 1.  cell_rows: 1 .. 64.  comb_q, diff_q: integer thresholds, 0 .. 65535.
+ * metrics: DEVICE pointer to T * 3 * Gy * Gx int32, contiguous (field, plane, cy, cx), Gy = ceil(Hf / cell_rows), Gx =
+ * ceil(W / 64).  Every element is written exactly once; fields 0 and T - 1 get zeros.
+ * Everything is integer.  q(uint8 b) = 257 * b; q(float v) = 0 for a NaN, else clamp(rint(65535.0 * v), 0, 65535), the
+ * product in fp64, rint half to even.
+ * For 1 <= t <= T - 2, p = (t + first) & 1, the centre rows are j = 1 .. Hf - 1 with (ja, jc) = (j - 1, j) for p = 0 and
+ * j = 0 .. Hf - 2 with (ja, jc) = (j, j + 1) for p = 1: the lines above and below frame row 2 j + p, which the neighbouring
+ * fields hold.  At a centre row j, a column x and a channel k:
+ *
+ *   b = q(field[t](j, x, k));  a-, c- = q(field[t - 1](ja | jc, x, k));  a+, c+ = q(field[t + 1](ja | jc, x, k))
+ *   m(b; a, c) = min(|a - b|, |c - b|) when (a > b and c > b) or (a < b and c < b), else 0
+ *   M- = max over k of m(b; a-, c-);  M+ = max over k of m(b; a+, c+)
+ *   nd = max over k of max(|a+ - a-|, |c+ - c-|)
+ *
+ * and cell (j / cell_rows, x / 64) counts, in plane 0, M+ > M- + comb_q (the next field fits worse here); in plane 1,
+ * M- > M+ + comb_q; in plane 2, nd > diff_q (the neighbours differ: field t + 1 does not repeat field t - 1).
+ * One wave per cell, the counts by ballot: no atomics, no device memory besides the tensors, nothing of the handle's; the
+ * result does not depend on what `metrics` held.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL:
+ * the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor, data pointer or metrics, fields that are not uint8 /
+ * float32 / float64, a negative stride, n_fields < 3, field_height < 1 or > 2^30 - 1, width < 1, c outside 1 .. 4, first
+ * outside {0, 1}, cell_rows outside 1 .. 64, or a threshold outside 0 .. 65535. */
+int papof_field_metrics_tensor(papof_handle* h, int n_fields, int field_height, int width, int c, const papof_tensor* fields,
+                               int first, int cell_rows, int comb_q, int diff_q, int* metrics, void* stream);
+
+/* Inverse telecine, part 2 (telecine.hip: k_weave_fields): n_frames = N frames of 2 Hf rows woven from the fields that a
+ * table names.  fields: as above, n_fields = T >= 1.  table: DEVICE pointer to N * 2 int32, (frame, {the field of the even
+ * rows, the field of the odd rows}).  video: uint8 / float32 / float64, (frame, row, column, channel) with 2 Hf rows, strides
+ * [0..3] > 0; it must not overlap fields.
+ *
+ *   video[n](2 j + r, x, k) = store(load(field[table[n, r]](j, x, k))),  r = 0, 1
+ *
+ * with papof_deinterlace_tensor's load and store of a kept line: uint8 to uint8 keeps the input's bytes.  One pass, every output
+ * element written once.  An index outside 0 .. T - 1 is the caller's error (as the sources of papof_mosaic_tensor): it is
+ * not checked.  Enqueued on `stream` and returns without waiting; no device memory besides the tensors.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor, data pointer or table, fields or a video that are not
+ * uint8 / float32 / float64, a negative stride, a zero stride of video along an axis in use, n_fields or n_frames < 1,
+ * field_height < 1 or > 2^30 - 1, width < 1, c outside 1 .. 4, or a video that starts where fields does. */
+int papof_weave_fields_tensor(papof_handle* h, int n_fields, int field_height, int width, int c, const papof_tensor* fields,
+                              int n_frames, const int* table, const papof_tensor* video, void* stream);
 
 /* Rolling-shutter rectification along the flows (rolling.hip: k_rs_rectify, k_rs_flow).  A rolling shutter reads the rows of
  * a frame one after another: row y of frame t of H rows is exposed at the time t + readout * (y - a) / H, in frame intervals,

@@ -82,7 +82,7 @@ SYMBOLS = [
     "papof_mesh_workspace", "papof_mesh_motion_tensor", "papof_warp_mesh_tensor",
     "papof_mosaic_mesh_workspace", "papof_mosaic_mesh_tensor",
     "papof_defect_detect_tensor", "papof_mask_dilate_tensor",
-    "papof_deinterlace_tensor",
+    "papof_deinterlace_tensor", "papof_field_metrics_tensor", "papof_weave_fields_tensor",
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
     "papof_deblur_tensor", "papof_deblur_workspace",
     "papof_warp_rows_tensor",
@@ -318,6 +318,11 @@ def load():
     L.papof_deinterlace_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, c_int, c_int, _T, _T, c_double, _T, _T,
                                            c_void_p]
     L.papof_deinterlace_tensor.restype = c_int
+    L.papof_field_metrics_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, c_int, c_int, c_int, c_int, c_void_p,
+                                             c_void_p]
+    L.papof_field_metrics_tensor.restype = c_int
+    L.papof_weave_fields_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, c_int, c_void_p, _T, c_void_p]
+    L.papof_weave_fields_tensor.restype = c_int
     L.papof_rs_rectify_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, c_double, c_int, _T, _T, _T,
                                           c_void_p]
     L.papof_rs_rectify_tensor.restype = c_int

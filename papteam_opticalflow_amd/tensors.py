@@ -176,9 +176,19 @@ one per field: each frame keeps its field's lines and makes the others from the 
 along the flows between them (`field_flows`: the solver on the fields themselves), weighted by the phase of the landing
 rows and the agreement of the two samples, over a four-tap cubic of the own field (`bob_fields`, the fallback);
 `split_fields` makes the fields from woven frames and `deinterlace_video` chains field_flows and deinterlace_fields.  No gain
-at the critical velocity; weaker end frames; no cadence detection.
+at the critical velocity; weaker end frames; telecined film goes through inverse_telecine instead.
 
     dv = deinterlace_video(split_fields(frames, layout="NHWC"), 4, layout="NHWC")   # dv.video (2 N, H, W, C), dv.confidence
+
+Inverse telecine: film on interlaced video (3:2 pulldown, 2:2) repeats every film frame over two or three consecutive
+fields, and weaving those gives the film frames exactly.  `field_metrics` (include/papof.h: papof_field_metrics_tensor)
+reduces every field to integer counts of where it weaves worse with its next field than with its previous one and the
+reverse, one HIP kernel; `match_fields` turns them into links, groups and a cadence report on the host; `weave_fields`
+(papof_weave_fields_tensor) weaves fields by a table; `inverse_telecine` chains them and sends the fields without a partner
+through bob_fields or deinterlace_fields, `inverse_telecine_video` computes the field flows for those when there are any.
+Wrong at the critical vertical velocity; thresholds are relative to the noise; no cadence lock; no blended telecine.
+
+    it = inverse_telecine(fields, layout="NHWC")   # it.video (N, H, W, C): the film frames, it.times, it.kinds, it.match.cadence
 
 Rolling shutter: `rectify_frames` (include/papof.h: papof_rs_rectify_tensor) resamples a video whose rows were read out one
 after another -- row y of frame t at t + readout (y - a) / H -- to what a global shutter would have recorded at the frame's
@@ -236,6 +246,10 @@ Restored = collections.namedtuple("Restored", "video masks detected status")
 RestoredVideo = collections.namedtuple("RestoredVideo", Restored._fields + ("flow_fw", "flow_bw", "timing"))
 Deinterlaced = collections.namedtuple("Deinterlaced", "video confidence")
 DeinterlacedVideo = collections.namedtuple("DeinterlacedVideo", Deinterlaced._fields + ("flow_fw", "flow_bw", "timing"))
+FieldMetrics = collections.namedtuple("FieldMetrics", "counts cell_rows first")
+FieldMatch = collections.namedtuple("FieldMatch", "votes links groups cadence share")
+Detelecined = collections.namedtuple("Detelecined", "video groups times kinds match")
+DetelecinedVideo = collections.namedtuple("DetelecinedVideo", Detelecined._fields + ("flow_fw", "flow_bw", "timing"))
 Rectified = collections.namedtuple("Rectified", "video valid flow_fw flow_bw occlusion timing")
 StabilizedRS = collections.namedtuple("StabilizedRS", "video valid transforms motion ok flow_fw flow_bw occlusion timing")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
@@ -2136,7 +2150,7 @@ def deinterlace_fields(fields, flow_fw, flow_bw, first=0, *, sigma=DEINT_SIGMA, 
     keeps the kept lines' bytes --, confidence (T, Hf, W) float64: q of every made pixel).  include/papof.h
     (papof_deinterlace_tensor) states the rule exactly.  Not gained: anything at the critical velocity (an odd number of
     frame rows per field: the neighbouring fields hold the same lines, the output is bob_fields'); the end frames are
-    weaker; the flows assume motion linear over two field periods; no cadence or telecine detection, no
+    weaker; the flows assume motion linear over two field periods; telecined film is inverse_telecine's case; no
     chroma-subsampling model.  Enqueued on the current stream; returns without waiting."""
     first = _check_parity(first)
     sigma = _check_deint_sigma(sigma)
@@ -2157,6 +2171,344 @@ def deinterlace_video(fields, pyramidLevels, first=0, *, sigma=DEINT_SIGMA, layo
     fb = _field_flows(ts, descs, layout, pyramidLevels, params)
     d = _deinterlace(ts, descs, first, 1, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), sigma, layout, out_dtype)
     return DeinterlacedVideo(d.video, d.confidence, fb.flow_fw, fb.flow_bw, fb.timing)
+
+
+# ---- inverse telecine (include/papof.h: papof_field_metrics_tensor, papof_weave_fields_tensor)
+MAX_CELL_ROWS = 64
+CELL_COLUMNS = 64
+MAX_Q = 65535                 # the thresholds' integer scale
+COMB_THRESHOLD = 10 / 255     # tests/test_telecine_cpu.py: the scenes hold at noise of 2 / 255; 26 / 255 for 5 / 255
+DIFF_THRESHOLD = 8 / 255
+FREE, PREV, NEXT, VIDEO = 0, 1, 2, 3  # a field's vote: no evidence (static), woven with its previous / next field, with neither
+ORPHANS = ("bob", "mc", "drop")
+
+
+def _check_q(name, v):
+    """a threshold in the fields' [0, 1] units as its integer rint(65535 v) (half to even)"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError("%s must be a number, got %r" % (name, v))
+    if not (math.isfinite(v) and 0 <= v <= 1):
+        raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
+    return int(round(float(MAX_Q) * float(v)))
+
+
+def _check_cell_rows(cell_rows):
+    return _int_in("cell_rows", cell_rows, 1, MAX_CELL_ROWS)
+
+
+def _check_telecine_fields(fields, layout, levels, out_dtype, solver=None):
+    """the fields of the inverse-telecine calls: _check_video's returns for T >= 3 fields"""
+    ts, descs, out_dtype, params = _check_video(fields, layout, levels, out_dtype, name="fields", min_frames=3, solver=solver)
+    if descs[0][0][1] > MAX_FIELD_HEIGHT:
+        raise ValueError("fields must have at most %d rows, got %d" % (MAX_FIELD_HEIGHT, descs[0][0][1]))
+    return ts, descs, out_dtype, params
+
+
+def _field_metrics(ts, descs, first, cell_rows, comb_q, diff_q):
+    """papof_field_metrics_tensor of the checked fields ts[0]: a FieldMetrics"""
+    torch = _torch()
+    (T, Hf, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    counts = torch.empty((T, 3, -(-Hf // cell_rows), -(-W // CELL_COLUMNS)), dtype=torch.int32, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    _launch(dev, "papof_field_metrics_tensor", T, Hf, W, C, ctypes.byref(d_in), first, cell_rows, comb_q, diff_q,
+            ctypes.c_void_p(counts.data_ptr()))
+    return FieldMetrics(counts, cell_rows, first)
+
+
+def field_metrics(fields, first=0, *, comb_threshold=COMB_THRESHOLD, diff_threshold=DIFF_THRESHOLD, cell_rows=16, layout="NCHW"):
+    """How every field of a sequence weaves with its two neighbours (papof_field_metrics_tensor, one HIP kernel): T >= 3
+    fields (T, C, Hf, W) or (T, Hf, W, C) by `layout`, C = 1 .. 4, uint8, float32 or float64, any strides, on a HIP device;
+    field k holds the rows of parity (k + first) & 1 of frame k.  Values are quantised to 0 .. 65535 (a byte b is 257 b, a
+    float v clamp(rint(65535 v), 0, 65535), NaN 0) and everything after that is integer.  For each interior field t every
+    pixel of its lines is tested against the lines above and below it in field t - 1 and in field t + 1 -- two fields of one
+    parity: the same rows --: M is how far the pixel lies outside the range of the two lines, the largest over the channels.
+    Per cell of cell_rows (1 .. 64) x 64 pixels, plane 0 counts the pixels with M+ > M- + comb_threshold (the next field fits
+    worse), plane 1 those with M- > M+ + comb_threshold, plane 2 those where the two neighbours differ by more than
+    diff_threshold.  The thresholds are in the fields' [0, 1] units and become rint(65535 v).  Absolute comb counts do not
+    separate film from video (vertical detail looks like combing); these relative ones do: the texture cancels.
+    Returns FieldMetrics(counts (T, 3, ceil(Hf / cell_rows), ceil(W / 64)) int32 on the fields' device -- fields 0 and T - 1
+    are zeros --, cell_rows, first).  Enqueued on the current stream; returns without waiting."""
+    first = _check_parity(first)
+    comb_q, diff_q = _check_q("comb_threshold", comb_threshold), _check_q("diff_threshold", diff_threshold)
+    cell_rows = _check_cell_rows(cell_rows)
+    ts, descs, _, _ = _check_telecine_fields(fields, layout, 1, None)
+    return _field_metrics(ts, descs, first, cell_rows, comb_q, diff_q)
+
+
+def _check_match_rule(cell_rows, margin, dominance):
+    """(margin -- by default cell_rows * 64 // 64 --, dominance) of match_fields' keywords"""
+    if margin is None:
+        margin = cell_rows * CELL_COLUMNS // 64
+    if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+        raise ValueError("margin must be None or an integer >= 0, got %r" % (margin,))
+    if isinstance(dominance, bool) or not isinstance(dominance, (int, float)) or not (math.isfinite(dominance) and dominance >= 1):
+        raise ValueError("dominance must be a finite number >= 1, got %r" % (dominance,))
+    return margin, dominance
+
+
+def _check_metrics(metrics):
+    """the counts of a FieldMetrics as a numpy (T, 3, Gy, Gx) int64 array: one copy from the device"""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(metrics, FieldMetrics):
+        raise TypeError("metrics must be a FieldMetrics (field_metrics' return), got %s" % type(metrics).__name__)
+    counts = metrics.counts
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+        raise TypeError("metrics.counts must be an int32 tensor")
+    if counts.dim() != 4 or counts.shape[0] < 3 or counts.shape[1] != 3 or min(counts.shape) < 1:
+        raise ValueError("metrics.counts must be (T >= 3, 3, Gy, Gx), got shape %s" % (tuple(counts.shape),))
+    return counts.detach().cpu().numpy().astype(np.int64)
+
+
+def field_votes(counts, margin, dominance):
+    """the votes (T,) uint8 of numpy counts (T, 3, Gy, Gx): match_fields' rule for one field after another"""
+    import numpy as np
+
+    def ev(A, B):
+        ok = (A > margin) & (dominance * B <= A)
+        return int((A - B)[ok].max()) if ok.any() else 0
+
+    T = counts.shape[0]
+    votes = np.full(T, FREE, np.uint8)
+    for t in range(1, T - 1):
+        A, B = counts[t, 0], counts[t, 1]
+        ep, en, hi = ev(A, B), ev(B, A), int(max(A.max(), B.max()))
+        votes[t] = PREV if ep > en else NEXT if en > ep else VIDEO if hi > margin else FREE
+    return votes
+
+
+def field_groups(links):
+    """[start, length] (N, 2) int64 of the groups of numpy links (T - 1,): the maximal runs of linked fields, a run of 4 or
+    more cut into groups of 2, the last one of 3 when the run is odd"""
+    import numpy as np
+    groups, start, T = [], 0, len(links) + 1
+    for t in range(T):
+        if t == T - 1 or not links[t]:
+            L = t + 1 - start
+            if L <= 3:
+                groups.append((start, L))
+            else:
+                for k in range(L // 2):
+                    groups.append((start + 2 * k, 3 if (L % 2 and k == L // 2 - 1) else 2))
+            start = t + 1
+    return np.array(groups, np.int64).reshape(-1, 2)
+
+
+def field_cadence(votes, groups):
+    """(cadence, share) of numpy votes and groups: match_fields' report"""
+    T = len(votes)
+    L = [int(n) for n in groups[:, 1]]
+    if all(v == FREE for v in votes):
+        return "static", 1.0
+    near = lambda i: [L[k] for k in (i - 1, i + 1) if 0 <= k < len(L)]  # noqa: E731
+    shares = {
+        "3:2": sum(n for i, n in enumerate(L) if n in (2, 3) and 5 - n in near(i)) / T,
+        "2:2": sum(n for n in L if n == 2) / T,
+        "video": sum(n for n in L if n == 1) / T,
+    }
+    if len(L) >= 2 and all(n in (2, 3) for n in L) and all(a + b == 5 for a, b in zip(L, L[1:])):
+        return "3:2", 1.0
+    for name in ("2:2", "video"):
+        if shares[name] == 1.0:
+            return name, 1.0
+    return "mixed", max(shares.values())
+
+
+def match_fields(metrics, *, margin=None, dominance=3):
+    """Which fields belong to one film frame, from field_metrics' counts: the host's rule, on one copy of the small table
+    from the device -- THIS CALL WAITS for the stream that wrote it.  With A = plane 0 and B = plane 1 of an interior field t,
+        ev(A, B) = the largest A - B over the cells where A > margin and dominance * B <= A, 0 without such a cell
+        ep = ev(A, B), en = ev(B, A), hi = the largest entry of A and B
+    field t votes PREV (1: it weaves with field t - 1) where ep > en, NEXT (2) where en > ep, otherwise VIDEO (3: it weaves
+    with neither) where hi > margin and FREE (0: nothing moves, any partner does) elsewhere; fields 0 and T - 1 are FREE.
+    margin defaults to cell_rows * 64 // 64 counts (16 for the default cell).  Fields t and t + 1 are linked where field t
+    votes NEXT or FREE and field t + 1 votes PREV or FREE; the groups are the maximal runs of linked fields: a run of 1, 2
+    or 3 fields is one group, a longer one -- a static stretch -- is cut into groups of 2, the last one of 3 when it is odd.
+    Returns FieldMatch(votes (T,) uint8, links (T - 1,) bool, groups (N, 2) int64 rows [start, length] -- torch tensors on
+    the host --, cadence, share).  cadence is a report and decides nothing: "static" where every vote is FREE, "3:2" where
+    the lengths alternate 2 and 3, "2:2" where all are 2, "video" where all are 1, else "mixed"; share is the share of the
+    fields in groups that follow the named pattern (a 2 or 3 next to a 3 or 2; a 2; a 1), for "mixed" the largest of the
+    three."""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(metrics, FieldMetrics):
+        raise TypeError("metrics must be a FieldMetrics (field_metrics' return), got %s" % type(metrics).__name__)
+    margin, dominance = _check_match_rule(_check_cell_rows(metrics.cell_rows), margin, dominance)
+    counts = _check_metrics(metrics)
+    votes = field_votes(counts, margin, dominance)
+    nxt, prv = np.isin(votes[:-1], (NEXT, FREE)), np.isin(votes[1:], (PREV, FREE))
+    links = nxt & prv
+    groups = field_groups(links)
+    cadence, share = field_cadence(votes, groups)
+    return FieldMatch(torch.from_numpy(votes), torch.from_numpy(links), torch.from_numpy(groups), cadence, share)
+
+
+def _check_weave_table(table, T):
+    """the weave's table as a contiguous int32 host tensor (N, 2), N >= 1, every entry in 0 .. T - 1"""
+    import numpy as np
+    torch = _torch()
+    if isinstance(table, torch.Tensor):
+        if table.dtype.is_floating_point or table.dtype.is_complex or table.dtype == torch.bool:
+            raise TypeError("table must hold integers, got %s" % table.dtype)
+        t = table.detach().to("cpu", torch.int64)
+    else:
+        try:
+            a = np.asarray(table)
+        except Exception:  # noqa: BLE001
+            raise TypeError("table must be an integer tensor or an integer array, got %r" % (table,)) from None
+        if a.dtype.kind not in "iu":
+            raise TypeError("table must hold integers, got %s" % a.dtype)
+        t = torch.from_numpy(np.ascontiguousarray(a).astype(np.int64))
+    if t.dim() != 2 or t.shape[1] != 2 or t.shape[0] < 1:
+        raise ValueError("table must be (N >= 1, 2): the fields of the even and of the odd rows, got shape %s" % (tuple(t.shape),))
+    if int(t.min()) < 0 or int(t.max()) >= T:
+        raise ValueError("table names fields %d .. %d of %d fields" % (int(t.min()), int(t.max()), T))
+    return t.to(torch.int32).contiguous()
+
+
+def _weave(ts, descs, table, layout, out_dtype):
+    """papof_weave_fields_tensor of the checked fields ts[0] by the checked host table: the video"""
+    (T, Hf, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    N = int(table.shape[0])
+    out, d_out = _new_frames(N, 2 * Hf, W, C, layout, out_dtype, dev)
+    tab = table.to(dev)
+    d_in = _struct(ts[0], strides, code)
+    _launch(dev, "papof_weave_fields_tensor", T, Hf, W, C, ctypes.byref(d_in), N, ctypes.c_void_p(tab.data_ptr()),
+            ctypes.byref(d_out))
+    return out
+
+
+def weave_fields(fields, table, *, layout="NCHW", out_dtype=None):
+    """Frames woven from the fields that a table names (papof_weave_fields_tensor, one HIP kernel, one pass): fields (T, C,
+    Hf, W) or (T, Hf, W, C) by `layout`, T >= 1, C = 1 .. 4, uint8, float32 or float64, any strides, on a HIP device; table
+    (N, 2) integers of any integer dtype, on any device or a numpy array: row 2 j of frame n is row j of field table[n, 0],
+    row 2 j + 1 is row j of field table[n, 1].  Fields may repeat and come in any order.  Returns the video (N, ..., 2 Hf, W
+    ...) in `layout` and out_dtype (by default the fields'; uint8 to uint8 keeps the bytes).  The table is checked on the
+    host (a device tensor waits for its stream); the kernel is enqueued on the current stream and the call returns without
+    waiting."""
+    ts, descs, out_dtype, _ = _check_video(fields, layout, 1, out_dtype, name="fields", min_frames=1)
+    if descs[0][0][1] > MAX_FIELD_HEIGHT:
+        raise ValueError("fields must have at most %d rows, got %d" % (MAX_FIELD_HEIGHT, descs[0][0][1]))
+    return _weave(ts, descs, _check_weave_table(table, descs[0][0][0]), layout, out_dtype)
+
+
+def telecine_plan(groups, first, orphans):
+    """What inverse_telecine makes of numpy groups (N, 2): (table (M, 2) int64 -- the fields of the even and the odd rows of
+    every output frame, an orphan's own field twice --, the rows of `groups` that give a frame, times (M,) float64, kinds
+    (M,) uint8).  A group of 2 or 3 is woven from its first two fields; a group of 1 is an orphan, left out by "drop"."""
+    import numpy as np
+    keep = [i for i, (s, n) in enumerate(groups) if n >= 2 or orphans != "drop"]
+    table, times, kinds = [], [], []
+    for i in keep:
+        s, n = int(groups[i, 0]), int(groups[i, 1])
+        if n == 1:
+            table.append((s, s))
+            times.append(float(s))
+            kinds.append(1)
+        else:
+            even = s if (s + first) & 1 == 0 else s + 1
+            table.append((even, 2 * s + 1 - even))
+            times.append(s + 0.5)
+            kinds.append(0)
+    return (np.array(table, np.int64).reshape(-1, 2), np.array(keep, np.int64), np.array(times, np.float64),
+            np.array(kinds, np.uint8))
+
+
+def _check_orphans(orphans):
+    if orphans not in ORPHANS:
+        raise ValueError("orphans must be one of %s, got %r" % (ORPHANS, orphans))
+    return orphans
+
+
+def _detelecine(ts, descs, first, match, orphans, deinterlacer, layout, out_dtype):
+    """inverse_telecine behind the match: deinterlacer() gives the (T, ...) video that the orphans' frames are taken from"""
+    torch = _torch()
+    T = descs[0][0][0]
+    table, keep, times, kinds = telecine_plan(match.groups.numpy(), first, orphans)
+    if len(table) == 0:
+        raise ValueError("every field is an orphan and orphans='drop' leaves no frame")
+    extra = None
+    if kinds.any():
+        if T < 4:
+            raise ValueError("field %d has no partner and the deinterlacer needs 4 fields, got %d: orphans='drop' leaves it out"
+                             % (int(table[kinds != 0][0, 0]), T))
+        extra = deinterlacer()
+    video = _weave(ts, descs, torch.from_numpy(table).to(torch.int32), layout, out_dtype)
+    if extra is not None:
+        dev = video.device
+        orphan = torch.from_numpy(kinds != 0)
+        video[orphan.to(dev)] = extra[torch.from_numpy(table[:, 0])[orphan].to(dev)]
+    return Detelecined(video, match.groups[torch.from_numpy(keep)], torch.from_numpy(times), torch.from_numpy(kinds), match)
+
+
+def inverse_telecine(fields, first=0, *, orphans="bob", flow_fw=None, flow_bw=None, sigma=DEINT_SIGMA,
+                     comb_threshold=COMB_THRESHOLD, diff_threshold=DIFF_THRESHOLD, cell_rows=16, margin=None, dominance=3,
+                     layout="NCHW", out_dtype=None):
+    """The film frames of a telecined sequence of fields: field_metrics (first, comb_threshold, diff_threshold, cell_rows),
+    match_fields (margin, dominance) and weave_fields chained.  fields (T, C, Hf, W) or (T, Hf, W, C) by `layout`, T >= 3,
+    as field_metrics takes them.  A group of 2 or 3 fields becomes one frame, woven from its first two fields (the third
+    of a triple is the repeat).  A group of 1 -- a video insert, a field orphaned by an edit -- has no partner and goes by
+    `orphans`: "bob": bob_fields' frame of it; "mc": deinterlace_fields' frame of it on flow_fw, flow_bw (T - 2, 2, Hf, W),
+    which are then required (and refused otherwise), with sigma; "drop": it is left out.  The deinterlacer needs T >= 4:
+    with T = 3 and an orphan, anything but "drop" raises; so does "drop" when every field is an orphan.
+    Returns Detelecined(video (N, ..., 2 Hf, W ...) in `layout` and out_dtype -- by default the fields'; uint8 to uint8:
+    the woven frames are the fields' bytes --, groups (N, 2) [start, length] of the frames, times (N,) float64: the mean
+    field index of the fields used, kinds (N,) uint8: 0 woven, 1 orphan, match: the FieldMatch).  The output rate is not
+    constant: times says when each frame was.  Not handled: the critical vertical velocity (an odd number of frame rows
+    per film frame makes the WRONG pairing a line-doubled frame without a comb: the match inverts; a video pan near one
+    row per field gets fields misvoted); the thresholds are relative to the noise (noise of 5 / 255 needs comb_threshold
+    26 / 255); no cadence lock (static stretches are cut 2-2-2); no blended telecine; no chroma-subsampling model.  Every
+    argument error raises before a launch; the call waits for the counts (match_fields), the video is enqueued on the
+    current stream behind them."""
+    first = _check_parity(first)
+    orphans = _check_orphans(orphans)
+    sigma = _check_deint_sigma(sigma)
+    comb_q, diff_q = _check_q("comb_threshold", comb_threshold), _check_q("diff_threshold", diff_threshold)
+    cell_rows = _check_cell_rows(cell_rows)
+    ts, descs, out_dtype, _ = _check_telecine_fields(fields, layout, 1, out_dtype)
+    (T, Hf, W, _), _, _ = descs[0]
+    codes = None
+    if orphans == "mc":
+        if T < 4:
+            raise ValueError("orphans='mc' needs at least 4 fields, got %d" % T)
+        codes = _check_flows(flow_fw, flow_bw, (T - 2, 2, Hf, W), ts[0].device)
+    elif flow_fw is not None or flow_bw is not None:
+        raise ValueError("flow_fw and flow_bw are read with orphans='mc' only, got orphans=%r" % (orphans,))
+    margin, dominance = _check_match_rule(cell_rows, margin, dominance)
+    match = match_fields(_field_metrics(ts, descs, first, cell_rows, comb_q, diff_q), margin=margin, dominance=dominance)
+    if orphans == "mc":
+        deinterlacer = lambda: _deinterlace(ts, descs, first, 1, (flow_fw, flow_bw), codes, sigma, layout, out_dtype).video  # noqa: E731
+    else:
+        deinterlacer = lambda: _deinterlace(ts, descs, first, 0, None, None, DEINT_SIGMA, layout, out_dtype).video  # noqa: E731
+    return _detelecine(ts, descs, first, match, orphans, deinterlacer, layout, out_dtype)
+
+
+def inverse_telecine_video(fields, pyramidLevels, first=0, *, sigma=DEINT_SIGMA, comb_threshold=COMB_THRESHOLD,
+                           diff_threshold=DIFF_THRESHOLD, cell_rows=16, margin=None, dominance=3, layout="NCHW", out_dtype=None,
+                           **solver):
+    """inverse_telecine with orphans="mc" on flows of its own: field_flows(fields, pyramidLevels, layout=layout, **solver)
+    is computed only when the match leaves a group of 1.  Returns DetelecinedVideo(Detelecined's fields, flow_fw, flow_bw
+    (T - 2, 2, Hf, W) float64 in field coordinates, timing of the flow call -- all three None when no field is an orphan)."""
+    first = _check_parity(first)
+    sigma = _check_deint_sigma(sigma)
+    comb_q, diff_q = _check_q("comb_threshold", comb_threshold), _check_q("diff_threshold", diff_threshold)
+    cell_rows = _check_cell_rows(cell_rows)
+    ts, descs, out_dtype, params = _check_telecine_fields(fields, layout, pyramidLevels, out_dtype, solver=solver)
+    margin, dominance = _check_match_rule(cell_rows, margin, dominance)
+    match = match_fields(_field_metrics(ts, descs, first, cell_rows, comb_q, diff_q), margin=margin, dominance=dominance)
+    flows = []
+
+    def deinterlacer():
+        fb = _field_flows(ts, descs, layout, pyramidLevels, params)
+        flows.append(fb)
+        return _deinterlace(ts, descs, first, 1, (fb.flow_fw, fb.flow_bw), (capi.DTYPE_F64, capi.DTYPE_F64), sigma, layout,
+                            out_dtype).video
+
+    d = _detelecine(ts, descs, first, match, "mc", deinterlacer, layout, out_dtype)
+    fb = flows[0] if flows else None
+    return DetelecinedVideo(*d, fb.flow_fw if fb else None, fb.flow_bw if fb else None, fb.timing if fb else None)
 
 
 MAX_RS_ITERS = 8  # include/papof.h: papof_rs_rectify_tensor
