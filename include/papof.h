@@ -1792,6 +1792,35 @@ int papof_field_metrics_tensor(papof_handle* h, int n_fields, int field_height, 
 int papof_weave_fields_tensor(papof_handle* h, int n_fields, int field_height, int width, int c, const papof_tensor* fields,
                               int n_frames, const int* table, const papof_tensor* video, void* stream);
 
+/* Shot boundaries, the device's part (shots.hip: k_cell_hist): every frame of a video reduced to histograms of its luma per
+ * cell of cell_rows x 64 pixels, as integer counts.  The calls above take their frames to be one continuous shot; the host
+ * compares the histograms of consecutive frames region by region to find the cuts (tensors.py: shot_distances, detect_cuts)
+ * and hands them over in the flows themselves: a NaN flow is "lost" to papof_track_tensor, "not alive" to
+ * papof_temporal_filter_tensor, papof_propagate_tensor and papof_super_resolve_tensor, "occluded" to papof_fb_check_tensor
+ * and "dead" to papof_refine_flow_tensor, papof_upsample_flow_tensor and papof_rs_rectify_tensor.  A parallel call: no call
+ * above changes.
+ * frames: n_frames = T >= 1 frames of height x width = H x W >= 1 x 1; uint8, float32 or float64, (frame, row, column,
+ * channel), any non-negative strides, c = C channels, 1 <= C <= 4.  cell_rows: 1 .. 64.  bins: 4, 8, 16, 32 or 64.
+ * hist: DEVICE pointer to T * Gy * Gx * bins int32, contiguous (frame, cy, cx, bin), Gy = ceil(H / cell_rows), Gx =
+ * ceil(W / 64); the cells at the bottom and right edges are clipped to the frame.  Every element is written exactly once.
+ * Everything is integer.  q as papof_field_metrics_tensor's: q(uint8 b) = 257 * b; q(float v) = 0 for a NaN, else
+ * clamp(rint(65535.0 * v), 0, 65535), the product in fp64, rint half to even.  At a pixel with channels q0 .. q(C-1):
+ *
+ *   L = q0                                     for C = 1 or 2  (a second channel is not read)
+ *   L = (77 * q0 + 150 * q1 + 29 * q2) >> 8    for C = 3 or 4  (a fourth channel is not read); 0 <= L <= 65535
+ *   bin = (L * bins) >> 16
+ *
+ * and hist[t, cy, cx, k] is the number of pixels (y, x) of frame t with y / cell_rows = cy, x / 64 = cx and bin = k: the bins of
+ * a cell add up to the cell's pixel count.
+ * One wave per cell, the counts by ballot: no atomics, no device memory besides the tensors, nothing of the handle's; the
+ * result does not depend on what `hist` held.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL:
+ * the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor, data pointer or hist, frames that are not uint8 /
+ * float32 / float64, a negative stride, n_frames, height or width < 1, c outside 1 .. 4, cell_rows outside 1 .. 64, or bins
+ * not one of 4, 8, 16, 32, 64. */
+int papof_cell_hist_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
+                           int cell_rows, int bins, int* hist, void* stream);
+
 /* Rolling-shutter rectification along the flows (rolling.hip: k_rs_rectify, k_rs_flow).  A rolling shutter reads the rows of
  * a frame one after another: row y of frame t of H rows is exposed at the time t + readout * (y - a) / H, in frame intervals,
  * with a = anchor * (H - 1) the row that is exposed at the frame's own time.  The video's dense flows give every pixel's

@@ -23,27 +23,20 @@
 // row of both neighbours in registers, so that every row of the three fields is loaded once per cell plus one halo row; the
 // three counts are __ballot + __popcll into wave-uniform accumulators (as k_mask_dilate packs its mask bits), and three
 // lanes store them.  No lane leaves before the last __ballot or __shfl.  Packed uint8 rows (NHWC frames) are loaded as
-// aligned dwords by the wave and handed to their lanes across the wave (packed_pixel); everything else lane by lane.  No
+// aligned dwords by the wave and handed to their lanes across the wave (cells.h: packed_pixel); everything else lane by lane.  No
 // atomics, no workspace, every element of `metrics` is written exactly once -- fields 0 and T - 1, which have one
 // neighbour, get zeros --, every offset 64-bit.
 //
 // Mapping, k_weave_fields.  k_deinterlace's: a block is a 64 x 4 tile of field pixels, blockIdx.x the tile, blockIdx.y the
 // frame; one lane writes rows 2 j and 2 j + 1 of its column from row j of the frame's two fields: one pass, every output
 // element written once.
-#include "sampler.h"
-
-#include <cmath>
+#include "cells.h"
 
 namespace papof {
 
 namespace {
 
-constexpr int kCellW = 64;     // columns of a cell: one wave
-constexpr int kCellsX = 4;     // cells of a block
-constexpr int kMaxCellRows = 64;
 constexpr int kRowsAhead = 4;  // rows of a cell whose loads are in flight together (1: 1.12 x, 8: 1.14 x the kernel's time at 4)
-constexpr int kMaxQ = 65535;
-constexpr int kMaxC = 4;
 
 struct MetricArgs {
     papof_tensor fl;  // fields (field, row, column, channel)
@@ -53,39 +46,11 @@ struct MetricArgs {
     int Gy, Gx;
 };
 
-// the quantised value of an element: 257 b of a byte; of a float 0 for a NaN, else clamp(rint(65535.0 v), 0, 65535) in fp64
-template <int FD>
-__device__ __forceinline__ int load_q(const papof_tensor& t, long long o) {
-    if (FD == PAPOF_DTYPE_U8) return 257 * (int)static_cast<const unsigned char*>(t.data)[o];
-    const double v = FD == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
-    return (int)fmin(fmax(rint(65535.0 * v), 0.0), (double)kMaxQ);  // (fmax: NaN -> 0)
-}
-
 // m(b; a, c): how far b lies outside the range of a and c
 __device__ __forceinline__ int comb(int b, int a, int c) {
     const int da = a - b, dc = c - b;
     if ((da > 0 && dc > 0) || (da < 0 && dc < 0)) return min(abs(da), abs(dc));
     return 0;
-}
-
-// The C bytes of pixel `lane` of a packed uint8 row segment (channels adjacent, pixels adjacent) that starts at p and has
-// n bytes, 1 <= n <= 64 C, as one word, channel k in byte k -- p and n wave-uniform, called by ALL lanes of the wave.  The
-// wave loads the segment once as aligned dwords (lane i the i-th; the last one, which is the 65th of a misaligned segment
-// of four channels, by every lane) and each lane takes the two dwords that hold its pixel from the lanes that loaded them
-// (ds_bpermute): one load and one register per row, where a lane that gathers its bytes itself has C of each.  (By itself
-// this measured no faster than the gathers; it is what keeps four rows of three fields in flight within 76 VGPRs.)  The
-// aligned words that hold the segment's first and last byte are read whole: up to 3 bytes on either side of it, of the
-// same 4-byte word and therefore of the same page.  A lane beyond the segment gets bytes that mean nothing.
-__device__ __forceinline__ unsigned packed_pixel(const unsigned char* p, int n, int lane, int C) {
-    const unsigned mis = (unsigned)(reinterpret_cast<unsigned long long>(p) & 3);
-    const unsigned* q = reinterpret_cast<const unsigned*>(p - mis);
-    const int ndw = (int)((mis + n + 3) >> 2);  // <= 65
-    const unsigned d = q[lane < ndw ? lane : ndw - 1];  // (no branch around a load: the rows' loads are issued together)
-    const unsigned e = q[ndw - 1];                      // the 65th where there is one (one address for the wave)
-    const unsigned o = mis + lane * C;          // <= 3 + 63 * 4: its first dword is one of the 64
-    const int i = (int)(o >> 2);
-    const unsigned lo = __shfl(d, i), up = __shfl(d, (i + 1) & 63);
-    return __builtin_amdgcn_alignbyte(i + 1 == 64 ? e : up, lo, o & 3);
 }
 
 // q of the C channels of pixel x0 + lane of the row at `row` (the offset of its field and row): PACKED (uint8, channels and

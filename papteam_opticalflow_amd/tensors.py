@@ -190,6 +190,16 @@ Wrong at the critical vertical velocity; thresholds are relative to the noise; n
 
     it = inverse_telecine(fields, layout="NHWC")   # it.video (N, H, W, C): the film frames, it.times, it.kinds, it.match.cadence
 
+Shot boundaries: every *_video call takes its frames to be one shot.  `shot_histograms` (include/papof.h:
+papof_cell_hist_tensor) reduces every frame to integer luma histograms per cell, one HIP kernel; `shot_distances` and
+`detect_cuts` compare consecutive frames region by region on the host (cuts, one-frame flashes, runs of cuts), `detect_shots`
+chains them, `split_shots` gives the frame ranges for running any call shot by shot, `cut_flows` marks the cut pairs of a
+FlowFB with NaN flows -- which every consumer of flows already takes as "nothing to follow" -- and `flow_video_shots` is
+flow_video_fb that spends no solve on a cut pair.  No gradual transitions; luma only; thresholds relative to the neighbourhood;
+nothing downstream calls it by itself.
+
+    fb, shots = flow_video_shots(frames, 5, layout="NHWC")   # shots.cuts, shots.ranges; fb: a FlowFB over all T - 1 pairs
+
 Rolling shutter: `rectify_frames` (include/papof.h: papof_rs_rectify_tensor) resamples a video whose rows were read out one
 after another -- row y of frame t at t + readout (y - a) / H -- to what a global shutter would have recorded at the frame's
 time: every pixel's position one frame earlier and later is in the flows, the parabola through the three points is its
@@ -250,6 +260,8 @@ FieldMetrics = collections.namedtuple("FieldMetrics", "counts cell_rows first")
 FieldMatch = collections.namedtuple("FieldMatch", "votes links groups cadence share")
 Detelecined = collections.namedtuple("Detelecined", "video groups times kinds match")
 DetelecinedVideo = collections.namedtuple("DetelecinedVideo", Detelecined._fields + ("flow_fw", "flow_bw", "timing"))
+ShotHist = collections.namedtuple("ShotHist", "hist cell_rows bins size")
+Shots = collections.namedtuple("Shots", "cuts flashes gradual distances ranges")
 Rectified = collections.namedtuple("Rectified", "video valid flow_fw flow_bw occlusion timing")
 StabilizedRS = collections.namedtuple("StabilizedRS", "video valid transforms motion ok flow_fw flow_bw occlusion timing")
 Consistent = collections.namedtuple("Consistent", "video flow_fw flow_bw timing")
@@ -2509,6 +2521,291 @@ def inverse_telecine_video(fields, pyramidLevels, first=0, *, sigma=DEINT_SIGMA,
     d = _detelecine(ts, descs, first, match, "mc", deinterlacer, layout, out_dtype)
     fb = flows[0] if flows else None
     return DetelecinedVideo(*d, fb.flow_fw if fb else None, fb.flow_bw if fb else None, fb.timing if fb else None)
+
+
+# ---- shot boundaries (include/papof.h: papof_cell_hist_tensor)
+HIST_BINS = (4, 8, 16, 32, 64)
+CUT_FLOOR = 0.2    # tests/test_shots_cpu.py: a one-frame flash of gain 1.8 reaches 0.306, a (4, 25) pan with noise 0.138
+CUT_RATIO = 3.0
+CUT_WINDOW = 4
+CUT_POOL = (4, 2)  # cells per region, down and across: 64 x 128 pixels at 16-row cells
+
+
+def _check_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins not in HIST_BINS:
+        raise ValueError("bins must be one of %s, got %r" % (HIST_BINS, bins))
+    return bins
+
+
+def _cell_hist(ts, descs, cell_rows, bins):
+    """papof_cell_hist_tensor of the checked frames ts[0]: a ShotHist"""
+    torch = _torch()
+    (T, H, W, C), strides, code = descs[0]
+    dev = ts[0].device
+    hist = torch.empty((T, -(-H // cell_rows), -(-W // CELL_COLUMNS), bins), dtype=torch.int32, device=dev)
+    d_in = _struct(ts[0], strides, code)
+    _launch(dev, "papof_cell_hist_tensor", T, H, W, C, ctypes.byref(d_in), cell_rows, bins, ctypes.c_void_p(hist.data_ptr()))
+    return ShotHist(hist, cell_rows, bins, (H, W))
+
+
+def shot_histograms(frames, *, cell_rows=16, bins=16, layout="NCHW"):
+    """The luma histograms of every frame of a video per cell of cell_rows (1 .. 64) x 64 pixels (papof_cell_hist_tensor, one
+    HIP kernel): T >= 1 frames (T, C, H, W) or (T, H, W, C) by `layout`, C = 1 .. 4, uint8, float32 or float64, any strides,
+    on a HIP device.  Values are quantised to 0 .. 65535 as field_metrics does (a byte b is 257 b, a float v clamp(rint(65535
+    v), 0, 65535), NaN 0) and everything after that is integer: the luma is channel 0 of 1 or 2 channels and (77 q0 + 150 q1 +
+    29 q2) >> 8 of 3 or 4, its bin (L * bins) >> 16 with bins one of 4, 8, 16, 32, 64.
+    Returns ShotHist(hist (T, ceil(H / cell_rows), ceil(W / 64), bins) int32 on the frames' device -- the cells at the bottom
+    and right edges are clipped; every cell's bins add up to its pixel count --, cell_rows, bins, size (H, W)).  Enqueued on
+    the current stream; returns without waiting."""
+    cell_rows = _check_cell_rows(cell_rows)
+    bins = _check_bins(bins)
+    ts, descs, _, _ = _check_video(frames, layout, 1, None, min_frames=1)
+    return _cell_hist(ts, descs, cell_rows, bins)
+
+
+def _check_pool(pool):
+    try:
+        py, px = pool
+    except (TypeError, ValueError):
+        raise TypeError("pool must be (cells down, cells across), got %r" % (pool,)) from None
+    for v in (py, px):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError("pool must be two integers >= 1, got %r" % (pool,))
+    return py, px
+
+
+def _check_hist(hist):
+    """the counts of a ShotHist as a numpy (T, Gy, Gx, bins) int64 array: one copy from the device"""
+    import numpy as np
+    torch = _torch()
+    if not isinstance(hist, ShotHist):
+        raise TypeError("hist must be a ShotHist (shot_histograms' return), got %s" % type(hist).__name__)
+    h = hist.hist
+    if not isinstance(h, torch.Tensor) or h.dtype != torch.int32:
+        raise TypeError("hist.hist must be an int32 tensor")
+    if h.dim() != 4 or min(h.shape) < 1:
+        raise ValueError("hist.hist must be (T >= 1, Gy, Gx, bins), got shape %s" % (tuple(h.shape),))
+    return h.detach().cpu().numpy().astype(np.int64)
+
+
+def pool_cells(counts, pool):
+    """numpy counts (T, Gy, Gx, bins) summed over regions of pool[0] x pool[1] cells -- histograms add --, the regions at the
+    bottom and right edges clipped: (T, ceil(Gy / pool[0]), ceil(Gx / pool[1]), bins)"""
+    import numpy as np
+    py, px = pool
+    return np.add.reduceat(np.add.reduceat(counts, np.arange(0, counts.shape[1], py), axis=1),
+                           np.arange(0, counts.shape[2], px), axis=2)
+
+
+def pooled_distances(regions, step):
+    """(T - step,) float64 of numpy region histograms (T, Ry, Rx, bins): shot_distances' rule behind the pooling"""
+    import numpy as np
+    a, b = regions[:-step], regions[step:]
+    if len(a) == 0:
+        return np.zeros((0,), np.float64)
+    d = np.abs(a - b).sum(-1).astype(np.float64) / (2.0 * a.sum(-1).astype(np.float64))
+    return np.median(d.reshape(len(a), -1), axis=1)
+
+
+def shot_distances(hist, *, pool=CUT_POOL, step=1):
+    """How much the luma distribution changes from frame t to frame t + step, region by region: the host's measure on one
+    copy of shot_histograms' counts -- THIS CALL WAITS for the stream that wrote them.  The cells are summed into regions of
+    pool[0] x pool[1] cells (down, across; the edge regions clipped); per region d = sum_k |a_k - b_k| / (2 sum_k a_k) in
+    float64, a and b the region's histograms in the two frames: 0 for equal histograms, 1 for disjoint ones; the pair's
+    distance is numpy.median over the regions (the mean of the middle two of an even number).  A histogram forgets where a
+    region's pixels are, so motion changes it only by what enters and leaves the region; the median forgets what happens in
+    fewer than half of the regions.  Returns a (T - step,) float64 numpy array, empty for T <= step."""
+    py, px = _check_pool(pool)
+    if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+        raise ValueError("step must be an integer >= 1, got %r" % (step,))
+    return pooled_distances(pool_cells(_check_hist(hist), (py, px)), step)
+
+
+def _check_cut_rule(floor, ratio, window):
+    """(floor in [0, 1], ratio >= 1, window >= 1) of detect_cuts' keywords as (float, float, int) -- TypeError / ValueError
+    otherwise"""
+    for name, v in (("floor", floor), ("ratio", ratio)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s must be a number, got %r" % (name, v))
+    if not 0 <= floor <= 1:  # (false for a NaN)
+        raise ValueError("floor must lie in [0, 1], got %r" % (floor,))
+    if not (math.isfinite(ratio) and ratio >= 1):
+        raise ValueError("ratio must be finite and >= 1, got %r" % (ratio,))
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError("window must be an integer >= 1, got %r" % (window,))
+    return float(floor), float(ratio), window
+
+
+def split_shots(n_frames, cuts):
+    """The frame ranges [(start, stop), ...] -- stop exclusive -- of a video of n_frames >= 1 frames cut between frames t and
+    t + 1 for every t of `cuts` (integers in 0 .. n_frames - 2, in any order, none twice): frames[start:stop] is one shot, for
+    running any *_video call shot by shot."""
+    if isinstance(n_frames, bool) or not isinstance(n_frames, int) or n_frames < 1:
+        raise ValueError("n_frames must be an integer >= 1, got %r" % (n_frames,))
+    cuts = _check_cuts(cuts, n_frames - 1)
+    edges = [0] + [t + 1 for t in cuts] + [n_frames]
+    return list(zip(edges[:-1], edges[1:]))
+
+
+def _check_cuts(cuts, n_pairs):
+    """the cuts as a sorted list of distinct integers in 0 .. n_pairs - 1 -- TypeError / ValueError otherwise"""
+    import numpy as np
+    torch = _torch()
+    if isinstance(cuts, torch.Tensor):
+        cuts = cuts.detach().cpu().numpy()
+    try:
+        a = np.asarray(cuts if not isinstance(cuts, (set, frozenset)) else sorted(cuts))
+    except Exception:  # noqa: BLE001
+        raise TypeError("cuts must be a sequence of integers, got %r" % (cuts,)) from None
+    if a.size == 0:
+        return []
+    if a.dtype.kind not in "iu" or a.ndim != 1:
+        raise TypeError("cuts must be a sequence of integers, got %r" % (cuts,))
+    out = sorted(int(t) for t in a)
+    if out[0] < 0 or out[-1] >= n_pairs:
+        raise ValueError("cuts must lie in 0 .. %d (a cut at t lies between frames t and t + 1), got %r" % (n_pairs - 1, out))
+    if len(set(out)) != len(out):
+        raise ValueError("cuts names a pair twice: %r" % (out,))
+    return out
+
+
+def cut_candidates(d, floor, ratio, window):
+    """which pairs of numpy distances (N,) are candidates: detect_cuts' rule for one pair after another"""
+    import numpy as np
+    cand = np.zeros(len(d), bool)
+    for t in range(len(d)):
+        others = np.concatenate([d[max(0, t - window):t], d[t + 1:t + 1 + window]])
+        base = float(np.median(others)) if len(others) else 0.0
+        cand[t] = d[t] >= floor and d[t] >= ratio * base
+    return cand
+
+
+def detect_cuts(hist, *, floor=CUT_FLOOR, ratio=CUT_RATIO, window=CUT_WINDOW, pool=CUT_POOL):
+    """The cuts of a video from shot_histograms' counts: the host's rule -- THIS CALL WAITS for the stream that wrote them.
+    With d = shot_distances(hist, pool=pool), pair t (frames t and t + 1) is a candidate where d[t] >= floor and d[t] >= ratio
+    times the median of the other d within `window` pairs either side (0 where there are none): the threshold is relative to
+    what the shot's own motion does to the measure.  A maximal run of consecutive candidates is judged by its length: one pair
+    is a cut; two pairs t, t + 1 are a FLASH at frame t + 1 -- and no cut -- where shot_distances(step=2)[t] < floor (frames t
+    and t + 2 belong together), otherwise two cuts around a one-frame shot; three or more are cuts all of them, and (first,
+    last) is reported in `gradual` as well: a dissolve and a run of one-frame shots get the same, safe treatment.
+    The defaults were calibrated on scenes cut from the committed 1080p frame (tests/test_shots_cpu.py): inside a shot a pan
+    of (4, 25) pixels per frame with noise stays below 0.138, an exposure ramp of 5 % per frame below 0.058; a cut to the
+    adjacent region reaches 0.333, a flash of gain 1.8 0.306 at both its pairs.
+    Returns Shots(cuts: the sorted pair indices t, a cut at t lies between frames t and t + 1; flashes: frame indices;
+    gradual: (first, last) pairs; distances: d, a (T - 1,) float64 numpy array; ranges: split_shots(T, cuts))."""
+    floor, ratio, window = _check_cut_rule(floor, ratio, window)
+    py, px = _check_pool(pool)
+    regions = pool_cells(_check_hist(hist), (py, px))
+    T = regions.shape[0]
+    d = pooled_distances(regions, 1)
+    cand = cut_candidates(d, floor, ratio, window)
+    cuts, flashes, gradual = [], [], []
+    t = 0
+    while t < len(d):
+        if not cand[t]:
+            t += 1
+            continue
+        n = 1
+        while t + n < len(d) and cand[t + n]:
+            n += 1
+        if n == 2 and pooled_distances(regions[t:t + 3], 2)[0] < floor:
+            flashes.append(t + 1)
+        else:
+            cuts.extend(range(t, t + n))
+            if n >= 3:
+                gradual.append((t, t + n - 1))
+        t += n
+    return Shots(cuts, flashes, gradual, d, split_shots(T, cuts))
+
+
+def detect_shots(frames, *, cell_rows=16, bins=16, layout="NCHW", floor=CUT_FLOOR, ratio=CUT_RATIO, window=CUT_WINDOW,
+                 pool=CUT_POOL):
+    """detect_cuts(shot_histograms(frames, cell_rows=, bins=, layout=), floor=, ratio=, window=, pool=): the Shots of a video
+    on a HIP device.  Every argument error raises before anything is enqueued; the call waits for the counts."""
+    cell_rows, bins = _check_cell_rows(cell_rows), _check_bins(bins)
+    _check_cut_rule(floor, ratio, window)
+    _check_pool(pool)
+    ts, descs, _, _ = _check_video(frames, layout, 1, None, min_frames=1)
+    return detect_cuts(_cell_hist(ts, descs, cell_rows, bins), floor=floor, ratio=ratio, window=window, pool=pool)
+
+
+def _kill_pairs(fb, pairs):
+    """the pairs `pairs` (an index or a slice) of a FlowFB's tensors made a cut's, in place"""
+    for f in (fb.flow_fw, fb.flow_bw):
+        f[pairs] = math.nan
+    if fb.occlusion is not None:
+        fb.occlusion[pairs] = True
+    for w in (fb.warpI2_fw, fb.warpI2_bw):
+        if w is not None:
+            w[pairs] = 0
+
+
+def cut_flows(fb, cuts):
+    """A FlowFB (flow_video_fb's return, or any FlowFB of (B, 2, H, W) flows) whose pairs `cuts` -- integers in 0 .. B - 1 --
+    say that there is nothing to follow: both flows of the pair are the quiet NaN, which every consumer takes as its ABI
+    states (track_points: lost; temporal_filter, propagate, super_resolve: the chain ends; fb_consistency: occluded;
+    refine_flow, upsample_flow, the rolling-shutter calls: dead), occlusion is True in both channels and warpI2_* zero where
+    they are present.  Every tensor of the result is a COPY: `fb` is left as it was and shares no storage with the result;
+    timing is the same dict.  Torch operations on the tensors' device, enqueued on the current stream."""
+    torch = _torch()
+    if not isinstance(fb, FlowFB):
+        raise TypeError("fb must be a FlowFB (flow_video_fb's return), got %s" % type(fb).__name__)
+    for name, f in (("fb.flow_fw", fb.flow_fw), ("fb.flow_bw", fb.flow_bw)):
+        _check_flow(name, f)
+    if fb.flow_fw.shape != fb.flow_bw.shape:
+        raise ValueError("fb.flow_fw %s and fb.flow_bw %s differ in shape" % (tuple(fb.flow_fw.shape), tuple(fb.flow_bw.shape)))
+    B = int(fb.flow_fw.shape[0])
+    for name, t in (("fb.warpI2_fw", fb.warpI2_fw), ("fb.warpI2_bw", fb.warpI2_bw), ("fb.occlusion", fb.occlusion)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[0] != B):
+            raise ValueError("%s must be None or a 4-D tensor of %d pairs" % (name, B))
+    cuts = _check_cuts(cuts, B)
+    out = FlowFB(*(t.clone() if t is not None else None for t in fb[:5]), fb.timing)
+    if cuts:
+        _kill_pairs(out, torch.tensor(cuts, dtype=torch.int64, device=fb.flow_fw.device))
+    return out
+
+
+def flow_video_shots(frames, pyramidLevels, *, cuts=None, layout="NCHW", out_dtype=None, consistency=CONSISTENCY, **solver):
+    """flow_video_fb of a video that has cuts: T >= 2 frames as flow_video_fb takes them; cuts: the pair indices that are cuts
+    (as split_shots takes them), or None: detect_shots(frames, layout=layout) at its defaults finds them (the frames then have
+    1 .. 4 channels).  flow_video_fb runs on every shot of at least two frames -- no solve is spent on a cut pair --, and the
+    result is one FlowFB over all T - 1 pairs: a shot's pairs are flow_video_fb's on that shot alone, byte for byte, a cut
+    pair is what cut_flows makes of it (NaN flows, occluded, warpI2_* zero); timing is the sum of the shots' timers.  An
+    initial flow is refused: it would have to know the cuts.  Returns (FlowFB, Shots) -- for given cuts Shots(cuts, [], [],
+    None, ranges).  Every argument error raises before anything is enqueued; complete on return."""
+    torch = _torch()
+    if "init_flow" in solver or "init_flow_bw" in solver:
+        raise TypeError("flow_video_shots takes no initial flow: run flow_video_fb on split_shots' ranges to give one per shot")
+    alphas = _alphas(consistency)
+    ts, descs, out_dtype, params = _check([("frames", frames)], layout, out_dtype, pyramidLevels, min_frames=2, solver=solver)
+    (T, H, W, C), _, _ = descs[0]
+    dev = ts[0].device
+    if cuts is None:
+        if C > MAX_CHANNELS:
+            raise ValueError("frames must have 1 .. %d channels to detect the cuts, got %d (layout %s)" % (MAX_CHANNELS, C, layout))
+        shots = detect_cuts(_cell_hist(ts, descs, 16, 16))
+    else:
+        cuts = _check_cuts(cuts, T - 1)
+        shots = Shots(cuts, [], [], None, split_shots(T, cuts))
+    flow_fw, warp_fw, _, _ = _outputs(T - 1, H, W, C, layout, out_dtype, dev)
+    flow_bw, warp_bw, _, _ = _outputs(T - 1, H, W, C, layout, out_dtype, dev)
+    occ = torch.empty((T - 1, 2, H, W), dtype=torch.bool, device=dev) if alphas[0] else None
+    keys = capi.timing_keys()
+    total = dict.fromkeys(keys, 0.0)
+    out = FlowFB(flow_fw, flow_bw, warp_fw, warp_bw, occ, None)
+    for start, stop in shots.ranges:
+        if stop - start >= 2:
+            sub = ts[0][start:stop]
+            fb = _run_fb([sub], [descriptor(sub, layout)], True, stop - start - 1, layout, out_dtype, pyramidLevels, alphas,
+                         params)
+            for dst, src in zip(out[:5], fb[:5]):
+                if dst is not None:
+                    dst[start:stop - 1] = src
+            for k in keys:
+                total[k] += float(fb.timing[k])
+        if stop < T:
+            _kill_pairs(out, stop - 1)
+    return out._replace(timing={k: "%f" % total[k] for k in keys}), shots
 
 
 MAX_RS_ITERS = 8  # include/papof.h: papof_rs_rectify_tensor
