@@ -10,7 +10,7 @@
 // Semantics: include/papof.h, papof_motion_blur_tensor.  Every sample is papof_interp_tensor's value (the three steps of
 // sampler.h, the same bits); fp64 without contraction (-ffp-contract=off), samples accumulated in the table's order.
 //
-// Mapping.  A block is a 64 x 4 tile of output pixels (k_interp's): blockIdx.x the tile, blockIdx.y the frame.  The sample
+// Mapping.  A block is a 64 x 4 tile of output pixels (k_interp's), over grid.h's grid of tiles and frames.  The sample
 // table (offsets and weights, at most kMaxSamples) travels in the kernel arguments: it is the same for every lane, so it
 // sits in scalar registers, and the call needs no device buffer and nothing the caller has to keep alive.  A sample with
 // offset < 0 lies in the pair (f - 1, f), one with offset > 0 in (f, f + 1).  The geometry of a sample (taps, weights,
@@ -139,17 +139,12 @@ __device__ __forceinline__ void blur_sample(const BlurArgs& a, const double* lut
     wsum = wsum + w;
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD, int NC, bool SORTED>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_motion_blur(const BlurArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    stage_u8_lut<FD, kInterpTX>(lut);
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long f = frame0 + blockIdx.y;
     const bool has[2] = {f > 0, f < a.T - 1};  // the pairs (f - 1, f) and (f, f + 1)
@@ -218,10 +213,7 @@ int launch_blur_of(hipStream_t st, BlurArgs a) {
     const bool sorted = k == a.n;
     const auto kernel = a.C == 3 ? (sorted ? k_motion_blur<FD, 3, true> : k_motion_blur<FD, 3, false>)
                                  : (sorted ? k_motion_blur<FD, 1, true> : k_motion_blur<FD, 1, false>);
-    const long long tiles = ((a.W + kInterpTX - 1) / (long long)kInterpTX) * ((a.H + kInterpTY - 1) / (long long)kInterpTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kInterpTX, kInterpTY), 0, st, a, t0, f0);
-    });
+    return launch_grid<InterpTile>(a.H, a.W, a.T, st, 0, kernel, a);
 }
 
 int launch_blur(hipStream_t st, const BlurArgs& a) {
@@ -241,13 +233,11 @@ extern "C" int papof_motion_blur_tensor(papof_handle* h, int n_frames, const pap
                                         const papof_tensor* occlusion, int n_samples, const double* offsets,
                                         const double* weights, const papof_tensor* out, void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto all = {0, 1, 2, 3};
-    if (!described(frames, I, all, false) || !described(flow_fw, F, all, false) || !described(flow_bw, F, all, false))
+    if (!in_frames(frames) || !in_flow_pair(flow_fw, flow_bw))
         return PAPOF_EINVAL;
     if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, all, false)) return PAPOF_EINVAL;
-    if (!described(out, I, all, true)) return PAPOF_EINVAL;
+    if (!out_frames(out)) return PAPOF_EINVAL;
     if (n_samples < 1 || n_samples > kMaxSamples || !offsets || !weights) return PAPOF_EINVAL;
     const double lo = std::ldexp(1.0, -20), hi = 1.0 - lo;
     BlurArgs a{};

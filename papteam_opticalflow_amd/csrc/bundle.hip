@@ -11,7 +11,7 @@
 // Semantics: include/papof.h, papof_bundle_sums_tensor.  fp64 without contraction (-ffp-contract=off).
 //
 // Reduction.  motion.hip's, over SAMPLED pixels: no atomics, bitwise reproducible from run to run.  Launch 1 (k_bundle_sums):
-// a block is a 64 x 32 tile of sampled pixels of one link (blockIdx.x the tile, blockIdx.y the link), a lane one sampled
+// a block is a 64 x 32 tile of sampled pixels of one link (grid.h's grid of tiles and links), a lane one sampled
 // column and 8 sampled rows (threadIdx.y + 4 k) in increasing row order; the lanes of a wave are summed by a fixed shuffle
 // tree (__shfl_down, 32 .. 1), the four waves in wave order through LDS, and the block writes one row of 32 doubles (twenty
 // used) to the workspace.  The link's row of ten doubles (R row-major, f) is read as uniform loads.  Launch 2
@@ -29,6 +29,7 @@ namespace {
 
 constexpr int kBTX = 64, kBTY = 4, kBRows = 8;  // a lane: one sampled column, kBRows sampled rows kBTY apart
 constexpr int kBTH = kBTY * kBRows;             // a block: 64 x 32 sampled pixels
+using SampleTile = Tile<kBTX, kBTH, kBTX, kBTY>;  // a strip of kBTH sampled rows under a block of kBTY
 constexpr int kBSums = 20;                      // include/papof.h: the order of the sums
 constexpr int kBRow = 32;                       // doubles per partial row (kBSums used)
 
@@ -65,9 +66,7 @@ __global__ __launch_bounds__(kBTX* kBTY) void k_bundle_sums(const BundleArgs a, 
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = rp[k * a.rot.stride[1]];
     const double f = rp[9 * a.rot.stride[1]];
-    const long long tx = (a.Ws + kBTX - 1) / kBTX, tile = blockIdx.x;
-    const long long sx = (tile % tx) * kBTX + threadIdx.x;
-    const long long sr0 = (tile / tx) * kBTH + threadIdx.y;
+    PAPOF_TILE_PIXEL(SampleTile, 0LL, a.Ws, long long, sx, long long, sr0);  // (one launch holds every strip: blocks <= kMaxTiles)
     double acc[kBSums];
 #pragma unroll
     for (int k = 0; k < kBSums; k++) acc[k] = 0.0;
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(64) void k_bundle_reduce(const BundleArgs a) {
 
 int launch_bundle(hipStream_t st, const BundleArgs& a, int n_links) {
     PAPOF_TRY(launch_tiles(a.blocks, n_links, [&](dim3 grid, long long, long long l0) {  // (blocks <= kMaxTiles)
-        hipLaunchKernelGGL(k_bundle_sums, grid, dim3(kBTX, kBTY), 0, st, a, l0);
+        hipLaunchKernelGGL(k_bundle_sums, grid, SampleTile::block(), 0, st, a, l0);
     }));
     hipLaunchKernelGGL(k_bundle_reduce, dim3((unsigned)n_links), dim3(64), 0, st, a);
     PAPOF_HIP(hipGetLastError());
@@ -176,8 +175,8 @@ extern "C" int papof_bundle_sums_tensor(papof_handle* h, int n_links, int height
                                         long long workspace_bytes, void* stream) {
     if (!h || n_links < 1 || height < 1 || width < 1 || step < 1) return PAPOF_EINVAL;
     if (!std::isfinite(scale) || !(scale > 0)) return PAPOF_EINVAL;
-    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow(flow)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
     if (!described(rotations, {PAPOF_DTYPE_F64}, {0, 1}, false) || !described(sums, {PAPOF_DTYPE_F64}, {0, 1}, true))
         return PAPOF_EINVAL;
     const long long need = papof_bundle_workspace(n_links, height, width, step);

@@ -12,6 +12,7 @@ namespace {
 
 constexpr int kCellW = 64;     // columns of a cell: one wave
 constexpr int kCellsX = 4;     // cells of a block
+using CellTile = Tile<kCellsX, 1, kCellW, kCellsX>;  // over the Gy x Gx plane of cells: a tile is kCellsX cells of one row
 constexpr int kMaxCellRows = 64;
 constexpr int kMaxQ = 65535;
 constexpr int kMaxC = 4;

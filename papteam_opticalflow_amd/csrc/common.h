@@ -326,6 +326,20 @@ inline bool described(const papof_tensor* t, std::initializer_list<int> dtypes, 
         if (t->stride[i] < 0 || (positive && t->stride[i] == 0)) return false;
     return true;
 }
+// The dtypes of a frame tensor and of a flow (or any other float) tensor, and the operand forms that the entry points of the
+// video calls share.  in_: strides >= 0 (an expanded tensor may be read); out_: strides > 0.  opt_: absent (null) is valid.
+constexpr std::initializer_list<int> kImageDtypes = {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64};
+constexpr std::initializer_list<int> kFlowDtypes = {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64};
+inline bool in_frames(const papof_tensor* t) { return described(t, kImageDtypes, {0, 1, 2, 3}, false); }
+inline bool out_frames(const papof_tensor* t) { return described(t, kImageDtypes, {0, 1, 2, 3}, true); }
+inline bool in_flow(const papof_tensor* t) { return described(t, kFlowDtypes, {0, 1, 2, 3}, false); }
+inline bool out_flow(const papof_tensor* t) { return described(t, kFlowDtypes, {0, 1, 2, 3}, true); }
+inline bool in_flow_pair(const papof_tensor* fw, const papof_tensor* bw) { return in_flow(fw) && in_flow(bw); }
+// a uint8 mask and a float plane per item (item, row, column)
+inline bool opt_in_mask(const papof_tensor* t) { return !t || described(t, {PAPOF_DTYPE_U8}, {0, 1, 2}, false); }
+inline bool opt_out_mask(const papof_tensor* t) { return !t || described(t, {PAPOF_DTYPE_U8}, {0, 1, 2}, true); }
+inline bool opt_in_plane(const papof_tensor* t) { return !t || described(t, kFlowDtypes, {0, 1, 2}, false); }
+inline bool opt_out_plane(const papof_tensor* t) { return !t || described(t, kFlowDtypes, {0, 1, 2}, true); }
 // the (alpha1, alpha2) of the forward-backward test: finite and >= 0
 inline bool valid_alphas(double a1, double a2) { return std::isfinite(a1) && std::isfinite(a2) && a1 >= 0 && a2 >= 0; }
 inline long long dtype_bytes(int dtype) { return dtype == PAPOF_DTYPE_U8 ? 1 : dtype == PAPOF_DTYPE_F32 ? 4 : 8; }

@@ -63,8 +63,7 @@ struct SetupArgs {
 // Frame 0: out[0] = store(first) if given, else store(P_0).
 __global__ __launch_bounds__(kTcBlock) void k_tc_first(const papof_tensor src, const papof_tensor out, int H, int W, int C) {
     __shared__ double lut[256];
-    fill_u8_lut(lut, threadIdx.x);
-    __syncthreads();
+    stage_u8_lut<-1>(lut);
     const long long i = (long long)blockIdx.x * kTcBlock + threadIdx.x;
     if (i >= (long long)H * W) return;
     const long long r = i / W, c = i % W;
@@ -78,8 +77,7 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_first(const papof_tensor src, c
 // r = O_{t-1}(X, Y) - P_t(x, r) into level 0 (w = a = r = 0 where the hop is not valid or w is not > 0).
 __global__ __launch_bounds__(kTcBlock) void k_tc_setup(const SetupArgs A, const Lv L0, double* wv, long long t) {
     __shared__ double lut[256];
-    fill_u8_lut(lut, threadIdx.x);
-    __syncthreads();
+    stage_u8_lut<-1>(lut);
     const long long i = (long long)blockIdx.x * kTcBlock + threadIdx.x;
     const int H = A.H, W = A.W;
     if (i >= (long long)H * W) return;
@@ -198,6 +196,7 @@ __global__ __launch_bounds__(kJX* kJW) void k_tc_jacobi(const JacobiArgs A, long
     const int lane = threadIdx.x, wave = threadIdx.y, tid = wave * kJX + lane;
     fill_u8_lut(lut, tid);
     const int g = A.g, cw = kJX - 2 * g, chh = kJY - 2 * g;
+    // (grid.h's decode with the core's run-time extent and the ghost ring taken off, kept as written: DESIGN.md section 41)
     const long long ntx = (A.W + cw - 1) / cw, tile = tile0 + blockIdx.x;
     const long long x0 = (tile % ntx) * cw - g, y0 = (tile / ntx) * chh - g;  // the region's origin
     const long long HW = (long long)A.H * A.W;
@@ -272,12 +271,9 @@ int launch_pixels(hipStream_t st, long long px, void (*kernel)(const Lv, const L
 
 int launch_jacobi(hipStream_t st, JacobiArgs a) {
     const long long cw = kJX - 2 * a.g, chh = kJY - 2 * a.g;
-    const long long tiles = ((a.W + cw - 1) / cw) * ((a.H + chh - 1) / chh);
-    for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-        hipLaunchKernelGGL(k_tc_jacobi, dim3((unsigned)std::min(kMaxTiles, tiles - t0)), dim3(kJX, kJW), 0, st, a, t0);
-        PAPOF_HIP(hipGetLastError());
-    }
-    return PAPOF_OK;
+    return launch_tiles(tile_count(a.H, a.W, cw, chh), 1, [&](dim3 grid, long long t0, long long) {
+        hipLaunchKernelGGL(k_tc_jacobi, grid, dim3(kJX, kJW), 0, st, a, t0);
+    });
 }
 
 int tc_depth() {
@@ -375,12 +371,10 @@ extern "C" int papof_temporal_consistency_tensor(papof_handle* h, int n_frames, 
     const long long need = papof_consistency_workspace(height, width, c_out);
     if (need < 0 || !workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 7) || workspace_bytes < need)
         return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(processed, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (first && !described(first, I, {1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !in_frames(processed)) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (first && !described(first, kImageDtypes, {1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!out_frames(out)) return PAPOF_EINVAL;
     const long long T = n_frames, H = height, W = width;
     const Span o = span(*out, {T, H, W, c_out});
     const Span ws{reinterpret_cast<std::uintptr_t>(workspace), reinterpret_cast<std::uintptr_t>(workspace) + (std::uintptr_t)need};

@@ -146,9 +146,9 @@ __device__ __forceinline__ void line_sum(const DeblurArgs& p, const double* img,
 
 // the pixel (x, r) of this lane; false: outside the frame
 __device__ __forceinline__ bool tile_pixel(const DeblurArgs& p, long long tile0, int& x, long long& r) {
-    const long long tx = (p.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    r = (tile / tx) * kInterpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(InterpTile, tile0, p.W, int, px, long long, pr);
+    x = px;
+    r = pr;
     return x < p.W && r < p.H;
 }
 
@@ -156,10 +156,7 @@ __device__ __forceinline__ bool tile_pixel(const DeblurArgs& p, long long tile0,
 template <int FD, int C>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_ingest(const DeblurArgs p, long long tile0, long long g0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kInterpTX>(lut);
     int x;
     long long r;
     if (!tile_pixel(p, tile0, x, r)) return;
@@ -174,10 +171,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_ingest(const De
 template <int FD, int C>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_ratio(const DeblurArgs p, long long tile0, long long i0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kInterpTX>(lut);
     const int slots = 2 * p.R + 1;
     const long long i = i0 + blockIdx.y, g = i / slots, t = p.t0 + g;
     const int j = (int)(i % slots);
@@ -256,22 +250,14 @@ long long per_target_bytes(long long n_frames, long long h, long long w, long lo
 
 template <int FD, int C>
 int run_deblur(hipStream_t st, DeblurArgs p, int iters, long long G) {
-    const long long tiles = ((p.W + kInterpTX - 1) / (long long)kInterpTX) * ((p.H + kInterpTY - 1) / (long long)kInterpTY);
-    const dim3 block(kInterpTX, kInterpTY);
     for (long long t0 = 0; t0 < p.T; t0 += G) {
         const long long n = std::min<long long>(p.T - t0, G);
         p.t0 = t0;
-        PAPOF_TRY(launch_tiles(tiles, n, [&](dim3 grid, long long tile0, long long g0) {
-            hipLaunchKernelGGL((k_deblur_ingest<FD, C>), grid, block, 0, st, p, tile0, g0);
-        }));
+        PAPOF_TRY(launch_grid<InterpTile>(p.H, p.W, n, st, 0, k_deblur_ingest<FD, C>, p));
         for (int it = 0; it < iters; it++) {
             p.last = it == iters - 1;
-            PAPOF_TRY(launch_tiles(tiles, n * (2 * p.R + 1), [&](dim3 grid, long long tile0, long long i0) {
-                hipLaunchKernelGGL((k_deblur_ratio<FD, C>), grid, block, 0, st, p, tile0, i0);
-            }));
-            PAPOF_TRY(launch_tiles(tiles, n, [&](dim3 grid, long long tile0, long long g0) {
-                hipLaunchKernelGGL((k_deblur_update<C>), grid, block, 0, st, p, tile0, g0);
-            }));
+            PAPOF_TRY(launch_grid<InterpTile>(p.H, p.W, n * (2 * p.R + 1), st, 0, k_deblur_ratio<FD, C>, p));
+            PAPOF_TRY(launch_grid<InterpTile>(p.H, p.W, n, st, 0, k_deblur_update<C>, p));
         }
     }
     return PAPOF_OK;
@@ -305,11 +291,9 @@ extern "C" int papof_deblur_tensor(papof_handle* h, int n_frames, int height, in
     if (!h) return PAPOF_EINVAL;
     const long long per = per_target_bytes(n_frames, height, width, c, radius);
     if (per < 0 || iters < 1 || iters > kMaxIters || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (support && !described(support, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (!opt_out_mask(support)) return PAPOF_EINVAL;
     if (n_samples < 1 || n_samples > kMaxSamples || !offsets || !weights) return PAPOF_EINVAL;
     const double lo = std::ldexp(1.0, -20), hi = 1.0 - lo;
     DeblurArgs p{};

@@ -33,6 +33,7 @@ namespace papof {
 namespace {
 
 constexpr int kDeintTX = 64, kDeintTY = 4;  // a 64 x 4 tile of made pixels per block (256 lanes: lut)
+using DeintTile = Tile<kDeintTX, kDeintTY>;
 constexpr int kMaxC = 4;                    // channels (registers per lane)
 
 struct DeintArgs {
@@ -48,17 +49,12 @@ struct DeintArgs {
 // the phase confidence of a landing row Y of the image: 1 on a field line, 0 halfway between two
 __device__ __forceinline__ double phase_confidence(double Y) { return 1.0 - 2.0 * fabs(Y - rint(Y)); }
 
-// blockIdx.x: tile `tile0` + x of the field's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the field's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD, int MODE>
 __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kDeintTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kDeintTX - 1) / kDeintTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kDeintTX + (int)threadIdx.x;
-    const long long j = (tile / tx) * kDeintTY + threadIdx.y;
+    stage_u8_lut<FD, kDeintTX>(lut);
+    PAPOF_TILE_PIXEL(DeintTile, tile0, a.W, int, x, long long, j);
     if (x >= a.W || j >= a.Hf) return;
     const long long t = frame0 + blockIdx.y;
     const int Hf = a.Hf, W = a.W;
@@ -155,13 +151,8 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
 
 template <int MODE>
 int launch_deinterlace(hipStream_t st, const DeintArgs& a) {
-    const auto kernel = a.fl.dtype == PAPOF_DTYPE_U8    ? k_deinterlace<PAPOF_DTYPE_U8, MODE>
-                        : a.fl.dtype == PAPOF_DTYPE_F32 ? k_deinterlace<PAPOF_DTYPE_F32, MODE>
-                                                        : k_deinterlace<PAPOF_DTYPE_F64, MODE>;
-    const long long tiles = ((a.W + kDeintTX - 1) / (long long)kDeintTX) * ((a.Hf + kDeintTY - 1) / (long long)kDeintTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kDeintTX, kDeintTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(a.fl.dtype, [](auto fd) { return k_deinterlace<fd(), MODE>; });
+    return launch_grid<DeintTile>(a.Hf, a.W, a.T, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -178,13 +169,10 @@ extern "C" int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field
         return PAPOF_EINVAL;
     if ((first != 0 && first != 1) || (mode != 0 && mode != 1)) return PAPOF_EINVAL;
     if (!std::isfinite(sigma) || !(sigma > 0)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(fields, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (mode && (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)))
-        return PAPOF_EINVAL;
-    if (!described(video, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (confidence && !described(confidence, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!in_frames(fields)) return PAPOF_EINVAL;
+    if (mode && !in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (!out_frames(video)) return PAPOF_EINVAL;
+    if (!opt_out_plane(confidence)) return PAPOF_EINVAL;
     if (video->data == fields->data) return PAPOF_EINVAL;
     DeintArgs a{};
     a.fl = *fields;

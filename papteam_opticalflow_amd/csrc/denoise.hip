@@ -25,6 +25,7 @@ namespace papof {
 namespace {
 
 constexpr int kFilterTX = 64, kFilterTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+using FilterTile = Tile<kFilterTX, kFilterTY>;
 constexpr int kMaxC = 4;                       // channels (registers per lane: centre values, sums, samples)
 constexpr int kMaxRadius = 16;
 
@@ -75,18 +76,13 @@ __device__ __forceinline__ void chain(const FilterArgs& a, const papof_tensor& f
     }
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(kFilterTX* kFilterTY) void k_temporal_filter(const FilterArgs a, long long tile0,
                                                                           long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kFilterTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kFilterTX - 1) / kFilterTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kFilterTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kFilterTY + threadIdx.y;
+    stage_u8_lut<FD, kFilterTX>(lut);
+    PAPOF_TILE_PIXEL(FilterTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long t = frame0 + blockIdx.y;
     const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
@@ -109,14 +105,8 @@ __global__ __launch_bounds__(kFilterTX* kFilterTY) void k_temporal_filter(const 
 }
 
 int launch_filter(hipStream_t st, const FilterArgs& a) {
-    const auto kernel = a.fr.dtype == PAPOF_DTYPE_U8    ? k_temporal_filter<PAPOF_DTYPE_U8>
-                        : a.fr.dtype == PAPOF_DTYPE_F32 ? k_temporal_filter<PAPOF_DTYPE_F32>
-                                                        : k_temporal_filter<PAPOF_DTYPE_F64>;
-    const long long tiles =
-        ((a.W + kFilterTX - 1) / (long long)kFilterTX) * ((a.H + kFilterTY - 1) / (long long)kFilterTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kFilterTX, kFilterTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(a.fr.dtype, [](auto fd) { return k_temporal_filter<fd()>; });
+    return launch_grid<FilterTile>(a.H, a.W, a.T, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -133,12 +123,10 @@ extern "C" int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int h
     if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
     if (radius < 1 || radius > kMaxRadius || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (support && !described(support, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames)) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (!out_frames(out)) return PAPOF_EINVAL;
+    if (!opt_out_mask(support)) return PAPOF_EINVAL;
     FilterArgs a{};
     a.fr = *frames;
     a.fw = *flow_fw;

@@ -30,6 +30,7 @@ namespace {
 
 constexpr int kFillBlock = 256;                // lanes per block of the fill kernels (256: the uint8 table)
 constexpr int kPropTX = 64, kPropTY = 4;       // a 64 x 4 tile of output pixels per block of k_propagate
+using PropTile = Tile<kPropTX, kPropTY>;
 constexpr int kMaxC = 4;
 constexpr int kMaxRelax = 1 << 16;
 
@@ -57,10 +58,7 @@ template <int FD>
 __global__ __launch_bounds__(kFillBlock) void k_fill_base(const papof_tensor x, const papof_tensor mask, const Level L,
                                                           int C, long long f0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.x);
-        __syncthreads();
-    }
+    stage_u8_lut<FD>(lut);
     const long long i = (long long)blockIdx.x * kFillBlock + threadIdx.x;
     if (i >= L.h * L.w) return;
     const long long t = f0 + blockIdx.y, r = i / L.w, c = i % L.w, p = t * L.h * L.w + i;
@@ -176,9 +174,7 @@ int launch_fill(hipStream_t st, const papof_tensor& x, const papof_tensor& mask,
         L.push_back(l);
         ws += level_bytes(n, s.first, s.second, C);
     }
-    const auto base = x.dtype == PAPOF_DTYPE_U8    ? k_fill_base<PAPOF_DTYPE_U8>
-                      : x.dtype == PAPOF_DTYPE_F32 ? k_fill_base<PAPOF_DTYPE_F32>
-                                                   : k_fill_base<PAPOF_DTYPE_F64>;
+    const auto base = by_dtype(x.dtype, [](auto fd) { return k_fill_base<fd()>; });
     PAPOF_TRY(launch_level(st, base, n, H, W, x, mask, L[0], C));
     const int top = (int)L.size() - 1;
     for (int l = 0; l < top; l++) PAPOF_TRY(launch_level(st, k_fill_pull, n, L[l + 1].h, L[l + 1].w, L[l], L[l + 1], C));
@@ -238,17 +234,12 @@ __device__ __forceinline__ int candidate(const PropArgs& a, const papof_tensor& 
     return 0;
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(kPropTX* kPropTY) void k_propagate(const PropArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kPropTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kPropTX - 1) / kPropTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kPropTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kPropTY + threadIdx.y;
+    stage_u8_lut<FD, kPropTX>(lut);
+    PAPOF_TILE_PIXEL(PropTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long t = frame0 + blockIdx.y;
     const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
@@ -282,13 +273,8 @@ __global__ __launch_bounds__(kPropTX* kPropTY) void k_propagate(const PropArgs a
 }
 
 int launch_propagate(hipStream_t st, const PropArgs& a) {
-    const auto kernel = a.fr.dtype == PAPOF_DTYPE_U8    ? k_propagate<PAPOF_DTYPE_U8>
-                        : a.fr.dtype == PAPOF_DTYPE_F32 ? k_propagate<PAPOF_DTYPE_F32>
-                                                        : k_propagate<PAPOF_DTYPE_F64>;
-    const long long tiles = ((a.W + kPropTX - 1) / (long long)kPropTX) * ((a.H + kPropTY - 1) / (long long)kPropTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kPropTX, kPropTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(a.fr.dtype, [](auto fd) { return k_propagate<fd()>; });
+    return launch_grid<PropTile>(a.H, a.W, a.T, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -316,8 +302,7 @@ extern "C" int papof_fill_holes_tensor(papof_handle* h, int n_frames, int height
     const long long need = papof_fill_workspace(n_frames, height, width, c);
     if (need < 0 || !workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 7) || workspace_bytes < need)
         return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(x, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(x) || !out_frames(out)) return PAPOF_EINVAL;
     if (!described(mask, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
     PAPOF_HIP(hipSetDevice(h->device));
     return launch_fill(static_cast<hipStream_t>(stream), *x, *mask, *out, n_frames, height, width, c, relax,
@@ -330,12 +315,10 @@ extern "C" int papof_propagate_tensor(papof_handle* h, int n_frames, int height,
                                       const papof_tensor* out, const papof_tensor* status, void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
     if (radius < 1 || radius > n_frames - 1 || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false))
+    if (!in_frames(frames) || !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false))
         return PAPOF_EINVAL;
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(out, I, {0, 1, 2, 3}, true) || !described(status, {PAPOF_DTYPE_U8}, {0, 1, 2}, true))
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (!out_frames(out) || !described(status, {PAPOF_DTYPE_U8}, {0, 1, 2}, true))
         return PAPOF_EINVAL;
     PropArgs a{};
     a.fr = *frames;

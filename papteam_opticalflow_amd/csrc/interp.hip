@@ -12,7 +12,7 @@
 // taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  The sampler and the pixel's rule
 // (interp_pixel, which k_interp_splat of splat.hip applies where no splat lands) are sampler.h's.
 //
-// Mapping.  A block is a 64 x 4 tile of output pixels (as k_fb_check's): blockIdx.x the tile, blockIdx.y the pair.  A wave is
+// Mapping.  A block is a 64 x 4 tile of output pixels (InterpTile; the grid of tiles and pairs is grid.h's).  A wave is
 // 64 neighbouring pixels of one row, whose taps share cache lines while the flow is smooth and whose stores are contiguous
 // along a row.  The times are kernel arguments (at most kMaxTimes per launch; more are launched in groups): they are the
 // same for every lane, so they sit in scalar registers with no load, and the call needs no device buffer and no copy to
@@ -26,35 +26,24 @@ namespace papof {
 
 namespace {
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: pair `pair0` + y.  Times
-// a.t[0 .. a.nt) are written at time slots j0 + j of out.
+// Times a.t[0 .. a.nt) are written at time slots j0 + j of out.
 template <int FD>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp(const InterpArgs a, long long tile0, long long pair0,
                                                                  long long j0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    stage_u8_lut<FD, kInterpTX>(lut);
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     interp_pixel<FD>(a, lut, pair0 + blockIdx.y, r, x, j0, [](int, long long) { return false; });
 }
 
 int launch_interp(hipStream_t st, InterpArgs a, int n_pairs, int n_times, const double* times) {
-    const int fd = a.f0.dtype == a.f1.dtype ? a.f0.dtype : -1;
-    const auto kernel = fd == PAPOF_DTYPE_U8    ? k_interp<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_interp<PAPOF_DTYPE_F32>
-                        : fd == PAPOF_DTYPE_F64 ? k_interp<PAPOF_DTYPE_F64>
-                                                : k_interp<-1>;
-    const long long tiles = ((a.W + kInterpTX - 1) / (long long)kInterpTX) * ((a.H + kInterpTY - 1) / (long long)kInterpTY);
+    const auto kernel = by_frame_dtype(a.f0.dtype == a.f1.dtype ? a.f0.dtype : -1, [](auto fd) { return k_interp<fd()>; });
     for (int j0 = 0; j0 < n_times; j0 += kMaxTimes) {
         a.nt = std::min(kMaxTimes, n_times - j0);
         std::copy(times + j0, times + j0 + a.nt, a.t);
-        PAPOF_TRY(launch_tiles(tiles, n_pairs, [&](dim3 grid, long long t0, long long p0) {
-            hipLaunchKernelGGL(kernel, grid, dim3(kInterpTX, kInterpTY), 0, st, a, t0, p0, (long long)j0);
+        PAPOF_TRY(launch_tiles(InterpTile::count(a.H, a.W), n_pairs, [&](dim3 grid, long long t0, long long p0) {
+            hipLaunchKernelGGL(kernel, grid, InterpTile::block(), 0, st, a, t0, p0, (long long)j0);
         }));
     }
     return PAPOF_OK;
@@ -71,14 +60,10 @@ extern "C" int papof_interp_tensor(papof_handle* h, int n_pairs, int sequence, c
                                    const papof_tensor* flow_bw, const papof_tensor* occlusion, int n_times,
                                    const double* times, const papof_tensor* out, long long time_stride, void* stream) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto all = {0, 1, 2, 3};
-    if (!described(frames, I, all, false) || (sequence ? frames2 != nullptr : !described(frames2, I, all, false)))
-        return PAPOF_EINVAL;
-    if (!described(flow_fw, F, all, false) || !described(flow_bw, F, all, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, all, false)) return PAPOF_EINVAL;
-    if (!described(out, I, all, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || (sequence ? frames2 != nullptr : !in_frames(frames2))) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!out_frames(out) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
     if (n_times < 1 || !times) return PAPOF_EINVAL;
     for (int j = 0; j < n_times; j++)
         if (!std::isfinite(times[j]) || !(times[j] > 0.0 && times[j] < 1.0)) return PAPOF_EINVAL;

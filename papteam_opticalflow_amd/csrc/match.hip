@@ -8,7 +8,7 @@
 // Mapping.  k_match_prepare: one lane per coarse pixel of a frame; it reads the stride^2 x C samples through the descriptor,
 // quantises, box-decimates and stores the pixel as ONE packed dword (channel c in byte c, missing channels 0), so that one
 // v_sad_u8 is the absolute difference of a pixel pair over all its channels.
-// k_match: a block is a 32 x 8 tile of coarse pixels (blockIdx.x the tile, blockIdx.y the item), one lane per pixel.  A's
+// k_match: a block is a 32 x 8 tile of coarse pixels (grid.h's grid of tiles and items), one lane per pixel.  A's
 // tile with a halo of `patch` and B's tile with a halo of `patch + search` are staged once in LDS, coordinates clamped as
 // the rule clamps them; a lane outside the grid computes on clamped data and stores nothing.  A lane evaluates kG = 4
 // horizontally neighbouring candidates at a time: per window row it reads the row of A (2 P + 1 dwords) and the row of B
@@ -55,6 +55,7 @@ namespace papof {
 namespace {
 
 constexpr int kTX = 32, kTY = 8;  // the tile of coarse pixels (256 lanes)
+using GridTile = Tile<kTX, kTY>;
 constexpr int kG = 4;             // candidates along dx that a lane evaluates together (1, 8, 16)
 constexpr int kMaxPatch = 7, kMaxSearch = 32, kMaxPenalty = 65535;
 
@@ -154,7 +155,7 @@ struct MatchArgs {
     unsigned* out;           // k_match<P, true>: [item][h][w] packed displacements in cells, instead of disp and cost
 };
 
-// P: the patch radius.  blockIdx.x: tile `tile0` + x of the grid's 32 x 8 tiles in row-major order; blockIdx.y: item
+// P: the patch radius.  grid.h's grid over the grid's 32 x 8 tiles; blockIdx.y: item
 // `item0` + y -- items below n_pairs run forward (A the pair's first frame), the others backward.
 // PACKED: the top level of the hierarchical search -- the match goes to a.out as one packed dword.
 template <int P, bool PACKED = false>
@@ -167,8 +168,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_match(const MatchArgs a, long long
     unsigned* const Bs = As + AW * AH;
 
     const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
-    const long long tx = (w + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    PAPOF_TILE_ORIGIN(GridTile, tile0, w, int, x0, int, y0);
     const int x = x0 + lx, y = y0 + ly;
     const long long item = item0 + blockIdx.y, cells = (long long)h * w;
     const bool back = item >= a.n_pairs;
@@ -281,10 +281,7 @@ bool valid_frame_size(int height, int width, int stride) {
 template <int P, bool PACKED = false>
 int launch_match(hipStream_t st, const MatchArgs& a, long long items) {
     const size_t lds = (size_t)lds_bytes(P, a.search);
-    const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
-    return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL((k_match<P, PACKED>), grid, dim3(kTX, kTY), lds, st, a, t0, i0);
-    });
+    return launch_grid<GridTile>(a.h, a.w, items, st, lds, k_match<P, PACKED>, a);
 }
 
 // the top level of the hierarchical search
@@ -381,8 +378,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_refine(const RefineArgs a, l
     unsigned* const Ws = Zs + ZW * ZH;
 
     const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
-    const long long tx = (w + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    PAPOF_TILE_ORIGIN(GridTile, tile0, w, int, x0, int, y0);
     const int x = x0 + lx, y = y0 + ly;
     const long long item = item0 + blockIdx.y, cells = (long long)h * w, cells1 = (long long)h1 * w1;
     const bool back = item >= a.n_pairs;
@@ -475,10 +471,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_refine(const RefineArgs a, l
 template <int P>
 int launch_refine(hipStream_t st, const RefineArgs& a, long long items) {
     const size_t lds = (size_t)refine_lds_bytes(P, a.refine);
-    const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
-    return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(k_match_refine<P>, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
-    });
+    return launch_grid<GridTile>(a.h, a.w, items, st, lds, k_match_refine<P>, a);
 }
 
 // k_match_prepare of both frame tensors at one stride, into `packed` ([frame][h][w], the first tensor's frames first)
@@ -528,8 +521,8 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_origin(const OriginArgs a, l
     __shared__ unsigned vec[kTX * kTY];
     __shared__ int med[2];
     const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
-    const long long tx = (a.w + kTX - 1) / kTX, ty = (a.h + kTY - 1) / kTY, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const long long ty = (a.h + kTY - 1) / kTY;
+    PAPOF_TILE_ORIGIN(GridTile, tile0, a.w, int, x0, int, y0);
     const int tw = min(kTX, a.w - x0), th = min(kTY, a.h - y0), n = tw * th;  // the tile clipped to the grid
     const long long item = item0 + blockIdx.y;
     const bool in = lx < tw && ly < th;
@@ -589,8 +582,8 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_recentre(const RecentreArgs 
     unsigned* const Bs = As + AW * AH;
 
     const int lx = (int)threadIdx.x, ly = (int)threadIdx.y, tid = ly * kTX + lx;
-    const long long tx = (w + kTX - 1) / kTX, ty = (h + kTY - 1) / kTY, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    const long long ty = (h + kTY - 1) / kTY;
+    PAPOF_TILE_ORIGIN(GridTile, tile0, w, int, x0, int, y0);
     const int x = x0 + lx, y = y0 + ly;
     const long long item = item0 + blockIdx.y, cells = (long long)h * w;
     const bool back = item >= a.n_pairs;
@@ -674,10 +667,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_recentre(const RecentreArgs 
 template <int P>
 int launch_recentre(hipStream_t st, const RecentreArgs& a, long long items) {
     const size_t lds = (size_t)lds_bytes(P, a.window);
-    const long long tiles = ((a.w + kTX - 1) / (long long)kTX) * ((a.h + kTY - 1) / (long long)kTY);
-    return launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(k_match_recentre<P>, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
-    });
+    return launch_grid<GridTile>(a.h, a.w, items, st, lds, k_match_recentre<P>, a);
 }
 
 bool valid_hier(int height, int width, int stride, int levels) {
@@ -709,11 +699,9 @@ extern "C" int papof_match_tensor(papof_handle* h, int n_pairs, int sequence, co
     if (need < 0 || c < 1 || c > 4 || patch < 1 || patch > kMaxPatch || search < 1 || search > kMaxSearch || penalty < 0 ||
         penalty > kMaxPenalty)
         return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || (!sequence && !described(frames2, I, {0, 1, 2, 3}, false)))
+    if (!in_frames(frames) || (!sequence && !in_frames(frames2)))
         return PAPOF_EINVAL;
-    if (!described(disp, F, {0, 1, 2, 3}, true) || !described(cost, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!out_flow(disp) || !described(cost, kFlowDtypes, {0, 1, 2}, true)) return PAPOF_EINVAL;
     if (!workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 3) || workspace_bytes < need) return PAPOF_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PAPOF_HIP(hipSetDevice(h->device));
@@ -784,11 +772,9 @@ static int match_hier(papof_handle* h, int n_pairs, int sequence, const papof_te
                                   cost, workspace, workspace_bytes, stream);
     if (c < 1 || c > 4 || patch < 1 || patch > kMaxPatch || search < 1 || search > kMaxSearch || penalty < 0 || penalty > kMaxPenalty)
         return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || (!sequence && !described(frames2, I, {0, 1, 2, 3}, false)))
+    if (!in_frames(frames) || (!sequence && !in_frames(frames2)))
         return PAPOF_EINVAL;
-    if (!described(disp, F, {0, 1, 2, 3}, true) || !described(cost, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!out_flow(disp) || !described(cost, kFlowDtypes, {0, 1, 2}, true)) return PAPOF_EINVAL;
     if (!workspace || (reinterpret_cast<std::uintptr_t>(workspace) & 3) || workspace_bytes < need) return PAPOF_EINVAL;
     const char* const env = std::getenv("PAPOF_MATCH_STAGED");
     const int staged = !(env && std::strcmp(env, "0") == 0);
@@ -869,7 +855,7 @@ extern "C" long long papof_match_recentre_workspace(int n_pairs, int sequence, i
     const long long hier = papof_match_hier_workspace(n_pairs, sequence, height, width, stride, levels);
     if (hier < 0 || levels < 2) return -1;
     const long long ch = height / stride, cw = width / stride;
-    const long long per = ch * cw + ((ch + kTY - 1) / kTY) * ((cw + kTX - 1) / kTX);  // d_h and the origins of one item
+    const long long per = ch * cw + GridTile::count(ch, cw);  // d_h and the origins of one item
     if (2LL * n_pairs > ((1LL << 60) - hier / 4) / per) return -1;
     return hier + 4 * 2LL * n_pairs * per;
 }
@@ -892,15 +878,12 @@ extern "C" int papof_match_recentre_tensor(papof_handle* h, int n_pairs, int seq
                          disp, cost, workspace, workspace_bytes, stream, dh));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long items = both ? 2LL * n_pairs : n_pairs;
-    const long long tiles = ((cw + kTX - 1) / (long long)kTX) * ((ch + kTY - 1) / (long long)kTY);
     OriginArgs o{};
     o.dh = dh;
     o.origin = origin;
     o.h = ch;
     o.w = cw;
-    PAPOF_TRY(launch_tiles(tiles, items, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(k_match_origin, grid, dim3(kTX, kTY), 0, st, o, t0, i0);
-    }));
+    PAPOF_TRY(launch_grid<GridTile>(ch, cw, items, st, 0, k_match_origin, o));
     RecentreArgs a{};
     a.packed = static_cast<const unsigned*>(workspace);  // level 0's frames come first
     a.dh = dh;
@@ -931,9 +914,8 @@ extern "C" int papof_match_densify_tensor(papof_handle* h, int n, int height, in
     if (!h || n < 1 || height < 1 || width < 1 || !valid_frame_size(height, width, stride) || tol < 0 || tol > 2 * kMaxSearch ||
         std::isnan(max_cost))
         return PAPOF_EINVAL;
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(disp, F, {0, 1, 2, 3}, false) || !described(disp_rev, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (max_cost >= 0 && !described(cost, F, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow_pair(disp, disp_rev)) return PAPOF_EINVAL;
+    if (max_cost >= 0 && !described(cost, kFlowDtypes, {0, 1, 2}, false)) return PAPOF_EINVAL;
     if (!described(flow, {PAPOF_DTYPE_F64}, {0, 1, 2, 3}, true) || !described(mask, {PAPOF_DTYPE_U8}, {0, 1, 2}, true))
         return PAPOF_EINVAL;
     DensifyArgs a{};

@@ -34,6 +34,7 @@ constexpr int kMeshRounds = 4;                       // samples per lane
 constexpr int kMeshSamples = kMeshLanes * kMeshRounds;  // include/papof.h: at most 1024 samples per window
 constexpr int kMeshStaged = 33 * 33;                 // vertices of a table that k_warp_mesh stages in LDS
 constexpr int kWarpTX = 64, kWarpTY = 4;             // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+using WarpTile = Tile<kWarpTX, kWarpTY>;
 constexpr long long kKeyNone = 0x7fffffffffffffffLL; // the key of a sample that does not count (a NaN's: NaNs do not count)
 
 // the bits of a double as a signed integer that orders as the double does (-0 before +0), and back
@@ -229,7 +230,7 @@ struct WarpMeshArgs {
     int H, W, C, GH, GW;
 };
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.  STAGED: the
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.  STAGED: the
 // frame's table is copied to LDS, (vertex row, vertex column, {dx, dy}) dense
 template <int FD, bool STAGED>
 __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_mesh(const WarpMeshArgs a, long long tile0, long long frame0) {
@@ -252,9 +253,7 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_mesh(const WarpMeshAr
     for (int r = 0; r < 2; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[1] + c * a.mat.stride[2]);
-    const long long tx = (a.W + kWarpTX - 1) / kWarpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kWarpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kWarpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(WarpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const double xd = (double)x, rd = (double)r;
     const double X0 = (m[0] * xd + m[1] * rd) + m[2], Y0 = (m[3] * xd + m[4] * rd) + m[5];
@@ -300,13 +299,8 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_mesh(const WarpMeshAr
 template <bool STAGED>
 int launch_warp_mesh(hipStream_t st, const WarpMeshArgs& a, int n_frames) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_warp_mesh<PAPOF_DTYPE_U8, STAGED>
-                        : fd == PAPOF_DTYPE_F32 ? k_warp_mesh<PAPOF_DTYPE_F32, STAGED>
-                                                : k_warp_mesh<PAPOF_DTYPE_F64, STAGED>;
-    const long long tiles = ((a.W + kWarpTX - 1) / (long long)kWarpTX) * ((a.H + kWarpTY - 1) / (long long)kWarpTY);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_warp_mesh<fd(), STAGED>; });
+    return launch_grid<WarpTile>(a.H, a.W, n_frames, st, 0, kernel, a);
 }
 
 bool valid_grid(int height, int width, int gh, int gw) {
@@ -332,8 +326,8 @@ extern "C" int papof_mesh_motion_tensor(papof_handle* h, int n_pairs, int height
                                         long long workspace_bytes, void* stream) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || min_support < 1) return PAPOF_EINVAL;
     if (!valid_grid(height, width, grid_rows, grid_cols)) return PAPOF_EINVAL;
-    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow(flow)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
     if (motion && !described(motion, {PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
     if (!described(vertices, {PAPOF_DTYPE_F64}, {0, 1, 2, 3}, true) || !described(residuals, {PAPOF_DTYPE_F64}, {0, 1, 2, 3}, true) ||
         !support)
@@ -371,11 +365,10 @@ extern "C" int papof_warp_mesh_tensor(papof_handle* h, int n_frames, int height,
                                       const papof_tensor* out, const papof_tensor* valid, void* stream) {
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
     if (!valid_grid(height, width, grid_rows, grid_cols)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
     if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
     if (!described(mesh, {PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!opt_out_mask(valid)) return PAPOF_EINVAL;
     WarpMeshArgs a{};
     a.fr = *frames;
     a.mat = *matrices;

@@ -8,7 +8,7 @@
 // Semantics: include/papof.h, papof_mosaic_tensor.  fp64 without contraction (-ffp-contract=off); the bilinear rule is
 // sampler.h's, unchanged.
 //
-// k_mosaic.  A block is a 64 x TY tile of output pixels of one output (blockIdx.x the tile, blockIdx.y the output), a lane
+// k_mosaic.  A block is a 64 x TY tile of output pixels of one output (grid.h's grid of tiles and outputs), a lane
 // one pixel.
 //   1. Culling: lane k of the block maps the tile's four corners through matrix (o, k).  Every step of
 //      X = (m00 x + m01 r) + m02 is monotone in x and in r under rounding, so over the tile X and Y take their extremes at
@@ -134,6 +134,8 @@ namespace papof {
 namespace {
 
 constexpr int kMosTX = 64;     // tile width: one wave per tile row
+template <int TY>
+using MosTile = Tile<kMosTX, TY>;
 constexpr int kMaxSrc = 256;   // the list's capacity (n_src <= PAPOF_MOSAIC_MAX_SOURCES = 255)
 
 struct MosaicArgs {
@@ -565,9 +567,7 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
     if (FD == PAPOF_DTYPE_U8)
         for (int j = tid; j < 256; j += NT) fill_u8_lut(lut, j);
     const long long o = out0 + blockIdx.y;
-    const long long tx = (a.Wc + kMosTX - 1) / kMosTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kMosTX;
-    const long long r0 = (tile / tx) * TY;
+    PAPOF_TILE_ORIGIN(MosTile<TY>, tile0, a.Wc, int, x0, long long, r0);
     const int* src = a.src + o * a.n_src;
     const long long mo = o * a.mat.stride[0];
     const double W1 = (double)(a.W - 1), H1 = (double)(a.H - 1);
@@ -658,13 +658,8 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
 template <int MODE, int CAP, int TY, typename A>
 int launch_mosaic_as(hipStream_t st, const A& a, int n_out) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic<PAPOF_DTYPE_U8, MODE, CAP, TY, A>
-                        : fd == PAPOF_DTYPE_F32 ? k_mosaic<PAPOF_DTYPE_F32, MODE, CAP, TY, A>
-                                                : k_mosaic<PAPOF_DTYPE_F64, MODE, CAP, TY, A>;
-    const long long tiles = ((a.Wc + kMosTX - 1) / (long long)kMosTX) * ((a.Hc + TY - 1) / (long long)TY);
-    return launch_tiles(tiles, n_out, [&](dim3 grid, long long t0, long long o0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kMosTX, TY), 0, st, a, t0, o0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_mosaic<fd(), MODE, CAP, TY, A>; });
+    return launch_grid<MosTile<TY>>(a.Hc, a.Wc, n_out, st, 0, kernel, a);
 }
 
 template <typename A>
@@ -684,6 +679,7 @@ int launch_mosaic(hipStream_t st, const A& a, int n_out, int mode) {
 
 // ---- papof_mosaic_overlap_tensor
 constexpr int kOvTY = 2;                   // a 64 x 2 tile of sampled pixels: two waves, and a column's sum fits 32 bits
+using OvTile = Tile<kMosTX, kOvTY>;
 constexpr int kOvNT = kMosTX * kOvTY;
 constexpr double kOvOne = 16777216.0;      // q = rint(t * 2^24)
 
@@ -717,9 +713,7 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
         tcnt[j] = 0;
     }
     const long long o = out0 + blockIdx.y;
-    const long long tx = (args.nsx + kMosTX - 1) / kMosTX, tile = tile0 + blockIdx.x;
-    const int sx0 = (int)(tile % tx) * kMosTX;
-    const long long sr0 = (tile / tx) * kOvTY;
+    PAPOF_TILE_ORIGIN(OvTile, tile0, args.nsx, int, sx0, long long, sr0);
     const int* src = a.src + o * a.n_src;
     const long long mo = o * a.mat.stride[0];
     const long long step = args.step;
@@ -819,13 +813,8 @@ __global__ __launch_bounds__(kOvNT) void k_mosaic_overlap(const OverlapArgsOf<A>
 template <int NS, typename A>
 int launch_overlap_as(hipStream_t st, const OverlapArgsOf<A>& a, int n_out) {
     const int fd = a.m.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_mosaic_overlap<PAPOF_DTYPE_U8, NS, A>
-                        : fd == PAPOF_DTYPE_F32 ? k_mosaic_overlap<PAPOF_DTYPE_F32, NS, A>
-                                                : k_mosaic_overlap<PAPOF_DTYPE_F64, NS, A>;
-    const long long tiles = ((a.nsx + kMosTX - 1) / (long long)kMosTX) * ((a.nsr + kOvTY - 1) / (long long)kOvTY);
-    return launch_tiles(tiles, n_out, [&](dim3 grid, long long t0, long long o0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kMosTX, kOvTY), 0, st, a, t0, o0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_mosaic_overlap<fd(), NS, A>; });
+    return launch_grid<OvTile>(a.nsr, a.nsx, n_out, st, 0, kernel, a);
 }
 
 // The arguments the three calls share, checked and gathered; out and count are the caller's to check and set
@@ -834,9 +823,9 @@ bool mosaic_args_from(MosaicArgs& a, const papof_handle* h, int n_frames, int he
                       const papof_tensor* matrices) {
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1 || n_out < 1 || out_height < 1 || out_width < 1) return false;
     if (n_src < 1 || n_src > PAPOF_MOSAIC_MAX_SOURCES || !sources) return false;
-    if (!described(frames, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return false;
-    if (masks && !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return false;
-    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return false;
+    if (!in_frames(frames)) return false;
+    if (!opt_in_mask(masks)) return false;
+    if (!in_flow(matrices)) return false;
     a.fr = *frames;
     if (masks) a.mask = *masks;
     a.mat = *matrices;
@@ -853,8 +842,8 @@ bool mosaic_args_from(MosaicArgs& a, const papof_handle* h, int n_frames, int he
 }
 
 bool mosaic_outputs(MosaicArgs& a, const papof_tensor* out, const papof_tensor* count) {
-    if (!described(out, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, true)) return false;
-    if (count && !described(count, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return false;
+    if (!out_frames(out)) return false;
+    if (!opt_out_mask(count)) return false;
     a.out = *out;
     if (count) a.count = *count;
     return true;

@@ -10,7 +10,7 @@
 // (-ffp-contract=off).
 //
 // Reduction.  Bitwise reproducible from run to run and on every device, so there are no atomics.  Launch 1 (k_motion_sums):
-// a block is a 64 x 32 tile of pixels of one pair (blockIdx.x the tile, blockIdx.y the pair), a lane one column and 8 rows
+// a block is a 64 x 32 tile of pixels of one pair (grid.h's grid of tiles and pairs), a lane one column and 8 rows
 // (threadIdx.y + 4 k) in increasing row order; the lanes of a wave are summed by a fixed shuffle tree (__shfl_down, 32 .. 1),
 // the four waves in wave order through LDS, and the block writes one row of fourteen doubles to the workspace.  The number
 // of blocks of a pair is a function of (H, W) alone.  Launch 2 (k_motion_solve): one wave per pair; lane l adds the rows
@@ -23,7 +23,7 @@
 // sum of the Cauchy weights are the other two) in the order above into rows of 32 doubles, k_homography_solve adds them and
 // eliminates the 8 x 9 system in lane 0, in registers; k_warp_projective is k_warp_affine with (X, Y) = (Nx / D, Ny / D).
 //
-// Warp.  k_warp_affine: a block is a 64 x 4 tile of output pixels (blockIdx.x the tile, blockIdx.y the frame), as k_interp's;
+// Warp.  k_warp_affine: a block is a 64 x 4 tile of output pixels (grid.h's grid of tiles and frames), as k_interp's;
 // the block reads its frame's matrix once (uniform loads) and samples with sampler.h's bilinear rule.
 #include "sampler.h"
 
@@ -36,13 +36,15 @@ namespace {
 
 constexpr int kFitTX = 64, kFitTY = 4, kFitRows = 8;  // a lane: one column, kFitRows rows kFitTY apart
 constexpr int kFitTH = kFitTY * kFitRows;            // a block: 64 x 32 pixels
+using FitTile = Tile<kFitTX, kFitTH, kFitTX, kFitTY>;  // a strip of kFitTH rows under a block of kFitTY
 constexpr int kSums = 14;                             // include/papof.h: the order of the sums
 constexpr int kRow = 16;                              // doubles per partial row (kSums used)
 constexpr int kState = 8;                             // doubles per pair: matrix (6), ok (1), finished (1)
 constexpr int kWarpTX = 64, kWarpTY = 4;              // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+using WarpTile = Tile<kWarpTX, kWarpTY>;
 
 long long fit_blocks(int H, int W) {
-    return ((W + kFitTX - 1) / (long long)kFitTX) * ((H + kFitTH - 1) / (long long)kFitTH);
+    return FitTile::count(H, W);
 }
 
 struct FitArgs {
@@ -85,9 +87,7 @@ __global__ __launch_bounds__(kFitTX* kFitTY) void k_motion_sums(const FitArgs a,
     if (a.iter > 0)
 #pragma unroll
         for (int k = 0; k < 6; k++) m[k] = st[k];
-    const long long tx = (a.W + kFitTX - 1) / kFitTX, tile = blockIdx.x;
-    const int x = (int)(tile % tx) * kFitTX + (int)threadIdx.x;
-    const long long r0 = (tile / tx) * kFitTH + threadIdx.y;
+    PAPOF_TILE_PIXEL(FitTile, 0LL, a.W, int, x, long long, r0);  // (one launch holds every strip: fit_blocks <= kMaxTiles)
     double acc[kSums];
 #pragma unroll
     for (int k = 0; k < kSums; k++) acc[k] = 0.0;
@@ -227,7 +227,7 @@ int launch_fit(hipStream_t st, FitArgs f, SolveArgs s, int n_pairs, int n_iter) 
     for (int it = 0; it < n_iter; it++) {
         f.iter = s.iter = it;
         PAPOF_TRY(launch_tiles(f.blocks, n_pairs, [&](dim3 grid, long long, long long p0) {  // (blocks <= kMaxTiles)
-            hipLaunchKernelGGL(k_motion_sums, grid, dim3(kFitTX, kFitTY), 0, st, f, p0);
+            hipLaunchKernelGGL(k_motion_sums, grid, FitTile::block(), 0, st, f, p0);
         }));
         hipLaunchKernelGGL(k_motion_solve, dim3((unsigned)n_pairs), dim3(64), 0, st, s, 0LL);
         PAPOF_HIP(hipGetLastError());
@@ -259,9 +259,7 @@ __global__ __launch_bounds__(kFitTX* kFitTY) void k_homography_sums(const FitArg
 #pragma unroll
         for (int k = 0; k < 9; k++) m[k] = st[k];
     const double dc = (m[6] * a.cx + m[7] * a.cy) + m[8];  // the denominator at the image centre
-    const long long tx = (a.W + kFitTX - 1) / kFitTX, tile = blockIdx.x;
-    const int x = (int)(tile % tx) * kFitTX + (int)threadIdx.x;
-    const long long r0 = (tile / tx) * kFitTH + threadIdx.y;
+    PAPOF_TILE_PIXEL(FitTile, 0LL, a.W, int, x, long long, r0);  // (one launch holds every strip: fit_blocks <= kMaxTiles)
     double acc[kHSums];
 #pragma unroll
     for (int k = 0; k < kHSums; k++) acc[k] = 0.0;
@@ -399,7 +397,7 @@ int launch_homography_fit(hipStream_t st, FitArgs f, SolveArgs s, int n_pairs, i
     for (int it = 0; it < n_iter; it++) {
         f.iter = s.iter = it;
         PAPOF_TRY(launch_tiles(f.blocks, n_pairs, [&](dim3 grid, long long, long long p0) {  // (blocks <= kMaxTiles)
-            hipLaunchKernelGGL(k_homography_sums, grid, dim3(kFitTX, kFitTY), 0, st, f, p0);
+            hipLaunchKernelGGL(k_homography_sums, grid, FitTile::block(), 0, st, f, p0);
         }));
         hipLaunchKernelGGL(k_homography_solve, dim3((unsigned)n_pairs), dim3(64), 0, st, s, (double)(f.W - 1), (double)(f.H - 1));
         PAPOF_HIP(hipGetLastError());
@@ -415,14 +413,11 @@ struct WarpArgs {
     int H, W, C;
 };
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y
 template <int FD>
 __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        fill_u8_lut(lut, threadIdx.y * kWarpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kWarpTX>(lut);
     const long long i = frame0 + blockIdx.y;
     const long long mb = i * a.mat.stride[0];
     double m[6];
@@ -430,9 +425,7 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs
     for (int r = 0; r < 2; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[1] + c * a.mat.stride[2]);
-    const long long tx = (a.W + kWarpTX - 1) / kWarpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kWarpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kWarpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(WarpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const double xd = (double)x, rd = (double)r;
     const double X = (m[0] * xd + m[1] * rd) + m[2], Y = (m[3] * xd + m[4] * rd) + m[5];
@@ -451,23 +444,15 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs
 
 int launch_warp(hipStream_t st, const WarpArgs& a, int n_frames) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_warp_affine<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_warp_affine<PAPOF_DTYPE_F32>
-                                                : k_warp_affine<PAPOF_DTYPE_F64>;
-    const long long tiles = ((a.W + kWarpTX - 1) / (long long)kWarpTX) * ((a.H + kWarpTY - 1) / (long long)kWarpTY);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_warp_affine<fd()>; });
+    return launch_grid<WarpTile>(a.H, a.W, n_frames, st, 0, kernel, a);
 }
 
 // k_warp_affine's tiling over 3 x 3 matrices: (X, Y) = (Nx / D, Ny / D), inside only where D > 0 (include/papof.h)
 template <int FD>
 __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_projective(const WarpArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        fill_u8_lut(lut, threadIdx.y * kWarpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kWarpTX>(lut);
     const long long i = frame0 + blockIdx.y;
     const long long mb = i * a.mat.stride[0];
     double m[9];
@@ -475,9 +460,7 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_projective(const Warp
     for (int r = 0; r < 3; r++)
 #pragma unroll
         for (int c = 0; c < 3; c++) m[3 * r + c] = load_flow(a.mat, mb + r * a.mat.stride[1] + c * a.mat.stride[2]);
-    const long long tx = (a.W + kWarpTX - 1) / kWarpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kWarpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kWarpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(WarpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const double xd = (double)x, rd = (double)r;
     const double D = (m[6] * xd + m[7] * rd) + m[8];
@@ -497,13 +480,8 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_projective(const Warp
 
 int launch_warp_projective(hipStream_t st, const WarpArgs& a, int n_frames) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_warp_projective<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_warp_projective<PAPOF_DTYPE_F32>
-                                                : k_warp_projective<PAPOF_DTYPE_F64>;
-    const long long tiles = ((a.W + kWarpTX - 1) / (long long)kWarpTX) * ((a.H + kWarpTY - 1) / (long long)kWarpTY);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kWarpTX, kWarpTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_warp_projective<fd()>; });
+    return launch_grid<WarpTile>(a.H, a.W, n_frames, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -526,8 +504,8 @@ extern "C" int papof_motion_fit_tensor(papof_handle* h, int n_pairs, int height,
     if (!h || n_pairs < 1 || height < 1 || width < 1 || n_iter < 1) return PAPOF_EINVAL;
     if (model != PAPOF_MOTION_SIMILARITY && model != PAPOF_MOTION_AFFINE) return PAPOF_EINVAL;
     if (!std::isfinite(scale) || !(scale > 0)) return PAPOF_EINVAL;
-    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow(flow)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
     if (!described(motion, {PAPOF_DTYPE_F64}, {0, 1, 2}, true) || !described(ok, {PAPOF_DTYPE_U8}, {0}, true) ||
         !described(support, {PAPOF_DTYPE_F64}, {0}, true))
         return PAPOF_EINVAL;
@@ -566,10 +544,9 @@ extern "C" int papof_warp_affine_tensor(papof_handle* h, int n_frames, int heigh
                                         const papof_tensor* frames, const papof_tensor* matrices, const papof_tensor* out,
                                         const papof_tensor* valid, void* stream) {
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
     if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!opt_out_mask(valid)) return PAPOF_EINVAL;
     WarpArgs a{};
     a.fr = *frames;
     a.mat = *matrices;
@@ -595,8 +572,8 @@ extern "C" int papof_homography_fit_tensor(papof_handle* h, int n_pairs, int hei
                                            long long workspace_bytes, void* stream) {
     if (!h || n_pairs < 1 || height < 1 || width < 1 || n_iter < 1) return PAPOF_EINVAL;
     if (!std::isfinite(scale) || !(scale > 0)) return PAPOF_EINVAL;
-    if (!described(flow, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow(flow)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
     if (!described(motion, {PAPOF_DTYPE_F64}, {0, 1, 2}, true) || !described(ok, {PAPOF_DTYPE_U8}, {0}, true) ||
         !described(support, {PAPOF_DTYPE_F64}, {0}, true))
         return PAPOF_EINVAL;
@@ -633,10 +610,9 @@ extern "C" int papof_warp_projective_tensor(papof_handle* h, int n_frames, int h
                                             const papof_tensor* frames, const papof_tensor* matrices, const papof_tensor* out,
                                             const papof_tensor* valid, void* stream) {
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
     if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!opt_out_mask(valid)) return PAPOF_EINVAL;
     WarpArgs a{};
     a.fr = *frames;
     a.mat = *matrices;

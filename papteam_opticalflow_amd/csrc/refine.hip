@@ -11,7 +11,7 @@
 // sums 64-bit integers and the values are ordered by the monotone integer key of their float64 bits, so the result is a pure
 // function of the inputs: the bits of one particular neighbour, whatever the order of evaluation.
 //
-// Mapping.  k_refine: a block is a 32 x 8 tile of output pixels (blockIdx.x the tile, blockIdx.y the item), one lane per
+// Mapping.  k_refine: a block is a 32 x 8 tile of output pixels (grid.h's grid of tiles and items), one lane per
 // pixel.  The tile plus its halo of r is staged once in LDS: both components as keys, the guide (uint8 packed in one dword,
 // float32 / float64 as they are), a dead byte folding "outside / occluded / not finite", and the two tables.  A tile with no
 // `where` pixel copies its input and leaves after reading the mask.
@@ -35,6 +35,7 @@ namespace papof {
 namespace {
 
 constexpr int kTX = 32, kTY = 8;      // the tile of output pixels (256 lanes)
+using OutTile = Tile<kTX, kTY>;
 constexpr int kMaxRadius = 15;
 constexpr int kMaxIters = 65536;
 constexpr int kBins = 4096;           // the range table's bins
@@ -126,7 +127,7 @@ struct Select {
     }
 };
 
-// GD: the guide's dtype.  blockIdx.x: tile `tile0` + x of the frame's 32 x 8 tiles in row-major order; blockIdx.y: item
+// GD: the guide's dtype.  grid.h's grid over the frame's 32 x 8 tiles; blockIdx.y: item
 // `item0` + y.
 template <int GD>
 __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long long tile0, long long item0) {
@@ -144,8 +145,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long lo
     const double* const g64 = reinterpret_cast<const double*>(gbase);
 
     const int tid = threadIdx.y * kTX + threadIdx.x;
-    const long long tx = (W + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    PAPOF_TILE_ORIGIN(OutTile, tile0, W, int, x0, int, y0);
     const int x = x0 + (int)threadIdx.x, y = y0 + (int)threadIdx.y;
     const long long i = item0 + blockIdx.y;
     const bool inside = x < W && y < H;
@@ -330,14 +330,11 @@ extern "C" int papof_refine_flow_tensor(papof_handle* h, int n, int height, int 
     if (!h) return PAPOF_EINVAL;
     const long long need = papof_refine_workspace(n, height, width, iters);
     if (need < 0 || c < 1 || c > 4 || radius < 1 || radius > kMaxRadius) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto all = {0, 1, 2, 3};
-    if (!described(flow, F, all, false) || !described(guide, I, all, false) || !described(out, F, all, true))
+    if (!in_flow(flow) || !in_frames(guide) || !out_flow(out))
         return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (where && !described(where, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (passes && !described(passes, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
+    if (!opt_in_mask(where)) return PAPOF_EINVAL;
+    if (!opt_in_mask(passes)) return PAPOF_EINVAL;
     if (!S || !R || !std::isfinite(q) || q < 0) return PAPOF_EINVAL;
     if (need > 0 && (!workspace || workspace_bytes < need)) return PAPOF_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -363,11 +360,8 @@ extern "C" int papof_refine_flow_tensor(papof_handle* h, int n, int height, int 
         mid[k].stride[3] = HW;
     }
     const int gd = guide->dtype;
-    const auto kernel = gd == PAPOF_DTYPE_U8    ? k_refine<PAPOF_DTYPE_U8>
-                        : gd == PAPOF_DTYPE_F32 ? k_refine<PAPOF_DTYPE_F32>
-                                                : k_refine<PAPOF_DTYPE_F64>;
+    const auto kernel = by_dtype(gd, [](auto fd) { return k_refine<fd()>; });
     const size_t lds = (size_t)lds_bytes(gd, c, radius);
-    const long long tiles = ((width + kTX - 1) / (long long)kTX) * ((height + kTY - 1) / (long long)kTY);
     PAPOF_HIP(hipSetDevice(h->device));
     if (lds > 64 * 1024) {  // (above the default bound of a launch's dynamic LDS; a refusal shows at the launch)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -377,9 +371,7 @@ extern "C" int papof_refine_flow_tensor(papof_handle* h, int n, int height, int 
         a.flow = it == 0 ? *flow : mid[(it - 1) & 1];
         a.out = it == iters - 1 ? *out : mid[it & 1];
         a.passes = passes && it == iters - 1 ? *passes : papof_tensor{};
-        PAPOF_TRY(launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
-            hipLaunchKernelGGL(kernel, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
-        }));
+        PAPOF_TRY(launch_grid<OutTile>(height, width, n, st, lds, kernel, a));
     }
     return PAPOF_OK;
 }

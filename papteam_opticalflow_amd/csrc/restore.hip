@@ -35,6 +35,7 @@ namespace papof {
 namespace {
 
 constexpr int kDetectTX = 64, kDetectTY = 4;  // a 64 x 4 tile of pixels per block (256 lanes: lut)
+using DetectTile = Tile<kDetectTX, kDetectTY>;
 constexpr int kMaxC = 4;                      // channels (registers per lane: centre values)
 
 struct DetectArgs {
@@ -56,18 +57,13 @@ __device__ __forceinline__ bool detect_hop(const DetectArgs& a, long long from, 
                    : hop(a.bw, a.fw, from - 1, a.H, a.W, a.check, a.a1, a.a2, X, Y, nX, nY);
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(kDetectTX* kDetectTY) void k_defect_detect(const DetectArgs a, long long tile0,
                                                                         long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kDetectTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kDetectTX - 1) / kDetectTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kDetectTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kDetectTY + threadIdx.y;
+    stage_u8_lut<FD, kDetectTX>(lut);
+    PAPOF_TILE_PIXEL(DetectTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long t = frame0 + blockIdx.y;
     // the references t + o1 and t + o2: (-1, +1) inside the video, (+1, +2) at frame 0, (-1, -2) at frame T - 1
@@ -112,18 +108,13 @@ __global__ __launch_bounds__(kDetectTX* kDetectTY) void k_defect_detect(const De
 }
 
 int launch_detect(hipStream_t st, const DetectArgs& a) {
-    const auto kernel = a.fr.dtype == PAPOF_DTYPE_U8    ? k_defect_detect<PAPOF_DTYPE_U8>
-                        : a.fr.dtype == PAPOF_DTYPE_F32 ? k_defect_detect<PAPOF_DTYPE_F32>
-                                                        : k_defect_detect<PAPOF_DTYPE_F64>;
-    const long long tiles =
-        ((a.W + kDetectTX - 1) / (long long)kDetectTX) * ((a.H + kDetectTY - 1) / (long long)kDetectTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kDetectTX, kDetectTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(a.fr.dtype, [](auto fd) { return k_defect_detect<fd()>; });
+    return launch_grid<DetectTile>(a.H, a.W, a.T, st, 0, kernel, a);
 }
 
 constexpr int kDilateTX = 64, kDilateWaves = 4;  // a wave is the 64 columns of one row: one word
 constexpr int kDilateTY = 16;                    // output rows per block
+using DilateTile = Tile<kDilateTX, kDilateTY, kDilateTX, kDilateWaves>;
 constexpr int kMaxDilate = 32;                   // radius: the left and right words reach 64 columns
 
 struct DilateArgs {
@@ -131,14 +122,12 @@ struct DilateArgs {
     int T, H, W, R;
 };
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 16 tiles in row-major order; blockIdx.y: frame `frame0` + y.  No lane
+// grid.h's grid over the frame's 64 x 16 tiles; blockIdx.y: frame `frame0` + y.  No lane
 // leaves before the last __ballot and the barrier: a lane beyond the image votes 0 and stores nothing.
 __global__ __launch_bounds__(kDilateTX* kDilateWaves) void k_mask_dilate(const DilateArgs a, long long tile0,
                                                                          long long frame0) {
     __shared__ unsigned long long hrow[kDilateTY + 2 * kMaxDilate];  // input rows r0 - R .. r0 + 15 + R, dilated along x
-    const long long tx = (a.W + kDilateTX - 1) / kDilateTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kDilateTX;
-    const long long r0 = (tile / tx) * kDilateTY;
+    PAPOF_TILE_ORIGIN(DilateTile, tile0, a.W, int, x0, long long, r0);
     const long long t = frame0 + blockIdx.y;
     const int lane = (int)threadIdx.x, wave = (int)threadIdx.y, R = a.R;
     const unsigned char* m = static_cast<const unsigned char*>(a.in.data) + t * a.in.stride[0];
@@ -168,11 +157,7 @@ __global__ __launch_bounds__(kDilateTX* kDilateWaves) void k_mask_dilate(const D
 }
 
 int launch_dilate(hipStream_t st, const DilateArgs& a) {
-    const long long tiles =
-        ((a.W + kDilateTX - 1) / (long long)kDilateTX) * ((a.H + kDilateTY - 1) / (long long)kDilateTY);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(k_mask_dilate, grid, dim3(kDilateTX, kDilateWaves), 0, st, a, t0, f0);
-    });
+    return launch_grid<DilateTile>(a.H, a.W, a.T, st, 0, k_mask_dilate, a);
 }
 
 }  // namespace
@@ -189,13 +174,11 @@ extern "C" int papof_defect_detect_tensor(papof_handle* h, int n_frames, int hei
     if (!h || n_frames < 3 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
     if (!std::isfinite(threshold) || threshold < 0) return PAPOF_EINVAL;
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!in_frames(frames)) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
     if (!described(mask, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
-    if (score && !described(score, F, {0, 1, 2}, true)) return PAPOF_EINVAL;
-    if (support && !described(support, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!opt_out_plane(score)) return PAPOF_EINVAL;
+    if (!opt_out_mask(support)) return PAPOF_EINVAL;
     DetectArgs a{};
     a.fr = *frames;
     a.fw = *flow_fw;

@@ -14,7 +14,7 @@
 // Semantics: include/papof.h, papof_rs_rectify_tensor.  The samplers are sampler.h's (taps_at, sample_flow, sample_frame),
 // fp64 without contraction (-ffp-contract=off); the fp64 divisions are IEEE (the restatement's bits).
 //
-// Mapping.  A block is a 64 x 4 tile of output pixels (as k_warp_affine's): blockIdx.x the tile, blockIdx.y the frame --
+// Mapping.  A block is a 64 x 4 tile of output pixels (as k_warp_affine's), over grid.h's grid of tiles and frames --
 // for k_rs_flow the (pair, direction) slot.  The frame, hence which of the three forms of the displacement applies, is
 // uniform over the block; the s == 0 row and a solve that dies early diverge within a wave and cost that wave nothing more
 // than the longest lane.  No atomics, no workspace: every output element belongs to one lane.  Every offset is 64-bit.
@@ -27,6 +27,7 @@ namespace papof {
 namespace {
 
 constexpr int kRsTX = 64, kRsTY = 4;  // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+using RsTile = Tile<kRsTX, kRsTY>;
 constexpr int kRsMaxIters = 8;
 constexpr int kRsMaxC = 4;
 
@@ -99,19 +100,14 @@ __device__ __forceinline__ bool rs_solve(const RsRule& g, long long t, double Qx
     return true;
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y
 template <int FD, bool HAS_MATRICES>
 __global__ __launch_bounds__(kRsTX* kRsTY) void k_rs_rectify(const RsRectifyArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kRsTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kRsTX>(lut);
     const int H = a.g.H, W = a.g.W;
     const long long t = frame0 + blockIdx.y;
-    const long long tx = (W + kRsTX - 1) / kRsTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kRsTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kRsTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(RsTile, tile0, W, int, x, long long, r);
     if (x >= W || r >= H) return;
     double Qx = (double)x, Qy = (double)r;
     if (HAS_MATRICES) {
@@ -145,9 +141,7 @@ __global__ __launch_bounds__(kRsTX* kRsTY) void k_rs_flow(const RsFlowArgs a, lo
     const int H = a.g.H, W = a.g.W;
     const long long slot = slot0 + blockIdx.y, i = slot >> 1;
     const bool back = slot & 1;
-    const long long tx = (W + kRsTX - 1) / kRsTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kRsTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kRsTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(RsTile, tile0, W, int, x, long long, r);
     if (x >= W || r >= H) return;
     const long long t = back ? i + 1 : i, t2 = back ? i : i + 1;  // the pixel's frame, and the frame its flow lands in
     const papof_tensor& f = back ? a.g.bw : a.g.fw;
@@ -174,20 +168,12 @@ __global__ __launch_bounds__(kRsTX* kRsTY) void k_rs_flow(const RsFlowArgs a, lo
 template <bool HAS_MATRICES>
 int launch_rectify(hipStream_t st, const RsRectifyArgs& a) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_rs_rectify<PAPOF_DTYPE_U8, HAS_MATRICES>
-                        : fd == PAPOF_DTYPE_F32 ? k_rs_rectify<PAPOF_DTYPE_F32, HAS_MATRICES>
-                                                : k_rs_rectify<PAPOF_DTYPE_F64, HAS_MATRICES>;
-    const long long tiles = ((a.g.W + kRsTX - 1) / (long long)kRsTX) * ((a.g.H + kRsTY - 1) / (long long)kRsTY);
-    return launch_tiles(tiles, a.g.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kRsTX, kRsTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_rs_rectify<fd(), HAS_MATRICES>; });
+    return launch_grid<RsTile>(a.g.H, a.g.W, a.g.T, st, 0, kernel, a);
 }
 
 int launch_rs_flow(hipStream_t st, const RsFlowArgs& a) {
-    const long long tiles = ((a.g.W + kRsTX - 1) / (long long)kRsTX) * ((a.g.H + kRsTY - 1) / (long long)kRsTY);
-    return launch_tiles(tiles, 2LL * (a.g.T - 1), [&](dim3 grid, long long t0, long long s0) {
-        hipLaunchKernelGGL(k_rs_flow, grid, dim3(kRsTX, kRsTY), 0, st, a, t0, s0);
-    });
+    return launch_grid<RsTile>(a.g.H, a.g.W, 2LL * (a.g.T - 1), st, 0, k_rs_flow, a);
 }
 
 // the arguments both calls share: false where the header refuses them
@@ -195,8 +181,7 @@ bool rs_rule(RsRule& g, int n_frames, int height, int width, const papof_tensor*
              double readout, double anchor, int iters) {
     if (n_frames < 2 || height < 1 || width < 1 || iters < 1 || iters > kRsMaxIters) return false;
     if (!std::isfinite(readout) || std::fabs(readout) > 1.0 || !(anchor >= 0.0 && anchor <= 1.0)) return false;
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return false;
+    if (!in_flow_pair(flow_fw, flow_bw)) return false;
     g.fw = *flow_fw;
     g.bw = *flow_bw;
     g.T = n_frames;
@@ -221,10 +206,9 @@ extern "C" int papof_rs_rectify_tensor(papof_handle* h, int n_frames, int height
     RsRectifyArgs a{};
     if (!h || c < 1 || c > kRsMaxC || !rs_rule(a.g, n_frames, height, width, flow_fw, flow_bw, readout, anchor, iters))
         return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (matrices && !described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
+    if (!opt_in_plane(matrices)) return PAPOF_EINVAL;
+    if (!opt_out_mask(valid)) return PAPOF_EINVAL;
     a.fr = *frames;
     if (matrices) a.mat = *matrices;
     a.out = *out;
@@ -240,8 +224,7 @@ extern "C" int papof_rs_flow_tensor(papof_handle* h, int n_frames, int height, i
                                     const papof_tensor* out_fw, const papof_tensor* out_bw, void* stream) {
     RsFlowArgs a{};
     if (!h || !rs_rule(a.g, n_frames, height, width, flow_fw, flow_bw, readout, anchor, iters)) return PAPOF_EINVAL;
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(out_fw, F, {0, 1, 2, 3}, true) || !described(out_bw, F, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!out_flow(out_fw) || !out_flow(out_bw)) return PAPOF_EINVAL;
     a.out_fw = *out_fw;
     a.out_bw = *out_bw;
     PAPOF_HIP(hipSetDevice(h->device));

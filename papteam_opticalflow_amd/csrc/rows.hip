@@ -11,7 +11,7 @@
 //
 // Semantics: include/papof.h, papof_warp_rows_tensor.  fp64 without contraction (-ffp-contract=off); IEEE divisions.
 //
-// Mapping.  k_warp_affine's: a block is a 64 x 4 tile of output pixels, blockIdx.x the tile, blockIdx.y the frame.  The lanes
+// Mapping.  k_warp_affine's: a block is a 64 x 4 tile of output pixels, over grid.h's grid of tiles and frames.  The lanes
 // of a wave share the output row and, but for the few waves whose iterate straddles a knot, the interval k, so the two
 // knots' loads are one address per wave (a broadcast from the cache); the table is read through global addresses, not staged
 // (DESIGN.md has the reasons).  Bounds: s = Yc * g is formed from a clamped Yc in [0, H - 1] that is never a NaN, so the
@@ -26,6 +26,7 @@ namespace papof {
 namespace {
 
 constexpr int kRowsTX = 64, kRowsTY = 4;  // a 64 x 4 tile of output pixels per block (256 lanes: lut)
+using RowsTile = Tile<kRowsTX, kRowsTY>;
 constexpr int kRowsMaxIters = 8;
 
 struct RowsArgs {
@@ -38,18 +39,13 @@ struct RowsArgs {
     double g;            // (double)(Kn - 1) / (double)(H - 1); unused for Kn == 1
 };
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y
+// grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y
 template <int FD>
 __global__ __launch_bounds__(kRowsTX* kRowsTY) void k_warp_rows(const RowsArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        fill_u8_lut(lut, threadIdx.y * kRowsTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kRowsTX>(lut);
     const long long i = frame0 + blockIdx.y;
-    const long long tx = (a.W + kRowsTX - 1) / kRowsTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kRowsTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kRowsTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(RowsTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const double xd = (double)x, rd = (double)r, H1 = (double)(a.H - 1);
     const long long mb = i * a.tab.stride[0];
@@ -100,13 +96,8 @@ __global__ __launch_bounds__(kRowsTX* kRowsTY) void k_warp_rows(const RowsArgs a
 
 int launch_warp_rows(hipStream_t st, const RowsArgs& a, int n_frames) {
     const int fd = a.fr.dtype;
-    const auto kernel = fd == PAPOF_DTYPE_U8 ? k_warp_rows<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_warp_rows<PAPOF_DTYPE_F32>
-                                                : k_warp_rows<PAPOF_DTYPE_F64>;
-    const long long tiles = ((a.W + kRowsTX - 1) / (long long)kRowsTX) * ((a.H + kRowsTY - 1) / (long long)kRowsTY);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kRowsTX, kRowsTY), 0, st, a, t0, f0);
-    });
+    const auto kernel = by_dtype(fd, [](auto fd) { return k_warp_rows<fd()>; });
+    return launch_grid<RowsTile>(a.H, a.W, n_frames, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -121,10 +112,9 @@ extern "C" int papof_warp_rows_tensor(papof_handle* h, int n_frames, int height,
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
     if (n_knots < 1 || n_knots > PAPOF_ROWS_MAX_KNOTS) return PAPOF_EINVAL;
     if (n_knots > 1 && (height < 2 || iters < 1 || iters > kRowsMaxIters)) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (!described(matrices, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (valid && !described(valid, {PAPOF_DTYPE_U8}, {0, 1, 2}, true)) return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
+    if (!in_flow(matrices)) return PAPOF_EINVAL;
+    if (!opt_out_mask(valid)) return PAPOF_EINVAL;
     RowsArgs a{};
     a.fr = *frames;
     a.tab = *matrices;

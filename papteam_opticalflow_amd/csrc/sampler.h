@@ -2,8 +2,9 @@
 // frames and flows at non-integer points (k_interp, k_warp_affine, k_temporal_filter, k_propagate, the fill and consistency
 // kernels, k_track, k_fb_check), the forward-backward test and the hop of a point through a pair's flows (k_track,
 // k_temporal_filter, k_propagate, k_tc_setup; the test also k_fb_check), the interpolation rule at one output pixel (k_interp,
-// k_interp_splat, k_motion_blur), and on the host the splitting of a (tile, frame)
-// grid at the grid's bounds and the pyramid level sizes of the fill and consistency workspaces.
+// k_interp_splat, k_motion_blur), the block's table of uint8 quotients (stage_u8_lut), and on the host the pyramid level
+// sizes of the fill and consistency workspaces.  The (tile, item) grid these kernels are launched over -- tile decode, tile
+// count, split launches, the choice of an instance by dtype -- is grid.h's.
 //
 // The rule is the reference's (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours
 // clamped into the image, taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  Frames are
@@ -12,6 +13,7 @@
 #pragma once
 
 #include "common.h"
+#include "grid.h"
 
 namespace papof {
 
@@ -20,6 +22,17 @@ namespace {
 // The 256 quotients k / 255.0 of a uint8 sample, one per lane of a 256-lane block: the block fills its table once and
 // synchronises before the first load_frame (the same bits as a division per tap, without the fp64 division).
 __device__ __forceinline__ void fill_u8_lut(double* lut, int k) { lut[k] = (double)k / 255.0; }
+
+// The prologue of a kernel whose frames are of dtype FD and whose block is TX lanes wide (0: a row of lanes) and 256 lanes in
+// all: each lane fills the quotient of its linear index and the block synchronises, where a uint8 sample can occur (FD uint8, or -1: read
+// from each descriptor).  It stands before any lane's early return: every lane of the block reaches the barrier.
+template <int FD, int TX = 0>
+__device__ __forceinline__ void stage_u8_lut(double* lut) {
+    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
+        fill_u8_lut(lut, TX ? threadIdx.y * TX + threadIdx.x : threadIdx.x);
+        __syncthreads();
+    }
+}
 
 // FD: the dtype of the frame tensors, fixed at compile time (the common case: one branch-free gather per tap), or -1: read
 // from each descriptor.  A uint8 sample is looked up in the block's table (fill_u8_lut).
@@ -135,6 +148,7 @@ __device__ __forceinline__ void add64(unsigned long long* p, long long v) {
 // ---- the rule of papof_interp_tensor at one output pixel, shared by k_interp (interp.hip) and by k_interp_splat
 // (splat.hip: the pixels that no splat reaches) ----
 constexpr int kInterpTX = 64, kInterpTY = 4;   // a 64 x 4 tile of pixels per block (256 lanes: lut)
+using InterpTile = Tile<kInterpTX, kInterpTY>;
 constexpr int kMaxTimes = 16;                  // times per launch (kernel arguments)
 
 struct InterpArgs {
@@ -242,21 +256,6 @@ __device__ __forceinline__ void interp_pixel(const InterpArgs& a, const double* 
             store(a.out, oj + ch * a.out.stride[3], val);
         }
     }
-}
-
-constexpr long long kMaxTiles = 0x7fffffffLL;  // gridDim.x
-constexpr long long kMaxFrames = 65535;        // gridDim.y
-
-// A (tile, frame) grid of `tiles` x `frames` blocks in launches that fit the grid's bounds, frames outermost: launch(grid,
-// tile0, frame0) enqueues one of them, whose blockIdx.x is tile tile0 + x and blockIdx.y frame frame0 + y.
-template <typename L>
-int launch_tiles(long long tiles, long long frames, L launch) {
-    for (long long f0 = 0; f0 < frames; f0 += kMaxFrames)
-        for (long long t0 = 0; t0 < tiles; t0 += kMaxTiles) {
-            launch(dim3((unsigned)std::min(kMaxTiles, tiles - t0), (unsigned)std::min(kMaxFrames, frames - f0)), t0, f0);
-            PAPOF_HIP(hipGetLastError());
-        }
-    return PAPOF_OK;
 }
 
 // The pyramid of the fill's and the consistency solve's workspaces: level l + 1 is ceil(h / 2) x ceil(w / 2) of level l, from

@@ -131,8 +131,7 @@ extern "C" int papof_cell_hist_tensor(papof_handle* h, int n_frames, int height,
     if (!h || n_frames < 1 || height < 1 || width < 1 || c < 1 || c > kMaxC || !hist) return PAPOF_EINVAL;
     if (cell_rows < 1 || cell_rows > kMaxCellRows) return PAPOF_EINVAL;
     if (bins != 4 && bins != 8 && bins != 16 && bins != 32 && bins != 64) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!in_frames(frames)) return PAPOF_EINVAL;
     HistArgs a{};
     a.fr = *frames;
     a.out = hist;
@@ -149,8 +148,5 @@ extern "C" int papof_cell_hist_tensor(papof_handle* h, int n_frames, int height,
                         : a.fr.dtype == PAPOF_DTYPE_U8  ? hist_kernel<PAPOF_DTYPE_U8, false>(c, bins)
                         : a.fr.dtype == PAPOF_DTYPE_F32 ? hist_kernel<PAPOF_DTYPE_F32, false>(c, bins)
                                                         : hist_kernel<PAPOF_DTYPE_F64, false>(c, bins);
-    const long long tiles = (long long)a.Gy * ((a.Gx + kCellsX - 1) / kCellsX);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kCellW, kCellsX), 0, static_cast<hipStream_t>(stream), a, t0, f0);
-    });
+    return launch_grid<CellTile>(a.Gy, a.Gx, n_frames, static_cast<hipStream_t>(stream), 0, kernel, a);
 }

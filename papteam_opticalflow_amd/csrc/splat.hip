@@ -12,7 +12,7 @@
 // so the order in which the adds arrive cannot change a bit.  A term is at most 2^32 in magnitude and a target receives at
 // most one tap per source pixel, so with height * width < 2^30 a sum stays inside int64.
 //
-// Mapping.  k_splat: a block is a 64 x 4 tile of SOURCE pixels (k_interp's tile), blockIdx.x the tile, blockIdx.y the item;
+// Mapping.  k_splat: a block is a 64 x 4 tile of SOURCE pixels (k_interp's tile), over grid.h's grid of tiles and items;
 // a lane reads its flow and weight once and loops over the times (kernel arguments, as k_interp's).  The accumulator is
 // PLANAR, [item][time][C + 1][row][column] with the denominator's plane last: neighbouring lanes of a wave are neighbouring
 // source pixels of a row, so while the flow is smooth one atomic wave-instruction covers 512 contiguous bytes of one plane
@@ -46,18 +46,13 @@ struct SplatArgs {
     double t[kMaxTimes];
 };
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles of source pixels in row-major order; blockIdx.y: item
+// grid.h's grid over the frame's 64 x 4 tiles of source pixels; blockIdx.y: item
 // `item0` + y.
 template <int FD>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_splat(const SplatArgs a, long long tile0, long long item0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    stage_u8_lut<FD, kInterpTX>(lut);
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const int H = a.H, W = a.W, C = a.C;
     const long long i = item0 + blockIdx.y;
@@ -111,13 +106,11 @@ struct ResolveArgs {
     int nt;
 };
 
-// blockIdx.x: tile `tile0` + x of the 64 x 4 tiles of TARGET pixels; blockIdx.y: item `item0` + y.  The launch's times are
+// grid.h's grid over the 64 x 4 tiles of TARGET pixels; blockIdx.y: item `item0` + y.  The launch's times are
 // the time slots j0 .. j0 + a.nt of out and coverage.
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_splat_resolve(const ResolveArgs a, long long tile0, long long item0,
                                                                         long long j0) {
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long i = item0 + blockIdx.y, C1 = a.C + 1, HW = a.H * (long long)a.W;
     const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
@@ -140,13 +133,8 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp_splat(const Int
                                                                        const long long* acc1, long long tile0, long long pair0,
                                                                        long long j0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8 || FD < 0) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);
-        __syncthreads();
-    }
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    stage_u8_lut<FD, kInterpTX>(lut);
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long i = pair0 + blockIdx.y, C1 = a.C + 1, HW = a.H * (long long)a.W;
     interp_pixel<FD>(a, lut, i, r, x, j0, [&](int j, long long oj) {
@@ -179,15 +167,10 @@ bool power_of_two_bound(double b) {
 }
 
 int launch_splat(hipStream_t st, SplatArgs a, int n, int g, const double* times) {
-    const auto kernel = a.x.dtype == PAPOF_DTYPE_U8    ? k_splat<PAPOF_DTYPE_U8>
-                        : a.x.dtype == PAPOF_DTYPE_F32 ? k_splat<PAPOF_DTYPE_F32>
-                                                       : k_splat<PAPOF_DTYPE_F64>;
+    const auto kernel = by_dtype(a.x.dtype, [](auto fd) { return k_splat<fd()>; });
     a.nt = g;
     std::copy(times, times + g, a.t);
-    const long long tiles = ((a.W + kInterpTX - 1) / (long long)kInterpTX) * ((a.H + kInterpTY - 1) / (long long)kInterpTY);
-    return launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kInterpTX, kInterpTY), 0, st, a, t0, i0);
-    });
+    return launch_grid<InterpTile>(a.H, a.W, n, st, 0, kernel, a);
 }
 
 }  // namespace
@@ -210,12 +193,10 @@ extern "C" int papof_splat_tensor(papof_handle* h, int n, int height, int width,
     if (!h) return PAPOF_EINVAL;
     const long long one = one_time_bytes(n, height, width, c);
     if (one < 0) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto all = {0, 1, 2, 3};
-    if (!described(x, I, all, false) || !described(flow, F, all, false)) return PAPOF_EINVAL;
-    if (weight && !described(weight, F, {0, 1, 2}, false)) return PAPOF_EINVAL;
-    if (!described(out, I, all, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
+    if (!in_frames(x) || !in_flow(flow)) return PAPOF_EINVAL;
+    if (!opt_in_plane(weight)) return PAPOF_EINVAL;
+    if (!out_frames(out) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
     if (coverage && !described(coverage, {PAPOF_DTYPE_F64}, all, true)) return PAPOF_EINVAL;
     if (n_times < 1 || !times || !power_of_two_bound(bound)) return PAPOF_EINVAL;
     for (int j = 0; j < n_times; j++)
@@ -242,7 +223,7 @@ extern "C" int papof_splat_tensor(papof_handle* h, int n, int height, int width,
     q.H = height;
     q.W = width;
     q.C = c;
-    const long long tiles = ((width + kInterpTX - 1) / (long long)kInterpTX) * ((height + kInterpTY - 1) / (long long)kInterpTY);
+    const long long tiles = InterpTile::count(height, width);
     PAPOF_HIP(hipSetDevice(h->device));
     for (int j0 = 0; j0 < n_times; j0 += g) {
         const int nt = std::min(g, n_times - j0);
@@ -250,7 +231,7 @@ extern "C" int papof_splat_tensor(papof_handle* h, int n, int height, int width,
         PAPOF_TRY(launch_splat(st, a, n, nt, times + j0));
         q.nt = nt;
         PAPOF_TRY(launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
-            hipLaunchKernelGGL(k_splat_resolve, grid, dim3(kInterpTX, kInterpTY), 0, st, q, t0, i0, (long long)j0);
+            hipLaunchKernelGGL(k_splat_resolve, grid, InterpTile::block(), 0, st, q, t0, i0, (long long)j0);
         }));
     }
     return PAPOF_OK;
@@ -266,16 +247,12 @@ extern "C" int papof_interp_splat_tensor(papof_handle* h, int n_pairs, int seque
     if (!h || n_pairs < 1 || n_pairs > 0x3fffffff) return PAPOF_EINVAL;
     const long long one = one_time_bytes(2LL * n_pairs, height, width, c);
     if (one < 0) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
     const auto all = {0, 1, 2, 3};
-    if (!described(frames, I, all, false) || (sequence ? frames2 != nullptr : !described(frames2, I, all, false)))
-        return PAPOF_EINVAL;
-    if (!described(flow_fw, F, all, false) || !described(flow_bw, F, all, false)) return PAPOF_EINVAL;
-    if ((weight_fw && !described(weight_fw, F, {0, 1, 2}, false)) || (weight_bw && !described(weight_bw, F, {0, 1, 2}, false)))
-        return PAPOF_EINVAL;
+    if (!in_frames(frames) || (sequence ? frames2 != nullptr : !in_frames(frames2))) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (!opt_in_plane(weight_fw) || !opt_in_plane(weight_bw)) return PAPOF_EINVAL;
     if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, all, false)) return PAPOF_EINVAL;
-    if (!described(out, I, all, true) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
+    if (!out_frames(out) || time_stride < 0 || (n_times > 1 && time_stride == 0)) return PAPOF_EINVAL;
     if (n_times < 1 || !times) return PAPOF_EINVAL;
     for (int j = 0; j < n_times; j++)
         if (!std::isfinite(times[j]) || !(times[j] > 0.0 && times[j] < 1.0)) return PAPOF_EINVAL;
@@ -306,12 +283,9 @@ extern "C" int papof_interp_splat_tensor(papof_handle* h, int n_pairs, int seque
     s0.H = s1.H = height;
     s0.W = s1.W = width;
     s0.C = s1.C = c;
-    const int fd = a.f0.dtype == a.f1.dtype ? a.f0.dtype : -1;
-    const auto kernel = fd == PAPOF_DTYPE_U8    ? k_interp_splat<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_interp_splat<PAPOF_DTYPE_F32>
-                        : fd == PAPOF_DTYPE_F64 ? k_interp_splat<PAPOF_DTYPE_F64>
-                                                : k_interp_splat<-1>;
-    const long long tiles = ((width + kInterpTX - 1) / (long long)kInterpTX) * ((height + kInterpTY - 1) / (long long)kInterpTY);
+    const auto kernel =
+        by_frame_dtype(a.f0.dtype == a.f1.dtype ? a.f0.dtype : -1, [](auto fd) { return k_interp_splat<fd()>; });
+    const long long tiles = InterpTile::count(height, width);
     PAPOF_HIP(hipSetDevice(h->device));
     for (int j0 = 0; j0 < n_times; j0 += g) {
         const int nt = std::min(g, n_times - j0);
@@ -327,7 +301,7 @@ extern "C" int papof_interp_splat_tensor(papof_handle* h, int n_pairs, int seque
         const long long* acc0 = reinterpret_cast<const long long*>(s0.acc);
         const long long* acc1 = reinterpret_cast<const long long*>(s1.acc);
         PAPOF_TRY(launch_tiles(tiles, n_pairs, [&](dim3 grid, long long t0, long long p0) {
-            hipLaunchKernelGGL(kernel, grid, dim3(kInterpTX, kInterpTY), 0, st, a, acc0, acc1, t0, p0, (long long)j0);
+            hipLaunchKernelGGL(kernel, grid, InterpTile::block(), 0, st, a, acc0, acc1, t0, p0, (long long)j0);
         }));
     }
     return PAPOF_OK;

@@ -38,6 +38,7 @@ constexpr int kMaxC = 4;                      // channels (registers per lane)
 constexpr int kMinScale = 2, kMaxScale = 4;
 constexpr long long kBudget = 1LL << 31;      // papof_sr_workspace: as many target frames as fit 2 GiB
 constexpr int kBpX = 16, kBpY = 8;            // k_sr_backproject: the block's tile of low-resolution pixels
+using LowTile = Tile<kBpX, kBpY, 256, 1>;     // ... under a row of 256 lanes
 
 struct SrArgs {
     papof_tensor fr;          // frames (frame, row, column, channel)
@@ -138,19 +139,14 @@ __device__ __forceinline__ void walk(const SrArgs& a, const papof_tensor& f, con
     }
 }
 
-// blockIdx.x: tile `tile0` + x of the frame's 64 x 4 tiles of source pixels in row-major order; blockIdx.y: source frame
+// grid.h's grid over the frame's 64 x 4 tiles of source pixels; blockIdx.y: source frame
 // `frame0` + y.  A wave is one row of 64 source pixels.
 template <int FD>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_sr_accumulate(const SrArgs a, long long tile0, long long frame0) {
     static_assert(kInterpTX == 64, "deposit: a wave is a row of the tile");
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kInterpTX + (int)threadIdx.x;
-    const long long r = (tile / tx) * kInterpTY + threadIdx.y;
+    stage_u8_lut<FD, kInterpTX>(lut);
+    PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (r >= a.H) return;  // (the whole wave)
     const bool valid = x < a.W;
     const long long k = frame0 + blockIdx.y;
@@ -189,17 +185,13 @@ struct SrResolveArgs {
     double prior;
 };
 
-// blockIdx.x: tile `tile0` + x of the 64 x 4 tiles of FINE pixels; blockIdx.y: target t0 + `frame0` + y.
+// grid.h's grid over the 64 x 4 tiles of FINE pixels; blockIdx.y: target t0 + `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_sr_resolve(const SrResolveArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kInterpTX + threadIdx.x);
-        __syncthreads();
-    }
+    stage_u8_lut<FD, kInterpTX>(lut);
     const long long FW = (long long)a.S * a.W, FH = (long long)a.S * a.H, plane = FW * FH;
-    const long long tx = (FW + kInterpTX - 1) / kInterpTX, tile = tile0 + blockIdx.x;
-    const long long x = (tile % tx) * kInterpTX + threadIdx.x, r = (tile / tx) * kInterpTY + threadIdx.y;
+    PAPOF_TILE_PIXEL(InterpTile, tile0, FW, long long, x, long long, r);
     if (x >= FW || r >= FH) return;
     const long long g = frame0 + blockIdx.y, t = a.t0 + g;
     const double S = (double)a.S;
@@ -246,7 +238,7 @@ struct SrBackArgs {
     int H, W, C, S;
 };
 
-// blockIdx.x: tile `tile0` + x of the kBpX x kBpY tiles of LOW-resolution pixels; blockIdx.y: target t0 + `frame0` + y.
+// grid.h's grid over the kBpX x kBpY tiles of LOW-resolution pixels; blockIdx.y: target t0 + `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(256) void k_sr_backproject(const SrBackArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
@@ -255,8 +247,7 @@ __global__ __launch_bounds__(256) void k_sr_backproject(const SrBackArgs a, long
     const int tid = threadIdx.x, S = a.S;
     if (FD == PAPOF_DTYPE_U8) fill_u8_lut(lut, tid);  // (the first barrier of the channel loop orders it)
     const long long FW = (long long)S * a.W, FH = (long long)S * a.H, plane = FW * FH;
-    const long long tx = (a.W + kBpX - 1) / kBpX, tile = tile0 + blockIdx.x;
-    const long long lx0 = (tile % tx) * kBpX, ly0 = (tile / tx) * kBpY;  // the tile's first low-resolution pixel
+    PAPOF_TILE_ORIGIN(LowTile, tile0, a.W, long long, lx0, long long, ly0);  // the tile's first low-resolution pixel
     const long long hx0 = lx0 - 1, hy0 = ly0 - 1;                       // the halo's
     const int sw = (kBpX + 2) * S, sh = (kBpY + 2) * S;                 // the staged fine pixels
     const long long g = frame0 + blockIdx.y, t = a.t0 + g;
@@ -333,11 +324,8 @@ extern "C" int papof_super_resolve_tensor(papof_handle* h, int n_frames, int hei
     if ((2LL * radius + 1) * height * width >= (1LL << 30)) return PAPOF_EINVAL;
     if (!std::isfinite(sigma) || sigma < 0 || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     if (!std::isfinite(prior) || prior < 1.0 / 16777216.0) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(frames, I, {0, 1, 2, 3}, false) || !described(out, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
-    if (n_frames > 1 && radius > 0 &&  // (no flow is read otherwise: they may be NULL)
-        (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)))
+    if (!in_frames(frames) || !out_frames(out)) return PAPOF_EINVAL;
+    if (n_frames > 1 && radius > 0 && !in_flow_pair(flow_fw, flow_bw))  // (no flow is read otherwise: they may be NULL)
         return PAPOF_EINVAL;
     if (coverage && !described(coverage, {PAPOF_DTYPE_F64}, {0, 1, 2}, true)) return PAPOF_EINVAL;
     if (!workspace || workspace_bytes < per) return PAPOF_EINVAL;
@@ -385,18 +373,9 @@ extern "C" int papof_super_resolve_tensor(papof_handle* h, int n_frames, int hei
     p.S = scale;
 
     const int fd = frames->dtype;
-    const auto k_acc = fd == PAPOF_DTYPE_U8    ? k_sr_accumulate<PAPOF_DTYPE_U8>
-                       : fd == PAPOF_DTYPE_F32 ? k_sr_accumulate<PAPOF_DTYPE_F32>
-                                               : k_sr_accumulate<PAPOF_DTYPE_F64>;
-    const auto k_res = fd == PAPOF_DTYPE_U8    ? k_sr_resolve<PAPOF_DTYPE_U8>
-                       : fd == PAPOF_DTYPE_F32 ? k_sr_resolve<PAPOF_DTYPE_F32>
-                                               : k_sr_resolve<PAPOF_DTYPE_F64>;
-    const auto k_back = fd == PAPOF_DTYPE_U8    ? k_sr_backproject<PAPOF_DTYPE_U8>
-                        : fd == PAPOF_DTYPE_F32 ? k_sr_backproject<PAPOF_DTYPE_F32>
-                                                : k_sr_backproject<PAPOF_DTYPE_F64>;
-    const long long src_tiles = ((width + kInterpTX - 1) / (long long)kInterpTX) * ((height + kInterpTY - 1) / (long long)kInterpTY);
-    const long long fine_tiles = ((FW + kInterpTX - 1) / kInterpTX) * ((FH + kInterpTY - 1) / kInterpTY);
-    const long long low_tiles = ((width + kBpX - 1) / (long long)kBpX) * ((height + kBpY - 1) / (long long)kBpY);
+    const auto k_acc = by_dtype(fd, [](auto fd) { return k_sr_accumulate<fd()>; });
+    const auto k_res = by_dtype(fd, [](auto fd) { return k_sr_resolve<fd()>; });
+    const auto k_back = by_dtype(fd, [](auto fd) { return k_sr_backproject<fd()>; });
     PAPOF_HIP(hipSetDevice(h->device));
     for (long long t0 = 0; t0 < n_frames; t0 += G) {
         const long long t1 = std::min<long long>(n_frames, t0 + G), n = t1 - t0;
@@ -404,18 +383,14 @@ extern "C" int papof_super_resolve_tensor(papof_handle* h, int n_frames, int hei
         a.t0 = q.t0 = p.t0 = t0;
         a.t1 = t1;
         PAPOF_HIP(hipMemsetAsync(workspace, 0, (size_t)(n * 8 * (c + 1) * plane), st));
-        PAPOF_TRY(launch_tiles(src_tiles, s1 - s0, [&](dim3 grid, long long tile0, long long f0) {
-            hipLaunchKernelGGL(k_acc, grid, dim3(kInterpTX, kInterpTY), 0, st, a, tile0, s0 + f0);
+        PAPOF_TRY(launch_tiles(InterpTile::count(height, width), s1 - s0, [&](dim3 grid, long long tile0, long long f0) {
+            hipLaunchKernelGGL(k_acc, grid, InterpTile::block(), 0, st, a, tile0, s0 + f0);  // (source frames s0 ..)
         }));
-        PAPOF_TRY(launch_tiles(fine_tiles, n, [&](dim3 grid, long long tile0, long long f0) {
-            hipLaunchKernelGGL(k_res, grid, dim3(kInterpTX, kInterpTY), 0, st, q, tile0, f0);
-        }));
+        PAPOF_TRY(launch_grid<InterpTile>(FH, FW, n, st, 0, k_res, q));
         for (int it = 0; it < iters; it++) {
             p.Xin = it % 2 ? X1 : X0;
             p.Xout = it == iters - 1 ? nullptr : (it % 2 ? X0 : X1);
-            PAPOF_TRY(launch_tiles(low_tiles, n, [&](dim3 grid, long long tile0, long long f0) {
-                hipLaunchKernelGGL(k_back, grid, dim3(256), 0, st, p, tile0, f0);
-            }));
+            PAPOF_TRY(launch_grid<LowTile>(height, width, n, st, 0, k_back, p));
         }
     }
     return PAPOF_OK;

@@ -150,6 +150,7 @@ auto metrics_kernel(int c) {
 }
 
 constexpr int kWeaveTX = 64, kWeaveTY = 4;  // a 64 x 4 tile of field pixels per block (256 lanes: lut)
+using WeaveTile = Tile<kWeaveTX, kWeaveTY>;
 
 struct WeaveArgs {
     papof_tensor fl;   // fields (field, row, column, channel)
@@ -158,17 +159,12 @@ struct WeaveArgs {
     int Hf, W, C;
 };
 
-// blockIdx.x: tile `tile0` + x of the field's 64 x 4 tiles in row-major order; blockIdx.y: frame `frame0` + y.
+// grid.h's grid over the field's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD>
 __global__ __launch_bounds__(kWeaveTX* kWeaveTY) void k_weave_fields(const WeaveArgs a, long long tile0, long long frame0) {
     __shared__ double lut[256];
-    if (FD == PAPOF_DTYPE_U8) {
-        fill_u8_lut(lut, threadIdx.y * kWeaveTX + threadIdx.x);  // (256 lanes: one quotient each)
-        __syncthreads();
-    }
-    const long long tx = (a.W + kWeaveTX - 1) / kWeaveTX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kWeaveTX + (int)threadIdx.x;
-    const long long j = (tile / tx) * kWeaveTY + threadIdx.y;
+    stage_u8_lut<FD, kWeaveTX>(lut);
+    PAPOF_TILE_PIXEL(WeaveTile, tile0, a.W, int, x, long long, j);
     if (x >= a.W || j >= a.Hf) return;
     const long long n = frame0 + blockIdx.y;
     const long long pix = j * a.fl.stride[1] + x * a.fl.stride[2];
@@ -196,8 +192,7 @@ extern "C" int papof_field_metrics_tensor(papof_handle* h, int n_fields, int fie
         return PAPOF_EINVAL;
     if ((first != 0 && first != 1) || cell_rows < 1 || cell_rows > kMaxCellRows) return PAPOF_EINVAL;
     if (comb_q < 0 || comb_q > kMaxQ || diff_q < 0 || diff_q > kMaxQ || !metrics) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(fields, I, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
+    if (!in_frames(fields)) return PAPOF_EINVAL;
     MetricArgs a{};
     a.fl = *fields;
     a.out = metrics;
@@ -218,10 +213,7 @@ extern "C" int papof_field_metrics_tensor(papof_handle* h, int n_fields, int fie
                         : a.fl.dtype == PAPOF_DTYPE_U8    ? metrics_kernel<PAPOF_DTYPE_U8, false>(c)
                         : a.fl.dtype == PAPOF_DTYPE_F32   ? metrics_kernel<PAPOF_DTYPE_F32, false>(c)
                                                           : metrics_kernel<PAPOF_DTYPE_F64, false>(c);
-    const long long tiles = (long long)a.Gy * ((a.Gx + kCellsX - 1) / kCellsX);
-    return launch_tiles(tiles, a.T, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kCellW, kCellsX), 0, static_cast<hipStream_t>(stream), a, t0, f0);
-    });
+    return launch_grid<CellTile>(a.Gy, a.Gx, a.T, static_cast<hipStream_t>(stream), 0, kernel, a);
 }
 
 extern "C" int papof_weave_fields_tensor(papof_handle* h, int n_fields, int field_height, int width, int c,
@@ -230,8 +222,7 @@ extern "C" int papof_weave_fields_tensor(papof_handle* h, int n_fields, int fiel
     if (!h || n_fields < 1 || field_height < 1 || field_height > 0x3fffffff || width < 1 || c < 1 || c > kMaxC)
         return PAPOF_EINVAL;
     if (n_frames < 1 || !table) return PAPOF_EINVAL;
-    const auto I = {(int)PAPOF_DTYPE_U8, (int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(fields, I, {0, 1, 2, 3}, false) || !described(video, I, {0, 1, 2, 3}, true)) return PAPOF_EINVAL;
+    if (!in_frames(fields) || !out_frames(video)) return PAPOF_EINVAL;
     if (video->data == fields->data) return PAPOF_EINVAL;
     WeaveArgs a{};
     a.fl = *fields;
@@ -241,11 +232,6 @@ extern "C" int papof_weave_fields_tensor(papof_handle* h, int n_fields, int fiel
     a.W = width;
     a.C = c;
     PAPOF_HIP(hipSetDevice(h->device));
-    const auto kernel = a.fl.dtype == PAPOF_DTYPE_U8    ? k_weave_fields<PAPOF_DTYPE_U8>
-                        : a.fl.dtype == PAPOF_DTYPE_F32 ? k_weave_fields<PAPOF_DTYPE_F32>
-                                                        : k_weave_fields<PAPOF_DTYPE_F64>;
-    const long long tiles = ((a.W + kWeaveTX - 1) / (long long)kWeaveTX) * ((a.Hf + kWeaveTY - 1) / (long long)kWeaveTY);
-    return launch_tiles(tiles, n_frames, [&](dim3 grid, long long t0, long long f0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kWeaveTX, kWeaveTY), 0, static_cast<hipStream_t>(stream), a, t0, f0);
-    });
+    const auto kernel = by_dtype(a.fl.dtype, [](auto fd) { return k_weave_fields<fd()>; });
+    return launch_grid<WeaveTile>(a.Hf, a.W, n_frames, static_cast<hipStream_t>(stream), 0, kernel, a);
 }

@@ -101,11 +101,10 @@ __global__ __launch_bounds__(256) void k_track(const TrackArgs a, long long firs
 int launch_track(hipStream_t st, const TrackArgs& a, bool dense) {
     if (dense) {
         const long long tx = (a.W + kTrackTX - 1) / kTrackTX, ty = (a.H + kTrackTY - 1) / kTrackTY;
-        for (long long y0 = 0; y0 < ty; y0 += kMaxFrames) {  // (tile rows along gridDim.y: sampler.h's bound)
-            const unsigned rows = (unsigned)std::min(kMaxFrames, ty - y0);
-            hipLaunchKernelGGL(k_track<true>, dim3((unsigned)tx, rows), dim3(kTrackTX, kTrackTY), 0, st, a, y0);
-            PAPOF_HIP(hipGetLastError());
-        }
+        // (tile columns along gridDim.x, tile rows as grid.h's items along gridDim.y, split at its bound)
+        PAPOF_TRY(launch_tiles(tx, ty, [&](dim3 grid, long long, long long y0) {
+            hipLaunchKernelGGL(k_track<true>, grid, dim3(kTrackTX, kTrackTY), 0, st, a, y0);
+        }));
     } else {
         const long long blocks = (a.n + kTrackQ - 1) / kTrackQ;
         for (long long b0 = 0; b0 < blocks; b0 += kMaxQueryBlocks) {
@@ -128,9 +127,8 @@ extern "C" int papof_track_tensor(papof_handle* h, int n_frames, int height, int
                                   double alpha1, double alpha2, const papof_tensor* tracks, const papof_tensor* visible,
                                   void* stream) {
     if (!h || n_frames < 2 || height < 1 || width < 1) return PAPOF_EINVAL;
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    if (!described(flow_fw, F, {0, 1, 2, 3}, false) || !described(flow_bw, F, {0, 1, 2, 3}, false)) return PAPOF_EINVAL;
-    if (queries && (n_queries < 1 || !described(queries, F, {0, 3}, false))) return PAPOF_EINVAL;
+    if (!in_flow_pair(flow_fw, flow_bw)) return PAPOF_EINVAL;
+    if (queries && (n_queries < 1 || !described(queries, kFlowDtypes, {0, 3}, false))) return PAPOF_EINVAL;
     if (!described(tracks, {PAPOF_DTYPE_F64}, {0, 1, 3}, true) || !described(visible, {PAPOF_DTYPE_U8}, {0, 1}, true))
         return PAPOF_EINVAL;
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;

@@ -12,7 +12,7 @@
 // order without contraction, so the result is a pure function of the inputs.
 //
 // Mapping.  k_decimate: one lane per low-resolution pixel on a 64 x 4 tile, a loop over the channels and the block.
-// k_upsample_flow: a block is a 32 x 8 tile of OUTPUT pixels (blockIdx.x the tile, blockIdx.y the item), one lane per pixel.
+// k_upsample_flow: a block is a 32 x 8 tile of OUTPUT pixels (grid.h's grid of tiles and items), one lane per pixel.
 // The low-resolution window of the tile -- at most 31 / f + 2 + 2 r by 7 / f + 2 + 2 r cells -- is staged once in LDS: both
 // flow components and the decimated guide as float64, a dead byte folding "outside / occluded / not finite", the two tables
 // and the 256 quotients of a uint8 sample.  A lane then reads its own guide pixel from global memory, loops over the taps
@@ -30,6 +30,8 @@ namespace {
 
 constexpr int kTX = 32, kTY = 8;   // k_upsample_flow's tile of output pixels (256 lanes: lut)
 constexpr int kDX = 64, kDY = 4;   // k_decimate's tile of low-resolution pixels
+using OutTile = Tile<kTX, kTY>;
+using LowTile = Tile<kDX, kDY>;
 constexpr int kMaxRadius = 3;
 constexpr int kBins = 1024;        // the range table's bins
 constexpr double kHalo = 1.0 / 16; // the Gaussian's share of a spatial weight; the tent has the rest
@@ -40,13 +42,11 @@ struct DecimateArgs {
     int H, W, C, f, h, w;
 };
 
-// blockIdx.x: tile `tile0` + x of the low-resolution frame's 64 x 4 tiles in row-major order; blockIdx.y: item `item0` + y.
+// grid.h's grid over the low-resolution frame's 64 x 4 tiles; blockIdx.y: item `item0` + y.
 __global__ __launch_bounds__(kDX* kDY) void k_decimate(const DecimateArgs a, long long tile0, long long item0) {
     __shared__ double lut[256];
-    fill_u8_lut(lut, (int)(threadIdx.y * kDX + threadIdx.x));
-    __syncthreads();
-    const long long tx = (a.w + kDX - 1) / kDX, tile = tile0 + blockIdx.x;
-    const int x = (int)(tile % tx) * kDX + (int)threadIdx.x, y = (int)(tile / tx) * kDY + (int)threadIdx.y;
+    stage_u8_lut<-1, kDX>(lut);  // (the input's dtype is read from its descriptor)
+    PAPOF_TILE_PIXEL(LowTile, tile0, a.w, int, x, int, y);
     if (x >= a.w || y >= a.h) return;
     const long long i = item0 + blockIdx.y;
     const int f = a.f, Y0 = y * f, X0 = x * f;
@@ -83,15 +83,14 @@ long long lds_bytes(int C, int f, int r) {
     return cells * (16 + 8LL * C) + 256 * 8 + kBins * 4 + f * f * side * side * 4 + ((cells + 15) & ~15LL);
 }
 
-// GD: the guide's dtype.  blockIdx.x: tile `tile0` + x of the output's 32 x 8 tiles in row-major order; blockIdx.y: item
+// GD: the guide's dtype.  grid.h's grid over the output's 32 x 8 tiles; blockIdx.y: item
 // `item0` + y.
 template <int GD>
 __global__ __launch_bounds__(kTX* kTY) void k_upsample_flow(const UpsampleArgs a, long long tile0, long long item0) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int r = a.r, C = a.C, f = a.f, side = 2 * r + 1, taps = side * side;
     const int tid = threadIdx.y * kTX + threadIdx.x;
-    const long long tx = (a.W + kTX - 1) / kTX, tile = tile0 + blockIdx.x;
-    const int x0 = (int)(tile % tx) * kTX, y0 = (int)(tile / tx) * kTY;
+    PAPOF_TILE_ORIGIN(OutTile, tile0, a.W, int, x0, int, y0);
     const long long i = item0 + blockIdx.y;
     // the window: the cells of the tile's pixels and r around them
     const int ox = x0 / f - r, oy = y0 / f - r;
@@ -193,10 +192,7 @@ using namespace papof;
 extern "C" int papof_decimate_tensor(papof_handle* h, int n, int height, int width, int c, int factor,
                                      const papof_tensor* frames, const papof_tensor* out, void* stream) {
     if (!h || !valid_sizes(n, height, width, c, factor)) return PAPOF_EINVAL;
-    const auto all = {0, 1, 2, 3};
-    if (!described(frames, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, false) ||
-        !described(out, {PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, true))
-        return PAPOF_EINVAL;
+    if (!in_frames(frames) || !out_flow(out)) return PAPOF_EINVAL;
     DecimateArgs a{};
     a.in = *frames;
     a.out = *out;
@@ -207,11 +203,8 @@ extern "C" int papof_decimate_tensor(papof_handle* h, int n, int height, int wid
     a.h = (height + factor - 1) / factor;
     a.w = (width + factor - 1) / factor;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const long long tiles = ((a.w + kDX - 1) / (long long)kDX) * ((a.h + kDY - 1) / (long long)kDY);
     PAPOF_HIP(hipSetDevice(h->device));
-    return launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(k_decimate, grid, dim3(kDX, kDY), 0, st, a, t0, i0);
-    });
+    return launch_grid<LowTile>(a.h, a.w, n, st, 0, k_decimate, a);
 }
 
 extern "C" int papof_upsample_tables(int factor, int radius, double sigma_s, unsigned* S, unsigned* R) {
@@ -239,12 +232,8 @@ extern "C" int papof_upsample_flow_tensor(papof_handle* h, int n, int height, in
                                           const papof_tensor* occlusion, int radius, const unsigned* S, const unsigned* R,
                                           double q, const papof_tensor* out, void* stream) {
     if (!h || !valid_sizes(n, height, width, c, factor) || radius < 0 || radius > kMaxRadius) return PAPOF_EINVAL;
-    const auto F = {(int)PAPOF_DTYPE_F32, (int)PAPOF_DTYPE_F64};
-    const auto all = {0, 1, 2, 3};
-    if (!described(flow_lr, F, all, false) || !described(guide, {PAPOF_DTYPE_U8, PAPOF_DTYPE_F32, PAPOF_DTYPE_F64}, all, false) ||
-        !described(guide_lr, F, all, false) || !described(out, F, all, true))
-        return PAPOF_EINVAL;
-    if (occlusion && !described(occlusion, {PAPOF_DTYPE_U8}, {0, 1, 2}, false)) return PAPOF_EINVAL;
+    if (!in_flow(flow_lr) || !in_frames(guide) || !in_flow(guide_lr) || !out_flow(out)) return PAPOF_EINVAL;
+    if (!opt_in_mask(occlusion)) return PAPOF_EINVAL;
     if (!S || !R || !std::isfinite(q) || q < 0) return PAPOF_EINVAL;
     UpsampleArgs a{};
     a.flow = *flow_lr;
@@ -264,13 +253,8 @@ extern "C" int papof_upsample_flow_tensor(papof_handle* h, int n, int height, in
     a.w = (width + factor - 1) / factor;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int gd = guide->dtype;
-    const auto kernel = gd == PAPOF_DTYPE_U8    ? k_upsample_flow<PAPOF_DTYPE_U8>
-                        : gd == PAPOF_DTYPE_F32 ? k_upsample_flow<PAPOF_DTYPE_F32>
-                                                : k_upsample_flow<PAPOF_DTYPE_F64>;
+    const auto kernel = by_dtype(gd, [](auto fd) { return k_upsample_flow<fd()>; });
     const size_t lds = (size_t)lds_bytes(c, factor, radius);
-    const long long tiles = ((width + kTX - 1) / (long long)kTX) * ((height + kTY - 1) / (long long)kTY);
     PAPOF_HIP(hipSetDevice(h->device));
-    return launch_tiles(tiles, n, [&](dim3 grid, long long t0, long long i0) {
-        hipLaunchKernelGGL(kernel, grid, dim3(kTX, kTY), lds, st, a, t0, i0);
-    });
+    return launch_grid<OutTile>(height, width, n, st, lds, kernel, a);
 }

@@ -2,7 +2,7 @@
 tests/test_seam_cpu.py).
 
 The device-tensor kernels are launched through splitters that cut the work at the grid's bounds and hand each launch the index
-at which it starts: launch_tiles (csrc/sampler.h) at 65535 items along gridDim.y, fb_check (csrc/kernels.hip) at 32767 pairs
+at which it starts: launch_tiles (csrc/grid.h) at 65535 items along gridDim.y, fb_check (csrc/kernels.hip) at 32767 pairs
 with shifted data pointers, launch_track (csrc/track.hip) at 65535 rows of tiles.  A second launch that forgets its start index
 in one operand computes item 0's result for the first item beyond the cut.  To see that, the first item of a second launch
 must differ from item 0 in every operand, and every one of the N items must be checked.
