@@ -376,6 +376,14 @@ int papof_flow_batch_u8(papof_handle* h, int n_pairs, int sequence, const unsign
                         int width, int c, int pyramid_levels, const papof_params* params, double* const* vx,
                         double* const* vy, double* const* warpI2, double timing_sec[PAPOF_N_TIMERS]);
 
+/* Which way the frame pairs of papof_flow_batch* (host frames and device tensors alike) went, cumulative over the handle's
+ * life: out[0] = launch chains run, out[1] = solver pairs run inside them (a forward-backward call's frame pair is two),
+ * out[2] = frame pairs run as single calls because the batched chain does not cover them (see above; a batch or a remainder
+ * of one pair) or had no room for them, out[3] = frame pairs run again as single calls because their Laplacian-noise guard
+ * was left unproven in the chain (forward-backward: once per frame pair, whichever direction lacked the proof).  Results do
+ * not depend on the way taken; a test that compares the batch with the single calls reads here that the chain ran. */
+int papof_batch_stats(papof_handle* h, long long out[4]);
+
 /* Strided 4-D device tensors (PyTorch's, or anyone's): element type and the distance, in ELEMENTS, between neighbours along
  * the logical axes (frame or pair, row, column, channel or component).  NCHW and NHWC are different strides of the same
  * description; a zero stride repeats an element (an expanded tensor). */

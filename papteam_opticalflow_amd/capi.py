@@ -65,7 +65,7 @@ SYMBOLS = [
     "papof_pyramid_levels_for_min_width", "papof_stage_smoothflow_ex", "papof_stage_est_gaussian_mixture",
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
     "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
-    "papof_flow_batch", "papof_flow_batch_u8", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
+    "papof_flow_batch", "papof_flow_batch_u8", "papof_batch_stats", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
     "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
     "papof_flow_batch_tensor_fb_init", "papof_motion_fit_tensor", "papof_motion_workspace", "papof_warp_affine_tensor",
     "papof_temporal_filter_tensor", "papof_fill_holes_tensor", "papof_fill_workspace", "papof_propagate_tensor",
@@ -179,6 +179,7 @@ def load():
                                         ctypes.POINTER(ctypes.c_double)]
     L.papof_lap_guard_stats.argtypes = [c_void_p, ctypes.POINTER(c_int)]
     L.papof_last_host_times.argtypes = [c_void_p, ctypes.POINTER(c_double)]
+    L.papof_batch_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     for fn in (L.papof_flow_batch, L.papof_flow_batch_u8):
         fn.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _D]
         fn.restype = c_int
@@ -445,6 +446,16 @@ def _u8(a):
     if a.dtype != np.uint8 or a.ndim != 3:
         raise ValueError("expected a uint8 H x W x C array, got %s %r" % (a.dtype, a.shape))
     return a
+
+
+def batch_frames_are_u8(frames):
+    """True for frames that are all uint8, False for frames that are all floating; ValueError for anything else -- a uint8 frame
+    among float64 ones would enter as 0..255, without papof_flow_batch_u8's division by 255"""
+    kinds = {"u8" if d == np.uint8 else "f" if d.kind == "f" else str(d)
+             for d in ([frames.dtype] if isinstance(frames, np.ndarray) else [np.asarray(f).dtype for f in frames])}
+    if kinds != {"u8"} and kinds != {"f"}:
+        raise ValueError("the frames of a batch must be all uint8 or all floating, got %s" % sorted(kinds))
+    return kinds == {"u8"}
 
 
 def _chk(rc, what):
@@ -780,7 +791,7 @@ class Papof:
         all float64 in [0, 1] or all uint8; sequence=True: pair i = (frames[i], frames[i + 1]); False: (frames[2i], frames[2i+1]).
         Returns [(vx, vy, warpI2), ...] per pair (out: a list of such triples to be reused) and the ten timers of the batch.
         Every pair's arrays are bit-identical to coarse2fine_flow(pair)."""
-        u8 = np.asarray(frames[0]).dtype == np.uint8
+        u8 = batch_frames_are_u8(frames)
         if isinstance(frames, np.ndarray) and frames.ndim == 4 and frames.flags["C_CONTIGUOUS"]:
             fr = frames if u8 else np.ascontiguousarray(frames, dtype=np.float64)
         else:
@@ -805,6 +816,14 @@ class Papof:
         fn = self.L.papof_flow_batch_u8 if u8 else self.L.papof_flow_batch
         _chk(fn(self.h, n_pairs, 1 if sequence else 0, fp, h, w, c, int(levels), pp, ox, oy, ow, _p(t)), "papof_flow_batch")
         return out, t
+
+    def batch_stats(self):
+        """dict(chains, chain_pairs, singles, reruns), cumulative: launch chains run by flow_batch and the tensor calls, solver
+        pairs inside them, frame pairs run singly outside the chain, frame pairs re-run singly for an unproven guard
+        (include/papof.h: papof_batch_stats)"""
+        out = (ctypes.c_longlong * 4)()
+        _chk(self.L.papof_batch_stats(self.h, out), "papof_batch_stats")
+        return dict(chains=out[0], chain_pairs=out[1], singles=out[2], reruns=out[3])
 
     def last_host_times(self):
         """(enqueue_sec, wait_sec) of the last call on this handle: host wall time spent enqueueing / waiting for the streams"""

@@ -96,6 +96,7 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
     const double ratio = cp.ratio;
     const int fstep = sequence ? 1 : 2, nF = sequence ? B + 1 : 2 * B;
     const int NP = with_bw ? 2 * B : B;  // solver pairs: per-pair arrays, operands, witness blocks
+    if (NP < 2) return PAPOF_EINVAL;     // the pair-to-pair strides below are read off pairs 0 and 1: a lone pair is the single call's
     const int fc = cp.fc, n_sor_max = cp.n_sor_max;
     const size_t np0 = (size_t)H * W;
     const bool guard = h->lap_guard && h->lap_flags_dev != nullptr;
@@ -302,7 +303,8 @@ int flow_batch_device(papof_handle* h, int B, int sequence, bool with_bw, const 
             const int f1 = (back ? p - B : p) * fstep, fa = back ? f1 + 1 : f1, fb = back ? f1 : f1 + 1;
             for (int s = 0; s + 1 < slot && open; s++)  // the estimate behind the call's last update is never consulted
                 for (int c = 0; c < fc; c++) {
-                    const size_t nzw = (size_t)slot_level[s] * 8 + c;
+                    // (beyond kLapNzWords / 8 levels there are no non-zero flags, and no words to read them from)
+                    const size_t nzw = nz_known ? (size_t)slot_level[s] * 8 + c : 0;
                     if (!lap_proven(hw[(size_t)p * kLapFlagWords + lap_wit_word(s) + c], epoch, nz_known,
                                     hn[(size_t)fa * kLapNzWords + nzw], hn[(size_t)fb * kLapNzWords + nzw]))
                         open = false;
@@ -344,6 +346,7 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
         return rc;
     };
     const auto all_single = [&]() -> int {  // the pairs one after the other
+        h->batch_singles += n_pairs;
         for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
         if (timing_sec) std::memcpy(timing_sec, tm, sizeof tm);
         return PAPOF_OK;
@@ -378,6 +381,8 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
             return all_single();
         }
         PAPOF_TRY(rc);
+        h->batch_chains++;
+        h->batch_chain_pairs += n_pairs;
     }
     const size_t np0 = (size_t)H * W;
     // Result arrays laid out as the device's ([pair][vx, vy][H x W] and [pair][H x W x c] in one block each -- what the Python
@@ -400,6 +405,7 @@ int flow_batch_host(papof_handle* h, int n_pairs, int sequence, const void* cons
     PAPOF_HIP(hipStreamSynchronize(h->stream));
     for (int p : out.unproven) {
         h->lap_reruns++;
+        h->batch_reruns++;
         PAPOF_TRY(single(p));
     }
     tm[PAPOF_T_TOTAL] = now_sec() - t0;  // the caller's view: uploads, the launch chain, downloads, re-runs
@@ -512,6 +518,7 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         return PAPOF_OK;
     };
     if (!batch_applies(h, n_pairs, H, W, C, levels, P)) {
+        h->batch_singles += n_pairs;
         for (int p = 0; p < n_pairs; p++) PAPOF_TRY(single(p));
         return PAPOF_OK;
     }
@@ -519,6 +526,12 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
     for (int p0 = 0; p0 < n_pairs;) {
         int nb = std::min(max_b, n_pairs - p0);
         if (n_pairs - (p0 + nb) == 1 && nb > 2) nb -= 1;  // leave two pairs for the last sub-batch rather than one
+        if (nb == 1 && !with_bw) {  // a bound of two leaves an odd collection's last pair alone: the single call, as the host entry's
+            h->batch_singles++;
+            PAPOF_TRY(single(p0));
+            p0 += 1;
+            continue;
+        }
         const papof_tensor a = shifted(fa, p0), b = sequence ? a : shifted(*fb, p0);
         BatchFrames bf;
         bf.a = &a;
@@ -530,17 +543,21 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
         double t1[PAPOF_N_TIMERS];
         const int rc = flow_batch_device(h, nb, sequence, with_bw, bf, H, W, C, levels, P, t1, out);
         if (rc == PAPOF_ENOMEM) {  // no room for the arrays of a batch on this device: the pairs one after the other
+            h->batch_singles += nb;
             for (int p = p0; p < p0 + nb; p++) PAPOF_TRY(single(p));
             p0 += nb;
             continue;
         }
         PAPOF_TRY(rc);
+        h->batch_chains++;
+        h->batch_chain_pairs += with_bw ? 2 * nb : nb;
         for (int i = 0; i < PAPOF_N_TIMERS; i++) tm[i] += t1[i];
         PAPOF_TRY(emit_outputs(h, out.uv, shifted(*o.flow, p0), true, H, W, 2, nb));
         PAPOF_TRY(emit_outputs(h, out.warp, shifted(*o.warp, p0), false, H, W, C, nb));
         if (!with_bw) {
             for (int p : out.unproven) {
                 h->lap_reruns++;
+                h->batch_reruns++;
                 PAPOF_TRY(single(p0 + p));
             }
             p0 += nb;
@@ -560,7 +577,10 @@ int flow_batch_tensor(papof_handle* h, int n_pairs, int sequence, const papof_te
             redo[p < nb ? p : p - nb] = 1;
         }
         for (int q = 0; q < nb; q++)
-            if (redo[q]) PAPOF_TRY(single(p0 + q));
+            if (redo[q]) {
+                h->batch_reruns++;  // frame pairs, whichever of the two directions lacked its proof
+                PAPOF_TRY(single(p0 + q));
+            }
         p0 += nb;
     }
     return PAPOF_OK;
@@ -674,6 +694,15 @@ int papof_flow_batch_tensor_fb_init(papof_handle* h, int n_pairs, int sequence, 
                       .a2 = alpha2};
     return tensor_entry(h, n_pairs, sequence, frames, frames2, height, width, c, pyramid_levels, params, o, stream, timing_sec,
                         TensorInit{.fw = init_fw, .bw = init_bw});
+}
+
+int papof_batch_stats(papof_handle* h, long long out[4]) {
+    if (!h || !out) return PAPOF_EINVAL;
+    out[0] = h->batch_chains;
+    out[1] = h->batch_chain_pairs;
+    out[2] = h->batch_singles;
+    out[3] = h->batch_reruns;
+    return PAPOF_OK;
 }
 
 int papof_fb_check_tensor(papof_handle* h, int n_pairs, int height, int width, const papof_tensor* flow_fw,

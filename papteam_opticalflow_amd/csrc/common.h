@@ -271,6 +271,9 @@ struct papof_handle {
     bool lap_exact = false;    // the next call starts in the exact pass (its predecessor ended with a channel lacking a proof)
     unsigned lap_epoch = 0;    // a flag is SET when it holds the number of the pass that wrote it: nothing is ever cleared
     int lap_reruns = 0, lap_exact_calls = 0;  // statistics (papof_lap_guard_stats)
+    // which way the pairs of papof_flow_batch* went (papof_batch_stats): launch chains, solver pairs inside them, frame pairs run
+    // singly because the chain does not cover them or had no room, frame pairs run again singly for an unproven guard
+    long long batch_chains = 0, batch_chain_pairs = 0, batch_singles = 0, batch_reruns = 0;
     double host_enqueue_sec = 0.0, host_wait_sec = 0.0;  // host wall time of the last call: enqueueing / waiting (papof_last_host_times)
     // Host buffers handed to the call itself (flow_host -> flow_device): the call then issues the PCIe copies where they
     // overlap device work -- frame 2 uploads while frame 1's share of the preparation runs, (vx, vy) go back beside the

@@ -94,6 +94,8 @@ def test_collection_in_flight_policy_and_setter_arguments(lib):
     assert lib.papof_set_stream_overlap(None, 0) == capi.EINVAL if hasattr(capi, "EINVAL") else lib.papof_set_stream_overlap(None, 0) != 0
     out = (capi.c_int * 4)()
     assert lib.papof_lap_guard_stats(None, out) != 0
+    import ctypes
+    assert lib.papof_batch_stats(None, (ctypes.c_longlong * 4)()) != 0
 
 
 def test_rccl_standin_builds_loads_and_exports_the_api_the_transport_binds():
