@@ -51,10 +51,10 @@ size_t arena_bytes_for(int H, int W, int C, int levels, int n_sor_max, double ra
     size_t planes = 0;
     planes += (size_t)2 * C * 5;           // two pyramids: sum of ratio^(2i) < 2.3 for ratio<=.75; 5 is safe to .98
     if (levels > 8) planes += (size_t)2 * C * levels;  // (ratio .98 decays slowly: bound by level count)
-    planes += (size_t)2 * C + 2 * C;       // staging of the interleaved inputs + pyramid temporaries
+    planes += (size_t)2 * C + 2 * C;       // staging of the interleaved inputs + pyramid temporaries (half-widths beyond 4 only)
     planes += (size_t)7 * fc;              // F1, F2, warp, F1 smoothed, h-pass temp, blend, imdt
     planes += 8;                           // u, v, resized u, v, phi + slack
-    planes += (size_t)3 * C + C;           // bicubic derivative planes + interleaved output
+    planes += (size_t)C;                   // interleaved output (the final bicubic warp takes its derivatives from frame 2)
     planes += (size_t)3 * fc;              // in-loop bicubic warping: derivative planes of the frame-2 features
     size_t bytes = planes * np * sizeof(double);
     bytes += 3 * (sor_cells + 2 * kLanes) * 16 + (sor_cells_d + 2 * kLanes) * 16 + 10 * np * sizeof(double);  // SOR operands
@@ -182,16 +182,33 @@ int fork_prep(papof_handle* h, int levels, bool overlap) {
     return PAPOF_OK;
 }
 
-// One pyramid level from its source level: GaussianSmoothing + imresize (src/GaussianPyramid.cpp:97-99, :103-105).  Both
-// filter passes are one launch; a half-width of 0 (level 1 at ratio 0.75: sigma * 3 truncates to 0) makes the
-// smoothing the identity -- a single tap of exactly 1.0 accumulated from 0.0 -- and the resize reads the source directly
-// (the resize accumulates from +0.0 as well, so not even the sign of a zero can differ).
+// One pyramid level from its source level: GaussianSmoothing + imresize (src/GaussianPyramid.cpp:97-99, :103-105), in ONE
+// launch for the half-widths 1 .. 4 (k_smooth_resize: the smoothed source is never written).  A half-width of 0 (level 1 at
+// ratio 0.75: sigma * 3 truncates to 0) makes the smoothing the identity -- a single tap of exactly 1.0
+// accumulated from 0.0 -- and the resize reads the source directly (the resize accumulates from +0.0 as well, so not even
+// the sign of a zero can differ).  Any other half-width: both filter passes into tmp_b (through tmp_a), then the resize.
+static bool level_is_resize_only(const Taps& g) { return g.fsize == 0 && g.t[0] == 1.0; }
+static bool level_is_fused(const Taps& g, const PyrPlan& p, int dh, int dw) {
+    return smooth_resize_fits(g, g, p.sh, p.sw, dh, dw, p.rate, p.rate);
+}
 int smooth_and_resize(papof_handle* h, const double* src, double* dst, double* tmp_a, double* tmp_b, const PyrPlan& p, int C,
                       int dh, int dw) {
     const Taps g = gaussian_taps(p.sigma, p.fsize);
-    if (g.fsize == 0 && g.t[0] == 1.0) return resize(h, src, dst, p.sh, p.sw, C, dh, dw, p.rate, p.rate, false, 0.0);
+    if (level_is_resize_only(g)) return resize(h, src, dst, p.sh, p.sw, C, dh, dw, p.rate, p.rate, false, 0.0);
+    if (level_is_fused(g, p, dh, dw)) return smooth_resize(h, src, dst, p.sh, p.sw, C, dh, dw, p.rate, p.rate, g, g);
     PAPOF_TRY(filter_hv(h, src, tmp_b, tmp_a, p.sh, p.sw, C, g, g));
     return resize(h, tmp_b, dst, p.sh, p.sw, C, dh, dw, p.rate, p.rate, false, 0.0);
+}
+// elements of EACH of smooth_and_resize()'s two temporaries for one plane-set of C planes: the largest source of a level that
+// takes neither the fused kernel nor the resize alone (0 for every plan up to half-width 4, the default's among them)
+size_t pyramid_tmp_elems(const std::vector<Level>& L, const std::vector<PyrPlan>& plan, int C) {
+    size_t n = 0;
+    for (size_t i = 1; i < L.size(); i++) {
+        const Taps g = gaussian_taps(plan[i].sigma, plan[i].fsize);
+        if (!level_is_resize_only(g) && !level_is_fused(g, plan[i], L[i].h, L[i].w))
+            n = std::max(n, (size_t)plan[i].sw * plan[i].sh * C);
+    }
+    return n;
 }
 
 // The caller's initial flow at the coarsest level (include/papof.h, papof_flow_batch_tensor_init: the rule).  Pairs 0 ..
@@ -538,8 +555,7 @@ struct FlowPass {
     // -- the arena, in allocation order
     double *tmp_a = nullptr, *tmp_b = nullptr;  // the pyramid's filter temporaries
     std::vector<double*> F1, F2, S1;            // per level: the features of both frames, the smoothed features of frame 1
-    double *gx = nullptr, *gy = nullptr, *gxy = nullptr;  // frame 2's central differences for the final warp (src/Image.h:2590-2594)
-    double *prep_tmp = nullptr, *warp = nullptr;  // (prep_tmp is allocated ahead of gx)
+    double *prep_tmp = nullptr, *warp = nullptr;
     // the flow lives in two PAIRS of planes (the update of an outer iteration writes the other pair); within a pair v follows
     // u at the pitch of the level in work, so that the up-sampling of (u, v) is one launch and their first clear one fill
     double *u = nullptr, *v = nullptr, *u2 = nullptr, *v2 = nullptr;
@@ -585,9 +601,9 @@ static int carve_pyramids(FlowPass& S) {
         l.p1 = slot[S.slot1];
         l.p2 = slot[S.slot1 ^ 1];
     }
-    const size_t np0 = (size_t)S.H * S.W;
-    S.tmp_a = A.f64(np0 * S.C);
-    S.tmp_b = A.f64(np0 * S.C);
+    const size_t tmp = pyramid_tmp_elems(S.cp.L, S.cp.plan, S.C);  // (nothing where every level is one launch)
+    S.tmp_a = A.f64(tmp);
+    S.tmp_b = A.f64(tmp);
     return A.overflow ? PAPOF_ENOMEM : PAPOF_OK;
 }
 
@@ -607,9 +623,6 @@ static int carve_buffers(FlowPass& S) {
         S.S1[k] = A.f64(n);
     }
     S.prep_tmp = A.f64(np0 * fc);
-    S.gx = A.f64(np0 * S.C);
-    S.gy = A.f64(np0 * S.C);
-    S.gxy = A.f64(np0 * S.C);
     S.warp = A.f64(np0 * fc);
     S.u = A.f64(2 * np0);
     S.v = S.u ? S.u + np0 : nullptr;
@@ -680,11 +693,6 @@ static int prep_frames(FlowPass& S, int first, int last, bool chained, bool smoo
     }
     return PAPOF_OK;
 }
-static int prep_final_planes(FlowPass& S) {  // derivative planes of the final bicubic warp (src/Image.h:2590-2594)
-    S.pclk.phase(PAPOF_T_POSTPROCESSING);
-    PAPOF_TRY(central3_planes(S.h, S.cp.L[0].p2, S.gx, S.gy, S.gxy, S.H, S.W, S.C));
-    return prep_level_ready(S, S.cp.levels);
-}
 // a frame's upload on the copy stream, the preparation stream behind it (this call may hold the host until the bytes are staged)
 static int prep_upload(FlowPass& S, const void* host, const FrameIn& f, int event) {
     papof_handle* h = S.h;
@@ -715,7 +723,9 @@ static int prepare(FlowPass& S) {
         PAPOF_TRY(prep_upload(S, S.h->hostio.im2, S.fb, 1));  // beside the kernels just queued
         PAPOF_TRY(prep_frames(S, 1, 2, chained, false, true));
     }
-    return prep_final_planes(S);
+    // (nothing is prepared for the final warp: its derivatives, src/Image.h:2590-2594, are taken from frame 2 in k_bicubic_grad,
+    // and level 0's event has ordered frame 2 and every other preparation before it)
+    return PAPOF_OK;
 }
 
 static int fork_and_prepare(FlowPass& S) {
@@ -801,11 +811,9 @@ static int solve_levels(FlowPass& S) {
 static int final_warp(FlowPass& S) {
     papof_handle* h = S.h;
     papof_handle::HostIO& io = h->hostio;
-    const int H = S.H, W = S.W, C = S.C, levels = S.cp.levels;
+    const int H = S.H, W = S.W, C = S.C;
     const size_t np0 = (size_t)H * W;
     const Level& l0 = S.cp.L[0];
-    S.clk.phase(-1);
-    if (S.overlap) PAPOF_HIP(hipStreamWaitEvent(S.main_stream, h->sync_events[levels], 0));
     S.clk.phase(PAPOF_T_POSTPROCESSING);
     if (S.hostio && io.early_out && S.u == S.d_vx && S.v == S.d_vy) {
         // page-locked result arrays: (vx, vy) are final -- their copies run beside the bicubic warp -- and warpI2 follows
@@ -819,7 +827,7 @@ static int final_warp(FlowPass& S) {
         for (int q = 0; q < kChunks; q++) {
             const Rect rc{0, (int)((long long)H * q / kChunks), W, (int)((long long)H * (q + 1) / kChunks)};
             if (rc.empty()) continue;
-            PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, S.gx, S.gy, S.gxy, S.u, S.v, S.d_warp, H, W, C, &rc));
+            PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, nullptr, nullptr, nullptr, S.u, S.v, S.d_warp, H, W, C, &rc));
             PAPOF_HIP(hipEventRecord(h->copy_events[3 + q], S.main_stream));
             PAPOF_HIP(hipStreamWaitEvent(cs, h->copy_events[3 + q], 0));
             const size_t off = (size_t)rc.y0 * W * C, cnt = (size_t)rc.h() * W * C;
@@ -828,7 +836,7 @@ static int final_warp(FlowPass& S) {
         io.out_issued = true;
         return PAPOF_OK;
     }
-    PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, S.gx, S.gy, S.gxy, S.u, S.v, S.d_warp, H, W, C));
+    PAPOF_TRY(bicubic_warp(h, l0.p1, l0.p2, nullptr, nullptr, nullptr, S.u, S.v, S.d_warp, H, W, C));
     if (S.u != S.d_vx) PAPOF_HIP(hipMemcpyAsync(S.d_vx, S.u, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     if (S.v != S.d_vy) PAPOF_HIP(hipMemcpyAsync(S.d_vy, S.v, np0 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     return PAPOF_OK;
@@ -1835,17 +1843,16 @@ int papof_stage_bicubic_warp(papof_handle* h, const double* im1, const double* i
 int papof_stage_bicubic_warp_ex(papof_handle* h, const double* im1, const double* im2, const double* vx,
                                 const double* vy, int height, int width, int c, int clamp, double* out) {
     if (!h || !im1 || !im2 || !vx || !vy || !out || height < 1 || width < 1 || c < 1) return PAPOF_EINVAL;
-    Scope S(h, img_bytes(height, width, c, 10) + img_bytes(height, width, 1, 4));
+    Scope S(h, img_bytes(height, width, c, 7) + img_bytes(height, width, 1, 4));
     PAPOF_TRY(S.rc);
     const size_t n = (size_t)height * width * c;
     double* a = S.up_planar(im1, height, width, c);
     double* b = S.up_planar(im2, height, width, c);
     double* fx = S.up_planar(vx, height, width, 1);
     double* fy = S.up_planar(vy, height, width, 1);
-    double *gx = S.dev(n), *gy = S.dev(n), *gxy = S.dev(n), *o = S.dev(n);
+    double* o = S.dev(n);
     PAPOF_TRY(S.rc);
-    PAPOF_TRY(central3_planes(h, b, gx, gy, gxy, height, width, c));
-    PAPOF_TRY(bicubic_warp(h, a, b, gx, gy, gxy, fx, fy, o, height, width, c, nullptr, false, clamp != 0));
+    PAPOF_TRY(bicubic_warp(h, a, b, nullptr, nullptr, nullptr, fx, fy, o, height, width, c, nullptr, false, clamp != 0));
     PAPOF_HIP(hipMemcpyAsync(out, o, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     PAPOF_HIP(hipStreamSynchronize(h->stream));
     return PAPOF_OK;

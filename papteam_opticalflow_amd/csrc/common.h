@@ -377,6 +377,9 @@ int resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int 
            double yr, bool use_post, double post, const Rect* rc = nullptr);
 int im2feature(papof_handle* h, const double* im, double* feat, int H, int W, int C, unsigned* nz = nullptr, int frames = 1,
                size_t nz_stride = 0);  // frames > 1: contiguous frames of a batch (common.h: BatchK)
+bool smooth_resize_fits(const Taps& fh, const Taps& fv, int sh, int sw, int dh, int dw, double xr, double yr);
+int smooth_resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int planes, int dh, int dw, double xr,
+                  double yr, const Taps& fh, const Taps& fv);
 int central3_planes(papof_handle* h, const double* src, double* gx, double* gy, double* gxy, int H, int W, int planes);
 int warp_bilinear(papof_handle* h, const double* im1, const double* im2, const double* vx, const double* vy,
                   double* out, int H, int W, int planes, const Rect* rc = nullptr);
@@ -410,6 +413,7 @@ int gm_scratch_doubles();
 int est_gaussian_mixture(papof_handle* h, const double* im1, const double* im2, int H, int W, int C, double* gm,
                          double* scratch);
 int laplacian(papof_handle* h, const double* in, const double* weight, double* out, int H, int W);
+// gx, gy, gxy: image 2's planes of central3_planes(), or all NULL (a single call): the kernel takes them from image 2 itself
 int bicubic_warp(papof_handle* h, const double* im1, const double* im2, const double* gx, const double* gy,
                  const double* gxy, const double* vx, const double* vy, double* out_hwc, int H, int W, int C,
                  const Rect* rc = nullptr, bool planar_out = false, bool clamp = true, int batch = 1, const BatchK* bk = nullptr);

@@ -205,6 +205,7 @@ int check_params(const papof_params& P, int levels);
 int pyramid_plan(int H, int W, double ratio, int nlev, std::vector<Level>& L, std::vector<PyrPlan>& plan);
 int build_pyramid(papof_handle* h, const std::vector<Level>& L, const std::vector<PyrPlan>& plan, int C, bool second,
                   double* tmp_a, double* tmp_b);
+size_t pyramid_tmp_elems(const std::vector<Level>& L, const std::vector<PyrPlan>& plan, int C);  // of each of tmp_a, tmp_b
 int smooth_and_resize(papof_handle* h, const double* src, double* dst, double* tmp_a, double* tmp_b, const PyrPlan& p, int C,
                       int dh, int dw);  // one pyramid level from its source level; C may count the planes of SEVERAL contiguous frames
 int feature_channels(int C);

@@ -31,7 +31,7 @@ __device__ __forceinline__ void stamp_now(unsigned long long* s) {
 }
 __global__ void k_stamp(unsigned long long* s) { stamp_now(s); }
 
-__device__ __forceinline__ int clampi(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
+__host__ __device__ __forceinline__ int clampi(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
     x = x < 0 ? 0 : x;
     return x > n - 1 ? n - 1 : x;
 }
@@ -362,36 +362,54 @@ struct BilinearTaps {
     int o[4];     // plane offsets of the 4 taps in visiting order
     double s[4];  // their weights
 };
+struct BilinearAxis {
+    int c[2];  // the two cells along one axis, clamped
+    double d;  // the fraction, clamped to [0, 1]
+};
+
+__host__ __device__ __forceinline__ BilinearAxis bilinear_axis(int n, double x) {
+    BilinearAxis a;
+    const int xx = (int)x;
+    double dx = x - xx;
+    dx = dx > 1 ? 1.0 : dx;
+    dx = dx < 0 ? 0.0 : dx;
+    a.d = dx;
+    a.c[0] = clampi(xx, n);
+    a.c[1] = clampi(xx + 1, n);
+    return a;
+}
 
 __device__ __forceinline__ BilinearTaps bilinear_taps(int W, int H, double x, double y) {
     BilinearTaps b;
-    const int xx = (int)x, yy = (int)y;
-    double dx = x - xx, dy = y - yy;
-    dx = dx > 1 ? 1.0 : dx;
-    dx = dx < 0 ? 0.0 : dx;
-    dy = dy > 1 ? 1.0 : dy;
-    dy = dy < 0 ? 0.0 : dy;
+    const BilinearAxis ax = bilinear_axis(W, x), ay = bilinear_axis(H, y);
 #pragma unroll
     for (int m = 0; m <= 1; m++)
 #pragma unroll
         for (int n = 0; n <= 1; n++) {
-            const int u = clampi(xx + m, W), v = clampi(yy + n, H);
-            b.o[m * 2 + n] = v * W + u;
-            b.s[m * 2 + n] = fabs((double)(1 - m) - dx) * fabs((double)(1 - n) - dy);
+            b.o[m * 2 + n] = ay.c[n] * W + ax.c[m];
+            b.s[m * 2 + n] = fabs((double)(1 - m) - ax.d) * fabs((double)(1 - n) - ay.d);
         }
     return b;
 }
 
-__device__ __forceinline__ double bilinear_apply(const double* __restrict__ p, const BilinearTaps& b) {
+// the accumulate statement; at(t) is the operand of tap t = 2 m + n, the cell (x_m, y_n)
+template <class At>
+__device__ __forceinline__ double bilinear_sum(const BilinearTaps& b, At at) {
     double acc = 0.0;
 #pragma unroll
-    for (int t = 0; t < 4; t++) acc += p[b.o[t]] * b.s[t];
+    for (int t = 0; t < 4; t++) acc += at(t) * b.s[t];
     return acc;
+}
+__device__ __forceinline__ double bilinear_apply(const double* __restrict__ p, const BilinearTaps& b) {
+    return bilinear_sum(b, [&](int t) { return p[b.o[t]]; });
 }
 
 // ImageProcessing::ResizeImage, src/ImageProcessing.h:214-253 (both overloads: xr == yr for the ratio form).
 // Optional post-scale = Image::Multiplywith (src/Image.h:1841-1850) for the flow up-sampling of
 // src/OpticalFlow.cpp:809-812.
+// the position of level pixel j in its source, along one axis (:226-227)
+__host__ __device__ __forceinline__ double resize_pos(int j, double r) { return (double)(j + 1) / r - 1; }
+
 __global__ void k_resize(const double* __restrict__ src, double* __restrict__ dst, int sh, int sw, int dh, int dw,
                          double xr, double yr, int use_post, double post, Rect rc, unsigned long long* stamp) {
     stamp_now(stamp);
@@ -399,12 +417,73 @@ __global__ void k_resize(const double* __restrict__ src, double* __restrict__ ds
     if (!xcd_tile((rc.x1 - rc.x0 + BX - 1) / BX, (rc.y1 - rc.y0 + BY - 1) / BY, tbx, tby)) return;
     const int j = rc.x0 + tbx * BX + threadIdx.x, i = rc.y0 + tby * BY + threadIdx.y;
     if (j >= rc.x1 || i >= rc.y1) return;
-    const double x = (double)(j + 1) / xr - 1;
-    const double y = (double)(i + 1) / yr - 1;
-    const BilinearTaps b = bilinear_taps(sw, sh, x, y);
+    const BilinearTaps b = bilinear_taps(sw, sh, resize_pos(j, xr), resize_pos(i, yr));
     double r = bilinear_apply(src + blockIdx.z * (size_t)sh * sw, b);
     if (use_post) r *= post;
     dst[blockIdx.z * (size_t)dh * dw + (size_t)i * dw + j] = r;
+}
+
+// One pyramid level in ONE launch: k_filter_hv_staged<F> followed by k_resize, without the smoothed source plane between
+// them (a level keeps 10-32 % of its source's pixels: most of that plane was written, read back once and never sampled).
+// A block owns a kSrT x kSrT tile of level pixels of one plane.  The taps of its pixels lie in the source cells
+// [u_lo, u_hi] x [v_lo, v_hi] (bilinear_axis() is monotone in the pixel, so the tile's first and last pixel bound them);
+// that rectangle grown by F is staged in LDS by clamped row reads, the h pass runs on its rows at the 2 kSrT tap COLUMNS of
+// the tile only, and each pixel takes the v pass of its four taps out of LDS and blends them.  The smoothed value at the tap
+// (v, u) is tap_sum<F>(fv, l -> h[clamp(v + l)][u]) with h[r][u] = tap_sum<F>(fh, l -> src[r][clamp(u + l)]) -- the
+// operations and the order of the two kernels; a value two taps share is identified by its clamped row and column.
+// nx, ny: the LDS image's pitch and rows, the largest footprint of any tile (smooth_resize() below walks the same expressions).
+constexpr int kSrT = 16;
+template <int F>
+__global__ __launch_bounds__(256) void k_smooth_resize(const double* __restrict__ src, double* __restrict__ dst, int sh,
+                                                       int sw, int dh, int dw, double xr, double yr, Taps fh, Taps fv,
+                                                       int nx, int ny) {
+    extern __shared__ __align__(16) double sr_lds[];
+    int tx, ty;
+    if (!xcd_tile((dw + kSrT - 1) / kSrT, (dh + kSrT - 1) / kSrT, tx, ty)) return;  // whole workgroup, before any barrier
+    const int j0 = tx * kSrT, i0 = ty * kSrT;
+    const int j1 = min(j0 + kSrT, dw) - 1, i1 = min(i0 + kSrT, dh) - 1;  // the tile's last pixel
+    // the positions of the tile's kSrT columns and kSrT rows in the source: one division each, by 2 kSrT threads for all
+    // (a division per thread and use -- the corners, the h pass, the blend -- was most of the kernel's arithmetic)
+    __shared__ double pos[2][kSrT];
+    const int t = threadIdx.y * BX + threadIdx.x;
+    if (t < kSrT)
+        pos[0][t] = resize_pos(j0 + t, xr);
+    else if (t < 2 * kSrT)
+        pos[1][t - kSrT] = resize_pos(i0 + t - kSrT, yr);
+    __syncthreads();
+    const int u_lo = bilinear_axis(sw, pos[0][0]).c[0], u_hi = bilinear_axis(sw, pos[0][j1 - j0]).c[1];
+    const int v_lo = bilinear_axis(sh, pos[1][0]).c[0], v_hi = bilinear_axis(sh, pos[1][i1 - i0]).c[1];
+    const int nxa = u_hi - u_lo + 1 + 2 * F, nya = v_hi - v_lo + 1 + 2 * F;
+    if (nxa > nx || nya > ny) return;  // (never: nx, ny are the maxima of these; nothing is written outside the LDS image)
+    double* const raw = sr_lds;                  // [ny][nx]: source cell (clamp(v_lo - F + r), clamp(u_lo - F + c))
+    double* const hs = sr_lds + (size_t)ny * nx;  // [ny][2][kSrT]: the h pass at the tile's tap columns x_m of its pixels
+    const double* plane = src + blockIdx.z * (size_t)sh * sw;
+    for (int r = threadIdx.y; r < nya; r += BY) {
+        const double* row = plane + (size_t)clampi(v_lo - F + r, sh) * sw;
+        for (int c = threadIdx.x; c < nxa; c += BX) raw[r * nx + c] = row[clampi(u_lo - F + c, sw)];
+    }
+    __syncthreads();
+    {
+        const int slot = t % (2 * kSrT), m = slot / kSrT, jj = j0 + slot % kSrT;
+        if (jj <= j1) {
+            const BilinearAxis ax = bilinear_axis(sw, pos[0][jj - j0]);
+            const int cu = (m == 0 ? ax.c[0] : ax.c[1]) - u_lo + F;
+            for (int r = t / (2 * kSrT); r < nya; r += BX * BY / (2 * kSrT)) {
+                const double* at = raw + r * nx + cu;
+                hs[r * (2 * kSrT) + slot] = tap_sum<F>(fh, [&](int l) { return at[l]; });
+            }
+        }
+    }
+    __syncthreads();
+    const int ox = t % kSrT, j = j0 + ox, i = i0 + t / kSrT;
+    if (j > j1 || i > i1) return;
+    const double x = pos[0][j - j0], y = pos[1][i - i0];
+    const BilinearAxis ay = bilinear_axis(sh, y);
+    const BilinearTaps b = bilinear_taps(sw, sh, x, y);
+    dst[blockIdx.z * (size_t)dh * dw + (size_t)i * dw + j] = bilinear_sum(b, [&](int k) {  // tap k = 2 m + n: (x_m, y_n)
+        const double* at = hs + (ay.c[k % 2] - v_lo + F) * (2 * kSrT) + (k / 2) * kSrT + ox;
+        return tap_sum<F>(fv, [&](int l) { return at[l * (2 * kSrT)]; });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -506,6 +585,21 @@ __global__ __launch_bounds__(256) void k_im2feature_tiled(const double* __restri
 // The three derivative planes of the final bicubic warp in one launch (Image::warpImageBicubicRef, src/Image.h:2590-2594:
 // imfilter_h, imfilter_v, imfilter_v of the first with {-.5, 0, .5}): gx, gy as k_filter_h / k_filter_v compute them,
 // gxy = the v pass over gx, whose three rows are recomputed here with the h pass's own operations (same bits).
+// The three expressions at one pixel, each stated once: at(dr, dc) is the image at the pixel's clamped neighbour dr rows down and
+// dc columns right.  The zero middle tap is multiplied and added like the others, and every sum starts from 0.0 (tap_sum).
+template <class At>
+__device__ __forceinline__ double central3_h(const Taps& c3, At at) {  // imfilter_h
+    return tap_sum<1>(c3, [&](int l) { return at(0, l); });
+}
+template <class At>
+__device__ __forceinline__ double central3_v(const Taps& c3, At at) {  // imfilter_v
+    return tap_sum<1>(c3, [&](int l) { return at(l, 0); });
+}
+template <class HRow>
+__device__ __forceinline__ double central3_hv(const Taps& c3, HRow hrow) {  // imfilter_v of imfilter_h; hrow(l): central3_h l rows down
+    return tap_sum<1>(c3, [&](int l) { return hrow(l); });
+}
+
 __global__ void k_central3_all(const double* __restrict__ src, double* __restrict__ gx, double* __restrict__ gy,
                                double* __restrict__ gxy, int H, int W, Taps c3) {
     int tbx, tby;
@@ -514,23 +608,11 @@ __global__ void k_central3_all(const double* __restrict__ src, double* __restric
     if (j >= W || i >= H) return;
     const size_t np = (size_t)H * W;
     const double* p = src + blockIdx.z * np;
-    const auto hrow = [&](int ii) {
-        const double* row = p + (size_t)ii * W;
-        double acc = 0.0;
-#pragma unroll
-        for (int l = -1; l <= 1; l++) acc += row[clampi(j + l, W)] * c3.t[l + 1];
-        return acc;
-    };
-    const double hx[3] = {hrow(clampi(i - 1, H)), hrow(i), hrow(clampi(i + 1, H))};
-    double vy = 0.0, vxy = 0.0;
-#pragma unroll
-    for (int l = -1; l <= 1; l++) vy += p[(size_t)clampi(i + l, H) * W + j] * c3.t[l + 1];
-#pragma unroll
-    for (int l = -1; l <= 1; l++) vxy += hx[l + 1] * c3.t[l + 1];
+    const auto at = [&](int dr, int dc) { return p[(size_t)clampi(i + dr, H) * W + clampi(j + dc, W)]; };
     const size_t o = blockIdx.z * np + (size_t)i * W + j;
-    gx[o] = hx[1];
-    gy[o] = vy;
-    gxy[o] = vxy;
+    gx[o] = central3_h(c3, at);
+    gy[o] = central3_v(c3, at);
+    gxy[o] = central3_hv(c3, [&](int l) { return central3_h(c3, [&](int, int dc) { return at(l, dc); }); });  // its three h rows recomputed
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1613,13 +1695,16 @@ __global__ void k_update_warp_phi(const double* __restrict__ sdu, const double* 
 // Corners A=(x0,y0) B=(x1,y0) C=(x0,y1) D=(x1,y1); cXY multiplies dx^X dy^Y; term order as in the
 // reference expressions.  Output goes straight to the interleaved HWC buffer handed back to the caller.
 // ------------------------------------------------------------------------------------------------
-template <bool BATCH>  // BATCH: blockIdx.y = the pair of a batch (a separate instantiation: the single call's code is untouched --
-                       // offsetting the pointers in the one kernel changed its register allocation and cost 47 us at 1080p)
-__global__ void k_bicubic(const double* __restrict__ im1, const double* __restrict__ im2,
-                          const double* __restrict__ gx, const double* __restrict__ gy,
-                          const double* __restrict__ gxy, const double* __restrict__ vx,
-                          const double* __restrict__ vy, double* __restrict__ out, int H, int W, int C, Rect rc,
-                          unsigned long long* stamp, int planar_out, int clamp, BatchK bk) {
+// GRAD: the derivatives at the four corners are taken from frame 2 itself (k_bicubic_grad below), not from gx, gy, gxy
+// CC: the channel count as a compile-time constant (the loop over the channels is unrolled: the loads of the next channel are
+// in flight while this one is evaluated), or -1: C at run time
+template <bool BATCH, bool GRAD, int CC = -1>
+__device__ __forceinline__ void bicubic_pixel(const double* __restrict__ im1, const double* __restrict__ im2,
+                                              const double* __restrict__ gx, const double* __restrict__ gy,
+                                              const double* __restrict__ gxy, const Taps& c3, const double* __restrict__ vx,
+                                              const double* __restrict__ vy, double* __restrict__ out, int H, int W, int C,
+                                              const Rect& rc, unsigned long long* stamp, int planar_out, int clamp,
+                                              const BatchK& bk) {
     if (BATCH) {  // blockIdx.y: the pair of a batch (common.h: BatchK)
         const size_t p = blockIdx.y;
         // gx, gy, gxy are image 2's planes: pair 0's frame 2, or -- a backward pair -- its frame 1, one frame back
@@ -1664,12 +1749,54 @@ __global__ void k_bicubic(const double* __restrict__ im1, const double* __restri
     const double dx2 = dx * dx, dy2 = dy * dy;
     const double dx3 = dx * dx2, dy3 = dy * dy2;
     const size_t a = (size_t)y0 * W + x0, b = (size_t)y0 * W + x1, c = (size_t)y1 * W + x0, d = (size_t)y1 * W + x1;
-    for (int k = 0; k < C; k++) {
-        const double *f = im2 + k * np, *px = gx + k * np, *py = gy + k * np, *pz = gxy + k * np;
-        const double fA = f[a], fB = f[b], fC = f[c], fD = f[d];
-        const double xA = px[a], xB = px[b], xC = px[c], xD = px[d];
-        const double yA = py[a], yB = py[b], yC = py[c], yD = py[d];
-        const double zA = pz[a], zB = pz[b], zC = pz[c], zD = pz[d];
+    // GRAD: the 4 x 4 cells of frame 2 around the corners -- rows clamp(y0 - 1), y0, y1, clamp(y1 + 1), columns alike.  The
+    // neighbours of corner row y0 are rows 0, 1, 2 of them and those of y1 rows 1, 2, 3, except where y1 == y0 (the last row):
+    // then y1's upper neighbour is row 0 -- a choice kept as a fifth row (nb: corner row 0 or 1, offset d -> row), and alike for
+    // x1's left neighbour, so that every operand is the cell k_central3_all reads at the corner: same values, same bits.
+    size_t ro[4], co[4];
+    if (GRAD) {
+        ro[0] = (size_t)clampi(y0 - 1, H) * W, ro[1] = (size_t)y0 * W, ro[2] = (size_t)y1 * W, ro[3] = (size_t)clampi(y1 + 1, H) * W;
+        co[0] = clampi(x0 - 1, W), co[1] = x0, co[2] = x1, co[3] = clampi(x1 + 1, W);
+    }
+    const auto nb = [](int corner, int d) { return corner == 0 ? 1 + d : (d == -1 ? 4 : 2 + d); };
+    const int nc = CC > 0 ? CC : C;
+#pragma unroll
+    for (int k = 0; k < nc; k++) {
+        const double* f = im2 + k * np;
+        double fA, fB, fC, fD, xA, xB, xC, xD, yA, yB, yC, yD, zA, zB, zC, zD;
+        if (GRAD) {
+            double e[5][4], h[5][2];  // the cells, and central3_h of each row of them at the columns x0 and x1
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) e[r][q] = f[ro[r] + co[q]];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const double left1 = x1 != x0 ? e[r][1] : e[r][0];  // x1's left neighbour
+                h[r][0] = central3_h(c3, [&](int, int dc) { return e[r][1 + dc]; });
+                h[r][1] = central3_h(c3, [&](int, int dc) { return dc == -1 ? left1 : e[r][2 + dc]; });
+            }
+#pragma unroll
+            for (int q = 1; q <= 2; q++) e[4][q] = y1 != y0 ? e[1][q] : e[0][q];  // y1's upper neighbour: the cells of x0 and x1,
+#pragma unroll
+            for (int cx = 0; cx < 2; cx++) h[4][cx] = y1 != y0 ? h[1][cx] : h[0][cx];  // and the h pass there (the same row: same bits)
+            const auto corner = [&](int cy, int cx, double& fv, double& dxv, double& dyv, double& dxyv) {
+                fv = e[1 + cy][1 + cx];
+                dxv = h[1 + cy][cx];
+                dyv = central3_v(c3, [&](int dr, int) { return e[nb(cy, dr)][1 + cx]; });
+                dxyv = central3_hv(c3, [&](int l) { return h[nb(cy, l)][cx]; });
+            };
+            corner(0, 0, fA, xA, yA, zA);
+            corner(0, 1, fB, xB, yB, zB);
+            corner(1, 0, fC, xC, yC, zC);
+            corner(1, 1, fD, xD, yD, zD);
+        } else {
+            const double *px = gx + k * np, *py = gy + k * np, *pz = gxy + k * np;
+            fA = f[a], fB = f[b], fC = f[c], fD = f[d];
+            xA = px[a], xB = px[b], xC = px[c], xD = px[d];
+            yA = py[a], yB = py[b], yC = py[c], yD = py[d];
+            zA = pz[a], zB = pz[b], zC = pz[c], zD = pz[d];
+        }
         const double c00 = fA;
         const double c10 = xA;
         const double c20 = -3 * fA + 3 * fB - 2 * xA - xB;
@@ -1699,6 +1826,34 @@ __global__ void k_bicubic(const double* __restrict__ im1, const double* __restri
         }
         out[obase + k * ostride] = r;
     }
+}
+
+template <bool BATCH>  // BATCH: blockIdx.y = the pair of a batch (a separate instantiation: the single call's code is untouched --
+                       // offsetting the pointers in the one kernel changed its register allocation and cost 47 us at 1080p)
+__global__ void k_bicubic(const double* __restrict__ im1, const double* __restrict__ im2,
+                          const double* __restrict__ gx, const double* __restrict__ gy,
+                          const double* __restrict__ gxy, const double* __restrict__ vx,
+                          const double* __restrict__ vy, double* __restrict__ out, int H, int W, int C, Rect rc,
+                          unsigned long long* stamp, int planar_out, int clamp, BatchK bk) {
+    bicubic_pixel<BATCH, false>(im1, im2, gx, gy, gxy, Taps{}, vx, vy, out, H, W, C, rc, stamp, planar_out, clamp, bk);
+}
+
+// The same warp without derivative planes: 16 loads per pixel and channel from frame 2's 4 x 4 cells instead of 4 from each of
+// four planes, and no launch that writes three planes to be read back once (the final warp of a call; a single pair)
+__global__ void k_bicubic_grad(const double* __restrict__ im1, const double* __restrict__ im2, Taps c3,
+                               const double* __restrict__ vx, const double* __restrict__ vy, double* __restrict__ out, int H,
+                               int W, int C, Rect rc, unsigned long long* stamp, int planar_out, int clamp) {
+    bicubic_pixel<false, true, -1>(im1, im2, nullptr, nullptr, nullptr, c3, vx, vy, out, H, W, C, rc, stamp, planar_out, clamp,
+                                   BatchK{});
+}
+// ... for three channels, the loop over them unrolled: 98 registers where the loop takes 110, and held to the 96 of five waves per
+// SIMD (the allocator gets there without scratch; the kernel is bound by its fp64 arithmetic and the waves that hide its latency)
+__global__ __attribute__((amdgpu_waves_per_eu(5, 5))) void k_bicubic_grad3(
+    const double* __restrict__ im1, const double* __restrict__ im2, Taps c3, const double* __restrict__ vx,
+    const double* __restrict__ vy, double* __restrict__ out, int H, int W, int C, Rect rc, unsigned long long* stamp,
+    int planar_out, int clamp) {
+    bicubic_pixel<false, true, 3>(im1, im2, nullptr, nullptr, nullptr, c3, vx, vy, out, H, W, C, rc, stamp, planar_out, clamp,
+                                  BatchK{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2007,6 +2162,62 @@ int resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int 
     return PAPOF_OK;
 }
 
+// One pyramid level, smoothed and resized in one launch (k_smooth_resize).  smooth_resize_fits(): the half-widths are the fused
+// kernel's and the largest tile's source footprint fits a workgroup's LDS; otherwise the caller takes filter_hv() and resize().
+namespace {
+constexpr size_t kSrMaxLds = 64 * 1024;
+struct SrShape {
+    int nx, ny;
+    size_t lds;
+};
+SrShape sr_shape(int f, int sh, int sw, int dh, int dw, double xr, double yr) {
+    const auto span = [](int n_src, int n_dst, double r) {  // most source cells between a tile's first and last tap
+        int s = 0;
+        for (int p0 = 0; p0 < n_dst; p0 += kSrT)
+            s = std::max(s, bilinear_axis(n_src, resize_pos(std::min(p0 + kSrT, n_dst) - 1, r)).c[1] -
+                                bilinear_axis(n_src, resize_pos(p0, r)).c[0] + 1);
+        return s;
+    };
+    SrShape s;
+    s.nx = (span(sw, dw, xr) + 2 * f) | 1;  // (an odd pitch: the rows of the LDS image start in different banks)
+    s.ny = span(sh, dh, yr) + 2 * f;
+    s.lds = ((size_t)s.ny * s.nx + (size_t)s.ny * 2 * kSrT) * sizeof(double);
+    return s;
+}
+}  // namespace
+
+bool smooth_resize_fits(const Taps& fh, const Taps& fv, int sh, int sw, int dh, int dw, double xr, double yr) {
+    if (fh.fsize != fv.fsize || fh.fsize < 1 || fh.fsize > kHvMaxF || dh < 1 || dw < 1 || !(xr > 0) || !(yr > 0)) return false;
+    return sr_shape(fh.fsize, sh, sw, dh, dw, xr, yr).lds <= kSrMaxLds;
+}
+
+int smooth_resize(papof_handle* h, const double* src, double* dst, int sh, int sw, int planes, int dh, int dw, double xr,
+                  double yr, const Taps& fh, const Taps& fv) {
+    if (!smooth_resize_fits(fh, fv, sh, sw, dh, dw, xr, yr)) return PAPOF_EINVAL;
+    const SrShape s = sr_shape(fh.fsize, sh, sw, dh, dw, xr, yr);
+    const dim3 grid(xcd_grid(tiles_of(dw, kSrT), tiles_of(dh, kSrT)), 1, planes), block(BX, BY);
+#define PAPOF_SR(FF)                                                                                                        \
+    do {                                                                                                                    \
+        static bool attr_set = false;  /* (more than 48 KB of dynamic LDS is asked for once per kernel) */                  \
+        if (!attr_set) {                                                                                                    \
+            PAPOF_HIP(hipFuncSetAttribute((const void*)k_smooth_resize<FF>, hipFuncAttributeMaxDynamicSharedMemorySize,     \
+                                          (int)kSrMaxLds));                                                                 \
+            attr_set = true;                                                                                                \
+        }                                                                                                                   \
+        hipLaunchKernelGGL(k_smooth_resize<FF>, grid, block, s.lds, h->stream, src, dst, sh, sw, dh, dw, xr, yr, fh, fv,    \
+                           s.nx, s.ny);                                                                                     \
+    } while (0)
+    switch (fh.fsize) {
+        case 1: PAPOF_SR(1); break;
+        case 2: PAPOF_SR(2); break;
+        case 3: PAPOF_SR(3); break;
+        default: PAPOF_SR(4); break;
+    }
+#undef PAPOF_SR
+    LAUNCH_CHECK();
+    return PAPOF_OK;
+}
+
 int im2feature(papof_handle* h, const double* im, double* feat, int H, int W, int C, unsigned* nz, int frames, size_t nz_stride) {
     // frames > 1 (a batch): frame f reads im + f * (C planes), writes feat + f * (5 or 3 planes), flags nz + f * nz_stride
     const size_t np = (size_t)H * W;
@@ -2203,6 +2414,13 @@ int bicubic_warp(papof_handle* h, const double* im1, const double* im2, const do
                  const Rect* rc, bool planar_out, bool clamp, int batch, const BatchK* bk) {
     const Rect r = region(rc, W, H);
     if (r.empty()) return PAPOF_OK;
+    if (!gx) {  // no derivative planes: they are taken from frame 2 itself
+        if (gy || gxy || batch > 1) return PAPOF_EINVAL;
+        hipLaunchKernelGGL(C == 3 ? k_bicubic_grad3 : k_bicubic_grad, dim3(xcd_grid(tiles_of(r.x1 - r.x0, BX), tiles_of(r.y1 - r.y0, BY))), dim3(BX, BY), 0, h->stream, im1, im2,
+                           central3_taps(), vx, vy, out_hwc, H, W, C, r, take_stamp(h), planar_out ? 1 : 0, clamp ? 1 : 0);
+        LAUNCH_CHECK();
+        return PAPOF_OK;
+    }
     hipLaunchKernelGGL(batch > 1 ? k_bicubic<true> : k_bicubic<false>, dim3(xcd_grid(tiles_of(r.x1 - r.x0, BX), tiles_of(r.y1 - r.y0, BY)), batch), dim3(BX, BY), 0, h->stream, im1, im2, gx, gy, gxy, vx, vy, out_hwc, H, W,
                        C, r, take_stamp(h), planar_out ? 1 : 0, clamp ? 1 : 0, bk ? *bk : kNoBatch);
     LAUNCH_CHECK();
