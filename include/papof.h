@@ -1736,8 +1736,8 @@ int papof_mask_dilate_tensor(papof_handle* h, int n_frames, int height, int widt
  * progressive video exactly.  What it is not: at the critical velocity (an odd number of frame rows per field) the
  * neighbouring fields hold the current field's lines, c = 0 and the output is mode 0's; the end frames, with one neighbour
  * and q <= 0.5, are weaker; the flows assume motion linear over two field periods; telecined film is not its case
- * (papof_field_metrics_tensor and papof_weave_fields_tensor below find and weave the fields of one film frame); no model of
- * chroma subsampling.
+ * (papof_field_metrics_tensor and papof_weave_fields_tensor below find and weave the fields of one film frame); chroma
+ * subsampling is papof_ycc_to_rgb_tensor's business, in front of this call.
  * One lane writes both rows 2 j and 2 j + 1 of its column: every output element is written once.  Enqueued on `stream` (the
  * caller's hipStream_t on the handle's device, NULL: the null stream) and returns without waiting.  No device memory besides
  * the tensors is used; no atomics; bitwise reproducible.
@@ -1828,6 +1828,104 @@ int papof_weave_fields_tensor(papof_handle* h, int n_fields, int field_height, i
  * not one of 4, 8, 16, 32, 64. */
 int papof_cell_hist_tensor(papof_handle* h, int n_frames, int height, int width, int c, const papof_tensor* frames,
                            int cell_rows, int bins, int* hist, void* stream);
+
+/* Decoder surfaces, the way in (surface.hip: k_ycc_to_rgb): 8-bit YCbCr planes with subsampled chroma, as a video decoder
+ * leaves them on the device, to RGB frames for the calls above.  A parallel call: no call above changes.
+ * n_frames = T >= 1 frames of height x width = H x W >= 1 x 1 luma samples.  y: uint8 (frame, row, column); cb, cr: uint8
+ * (frame, row, column) of Hc x Wc samples, Wc = ceil(W / 2), Hc = ceil(H / sub_v), sub_v = 2 (4:2:0) or 1 (4:2:2); stride[3] of
+ * the three is not read; any non-negative strides.  One descriptor per plane makes every common format a view of the
+ * decoder's memory: NV12 / NV21 (column stride 2, cr one byte beside cb or the reverse), I420 / YV12, NV16, YUY2 / UYVY (y at
+ * column stride 2, chroma at 4); a row pitch beyond the width is a stride.  rgb: uint8, float32 or float64 (frame, row,
+ * column, channel) of 3 channels, strides [0..3] > 0 (NCHW and NHWC are strides); it must not overlap the planes.
+ * tables: HOST pointer to six int32 {y_off, cy, crv, cgu, cgv, cbu}: the luma offset, 0 .. 255, and five coefficients at the
+ * scale 2^14, each 0 .. 65535 -- the standard is the host's (tensors.py: ycc_tables), the device knows none.  For Kr, Kb, Kg =
+ * 1 - Kr - Kb and limited range they are 16, rint(2^14 * 255 / 219), and rint(2^14 * f * 255 / 224) of f = 2 (1 - Kr),
+ * 2 Kb (1 - Kb) / Kg, 2 Kr (1 - Kr) / Kg, 2 (1 - Kb); for full range 0, 2^14 and rint(2^14 * f).
+ * siting_h: 0 "left" (chroma k at luma column 2 k) or 1 "center" (at 2 k + 0.5).  siting_v: 0 "center" (chroma j at row
+ * 2 j + 0.5) or 1 "top" (at 2 j).  interlaced != 0: chroma row 2 i + p of the frame belongs to field p and sits at frame row
+ * 4 i + 0.5 (p = 0) or 4 i + 2.5 (p = 1), the MPEG-2 / H.264 field positions; siting_v is then not used.
+ * Everything is integer.  (a, b | wa, wb) is chroma index a with weight wa and index b with weight wb, both indices clamped
+ * to the valid range.  At luma pixel (x, y):
+ *
+ *   horizontally, k = x >> 1:    left:    x even (k, k | 4, 0)        x odd (k, k + 1 | 2, 2)
+ *                                center:  x even (k - 1, k | 1, 3)    x odd (k, k + 1 | 3, 1)         clamped to 0 .. Wc - 1
+ *   vertically, sub_v = 1:       (y, y | 8, 0), whatever siting_v and interlaced
+ *   sub_v = 2, j = y >> 1:       center:  y even (j - 1, j | 2, 6)    y odd (j, j + 1 | 6, 2)
+ *                                top:     y even (j, j | 8, 0)        y odd (j, j + 1 | 4, 4)         clamped to 0 .. Hc - 1
+ *   sub_v = 2, interlaced, p = y & 1, m = y >> 2, indices i of field p's own chroma rows, of which there are
+ *   n = (Hc - p + 1) >> 1:       y = 4 m: (m - 1, m | 1, 7)   y = 4 m + 2: (m, m + 1 | 5, 3)
+ *                                y = 4 m + 1: (m - 1, m | 3, 5)   y = 4 m + 3: (m, m + 1 | 7, 1)      clamped to 0 .. n - 1
+ *                                and index i is row 2 i + p of the chroma planes
+ *   C32 = sum over the four taps of wx * wy * c      (the weights add to 32; carried unrounded: chroma is not rounded twice)
+ *   L = 32 * cy * (Y - y_off);  U = Cb32 - 4096;  V = Cr32 - 4096
+ *   N_r = L + crv * V;   N_g = L - cgu * U - cgv * V;   N_b = L + cbu * U
+ *   uint8:             clamp((N + 2^18) >> 19, 0, 255), an arithmetic shift
+ *   float32, float64:  clamp(N, 0, 255 * 2^19) / (255 * 2^19) in fp64 (float32: one more rounding), the unrounded value
+ *
+ * No intermediate leaves int32: |L| <= 32 * 65535 * 255 < 2^29, |U|, |V| <= 4096 so a chroma term is at most 65535 * 4096
+ * < 2^28, and |N| + 2^18 < 2^29 + 2 * 2^28 + 2^18 < 2^31.
+ * Precision: with the tables of a standard a uint8 result is within 0.5 + 511 * 2^-15 = 0.5156 LSB of that standard's
+ * real-valued matrix on the same bilinear chroma: 0.5 of the one rounding, and 2^-15 LSB per level of |Y - y_off| <= 255 and of
+ * |C - 128| <= 128, twice for green, of the coefficients' own rounding to 2^-14.
+ * One pass, every element of rgb written exactly once: the result does not depend on what rgb held.  No atomics, no device
+ * memory besides the tensors, nothing of the handle's.  Enqueued on `stream` (the caller's hipStream_t on the handle's
+ * device, NULL: the null stream) and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor, data pointer or tables; planes that are not uint8; an
+ * rgb that is not uint8 / float32 / float64; a negative stride, or a zero stride of rgb; n_frames, height or width < 1; sub_v
+ * not 1 or 2; siting_h or siting_v not 0 or 1; y_off outside 0 .. 255 or a coefficient outside 0 .. 65535; interlaced with an
+ * odd height or a height < 4. */
+int papof_ycc_to_rgb_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* y,
+                            const papof_tensor* cb, const papof_tensor* cr, int sub_v, int siting_h, int siting_v,
+                            int interlaced, const int* tables, const papof_tensor* rgb, void* stream);
+
+/* Which of its two kernel instances papof_ycc_to_rgb_tensor runs for these descriptors (no device is touched): 1 for the one
+ * that loads and stores whole dwords, 0 for the one that goes lane by lane through the strides.  Both write the same bytes;
+ * a test that means to cover one of them reads here that it did.  1 needs all of: width a multiple of 4; y with column
+ * stride 1; cb and cr with column stride 2, equal row and frame strides and adjacent first bytes (cr = cb + 1: NV12, NV16;
+ * cb = cr + 1: NV21); a uint8 or float32 rgb with strides [2], [3] of (3, 1) (NHWC) or with stride[2] = 1 and stride[3] a
+ * multiple of 4 bytes (uint8) or 4 elements (float32) (NCHW); and the first byte, the rows and the frames of y, of the chroma
+ * pair and of rgb on 4-byte boundaries (a float32 rgb: 16-byte).  PAPOF_EINVAL: width < 1, or a descriptor that
+ * papof_ycc_to_rgb_tensor refuses. */
+int papof_ycc_to_rgb_fast(int width, const papof_tensor* y, const papof_tensor* cb, const papof_tensor* cr,
+                          const papof_tensor* rgb);
+
+/* Decoder surfaces, the way out (surface.hip: k_rgb_to_ycc): RGB frames to 8-bit YCbCr planes with subsampled chroma, for an
+ * encoder.  Sizes, planes, sub_v, the siting codes and interlaced as above; y, cb and cr are written (strides [0..2] > 0,
+ * stride[3] not read), so the call writes straight into an NV12 surface and leaves its pitch padding alone.  rgb: uint8,
+ * float32 or float64 (frame, row, column, channel) of 3 channels, any non-negative strides.
+ * tables: HOST pointer to eight int32 {y_off, yr, yg, yb, ur, ug, vg, vb}: the luma offset, 0 .. 255, and seven coefficients
+ * at the scale 2^14, each 0 .. 65535.  With sy = 219 / 255 and sc = 224 / 255 for limited range, 1 and 1 for full range:
+ * yr = rint(2^14 sy Kr), yb = rint(2^14 sy Kb), yg = rint(2^14 sy) - yr - yb; ur, ug = rint(2^14 sc * 0.5 * (Kr, Kg) /
+ * (1 - Kb)); vg, vb = rint(2^14 sc * 0.5 * (Kg, Kb) / (1 - Kr)).  The weight of B in Cb is ur + ug and that of R in Cr is
+ * vg + vb, so a grey pixel has chroma 128 exactly, and full-range luma of a grey byte is that byte.
+ * Everything is 64-bit integer.  q as papof_cell_hist_tensor's, of the three channels R, G, B of a pixel; D = 257 * 2^14, one
+ * level of a byte:
+ *
+ *   Y  = clamp(floor((yr R + yg G + yb B + y_off D + D / 2) / D), 0, 255)                  per luma pixel
+ *   Nu = (ur + ug) B - ur R - ug G;   Nv = (vg + vb) R - vg G - vb B                       per luma pixel, unrounded
+ *   S  = sum over the taps of wx * wy * N     (the adjoint taps below; wx and wy each add to 4)
+ *   Cb, Cr = clamp(floor((S + 128 * 16 D + 8 D) / (16 D)), 0, 255)                         one rounding per chroma sample
+ *
+ *   horizontally, chroma k:   left:    columns 2 k - 1, 2 k, 2 k + 1 with (1, 2, 1)    center:  2 k, 2 k + 1 with (2, 2)
+ *                             columns clamped to 0 .. W - 1
+ *   vertically, sub_v = 1:    row j with (4)
+ *   sub_v = 2, chroma j:      center:  rows 2 j, 2 j + 1 with (2, 2)    top:  2 j - 1, 2 j, 2 j + 1 with (1, 2, 1)
+ *                             rows clamped to 0 .. H - 1
+ *   sub_v = 2, interlaced:    chroma row 2 m (top field) from luma rows 4 m, 4 m + 2 with (3, 1); chroma row 2 m + 1 (bottom
+ *                             field) from rows 4 m + 1, 4 m + 3 with (1, 3); the second row clamped to the field's last
+ *                             row, H - 2 + p
+ *
+ * Precision: with the tables of a standard a sample is within 0.5 + 2.5 * 255 * 2^-14 = 0.5389 LSB of the standard's
+ * real-valued matrix and the same taps on q / 257 (three coefficients, one of them a difference of three roundings).
+ * One pass, every sample of the three planes written exactly once, nothing else; no atomics, no device memory besides the
+ * tensors.  Enqueued on `stream` and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: a NULL handle, descriptor, data pointer or tables; planes that are not uint8; an
+ * rgb that is not uint8 / float32 / float64; a negative stride, or a zero stride of a plane along (frame, row, column);
+ * n_frames, height or width < 1; sub_v not 1 or 2; siting_h or siting_v not 0 or 1; y_off outside 0 .. 255 or a coefficient
+ * outside 0 .. 65535; interlaced with an odd height or a height < 4. */
+int papof_rgb_to_ycc_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* rgb, int sub_v,
+                            int siting_h, int siting_v, int interlaced, const int* tables, const papof_tensor* y,
+                            const papof_tensor* cb, const papof_tensor* cr, void* stream);
 
 /* Rolling-shutter rectification along the flows (rolling.hip: k_rs_rectify, k_rs_flow).  A rolling shutter reads the rows of
  * a frame one after another: row y of frame t of H rows is exposed at the time t + readout * (y - a) / H, in frame intervals,

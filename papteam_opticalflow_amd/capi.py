@@ -84,6 +84,7 @@ SYMBOLS = [
     "papof_defect_detect_tensor", "papof_mask_dilate_tensor",
     "papof_deinterlace_tensor", "papof_field_metrics_tensor", "papof_weave_fields_tensor",
     "papof_cell_hist_tensor",
+    "papof_ycc_to_rgb_tensor", "papof_ycc_to_rgb_fast", "papof_rgb_to_ycc_tensor",
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
     "papof_deblur_tensor", "papof_deblur_workspace",
     "papof_warp_rows_tensor",
@@ -327,6 +328,12 @@ def load():
     L.papof_weave_fields_tensor.restype = c_int
     L.papof_cell_hist_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, c_int, c_int, c_void_p, c_void_p]
     L.papof_cell_hist_tensor.restype = c_int
+    L.papof_ycc_to_rgb_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, c_int, c_int, _I, _T, c_void_p]
+    L.papof_ycc_to_rgb_tensor.restype = c_int
+    L.papof_ycc_to_rgb_fast.argtypes = [c_int, _T, _T, _T, _T]
+    L.papof_ycc_to_rgb_fast.restype = c_int
+    L.papof_rgb_to_ycc_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, c_int, c_int, c_int, c_int, _I, _T, _T, _T, c_void_p]
+    L.papof_rgb_to_ycc_tensor.restype = c_int
     L.papof_rs_rectify_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, c_double, c_int, _T, _T, _T,
                                           c_void_p]
     L.papof_rs_rectify_tensor.restype = c_int

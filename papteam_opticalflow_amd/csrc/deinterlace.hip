@@ -13,7 +13,7 @@
 // What it is not.  At the critical velocity -- an odd number of frame rows per field -- the neighbouring fields hold the
 // lines of the current one and nothing is gained: the rule falls back to the cubic.  The end frames have one neighbour and
 // are weaker.  The flows assume motion that is linear over two field periods.  Telecined film is not its case (telecine.hip
-// finds and weaves the fields of one film frame); no model of chroma subsampling.
+// finds and weaves the fields of one film frame); chroma subsampling is surface.hip's business, in front of this call.
 //
 // Semantics: include/papof.h, papof_deinterlace_tensor.  The landing points and taps are sampler.h's (interp_points,
 // taps_at), the samplers too (sample_frame, load_frame, store), fp64 without contraction (-ffp-contract=off): the result is

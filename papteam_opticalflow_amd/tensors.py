@@ -220,6 +220,19 @@ under a steady pan; few iterations, no prior.
 
     dv = deblur_video(frames, 4, shutter=0.5, layout="NHWC")   # dv.video: the frames' shape, dv.support (T, H, W) uint8
 
+Decoder surfaces: a decoder on the device hands over YCbCr planes with subsampled chroma (NV12, I420, NV16, YUY2 ...) and an
+encoder wants them back.  `ycc_to_rgb` (include/papof.h: papof_ycc_to_rgb_tensor) and `rgb_to_ycc` (papof_rgb_to_ycc_tensor),
+one HIP kernel each, are the way in and out with one stated integer rule: bilinear chroma at the stated siting, the matrix
+and range of `ycc_tables` (BT.601, BT.709, BT.2020; limited or full), one rounding, and with interlaced=True the chroma of
+each FIELD taken from that field's own chroma lines.  `nv12_planes`, `i420_planes` and `packed422_planes` make the three
+planes as views of a surface (nothing is copied), `new_nv12` allocates one.  8-bit only; no 4:1:1 or 4:4:4; no transfer
+function or gamut conversion; bilinear chroma; `interlaced` is the caller's knowledge; no other call takes surfaces.
+
+    rgb = ycc_to_rgb(*nv12_planes(surface, 1080), interlaced=True)   # (T, 1080, W, 3) uint8 NHWC; then e.g.
+    out = rgb_to_ycc(inverse_telecine(split_fields(rgb, layout="NHWC"), layout="NHWC").video, layout="NHWC")   # out.y, out.cb, out.cr
+
+The luma plane of a surface is a one-channel video as it lies: `flow_video(y.unsqueeze(1), 5)` runs on it in place.
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
@@ -261,6 +274,7 @@ FieldMatch = collections.namedtuple("FieldMatch", "votes links groups cadence sh
 Detelecined = collections.namedtuple("Detelecined", "video groups times kinds match")
 DetelecinedVideo = collections.namedtuple("DetelecinedVideo", Detelecined._fields + ("flow_fw", "flow_bw", "timing"))
 ShotHist = collections.namedtuple("ShotHist", "hist cell_rows bins size")
+Surfaces = collections.namedtuple("Surfaces", "y cb cr")
 Shots = collections.namedtuple("Shots", "cuts flashes gradual distances ranges")
 Rectified = collections.namedtuple("Rectified", "video valid flow_fw flow_bw occlusion timing")
 StabilizedRS = collections.namedtuple("StabilizedRS", "video valid transforms motion ok flow_fw flow_bw occlusion timing")
@@ -2162,8 +2176,8 @@ def deinterlace_fields(fields, flow_fw, flow_bw, first=0, *, sigma=DEINT_SIGMA, 
     keeps the kept lines' bytes --, confidence (T, Hf, W) float64: q of every made pixel).  include/papof.h
     (papof_deinterlace_tensor) states the rule exactly.  Not gained: anything at the critical velocity (an odd number of
     frame rows per field: the neighbouring fields hold the same lines, the output is bob_fields'); the end frames are
-    weaker; the flows assume motion linear over two field periods; telecined film is inverse_telecine's case; no
-    chroma-subsampling model.  Enqueued on the current stream; returns without waiting."""
+    weaker; the flows assume motion linear over two field periods; telecined film is inverse_telecine's case;
+    interlaced 4:2:0 surfaces come in through ycc_to_rgb(..., interlaced=True).  Enqueued on the current stream; returns without waiting."""
     first = _check_parity(first)
     sigma = _check_deint_sigma(sigma)
     ts, descs, out_dtype, _ = _check_field_video(fields, layout, 1, out_dtype)
@@ -2471,7 +2485,7 @@ def inverse_telecine(fields, first=0, *, orphans="bob", flow_fw=None, flow_bw=No
     constant: times says when each frame was.  Not handled: the critical vertical velocity (an odd number of frame rows
     per film frame makes the WRONG pairing a line-doubled frame without a comb: the match inverts; a video pan near one
     row per field gets fields misvoted); the thresholds are relative to the noise (noise of 5 / 255 needs comb_threshold
-    26 / 255); no cadence lock (static stretches are cut 2-2-2); no blended telecine; no chroma-subsampling model.  Every
+    26 / 255); no cadence lock (static stretches are cut 2-2-2); no blended telecine; decoder surfaces come in through ycc_to_rgb(..., interlaced=True).  Every
     argument error raises before a launch; the call waits for the counts (match_fields), the video is enqueued on the
     current stream behind them."""
     first = _check_parity(first)
@@ -2808,7 +2822,257 @@ def flow_video_shots(frames, pyramidLevels, *, cuts=None, layout="NCHW", out_dty
     return out._replace(timing={k: "%f" % total[k] for k in keys}), shots
 
 
-MAX_RS_ITERS = 8  # include/papof.h: papof_rs_rectify_tensor
+# ---- decoder surfaces (include/papof.h: papof_ycc_to_rgb_tensor, papof_rgb_to_ycc_tensor)
+YCC_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}  # (Kr, Kb)
+YCC_RANGES = ("limited", "full")
+SITING_H = {"left": 0, "center": 1}
+SITING_V = {"center": 0, "top": 1}
+PACKED_422 = {"yuyv": (0, 1, 3), "yvyu": (0, 3, 1), "uyvy": (1, 0, 2), "vyuy": (1, 2, 0)}  # the first byte of y, cb, cr
+NV12_PITCH = 256  # new_nv12 rounds the width up to a multiple of this, as decoders pad their rows
+
+
+def ycc_tables(matrix="bt709", range="limited", *, reverse=False):
+    """The integers that the surface kernels take for a matrix ("bt601", "bt709", "bt2020") and a range ("limited": luma 16 ..
+    235, chroma 16 .. 240; "full"), at the scale 2^14 (include/papof.h).  Forward (ycc_to_rgb): [y_off, cy, crv, cgu, cgv, cbu]
+    with cy = rint(2^14 * 255 / 219) and crv = rint(2^14 * 2 (1 - Kr) * 255 / 224) etc. for limited range, the plain factors for
+    full range.  reverse=True (rgb_to_ycc): [y_off, yr, yg, yb, ur, ug, vg, vb], yg what is left of the luma weights' sum, so that
+    a grey maps exactly.  The device knows no standard: other integers in 0 .. 65535 passed to the C ABI are another matrix."""
+    if matrix not in YCC_MATRICES:
+        raise ValueError("matrix must be one of %s, got %r" % (tuple(YCC_MATRICES), matrix))
+    if range not in YCC_RANGES:
+        raise ValueError("range must be one of %s, got %r" % (YCC_RANGES, range))
+    kr, kb = YCC_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    y_off, sy, sc = (16, 219.0 / 255.0, 224.0 / 255.0) if range == "limited" else (0, 1.0, 1.0)
+    one = float(1 << 14)
+    if not reverse:
+        return [y_off, round(one / sy)] + [round(one * f / sc) for f in (
+            2.0 * (1.0 - kr), 2.0 * kb * (1.0 - kb) / kg, 2.0 * kr * (1.0 - kr) / kg, 2.0 * (1.0 - kb))]
+    yr, yb = round(one * sy * kr), round(one * sy * kb)
+    return [y_off, yr, round(one * sy) - yr - yb, yb] + [round(one * sc * 0.5 * f) for f in (
+        kr / (1.0 - kb), kg / (1.0 - kb), kg / (1.0 - kr), kb / (1.0 - kr))]
+
+
+def _check_surface_rule(matrix, range, siting, interlaced, sub_v, reverse):
+    """(the tables as a ctypes array, siting_h, siting_v, interlaced, sub_v) of the surface calls' keywords"""
+    tables = ycc_tables(matrix, range, reverse=reverse)
+    try:
+        sh, sv = siting
+    except (TypeError, ValueError):
+        raise TypeError("siting must be (horizontal, vertical), got %r" % (siting,)) from None
+    if not isinstance(sh, str) or sh not in SITING_H or not isinstance(sv, str) or sv not in SITING_V:
+        raise ValueError("siting must be (one of %s, one of %s), got %r" % (tuple(SITING_H), tuple(SITING_V), siting))
+    if not isinstance(interlaced, (bool, int)) or interlaced not in (0, 1):
+        raise ValueError("interlaced must be True or False, got %r" % (interlaced,))
+    if isinstance(sub_v, bool) or not isinstance(sub_v, int) or sub_v not in (1, 2):
+        raise ValueError("sub_v must be 2 (4:2:0) or 1 (4:2:2), got %r" % (sub_v,))
+    return (ctypes.c_int * len(tables))(*tables), SITING_H[sh], SITING_V[sv], int(interlaced), sub_v
+
+
+def _check_interlaced_height(interlaced, H):
+    if interlaced and (H % 2 or H < 4):
+        raise ValueError("interlaced surfaces have an even number of rows, at least 4, got %d" % H)
+
+
+def _as_plane(name, t):
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("%s must be uint8, got %s" % (name, t.dtype))
+    if t.dim() == 2:
+        return t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError("%s must be a 3-D plane (T, rows, columns) (or 2-D: one frame), got shape %s" % (name, tuple(t.shape)))
+    return t
+
+
+def _check_planes(y, cb, cr, sub_v, interlaced, size=None, written=False):
+    """the three planes of a surface as 3-D uint8 tensors on one HIP device, cb and cr of ceil(H / sub_v) x ceil(W / 2)
+    samples; size: the (T, H, W) they must have; written: no zero strides"""
+    ps = [_as_plane(n, t) for n, t in (("y", y), ("cb", cb), ("cr", cr))]
+    T, H, W = (int(v) for v in ps[0].shape)
+    if min(T, H, W) < 1:
+        raise ValueError("empty surface: y has shape %s" % (tuple(ps[0].shape),))
+    if size is not None and (T, H, W) != size:
+        raise ValueError("y must be %s for these frames, got %s" % (size, (T, H, W)))
+    want = (T, -(-H // sub_v), -(-W // 2))
+    for n, p in zip(("cb", "cr"), ps[1:]):
+        if tuple(p.shape) != want:
+            raise ValueError("%s must be %s for y %s and sub_v %d, got %s" % (n, want, (T, H, W), sub_v, tuple(p.shape)))
+    _check_interlaced_height(interlaced, H)
+    for n, p in zip(("y", "cb", "cr"), ps):
+        if p.device != ps[0].device:
+            raise ValueError("%s is on %s, y on %s: all planes must be on one device" % (n, p.device, ps[0].device))
+        if written and min(p.stride()) < 1:
+            raise ValueError("%s is written: its strides must be positive, got %s" % (n, tuple(p.stride())))
+    if not _on_gpu(ps[0]):
+        raise ValueError("surfaces must be on a HIP device (cuda:N), got %s" % ps[0].device)
+    return ps, (T, H, W)
+
+
+def _plane_struct(p):
+    return _struct(p, (p.stride(0), p.stride(1), p.stride(2), 0), capi.DTYPE_U8)
+
+
+def ycc_to_rgb(y, cb, cr, *, matrix="bt709", range="limited", siting=("left", "center"), interlaced=False, sub_v=2,
+               layout="NHWC", out_dtype=None):
+    """A decoder's YCbCr planes as RGB frames (papof_ycc_to_rgb_tensor, one HIP kernel): y (T, H, W) uint8, cb and cr (T,
+    ceil(H / sub_v), ceil(W / 2)) uint8 (2-D planes: one frame) with any non-negative strides on a HIP device -- views of the
+    decoder's surface (nv12_planes, i420_planes, packed422_planes) are read in place.  sub_v: 2 for 4:2:0, 1 for 4:2:2.
+    siting: (horizontal "left" | "center", vertical "center" | "top"), where the chroma samples sit; ("left", "center") is
+    MPEG-2's and H.264's default.  interlaced=True: the surface holds two woven fields, and every row takes its chroma from
+    the chroma lines of its own field (H even, >= 4; the vertical siting is then the standard's field positions).  matrix and
+    range: ycc_tables'.  The rule is integer and stated in include/papof.h: bilinear chroma with weights that add to 32, carried
+    unrounded into the matrix at the scale 2^14, one rounding -- a uint8 result is within 0.5156 LSB of the real-valued rule.
+    Returns a new (T, H, W, 3) (NHWC) or (T, 3, H, W) (NCHW) tensor of out_dtype: torch.uint8 (the default) or float32 /
+    float64, which get the unrounded value in 0 .. 1.  Enqueued on the current stream; returns without waiting."""
+    torch = _torch()
+    if layout not in LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (LAYOUTS, layout))
+    tables, sh, sv, inter, sub_v = _check_surface_rule(matrix, range, siting, interlaced, sub_v, False)
+    out_dtype = torch.uint8 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.uint8, torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.uint8, torch.float32 or torch.float64, got %s" % (out_dtype,))
+    ps, (T, H, W) = _check_planes(y, cb, cr, sub_v, inter)
+    out, d_out = _new_frames(T, H, W, 3, layout, out_dtype, ps[0].device)
+    d = [_plane_struct(p) for p in ps]
+    _launch(ps[0].device, "papof_ycc_to_rgb_tensor", T, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), ctypes.byref(d[2]), sub_v,
+            sh, sv, inter, tables, ctypes.byref(d_out))
+    return out
+
+
+def rgb_to_ycc(frames, *, matrix="bt709", range="limited", siting=("left", "center"), interlaced=False, sub_v=2,
+               layout="NHWC", out=None):
+    """RGB frames as the YCbCr planes an encoder takes (papof_rgb_to_ycc_tensor, one HIP kernel): frames (T, H, W, 3) or (T,
+    3, H, W) by `layout` (3-D: one frame), uint8, float32 or float64 (quantised to 0 .. 65535 as field_metrics does), any
+    strides, on a HIP device.  Luma per pixel; chroma computed per pixel unrounded, reduced with the adjoint taps of
+    ycc_to_rgb's siting -- (1, 2, 1) / 4 or (1, 1) / 2 across and down, (3, 1) / 4 and (1, 3) / 4 within each field when
+    interlaced -- and rounded once per sample, in 64-bit integers (include/papof.h).  The keywords are ycc_to_rgb's;
+    ycc_tables(..., reverse=True) gives the integers.  out: None, or (y, cb, cr) uint8 tensors of (T, H, W) and twice (T,
+    ceil(H / sub_v), ceil(W / 2)) with positive strides that are written in place -- the planes of an NV12 surface, whose pitch
+    padding stays as it was.  Returns Surfaces(y, cb, cr): new contiguous planes, or `out`'s.  Enqueued on the current
+    stream; returns without waiting."""
+    torch = _torch()
+    tables, sh, sv, inter, sub_v = _check_surface_rule(matrix, range, siting, interlaced, sub_v, True)
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    (T, H, W, C), strides, code = descs[0]
+    if C != 3:
+        raise ValueError("frames must have 3 channels (R, G, B), got %d (layout %s)" % (C, layout))
+    _check_interlaced_height(inter, H)
+    dev = ts[0].device
+    if out is None:
+        Hc, Wc = -(-H // sub_v), -(-W // 2)
+        ps = [torch.empty(s, dtype=torch.uint8, device=dev) for s in ((T, H, W), (T, Hc, Wc), (T, Hc, Wc))]
+    else:
+        try:
+            oy, ocb, ocr = out
+        except (TypeError, ValueError):
+            raise TypeError("out must be None or (y, cb, cr), got %r" % (type(out).__name__,)) from None
+        ps, _ = _check_planes(oy, ocb, ocr, sub_v, inter, size=(T, H, W), written=True)
+        if ps[0].device != dev:
+            raise ValueError("out is on %s, frames on %s" % (ps[0].device, dev))
+    d = [_plane_struct(p) for p in ps]
+    d_in = _struct(ts[0], strides, code)
+    _launch(dev, "papof_rgb_to_ycc_tensor", T, H, W, ctypes.byref(d_in), sub_v, sh, sv, inter, tables, ctypes.byref(d[0]),
+            ctypes.byref(d[1]), ctypes.byref(d[2]))
+    return Surfaces(*ps)
+
+
+def _as_surface(surface):
+    torch = _torch()
+    if not isinstance(surface, torch.Tensor):
+        raise TypeError("surface must be a torch.Tensor, got %s" % type(surface).__name__)
+    if surface.dtype != torch.uint8:
+        raise TypeError("surface must be uint8, got %s" % surface.dtype)
+    if surface.dim() == 2:
+        return surface.unsqueeze(0)
+    if surface.dim() != 3:
+        raise ValueError("surface must be (T, rows, bytes per row) (or 2-D: one frame), got shape %s" % (tuple(surface.shape),))
+    return surface
+
+
+def _surface_size(height, width, pitch):
+    if isinstance(height, bool) or not isinstance(height, int) or height < 1:
+        raise ValueError("height must be an integer >= 1, got %r" % (height,))
+    if width is None:
+        width = pitch
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= pitch:
+        raise ValueError("width must be an integer in 1 .. %d (the bytes of a row), got %r" % (pitch, width))
+    return height, width
+
+
+def nv12_planes(surface, height, order="uv", *, width=None, sub_v=2):
+    """The planes of a semi-planar surface as views -- nothing is copied: surface (T, rows, pitch) uint8 (2-D: one frame) on any
+    device holds `height` rows of luma and below them ceil(height / sub_v) rows of interleaved chroma, rows >= their sum.
+    order "uv": Cb first (NV12; NV16 with sub_v=1), "vu": Cr first (NV21, NV61).  width: the luma columns in use (by default
+    the whole pitch).  Returns Surfaces(y (T, height, width), cb, cr (T, ceil(height / sub_v), ceil(width / 2)), column
+    stride 2)."""
+    s = _as_surface(surface)
+    if order not in ("uv", "vu"):
+        raise ValueError("order must be 'uv' or 'vu', got %r" % (order,))
+    if sub_v not in (1, 2):
+        raise ValueError("sub_v must be 2 (4:2:0) or 1 (4:2:2), got %r" % (sub_v,))
+    H, W = _surface_size(height, width, int(s.shape[2]))
+    Hc, Wc = -(-H // sub_v), -(-W // 2)
+    if s.shape[1] < H + Hc or s.shape[2] < 2 * Wc:
+        raise ValueError("a surface of %d x %d (sub_v %d) needs %d rows of %d bytes, got shape %s" % (
+            H, W, sub_v, H + Hc, 2 * Wc, tuple(s.shape)))
+    c = s[:, H:H + Hc]
+    first, second = c[:, :, 0:2 * Wc:2], c[:, :, 1:2 * Wc:2]
+    return Surfaces(s[:, :H, :W], *((first, second) if order == "uv" else (second, first)))
+
+
+def i420_planes(surface, height, order="uv", *, width=None):
+    """The planes of a planar 4:2:0 surface as views: surface (T, rows, pitch) uint8 (2-D: one frame) whose rows are adjacent
+    in memory (pitch even) holds `height` rows of luma at `pitch`, then ceil(height / 2) rows of one chroma plane at pitch / 2,
+    then the other's.  order "uv": Cb first (I420), "vu": Cr first (YV12).  Returns Surfaces(y (T, height, width), cb, cr (T,
+    ceil(height / 2), ceil(width / 2)))."""
+    s = _as_surface(surface)
+    if order not in ("uv", "vu"):
+        raise ValueError("order must be 'uv' or 'vu', got %r" % (order,))
+    pitch = int(s.shape[2])
+    H, W = _surface_size(height, width, pitch)
+    Hc, Wc = -(-H // 2), -(-W // 2)
+    if pitch % 2 or s.stride(2) != 1 or s.stride(1) != pitch:
+        raise ValueError("a planar surface has adjacent rows of an even number of bytes, got shape %s strides %s" % (
+            tuple(s.shape), tuple(s.stride())))
+    if s.shape[1] * pitch < H * pitch + 2 * Hc * (pitch // 2):
+        raise ValueError("a planar surface of %d rows needs %d bytes per frame, got %d" % (
+            H, H * pitch + 2 * Hc * (pitch // 2), s.shape[1] * pitch))
+    at = lambda i: s.as_strided((s.shape[0], Hc, Wc), (s.stride(0), pitch // 2, 1),  # noqa: E731
+                                s.storage_offset() + H * pitch + i * Hc * (pitch // 2))
+    return Surfaces(s[:, :H, :W], *((at(0), at(1)) if order == "uv" else (at(1), at(0))))
+
+
+def packed422_planes(surface, order="yuyv"):
+    """The planes of a packed 4:2:2 surface as views: surface (T, H, 2 W) uint8 (2-D: one frame), W even, four bytes per two
+    pixels in `order`: "yuyv" (YUY2), "uyvy", "yvyu" or "vyuy".  Returns Surfaces(y (T, H, W) at column stride 2, cb, cr (T,
+    H, W / 2) at column stride 4) for ycc_to_rgb(..., sub_v=1)."""
+    s = _as_surface(surface)
+    if order not in PACKED_422:
+        raise ValueError("order must be one of %s, got %r" % (tuple(PACKED_422), order))
+    if s.shape[2] % 4 or min(s.shape) < 1:
+        raise ValueError("a packed 4:2:2 row is a multiple of 4 bytes, got shape %s" % (tuple(s.shape),))
+    oy, ou, ov = PACKED_422[order]
+    return Surfaces(s[:, :, oy::2], s[:, :, ou::4], s[:, :, ov::4])
+
+
+def new_nv12(T, H, W, device, *, pitch=None):
+    """A zeroed NV12 surface for T frames of H x W and its planes: (surface (T, H + ceil(H / 2), pitch) uint8 on `device`,
+    nv12_planes(surface, H, width=W)); pitch: by default W rounded up to a multiple of 256."""
+    for n, v in (("T", T), ("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (n, v))
+    if pitch is None:
+        pitch = -(-W // NV12_PITCH) * NV12_PITCH
+    if isinstance(pitch, bool) or not isinstance(pitch, int) or pitch < 2 * -(-W // 2):
+        raise ValueError("pitch must be an integer >= %d, got %r" % (2 * -(-W // 2), pitch))
+    surface = _torch().zeros((T, H + -(-H // 2), pitch), dtype=_torch().uint8, device=device)
+    return surface, nv12_planes(surface, H, width=W)
+
+
+MAX_RS_ITERS = 8 # include/papof.h: papof_rs_rectify_tensor
 _F64_FLOWS = (capi.DTYPE_F64, capi.DTYPE_F64)  # the dtype codes of flow_video_fb's float64 flows
 
 
