@@ -388,6 +388,9 @@ int papof_batch_stats(papof_handle* h, long long out[4]);
  * the logical axes (frame or pair, row, column, channel or component).  NCHW and NHWC are different strides of the same
  * description; a zero stride repeats an element (an expanded tensor). */
 enum { PAPOF_DTYPE_U8 = 0, PAPOF_DTYPE_F32 = 1, PAPOF_DTYPE_F64 = 2 };
+/* 16-bit words, strides in words: only the plane descriptors of papof_ycc16_to_rgb_tensor, papof_ycc16_to_rgb_fast and
+ * papof_rgb_to_ycc16_tensor take it; every other entry point refuses it with PAPOF_EINVAL. */
+enum { PAPOF_DTYPE_U16 = 3 };
 typedef struct papof_tensor {
     void* data;          /* device memory on the handle's device */
     int dtype;           /* PAPOF_DTYPE_* */
@@ -1926,6 +1929,81 @@ int papof_ycc_to_rgb_fast(int width, const papof_tensor* y, const papof_tensor* 
 int papof_rgb_to_ycc_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* rgb, int sub_v,
                             int siting_h, int siting_v, int interlaced, const int* tables, const papof_tensor* y,
                             const papof_tensor* cb, const papof_tensor* cr, void* stream);
+
+/* High-bit-depth decoder surfaces, the way in (surface.hip: k_ycc16_to_rgb, k_ycc16_to_rgb_nv): YCbCr planes of 9 .. 16 bits
+ * per sample in 16-bit little-endian words -- P010, P012, P016, P210, P216, Y210, Y216, planar yuv420p10le / I010, I012,
+ * yuv422p10le -- to RGB frames.  A parallel call: papof_ycc_to_rgb_tensor and everything behind it stay as they are.
+ * Sizes, sub_v, siting_h, siting_v, interlaced, rgb and the plane shapes as papof_ycc_to_rgb_tensor's.  y, cb, cr:
+ * PAPOF_DTYPE_U16 (frame, row, column), strides in WORDS, any non-negative strides, stride[3] not read: P010 has cb and cr at
+ * column stride 2, cr one word beside cb; Y210 has y at column stride 2 and chroma at 4.
+ * depth = d in 9 .. 16, P = 2^d - 1.  The sample of a word is s = (word >> shift) & P: shift = 16 - d for the MSB-aligned
+ * formats (P010, P012, P016, P210, P216, Y210, Y216), 0 for the LSB-aligned ones (I010, I012, yuv422p10le); 0 <= shift <=
+ * 16 - d.  The word's other bits are not looked at.
+ * tables: HOST pointer to seven int32 {y_off, cy, crv, cgu, cgv, cbu, peak}: the luma offset, 0 .. P; five coefficients at the
+ * scale 2^(d+6), each 0 .. 2^(d+8) - 1; and peak = Q in 1 .. 65535, the output level that means 1.0.  The standard is the host's
+ * (tensors.py: ycc_tables16).  With m = 2^(d-8), for limited range y_off = 16 m, cy = rint(2^(d+6) Q / (219 m)) and the chroma
+ * coefficients rint(2^(d+6) f Q / (224 m)) of the four factors f of papof_ycc_to_rgb_tensor; for full range y_off = 0 and both
+ * divisors are P.  Q = 255 for a uint8 rgb, Q = P for float32 / float64 (the float is then the d-bit level over P); the device
+ * divides by nothing but the constant Q * 2^(d+11).  At d = 8, Q = 255 these would be papof_ycc_to_rgb_tensor's tables and rule.
+ * Everything is exact integer arithmetic; every product is int32 x int32 -> int64.  With the taps of
+ * papof_ycc_to_rgb_tensor word for word (h_taps, v_taps, the field positions under interlaced; weights adding to 32):
+ *
+ *   C32 = sum over the four taps of wx * wy * c                                 (< 2^21; chroma carried unrounded)
+ *   L = 32 * cy * (Y - y_off);  U = Cb32 - 2^(d+4);  V = Cr32 - 2^(d+4)
+ *   N_r = L + crv * V;   N_g = L - cgu * U - cgv * V;   N_b = L + cbu * U
+ *   uint8 (needs peak = 255):  clamp((N + 2^(d+10)) >> (d+11), 0, 255), an arithmetic shift
+ *   float32, float64:          clamp(N, 0, Q * 2^(d+11)) / (Q * 2^(d+11)) in fp64 (float32: one more rounding)
+ *
+ * Bounds: |L| <= 32 * (2^(d+8) - 1) * P < 2^(2d+13); |U|, |V| <= 2^(d+4), so a chroma term is < 2^(2d+12) and green's two
+ * < 2^(2d+13); |N| < 2^(2d+14) <= 2^46, and Q * 2^(d+11) < 2^43 is exact in fp64.
+ * Precision: N / 2^(d+11) is the level in output LSB (1 / Q of full scale).  A coefficient is off its real value by at most
+ * 0.5 at the scale 2^(d+6), which costs 2^-(d+7) LSB per level of |Y - y_off| <= P < 2^d (at most 2^-7) and per level of
+ * |C - 2^(d-1)| <= 2^(d-1) (at most 2^-8, counted twice for green: 2^-7): less than 2^-6 LSB.  A float result is within 2^-6
+ * LSB of d bits (Q = P) of the standard's real-valued matrix on the same bilinear chroma, a uint8 result within 0.5 + 2^-6 =
+ * 0.5156 LSB of 8 bits.
+ * One pass, every element of rgb written exactly once; no atomics, no device memory besides the tensors, nothing of the
+ * handle's.  Enqueued on `stream` (the caller's hipStream_t on the handle's device, NULL: the null stream), returns without
+ * waiting.
+ * PAPOF_EINVAL, before anything is enqueued: what papof_ycc_to_rgb_tensor refuses of the handle, descriptors, sizes and codes;
+ * planes that are not PAPOF_DTYPE_U16; depth outside 9 .. 16; shift outside 0 .. 16 - depth; y_off outside 0 .. P, a
+ * coefficient outside 0 .. 2^(d+8) - 1, peak outside 1 .. 65535; peak != 255 with a uint8 rgb. */
+int papof_ycc16_to_rgb_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* y,
+                              const papof_tensor* cb, const papof_tensor* cr, int depth, int shift, int sub_v, int siting_h,
+                              int siting_v, int interlaced, const int* tables, const papof_tensor* rgb, void* stream);
+
+/* Which of its two kernel instances papof_ycc16_to_rgb_tensor runs for these descriptors (no device is touched): 1 for the one
+ * that loads 8 bytes at a time and stores whole dwords (P010 / P016 / P210 as decoders hand them over), 0 for the one that goes
+ * lane by lane through the strides.  Both write the same bytes.  1 needs all of: width a multiple of 4; y with column stride 1;
+ * cb and cr with column stride 2, equal row and frame strides and adjacent first words (cr = cb + 1 word, or the reverse);
+ * the first word, the rows and the frames of y and of the chroma pair on 8-byte boundaries; and rgb as papof_ycc_to_rgb_fast
+ * requires it.  PAPOF_EINVAL: width < 1, or a descriptor that papof_ycc16_to_rgb_tensor refuses. */
+int papof_ycc16_to_rgb_fast(int width, const papof_tensor* y, const papof_tensor* cb, const papof_tensor* cr,
+                            const papof_tensor* rgb);
+
+/* High-bit-depth decoder surfaces, the way out (surface.hip: k_rgb_to_ycc16): RGB frames to planes of d = depth bits in 16-bit
+ * words.  rgb, q, the adjoint taps and the field rule as papof_rgb_to_ycc_tensor's; depth, shift and the planes as
+ * papof_ycc16_to_rgb_tensor's, written (strides [0..2] > 0).  The stored word is level << shift: all its other bits are 0.
+ * tables: HOST pointer to eight int32 {y_off, yr, yg, yb, ur, ug, vg, vb}: the luma offset, 0 .. P, and seven coefficients,
+ * each 0 .. 2^30.  With Sy = 219 m, Sc = 224 m (m = 2^(d-8)) for limited range and Sy = Sc = P for full range:
+ * yr = rint(2^14 Sy Kr), yb = rint(2^14 Sy Kb), yg = 2^14 Sy - yr - yb; ur, ug = rint(2^14 Sc * 0.5 * (Kr, Kg) / (1 - Kb));
+ * vg, vb = rint(2^14 Sc * 0.5 * (Kg, Kb) / (1 - Kr)).  Arithmetic is 64-bit integer; E = 65535 * 2^14 for every depth:
+ *
+ *   Y      = clamp(floor((yr R + yg G + yb B + y_off E + E / 2) / E), 0, P)             (the sum < 2^48)
+ *   Nu     = (ur + ug) B - ur R - ug G;   Nv = (vg + vb) R - vg G - vb B                per luma pixel, unrounded, |N| < 2^47
+ *   S      = sum over the adjoint taps of wx * wy * N                                   (weights add to 16; |S| < 2^51)
+ *   Cb, Cr = clamp(floor((S + 2^(d-1) * 16 E + 8 E) / (16 E)), 0, P)                    one rounding per chroma sample
+ *
+ * A grey pixel has chroma exactly 2^(d-1); full-range luma of a grey q is rint(P q / 65535), which is q itself at d = 16.
+ * Precision: a sample is within 0.5 + 2^-13 LSB of d bits of the standard's real-valued matrix and the same taps on q / 65535:
+ * 0.5 of the one rounding; two coefficients off by at most 0.5 and the third, a difference, by at most 1 at the scale 2^14.
+ * One pass, every sample of the three planes written exactly once, nothing else; no atomics, no device memory besides the
+ * tensors.  Enqueued on `stream` and returns without waiting.
+ * PAPOF_EINVAL, before anything is enqueued: what papof_rgb_to_ycc_tensor refuses of the handle, descriptors, sizes and codes;
+ * planes that are not PAPOF_DTYPE_U16; depth outside 9 .. 16; shift outside 0 .. 16 - depth; y_off outside 0 .. P or a
+ * coefficient outside 0 .. 2^30. */
+int papof_rgb_to_ycc16_tensor(papof_handle* h, int n_frames, int height, int width, const papof_tensor* rgb, int depth,
+                              int shift, int sub_v, int siting_h, int siting_v, int interlaced, const int* tables,
+                              const papof_tensor* y, const papof_tensor* cb, const papof_tensor* cr, void* stream);
 
 /* Rolling-shutter rectification along the flows (rolling.hip: k_rs_rectify, k_rs_flow).  A rolling shutter reads the rows of
  * a frame one after another: row y of frame t of H rows is exposed at the time t + readout * (y - a) / H, in frame intervals,

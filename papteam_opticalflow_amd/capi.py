@@ -28,6 +28,7 @@ class Params(ctypes.Structure):
 
 
 DTYPE_U8, DTYPE_F32, DTYPE_F64 = 0, 1, 2
+DTYPE_U16 = 3  # PAPOF_DTYPE_U16: the plane descriptors of the ycc16 calls only
 MOTION_SIMILARITY, MOTION_AFFINE = 0, 1
 MOSAIC_FIRST, MOSAIC_MEAN, MOSAIC_MEDIAN, MOSAIC_FEATHER = 0, 1, 2, 3
 MOSAIC_MAX_SOURCES, MOSAIC_MAX_MEDIAN, MOSAIC_MAX_OVERLAP = 255, 64, 64
@@ -85,6 +86,7 @@ SYMBOLS = [
     "papof_deinterlace_tensor", "papof_field_metrics_tensor", "papof_weave_fields_tensor",
     "papof_cell_hist_tensor",
     "papof_ycc_to_rgb_tensor", "papof_ycc_to_rgb_fast", "papof_rgb_to_ycc_tensor",
+    "papof_ycc16_to_rgb_tensor", "papof_ycc16_to_rgb_fast", "papof_rgb_to_ycc16_tensor",
     "papof_rs_rectify_tensor", "papof_rs_flow_tensor",
     "papof_deblur_tensor", "papof_deblur_workspace",
     "papof_warp_rows_tensor",
@@ -334,6 +336,14 @@ def load():
     L.papof_ycc_to_rgb_fast.restype = c_int
     L.papof_rgb_to_ycc_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, c_int, c_int, c_int, c_int, _I, _T, _T, _T, c_void_p]
     L.papof_rgb_to_ycc_tensor.restype = c_int
+    L.papof_ycc16_to_rgb_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, _T, _T, c_int, c_int, c_int, c_int, c_int, c_int, _I, _T,
+                                            c_void_p]
+    L.papof_ycc16_to_rgb_tensor.restype = c_int
+    L.papof_ycc16_to_rgb_fast.argtypes = [c_int, _T, _T, _T, _T]
+    L.papof_ycc16_to_rgb_fast.restype = c_int
+    L.papof_rgb_to_ycc16_tensor.argtypes = [c_void_p, c_int, c_int, c_int, _T, c_int, c_int, c_int, c_int, c_int, c_int, _I, _T, _T, _T,
+                                            c_void_p]
+    L.papof_rgb_to_ycc16_tensor.restype = c_int
     L.papof_rs_rectify_tensor.argtypes = [c_void_p, c_int, c_int, c_int, c_int, _T, _T, _T, c_double, c_double, c_int, _T, _T, _T,
                                           c_void_p]
     L.papof_rs_rectify_tensor.restype = c_int

@@ -233,10 +233,19 @@ function or gamut conversion; bilinear chroma; `interlaced` is the caller's know
 
 The luma plane of a surface is a one-channel video as it lies: `flow_video(y.unsqueeze(1), 5)` runs on it in place.
 
+High-bit-depth surfaces: `ycc16_to_rgb` and `rgb_to_ycc16` (papof_ycc16_to_rgb_tensor, papof_rgb_to_ycc16_tensor) are the same
+pair for samples of 9 to 16 bits in 16-bit words -- P010 / P012 / P016, P210, I010 / yuv420p10le, Y210 -- with the same taps and
+an integer rule at the depth's own scale (`ycc_tables16`); a float32 result keeps every bit of a 10- or 12-bit level.
+`p010_planes`, `i010_planes` and `y210_planes` make the views, `new_p010` allocates a surface.  No transfer function or gamut
+mapping (PQ / HLG stay encoded); no 4:4:4; no uint16 RGB result.
+
+    rgb = ycc16_to_rgb(*p010_planes(surface, 2160), depth=10, matrix="bt2020")   # (T, 2160, W, 3) float32 NHWC
+
 torch is imported when a function is called, not when the package is imported.
 """
 import collections
 import ctypes
+import fractions
 import math
 import threading
 
@@ -2887,10 +2896,10 @@ def _as_plane(name, t):
     return t
 
 
-def _check_planes(y, cb, cr, sub_v, interlaced, size=None, written=False):
+def _check_planes(y, cb, cr, sub_v, interlaced, size=None, written=False, as_plane=None):
     """the three planes of a surface as 3-D uint8 tensors on one HIP device, cb and cr of ceil(H / sub_v) x ceil(W / 2)
-    samples; size: the (T, H, W) they must have; written: no zero strides"""
-    ps = [_as_plane(n, t) for n, t in (("y", y), ("cb", cb), ("cr", cr))]
+    samples; size: the (T, H, W) they must have; written: no zero strides; as_plane: _as_plane16 for planes of 16-bit words"""
+    ps = [(as_plane or _as_plane)(n, t) for n, t in (("y", y), ("cb", cb), ("cr", cr))]
     T, H, W = (int(v) for v in ps[0].shape)
     if min(T, H, W) < 1:
         raise ValueError("empty surface: y has shape %s" % (tuple(ps[0].shape),))
@@ -2992,13 +3001,13 @@ def _as_surface(surface):
     return surface
 
 
-def _surface_size(height, width, pitch):
+def _surface_size(height, width, pitch, unit="bytes"):
     if isinstance(height, bool) or not isinstance(height, int) or height < 1:
         raise ValueError("height must be an integer >= 1, got %r" % (height,))
     if width is None:
         width = pitch
     if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= pitch:
-        raise ValueError("width must be an integer in 1 .. %d (the bytes of a row), got %r" % (pitch, width))
+        raise ValueError("width must be an integer in 1 .. %d (the %s of a row), got %r" % (pitch, unit, width))
     return height, width
 
 
@@ -3070,6 +3079,233 @@ def new_nv12(T, H, W, device, *, pitch=None):
         raise ValueError("pitch must be an integer >= %d, got %r" % (2 * -(-W // 2), pitch))
     surface = _torch().zeros((T, H + -(-H // 2), pitch), dtype=_torch().uint8, device=device)
     return surface, nv12_planes(surface, H, width=W)
+
+
+# ---- decoder surfaces of 9 .. 16 bits per sample in 16-bit words (include/papof.h: papof_ycc16_to_rgb_tensor,
+# papof_rgb_to_ycc16_tensor)
+DEPTHS = (9, 16)  # the least and the greatest depth
+ALIGNED = ("msb", "lsb")  # the sample in the high bits of its word (P010, P016, Y210 ...) or in the low ones (I010 ...)
+P010_PITCH = 256  # new_p010 rounds a row's bytes up to a multiple of this
+
+
+def _check_depth(depth, aligned):
+    """the shift of a sample within its word"""
+    if isinstance(depth, bool) or not isinstance(depth, int) or not DEPTHS[0] <= depth <= DEPTHS[1]:
+        raise ValueError("depth must be an integer in %d .. %d, got %r" % (DEPTHS + (depth,)))
+    if aligned not in ALIGNED:
+        raise ValueError("aligned must be one of %s, got %r" % (ALIGNED, aligned))
+    return 16 - depth if aligned == "msb" else 0
+
+
+def ycc_tables16(matrix="bt709", range="limited", depth=10, *, peak=None, reverse=False):
+    """The integers that the 16-bit surface kernels take for a matrix, a range and a depth d in 9 .. 16 (include/papof.h).
+    Forward (ycc16_to_rgb): [y_off, cy, crv, cgu, cgv, cbu, peak] with the coefficients at the scale 2^(d+6) for an output
+    level `peak` that means 1.0 (by default P = 2^d - 1; 255 for a uint8 result): cy = rint(2^(d+6) peak / Sy), the others
+    rint(2^(d+6) f peak / Sc) of ycc_tables' four factors f, with y_off, Sy, Sc = 16 m, 219 m, 224 m (m = 2^(d-8)) for limited
+    range and 0, P, P for full range.  reverse=True (rgb_to_ycc16): [y_off, yr, yg, yb, ur, ug, vg, vb] at the scale 2^14 Sy
+    and 2^14 Sc, yg what is left of 2^14 Sy.  The roundings are exact (rational arithmetic, ties to even)."""
+    if matrix not in YCC_MATRICES:
+        raise ValueError("matrix must be one of %s, got %r" % (tuple(YCC_MATRICES), matrix))
+    if range not in YCC_RANGES:
+        raise ValueError("range must be one of %s, got %r" % (YCC_RANGES, range))
+    _check_depth(depth, "msb")
+    F = fractions.Fraction
+    P, m = (1 << depth) - 1, 1 << (depth - 8)
+    kr, kb = (F(repr(k)) for k in YCC_MATRICES[matrix])
+    kg = 1 - kr - kb
+    y_off, sy, sc = (16 * m, 219 * m, 224 * m) if range == "limited" else (0, P, P)
+    if reverse:
+        if peak is not None:
+            raise ValueError("peak belongs to the forward tables")
+        yr, yb = round((sy << 14) * kr), round((sy << 14) * kb)
+        return [y_off, yr, (sy << 14) - yr - yb, yb] + [round((sc << 13) * f) for f in (
+            kr / (1 - kb), kg / (1 - kb), kg / (1 - kr), kb / (1 - kr))]
+    peak = P if peak is None else peak
+    if isinstance(peak, bool) or not isinstance(peak, int) or not 1 <= peak <= 65535:
+        raise ValueError("peak must be an integer in 1 .. 65535, got %r" % (peak,))
+    one = peak << (depth + 6)
+    tables = [y_off, round(F(one, sy))] + [round(one * f / sc) for f in (
+        2 * (1 - kr), 2 * kb * (1 - kb) / kg, 2 * kr * (1 - kr) / kg, 2 * (1 - kb))] + [peak]
+    if max(tables[1:6]) >= 1 << (depth + 8):
+        raise ValueError("peak %d is too large for depth %d: a coefficient reaches %d, the kernels take less than 2^%d" % (
+            peak, depth, max(tables[1:6]), depth + 8))
+    return tables
+
+
+def _as_plane16(name, t):
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, got %s" % (name, type(t).__name__))
+    if t.dtype not in (torch.uint16, torch.int16):
+        raise TypeError("%s must be uint16 (or int16 with the same bits), got %s" % (name, t.dtype))
+    if t.dim() == 2:
+        return t.unsqueeze(0)
+    if t.dim() != 3:
+        raise ValueError("%s must be a 3-D plane (T, rows, columns) (or 2-D: one frame), got shape %s" % (name, tuple(t.shape)))
+    return t
+
+
+def _plane_struct16(p):
+    return _struct(p, (p.stride(0), p.stride(1), p.stride(2), 0), capi.DTYPE_U16)
+
+
+def ycc16_to_rgb(y, cb, cr, *, depth=10, aligned="msb", matrix="bt709", range="limited", siting=("left", "center"),
+                 interlaced=False, sub_v=2, layout="NHWC", out_dtype=None):
+    """A decoder's high-bit-depth YCbCr planes as RGB frames (papof_ycc16_to_rgb_tensor, one HIP kernel): ycc_to_rgb for samples
+    of `depth` = 9 .. 16 bits in 16-bit words.  y (T, H, W), cb and cr (T, ceil(H / sub_v), ceil(W / 2)), torch.uint16 or
+    torch.int16 with the same bits (2-D planes: one frame), any non-negative strides, on a HIP device -- views of the decoder's
+    surface (p010_planes, i010_planes, y210_planes) are read in place.  aligned: "msb", the sample in the high bits of its word
+    (P010, P012, P016, P210, Y210), or "lsb" (I010 / yuv420p10le, I012); the word's other bits are not looked at.  matrix,
+    range, siting, interlaced, sub_v, layout: ycc_to_rgb's.  The rule is ycc_to_rgb's with wider integers (include/papof.h;
+    ycc_tables16 gives them): a float result is the level over 2^depth - 1, within 2^-6 LSB of `depth` bits of the real-valued
+    rule before its own rounding, so no bit of the surface is lost; a uint8 result is within 0.5156 LSB of 8 bits.  Returns a
+    new (T, H, W, 3) (NHWC) or (T, 3, H, W) (NCHW) tensor of out_dtype: torch.float32 (the default), float64 or uint8.
+    Enqueued on the current stream; returns without waiting."""
+    torch = _torch()
+    if layout not in LAYOUTS:
+        raise ValueError("layout must be one of %s, got %r" % (LAYOUTS, layout))
+    shift = _check_depth(depth, aligned)
+    _, sh, sv, inter, sub_v = _check_surface_rule(matrix, range, siting, interlaced, sub_v, False)
+    out_dtype = torch.float32 if out_dtype is None else out_dtype
+    if out_dtype not in (torch.uint8, torch.float32, torch.float64):
+        raise TypeError("out_dtype must be torch.uint8, torch.float32 or torch.float64, got %s" % (out_dtype,))
+    tables = ycc_tables16(matrix, range, depth, peak=255 if out_dtype == torch.uint8 else None)
+    ps, (T, H, W) = _check_planes(y, cb, cr, sub_v, inter, as_plane=_as_plane16)
+    out, d_out = _new_frames(T, H, W, 3, layout, out_dtype, ps[0].device)
+    d = [_plane_struct16(p) for p in ps]
+    _launch(ps[0].device, "papof_ycc16_to_rgb_tensor", T, H, W, ctypes.byref(d[0]), ctypes.byref(d[1]), ctypes.byref(d[2]), depth,
+            shift, sub_v, sh, sv, inter, (ctypes.c_int * 7)(*tables), ctypes.byref(d_out))
+    return out
+
+
+def rgb_to_ycc16(frames, *, depth=10, aligned="msb", matrix="bt709", range="limited", siting=("left", "center"),
+                 interlaced=False, sub_v=2, layout="NHWC", out=None):
+    """RGB frames as high-bit-depth YCbCr planes (papof_rgb_to_ycc16_tensor, one HIP kernel): rgb_to_ycc for samples of `depth` =
+    9 .. 16 bits in 16-bit words, stored as level << shift with every other bit of the word 0 (aligned: ycc16_to_rgb's).
+    frames and the other keywords as rgb_to_ycc's; ycc_tables16(..., reverse=True) gives the integers.  A sample is within 0.5
+    + 2^-13 LSB of `depth` bits of the real-valued rule.  out: None, or (y, cb, cr) uint16 / int16 tensors with positive
+    strides that are written in place -- the planes of a P010 surface (new_p010), whose pitch padding stays as it was.  Returns
+    Surfaces(y, cb, cr): new contiguous torch.uint16 planes, or `out`'s.  Enqueued on the current stream; returns without
+    waiting."""
+    torch = _torch()
+    shift = _check_depth(depth, aligned)
+    _, sh, sv, inter, sub_v = _check_surface_rule(matrix, range, siting, interlaced, sub_v, True)
+    tables = ycc_tables16(matrix, range, depth, reverse=True)
+    ts, descs, _, _ = _check([("frames", frames)], layout, None, 1)
+    (T, H, W, C), strides, code = descs[0]
+    if C != 3:
+        raise ValueError("frames must have 3 channels (R, G, B), got %d (layout %s)" % (C, layout))
+    _check_interlaced_height(inter, H)
+    dev = ts[0].device
+    if out is None:
+        Hc, Wc = -(-H // sub_v), -(-W // 2)
+        ps = [torch.empty(s, dtype=torch.uint16, device=dev) for s in ((T, H, W), (T, Hc, Wc), (T, Hc, Wc))]
+    else:
+        try:
+            oy, ocb, ocr = out
+        except (TypeError, ValueError):
+            raise TypeError("out must be None or (y, cb, cr), got %r" % (type(out).__name__,)) from None
+        ps, _ = _check_planes(oy, ocb, ocr, sub_v, inter, size=(T, H, W), written=True, as_plane=_as_plane16)
+        if ps[0].device != dev:
+            raise ValueError("out is on %s, frames on %s" % (ps[0].device, dev))
+    d = [_plane_struct16(p) for p in ps]
+    d_in = _struct(ts[0], strides, code)
+    _launch(dev, "papof_rgb_to_ycc16_tensor", T, H, W, ctypes.byref(d_in), depth, shift, sub_v, sh, sv, inter,
+            (ctypes.c_int * 8)(*tables), ctypes.byref(d[0]), ctypes.byref(d[1]), ctypes.byref(d[2]))
+    return Surfaces(*ps)
+
+
+def _as_surface16(surface):
+    """a surface as (T, rows, words): uint16 / int16 as it is, uint8 (T, rows, bytes) with its rows reinterpreted"""
+    torch = _torch()
+    if not isinstance(surface, torch.Tensor):
+        raise TypeError("surface must be a torch.Tensor, got %s" % type(surface).__name__)
+    if surface.dtype not in (torch.uint16, torch.int16, torch.uint8):
+        raise TypeError("surface must be uint16, int16 or uint8 (bytes), got %s" % surface.dtype)
+    s = surface
+    if s.dim() == 2:
+        s = s.unsqueeze(0)
+    if s.dim() != 3:
+        raise ValueError("surface must be (T, rows, words per row) (or 2-D: one frame), got shape %s" % (tuple(surface.shape),))
+    if s.dtype == torch.uint8:
+        if s.shape[2] % 2 or s.stride(2) != 1 or s.stride(0) % 2 or s.stride(1) % 2 or s.storage_offset() % 2:
+            raise ValueError("a surface of bytes is read as 16-bit words: it needs adjacent bytes, an even pitch and frame "
+                             "stride and a 2-byte-aligned storage offset, got shape %s strides %s offset %d" % (
+                                 tuple(s.shape), tuple(s.stride()), s.storage_offset()))
+        s = s.view(torch.uint16)
+    return s
+
+
+def p010_planes(surface, height, order="uv", *, width=None, sub_v=2):
+    """The planes of a semi-planar surface of 16-bit words as views -- nothing is copied: P010 / P012 / P016 (sub_v=2) and P210 /
+    P216 (sub_v=1).  surface (T, rows, words per row) uint16 / int16, or (T, rows, bytes per row) uint8 whose rows are
+    reinterpreted (2-D: one frame), on any device, holds `height` rows of luma and below them ceil(height / sub_v) rows of
+    interleaved chroma.  order "uv": Cb first, "vu": Cr first.  width: the luma columns in use (by default the whole pitch).
+    Returns Surfaces(y (T, height, width), cb, cr (T, ceil(height / sub_v), ceil(width / 2)) at column stride 2)."""
+    s = _as_surface16(surface)
+    if order not in ("uv", "vu"):
+        raise ValueError("order must be 'uv' or 'vu', got %r" % (order,))
+    if sub_v not in (1, 2):
+        raise ValueError("sub_v must be 2 (4:2:0) or 1 (4:2:2), got %r" % (sub_v,))
+    H, W = _surface_size(height, width, int(s.shape[2]), "words")
+    Hc, Wc = -(-H // sub_v), -(-W // 2)
+    if s.shape[1] < H + Hc or s.shape[2] < 2 * Wc:
+        raise ValueError("a surface of %d x %d (sub_v %d) needs %d rows of %d words, got shape %s" % (
+            H, W, sub_v, H + Hc, 2 * Wc, tuple(s.shape)))
+    c = s[:, H:H + Hc]
+    first, second = c[:, :, 0:2 * Wc:2], c[:, :, 1:2 * Wc:2]
+    return Surfaces(s[:, :H, :W], *((first, second) if order == "uv" else (second, first)))
+
+
+def i010_planes(surface, height, order="uv", *, width=None, sub_v=2):
+    """The planes of a planar surface of 16-bit words as views: I010 / yuv420p10le, I012 (sub_v=2), yuv422p10le (sub_v=1); read
+    them with aligned="lsb".  surface as p010_planes', its rows adjacent in memory and of an even number of words: `height`
+    rows of luma at the pitch, then ceil(height / sub_v) rows of one chroma plane at half the pitch, then the other's.  order
+    "uv": Cb first.  Returns Surfaces(y (T, height, width), cb, cr (T, ceil(height / sub_v), ceil(width / 2)))."""
+    s = _as_surface16(surface)
+    if order not in ("uv", "vu"):
+        raise ValueError("order must be 'uv' or 'vu', got %r" % (order,))
+    if sub_v not in (1, 2):
+        raise ValueError("sub_v must be 2 (4:2:0) or 1 (4:2:2), got %r" % (sub_v,))
+    pitch = int(s.shape[2])
+    H, W = _surface_size(height, width, pitch, "words")
+    Hc, Wc = -(-H // sub_v), -(-W // 2)
+    if pitch % 2 or s.stride(2) != 1 or s.stride(1) != pitch:
+        raise ValueError("a planar surface has adjacent rows of an even number of words, got shape %s strides %s" % (
+            tuple(s.shape), tuple(s.stride())))
+    if s.shape[1] * pitch < H * pitch + 2 * Hc * (pitch // 2):
+        raise ValueError("a planar surface of %d rows (sub_v %d) needs %d words per frame, got %d" % (
+            H, sub_v, H * pitch + 2 * Hc * (pitch // 2), s.shape[1] * pitch))
+    at = lambda i: s.as_strided((s.shape[0], Hc, Wc), (s.stride(0), pitch // 2, 1),  # noqa: E731
+                                s.storage_offset() + H * pitch + i * Hc * (pitch // 2))
+    return Surfaces(s[:, :H, :W], *((at(0), at(1)) if order == "uv" else (at(1), at(0))))
+
+
+def y210_planes(surface, order="yuyv"):
+    """The planes of a packed 4:2:2 surface of 16-bit words as views (Y210, Y216): surface (T, H, 2 W words) as p010_planes', W
+    even, four words per two pixels in `order` ("yuyv": Y210's).  Returns Surfaces(y (T, H, W) at column stride 2, cb, cr (T,
+    H, W / 2) at column stride 4) for ycc16_to_rgb(..., sub_v=1) and rgb_to_ycc16(..., sub_v=1, out=)."""
+    s = _as_surface16(surface)
+    if order not in PACKED_422:
+        raise ValueError("order must be one of %s, got %r" % (tuple(PACKED_422), order))
+    if s.shape[2] % 4 or min(s.shape) < 1:
+        raise ValueError("a packed 4:2:2 row is a multiple of 4 words, got shape %s" % (tuple(s.shape),))
+    oy, ou, ov = PACKED_422[order]
+    return Surfaces(s[:, :, oy::2], s[:, :, ou::4], s[:, :, ov::4])
+
+
+def new_p010(T, H, W, device, *, pitch=None):
+    """A zeroed P010 / P016 surface for T frames of H x W and its planes: (surface (T, H + ceil(H / 2), pitch / 2) uint16 on
+    `device`, p010_planes(surface, H, width=W)); pitch: a row's BYTES, even, by default 2 W rounded up to a multiple of 256."""
+    for n, v in (("T", T), ("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError("%s must be an integer >= 1, got %r" % (n, v))
+    if pitch is None:
+        pitch = -(-2 * W // P010_PITCH) * P010_PITCH
+    if isinstance(pitch, bool) or not isinstance(pitch, int) or pitch % 2 or pitch < 4 * -(-W // 2):
+        raise ValueError("pitch must be an even integer >= %d (bytes), got %r" % (4 * -(-W // 2), pitch))
+    surface = _torch().zeros((T, H + -(-H // 2), pitch // 2), dtype=_torch().uint16, device=device)
+    return surface, p010_planes(surface, H, width=W)
 
 
 MAX_RS_ITERS = 8 # include/papof.h: papof_rs_rectify_tensor
