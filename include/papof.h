@@ -87,7 +87,11 @@ typedef struct papof_params {
                               Phase4_LinearSystem are ONE fused kernel here: its time is apportioned 30 : 70; on the default
                               branches phi (Phase2_Derivatives) is written by the warp-and-smooth kernel of Phase1_Generate
                               and reported as a fixed 4 % of it; where ONE kernel does Phase1 ... Phase4 (k_flow_system: default
-                              branches, one GPU) its time is apportioned 51 : 2 : 14 : 33.                              */
+                              branches, one GPU) its time is apportioned 51 : 2 : 14 : 33.  Between two outer iterations of
+                              a level that kernel also carries Phase6_Update (u += du, v += dv: one scattered 16-byte load
+                              per warped pixel and two 8-byte stores per cell, no measurable part of the launch -- it is no
+                              slower than without them): Phase6 then has no kernel of its own and reads the gap in front of
+                              the launch; its share stays inside the four.                                                */
     int interpolation;     /* PAPOF_INTERP_*  (0 = the reference's default)                                          */
     int noise_model;       /* PAPOF_NOISE_*   (0 = the reference's default)                                          */
 } papof_params;
@@ -2175,8 +2179,15 @@ int papof_warp_rows_tensor(papof_handle* h, int n_frames, int height, int width,
 
 /* Measurement aid (tools/collection_trace.py): host-side wall seconds of the LAST papof_flow* / papof_seq_push* call on this
  * handle -- out[0] from the call's entry until everything was enqueued (the runtime's launch path: ~200 launches for a
- * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] reserved (0). */
+ * 240x135 pair on the reference schedule), out[1] the wait for the streams that followed, out[2] from the call's entry until
+ * the host began to enqueue the coarsest level's solves (what it enqueues first delays the main stream's first kernel). */
 int papof_last_host_times(papof_handle* h, double out[3]);
+
+/* Measurement / test aid: what the LAST papof_flow* / papof_seq_push* call on this handle enqueued -- out[0] k_flow_system
+ * launches (one kernel from the flow to the linear system), out[1] those of them that carried the previous outer iteration's
+ * increment (no update kernel in front of them), out[2] update kernel launches (k_update_warp_phi), out[3] fills of the
+ * solver's (du, dv) planes in front of a solve. */
+int papof_last_chain_stats(papof_handle* h, long long out[4]);
 
 /* Test aid: one exact-order solve of `n_sor` sweeps on synthetic height x width planes (the micro-benchmark's), once
  * whole and `reps` times as two band launches on two streams -- bands < split_band on a stream of the call's own, the

@@ -65,7 +65,7 @@ SYMBOLS = [
     "papof_flow_dequantize16", "papof_flow_to_bgr", "papof_set_stream_overlap", "papof_sor_plan", "papof_last_sor_stats", "papof_test_sor_strips",
     "papof_pyramid_levels_for_min_width", "papof_stage_smoothflow_ex", "papof_stage_est_gaussian_mixture",
     "papof_stage_bicubic_warp_ex", "papof_tiles_comm_info", "papof_host_alloc", "papof_host_free",
-    "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times",
+    "papof_last_sor_solves", "papof_bands_plan", "papof_lap_guard_stats", "papof_last_host_times", "papof_last_chain_stats",
     "papof_flow_batch", "papof_flow_batch_u8", "papof_batch_stats", "papof_flow_batch_tensor", "papof_flow_batch_tensor_fb",
     "papof_fb_check_tensor", "papof_track_tensor", "papof_interp_tensor", "papof_flow_batch_tensor_init",
     "papof_flow_batch_tensor_fb_init", "papof_motion_fit_tensor", "papof_motion_workspace", "papof_warp_affine_tensor",
@@ -183,6 +183,8 @@ def load():
     L.papof_lap_guard_stats.argtypes = [c_void_p, ctypes.POINTER(c_int)]
     L.papof_last_host_times.argtypes = [c_void_p, ctypes.POINTER(c_double)]
     L.papof_batch_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
+    if hasattr(L, "papof_last_chain_stats"):  # (an older library under PAPOF_LIB: A/B runs)
+        L.papof_last_chain_stats.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_longlong)]
     for fn in (L.papof_flow_batch, L.papof_flow_batch_u8):
         fn.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _D]
         fn.restype = c_int
@@ -842,11 +844,20 @@ class Papof:
         _chk(self.L.papof_batch_stats(self.h, out), "papof_batch_stats")
         return dict(chains=out[0], chain_pairs=out[1], singles=out[2], reruns=out[3])
 
-    def last_host_times(self):
-        """(enqueue_sec, wait_sec) of the last call on this handle: host wall time spent enqueueing / waiting for the streams"""
+    def last_host_times(self, first_solve=False):
+        """(enqueue_sec, wait_sec) of the last call on this handle: host wall time spent enqueueing / waiting for the streams;
+        first_solve: and the seconds from the call's entry until the host began to enqueue the coarsest level's solves"""
         out = (c_double * 3)()
         _chk(self.L.papof_last_host_times(self.h, out), "papof_last_host_times")
-        return out[0], out[1]
+        return (out[0], out[1], out[2]) if first_solve else (out[0], out[1])
+
+    def last_chain_stats(self):
+        """dict(flow_systems, carried, updates, clears) of the last call on this handle: k_flow_system launches, those that
+        carried the previous increment, k_update_warp_phi launches, per-solve (du, dv) fills (include/papof.h:
+        papof_last_chain_stats)"""
+        out = (ctypes.c_longlong * 4)()
+        _chk(self.L.papof_last_chain_stats(self.h, out), "papof_last_chain_stats")
+        return dict(flow_systems=out[0], carried=out[1], updates=out[2], clears=out[3])
 
     def lap_guard_stats(self):
         """dict(reruns, exact_calls, exact_next, guard_on): the Laplacian-noise guard (include/papof.h: papof_lap_guard_stats)"""

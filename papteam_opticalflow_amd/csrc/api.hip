@@ -386,6 +386,7 @@ struct LevelSolve {
     bool fold_warp = false;
     LapGuard* lg = nullptr;
     int level = 0;
+    bool dudv_cleared = false;  // B.sp's (du, dv) planes were cleared when the level was bound (sor_reset_dudv): no fill per solve
 };
 
 // Phase5_SOR is the solver kernels' own duration (the roofline of the dominant kernel is priced on it): the events are
@@ -397,6 +398,7 @@ static int marked_solve(papof_handle* h, PhaseClock& clk, unsigned* prog, SorPla
     };
     h->sor_mark_ctx = &clk;
     h->sor_prog_next = prog;
+    h->sor_dudv_cleared = s.dudv_cleared && &SP == &s.B.sp;
     const int rc = sor_solve(h, SP, s.H, s.W, s.alpha, s.omega, s.n_sor, s.mode);
     h->sor_prog_next = nullptr;
     h->sor_mark = nullptr;
@@ -429,12 +431,21 @@ int smooth_flow(papof_handle* h, const LevelSolve& s, PhaseClock& clk, double*& 
     // (a one-block level keeps the pair of kernels while the guard collects proofs: their exhaustive check needs ONE block)
     const bool fused_system = fused_env && s.fold_warp && s.n_inner == 1 && !B.gm && (s.fc == 5 || s.fc == 3) &&
                               !(s.lg && s.lg->guard()) && !(s.lg && s.lg->on && lap_one_block_level(s.H, s.W));
+    // k_flow_system carries the update of the outer iteration before it: u + du, v + dv is the flow it works at, and it
+    // writes the sums to the other pair of planes -- no update kernel between two outer iterations of a level
+    bool carried = false;  // the last solve's increment is not in (u, v) yet
     for (int count = 0; count < s.n_outer; count++) {
         clk.phase(fused_system ? kTimerFused : (int)PAPOF_T_PHASE1_GENERATE);
-        if (fused_system)
+        if (fused_system) {
             PAPOF_TRY(flow_system(h, s.f1, s.f2, u, v, im1s, s.H, s.W, s.fc, s.alpha, s.omega, SP,
-                                  s.lg && count > 0 ? s.lg->wit(s.lg->slot - 1) : nullptr));
-        else if (s.fold_warp)
+                                  s.lg && count > 0 ? s.lg->wit(s.lg->slot - 1) : nullptr, 0, -1, 1, nullptr,
+                                  carried ? &SP : nullptr, carried ? ua : nullptr, carried ? va : nullptr));
+            if (carried) {
+                std::swap(u, ua);
+                std::swap(v, va);
+                carried = false;
+            }
+        } else if (s.fold_warp)
             // warp + both passes + blend + imdt; the warp at the flow the previous iteration left is what that iteration's
             // noise estimate is about: its witnesses are taken here (LapGuard)
             PAPOF_TRY(warp_smooth_blend(h, s.f1, s.f2, u, v, im1s, B.blend, B.imdt, s.H, s.W, s.fc,
@@ -476,9 +487,15 @@ int smooth_flow(papof_handle* h, const LevelSolve& s, PhaseClock& clk, double*& 
         unsigned* const wit = s.lg && !B.gm && !B.bgx && !wit_later && !wit_small ? s.lg->wit(s.lg->slot) : nullptr;
         // the level's last update writes straight to the caller's buffers where there are any, every other one to the other pair
         const bool to_caller = s.out_u && s.out_v && count + 1 == s.n_outer;
-        PAPOF_TRY(update_warp_phi(h, SP, u, v, to_caller ? s.out_u : ua, to_caller ? s.out_v : va, s.f1, s.f2, s.warp, phi_next,
-                                  s.H, s.W, s.fc, rewarp, 0, -1, wit));
-        if (to_caller) {
+        // fused_system: nothing but the sums is due here while another outer iteration follows (no phi, no re-warp, the
+        // witnesses are the next k_flow_system's): it carries them.  The level's LAST update stays this kernel.
+        carried = fused_system && count + 1 < s.n_outer;
+        if (!carried)
+            PAPOF_TRY(update_warp_phi(h, SP, u, v, to_caller ? s.out_u : ua, to_caller ? s.out_v : va, s.f1, s.f2, s.warp,
+                                      phi_next, s.H, s.W, s.fc, rewarp, 0, -1, wit));
+        if (carried) {
+            // (u, v) stay the planes the next k_flow_system reads
+        } else if (to_caller) {
             u = s.out_u;
             v = s.out_v;
         } else {
@@ -571,6 +588,7 @@ struct FlowPass {
     // Allocation / PostProcessing (preparation stream) run beside the solver phases and the ten values add up to more than
     // the total; phase_timing == 1 runs everything on one stream.
     PhaseClock clk, pclk, total;
+    double t_entry = 0.0;  // host wall time at the call's entry
 };
 
 static void keep_seq(const FlowPass& S, int slot) {
@@ -584,6 +602,7 @@ static void start_clocks(FlowPass& S) {
     S.clk.only_sor = S.pclk.only_sor = (!h->phase_events && S.P.phase_timing == 0) || S.P.phase_timing == 2;
     h->sor_launches = 0;
     h->sor_log.clear();
+    std::fill(h->chain_stats, h->chain_stats + 4, 0LL);
     S.clk.stamps = true;  // the main stream's phase boundaries are in-kernel stamps, not events (flow_internal.h)
     h->stamps_used = 0;
     h->next_stamp = nullptr;
@@ -777,10 +796,16 @@ static int enter_level(FlowPass& S, int k, int pw, int ph, bool fold_warp) {
     return PAPOF_OK;
 }
 
+// [Also built: the coarsest level's solves enqueued behind that level's share of the preparation and in FRONT of the finer
+// levels' (frames on the device, pyramid from level 0; every stream's list of work unchanged).  The host then gets here 36 us
+// after the call's entry (papof_last_host_times) and the main stream's first kernel starts at 138 us instead of 204, yet a
+// 1080p pair is no faster: 9.284 vs 9.275 ms, 26.250 vs 26.235 on the reference schedule (profiles/iteration_fold_ab.txt).
+// Removed.]
 static int solve_levels(FlowPass& S) {
     papof_handle* h = S.h;
     const CallPlan& cp = S.cp;
     LapGuard* const lg = S.lg;
+    h->host_first_solve_sec = wall() - S.t_entry;
     if (lg && lg->guard())  // LapPara starts every call at 0.02 (src/OpticalFlow.cpp:773-775)
         PAPOF_HIP(hipMemcpyAsync(lg->lap, h->lap_init_dev, 8 * sizeof(double), hipMemcpyDeviceToDevice, S.main_stream));
     int pw = 0, ph = 0;
@@ -792,13 +817,14 @@ static int solve_levels(FlowPass& S) {
         const bool tiny_k = S.exact && sor_tiny_fits(h, lh, lw, cp.n_sor[k]);  // k_sor_tiny level
         if (!tiny_k) PAPOF_TRY(sor_bind(h, S.B.sp, lh, lw, cp.n_sor[k]));
         // (no final warp: the next level warps anew, and the result is the bicubic warp of the originals)
-        const LevelSolve s{.B = S.B, .f1 = S.F1[k], .f2 = S.F2[k], .warp = S.warp, .H = lh, .W = lw, .fc = cp.fc,
-                           .alpha = S.P.alpha, .omega = S.P.omega, .n_outer = cp.n_outer[k], .n_inner = S.P.n_inner,
-                           .n_sor = cp.n_sor[k], .mode = S.P.sor_mode, .im1s_ready = S.S1[k], .final_warp = false,
-                           .counters = S.exact ? &S.counters : nullptr, .out_u = k == 0 ? S.d_vx : nullptr,
-                           .out_v = k == 0 ? S.d_vy : nullptr, .fold_warp = !S.B.bgx && !S.B.gm, .lg = lg, .level = k};
+        LevelSolve s{.B = S.B, .f1 = S.F1[k], .f2 = S.F2[k], .warp = S.warp, .H = lh, .W = lw, .fc = cp.fc,
+                     .alpha = S.P.alpha, .omega = S.P.omega, .n_outer = cp.n_outer[k], .n_inner = S.P.n_inner,
+                     .n_sor = cp.n_sor[k], .mode = S.P.sor_mode, .im1s_ready = S.S1[k], .final_warp = false,
+                     .counters = S.exact ? &S.counters : nullptr, .out_u = k == 0 ? S.d_vx : nullptr,
+                     .out_v = k == 0 ? S.d_vy : nullptr, .fold_warp = !S.B.bgx && !S.B.gm, .lg = lg, .level = k};
         PAPOF_TRY(enter_level(S, k, pw, ph, s.fold_warp));
         if (!tiny_k) PAPOF_TRY(sor_reset_planes(h, S.B.sp));
+        if (!tiny_k && S.exact) PAPOF_TRY(sor_reset_dudv(h, S.B.sp, &s.dudv_cleared));
         PAPOF_TRY(smooth_flow(h, s, S.clk, S.u, S.v, S.u2, S.v2));
         pw = lw;
         ph = lh;
@@ -891,6 +917,7 @@ int flow_pass(papof_handle* h, const FrameIn& fa, const FrameIn& fb, SeqOp op, i
               const papof_tensor* init = nullptr) {
     const double t_entry = wall();
     FlowPass S{h, fa, fb, op, H, W, C, P, d_vx, d_vy, d_warp, lg, init};
+    S.t_entry = t_entry;
     // 1. the plan
     PAPOF_TRY(call_plan(H, W, C, levels, P, S.cp));
     const size_t need = arena_bytes_for(H, W, C, levels, S.cp.n_sor_max, P.ratio);
@@ -1935,7 +1962,13 @@ int papof_last_host_times(papof_handle* h, double out[3]) {
     if (!h || !out) return PAPOF_EINVAL;
     out[0] = h->host_enqueue_sec;
     out[1] = h->host_wait_sec;
-    out[2] = 0.0;
+    out[2] = h->host_first_solve_sec;
+    return PAPOF_OK;
+}
+
+int papof_last_chain_stats(papof_handle* h, long long out[4]) {
+    if (!h || !out) return PAPOF_EINVAL;
+    std::copy(h->chain_stats, h->chain_stats + 4, out);
     return PAPOF_OK;
 }
 

@@ -244,6 +244,11 @@ struct papof_handle {
     int sor_resident = 0;            // tasks per launch of the exact-order kernels; 0 = 8 per CU (sor.hip: resident_tasks)
     int sor_skip_dead = 1;           // k_sor_exact: lanes whose row lies outside the image neither load nor store (PAPOF_SOR_DEAD=0: A/B)
     unsigned* sor_prog_next = nullptr;  // cleared progress counters for the NEXT sor_solve() (else it clears its own)
+    // the current / last call's k_flow_system launches, those of them that carried an increment, k_update_warp_phi launches and
+    // per-solve (du, dv) clears (papof_last_chain_stats)
+    long long chain_stats[4] = {0, 0, 0, 0};
+    // the NEXT sor_solve() finds (du, dv) cleared since its layout was bound (sor_reset_dudv), solves on it in between or not
+    bool sor_dudv_cleared = false;
     int sor_launches = 0;            // exact-order solver kernels launched by the current / last call (measurement: bench.py)
     // one entry per sor_solve() of the current / last call, in stream order (measurement: bench.py's roofline.by_level);
     // kind: 0 k_sor_exact, 1 k_sor_fused, 2 k_sor_group, 3 k_sor_blocked red-black, 4 k_sor_blocked Jacobi, 6 k_sor_tiny
@@ -274,6 +279,7 @@ struct papof_handle {
     // which way the pairs of papof_flow_batch* went (papof_batch_stats): launch chains, solver pairs inside them, frame pairs run
     // singly because the chain does not cover them or had no room, frame pairs run again singly for an unproven guard
     long long batch_chains = 0, batch_chain_pairs = 0, batch_singles = 0, batch_reruns = 0;
+    double host_first_solve_sec = 0.0;  // ... from the call's entry until the host began to enqueue the coarsest level's solves
     double host_enqueue_sec = 0.0, host_wait_sec = 0.0;  // host wall time of the last call: enqueueing / waiting (papof_last_host_times)
     // Host buffers handed to the call itself (flow_host -> flow_device): the call then issues the PCIe copies where they
     // overlap device work -- frame 2 uploads while frame 1's share of the preparation runs, (vx, vy) go back beside the
@@ -399,7 +405,10 @@ int assemble_system(papof_handle* h, const double* blend, const double* imdt, co
 int flow_system(papof_handle* h, const double* im1, const double* im2, const double* u, const double* v, const double* im1s,
                 int H, int W, int planes, double alpha, double omega, const SorPlanes& out, unsigned* wit = nullptr,
                 int row0 = 0, int row1 = -1,  // rows row0 .. row1-1 (a rank's range of rows: tiles.hip)
-                int batch = 1, const BatchK* bk = nullptr);  // pairs of a batch (blockIdx.y), each pointer advanced by its stride
+                int batch = 1, const BatchK* bk = nullptr,  // pairs of a batch (blockIdx.y), each pointer advanced by its stride
+                // the flow is (u, v) + the increment the last solve left in `inc`, and is written to (u_out, v_out): the update
+                // of the previous outer iteration, carried by this launch (whole planes of one pair only)
+                const SorPlanes* inc = nullptr, double* u_out = nullptr, double* v_out = nullptr);
 int lap_scratch_doubles();
 int lap_rows_check(papof_handle* h, const double* im1, const double* im2, const double* u, const double* v, int H, int W,
                    int C, int r0, int r1, unsigned* wit, unsigned* val, unsigned mark);  // rows r0 .. r1-1, every pixel
@@ -473,6 +482,9 @@ int sor_alloc_planes(Arena& A, int H, int W, int mode, int n_sor_cap, SorPlanes&
 int sor_bind(papof_handle* h, SorPlanes& sp, int H, int W, int n_sor);  // choose the layout of the next solves (skew mode)
 int sor_group_size(const papof_handle* h, int H, int W, int n_sor);   // sweeps per workgroup the solver will use
 int sor_reset_planes(papof_handle* h, const SorPlanes& sp);    // zero all padding of the bound layout
+// ... and the (du, dv) planes of the bound layout where ONE clear serves every solve on it (k_sor_exact / k_sor_fused); *done says
+// whether it did: the caller hands that to each of those solves (papof_handle::sor_dudv_cleared)
+int sor_reset_dudv(papof_handle* h, const SorPlanes& sp, bool* done);
 int sor_reset_planes_batch(papof_handle* h, const SorPlanes& sp, int batch, size_t stride);  // ... of every pair of a batch
 int sor_probe_dpp(papof_handle* h);  // sets h->use_dpp after checking the cross-lane DPP semantics on the device
 

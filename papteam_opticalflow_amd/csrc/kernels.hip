@@ -1218,6 +1218,11 @@ __global__ __launch_bounds__(256) void k_assemble_skew(const double* __restrict_
 // clamp(p + l) up): the warp on the tile + 4, its smoothing on + 2 (which is where the blend and imdt live), the derivatives on
 // the tile.  phi of the tile (and its upper / left neighbours) is computed from (u, v) into LDS.  Every expression and its
 // order are those of the two kernels it replaces: same bits.
+// The flow of the tile + 4 is read from memory ONCE, by the tap pass, and parked in LDS: phi and the cell's cross of (u, v)
+// take it from there.  `sdu` (null: none): the increment the previous outer iteration's solve left, where and as
+// k_update_warp_phi reads it -- the flow is then u + du, v + dv everywhere in this kernel (that kernel's load, add: its bits),
+// and the tile's own cells write it to (u_out, v_out), the OTHER pair of planes: neighbouring blocks read the old pair and the
+// increment only.  A run-time, wave-uniform argument, and all of it in front of the channel loop.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFT = 16, kFH = 4, kFW = kFT + 2 * kFH;  // tile rows and columns, halo, tile rows with halo
 // [162 - 164 registers (at most 168: three workgroups per CU, tests/test_codegen_flow_system.py); forcing four or five waves per
@@ -1240,8 +1245,10 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
                                                      const double* __restrict__ im1s, int H, int W, double alpha,
                                                      double omega, SkewIdx sk, SixPlanes out, Taps g, Taps d,
                                                      unsigned long long* stamp, unsigned* __restrict__ wit, double wit_thr,
-                                                     unsigned mark, int row0, int row1, BatchK bk) {
-    if (BATCH) {  // blockIdx.y: the pair of a batch (common.h: BatchK)
+                                                     unsigned mark, int row0, int row1, BatchK bk,
+                                                     const double* __restrict__ sdu, const double* __restrict__ sdv,
+                                                     double* __restrict__ u_out, double* __restrict__ v_out) {
+    if (BATCH) {  // blockIdx.y: the pair of a batch (common.h: BatchK; no increment there: flow_system())
         const size_t p = blockIdx.y;
         im1s += batch_frames(bk, p, im1, im2);  // (a backward pair: image 1's smoothed features are frame 2's)
         u += p * bk.uv;
@@ -1259,6 +1266,7 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     __shared__ double it[kFT][kFT + 1];             // imdt of the tile
     __shared__ double ph[kFT + 1][kFT + 1 + 1];     // phi, pixels (ib - 1 .. ib + 15) x (j0 - 1 .. j0 + 15)
     __shared__ double stage[6][kFT][kFT + 1];
+    __shared__ double fu[kFW][HWc + 1], fv[kFW][HWc + 1];  // the flow (with the increment) on the pixels of raw
     stamp_now(stamp);
     // Workgroups are dealt round-robin over the 8 XCDs (observed; speed only): give each XCD a contiguous run of tiles, so
     // that the halo pixels neighbouring tiles both gather are found in that XCD's L2 (as k_sor_blocked does)
@@ -1316,8 +1324,24 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
             double x = 0.0, y = 0.0;  // (a cell outside the image: any valid position, its value is not used)
             t_out[q] = false;
             if (t_in[q]) {
-                y = i + v[o];
-                x = j + u[o];
+                double pu = u[o], pv = v[o];
+                if (sdu != nullptr) {
+                    double a, b;
+                    if (SKEW) {
+                        const double2s c = reinterpret_cast<const double2s*>(sdu)[dudv_cell(i, j, sk)];
+                        a = c.x;
+                        b = c.y;
+                    } else {
+                        a = sdu[o];
+                        b = sdv[o];
+                    }
+                    pu += a;
+                    pv += b;
+                }
+                (&fu[0][0])[t_ra[q]] = pu;  // (the third slot: by every wave, the same value)
+                (&fv[0][0])[t_ra[q]] = pv;
+                y = i + pv;
+                x = j + pu;
                 t_out[q] = leaves_image(x, y, W, H);
                 if (t_out[q]) {
                     x = j;
@@ -1338,21 +1362,23 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
     // a pixel that leaves the image takes frame 1's value: loaded (beside the gathers, which such a pixel does around itself in
     // frame 2, unused) only in a wave that has such a pixel -- a scalar test
     const bool wout = __ballot(t_out[0] || t_out[1] || t_out[2]) != 0ull;
-    // ---- phi of the tile and its upper / left neighbours (no increment)
+    __syncthreads();
+    // ---- phi of the tile and its upper / left neighbours, from the parked flow: pixel (i, j), its right and its lower
+    // neighbour are pixels of the tile + 4 on rows the operands are valid on (i + 1 <= row1 < vy1 where it is used)
     for (int c = tid; c < (kFT + 1) * (kFT + 1); c += NT) {
         const int r = c / (kFT + 1), cc = c - r * (kFT + 1);
         const int i = ib - 1 + r, j = j0 - 1 + cc;
         if (i < 0 || i >= min(H, row1) || j < 0 || j >= W) continue;
-        const size_t o = (size_t)i * W + j;  // (phi_at()'s loads in place: through the function the register allocation of
-        const double uc = u[o], vc = v[o];    // every instance changes; with them here the code is the parent's)
+        const double *const pu = &fu[r + kFH - 1][cc + kFH - 1], *const pv = &fv[r + kFH - 1][cc + kFH - 1];
+        const double uc = pu[0], vc = pv[0];
         double ur = 0.0, vr = 0.0, ud = 0.0, vd = 0.0;
         if (j < W - 1) {
-            ur = u[o + 1];
-            vr = v[o + 1];
+            ur = pu[1];
+            vr = pv[1];
         }
         if (i < H - 1) {
-            ud = u[o + W];
-            vd = v[o + W];
+            ud = pu[HWc + 1];
+            vd = pv[HWc + 1];
         }
         ph[r][cc] = phi_value(uc, vc, ur, vr, ud, vd, j < W - 1, i < H - 1);
     }
@@ -1523,7 +1549,16 @@ __global__ __launch_bounds__(256, 1) void k_flow_system(const double* __restrict
         const size_t o = (size_t)oi * W + oj;
         const Nbrs n = nbrs_at(oi, oj, H, W);
         const PhiAround p{ph[orow + 1][ocol + 1], n.left ? ph[orow + 1][ocol] : 0.0, n.up ? ph[orow][ocol + 1] : 0.0};  // phi from LDS
-        const SystemCell c = system_cell<true>(s, p, cross_at<true>(u, o, W, n), cross_at<true>(v, o, W, n), n, alpha, omega);
+        // cross_at<true>() on the parked flow: a neighbour that does not exist reads the cell itself and is not used
+        const auto cross = [&](const double* c) {
+            return Cross{c[0], c[n.left ? -1 : 0], c[n.right ? 1 : 0], c[n.up ? -(HWc + 1) : 0], c[n.down ? HWc + 1 : 0]};
+        };
+        const Cross cu = cross(&fu[orow + kFH][ocol + kFH]), cv = cross(&fv[orow + kFH][ocol + kFH]);
+        if (u_out != nullptr) {  // the flow with the increment: what k_update_warp_phi would have written
+            u_out[o] = cu.c;
+            v_out[o] = cv.c;
+        }
+        const SystemCell c = system_cell<true>(s, p, cu, cv, n, alpha, omega);
         if (SKEW) {
             stage_cell(stage, orow, ocol, c);
         } else {
@@ -2334,8 +2369,13 @@ int assemble_system(papof_handle* h, const double* blend, const double* imdt, co
 // feature channels); returns PAPOF_EINVAL where it does not apply
 int flow_system(papof_handle* h, const double* im1, const double* im2, const double* u, const double* v, const double* im1s,
                 int H, int W, int planes, double alpha, double omega, const SorPlanes& out, unsigned* wit, int row0, int row1,
-                int batch, const BatchK* bk) {
+                int batch, const BatchK* bk, const SorPlanes* inc, double* u_out, double* v_out) {
     if (planes != 5 && planes != 3) return PAPOF_EINVAL;
+    // an increment: whole planes of one pair, in the layout of the operands, and the other pair of planes for the sums
+    if (inc && (batch > 1 || row0 != 0 || (row1 >= 0 && row1 != H) || inc->skew != out.skew || !inc->du || !u_out || !v_out ||
+                u_out == u || v_out == v))
+        return PAPOF_EINVAL;
+    if (!inc && (u_out || v_out)) return PAPOF_EINVAL;
     if ((unsigned long long)H * (unsigned long long)W > (1ull << 29)) return PAPOF_EINVAL;  // 32-bit byte offsets into a plane
     int rc;
     if (!rows_of(row0, row1, H, rc)) return rc;
@@ -2346,7 +2386,10 @@ int flow_system(papof_handle* h, const double* im1, const double* im2, const dou
     }, planes == 5, out.skew, batch > 1, W == 1);
     hipLaunchKernelGGL(kern, grid, dim3(kFT * kFT), 0, h->stream, im1, im2, u, v, im1s, H, W, alpha, omega,
                        out.skew ? skew_idx(out) : kNoSkew, six, smooth5_taps(), deriv5_taps(),
-                       take_stamp(h), wit, lap_wit_threshold(H, W), h->lap_epoch, row0, row1, bk ? *bk : kNoBatch);
+                       take_stamp(h), wit, lap_wit_threshold(H, W), h->lap_epoch, row0, row1, bk ? *bk : kNoBatch,
+                       inc ? inc->du : nullptr, inc ? inc->dv : nullptr, u_out, v_out);
+    h->chain_stats[0]++;
+    h->chain_stats[1] += inc != nullptr;
     LAUNCH_CHECK();
     return PAPOF_OK;
 }
@@ -2370,6 +2413,7 @@ int update_warp_phi(papof_handle* h, const SorPlanes& sp, const double* u, const
     hipLaunchKernelGGL(kern, grid, dim3(BX, BY), 0, h->stream, sp.du, sp.dv, sp.skew ? skew_idx(sp) : kNoSkew, u, v, u_out,
                        v_out, im1, im2, warp, phi_out, H, W, planes, do_warp ? 1 : 0, take_stamp(h), row0, row1, wit,
                        lap_wit_threshold(H, W), h->lap_epoch, bk ? *bk : kNoBatch);
+    h->chain_stats[2]++;
     LAUNCH_CHECK();
     return PAPOF_OK;
 }

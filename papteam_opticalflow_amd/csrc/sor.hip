@@ -2031,6 +2031,8 @@ int sor_plan(const papof_handle* h, int H, int W, int n_sor, int mode, int* laun
 int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, double omega, int n_sor, int mode,
               const SorBatch* bt) {
     const double nalpha = -alpha, om1 = 1 - omega;
+    const bool dudv_cleared = h->sor_dudv_cleared;  // (of this solve only, whatever becomes of it)
+    h->sor_dudv_cleared = false;
     if (n_sor <= 0) return PAPOF_EINVAL;
     const int batch = bt ? bt->n : 1;
     if (batch < 1 || (bt && mode != PAPOF_SOR_EXACT)) return PAPOF_EINVAL;
@@ -2092,15 +2094,20 @@ int sor_solve(papof_handle* h, const SorPlanes& sp, int H, int W, double alpha, 
         if (std::getenv("PAPOF_SOR_INJECT_ABORT")) PAPOF_HIP(hipMemsetAsync(h->sync_words, 1, sizeof(unsigned), h->stream));
         // The (du, dv) planes.  The grouped kernel reads du = dv = 0 before the first sweep (src/OpticalFlow.cpp:452-453) and
         // its halo rows from memory.  k_sor_exact / k_sor_fused read those zeros as out-of-range offsets and write every
-        // position 1 .. n_iter * R of a plane before anybody reads it, so all they NEED cleared are the tail positions
-        // that ghost lanes read up to 65 steps ahead and nobody writes (one strided memset would do).  Yet
-        // clearing both planes entirely is what is done, because it is FASTER, its own cost included: the
-        // memset leaves the planes resident in the Infinity Cache, and every level's solve then runs 4-5 % faster
-        // (1920x1080: 0.941 -> 0.900 ms, 607x341: 0.354 -> 0.338 ms, a whole 1080p pair 11.98 -> 11.56 ms).
+        // position 1 .. n_iter * R of a plane before anybody reads it, so all they NEED cleared are the cells that are read
+        // and written by nobody: those of rows outside the image, and the tail positions that ghost lanes read up to 65 steps
+        // ahead.  They are the same in every solve on one layout, so where the caller has cleared the planes since it bound
+        // the layout (sor_reset_dudv; flow_pass, once per level: `dudv_cleared`) nothing is cleared here.  [Round 1 kept the
+        // fill per solve because it was FASTER, its own cost included -- it left the planes resident in the Infinity Cache:
+        // 1920x1080 0.941 -> 0.900 ms per solve.  With k_flow_system, which reads the planes' last increment right in front of
+        // a solve, that no longer holds: without the fills the solver kernels take what they took (7.521 vs 7.525 ms per
+        // 1080p pair) and the pair loses the fills and their gaps, 9.341 -> 9.275 ms (profiles/iteration_fold_ab.txt).]
+        // A solve without that hand-over (the stage entry points, bands, strips) clears as ever.
         if (bt) {  // every pair's two planes in one fill node (the pairs' planes lie bt->d doubles apart)
             PAPOF_TRY(fill_pairs(h, sp.du, bt->d * sizeof(double), sd.nd * 16, batch));
-        } else {
+        } else if (!(dudv_cleared && sd.group == 1)) {
             PAPOF_HIP(hipMemsetAsync(sp.du, 0, (sd.nd + sd.nh) * 16, h->stream));  // both planes (+ the halo rows)
+            h->chain_stats[3]++;
         }
         mark(1);  // everything below is solver kernels
         if (sd.group > 1) {
@@ -2324,7 +2331,18 @@ static void pack_planes(SorPlanes& sp) {
 int sor_reset_planes(papof_handle* h, const SorPlanes& sp) {
     if (!sp.skew) return PAPOF_OK;
     PAPOF_HIP(hipMemsetAsync(sp.phi, 0, 3 * plane_pitch(sp.sd) * sizeof(double), h->stream));
-    return PAPOF_OK;  // the (du, dv) planes are cleared by every solve
+    return PAPOF_OK;  // the (du, dv) planes: sor_reset_dudv(), or every solve
+}
+// k_sor_exact / k_sor_fused write every cell of (du, dv) that a later sweep reads and take sweep 0's zeros from switched-off
+// offsets (kOob, where a task's lanes are set up); what they read and never write -- the cells of rows outside the image, the positions
+// a ghost lane reads ahead of the last step -- is the same in every solve on one layout, so zeros put there once stay there.
+// k_sor_group reads its zeros and its halo rows from memory: it keeps the fill in front of every solve.
+int sor_reset_dudv(papof_handle* h, const SorPlanes& sp, bool* done) {
+    *done = false;
+    if (!sp.skew || sp.sd.group != 1) return PAPOF_OK;
+    PAPOF_HIP(hipMemsetAsync(sp.du, 0, sp.sd.nd * 16, h->stream));
+    *done = true;
+    return PAPOF_OK;
 }
 
 // ... of every pair of a batch at once: the pairs' operand blocks lie `stride` doubles apart (api.hip / batch.hip: flow_batch)
