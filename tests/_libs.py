@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_SO = os.path.join(ORACLE_DIR, "libpapof_oracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libpapof_ref.so")
+ORACLE_BOUND = 1e-9  # max-abs of the device's flow and warpI2 against the oracle, wherever a GPU test holds a flow call to it
 
 _D = ctypes.POINTER(ctypes.c_double)
 _I = ctypes.POINTER(ctypes.c_int)
