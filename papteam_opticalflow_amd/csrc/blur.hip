@@ -152,15 +152,15 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_motion_blur(const Blur
 #pragma unroll
     for (int side = 0; side < 2; side++)
         if (has[side]) {
-            const long long of = (f - 1 + side) * a.fw.stride[0] + r * a.fw.stride[1] + x * a.fw.stride[2];
-            const long long ob = (f - 1 + side) * a.bw.stride[0] + r * a.bw.stride[1] + x * a.bw.stride[2];
+            const long long of = PAPOF_AT(a.fw, f - 1 + side, r, x);
+            const long long ob = PAPOF_AT(a.bw, f - 1 + side, r, x);
             fl[side][0] = load_flow(a.fw, of);
             fl[side][1] = load_flow(a.fw, of + a.fw.stride[3]);
             fl[side][2] = load_flow(a.bw, ob);
             fl[side][3] = load_flow(a.bw, ob + a.bw.stride[3]);
         }
     const long long pix = r * a.fr.stride[1] + x * a.fr.stride[2];  // the pixel within a frame
-    const long long outp = f * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    const long long outp = PAPOF_AT(a.out, f, r, x);
     for (int ch0 = 0; ch0 < a.C; ch0 += NC) {
         const long long chan = ch0 * a.fr.stride[3];
         double centre[NC], acc[NC];

@@ -78,13 +78,12 @@ __global__ __launch_bounds__(kBTX* kBTY) void k_bundle_sums(const BundleArgs a, 
             const long long sr = sr0 + (long long)j * kBTY;
             if (sr >= a.Hs) break;
             const long long r = sr * a.step;
-            const long long o = i * a.flow.stride[0] + r * a.flow.stride[1] + x * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, i, r, x);
             const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
             const double rd = (double)r, X = xd + u, Y = rd + v;
             bool valid = X >= 0 && X <= W1 && Y >= 0 && Y <= H1;  // false for a NaN or an infinity
             if (valid && a.occ.data)
-                valid = static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + r * a.occ.stride[1] +
-                                                                      x * a.occ.stride[2]] == 0;
+                valid = load_u8(a.occ, PAPOF_AT(a.occ, i, r, x)) == 0;
             if (!valid) continue;
             const double py = (rd - a.cy) / f;
             const double qx = (R[0] * px + R[1] * py) + R[2], qy = (R[3] * px + R[4] * py) + R[5];

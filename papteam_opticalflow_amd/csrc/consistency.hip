@@ -36,7 +36,6 @@ constexpr int kJX = 64, kJW = 4, kJR = 8;      // k_tc_jacobi: a region of 64 co
 constexpr int kJY = kJW * kJR;
 constexpr int kMaxDepth = 15;                  // sweeps per launch: the core tile (64 - 2 g) x (32 - 2 g) stays >= 34 x 2
 constexpr int kDefaultDepth = 8;               // measured: DESIGN.md 18, profiles/consistency_probe.txt
-constexpr int kMaxC = 4;
 constexpr int kMaxIters = 1 << 16;
 
 // One pyramid level of the start value, planar: a (h w confidences), v (C planes of h w values).  Level 0's v is r.
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_first(const papof_tensor src, c
     const long long r = i / W, c = i % W;
     const long long o = r * src.stride[1] + c * src.stride[2], q = r * out.stride[1] + c * out.stride[2];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) store(out, q + ch * out.stride[3], load_frame<-1>(src, o + ch * src.stride[3], lut));
 }
 
@@ -83,19 +82,19 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_setup(const SetupArgs A, const 
     if (i >= (long long)H * W) return;
     const long long HW = (long long)H * W;
     const int x = (int)(i % W);
-    const long long r = i / W, pair = t - 1;
+    const long long r = i / W, pair = chain_pair(t, -1, 1);  // (frame t - 1's output is sampled: the pair's index)
     double X, Y;
-    const bool valid = hop(A.bw, A.fw, pair, H, W, A.check, A.a1, A.a2, (double)x, (double)r, X, Y);
-    double w = 0.0, a = 0.0, res[kMaxC];
+    const bool valid = chain_hop(A, pair, -1, H, W, (double)x, (double)r, X, Y);  // (sampler.h, the direction rule)
+    double w = 0.0, a = 0.0, res[kMaxChannels];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++) res[ch] = 0.0;
+    for (int ch = 0; ch < kMaxChannels; ch++) res[ch] = 0.0;
     if (valid) {
         const Bilinear k = taps_at(X, Y, H, W);
-        const long long pix = t * A.fr.stride[0] + r * A.fr.stride[1] + x * A.fr.stride[2];
+        const long long pix = PAPOF_AT(A.fr, t, r, x);
         const long long prev = pair * A.fr.stride[0];
         double D = 0.0;
 #pragma unroll
-        for (int ch = 0; ch < kMaxC; ch++)
+        for (int ch = 0; ch < kMaxChannels; ch++)
             if (ch < A.CI) {
                 const double d = load_frame<-1>(A.fr, pix + ch * A.fr.stride[3], lut) -
                                  sample_frame<-1>(A.fr, prev + ch * A.fr.stride[3], k, lut);
@@ -105,10 +104,10 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_setup(const SetupArgs A, const 
         w = A.sigma > 0 ? A.lam / (1.0 + D / A.s2) : A.lam;
         if (w > 0) {  // (false for a NaN)
             a = w / A.lam;
-            const long long pp = t * A.pr.stride[0] + r * A.pr.stride[1] + x * A.pr.stride[2];
+            const long long pp = PAPOF_AT(A.pr, t, r, x);
             const long long ob = pair * A.out.stride[0];
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < A.CP)
                     res[ch] = sample_frame<-1>(A.out, ob + ch * A.out.stride[3], k, lut) -
                               load_frame<-1>(A.pr, pp + ch * A.pr.stride[3], lut);
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_setup(const SetupArgs A, const 
     L0.a[i] = a;
     wv[i] = w;
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < A.CP) L0.v[ch * HW + i] = res[ch];
 }
 
@@ -129,9 +128,9 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_pull(const Lv F, const Lv G, in
     const long long i = (long long)blockIdx.x * kTcBlock + threadIdx.x;
     if (i >= G.h * G.w) return;
     const long long r = i / G.w, c = i % G.w, fpx = F.h * F.w, gpx = G.h * G.w;
-    double s[kMaxC], A = 0.0;
+    double s[kMaxChannels], A = 0.0;
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++) s[ch] = 0.0;
+    for (int ch = 0; ch < kMaxChannels; ch++) s[ch] = 0.0;
 #pragma unroll
     for (int a = 0; a <= 1; a++)
 #pragma unroll
@@ -142,11 +141,11 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_pull(const Lv F, const Lv G, in
             const double conf = F.a[q];
             A += conf;
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < C) s[ch] += conf * F.v[ch * fpx + q];
         }
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) G.v[ch * gpx + i] = A > 0 ? s[ch] / A : 0.0;
     G.a[i] = A < 1.0 ? A : 1.0;
 }
@@ -165,7 +164,7 @@ __global__ __launch_bounds__(kTcBlock) void k_tc_push(const Lv F, const Lv G, do
     const Bilinear k = taps_at(X, Y, (int)G.h, (int)G.w);
     const double a = F.a[i];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) {
             double g = 0.0;
 #pragma unroll
@@ -254,8 +253,8 @@ __global__ __launch_bounds__(kJX* kJW) void k_tc_jacobi(const JacobiArgs A, long
                     A.dst[ch * HW + p[j]] = d;
                 } else {
                     const long long row = p[j] / A.W;
-                    const long long pp = A.t * A.pr.stride[0] + row * A.pr.stride[1] + col * A.pr.stride[2];
-                    const long long q = A.t * A.out.stride[0] + row * A.out.stride[1] + col * A.out.stride[2];
+                    const long long pp = PAPOF_AT(A.pr, A.t, row, col);
+                    const long long q = PAPOF_AT(A.out, A.t, row, col);
                     store(A.out, q + ch * A.out.stride[3], load_frame<-1>(A.pr, pp + ch * A.pr.stride[3], lut) + d);
                 }
             }
@@ -351,7 +350,7 @@ bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; 
 using namespace papof;
 
 extern "C" long long papof_consistency_workspace(int height, int width, int c_out) {
-    if (height < 1 || width < 1 || c_out < 1 || c_out > kMaxC) return -1;
+    if (height < 1 || width < 1 || c_out < 1 || c_out > kMaxChannels) return -1;
     if ((long long)height * width > kMaxTiles * kTcBlock) return -1;
     long long n = 0;
     const auto s = level_sizes(height, width);
@@ -365,7 +364,7 @@ extern "C" int papof_temporal_consistency_tensor(papof_handle* h, int n_frames, 
                                                  const papof_tensor* first, double lambda, double sigma, int iters,
                                                  int use_check, double alpha1, double alpha2, const papof_tensor* out,
                                                  void* workspace, long long workspace_bytes, void* stream) {
-    if (!h || n_frames < 2 || height < 1 || width < 1 || c_frames < 1 || c_frames > kMaxC) return PAPOF_EINVAL;
+    if (!h || n_frames < 2 || height < 1 || width < 1 || c_frames < 1 || c_frames > kMaxChannels) return PAPOF_EINVAL;
     if (!std::isfinite(lambda) || lambda < 0 || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
     if (iters < 0 || iters > kMaxIters || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     const long long need = papof_consistency_workspace(height, width, c_out);

@@ -34,7 +34,6 @@ namespace papof {
 namespace {
 
 constexpr int kMaxSamples = 64;
-constexpr int kMaxC = 4;
 constexpr int kMaxRadius = 4;
 constexpr int kMaxIters = 256;
 constexpr long long kBudget = 2LL << 30;  // bytes papof_deblur_workspace asks for at most (one target's share if that is more)
@@ -59,17 +58,17 @@ struct DeblurArgs {
 // slot j of target t is frame t, t + 1, t - 1, t + 2, t - 2, ...
 __device__ __forceinline__ long long slot_frame(long long t, int j) { return j & 1 ? t + (j + 1) / 2 : t - j / 2; }
 
-// The chain of the point (X, Y) from frame a to frame b: hops forward through flow_fw (checked with flow_bw) or backward
-// through flow_bw (checked with flow_fw).  False, for good, once a hop fails; a == b: the point, alive.
+// The chain of the point (X, Y) from frame a to frame b, forward or backward (sampler.h, the direction rule).  False, for
+// good, once a hop fails; a == b: the point, alive.
 __device__ __forceinline__ bool chain_to(const DeblurArgs& p, long long a, long long b, double& X, double& Y) {
     double nX, nY;
     for (long long f = a; f < b; f++) {
-        if (!hop(p.fw, p.bw, f, p.H, p.W, p.check, p.a1, p.a2, X, Y, nX, nY)) return false;
+        if (!hop_from(p, f, +1, X, Y, nX, nY)) return false;
         X = nX;
         Y = nY;
     }
     for (long long f = a; f > b; f--) {
-        if (!hop(p.bw, p.fw, f - 1, p.H, p.W, p.check, p.a1, p.a2, X, Y, nX, nY)) return false;
+        if (!hop_from(p, f, -1, X, Y, nX, nY)) return false;
         X = nX;
         Y = nY;
     }
@@ -96,12 +95,12 @@ __device__ __forceinline__ void velocity(const DeblurArgs& p, long long s, doubl
 __device__ __forceinline__ void velocity_at_pixel(const DeblurArgs& p, long long s, int x, long long r, double& vx, double& vy) {
     double fu = 0.0, fv = 0.0, bu = 0.0, bv = 0.0;
     if (s < p.T - 1) {
-        const long long o = s * p.fw.stride[0] + r * p.fw.stride[1] + x * p.fw.stride[2];
+        const long long o = PAPOF_AT(p.fw, s, r, x);
         fu = load_flow(p.fw, o);
         fv = load_flow(p.fw, o + p.fw.stride[3]);
     }
     if (s > 0) {
-        const long long o = (s - 1) * p.bw.stride[0] + r * p.bw.stride[1] + x * p.bw.stride[2];
+        const long long o = PAPOF_AT(p.bw, s - 1, r, x);
         bu = load_flow(p.bw, o);
         bv = load_flow(p.bw, o + p.bw.stride[3]);
     }
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_ingest(const De
     if (!tile_pixel(p, tile0, x, r)) return;
     const long long g = g0 + blockIdx.y, plane = (long long)p.H * p.W * C;
     double* L = p.ws + g * (2 * p.R + 2) * plane + (r * p.W + x) * C;
-    const long long pix = (p.t0 + g) * p.fr.stride[0] + r * p.fr.stride[1] + x * p.fr.stride[2];
+    const long long pix = PAPOF_AT(p.fr, p.t0 + g, r, x);
 #pragma unroll
     for (int ch = 0; ch < C; ch++) L[ch] = fmax(load_frame<FD>(p.fr, pix + ch * p.fr.stride[3], lut), 0.0);
 }
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_ratio(const Deb
     }
     double est[C];
     line_sum<C>(p, base, X, Y, vx, vy, 1.0, est);
-    const long long pix = s * p.fr.stride[0] + r * p.fr.stride[1] + x * p.fr.stride[2];
+    const long long pix = PAPOF_AT(p.fr, s, r, x);
 #pragma unroll
     for (int ch = 0; ch < C; ch++) {
         const double b = fmax(load_frame<FD>(p.fr, pix + ch * p.fr.stride[3], lut), 0.0);
@@ -227,7 +226,7 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_update(const De
         n += 1;
     }
     double* L = base + (r * p.W + x) * C;
-    const long long o = t * p.out.stride[0] + r * p.out.stride[1] + x * p.out.stride[2];
+    const long long o = PAPOF_AT(p.out, t, r, x);
 #pragma unroll
     for (int ch = 0; ch < C; ch++) {
         double v = L[ch];
@@ -238,12 +237,12 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_deblur_update(const De
             L[ch] = v;
     }
     if (p.last && p.sup.data)
-        static_cast<unsigned char*>(p.sup.data)[t * p.sup.stride[0] + r * p.sup.stride[1] + x * p.sup.stride[2]] = (unsigned char)n;
+        store_u8(p.sup, PAPOF_AT(p.sup, t, r, x), (unsigned char)n);
 }
 
 // bytes of one target's share of the workspace; < 0: refused
 long long per_target_bytes(long long n_frames, long long h, long long w, long long c, long long radius) {
-    if (n_frames < 2 || h < 1 || w < 1 || c < 1 || c > kMaxC || radius < 0 || radius > kMaxRadius) return -1;
+    if (n_frames < 2 || h < 1 || w < 1 || c < 1 || c > kMaxChannels || radius < 0 || radius > kMaxRadius) return -1;
     if (h >= (1LL << 30) || w >= (1LL << 30) || h * w >= (1LL << 30)) return -1;
     return 8 * c * h * w * (2 * radius + 2);
 }

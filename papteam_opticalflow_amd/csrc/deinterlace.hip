@@ -34,7 +34,6 @@ namespace {
 
 constexpr int kDeintTX = 64, kDeintTY = 4;  // a 64 x 4 tile of made pixels per block (256 lanes: lut)
 using DeintTile = Tile<kDeintTX, kDeintTY>;
-constexpr int kMaxC = 4;                    // channels (registers per lane)
 
 struct DeintArgs {
     papof_tensor fl;      // fields (field, row, column, channel)
@@ -69,8 +68,8 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
     Bilinear k0, k1;
     if (MODE) {
         if (t >= 1 && t <= a.T - 2) {
-            const long long of = (t - 1) * a.fw.stride[0] + j * a.fw.stride[1] + x * a.fw.stride[2];
-            const long long ob = (t - 1) * a.bw.stride[0] + j * a.bw.stride[1] + x * a.bw.stride[2];
+            const long long of = PAPOF_AT(a.fw, t - 1, j, x);
+            const long long ob = PAPOF_AT(a.bw, t - 1, j, x);
             const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
             const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
             const InterpPoints p = interp_points(x, j, u, v, bu, bv, 0.5, Hf, W);
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
         } else {
             // frame 0: field 1 along half of flow_fw[1]; frame T - 1: field T - 2 along half of flow_bw[T - 4]
             const papof_tensor& f = t == 0 ? a.fw : a.bw;
-            const long long o = (t == 0 ? 1 : a.T - 4) * f.stride[0] + j * f.stride[1] + x * f.stride[2];
+            const long long o = PAPOF_AT(f, t == 0 ? 1 : a.T - 4, j, x);
             const double X = (double)x + 0.5 * load_flow(f, o), Y = (double)j + 0.5 * load_flow(f, o + f.stride[3]);
             const bool in = X >= 0 && X <= (double)(W - 1) && Y >= 0 && Y <= (double)(Hf - 1);  // (false for a NaN)
             const Bilinear k = taps_at(in ? X : 0.0, in ? Y : 0.0, Hf, W);
@@ -100,10 +99,10 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
     const bool use0 = c0 > 0, use1 = c1 > 0;  // (both false in mode 0)
     const long long base0 = (t - 1) * a.fl.stride[0], base1 = (t + 1) * a.fl.stride[0];  // (read only where use_i)
 
-    double s[kMaxC], kept[kMaxC], g0[kMaxC], g1[kMaxC];
+    double s[kMaxChannels], kept[kMaxChannels], g0[kMaxChannels], g1[kMaxChannels];
     double D = 0.0;
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) {
             const long long oc = own + ch * a.fl.stride[3];
             const double a1 = load_frame<FD>(a.fl, oc + ja1 * a.fl.stride[1], lut);
@@ -127,10 +126,10 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
     else if (use1)
         q = 0.5 * c1;
 
-    const long long ok = t * a.out.stride[0] + (2 * j + 1 - pm) * a.out.stride[1] + x * a.out.stride[2];
-    const long long om = t * a.out.stride[0] + (2 * j + pm) * a.out.stride[1] + x * a.out.stride[2];
+    const long long ok = PAPOF_AT(a.out, t, 2 * j + 1 - pm, x);
+    const long long om = PAPOF_AT(a.out, t, 2 * j + pm, x);
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) {
             double made = s[ch];
             if (q != 0) {  // (q == 0: the cubic alone -- a NaN never reaches the output through a zero weight)
@@ -141,7 +140,7 @@ __global__ __launch_bounds__(kDeintTX* kDeintTY) void k_deinterlace(const DeintA
             store(a.out, om + ch * a.out.stride[3], made);
         }
     if (a.conf.data) {
-        const long long oq = t * a.conf.stride[0] + j * a.conf.stride[1] + x * a.conf.stride[2];
+        const long long oq = PAPOF_AT(a.conf, t, j, x);
         if (a.conf.dtype == PAPOF_DTYPE_F32)
             static_cast<float*>(a.conf.data)[oq] = (float)q;
         else
@@ -165,7 +164,7 @@ extern "C" int papof_deinterlace_tensor(papof_handle* h, int n_fields, int field
                                         const papof_tensor* fields, int first, int mode, const papof_tensor* flow_fw,
                                         const papof_tensor* flow_bw, double sigma, const papof_tensor* video,
                                         const papof_tensor* confidence, void* stream) {
-    if (!h || n_fields < 4 || field_height < 1 || field_height > 0x3fffffff || width < 1 || c < 1 || c > kMaxC)
+    if (!h || n_fields < 4 || field_height < 1 || field_height > 0x3fffffff || width < 1 || c < 1 || c > kMaxChannels)
         return PAPOF_EINVAL;
     if ((first != 0 && first != 1) || (mode != 0 && mode != 1)) return PAPOF_EINVAL;
     if (!std::isfinite(sigma) || !(sigma > 0)) return PAPOF_EINVAL;

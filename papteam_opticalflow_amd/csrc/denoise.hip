@@ -26,7 +26,6 @@ namespace {
 
 constexpr int kFilterTX = 64, kFilterTY = 4;   // a 64 x 4 tile of output pixels per block (256 lanes: lut)
 using FilterTile = Tile<kFilterTX, kFilterTY>;
-constexpr int kMaxC = 4;                       // channels (registers per lane: centre values, sums, samples)
 constexpr int kMaxRadius = 16;
 
 struct FilterArgs {
@@ -40,35 +39,32 @@ struct FilterArgs {
     double a1, a2;
 };
 
-// The samples of one direction of frame t's pixel (x, r), added to num / den / support.  dir = +1: hops t + j - 1 -> t + j
-// through f = flow_fw[t + j - 1], checked with b = flow_bw[t + j - 1]; dir = -1: t - j + 1 -> t - j through f = flow_bw[t - j],
-// checked with b = flow_fw[t - j].
+// The samples of one direction (dir = +-1: sampler.h, the direction rule) of frame t's pixel (x, r), added to num / den /
+// support.
 template <int FD>
-__device__ __forceinline__ void chain(const FilterArgs& a, const papof_tensor& f, const papof_tensor& b, long long t, int dir,
-                                      int steps, double X, double Y, const double* c, double* num, double& den, int& support,
-                                      const double* lut) {
+__device__ __forceinline__ void chain(const FilterArgs& a, long long t, int dir, int steps, double X, double Y,
+                                      const double* c, double* num, double& den, int& support, const double* lut) {
     const int H = a.H, W = a.W;
     for (int j = 1; j <= steps; j++) {
-        const long long pair = dir > 0 ? t + j - 1 : t - j, frame = t + dir * j;
+        const long long pair = chain_pair(t, dir, j), frame = chain_frame(t, dir, j);
         double nX, nY;
-        if (!hop(f, b, pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY)) return;  // once dead, the chain stays dead
+        if (!chain_hop(a, pair, dir, H, W, X, Y, nX, nY)) return;  // once dead, the chain stays dead
         X = nX;
         Y = nY;
         const Bilinear k = taps_at(X, Y, H, W);
         const long long base = frame * a.fr.stride[0];
-        double g[kMaxC], D = 0.0;
+        double g[kMaxChannels], D = 0.0;
 #pragma unroll
-        for (int ch = 0; ch < kMaxC; ch++)
+        for (int ch = 0; ch < kMaxChannels; ch++)
             if (ch < a.C) {
                 g[ch] = sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], k, lut);
                 const double d = g[ch] - c[ch];
                 D += d * d;
             }
-        D = D / (double)a.C;
-        const double w = a.sigma > 0 ? 1.0 / (1.0 + D / a.s2) : 1.0;
+        const double w = a.sigma > 0 ? photometric_weight(D, a.C, a.s2) : 1.0;
         if (w > 0) {  // (false for a NaN)
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < a.C) num[ch] += w * g[ch];
             den += w;
             support += 1;
@@ -85,23 +81,21 @@ __global__ __launch_bounds__(kFilterTX* kFilterTY) void k_temporal_filter(const 
     PAPOF_TILE_PIXEL(FilterTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long t = frame0 + blockIdx.y;
-    const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
-    double c[kMaxC], num[kMaxC];
+    const long long pix = PAPOF_AT(a.fr, t, r, x);
+    double c[kMaxChannels], num[kMaxChannels];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) num[ch] = c[ch] = load_frame<FD>(a.fr, pix + ch * a.fr.stride[3], lut);
     double den = 1.0;
     int support = 0;
-    const int fwd = a.T - 1 - t < a.R ? (int)(a.T - 1 - t) : a.R, bwd = t < a.R ? (int)t : a.R;
-    chain<FD>(a, a.fw, a.bw, t, +1, fwd, (double)x, (double)r, c, num, den, support, lut);
-    chain<FD>(a, a.bw, a.fw, t, -1, bwd, (double)x, (double)r, c, num, den, support, lut);
-    const long long o = t * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    const int fwd = chain_steps(a.T, t, +1, a.R), bwd = chain_steps(a.T, t, -1, a.R);
+    chain<FD>(a, t, +1, fwd, (double)x, (double)r, c, num, den, support, lut);
+    chain<FD>(a, t, -1, bwd, (double)x, (double)r, c, num, den, support, lut);
+    const long long o = PAPOF_AT(a.out, t, r, x);
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) store(a.out, o + ch * a.out.stride[3], num[ch] / den);
-    if (a.sup.data)
-        static_cast<unsigned char*>(a.sup.data)[t * a.sup.stride[0] + r * a.sup.stride[1] + x * a.sup.stride[2]] =
-            (unsigned char)support;
+    if (a.sup.data) store_u8(a.sup, PAPOF_AT(a.sup, t, r, x), (unsigned char)support);
 }
 
 int launch_filter(hipStream_t st, const FilterArgs& a) {
@@ -120,7 +114,7 @@ extern "C" int papof_temporal_filter_tensor(papof_handle* h, int n_frames, int h
                                             const papof_tensor* flow_bw, int radius, double sigma, int use_check,
                                             double alpha1, double alpha2, const papof_tensor* out,
                                             const papof_tensor* support, void* stream) {
-    if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
+    if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxChannels) return PAPOF_EINVAL;
     if (radius < 1 || radius > kMaxRadius || !std::isfinite(sigma) || sigma < 0) return PAPOF_EINVAL;
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     if (!in_frames(frames)) return PAPOF_EINVAL;

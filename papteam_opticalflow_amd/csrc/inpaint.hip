@@ -31,7 +31,6 @@ namespace {
 constexpr int kFillBlock = 256;                // lanes per block of the fill kernels (256: the uint8 table)
 constexpr int kPropTX = 64, kPropTY = 4;       // a 64 x 4 tile of output pixels per block of k_propagate
 using PropTile = Tile<kPropTX, kPropTY>;
-constexpr int kMaxC = 4;
 constexpr int kMaxRelax = 1 << 16;
 
 // One pyramid level of the fill's workspace: all frames' (row, column, channel) values, row-major, channels innermost.
@@ -62,11 +61,10 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_base(const papof_tensor x, 
     const long long i = (long long)blockIdx.x * kFillBlock + threadIdx.x;
     if (i >= L.h * L.w) return;
     const long long t = f0 + blockIdx.y, r = i / L.w, c = i % L.w, p = t * L.h * L.w + i;
-    const bool known = static_cast<const unsigned char*>(mask.data)[t * mask.stride[0] + r * mask.stride[1] +
-                                                                     c * mask.stride[2]] == 0;
-    const long long o = t * x.stride[0] + r * x.stride[1] + c * x.stride[2];
+    const bool known = load_u8(mask, PAPOF_AT(mask, t, r, c)) == 0;
+    const long long o = PAPOF_AT(x, t, r, c);
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) L.v0[p * C + ch] = known ? load_frame<FD>(x, o + ch * x.stride[3], lut) : 0.0;
     L.k[p] = known ? 1 : 0;
 }
@@ -77,9 +75,9 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_pull(const Level F, const L
     const long long i = (long long)blockIdx.x * kFillBlock + threadIdx.x;
     if (i >= G.h * G.w) return;
     const long long t = f0 + blockIdx.y, r = i / G.w, c = i % G.w, p = t * G.h * G.w + i;
-    double s[kMaxC];
+    double s[kMaxChannels];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++) s[ch] = 0.0;
+    for (int ch = 0; ch < kMaxChannels; ch++) s[ch] = 0.0;
     int n = 0;
 #pragma unroll
     for (int a = 0; a <= 1; a++)
@@ -90,12 +88,12 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_pull(const Level F, const L
             const long long q = (t * F.h + fr) * F.w + fc;
             if (!F.k[q]) continue;
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < C) s[ch] += F.v0[q * C + ch];
             n += 1;
         }
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) G.v0[p * C + ch] = n > 0 ? s[ch] / (double)n : 0.0;
     G.k[p] = n > 0 ? 1 : 0;
 }
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_push(const Level F, const L
     const Bilinear k = taps_at(X, Y, (int)G.h, (int)G.w);
     const long long base = t * G.h * G.w;
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) {
             double g = 0.0;
 #pragma unroll
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_relax(const Level L, const 
     const long long n = base + (r > 0 ? r - 1 : 0) * L.w + c, s = base + (r < L.h - 1 ? r + 1 : r) * L.w + c;
     const long long w = base + r * L.w + (c > 0 ? c - 1 : 0), e = base + r * L.w + (c < L.w - 1 ? c + 1 : c);
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C)
             dst[p * C + ch] = ((value(L, src, n, C, ch) + value(L, src, s, C, ch)) +
                                (value(L, src, w, C, ch) + value(L, src, e, C, ch))) * 0.25;
@@ -148,9 +146,9 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_store(const Level L, const 
     const long long i = (long long)blockIdx.x * kFillBlock + threadIdx.x;
     if (i >= L.h * L.w) return;
     const long long t = f0 + blockIdx.y, r = i / L.w, c = i % L.w, p = t * L.h * L.w + i;
-    const long long o = t * out.stride[0] + r * out.stride[1] + c * out.stride[2];
+    const long long o = PAPOF_AT(out, t, r, c);
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < C) store(out, o + ch * out.stride[3], value(L, it, p, C, ch));
 }
 
@@ -204,16 +202,18 @@ struct PropArgs {
 };
 
 // The candidate of one direction of frame t's hole pixel (x, r): the chain hops as k_temporal_filter's (denoise.hip) and
-// stops at the first frame whose four clamped taps at the landing point are all outside that frame's mask.  dir = +1: hops
-// t + j - 1 -> t + j through f = flow_fw[t + j - 1], checked with b = flow_bw[t + j - 1]; dir = -1: t - j + 1 -> t - j
-// through f = flow_bw[t - j], checked with b = flow_fw[t - j].  Returns the distance j, or 0 where the chain dies first.
+// stops at the first frame whose four clamped taps at the landing point are all outside that frame's mask.  dir = +-1:
+// sampler.h, the direction rule, whose steps, pairs and frames these are.  The flow f that is read and the flow b it is checked
+// with are the rule's too, chain_flow(a, dir) and chain_check(a, dir), chosen by the kernel in front of the call: with
+// chain_hop's selection inside this loop the kernel's loop invariants were hoisted in another order (DESIGN.md section 45,
+// kernels that deviate).  Returns the distance j, or 0 where the chain dies first.
 template <int FD>
 __device__ __forceinline__ int candidate(const PropArgs& a, const papof_tensor& f, const papof_tensor& b, long long t,
                                          int dir, int steps, double X, double Y, double* g, const double* lut) {
     const int H = a.H, W = a.W;
-    const unsigned char* mk = static_cast<const unsigned char*>(a.mk.data);
+    const unsigned char* mk = static_cast<const unsigned char*>(a.mk.data);  // (the taps' bytes: one pointer for the loop)
     for (int j = 1; j <= steps; j++) {
-        const long long pair = dir > 0 ? t + j - 1 : t - j, frame = t + dir * j;
+        const long long pair = chain_pair(t, dir, j), frame = chain_frame(t, dir, j);
         double nX, nY;
         if (!hop(f, b, pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY)) return 0;  // once dead, the chain stays dead
         X = nX;
@@ -226,7 +226,7 @@ __device__ __forceinline__ int candidate(const PropArgs& a, const papof_tensor& 
         if (clear) {
             const long long base = frame * a.fr.stride[0];
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < a.C) g[ch] = sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], k, lut);
             return j;
         }
@@ -242,20 +242,19 @@ __global__ __launch_bounds__(kPropTX* kPropTY) void k_propagate(const PropArgs a
     PAPOF_TILE_PIXEL(PropTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long t = frame0 + blockIdx.y;
-    const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
-    const long long o = t * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
-    const bool hole =
-        static_cast<const unsigned char*>(a.mk.data)[t * a.mk.stride[0] + r * a.mk.stride[1] + x * a.mk.stride[2]] != 0;
-    double gf[kMaxC], gb[kMaxC];
+    const long long pix = PAPOF_AT(a.fr, t, r, x);
+    const long long o = PAPOF_AT(a.out, t, r, x);
+    const bool hole = load_u8(a.mk, PAPOF_AT(a.mk, t, r, x)) != 0;
+    double gf[kMaxChannels], gb[kMaxChannels];
     int df = 0, db = 0;
     if (hole) {
-        const int fwd = a.T - 1 - t < a.R ? (int)(a.T - 1 - t) : a.R, bwd = t < a.R ? (int)t : a.R;
-        df = candidate<FD>(a, a.fw, a.bw, t, +1, fwd, (double)x, (double)r, gf, lut);
-        db = candidate<FD>(a, a.bw, a.fw, t, -1, bwd, (double)x, (double)r, gb, lut);
+        const int fwd = chain_steps(a.T, t, +1, a.R), bwd = chain_steps(a.T, t, -1, a.R);
+        df = candidate<FD>(a, chain_flow(a, +1), chain_check(a, +1), t, +1, fwd, (double)x, (double)r, gf, lut);
+        db = candidate<FD>(a, chain_flow(a, -1), chain_check(a, -1), t, -1, bwd, (double)x, (double)r, gb, lut);
     }
     const double wf = df ? 1.0 / (double)df : 0.0, wb = db ? 1.0 / (double)db : 0.0;
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) {
             double v;
             if (df && db)
@@ -268,8 +267,8 @@ __global__ __launch_bounds__(kPropTX* kPropTY) void k_propagate(const PropArgs a
                 v = load_frame<FD>(a.fr, pix + ch * a.fr.stride[3], lut);
             store(a.out, o + ch * a.out.stride[3], v);
         }
-    static_cast<unsigned char*>(a.st.data)[t * a.st.stride[0] + r * a.st.stride[1] + x * a.st.stride[2]] =
-        !hole ? 0 : (df || db) ? 1 : 2;
+    // (store_u8 would evaluate the value before it reads a.st.data, and the kernel's tail is scheduled differently)
+    static_cast<unsigned char*>(a.st.data)[PAPOF_AT(a.st, t, r, x)] = !hole ? 0 : (df || db) ? 1 : 2;
 }
 
 int launch_propagate(hipStream_t st, const PropArgs& a) {
@@ -284,7 +283,7 @@ int launch_propagate(hipStream_t st, const PropArgs& a) {
 using namespace papof;
 
 extern "C" long long papof_fill_workspace(int n_frames, int height, int width, int c) {
-    if (n_frames < 1 || height < 1 || width < 1 || c < 1 || c > kMaxC) return -1;
+    if (n_frames < 1 || height < 1 || width < 1 || c < 1 || c > kMaxChannels) return -1;
     if ((long long)height * width > kMaxTiles * kFillBlock) return -1;
     long long bytes = 0;
     for (const auto& s : level_sizes(height, width)) {
@@ -313,7 +312,7 @@ extern "C" int papof_propagate_tensor(papof_handle* h, int n_frames, int height,
                                       const papof_tensor* frames, const papof_tensor* masks, const papof_tensor* flow_fw,
                                       const papof_tensor* flow_bw, int radius, int use_check, double alpha1, double alpha2,
                                       const papof_tensor* out, const papof_tensor* status, void* stream) {
-    if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
+    if (!h || n_frames < 2 || height < 1 || width < 1 || c < 1 || c > kMaxChannels) return PAPOF_EINVAL;
     if (radius < 1 || radius > n_frames - 1 || !valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     if (!in_frames(frames) || !described(masks, {PAPOF_DTYPE_U8}, {0, 1, 2}, false))
         return PAPOF_EINVAL;

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void k_match_prepare(const PrepArgs a, long lo
     if (cell >= cells) return;
     const long long f = frame0 + blockIdx.y;
     const int y = (int)(cell / a.w), x = (int)(cell - (long long)y * a.w), s = a.stride;
-    const long long base = f * a.in.stride[0] + (long long)y * s * a.in.stride[1] + (long long)x * s * a.in.stride[2];
+    const long long base = PAPOF_AT(a.in, f, (long long)y * s, (long long)x * s);
     const unsigned area = (unsigned)(s * s);
     unsigned pk = 0;
     for (int c = 0; c < a.C; c++) {
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_match_prepare_wide(const PrepArgs a, lo
     const int t = (int)threadIdx.x % G, s = a.stride;
     const long long f = frame0 + blockIdx.y;
     const int y = (int)(cell / a.w), x = (int)(cell - (long long)y * a.w);
-    const long long base = f * a.in.stride[0] + (long long)y * s * a.in.stride[1] + (long long)x * s * a.in.stride[2];
+    const long long base = PAPOF_AT(a.in, f, (long long)y * s, (long long)x * s);
     unsigned sum[4] = {0, 0, 0, 0};
     for (int idx = t; idx < s * s; idx += G) {
         const int j = idx / s, i = idx - j * s;
@@ -230,10 +230,10 @@ __global__ __launch_bounds__(kTX* kTY) void k_match(const MatchArgs a, long long
         a.out[item * cells + (long long)y * w + x] = pack_d(bdx, bdy);
         return;
     }
-    const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    const long long od = PAPOF_AT(a.disp, item, (long long)y, (long long)x);
     store(a.disp, od, (double)(a.stride * bdx));
     store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
-    store(a.cost, item * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2],
+    store(a.cost, PAPOF_AT(a.cost, item, (long long)y, (long long)x),
           (double)(best >> 26));
 }
 
@@ -253,25 +253,25 @@ __global__ __launch_bounds__(256) void k_match_densify(const DensifyArgs a, long
     const long long i = item0 + blockIdx.y;
     const int Y = (int)(pix / a.W), X = (int)(pix - (long long)Y * a.W);
     const int y = min(Y / a.stride, a.h - 1), x = min(X / a.stride, a.w - 1);
-    const long long od = i * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    const long long od = PAPOF_AT(a.disp, i, (long long)y, (long long)x);
     const double fx = load_flow(a.disp, od), fy = load_flow(a.disp, od + a.disp.stride[3]);
     const double dx = fx / (double)a.stride, dy = fy / (double)a.stride;
     const double qx = (double)x + dx, qy = (double)y + dy;
     // a whole number of cells that lands inside the grid (false for a NaN)
     bool ok = rint(dx) == dx && rint(dy) == dy && qx >= 0 && qx <= (double)(a.w - 1) && qy >= 0 && qy <= (double)(a.h - 1);
     if (ok) {
-        const long long orv = i * a.rev.stride[0] + (long long)(int)qy * a.rev.stride[1] + (long long)(int)qx * a.rev.stride[2];
+        const long long orv = PAPOF_AT(a.rev, i, (long long)(int)qy, (long long)(int)qx);
         const double ex = dx + load_flow(a.rev, orv) / (double)a.stride;
         const double ey = dy + load_flow(a.rev, orv + a.rev.stride[3]) / (double)a.stride;
         ok = fabs(ex) <= (double)a.tol && fabs(ey) <= (double)a.tol;
     }
     if (ok && a.max_cost >= 0)
-        ok = load_flow(a.cost, i * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2]) <= a.max_cost;
-    const long long of = i * a.flow.stride[0] + (long long)Y * a.flow.stride[1] + (long long)X * a.flow.stride[2];
+        ok = load_flow(a.cost, PAPOF_AT(a.cost, i, (long long)y, (long long)x)) <= a.max_cost;
+    const long long of = PAPOF_AT(a.flow, i, (long long)Y, (long long)X);
     static_cast<double*>(a.flow.data)[of] = ok ? fx : 0.0;
     static_cast<double*>(a.flow.data)[of + a.flow.stride[3]] = ok ? fy : 0.0;
-    static_cast<unsigned char*>(a.mask.data)[i * a.mask.stride[0] + (long long)Y * a.mask.stride[1] +
-                                             (long long)X * a.mask.stride[2]] = ok ? 0 : 1;
+    // (store_u8 would evaluate the value before it reads a.mask.data: the kernel's tail is scheduled differently)
+    static_cast<unsigned char*>(a.mask.data)[PAPOF_AT(a.mask, i, (long long)Y, (long long)X)] = ok ? 0 : 1;
 }
 
 bool valid_frame_size(int height, int width, int stride) {
@@ -461,10 +461,10 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_refine(const RefineArgs a, l
         a.out[item * cells + (long long)y * w + x] = pack_d(bdx, bdy);
         return;
     }
-    const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    const long long od = PAPOF_AT(a.disp, item, (long long)y, (long long)x);
     store(a.disp, od, (double)(a.stride * bdx));
     store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
-    store(a.cost, item * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2],
+    store(a.cost, PAPOF_AT(a.cost, item, (long long)y, (long long)x),
           (double)(best >> 38));
 }
 
@@ -657,10 +657,10 @@ __global__ __launch_bounds__(kTX* kTY) void k_match_recentre(const RecentreArgs 
         best = key < best ? key : best;
     }
     const int bdx = (int)(best & 1023) - 512, bdy = (int)((best >> 10) & 1023) - 512;
-    const long long od = item * a.disp.stride[0] + (long long)y * a.disp.stride[1] + (long long)x * a.disp.stride[2];
+    const long long od = PAPOF_AT(a.disp, item, (long long)y, (long long)x);
     store(a.disp, od, (double)(a.stride * bdx));
     store(a.disp, od + a.disp.stride[3], (double)(a.stride * bdy));
-    store(a.cost, item * a.cost.stride[0] + (long long)y * a.cost.stride[1] + (long long)x * a.cost.stride[2],
+    store(a.cost, PAPOF_AT(a.cost, item, (long long)y, (long long)x),
           (double)(best >> 38));
 }
 

@@ -102,13 +102,12 @@ __global__ __launch_bounds__(kMeshLanes) void k_mesh_median(const MeshArgs a, lo
         if (k < total) {
             const int x = xs + (k % nx) * a.step;
             const long long y = ys + (k / nx) * a.step;
-            const long long o = b * a.flow.stride[0] + y * a.flow.stride[1] + x * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, b, y, x);
             const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
             const double xd = (double)x, yd = (double)y, X = xd + u, Y = yd + v;
             valid = X >= 0 && X <= W1 && Y >= 0 && Y <= H1;  // false for a NaN or an infinity
             if (valid && a.occ.data)
-                valid = static_cast<const unsigned char*>(a.occ.data)[b * a.occ.stride[0] + y * a.occ.stride[1] +
-                                                                      x * a.occ.stride[2]] == 0;
+                valid = load_u8(a.occ, PAPOF_AT(a.occ, b, y, x)) == 0;
             rx = u - (((m[0] * xd + m[1] * yd) + m[2]) - xd);
             ry = v - (((m[3] * xd + m[4] * yd) + m[5]) - yd);
             valid = valid && rx == rx && ry == ry;  // (a NaN only through a matrix that is not finite)
@@ -205,10 +204,10 @@ __global__ __launch_bounds__(64) void k_mesh_spatial(const MeshArgs a, long long
     load_matrix(a.mat, b, m);
     const double px = ((double)vj * (double)(a.W - 1)) / (double)a.GW, py = ((double)vi * (double)(a.H - 1)) / (double)a.GH;
     const double gx = ((m[0] * px + m[1] * py) + m[2]) - px, gy = ((m[3] * px + m[4] * py) + m[5]) - py;
-    const long long orr = b * a.resid.stride[0] + vi * a.resid.stride[1] + vj * a.resid.stride[2];
+    const long long orr = PAPOF_AT(a.resid, b, vi, vj);
     static_cast<double*>(a.resid.data)[orr] = rx;
     static_cast<double*>(a.resid.data)[orr + a.resid.stride[3]] = ry;
-    const long long ov = b * a.vert.stride[0] + vi * a.vert.stride[1] + vj * a.vert.stride[2];
+    const long long ov = PAPOF_AT(a.vert, b, vi, vj);
     static_cast<double*>(a.vert.data)[ov] = rx + gx;
     static_cast<double*>(a.vert.data)[ov + a.vert.stride[3]] = ry + gy;
 }
@@ -285,8 +284,8 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_mesh(const WarpMeshAr
     const double X = X0 + dx, Y = Y0 + dy;
     const bool in = X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
     if (a.valid.data)
-        static_cast<unsigned char*>(a.valid.data)[i * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = in;
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        store_u8(a.valid, PAPOF_AT(a.valid, i, r, x), in);
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     if (!in) {
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;

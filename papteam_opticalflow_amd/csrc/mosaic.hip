@@ -584,7 +584,7 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
     if (x >= a.Wc || r >= a.Hc) return;  // (no barrier below)
 
     // ---- 2, 3. the walk
-    const long long outp = o * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    const long long outp = PAPOF_AT(a.out, o, r, x);
     const bool all_sources = a.count.data != nullptr || MODE != PAPOF_MOSAIC_FIRST;
     double p[3] = {(double)x, (double)r};  // the pixel, or (RayArgs) its ray: once for every source and channel
     if constexpr (kRay<A>) ray_of(a, x, r, p);
@@ -623,8 +623,7 @@ __global__ __launch_bounds__(kMosTX* TY) void k_mosaic(const A a, long long tile
             if (!all_sources) break;
         }
         if (c0 == 0 && a.count.data)
-            static_cast<unsigned char*>(a.count.data)[o * a.count.stride[0] + r * a.count.stride[1] + x * a.count.stride[2]] =
-                (unsigned char)n;
+            store_u8(a.count, PAPOF_AT(a.count, o, r, x), (unsigned char)n);
         if (MODE == PAPOF_MOSAIC_MEDIAN) {
             // the sample with exactly (n - 1) / 2 samples before it under (value, k): the compaction kept the k order
             const int want = (n - 1) / 2;

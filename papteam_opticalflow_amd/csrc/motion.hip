@@ -97,13 +97,12 @@ __global__ __launch_bounds__(kFitTX* kFitTY) void k_motion_sums(const FitArgs a,
         for (int j = 0; j < kFitRows; j++) {
             const long long r = r0 + (long long)j * kFitTY;
             if (r >= a.H) break;
-            const long long o = i * a.flow.stride[0] + r * a.flow.stride[1] + x * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, i, r, x);
             const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
             const double rd = (double)r, X = xd + u, Y = rd + v;
             bool valid = X >= 0 && X <= W1 && Y >= 0 && Y <= H1;  // false for a NaN or an infinity
             if (valid && a.occ.data)
-                valid = static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + r * a.occ.stride[1] +
-                                                                      x * a.occ.stride[2]] == 0;
+                valid = load_u8(a.occ, PAPOF_AT(a.occ, i, r, x)) == 0;
             if (!valid) continue;
             double w = 1.0;
             if (a.iter > 0) {
@@ -219,7 +218,7 @@ __global__ __launch_bounds__(64) void k_motion_solve(const SolveArgs a, long lon
     double* mo = static_cast<double*>(a.motion.data) + i * a.motion.stride[0];
     for (int r = 0; r < 2; r++)
         for (int c = 0; c < 3; c++) mo[r * a.motion.stride[1] + c * a.motion.stride[2]] = st[3 * r + c];
-    static_cast<unsigned char*>(a.ok.data)[i * a.ok.stride[0]] = st[6] != 0.0 ? 1 : 0;
+    static_cast<unsigned char*>(a.ok.data)[i * a.ok.stride[0]] = st[6] != 0.0 ? 1 : 0;  // (store_u8 evaluates the value first: other schedule)
     static_cast<double*>(a.support.data)[i * a.support.stride[0]] = acc[5] / a.hw;
 }
 
@@ -269,13 +268,12 @@ __global__ __launch_bounds__(kFitTX* kFitTY) void k_homography_sums(const FitArg
         for (int j = 0; j < kFitRows; j++) {
             const long long r = r0 + (long long)j * kFitTY;
             if (r >= a.H) break;
-            const long long o = i * a.flow.stride[0] + r * a.flow.stride[1] + x * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, i, r, x);
             const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
             const double rd = (double)r, X = xd + u, Y = rd + v;
             bool valid = X >= 0 && X <= W1 && Y >= 0 && Y <= H1;  // false for a NaN or an infinity
             if (valid && a.occ.data)
-                valid = static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + r * a.occ.stride[1] +
-                                                                      x * a.occ.stride[2]] == 0;
+                valid = load_u8(a.occ, PAPOF_AT(a.occ, i, r, x)) == 0;
             if (!valid) continue;
             acc[23] += 1.0;
             double w = 1.0, c = 1.0;
@@ -389,7 +387,7 @@ __global__ __launch_bounds__(64) void k_homography_solve(const SolveArgs a, doub
     double* mo = static_cast<double*>(a.motion.data) + i * a.motion.stride[0];
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) mo[r * a.motion.stride[1] + c * a.motion.stride[2]] = st[3 * r + c];
-    static_cast<unsigned char*>(a.ok.data)[i * a.ok.stride[0]] = st[9] != 0.0 ? 1 : 0;
+    static_cast<unsigned char*>(a.ok.data)[i * a.ok.stride[0]] = st[9] != 0.0 ? 1 : 0;  // (store_u8 evaluates the value first: other schedule)
     static_cast<double*>(a.support.data)[i * a.support.stride[0]] = acc[24] / a.hw;
 }
 
@@ -431,8 +429,8 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_affine(const WarpArgs
     const double X = (m[0] * xd + m[1] * rd) + m[2], Y = (m[3] * xd + m[4] * rd) + m[5];
     const bool in = X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
     if (a.valid.data)
-        static_cast<unsigned char*>(a.valid.data)[i * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = in;
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        store_u8(a.valid, PAPOF_AT(a.valid, i, r, x), in);
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     if (!in) {
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;
@@ -467,8 +465,8 @@ __global__ __launch_bounds__(kWarpTX* kWarpTY) void k_warp_projective(const Warp
     const double X = ((m[0] * xd + m[1] * rd) + m[2]) / D, Y = ((m[3] * xd + m[4] * rd) + m[5]) / D;
     const bool in = D > 0 && X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= (double)(a.H - 1);  // (false for a NaN)
     if (a.valid.data)
-        static_cast<unsigned char*>(a.valid.data)[i * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = in;
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        store_u8(a.valid, PAPOF_AT(a.valid, i, r, x), in);
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     if (!in) {
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;

@@ -152,16 +152,15 @@ __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long lo
 
     bool mine = inside;
     if (inside && a.where.data)
-        mine = static_cast<const unsigned char*>(a.where.data)[i * a.where.stride[0] + y * a.where.stride[1] +
-                                                               x * a.where.stride[2]] != 0;
-    const long long of = i * a.flow.stride[0] + (long long)y * a.flow.stride[1] + (long long)x * a.flow.stride[2];
-    const long long oo = i * a.out.stride[0] + (long long)y * a.out.stride[1] + (long long)x * a.out.stride[2];
-    const long long op = i * a.passes.stride[0] + (long long)y * a.passes.stride[1] + (long long)x * a.passes.stride[2];
+        mine = static_cast<const unsigned char*>(a.where.data)[PAPOF_AT(a.where, i, y, x)] != 0;  // (through load_u8 an s_nor takes its operands in the other order)
+    const long long of = PAPOF_AT(a.flow, i, (long long)y, (long long)x);
+    const long long oo = PAPOF_AT(a.out, i, (long long)y, (long long)x);
+    const long long op = PAPOF_AT(a.passes, i, (long long)y, (long long)x);
     const bool any = __syncthreads_or(mine ? 1 : 0) != 0;
     if (inside && !mine) {  // copied
         store(a.out, oo, load_flow(a.flow, of));
         store(a.out, oo + a.out.stride[3], load_flow(a.flow, of + a.flow.stride[3]));
-        if (a.passes.data) static_cast<unsigned char*>(a.passes.data)[op] = 0;
+        if (a.passes.data) store_u8(a.passes, op, 0);
     }
     if (!any) return;
 
@@ -172,20 +171,19 @@ __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long lo
         bool d = !(gx >= 0 && gx < W && gy >= 0 && gy < H);
         long long ku = 0, kv = 0;
         if (!d) {
-            const long long o = i * a.flow.stride[0] + (long long)gy * a.flow.stride[1] + (long long)gx * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, i, (long long)gy, (long long)gx);
             const double u = load_flow(a.flow, o), v = load_flow(a.flow, o + a.flow.stride[3]);
             ku = key_of(u);
             kv = key_of(v);
             d = !(isfinite(u) && isfinite(v));
             if (a.occ.data)
-                d = d || static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + gy * a.occ.stride[1] +
-                                                                       gx * a.occ.stride[2]] != 0;
+                d = d || load_u8(a.occ, PAPOF_AT(a.occ, i, gy, gx)) != 0;
         }
         keyU[c] = ku;
         keyV[c] = kv;
         dead[c] = d ? 1 : 0;
         const bool in = gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const long long og = i * a.guide.stride[0] + (long long)gy * a.guide.stride[1] + (long long)gx * a.guide.stride[2];
+        const long long og = PAPOF_AT(a.guide, i, (long long)gy, (long long)gx);
         if (GD == PAPOF_DTYPE_U8) {
             unsigned pk = 0;
             if (in)
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long lo
         if (T == 0) {  // every neighbour dead: the input
             store(a.out, oo, load_flow(a.flow, of));
             store(a.out, oo + a.out.stride[3], load_flow(a.flow, of + a.flow.stride[3]));
-            if (a.passes.data) static_cast<unsigned char*>(a.passes.data)[op] = 1;
+            if (a.passes.data) store_u8(a.passes, op, 1);
             return;
         }
         su.narrowed(mnu, sumu, cnt, 0);
@@ -290,7 +288,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_refine(const RefineArgs a, long lo
     }
     store(a.out, oo, value_of(su.hi));
     store(a.out, oo + a.out.stride[3], value_of(sv.hi));
-    if (a.passes.data) static_cast<unsigned char*>(a.passes.data)[op] = (unsigned char)(pass > 255 ? 255 : pass);
+    if (a.passes.data) store_u8(a.passes, op, (unsigned char)(pass > 255 ? 255 : pass));
 }
 
 long long plane_pair_bytes(long long n, long long h, long long w) {  // one float64 (n, 2, h, w) field; < 0: refused

@@ -36,7 +36,6 @@ namespace {
 
 constexpr int kDetectTX = 64, kDetectTY = 4;  // a 64 x 4 tile of pixels per block (256 lanes: lut)
 using DetectTile = Tile<kDetectTX, kDetectTY>;
-constexpr int kMaxC = 4;                      // channels (registers per lane: centre values)
 
 struct DetectArgs {
     papof_tensor fr;      // frames (frame, row, column, channel)
@@ -48,14 +47,6 @@ struct DetectArgs {
     int check;            // the consistency test is applied
     double thr, a1, a2;
 };
-
-// One hop of frame `from`'s point (X, Y) in direction dir = +-1, as k_temporal_filter's chain makes it: forward through
-// flow_fw[from] checked with flow_bw[from], backward through flow_bw[from - 1] checked with flow_fw[from - 1].
-__device__ __forceinline__ bool detect_hop(const DetectArgs& a, long long from, int dir, double X, double Y, double& nX,
-                                           double& nY) {
-    return dir > 0 ? hop(a.fw, a.bw, from, a.H, a.W, a.check, a.a1, a.a2, X, Y, nX, nY)
-                   : hop(a.bw, a.fw, from - 1, a.H, a.W, a.check, a.a1, a.a2, X, Y, nX, nY);
-}
 
 // grid.h's grid over the frame's 64 x 4 tiles; blockIdx.y: frame `frame0` + y.
 template <int FD>
@@ -69,20 +60,20 @@ __global__ __launch_bounds__(kDetectTX* kDetectTY) void k_defect_detect(const De
     // the references t + o1 and t + o2: (-1, +1) inside the video, (+1, +2) at frame 0, (-1, -2) at frame T - 1
     const int o1 = t == 0 ? 1 : -1, o2 = t == 0 ? 2 : (t == a.T - 1 ? -2 : 1);
     double X1, Y1, X2, Y2;
-    const bool alive1 = detect_hop(a, t, o1, (double)x, (double)r, X1, Y1);
+    const bool alive1 = hop_from(a, t, o1, (double)x, (double)r, X1, Y1);  // (sampler.h, the direction rule)
     bool alive2;
     if (o1 * o2 < 0)  // two chains of one hop
-        alive2 = detect_hop(a, t, o2, (double)x, (double)r, X2, Y2);
+        alive2 = hop_from(a, t, o2, (double)x, (double)r, X2, Y2);
     else              // one chain of two hops: dead after the first, it stays dead
-        alive2 = alive1 && detect_hop(a, t + o1, o1, X1, Y1, X2, Y2);
+        alive2 = alive1 && hop_from(a, t + o1, o1, X1, Y1, X2, Y2);
     const int support = (alive1 ? 1 : 0) + (alive2 ? 1 : 0);
     double s = 0.0;
     if (support == 2) {
         const Bilinear k1 = taps_at(X1, Y1, a.H, a.W), k2 = taps_at(X2, Y2, a.H, a.W);
-        const long long pix = t * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
+        const long long pix = PAPOF_AT(a.fr, t, r, x);
         const long long base1 = (t + o1) * a.fr.stride[0], base2 = (t + o2) * a.fr.stride[0];
 #pragma unroll
-        for (int ch = 0; ch < kMaxC; ch++)
+        for (int ch = 0; ch < kMaxChannels; ch++)
             if (ch < a.C) {
                 const double c = load_frame<FD>(a.fr, pix + ch * a.fr.stride[3], lut);
                 const double g1 = sample_frame<FD>(a.fr, base1 + ch * a.fr.stride[3], k1, lut);
@@ -93,18 +84,9 @@ __global__ __launch_bounds__(kDetectTX* kDetectTY) void k_defect_detect(const De
                 s = d > s ? d : s;  // (false for a NaN)
             }
     }
-    const long long o = t * a.mask.stride[0] + r * a.mask.stride[1] + x * a.mask.stride[2];
-    static_cast<unsigned char*>(a.mask.data)[o] = support == 2 && s > a.thr ? 1 : 0;
-    if (a.score.data) {
-        const long long os = t * a.score.stride[0] + r * a.score.stride[1] + x * a.score.stride[2];
-        if (a.score.dtype == PAPOF_DTYPE_F32)
-            static_cast<float*>(a.score.data)[os] = (float)s;
-        else
-            static_cast<double*>(a.score.data)[os] = s;
-    }
-    if (a.sup.data)
-        static_cast<unsigned char*>(a.sup.data)[t * a.sup.stride[0] + r * a.sup.stride[1] + x * a.sup.stride[2]] =
-            (unsigned char)support;
+    store_u8(a.mask, PAPOF_AT(a.mask, t, r, x), support == 2 && s > a.thr ? 1 : 0);
+    if (a.score.data) store_plane(a.score, PAPOF_AT(a.score, t, r, x), s);
+    if (a.sup.data) store_u8(a.sup, PAPOF_AT(a.sup, t, r, x), (unsigned char)support);
 }
 
 int launch_detect(hipStream_t st, const DetectArgs& a) {
@@ -171,7 +153,7 @@ extern "C" int papof_defect_detect_tensor(papof_handle* h, int n_frames, int hei
                                           const papof_tensor* flow_bw, double threshold, int use_check, double alpha1,
                                           double alpha2, const papof_tensor* mask, const papof_tensor* score,
                                           const papof_tensor* support, void* stream) {
-    if (!h || n_frames < 3 || height < 1 || width < 1 || c < 1 || c > kMaxC) return PAPOF_EINVAL;
+    if (!h || n_frames < 3 || height < 1 || width < 1 || c < 1 || c > kMaxChannels) return PAPOF_EINVAL;
     if (!std::isfinite(threshold) || threshold < 0) return PAPOF_EINVAL;
     if (!valid_alphas(alpha1, alpha2)) return PAPOF_EINVAL;
     if (!in_frames(frames)) return PAPOF_EINVAL;

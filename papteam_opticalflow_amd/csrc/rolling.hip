@@ -124,8 +124,8 @@ __global__ __launch_bounds__(kRsTX* kRsTY) void k_rs_rectify(const RsRectifyArgs
     double Px, Py;
     const bool alive = rs_solve(a.g, t, Qx, Qy, Px, Py);
     if (a.valid.data)
-        static_cast<unsigned char*>(a.valid.data)[t * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = alive;
-    const long long outp = t * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        store_u8(a.valid, PAPOF_AT(a.valid, t, r, x), alive);
+    const long long outp = PAPOF_AT(a.out, t, r, x);
     if (!alive) {
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kRsTX* kRsTY) void k_rs_flow(const RsFlowArgs a, lo
             v = v != v ? qnan : v;
         }
     }
-    const long long op = i * o.stride[0] + r * o.stride[1] + x * o.stride[2];
+    const long long op = PAPOF_AT(o, i, r, x);
     store(o, op, u);
     store(o, op + o.stride[3], v);
 }

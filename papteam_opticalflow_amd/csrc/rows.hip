@@ -83,8 +83,8 @@ __global__ __launch_bounds__(kRowsTX* kRowsTY) void k_warp_rows(const RowsArgs a
     }
     const bool in = D > 0 && X >= 0 && X <= (double)(a.W - 1) && Y >= 0 && Y <= H1;  // (false for a NaN)
     if (a.valid.data)
-        static_cast<unsigned char*>(a.valid.data)[i * a.valid.stride[0] + r * a.valid.stride[1] + x * a.valid.stride[2]] = in;
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        store_u8(a.valid, PAPOF_AT(a.valid, i, r, x), in);
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     if (!in) {
         for (int ch = 0; ch < a.C; ch++) store(a.out, outp + ch * a.out.stride[3], 0.0);
         return;

@@ -6,6 +6,11 @@
 // sizes of the fill and consistency workspaces.  The (tile, item) grid these kernels are launched over -- tile decode, tile
 // count, split launches, the choice of an instance by dtype -- is grid.h's.
 //
+// Two decisions that several files must know are stated here once: the direction rule of a chain of
+// hops through a video's flows (chain_flow, chain_check, chain_pair, chain_frame, chain_steps, chain_hop, hop_from: which
+// flow a hop reads, which it is checked with, through which pair, how many steps), and the element format of a
+// papof_tensor (PAPOF_AT, PAPOF_AT_CH, load_u8, store_u8, store_plane; kMaxChannels).
+//
 // The rule is the reference's (src/ImageProcessing.h:138-157): truncation toward zero, fraction clamped to [0, 1], neighbours
 // clamped into the image, taps accumulated from 0 in (m, n) order; fp64 without contraction (-ffp-contract=off).  Frames are
 // papof_tensor descriptors (frame, row, column, channel) of uint8 (x / 255.0, as k_ingest_frames computes it), float32
@@ -46,6 +51,38 @@ __device__ __forceinline__ double load_frame(const papof_tensor& t, long long o,
 
 __device__ __forceinline__ double load_flow(const papof_tensor& t, long long o) {
     return t.dtype == PAPOF_DTYPE_F32 ? (double)static_cast<const float*>(t.data)[o] : static_cast<const double*>(t.data)[o];
+}
+
+constexpr int kMaxChannels = 4;  // channels of a frame tensor (registers per lane: centre values, sums, samples)
+
+// ---- the elements of a papof_tensor: offsets in elements, 64-bit, by the descriptor's strides ----
+//   PAPOF_AT(t, i, r, x)         element (i, r, x, 0) of t: item (frame, pair ...) i, row r, column x
+//   PAPOF_AT_CH(t, i, r, x, ch)  element (i, r, x, ch)
+// Every index is widened by the 64-bit stride it multiplies: the offset is 64-bit whatever the indices' types.
+//
+// Why macros, as grid.h's decode: a function at(t, i, r, x) was written first, taking long long, then the caller's types,
+// then references.  A callee is optimised on its own before it is inlined, and the sum's operands are ordered there, not
+// among the kernel's values: k_temporal_filter's address chain came out as data + r s1 + t s0 where it was data + t s0 + r s1,
+// and its scalar address arithmetic was scheduled differently (profiles/flow_chain_isa.txt).  Text expanded in place
+// leaves every kernel as it was.
+#define PAPOF_AT(t, i, r, x) ((i) * (t).stride[0] + (r) * (t).stride[1] + (x) * (t).stride[2])
+#define PAPOF_AT_CH(t, i, r, x, ch) ((i) * (t).stride[0] + (r) * (t).stride[1] + (x) * (t).stride[2] + (ch) * (t).stride[3])
+
+// a byte of a uint8 descriptor (mask, support, status, valid plane) at offset o
+__device__ __forceinline__ unsigned char load_u8(const papof_tensor& t, long long o) {
+    return static_cast<const unsigned char*>(t.data)[o];
+}
+
+__device__ __forceinline__ void store_u8(const papof_tensor& t, long long o, unsigned char v) {
+    static_cast<unsigned char*>(t.data)[o] = v;
+}
+
+// v into a float32 (one round-to-nearest) or float64 plane (score, coverage ...)
+__device__ __forceinline__ void store_plane(const papof_tensor& t, long long o, double v) {
+    if (t.dtype == PAPOF_DTYPE_F32)
+        static_cast<float*>(t.data)[o] = (float)v;
+    else
+        static_cast<double*>(t.data)[o] = v;
 }
 
 __device__ __forceinline__ int clamp_to(int x, int n) {  // EnforceRange, src/ImageProcessing.h:34
@@ -126,6 +163,59 @@ __device__ __forceinline__ bool hop(const papof_tensor& f, const papof_tensor& b
         alive = fb_passes(u, v, bu, bv, a1, a2);
     }
     return alive;
+}
+
+// ---- THE DIRECTION RULE of a chain of hops through a video's flows, stated once ----
+// Pair p of flow_fw runs from frame p to p + 1, pair p of flow_bw from frame p + 1 to p.  So
+//   a hop forward from frame t reads flow_fw[t] and is checked with flow_bw[t];
+//   a hop backward from frame t reads flow_bw[t - 1] and is checked with flow_fw[t - 1];
+//   a chain of radius R from frame t takes min(R, T - 1 - t) steps forward and min(R, t) steps backward;
+//   step j >= 1 of a chain from t in direction dir = +-1 leaves frame t + dir (j - 1) and reaches frame t + dir j;
+//   a hop that fails ends the chain: the caller makes no further hop (once dead, a chain stays dead).
+// The functions below are the rule.  Those that read the flows are templated on the kernel's Args: any struct with fw, bw,
+// H, W, check, a1, a2, read where the kernels read them; with a literal dir the selection folds away.  hop() above stays the
+// primitive for what has no direction (k_fb_check, the interpolation rule).
+//
+// chain_hop takes H and W from its caller although they are a's: a chain loop keeps `const int H = a.H, W = a.W` in front of
+// it for taps_at at the landing point, and the hop uses the same two values, read once per chain and not once per hop (read
+// inside the hop, (double)(W - 1) and (double)(H - 1) stay in the loop until a late pass hoists them).  hop_from, with no
+// loop of its own, reads them itself.
+
+// the flow a hop in direction dir reads, and the reverse flow it is checked with
+template <typename A>
+__device__ __forceinline__ const papof_tensor& chain_flow(const A& a, int dir) { return dir > 0 ? a.fw : a.bw; }
+template <typename A>
+__device__ __forceinline__ const papof_tensor& chain_check(const A& a, int dir) { return dir > 0 ? a.bw : a.fw; }
+
+// the steps a chain of radius R may take from frame t of T
+__device__ __forceinline__ int chain_steps(int T, long long t, int dir, int R) {
+    return dir > 0 ? (T - 1 - t < R ? (int)(T - 1 - t) : R) : (t < R ? (int)t : R);
+}
+
+// the pair that step j of the chain from frame t hops through, and the frame it reaches
+__device__ __forceinline__ long long chain_pair(long long t, int dir, int j) { return dir > 0 ? t + j - 1 : t - j; }
+__device__ __forceinline__ long long chain_frame(long long t, int dir, int j) { return t + dir * j; }
+
+// the hop of (X, Y) through pair `pair` in direction dir: which flow is read and which it is checked with
+template <typename A>
+__device__ __forceinline__ bool chain_hop(const A& a, long long pair, int dir, int H, int W, double X, double Y, double& nX,
+                                          double& nY) {
+    return hop(chain_flow(a, dir), chain_check(a, dir), pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY);
+}
+
+// one hop from frame `from` to frame from + dir: step 1 of the chain from `from` (a dir known only at run time chooses
+// between the two hops, each with its flows fixed)
+template <typename A>
+__device__ __forceinline__ bool hop_from(const A& a, long long from, int dir, double X, double Y, double& nX, double& nY) {
+    return dir > 0 ? chain_hop(a, chain_pair(from, +1, 1), +1, a.H, a.W, X, Y, nX, nY)
+                   : chain_hop(a, chain_pair(from, -1, 1), -1, a.H, a.W, X, Y, nX, nY);
+}
+
+// The photometric weight of a sample against its centre (k_temporal_filter, k_sr_accumulate): D the squared differences
+// summed over the C channels, 1 / (1 + mean / s2).
+__device__ __forceinline__ double photometric_weight(double D, int C, double s2) {
+    D = D / (double)C;
+    return 1.0 / (1.0 + D / s2);
 }
 
 // stores as papof_interp_tensor states: float64 as is, float32 with one round-to-nearest, uint8 = clamp(rint(255 v), 0, 255)
@@ -225,15 +315,15 @@ template <int FD, typename D>
 __device__ __forceinline__ void interp_pixel(const InterpArgs& a, const double* lut, long long i, long long r, int x,
                                              long long j0, D done) {
     const int H = a.H, W = a.W;
-    const long long of = i * a.fw.stride[0] + r * a.fw.stride[1] + x * a.fw.stride[2];
-    const long long ob = i * a.bw.stride[0] + r * a.bw.stride[1] + x * a.bw.stride[2];
+    const long long of = PAPOF_AT(a.fw, i, r, x);
+    const long long ob = PAPOF_AT(a.bw, i, r, x);
     const double u = load_flow(a.fw, of), v = load_flow(a.fw, of + a.fw.stride[3]);
     const double bu = load_flow(a.bw, ob), bv = load_flow(a.bw, ob + a.bw.stride[3]);
     const long long base0 = i * a.f0.stride[0], base1 = (i + a.seq) * a.f1.stride[0];
     const long long baseo = i * a.occ.stride[0];
     const long long pix0 = base0 + r * a.f0.stride[1] + x * a.f0.stride[2];
     const long long pix1 = base1 + r * a.f1.stride[1] + x * a.f1.stride[2];
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     for (int j = 0; j < a.nt; j++) {
         const long long oj = outp + (j0 + j) * a.tstride;
         if (done(j, oj)) continue;

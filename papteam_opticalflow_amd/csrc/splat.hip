@@ -56,13 +56,13 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_splat(const SplatArgs 
     if (x >= a.W || r >= a.H) return;
     const int H = a.H, W = a.W, C = a.C;
     const long long i = item0 + blockIdx.y;
-    const long long of = i * a.flow.stride[0] + r * a.flow.stride[1] + x * a.flow.stride[2];
+    const long long of = PAPOF_AT(a.flow, i, r, x);
     const double u = load_flow(a.flow, of), v = load_flow(a.flow, of + a.flow.stride[3]);
     double w = 1.0;
-    if (a.weight.data) w = load_flow(a.weight, i * a.weight.stride[0] + r * a.weight.stride[1] + x * a.weight.stride[2]);
+    if (a.weight.data) w = load_flow(a.weight, PAPOF_AT(a.weight, i, r, x));
     if (!(isfinite(u) && isfinite(v) && isfinite(w)) || !(w > 0)) return;
     w = w > 1.0 ? 1.0 : w;
-    const long long pix = i * a.x.stride[0] + r * a.x.stride[1] + x * a.x.stride[2];
+    const long long pix = PAPOF_AT(a.x, i, r, x);
     const long long C1 = C + 1, HW = H * (long long)W;
     for (int j = 0; j < a.nt; j++) {
         const double X = (double)x + a.t[j] * u, Y = (double)r + a.t[j] * v;
@@ -113,13 +113,13 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_splat_resolve(const Re
     PAPOF_TILE_PIXEL(InterpTile, tile0, a.W, int, x, long long, r);
     if (x >= a.W || r >= a.H) return;
     const long long i = item0 + blockIdx.y, C1 = a.C + 1, HW = a.H * (long long)a.W;
-    const long long outp = i * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+    const long long outp = PAPOF_AT(a.out, i, r, x);
     for (int j = 0; j < a.nt; j++) {
         const long long* p = a.acc + (i * a.nt + j) * C1 * HW + r * a.W + x;
         const long long den = p[a.C * HW];
         if (a.coverage.data)
-            static_cast<double*>(a.coverage.data)[i * a.coverage.stride[0] + (j0 + j) * a.coverage.stride[1] +
-                                                  r * a.coverage.stride[2] + x * a.coverage.stride[3]] = (double)den * (1.0 / kFix);
+            static_cast<double*>(a.coverage.data)[PAPOF_AT_CH(a.coverage, i, j0 + j, r, x)] =  // (item, time, row, column)
+                (double)den * (1.0 / kFix);
         const long long oj = outp + (j0 + j) * a.tstride;
         for (int ch = 0; ch < a.C; ch++)
             store(a.out, oj + ch * a.out.stride[3], den >= kMinDen ? ((double)p[ch * HW] / (double)den) * a.bound : a.fill);
@@ -148,10 +148,10 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_interp_splat(const Int
     });
 }
 
-constexpr long long kMaxChannels = 1 << 20;  // (keeps the bytes of one time below 2^54)
+constexpr long long kMaxSplatChannels = 1 << 20;  // (keeps the bytes of one time below 2^54)
 
 long long one_time_bytes(long long n, long long h, long long w, long long c) {  // < 0: refused
-    if (n < 1 || h < 1 || w < 1 || c < 1 || c > kMaxChannels || h > (1LL << 30) || w > (1LL << 30) || h * w >= (1LL << 30))
+    if (n < 1 || h < 1 || w < 1 || c < 1 || c > kMaxSplatChannels || h > (1LL << 30) || w > (1LL << 30) || h * w >= (1LL << 30))
         return -1;
     const long long per = h * w * (c + 1) * 8;
     if (n > (1LL << 62) / per) return -1;

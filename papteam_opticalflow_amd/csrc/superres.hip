@@ -34,7 +34,6 @@ namespace papof {
 namespace {
 
 constexpr double kFix = 4294967296.0;         // 2^32: the fixed point's scale
-constexpr int kMaxC = 4;                      // channels (registers per lane)
 constexpr int kMinScale = 2, kMaxScale = 4;
 constexpr long long kBudget = 1LL << 31;      // papof_sr_workspace: as many target frames as fit 2 GiB
 constexpr int kBpX = 16, kBpY = 8;            // k_sr_backproject: the block's tile of low-resolution pixels
@@ -83,7 +82,7 @@ __device__ __forceinline__ void deposit(const SrArgs& a, long long target, doubl
 #pragma unroll
         for (int h = 0; h <= 1; h++) off[m][h] = __shfl((y0 + m) * FW + x0, 32 * h + (lane >> 1)) + sel;
 #pragma unroll
-    for (int p = 0; p <= kMaxC; p++) {  // p = 0: den's plane (the last one), then the channels
+    for (int p = 0; p <= kMaxChannels; p++) {  // p = 0: den's plane (the last one), then the channels
         if (p > a.C) break;
         unsigned long long* const q = at + (p ? p - 1 : a.C) * plane;
         long long term[4];
@@ -101,21 +100,19 @@ __device__ __forceinline__ void deposit(const SrArgs& a, long long target, doubl
     }
 }
 
-// One direction of source frame k's pixel: dir = +1 hops k + n - 1 -> k + n through f = flow_fw[k + n - 1], checked with
-// b = flow_bw[k + n - 1]; dir = -1 hops k - n + 1 -> k - n through f = flow_bw[k - n], checked with b = flow_fw[k - n].  The
-// chain stops at the first target beyond this round's [t0, t1): what it would do there belongs to another round.  The loop
-// is the WAVE's (deposit exchanges terms between the lanes): a lane whose chain is dead stays in it with weight 0, and
-// the wave leaves once none of its chains is alive.
+// One direction (dir = +-1: sampler.h, the direction rule) of source frame k's pixel.  The chain stops at the first target
+// beyond this round's [t0, t1): what it would do there belongs to another round.  The loop is the WAVE's (deposit exchanges
+// terms between the lanes): a lane whose chain is dead stays in it with weight 0, and the wave leaves once none of its
+// chains is alive.
 template <int FD>
-__device__ __forceinline__ void walk(const SrArgs& a, const papof_tensor& f, const papof_tensor& b, long long k, int dir,
-                                     int steps, bool alive, double X, double Y, const double* v, const double* val,
-                                     const double* lut) {
+__device__ __forceinline__ void walk(const SrArgs& a, long long k, int dir, int steps, bool alive, double X, double Y,
+                                     const double* v, const double* val, const double* lut) {
     const int H = a.H, W = a.W;
     for (int n = 1; n <= steps; n++) {
-        const long long pair = dir > 0 ? k + n - 1 : k - n, target = k + dir * n;
+        const long long pair = chain_pair(k, dir, n), target = chain_frame(k, dir, n);
         if (dir > 0 ? target >= a.t1 : target < a.t0) return;
         double nX, nY;
-        alive = alive && hop(f, b, pair, H, W, a.check, a.a1, a.a2, X, Y, nX, nY);  // once dead, the chain stays dead
+        alive = alive && chain_hop(a, pair, dir, H, W, X, Y, nX, nY);  // once dead, the chain stays dead
         if (__ballot(alive) == 0) return;
         X = alive ? nX : 0.0;
         Y = alive ? nY : 0.0;
@@ -126,13 +123,12 @@ __device__ __forceinline__ void walk(const SrArgs& a, const papof_tensor& f, con
             const long long base = target * a.fr.stride[0];
             double D = 0.0;
 #pragma unroll
-            for (int ch = 0; ch < kMaxC; ch++)
+            for (int ch = 0; ch < kMaxChannels; ch++)
                 if (ch < a.C) {
                     const double d = v[ch] - sample_frame<FD>(a.fr, base + ch * a.fr.stride[3], t, lut);
                     D += d * d;
                 }
-            D = D / (double)a.C;
-            w = a.weighted ? 1.0 / (1.0 + D / a.s2) : 1.0;
+            w = a.weighted ? photometric_weight(D, a.C, a.s2) : 1.0;
             w = w > 0 ? w : 0.0;  // (0 for a NaN: nothing is deposited)
         }
         deposit(a, target, X, Y, w, val);
@@ -150,19 +146,19 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_sr_accumulate(const Sr
     if (r >= a.H) return;  // (the whole wave)
     const bool valid = x < a.W;
     const long long k = frame0 + blockIdx.y;
-    const long long pix = k * a.fr.stride[0] + r * a.fr.stride[1] + x * a.fr.stride[2];
-    double v[kMaxC], val[kMaxC];
+    const long long pix = PAPOF_AT(a.fr, k, r, x);
+    double v[kMaxChannels], val[kMaxChannels];
 #pragma unroll
-    for (int ch = 0; ch < kMaxC; ch++)
+    for (int ch = 0; ch < kMaxChannels; ch++)
         if (ch < a.C) {
             v[ch] = valid ? load_frame<FD>(a.fr, pix + ch * a.fr.stride[3], lut) : 0.0;
             val[ch] = fmin(fmax(v[ch], -1.0), 1.0);  // k_splat's clamp with bound 1: no sum can overflow
         }
     const double X = valid ? (double)x : 0.0, Y = (double)r;
     if (k >= a.t0 && k < a.t1) deposit(a, k, X, Y, valid ? 1.0 : 0.0, val);
-    const int fwd = a.T - 1 - k < a.R ? (int)(a.T - 1 - k) : a.R, bwd = k < a.R ? (int)k : a.R;
-    walk<FD>(a, a.fw, a.bw, k, +1, fwd, valid, X, Y, v, val, lut);
-    walk<FD>(a, a.bw, a.fw, k, -1, bwd, valid, X, Y, v, val, lut);
+    const int fwd = chain_steps(a.T, k, +1, a.R), bwd = chain_steps(a.T, k, -1, a.R);
+    walk<FD>(a, k, +1, fwd, valid, X, Y, v, val, lut);
+    walk<FD>(a, k, -1, bwd, valid, X, Y, v, val, lut);
 }
 
 // The four weights of the cubic convolution kernel (Keys 1981, a = -0.5) for the taps at -1, 0, 1, 2 around a point at
@@ -209,8 +205,8 @@ __global__ __launch_bounds__(kInterpTX* kInterpTY) void k_sr_resolve(const SrRes
     const long long* p = a.acc + g * (a.C + 1) * plane + r * FW + x;
     const double coverage = (double)p[a.C * plane] * (1.0 / kFix);
     if (a.cov.data)
-        static_cast<double*>(a.cov.data)[t * a.cov.stride[0] + r * a.cov.stride[1] + x * a.cov.stride[2]] = coverage;
-    const long long o = t * a.out.stride[0] + r * a.out.stride[1] + x * a.out.stride[2];
+        static_cast<double*>(a.cov.data)[PAPOF_AT(a.cov, t, r, x)] = coverage;
+    const long long o = PAPOF_AT(a.out, t, r, x);
     for (int ch = 0; ch < a.C; ch++) {
         const long long base = t * a.fr.stride[0] + ch * a.fr.stride[3];
         double b = 0.0;
@@ -267,7 +263,7 @@ __global__ __launch_bounds__(256) void k_sr_backproject(const SrBackArgs a, long
                 double sum = 0.0;
                 for (int m = 0; m < S; m++)
                     for (int n = 0; n < S; n++) sum += xs[(hy * S + m) * sw + hx * S + n];
-                const double y = load_frame<FD>(a.fr, t * a.fr.stride[0] + ly * a.fr.stride[1] + lx * a.fr.stride[2] + ch * a.fr.stride[3], lut);
+                const double y = load_frame<FD>(a.fr, PAPOF_AT_CH(a.fr, t, ly, lx, ch), lut);
                 res[i] = y - sum / n2;
             }
         }
@@ -287,14 +283,14 @@ __global__ __launch_bounds__(256) void k_sr_backproject(const SrBackArgs a, long
             if (a.Xout)
                 a.Xout[(g * a.C + ch) * plane + gy * FW + gx] = X;
             else
-                store(a.out, t * a.out.stride[0] + gy * a.out.stride[1] + gx * a.out.stride[2] + ch * a.out.stride[3], X);
+                store(a.out, PAPOF_AT_CH(a.out, t, gy, gx, ch), X);
         }
     }
 }
 
 // bytes of one target frame's share of the workspace; < 0: refused
 long long per_target_bytes(long long n_frames, long long h, long long w, long long c, long long scale, long long iters) {
-    if (n_frames < 1 || h < 1 || w < 1 || c < 1 || c > kMaxC || scale < kMinScale || scale > kMaxScale || iters < 0 || iters > 65536)
+    if (n_frames < 1 || h < 1 || w < 1 || c < 1 || c > kMaxChannels || scale < kMinScale || scale > kMaxScale || iters < 0 || iters > 65536)
         return -1;
     if (h >= (1LL << 30) || w >= (1LL << 30) || h * w >= (1LL << 30)) return -1;
     return 8 * scale * scale * h * w * ((c + 1) + (iters > 0 ? 2 * c : 0));

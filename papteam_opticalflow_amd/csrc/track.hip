@@ -46,7 +46,7 @@ __device__ __forceinline__ void put(const TrackArgs& a, long long t, long long n
     double* tr = static_cast<double*>(a.tr.data) + t * a.tr.stride[0] + n * a.tr.stride[1];
     tr[0] = x;
     tr[a.tr.stride[3]] = y;
-    static_cast<unsigned char*>(a.vis.data)[t * a.vis.stride[0] + n * a.vis.stride[1]] = visible ? 1 : 0;
+    store_u8(a.vis, t * a.vis.stride[0] + n * a.vis.stride[1], visible ? 1 : 0);
 }
 
 // blockIdx.y: the direction (queries) or the tile row (dense, from tile row `first`: launches split at gridDim.y's bound);
@@ -81,6 +81,8 @@ __global__ __launch_bounds__(256) void k_track(const TrackArgs a, long long firs
     }
     if (!alive) x = y = qnan;
     if (dir == 0) put(a, s, n, x, y, alive);  // frame t0, written once
+    // sampler.h's direction rule, kept as written: the direction is known only at run time, and the flows are selected
+    // once, outside the loop (kernels that deviate)
     const papof_tensor& f = dir ? a.bw : a.fw;  // (dir is uniform over the block)
     const papof_tensor& b = dir ? a.fw : a.bw;
     const int steps = dir ? s : a.T - 1 - s;

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kDX* kDY) void k_decimate(const DecimateArgs a, lon
     const int f = a.f, Y0 = y * f, X0 = x * f;
     const int ny = min(f, a.H - Y0), nx = min(f, a.W - X0);
     const double count = (double)(ny * nx);
-    const long long oi = i * a.in.stride[0], oo = i * a.out.stride[0] + (long long)y * a.out.stride[1] + (long long)x * a.out.stride[2];
+    const long long oi = i * a.in.stride[0], oo = PAPOF_AT(a.out, i, (long long)y, (long long)x);
     for (int ch = 0; ch < a.C; ch++) {
         double s = 0.0;
         for (int j = 0; j < ny; j++)
@@ -113,18 +113,17 @@ __global__ __launch_bounds__(kTX* kTY) void k_upsample_flow(const UpsampleArgs a
         double u = 0.0, v = 0.0;
         bool d = !in;
         if (in) {
-            const long long o = i * a.flow.stride[0] + (long long)gy * a.flow.stride[1] + (long long)gx * a.flow.stride[2];
+            const long long o = PAPOF_AT(a.flow, i, (long long)gy, (long long)gx);
             u = load_flow(a.flow, o);
             v = load_flow(a.flow, o + a.flow.stride[3]);
             d = !(isfinite(u) && isfinite(v));
             if (a.occ.data)
-                d = d || static_cast<const unsigned char*>(a.occ.data)[i * a.occ.stride[0] + (long long)gy * a.occ.stride[1] +
-                                                                       (long long)gx * a.occ.stride[2]] != 0;
+                d = d || load_u8(a.occ, PAPOF_AT(a.occ, i, (long long)gy, (long long)gx)) != 0;
         }
         U[c] = u;
         V[c] = v;
         dead[c] = d ? 1 : 0;
-        const long long og = i * a.guide_lr.stride[0] + (long long)gy * a.guide_lr.stride[1] + (long long)gx * a.guide_lr.stride[2];
+        const long long og = PAPOF_AT(a.guide_lr, i, (long long)gy, (long long)gx);
         for (int ch = 0; ch < C; ch++) G[c * C + ch] = in ? load_flow(a.guide_lr, og + ch * a.guide_lr.stride[3]) : 0.0;
     }
     for (int k = tid; k < kBins; k += kTX * kTY) Rt[k] = a.R[k];
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_upsample_flow(const UpsampleArgs a
     const int cc = (cyc - oy) * PW + cxc - ox;  // the centre cell: r cells from the window's borders at least
     const unsigned* const Sp = St + ((Y - cyc * f) * f + (X - cxc * f)) * taps;
     double gc[4] = {0.0, 0.0, 0.0, 0.0};
-    const long long og = i * a.guide.stride[0] + (long long)Y * a.guide.stride[1] + (long long)X * a.guide.stride[2];
+    const long long og = PAPOF_AT(a.guide, i, (long long)Y, (long long)X);
     for (int ch = 0; ch < 4; ch++)
         if (ch < C) gc[ch] = load_frame<GD>(a.guide, og + ch * a.guide.stride[3], lut);
     const double q = a.q;
@@ -174,7 +173,7 @@ __global__ __launch_bounds__(kTX* kTY) void k_upsample_flow(const UpsampleArgs a
         ou = su / den * fd;
         ov = sv / den * fd;
     }
-    const long long oo = i * a.out.stride[0] + (long long)Y * a.out.stride[1] + (long long)X * a.out.stride[2];
+    const long long oo = PAPOF_AT(a.out, i, (long long)Y, (long long)X);
     store(a.out, oo, ou);
     store(a.out, oo + a.out.stride[3], ov);
 }

@@ -1,12 +1,11 @@
 """The deblurring rule of include/papof.h (papof_deblur_tensor) restated in numpy fp64, in the header's order of operations
 -- the rule that tests/test_deblur_cpu.py checks with known answers and quality bars and tests/test_gpu_deblur.py compares
-the device's output with, byte for byte.  The taps are _interp_ref's (_taps), the frame sampler _denoise_ref's (_sample),
+the device's output with, byte for byte.  The taps are _interp_ref's (_taps), the frame sampler _interp_ref's (sample_plane),
 the flow sampler and the hop test_track_cpu's (_bilinear, _step: k_track's step).  numpy does not contract a * b + c and
 divides with correct rounding: the bits are the kernel's."""
 import numpy as np
 
-from _denoise_ref import _sample
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 from test_track_cpu import _bilinear, _step
 
 EPS = 2.0 ** -10
@@ -69,7 +68,7 @@ def _line(img, X, Y, vx, vy, table, sign, use):
         taps = _taps(Xs, Ys, H, W)
         with np.errstate(invalid="ignore", over="ignore"):
             for ch in range(C):
-                acc[:, ch] = acc[:, ch] + w * _sample(img[..., ch], taps)
+                acc[:, ch] = acc[:, ch] + w * sample_plane(img[..., ch], taps)
     return acc, clamped
 
 

@@ -4,7 +4,7 @@ tests/test_gpu_deinterlace.py compares the device's video and confidence with, b
 stores are _interp_ref's.  numpy does not contract a * b + c and divides with correct rounding: the bits are the kernel's."""
 import numpy as np
 
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 
 
 def split_reference(frames, top_first=True):
@@ -24,15 +24,6 @@ def fields_of(video, first=0):
     """field k of a progressive video (T, H, W, C): the rows of parity (k + first) & 1 of frame k"""
     video = np.asarray(video)
     return np.stack([video[k, (k + first) & 1::2] for k in range(len(video))])
-
-
-def _sample(field, taps):
-    """field (Hf, W) sampled at the taps, accumulated from 0 in (m, n) order"""
-    g = np.zeros(taps[0][0].shape)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for rows, cols, w in taps:
-            g = g + field[rows, cols] * w
-    return g
 
 
 def _phase(inside, Y):
@@ -96,9 +87,9 @@ def deinterlace_reference(fields, flow_fw=None, flow_bw=None, first=0, mode=1, s
             g0 = np.zeros((Hf, W, C))
             g1 = np.zeros((Hf, W, C))
             if t >= 1:
-                g0 = np.stack([np.where(use0, _sample(F[t - 1][..., k], k0), 0.0) for k in range(C)], -1)
+                g0 = np.stack([np.where(use0, sample_plane(F[t - 1][..., k], k0), 0.0) for k in range(C)], -1)
             if t <= T - 2:
-                g1 = np.stack([np.where(use1, _sample(F[t + 1][..., k], k1), 0.0) for k in range(C)], -1)
+                g1 = np.stack([np.where(use1, sample_plane(F[t + 1][..., k], k1), 0.0) for k in range(C)], -1)
             with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
                 D = np.zeros((Hf, W))
                 for k in range(C):

@@ -4,17 +4,8 @@ for byte.  The hop is test_track_cpu's (_step: k_track's step), the frame sample
 contract a * b + c and divides with correct rounding: the bits are the kernel's."""
 import numpy as np
 
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 from test_track_cpu import _step
-
-
-def _sample(img, taps):
-    """img (H, W) sampled at the taps, accumulated from 0 in (m, n) order"""
-    g = np.zeros(taps[0][0].shape)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for rows, cols, w in taps:
-            g = g + img[rows, cols] * w
-    return g
 
 
 def denoise_reference(frames, flow_fw, flow_bw, radius, sigma=None, consistency=(0.01, 0.5), out_dtype=np.float64):
@@ -43,7 +34,7 @@ def denoise_reference(frames, flow_fw, flow_bw, radius, sigma=None, consistency=
                 f, b = (fw[pair], bw[pair]) if d > 0 else (bw[pair], fw[pair])
                 X, Y, alive = _step(f, b, X, Y, alive, check, a1, a2)
                 taps = _taps(np.where(alive, X, 0.0), np.where(alive, Y, 0.0), H, W)
-                g = [_sample(F[t + d * j][..., k], taps) for k in range(C)]
+                g = [sample_plane(F[t + d * j][..., k], taps) for k in range(C)]
                 with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
                     D = np.zeros(H * W)
                     for k in range(C):

@@ -5,7 +5,7 @@ step), the bilinear taps _interp_ref's (_taps).  numpy does not contract a * b +
 bits are the kernels'."""
 import numpy as np
 
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 from test_track_cpu import _step
 
 
@@ -84,15 +84,6 @@ def fill_reference(x, mask, relax, out_dtype=np.float64):
     return convert(np.where(K[..., None], V, it), out_dtype)
 
 
-def _sample(img, taps):
-    """img (H, W) sampled at the taps, accumulated from 0 in (m, n) order"""
-    g = np.zeros(taps[0][0].shape)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for rows, cols, w in taps:
-            g = g + img[rows, cols] * w
-    return g
-
-
 def propagate_reference(frames, masks, flow_fw, flow_bw, radius, consistency=(0.01, 0.5), out_dtype=np.float64):
     """frames (T, H, W, C) uint8 / float32 / float64, masks (T, H, W) (nonzero: a hole), flow_fw, flow_bw (T - 1, 2, H, W)
     (vx, vy), radius 1 .. T - 1, consistency (alpha1, alpha2) or None: no check -> (out (T, H, W, C) of out_dtype, status
@@ -124,7 +115,7 @@ def propagate_reference(frames, masks, flow_fw, flow_bw, radius, consistency=(0.
                 for rows, cols, _ in taps:
                     clear &= ~M[t + d * j][rows, cols]
                 for k in range(C):
-                    g[:, k] = np.where(clear, _sample(F[t + d * j][..., k], taps), g[:, k])
+                    g[:, k] = np.where(clear, sample_plane(F[t + d * j][..., k], taps), g[:, k])
                 dist = np.where(clear, j, dist)
                 active = active & ~clear  # the chain stops where it found its candidate
             cand.append((g, dist))

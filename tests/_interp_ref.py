@@ -41,6 +41,15 @@ def _taps(X, Y, H, W):
     return out
 
 
+def sample_plane(img, taps):
+    """one plane img (H, W) sampled at the taps, accumulated from 0 in (m, n) order (the video references' sampler)"""
+    g = np.zeros(taps[0][0].shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for rows, cols, w in taps:
+            g = g + img[rows, cols] * w
+    return g
+
+
 def _sample(img, pb, taps):
     """img (B, H, W) sampled at the taps, accumulated from 0 in (m, n) order"""
     g = np.zeros(taps[0][0].shape)

@@ -5,8 +5,8 @@ for byte.  The hop is test_track_cpu's (_step: k_track's step), the bilinear tap
 propagation _inpaint_ref's.  numpy does not contract a * b + c: the bits are the kernel's."""
 import numpy as np
 
-from _inpaint_ref import _sample, fill_reference, propagate_reference
-from _interp_ref import _taps, as_f64
+from _inpaint_ref import fill_reference, propagate_reference
+from _interp_ref import _taps, as_f64, sample_plane
 from test_track_cpu import _step
 
 
@@ -50,7 +50,7 @@ def detect_reference(frames, flow_fw, flow_bw, threshold, consistency=None, scor
         s = np.zeros(H * W)
         with np.errstate(invalid="ignore", over="ignore"):
             for k in range(C):
-                g1, g2 = _sample(F[t + o1][..., k], t1), _sample(F[t + o2][..., k], t2)
+                g1, g2 = sample_plane(F[t + o1][..., k], t1), sample_plane(F[t + o2][..., k], t2)
                 lo, hi = np.where(g2 < g1, g2, g1), np.where(g2 > g1, g2, g1)
                 a, b = c[:, k] - hi, lo - c[:, k]
                 d = np.where(b > a, b, a)

@@ -4,7 +4,7 @@ tests/test_gpu_rolling.py compares the device's output with, byte for byte.  The
 _interp_ref's.  numpy does not contract a * b + c and divides with correct rounding: the bits are the kernel's."""
 import numpy as np
 
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 
 BRANCHES = ("s_zero", "tf_fails", "tb_fails", "left", "first", "last", "interior")
 
@@ -12,15 +12,6 @@ BRANCHES = ("s_zero", "tf_fails", "tb_fails", "left", "first", "last", "interior
 def _inside(X, Y, H, W):
     with np.errstate(invalid="ignore"):
         return (X >= 0) & (X <= W - 1) & (Y >= 0) & (Y <= H - 1)
-
-
-def _sample(field, taps):
-    """field (H, W) sampled at the taps, accumulated from 0 in (m, n) order"""
-    g = np.zeros(taps[0][0].shape)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for rows, cols, w in taps:
-            g = g + field[rows, cols] * w
-    return g
 
 
 class _Rule:
@@ -42,8 +33,8 @@ class _Rule:
         zero = s == 0
         k = _taps(X, Y, H, W)
         z = np.zeros(X.shape)
-        Fu, Fv = (_sample(self.fw[t, 0], k), _sample(self.fw[t, 1], k)) if t < self.T - 1 else (z, z)
-        Bu, Bv = (_sample(self.bw[t - 1, 0], k), _sample(self.bw[t - 1, 1], k)) if t > 0 else (z, z)
+        Fu, Fv = (sample_plane(self.fw[t, 0], k), sample_plane(self.fw[t, 1], k)) if t < self.T - 1 else (z, z)
+        Bu, Bv = (sample_plane(self.bw[t - 1, 0], k), sample_plane(self.bw[t - 1, 1], k)) if t > 0 else (z, z)
         with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
             tf, tb = 1.0 + r * Fv, r * Bv - 1.0
             okf, okb = tf >= 0.5, tb <= -0.5
@@ -106,7 +97,7 @@ def rectify_reference(frames, flow_fw, flow_bw, readout, anchor=0.5, iters=3, ma
         Px, Py, alive = g.solve(t, Qx, Qy)
         k = _taps(np.where(alive, Px, 0.0), np.where(alive, Py, 0.0), H, W)
         for ch in range(C):
-            out[t, :, :, ch] = np.where(alive, _sample(I[t, :, :, ch], k), 0.0)
+            out[t, :, :, ch] = np.where(alive, sample_plane(I[t, :, :, ch], k), 0.0)
         valid[t] = alive
         P[t, ..., 0], P[t, ..., 1] = np.where(alive, Px, np.nan), np.where(alive, Py, np.nan)
     res = (convert(out, frames.dtype if out_dtype is None else out_dtype), valid)
@@ -126,7 +117,7 @@ def flows_reference(flow_fw, flow_bw, readout, anchor=0.5, iters=3, out_dtype=np
             t, t2 = (i + 1, i) if back else (i, i + 1)
             Px, Py, alive = g.solve(t, x, r)
             k = _taps(np.where(alive, Px, 0.0), np.where(alive, Py, 0.0), H, W)
-            Fu, Fv = _sample(f[i, 0], k), _sample(f[i, 1], k)
+            Fu, Fv = sample_plane(f[i, 0], k), sample_plane(f[i, 1], k)
             with np.errstate(invalid="ignore", over="ignore"):
                 X2, Y2 = Px + Fu, Py + Fv
             alive = alive & _inside(X2, Y2, H, W)

@@ -5,8 +5,7 @@ the fine grid: every term is one product of doubles (numpy does not contract a *
 int64 (np.add.at), so the bits are the kernel's whatever order its atomic adds arrive in."""
 import numpy as np
 
-from _denoise_ref import _sample
-from _interp_ref import _taps, as_f64, convert
+from _interp_ref import _taps, as_f64, convert, sample_plane
 from test_track_cpu import _step
 
 FIX = 4294967296.0  # 2^32
@@ -57,7 +56,7 @@ def accumulate(F, fw, bw, S, radius, sigma=None, consistency=None):
                 with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
                     D = np.zeros(H * W)
                     for c in range(C):
-                        dc = v[:, c] - _sample(F[k + d * j][..., c], taps)
+                        dc = v[:, c] - sample_plane(F[k + d * j][..., c], taps)
                         D = D + dc * dc
                     D = D / C
                     w = 1.0 / (1.0 + D / s2) if weighted else np.ones(H * W)
